@@ -14,8 +14,14 @@ Workload (config.workload): the BASELINE.json configs[2]/[3] problem — random-
 multi-hypothesis trajectories of 16 MINCO pieces x 32 pts/piece (33 samples), 50 static
 obstacles, every trajectory with its own H=4 rectangle corridor — at 4096 trajectories per GPU
 (weak scaling: per-GPU batch fixed; the solver is latency-bound per trajectory, so throughput is
-quoted on a batch that fills the chip).  At N=1 the line also carries the exact configs[2] case
-(batch 256) and the configs[1] case (one gear-shift trajectory) under "batch256" / "single".
+quoted on a batch that fills the chip).
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the line; nothing else.
+--full adds every other measurement and check: at N=1 the exact configs[2] case (batch 256) and the configs[1] case (one gear-shift
+trajectory) under "batch256" / "single", the other configurations, the strong-scaling shard, the live hardware counters, the CPU
+baseline and the parity legs; at N>1 the other scaling mode.  --dump-outputs DIR writes what the timed path returned for the batch
+of its last step as DIR/<name>.npy (float64), for comparing two builds output for output: with the same arguments the inputs
+are the same on every run.
 """
 import argparse
 import json
@@ -28,6 +34,9 @@ import time
 os.environ.setdefault("OMP_PROC_BIND", "close")
 os.environ.setdefault("OMP_PLACES", "cores")
 os.environ.setdefault("OMP_WAIT_POLICY", "passive")
+# the CPUs this process may use, read before libgomp binds the main thread to one core (OMP_PROC_BIND above): main_shards spreads
+# its worker processes over them
+HOST_CPUS = os.sched_getaffinity(0) if hasattr(os, "sched_getaffinity") else None
 # The HIP runtime multiplexes a process's streams onto 4 hardware queues by default: the fifth batch in flight waits for one of
 # the first four to END, however empty the device is.  The side runs that keep 8..16 small batches in flight (a 512-trajectory
 # shard of a strong-scaled 4096, 8 planner threads of 256) want as many queues as streams: 19 k -> 33 k solves/s on 512-
@@ -46,7 +55,7 @@ from dftpav_amd import capi, distributed as dd, scenarios as sc  # noqa: E402
 # side_runs() call them through this module (tests/bench_standin_main.py replaces some of them by name)
 from benchlib.common import (HBM_PEAK_GBS, DEV, SOLVE_FIELDS, Ctx, algorithmic_bytes, effective_cores, same_solve, same_as_ref_run,  # noqa: E402,F401
                              bit_check)
-from benchlib.stream import Stream, shard_schedule  # noqa: E402,F401
+from benchlib.stream import Stream, shard_schedule, stream_depth, make_shards  # noqa: E402,F401
 from benchlib.counters import live_pmc, hbm_traffic  # noqa: E402,F401
 from benchlib.side import (side_isolated, side_batch, side_single, side_reference_order_batch, side_reference_order_other_configs,  # noqa: E402,F401
                            side_neighbours, side_device_order)
@@ -58,7 +67,7 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     # (defaults = the driver's settings: a run of 5 steps ends with one batch's tail in five and reads 15-20 % lower; the timed region of 20
-    # steps is 2.3 s of a run that takes minutes for its side measurements)
+    # steps is 2.3 s of a --full run that takes minutes for its side measurements)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch-per-gpu", type=int, default=4096)
@@ -70,9 +79,14 @@ def parse_args(argv=None):
                     help="floating-point order of the value line: reference (bit-equal to the CPU restatement of the reference; default) or "
                          "device (reassociated sums; statistically equal only)")
     ap.add_argument("--cpu-sample", type=int, default=-1,
-                    help="trajectories timed on the host cores (-1 = 4 per core, 0 = skip)")
+                    help="with --full: trajectories timed on the host cores (-1 = 4 per core, 0 = skip)")
     ap.add_argument("--seed", type=int, default=20240)
-    ap.add_argument("--no-extras", action="store_true", help="skip the batch-256 / single-trajectory side runs (profiling)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the value line, every side run, the hardware counters, the CPU baseline and the parity legs (N=1) / "
+                         "the other scaling mode (N>1); a plain run does only what the value line needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the timed path's last step (this rank's shard) to DIR/<name>.npy, float64")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the batch-256 / single-trajectory side runs (profiling)")
     ap.add_argument("--schedule", choices=["overlap", "chain", "plain"], default="overlap",
                     help="overlap: --depth batches resident, each on its own HIP stream, every trajectory stays in its queue launch, the next "
                          "launches fill the slots an earlier one frees (default); chain: one stream, the stragglers of a batch are "
@@ -80,8 +94,8 @@ def parse_args(argv=None):
     ap.add_argument("--no-chain", action="store_true", help="same as --schedule plain")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak: --batch-per-gpu trajectories on every GPU (the value line); strong: --batch-per-gpu trajectories in all, "
-                         "sharded over the GPUs (BASELINE configs[3]: 4096 over 8 = 512 per GPU).  At N > 1 the other mode is timed as "
-                         "well and reported beside the value line")
+                         "sharded over the GPUs (BASELINE configs[3]: 4096 over 8 = 512 per GPU).  With --full at N > 1 the other mode is "
+                         "timed as well and reported beside the value line")
     return ap.parse_args(argv)
 
 
@@ -282,16 +296,57 @@ def other_scaling(ctx, args, out):
     wd.cancel()
 
 
+def global_batch(args, world):
+    """the value line: weak = --batch-per-gpu on every GPU, strong = --batch-per-gpu in all (BASELINE configs[3] as written)"""
+    return args.batch_per_gpu * world if args.scaling == "weak" else args.batch_per_gpu
+
+
+def main_shards(args):
+    """the value line's resident batches on this rank, made BEFORE init_job initialises the GPU: several batches of 4096
+    trajectories are tens of seconds of numpy on one core, so they are made side by side in forked processes, on the CPUs the
+    process had before libgomp bound it to one (HOST_CPUS)"""
+    rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
+    schedule = "plain" if args.no_chain else args.schedule
+    B_total = global_batch(args, world)
+    d_main, _ = shard_schedule(args, schedule, B_total // world)
+    return make_shards(B_total, args.config, args.seed, rank, world, stream_depth(schedule, d_main),
+                       workers=effective_cores(HOST_CPUS)["effective"], cpus=HOST_CPUS)
+
+
+DUMP_FIELDS = ("x", "final_cost", "status", "success", "iters", "evals", "hist_sum")
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, res):
+    """--dump-outputs: what a caller of the timed path receives for the batch of the last timed step (this rank's shard), every
+    array as float64; a shard too large for DUMP_LIMIT_BYTES is written for a fixed, seeded sample of its trajectories (rows.npy)"""
+    r = res["rs"][res["last"]]
+    B = len(r["final_cost"])
+    row_bytes = 8 * sum(int(np.prod(r[k].shape[1:])) for k in DUMP_FIELDS)
+    rows = None
+    if B * row_bytes > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(12345).choice(B, (DUMP_LIMIT_BYTES - 8 * 4096) // (row_bytes + 8), replace=False))
+    os.makedirs(d, exist_ok=True)
+    for k in DUMP_FIELDS:
+        a = r[k] if rows is None else r[k][rows]
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    if rows is not None:
+        np.save(os.path.join(d, "rows.npy"), rows.astype(np.float64))
+
+
 def main(argv=None):
     args = parse_args(argv)
+    shards = main_shards(args)
     ctx = init_job(args)
     world = ctx.world
-    # the value line: weak = --batch-per-gpu on every GPU, strong = --batch-per-gpu in all (BASELINE configs[3] as written)
-    B_total = args.batch_per_gpu * world if args.scaling == "weak" else args.batch_per_gpu
+    B_total = global_batch(args, world)
     d_main, r_main = shard_schedule(args, ctx.schedule, B_total // world)
-    st = Stream(ctx, B_total, args.config, args.seed, depth=d_main, residency=r_main, order=ctx.order)
+    st = Stream(ctx, B_total, args.config, args.seed, depth=d_main, residency=r_main, order=ctx.order, shards=shards)
     res = st.run(args.steps, args.warmup)
-    side = world == 1 and not args.no_extras
+    if args.dump_outputs and ctx.rank == 0:
+        dump_outputs(args.dump_outputs, res)
+    # everything below the value line is --full's
+    side = args.full and world == 1 and not args.no_extras
     strong_shard = run_strong_shard(ctx, args) if side and args.scaling == "weak" else None
     out = None
     if ctx.rank == 0:
@@ -301,9 +356,9 @@ def main(argv=None):
         cpu = effective_cores()
         if side:
             guarded(out, "extras", side_runs, ctx, args, st, out, cpu["effective"], B_total, res["rs"][0])
-        if world == 1 and args.cpu_sample != 0:
+        if args.full and world == 1 and args.cpu_sample != 0:
             guarded(out, "cpu_baseline_and_parity", cpu_baseline_and_parity, ctx, args, st, res["rs"][0], out, cpu, B_total)
-    if world > 1 or (ctx.distributed and os.environ.get("DFTPAV_BENCH_FORCE_OTHER") == "1"):  # (forced: the one-GPU test of this code)
+    if args.full and (world > 1 or (ctx.distributed and os.environ.get("DFTPAV_BENCH_FORCE_OTHER") == "1")):  # (forced: the one-GPU test of this code)
         other_scaling(ctx, args, out)
     if ctx.rank == 0:
         (out.get("device_order") or {}).pop("_results", None)

@@ -20,9 +20,12 @@ def algorithmic_bytes(lay, npts, H, M, iters, evals, hist_sum, w=8):
     return evals.astype(np.float64) * e_eval + (4.0 * hist_sum * n + 14.0 * n * iters) * w
 
 
-def effective_cores():
-    """host cores this process may actually use: the affinity mask, capped by the cgroup CPU quota"""
-    n_aff = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+def effective_cores(cpus=None):
+    """host cores this process may actually use: the affinity mask (or the set `cpus`), capped by the cgroup CPU quota"""
+    if cpus:
+        n_aff = len(cpus)
+    else:
+        n_aff = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
     quota = None
     for path in ("/sys/fs/cgroup/cpu.max", "/sys/fs/cgroup/cpu/cpu.cfs_quota_us"):
         try:

@@ -66,7 +66,7 @@ def live_pmc(args, schedule):
 
 def hbm_traffic(ctx, args, shard_B):
     """HBM bytes per launch and VALU instructions per solve of the dominant kernel: the counters of THIS tree on THIS box
-    (live_pmc) when the line carries its side runs at N = 1, else the last collection committed (profiles/pmc_latest.json).
+    (live_pmc) when a --full line carries its side runs at N = 1, else the last collection committed (profiles/pmc_latest.json).
     -> (traffic, traffic_uncorrected, traffic_source, valu_per_solve)"""
     traffic, traffic_source, valu_per_solve, traffic_raw = None, None, None, None
     pmc = os.path.join(ROOT, "profiles", "pmc_latest.json")
@@ -81,7 +81,7 @@ def hbm_traffic(ctx, args, shard_B):
                 pj.get("command", "bench.py --steps 3 --no-extras"), pj.get("collected", "round 1"))
         except Exception:
             traffic = None
-    if ctx.world == 1 and not args.no_extras and os.environ.get("DFTPAV_BENCH_PMC", "1") != "0":
+    if ctx.world == 1 and getattr(args, "full", False) and not args.no_extras and os.environ.get("DFTPAV_BENCH_PMC", "1") != "0":
         try:
             lp, note = live_pmc(args, ctx.schedule)
         except Exception as ex:  # noqa: BLE001

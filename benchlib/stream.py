@@ -24,17 +24,19 @@ class Stream:
         (dftpav_batch_solve_chained), the last batch is flushed in the latency shape.
       plain: isolated solves, a step waits for its own batch."""
 
-    def __init__(self, ctx, B_total, config, seed, depth=2, residency=None, order=None):
+    def __init__(self, ctx, B_total, config, seed, depth=2, residency=None, order=None, shards=None):
         self.c = ctx
         # every rank generates its own shard from (seed, rank) — trajectories are independent, nothing is scattered
         # (SURVEY §8e); rank r owns global trajectories [r*B/G, (r+1)*B/G)
         # depth: resident batches = steps in flight (overlap schedule only; --depth for the value line).  A shard too small to
         # fill the device alone (512 of a strong-scaled 4096) is run deeper, in the throughput residency, so that a GPU
         # holds as many trajectories as it does at 4096 per step.
-        self.D = D = depth if self.c.schedule == "overlap" else 2
+        self.D = D = stream_depth(ctx.schedule, depth)
         self.B_total = B_total
         self.lo, self.hi = dd.shard_range(B_total, self.c.rank, self.c.world)
-        self.shards = [sc.baseline_config(config, B=self.hi - self.lo, seed=seed + 7919 * self.c.rank + 104729 * i) for i in range(D)]
+        # shards: the same scenarios made beforehand by make_shards (bench.py makes the value line's before the GPU is initialised)
+        self.shards = shards if shards is not None else make_shards(B_total, config, seed, self.c.rank, self.c.world, D)
+        assert len(self.shards) == D and all(sh.B == self.hi - self.lo for sh in self.shards)
         for sh in self.shards:
             sh.apply_resolution(self.c.params)
         self.shard = self.shards[0]
@@ -170,7 +172,7 @@ class Stream:
         rs = [b_.results() if i_ < self.k else None for i_, b_ in enumerate(self.bts)]
         cost_all, status_all, iters_all = dd.unpack_records(allrec if isinstance(allrec, np.ndarray) else allrec.cpu().numpy())
         assert len(cost_all) == self.B_total and np.array_equal(cost_all[self.lo:self.hi], rs[last]["final_cost"])
-        return dict(elapsed=elapsed, gpu_ms=gpu_ms, rs=rs, steps=steps, value=self.B_total * steps / elapsed,
+        return dict(elapsed=elapsed, gpu_ms=gpu_ms, rs=rs, last=last, steps=steps, value=self.B_total * steps / elapsed,
                     ms_per_step=1e3 * elapsed / steps, to_result_ms=1e3 * float(np.mean(self.to_result)),
                     deliver_ms=1e3 * float(np.mean(self.in_deliver)), wait_for_solve_ms=1e3 * float(np.mean(self.wait_solve)))
 
@@ -182,6 +184,35 @@ class Stream:
             b_.close()
         for hh in set(self.hs):
             hh.close()
+
+
+def stream_depth(schedule, depth):
+    """resident batches of a Stream: --depth in the overlap schedule, two in the others"""
+    return depth if schedule == "overlap" else 2
+
+
+def _make_shard(config, B, seed):
+    return sc.baseline_config(config, B=B, seed=seed)
+
+
+def _spread(cpus):
+    if cpus:
+        os.sched_setaffinity(0, cpus)
+
+
+def make_shards(B_total, config, seed, rank, world, D, workers=1, cpus=None):
+    """The scenarios of a Stream's D resident batches on this rank: shard i from seed + 7919 rank + 104729 i.  A scenario of
+    thousands of trajectories is seconds of numpy on one core (the corridors), so with workers > 1 the batches of a large shard are
+    made side by side in forked processes, each allowed onto `cpus` (the forked children would otherwise share the core the parent
+    is bound to) -- call it so only before this process has initialised the GPU.  The arrays do not depend on where they were made."""
+    lo, hi = dd.shard_range(B_total, rank, world)
+    jobs = [(config, hi - lo, seed + 7919 * rank + 104729 * i) for i in range(D)]
+    workers = min(workers, D)
+    if workers > 1 and hi - lo >= 256:
+        import multiprocessing
+        with multiprocessing.get_context("fork").Pool(workers, initializer=_spread, initargs=(cpus,)) as pool:
+            return pool.starmap(_make_shard, jobs)
+    return [_make_shard(*j) for j in jobs]
 
 
 def shard_schedule(args, schedule, per_gpu):

@@ -21,4 +21,4 @@ cd $R
 # reference order: the WAVE shape at 4096 (one wave per trajectory, ring), the TEAM shape at 32, kernel times over the batch sizes
 { ORDER=ref timeout 600 python scripts/profile_phases.py 3 4096; ORDER=ref timeout 600 python scripts/profile_phases.py 3 32; ORDER=ref timeout 600 python scripts/profile_phases.py 1 32; timeout 600 python scripts/ref_order_time.py 3 1 32 256 1024 2048 4096; } > $O/ref_phases_$tag.txt 2>&1
 { timeout 600 python scripts/profile_phases.py 3 4096; timeout 600 python scripts/profile_phases.py 3 256; timeout 600 python scripts/cfg5_time.py; } > $O/phases_$tag.txt 2>&1
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_line_$tag.json 2> $O/bench_line_$tag.err; echo "bench rc=$?"
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_line_$tag.json 2> $O/bench_line_$tag.err; echo "bench rc=$?"

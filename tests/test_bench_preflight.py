@@ -11,6 +11,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -68,10 +69,45 @@ def test_one_rank_line_and_step_count():
     assert "other_scaling" not in out and "cpu_baseline" not in out
 
 
+def test_a_plain_run_is_the_value_line_alone():
+    """without --full the run sets up, warms up, times its steps and prints the line: no side run, no counter pass, no CPU
+    baseline, no parity leg at N = 1, no other scaling mode at N > 1"""
+    out = _bench(["--steps", "3", "--warmup", "2", "--batch-per-gpu", "6"])
+    assert out["steps"] == 3 and out["warmup"] == 2
+    assert _count(out, "solve") == 5                                           # warm-up + timed steps, nothing else
+    for k in ("strong_shard", "isolated", "device_order", "batch256", "single", "moving_obstacles_1024", "cpu_baseline", "parity",
+              "with_upload", "other_scaling", "side_run_errors"):
+        assert k not in out, k
+    assert not (out["roofline"]["traffic_source"] or "").startswith("live")    # the committed collection, not a counter run of its own
+    out = _bench(["--steps", "2", "--warmup", "1", "--batch-per-gpu", "4"], nproc=2)
+    assert "other_scaling" not in out and _count(out, "solve", 4) == 3 and _count(out, "allgather", 8) == 3
+
+
+def test_dump_outputs_is_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: the results of the batch the last timed step launched, float64, the same on every run with the same
+    arguments.  Four batches in flight, 1 warm-up + 3 timed steps: the last step launched batch 3 of the stream"""
+    from dftpav_amd import capi, scenarios as sc
+    from oracle import pyoracle as po
+    flags = ["--steps", "3", "--warmup", "1", "--batch-per-gpu", "6", "--seed", "11"]
+    _bench(flags + ["--dump-outputs", str(tmp_path / "a")])
+    _bench(flags + ["--dump-outputs", str(tmp_path / "b")])
+    s = sc.baseline_config(3, B=6, seed=11 + 104729 * 3)
+    p = capi.default_params()
+    s.apply_resolution(p)
+    ro = po.solve_batch(p, s, nthreads=1, order=2)       # what the stand-in computes for a batch in the reference order
+    names = ("x", "final_cost", "status", "success", "iters", "evals", "hist_sum")
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(n + ".npy" for n in names)
+    for n in names:
+        a, b = np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, b), n
+        assert np.array_equal(a, ro[n].astype(np.float64)), n
+    assert np.load(tmp_path / "a" / "x.npy").shape == (6, s.layout.n_vars)
+
+
 @pytest.mark.parametrize("nproc", [2, 4])
 def test_ranks_weak_value_line_and_the_strong_side_run(nproc):
     B = 8
-    out = _bench(["--steps", "3", "--warmup", "1", "--batch-per-gpu", str(B), "--depth", "2", "--no-extras", "--cpu-sample", "0"], nproc=nproc)
+    out = _bench(["--full", "--steps", "3", "--warmup", "1", "--batch-per-gpu", str(B), "--depth", "2", "--no-extras", "--cpu-sample", "0"], nproc=nproc)
     assert out["n_gpus"] == nproc and out["scaling"] == "weak" and out["config"]["global_batch"] == nproc * B
     assert out["config"]["steps_in_flight"] == 2
     assert "dftpav_batch_allgather_results" in out["config"]["allgather_via"]
@@ -86,7 +122,7 @@ def test_ranks_weak_value_line_and_the_strong_side_run(nproc):
 
 
 def test_two_ranks_strong_with_shards_of_unequal_size():
-    out = _bench(["--steps", "2", "--warmup", "1", "--batch-per-gpu", "9", "--scaling", "strong", "--no-extras", "--cpu-sample", "0"], nproc=2)
+    out = _bench(["--full", "--steps", "2", "--warmup", "1", "--batch-per-gpu", "9", "--scaling", "strong", "--no-extras", "--cpu-sample", "0"], nproc=2)
     assert out["scaling"] == "strong" and out["config"]["global_batch"] == 9      # rank 0 owns 4, rank 1 owns 5
     assert _count(out, "solve", 4) >= 3 and _count(out, "allgather", 9) >= 3
     assert out["other_scaling"]["scaling"] == "weak" and out["other_scaling"]["global_batch"] == 18 and out["other_scaling"]["per_gpu"] == 9
@@ -95,7 +131,7 @@ def test_two_ranks_strong_with_shards_of_unequal_size():
 def test_a_rank_without_communicator_moves_every_rank_to_the_torch_path():
     """dftpav_comm_create fails on rank 1 only: dd.RcclComm (the real one) must raise on BOTH ranks, bench.py then takes
     torch.distributed's all_gather_into_tensor on both -- a rank left on the other path would hang the job"""
-    out = _bench(["--steps", "2", "--warmup", "1", "--batch-per-gpu", "4", "--no-extras", "--cpu-sample", "0"], nproc=2,
+    out = _bench(["--full", "--steps", "2", "--warmup", "1", "--batch-per-gpu", "4", "--no-extras", "--cpu-sample", "0"], nproc=2,
                  env={"STANDIN_COMM": "fail_rank1"})
     via = out["config"]["allgather_via"]
     assert via.startswith("torch.distributed all_gather_into_tensor") and "failed on another rank" in via
@@ -113,7 +149,7 @@ def test_torch_path_on_request_and_the_other_schedules():
 
 def test_world_size_one_through_the_collective_path():
     """what tests/test_gpu_dist.py runs on the GPU box (DFTPAV_BENCH_FORCE_DIST / _FORCE_OTHER)"""
-    out = _bench(["--steps", "2", "--warmup", "1", "--batch-per-gpu", "8", "--no-extras", "--cpu-sample", "0"],
+    out = _bench(["--full", "--steps", "2", "--warmup", "1", "--batch-per-gpu", "8", "--no-extras", "--cpu-sample", "0"],
                  env={"DFTPAV_BENCH_FORCE_DIST": "1", "DFTPAV_BENCH_FORCE_OTHER": "1", "MASTER_PORT": str(_port())})
     assert out["n_gpus"] == 1 and out["other_scaling"]["scaling"] == "strong" and _count(out, "allgather", 8) >= 3
 
@@ -121,7 +157,7 @@ def test_world_size_one_through_the_collective_path():
 def test_every_side_run_of_the_one_gpu_line():
     """the default N = 1 line with all its side runs, at sizes the oracle finishes in half a minute: no side run fails, every
     entry the documents quote is there"""
-    out = _bench(["--steps", "2", "--warmup", "1", "--batch-per-gpu", "16", "--cpu-sample", "16"], timeout=900)
+    out = _bench(["--full", "--steps", "2", "--warmup", "1", "--batch-per-gpu", "16", "--cpu-sample", "16"], timeout=900)
     assert "side_run_errors" not in out, out.get("side_run_errors")
     for k in ("strong_shard", "isolated", "batch256", "single", "moving_obstacles_1024", "validate", "readout", "shots", "corridor",
               "cpu_baseline", "with_upload", "parity", "device_order", "order"):
@@ -157,9 +193,9 @@ def test_every_side_run_of_the_one_gpu_line():
 
 def test_a_side_run_over_its_time_limit_costs_its_entry_not_the_line():
     """the watchdog of the other scaling mode (what tests/test_gpu_dist.py checks on the device)"""
-    out = _bench(["--steps", "4", "--warmup", "1", "--batch-per-gpu", "16", "--no-extras", "--cpu-sample", "0"],
+    out = _bench(["--full", "--steps", "4", "--warmup", "1", "--batch-per-gpu", "16", "--no-extras", "--cpu-sample", "0"],
                  env={"DFTPAV_BENCH_FORCE_DIST": "1", "DFTPAV_BENCH_FORCE_OTHER": "1", "MASTER_PORT": str(_port()), "DFTPAV_BENCH_SIDE_LIMIT_S": "0.05"})
     assert out["value"] > 0 and "time limit" in out["other_scaling"]["error"]
-    out = _bench(["--steps", "4", "--warmup", "1", "--batch-per-gpu", "16", "--no-extras", "--cpu-sample", "0"],
+    out = _bench(["--full", "--steps", "4", "--warmup", "1", "--batch-per-gpu", "16", "--no-extras", "--cpu-sample", "0"],
                  env={"DFTPAV_BENCH_FORCE_DIST": "1", "DFTPAV_BENCH_FORCE_OTHER": "1", "MASTER_PORT": str(_port()), "DFTPAV_BENCH_DEPTH": "4,2"})
     assert out["other_scaling"]["steps_in_flight"] == 4 and out["other_scaling"]["steps"] >= 8

@@ -118,7 +118,7 @@ def test_bench_side_run_of_the_other_scaling_mode(hiplib):
     short for the side run, which must cost its own entry and not the line."""
     base = dict(os.environ, DFTPAV_BENCH_FORCE_DIST="1", DFTPAV_BENCH_FORCE_OTHER="1", MASTER_ADDR="127.0.0.1", RANK="0",
                 WORLD_SIZE="1", LOCAL_RANK="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--batch-per-gpu", "512",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "4", "--warmup", "1", "--batch-per-gpu", "512",
            "--no-extras", "--cpu-sample", "0"]
     out = subprocess.run(cmd, env=dict(base, MASTER_PORT=str(_free_port()), DFTPAV_BENCH_DEPTH="4,2"), capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
