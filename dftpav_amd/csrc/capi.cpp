@@ -11,6 +11,7 @@
 #include <atomic>
 #include <mutex>
 
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <algorithm>
@@ -56,18 +57,16 @@ size_t reference_order_scratch_doubles(const DevLayout &L, int B, int S);
 size_t reference_order_table_doubles(int N);
 void reference_order_pack_tables(int N, const double *full, double *packed);
 int reference_order_interior_mask(int sweep, int row_mod_6);
-RefPlan reference_order_plan(const DevLayout &L, const DevParams &P, int S, int B, int n_cu, bool allow_quad = true, bool throughput = false);
-// the QUAD shape (solver_ref4.hip): four trajectories per wave; its copy of the corridor and its launches
-size_t reference_order_quad_corridor_doubles(const DevLayout &L, int B);
-hipError_t launch_quad_corridor(const DevBatch &D, double *cor_t, hipStream_t stream);
-hipError_t launch_ring_reset(const DevBatch &D, hipStream_t stream); // solver_ref.hip
-hipError_t launch_quadm_corridor(const DevBatch &D, double *cor_t, hipStream_t stream); // solver_ref4m.hip: the QUAD shape for several gear segments (RefPlan::quad == 2)
-hipError_t launch_solver_ref4m(const DevBatch &D, const DevBatch *d_dev, int mode, const double *tabs, const double *cor_t, double *scratch, const RefPlan &pl,
-                               int scheduled, int slots, int hand, hipStream_t stream);
-hipError_t launch_solver_ref4(const DevBatch &D, const DevBatch *d_dev, int mode, const double *tabs, const double *cor_t, double *scratch, const RefPlan &pl,
-                              int scheduled, int slots, int hand, hipStream_t stream);
+RefPlan reference_order_plan(const DevLayout &L, const DevParams &P, int S, int B, int n_cu, bool throughput, const RefOptions &o);
+hipError_t launch_ring_reset(const DevBatch &D, hipStream_t stream);
 hipError_t launch_solver_ref(const DevBatch &D, const DevBatch *d_dev, int mode, const double *tabs, double *scratch, const RefPlan &pl, int scheduled,
                              hipStream_t stream);
+hipError_t launch_solver_quad(const DevBatch &D, const DevBatch *d_dev, int mode, const double *tabs, const double *cor_t, double *scratch, const RefPlan &pl,
+                              int scheduled, bool alone, hipStream_t stream);
+// the QUAD shapes' copy of the corridor (solver_ref4.hip: one gear segment, solver_ref4m.hip: several)
+size_t reference_order_quad_corridor_doubles(const DevLayout &L, int B);
+hipError_t launch_quad_corridor(const DevBatch &D, double *cor_t, hipStream_t stream);
+hipError_t launch_quadm_corridor(const DevBatch &D, double *cor_t, hipStream_t stream);
 }
 using namespace dftpav;
 
@@ -166,9 +165,8 @@ struct dftpav_batch {
   int order = DFTPAV_ORDER_DEVICE;
   int ref_S = 0; // moving obstacles on the handle when the reference order was chosen (the term records are sized for them)
   double *d_ref_tab = nullptr, *d_ref_scratch = nullptr;
-  RefPlan ref_plan{}; // its launch shape (chosen with the order)
-  RefPlan ref_plan_wt{}; // QUAD shape: the TEAM / WAVE plan of the same batch (what the QUAD kernel leaves to solver_ref.hip: the coefficient read-out)
-  double *d_cor_t = nullptr; // QUAD shape: the corridor as [B][4 H][Kmax + 1][16] (solver_ref4.hip), refreshed when the corridor changes
+  RefPlan ref_plan{}; // its launch plan (chosen with the order)
+  double *d_cor_t = nullptr; // QUAD shapes: the corridor as [B][4 H][Kmax + 1][16] (solver_ref4.hip), refreshed when the corridor changes
   bool cor_t_dirty = true;
   bool coef_override = false; // test hook dftpav_debug_batch_set_coeffs: validate / sample_states take the coefficients as they are
   int residency = -1; // the caller's residency hint (dftpav_batch_create_shaped); 2 = many such batches in flight: the throughput shapes whatever B
@@ -960,8 +958,27 @@ static void fill_dev_layout(const dftpav_layout &layout, int K, int Kd, DevLayou
   L.n = L.x_ang0 + (L.M - 1);
   L.npad = ((L.n + 63) / 64) * 64;
 }
+// The reference order's developer options (device_types.h: RefOptions), read where a plan is chosen and nowhere else.
+static RefOptions ref_options_from_env() {
+  auto num = [](const char *name, int unset, int lo) { // the variable's number, at least lo; `unset` where it is not set
+    const char *e = std::getenv(name);
+    return e ? std::max(lo, std::atoi(e)) : unset;
+  };
+  RefOptions o{};
+  const char *shape = std::getenv("DFTPAV_REF_SHAPE");
+  o.shape = shape ? (unsigned char)shape[0] : -1;
+  o.waves = num("DFTPAV_REF_WAVES", 0, 0);
+  o.threads = num("DFTPAV_REF_THREADS", 0, 0);
+  o.quad_waves = num("DFTPAV_REF_QUAD_WAVES", 0, 0);
+  o.quad_hand = num("DFTPAV_REF_QUAD_HANDOVER", -1, 0);
+  o.slice = num("DFTPAV_REF_SLICE", -1, 0);
+  o.slots = num("DFTPAV_REF_SLOTS", 0, 1);
+  o.exact_div = num("DFTPAV_REF_EXACT_DIV", 0, INT_MIN) != 0;
+  o.verbose = std::getenv("DFTPAV_VERBOSE") != nullptr;
+  return o;
+}
 // test hook (host only): is the reference order available for this layout with S moving obstacles, and which launch shape would
-// a batch of B trajectories take on a device of n_cu CUs?  out = {supported, wave, threads, workgroups per CU, persistent
+// a batch of B trajectories take on a device of n_cu CUs?  out = {supported, shape (RefKind), threads, workgroups per CU, persistent
 // workgroups, slice, LDS bytes per workgroup, width of the sequential sums}
 extern "C" int dftpav_debug_reference_plan(const dftpav_layout *layout, const dftpav_params *p, int S, int B, int n_cu, long long *out) {
   if (!layout || !p || !out || layout->M < 1 || layout->M > kMaxSeg || B < 1 || n_cu < 1) return DFTPAV_E_INVALID;
@@ -970,8 +987,8 @@ extern "C" int dftpav_debug_reference_plan(const dftpav_layout *layout, const df
   DevParams P;
   fill_dev_params(*p, P);
   out[0] = reference_order_supported(L, P, S) ? 1 : 0;
-  const RefPlan pl = reference_order_plan(L, P, S, B, n_cu);
-  out[1] = pl.wave | (pl.quad << 1); // 0: TEAM, 1: WAVE, 3: QUAD
+  const RefPlan pl = reference_order_plan(L, P, S, B, n_cu, false, ref_options_from_env());
+  out[1] = pl.kind; // 0: TEAM, 1: WAVE, 3: QUAD, 5: QUAD, several segments
   out[2] = pl.threads;
   out[3] = pl.wg_per_cu;
   out[4] = pl.slots;
@@ -1530,26 +1547,19 @@ extern "C" int dftpav_batch_get_trace(dftpav_batch *b, double *out, int *n_evals
 
 // every launch of the solve kernel for a batch goes through here: the reference-order kernel when the batch asks for it
 static hipError_t launch_ref(dftpav_batch *b, const DevBatch &D, int mode, int scheduled) {
-  if (b->ref_plan.quad && mode != kModeCoeffs) {
-    if (b->cor_t_dirty) { // the QUAD shape reads its own layout of the corridor
-      const hipError_t e = b->ref_plan.quad == 2 ? launch_quadm_corridor(D, b->d_cor_t, b->h->stream) : launch_quad_corridor(D, b->d_cor_t, b->h->stream);
-      if (e != hipSuccess) return e;
-      b->cor_t_dirty = false;
-    }
-    // A batch that has the device to itself (the default; dftpav_batch_set_hand_over(b, 0) says that other batches follow on other
-    // streams) takes every wave slot and hands its last trajectories to the WAVE shape: a launch of solver_ref.hip's kernel queued
-    // behind this one pops them from the same ring and resumes them from the same records (a wave per trajectory is 2-3 x faster
-    // per iteration once the device is emptying).  In a stream of batches the launch is half as wide as the batch (solver_ref4.hip).
-    const bool alone = b->hand_over != 0 && scheduled && mode == kModeSolve;
-    const int slots = alone ? b->ref_plan.slots_wide : b->ref_plan.slots;
-    const int hand = alone && b->ref_plan_wt.wave ? std::min(b->ref_plan.hand, b->B / 2) : 0;
-    hipError_t e = b->ref_plan.quad == 2
-                       ? launch_solver_ref4m(D, b->d_dev, mode, b->d_ref_tab, b->d_cor_t, b->d_ref_scratch, b->ref_plan, scheduled, slots, hand, b->h->stream)
-                       : launch_solver_ref4(D, b->d_dev, mode, b->d_ref_tab, b->d_cor_t, b->d_ref_scratch, b->ref_plan, scheduled, slots, hand, b->h->stream);
-    if (e == hipSuccess && hand > 0) e = launch_solver_ref(D, b->d_dev, kModeSolve, b->d_ref_tab, b->d_ref_scratch, b->ref_plan_wt, 1, b->h->stream);
-    return e;
+  const RefPlan &pl = b->ref_plan;
+  if (pl.kind < kRefQuad || mode == kModeCoeffs)
+    return launch_solver_ref(D, b->d_dev, mode, b->d_ref_tab, b->d_ref_scratch, pl, scheduled, b->h->stream);
+  if (b->cor_t_dirty) { // the QUAD shapes read their own layout of the corridor
+    const hipError_t e = pl.kind == kRefQuadSeg ? launch_quadm_corridor(D, b->d_cor_t, b->h->stream) : launch_quad_corridor(D, b->d_cor_t, b->h->stream);
+    if (e != hipSuccess) return e;
+    b->cor_t_dirty = false;
   }
-  return launch_solver_ref(D, b->d_dev, mode, b->d_ref_tab, b->d_ref_scratch, b->ref_plan.quad ? b->ref_plan_wt : b->ref_plan, scheduled, b->h->stream);
+  // A batch that has the device to itself (the default; dftpav_batch_set_hand_over(b, 0) says that other batches follow on other
+  // streams) takes every wave slot and hands its last trajectories to the WAVE shape.  In a stream of batches the launch is half as
+  // wide as the batch (solver_ref.hip: quad_shape).
+  const bool alone = b->hand_over != 0 && scheduled && mode == kModeSolve;
+  return launch_solver_quad(D, b->d_dev, mode, b->d_ref_tab, b->d_cor_t, b->d_ref_scratch, pl, scheduled, alone, b->h->stream);
 }
 static hipError_t launch_for(dftpav_batch *b, const DevBatch &D, int mode) {
   if (b->order == DFTPAV_ORDER_REFERENCE) return launch_ref(b, D, mode, 0);
@@ -1709,54 +1719,53 @@ extern "C" int dftpav_batch_set_order(dftpav_batch *b, int order) {
       h->err = "reference order: n <= 256 variables, H <= 12 half-planes, 5 H + S + 4 <= 64 terms per point, every gear segment >= 2 pieces, 159 KB of LDS";
       return DFTPAV_E_UNSUPPORTED;
     }
-    {
-      int n_cu = 256;
-      hipDeviceProp_t prop;
-      if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
-      const RefPlan pl = reference_order_plan(b->L, b->P, h->S, b->B, n_cu, true, b->residency == 2);
-      if (pl.wave && ensure_ring_buffers(b) != hipSuccess) {
-        h->err = "reference order: no device memory for the ring of this batch";
-        return DFTPAV_E_HIP;
-      }
-      b->ref_plan = pl;
-      if (pl.quad) {
-        b->ref_plan_wt = reference_order_plan(b->L, b->P, h->S, b->B, n_cu, false, true); // (the WAVE shape whatever B: it finishes the QUAD shape's last trajectories)
-        if (!b->d_cor_t && hipMalloc(&b->d_cor_t, sizeof(double) * reference_order_quad_corridor_doubles(b->L, b->B)) != hipSuccess) {
-          (void)hipGetLastError();
-          h->err = "reference order: no device memory for the QUAD shape's copy of the corridor";
-          return DFTPAV_E_HIP;
-        }
-        b->cor_t_dirty = true;
-      }
+    int n_cu = 256;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
+    const RefPlan pl = reference_order_plan(b->L, b->P, h->S, b->B, n_cu, b->residency == 2, ref_options_from_env());
+    if (pl.kind != kRefTeam && ensure_ring_buffers(b) != hipSuccess) {
+      h->err = "reference order: no device memory for the ring of this batch";
+      return DFTPAV_E_HIP;
     }
-    if (!b->d_ref_tab || !b->d_ref_scratch || b->ref_S != h->S) {
-      std::vector<double> tab; // the tables of the segments, one after the other
-      for (int sg = 0; sg < b->L.M; sg++) {
-        std::vector<double> one;
-        if (!reference_order_tables(b->L.piece_nums[sg], one)) {
-          h->err = "reference order: the LU factors of this band system do not have the pattern the kernel assumes";
-          return DFTPAV_E_UNSUPPORTED;
-        }
-        std::vector<double> packed(reference_order_table_doubles(b->L.piece_nums[sg]));
-        reference_order_pack_tables(b->L.piece_nums[sg], one.data(), packed.data());
-        tab.insert(tab.end(), packed.begin(), packed.end());
+    // Everything else is built on the side and committed to the batch together: a failure leaves the batch as it was (the
+    // order, its plan, the corridor copy, the tables and the term records) and frees what this call allocated.
+    const bool new_tab = !b->d_ref_tab || !b->d_ref_scratch || b->ref_S != h->S;
+    std::vector<double> tab; // the tables of the segments, one after the other
+    for (int sg = 0; new_tab && sg < b->L.M; sg++) {
+      std::vector<double> one;
+      if (!reference_order_tables(b->L.piece_nums[sg], one)) {
+        h->err = "reference order: the LU factors of this band system do not have the pattern the kernel assumes";
+        return DFTPAV_E_UNSUPPORTED;
       }
-      double *d_tab = nullptr, *d_scr = nullptr;
-      if (hipMalloc(&d_tab, sizeof(double) * tab.size()) != hipSuccess ||
-          hipMalloc(&d_scr, sizeof(double) * reference_order_scratch_doubles(b->L, b->B, h->S)) != hipSuccess ||
-          hipMemcpy(d_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        if (d_tab) (void)hipFree(d_tab);
-        if (d_scr) (void)hipFree(d_scr);
-        (void)hipGetLastError();
-        h->err = "reference order: no device memory for the term records of this batch";
-        return DFTPAV_E_HIP; // the order stays as it was, the batch usable
-      }
+      std::vector<double> packed(reference_order_table_doubles(b->L.piece_nums[sg]));
+      reference_order_pack_tables(b->L.piece_nums[sg], one.data(), packed.data());
+      tab.insert(tab.end(), packed.begin(), packed.end());
+    }
+    double *cor_t = b->d_cor_t, *d_tab = nullptr, *d_scr = nullptr; // (the corridor copy's size does not change: a batch keeps its first)
+    auto undo = [&](const char *msg) {
+      if (cor_t != b->d_cor_t) (void)hipFree(cor_t);
+      if (d_tab) (void)hipFree(d_tab);
+      if (d_scr) (void)hipFree(d_scr);
+      (void)hipGetLastError();
+      h->err = msg;
+      return DFTPAV_E_HIP; // the order stays as it was, the batch usable
+    };
+    if (pl.kind >= kRefQuad && !cor_t && hipMalloc(&cor_t, sizeof(double) * reference_order_quad_corridor_doubles(b->L, b->B)) != hipSuccess)
+      return undo("reference order: no device memory for the QUAD shape's copy of the corridor");
+    if (new_tab && (hipMalloc(&d_tab, sizeof(double) * tab.size()) != hipSuccess ||
+                    hipMalloc(&d_scr, sizeof(double) * reference_order_scratch_doubles(b->L, b->B, h->S)) != hipSuccess ||
+                    hipMemcpy(d_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice) != hipSuccess))
+      return undo("reference order: no device memory for the term records of this batch");
+    if (new_tab) {
       if (b->d_ref_tab) (void)hipFree(b->d_ref_tab);
       if (b->d_ref_scratch) (void)hipFree(b->d_ref_scratch);
       b->d_ref_tab = d_tab;
       b->d_ref_scratch = d_scr;
       b->ref_S = h->S;
     }
+    if (pl.kind >= kRefQuad) b->cor_t_dirty = true;
+    b->d_cor_t = cor_t;
+    b->ref_plan = pl;
   }
   b->order = order;
   b->solved = false;
@@ -1832,8 +1841,7 @@ static int solve_impl(dftpav_batch *b, dftpav_batch *prev, bool chained) {
   if (int rc = sync_dev(b, D)) return rc;
   HIPCHK(h, hipEventRecord(b->ev0, h->stream));
   if (b->order == DFTPAV_ORDER_REFERENCE) {
-    // (the QUAD shape always runs from the ring: its rows take a new trajectory as soon as one ends)
-    if (b->ref_plan.wave && b->ref_plan.slots > 0 && b->ref_plan.slice > 0 && (b->ref_plan.quad || b->ref_plan.slots * (b->ref_plan.threads / 64) < b->B)) {
+    if (b->ref_plan.ring) {
       // more trajectories than resident waves: persistent workgroups whose waves pop trajectories from the ring and run them a
       // slice of iterations at a time (solver_ref.hip); queue = all trajectories, flags cleared, counters reset on the stream
       HIPCHK(h, launch_ring_reset(D, h->stream));

@@ -180,18 +180,51 @@ struct SchedArgs {
 // doubles of solver state per suspended trajectory
 inline int solver_state_doubles(const DevLayout &L, const DevParams &P) { (void)P; return 5 * L.npad + 24 + 8; }
 
-// launch shape of a reference-order batch (solver_ref.hip: reference_order_plan)
-struct RefPlan {
-  int wave;      // 1: one wave per trajectory, several per workgroup (throughput); 0: one workgroup per trajectory (latency)
-  int quad;      // 1 (with wave = 1): FOUR trajectories per wave, one per row of 16 lanes (solver_ref4.hip)
+// The reference order's developer options, read from the environment once, when dftpav_batch_set_order chooses the plan
+// (capi.cpp: ref_options_from_env).  0 / -1: not set.
+struct RefOptions {
+  int shape;    // DFTPAV_REF_SHAPE: its first character; "team" / "wave" / "quad" force that shape (-1: by the batch)
+  int waves;    // DFTPAV_REF_WAVES: waves per workgroup of the WAVE shape
+  int threads;  // DFTPAV_REF_THREADS: workgroup size of the TEAM shape (128 / 192 / 256)
+  int quad_waves; // DFTPAV_REF_QUAD_WAVES: waves per workgroup of the QUAD shapes
+  int quad_hand;  // DFTPAV_REF_QUAD_HANDOVER: RefShape::hand (-1: the shape's own)
+  int slice;      // DFTPAV_REF_SLICE: RefShape::slice (-1: the shape's own; 0: never back to the ring)
+  int slots;      // DFTPAV_REF_SLOTS: persistent workgroups of a scheduled solve (RefShape::slots and slots_wide)
+  bool exact_div; // DFTPAV_REF_EXACT_DIV: true divisions in the recursion (test hook; its fallback for divisors beyond 2^+-500)
+  bool verbose;   // DFTPAV_VERBOSE: every launch prints its shape
+};
+
+// launch shape of the reference order's kernels; the kind's numbers are those dftpav_debug_reference_plan reports
+enum RefKind { kRefTeam = 0, kRefWave = 1, kRefQuad = 3, kRefQuadSeg = 5 }; // (the QUAD kinds: kind >= kRefQuad)
+struct RefShape {
+  int kind;      // TEAM: one workgroup per trajectory (latency); WAVE: one wave per trajectory, several per workgroup (throughput);
+                 // QUAD: FOUR trajectories per wave, one per row of 16 lanes (solver_ref4.hip; QuadSeg: several gear segments, solver_ref4m.hip)
   int threads;   // workgroup size
-  int wg_per_cu; // WAVE shape: resident workgroups per CU
-  int slots;     // WAVE shape: persistent workgroups of a scheduled solve
-  int slice;     // WAVE shape: iterations after which an unfinished trajectory goes back to the ring
-  int slots_wide; // QUAD shape: persistent workgroups of a launch that has the device to itself (dftpav_batch_set_hand_over != 0)
-  int hand;       // QUAD shape, such a launch: unfinished trajectories at which its waves leave theirs to a follow-up launch in the WAVE shape
+  int wg_per_cu; // WAVE / QUAD: resident workgroups per CU
+  int slots;     // WAVE / QUAD: persistent workgroups of a scheduled solve
+  int slice;     // WAVE / QUAD: iterations after which an unfinished trajectory goes back to the ring
+  int slots_wide; // QUAD: persistent workgroups of a launch that has the device to itself (dftpav_batch_set_hand_over != 0)
+  int hand;       // QUAD, such a launch: unfinished trajectories at which its waves leave theirs to a follow-up launch in the WAVE shape
   size_t lds;    // dynamic LDS per workgroup
 };
+// everything the launches of a reference-order batch read, chosen once by dftpav_batch_set_order (solver_ref.hip: reference_order_plan)
+struct RefPlan : RefShape {
+  RefShape wt;    // the shape solver_ref.hip's kernel launches with: the plan's own, or under a QUAD kind the TEAM / WAVE shape for
+                  // throughput, which does the coefficient read-out and finishes the last trajectories of a batch alone on the device
+  bool ring;      // a solve runs from the batch's ring (more trajectories than resident waves; QUAD always)
+  bool fast;      // QUAD kernels: the instance for H = 4 (the launch adds help_eps == 0.0, which comes with every upload)
+  bool tail1;     // QuadSeg kernel: the instance for n = 33 (TAIL = 1)
+  bool exact_div; // bit 1 of the kernels' source (RefOptions::exact_div)
+  bool verbose;   // RefOptions::verbose
+};
+// what differs between the plans of the two QUAD shapes: the LDS of the tables a workgroup shares and of one row (a quarter of a
+// wave), resident waves per CU at most, and RefShape::hand
+struct QuadSizes {
+  size_t shared, row;
+  int waves_per_cu, hand;
+};
+// a QUAD kernel's instance (solver_ref4.hip: ref4_kernel_for, solver_ref4m.hip: ref4m_kernel_for; the two share one signature)
+using QuadKernel = void (*)(const DevBatch *, int, const double *, const double *, double *, int, int, int);
 
 // host-side E4 lane plan of a layout for a workgroup size (tables of DevBatch::e4_*)
 struct E4Sizes {

@@ -46,6 +46,10 @@ template <int CTRL> __device__ __forceinline__ double nb_dpp(double v) {
 // (solver_ref4m.hip, several gear segments: tried and not kept -- its kernel has no registers left for the list's code: 64 bytes of
 // scratch per lane and 165 -> 171 ms per step of configs[1]'s stream)
 constexpr int kDense = 24;
+static_assert(kDense <= 32, "a lane's slots of the list are the bits of a 32-bit mask (solver_ref4.hip: mine |= 1u << e)");
+// DenseLds::id packs an entry into an int: the owner lane in bits 0-5 (lane & 63), the term in bits 6-11, the point from bit 12 on.
+// Term and point are run-time values: the term is < 5 H + 4 <= 29 (reference_order_quad_supported: H <= 5); the point is <= Kmax + 1,
+// which keeps the id positive while Kmax + 1 < 2^19 -- no predicate bounds K.
 struct DenseLds {
   ldsi_t id;   // [kDense] owner lane | term << 6 | point << 12
   ldsd_t s1;   // [kDense]

@@ -1968,9 +1968,11 @@ __global__ void __launch_bounds__((WAVE && CAP <= kNarrowCap && !SUR) ? 512 : 25
 #define DFTPAV_REF_PART 0
 #endif
 bool reference_order_quad_supported(const DevLayout &L, const DevParams &P, int S); // solver_ref4.hip
-void reference_order_quad_plan(const DevLayout &L, const DevParams &P, int B, int n_cu, RefPlan &pl);
+QuadSizes reference_order_quad_sizes(const DevLayout &L, const DevParams &P);
 bool reference_order_quadm_supported(const DevLayout &L, const DevParams &P, int S); // solver_ref4m.hip: several gear segments
-void reference_order_quadm_plan(const DevLayout &L, const DevParams &P, int B, int n_cu, RefPlan &pl);
+QuadSizes reference_order_quadm_sizes(const DevLayout &L, const DevParams &P);
+QuadKernel ref4_kernel_for(bool fast);                 // solver_ref4.hip
+QuadKernel ref4m_kernel_for(bool fast, bool tail1);   // solver_ref4m.hip
 #if DFTPAV_REF_PART != 2
 // what the layout must satisfy for the reference-order kernel (solver_ref.hip header)
 bool reference_order_supported(const DevLayout &L, const DevParams &P, int S) {
@@ -2053,13 +2055,13 @@ hipError_t launch_ring_reset(const DevBatch &D, hipStream_t stream) {
   return hipGetLastError();
 }
 
-// The launch shape of a batch (see the header).  TEAM: four waves per trajectory while the batch leaves CUs to spare (the
+// The TEAM / WAVE shape of a batch (see the header).  TEAM: four waves per trajectory while the batch leaves CUs to spare (the
 // parallel stages finish sooner: 70 against 73 ms at batch 32, 133 against 140 at 256), two for more.  WAVE: as many waves per
 // workgroup as keep the most trajectories resident on a CU -- 8 waves of 256 registers (4 for the kernels that take 512), the
 // LDS of the shared tables plus a team's part per wave.
 // throughput: the caller keeps many such batches in flight (dftpav_batch_create_shaped, residency 2) -- the throughput shapes whatever B
-RefPlan reference_order_plan(const DevLayout &L, const DevParams &P, int S, int B, int n_cu, bool allow_quad, bool throughput) {
-  RefPlan pl{};
+static RefShape team_wave_shape(const DevLayout &L, const DevParams &P, int S, int B, int n_cu, bool throughput, const RefOptions &o) {
+  RefShape pl{};
   const bool narrow = reford::ref_cap_of(L.n) <= reford::kNarrowCap && S == 0; // the kernels built for 256 registers (two waves per SIMD)
   const int max_waves_cu = narrow ? 8 : 4;
   const reford::Shape sw = reford::make_shape(L, S, true);
@@ -2080,60 +2082,92 @@ RefPlan reference_order_plan(const DevLayout &L, const DevParams &P, int S, int 
   // 171 against 195 ms at 1024, 133 against 189 at 512; at 2048 the WAVE shape is ahead, 262 against 320 ms
   const bool wide_n = L.n > 64 || L.H > 5; // more variables than a wave has lanes, or more than five half-planes per point: the generic TEAM kernel, whatever B
   bool wave = best_w > 0 && !wide_n && (B > 5 * n_cu || throughput);
-  if (const char *e = std::getenv("DFTPAV_REF_SHAPE")) { // developer knob: "team" / "wave"
-    if (e[0] == 't') wave = false;
-    if (e[0] == 'w' && best_w > 0 && !wide_n) wave = true;
+  if (o.shape == 't') wave = false;
+  if (o.shape == 'w' && best_w > 0 && !wide_n) wave = true;
+  if (o.waves >= 1 && o.waves <= max_waves_cu && shared + (size_t)o.waves * team_w <= budget) {
+    best_w = o.waves;
+    best_wg = (int)std::min<size_t>((size_t)(max_waves_cu / best_w), budget / (shared + (size_t)best_w * team_w));
   }
-  if (const char *e = std::getenv("DFTPAV_REF_WAVES")) { // developer knob: waves per workgroup in the WAVE shape
-    const int w = std::atoi(e);
-    if (w >= 1 && w <= max_waves_cu && shared + (size_t)w * team_w <= budget) {
-      best_w = w;
-      best_wg = (int)std::min<size_t>((size_t)(max_waves_cu / w), budget / (shared + (size_t)w * team_w));
-    }
-  }
-  bool quad = allow_quad && wave && reference_order_quad_supported(L, P, S);
-  if (const char *e = std::getenv("DFTPAV_REF_SHAPE")) { // "quad": four trajectories per wave wherever the layout allows it
-    if (e[0] == 'q') quad = allow_quad && reference_order_quad_supported(L, P, S);
-    else quad = false;
-  }
-  pl.quad = 0;
-  if (quad) {
-    reference_order_quad_plan(L, P, B, n_cu, pl);
-    return pl;
-  }
-  // several gear segments (solver_ref4m.hip)
-  bool quadm = allow_quad && wave && L.M > 1 && reference_order_quadm_supported(L, P, S);
-  if (const char *e = std::getenv("DFTPAV_REF_QUADM_OFF")) quadm = quadm && !(e[0] != 0 && e[0] != '0'); // developer knob: several segments stay with the WAVE shape
-  if (const char *e = std::getenv("DFTPAV_REF_SHAPE")) {
-    if (e[0] == 'q') quadm = allow_quad && reference_order_quadm_supported(L, P, S);
-    else quadm = false;
-  }
-  if (quadm) {
-    reference_order_quadm_plan(L, P, B, n_cu, pl);
-    return pl;
-  }
-  pl.wave = wave ? 1 : 0;
   if (wave) {
+    pl.kind = kRefWave;
     pl.threads = 64 * best_w;
     pl.lds = shared + (size_t)best_w * team_w;
     pl.wg_per_cu = best_wg;
-    pl.slots = n_cu * best_wg; // persistent workgroups of a scheduled solve
-    pl.slice = 128;
-    if (const char *e = std::getenv("DFTPAV_REF_SLICE")) pl.slice = std::atoi(e);
-    if (const char *e = std::getenv("DFTPAV_REF_SLOTS")) pl.slots = std::max(1, std::atoi(e)); // developer knob: persistent workgroups
+    pl.slots = o.slots > 0 ? o.slots : n_cu * best_wg; // persistent workgroups of a scheduled solve
+    pl.slice = o.slice >= 0 ? o.slice : 128;
   } else {
     int threads = B > 768 ? 128 : 256;
-    if (const char *e = std::getenv("DFTPAV_REF_THREADS")) { // developer knob: whole waves, at most the launch bound
-      const int t = std::atoi(e);
-      if (t == 128 || t == 192 || t == 256) threads = t; // wave 1 has jobs of its own: at least two waves
-    }
+    if (o.threads == 128 || o.threads == 192 || o.threads == 256) threads = o.threads; // wave 1 has jobs of its own: at least two waves
     const reford::Shape st = reford::make_shape(L, S, false);
+    pl.kind = kRefTeam;
     pl.threads = threads;
     pl.lds = shared + reford::lds_team_bytes(L, P.mem_size, st);
-    pl.wg_per_cu = 0;
-    pl.slots = 0;
-    pl.slice = 0;
   }
+  return pl;
+}
+
+// The QUAD shapes: as many waves per workgroup (at most 4) and workgroups per CU as the LDS holds, z.waves_per_cu at most.
+static RefShape quad_shape(const QuadSizes &z, int B, int n_cu, const RefOptions &o) {
+  const size_t budget = 160 * 1024;
+  int best_w = 1, best_wg = 1, best_res = 0;
+  for (int w = std::min(4, z.waves_per_cu); w >= 1; w--) {
+    const size_t lds = z.shared + (size_t)w * 4 * z.row;
+    if (lds > budget) continue;
+    const int wg = (int)std::min<size_t>((size_t)(z.waves_per_cu / w), budget / lds);
+    if (wg * w >= best_res) { // ties: the smaller workgroup (it leaves sooner at the end of a launch)
+      best_res = wg * w;
+      best_w = w;
+      best_wg = wg;
+    }
+  }
+  if (o.quad_waves >= 1 && o.quad_waves <= 4 && z.shared + (size_t)o.quad_waves * 4 * z.row <= budget) {
+    best_w = o.quad_waves;
+    best_wg = (int)std::min<size_t>((size_t)(z.waves_per_cu / best_w), budget / (z.shared + (size_t)best_w * 4 * z.row));
+  }
+  RefShape pl{};
+  pl.threads = 64 * best_w;
+  pl.lds = z.shared + (size_t)best_w * 4 * z.row;
+  pl.wg_per_cu = best_wg;
+  // Persistent workgroups of a scheduled solve: a wave's rows are only refilled while the batch's ring holds waiting
+  // trajectories, so a launch takes HALF as many rows as the batch has trajectories (two per row) -- the rows stay busy until half
+  // of the batch is done, the rest gathers in ever fewer waves (slices), and the waves that leave make room for the next batch's
+  // launch on another stream.  Measured on the bench's stream of 4096-batches, four in flight (gpurun_out/q4.log, round 6): 256 / 512 /
+  // 768 waves per launch -> 22.7 / 28.0 / 27.1 k solves/s; a launch as wide as the device (every trajectory its own row from the
+  // start, no refill): 19.3 k.
+  const int per_wg = 4 * best_w;
+  pl.slots = std::max(1, std::min(n_cu * best_wg, (B + 2 * per_wg - 1) / (2 * per_wg)));
+  pl.slice = 64; // evaluations between two visits to the ring (64 / 256: 28.0 / 26.0 k solves/s)
+  pl.slots_wide = n_cu * best_wg; // a batch with the device to itself: every wave slot
+  pl.hand = z.hand;               // ... and its last trajectories finish in the WAVE shape (launch_solver_quad)
+  if (o.quad_hand >= 0) pl.hand = o.quad_hand;
+  if (o.slice >= 0) pl.slice = o.slice;
+  if (o.slots > 0) pl.slots = pl.slots_wide = o.slots;
+  return pl;
+}
+
+// The plan of a batch: the QUAD shape wherever the WAVE shape would run and the layout allows it (DFTPAV_REF_SHAPE=quad:
+// wherever the layout allows it), otherwise the TEAM / WAVE shape.
+RefPlan reference_order_plan(const DevLayout &L, const DevParams &P, int S, int B, int n_cu, bool throughput, const RefOptions &o) {
+  RefPlan pl{};
+  static_cast<RefShape &>(pl) = team_wave_shape(L, P, S, B, n_cu, throughput, o);
+  const bool by_batch = o.shape < 0 ? pl.kind == kRefWave : o.shape == 'q';
+  if (by_batch && reference_order_quad_supported(L, P, S)) pl.kind = kRefQuad;
+  else if (by_batch && (L.M > 1 || o.shape == 'q') && reference_order_quadm_supported(L, P, S)) pl.kind = kRefQuadSeg;
+  if (pl.kind >= kRefQuad) {
+    pl.wt = team_wave_shape(L, P, S, B, n_cu, true, o);
+    const int kind = pl.kind;
+    static_cast<RefShape &>(pl) = quad_shape(kind == kRefQuad ? reference_order_quad_sizes(L, P) : reference_order_quadm_sizes(L, P), B, n_cu, o);
+    pl.kind = kind;
+    pl.fast = L.H == 4;
+    pl.tail1 = kind == kRefQuadSeg && L.n == 33;
+    // (the QUAD shape always runs from the ring: its rows take a new trajectory as soon as one ends)
+    pl.ring = pl.slots > 0 && pl.slice > 0;
+  } else {
+    pl.wt = pl;
+    pl.ring = pl.kind == kRefWave && pl.slots > 0 && pl.slice > 0 && pl.slots * (pl.threads / 64) < B;
+  }
+  pl.exact_div = o.exact_div;
+  pl.verbose = o.verbose;
   return pl;
 }
 
@@ -2175,10 +2209,12 @@ static hipError_t launch_ref_variant_gen(const DevBatch *d_dev, int grid, int th
   hipLaunchKernelGGL((reford::ref_kernel<64, SUR, false, true>), dim3(grid), dim3(threads), lds, stream, d_dev, mode, tabs, scratch, source, slice);
   return hipGetLastError();
 }
-// scheduled != 0: a solve in the WAVE shape whose waves pop from the batch's ring (the caller has reset it)
-hipError_t launch_solver_ref(const DevBatch &D, const DevBatch *d_dev, int mode, const double *tabs, double *scratch, const RefPlan &pl, int scheduled,
+// the kernel of this file in the plan's TEAM / WAVE shape (RefPlan::wt); scheduled != 0: a solve in the WAVE shape whose waves pop
+// from the batch's ring (the caller has reset it)
+hipError_t launch_solver_ref(const DevBatch &D, const DevBatch *d_dev, int mode, const double *tabs, double *scratch, const RefPlan &plan, int scheduled,
                              hipStream_t stream) {
-  const bool wave = pl.wave != 0, sur = D.sur.S > 0;
+  const RefShape &pl = plan.wt;
+  const bool wave = pl.kind == kRefWave, sur = D.sur.S > 0;
   const int W = pl.threads / 64;
   int grid = wave ? (D.B + W - 1) / W : D.B, source = 0, slice = 0;
   if (wave && scheduled && mode == kModeSolve) {
@@ -2186,9 +2222,8 @@ hipError_t launch_solver_ref(const DevBatch &D, const DevBatch *d_dev, int mode,
     source = 1;
     slice = pl.slice;
   }
-  if (const char *e = std::getenv("DFTPAV_REF_EXACT_DIV")) // test hook: true divisions in the recursion (its fallback for divisors beyond 2^+-500)
-    if (std::atoi(e) != 0) source |= 2;
-  if (std::getenv("DFTPAV_VERBOSE"))
+  if (plan.exact_div) source |= 2;
+  if (plan.verbose)
     std::fprintf(stderr, "[dftpav] reference order, %s shape: grid %d x %d threads, %zu B of LDS, source %d slice %d\n", wave ? "WAVE" : "TEAM", grid, pl.threads,
                  pl.lds, source, slice);
   if (D.L.n > 64 || D.L.H > 5) { // (reference_order_plan keeps these in the TEAM shape)
@@ -2202,6 +2237,34 @@ hipError_t launch_solver_ref(const DevBatch &D, const DevBatch *d_dev, int mode,
   case 48: return launch_ref_cap<48>(sur, wave, d_dev, grid, pl.threads, pl.lds, mode, tabs, scratch, source, slice, stream);
   default: return launch_ref_cap<64>(sur, wave, d_dev, grid, pl.threads, pl.lds, mode, tabs, scratch, source, slice, stream);
   }
+}
+
+// the QUAD kernels (solver_ref4.hip, solver_ref4m.hip); scheduled != 0: a solve whose rows pop from the batch's ring (the caller has
+// reset it).  alone: a scheduled solve of a batch that has the device to itself -- every wave slot, and once RefShape::hand
+// trajectories are unfinished its waves leave theirs to a launch in the WAVE shape queued behind, which pops them from the same ring
+// and resumes them from the same records (a wave per trajectory is 2-3 x faster per iteration once the device is emptying).
+hipError_t launch_solver_quad(const DevBatch &D, const DevBatch *d_dev, int mode, const double *tabs, const double *cor_t, double *scratch, const RefPlan &pl,
+                              int scheduled, bool alone, hipStream_t stream) {
+  const int W = pl.threads / 64;
+  int grid = (D.B + 4 * W - 1) / (4 * W), source = 0, slice = 0, hand = 0;
+  if (scheduled && mode == kModeSolve) {
+    grid = std::min(grid, alone ? pl.slots_wide : pl.slots);
+    source = 1;
+    slice = pl.slice;
+    if (alone && pl.wt.kind == kRefWave) hand = std::min(pl.hand, D.B / 2);
+  }
+  if (pl.exact_div) source |= 2;
+  if (pl.verbose)
+    std::fprintf(stderr, "[dftpav] reference order, QUAD shape%s: grid %d x %d threads, %zu B of LDS, source %d slice %d hand-over at %d\n",
+                 pl.kind == kRefQuad ? "" : " (several segments)", grid, pl.threads, pl.lds, source, slice, hand);
+  const bool fast = pl.fast && D.epis == 0.0; // the live path's constants (solver_ref4.hip: q4_eval)
+  const QuadKernel fn = pl.kind == kRefQuad ? ref4_kernel_for(fast) : ref4m_kernel_for(fast, pl.tail1);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(fn, dim3(grid), dim3(pl.threads), pl.lds, stream, d_dev, mode, tabs, cor_t, scratch, source, slice, hand);
+  e = hipGetLastError();
+  if (e == hipSuccess && hand > 0) e = launch_solver_ref(D, d_dev, kModeSolve, tabs, scratch, pl, 1, stream);
+  return e;
 }
 #endif // DFTPAV_REF_PART != 2
 

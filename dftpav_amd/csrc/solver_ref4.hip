@@ -285,11 +285,10 @@ __device__ __forceinline__ void sweep4_split(ldscd_t tab, double (&X)[6], double
 // trajectory's global scratch for the parked terms beyond the LDS window.
 // FAST: the live path's constants known at compile time -- H = 4 half-planes per point (rectangles, traj_manager.cpp:1225) and
 // help_eps = 0.0 (:610): the fifth plane slot and the second reciprocal of the curvature term drop out of the point loop.
-template <bool FAST, bool DENSE>
+template <bool FAST>
 __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const DenseLds &dl, ldscd_t tab, gcd_t cor, size_t cpitch, gd_t ovf, int l, Prof &pr) {
   const DevLayout &L = D.L;
   const DevParams &P = D.P;
-  constexpr bool SPLIT = DENSE; // (the round's two late changes share the switch DFTPAV_REF_QUAD_DENSE: the sweeps of 16 pieces with a dimension per lane)
   const int N = L.Ntot, H = FAST ? 4 : L.H, nterm = 5 * H + 4, t0 = 5 * H;
   const double epis = FAST ? 0.0 : D.epis;
   // ---- durations (VirtualT2RealT, :371-379), their powers (poly_traj_utils.hpp:961-966)
@@ -321,7 +320,7 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
     bq[11] = q.xs[2 * l + 1];
   }
   // ---- BandedSystem::solve (poly_traj_utils.hpp:805-826)
-  if (N == 16 && SPLIT) { // (uniform)
+  if (N == 16) { // (uniform)
     double X[6], Y[6];
     q4_split(bq, X, Y, l);
     sweep4_split<0>(tab, X, Y, l);
@@ -398,7 +397,7 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
     }
     cnt++;
   };
-  // DENSE: the list of the wave
+  // the list of the wave
   const int lane64 = (int)(threadIdx.x & 63);
   int listed = 0;       // (uniform) entries in the list
   unsigned mine = 0u;   // the list's slots that hold terms of this lane's piece
@@ -465,9 +464,9 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
     listed = 0;
     mine = 0u;
   };
-  // (DENSE: one more round than the pieces have points -- it only empties the list: the emission's code exists once)
+  // (one more round than the pieces have points -- it only empties the list: the emission's code exists once)
 #pragma unroll 1
-  for (int j = 0; j <= L.Kmax + (DENSE ? 1 : 0); j++) {
+  for (int j = 0; j <= L.Kmax + 1; j++) {
     const bool extra = j > L.Kmax; // (uniform)
     unsigned m = 0u;
     PtState pst;
@@ -499,40 +498,38 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
         q1 = k == u ? pl[4 * u + 3] : q1;
       }
     };
-    bool in_place = !DENSE;
-    if (DENSE) {
-      const int c = __builtin_popcount(m);
-      const bool any = __builtin_amdgcn_ballot_w64(c != 0) != 0ull; // (uniform) some point of this round has active terms
-      int incl = 0, total = 0;
-      if (any) incl = scan_here(c, total);
-      // the list is emptied when this round's terms do not fit behind what it holds, and by the extra round
-      if (listed > 0 && (extra || listed + total > kDense)) flush(); // (uniform)
-      if (any && total > kDense) { // (uniform, rare) more than a list's worth in one round: in place, behind the earlier points' terms
-        in_place = true;
-      } else if (any) {
-        int e = listed + incl - c;
-        for (unsigned mm = m; mm;) {
-          const int t = __builtin_ctz(mm);
-          mm &= mm - 1;
-          dl.id[e] = lane64 | (t << 6) | (j << 12);
-          dl.s1[e] = s1_pt;
-          if (t < t0) { // a corridor term: vertex v against half-plane k = t - v H
-            int v = 0;
+    bool in_place = false;
+    const int c = __builtin_popcount(m);
+    const bool any = __builtin_amdgcn_ballot_w64(c != 0) != 0ull; // (uniform) some point of this round has active terms
+    int incl = 0, total = 0;
+    if (any) incl = scan_here(c, total);
+    // the list is emptied when this round's terms do not fit behind what it holds, and by the extra round
+    if (listed > 0 && (extra || listed + total > kDense)) flush(); // (uniform)
+    if (any && total > kDense) { // (uniform, rare) more than a list's worth in one round: in place, behind the earlier points' terms
+      in_place = true;
+    } else if (any) {
+      int e = listed + incl - c;
+      for (unsigned mm = m; mm;) {
+        const int t = __builtin_ctz(mm);
+        mm &= mm - 1;
+        dl.id[e] = lane64 | (t << 6) | (j << 12);
+        dl.s1[e] = s1_pt;
+        if (t < t0) { // a corridor term: vertex v against half-plane k = t - v H
+          int v = 0;
 #pragma unroll
-            for (int qv = 1; qv < 5; qv++) v += t >= qv * H ? 1 : 0;
-            double on0, on1, q0, q1;
-            plane_of(t - v * H, on0, on1, q0, q1);
-            ldsd_t w = dl.pl + 4 * e;
-            w[0] = on0;
-            w[1] = on1;
-            w[2] = q0;
-            w[3] = q1;
-          }
-          mine |= 1u << e;
-          e++;
+          for (int qv = 1; qv < 5; qv++) v += t >= qv * H ? 1 : 0;
+          double on0, on1, q0, q1;
+          plane_of(t - v * H, on0, on1, q0, q1);
+          ldsd_t w = dl.pl + 4 * e;
+          w[0] = on0;
+          w[1] = on1;
+          w[2] = q0;
+          w[3] = q1;
         }
-        listed += total;
+        mine |= 1u << e;
+        e++;
       }
+      listed += total;
     }
     if (in_place) {
       for (unsigned mm = m; mm;) {
@@ -627,7 +624,7 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
   double adj[12];
 #pragma unroll
   for (int u = 0; u < 12; u++) adj[u] = gdC[u] * tI[u >> 1];
-  if (N == 16 && SPLIT) { // (uniform)
+  if (N == 16) { // (uniform)
     double X[6], Y[6];
     q4_split(adj, X, Y, l);
     sweep4_split<2>(tab + pk_sweep_offset(2, 16), X, Y, l);
@@ -1096,7 +1093,7 @@ __device__ inline void q4_state_io(const DevBatch &D, const Q4 &q, QVec &v, int 
 // r of wave w of workgroup i takes trajectory (i W + w) 4 + r; bit 1: test hook, true divisions in the recursion from the start.
 // slice: evaluations of a wave after which its unfinished trajectories go back to the ring (all four rows together, so that the
 // rows of a wave are refilled together and the last trajectories of a batch gather in few waves).  hand: see the slice's end.
-template <bool FAST, bool DENSE>
+template <bool FAST>
 __global__ void __launch_bounds__(256, DFTPAV_Q4_WAVES_PER_EU)
     ref4_kernel(const DevBatch *__restrict__ Dp, int mode, const double *__restrict__ tabs, const double *__restrict__ cor_t, double *__restrict__ scratch, int source,
                 int slice, int hand) {
@@ -1165,7 +1162,7 @@ __global__ void __launch_bounds__(256, DFTPAV_Q4_WAVES_PER_EU)
     if (act) {
       const gcd_t cor = (gcd_t)(cor_t + (size_t)b * L.H * 4 * cpitch + l);
       const gd_t ovf = (gd_t)(scratch + (size_t)b * scratch_per_traj);
-      const double f = q4_eval<FAST, DENSE>(D, q, dl, tab, cor, cpitch, ovf, l, pr);
+      const double f = q4_eval<FAST>(D, q, dl, tab, cor, cpitch, ovf, l, pr);
       if (mode == kModeEval) {
         for (int h = 0; h < 2; h++) {
           const int e = 16 * h + l;
@@ -1270,52 +1267,15 @@ __global__ void q4_corridor_kernel(const double *__restrict__ cor, double *__res
 // ---- host side
 // what the layout must satisfy for the QUAD shape (header)
 bool reference_order_quad_supported(const DevLayout &L, const DevParams &P, int S) {
+  // (H <= 5: a point's 5 H + 4 <= 29 terms fit the 6-bit term field of the dense list's ids, quad_common.h)
   if (L.M != 1 || S != 0 || L.n > 32 || L.Ntot > 16 || L.Ntot < 2 || L.H < 1 || L.H > 5) return false;
   return reford::q4_shared_bytes(L.Ntot) + 4 * reford::q4_team_bytes(P.mem_size) + reford::q4_dense_bytes() <= 160 * 1024;
 }
 size_t reference_order_quad_corridor_doubles(const DevLayout &L, int B) { return (size_t)B * L.H * 4 * (L.Kmax + 1) * 16; }
-// fills RefPlan for the QUAD shape: as many waves per workgroup (at most 4) and workgroups per CU as the LDS holds, eight waves
-// per CU at most (256 registers)
-void reference_order_quad_plan(const DevLayout &L, const DevParams &P, int B, int n_cu, RefPlan &pl) {
-  // (a wave: its four rows and its list of active terms)
-  const size_t shared = reford::q4_shared_bytes(L.Ntot), team = reford::q4_team_bytes(P.mem_size) + (reford::q4_dense_bytes() + 3) / 4, budget = 160 * 1024;
-  int best_w = 1, best_wg = 1, best_res = 0;
-  for (int w = std::min(4, reford::kQ4WavesPerCU); w >= 1; w--) {
-    const size_t lds = shared + (size_t)w * 4 * team;
-    if (lds > budget) continue;
-    const int wg = (int)std::min<size_t>((size_t)(reford::kQ4WavesPerCU / w), budget / lds);
-    if (wg * w >= best_res) { // ties: the smaller workgroup (it leaves sooner at the end of a launch)
-      best_res = wg * w;
-      best_w = w;
-      best_wg = wg;
-    }
-  }
-  if (const char *e = std::getenv("DFTPAV_REF_QUAD_WAVES")) { // developer knob: waves per workgroup
-    const int w = std::atoi(e);
-    if (w >= 1 && w <= 4 && shared + (size_t)w * 4 * team <= budget) {
-      best_w = w;
-      best_wg = (int)std::min<size_t>((size_t)(reford::kQ4WavesPerCU / w), budget / (shared + (size_t)w * 4 * team));
-    }
-  }
-  pl.quad = 1;
-  pl.wave = 1;
-  pl.threads = 64 * best_w;
-  pl.lds = shared + (size_t)best_w * 4 * team;
-  pl.wg_per_cu = best_wg;
-  // Persistent workgroups of a scheduled solve: a wave's rows are only refilled while the batch's ring holds waiting
-  // trajectories, so a launch takes HALF as many rows as the batch has trajectories (two per row) -- the rows stay busy until half
-  // of the batch is done, the rest gathers in ever fewer waves (slices), and the waves that leave make room for the next batch's
-  // launch on another stream.  Measured on the bench's stream of 4096-batches, four in flight (gpurun_out/q4.log, round 6): 256 / 512 /
-  // 768 waves per launch -> 22.7 / 28.0 / 27.1 k solves/s; a launch as wide as the device (every trajectory its own row from the
-  // start, no refill): 19.3 k.
-  const int per_wg = 4 * best_w;
-  pl.slots = std::max(1, std::min(n_cu * best_wg, (B + 2 * per_wg - 1) / (2 * per_wg)));
-  pl.slice = 64; // evaluations between two visits to the ring (64 / 256: 28.0 / 26.0 k solves/s)
-  pl.slots_wide = n_cu * best_wg; // a batch with the device to itself: every wave slot
-  pl.hand = 768;                  // ... and its last trajectories finish in the WAVE shape (launch_ref, capi.cpp)
-  if (const char *e = std::getenv("DFTPAV_REF_QUAD_HANDOVER")) pl.hand = std::max(0, std::atoi(e));
-  if (const char *e = std::getenv("DFTPAV_REF_SLICE")) pl.slice = std::atoi(e);
-  if (const char *e = std::getenv("DFTPAV_REF_SLOTS")) pl.slots = pl.slots_wide = std::max(1, std::atoi(e)); // developer knob: persistent workgroups
+// the QUAD shape's LDS (a row: its part of a wave and a quarter of the wave's list of active terms), eight waves per CU at most
+// (256 registers); a batch alone on the device hands its last 768 trajectories to the WAVE shape
+QuadSizes reference_order_quad_sizes(const DevLayout &L, const DevParams &P) {
+  return {reford::q4_shared_bytes(L.Ntot), reford::q4_team_bytes(P.mem_size) + (reford::q4_dense_bytes() + 3) / 4, reford::kQ4WavesPerCU, 768};
 }
 hipError_t launch_quad_corridor(const DevBatch &D, double *cor_t, hipStream_t stream) {
   const DevLayout &L = D.L;
@@ -1324,33 +1284,6 @@ hipError_t launch_quad_corridor(const DevBatch &D, double *cor_t, hipStream_t st
   hipLaunchKernelGGL(reford::q4_corridor_kernel, dim3(grid), dim3(256), 0, stream, D.corridor, cor_t, D.B, L.H * 4, D.NptsPad, L.Ntot, L.K, L.Kd, L.Kmax + 1);
   return hipGetLastError();
 }
-// scheduled != 0: a solve whose rows pop from the batch's ring (the caller has reset it)
-// slots: persistent workgroups of this launch; hand: unfinished trajectories at which the waves leave theirs to a follow-up launch
-hipError_t launch_solver_ref4(const DevBatch &D, const DevBatch *d_dev, int mode, const double *tabs, const double *cor_t, double *scratch, const RefPlan &pl,
-                              int scheduled, int slots, int hand, hipStream_t stream) {
-  const int W = pl.threads / 64;
-  int grid = (D.B + 4 * W - 1) / (4 * W), source = 0, slice = 0;
-  if (scheduled && mode == kModeSolve) {
-    grid = slots < grid ? slots : grid;
-    source = 1;
-    slice = pl.slice;
-  } else {
-    hand = 0;
-  }
-  if (const char *e = std::getenv("DFTPAV_REF_EXACT_DIV"))
-    if (std::atoi(e) != 0) source |= 2;
-  if (std::getenv("DFTPAV_VERBOSE"))
-    std::fprintf(stderr, "[dftpav] reference order, QUAD shape: grid %d x %d threads, %zu B of LDS, source %d slice %d hand-over at %d\n", grid, pl.threads, pl.lds, source, slice, hand);
-  const bool fast = D.L.H == 4 && D.epis == 0.0 && !std::getenv("DFTPAV_REF_QUAD_GENERIC"); // the live path's constants (q4_eval)
-  bool dense = true; // the active terms evaluated densely packed (DFTPAV_REF_QUAD_DENSE=0: in place, as until late in round 6)
-  if (const char *e = std::getenv("DFTPAV_REF_QUAD_DENSE")) dense = std::atoi(e) != 0;
-  using Kern = void (*)(const DevBatch *, int, const double *, const double *, double *, int, int, int);
-  const Kern fn = fast ? (dense ? &reford::ref4_kernel<true, true> : &reford::ref4_kernel<true, false>)
-                       : (dense ? &reford::ref4_kernel<false, true> : &reford::ref4_kernel<false, false>);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(fn, dim3(grid), dim3(pl.threads), pl.lds, stream, d_dev, mode, tabs, cor_t, scratch, source, slice, hand);
-  return hipGetLastError();
-}
+QuadKernel ref4_kernel_for(bool fast) { return fast ? &reford::ref4_kernel<true> : &reford::ref4_kernel<false>; }
 
 } // namespace dftpav

@@ -1162,71 +1162,17 @@ bool reference_order_quadm_supported(const DevLayout &L, const DevParams &P, int
     if (L.piece_nums[i] < 2) return false;
   return reford::q4m_shared_bytes(L) + 4 * reford::q4m_team_bytes(P.mem_size) <= 160 * 1024;
 }
-void reference_order_quadm_plan(const DevLayout &L, const DevParams &P, int B, int n_cu, RefPlan &pl) {
-  const size_t shared = reford::q4m_shared_bytes(L), team = reford::q4m_team_bytes(P.mem_size), budget = 160 * 1024;
-  int best_w = 1, best_wg = 1, best_res = 0;
-  for (int w = 4; w >= 1; w--) {
-    const size_t lds = shared + (size_t)w * 4 * team;
-    if (lds > budget) continue;
-    const int wg = (int)std::min<size_t>((size_t)(4 / w), budget / lds);
-    if (wg * w >= best_res) {
-      best_res = wg * w;
-      best_w = w;
-      best_wg = wg;
-    }
-  }
-  if (const char *e = std::getenv("DFTPAV_REF_QUAD_WAVES")) { // developer knob: waves per workgroup
-    const int w = std::atoi(e);
-    if (w >= 1 && w <= 4 && shared + (size_t)w * 4 * team <= budget) {
-      best_w = w;
-      best_wg = (int)std::min<size_t>((size_t)(4 / w), budget / (shared + (size_t)w * 4 * team));
-    }
-  }
-  pl.quad = 2;
-  pl.wave = 1;
-  pl.threads = 64 * best_w;
-  pl.lds = shared + (size_t)best_w * 4 * team;
-  pl.wg_per_cu = best_wg;
-  const int per_wg = 4 * best_w;
-  pl.slots = std::max(1, std::min(n_cu * best_wg, (B + 2 * per_wg - 1) / (2 * per_wg)));
-  pl.slice = 64;
-  pl.slots_wide = n_cu * best_wg;
-  pl.hand = 2048; // (a batch alone on the device, configs[1] at 4096: 401 ms with the hand-over at 768 unfinished trajectories, 386 at 1280, 373-390 at 2048)
-  if (const char *e = std::getenv("DFTPAV_REF_QUAD_HANDOVER")) pl.hand = std::max(0, std::atoi(e));
-  if (const char *e = std::getenv("DFTPAV_REF_SLICE")) pl.slice = std::atoi(e);
-  if (const char *e = std::getenv("DFTPAV_REF_SLOTS")) pl.slots = pl.slots_wide = std::max(1, std::atoi(e));
-}
+// the LDS of the QUAD shape for several segments, four waves per CU at most (one per SIMD); a batch alone on the device hands its last
+// 2048 trajectories to the WAVE shape (configs[1] at 4096: 401 ms with the hand-over at 768 unfinished trajectories, 386 at 1280, 373-390 at 2048)
+QuadSizes reference_order_quadm_sizes(const DevLayout &L, const DevParams &P) { return {reford::q4m_shared_bytes(L), reford::q4m_team_bytes(P.mem_size), 4, 2048}; }
 hipError_t launch_quadm_corridor(const DevBatch &D, double *cor_t, hipStream_t stream) {
   const size_t total = (size_t)D.B * D.L.H * 4 * (D.L.Kmax + 1) * 16;
   const int grid = (int)std::min<size_t>((total + 255) / 256, 65536);
   hipLaunchKernelGGL(reford::q4m_corridor_kernel, dim3(grid), dim3(256), 0, stream, D.corridor, cor_t, D.B, D.NptsPad, D.L);
   return hipGetLastError();
 }
-hipError_t launch_solver_ref4m(const DevBatch &D, const DevBatch *d_dev, int mode, const double *tabs, const double *cor_t, double *scratch, const RefPlan &pl,
-                               int scheduled, int slots, int hand, hipStream_t stream) {
-  const int W = pl.threads / 64;
-  int grid = (D.B + 4 * W - 1) / (4 * W), source = 0, slice = 0;
-  if (scheduled && mode == kModeSolve) {
-    grid = slots < grid ? slots : grid;
-    source = 1;
-    slice = pl.slice;
-  } else {
-    hand = 0;
-  }
-  if (const char *e = std::getenv("DFTPAV_REF_EXACT_DIV"))
-    if (std::atoi(e) != 0) source |= 2;
-  if (std::getenv("DFTPAV_VERBOSE"))
-    std::fprintf(stderr, "[dftpav] reference order, QUAD shape (several segments): grid %d x %d threads, %zu B of LDS, source %d slice %d hand-over at %d\n", grid,
-                 pl.threads, pl.lds, source, slice, hand);
-  const bool fast = D.L.H == 4 && D.epis == 0.0 && !std::getenv("DFTPAV_REF_QUAD_GENERIC");
-  const bool tail1 = D.L.n == 33 && !std::getenv("DFTPAV_REF_QUAD_GENERIC");
-  using Kern = void (*)(const DevBatch *, int, const double *, const double *, double *, int, int, int);
-  const Kern fn = fast ? (tail1 ? &reford::ref4m_kernel<true, 1> : &reford::ref4m_kernel<true, 16>)
-                       : (tail1 ? &reford::ref4m_kernel<false, 1> : &reford::ref4m_kernel<false, 16>);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(fn, dim3(grid), dim3(pl.threads), pl.lds, stream, d_dev, mode, tabs, cor_t, scratch, source, slice, hand);
-  return hipGetLastError();
+QuadKernel ref4m_kernel_for(bool fast, bool tail1) {
+  return fast ? (tail1 ? &reford::ref4m_kernel<true, 1> : &reford::ref4m_kernel<true, 16>) : (tail1 ? &reford::ref4m_kernel<false, 1> : &reford::ref4m_kernel<false, 16>);
 }
 
 } // namespace dftpav

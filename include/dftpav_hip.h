@@ -325,7 +325,11 @@ int dftpav_batch_upload(dftpav_batch *b, const dftpav_batch_data *d);
  *   configs[1], the reference's live layouts -- the same shape with the segments' pieces side by side on a row (solver_ref4m.hip;
  *   22-25 k solves/s on such a stream); everything else one WAVE per trajectory, eight per CU (solver_ref.hip).  A batch that has
  *   the device to itself (the default; dftpav_batch_set_hand_over(b, 0) announces others behind it) takes every wave slot and
- *   hands its last trajectories to the WAVE shape.  Every shape returns the same bits. */
+ *   hands its last trajectories to the WAVE shape.  Every shape returns the same bits.
+ *   The launch plan is chosen here, once, and every later launch of the batch follows it.  The developer options of this mode
+ *   (DFTPAV_REF_SHAPE, _WAVES, _THREADS, _QUAD_WAVES, _QUAD_HANDOVER, _SLICE, _SLOTS, _EXACT_DIV and DFTPAV_VERBOSE) are read
+ *   then: a change of them applies from the next call that chooses the reference order (a call that finds the batch in it, with
+ *   the same number of obstacles, changes nothing).  On an error the batch keeps its order and plan as they were. */
 #define DFTPAV_ORDER_DEVICE 0
 #define DFTPAV_ORDER_REFERENCE 1
 int dftpav_batch_set_order(dftpav_batch *b, int order);
