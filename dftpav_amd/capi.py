@@ -35,6 +35,7 @@ EXPORTS = [
     "dftpav_batch_trace", "dftpav_batch_get_trace", "dftpav_plan_cycle", "dftpav_plan_cycle_fetch", "dftpav_batch_create_shaped",
     "dftpav_batch_set_order", "dftpav_batch_get_order", "dftpav_batch_trace_range", "dftpav_batch_get_trace_of",
     "dftpav_comm_available", "dftpav_comm_unique_id", "dftpav_comm_create", "dftpav_comm_destroy", "dftpav_comm_share", "dftpav_comm_layout", "dftpav_batch_allgather_results",
+    "dftpav_default_search_params", "dftpav_kino_search",
 ]
 
 
@@ -185,6 +186,23 @@ class Handle:
                        ptr(out["length"]), ptr(out["type"]), ptr(out["seg"]), ptr(out["samples"]), ptr(out["n_samples"]),
                        ptr(out["collides"])), "reeds_shepp_shots")
         return out
+
+    def kino_search(self, start_states, end_states, start_ctrl=None, sp=None, max_nodes=512, max_path=4096):
+        """getKinoPath (KinoAstar::search with its 2D retry) + getKinoNode up to SampleTraj on the device for n queries on the
+        installed grid map: dict(status, shot_success, used_3d, budget_hit, iters, nodes_used, n_nodes, nodes [n][max_nodes][6],
+        path_len, paths [n][max_path][3]) -- paths / path_len are what frontend_resample takes."""
+        from .pods import SearchOut, SearchParams
+        st = np.ascontiguousarray(start_states, dtype=np.float64).reshape(-1, 4)
+        en = np.ascontiguousarray(end_states, dtype=np.float64).reshape(-1, 4)
+        n = st.shape[0]
+        ct = np.ascontiguousarray(start_ctrl if start_ctrl is not None else np.zeros((n, 2)), dtype=np.float64).reshape(-1, 2)
+        sp = sp if sp is not None else SearchParams.default()
+        out = SearchOut(n, max_nodes, max_path)
+        fn = lib().dftpav_kino_search
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        self._check(fn(self._h, C.byref(sp), st.ctypes.data_as(C.c_void_p), ct.ctypes.data_as(C.c_void_p),
+                       en.ctypes.data_as(C.c_void_p), n, C.byref(out.c)), "kino_search")
+        return out.arrays()
 
     def comm_create(self, nranks, rank, unique_id):
         """ncclCommInitRank on this handle's device, collectively (dftpav_comm_create); unique_id: the 128 bytes of comm_unique_id()

@@ -25,6 +25,8 @@
 #include "e4_plan.h"
 #include "traj_math.h"
 #include "cr_trig.h"
+#include "rs_math.h"
+#include "search_args.h"
 
 namespace dftpav {
 hipError_t launch_solver(const DevBatch &D, const DevBatch *d_dev, int mode, int threads, int grid, SchedArgs sched,
@@ -49,6 +51,7 @@ hipError_t launch_shots(const double *from, const double *to, int n, double rho,
                         const unsigned char *cells, int size_x, int size_y, double resolution, double origin_x, double origin_y,
                         double veh_width, double veh_length, double veh_dcr, const double *v_tab, int n_v, double *length, int *type,
                         double *seg, double *samples, int *n_samples, int *collides, hipStream_t stream);
+hipError_t launch_search(const SearchArgs &A, int blocks, hipStream_t stream);
 hipError_t launch_corridor_layout(const double *raw, double *out, int B, int Npts, int H, int NptsPad, hipStream_t stream);
 hipError_t launch_adopt(const DevBatch &D, const DevBatch &prev, hipStream_t stream);
 // solver_ref.hip: the same path in the reference's own floating-point order
@@ -110,6 +113,9 @@ struct dftpav_handle {
   int comm_ranks = 0, comm_rank = 0;
   unsigned char *d_comm_send = nullptr;
   size_t comm_send_bytes = 0;
+  // workspace of dftpav_kino_search (node pools, heaps, hash tables of the queries in flight), grown on demand
+  void *d_search_ws = nullptr;
+  size_t search_ws_bytes = 0;
 };
 
 struct dftpav_batch {
@@ -440,6 +446,7 @@ extern "C" void dftpav_destroy(dftpav_handle *h) {
   if (h->d_cells) (void)hipFree(h->d_cells);
   if (h->d_bits) (void)hipFree(h->d_bits);
   if (h->d_dl) (void)hipFree(h->d_dl);
+  if (h->d_search_ws) (void)hipFree(h->d_search_ws);
   for (hipEvent_t &e : h->mark)
     if (e) (void)hipEventDestroy(e);
   if (h->cev0) (void)hipEventDestroy(h->cev0);
@@ -696,6 +703,214 @@ extern "C" int dftpav_reeds_shepp_shots(dftpav_handle *h, const double *from, co
   for (void *p : {(void *)d_from, (void *)d_to, (void *)d_len, (void *)d_seg, (void *)d_smp, (void *)d_v, (void *)d_type, (void *)d_ns,
                   (void *)d_col})
     if (p) (void)hipFree(p);
+  return rc;
+}
+
+// ------------------------------------------------- hybrid A* front-end search (search.hip)
+extern "C" void dftpav_default_search_params(dftpav_search_params *sp) {
+  std::memset(sp, 0, sizeof(*sp));
+  // config/minco_config.pb.txt:13-59 (map_cfg), :81 (max_frontend_cur); kino_astar.h:167; kino_astar.cpp:426-427
+  sp->map_size_x = 1000.0;
+  sp->map_size_y = 1000.0;
+  sp->map_resl = 0.3;
+  sp->phi_grid_resolution = 0.3;
+  sp->lambda_heu = 5.0;
+  sp->tie_breaker = 1.0 + 1.0 / 10000;
+  sp->allocate_num = 100000;
+  sp->check_num = 5;
+  sp->step_arc = 0.9;
+  sp->max_frontend_cur = 1.0;
+  sp->checkl = 0.2;
+  sp->traj_forward_penalty = 1.0;
+  sp->traj_back_penalty = 2.5;
+  sp->traj_gear_switch_penalty = 15.0;
+  sp->traj_steer_penalty = 0.5;
+  sp->traj_steer_change_penalty = 0.0;
+  sp->veh_width = 1.90 + 0.2;
+  sp->veh_length = 4.88 + 0.2;
+  sp->veh_d_cr = 1.015;
+  sp->wheel_base = 2.85;
+  sp->vertex_res = 0.1;
+  sp->max_iters = 20000;
+  sp->use3d = 1;
+  sp->retry_2d = 1;
+}
+
+// the inputs of one expansion as the reference's loops build them (kino_astar.cpp:143-171): running sums, tabulated here
+static int search_inputs(const dftpav_search_params &sp, double max_steer, int which, double *tab) {
+  const double res = 0.5;
+  int n = 0;
+  auto steers = [&](double arc) {
+    for (double steer = -max_steer; steer <= max_steer + 1e-3; steer += res * max_steer * 1.0) {
+      if (n < kSearchMaxIn) {
+        tab[2 * n] = steer;
+        tab[2 * n + 1] = arc;
+      }
+      if (++n > 4 * kSearchMaxIn) return;
+    }
+  };
+  if (which == 0) {
+    for (double arc = sp.map_resl; arc <= 2 * sp.map_resl + 1e-3 && n <= kSearchMaxIn; arc += sp.map_resl) steers(arc);
+  } else if (which == 1) {
+    for (double arc = -sp.map_resl; arc >= -2 * sp.map_resl - 1e-3 && n <= kSearchMaxIn; arc -= sp.map_resl) steers(arc);
+  } else {
+    for (double arc = -sp.step_arc; arc <= sp.step_arc + 1e-3 && n <= kSearchMaxIn; arc += 0.5 * sp.step_arc) {
+      if (std::fabs(arc) < 1.0e-2) continue;
+      steers(arc);
+    }
+  }
+  return n;
+}
+
+extern "C" int dftpav_kino_search(dftpav_handle *h, const dftpav_search_params *sp, const double *start_states,
+                                  const double *start_ctrl, const double *end_states, int n, const dftpav_search_out *out) {
+  (void)start_ctrl; // kept by search (kino_astar.cpp:54) for getKinoNode's flat states: dftpav_frontend_resample takes it
+  if (!h || !sp || !out || n < 0 || out->max_nodes < 0 || out->max_path < 0) return DFTPAV_E_INVALID;
+  if (!h->d_cells) return DFTPAV_E_INVALID; // no map
+  if (n == 0) return DFTPAV_OK;
+  if (!start_states || !end_states || !out->status || !out->shot_success || !out->used_3d || !out->budget_hit || !out->iters ||
+      !out->nodes_used || !out->n_nodes || !out->path_len || (out->max_nodes > 0 && !out->nodes) || (out->max_path > 0 && !out->paths))
+    return DFTPAV_E_INVALID;
+  const dftpav_search_params &P = *sp;
+  if (P.allocate_num < 2 || P.check_num < 1 || P.max_iters < 0 || !(P.map_resl > 0.0) || !(P.phi_grid_resolution > 0.0) ||
+      !(P.step_arc > 0.0) || !(P.max_frontend_cur > 0.0) || !(P.checkl > 0.0) || !(P.vertex_res > 0.0) || !(P.wheel_base > 0.0))
+    return DFTPAV_E_INVALID;
+  // the tables of the running sums: inputs, outline point spacing, shot sample offsets
+  const double max_steer = crt::atan(P.wheel_base * P.max_frontend_cur); // kino_astar.cpp:419 (correctly rounded)
+  std::vector<double> in_tab(3 * kSearchMaxIn * 2, 0.0);
+  int n_in[3];
+  for (int w = 0; w < 3; w++) {
+    n_in[w] = search_inputs(P, max_steer, w, in_tab.data() + (size_t)w * kSearchMaxIn * 2);
+    if (n_in[w] > kSearchMaxIn || n_in[w] * P.check_num > kSearchThreads) return DFTPAV_E_UNSUPPORTED;
+  }
+  if (P.check_num > kSearchMaxCheck) return DFTPAV_E_UNSUPPORTED;
+  std::vector<double> vv;
+  const double longest = std::max(P.veh_length, P.veh_width) + 1.0;
+  for (double dl = P.vertex_res; dl < longest; dl += P.vertex_res) vv.push_back(dl);
+  if (vv.empty()) vv.push_back(longest);
+  // a shot is tried within 15 m of the goal (kino_astar.cpp:90); an LSL path, which always exists, is no longer than
+  // d + 2 r + 4 pi r, and the shortest path is no longer than it.  getKinoNode's second shot starts from a pose of the
+  // terminal node's last arc: one step_arc more.  The table holds every offset up to that bound and a margin.
+  const double rho = 1.0 / P.max_frontend_cur;
+  const double bound = 15.0 + std::max(P.step_arc, 2 * P.map_resl) + (2.0 + 4.0 * rs::kPi) * rho;
+  const double n_l_need = bound / P.checkl + 8.0;
+  if (!(n_l_need < (double)kSearchMaxShot)) return DFTPAV_E_UNSUPPORTED;
+  std::vector<double> ll;
+  for (double l = 0.0; (int)ll.size() < (int)n_l_need; l += P.checkl) ll.push_back(l); // kino_astar.cpp:338, 594
+  HIPCHK(h, hipSetDevice(h->device));
+  if (!h->cev0) HIPCHK(h, hipEventCreate(&h->cev0));
+  if (!h->cev1) HIPCHK(h, hipEventCreate(&h->cev1));
+  // workspace per query in flight: node pool, heap (node, key, position), path list, hash table
+  int hcap = 1;
+  while (hcap < 2 * P.allocate_num) hcap <<= 1;
+  const size_t A = (size_t)P.allocate_num;
+  const size_t per = A * sizeof(SearchNode) + A * (3 * sizeof(int) + sizeof(double)) + (size_t)hcap * sizeof(int) + 256;
+  const size_t budget = (size_t)6 << 30; // 6 GiB of workspace at most: the queries beyond run in further launches
+  int slots = (int)std::min<size_t>((size_t)n, std::max<size_t>(1, budget / per));
+  const size_t ws = per * slots;
+  if (h->search_ws_bytes < ws) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->d_search_ws) (void)hipFree(h->d_search_ws);
+    h->d_search_ws = nullptr;
+    h->search_ws_bytes = 0;
+    HIPCHK(h, hipMalloc(&h->d_search_ws, ws));
+    h->search_ws_bytes = ws;
+  }
+  unsigned char *w = (unsigned char *)h->d_search_ws;
+  auto take = [&](size_t bytes) {
+    void *p = w;
+    w += (bytes + 255) / 256 * 256;
+    return p;
+  };
+  SearchArgs S{};
+  S.pool = (SearchNode *)take(A * slots * sizeof(SearchNode));
+  S.h_node = (int *)take(A * slots * sizeof(int));
+  S.h_pos = (int *)take(A * slots * sizeof(int));
+  S.path_idx = (int *)take(A * slots * sizeof(int));
+  S.h_key = (double *)take(A * slots * sizeof(double));
+  S.table = (int *)take((size_t)hcap * slots * sizeof(int));
+  S.hcap = hcap;
+  S.sp = P;
+  S.cells = h->d_cells;
+  S.size_x = h->map.size_x;
+  S.size_y = h->map.size_y;
+  S.resolution = h->map.resolution;
+  S.origin_x = h->map.origin_x;
+  S.origin_y = h->map.origin_y;
+  S.inv_yaw_res = 1.0 / P.phi_grid_resolution; // kino_astar.cpp:421
+  S.origin_sx = -0.5 * P.map_size_x;
+  S.origin_sy = -0.5 * P.map_size_y;
+  S.half_size_x = P.map_size_x * 0.5;
+  S.half_size_y = P.map_size_y * 0.5;
+  S.rho = rho;
+  for (int k = 0; k < 3; k++) S.n_in[k] = n_in[k];
+  S.n = n;
+  int rc = DFTPAV_OK;
+  auto chk = [&](hipError_t e) {
+    if (e != hipSuccess && rc == DFTPAV_OK) {
+      h->err = hipGetErrorString(e);
+      rc = DFTPAV_E_HIP;
+    }
+  };
+  const size_t nn = (size_t)n;
+  double *d_tabs = nullptr, *d_st = nullptr, *d_en = nullptr, *d_nodes = nullptr, *d_paths = nullptr;
+  int *d_ints = nullptr;
+  const size_t ntab = in_tab.size() + vv.size() + ll.size();
+  chk(hipMalloc(&d_tabs, sizeof(double) * ntab));
+  chk(hipMalloc(&d_st, sizeof(double) * 4 * nn));
+  chk(hipMalloc(&d_en, sizeof(double) * 4 * nn));
+  chk(hipMalloc(&d_ints, sizeof(int) * 9 * nn));
+  if (out->max_nodes > 0) chk(hipMalloc(&d_nodes, sizeof(double) * 6 * nn * out->max_nodes));
+  if (out->max_path > 0) chk(hipMalloc(&d_paths, sizeof(double) * 3 * nn * out->max_path));
+  if (rc == DFTPAV_OK) {
+    std::vector<double> tabs(in_tab);
+    tabs.insert(tabs.end(), vv.begin(), vv.end());
+    tabs.insert(tabs.end(), ll.begin(), ll.end());
+    chk(hipMemcpyAsync(d_tabs, tabs.data(), sizeof(double) * ntab, hipMemcpyHostToDevice, h->stream));
+    chk(hipMemcpyAsync(d_st, start_states, sizeof(double) * 4 * nn, hipMemcpyHostToDevice, h->stream));
+    chk(hipMemcpyAsync(d_en, end_states, sizeof(double) * 4 * nn, hipMemcpyHostToDevice, h->stream));
+    // rows past n_nodes / path_len read back as zeros
+    if (d_nodes) chk(hipMemsetAsync(d_nodes, 0, sizeof(double) * 6 * nn * out->max_nodes, h->stream));
+    if (d_paths) chk(hipMemsetAsync(d_paths, 0, sizeof(double) * 3 * nn * out->max_path, h->stream));
+    S.in_tab = d_tabs;
+    S.v_tab = d_tabs + in_tab.size();
+    S.n_v = (int)vv.size();
+    S.l_tab = d_tabs + in_tab.size() + vv.size();
+    S.n_l = (int)ll.size();
+    S.start = d_st;
+    S.end = d_en;
+    int *const fields[9] = {out->status, out->shot_success, out->used_3d, out->budget_hit, out->iters, out->nodes_used,
+                            out->n_nodes, out->path_len, nullptr};
+    dftpav_search_out &O = S.out;
+    O.max_nodes = out->max_nodes;
+    O.max_path = out->max_path;
+    O.status = d_ints;
+    O.shot_success = d_ints + nn;
+    O.used_3d = d_ints + 2 * nn;
+    O.budget_hit = d_ints + 3 * nn;
+    O.iters = d_ints + 4 * nn;
+    O.nodes_used = d_ints + 5 * nn;
+    O.n_nodes = d_ints + 6 * nn;
+    O.path_len = d_ints + 7 * nn;
+    O.nodes = d_nodes;
+    O.paths = d_paths;
+    chk(hipEventRecord(h->cev0, h->stream));
+    for (int q0 = 0; q0 < n && rc == DFTPAV_OK; q0 += slots) {
+      S.q0 = q0;
+      chk(launch_search(S, std::min(slots, n - q0), h->stream));
+    }
+    chk(hipEventRecord(h->cev1, h->stream));
+    for (int f = 0; f < 8; f++) chk(hipMemcpyAsync(fields[f], d_ints + f * nn, sizeof(int) * nn, hipMemcpyDeviceToHost, h->stream));
+    if (d_nodes) chk(hipMemcpyAsync(out->nodes, d_nodes, sizeof(double) * 6 * nn * out->max_nodes, hipMemcpyDeviceToHost, h->stream));
+    if (d_paths) chk(hipMemcpyAsync(out->paths, d_paths, sizeof(double) * 3 * nn * out->max_path, hipMemcpyDeviceToHost, h->stream));
+    chk(hipStreamSynchronize(h->stream));
+    h->ctimed = rc == DFTPAV_OK;
+  }
+  for (void *p : {(void *)d_tabs, (void *)d_st, (void *)d_en, (void *)d_ints, (void *)d_nodes, (void *)d_paths})
+    if (p) (void)hipFree(p);
+  if (rc == DFTPAV_OK)
+    for (int q = 0; q < n; q++)
+      if (out->status[q] == 0) return DFTPAV_E_UNSUPPORTED; // a shot beyond the sample table (not reached: see the bound)
   return rc;
 }
 

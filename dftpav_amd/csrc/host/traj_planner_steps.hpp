@@ -7,6 +7,8 @@
 //   map_itf_->GetObstacleMap(&grid_map)             MGR:1216           setObstacleMap(cells, size_x, size_y, resolution, origin)
 //   KinoAstar::getKinoNode(flat_trajs) + the        KA:606-743,        getKinoNode(SampleTraj, start_state, end_state, start_ctrl)
 //     resampling loop of RunMINCOParking            MGR:531-568          -> std::vector<FlatTrajData> (one per gear segment)
+//   KinoAstar::search + getKinoNode up to SampleTraj KA:37-301,554-612 search(start_state, init_ctrl, end_state, SampleTraj)
+//     as getKinoPath runs them (3D, 2D retry)       MGR:69-117
 //   KinoAstar::computeShotTraj / is_shot_sucess     KA:304-345         computeShotTraj(state1, state2, path_list, len) / is_shot_sucess(state1, state2)
 //   TrajPlanner::getRectangleConst(statelist)       MGR:1213-1469      getRectangleConst(statelist) -> hPolys_
 //   TrajPlanner::ConverSurroundTrajFromPoints(...)  MGR:743-789        ConverSurroundTrajFromPoints(sur_trajs) (installs them)
@@ -117,6 +119,26 @@ class TrajPlannerSteps {
       for (const auto &s : t) st.insert(st.end(), {s.x, s.y, s.angle, s.velocity, s.acceleration, s.curvature, s.time_stamp});
     }
     return ok(dftpav_fit_surround(h_, st.data(), (int)sur_trajs.size(), (int)n));
+  }
+
+  // KinoAstar::search as getKinoPath runs it (3D, then the 2D retry) followed by getKinoNode up to SampleTraj, one query:
+  // returns the reference's status (DFTPAV_SEARCH_REACH_END / _NO_PATH, or a negative DFTPAV_E_* code); SampleTraj is what
+  // getKinoNode above takes
+  int search(const std::array<double, 4> &start_state, const std::array<double, 2> &init_ctrl, const std::array<double, 4> &end_state,
+             std::vector<std::array<double, 3>> &SampleTraj, const dftpav_search_params *sp = nullptr) {
+    dftpav_search_params d;
+    dftpav_default_search_params(&d);
+    if (!sp) sp = &d;
+    SampleTraj.clear();
+    for (int cap = 4096;; cap *= 4) {
+      int st = 0, shot = 0, u3 = 0, bud = 0, it = 0, used = 0, nn = 0, len = 0;
+      std::vector<double> path((size_t)cap * 3);
+      dftpav_search_out out{0, cap, &st, &shot, &u3, &bud, &it, &used, &nn, nullptr, &len, path.data()};
+      if (!ok(dftpav_kino_search(h_, sp, start_state.data(), init_ctrl.data(), end_state.data(), 1, &out))) return err_;
+      if (len > cap) continue; // the path did not fit: again with room for it
+      for (int i = 0; i < len; i++) SampleTraj.push_back({path[3 * i], path[3 * i + 1], path[3 * i + 2]});
+      return st;
+    }
   }
 
   // the Reeds-Shepp shot from a pose to the goal (turning radius 1 / max_cur, samples every checkl)

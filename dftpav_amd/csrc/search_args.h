@@ -1,0 +1,41 @@
+// search_args.h — what the host half of dftpav_kino_search (capi.cpp) hands the search kernel (search.hip).
+#pragma once
+#include "../../include/dftpav_hip.h"
+
+namespace dftpav {
+
+constexpr int kSearchThreads = 256; // one workgroup per query
+constexpr int kSearchMaxIn = 32;    // inputs per expansion
+constexpr int kSearchMaxCheck = 8;  // check_num
+constexpr int kSearchMaxShot = 1024; // shot sample offsets in the table
+
+struct SearchNode { // PathNode, kino_astar.h:42-61
+  double x, y, yaw, g, f, steer, arc;
+  int parent, ix, iy, yaw_idx, singul;
+  int state;
+};
+
+struct SearchArgs {
+  dftpav_search_params sp;
+  const unsigned char *cells;
+  int size_x, size_y;
+  double resolution, origin_x, origin_y;
+  const double *v_tab; // outline point spacing: vertex_res, + vertex_res, ...
+  int n_v;
+  const double *l_tab; // shot sample offsets: 0, checkl, checkl + checkl, ...
+  int n_l;
+  const double *in_tab; // [3][kSearchMaxIn][2] (steer, arc): first expansion forward, backward, later expansions
+  int n_in[3];
+  double inv_yaw_res, origin_sx, origin_sy, half_size_x, half_size_y, rho; // origin_ = -0.5 map_size (kino_astar.cpp:408-409)
+  const double *start, *end; // [n][4]
+  int q0, n;
+  // workspace, per slot (query in flight)
+  SearchNode *pool;
+  int *h_node, *h_pos, *path_idx; // [slots][allocate_num]
+  double *h_key;
+  int *table; // [slots][hcap]
+  int hcap;
+  dftpav_search_out out; // device pointers
+};
+
+} // namespace dftpav

@@ -202,3 +202,48 @@ class FrontendOut:
         return dict(n_seg=self.n_seg, singul=self.singul, piece_nums=self.piece_nums, piece_dt=self.piece_dt,
                     ini_states=self.ini_states, fin_states=self.fin_states, inner_pts=self.inner_pts, n_states=self.n_states,
                     states=self.states)
+
+
+class SearchParams(C.Structure):
+    """dftpav_search_params (include/dftpav_hip.h): the map_cfg / opt_cfg values of KinoAstar::init (kino_astar.cpp:372-442),
+    defaults of minco_config.pb.txt:13-59,81 and the vehicle of semantics.h with the search's +0.2 m margin."""
+    _fields_ = [("map_size_x", C.c_double), ("map_size_y", C.c_double), ("map_resl", C.c_double),
+                ("phi_grid_resolution", C.c_double), ("lambda_heu", C.c_double), ("tie_breaker", C.c_double),
+                ("allocate_num", C.c_int), ("check_num", C.c_int), ("step_arc", C.c_double), ("max_frontend_cur", C.c_double),
+                ("checkl", C.c_double), ("traj_forward_penalty", C.c_double), ("traj_back_penalty", C.c_double),
+                ("traj_gear_switch_penalty", C.c_double), ("traj_steer_penalty", C.c_double),
+                ("traj_steer_change_penalty", C.c_double), ("veh_width", C.c_double), ("veh_length", C.c_double),
+                ("veh_d_cr", C.c_double), ("wheel_base", C.c_double), ("vertex_res", C.c_double), ("max_iters", C.c_int),
+                ("use3d", C.c_int), ("retry_2d", C.c_int)]
+
+    @classmethod
+    def default(cls):
+        return cls(1000.0, 1000.0, 0.3, 0.3, 5.0, 1.0 + 1.0 / 10000, 100000, 5, 0.9, 1.0, 0.2, 1.0, 2.5, 15.0, 0.5, 0.0,
+                   1.90 + 0.2, 4.88 + 0.2, 1.015, 2.85, 0.1, 20000, 1, 1)
+
+    def copy(self, **kw):
+        c = type(self)()
+        C.pointer(c)[0] = self
+        for k, v in kw.items():
+            setattr(c, k, v)
+        return c
+
+
+class SearchOutC(C.Structure):
+    _fields_ = [("max_nodes", C.c_int), ("max_path", C.c_int)] + [(n, C.c_void_p) for n in (
+        "status", "shot_success", "used_3d", "budget_hit", "iters", "nodes_used", "n_nodes", "nodes", "path_len", "paths")]
+
+
+class SearchOut:
+    """Owner of the padded output arrays of dftpav_kino_search (and of the oracle's restatement)."""
+    INTS = ("status", "shot_success", "used_3d", "budget_hit", "iters", "nodes_used", "n_nodes")
+
+    def __init__(self, n, max_nodes=512, max_path=4096):
+        self.a = {k: np.zeros(n, dtype=np.int32) for k in self.INTS}
+        self.a["nodes"] = np.zeros((n, max_nodes, 6))
+        self.a["path_len"] = np.zeros(n, dtype=np.int32)
+        self.a["paths"] = np.zeros((n, max_path, 3))
+        self.c = SearchOutC(max_nodes, max_path, *[self.a[k].ctypes.data for k in self.INTS + ("nodes", "path_len", "paths")])
+
+    def arrays(self):
+        return dict(self.a)

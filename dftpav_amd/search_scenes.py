@@ -1,0 +1,97 @@
+"""Queries for the hybrid A* front end (dftpav_kino_search): small hand-made maps that each exercise one branch of
+KinoAstar::search (kino_astar.cpp:37-301), and goals on the reference's default arena that the direct shot cannot reach.
+
+Every scene is (name, grid [size_y][size_x] uint8 (80 = occupied), resolution, origin, start [4], goal [4]); start and
+goal are (x, y, yaw, v) as TrajPlanner::getKinoPath passes them (traj_manager.cpp:74)."""
+import numpy as np
+
+from . import scenarios as sc
+
+RES = 0.2
+ORIGIN = (-20.0, -20.0)
+SIZE = 200                      # 40 m x 40 m
+
+
+def _grid():
+    return np.full((SIZE, SIZE), 127, dtype=np.uint8)
+
+
+def _box(g, x0, y0, x1, y1):
+    """occupies the cells whose centres lie in [x0, x1] x [y0, y1]"""
+    xs = ORIGIN[0] + np.arange(SIZE) * RES
+    ys = ORIGIN[1] + np.arange(SIZE) * RES
+    ix = (xs >= x0 - 1e-9) & (xs <= x1 + 1e-9)
+    iy = (ys >= y0 - 1e-9) & (ys <= y1 + 1e-9)
+    g[np.ix_(iy, ix)] = 80
+    return g
+
+
+def empty():
+    """nothing in the way: a start at rest reaches the goal by the shot from the start node (iteration 0)"""
+    return "empty", _grid(), RES, ORIGIN, np.array([0.0, 0.0, 0.0, 0.0]), np.array([8.0, 3.0, 0.5, 0.0])
+
+
+def moving_start():
+    """a start moving forwards: the first expansion takes only the forward arcs map_resl and 2 map_resl (:143-151)"""
+    return "moving", _grid(), RES, ORIGIN, np.array([0.0, 0.0, 0.3, 1.5]), np.array([9.0, 2.0, 0.3, 0.0])
+
+
+def wall_gap():
+    """a wall across the way with a gap to one side: the shot from the start collides, the search goes round"""
+    g = _box(_grid(), 5.0, -20.0, 6.0, 3.0)
+    g = _box(g, 5.0, 9.0, 6.0, 20.0)
+    return "wall-gap", g, RES, ORIGIN, np.array([0.0, 0.0, 0.0, 0.0]), np.array([12.0, 0.0, 0.0, 0.0])
+
+
+def reverse():
+    """a goal behind a start that is rolling backwards: the first expansion is reverse only (:152-159)"""
+    g = _box(_grid(), -20.0, 3.0, 20.0, 4.0)
+    g = _box(g, -20.0, -4.0, 20.0, -3.0)
+    return "reverse", g, RES, ORIGIN, np.array([0.0, 0.0, 0.0, -1.0]), np.array([-8.0, 0.0, 0.0, 0.0])
+
+
+def enclosed():
+    """a start boxed in by walls (the goal outside): the open set runs dry, in 3D and in the 2D retry (:298-300)"""
+    g = _grid()
+    for x0, y0, x1, y1 in ((-3.5, -3.0, 5.5, -2.0), (-3.5, 2.0, 5.5, 3.0), (-3.5, -3.0, -2.5, 3.0), (4.5, -3.0, 5.5, 3.0)):
+        g = _box(g, x0, y0, x1, y1)
+    return "enclosed", g, RES, ORIGIN, np.array([0.0, 0.0, 0.0, 0.0]), np.array([12.0, 0.0, 0.0, 0.0])
+
+
+def occupied_start():
+    g = _box(_grid(), -1.0, -1.0, 1.0, 1.0)
+    return "occupied-start", g, RES, ORIGIN, np.array([0.0, 0.0, 0.0, 0.0]), np.array([10.0, 0.0, 0.0, 0.0])
+
+
+def occupied_goal():
+    g = _box(_grid(), 9.0, -1.0, 11.0, 1.0)
+    return "occupied-goal", g, RES, ORIGIN, np.array([0.0, 0.0, 0.0, 0.0]), np.array([10.0, 0.0, 0.0, 0.0])
+
+
+def small_scenes():
+    return [empty(), moving_start(), wall_gap(), reverse(), enclosed(), occupied_start(), occupied_goal()]
+
+
+# goals on the default arena (sc.default_sim_map): free poses near the ego vehicle whose direct shot from the ego start
+# collides (checked by tests/test_search_oracle.py)
+ARENA_GOALS = np.array([
+    [-62.7, 34.3, 0.0, 0.0],
+    [-44.4, 24.5, 2.8, 0.0],
+    [-63.5, 33.4, -2.9, 0.0],
+    [-50.4, 22.9, 0.6, 0.0],
+    [-43.8, 39.1, 1.5, 0.0],
+    [-45.3, 24.3, 2.6, 0.0],
+    [-43.3, 37.7, -0.8, 0.0],
+    [-44.9, 23.6, 2.8, 0.0],
+    [-43.6, 21.6, 0.0, 0.0],
+    [-61.5, 34.5, -2.4, 0.0],
+    [-50.0, 24.2, -2.1, 0.0],
+    [-47.0, 22.8, 3.0, 0.0],
+])
+
+
+def arena():
+    """(grid, resolution, origin, start [4], goals [k][4]) on the default arena, the ego vehicle at rest"""
+    grid, origin, res, ego = sc.default_sim_map()
+    start = np.array([ego[0], ego[1], ego[2], 0.0])
+    return grid, res, origin, start, ARENA_GOALS.copy()

@@ -581,6 +581,60 @@ int dftpav_reeds_shepp_shots(dftpav_handle *h, const double *from, const double 
                              int max_samples, double vertex_res, double *length, int *type, double *seg, double *samples,
                              int *n_samples, int *collides);
 
+/* ---- hybrid A* front-end search: a start pose and a goal to the searched path --------
+ * Replaces TrajPlanner::getKinoPath (traj_manager.cpp:69-117): KinoAstar::search (kino_astar.cpp:37-301) with its
+ * 3D-then-2D retry, then getKinoNode up to SampleTraj (kino_astar.cpp:554-612), for n independent queries on the map of
+ * dftpav_set_grid_map (cells outside the grid are free).  One deviation: the reference's wall-clock budget
+ * max_search_time (1.0 s, minco_config.pb.txt:50) is the iteration budget max_iters; when iter_num_ reaches it the
+ * reference's time-out branch is taken (kino_astar.cpp:115-132).  The default max_iters is a chosen number, not derived
+ * from the 1 s. */
+typedef struct dftpav_search_params {
+  double map_size_x, map_size_y;   /* 1000, 1000: origin_ = -0.5 map_size, the search's index frame (pb.txt:14-15, KA:404-409) */
+  double map_resl;                 /* 0.3   (pb.txt:57) */
+  double phi_grid_resolution;      /* 0.3   (pb.txt:51) */
+  double lambda_heu;               /* 5.0   (pb.txt:47) */
+  double tie_breaker;              /* 1 + 1 / 10000 (kino_astar.h:167) */
+  int allocate_num;                /* 100000 nodes (pb.txt:48) */
+  int check_num;                   /* 5     (pb.txt:49) */
+  double step_arc;                 /* 0.9   (pb.txt:58) */
+  double max_frontend_cur;         /* 1.0   (pb.txt:81): max_steer = atan(wheel_base * max_cur), shot radius 1 / max_cur */
+  double checkl;                   /* 0.2   (pb.txt:59) */
+  double traj_forward_penalty;     /* 1.0   (pb.txt:52) */
+  double traj_back_penalty;        /* 2.5   (pb.txt:53) */
+  double traj_gear_switch_penalty; /* 15.0  (pb.txt:54) */
+  double traj_steer_penalty;       /* 0.5   (pb.txt:55) */
+  double traj_steer_change_penalty;/* 0.0   (pb.txt:56) */
+  double veh_width, veh_length;    /* 1.90 + 0.2, 4.88 + 0.2: vp_ with its margin (semantics.h, kino_astar.cpp:426-427) */
+  double veh_d_cr, wheel_base;     /* 1.015, 2.85 (semantics.h) */
+  double vertex_res;               /* 0.1   outline point spacing (shapes.h:201) */
+  int max_iters;                   /* 20000 pops: stands for max_search_time (chosen, see above) */
+  int use3d;                       /* 1: the first search keys nodes on (x, y, yaw) cells (getKinoPath: true) */
+  int retry_2d;                    /* 1: a NO_PATH of a 3D search is searched again in 2D (traj_manager.cpp:87-103) */
+} dftpav_search_params;
+void dftpav_default_search_params(dftpav_search_params *sp);
+#define DFTPAV_SEARCH_REACH_END 2 /* KinoAstar's enum, kino_astar.h:234 */
+#define DFTPAV_SEARCH_NO_PATH 3
+/* Caller-allocated outputs, per query q (every pointer required when its size is > 0). */
+typedef struct dftpav_search_out {
+  int max_nodes, max_path;
+  int *status;       /* [n] DFTPAV_SEARCH_REACH_END or DFTPAV_SEARCH_NO_PATH */
+  int *shot_success; /* [n] the search ended on a free shot (is_shot_succ_) */
+  int *used_3d;      /* [n] the answer comes from a 3D search */
+  int *budget_hit;   /* [n] the search ended at max_iters (the time-out branch) */
+  int *iters;        /* [n] iter_num_ of the answering search */
+  int *nodes_used;   /* [n] use_node_num_ of the answering search */
+  int *n_nodes;      /* [n] path nodes, start to terminal (0 for NO_PATH; may exceed max_nodes: only the first are written) */
+  double *nodes;     /* [n][max_nodes][6] x, y, yaw (as searched, not normalised), steer, arc, singul */
+  int *path_len;     /* [n] SampleTraj poses (0 for NO_PATH; may exceed max_path: only the first are written) */
+  double *paths;     /* [n][max_path][3] SampleTraj: the layout dftpav_frontend_resample takes */
+} dftpav_search_out;
+/* start_states / end_states [n][4] (x, y, yaw, v); start_ctrl [n][2] (steer, acceleration: search keeps it for
+ * getKinoNode's flat states, i.e. for dftpav_frontend_resample).  DFTPAV_E_INVALID without a map;
+ * DFTPAV_E_UNSUPPORTED for parameters beyond the kernel's bounds (more than 32 inputs per expansion, check_num > 8,
+ * inputs x check_num > 256, a shot longer than its sample table).  dftpav_corridor_last_ms reports the kernel time. */
+int dftpav_kino_search(dftpav_handle *h, const dftpav_search_params *sp, const double *start_states, const double *start_ctrl,
+                       const double *end_states, int n, const dftpav_search_out *out);
+
 /* One-shot convenience == OptimizeTrajectory for B trajectories. */
 int dftpav_solve_batch(dftpav_handle *h, const dftpav_layout *layout, int B,
                        const dftpav_batch_data *d, double *x, double *final_cost,

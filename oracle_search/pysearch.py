@@ -1,0 +1,67 @@
+"""ctypes loader of the CPU restatement of the hybrid A* front end -- TEST INFRASTRUCTURE (kino_search_oracle.cpp).
+
+Only tests/ and scripts/ import this."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+from dftpav_amd.pods import SearchOut, SearchParams
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_SO = os.path.join(_HERE, "libkino_search_oracle.so")
+_LIB = None
+_SRCS = ("kino_search_oracle.cpp", "../oracle/step_trig.h", "../dftpav_amd/csrc/kino_heap.h", "../dftpav_amd/csrc/rs_math.h",
+         "../dftpav_amd/csrc/cr_trig.h", "../include/dftpav_hip.h")
+
+
+def build(force=False):
+    if force or not os.path.exists(_SO) or any(os.path.getmtime(_SO) < os.path.getmtime(os.path.join(_HERE, s)) for s in _SRCS):
+        subprocess.check_call(["make", "-C", _HERE, "-s"])
+    return _SO
+
+
+def lib():
+    global _LIB
+    if _LIB is None:
+        build()
+        L = C.CDLL(_SO)
+        L.oracle_kino_search.restype = None
+        L.oracle_kino_search.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.oracle_state_transit.restype = None
+        L.oracle_state_transit.argtypes = [C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.heap_selftest.restype = C.c_longlong
+        L.heap_selftest.argtypes = [C.c_ulonglong, C.c_longlong]
+        _LIB = L
+    return _LIB
+
+
+def kino_search(grid, resolution, origin, start_states, end_states, sp=None, order=2, max_nodes=512, max_path=4096,
+                nthreads=1):
+    """getKinoPath (KinoAstar::search with its 2D retry) + getKinoNode up to SampleTraj for n queries: the dict of
+    dftpav_amd.pods.SearchOut.  start_states / end_states [n][4] (x, y, yaw, v)."""
+    g = np.ascontiguousarray(grid, dtype=np.uint8)
+    st = np.ascontiguousarray(start_states, dtype=np.float64).reshape(-1, 4)
+    en = np.ascontiguousarray(end_states, dtype=np.float64).reshape(-1, 4)
+    sp = sp if sp is not None else SearchParams.default()
+    out = SearchOut(st.shape[0], max_nodes, max_path)
+    lib().oracle_kino_search(g.ctypes.data, g.shape[1], g.shape[0], float(resolution), float(origin[0]), float(origin[1]),
+                             C.addressof(sp), st.ctypes.data, en.ctypes.data, st.shape[0], int(order), int(nthreads),
+                             C.addressof(out.c))
+    return out.arrays()
+
+
+def state_transit(state0, ctrl, wheel_base=2.85, order=2):
+    """KinoAstar::stateTransit (kino_astar.cpp:21-36) in the given order: (x, y, yaw) of (steer, arc) from state0."""
+    s0 = np.ascontiguousarray(state0, dtype=np.float64)[:3].copy()
+    u = np.ascontiguousarray(ctrl, dtype=np.float64)[:2].copy()
+    o = np.zeros(3)
+    lib().oracle_state_transit(int(order), float(wheel_base), s0.ctypes.data, u.ctypes.data, o.ctypes.data)
+    return o
+
+
+def heap_selftest(seed, n_ops):
+    """kino_heap.h against std::priority_queue: -1, or the first operation after which they differ."""
+    return int(lib().heap_selftest(int(seed), int(n_ops)))
