@@ -64,11 +64,12 @@ RefPlan reference_order_plan(const DevLayout &L, const DevParams &P, int S, int 
 hipError_t launch_ring_reset(const DevBatch &D, hipStream_t stream);
 hipError_t launch_solver_ref(const DevBatch &D, const DevBatch *d_dev, int mode, const double *tabs, double *scratch, const RefPlan &pl, int scheduled,
                              hipStream_t stream);
-hipError_t launch_solver_quad(const DevBatch &D, const DevBatch *d_dev, int mode, const double *tabs, const double *cor_t, double *scratch, const RefPlan &pl,
-                              int scheduled, bool alone, hipStream_t stream);
+hipError_t launch_solver_quad(const DevBatch &D, const DevBatch *d_dev, int mode, const double *tabs, const double *cor_t, bool rect, double *scratch,
+                              const RefPlan &pl, int scheduled, bool alone, hipStream_t stream);
 // the QUAD shapes' copy of the corridor (solver_ref4.hip: one gear segment, solver_ref4m.hip: several)
 size_t reference_order_quad_corridor_doubles(const DevLayout &L, int B);
-hipError_t launch_quad_corridor(const DevBatch &D, double *cor_t, hipStream_t stream);
+hipError_t launch_quad_corridor(const DevBatch &D, double *cor_t, bool rect, hipStream_t stream);
+hipError_t launch_quad_rect_check(const double *corridor, int B, int Npts, int NptsPad, int *d_flag, hipStream_t stream);
 hipError_t launch_quadm_corridor(const DevBatch &D, double *cor_t, hipStream_t stream);
 }
 using namespace dftpav;
@@ -174,6 +175,11 @@ struct dftpav_batch {
   RefPlan ref_plan{}; // its launch plan (chosen with the order)
   double *d_cor_t = nullptr; // QUAD shapes: the corridor as [B][4 H][Kmax + 1][16] (solver_ref4.hip), refreshed when the corridor changes
   bool cor_t_dirty = true;
+  // Rectangles (solver_ref4.hip: RECT).  cor_rect: every corridor in d_corridor is known to be one -- learned by dftpav_batch_upload,
+  // which waits for the device anyway; the corridors the device makes from the map (dftpav_batch_corridor_from_hypotheses,
+  // dftpav_plan_cycle: no wait, none added) leave it false and run the sixteen-double layout.  cor_t_rect: the layout d_cor_t is in.
+  bool cor_rect = false, cor_t_rect = false;
+  int *d_rect_flag = nullptr;
   bool coef_override = false; // test hook dftpav_debug_batch_set_coeffs: validate / sample_states take the coefficients as they are
   int residency = -1; // the caller's residency hint (dftpav_batch_create_shaped); 2 = many such batches in flight: the throughput shapes whatever B
   // dftpav_plan_cycle: work buffers that live from the call to dftpav_plan_cycle_fetch (reused by the next cycle)
@@ -1115,7 +1121,7 @@ extern "C" void dftpav_batch_destroy(dftpav_batch *b) {
                   b->d_x_in, b->d_x_out, b->d_f, b->d_g, b->d_status, b->d_success, b->d_iters, b->d_evals,
                   b->d_hist, b->d_ticks, b->d_prof, b->d_dev, b->d_coef, b->d_dt, b->d_records,
                   b->d_queue, b->d_stragglers, b->d_stragglers2, b->d_sflag, b->d_iota, b->d_qctl, b->d_state, b->d_dev2,
-                  b->d_f_eval, b->d_trace, b->d_cor_raw, b->d_ref_tab, b->d_ref_scratch, b->d_cor_t, b->pc.d_poses, b->pc.d_t, b->pc.d_v, b->pc.d_rd, b->pc.d_col, b->pc.d_first,
+                  b->d_f_eval, b->d_trace, b->d_cor_raw, b->d_ref_tab, b->d_ref_scratch, b->d_cor_t, b->d_rect_flag, b->pc.d_poses, b->pc.d_t, b->pc.d_v, b->pc.d_rd, b->pc.d_col, b->pc.d_first,
                   b->pc.d_valid};
   {
     auto &v = b->h->batches;
@@ -1507,12 +1513,23 @@ extern "C" int dftpav_batch_upload(dftpav_batch *b, const dftpav_batch_data *d) 
   // a new upload without half-planes does not inherit the previous cycle's: they must follow from
   // dftpav_batch_corridor_from_states / _from_hypotheses before the next solve
   b->have_corridor = false;
+  b->cor_rect = false;
   if (d->corridor) {
     const size_t nraw = (size_t)B * L.Npts * L.H * 4;
     if (!b->d_cor_raw) HIPCHK(h, hipMalloc(&b->d_cor_raw, sizeof(double) * nraw));
     HIPCHK(h, hipMemcpyAsync(b->d_cor_raw, d->corridor, sizeof(double) * nraw, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, launch_corridor_layout(b->d_cor_raw, b->d_corridor, B, L.Npts, L.H, b->NptsPad, h->stream));
+    // whether they are all rectangles is asked here, in front of the wait this call ends with anyway.  DFTPAV_RECT_CORRIDOR=0: not
+    // asked -- the batch keeps the sixteen-double layout (A/B runs, tests); read here, where the layout is decided, not per launch
+    int not_rect = 1;
+    const char *knob = std::getenv("DFTPAV_RECT_CORRIDOR");
+    if (L.H == 4 && L.M == 1 && !(knob && std::strcmp(knob, "0") == 0)) {
+      if (!b->d_rect_flag) HIPCHK(h, hipMalloc(&b->d_rect_flag, sizeof(int)));
+      HIPCHK(h, launch_quad_rect_check(b->d_corridor, B, L.Npts, b->NptsPad, b->d_rect_flag, h->stream));
+      HIPCHK(h, hipMemcpyAsync(&not_rect, b->d_rect_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    }
     HIPCHK(h, hipStreamSynchronize(h->stream)); // the caller's buffer is free again when this returns
+    b->cor_rect = not_rect == 0;
     b->have_corridor = true;
     b->cor_t_dirty = true;
   }
@@ -1537,6 +1554,7 @@ extern "C" int dftpav_batch_corridor_from_hypotheses(dftpav_batch *b, const doub
   if (rc == DFTPAV_OK) {
     b->have_corridor = true;
     b->cor_t_dirty = true;
+    b->cor_rect = false; // (not asked: see dftpav_batch::cor_rect)
   }
   return rc;
 }
@@ -1765,16 +1783,26 @@ static hipError_t launch_ref(dftpav_batch *b, const DevBatch &D, int mode, int s
   const RefPlan &pl = b->ref_plan;
   if (pl.kind < kRefQuad || mode == kModeCoeffs)
     return launch_solver_ref(D, b->d_dev, mode, b->d_ref_tab, b->d_ref_scratch, pl, scheduled, b->h->stream);
-  if (b->cor_t_dirty) { // the QUAD shapes read their own layout of the corridor
-    const hipError_t e = pl.kind == kRefQuadSeg ? launch_quadm_corridor(D, b->d_cor_t, b->h->stream) : launch_quad_corridor(D, b->d_cor_t, b->h->stream);
+  // the QUAD shapes read their own layout of the corridor; the one-segment kernel's fast instance (H = 4, help_eps == 0.0) reads a
+  // batch of rectangles as 10 doubles per point (solver_ref4.hip: RECT)
+  const bool rect = b->cor_rect && pl.kind == kRefQuad && pl.fast && D.epis == 0.0;
+  if (b->cor_t_dirty || rect != b->cor_t_rect) {
+    const hipError_t e = pl.kind == kRefQuadSeg ? launch_quadm_corridor(D, b->d_cor_t, b->h->stream) : launch_quad_corridor(D, b->d_cor_t, rect, b->h->stream);
     if (e != hipSuccess) return e;
     b->cor_t_dirty = false;
+    b->cor_t_rect = rect;
   }
   // A batch that has the device to itself (the default; dftpav_batch_set_hand_over(b, 0) says that other batches follow on other
   // streams) takes every wave slot and hands its last trajectories to the WAVE shape.  In a stream of batches the launch is half as
   // wide as the batch (solver_ref.hip: quad_shape).
   const bool alone = b->hand_over != 0 && scheduled && mode == kModeSolve;
-  return launch_solver_quad(D, b->d_dev, mode, b->d_ref_tab, b->d_cor_t, b->d_ref_scratch, pl, scheduled, alone, b->h->stream);
+  return launch_solver_quad(D, b->d_dev, mode, b->d_ref_tab, b->d_cor_t, rect, b->d_ref_scratch, pl, scheduled, alone, b->h->stream);
+}
+// test hook: the layout of the QUAD shapes' corridor copy the last reference-order launch of this batch read -- 1: rectangles (10
+// doubles per point), 0: sixteen doubles per point, -1: no current copy (another shape, or the corridor changed since)
+extern "C" int dftpav_debug_batch_corridor_layout(const dftpav_batch *b) {
+  if (!b || b->order != DFTPAV_ORDER_REFERENCE || b->ref_plan.kind < kRefQuad || b->cor_t_dirty) return -1;
+  return b->cor_t_rect ? 1 : 0;
 }
 static hipError_t launch_for(dftpav_batch *b, const DevBatch &D, int mode) {
   if (b->order == DFTPAV_ORDER_REFERENCE) return launch_ref(b, D, mode, 0);
@@ -2551,6 +2579,7 @@ extern "C" int dftpav_plan_cycle(dftpav_batch *b, const dftpav_batch_data *d, co
                             nullptr, b->d_corridor, b->L.Npts, b->NptsPad, n_restarts, h->stream));
   b->have_corridor = true;
   b->cor_t_dirty = true;
+  b->cor_rect = false; // (nothing here waits for the device: the sixteen-double layout)
   if (int rc = solve_impl(b, nullptr, false)) return rc;
   DevBatch D;
   if (int rc = sync_dev(b, D)) return rc;

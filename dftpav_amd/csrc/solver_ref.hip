@@ -1971,7 +1971,7 @@ bool reference_order_quad_supported(const DevLayout &L, const DevParams &P, int 
 QuadSizes reference_order_quad_sizes(const DevLayout &L, const DevParams &P);
 bool reference_order_quadm_supported(const DevLayout &L, const DevParams &P, int S); // solver_ref4m.hip: several gear segments
 QuadSizes reference_order_quadm_sizes(const DevLayout &L, const DevParams &P);
-QuadKernel ref4_kernel_for(bool fast);                 // solver_ref4.hip
+QuadKernel ref4_kernel_for(bool fast, bool rect);      // solver_ref4.hip
 QuadKernel ref4m_kernel_for(bool fast, bool tail1);   // solver_ref4m.hip
 #if DFTPAV_REF_PART != 2
 // what the layout must satisfy for the reference-order kernel (solver_ref.hip header)
@@ -2243,8 +2243,9 @@ hipError_t launch_solver_ref(const DevBatch &D, const DevBatch *d_dev, int mode,
 // reset it).  alone: a scheduled solve of a batch that has the device to itself -- every wave slot, and once RefShape::hand
 // trajectories are unfinished its waves leave theirs to a launch in the WAVE shape queued behind, which pops them from the same ring
 // and resumes them from the same records (a wave per trajectory is 2-3 x faster per iteration once the device is emptying).
-hipError_t launch_solver_quad(const DevBatch &D, const DevBatch *d_dev, int mode, const double *tabs, const double *cor_t, double *scratch, const RefPlan &pl,
-                              int scheduled, bool alone, hipStream_t stream) {
+// rect: cor_t is the copy of a batch of rectangles (solver_ref4.hip: RECT; the one-segment kernel's fast instance only).
+hipError_t launch_solver_quad(const DevBatch &D, const DevBatch *d_dev, int mode, const double *tabs, const double *cor_t, bool rect, double *scratch,
+                              const RefPlan &pl, int scheduled, bool alone, hipStream_t stream) {
   const int W = pl.threads / 64;
   int grid = (D.B + 4 * W - 1) / (4 * W), source = 0, slice = 0, hand = 0;
   if (scheduled && mode == kModeSolve) {
@@ -2256,9 +2257,10 @@ hipError_t launch_solver_quad(const DevBatch &D, const DevBatch *d_dev, int mode
   if (pl.exact_div) source |= 2;
   if (pl.verbose)
     std::fprintf(stderr, "[dftpav] reference order, QUAD shape%s: grid %d x %d threads, %zu B of LDS, source %d slice %d hand-over at %d\n",
-                 pl.kind == kRefQuad ? "" : " (several segments)", grid, pl.threads, pl.lds, source, slice, hand);
+                 pl.kind == kRefQuad ? (rect ? " (rectangles)" : "") : " (several segments)", grid, pl.threads, pl.lds, source, slice, hand);
   const bool fast = pl.fast && D.epis == 0.0; // the live path's constants (solver_ref4.hip: q4_eval)
-  const QuadKernel fn = pl.kind == kRefQuad ? ref4_kernel_for(fast) : ref4m_kernel_for(fast, pl.tail1);
+  if (rect && !(fast && pl.kind == kRefQuad)) return hipErrorInvalidValue; // (the caller makes that copy for this instance only)
+  const QuadKernel fn = pl.kind == kRefQuad ? ref4_kernel_for(fast, rect) : ref4m_kernel_for(fast, pl.tail1);
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(fn, dim3(grid), dim3(pl.threads), pl.lds, stream, d_dev, mode, tabs, cor_t, scratch, source, slice, hand);

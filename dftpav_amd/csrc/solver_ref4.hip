@@ -20,7 +20,8 @@
 //     (three doubles) is parked, per piece, and chained afterwards over the pieces in order.  The active terms themselves are
 //     EVALUATED densely packed: listed by the lanes that find them, taken 24 at a time one per lane, their results handed back to
 //     the owners through LDS in list order (quad_common.h: DenseLds; q4_eval: flush);
-//   * the corridor is read from a copy laid out [component][j][piece]: the 16 lanes of a row read 128 contiguous bytes;
+//   * the corridor is read from a copy laid out [component][j][piece]: the 16 lanes of a row read 128 contiguous bytes; a batch whose
+//     corridors are all rectangles (q4_rect_check_kernel) reads a copy of 10 doubles per point instead of 16 (RECT, below);
 //   * lbfgs_optimize / line_search_lewisoverton (lbfgs.hpp:276-390, 440-751): solver_ref.hip's lbfgs_advance, per row; a vector of
 //     n <= 32 variables is two registers per lane (elements l and 16 + l), a sequential dot product is the 32-step DPP chain --
 //     each row chains its own sixteen lanes, no permlane swap -- and the two-loop recursion (:716-739) runs the four rows' history
@@ -285,7 +286,33 @@ __device__ __forceinline__ void sweep4_split(ldscd_t tab, double (&X)[6], double
 // trajectory's global scratch for the parked terms beyond the LDS window.
 // FAST: the live path's constants known at compile time -- H = 4 half-planes per point (rectangles, traj_manager.cpp:1225) and
 // help_eps = 0.0 (:610): the fifth plane slot and the second reciprocal of the curvature term drop out of the point loop.
-template <bool FAST>
+// RECT (with FAST): every corridor of the batch is a rectangle whose four normals are (-S, C), (C, S), (S, -C), (-C, -S) with the same
+// bits of C and S (q4_rect_check_kernel).  cor: &rect copy[b][0][0][l] in 16-byte units (q4_corridor_rect_kernel: [j][unit 5][piece 16],
+// unit 0 = (C, S), units 1-4 = (p_x, p_y) of planes 0-3): five 16-byte loads per round from one base instead of sixteen 8-byte loads
+// with an address each.  The normals are rebuilt by sign flips -- negation is exact, so every expression that uses them forms the bits
+// it forms from the sixteen doubles.
+struct RectSet { // a round's rectangle of one point
+  d2_t u[5];
+};
+__device__ __forceinline__ void load_rect(gcd2_t cor, RectSet &r) {
+#pragma unroll
+  for (int u = 0; u < 5; u++) r.u[u] = cor[16 * u];
+}
+__device__ __forceinline__ void rect_planes(const RectSet &r, double (&pl)[20]) {
+  const double C = r.u[0].x, S = r.u[0].y;
+  pl[0] = -S; pl[1] = C;
+  pl[4] = C; pl[5] = S;
+  pl[8] = S; pl[9] = -C;
+  pl[12] = -C; pl[13] = -S;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    pl[4 * k + 2] = r.u[1 + k].x;
+    pl[4 * k + 3] = r.u[1 + k].y;
+  }
+#pragma unroll
+  for (int u = 16; u < 20; u++) pl[u] = 0.0;
+}
+template <bool FAST, bool RECT>
 __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const DenseLds &dl, ldscd_t tab, gcd_t cor, size_t cpitch, gd_t ovf, int l, Prof &pr) {
   const DevLayout &L = D.L;
   const DevParams &P = D.P;
@@ -375,7 +402,10 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
   // a round's half-planes are requested one round ahead (the copy holds zeros where a piece has no such point: every lane
   // loads, whatever its piece): 33 rounds of a dependent HBM round trip each were 3/4 of this kernel's time
   double pl[20];
-  load_planes(cor, cpitch, H, pl);
+  RectSet rs; // RECT: the round's rectangle as loaded; pl is rebuilt from it at the head of a round
+  const gcd2_t rcor = (gcd2_t)cor;
+  if constexpr (RECT) load_rect(rcor, rs);
+  else load_planes(cor, cpitch, H, pl);
   // (the first round's half-planes are waited for HERE: left pending into the loop, they make the compiler wait for ALL vector loads in front of
   // every round's first use of a half-plane -- its count of the loads in flight merges to zero at the loop's head -- and that includes the
   // next round's, requested a few hundred instructions earlier: the request ahead bought half a round instead of a whole one)
@@ -471,7 +501,13 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
     unsigned m = 0u;
     PtState pst;
     double nx[20];
-    load_planes(cor + (size_t)(j < L.Kmax ? j + 1 : L.Kmax) * 16, cpitch, H, nx);
+    RectSet nr;
+    if constexpr (RECT) {
+      load_rect(rcor + (size_t)(j < L.Kmax ? j + 1 : L.Kmax) * 80, nr);
+      rect_planes(rs, pl);
+    } else {
+      load_planes(cor + (size_t)(j < L.Kmax ? j + 1 : L.Kmax) * 16, cpitch, H, nx);
+    }
     if (piece && j <= Kl && !extra)
       m = (unsigned)point_masks<false>(P, cc, l, N, j, Kl, step, s1, singul_, epis, H, pl, (gd_t) nullptr, D.sur, 0.0, 0.0, 0, 0.0, pst);
     const double s1_pt = s1;
@@ -547,8 +583,12 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
 #ifdef DFTPAV_PROF_EMIT_CYCLES
     if (D.prof != nullptr) pr.count(11, clock64() - emit_t0);
 #endif
+    if constexpr (RECT) {
+      rs = nr;
+    } else {
 #pragma unroll
-    for (int u = 0; u < 20; u++) pl[u] = nx[u];
+      for (int u = 0; u < 20; u++) pl[u] = nx[u];
+    }
   }
   q.tcnt[l] = piece ? cnt : 0;
   __threadfence_block(); // parked terms beyond the LDS window went to global memory; the counts are read by the other lanes
@@ -1093,7 +1133,7 @@ __device__ inline void q4_state_io(const DevBatch &D, const Q4 &q, QVec &v, int 
 // r of wave w of workgroup i takes trajectory (i W + w) 4 + r; bit 1: test hook, true divisions in the recursion from the start.
 // slice: evaluations of a wave after which its unfinished trajectories go back to the ring (all four rows together, so that the
 // rows of a wave are refilled together and the last trajectories of a batch gather in few waves).  hand: see the slice's end.
-template <bool FAST>
+template <bool FAST, bool RECT>
 __global__ void __launch_bounds__(256, DFTPAV_Q4_WAVES_PER_EU)
     ref4_kernel(const DevBatch *__restrict__ Dp, int mode, const double *__restrict__ tabs, const double *__restrict__ cor_t, double *__restrict__ scratch, int source,
                 int slice, int hand) {
@@ -1160,9 +1200,10 @@ __global__ void __launch_bounds__(256, DFTPAV_Q4_WAVES_PER_EU)
     }
     if (__builtin_amdgcn_ballot_w64(act) == 0ull) break; // (uniform) this wave has nothing left to do
     if (act) {
-      const gcd_t cor = (gcd_t)(cor_t + (size_t)b * L.H * 4 * cpitch + l);
+      // (RECT: the copy of 16-byte units [b][j][unit 5][piece 16], q4_corridor_rect_kernel)
+      const gcd_t cor = RECT ? (gcd_t)(cor_t + ((size_t)b * JP * 80 + l) * 2) : (gcd_t)(cor_t + (size_t)b * L.H * 4 * cpitch + l);
       const gd_t ovf = (gd_t)(scratch + (size_t)b * scratch_per_traj);
-      const double f = q4_eval<FAST>(D, q, dl, tab, cor, cpitch, ovf, l, pr);
+      const double f = q4_eval<FAST, RECT>(D, q, dl, tab, cor, cpitch, ovf, l, pr);
       if (mode == kModeEval) {
         for (int h = 0; h < 2; h++) {
           const int e = 16 * h + l;
@@ -1262,6 +1303,53 @@ __global__ void q4_corridor_kernel(const double *__restrict__ cor, double *__res
   }
 }
 
+// Whether every corridor of a batch is a rectangle in the sense of RECT (q4_eval): H = 4 and, at every point, the four normals are
+// (-S, C), (C, S), (S, -C), (-C, -S) with (C, S) the normal of plane 1 -- compared as 64-bit patterns, so a +0.0 where the relation
+// wants -0.0 does not pass, and neither does a NaN.  cor: the solver's layout [B][16][NptsPad]; *flag (zero before the launch) is set
+// to 1 by every point that does not satisfy the relations.
+__global__ void q4_rect_check_kernel(const double *__restrict__ cor, int B, int Npts, int NptsPad, int *__restrict__ flag) {
+  const size_t total = (size_t)B * Npts;
+  const unsigned long long sign = 0x8000000000000000ull;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const size_t b = i / Npts;
+    const int pt = (int)(i % Npts);
+    const double *c = cor + b * 16 * NptsPad + pt;
+    unsigned long long n[4][2];
+    for (int k = 0; k < 4; k++)
+      for (int q = 0; q < 2; q++) n[k][q] = (unsigned long long)__double_as_longlong(c[(size_t)(4 * k + q) * NptsPad]);
+    const unsigned long long C = n[1][0], S = n[1][1];
+    const bool nan = (C & ~sign) > 0x7ff0000000000000ull || (S & ~sign) > 0x7ff0000000000000ull;
+    const bool ok = !nan && n[0][0] == (S ^ sign) && n[0][1] == C && n[2][0] == S && n[2][1] == (C ^ sign) && n[3][0] == (C ^ sign) && n[3][1] == (S ^ sign);
+    if (!ok) *flag = 1;
+  }
+}
+
+// the corridor of such a batch [B][16][NptsPad] -> 16-byte units [B][Kmax + 1][5][16]: unit 0 of (j, p) = (C, S), units 1-4 = (p_x, p_y)
+// of planes 0-3 at constraint point j of piece p (zeros where the piece has no such point): the 16 lanes of a row read a unit as 256
+// contiguous bytes, a round is 1280 bytes from one base.  10 / 16 of the size of q4_corridor_kernel's copy.
+__global__ void q4_corridor_rect_kernel(const double *__restrict__ cor, d2_t *__restrict__ out, int B, int NptsPad, int N, int K, int Kd, int JP) {
+  const size_t total = (size_t)B * JP * 80;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int p = (int)(i & 15);
+    const int u = (int)((i >> 4) % 5);
+    const size_t r = i / 80;
+    const int j = (int)(r % JP);
+    const size_t b = r / JP;
+    d2_t v = {0.0, 0.0};
+    if (p < N) {
+      const int Kp = (p == 0 || p == N - 1) ? Kd : K;
+      const int pt0 = p == 0 ? 0 : (Kd + 1) + (p - 1) * (K + 1);
+      if (j <= Kp) {
+        const int c0 = u == 0 ? 4 : 4 * (u - 1) + 2; // (C, S): the normal of plane 1; else the point of plane u - 1
+        const double *src = cor + (b * 16 + c0) * NptsPad + pt0 + j;
+        v.x = src[0];
+        v.y = src[NptsPad];
+      }
+    }
+    out[i] = v;
+  }
+}
+
 } // namespace reford
 
 // ---- host side
@@ -1277,13 +1365,30 @@ size_t reference_order_quad_corridor_doubles(const DevLayout &L, int B) { return
 QuadSizes reference_order_quad_sizes(const DevLayout &L, const DevParams &P) {
   return {reford::q4_shared_bytes(L.Ntot), reford::q4_team_bytes(P.mem_size) + (reford::q4_dense_bytes() + 3) / 4, reford::kQ4WavesPerCU, 768};
 }
-hipError_t launch_quad_corridor(const DevBatch &D, double *cor_t, hipStream_t stream) {
+// rect: the copy of a batch of rectangles (q4_corridor_rect_kernel; it fits the same allocation)
+hipError_t launch_quad_corridor(const DevBatch &D, double *cor_t, bool rect, hipStream_t stream) {
   const DevLayout &L = D.L;
-  const size_t total = reference_order_quad_corridor_doubles(L, D.B);
+  const size_t total = rect ? (size_t)D.B * (L.Kmax + 1) * 80 : reference_order_quad_corridor_doubles(L, D.B);
   const int grid = (int)std::min<size_t>((total + 255) / 256, 65536);
-  hipLaunchKernelGGL(reford::q4_corridor_kernel, dim3(grid), dim3(256), 0, stream, D.corridor, cor_t, D.B, L.H * 4, D.NptsPad, L.Ntot, L.K, L.Kd, L.Kmax + 1);
+  if (rect)
+    hipLaunchKernelGGL(reford::q4_corridor_rect_kernel, dim3(grid), dim3(256), 0, stream, D.corridor, reinterpret_cast<reford::d2_t *>(cor_t), D.B, D.NptsPad, L.Ntot, L.K,
+                       L.Kd, L.Kmax + 1);
+  else
+    hipLaunchKernelGGL(reford::q4_corridor_kernel, dim3(grid), dim3(256), 0, stream, D.corridor, cor_t, D.B, L.H * 4, D.NptsPad, L.Ntot, L.K, L.Kd, L.Kmax + 1);
   return hipGetLastError();
 }
-QuadKernel ref4_kernel_for(bool fast) { return fast ? &reford::ref4_kernel<true> : &reford::ref4_kernel<false>; }
+// *d_flag = 1 if some corridor of the batch (H = 4, the solver's layout) is not a rectangle in the sense of RECT, else 0
+hipError_t launch_quad_rect_check(const double *corridor, int B, int Npts, int NptsPad, int *d_flag, hipStream_t stream) {
+  hipError_t e = hipMemsetAsync(d_flag, 0, sizeof(int), stream);
+  if (e != hipSuccess) return e;
+  const size_t total = (size_t)B * Npts;
+  const int grid = (int)std::min<size_t>((total + 255) / 256, 65536);
+  hipLaunchKernelGGL(reford::q4_rect_check_kernel, dim3(grid), dim3(256), 0, stream, corridor, B, Npts, NptsPad, d_flag);
+  return hipGetLastError();
+}
+QuadKernel ref4_kernel_for(bool fast, bool rect) {
+  if (fast && rect) return &reford::ref4_kernel<true, true>;
+  return fast ? &reford::ref4_kernel<true, false> : &reford::ref4_kernel<false, false>;
+}
 
 } // namespace dftpav
