@@ -20,6 +20,9 @@ _LIB = None
 OK = 0
 ORDER_DEVICE, ORDER_REFERENCE = 0, 1
 E_INVALID, E_MINI_T, E_ONE_PIECE, E_NO_DEVICE, E_HIP, E_UNSUPPORTED, E_COMM = -1, -2, -3, -4, -5, -6, -7
+# plan_status of dftpav_plan_queries (DFTPAV_PLAN_*); search status (DFTPAV_SEARCH_*)
+PLAN_OK, PLAN_NO_PATH, PLAN_TOO_MANY_SEGMENTS, PLAN_LAYOUT_UNSUPPORTED, PLAN_NO_VALID_RESTART, PLAN_ARRIVED = 0, 1, 2, 3, 4, 5
+SEARCH_REACH_END, SEARCH_NO_PATH = 2, 3
 
 # every symbol include/dftpav_hip.h declares
 EXPORTS = [
@@ -36,6 +39,8 @@ EXPORTS = [
     "dftpav_batch_set_order", "dftpav_batch_get_order", "dftpav_batch_trace_range", "dftpav_batch_get_trace_of",
     "dftpav_comm_available", "dftpav_comm_unique_id", "dftpav_comm_create", "dftpav_comm_destroy", "dftpav_comm_share", "dftpav_comm_layout", "dftpav_batch_allgather_results",
     "dftpav_default_search_params", "dftpav_kino_search",
+    "dftpav_default_plan_params", "dftpav_planner_create", "dftpav_planner_destroy", "dftpav_plan_queries", "dftpav_planner_info",
+    "dftpav_plan_group_layouts", "dftpav_debug_plan_select",
 ]
 
 
@@ -346,6 +351,109 @@ class Handle:
             self.close()
         except Exception:
             pass
+
+
+def default_plan_params():
+    """dftpav_default_plan_params: pods.PlanParams filled from the defaults of the stages"""
+    from .pods import PlanParams
+    pp = PlanParams()
+    fn = lib().dftpav_default_plan_params
+    fn.argtypes = [C.c_void_p]
+    fn.restype = None
+    fn(C.byref(pp))
+    return pp
+
+
+def plan_group_layouts(search_status, n_seg, singul, piece_nums):
+    """dftpav_plan_group_layouts (host only): per-query tables (singul / piece_nums [Q][max_seg]) ->
+    dict(group [Q], group_first [n_groups], plan_status [Q])"""
+    st = np.ascontiguousarray(search_status, dtype=np.int32)
+    ns = np.ascontiguousarray(n_seg, dtype=np.int32)
+    Q = st.shape[0]
+    sg = np.ascontiguousarray(singul, dtype=np.int32)
+    pn = np.ascontiguousarray(piece_nums, dtype=np.int32)
+    assert sg.ndim == 2 and sg.shape[0] == Q and pn.shape == sg.shape and ns.shape == (Q,)
+    max_seg = max(1, sg.shape[1])
+    group, first, status = np.zeros(Q, dtype=np.int32), np.zeros(Q, dtype=np.int32), np.zeros(Q, dtype=np.int32)
+    ng = C.c_int(-1)
+    fn = lib().dftpav_plan_group_layouts
+    fn.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 8
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    rc = fn(Q, max_seg, ptr(st), ptr(ns), ptr(sg), ptr(pn), ptr(group), ptr(first), C.byref(ng), ptr(status))
+    if rc != OK:
+        raise DftpavError(rc, "plan_group_layouts")
+    return dict(group=group, group_first=first[:ng.value].copy(), plan_status=status)
+
+
+class Planner:
+    """dftpav_planner: a batch of start / goal queries to their plans on a handle's map (dftpav_plan_queries); owns the device work
+    buffers and one batch per layout met so far."""
+
+    def __init__(self, handle, max_queries, n_restarts):
+        self.handle = handle
+        self.max_queries, self.n_restarts = int(max_queries), int(n_restarts)
+        self._p = C.c_void_p()
+        fn = lib().dftpav_planner_create
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        rc = fn(handle._h if handle is not None else None, self.max_queries, self.n_restarts, C.byref(self._p))
+        if rc != OK:
+            self._p = None
+            raise DftpavError(rc, "planner_create")
+
+    def plan(self, start_states, end_states, start_ctrl=None, pp=None, t_now=0.0):
+        """-> the dict of pods.PlanOut: plan_status, the layout found, winner and its final_cost / iters / x / coeffs / coeff_dt per
+        query; r_* per (query, restart); search_status / search_iters / search_path_len"""
+        from .pods import PlanOut
+        st = np.ascontiguousarray(start_states, dtype=np.float64).reshape(-1, 4)
+        en = np.ascontiguousarray(end_states, dtype=np.float64).reshape(-1, 4)
+        Q = st.shape[0]
+        ct = np.ascontiguousarray(start_ctrl if start_ctrl is not None else np.zeros((Q, 2)), dtype=np.float64).reshape(-1, 2)
+        pp = pp if pp is not None else default_plan_params()
+        out = PlanOut(Q, self.n_restarts, pp.max_seg, pp.max_pieces)
+        fn = lib().dftpav_plan_queries
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]
+        self.handle._check(fn(self._p, C.byref(pp), st.ctypes.data_as(C.c_void_p), ct.ctypes.data_as(C.c_void_p),
+                              en.ctypes.data_as(C.c_void_p), Q, float(t_now), C.byref(out.c)), "plan_queries")
+        return out.arrays()
+
+    def info(self):
+        """dict(n_batches, group_sizes of the last call, stage_ms = device time of its search, resampling, groups, all)"""
+        nb, ng = C.c_int(0), C.c_int(0)
+        sizes = np.zeros(self.max_queries, dtype=np.int32)
+        ms = np.zeros(4, dtype=np.float32)
+        fn = lib().dftpav_planner_info
+        fn.argtypes = [C.c_void_p] * 5
+        self.handle._check(fn(self._p, C.byref(nb), C.byref(ng), sizes.ctypes.data_as(C.c_void_p), ms.ctypes.data_as(C.c_void_p)),
+                           "planner_info")
+        return dict(n_batches=nb.value, group_sizes=sizes[:ng.value].copy(), stage_ms=ms.astype(np.float64))
+
+    def close(self):
+        if self._p:
+            fn = lib().dftpav_planner_destroy
+            fn.argtypes = [C.c_void_p]
+            fn.restype = None
+            fn(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def debug_plan_select(handle, cost, success, collision):
+    """dftpav_debug_plan_select: the selection kernel on [n_query][n_restarts] arrays -> winner [n_query]"""
+    c = np.ascontiguousarray(cost, dtype=np.float64)
+    s = np.ascontiguousarray(success, dtype=np.int32)
+    k = np.ascontiguousarray(collision, dtype=np.int32)
+    nq, R = c.shape
+    w = np.zeros(nq, dtype=np.int32)
+    fn = lib().dftpav_debug_plan_select
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    handle._check(fn(handle._h, nq, R, ptr(c), ptr(s), ptr(k), ptr(w)), "debug_plan_select")
+    return w
 
 
 class GridMap(C.Structure):

@@ -27,6 +27,7 @@
 #include "cr_trig.h"
 #include "rs_math.h"
 #include "search_args.h"
+#include "plan_args.h"
 
 namespace dftpav {
 hipError_t launch_solver(const DevBatch &D, const DevBatch *d_dev, int mode, int threads, int grid, SchedArgs sched,
@@ -52,6 +53,11 @@ hipError_t launch_shots(const double *from, const double *to, int n, double rho,
                         double veh_width, double veh_length, double veh_dcr, const double *v_tab, int n_v, double *length, int *type,
                         double *seg, double *samples, int *n_samples, int *collides, hipStream_t stream);
 hipError_t launch_search(const SearchArgs &A, int blocks, hipStream_t stream);
+// plan.hip: the kernels between the stages of dftpav_plan_queries
+hipError_t launch_plan_paths(const int *status, const int *path_len, const int *skip, int n, int max_path, double *paths, int *fe_len,
+                             hipStream_t stream);
+hipError_t launch_plan_pack(const PlanPackArgs &A, hipStream_t stream);
+hipError_t launch_plan_select(const PlanSelectArgs &A, hipStream_t stream);
 hipError_t launch_corridor_layout(const double *raw, double *out, int B, int Npts, int H, int NptsPad, hipStream_t stream);
 hipError_t launch_adopt(const DevBatch &D, const DevBatch &prev, hipStream_t stream);
 // solver_ref.hip: the same path in the reference's own floating-point order
@@ -122,6 +128,7 @@ struct dftpav_handle {
 struct dftpav_batch {
   dftpav_handle *h = nullptr;
   int B = 0;
+  int n_active = 0; // dftpav_plan_queries: the leading trajectories in use this call (0: all B); the kernels see it as the batch size
   DevLayout L{};
   DevParams P{};
   int threads = 0;
@@ -768,15 +775,16 @@ static int search_inputs(const dftpav_search_params &sp, double max_steer, int w
   return n;
 }
 
-extern "C" int dftpav_kino_search(dftpav_handle *h, const dftpav_search_params *sp, const double *start_states,
-                                  const double *start_ctrl, const double *end_states, int n, const dftpav_search_out *out) {
-  (void)start_ctrl; // kept by search (kino_astar.cpp:54) for getKinoNode's flat states: dftpav_frontend_resample takes it
-  if (!h || !sp || !out || n < 0 || out->max_nodes < 0 || out->max_path < 0) return DFTPAV_E_INVALID;
-  if (!h->d_cells) return DFTPAV_E_INVALID; // no map
-  if (n == 0) return DFTPAV_OK;
-  if (!start_states || !end_states || !out->status || !out->shot_success || !out->used_3d || !out->budget_hit || !out->iters ||
-      !out->nodes_used || !out->n_nodes || !out->path_len || (out->max_nodes > 0 && !out->nodes) || (out->max_path > 0 && !out->paths))
-    return DFTPAV_E_INVALID;
+// What a launch of the search needs besides the queries and the outputs: the checked parameters, the tables of the running sums
+// (inputs, outline point spacing, shot sample offsets; `tabs` is their host copy, in_tab | v_tab | l_tab) and the handle's
+// workspace for `slots` queries in flight.  Shared by dftpav_kino_search and dftpav_plan_queries.
+struct SearchSetup {
+  SearchArgs S{};
+  std::vector<double> tabs;
+  size_t n_in_tab = 0, n_vv = 0, n_ll = 0;
+  int slots = 0;
+};
+static int search_setup(dftpav_handle *h, const dftpav_search_params *sp, int n, SearchSetup &U) {
   const dftpav_search_params &P = *sp;
   if (P.allocate_num < 2 || P.check_num < 1 || P.max_iters < 0 || !(P.map_resl > 0.0) || !(P.phi_grid_resolution > 0.0) ||
       !(P.step_arc > 0.0) || !(P.max_frontend_cur > 0.0) || !(P.checkl > 0.0) || !(P.vertex_res > 0.0) || !(P.wheel_base > 0.0))
@@ -828,7 +836,8 @@ extern "C" int dftpav_kino_search(dftpav_handle *h, const dftpav_search_params *
     w += (bytes + 255) / 256 * 256;
     return p;
   };
-  SearchArgs S{};
+  SearchArgs &S = U.S;
+  S = SearchArgs{};
   S.pool = (SearchNode *)take(A * slots * sizeof(SearchNode));
   S.h_node = (int *)take(A * slots * sizeof(int));
   S.h_pos = (int *)take(A * slots * sizeof(int));
@@ -851,6 +860,32 @@ extern "C" int dftpav_kino_search(dftpav_handle *h, const dftpav_search_params *
   S.rho = rho;
   for (int k = 0; k < 3; k++) S.n_in[k] = n_in[k];
   S.n = n;
+  S.n_v = (int)vv.size();
+  S.n_l = (int)ll.size();
+  U.tabs = in_tab;
+  U.tabs.insert(U.tabs.end(), vv.begin(), vv.end());
+  U.tabs.insert(U.tabs.end(), ll.begin(), ll.end());
+  U.n_in_tab = in_tab.size();
+  U.n_vv = vv.size();
+  U.n_ll = ll.size();
+  U.slots = slots;
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_kino_search(dftpav_handle *h, const dftpav_search_params *sp, const double *start_states,
+                                  const double *start_ctrl, const double *end_states, int n, const dftpav_search_out *out) {
+  (void)start_ctrl; // kept by search (kino_astar.cpp:54) for getKinoNode's flat states: dftpav_frontend_resample takes it
+  if (!h || !sp || !out || n < 0 || out->max_nodes < 0 || out->max_path < 0) return DFTPAV_E_INVALID;
+  if (!h->d_cells) return DFTPAV_E_INVALID; // no map
+  if (n == 0) return DFTPAV_OK;
+  if (!start_states || !end_states || !out->status || !out->shot_success || !out->used_3d || !out->budget_hit || !out->iters ||
+      !out->nodes_used || !out->n_nodes || !out->path_len || (out->max_nodes > 0 && !out->nodes) || (out->max_path > 0 && !out->paths))
+    return DFTPAV_E_INVALID;
+  SearchSetup U;
+  if (int rc0 = search_setup(h, sp, n, U)) return rc0;
+  SearchArgs &S = U.S;
+  const std::vector<double> &tabs = U.tabs;
+  const int slots = U.slots;
   int rc = DFTPAV_OK;
   auto chk = [&](hipError_t e) {
     if (e != hipSuccess && rc == DFTPAV_OK) {
@@ -861,7 +896,7 @@ extern "C" int dftpav_kino_search(dftpav_handle *h, const dftpav_search_params *
   const size_t nn = (size_t)n;
   double *d_tabs = nullptr, *d_st = nullptr, *d_en = nullptr, *d_nodes = nullptr, *d_paths = nullptr;
   int *d_ints = nullptr;
-  const size_t ntab = in_tab.size() + vv.size() + ll.size();
+  const size_t ntab = tabs.size();
   chk(hipMalloc(&d_tabs, sizeof(double) * ntab));
   chk(hipMalloc(&d_st, sizeof(double) * 4 * nn));
   chk(hipMalloc(&d_en, sizeof(double) * 4 * nn));
@@ -869,9 +904,6 @@ extern "C" int dftpav_kino_search(dftpav_handle *h, const dftpav_search_params *
   if (out->max_nodes > 0) chk(hipMalloc(&d_nodes, sizeof(double) * 6 * nn * out->max_nodes));
   if (out->max_path > 0) chk(hipMalloc(&d_paths, sizeof(double) * 3 * nn * out->max_path));
   if (rc == DFTPAV_OK) {
-    std::vector<double> tabs(in_tab);
-    tabs.insert(tabs.end(), vv.begin(), vv.end());
-    tabs.insert(tabs.end(), ll.begin(), ll.end());
     chk(hipMemcpyAsync(d_tabs, tabs.data(), sizeof(double) * ntab, hipMemcpyHostToDevice, h->stream));
     chk(hipMemcpyAsync(d_st, start_states, sizeof(double) * 4 * nn, hipMemcpyHostToDevice, h->stream));
     chk(hipMemcpyAsync(d_en, end_states, sizeof(double) * 4 * nn, hipMemcpyHostToDevice, h->stream));
@@ -879,10 +911,8 @@ extern "C" int dftpav_kino_search(dftpav_handle *h, const dftpav_search_params *
     if (d_nodes) chk(hipMemsetAsync(d_nodes, 0, sizeof(double) * 6 * nn * out->max_nodes, h->stream));
     if (d_paths) chk(hipMemsetAsync(d_paths, 0, sizeof(double) * 3 * nn * out->max_path, h->stream));
     S.in_tab = d_tabs;
-    S.v_tab = d_tabs + in_tab.size();
-    S.n_v = (int)vv.size();
-    S.l_tab = d_tabs + in_tab.size() + vv.size();
-    S.n_l = (int)ll.size();
+    S.v_tab = d_tabs + U.n_in_tab;
+    S.l_tab = d_tabs + U.n_in_tab + U.n_vv;
     S.start = d_st;
     S.end = d_en;
     int *const fields[9] = {out->status, out->shot_success, out->used_3d, out->budget_hit, out->iters, out->nodes_used,
@@ -1586,7 +1616,7 @@ static DevBatch make_dev(dftpav_batch *b) {
   DevBatch D{};
   D.L = b->L;
   D.P = b->P;
-  D.B = b->B;
+  D.B = b->n_active > 0 ? b->n_active : b->B;
   D.x0 = b->d_x0;
   D.iniS = b->d_iniS;
   D.finS = b->d_finS;
@@ -2803,3 +2833,560 @@ extern "C" int dftpav_solve_batch(dftpav_handle *h, const dftpav_layout *layout,
   return rc;
 }
 
+// ------------------------------------------------- a batch of queries to their plans (plan.hip)
+// TrajPlanner::RunOnceParking from the arrival test on (traj_manager.cpp:194-217) for Q queries: search -> resampling on the device,
+// one read-back of the tables that decide the layouts, then per layout group pack -> rectangles -> reference-order solve ->
+// coefficients -> collision re-check -> selection, all enqueued on the handle's stream with no wait between stages or groups.
+extern "C" void dftpav_default_plan_params(dftpav_plan_params *pp) {
+  std::memset(pp, 0, sizeof(*pp));
+  dftpav_default_search_params(&pp->search);
+  // minco_config.pb.txt:66-67, 76-80; kino_astar.h:207; semantics.h:68 (the defaults of dftpav_frontend_resample's callers)
+  pp->frontend.max_forward_vel = 5.0;
+  pp->frontend.max_forward_acc = 8.0;
+  pp->frontend.max_backward_vel = 2.0;
+  pp->frontend.max_backward_acc = 4.0;
+  pp->frontend.non_siguav = 0.2;
+  pp->frontend.wheel_base = 2.85;
+  pp->frontend.piece_duration = 1.0;
+  pp->frontend.traj_res = 16;
+  pp->frontend.dense_traj_res = 32;
+  pp->sigma = 0.3;
+  pp->dur_lo = 0.8;
+  pp->dur_hi = 1.25;
+  pp->seed = 0;
+  pp->check_dt = 0.05;  // traj_server_ros.cpp:387
+  pp->vertex_res = 0.1; // shapes.h:201
+  pp->max_seg = 8;
+  pp->max_pieces = 64;
+  pp->max_path = 4096;
+}
+extern "C" int dftpav_abi_sizeof_plan_params(void) { return (int)sizeof(dftpav_plan_params); }
+extern "C" int dftpav_abi_sizeof_plan_out(void) { return (int)sizeof(dftpav_plan_out); }
+
+extern "C" int dftpav_plan_group_layouts(int Q, int max_seg, const int *search_status, const int *n_seg, const int *singul,
+                                         const int *piece_nums, int *group, int *group_first, int *n_groups, int *plan_status) {
+  if (Q < 0 || max_seg < 1 || !n_groups || (Q > 0 && (!search_status || !n_seg || !singul || !piece_nums || !group || !group_first)))
+    return DFTPAV_E_INVALID;
+  int ng = 0;
+  for (int q = 0; q < Q; q++) {
+    group[q] = -1;
+    if (search_status[q] != DFTPAV_SEARCH_REACH_END) {
+      if (plan_status) plan_status[q] = DFTPAV_PLAN_NO_PATH;
+      continue;
+    }
+    const int M = n_seg[q];
+    if (M < 1 || M > max_seg) {
+      if (plan_status) plan_status[q] = DFTPAV_PLAN_TOO_MANY_SEGMENTS;
+      continue;
+    }
+    const int *sg = singul + (size_t)q * max_seg, *pn = piece_nums + (size_t)q * max_seg;
+    int g = 0;
+    for (; g < ng; g++) {
+      const int f = group_first[g];
+      if (n_seg[f] == M && std::memcmp(singul + (size_t)f * max_seg, sg, sizeof(int) * M) == 0 &&
+          std::memcmp(piece_nums + (size_t)f * max_seg, pn, sizeof(int) * M) == 0)
+        break;
+    }
+    if (g == ng) group_first[ng++] = q;
+    group[q] = g;
+    if (plan_status) plan_status[q] = DFTPAV_PLAN_OK;
+  }
+  *n_groups = ng;
+  return DFTPAV_OK;
+}
+
+struct dftpav_planner {
+  dftpav_handle *h = nullptr;
+  int max_queries = 0, R = 0;
+  struct Entry {
+    std::vector<int> key; // M, singul[M], piece_nums[M]
+    dftpav_batch *b;
+  };
+  std::vector<Entry> cache; // one batch per layout met so far
+  // device work buffers: one allocation, carved up for the paddings of the last call (kept while they do not change)
+  unsigned char *d_arena = nullptr;
+  size_t arena_bytes = 0;
+  long long sig[6] = {0, 0, 0, 0, 0, 0}; // max_seg, max_pieces, max_path, max_states, doubles of the search tables, of the validation tables
+  double *d_st = nullptr, *d_en = nullptr, *d_ct = nullptr, *d_tabs = nullptr, *d_paths = nullptr, *d_vt = nullptr;
+  int *d_skip = nullptr, *d_sints = nullptr, *d_fe_len = nullptr, *d_members = nullptr, *d_minit = nullptr, *d_col = nullptr, *d_first = nullptr;
+  dftpav_frontend_out fe{}; // device pointers
+  double *d_poses = nullptr;
+  size_t fe_zero_bytes = 0; // the front-end outputs are one stretch of the arena, zeroed per call (as dftpav_frontend_resample does)
+  unsigned char *d_fe0 = nullptr;
+  // compact outputs (zeroed per call): one stretch too
+  unsigned char *d_out0 = nullptr;
+  size_t out_zero_bytes = 0;
+  int *d_winner = nullptr, *d_witers = nullptr, *d_rint[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  double *d_wcost = nullptr, *d_wx = nullptr, *d_wcoef = nullptr, *d_wdt = nullptr, *d_rcost = nullptr;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool timed = false;
+  std::vector<int> group_sizes;
+  // host staging of the tables that decide the grouping
+  std::vector<int> h_sints, h_nseg, h_singul, h_pn, h_nstates, h_skip, h_members, h_minit;
+  std::vector<double> h_dt, h_vt;
+};
+
+extern "C" int dftpav_planner_create(dftpav_handle *h, int max_queries, int n_restarts, dftpav_planner **out) {
+  if (out) *out = nullptr;
+  if (!h || !out) return DFTPAV_E_INVALID;
+  if (max_queries < 1 || n_restarts < 1 || n_restarts > 65535 || (long long)max_queries * n_restarts > (1 << 24)) return DFTPAV_E_INVALID;
+  HIPCHK(h, hipSetDevice(h->device));
+  auto *p = new dftpav_planner();
+  p->h = h;
+  p->max_queries = max_queries;
+  p->R = n_restarts;
+  for (auto &e : p->ev)
+    if (hipEventCreate(&e) != hipSuccess) {
+      h->err = "dftpav_planner_create: hipEventCreate";
+      for (auto &f : p->ev)
+        if (f) (void)hipEventDestroy(f);
+      delete p;
+      return DFTPAV_E_HIP;
+    }
+  *out = p;
+  return DFTPAV_OK;
+}
+extern "C" void dftpav_planner_destroy(dftpav_planner *p) {
+  if (!p) return;
+  (void)hipSetDevice(p->h->device);
+  (void)hipStreamSynchronize(p->h->stream);
+  for (auto &e : p->cache) dftpav_batch_destroy(e.b);
+  if (p->d_arena) (void)hipFree(p->d_arena);
+  for (auto &e : p->ev)
+    if (e) (void)hipEventDestroy(e);
+  delete p;
+}
+
+extern "C" int dftpav_planner_info(dftpav_planner *p, int *n_batches, int *n_groups, int *group_sizes, float *stage_ms) {
+  if (!p) return DFTPAV_E_INVALID;
+  if (n_batches) *n_batches = (int)p->cache.size();
+  if (n_groups) *n_groups = (int)p->group_sizes.size();
+  if (group_sizes)
+    for (size_t g = 0; g < p->group_sizes.size(); g++) group_sizes[g] = p->group_sizes[g];
+  if (stage_ms) {
+    dftpav_handle *h = p->h;
+    for (int k = 0; k < 4; k++) stage_ms[k] = 0.0f;
+    if (p->timed) {
+      HIPCHK(h, hipSetDevice(h->device));
+      HIPCHK(h, hipEventSynchronize(p->ev[3]));
+      HIPCHK(h, hipEventElapsedTime(&stage_ms[0], p->ev[0], p->ev[1]));
+      HIPCHK(h, hipEventElapsedTime(&stage_ms[1], p->ev[1], p->ev[2]));
+      HIPCHK(h, hipEventElapsedTime(&stage_ms[2], p->ev[2], p->ev[3]));
+      HIPCHK(h, hipEventElapsedTime(&stage_ms[3], p->ev[0], p->ev[3]));
+    }
+  }
+  return DFTPAV_OK;
+}
+
+// carves the planner's arena for these paddings (a no-op while they are those of the previous call)
+static int planner_buffers(dftpav_planner *p, const dftpav_plan_params &pp, int max_states, size_t n_tabs, size_t n_vt) {
+  dftpav_handle *h = p->h;
+  const long long sig[6] = {pp.max_seg, pp.max_pieces, pp.max_path, max_states, (long long)n_tabs, (long long)n_vt};
+  if (p->d_arena && std::memcmp(sig, p->sig, sizeof(sig)) == 0) return DFTPAV_OK;
+  const size_t Q = (size_t)p->max_queries, R = (size_t)p->R, MS = (size_t)pp.max_seg, MP = (size_t)pp.max_pieces, MST = (size_t)max_states;
+  for (int pass = 0; pass < 2; pass++) { // measure, then carve
+    unsigned char *w = p->d_arena;
+    size_t used = 0;
+    auto take = [&](size_t bytes) {
+      void *r = pass ? (void *)(w + used) : nullptr;
+      used += (bytes + 255) / 256 * 256;
+      return r;
+    };
+    p->d_st = (double *)take(sizeof(double) * 4 * Q);
+    p->d_en = (double *)take(sizeof(double) * 4 * Q);
+    p->d_ct = (double *)take(sizeof(double) * 2 * Q);
+    p->d_tabs = (double *)take(sizeof(double) * n_tabs);
+    p->d_vt = (double *)take(sizeof(double) * n_vt);
+    p->d_paths = (double *)take(sizeof(double) * 3 * Q * (size_t)pp.max_path);
+    p->d_skip = (int *)take(sizeof(int) * Q);
+    p->d_sints = (int *)take(sizeof(int) * 9 * Q);
+    p->d_fe_len = (int *)take(sizeof(int) * Q);
+    p->d_members = (int *)take(sizeof(int) * Q);
+    p->d_col = (int *)take(sizeof(int) * Q * R);
+    p->d_first = (int *)take(sizeof(int) * Q * R);
+    p->d_poses = (double *)take(sizeof(double) * 3 * Q * MS * MST);
+    const size_t fe0 = used;
+    p->d_fe0 = (unsigned char *)take(0);
+    p->fe.max_seg = pp.max_seg;
+    p->fe.max_pieces = pp.max_pieces;
+    p->fe.max_states = max_states;
+    p->fe.n_seg = (int *)take(sizeof(int) * Q);
+    p->fe.singul = (int *)take(sizeof(int) * Q * MS);
+    p->fe.piece_nums = (int *)take(sizeof(int) * Q * MS);
+    p->fe.piece_dt = (double *)take(sizeof(double) * Q * MS);
+    p->fe.ini_states = (double *)take(sizeof(double) * Q * MS * 6);
+    p->fe.fin_states = (double *)take(sizeof(double) * Q * MS * 6);
+    p->fe.inner_pts = (double *)take(sizeof(double) * Q * MS * (MP - 1) * 2);
+    p->fe.n_states = (int *)take(sizeof(int) * Q * MS);
+    p->fe.states = (double *)take(sizeof(double) * Q * MS * MST * 3);
+    p->fe_zero_bytes = used - fe0;
+    const size_t out0 = used;
+    p->d_out0 = (unsigned char *)take(0);
+    p->d_minit = (int *)take(sizeof(int) * Q);
+    p->d_winner = (int *)take(sizeof(int) * Q);
+    p->d_witers = (int *)take(sizeof(int) * Q);
+    p->d_wcost = (double *)take(sizeof(double) * Q);
+    p->d_wx = (double *)take(sizeof(double) * Q * DFTPAV_PLAN_MAX_VARS);
+    p->d_wcoef = (double *)take(sizeof(double) * Q * MS * MP * 12);
+    p->d_wdt = (double *)take(sizeof(double) * Q * MS);
+    p->d_rcost = (double *)take(sizeof(double) * Q * R);
+    for (int k = 0; k < 6; k++) p->d_rint[k] = (int *)take(sizeof(int) * Q * R);
+    p->out_zero_bytes = used - out0;
+    if (pass == 0) {
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+      if (p->d_arena && p->arena_bytes < used) {
+        (void)hipFree(p->d_arena);
+        p->d_arena = nullptr;
+        p->arena_bytes = 0;
+      }
+      if (!p->d_arena) {
+        HIPCHK(h, hipMalloc(&p->d_arena, used));
+        p->arena_bytes = used;
+      }
+    }
+  }
+  std::memcpy(p->sig, sig, sizeof(sig));
+  return DFTPAV_OK;
+}
+
+// the batch of a layout: from the cache, or created with room for max_queries * n_restarts trajectories in the reference order.
+// *out == nullptr with DFTPAV_OK: the layout is outside the reference order's limits.
+static int planner_batch(dftpav_planner *p, const dftpav_layout &lay, dftpav_batch **out) {
+  dftpav_handle *h = p->h;
+  *out = nullptr;
+  std::vector<int> key;
+  key.push_back(lay.M);
+  key.insert(key.end(), lay.singuls, lay.singuls + lay.M);
+  key.insert(key.end(), lay.piece_nums, lay.piece_nums + lay.M);
+  dftpav_batch *b = nullptr;
+  for (auto &e : p->cache)
+    if (e.key == key) b = e.b;
+  if (lay.M > kMaxSeg) return DFTPAV_OK;
+  for (int i = 0; i < lay.M; i++)
+    if (lay.piece_nums[i] < 2) return DFTPAV_OK;
+  DevLayout L;
+  fill_dev_layout(lay, h->params.traj_resolution, h->params.des_traj_resolution, L);
+  DevParams P;
+  fill_dev_params(h->params, P);
+  if (L.n > DFTPAV_PLAN_MAX_VARS || L.Ntot > 1024 || L.Npts > 32767 || (long long)L.Npts * h->S > 65535 || !reference_order_supported(L, P, h->S))
+    return DFTPAV_OK;
+  const bool fresh = b == nullptr;
+  if (fresh) {
+    const int rc = dftpav_batch_create(h, &lay, p->max_queries * p->R, &b);
+    if (rc == DFTPAV_E_UNSUPPORTED) return DFTPAV_OK;
+    if (rc) return rc;
+  }
+  const int rc = dftpav_batch_set_order(b, DFTPAV_ORDER_REFERENCE); // (nothing to do for a cached batch unless the obstacles changed)
+  if (rc) {
+    if (fresh) dftpav_batch_destroy(b);
+    return rc == DFTPAV_E_UNSUPPORTED ? DFTPAV_OK : rc;
+  }
+  if (fresh) p->cache.push_back({key, b});
+  *out = b;
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *pp, const double *start_states, const double *start_ctrl,
+                                   const double *end_states, int Q, double t_now, const dftpav_plan_out *out) {
+  if (!p || !pp || !out || Q < 0 || Q > p->max_queries) return DFTPAV_E_INVALID;
+  dftpav_handle *h = p->h;
+  if (!h->d_cells) return DFTPAV_E_INVALID; // no map
+  const dftpav_frontend_params &fp = pp->frontend;
+  if (pp->max_seg < 1 || pp->max_seg > kMaxSeg || pp->max_pieces < 2 || pp->max_pieces > 1024 || pp->max_path < 2 || pp->max_path > (1 << 20) ||
+      !(pp->sigma >= 0.0) || !(pp->dur_lo > 0.0) || !(pp->dur_hi >= pp->dur_lo) || !(pp->check_dt > 0.0) || !(pp->vertex_res > 0.0) ||
+      fp.traj_res != h->params.traj_resolution || fp.dense_traj_res != h->params.des_traj_resolution || fp.traj_res < 1 || fp.dense_traj_res < 1 ||
+      !(fp.piece_duration > 0.0) || !(fp.max_forward_vel > 0.0) || !(fp.max_forward_acc > 0.0) || !(fp.max_backward_vel > 0.0) ||
+      !(fp.max_backward_acc > 0.0))
+    return DFTPAV_E_INVALID;
+  p->group_sizes.clear();
+  p->timed = false;
+  if (Q == 0) return DFTPAV_OK;
+  if (!start_states || !start_ctrl || !end_states) return DFTPAV_E_INVALID;
+  SearchSetup U;
+  if (int rc = search_setup(h, &pp->search, Q, U)) return rc;
+  const int R = p->R, MS = pp->max_seg, MP = pp->max_pieces;
+  const int MST = (MP - 2) * (fp.traj_res + 1) + 2 * (fp.dense_traj_res + 1); // poses of a segment of max_pieces pieces
+  // the two running sums of the collision re-check, tabulated (as dftpav_batch_validate): sample times | outline point spacing
+  std::vector<double> &vt = p->h_vt;
+  vt.clear();
+  {
+    double t = 0.0;
+    for (int k = 0; k < 4096; k++, t += pp->check_dt) vt.push_back(t);
+    const double longest = std::max(h->params.veh_length, h->params.veh_width) + 1.0;
+    for (double dl = pp->vertex_res; dl < longest; dl += pp->vertex_res) vt.push_back(dl);
+    if (vt.size() == 4096) vt.push_back(pp->vertex_res);
+  }
+  const int n_t = 4096, n_v = (int)vt.size() - 4096;
+  if (int rc = planner_buffers(p, *pp, MST, U.tabs.size(), vt.size())) return rc;
+  const size_t nq = (size_t)Q;
+  // ---- arrival test (traj_manager.cpp:196), uploads, search, resampling
+  p->h_skip.assign(Q, 0);
+  for (int q = 0; q < Q; q++) {
+    const double dx = end_states[4 * q] - start_states[4 * q], dy = end_states[4 * q + 1] - start_states[4 * q + 1];
+    if (std::sqrt(dx * dx + dy * dy) < 1.0) p->h_skip[q] = 1;
+  }
+  HIPCHK(h, hipMemcpyAsync(p->d_st, start_states, sizeof(double) * 4 * nq, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(p->d_en, end_states, sizeof(double) * 4 * nq, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(p->d_ct, start_ctrl, sizeof(double) * 2 * nq, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(p->d_skip, p->h_skip.data(), sizeof(int) * nq, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(p->d_tabs, U.tabs.data(), sizeof(double) * U.tabs.size(), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(p->d_vt, vt.data(), sizeof(double) * vt.size(), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemsetAsync(p->d_paths, 0, sizeof(double) * 3 * nq * pp->max_path, h->stream));
+  HIPCHK(h, hipMemsetAsync(p->d_fe0, 0, p->fe_zero_bytes, h->stream));
+  HIPCHK(h, hipMemsetAsync(p->d_out0, 0, p->out_zero_bytes, h->stream));
+  SearchArgs &S = U.S;
+  S.in_tab = p->d_tabs;
+  S.v_tab = p->d_tabs + U.n_in_tab;
+  S.l_tab = p->d_tabs + U.n_in_tab + U.n_vv;
+  S.start = p->d_st;
+  S.end = p->d_en;
+  {
+    dftpav_search_out &O = S.out;
+    int *d = p->d_sints;
+    O.max_nodes = 0;
+    O.max_path = pp->max_path;
+    O.status = d;
+    O.shot_success = d + nq;
+    O.used_3d = d + 2 * nq;
+    O.budget_hit = d + 3 * nq;
+    O.iters = d + 4 * nq;
+    O.nodes_used = d + 5 * nq;
+    O.n_nodes = d + 6 * nq;
+    O.path_len = d + 7 * nq;
+    O.nodes = nullptr;
+    O.paths = p->d_paths;
+  }
+  HIPCHK(h, hipEventRecord(p->ev[0], h->stream));
+  for (int q0 = 0; q0 < Q; q0 += U.slots) {
+    S.q0 = q0;
+    HIPCHK(h, launch_search(S, std::min(U.slots, Q - q0), h->stream));
+  }
+  HIPCHK(h, hipEventRecord(p->ev[1], h->stream));
+  HIPCHK(h, launch_plan_paths(S.out.status, S.out.path_len, p->d_skip, Q, pp->max_path, p->d_paths, p->d_fe_len, h->stream));
+  HIPCHK(h, launch_frontend(fp, p->d_paths, p->d_fe_len, pp->max_path, p->d_st, p->d_en, p->d_ct, Q, p->fe, h->stream));
+  HIPCHK(h, hipEventRecord(p->ev[2], h->stream));
+  // ---- the one read-back before the end: the tables that decide the grouping
+  p->h_sints.assign(8 * nq, 0);
+  p->h_nseg.assign(nq, 0);
+  p->h_singul.assign(nq * MS, 0);
+  p->h_pn.assign(nq * MS, 0);
+  p->h_nstates.assign(nq * MS, 0);
+  p->h_dt.assign(nq * MS, 0.0);
+  for (int f = 0; f < 8; f++)
+    HIPCHK(h, hipMemcpyAsync(p->h_sints.data() + f * nq, p->d_sints + f * nq, sizeof(int) * nq, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(p->h_nseg.data(), p->fe.n_seg, sizeof(int) * nq, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(p->h_singul.data(), p->fe.singul, sizeof(int) * nq * MS, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(p->h_pn.data(), p->fe.piece_nums, sizeof(int) * nq * MS, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(p->h_nstates.data(), p->fe.n_states, sizeof(int) * nq * MS, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(p->h_dt.data(), p->fe.piece_dt, sizeof(double) * nq * MS, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  const int *s_status = p->h_sints.data(), *s_iters = p->h_sints.data() + 4 * nq, *s_len = p->h_sints.data() + 7 * nq;
+  for (int q = 0; q < Q; q++)
+    if (s_status[q] == 0) return DFTPAV_E_UNSUPPORTED; // a shot beyond the sample table (as dftpav_kino_search)
+  // ---- grouping.  Queries that were not resampled (arrived, a path beyond its padding) are kept out of it, as those without a path are
+  std::vector<int> gate(nq), group(nq), first(nq), status(nq);
+  for (int q = 0; q < Q; q++) {
+    const bool usable = s_status[q] == DFTPAV_SEARCH_REACH_END && s_len[q] >= 2 && s_len[q] <= pp->max_path && !p->h_skip[q];
+    gate[q] = usable ? DFTPAV_SEARCH_REACH_END : DFTPAV_SEARCH_NO_PATH;
+    if (!usable) {
+      p->h_nseg[q] = 0;
+      for (int i = 0; i < MS; i++) p->h_singul[(size_t)q * MS + i] = p->h_pn[(size_t)q * MS + i] = p->h_nstates[(size_t)q * MS + i] = 0, p->h_dt[(size_t)q * MS + i] = 0.0;
+    } else if (p->h_nseg[q] >= 1 && p->h_nseg[q] <= MS) {
+      for (int i = 0; i < p->h_nseg[q]; i++) // a segment of more pieces than the padding: its waypoints and poses were cut
+        if (p->h_pn[(size_t)q * MS + i] > MP || p->h_nstates[(size_t)q * MS + i] > MST) gate[q] = -1;
+    }
+  }
+  int ng = 0;
+  if (int rc = dftpav_plan_group_layouts(Q, MS, gate.data(), p->h_nseg.data(), p->h_singul.data(), p->h_pn.data(), group.data(), first.data(), &ng,
+                                         status.data()))
+    return rc;
+  for (int q = 0; q < Q; q++) {
+    if (p->h_skip[q]) status[q] = DFTPAV_PLAN_ARRIVED;
+    else if (gate[q] == -1 || (s_status[q] == DFTPAV_SEARCH_REACH_END && s_len[q] > pp->max_path)) status[q] = DFTPAV_PLAN_TOO_MANY_SEGMENTS;
+  }
+  // ---- the groups' batches (created on first use), the members in group order
+  std::vector<dftpav_batch *> batch(ng, nullptr);
+  std::vector<int> g_off(ng + 1, 0);
+  p->h_members.clear();
+  for (int g = 0; g < ng; g++) {
+    const int f = first[g];
+    dftpav_layout lay{p->h_nseg[f], p->h_pn.data() + (size_t)f * MS, p->h_singul.data() + (size_t)f * MS, 4};
+    if (int rc = planner_batch(p, lay, &batch[g])) return rc;
+    g_off[g] = (int)p->h_members.size();
+    for (int q = 0; q < Q; q++)
+      if (group[q] == g) {
+        if (batch[g]) p->h_members.push_back(q);
+        else status[q] = DFTPAV_PLAN_LAYOUT_UNSUPPORTED;
+      }
+    g_off[g + 1] = (int)p->h_members.size();
+    p->group_sizes.push_back(g_off[g + 1] - g_off[g]);
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  if (!p->h_members.empty())
+    HIPCHK(h, hipMemcpyAsync(p->d_members, p->h_members.data(), sizeof(int) * p->h_members.size(), hipMemcpyHostToDevice, h->stream));
+  // ---- per group: pack -> rectangles -> solve -> coefficients -> collision re-check -> selection; nothing waits in between
+  size_t pose_off = 0;
+  for (int g = 0; g < ng; g++) {
+    dftpav_batch *b = batch[g];
+    const int nm = g_off[g + 1] - g_off[g];
+    if (!b || nm == 0) continue;
+    const DevLayout &L = b->L;
+    b->pending = false;
+    b->n_active = nm * R;
+    b->t_now = t_now;
+    b->epis = 0.0; // help_eps of the live call, traj_manager.cpp:610
+    b->uploaded = true;
+    b->solved = false;
+    b->coef_override = false;
+    b->dev_version = -1; // n_active / t_now live in the device copy of the launch descriptor
+    PlanPackArgs A{};
+    A.L = L;
+    A.fe = p->fe;
+    A.members = p->d_members + g_off[g];
+    A.n_members = nm;
+    A.n_restarts = R;
+    A.sigma = pp->sigma;
+    A.lo = pp->dur_lo;
+    A.hi = pp->dur_hi;
+    A.seed = pp->seed;
+    A.mini_T = h->params.mini_T;
+    A.max_vel[0] = h->params.max_forward_vel;
+    A.max_vel[1] = h->params.max_backward_vel;
+    A.max_acc[0] = h->params.max_forward_acc;
+    A.max_acc[1] = h->params.max_backward_acc;
+    A.x0 = b->d_x0;
+    A.iniS = b->d_iniS;
+    A.finS = b->d_finS;
+    A.poses = p->d_poses + 3 * pose_off;
+    A.mini_t_flag = p->d_minit;
+    HIPCHK(h, launch_plan_pack(A, h->stream));
+    HIPCHK(h, launch_corridor(h->d_cells, h->d_bits, h->map.size_x, h->map.size_y, h->map.resolution, h->map.origin_x, h->map.origin_y, A.poses,
+                              nm * L.Npts, h->params.veh_width, h->params.veh_length, h->params.veh_d_cr, h->d_dl, h->n_dl, nullptr, b->d_corridor,
+                              L.Npts, b->NptsPad, R, h->stream));
+    pose_off += (size_t)nm * L.Npts;
+    b->have_corridor = true;
+    b->cor_t_dirty = true;
+    b->cor_rect = false; // (nothing here waits for the device: the sixteen-double layout)
+    if (int rc = solve_impl(b, nullptr, false)) return rc;
+    DevBatch D;
+    if (int rc = sync_dev(b, D)) return rc;
+    HIPCHK(h, launch_for(b, D, kModeCoeffs));
+    int *col = p->d_col + (size_t)g_off[g] * R, *fst = p->d_first + (size_t)g_off[g] * R;
+    HIPCHK(h, launch_validate(h->d_cells, h->map.size_x, h->map.size_y, h->map.resolution, h->map.origin_x, h->map.origin_y, b->d_coef, b->d_dt, L,
+                              nm * R, h->params.veh_width, h->params.veh_length, h->params.veh_d_cr, p->d_vt, n_t, pp->check_dt, p->d_vt + n_t, n_v,
+                              col, fst, h->stream));
+    PlanSelectArgs Z{};
+    Z.cost = b->d_f;
+    Z.success = b->d_success;
+    Z.collision = col;
+    Z.status = b->d_status;
+    Z.iters = b->d_iters;
+    Z.evals = b->d_evals;
+    Z.first_sample = fst;
+    Z.x = b->d_x_out;
+    Z.coef = b->d_coef;
+    Z.dt = b->d_dt;
+    Z.n = L.n;
+    Z.n_coef = 12 * L.Ntot;
+    Z.M = L.M;
+    Z.members = A.members;
+    Z.n_members = nm;
+    Z.R = R;
+    Z.winner = p->d_winner;
+    Z.w_cost = p->d_wcost;
+    Z.w_iters = p->d_witers;
+    Z.w_x = p->d_wx;
+    Z.w_coef = p->d_wcoef;
+    Z.w_dt = p->d_wdt;
+    Z.x_stride = DFTPAV_PLAN_MAX_VARS;
+    Z.coef_stride = MS * MP * 12;
+    Z.dt_stride = MS;
+    Z.r_cost = p->d_rcost;
+    Z.r_status = p->d_rint[0];
+    Z.r_success = p->d_rint[1];
+    Z.r_iters = p->d_rint[2];
+    Z.r_evals = p->d_rint[3];
+    Z.r_collision = p->d_rint[4];
+    Z.r_first_sample = p->d_rint[5];
+    HIPCHK(h, launch_plan_select(Z, h->stream));
+  }
+  HIPCHK(h, hipEventRecord(p->ev[3], h->stream));
+  p->timed = true;
+  // ---- the compact results
+  std::vector<int> winner(nq, -1);
+  p->h_minit.assign(nq, 0);
+  auto fetch = [&](void *dst, const void *src, size_t bytes) { return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess; };
+  HIPCHK(h, fetch(winner.data(), p->d_winner, sizeof(int) * nq));
+  HIPCHK(h, fetch(p->h_minit.data(), p->d_minit, sizeof(int) * nq));
+  HIPCHK(h, fetch(out->final_cost, p->d_wcost, sizeof(double) * nq));
+  HIPCHK(h, fetch(out->iters, p->d_witers, sizeof(int) * nq));
+  HIPCHK(h, fetch(out->x, p->d_wx, sizeof(double) * nq * DFTPAV_PLAN_MAX_VARS));
+  HIPCHK(h, fetch(out->coeffs, p->d_wcoef, sizeof(double) * nq * MS * MP * 12));
+  HIPCHK(h, fetch(out->coeff_dt, p->d_wdt, sizeof(double) * nq * MS));
+  HIPCHK(h, fetch(out->r_final_cost, p->d_rcost, sizeof(double) * nq * R));
+  int *const r_out[6] = {out->r_status, out->r_success, out->r_iters, out->r_evals, out->r_collision, out->r_first_sample};
+  for (int k = 0; k < 6; k++) HIPCHK(h, fetch(r_out[k], p->d_rint[k], sizeof(int) * nq * R));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (int q = 0; q < Q; q++) {
+    if (status[q] != DFTPAV_PLAN_OK) {
+      winner[q] = -1;
+      continue;
+    }
+    if (p->h_minit[q]) { // a restart below mini_T: OptimizeTrajectory refuses the call (see the header); no plan is reported
+      winner[q] = -1;
+      if (out->final_cost) out->final_cost[q] = 0.0;
+      if (out->iters) out->iters[q] = 0;
+      if (out->x) std::memset(out->x + (size_t)q * DFTPAV_PLAN_MAX_VARS, 0, sizeof(double) * DFTPAV_PLAN_MAX_VARS);
+      if (out->coeffs) std::memset(out->coeffs + (size_t)q * MS * MP * 12, 0, sizeof(double) * MS * MP * 12);
+      if (out->coeff_dt) std::memset(out->coeff_dt + (size_t)q * MS, 0, sizeof(double) * MS);
+    }
+    if (winner[q] < 0) status[q] = DFTPAV_PLAN_NO_VALID_RESTART;
+  }
+  if (out->plan_status) std::memcpy(out->plan_status, status.data(), sizeof(int) * nq);
+  if (out->winner) std::memcpy(out->winner, winner.data(), sizeof(int) * nq);
+  if (out->n_seg) std::memcpy(out->n_seg, p->h_nseg.data(), sizeof(int) * nq);
+  if (out->singul) std::memcpy(out->singul, p->h_singul.data(), sizeof(int) * nq * MS);
+  if (out->piece_nums) std::memcpy(out->piece_nums, p->h_pn.data(), sizeof(int) * nq * MS);
+  if (out->piece_dt) std::memcpy(out->piece_dt, p->h_dt.data(), sizeof(double) * nq * MS);
+  if (out->search_status) std::memcpy(out->search_status, s_status, sizeof(int) * nq);
+  if (out->search_iters) std::memcpy(out->search_iters, s_iters, sizeof(int) * nq);
+  if (out->search_path_len) std::memcpy(out->search_path_len, s_len, sizeof(int) * nq);
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_debug_plan_select(dftpav_handle *h, int n_query, int n_restarts, const double *cost, const int *success,
+                                        const int *collision, int *winner_out) {
+  if (!h || n_query < 0 || n_restarts < 1 || (n_query > 0 && (!cost || !success || !collision || !winner_out))) return DFTPAV_E_INVALID;
+  if (n_query == 0) return DFTPAV_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t nt = (size_t)n_query * n_restarts;
+  double *d_cost = nullptr;
+  int *d_int = nullptr; // success | collision | winner
+  int rc = DFTPAV_OK;
+  auto chk = [&](hipError_t e) {
+    if (e != hipSuccess && rc == DFTPAV_OK) {
+      h->err = hipGetErrorString(e);
+      rc = DFTPAV_E_HIP;
+    }
+  };
+  chk(hipMalloc(&d_cost, sizeof(double) * nt));
+  chk(hipMalloc(&d_int, sizeof(int) * (2 * nt + n_query)));
+  if (rc == DFTPAV_OK) {
+    chk(hipMemcpyAsync(d_cost, cost, sizeof(double) * nt, hipMemcpyHostToDevice, h->stream));
+    chk(hipMemcpyAsync(d_int, success, sizeof(int) * nt, hipMemcpyHostToDevice, h->stream));
+    chk(hipMemcpyAsync(d_int + nt, collision, sizeof(int) * nt, hipMemcpyHostToDevice, h->stream));
+    PlanSelectArgs Z{};
+    Z.cost = d_cost;
+    Z.success = d_int;
+    Z.collision = d_int + nt;
+    Z.n_members = n_query;
+    Z.R = n_restarts;
+    Z.winner = d_int + 2 * nt;
+    chk(launch_plan_select(Z, h->stream));
+    chk(hipMemcpyAsync(winner_out, d_int + 2 * nt, sizeof(int) * n_query, hipMemcpyDeviceToHost, h->stream));
+    chk(hipStreamSynchronize(h->stream));
+  }
+  if (d_cost) (void)hipFree(d_cost);
+  if (d_int) (void)hipFree(d_int);
+  return rc;
+}

@@ -20,6 +20,7 @@
 
 #include "device_types.h"
 #include "traj_math.h"
+#include "restart_rng.h"
 
 namespace dftpav {
 
@@ -33,19 +34,6 @@ struct RestartArgs {
   double *out_durs;  // [n_hyp * n_restarts][M]
 };
 
-__host__ __device__ inline unsigned long long splitmix64(unsigned long long s0, unsigned long long k) {
-  unsigned long long z = s0 + k * 0x9E3779B97F4A7C15ull;
-  z ^= z >> 30;
-  z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27;
-  z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z;
-}
-__host__ __device__ inline double u01(unsigned long long s0, unsigned long long k) {
-  return ((double)(splitmix64(s0, k) >> 11) + 0.5) * 1.1102230246251565e-16; // 2^-53
-}
-
 __global__ void __launch_bounds__(256) restart_kernel(RestartArgs A) {
   const int nw = A.n_inner / 2;      // waypoints
   const int per = nw + A.M;          // work items per trajectory
@@ -53,7 +41,7 @@ __global__ void __launch_bounds__(256) restart_kernel(RestartArgs A) {
   for (long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x; w < total; w += (long long)gridDim.x * blockDim.x) {
     const int b = (int)(w / per), q = (int)(w - (long long)b * per);
     const int hyp = b / A.n_restarts, r = b - hyp * A.n_restarts;
-    const unsigned long long s0 = splitmix64(A.seed, 1ull + (unsigned long long)hyp * 65536ull + (unsigned long long)r);
+    const unsigned long long s0 = restart_stream(A.seed, hyp, r);
     if (q < nw) {
       const double bx = A.inner[(size_t)hyp * A.n_inner + 2 * q], by = A.inner[(size_t)hyp * A.n_inner + 2 * q + 1];
       double dx = 0.0, dy = 0.0;

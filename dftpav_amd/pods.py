@@ -247,3 +247,39 @@ class SearchOut:
 
     def arrays(self):
         return dict(self.a)
+
+
+class PlanParams(C.Structure):
+    """dftpav_plan_params (include/dftpav_hip.h): the parameters of every stage of dftpav_plan_queries."""
+    _fields_ = [("search", SearchParams), ("frontend", FrontendParams), ("sigma", C.c_double), ("dur_lo", C.c_double),
+                ("dur_hi", C.c_double), ("seed", C.c_ulonglong), ("check_dt", C.c_double), ("vertex_res", C.c_double),
+                ("max_seg", C.c_int), ("max_pieces", C.c_int), ("max_path", C.c_int)]
+
+
+MAX_PLAN_VARS = 256             # DFTPAV_PLAN_MAX_VARS
+
+
+class PlanOutC(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in (
+        "plan_status", "n_seg", "singul", "piece_nums", "piece_dt", "winner", "final_cost", "iters", "x", "coeffs", "coeff_dt",
+        "r_final_cost", "r_status", "r_success", "r_iters", "r_evals", "r_collision", "r_first_sample", "search_status",
+        "search_iters", "search_path_len")]
+
+
+class PlanOut:
+    """Owner of the output arrays of dftpav_plan_queries: Q queries, R restarts, padded to max_seg / max_pieces."""
+
+    def __init__(self, Q, R, max_seg=8, max_pieces=64):
+        i32 = np.int32
+        a = dict(plan_status=np.zeros(Q, i32), n_seg=np.zeros(Q, i32), singul=np.zeros((Q, max_seg), i32),
+                 piece_nums=np.zeros((Q, max_seg), i32), piece_dt=np.zeros((Q, max_seg)), winner=np.zeros(Q, i32),
+                 final_cost=np.zeros(Q), iters=np.zeros(Q, i32), x=np.zeros((Q, MAX_PLAN_VARS)),
+                 coeffs=np.zeros((Q, max_seg * max_pieces, 6, 2)), coeff_dt=np.zeros((Q, max_seg)), r_final_cost=np.zeros((Q, R)),
+                 r_status=np.zeros((Q, R), i32), r_success=np.zeros((Q, R), i32), r_iters=np.zeros((Q, R), i32),
+                 r_evals=np.zeros((Q, R), i32), r_collision=np.zeros((Q, R), i32), r_first_sample=np.zeros((Q, R), i32),
+                 search_status=np.zeros(Q, i32), search_iters=np.zeros(Q, i32), search_path_len=np.zeros(Q, i32))
+        self.a = a
+        self.c = PlanOutC(*[a[n].ctypes.data for n, _ in PlanOutC._fields_])
+
+    def arrays(self):
+        return dict(self.a)

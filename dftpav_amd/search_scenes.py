@@ -95,3 +95,13 @@ def arena():
     grid, origin, res, ego = sc.default_sim_map()
     start = np.array([ego[0], ego[1], ego[2], 0.0])
     return grid, res, origin, start, ARENA_GOALS.copy()
+
+
+def arena_plan_queries():
+    """(grid, resolution, origin, starts [14][4], goals [14][4]) for dftpav_plan_queries on the default arena: ARENA_GOALS from the
+    ego start, then a goal inside an obstacle (no path) and one closer than 1 m to the start (arrived)."""
+    grid, res, origin, start, goals = arena()
+    extra = np.array([[-47.8, 40.0, 0.0, 0.0],
+                      [start[0] + 0.6, start[1] + 0.3, start[2], 0.0]])
+    goals = np.concatenate([goals, extra])
+    return grid, res, origin, np.repeat(start[None], len(goals), 0), goals

@@ -635,6 +635,82 @@ typedef struct dftpav_search_out {
 int dftpav_kino_search(dftpav_handle *h, const dftpav_search_params *sp, const double *start_states, const double *start_ctrl,
                        const double *end_states, int n, const dftpav_search_out *out);
 
+/* ---- a batch of start / goal queries to their plans, mixed layouts included --------------
+ * Replaces TrajPlanner::RunOnceParking from the arrival test on (traj_manager.cpp:194-217): per query the
+ * arrival test (:196), getKinoPath (:69-117, as dftpav_kino_search), getKinoNode from SampleTraj on and the
+ * resampling of RunMINCOParking (as dftpav_frontend_resample), n_restarts seeded restarts of the searched
+ * hypothesis (as dftpav_sample_restarts, keyed by (seed, query index in the call, restart)), getRectangleConst,
+ * OptimizeTrajectory in DFTPAV_ORDER_REFERENCE, the coefficients and the collision re-check of CheckReplan
+ * (traj_server_ros.cpp:385-397), and the choice of the cheapest collision-free restart.  The map is the one of
+ * dftpav_set_grid_map, the moving obstacles those installed on the handle.
+ *
+ * Searched paths of different goals come back with different layouts (gear segments, pieces, directions).  The
+ * queries are grouped by layout (dftpav_plan_group_layouts); every layout has a batch of its own in the planner,
+ * created on first use with room for max_queries * n_restarts trajectories and kept for later calls.  The stages
+ * run on the handle's stream from device memory; the host reads the small tables that decide the grouping once,
+ * after the resampling, and the compact results at the end.  Bit for bit what the separate calls return.
+ * A query without a plan does not disturb the others.  A restart that fails the mini_T test of
+ * traj_optimizer.cpp:30-33 makes its query DFTPAV_PLAN_NO_VALID_RESTART (OptimizeTrajectory refuses it).
+ * Destroy a planner before its handle. */
+typedef struct dftpav_planner dftpav_planner;
+#define DFTPAV_PLAN_OK 0
+#define DFTPAV_PLAN_NO_PATH 1            /* the search found none (DFTPAV_SEARCH_NO_PATH) */
+#define DFTPAV_PLAN_TOO_MANY_SEGMENTS 2  /* more segments, pieces, poses or path poses than the padding holds */
+#define DFTPAV_PLAN_LAYOUT_UNSUPPORTED 3 /* outside the limits of DFTPAV_ORDER_REFERENCE (dftpav_batch_set_order) */
+#define DFTPAV_PLAN_NO_VALID_RESTART 4   /* every restart failed or collides */
+#define DFTPAV_PLAN_ARRIVED 5            /* closer to the goal than 1.0 m (traj_manager.cpp:196): nothing is planned */
+#define DFTPAV_PLAN_MAX_VARS 256         /* decision variables of a plan at most (the reference order's limit) */
+typedef struct dftpav_plan_params {
+  dftpav_search_params search;     /* dftpav_default_search_params */
+  dftpav_frontend_params frontend; /* as dftpav_frontend_resample; traj_res / dense_traj_res must equal the handle's
+                                      traj_resolution / des_traj_resolution */
+  double sigma, dur_lo, dur_hi;    /* 0.3, 0.8, 1.25: the restart sampler (dftpav_sample_restarts) */
+  unsigned long long seed;         /* 0 */
+  double check_dt, vertex_res;     /* 0.05, 0.1: the collision re-check (dftpav_batch_validate) */
+  int max_seg, max_pieces, max_path; /* 8, 64, 4096: padding of the front end (max_seg <= 8); a segment holds up to
+                                      (max_pieces - 2) (traj_res + 1) + 2 (dense_traj_res + 1) poses */
+} dftpav_plan_params;
+void dftpav_default_plan_params(dftpav_plan_params *pp);
+/* Caller-allocated outputs.  Q queries, R = the planner's n_restarts, padded with max_seg / max_pieces of the
+ * parameters.  Every pointer may be NULL.  Rows of queries without a plan are zero (winner: -1). */
+typedef struct dftpav_plan_out {
+  int *plan_status;     /* [Q] DFTPAV_PLAN_* */
+  int *n_seg;           /* [Q] gear segments found (as dftpav_frontend_out; 0 where nothing was searched or resampled) */
+  int *singul;          /* [Q][max_seg] */
+  int *piece_nums;      /* [Q][max_seg] */
+  double *piece_dt;     /* [Q][max_seg] of the searched hypothesis */
+  int *winner;          /* [Q] restart index, -1 if none */
+  double *final_cost;   /* [Q] the winner's */
+  int *iters;           /* [Q] */
+  double *x;            /* [Q][DFTPAV_PLAN_MAX_VARS] the winner's decision vector (dftpav_num_vars of its layout are used) */
+  double *coeffs;       /* [Q][max_seg * max_pieces][6][2] the winner's pieces, as dftpav_batch_coeffs / dftpav_wire_pack take them */
+  double *coeff_dt;     /* [Q][max_seg] the winner's piece durations (piece_dt of dftpav_batch_coeffs) */
+  double *r_final_cost; /* [Q][R] per restart, as dftpav_batch_results / dftpav_batch_validate */
+  int *r_status, *r_success, *r_iters, *r_evals, *r_collision, *r_first_sample; /* [Q][R] */
+  int *search_status, *search_iters, *search_path_len;                          /* [Q] as dftpav_search_out */
+} dftpav_plan_out;
+int dftpav_planner_create(dftpav_handle *h, int max_queries, int n_restarts, dftpav_planner **out);
+void dftpav_planner_destroy(dftpav_planner *p);
+/* start_states / end_states [Q][4] (x, y, yaw, v), start_ctrl [Q][2]; t_now: `now` of OptimizeTrajectory.
+ * DFTPAV_E_INVALID without a map, for Q > max_queries or bad parameters; the planner stays usable. */
+int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *pp, const double *start_states, const double *start_ctrl,
+                        const double *end_states, int Q, double t_now, const dftpav_plan_out *out);
+/* n_batches: batches the planner holds (one per layout met so far); n_groups / group_sizes [max_queries]: the layout groups of
+ * the last call, in order of first appearance; stage_ms [4]: device time of the last call's search, resampling, groups
+ * (pack to selection) and everything together.  Any pointer may be NULL. */
+int dftpav_planner_info(dftpav_planner *p, int *n_batches, int *n_groups, int *group_sizes, float *stage_ms);
+/* The grouping rule, pure host code: query q with search_status[q] == DFTPAV_SEARCH_REACH_END and 1 <= n_seg[q] <= max_seg
+ * joins the group of the first query with the same n_seg, singul[0 .. n_seg) and piece_nums[0 .. n_seg) (rows of max_seg
+ * ints); group[q] = its index in order of first appearance, group_first[g] = that first query.  Otherwise group[q] = -1 and
+ * plan_status[q] = DFTPAV_PLAN_NO_PATH (not REACH_END) or DFTPAV_PLAN_TOO_MANY_SEGMENTS; grouped queries get DFTPAV_PLAN_OK.
+ * plan_status may be NULL.  n_groups receives the number of groups. */
+int dftpav_plan_group_layouts(int Q, int max_seg, const int *search_status, const int *n_seg, const int *singul,
+                              const int *piece_nums, int *group, int *group_first, int *n_groups, int *plan_status);
+/* Test hook: the selection rule on caller-supplied arrays [n_query][n_restarts]: among restarts with success != 0 and
+ * collision == 0 the smallest cost (a NaN never wins), ties to the lowest index, -1 if none. */
+int dftpav_debug_plan_select(dftpav_handle *h, int n_query, int n_restarts, const double *cost, const int *success,
+                             const int *collision, int *winner_out);
+
 /* One-shot convenience == OptimizeTrajectory for B trajectories. */
 int dftpav_solve_batch(dftpav_handle *h, const dftpav_layout *layout, int B,
                        const dftpav_batch_data *d, double *x, double *final_cost,
