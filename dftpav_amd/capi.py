@@ -41,6 +41,9 @@ EXPORTS = [
     "dftpav_default_search_params", "dftpav_kino_search",
     "dftpav_default_plan_params", "dftpav_planner_create", "dftpav_planner_destroy", "dftpav_plan_queries", "dftpav_planner_info",
     "dftpav_plan_group_layouts", "dftpav_debug_plan_select",
+    "dftpav_planner_install", "dftpav_planner_adopt", "dftpav_planner_set_history", "dftpav_planner_clear", "dftpav_planner_executing",
+    "dftpav_planner_padding",
+    "dftpav_replan_check", "dftpav_replan_tick", "dftpav_replan_last_ms",
 ]
 
 
@@ -426,6 +429,126 @@ class Planner:
         self.handle._check(fn(self._p, C.byref(nb), C.byref(ng), sizes.ctypes.data_as(C.c_void_p), ms.ctypes.data_as(C.c_void_p)),
                            "planner_info")
         return dict(n_batches=nb.value, group_sizes=sizes[:ng.value].copy(), stage_ms=ms.astype(np.float64))
+
+    # ---- the replan loop: the executing table (one slot per query of max_queries), its check and the tick
+    @staticmethod
+    def _ip(a):
+        return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+    def install(self, slots, n_seg, singul, piece_nums, coeff_dt, coeffs, end_states, t_start=0.0):
+        """dftpav_planner_install: plans from host arrays padded as pods.PlanOut (singul / piece_nums / coeff_dt [n][max_seg],
+        coeffs [n][max_seg * max_pieces][6][2], end_states [n][4]) become the executing plans of `slots`"""
+        sl = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        n = sl.shape[0]
+        ns = np.ascontiguousarray(n_seg, dtype=np.int32).reshape(n)
+        sg = np.ascontiguousarray(singul, dtype=np.int32).reshape(n, -1)
+        pn = np.ascontiguousarray(piece_nums, dtype=np.int32).reshape(n, -1)
+        dt = np.ascontiguousarray(coeff_dt, dtype=np.float64).reshape(n, -1)
+        co = np.ascontiguousarray(coeffs, dtype=np.float64).reshape(n, -1, 6, 2)
+        en = np.ascontiguousarray(end_states, dtype=np.float64).reshape(n, 4)
+        max_seg = sg.shape[1]
+        assert pn.shape == sg.shape == dt.shape and max_seg >= 1 and co.shape[1] % max_seg == 0
+        fn = lib().dftpav_planner_install
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_double]
+        self.handle._check(fn(self._p, n, self._ip(sl), max_seg, co.shape[1] // max_seg, self._ip(ns), self._ip(sg), self._ip(pn), self._ip(dt),
+                              self._ip(co), self._ip(en), float(t_start)), "planner_install")
+
+    def adopt(self, queries, slots, t_start=0.0, pp=None):
+        """dftpav_planner_adopt: the winners of the last plan() become the executing plans of `slots`; -> adopted [n] (0: the query
+        had no winner, its slot is untouched).  pp is not read (the library knows that plan()'s padding)."""
+        q = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1)
+        sl = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        assert q.shape == sl.shape
+        ad = np.zeros(q.shape[0], dtype=np.int32)
+        fn = lib().dftpav_planner_adopt
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
+        self.handle._check(fn(self._p, q.shape[0], self._ip(q), self._ip(sl), float(t_start), self._ip(ad)), "planner_adopt")
+        return ad
+
+    def set_history(self, slots, stamps, angles):
+        """dftpav_planner_set_history: the previous desired state (time stamp, angle) of the singularity filter of `slots`"""
+        sl = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        ts = np.ascontiguousarray(stamps, dtype=np.float64).reshape(-1)
+        an = np.ascontiguousarray(angles, dtype=np.float64).reshape(-1)
+        assert sl.shape == ts.shape == an.shape
+        fn = lib().dftpav_planner_set_history
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        self.handle._check(fn(self._p, sl.shape[0], self._ip(sl), self._ip(ts), self._ip(an)), "planner_set_history")
+
+    def clear(self, slots):
+        """dftpav_planner_clear: empties `slots`"""
+        sl = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        fn = lib().dftpav_planner_clear
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        self.handle._check(fn(self._p, sl.shape[0], self._ip(sl)), "planner_clear")
+
+    def padding(self):
+        """dftpav_planner_padding: (max_seg, max_pieces) of the executing table, (0, 0) before it was filled once"""
+        ms, mp = C.c_int(0), C.c_int(0)
+        fn = lib().dftpav_planner_padding
+        fn.argtypes = [C.c_void_p] * 3
+        self.handle._check(fn(self._p, C.byref(ms), C.byref(mp)), "planner_padding")
+        return ms.value, mp.value
+
+    def executing(self, slot):
+        """dftpav_planner_executing: dict(n_seg, singul, piece_nums, coeff_dt, coeffs, duration, start_time, end_time, end_state,
+        hist (time stamp, angle), have_hist) of a slot; n_seg 0: empty.  The arrays have the table's padding (padding())."""
+        ms, mp = self.padding()
+        i32 = np.int32
+        a = dict(n_seg=np.zeros(1, i32), singul=np.zeros(ms, i32), piece_nums=np.zeros(ms, i32), coeff_dt=np.zeros(ms),
+                 coeffs=np.zeros((ms * mp, 6, 2)), duration=np.zeros(ms), start_time=np.zeros(ms), end_time=np.zeros(ms),
+                 end_state=np.zeros(4), hist=np.zeros(2), have_hist=np.zeros(1, i32))
+        fn = lib().dftpav_planner_executing
+        fn.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 11
+        self.handle._check(fn(self._p, int(slot), *[self._ip(a[k]) for k in (
+            "n_seg", "singul", "piece_nums", "coeff_dt", "coeffs", "duration", "start_time", "end_time", "end_state", "hist", "have_hist")]),
+            "planner_executing")
+        a["n_seg"], a["have_hist"] = int(a["n_seg"][0]), int(a["have_hist"][0])
+        return a
+
+    def _slot_rows(self, a, width):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        assert a.shape == (self.max_queries, width), a.shape
+        return a
+
+    def check(self, t_now, budget=0.5, end_states=None, ego_states=None, check_dt=0.05, vertex_res=0.1):
+        """dftpav_replan_check: completion, CheckReplan and Replan's desired state of every slot at clock t_now -> the dict of
+        pods.ReplanOut.  end_states [slots][4] (None: the stored goals), ego_states [slots][6] x, y, angle, v, steer, acc (None)."""
+        from .pods import ReplanOut
+        en, eg = self._slot_rows(end_states, 4), self._slot_rows(ego_states, 6)
+        out = ReplanOut(self.max_queries)
+        fn = lib().dftpav_replan_check
+        fn.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p]
+        self.handle._check(fn(self._p, float(t_now), float(budget), self._ip(en), self._ip(eg), float(check_dt), float(vertex_res),
+                              C.byref(out.c)), "replan_check")
+        return out.arrays()
+
+    def tick(self, t_now, budget=0.5, end_states=None, ego_states=None, pp=None):
+        """dftpav_replan_tick: the check, then one plan() of the flagged slots from their desired states at t_now + budget, the
+        winners adopted into their slots -> dict(check = the dict of pods.ReplanOut, query_slot [n_queries], plan = the dict of
+        pods.PlanOut indexed by query)"""
+        from .pods import PlanOut, ReplanOut
+        en, eg = self._slot_rows(end_states, 4), self._slot_rows(ego_states, 6)
+        pp = pp if pp is not None else default_plan_params()
+        S = self.max_queries
+        chk, po = ReplanOut(S), PlanOut(S, self.n_restarts, pp.max_seg, pp.max_pieces)
+        qslot, nq = np.zeros(S, dtype=np.int32), C.c_int(0)
+        fn = lib().dftpav_replan_tick
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double] + [C.c_void_p] * 6
+        self.handle._check(fn(self._p, C.byref(pp), float(t_now), float(budget), self._ip(en), self._ip(eg), C.byref(chk.c),
+                              self._ip(qslot), C.byref(nq), C.byref(po.c)), "replan_tick")
+        n = nq.value
+        return dict(check=chk.arrays(), query_slot=qslot[:n].copy(), plan={k: v[:n].copy() for k, v in po.arrays().items()})
+
+    def replan_last_ms(self):
+        """dftpav_replan_last_ms: (device ms of the last check kernel, of the last tick from its check to its adoption)"""
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        fn = lib().dftpav_replan_last_ms
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        self.handle._check(fn(self._p, C.byref(a), C.byref(b)), "replan_last_ms")
+        return float(a.value), float(b.value)
 
     def close(self):
         if self._p:

@@ -58,6 +58,8 @@ hipError_t launch_plan_paths(const int *status, const int *path_len, const int *
                              hipStream_t stream);
 hipError_t launch_plan_pack(const PlanPackArgs &A, hipStream_t stream);
 hipError_t launch_plan_select(const PlanSelectArgs &A, hipStream_t stream);
+hipError_t launch_replan_check(const ReplanArgs &A, hipStream_t stream);
+hipError_t launch_exec_adopt(const ExecAdoptArgs &A, hipStream_t stream);
 hipError_t launch_corridor_layout(const double *raw, double *out, int B, int Npts, int H, int NptsPad, hipStream_t stream);
 hipError_t launch_adopt(const DevBatch &D, const DevBatch &prev, hipStream_t stream);
 // solver_ref.hip: the same path in the reference's own floating-point order
@@ -2924,6 +2926,25 @@ struct dftpav_planner {
   // host staging of the tables that decide the grouping
   std::vector<int> h_sints, h_nseg, h_singul, h_pn, h_nstates, h_skip, h_members, h_minit;
   std::vector<double> h_dt, h_vt;
+  // ---- the replan loop (dftpav_planner_install ... dftpav_replan_tick)
+  // what the last dftpav_plan_queries call left behind for dftpav_planner_adopt: its size and paddings, per query the final
+  // plan_status and winner, and the goals
+  int last_Q = 0, last_MS = 0, last_MP = 0;
+  std::vector<int> last_status, last_winner;
+  std::vector<double> last_goal;
+  // the executing table: one allocation of its own (the arena above is carved again when the paddings of a call change)
+  unsigned char *d_exec = nullptr;
+  ExecTable T{};
+  std::vector<int> h_occupied;  // host mirror: n_seg of every slot
+  std::vector<double> h_goal;   // host mirror: the stored goals [slots][4]
+  // outputs of the check, its two tables and its inputs: one allocation
+  unsigned char *d_rc = nullptr;
+  int *d_rc_int = nullptr, *d_pairs = nullptr;
+  double *d_rc_des = nullptr, *d_rc_st = nullptr, *d_rc_ct = nullptr, *d_rc_goal = nullptr, *d_rc_ego = nullptr, *d_rc_tab = nullptr;
+  int rc_n_t = 0, rc_n_v = 0;
+  double rc_dt = 0.0, rc_res = 0.0; // what d_rc_tab was tabulated for
+  hipEvent_t rev[4] = {nullptr, nullptr, nullptr, nullptr}; // check start / end, tick start / end
+  bool check_timed = false, tick_timed = false;
 };
 
 extern "C" int dftpav_planner_create(dftpav_handle *h, int max_queries, int n_restarts, dftpav_planner **out) {
@@ -2943,6 +2964,15 @@ extern "C" int dftpav_planner_create(dftpav_handle *h, int max_queries, int n_re
       delete p;
       return DFTPAV_E_HIP;
     }
+  for (auto &e : p->rev)
+    if (hipEventCreate(&e) != hipSuccess) {
+      h->err = "dftpav_planner_create: hipEventCreate";
+      for (auto &f : p->ev) (void)hipEventDestroy(f);
+      for (auto &f : p->rev)
+        if (f) (void)hipEventDestroy(f);
+      delete p;
+      return DFTPAV_E_HIP;
+    }
   *out = p;
   return DFTPAV_OK;
 }
@@ -2952,7 +2982,11 @@ extern "C" void dftpav_planner_destroy(dftpav_planner *p) {
   (void)hipStreamSynchronize(p->h->stream);
   for (auto &e : p->cache) dftpav_batch_destroy(e.b);
   if (p->d_arena) (void)hipFree(p->d_arena);
+  if (p->d_exec) (void)hipFree(p->d_exec);
+  if (p->d_rc) (void)hipFree(p->d_rc);
   for (auto &e : p->ev)
+    if (e) (void)hipEventDestroy(e);
+  for (auto &e : p->rev)
     if (e) (void)hipEventDestroy(e);
   delete p;
 }
@@ -3100,6 +3134,7 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
     return DFTPAV_E_INVALID;
   p->group_sizes.clear();
   p->timed = false;
+  p->last_Q = 0; // nothing to adopt until this call has ended well
   if (Q == 0) return DFTPAV_OK;
   if (!start_states || !start_ctrl || !end_states) return DFTPAV_E_INVALID;
   SearchSetup U;
@@ -3351,6 +3386,13 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
   if (out->search_status) std::memcpy(out->search_status, s_status, sizeof(int) * nq);
   if (out->search_iters) std::memcpy(out->search_iters, s_iters, sizeof(int) * nq);
   if (out->search_path_len) std::memcpy(out->search_path_len, s_len, sizeof(int) * nq);
+  // what dftpav_planner_adopt needs of this call (the winners' pieces stay where they are, in the arena)
+  p->last_status = status;
+  p->last_winner = winner;
+  p->last_goal.assign(end_states, end_states + 4 * nq);
+  p->last_MS = MS;
+  p->last_MP = MP;
+  p->last_Q = Q;
   return DFTPAV_OK;
 }
 
@@ -3389,4 +3431,440 @@ extern "C" int dftpav_debug_plan_select(dftpav_handle *h, int n_query, int n_res
   if (d_cost) (void)hipFree(d_cost);
   if (d_int) (void)hipFree(d_int);
   return rc;
+}
+
+// ------------------------------------------------- the replan loop: the executing table, its check and the tick (replan.hip)
+// TrajPlannerServer's 20 Hz loop (traj_server_ros.cpp:130-192, 359-501) for every slot of a planner at once.  The table lives in
+// device memory; the host mirrors what it needs to pack queries without a read-back: which slots are occupied, and their goals.
+extern "C" int dftpav_abi_sizeof_replan_out(void) { return (int)sizeof(dftpav_replan_out); }
+
+// the table, allocated (and zeroed: every slot empty) by the first call that fills it; later calls must bring the same padding
+static int exec_table(dftpav_planner *p, int MS, int MP) {
+  dftpav_handle *h = p->h;
+  if (MS < 1 || MS > kMaxSeg || MP < 1 || MP > 1024) return DFTPAV_E_INVALID;
+  if (p->d_exec) return (p->T.max_seg == MS && p->T.max_pieces == MP) ? DFTPAV_OK : DFTPAV_E_INVALID;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t S = (size_t)p->max_queries, ms = (size_t)MS, mp = (size_t)MP;
+  ExecTable T{};
+  T.n_slots = p->max_queries;
+  T.max_seg = MS;
+  T.max_pieces = MP;
+  unsigned char *base = nullptr;
+  size_t used = 0;
+  for (int pass = 0; pass < 2; pass++) { // measure, then carve
+    used = 0;
+    auto take = [&](size_t bytes) {
+      void *r = pass ? (void *)(base + used) : nullptr;
+      used += (bytes + 255) / 256 * 256;
+      return r;
+    };
+    T.coeffs = (double *)take(sizeof(double) * S * ms * mp * 12);
+    T.coeff_dt = (double *)take(sizeof(double) * S * ms);
+    T.duration = (double *)take(sizeof(double) * S * ms);
+    T.start_time = (double *)take(sizeof(double) * S * ms);
+    T.end_time = (double *)take(sizeof(double) * S * ms);
+    T.end_state = (double *)take(sizeof(double) * S * 4);
+    T.hist = (double *)take(sizeof(double) * S * 2);
+    T.n_seg = (int *)take(sizeof(int) * S);
+    T.singul = (int *)take(sizeof(int) * S * ms);
+    T.piece_nums = (int *)take(sizeof(int) * S * ms);
+    T.have_hist = (int *)take(sizeof(int) * S);
+    if (pass == 0) {
+      HIPCHK(h, hipMalloc(&base, used));
+      if (hipMemsetAsync(base, 0, used, h->stream) != hipSuccess) {
+        (void)hipFree(base);
+        h->err = "dftpav_planner: hipMemsetAsync of the executing table";
+        return DFTPAV_E_HIP;
+      }
+    }
+  }
+  p->d_exec = base;
+  p->T = T;
+  p->h_occupied.assign(S, 0);
+  p->h_goal.assign(4 * S, 0.0);
+  return DFTPAV_OK;
+}
+
+// slots [n]: each inside the table, none twice
+static bool slots_valid(const dftpav_planner *p, int n, const int *slots) {
+  std::vector<char> seen((size_t)p->max_queries, 0);
+  for (int i = 0; i < n; i++) {
+    if (slots[i] < 0 || slots[i] >= p->max_queries || seen[slots[i]]) return false;
+    seen[slots[i]] = 1;
+  }
+  return true;
+}
+
+extern "C" int dftpav_planner_install(dftpav_planner *p, int n, const int *slots, int max_seg, int max_pieces, const int *n_seg,
+                                      const int *singul, const int *piece_nums, const double *coeff_dt, const double *coeffs,
+                                      const double *end_states, double t_start) {
+  if (!p || n < 0 || n > p->max_queries) return DFTPAV_E_INVALID;
+  if (n > 0 && (!slots || !n_seg || !singul || !piece_nums || !coeff_dt || !coeffs || !end_states)) return DFTPAV_E_INVALID;
+  if (max_seg < 1 || max_seg > kMaxSeg || max_pieces < 1 || max_pieces > 1024) return DFTPAV_E_INVALID;
+  if (p->d_exec && (p->T.max_seg != max_seg || p->T.max_pieces != max_pieces)) return DFTPAV_E_INVALID;
+  if (!slots_valid(p, n, slots)) return DFTPAV_E_INVALID;
+  const size_t MS = (size_t)max_seg, MP = (size_t)max_pieces;
+  for (int i = 0; i < n; i++) {
+    if (n_seg[i] < 1 || n_seg[i] > max_seg) return DFTPAV_E_INVALID;
+    for (int j = 0; j < n_seg[i]; j++) {
+      const int N = piece_nums[(size_t)i * MS + j];
+      if (N < 1 || N > max_pieces) return DFTPAV_E_INVALID; // so the pieces of a plan fit its row of max_seg * max_pieces
+    }
+  }
+  if (int rc = exec_table(p, max_seg, max_pieces)) return rc;
+  if (n == 0) return DFTPAV_OK;
+  dftpav_handle *h = p->h;
+  HIPCHK(h, hipSetDevice(h->device));
+  const ExecTable &T = p->T;
+  std::vector<int> sg(MS), pn(MS);
+  std::vector<double> dtv(MS), dur(MS), st(MS), en(MS);
+  for (int i = 0; i < n; i++) {
+    const size_t s = (size_t)slots[i];
+    const int M = n_seg[i];
+    double world = t_start;
+    for (size_t j = 0; j < MS; j++) {
+      const bool used = (int)j < M;
+      sg[j] = used ? singul[(size_t)i * MS + j] : 0;
+      pn[j] = used ? piece_nums[(size_t)i * MS + j] : 0;
+      dtv[j] = used ? coeff_dt[(size_t)i * MS + j] : 0.0;
+      double d = 0.0; // Trajectory::getTotalDuration: the piece durations summed in order
+      for (int k = 0; k < pn[j]; k++) d += dtv[j];
+      dur[j] = used ? d : 0.0;
+      st[j] = used ? world : 0.0;          // traj_container.hpp:58-73: start_time, then end_time = start_time + duration
+      en[j] = used ? world + d : 0.0;
+      if (used) world = world + d;         // traj_manager.cpp:618-625: the next segment starts at that end
+    }
+    const int zero = 0;
+    const double hist0[2] = {0.0, 0.0};
+    // (pageable host memory: each copy has left its source when the call returns)
+    HIPCHK(h, hipMemcpyAsync(T.coeffs + s * MS * MP * 12, coeffs + (size_t)i * MS * MP * 12, sizeof(double) * MS * MP * 12, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(T.coeff_dt + s * MS, dtv.data(), sizeof(double) * MS, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(T.duration + s * MS, dur.data(), sizeof(double) * MS, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(T.start_time + s * MS, st.data(), sizeof(double) * MS, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(T.end_time + s * MS, en.data(), sizeof(double) * MS, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(T.end_state + s * 4, end_states + 4 * (size_t)i, sizeof(double) * 4, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(T.hist + s * 2, hist0, sizeof(double) * 2, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(T.singul + s * MS, sg.data(), sizeof(int) * MS, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(T.piece_nums + s * MS, pn.data(), sizeof(int) * MS, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(T.have_hist + s, &zero, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(T.n_seg + s, &M, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream)); // the staging vectors are reused by the next plan
+    p->h_occupied[s] = M;
+    std::memcpy(&p->h_goal[4 * s], end_states + 4 * (size_t)i, sizeof(double) * 4);
+  }
+  return DFTPAV_OK;
+}
+
+// the winners of the last call into their slots; d_desired: the slots' new filter history, or nullptr for none
+static int adopt_impl(dftpav_planner *p, int n, const int *queries, const int *slots, double t_start, const double *d_desired, int *adopted) {
+  dftpav_handle *h = p->h;
+  if (p->last_Q <= 0) return DFTPAV_E_INVALID; // no call of dftpav_plan_queries to adopt from
+  if (!slots_valid(p, n, slots)) return DFTPAV_E_INVALID;
+  for (int i = 0; i < n; i++)
+    if (queries[i] < 0 || queries[i] >= p->last_Q) return DFTPAV_E_INVALID;
+  if (int rc = exec_table(p, p->last_MS, p->last_MP)) return rc;
+  std::vector<int> pairs;
+  for (int i = 0; i < n; i++) {
+    const int q = queries[i];
+    const bool ok = p->last_status[q] == DFTPAV_PLAN_OK && p->last_winner[q] >= 0;
+    if (adopted) adopted[i] = ok ? 1 : 0;
+    if (!ok) continue;
+    pairs.push_back(q);
+    pairs.push_back(slots[i]);
+  }
+  const int na = (int)pairs.size() / 2;
+  if (na == 0) return DFTPAV_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipMemcpyAsync(p->d_pairs, pairs.data(), sizeof(int) * pairs.size(), hipMemcpyHostToDevice, h->stream));
+  ExecAdoptArgs A{};
+  A.T = p->T;
+  A.pairs = p->d_pairs;
+  A.n = na;
+  A.q_n_seg = p->fe.n_seg;
+  A.q_singul = p->fe.singul;
+  A.q_piece_nums = p->fe.piece_nums;
+  A.q_dt = p->d_wdt;
+  A.q_coeffs = p->d_wcoef;
+  A.q_goal = p->d_en;
+  A.desired = d_desired;
+  A.t_start = t_start;
+  HIPCHK(h, launch_exec_adopt(A, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream)); // `pairs` has left the host; the table is current when the call returns
+  for (int k = 0; k < na; k++) {
+    const int q = pairs[2 * k], s = pairs[2 * k + 1];
+    p->h_occupied[s] = p->h_nseg[q];
+    std::memcpy(&p->h_goal[4 * (size_t)s], &p->last_goal[4 * (size_t)q], sizeof(double) * 4);
+  }
+  return DFTPAV_OK;
+}
+
+// the device buffers of the check: outputs, inputs and the (query, slot) pairs of an adoption
+static int replan_buffers(dftpav_planner *p) {
+  if (p->d_rc) return DFTPAV_OK;
+  dftpav_handle *h = p->h;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t S = (size_t)p->max_queries;
+  unsigned char *base = nullptr;
+  size_t used = 0;
+  for (int pass = 0; pass < 2; pass++) {
+    used = 0;
+    auto take = [&](size_t bytes) {
+      void *r = pass ? (void *)(base + used) : nullptr;
+      used += (bytes + 255) / 256 * 256;
+      return r;
+    };
+    p->d_rc_des = (double *)take(sizeof(double) * 8 * S);
+    p->d_rc_st = (double *)take(sizeof(double) * 4 * S);
+    p->d_rc_ct = (double *)take(sizeof(double) * 2 * S);
+    p->d_rc_goal = (double *)take(sizeof(double) * 4 * S);
+    p->d_rc_ego = (double *)take(sizeof(double) * 6 * S);
+    p->d_rc_tab = (double *)take(sizeof(double) * (4096 + 4096));
+    p->d_rc_int = (int *)take(sizeof(int) * kRcInts * S);
+    p->d_pairs = (int *)take(sizeof(int) * 2 * S);
+    if (pass == 0) HIPCHK(h, hipMalloc(&base, used));
+  }
+  p->d_rc = base;
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_planner_adopt(dftpav_planner *p, int n, const int *queries, const int *slots, double t_start, int *adopted) {
+  if (!p || n < 0 || n > p->max_queries || (n > 0 && (!queries || !slots))) return DFTPAV_E_INVALID;
+  if (p->d_exec && p->last_Q > 0 && (p->T.max_seg != p->last_MS || p->T.max_pieces != p->last_MP)) return DFTPAV_E_INVALID;
+  if (int rc = replan_buffers(p)) return rc;
+  return adopt_impl(p, n, queries, slots, t_start, nullptr, adopted);
+}
+
+extern "C" int dftpav_planner_set_history(dftpav_planner *p, int n, const int *slots, const double *stamps, const double *angles) {
+  if (!p || n < 0 || n > p->max_queries || (n > 0 && (!slots || !stamps || !angles))) return DFTPAV_E_INVALID;
+  if (!p->d_exec || !slots_valid(p, n, slots)) return DFTPAV_E_INVALID;
+  for (int i = 0; i < n; i++)
+    if (!p->h_occupied[slots[i]]) return DFTPAV_E_INVALID;
+  dftpav_handle *h = p->h;
+  HIPCHK(h, hipSetDevice(h->device));
+  const int one = 1;
+  for (int i = 0; i < n; i++) {
+    const double hv[2] = {stamps[i], angles[i]};
+    HIPCHK(h, hipMemcpyAsync(p->T.hist + 2 * (size_t)slots[i], hv, sizeof(hv), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(p->T.have_hist + slots[i], &one, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_planner_clear(dftpav_planner *p, int n, const int *slots) {
+  if (!p || n < 0 || n > p->max_queries || (n > 0 && !slots)) return DFTPAV_E_INVALID;
+  if (!slots_valid(p, n, slots)) return DFTPAV_E_INVALID;
+  if (!p->d_exec) return DFTPAV_OK; // nothing was ever installed: every slot is empty
+  dftpav_handle *h = p->h;
+  HIPCHK(h, hipSetDevice(h->device));
+  const ExecTable &T = p->T;
+  const size_t MS = (size_t)T.max_seg, MP = (size_t)T.max_pieces;
+  for (int i = 0; i < n; i++) {
+    const size_t s = (size_t)slots[i];
+    HIPCHK(h, hipMemsetAsync(T.n_seg + s, 0, sizeof(int), h->stream));
+    HIPCHK(h, hipMemsetAsync(T.have_hist + s, 0, sizeof(int), h->stream));
+    HIPCHK(h, hipMemsetAsync(T.singul + s * MS, 0, sizeof(int) * MS, h->stream));
+    HIPCHK(h, hipMemsetAsync(T.piece_nums + s * MS, 0, sizeof(int) * MS, h->stream));
+    HIPCHK(h, hipMemsetAsync(T.coeff_dt + s * MS, 0, sizeof(double) * MS, h->stream));
+    HIPCHK(h, hipMemsetAsync(T.duration + s * MS, 0, sizeof(double) * MS, h->stream));
+    HIPCHK(h, hipMemsetAsync(T.start_time + s * MS, 0, sizeof(double) * MS, h->stream));
+    HIPCHK(h, hipMemsetAsync(T.end_time + s * MS, 0, sizeof(double) * MS, h->stream));
+    HIPCHK(h, hipMemsetAsync(T.end_state + s * 4, 0, sizeof(double) * 4, h->stream));
+    HIPCHK(h, hipMemsetAsync(T.hist + s * 2, 0, sizeof(double) * 2, h->stream));
+    HIPCHK(h, hipMemsetAsync(T.coeffs + s * MS * MP * 12, 0, sizeof(double) * MS * MP * 12, h->stream));
+    p->h_occupied[s] = 0;
+    for (int k = 0; k < 4; k++) p->h_goal[4 * s + k] = 0.0;
+  }
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_planner_executing(dftpav_planner *p, int slot, int *n_seg, int *singul, int *piece_nums, double *coeff_dt,
+                                        double *coeffs, double *duration, double *start_time, double *end_time, double *end_state,
+                                        double *hist, int *have_hist) {
+  if (!p || slot < 0 || slot >= p->max_queries) return DFTPAV_E_INVALID;
+  if (!p->d_exec) { // nothing was ever installed: the slot is empty, and no padding is known to size the arrays by
+    if (n_seg) *n_seg = 0;
+    if (have_hist) *have_hist = 0;
+    return DFTPAV_OK;
+  }
+  dftpav_handle *h = p->h;
+  HIPCHK(h, hipSetDevice(h->device));
+  const ExecTable &T = p->T;
+  const size_t MS = (size_t)T.max_seg, MP = (size_t)T.max_pieces, s = (size_t)slot;
+  auto fetch = [&](void *dst, const void *src, size_t bytes) { return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess; };
+  HIPCHK(h, fetch(n_seg, T.n_seg + s, sizeof(int)));
+  HIPCHK(h, fetch(singul, T.singul + s * MS, sizeof(int) * MS));
+  HIPCHK(h, fetch(piece_nums, T.piece_nums + s * MS, sizeof(int) * MS));
+  HIPCHK(h, fetch(coeff_dt, T.coeff_dt + s * MS, sizeof(double) * MS));
+  HIPCHK(h, fetch(coeffs, T.coeffs + s * MS * MP * 12, sizeof(double) * MS * MP * 12));
+  HIPCHK(h, fetch(duration, T.duration + s * MS, sizeof(double) * MS));
+  HIPCHK(h, fetch(start_time, T.start_time + s * MS, sizeof(double) * MS));
+  HIPCHK(h, fetch(end_time, T.end_time + s * MS, sizeof(double) * MS));
+  HIPCHK(h, fetch(end_state, T.end_state + s * 4, sizeof(double) * 4));
+  HIPCHK(h, fetch(hist, T.hist + s * 2, sizeof(double) * 2));
+  HIPCHK(h, fetch(have_hist, T.have_hist + s, sizeof(int)));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_planner_padding(dftpav_planner *p, int *max_seg, int *max_pieces) {
+  if (!p) return DFTPAV_E_INVALID;
+  if (max_seg) *max_seg = p->d_exec ? p->T.max_seg : 0;
+  if (max_pieces) *max_pieces = p->d_exec ? p->T.max_pieces : 0;
+  return DFTPAV_OK;
+}
+
+// enqueues the check on the handle's stream (results stay in the planner's device buffers)
+static int replan_check_enqueue(dftpav_planner *p, double t_now, double budget, const double *end_states, const double *ego_states,
+                                double check_dt, double vertex_res) {
+  dftpav_handle *h = p->h;
+  if (!h->d_cells || !p->d_exec) return DFTPAV_E_INVALID; // no map; no table
+  if (!(check_dt > 0.0) || !(vertex_res > 0.0) || !(t_now == t_now) || !(budget == budget)) return DFTPAV_E_INVALID;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (int rc = replan_buffers(p)) return rc;
+  const size_t S = (size_t)p->max_queries;
+  if (p->rc_dt != check_dt || p->rc_res != vertex_res) {
+    // the two running sums of the reference, tabulated (as dftpav_batch_validate): sample times | outline point spacing
+    std::vector<double> tab;
+    double t = 0.0;
+    for (int k = 0; k < 4096; k++, t += check_dt) tab.push_back(t);
+    const double longest = std::max(h->params.veh_length, h->params.veh_width) + 1.0;
+    for (double dl = vertex_res; dl < longest && tab.size() < 8192; dl += vertex_res) tab.push_back(dl);
+    if (tab.size() == 4096) tab.push_back(vertex_res);
+    if (tab.size() >= 8192) return DFTPAV_E_UNSUPPORTED; // an outline of 4096 points and more
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(p->d_rc_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
+    p->rc_n_t = 4096;
+    p->rc_n_v = (int)tab.size() - 4096;
+    p->rc_dt = check_dt;
+    p->rc_res = vertex_res;
+  }
+  if (end_states) HIPCHK(h, hipMemcpyAsync(p->d_rc_goal, end_states, sizeof(double) * 4 * S, hipMemcpyHostToDevice, h->stream));
+  if (ego_states) HIPCHK(h, hipMemcpyAsync(p->d_rc_ego, ego_states, sizeof(double) * 6 * S, hipMemcpyHostToDevice, h->stream));
+  ReplanArgs A{};
+  A.T = p->T;
+  A.cells = h->d_cells;
+  A.size_x = h->map.size_x;
+  A.size_y = h->map.size_y;
+  A.resolution = h->map.resolution;
+  A.origin_x = h->map.origin_x;
+  A.origin_y = h->map.origin_y;
+  A.veh_width = h->params.veh_width;
+  A.veh_length = h->params.veh_length;
+  A.veh_dcr = h->params.veh_d_cr;
+  A.wheel_base = h->params.veh_wheel_base;
+  A.t_tab = p->d_rc_tab;
+  A.n_t = p->rc_n_t;
+  A.sample_dt = check_dt;
+  A.v_tab = p->d_rc_tab + p->rc_n_t;
+  A.n_v = p->rc_n_v;
+  A.t_now = t_now;
+  A.budget = budget;
+  A.goals = end_states ? p->d_rc_goal : nullptr;
+  A.ego = ego_states ? p->d_rc_ego : nullptr;
+  A.o_int = p->d_rc_int;
+  A.desired = p->d_rc_des;
+  A.start_state = p->d_rc_st;
+  A.start_ctrl = p->d_rc_ct;
+  HIPCHK(h, hipEventRecord(p->rev[0], h->stream));
+  HIPCHK(h, launch_replan_check(A, h->stream));
+  HIPCHK(h, hipEventRecord(p->rev[1], h->stream));
+  p->check_timed = true;
+  return DFTPAV_OK;
+}
+
+// copies of the check's results for the caller (enqueued; the caller of this function waits for the stream)
+static int replan_check_fetch(dftpav_planner *p, const dftpav_replan_out *out) {
+  if (!out) return DFTPAV_OK;
+  dftpav_handle *h = p->h;
+  const size_t S = (size_t)p->max_queries;
+  auto fetch = [&](void *dst, const void *src, size_t bytes) { return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess; };
+  int *const io[kRcInts] = {out->occupied, out->complete, out->exe_index, out->is_close_turnpoint, out->is_near, out->target_moved,
+                            out->collision, out->first_sample, out->replan};
+  for (int k = 0; k < kRcInts; k++) HIPCHK(h, fetch(io[k], p->d_rc_int + (size_t)k * S, sizeof(int) * S));
+  HIPCHK(h, fetch(out->desired, p->d_rc_des, sizeof(double) * 8 * S));
+  HIPCHK(h, fetch(out->start_state, p->d_rc_st, sizeof(double) * 4 * S));
+  HIPCHK(h, fetch(out->start_ctrl, p->d_rc_ct, sizeof(double) * 2 * S));
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_replan_check(dftpav_planner *p, double t_now, double budget, const double *end_states, const double *ego_states,
+                                   double check_dt, double vertex_res, const dftpav_replan_out *out) {
+  if (!p) return DFTPAV_E_INVALID;
+  dftpav_handle *h = p->h;
+  if (int rc = replan_check_enqueue(p, t_now, budget, end_states, ego_states, check_dt, vertex_res)) return rc;
+  if (int rc = replan_check_fetch(p, out)) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_replan_tick(dftpav_planner *p, const dftpav_plan_params *pp, double t_now, double budget, const double *end_states,
+                                  const double *ego_states, const dftpav_replan_out *check_out, int *query_slot, int *n_queries,
+                                  const dftpav_plan_out *plan_out) {
+  if (n_queries) *n_queries = 0;
+  if (!p || !pp) return DFTPAV_E_INVALID;
+  if (ego_states && !end_states) return DFTPAV_E_INVALID; // an empty slot has no stored goal
+  dftpav_handle *h = p->h;
+  // the padding of the plans to come must be the table's: checked before anything runs
+  if (p->d_exec && (p->T.max_seg != pp->max_seg || p->T.max_pieces != pp->max_pieces)) return DFTPAV_E_INVALID;
+  if (!p->d_exec) { // an all-empty table is a valid start (every vehicle waits for its first plan)
+    if (int rc = exec_table(p, pp->max_seg, pp->max_pieces)) return rc;
+  }
+  p->tick_timed = false;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipEventRecord(p->rev[2], h->stream));
+  if (int rc = replan_check_enqueue(p, t_now, budget, end_states, ego_states, pp->check_dt, pp->vertex_res)) return rc;
+  // ---- the tick's one extra wait: replan, start_state, start_ctrl (with whatever else of the check the caller asked for)
+  const size_t S = (size_t)p->max_queries;
+  std::vector<int> flag(S, 0);
+  std::vector<double> st(4 * S), ct(2 * S);
+  HIPCHK(h, hipMemcpyAsync(flag.data(), p->d_rc_int + (size_t)kRcReplan * S, sizeof(int) * S, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(st.data(), p->d_rc_st, sizeof(double) * 4 * S, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(ct.data(), p->d_rc_ct, sizeof(double) * 2 * S, hipMemcpyDeviceToHost, h->stream));
+  if (int rc = replan_check_fetch(p, check_out)) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  // ---- the flagged slots, in rising slot order, are the queries
+  std::vector<int> slot_of;
+  std::vector<double> qs, qc, qe;
+  for (size_t s = 0; s < S; s++) {
+    if (!flag[s]) continue;
+    slot_of.push_back((int)s);
+    qs.insert(qs.end(), st.begin() + 4 * s, st.begin() + 4 * s + 4);
+    qc.insert(qc.end(), ct.begin() + 2 * s, ct.begin() + 2 * s + 2);
+    const double *g = end_states ? end_states + 4 * s : &p->h_goal[4 * s];
+    qe.insert(qe.end(), g, g + 4);
+  }
+  const int nq = (int)slot_of.size();
+  if (n_queries) *n_queries = nq;
+  if (query_slot)
+    for (int q = 0; q < nq; q++) query_slot[q] = slot_of[q];
+  if (nq > 0) {
+    static const dftpav_plan_out none{};
+    const double stamp = t_now + budget; // desired_state.time_stamp, traj_server_ros.cpp:414; `now` of the plan, traj_manager.cpp:520
+    if (int rc = dftpav_plan_queries(p, pp, qs.data(), qc.data(), qe.data(), nq, stamp, plan_out ? plan_out : &none)) return rc;
+    std::vector<int> qi(nq);
+    for (int q = 0; q < nq; q++) qi[q] = q;
+    if (int rc = adopt_impl(p, nq, qi.data(), slot_of.data(), stamp, p->d_rc_des, nullptr)) return rc;
+  }
+  HIPCHK(h, hipEventRecord(p->rev[3], h->stream));
+  p->tick_timed = true;
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_replan_last_ms(dftpav_planner *p, float *check_ms, float *tick_ms) {
+  if (!p) return DFTPAV_E_INVALID;
+  dftpav_handle *h = p->h;
+  if (check_ms) *check_ms = 0.0f;
+  if (tick_ms) *tick_ms = 0.0f;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (check_ms && p->check_timed) {
+    HIPCHK(h, hipEventSynchronize(p->rev[1]));
+    HIPCHK(h, hipEventElapsedTime(check_ms, p->rev[0], p->rev[1]));
+  }
+  if (tick_ms && p->tick_timed) {
+    HIPCHK(h, hipEventSynchronize(p->rev[3]));
+    HIPCHK(h, hipEventElapsedTime(tick_ms, p->rev[2], p->rev[3]));
+  }
+  return DFTPAV_OK;
 }

@@ -38,4 +38,50 @@ struct PlanSelectArgs {
   int *r_status, *r_success, *r_iters, *r_evals, *r_collision, *r_first_sample;
 };
 
+// the executing table of a planner (capi.cpp: dftpav_planner_install / _adopt): one row per slot, device pointers.  n_seg == 0: empty.
+// Padded as dftpav_plan_out: the pieces of a slot's segments follow one another in `coeffs`.
+struct ExecTable {
+  int n_slots, max_seg, max_pieces;
+  int *n_seg;                              // [slots]
+  int *singul, *piece_nums;                // [slots][max_seg]
+  double *coeff_dt;                        // [slots][max_seg] duration of a piece of each segment
+  double *coeffs;                          // [slots][max_seg * max_pieces][6][2]
+  double *duration, *start_time, *end_time; // [slots][max_seg] (traj_container.hpp:58-73)
+  double *end_state;                       // [slots][4] the goal the plan was made for
+  double *hist;                            // [slots][2] previous desired state: time stamp, angle
+  int *have_hist;                          // [slots]
+};
+
+// exec_adopt_kernel: the winners of the last dftpav_plan_queries call into slots of the table, device to device
+struct ExecAdoptArgs {
+  ExecTable T;
+  const int *pairs;         // [n][2] query, slot
+  int n;
+  const int *q_n_seg, *q_singul, *q_piece_nums; // the front end's rows of the call, by query
+  const double *q_dt, *q_coeffs;                // the winners' piece durations [Q][max_seg] and pieces [Q][max_seg * max_pieces][12]
+  const double *q_goal;                         // [Q][4]
+  const double *desired;                        // [slots][8] or nullptr: the slot's new filter history (stamp, angle); nullptr: none
+  double t_start;
+};
+
+// replan_check_kernel (replan.hip)
+enum { kRcOccupied = 0, kRcComplete, kRcExeIndex, kRcCloseTurn, kRcNear, kRcTargetMoved, kRcCollision, kRcFirstSample, kRcReplan, kRcInts };
+struct ReplanArgs {
+  ExecTable T;
+  const unsigned char *cells;
+  int size_x, size_y;
+  double resolution, origin_x, origin_y;
+  double veh_width, veh_length, veh_dcr, wheel_base;
+  const double *t_tab; // 0, dt, dt + dt, ...
+  int n_t;
+  double sample_dt;
+  const double *v_tab; // res, res + res, ...
+  int n_v;
+  double t_now, budget;
+  const double *goals; // [slots][4] or nullptr: the stored goals
+  const double *ego;   // [slots][6] x, y, angle, v, steer, acc, or nullptr
+  int *o_int;          // [kRcInts][slots]
+  double *desired, *start_state, *start_ctrl; // [slots][8], [slots][4], [slots][2]
+};
+
 } // namespace dftpav

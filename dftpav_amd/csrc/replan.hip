@@ -1,0 +1,339 @@
+// One tick of the replan loop for every executing plan of a planner's table (docs/NEXT_ROWS.md §4.15).
+//
+//   TrajPlannerServer::PlanCycleCallback, completion  traj_planner/src/traj_server_ros.cpp:149-158
+//   TrajPlannerServer::PublishData, exe_traj_index_   traj_server_ros.cpp:248-252
+//   TrajPlannerServer::CheckReplan                    traj_server_ros.cpp:359-402
+//   TrajPlannerServer::Replan, desired state          traj_server_ros.cpp:414, 445-461
+//   TrajPlannerServer::FilterSingularityState         traj_server_ros.cpp:335-356
+//   Trajectory::GetState / locatePieceIdx             plan_utils/poly_traj_utils.hpp:378-406, 510-528
+//   Piece::getPos / getdSigma / getddSigma / getStateExpPos   poly_traj_utils.hpp:77-87, 179-211, 303-340
+//   TrajPlanner::getKinoPath, start state and control traj_manager.cpp:74-75
+//   SemanticMapManager::CheckCollisionUsingPosAndYaw  semantic_map_manager.cc:639-662, shapes.cc:110-149
+//
+// One workgroup of 256 threads per slot; the layout (segments, pieces, directions) is read from the slot's own row of the
+// table, so plans of different layouts are checked in one launch.  Thread 0 makes the scalar decisions in the reference's
+// statements and order and reads the desired state; all threads then take the collision samples of CheckReplan exactly as
+// validate.hip takes them (tabulated running sums, an atomic minimum over the samples), so collision / first_sample are the
+// bits dftpav_batch_validate gives for the same plan.  The pose evaluation and the outline walk are restated here rather
+// than shared with validate.hip / states.hip: those kernels read a launch-wide DevLayout, this one a row of the table.
+// fp64, no contraction, cr_trig.h wherever the reference calls libm: bit-identical to oracle_replan/replan_oracle.cpp in
+// order 2.  The kernel writes nothing into the table.
+#include <hip/hip_runtime.h>
+
+#include "cr_trig.h"
+#include "plan_args.h"
+
+namespace dftpav {
+
+namespace {
+
+__device__ inline double rp_normalize_angle(double theta) { // calculations.cc:18-23
+  const double pi = 3.14159265358979323846;
+  double tmp = theta;
+  tmp -= (double)((theta >= pi) * 2) * pi;
+  tmp += (double)((theta < -pi) * 2) * pi;
+  return tmp;
+}
+
+__device__ inline bool rp_occupied(const ReplanArgs &A, double x, double y) {
+  const double cx = round((x - A.origin_x) / A.resolution), cy = round((y - A.origin_y) / A.resolution);
+  if (!(cx >= 0.0 && cx < (double)A.size_x && cy >= 0.0 && cy < (double)A.size_y)) return false;
+  return A.cells[(int)cx + A.size_x * (int)cy] == 80;
+}
+__device__ inline bool rp_edge_hits(const ReplanArgs &A, double ax, double ay, double bx, double by) {
+  const double dx = bx - ax, dy = by - ay;
+  const double norm = sqrt(dx * dx + dy * dy);
+  for (int j = 0; j < A.n_v; j++) {
+    const double dl = A.v_tab[j];
+    if (!(dl < norm)) break;
+    const double f = dl / norm;
+    if (rp_occupied(A, f * dx + ax, f * dy + ay)) return true;
+  }
+  return false;
+}
+
+// locatePieceIdx, poly_traj_utils.hpp:510-528, for a segment of N pieces of duration dtp each
+__device__ inline int rp_locate(int N, double dtp, double &tt) {
+  int idx = 0;
+  while (idx < N && tt > dtp) {
+    tt -= dtp;
+    idx++;
+  }
+  if (idx == N) {
+    idx--;
+    tt += dtp;
+  }
+  return idx;
+}
+__device__ inline void rp_pos(const double *c, double tt, double &px, double &py) { // Piece::getPos
+  px = 0.0;
+  py = 0.0;
+  double tn = 1.0;
+#pragma unroll
+  for (int k = 0; k <= 5; k++) {
+    px += tn * c[2 * k];
+    py += tn * c[2 * k + 1];
+    tn *= tt;
+  }
+}
+__device__ inline void rp_vel(const double *c, double tt, double &vx, double &vy) { // Piece::getdSigma
+  vx = 0.0;
+  vy = 0.0;
+  double tn = 1.0;
+#pragma unroll
+  for (int k = 1; k <= 5; k++) {
+    vx += (double)k * tn * c[2 * k];
+    vy += (double)k * tn * c[2 * k + 1];
+    tn *= tt;
+  }
+}
+__device__ inline void rp_acc(const double *c, double tt, double &ax, double &ay) { // Piece::getddSigma
+  ax = 0.0;
+  ay = 0.0;
+  double tn = 1.0;
+#pragma unroll
+  for (int k = 2; k <= 5; k++) {
+    ax += (double)((k - 1) * k) * tn * c[2 * k];
+    ay += (double)((k - 1) * k) * tn * c[2 * k + 1];
+    tn *= tt;
+  }
+}
+
+} // namespace
+
+__global__ void __launch_bounds__(256) replan_check_kernel(ReplanArgs A) {
+  __shared__ int s_count[kMaxSeg + 1];  // samples of the segments before segment i
+  __shared__ int s_piece0[kMaxSeg + 1]; // first piece of segment i in the slot's row
+  __shared__ int s_first, s_go, s_rule;
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const ExecTable &T = A.T;
+  const int S = T.n_slots, MS = T.max_seg;
+  const int *pn = T.piece_nums + (size_t)s * MS, *sg = T.singul + (size_t)s * MS;
+  const double *dtv = T.coeff_dt + (size_t)s * MS;
+  const double *cb = T.coeffs + (size_t)s * MS * T.max_pieces * 12;
+  const int M = T.n_seg[s];
+  if (tid == 0) {
+    const double *dur = T.duration + (size_t)s * MS, *st = T.start_time + (size_t)s * MS, *en = T.end_time + (size_t)s * MS;
+    int o[kRcInts];
+    for (int k = 0; k < kRcInts; k++) o[k] = 0;
+    o[kRcFirstSample] = -1;
+    double des[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    bool have_des = false;
+    int go = 0, rule = 0;
+    const double stamp = A.t_now + A.budget; // traj_server_ros.cpp:414
+    if (M == 0) {
+      // executing_traj_ == nullptr: CheckReplan returns true (:361), Replan plans from the ego state with the stamp (:411-416)
+      if (A.ego) {
+        const double *e = A.ego + 6 * (size_t)s;
+        o[kRcReplan] = 1;
+        des[0] = stamp; des[1] = e[0]; des[2] = e[1]; des[3] = e[2]; des[4] = 0.0; des[5] = e[3]; des[6] = e[5]; des[7] = e[4];
+        have_des = true;
+      }
+    } else {
+      o[kRcOccupied] = 1;
+      const int last = M - 1;
+      if (A.t_now > en[last]) { // :150
+        o[kRcComplete] = 1;
+      } else {
+        // exe_traj_index_, :248-252, derived from t_now (at t_now == the last end_time it stays on the last segment)
+        int exe = 0;
+        while (exe < last && en[exe] <= A.t_now) exe++;
+        o[kRcExeIndex] = exe;
+        int acc = 0, p0 = 0;
+        for (int i = 0; i < M; i++) {
+          s_piece0[i] = p0;
+          p0 += pn[i];
+          // number of samples t_k < dur: the table is increasing; past its end the running sum is continued (validate.hip)
+          const double d = dur[i];
+          int lo = 0, hi = A.n_t;
+          while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (A.t_tab[mid] < d) lo = mid + 1;
+            else hi = mid;
+          }
+          int cnt = lo;
+          if (cnt == A.n_t) {
+            for (double t = A.t_tab[A.n_t - 1] + A.sample_dt; t < d; t += A.sample_dt) cnt++;
+          }
+          s_count[i] = acc;
+          acc += cnt;
+        }
+        s_count[M] = acc;
+        s_piece0[M] = p0;
+        // CheckReplan, :366-383
+        const double *goal = (A.goals ? A.goals : T.end_state) + 4 * (size_t)s;
+        double ltx, lty;
+        {
+          double tt = dur[last];
+          const int idx = rp_locate(pn[last], dtv[last], tt);
+          rp_pos(cb + (size_t)(s_piece0[last] + idx) * 12, tt, ltx, lty);
+        }
+        double total = 0.0;
+        for (int i = 0; i < M; i++) total += dur[i];
+        int close_turn = 0;
+        if (exe != last) {
+          if ((en[exe] - A.t_now) < 2.5) close_turn = 1;
+        }
+        const int near = (en[last] - A.t_now) < 2 * total / 3.0 ? 1 : 0;
+        const double gx = ltx - goal[0], gy = lty - goal[1];
+        const int moved = sqrt(gx * gx + gy * gy) > 0.1 ? 1 : 0;
+        o[kRcCloseTurn] = close_turn;
+        o[kRcNear] = near;
+        o[kRcTargetMoved] = moved;
+        rule = (near && !close_turn && moved) ? 1 : 0;
+        // Replan, :445-458: the segment the stamp falls into, walked from exe_traj_index_
+        int pidx = exe;
+        while (true) {
+          if (stamp <= st[pidx] + dur[pidx]) {
+            break;
+          } else {
+            pidx++;
+            if (pidx >= M) {
+              pidx--;
+              break;
+            }
+          }
+        }
+        const double t = stamp - st[pidx];
+        // Trajectory::GetState, poly_traj_utils.hpp:378-406
+        double inner = t;
+        if (inner > dur[pidx]) inner = dur[pidx];
+        const int idx = rp_locate(pn[pidx], dtv[pidx], inner);
+        const double *c = cb + (size_t)(s_piece0[pidx] + idx) * 12;
+        double px, py, vx, vy, ax, ay;
+        rp_pos(c, inner, px, py);
+        rp_vel(c, inner, vx, vy);
+        rp_acc(c, inner, ax, ay);
+        const double sgn = (double)sg[pidx];
+        double angle = crt::atan2(sgn * vy, sgn * vx); // (the reference: libm; here correctly rounded, as oracle order 2)
+        const double vel = sgn * sqrt(vx * vx + vy * vy);
+        double curv = 0.0, ac = 0.0, steer = 0.0;
+        if (!(fabs(vel) < 1e-6)) {
+          curv = (vx * ay - vy * ax) / crt::cube_cr(vel); // (the reference: pow(vel, 3) of libm; here the correctly rounded cube)
+          ac = (vx * ax + vy * ay) / vel;
+          steer = crt::atan(A.wheel_base * curv);
+        }
+        if (T.have_hist[s]) { // FilterSingularityState against desired_state_hist_.back(), :335-356, :460
+          const double duration = stamp - T.hist[2 * (size_t)s];
+          const double hist_angle = T.hist[2 * (size_t)s + 1];
+          const double max_rate = 0x1.fffffffffffffp-1 / 2.85 * 0.1; // tan(M_PI / 4) correctly rounded (what glibc returns)
+          const double max_change = max_rate * duration;
+          if (fabs(vel) < 0.1 && fabs(rp_normalize_angle(angle - hist_angle)) > max_change) angle = hist_angle;
+        }
+        des[0] = stamp; des[1] = px; des[2] = py; des[3] = angle; des[4] = curv; des[5] = vel; des[6] = ac; des[7] = steer;
+        have_des = true;
+        go = 1;
+      }
+    }
+    for (int k = 0; k < kRcInts; k++) A.o_int[(size_t)k * S + s] = o[k];
+    for (int k = 0; k < 8; k++) A.desired[8 * (size_t)s + k] = des[k];
+    // getKinoPath, traj_manager.cpp:74-75: start_state << vec_position, angle, velocity; init_ctrl << steer, acceleration
+    A.start_state[4 * (size_t)s] = have_des ? des[1] : 0.0;
+    A.start_state[4 * (size_t)s + 1] = have_des ? des[2] : 0.0;
+    A.start_state[4 * (size_t)s + 2] = have_des ? des[3] : 0.0;
+    A.start_state[4 * (size_t)s + 3] = have_des ? des[5] : 0.0;
+    A.start_ctrl[2 * (size_t)s] = have_des ? des[7] : 0.0;
+    A.start_ctrl[2 * (size_t)s + 1] = have_des ? des[6] : 0.0;
+    s_first = 0x7fffffff;
+    s_go = go;
+    s_rule = rule;
+  }
+  __syncthreads();
+  if (!s_go) return; // an empty or completed slot: nothing else is computed (the whole workgroup leaves)
+  // the collision loop of CheckReplan, :385-397, sample by sample as validate.hip
+  const int total = s_count[M];
+  for (int q = tid; q < total; q += blockDim.x) {
+    int i = 0;
+    while (i + 1 < M && q >= s_count[i + 1]) i++;
+    const int k = q - s_count[i];
+    double t;
+    if (k < A.n_t) {
+      t = A.t_tab[k];
+    } else {
+      t = A.t_tab[A.n_t - 1];
+      for (int j = A.n_t - 1; j < k; j++) t += A.sample_dt;
+    }
+    double tt = t;
+    const int idx = rp_locate(pn[i], dtv[i], tt);
+    const double *c = cb + (size_t)(s_piece0[i] + idx) * 12;
+    double px, py, vx, vy;
+    rp_pos(c, tt, px, py);
+    rp_vel(c, tt, vx, vy);
+    const double sgn = (double)sg[i];
+    const double yaw = crt::atan2(sgn * vy, sgn * vx);
+    // CheckCollisionUsingPosAndYaw, semantic_map_manager.cc:639-662 + shapes.cc:116-147
+    double cs, sn;
+    crt::sincos(yaw, sn, cs);
+    const double W = A.veh_width, Lv = A.veh_length;
+    const double x = px + A.veh_dcr * cs, y = py + A.veh_dcr * sn;
+    const double c1x = x + 0.5 * Lv * cs + 0.5 * W * sn, c1y = y + 0.5 * Lv * sn - 0.5 * W * cs;
+    const double c2x = x + 0.5 * Lv * cs - 0.5 * W * sn, c2y = y + 0.5 * Lv * sn + 0.5 * W * cs;
+    const double c3x = x - 0.5 * Lv * cs - 0.5 * W * sn, c3y = y - 0.5 * Lv * sn + 0.5 * W * cs;
+    const double c4x = x - 0.5 * Lv * cs + 0.5 * W * sn, c4y = y - 0.5 * Lv * sn - 0.5 * W * cs;
+    const bool hit = rp_edge_hits(A, c1x, c1y, c2x, c2y) || rp_edge_hits(A, c2x, c2y, c3x, c3y) ||
+                     rp_edge_hits(A, c3x, c3y, c4x, c4y) || rp_edge_hits(A, c4x, c4y, c1x, c1y) || rp_occupied(A, c1x, c1y) ||
+                     rp_occupied(A, c2x, c2y) || rp_occupied(A, c3x, c3y) || rp_occupied(A, c4x, c4y);
+    if (hit) atomicMin(&s_first, q);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const bool any = s_first != 0x7fffffff;
+    A.o_int[(size_t)kRcCollision * S + s] = any ? 1 : 0;
+    A.o_int[(size_t)kRcFirstSample * S + s] = any ? s_first : -1;
+    A.o_int[(size_t)kRcReplan * S + s] = (s_rule || any) ? 1 : 0; // the early return of :381-383, then the loop
+  }
+}
+
+// The winners of a dftpav_plan_queries call into slots of the table: one workgroup per (query, slot) pair copies the pieces;
+// thread 0 copies the layout row and chains the times as TrajContainer::addSingulTraj does (traj_container.hpp:58-73,
+// traj_manager.cpp:618-625): duration = the piece durations summed in order, end = start + duration, the next segment
+// starts at that end.
+__global__ void __launch_bounds__(256) exec_adopt_kernel(ExecAdoptArgs A) {
+  const int q = A.pairs[2 * blockIdx.x], s = A.pairs[2 * blockIdx.x + 1], tid = threadIdx.x;
+  const ExecTable &T = A.T;
+  const int MS = T.max_seg;
+  const size_t row = (size_t)MS * T.max_pieces * 12;
+  const double *src = A.q_coeffs + (size_t)q * row;
+  double *dst = T.coeffs + (size_t)s * row;
+  for (size_t k = tid; k < row; k += blockDim.x) dst[k] = src[k];
+  if (tid == 0) {
+    const int M = A.q_n_seg[q];
+    T.n_seg[s] = M;
+    double world = A.t_start;
+    for (int i = 0; i < MS; i++) {
+      const bool used = i < M;
+      const int N = used ? A.q_piece_nums[(size_t)q * MS + i] : 0;
+      const double dtp = used ? A.q_dt[(size_t)q * MS + i] : 0.0;
+      T.singul[(size_t)s * MS + i] = used ? A.q_singul[(size_t)q * MS + i] : 0;
+      T.piece_nums[(size_t)s * MS + i] = N;
+      T.coeff_dt[(size_t)s * MS + i] = dtp;
+      double d = 0.0; // Trajectory::getTotalDuration
+      for (int p = 0; p < N; p++) d += dtp;
+      T.duration[(size_t)s * MS + i] = used ? d : 0.0;
+      T.start_time[(size_t)s * MS + i] = used ? world : 0.0;
+      T.end_time[(size_t)s * MS + i] = used ? world + d : 0.0;
+      if (used) world = world + d;
+    }
+    for (int k = 0; k < 4; k++) T.end_state[4 * (size_t)s + k] = A.q_goal[4 * (size_t)q + k];
+    if (A.desired) { // desired_state_hist_.push_back(desired_state), traj_server_ros.cpp:461
+      T.hist[2 * (size_t)s] = A.desired[8 * (size_t)s];
+      T.hist[2 * (size_t)s + 1] = A.desired[8 * (size_t)s + 3];
+      T.have_hist[s] = 1;
+    } else {
+      T.hist[2 * (size_t)s] = 0.0;
+      T.hist[2 * (size_t)s + 1] = 0.0;
+      T.have_hist[s] = 0;
+    }
+  }
+}
+
+hipError_t launch_replan_check(const ReplanArgs &A, hipStream_t stream) {
+  hipLaunchKernelGGL(replan_check_kernel, dim3(A.T.n_slots), dim3(256), 0, stream, A);
+  return hipGetLastError();
+}
+hipError_t launch_exec_adopt(const ExecAdoptArgs &A, hipStream_t stream) {
+  hipLaunchKernelGGL(exec_adopt_kernel, dim3(A.n), dim3(256), 0, stream, A);
+  return hipGetLastError();
+}
+
+} // namespace dftpav

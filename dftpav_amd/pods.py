@@ -283,3 +283,23 @@ class PlanOut:
 
     def arrays(self):
         return dict(self.a)
+
+
+class ReplanOutC(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in (
+        "occupied", "complete", "exe_index", "is_close_turnpoint", "is_near", "target_moved", "collision", "first_sample", "replan",
+        "desired", "start_state", "start_ctrl")]
+
+
+class ReplanOut:
+    """Owner of the output arrays of dftpav_replan_check (dftpav_replan_out): one row per slot."""
+    INTS = ("occupied", "complete", "exe_index", "is_close_turnpoint", "is_near", "target_moved", "collision", "first_sample", "replan")
+
+    def __init__(self, slots):
+        a = {k: np.zeros(slots, dtype=np.int32) for k in self.INTS}
+        a.update(desired=np.zeros((slots, 8)), start_state=np.zeros((slots, 4)), start_ctrl=np.zeros((slots, 2)))
+        self.a = a
+        self.c = ReplanOutC(*[a[n].ctypes.data for n, _ in ReplanOutC._fields_])
+
+    def arrays(self):
+        return dict(self.a)

@@ -711,6 +711,102 @@ int dftpav_plan_group_layouts(int Q, int max_seg, const int *search_status, cons
 int dftpav_debug_plan_select(dftpav_handle *h, int n_query, int n_restarts, const double *cost, const int *success,
                              const int *collision, int *winner_out);
 
+/* ---- the replan loop: a table of executing plans, checked and planned again once per tick ----------
+ * Replaces the 20 Hz loop of TrajPlannerServer for as many plans as the planner has slots (max_queries of
+ * dftpav_planner_create): PlanCycleCallback's completion test (traj_server_ros.cpp:149-158), CheckReplan (:359-402),
+ * the desired state of Replan (:414, :445-461, with Trajectory::GetState, poly_traj_utils.hpp:378-406, and
+ * FilterSingularityState, :335-356), the hand-over of that state to the planner (getKinoPath, traj_manager.cpp:74-75) and
+ * the swap of the new plan for the executing one (:171-178).  A slot is empty or holds one executing plan in device memory:
+ * its layout, pieces and piece durations padded as dftpav_plan_out, per gear segment duration / start_time / end_time
+ * chained as TrajContainer::addSingulTraj does (traj_container.hpp:58-73, traj_manager.cpp:618-625: duration = the piece
+ * durations summed in order, segment 0 starts at t_start, end_time = start_time + duration, the next segment starts at that
+ * end_time), the goal the plan was made for, and the previous desired state of the singularity filter (time stamp, angle).
+ * The padding (max_seg <= 8, max_pieces) is fixed by the first call that fills the table; another padding later is
+ * DFTPAV_E_INVALID.  Slots named twice in one call, slots outside [0, max_queries), n_seg outside [1, max_seg] and
+ * piece_nums outside [1, max_pieces] are DFTPAV_E_INVALID; a refused call changes nothing.
+ * NOT reproduced: Replan's busy-wait until the budget has passed with its "exceed time budget"
+ * refusal (traj_server_ros.cpp:472-484) -- wall clock belongs to the caller --, the restamping of the first plan
+ * (traj_manager.cpp:631-637), the refusal of a new plan whose first segment lasts <= 1e-5 s (traj_server_ros.cpp:496-499)
+ * and the reset of the filter history to the map message's ego state after a first plan (:436-437: the tick stores
+ * (t_now + budget, the ego angle) instead).
+ *
+ * dftpav_planner_install: n plans from host arrays (TrajContainer::addSingulTraj, traj_container.hpp:58-73) into `slots`
+ *   [n]: n_seg [n], singul / piece_nums / coeff_dt [n][max_seg], coeffs [n][max_seg * max_pieces][6][2] (the pieces of a
+ *   plan's segments one after another), end_states [n][4].  The times are chained on the host.  The slots start without
+ *   filter history.
+ * dftpav_planner_adopt: the winners of the LAST dftpav_plan_queries call of this planner become the executing plans
+ *   (executing_traj_ = std::move(next_traj_), traj_server_ros.cpp:171-178): query queries[i] into slot slots[i], a
+ *   device-to-device gather by one small kernel, the times chained there by the same additions.  A query without a winner
+ *   leaves its slot untouched; adopted [n] (may be NULL) reports 1 / 0.  The goal stored is the query's end state.
+ * dftpav_planner_set_history: the previous desired state of `slots` [n] (desired_state_hist_.back(), :460-461): time stamps
+ *   and angles [n].  An empty slot is DFTPAV_E_INVALID.
+ * dftpav_planner_clear: empties `slots` [n] (executing_traj_.release(), :154).
+ * dftpav_planner_executing: reads a slot back; any pointer may be NULL.  n_seg 0: empty (the arrays are then zero).
+ *   singul / piece_nums / coeff_dt / duration / start_time / end_time [max_seg], coeffs [max_seg * max_pieces][6][2],
+ *   end_state [4], hist [2] (time stamp, angle), have_hist [1].  Size them by dftpav_planner_padding.
+ * dftpav_planner_padding: the table's padding (max_seg, max_pieces), 0 and 0 before the first call that fills the table
+ *   (dftpav_planner_executing then writes n_seg and have_hist only).  Either pointer may be NULL. */
+int dftpav_planner_install(dftpav_planner *p, int n, const int *slots, int max_seg, int max_pieces, const int *n_seg,
+                           const int *singul, const int *piece_nums, const double *coeff_dt, const double *coeffs,
+                           const double *end_states, double t_start);
+int dftpav_planner_adopt(dftpav_planner *p, int n, const int *queries, const int *slots, double t_start, int *adopted);
+int dftpav_planner_set_history(dftpav_planner *p, int n, const int *slots, const double *stamps, const double *angles);
+int dftpav_planner_clear(dftpav_planner *p, int n, const int *slots);
+int dftpav_planner_executing(dftpav_planner *p, int slot, int *n_seg, int *singul, int *piece_nums, double *coeff_dt,
+                             double *coeffs, double *duration, double *start_time, double *end_time, double *end_state,
+                             double *hist, int *have_hist);
+int dftpav_planner_padding(dftpav_planner *p, int *max_seg, int *max_pieces);
+
+/* Caller-allocated outputs of the check, one row per slot; every pointer may be NULL.  Rows of empty slots without an ego
+ * state and of completed slots are zero apart from occupied / complete (first_sample: -1). */
+typedef struct dftpav_replan_out {
+  int *occupied;           /* [slots] the slot holds a plan */
+  int *complete;           /* [slots] t_now > end_time of the last segment (traj_server_ros.cpp:150) */
+  int *exe_index;          /* [slots] first segment whose end_time is not <= t_now (:248-252); at t_now == the last end_time the last */
+  int *is_close_turnpoint; /* [slots] :373-377 */
+  int *is_near;            /* [slots] :379 */
+  int *target_moved;       /* [slots] (localTarget - end_state.head(2)).norm() > 0.1 (:367, :381) */
+  int *collision;          /* [slots] the loop of :385-397, as dftpav_batch_validate */
+  int *first_sample;       /* [slots] as dftpav_batch_validate (-1: none) */
+  int *replan;             /* [slots] is_near && !is_close_turnpoint && target_moved, or collision; 1 for an empty slot with an ego state */
+  double *desired;         /* [slots][8] time_stamp, x, y, angle, curvature, velocity, acceleration, steer at t_now + budget */
+  double *start_state;     /* [slots][4] x, y, angle, velocity (traj_manager.cpp:74) */
+  double *start_ctrl;      /* [slots][2] steer, acceleration (traj_manager.cpp:75) */
+} dftpav_replan_out;
+
+/* One kernel (replan.hip), one workgroup per slot, whatever the layouts: completion, CheckReplan and Replan's desired state
+ * (see above) for every slot at clock t_now.  The collision loop runs on the map of dftpav_set_grid_map every check_dt
+ * seconds with outline points every vertex_res m, and always (the reference returns before it when the near / target rule
+ * fires, :381-383: `replan` is the same, `collision` is additionally known).  exe_traj_index_ is derived from t_now, so
+ * the call keeps no state; the table is not written.  The desired state is read at t_now + budget (Budget = 0.5 s in
+ * the reference) from the segment the pidx walk of :445-457 stops at, and filtered against the slot's stored previous
+ * desired state where it has one.  end_states [slots][4]: the goals (end_pt_) to test the local target against, NULL = the
+ * stored ones.  ego_states [slots][6] (x, y, angle, velocity, steer, acceleration) or NULL: an empty slot with an ego state
+ * wants a plan (executing_traj_ == nullptr, :361, :415-416), its desired state is the ego state with the stamp (curvature
+ * 0).  ego_states has a row for every slot and no per-slot switch: with it given EVERY empty slot is flagged, and the tick
+ * plans every one of them; a caller who wants some slots to stay idle passes NULL and fills those that should start with
+ * dftpav_plan_queries + dftpav_planner_adopt.  DFTPAV_E_INVALID without a map or before the table was filled once. */
+int dftpav_replan_check(dftpav_planner *p, double t_now, double budget, const double *end_states, const double *ego_states,
+                        double check_dt, double vertex_res, const dftpav_replan_out *out);
+
+/* One tick of PlanCycleCallback (traj_server_ros.cpp:130-192) for every slot: the check above (with pp's check_dt /
+ * vertex_res), ONE small read-back of replan / start_state / start_ctrl -- the tick's one wait beyond those of
+ * dftpav_plan_queries, which does its arrival test on the host anyway --, the flagged slots packed in rising slot order
+ * into the queries of dftpav_plan_queries (that code, with t_now + budget as its t_now; query_slot[q] = the slot of query
+ * q, n_queries their number; query_slot [slots]), and for every query that ends DFTPAV_PLAN_OK with a winner the adoption
+ * of the winner into its slot with t_start = t_now + budget (:414, traj_manager.cpp:520), the desired state stored as
+ * the slot's filter history (:461) and the goal stored.  A flagged slot whose planning fails keeps its executing plan
+ * (next_traj_ stays null).  plan_out is indexed by query, as in a plain call.  check_out, query_slot, n_queries and plan_out
+ * may be NULL.  With ego_states given, end_states must be given too (an empty slot has no stored goal).
+ * Restarts stay keyed by (seed, query index in the call, restart): the restarts of a slot therefore depend on which other
+ * slots replan in the same tick (restart 0, the searched hypothesis itself, does not). */
+int dftpav_replan_tick(dftpav_planner *p, const dftpav_plan_params *pp, double t_now, double budget, const double *end_states,
+                       const double *ego_states, const dftpav_replan_out *check_out, int *query_slot, int *n_queries,
+                       const dftpav_plan_out *plan_out);
+/* Device time in ms (the planner's HIP events) of the last check kernel, and of the last tick from the start of its check to
+ * the end of its adoption (the host's read-back and grouping in between included).  Either pointer may be NULL. */
+int dftpav_replan_last_ms(dftpav_planner *p, float *check_ms, float *tick_ms);
+
 /* One-shot convenience == OptimizeTrajectory for B trajectories. */
 int dftpav_solve_batch(dftpav_handle *h, const dftpav_layout *layout, int B,
                        const dftpav_batch_data *d, double *x, double *final_cost,
