@@ -160,6 +160,7 @@ struct dftpav_batch {
   int16_t *d_pt_piece = nullptr, *d_pt_j = nullptr;
   double *d_opM[kMaxSeg] = {nullptr}, *d_opMT[kMaxSeg] = {nullptr};
   double *d_histS = nullptr, *d_histY = nullptr, *d_histU = nullptr, *d_histV = nullptr, *d_histR = nullptr;
+  double *d_histM = nullptr; // QUAD shape of the reference order: the mirrored ends of the history rings (DevBatch::histM)
   double *d_x_in = nullptr, *d_x_out = nullptr, *d_f = nullptr, *d_g = nullptr;
   int *d_status = nullptr, *d_success = nullptr, *d_iters = nullptr, *d_evals = nullptr;
   long long *d_hist = nullptr, *d_ticks = nullptr, *d_prof = nullptr;
@@ -1149,7 +1150,7 @@ extern "C" void dftpav_batch_destroy(dftpav_batch *b) {
   if (!b) return;
   (void)hipSetDevice(b->h->device);
   (void)hipStreamSynchronize(b->h->stream);
-  void *ptrs[] = {b->d_x0, b->d_iniS, b->d_finS, b->d_corridor, b->d_pt_piece, b->d_pt_j, b->d_histS, b->d_histU, b->d_histV, b->d_histR,
+  void *ptrs[] = {b->d_x0, b->d_iniS, b->d_finS, b->d_corridor, b->d_pt_piece, b->d_pt_j, b->d_histS, b->d_histU, b->d_histV, b->d_histR, b->d_histM,
                   b->d_x_in, b->d_x_out, b->d_f, b->d_g, b->d_status, b->d_success, b->d_iters, b->d_evals,
                   b->d_hist, b->d_ticks, b->d_prof, b->d_dev, b->d_coef, b->d_dt, b->d_records,
                   b->d_queue, b->d_stragglers, b->d_stragglers2, b->d_sflag, b->d_iota, b->d_qctl, b->d_state, b->d_dev2,
@@ -1662,6 +1663,7 @@ static DevBatch make_dev(dftpav_batch *b) {
   D.histU = b->d_histU;
   D.histV = b->d_histV;
   D.histR = b->d_histR;
+  D.histM = b->d_histM;
   D.queue = b->d_queue;
   D.qctl = b->d_qctl;
   D.stragglers = b->d_stragglers;
@@ -2017,8 +2019,10 @@ extern "C" int dftpav_batch_set_order(dftpav_batch *b, int order) {
       tab.insert(tab.end(), packed.begin(), packed.end());
     }
     double *cor_t = b->d_cor_t, *d_tab = nullptr, *d_scr = nullptr; // (the corridor copy's size does not change: a batch keeps its first)
+    double *hist_m = b->d_histM;                                    // (nor does the history mirror's)
     auto undo = [&](const char *msg) {
       if (cor_t != b->d_cor_t) (void)hipFree(cor_t);
+      if (hist_m != b->d_histM) (void)hipFree(hist_m);
       if (d_tab) (void)hipFree(d_tab);
       if (d_scr) (void)hipFree(d_scr);
       (void)hipGetLastError();
@@ -2027,6 +2031,11 @@ extern "C" int dftpav_batch_set_order(dftpav_batch *b, int order) {
     };
     if (pl.kind >= kRefQuad && !cor_t && hipMalloc(&cor_t, sizeof(double) * reference_order_quad_corridor_doubles(b->L, b->B)) != hipSuccess)
       return undo("reference order: no device memory for the QUAD shape's copy of the corridor");
+    // cleared as histS is: the elements of a row that are no variables must read +0.0 (solver_ref4.hip: q4_rec_sum)
+    if (pl.kind == kRefQuad && !hist_m &&
+        (hipMalloc(&hist_m, sizeof(double) * quad_mirror_doubles(b->L, b->B)) != hipSuccess ||
+         hipMemset(hist_m, 0, sizeof(double) * quad_mirror_doubles(b->L, b->B)) != hipSuccess))
+      return undo("reference order: no device memory for the QUAD shape's mirror of the history ends");
     if (new_tab && (hipMalloc(&d_tab, sizeof(double) * tab.size()) != hipSuccess ||
                     hipMalloc(&d_scr, sizeof(double) * reference_order_scratch_doubles(b->L, b->B, h->S)) != hipSuccess ||
                     hipMemcpy(d_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice) != hipSuccess))
@@ -2040,6 +2049,8 @@ extern "C" int dftpav_batch_set_order(dftpav_batch *b, int order) {
     }
     if (pl.kind >= kRefQuad) b->cor_t_dirty = true;
     b->d_cor_t = cor_t;
+    b->d_histM = hist_m;
+    b->dev_version = -1; // (the device descriptor carries the mirror's pointer)
     b->ref_plan = pl;
   }
   b->order = order;

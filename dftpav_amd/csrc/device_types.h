@@ -130,6 +130,10 @@ struct DevBatch {
   //   histU[j][d] = s_j . y_(the d+1-th pair after j),  histV[j][d] = y_j . s_(the d+1-th pair before j)
   double *histU, *histV;
   double *histR; // [B][mem][2] (ys, 1 / ys) of the stored pairs (lbfgs.hpp:685 lm_ys and its reciprocal)
+  // QUAD shape (solver_ref4.hip) only, else nullptr: [B][kQuadMirrorRows][npad][2] the ends of a trajectory's ring in histS once
+  // more -- its last kQuadMirrorRows / 2 rows, then its first -- so that a block of the recursion that crosses the ring's end reads
+  // consecutive rows as every other block does
+  double *histM;
   // time-sliced scheduling of batches larger than the device holds at once (solver.hip, solver_kernel)
   int *queue;          // [B] ring of trajectories waiting for a workgroup
   unsigned *qctl;      // [0] head  [1] published tail  [2] reserved tail  [3] unfinished  [4] number of stragglers
@@ -164,6 +168,9 @@ struct DevBatch {
   double *trace;
   int trace_b, trace_cap, trace_n;
 };
+
+constexpr int kQuadMirrorRows = 16; // rows of DevBatch::histM per trajectory (twice solver_ref4.hip's register block of stored pairs)
+inline size_t quad_mirror_doubles(const DevLayout &L, int B) { return (size_t)B * kQuadMirrorRows * L.npad * 2; }
 
 enum KernelMode { kModeSolve = 0, kModeEval = 1, kModeCoeffs = 2 };
 

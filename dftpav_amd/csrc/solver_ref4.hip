@@ -757,99 +757,172 @@ __device__ __forceinline__ bool q4_begin_iteration(const DevParams &P, const Q4 
 
 // The two-loop recursion (lbfgs.hpp:716-739) over `bound` stored pairs of this row's trajectory, the newest in slot ne - 1;
 // d = -g on entry (elements from n on: 0.0).  The four rows run their steps in the same instructions; bound, the ring position
-// and the division mode belong to the row.  History rows: (s, y) interleaved per element at pitch npad; (ys, 1 / ys) per pair.
-constexpr int kQB = 8; // stored pairs per register block (the next block is in flight while one is worked on)
-struct QBlk {
-  d2_t a[kQB], b[kQB]; // (s, y) of elements l and 16 + l
-  d2_t yr[kQB];        // (ys, 1 / ys)
+// and the division mode belong to the row.  History rows: (s, y) interleaved per element at pitch kQNpad; (ys, 1 / ys) per pair.
+//
+// What a step does besides its chain is kept short:
+//   * a block of kQB pairs is kQB CONSECUTIVE rows from one address, the pairs at compile-time offsets.  A block that crosses the
+//     end of the ring is read from the MIRROR (DevBatch::histM, 2 kQB rows per trajectory: the ring's rows m - kQB .. m - 1, then its
+//     rows 0 .. kQB - 1), in which those rows are consecutive too; q4_store_pair writes a pair of either end to both places.  The
+//     wrap is decided once per block.  The ring itself lies where the WAVE shape expects it (a hand-over resumes from it).
+//   * n <= 31 (Y3 = false): element 31 of a row is no variable, and the pair's (ys, 1 / ys) sit there -- they arrive with lane 15's
+//     second load and go to the row by DPP; histR is written as before (the WAVE shape reads it) but not read here.  n = 32 (Y3):
+//     they are loaded from histR.
+//   * alpha is kept by step number, not by ring slot: a compile-time offset from the block's first step.
+constexpr int kQB = 8;     // stored pairs per register block (the next block is in flight while one is worked on)
+constexpr int kQNpad = 64; // pitch of a history row: DevLayout::npad of every layout in scope (n <= 32; reference_order_quad_supported)
+static_assert(kQuadMirrorRows == 2 * kQB, "DevBatch::histM holds kQB rows of either end of a ring");
+template <bool Y3> struct QBlk {
+  d2_t a[kQB], b[kQB];    // (s, y) of elements l and 16 + l
+  d2_t yr[Y3 ? kQB : 1];  // Y3: (ys, 1 / ys)
 };
 typedef double __attribute__((ext_vector_type(2))) qd2_t;
-template <int DIR>
-__device__ __forceinline__ void q4_load_blk(QBlk &R, gcd2_t hS, gcd2_t hR, int npad, int m, int la, int lb, int &jl) {
+
+// 0.0 + p[0] + ... + p[n-1] in the recursion: row_sum32 without its selects.  The elements from n on of d are +-0.0 wherever this is
+// called (q4_state_io, q4_begin_iteration's callers and q4_advance set them to 0.0, and a step adds coefficient * 0.0 to them: the
+// elements from n on of every stored s and y are +0.0 -- the buffers are cleared when they are allocated and no lane >= n stores),
+// so their products are +-0.0 as long as the coefficients are finite.  The chain starts from +0.0, and a sum rounded to nearest is
+// -0.0 only if both operands are: the accumulator is never -0.0, and adding +0.0 or -0.0 leaves it as it is -- what row_sum32's
+// -0.0 does.  Y3 = false: lane 15's second element is (ys, 1 / ys), not zero -- the chain's last link, which would read it, is left
+// out (n <= 31: it would add -0.0).
+#define DFTPAV_FMAC_BCAST15 \
+  DFTPAV_FMAC_BCAST(0) DFTPAV_FMAC_BCAST(1) DFTPAV_FMAC_BCAST(2) DFTPAV_FMAC_BCAST(3) DFTPAV_FMAC_BCAST(4) DFTPAV_FMAC_BCAST(5) DFTPAV_FMAC_BCAST(6) \
+  DFTPAV_FMAC_BCAST(7) DFTPAV_FMAC_BCAST(8) DFTPAV_FMAC_BCAST(9) DFTPAV_FMAC_BCAST(10) DFTPAV_FMAC_BCAST(11) DFTPAV_FMAC_BCAST(12) \
+  DFTPAV_FMAC_BCAST(13) DFTPAV_FMAC_BCAST(14)
+__device__ __forceinline__ double row_chain15(double acc, double v) {
+  const double one = 1.0;
+  asm volatile("s_nop 1\n\t" DFTPAV_FMAC_BCAST15 : "+v"(acc) : "v"(v), "v"(one));
+  return acc;
+}
+template <bool Y3> __device__ __forceinline__ double q4_rec_sum(double p0, double p1, int n) {
+  double acc = row_chain16(0.0, p0);
+  if (n > 16) acc = Y3 ? row_chain16(acc, p1) : row_chain15(acc, p1); // (uniform)
+  return acc;
+}
+
+// the block of kQB pairs that starts in slot jl and walks downwards (DIR = -1) or upwards; jl: the next block's first slot.
+// Unconditional loads from always-valid addresses (ring or mirror, both cleared at allocation); m >= kQB.
+template <int DIR, bool Y3>
+__device__ __forceinline__ void q4_load_blk(QBlk<Y3> &R, gcd2_t hS, gcd2_t hM, gcd2_t hR, int m, int l, int &jl) {
+  // mirror row of ring row r: r - (m - kQB) for the last kQB rows, kQB + r for the first kQB
+  const bool wrap = DIR < 0 ? jl < kQB - 1 : jl > m - kQB;
+  const int mr = DIR < 0 ? kQB + jl : jl - (m - kQB);
+  const gcd2_t row = (wrap ? hM + mr * kQNpad : hS + jl * kQNpad) + l;
 #pragma unroll
   for (int u = 0; u < kQB; u++) {
-    const gcd2_t row = hS + (size_t)jl * npad + la; // (element 16 + l sits 16 entries on: rows are npad >= 32 long, what lies beyond n is never used)
-    R.a[u] = row[0];
-    R.b[u] = row[16];
-    R.yr[u] = hR[jl];
-    if (DIR < 0) jl = jl == 0 ? m - 1 : jl - 1;
-    else jl = jl == m - 1 ? 0 : jl + 1;
+    R.a[u] = row[DIR * u * kQNpad];
+    R.b[u] = row[DIR * u * kQNpad + 16]; // (element 16 + l)
+  }
+  if (Y3) {
+    int jr = jl;
+#pragma unroll
+    for (int u = 0; u < kQB; u++) {
+      R.yr[Y3 ? u : 0] = hR[jr];
+      if (DIR < 0) jr = jr == 0 ? m - 1 : jr - 1;
+      else jr = jr == m - 1 ? 0 : jr + 1;
+    }
+  }
+  if (DIR < 0) {
+    jl -= kQB;
+    jl = jl < 0 ? jl + m : jl;
+  } else {
+    jl += kQB;
+    jl = jl >= m ? jl - m : jl;
   }
 }
-__device__ __forceinline__ void q4_pin_blk(QBlk &R) {
+template <bool Y3> __device__ __forceinline__ void q4_pin_blk(QBlk<Y3> &R) {
 #pragma unroll
-  for (int u = 0; u < kQB; u++)
-    asm volatile("" : "+v"(R.a[u].x), "+v"(R.a[u].y), "+v"(R.b[u].x), "+v"(R.b[u].y), "+v"(R.yr[u].x), "+v"(R.yr[u].y));
+  for (int u = 0; u < kQB; u++) {
+    asm volatile("" : "+v"(R.a[u].x), "+v"(R.a[u].y), "+v"(R.b[u].x), "+v"(R.b[u].y));
+    if (Y3) asm volatile("" : "+v"(R.yr[Y3 ? u : 0].x), "+v"(R.yr[Y3 ? u : 0].y));
+  }
 }
-template <bool EXACT>
-__device__ __forceinline__ void q4_first_steps(const QBlk &R, const Q4 &q, int i0, int bound, int m, int n, int l, bool exact, int &j, double &d0, double &d1) {
+// (ys, 1 / ys) of pair u of a block: every lane of the row gets lane 15's second element (row_newbcast:15)
+template <bool Y3> __device__ __forceinline__ d2_t q4_blk_yr(const QBlk<Y3> &R, int u) {
+  if (Y3) return R.yr[Y3 ? u : 0];
+  d2_t yr;
+  yr.x = mov_dpp<0x15F>(R.b[u].x);
+  yr.y = mov_dpp<0x15F>(R.b[u].y);
+  return yr;
+}
+// al: alpha of step i0 (first loop: step i of the recursion takes the i-th newest pair)
+template <bool EXACT, bool Y3>
+__device__ __forceinline__ void q4_first_steps(const QBlk<Y3> &R, ldsd_t al, int i0, int bound, int n, int l, bool exact, double &d0, double &d1) {
 #pragma unroll
   for (int u = 0; u < kQB; u++) {
     if (i0 + u < bound) { // (row-uniform)
-      j = j == 0 ? m - 1 : j - 1;
-      const double dot = row_sum32(R.a[u].x * d0, R.b[u].x * d1, n, l);
+      const d2_t yr = q4_blk_yr<Y3>(R, u);
+      const double dot = q4_rec_sum<Y3>(R.a[u].x * d0, R.b[u].x * d1, n);
       // lm_alpha[j] = lm_s.col(j).dot(d) / lm_ys[j]  (EXACT: some row of the wave divides -- only its lanes take the division's result)
-      const double a = EXACT && exact ? dot / R.yr[u].x : div_by_rcp<false>(dot, R.yr[u].x, R.yr[u].y);
-      if (l == 0) q.alpha[j] = a;
+      const double a = EXACT && exact ? dot / yr.x : div_by_rcp<false>(dot, yr.x, yr.y);
+      if (l == 0) al[u] = a;
       const double na = -a;
       d0 = d0 + na * R.a[u].y; // d += (-alpha) * lm_y.col(j)
       d1 = d1 + na * R.b[u].y;
     }
   }
 }
-template <bool EXACT>
-__device__ __forceinline__ void q4_second_steps(const QBlk &R, const Q4 &q, int i0, int bound, int m, int n, int l, bool exact, int &j, double &d0, double &d1) {
+// al: alpha of the pair of this block's LAST step (the second loop takes the pairs in the opposite order: step u reads al[kQB - 1 - u])
+template <bool EXACT, bool Y3>
+__device__ __forceinline__ void q4_second_steps(const QBlk<Y3> &R, ldscd_t al, int i0, int bound, int n, int l, bool exact, double &d0, double &d1) {
 #pragma unroll
   for (int u = 0; u < kQB; u++) {
     if (i0 + u < bound) { // (row-uniform)
-      const double al = q.alpha[j];
-      const double dot = row_sum32(R.a[u].y * d0, R.b[u].y * d1, n, l);
-      const double beta = EXACT && exact ? dot / R.yr[u].x : div_by_rcp<false>(dot, R.yr[u].x, R.yr[u].y);
-      const double cf = al - beta;
+      const double av = al[kQB - 1 - u];
+      const d2_t yr = q4_blk_yr<Y3>(R, u);
+      const double dot = q4_rec_sum<Y3>(R.a[u].y * d0, R.b[u].y * d1, n);
+      const double beta = EXACT && exact ? dot / yr.x : div_by_rcp<false>(dot, yr.x, yr.y);
+      const double cf = av - beta;
       d0 = d0 + cf * R.a[u].x; // d += (alpha - beta) * lm_s.col(j)
       d1 = d1 + cf * R.b[u].x;
-      j = j == m - 1 ? 0 : j + 1;
     }
   }
 }
-template <bool EXACT>
-__device__ __forceinline__ void q4_two_loop(const Q4 &q, gcd2_t hS, gcd2_t hR, int npad, int m, int n, int l, int bound, int ne, bool exact, double sc0, double &d0,
+template <bool EXACT, bool Y3>
+__device__ __forceinline__ void q4_two_loop(const Q4 &q, gcd2_t hS, gcd2_t hM, gcd2_t hR, int m, int n, int l, int bound, int ne, bool exact, double sc0, double &d0,
                                             double &d1) {
-  const int la = l, lb = 16 + l;
-  QBlk A, B;
-  int j = ne;
+  QBlk<Y3> A, B;
   int jl = ne == 0 ? m - 1 : ne - 1;
-  q4_load_blk<-1>(A, hS, hR, npad, m, la, lb, jl);
+  q4_load_blk<-1>(A, hS, hM, hR, m, l, jl);
 #pragma unroll 1
   for (int i0 = 0; i0 < bound; i0 += 2 * kQB) {
     q4_pin_blk(A);
-    q4_load_blk<-1>(B, hS, hR, npad, m, la, lb, jl);
-    q4_first_steps<EXACT>(A, q, i0, bound, m, n, l, exact, j, d0, d1);
+    q4_load_blk<-1>(B, hS, hM, hR, m, l, jl);
+    q4_first_steps<EXACT>(A, q.alpha + i0, i0, bound, n, l, exact, d0, d1);
     q4_pin_blk(B);
-    q4_load_blk<-1>(A, hS, hR, npad, m, la, lb, jl);
-    q4_first_steps<EXACT>(B, q, i0 + kQB, bound, m, n, l, exact, j, d0, d1);
+    q4_load_blk<-1>(A, hS, hM, hR, m, l, jl);
+    q4_first_steps<EXACT>(B, q.alpha + (i0 + kQB), i0 + kQB, bound, n, l, exact, d0, d1);
   }
   d0 = d0 * sc0;
   d1 = d1 * sc0;
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); // alpha written by lane 0 of the row, read by all below
-  jl = j;
-  q4_load_blk<+1>(A, hS, hR, npad, m, la, lb, jl);
+  jl = ne - bound; // the oldest pair's slot
+  jl = jl < 0 ? jl + m : jl;
+  q4_load_blk<+1>(A, hS, hM, hR, m, l, jl);
 #pragma unroll 1
   for (int i0 = 0; i0 < bound; i0 += 2 * kQB) {
+    // (step i0 + u takes the pair of first-loop step bound - 1 - i0 - u; the pointer may lie in front of alpha where the steps that
+    // would read there are masked)
+    const ldscd_t al = (ldscd_t)(q.alpha + (bound - kQB - i0));
     q4_pin_blk(A);
-    q4_load_blk<+1>(B, hS, hR, npad, m, la, lb, jl);
-    q4_second_steps<EXACT>(A, q, i0, bound, m, n, l, exact, j, d0, d1);
+    q4_load_blk<+1>(B, hS, hM, hR, m, l, jl);
+    q4_second_steps<EXACT>(A, al, i0, bound, n, l, exact, d0, d1);
     q4_pin_blk(B);
-    q4_load_blk<+1>(A, hS, hR, npad, m, la, lb, jl);
-    q4_second_steps<EXACT>(B, q, i0 + kQB, bound, m, n, l, exact, j, d0, d1);
+    q4_load_blk<+1>(A, hS, hM, hR, m, l, jl);
+    q4_second_steps<EXACT>(B, al - kQB, i0 + kQB, bound, n, l, exact, d0, d1);
   }
+}
+// One 16-byte unit of ring row `end` (element e: (s, y), or (ys, 1 / ys) in element 31), and of the mirror's copies of that row
+__device__ __forceinline__ void q4_store_pair(gd_t hS, gd_t hM, int m, int end, int e, d2_t v) {
+  ((gd2_t)hS)[(size_t)end * kQNpad + e] = v;
+  if (end < kQB) ((gd2_t)hM)[(kQB + end) * kQNpad + e] = v;
+  if (end >= m - kQB) ((gd2_t)hM)[(end - (m - kQB)) * kQNpad + e] = v;
 }
 
 // Everything lbfgs_optimize does between two evaluations (lbfgs.hpp:524-745 with the line search of :312-389 unrolled into it):
 // solver_ref.hip's lbfgs_advance for the trajectory of this row; f: the cost of the evaluation just made; sets iACTION.
-__device__ __forceinline__ void q4_advance(const DevBatch &D, const Q4 &q, QVec &v, double f, gd_t hS, gd_t hR, int l, Prof &pr) {
+__device__ __forceinline__ void q4_advance(const DevBatch &D, const Q4 &q, QVec &v, double f, gd_t hS, gd_t hM, gd_t hR, int l, Prof &pr) {
   const DevParams &P = D.P;
-  const int n = D.L.n, m = P.mem_size, npad = D.L.npad;
+  const int n = D.L.n, m = P.mem_size;
   const bool e0 = l < n, e1 = 16 + l < n;
   int action = kActEval;
   if (q.ist[iPHASE] == 0) { // after the first evaluation: lbfgs.hpp:524-551
@@ -1028,13 +1101,13 @@ __device__ __forceinline__ void q4_advance(const DevBatch &D, const Q4 &q, QVec 
     d2_t sy;
     sy.x = sv0;
     sy.y = yv0;
-    ((gd2_t)hS)[(size_t)end * npad + l] = sy;
+    q4_store_pair(hS, hM, m, end, l, sy);
   }
   if (e1) {
     d2_t sy;
     sy.x = sv1;
     sy.y = yv1;
-    ((gd2_t)hS)[(size_t)end * npad + 16 + l] = sy;
+    q4_store_pair(hS, hM, m, end, 16 + l, sy);
   }
   v.d0 = e0 ? -g0 : 0.0;
   v.d1 = e1 ? -g1 : 0.0;
@@ -1050,6 +1123,13 @@ __device__ __forceinline__ void q4_advance(const DevBatch &D, const Q4 &q, QVec 
     ((gd2_t)hR)[end] = yr;
     if (!rcp_route_ok(ys)) q.ist[iSLOWDIV] = 1; // from here on the recursion divides (see div_by_rcp)
   }
+  const bool y3 = n > 31; // (uniform) element 31 is a variable: (ys, 1 / ys) come from histR
+  if (l == 15 && !y3) { // ... otherwise they travel in the row, as its element 31 (every lane of the row holds ys)
+    d2_t yr;
+    yr.x = ys;
+    yr.y = 1.0 / ys;
+    q4_store_pair(hS, hM, m, end, 31, yr);
+  }
   const double cau = ss * sqrt(gpgp) * P.cautious_factor;
   pr.tick(7);
   if (ys > cau) {
@@ -1059,9 +1139,15 @@ __device__ __forceinline__ void q4_advance(const DevBatch &D, const Q4 &q, QVec 
     __threadfence_block(); // the newest pair's row and (ys, 1 / ys) are read back below
     const bool exact = q.ist[iSLOWDIV] != 0;
     double d0 = v.d0, d1 = v.d1;
+    const gcd2_t cS = (gcd2_t)hS, cM = (gcd2_t)hM, cR = (gcd2_t)hR;
     // (the division mode is a wave-level choice of code: the reciprocal route has no branch in its steps)
-    if (__builtin_amdgcn_ballot_w64(exact) != 0ull) q4_two_loop<true>(q, (gcd2_t)hS, (gcd2_t)hR, npad, m, n, l, bound, ne, exact, ys / yy, d0, d1);
-    else q4_two_loop<false>(q, (gcd2_t)hS, (gcd2_t)hR, npad, m, n, l, bound, ne, exact, ys / yy, d0, d1);
+    if (__builtin_amdgcn_ballot_w64(exact) != 0ull) {
+      if (y3) q4_two_loop<true, true>(q, cS, cM, cR, m, n, l, bound, ne, exact, ys / yy, d0, d1);
+      else q4_two_loop<true, false>(q, cS, cM, cR, m, n, l, bound, ne, exact, ys / yy, d0, d1);
+    } else {
+      if (y3) q4_two_loop<false, true>(q, cS, cM, cR, m, n, l, bound, ne, exact, ys / yy, d0, d1);
+      else q4_two_loop<false, false>(q, cS, cM, cR, m, n, l, bound, ne, exact, ys / yy, d0, d1);
+    }
     v.d0 = e0 ? d0 : 0.0;
     v.d1 = e1 ? d1 : 0.0;
     if (l == 0) {
@@ -1212,9 +1298,10 @@ __global__ void __launch_bounds__(256, DFTPAV_Q4_WAVES_PER_EU)
         if (l == 0) D.f_eval[b] = f;
         act = false;
       } else {
-        const gd_t hS = (gd_t)(D.histS + (size_t)b * mem * L.npad * 2);
+        const gd_t hS = (gd_t)(D.histS + (size_t)b * mem * kQNpad * 2);
+        const gd_t hM = (gd_t)(D.histM + (size_t)b * kQuadMirrorRows * kQNpad * 2);
         const gd_t hR = (gd_t)(D.histR + (size_t)b * mem * 2);
-        q4_advance(D, q, v, f, hS, hR, l, pr);
+        q4_advance(D, q, v, f, hS, hM, hR, l, pr);
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         if (q.ist[iACTION] == kActDone) { // the epilogue of solver_ref.hip
           for (int h = 0; h < 2; h++) {
@@ -1357,6 +1444,8 @@ __global__ void q4_corridor_rect_kernel(const double *__restrict__ cor, d2_t *__
 bool reference_order_quad_supported(const DevLayout &L, const DevParams &P, int S) {
   // (H <= 5: a point's 5 H + 4 <= 29 terms fit the 6-bit term field of the dense list's ids, quad_common.h)
   if (L.M != 1 || S != 0 || L.n > 32 || L.Ntot > 16 || L.Ntot < 2 || L.H < 1 || L.H > 5) return false;
+  // (the recursion reads blocks of kQB consecutive history rows at pitch kQNpad, the ring's ends from a mirror of 2 kQB rows)
+  if (L.npad != reford::kQNpad || P.mem_size < reford::kQB) return false;
   return reford::q4_shared_bytes(L.Ntot) + 4 * reford::q4_team_bytes(P.mem_size) + reford::q4_dense_bytes() <= 160 * 1024;
 }
 size_t reference_order_quad_corridor_doubles(const DevLayout &L, int B) { return (size_t)B * L.H * 4 * (L.Kmax + 1) * 16; }
