@@ -20,6 +20,7 @@ _LIB = None
 OK = 0
 ORDER_DEVICE, ORDER_REFERENCE = 0, 1
 E_INVALID, E_MINI_T, E_ONE_PIECE, E_NO_DEVICE, E_HIP, E_UNSUPPORTED, E_COMM = -1, -2, -3, -4, -5, -6, -7
+PUBLISH_CHUNK, PUBLISH_MAX_TICKS = 256, 4096   # DFTPAV_PUBLISH_CHUNK, DFTPAV_PUBLISH_MAX_TICKS
 # plan_status of dftpav_plan_queries (DFTPAV_PLAN_*); search status (DFTPAV_SEARCH_*)
 PLAN_OK, PLAN_NO_PATH, PLAN_TOO_MANY_SEGMENTS, PLAN_LAYOUT_UNSUPPORTED, PLAN_NO_VALID_RESTART, PLAN_ARRIVED = 0, 1, 2, 3, 4, 5
 SEARCH_REACH_END, SEARCH_NO_PATH = 2, 3
@@ -44,6 +45,7 @@ EXPORTS = [
     "dftpav_planner_install", "dftpav_planner_adopt", "dftpav_planner_set_history", "dftpav_planner_clear", "dftpav_planner_executing",
     "dftpav_planner_padding",
     "dftpav_replan_check", "dftpav_replan_tick", "dftpav_replan_last_ms",
+    "dftpav_planner_publish", "dftpav_planner_publisher_state", "dftpav_planner_set_ctrl_history", "dftpav_publish_last_ms",
 ]
 
 
@@ -549,6 +551,47 @@ class Planner:
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         self.handle._check(fn(self._p, C.byref(a), C.byref(b)), "replan_last_ms")
         return float(a.value), float(b.value)
+
+    # ---- the publisher: the 100 Hz half of the server's loop (PublishData), K ticks for every slot in one call
+    def publish(self, clocks, want_states=True, want_published=True):
+        """dftpav_planner_publish: K publisher ticks at `clocks` [K], in order -> dict(states [K][slots][8] = time_stamp, x, y, angle,
+        curvature, velocity, acceleration, steer (zero rows where nothing is published), published [K][slots] = 0 / 1 / 2 (the
+        angle replaced by the filter)); an output not wanted is None"""
+        t = np.ascontiguousarray(clocks, dtype=np.float64).reshape(-1)
+        K, S = t.shape[0], self.max_queries
+        st = np.zeros((K, S, 8)) if want_states else None
+        pb = np.zeros((K, S), dtype=np.int32) if want_published else None
+        fn = lib().dftpav_planner_publish
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        self.handle._check(fn(self._p, K, self._ip(t), self._ip(st), self._ip(pb)), "planner_publish")
+        return dict(states=st, published=pb)
+
+    def publisher_state(self, slot):
+        """dftpav_planner_publisher_state: dict(exe_index, hist (time stamp, angle), have_hist) of a slot"""
+        e, hv = C.c_int(0), C.c_int(0)
+        hist = np.zeros(2)
+        fn = lib().dftpav_planner_publisher_state
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        self.handle._check(fn(self._p, int(slot), C.byref(e), self._ip(hist), C.byref(hv)), "planner_publisher_state")
+        return dict(exe_index=e.value, hist=hist, have_hist=hv.value)
+
+    def set_ctrl_history(self, slots, stamps, angles):
+        """dftpav_planner_set_ctrl_history: the back of the control history (time stamp, angle) of `slots`"""
+        sl = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        ts = np.ascontiguousarray(stamps, dtype=np.float64).reshape(-1)
+        an = np.ascontiguousarray(angles, dtype=np.float64).reshape(-1)
+        assert sl.shape == ts.shape == an.shape
+        fn = lib().dftpav_planner_set_ctrl_history
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        self.handle._check(fn(self._p, sl.shape[0], self._ip(sl), self._ip(ts), self._ip(an)), "planner_set_ctrl_history")
+
+    def publish_last_ms(self):
+        """dftpav_publish_last_ms: device ms of the last publish kernel (0.0 before the first)"""
+        a = C.c_float(0.0)
+        fn = lib().dftpav_publish_last_ms
+        fn.argtypes = [C.c_void_p, C.c_void_p]
+        self.handle._check(fn(self._p, C.byref(a)), "publish_last_ms")
+        return float(a.value)
 
     def close(self):
         if self._p:

@@ -60,6 +60,8 @@ hipError_t launch_plan_pack(const PlanPackArgs &A, hipStream_t stream);
 hipError_t launch_plan_select(const PlanSelectArgs &A, hipStream_t stream);
 hipError_t launch_replan_check(const ReplanArgs &A, hipStream_t stream);
 hipError_t launch_exec_adopt(const ExecAdoptArgs &A, hipStream_t stream);
+hipError_t launch_publish(const PublishArgs &A, hipStream_t stream);
+hipError_t launch_pub_reset(const PubResetArgs &A, hipStream_t stream);
 hipError_t launch_corridor_layout(const double *raw, double *out, int B, int Npts, int H, int NptsPad, hipStream_t stream);
 hipError_t launch_adopt(const DevBatch &D, const DevBatch &prev, hipStream_t stream);
 // solver_ref.hip: the same path in the reference's own floating-point order
@@ -2956,6 +2958,15 @@ struct dftpav_planner {
   double rc_dt = 0.0, rc_res = 0.0; // what d_rc_tab was tabulated for
   hipEvent_t rev[4] = {nullptr, nullptr, nullptr, nullptr}; // check start / end, tick start / end
   bool check_timed = false, tick_timed = false;
+  // ---- the publisher (dftpav_planner_publish): its state per slot lives in d_exec beside the table; clocks and outputs grow on demand
+  PubTable P{};
+  int *d_pub_mode = nullptr; // [slots] of d_rc: what an adoption does to the control history of each adopted pair
+  unsigned char *d_pub = nullptr;
+  size_t pub_ticks = 0; // d_pub holds the clocks and outputs of this many ticks
+  double *d_pub_t = nullptr, *d_pub_states = nullptr;
+  int *d_pub_code = nullptr;
+  hipEvent_t pev[2] = {nullptr, nullptr};
+  bool pub_timed = false;
 };
 
 extern "C" int dftpav_planner_create(dftpav_handle *h, int max_queries, int n_restarts, dftpav_planner **out) {
@@ -2995,6 +3006,9 @@ extern "C" void dftpav_planner_destroy(dftpav_planner *p) {
   if (p->d_arena) (void)hipFree(p->d_arena);
   if (p->d_exec) (void)hipFree(p->d_exec);
   if (p->d_rc) (void)hipFree(p->d_rc);
+  if (p->d_pub) (void)hipFree(p->d_pub);
+  for (auto &e : p->pev)
+    if (e) (void)hipEventDestroy(e);
   for (auto &e : p->ev)
     if (e) (void)hipEventDestroy(e);
   for (auto &e : p->rev)
@@ -3457,6 +3471,7 @@ static int exec_table(dftpav_planner *p, int MS, int MP) {
   HIPCHK(h, hipSetDevice(h->device));
   const size_t S = (size_t)p->max_queries, ms = (size_t)MS, mp = (size_t)MP;
   ExecTable T{};
+  PubTable P{};
   T.n_slots = p->max_queries;
   T.max_seg = MS;
   T.max_pieces = MP;
@@ -3480,6 +3495,9 @@ static int exec_table(dftpav_planner *p, int MS, int MP) {
     T.singul = (int *)take(sizeof(int) * S * ms);
     T.piece_nums = (int *)take(sizeof(int) * S * ms);
     T.have_hist = (int *)take(sizeof(int) * S);
+    P.hist = (double *)take(sizeof(double) * S * 2);
+    P.exe_index = (int *)take(sizeof(int) * S);
+    P.have = (int *)take(sizeof(int) * S);
     if (pass == 0) {
       HIPCHK(h, hipMalloc(&base, used));
       if (hipMemsetAsync(base, 0, used, h->stream) != hipSuccess) {
@@ -3491,6 +3509,7 @@ static int exec_table(dftpav_planner *p, int MS, int MP) {
   }
   p->d_exec = base;
   p->T = T;
+  p->P = P;
   p->h_occupied.assign(S, 0);
   p->h_goal.assign(4 * S, 0.0);
   return DFTPAV_OK;
@@ -3559,6 +3578,10 @@ extern "C" int dftpav_planner_install(dftpav_planner *p, int n, const int *slots
     HIPCHK(h, hipMemcpyAsync(T.piece_nums + s * MS, pn.data(), sizeof(int) * MS, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(T.have_hist + s, &zero, sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(T.n_seg + s, &M, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    // the publisher starts on segment 0 without control history
+    HIPCHK(h, hipMemsetAsync(p->P.exe_index + s, 0, sizeof(int), h->stream));
+    HIPCHK(h, hipMemsetAsync(p->P.have + s, 0, sizeof(int), h->stream));
+    HIPCHK(h, hipMemsetAsync(p->P.hist + s * 2, 0, sizeof(double) * 2, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream)); // the staging vectors are reused by the next plan
     p->h_occupied[s] = M;
     std::memcpy(&p->h_goal[4 * s], end_states + 4 * (size_t)i, sizeof(double) * 4);
@@ -3574,7 +3597,7 @@ static int adopt_impl(dftpav_planner *p, int n, const int *queries, const int *s
   for (int i = 0; i < n; i++)
     if (queries[i] < 0 || queries[i] >= p->last_Q) return DFTPAV_E_INVALID;
   if (int rc = exec_table(p, p->last_MS, p->last_MP)) return rc;
-  std::vector<int> pairs;
+  std::vector<int> pairs, mode;
   for (int i = 0; i < n; i++) {
     const int q = queries[i];
     const bool ok = p->last_status[q] == DFTPAV_PLAN_OK && p->last_winner[q] >= 0;
@@ -3582,6 +3605,8 @@ static int adopt_impl(dftpav_planner *p, int n, const int *queries, const int *s
     if (!ok) continue;
     pairs.push_back(q);
     pairs.push_back(slots[i]);
+    // ctrl_state_hist_ outlives a replan; a first plan starts it from the tick's desired state (the ego state), or without one
+    mode.push_back(p->h_occupied[slots[i]] ? kPubKeep : (d_desired ? kPubSeed : kPubDrop));
   }
   const int na = (int)pairs.size() / 2;
   if (na == 0) return DFTPAV_OK;
@@ -3600,7 +3625,15 @@ static int adopt_impl(dftpav_planner *p, int n, const int *queries, const int *s
   A.desired = d_desired;
   A.t_start = t_start;
   HIPCHK(h, launch_exec_adopt(A, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream)); // `pairs` has left the host; the table is current when the call returns
+  HIPCHK(h, hipMemcpyAsync(p->d_pub_mode, mode.data(), sizeof(int) * mode.size(), hipMemcpyHostToDevice, h->stream));
+  PubResetArgs R{};
+  R.P = p->P;
+  R.pairs = p->d_pairs;
+  R.mode = p->d_pub_mode;
+  R.n = na;
+  R.desired = d_desired;
+  HIPCHK(h, launch_pub_reset(R, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream)); // `pairs` and `mode` have left the host; the table is current when the call returns
   for (int k = 0; k < na; k++) {
     const int q = pairs[2 * k], s = pairs[2 * k + 1];
     p->h_occupied[s] = p->h_nseg[q];
@@ -3632,6 +3665,7 @@ static int replan_buffers(dftpav_planner *p) {
     p->d_rc_tab = (double *)take(sizeof(double) * (4096 + 4096));
     p->d_rc_int = (int *)take(sizeof(int) * kRcInts * S);
     p->d_pairs = (int *)take(sizeof(int) * 2 * S);
+    p->d_pub_mode = (int *)take(sizeof(int) * S);
     if (pass == 0) HIPCHK(h, hipMalloc(&base, used));
   }
   p->d_rc = base;
@@ -3683,6 +3717,9 @@ extern "C" int dftpav_planner_clear(dftpav_planner *p, int n, const int *slots) 
     HIPCHK(h, hipMemsetAsync(T.end_state + s * 4, 0, sizeof(double) * 4, h->stream));
     HIPCHK(h, hipMemsetAsync(T.hist + s * 2, 0, sizeof(double) * 2, h->stream));
     HIPCHK(h, hipMemsetAsync(T.coeffs + s * MS * MP * 12, 0, sizeof(double) * MS * MP * 12, h->stream));
+    HIPCHK(h, hipMemsetAsync(p->P.exe_index + s, 0, sizeof(int), h->stream));
+    HIPCHK(h, hipMemsetAsync(p->P.have + s, 0, sizeof(int), h->stream));
+    HIPCHK(h, hipMemsetAsync(p->P.hist + s * 2, 0, sizeof(double) * 2, h->stream));
     p->h_occupied[s] = 0;
     for (int k = 0; k < 4; k++) p->h_goal[4 * s + k] = 0.0;
   }
@@ -3877,5 +3914,104 @@ extern "C" int dftpav_replan_last_ms(dftpav_planner *p, float *check_ms, float *
     HIPCHK(h, hipEventSynchronize(p->rev[3]));
     HIPCHK(h, hipEventElapsedTime(tick_ms, p->rev[2], p->rev[3]));
   }
+  return DFTPAV_OK;
+}
+
+// ------------------------------------------------- the publisher: PublishData (traj_server_ros.cpp:195-318) for every slot (replan.hip)
+extern "C" int dftpav_planner_publish(dftpav_planner *p, int K, const double *t, double *states, int *published) {
+  if (!p || !p->d_exec || !t || K < 1 || K > DFTPAV_PUBLISH_MAX_TICKS) return DFTPAV_E_INVALID;
+  for (int k = 0; k < K; k++)
+    if (!(t[k] == t[k])) return DFTPAV_E_INVALID;
+  dftpav_handle *h = p->h;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t S = (size_t)p->max_queries;
+  for (auto &e : p->pev)
+    if (!e) HIPCHK(h, hipEventCreate(&e));
+  if ((size_t)K > p->pub_ticks) { // the clocks and the outputs of K ticks: one allocation, grown to the largest K met
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (p->d_pub) (void)hipFree(p->d_pub);
+    p->d_pub = nullptr;
+    p->pub_ticks = 0;
+    unsigned char *base = nullptr;
+    size_t used = 0;
+    for (int pass = 0; pass < 2; pass++) {
+      used = 0;
+      auto take = [&](size_t bytes) {
+        void *r = pass ? (void *)(base + used) : nullptr;
+        used += (bytes + 255) / 256 * 256;
+        return r;
+      };
+      p->d_pub_states = (double *)take(sizeof(double) * 8 * S * (size_t)K);
+      p->d_pub_t = (double *)take(sizeof(double) * (size_t)K);
+      p->d_pub_code = (int *)take(sizeof(int) * S * (size_t)K);
+      if (pass == 0) HIPCHK(h, hipMalloc(&base, used));
+    }
+    p->d_pub = base;
+    p->pub_ticks = (size_t)K;
+  }
+  p->pub_timed = false;
+  HIPCHK(h, hipMemcpyAsync(p->d_pub_t, t, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, h->stream));
+  PublishArgs A{};
+  A.T = p->T;
+  A.P = p->P;
+  A.K = K;
+  A.t = p->d_pub_t;
+  A.wheel_base = h->params.veh_wheel_base;
+  A.states = states ? p->d_pub_states : nullptr;
+  A.published = published ? p->d_pub_code : nullptr;
+  HIPCHK(h, hipEventRecord(p->pev[0], h->stream));
+  HIPCHK(h, launch_publish(A, h->stream));
+  HIPCHK(h, hipEventRecord(p->pev[1], h->stream));
+  p->pub_timed = true;
+  if (states) HIPCHK(h, hipMemcpyAsync(states, p->d_pub_states, sizeof(double) * 8 * S * (size_t)K, hipMemcpyDeviceToHost, h->stream));
+  if (published) HIPCHK(h, hipMemcpyAsync(published, p->d_pub_code, sizeof(int) * S * (size_t)K, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream)); // the one wait: `t` has left the host, the outputs have arrived
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_planner_publisher_state(dftpav_planner *p, int slot, int *exe_index, double *hist, int *have_hist) {
+  if (!p || slot < 0 || slot >= p->max_queries) return DFTPAV_E_INVALID;
+  if (!p->d_exec) { // nothing was ever installed
+    if (exe_index) *exe_index = 0;
+    if (hist) hist[0] = hist[1] = 0.0;
+    if (have_hist) *have_hist = 0;
+    return DFTPAV_OK;
+  }
+  dftpav_handle *h = p->h;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t s = (size_t)slot;
+  auto fetch = [&](void *dst, const void *src, size_t bytes) { return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess; };
+  HIPCHK(h, fetch(exe_index, p->P.exe_index + s, sizeof(int)));
+  HIPCHK(h, fetch(hist, p->P.hist + s * 2, sizeof(double) * 2));
+  HIPCHK(h, fetch(have_hist, p->P.have + s, sizeof(int)));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_planner_set_ctrl_history(dftpav_planner *p, int n, const int *slots, const double *stamps, const double *angles) {
+  if (!p || n < 0 || n > p->max_queries || (n > 0 && (!slots || !stamps || !angles))) return DFTPAV_E_INVALID;
+  if (!p->d_exec || !slots_valid(p, n, slots)) return DFTPAV_E_INVALID;
+  for (int i = 0; i < n; i++)
+    if (!p->h_occupied[slots[i]]) return DFTPAV_E_INVALID;
+  dftpav_handle *h = p->h;
+  HIPCHK(h, hipSetDevice(h->device));
+  const int one = 1;
+  for (int i = 0; i < n; i++) {
+    const double hv[2] = {stamps[i], angles[i]};
+    HIPCHK(h, hipMemcpyAsync(p->P.hist + 2 * (size_t)slots[i], hv, sizeof(hv), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(p->P.have + slots[i], &one, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_publish_last_ms(dftpav_planner *p, float *ms) {
+  if (!p || !ms) return DFTPAV_E_INVALID;
+  dftpav_handle *h = p->h;
+  *ms = 0.0f;
+  if (!p->pub_timed) return DFTPAV_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipEventSynchronize(p->pev[1]));
+  HIPCHK(h, hipEventElapsedTime(ms, p->pev[0], p->pev[1]));
   return DFTPAV_OK;
 }

@@ -52,6 +52,14 @@ struct ExecTable {
   int *have_hist;                          // [slots]
 };
 
+// the publisher's state of every slot of the table (TrajPlannerServer::PublishData, traj_server_ros.cpp:195-318), beside the table: the
+// kernels that take an ExecTable by value do not see it
+struct PubTable {
+  int *exe_index; // [slots] exe_traj_index_
+  double *hist;   // [slots][2] ctrl_state_hist_.back(): time stamp, angle
+  int *have;      // [slots] ctrl_state_hist_ is not empty
+};
+
 // exec_adopt_kernel: the winners of the last dftpav_plan_queries call into slots of the table, device to device
 struct ExecAdoptArgs {
   ExecTable T;
@@ -82,6 +90,28 @@ struct ReplanArgs {
   const double *ego;   // [slots][6] x, y, angle, v, steer, acc, or nullptr
   int *o_int;          // [kRcInts][slots]
   double *desired, *start_state, *start_ctrl; // [slots][8], [slots][4], [slots][2]
+};
+
+// publish_kernel (replan.hip): K publisher ticks for every slot
+enum { kPubChunk = DFTPAV_PUBLISH_CHUNK }; // ticks a workgroup takes at a time (its size)
+struct PublishArgs {
+  ExecTable T; // read only
+  PubTable P;  // read, and written back at the end
+  int K;
+  const double *t; // [K] the clocks
+  double wheel_base;
+  double *states; // [K][slots][8]
+  int *published; // [K][slots]
+};
+
+// pub_reset_kernel: the publisher's state of the slots an adoption fills (traj_server_ros.cpp:177)
+enum { kPubKeep = 0, kPubDrop = 1, kPubSeed = 2 };
+struct PubResetArgs {
+  PubTable P;
+  const int *pairs; // [n][2] query, slot (the adoption's)
+  const int *mode;  // [n] kPubKeep: exe_index = 0, the history stays; kPubDrop: and no history; kPubSeed: the history from `desired`
+  int n;
+  const double *desired; // [slots][8], read for kPubSeed: time stamp, ., ., angle
 };
 
 } // namespace dftpav

@@ -18,6 +18,8 @@
 // than shared with validate.hip / states.hip: those kernels read a launch-wide DevLayout, this one a row of the table.
 // fp64, no contraction, cr_trig.h wherever the reference calls libm: bit-identical to oracle_replan/replan_oracle.cpp in
 // order 2.  The kernel writes nothing into the table.
+//
+// publish_kernel, further down, is the other half of the server's loop: the 100 Hz publisher (PublishData, traj_server_ros.cpp:195-318).
 #include <hip/hip_runtime.h>
 
 #include "cr_trig.h"
@@ -327,12 +329,175 @@ __global__ void __launch_bounds__(256) exec_adopt_kernel(ExecAdoptArgs A) {
   }
 }
 
+// K ticks of the 100 Hz publisher for every slot of the table (docs/NEXT_ROWS.md §4.16).
+//
+//   TrajPlannerServer::PublishData, the trajectory feedback   traj_server_ros.cpp:240-289
+//   TrajPlannerServer::FilterSingularityState                 traj_server_ros.cpp:335-356
+//   Trajectory::GetState / locatePieceIdx                     poly_traj_utils.hpp:378-406, 510-528
+//
+// One workgroup of kPubChunk threads per slot takes the ticks in chunks of kPubChunk.  The two recurrences of a tick are serial and
+// cheap and run on thread 0: the index walk (:248-252, compares only) before the evaluation, the filter chain (:257-258, a
+// subtraction, normalize_angle and a compare against the previous filtered angle and stamp) after it.  The state evaluation (double-double
+// atan2 / atan) is independent per tick once its segment is known: every thread takes one tick.  exe_index and the history back are
+// carried from chunk to chunk in LDS and written back at the end.  The idle branch (:210-237) is not reproduced: such ticks publish nothing
+// and change nothing.  The table is not written.
+__global__ void __launch_bounds__(kPubChunk) publish_kernel(PublishArgs A) {
+  __shared__ int s_piece0[kMaxSeg + 1];
+  __shared__ int s_seg[kPubChunk];      // the segment of tick j of the chunk, -1: nothing is published
+  __shared__ double s_ang[kPubChunk], s_vel[kPubChunk];
+  __shared__ int s_code[kPubChunk];
+  __shared__ int s_exe, s_have;
+  __shared__ double s_hist[2];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const ExecTable &T = A.T;
+  const int S = T.n_slots, MS = T.max_seg;
+  const int *pn = T.piece_nums + (size_t)s * MS, *sg = T.singul + (size_t)s * MS;
+  const double *dtv = T.coeff_dt + (size_t)s * MS;
+  const double *cb = T.coeffs + (size_t)s * MS * T.max_pieces * 12;
+  const double *dur = T.duration + (size_t)s * MS, *st = T.start_time + (size_t)s * MS, *en = T.end_time + (size_t)s * MS;
+  const int M = T.n_seg[s];
+  if (tid == 0) {
+    int p0 = 0;
+    for (int i = 0; i < M; i++) {
+      s_piece0[i] = p0;
+      p0 += pn[i];
+    }
+    s_piece0[M] = p0;
+    s_exe = A.P.exe_index[s];
+    s_have = A.P.have[s];
+    s_hist[0] = A.P.hist[2 * (size_t)s];
+    s_hist[1] = A.P.hist[2 * (size_t)s + 1];
+  }
+  for (int k0 = 0; k0 < A.K; k0 += kPubChunk) {
+    __syncthreads(); // the set-up above; the previous chunk's reads of s_seg / s_code / s_ang
+    const int nk = min(kPubChunk, A.K - k0);
+    if (tid == 0) { // the index walk
+      int exe = s_exe;
+      const int last = M - 1; // final_traj_index_
+      for (int j = 0; j < nk; j++) {
+        int seg = -1;
+        // :210-211 executing_traj_ == nullptr || exe_traj_index_ > final_traj_index_ || duration < 1e-5: the idle branch, not reproduced
+        if (M > 0 && exe >= 0 && exe <= last && !(dur[exe] < 1e-5)) {
+          const double t = A.t[k0 + j];
+          if (en[exe] <= t) exe += 1; // :248-250, one step per tick
+          if (exe <= last) seg = exe; // :251-252
+        }
+        s_seg[j] = seg;
+      }
+      s_exe = exe;
+    }
+    __syncthreads();
+    const int k = k0 + tid;
+    const int seg = tid < nk ? s_seg[tid] : -1;
+    double row[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (seg >= 0) {
+      const double t = A.t[k];
+      // Trajectory::GetState(t - start_time), poly_traj_utils.hpp:378-406
+      double inner = t - st[seg];
+      if (inner > dur[seg]) inner = dur[seg];
+      const int idx = rp_locate(pn[seg], dtv[seg], inner);
+      const double *c = cb + (size_t)(s_piece0[seg] + idx) * 12;
+      double px, py, vx, vy, ax, ay;
+      rp_pos(c, inner, px, py);
+      rp_vel(c, inner, vx, vy);
+      rp_acc(c, inner, ax, ay);
+      const double sgn = (double)sg[seg];
+      const double angle = crt::atan2(sgn * vy, sgn * vx);
+      const double vel = sgn * sqrt(vx * vx + vy * vy);
+      double curv = 0.0, ac = 0.0, steer = 0.0;
+      if (!(fabs(vel) < 1e-6)) {
+        curv = (vx * ay - vy * ax) / crt::cube_cr(vel);
+        ac = (vx * ax + vy * ay) / vel;
+        steer = crt::atan(A.wheel_base * curv);
+      }
+      row[0] = t; row[1] = px; row[2] = py; row[3] = angle; row[4] = curv; row[5] = vel; row[6] = ac; row[7] = steer;
+      s_ang[tid] = angle;
+      s_vel[tid] = vel;
+    }
+    __syncthreads();
+    if (tid == 0) { // the filter chain: FilterSingularityState against ctrl_state_hist_.back(), then push_back (:257-258)
+      int have = s_have;
+      double h_stamp = s_hist[0], h_angle = s_hist[1];
+      const double max_rate = 0x1.fffffffffffffp-1 / 2.85 * 0.1; // tan(M_PI / 4) correctly rounded, as replan_check_kernel
+      for (int j = 0; j < nk; j++) {
+        int code = 0;
+        if (s_seg[j] >= 0) {
+          const double t = A.t[k0 + j];
+          double angle = s_ang[j];
+          code = 1;
+          if (have) {
+            const double duration = t - h_stamp;
+            const double max_change = max_rate * duration;
+            if (fabs(s_vel[j]) < 0.1 && fabs(rp_normalize_angle(angle - h_angle)) > max_change) {
+              angle = h_angle;
+              code = 2;
+            }
+          }
+          s_ang[j] = angle;
+          h_stamp = t;
+          h_angle = angle;
+          have = 1;
+        }
+        s_code[j] = code;
+      }
+      s_have = have;
+      s_hist[0] = h_stamp;
+      s_hist[1] = h_angle;
+    }
+    __syncthreads();
+    if (tid < nk) {
+      const int code = s_code[tid];
+      if (code) row[3] = s_ang[tid];
+      if (A.states) {
+        double *o = A.states + ((size_t)k * S + s) * 8;
+#pragma unroll
+        for (int q = 0; q < 8; q++) o[q] = row[q];
+      }
+      if (A.published) A.published[(size_t)k * S + s] = code;
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    A.P.exe_index[s] = s_exe;
+    A.P.have[s] = s_have;
+    A.P.hist[2 * (size_t)s] = s_hist[0];
+    A.P.hist[2 * (size_t)s + 1] = s_hist[1];
+  }
+}
+
+// exe_traj_index_ = 0 for the slots an adoption fills (traj_server_ros.cpp:177); ctrl_state_hist_ stays (the reference keeps it across
+// replans), is dropped, or is seeded from the slot's desired state: one thread per adopted pair
+__global__ void __launch_bounds__(256) pub_reset_kernel(PubResetArgs A) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= A.n) return;
+  const int s = A.pairs[2 * i + 1], mode = A.mode[i];
+  A.P.exe_index[s] = 0;
+  if (mode == kPubDrop) {
+    A.P.hist[2 * (size_t)s] = 0.0;
+    A.P.hist[2 * (size_t)s + 1] = 0.0;
+    A.P.have[s] = 0;
+  } else if (mode == kPubSeed) {
+    A.P.hist[2 * (size_t)s] = A.desired[8 * (size_t)s];
+    A.P.hist[2 * (size_t)s + 1] = A.desired[8 * (size_t)s + 3];
+    A.P.have[s] = 1;
+  }
+}
+
 hipError_t launch_replan_check(const ReplanArgs &A, hipStream_t stream) {
   hipLaunchKernelGGL(replan_check_kernel, dim3(A.T.n_slots), dim3(256), 0, stream, A);
   return hipGetLastError();
 }
 hipError_t launch_exec_adopt(const ExecAdoptArgs &A, hipStream_t stream) {
   hipLaunchKernelGGL(exec_adopt_kernel, dim3(A.n), dim3(256), 0, stream, A);
+  return hipGetLastError();
+}
+
+hipError_t launch_publish(const PublishArgs &A, hipStream_t stream) {
+  hipLaunchKernelGGL(publish_kernel, dim3(A.T.n_slots), dim3(kPubChunk), 0, stream, A);
+  return hipGetLastError();
+}
+hipError_t launch_pub_reset(const PubResetArgs &A, hipStream_t stream) {
+  hipLaunchKernelGGL(pub_reset_kernel, dim3((A.n + 255) / 256), dim3(256), 0, stream, A);
   return hipGetLastError();
 }
 

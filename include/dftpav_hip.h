@@ -807,6 +807,49 @@ int dftpav_replan_tick(dftpav_planner *p, const dftpav_plan_params *pp, double t
  * the end of its adoption (the host's read-back and grouping in between included).  Either pointer may be NULL. */
 int dftpav_replan_last_ms(dftpav_planner *p, float *check_ms, float *tick_ms);
 
+/* ---- the replan loop, its other half: the 100 Hz publisher of every executing plan's control state ----------
+ * Replaces TrajPlannerServer::PublishData's trajectory feedback (traj_server_ros.cpp:240-289) for every slot of the table: the
+ * walk of exe_traj_index_ (:248-252), Trajectory::GetState on that segment (:255, poly_traj_utils.hpp:378-406, 510-528),
+ * FilterSingularityState against ctrl_state_hist_.back() (:257, :335-356) and the push_back of the filtered state (:258).  The
+ * state published is what common::VehicleControlSignal(state) is built from (:261-264, :287).  The simulator drives the
+ * vehicle open-loop from it, so it is also the ego state of the next tick.
+ * Per slot the planner keeps, beside the table: exe_index (exe_traj_index_), the back of ctrl_state_hist_ as (time stamp,
+ * angle), and whether there is one.
+ *   dftpav_planner_install                         exe_index 0, no control history
+ *   dftpav_planner_adopt, the tick's adoption      exe_index 0 (:177); the control history is kept if the slot had a plan (the
+ *                                                  reference keeps ctrl_state_hist_ across replans)
+ *   first plan into an empty slot by the tick      exe_index 0, the history seeded with (t_now + budget, the ego angle), as the
+ *                                                  tick does for the desired-state history, in place of :438-439
+ *   first plan into an empty slot by a plain adopt exe_index 0, no control history
+ *   dftpav_planner_clear                           exe_index 0, the history dropped
+ * NOT reproduced: the idle branch (:210-237), which holds the ego state still, with no plan read, when
+ * nothing executes, when exe_index is past the last segment or when the segment lasts < 1e-5 s -- those ticks report
+ * published = 0 and change nothing --; the 100-entry cap of ctrl_state_hist_ (:259: only its back is ever read); and
+ * use_sim_state_ == false (:241).
+ *
+ * dftpav_planner_publish: K ticks with the clocks t [K], applied in order (they need not increase), for every slot, in ONE
+ *   kernel launch (publish_kernel, replan.hip) on the handle's stream and one read-back at the end.  Per tick and slot, in the
+ *   reference's statements and order: an empty slot, or exe_index past the last segment, publishes nothing; if
+ *   end_time[exe_index] <= t the index advances by ONE (:248-250); past the last segment then, nothing is published, and the slot
+ *   stays finished (:251-252); else the state is GetState(t - start_time[exe_index]) -- clamped to the segment's duration, a
+ *   negative time evaluates piece 0 as it stands --, filtered against the history back where there is one, and becomes the
+ *   history back.  states [K][slots][8]: time_stamp, x, y, angle, curvature, velocity, acceleration, steer (the fields and
+ *   order of dftpav_replan_out.desired), zero where nothing is published.  published [K][slots]: 0 nothing, 1 published, 2
+ *   published with the angle replaced by the filter.  Either may be NULL.  DFTPAV_E_INVALID before the table was filled
+ *   once, for K < 1, K > DFTPAV_PUBLISH_MAX_TICKS, t NULL or a NaN clock; a refused call changes nothing.  The table is not
+ *   written; dftpav_replan_check goes on deriving its index from its clock.
+ * dftpav_planner_publisher_state: reads a slot's state back: exe_index [1], hist [2] (time stamp, angle), have_hist [1]; any may
+ *   be NULL.  Before the table was filled once: zeros.
+ * dftpav_planner_set_ctrl_history: the control history back of `slots` [n] (ctrl_state_hist_.back()): stamps and angles [n].  An
+ *   empty slot is DFTPAV_E_INVALID, as for dftpav_planner_set_history.
+ * dftpav_publish_last_ms: device time in ms (the planner's HIP events) of the last publish kernel; 0 before the first. */
+#define DFTPAV_PUBLISH_CHUNK 256      /* ticks a workgroup of publish_kernel takes at a time */
+#define DFTPAV_PUBLISH_MAX_TICKS 4096 /* the cap on K: 40 s at 100 Hz (the outputs are K * slots rows of device memory) */
+int dftpav_planner_publish(dftpav_planner *p, int K, const double *t, double *states, int *published);
+int dftpav_planner_publisher_state(dftpav_planner *p, int slot, int *exe_index, double *hist, int *have_hist);
+int dftpav_planner_set_ctrl_history(dftpav_planner *p, int n, const int *slots, const double *stamps, const double *angles);
+int dftpav_publish_last_ms(dftpav_planner *p, float *ms);
+
 /* One-shot convenience == OptimizeTrajectory for B trajectories. */
 int dftpav_solve_batch(dftpav_handle *h, const dftpav_layout *layout, int B,
                        const dftpav_batch_data *d, double *x, double *final_cost,
