@@ -39,7 +39,7 @@ EXPORTS = [
     "dftpav_batch_trace", "dftpav_batch_get_trace", "dftpav_plan_cycle", "dftpav_plan_cycle_fetch", "dftpav_batch_create_shaped",
     "dftpav_batch_set_order", "dftpav_batch_get_order", "dftpav_batch_trace_range", "dftpav_batch_get_trace_of",
     "dftpav_comm_available", "dftpav_comm_unique_id", "dftpav_comm_create", "dftpav_comm_destroy", "dftpav_comm_share", "dftpav_comm_layout", "dftpav_batch_allgather_results",
-    "dftpav_default_search_params", "dftpav_kino_search",
+    "dftpav_default_search_params", "dftpav_kino_search", "dftpav_debug_search_slots",
     "dftpav_default_plan_params", "dftpav_planner_create", "dftpav_planner_destroy", "dftpav_plan_queries", "dftpav_planner_info",
     "dftpav_plan_group_layouts", "dftpav_debug_plan_select",
     "dftpav_planner_install", "dftpav_planner_adopt", "dftpav_planner_set_history", "dftpav_planner_clear", "dftpav_planner_executing",

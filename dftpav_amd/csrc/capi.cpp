@@ -789,6 +789,40 @@ struct SearchSetup {
   size_t n_in_tab = 0, n_vv = 0, n_ll = 0;
   int slots = 0;
 };
+
+// The workspace of a search of n queries: per query in flight a node pool, the heap (node, key, position), the path list and the
+// hash table (the power of two >= 2 allocate_num); `slots` queries in flight, n or as many as 6 GiB hold -- the queries beyond run
+// in further launches over the same slots.  Each array holds every slot's part and starts on a 256-byte boundary: off[] in the
+// order pool, h_node, h_pos, path_idx, h_key, table, and `bytes` for all of them.
+struct SearchWorkspace {
+  int hcap = 0, slots = 0;
+  size_t per = 0, off[6] = {}, bytes = 0;
+};
+static SearchWorkspace search_workspace(const dftpav_search_params &P, int n) {
+  SearchWorkspace W;
+  W.hcap = 1;
+  while (W.hcap < 2 * P.allocate_num) W.hcap <<= 1;
+  const size_t A = (size_t)P.allocate_num;
+  W.per = A * sizeof(SearchNode) + A * (3 * sizeof(int) + sizeof(double)) + (size_t)W.hcap * sizeof(int) + 256;
+  const size_t budget = ((size_t)6 << 30) - 6 * 256; // 6 GiB at most, the arrays' alignment included
+  W.slots = (int)std::min<size_t>((size_t)n, std::max<size_t>(1, budget / W.per));
+  const size_t S = (size_t)W.slots;
+  const size_t sizes[6] = {A * S * sizeof(SearchNode), A * S * sizeof(int), A * S * sizeof(int), A * S * sizeof(int),
+                           A * S * sizeof(double), (size_t)W.hcap * S * sizeof(int)};
+  for (int k = 0; k < 6; k++) {
+    W.off[k] = W.bytes;
+    W.bytes += (sizes[k] + 255) / 256 * 256;
+  }
+  return W;
+}
+extern "C" int dftpav_debug_search_slots(const dftpav_search_params *sp, int n, int *slots, size_t *bytes_per_query) {
+  if (!sp || n < 1 || sp->allocate_num < 2) return DFTPAV_E_INVALID;
+  const SearchWorkspace W = search_workspace(*sp, n);
+  if (slots) *slots = W.slots;
+  if (bytes_per_query) *bytes_per_query = W.per;
+  return DFTPAV_OK;
+}
+
 static int search_setup(dftpav_handle *h, const dftpav_search_params *sp, int n, SearchSetup &U) {
   const dftpav_search_params &P = *sp;
   if (P.allocate_num < 2 || P.check_num < 1 || P.max_iters < 0 || !(P.map_resl > 0.0) || !(P.phi_grid_resolution > 0.0) ||
@@ -819,36 +853,32 @@ static int search_setup(dftpav_handle *h, const dftpav_search_params *sp, int n,
   HIPCHK(h, hipSetDevice(h->device));
   if (!h->cev0) HIPCHK(h, hipEventCreate(&h->cev0));
   if (!h->cev1) HIPCHK(h, hipEventCreate(&h->cev1));
-  // workspace per query in flight: node pool, heap (node, key, position), path list, hash table
-  int hcap = 1;
-  while (hcap < 2 * P.allocate_num) hcap <<= 1;
-  const size_t A = (size_t)P.allocate_num;
-  const size_t per = A * sizeof(SearchNode) + A * (3 * sizeof(int) + sizeof(double)) + (size_t)hcap * sizeof(int) + 256;
-  const size_t budget = (size_t)6 << 30; // 6 GiB of workspace at most: the queries beyond run in further launches
-  int slots = (int)std::min<size_t>((size_t)n, std::max<size_t>(1, budget / per));
-  const size_t ws = per * slots;
+  const SearchWorkspace W = search_workspace(P, n);
+  const int hcap = W.hcap, slots = W.slots;
+  const size_t ws = W.bytes;
   if (h->search_ws_bytes < ws) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (h->d_search_ws) (void)hipFree(h->d_search_ws);
     h->d_search_ws = nullptr;
     h->search_ws_bytes = 0;
-    HIPCHK(h, hipMalloc(&h->d_search_ws, ws));
+    const hipError_t e = hipMalloc(&h->d_search_ws, ws);
+    if (e != hipSuccess) { // the handle stays usable: no workspace, and no error left for the next launch's hipGetLastError
+      (void)hipGetLastError();
+      h->d_search_ws = nullptr;
+      h->err = std::string("hipMalloc of the search workspace: ") + hipGetErrorString(e);
+      return DFTPAV_E_HIP;
+    }
     h->search_ws_bytes = ws;
   }
   unsigned char *w = (unsigned char *)h->d_search_ws;
-  auto take = [&](size_t bytes) {
-    void *p = w;
-    w += (bytes + 255) / 256 * 256;
-    return p;
-  };
   SearchArgs &S = U.S;
   S = SearchArgs{};
-  S.pool = (SearchNode *)take(A * slots * sizeof(SearchNode));
-  S.h_node = (int *)take(A * slots * sizeof(int));
-  S.h_pos = (int *)take(A * slots * sizeof(int));
-  S.path_idx = (int *)take(A * slots * sizeof(int));
-  S.h_key = (double *)take(A * slots * sizeof(double));
-  S.table = (int *)take((size_t)hcap * slots * sizeof(int));
+  S.pool = (SearchNode *)(w + W.off[0]);
+  S.h_node = (int *)(w + W.off[1]);
+  S.h_pos = (int *)(w + W.off[2]);
+  S.path_idx = (int *)(w + W.off[3]);
+  S.h_key = (double *)(w + W.off[4]);
+  S.table = (int *)(w + W.off[5]);
   S.hcap = hcap;
   S.sp = P;
   S.cells = h->d_cells;

@@ -229,11 +229,12 @@ __device__ void sr_search(const SearchArgs &A, SShared &S, SearchNode *pool, Kin
   }
   __syncthreads();
   for (;;) {
-    // top of the open set (an empty set: "open set empty, no path", :298-300)
+    // top of the open set (an empty set: "open set empty, no path", :298-300).  The empty set is told by cur_node, not by go:
+    // other waves may still be reading go after the barrier that ended the last expansion
     if (lane == 0) {
       if (heap.empty()) {
         S.status = kNoPath;
-        S.go = 0;
+        S.cur_node = -1;
       } else {
         const int t = heap.top();
         S.cur_node = t;
@@ -243,7 +244,7 @@ __device__ void sr_search(const SearchArgs &A, SShared &S, SearchNode *pool, Kin
       }
     }
     __syncthreads();
-    if (!S.go) break;
+    if (S.cur_node < 0) break;
     const double cur[3] = {S.cur[0], S.cur[1], S.cur[2]};
     // the shot, :90-114
     int shot = 0;

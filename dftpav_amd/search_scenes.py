@@ -72,6 +72,18 @@ def small_scenes():
     return [empty(), moving_start(), wall_gap(), reverse(), enclosed(), occupied_start(), occupied_goal()]
 
 
+MAZE_MAX_ITERS = 2000           # the oracle (order 2) ends on this budget with nodes_used = 5337 (4162 at 1500, 6638 at 2500)
+
+
+def maze():
+    """two staggered walls between start and goal: a search of thousands of nodes (a deep heap with in-place key changes).  Not one
+    of small_scenes(): at the default budget it runs its 20 000 iterations out, with 28 677 nodes.  Run it with
+    max_iters = MAZE_MAX_ITERS, the smallest multiple of 500 at which the oracle uses 5000 nodes or more; it ends on that budget."""
+    g = _box(_grid(), -8.0, -20.0, -7.0, 10.0)
+    g = _box(g, -1.0, -10.0, 0.0, 20.0)
+    return "maze", g, RES, ORIGIN, np.array([-15.0, -5.0, 0.0, 0.0]), np.array([3.0, 0.0, 0.0, 0.0])
+
+
 # goals on the default arena (sc.default_sim_map): free poses near the ego vehicle whose direct shot from the ego start
 # collides (checked by tests/test_search_oracle.py)
 ARENA_GOALS = np.array([

@@ -634,6 +634,11 @@ typedef struct dftpav_search_out {
  * inputs x check_num > 256, a shot longer than its sample table).  dftpav_corridor_last_ms reports the kernel time. */
 int dftpav_kino_search(dftpav_handle *h, const dftpav_search_params *sp, const double *start_states, const double *start_ctrl,
                        const double *end_states, int n, const dftpav_search_out *out);
+/* Test hook, pure host code: the workspace arithmetic of a search of n queries.  bytes_per_query: node pool, heap, path list
+ * and hash table of one query in flight; slots: the queries in flight at once, n or as many as 6 GiB of workspace hold (at
+ * least 1) -- the queries beyond run in further launches over the same slots.  Either pointer may be NULL.
+ * DFTPAV_E_INVALID for n < 1 or allocate_num < 2. */
+int dftpav_debug_search_slots(const dftpav_search_params *sp, int n, int *slots, size_t *bytes_per_query);
 
 /* ---- a batch of start / goal queries to their plans, mixed layouts included --------------
  * Replaces TrajPlanner::RunOnceParking from the arrival test on (traj_manager.cpp:194-217): per query the

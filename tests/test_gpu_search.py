@@ -1,6 +1,7 @@
 """dftpav_kino_search on the device against the CPU restatement in order 2 (oracle_search/), bit for bit in every output field,
-on a batch of every scene of dftpav_amd/search_scenes.py; then the default-arena chain with a real search in front:
-kino_search -> frontend_resample -> corridor_from_states -> reference-order solve -> validate."""
+on a batch of every scene of dftpav_amd/search_scenes.py; on the cases of search_cases.py, the branches that the default parameters
+and searches that end well never take; with more queries than workspace slots; then the default-arena chain with a real search in
+front: kino_search -> frontend_resample -> corridor_from_states -> reference-order solve -> validate."""
 import numpy as np
 import pytest
 
@@ -8,6 +9,8 @@ from dftpav_amd import search_scenes as ss
 from dftpav_amd.pods import FrontendParams, LayoutSpec, SearchParams
 from dftpav_amd.scenarios import Scenario
 from oracle_search import pysearch as ps
+
+import search_cases as sc
 
 pytestmark = pytest.mark.gpu
 
@@ -48,6 +51,59 @@ def test_batch_matches_the_oracle(hiplib, variant):
     o = ps.kino_search(grid, res, org, S, E, sp=sp, order=2, nthreads=8)
     _compare(r, o)
     assert (r["status"] == 2).all()
+    h.close()
+
+
+@pytest.fixture(scope="module")
+def scene_handles(hiplib):
+    """one handle per scene of search_cases.py, kept for the module: the cases of a scene follow one another over one workspace,
+    whatever allocate_num each asks for"""
+    handles = {}
+    yield handles, hiplib
+    for h in handles.values():
+        h.close()
+
+
+@pytest.mark.parametrize("case", sc.NEW_CASES)
+def test_case_matches_the_oracle(scene_handles, case):
+    """the branches only the CPU restatement took before (search_cases.py: the budget exit, node-pool exhaustion with its 2D retry
+    in a crowded hash table, the bounds of the search space, every parameter off its default, yaws to wrap, a search of 5337 nodes):
+    every output field bit-equal to the restatement in order 2.  tests/test_search_oracle.py holds each case to its condition."""
+    handles, hiplib = scene_handles
+    grid, res, org, S, E, sp = sc.queries(case)
+    scene = sc.CASES[case][0]
+    if scene not in handles:
+        handles[scene] = hiplib.Handle()
+        handles[scene].set_grid_map(grid, res, org)
+    r = handles[scene].kino_search(S, E, sp=sp)
+    _compare(r, sc.oracle(case))
+
+
+def test_more_queries_than_slots_and_workspace_reuse(hiplib):
+    """32 queries with allocate_num = 4194304 fit 14 at a time into the 6 GiB of workspace: three launches, the later ones writing
+    the outputs of q0 + block over the slots of the first; before and after it a call at the default parameters, the workspace grown
+    and then reused.  No search here uses more than 448 nodes, far below either pool size, and no output depends on allocate_num
+    otherwise: the large call equals the default run's rows, cycled."""
+    import ctypes as C
+    big = SearchParams.default().copy(allocate_num=4194304)
+    fn = hiplib.lib().dftpav_debug_search_slots
+    fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
+    slots = C.c_int(0)
+    assert fn(C.byref(big), 32, C.byref(slots), None) == hiplib.OK and slots.value == 14
+    grid, res, org, S, E, _ = sc.queries("default-arena")
+    o = sc.oracle("default-arena")
+    assert o["nodes_used"].max() == 448
+    idx = np.arange(32) % len(S)
+    h = hiplib.Handle()
+    h.set_grid_map(grid, res, org)
+    first = h.kino_search(S, E)
+    cycled = h.kino_search(S[idx], E[idx], sp=big)
+    again = h.kino_search(S, E)
+    _compare(first, o)
+    _compare(again, o)
+    _compare(again, first)
+    for k in o:
+        assert np.array_equal(cycled[k], o[k][idx]), k
     h.close()
 
 
