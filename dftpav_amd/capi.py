@@ -39,7 +39,7 @@ EXPORTS = [
     "dftpav_batch_trace", "dftpav_batch_get_trace", "dftpav_plan_cycle", "dftpav_plan_cycle_fetch", "dftpav_batch_create_shaped",
     "dftpav_batch_set_order", "dftpav_batch_get_order", "dftpav_batch_trace_range", "dftpav_batch_get_trace_of",
     "dftpav_comm_available", "dftpav_comm_unique_id", "dftpav_comm_create", "dftpav_comm_destroy", "dftpav_comm_share", "dftpav_comm_layout", "dftpav_batch_allgather_results",
-    "dftpav_default_search_params", "dftpav_kino_search", "dftpav_debug_search_slots",
+    "dftpav_default_search_params", "dftpav_kino_search", "dftpav_debug_search_slots", "dftpav_debug_validation_table",
     "dftpav_default_plan_params", "dftpav_planner_create", "dftpav_planner_destroy", "dftpav_plan_queries", "dftpav_planner_info",
     "dftpav_plan_group_layouts", "dftpav_debug_plan_select",
     "dftpav_planner_install", "dftpav_planner_adopt", "dftpav_planner_set_history", "dftpav_planner_clear", "dftpav_planner_executing",
@@ -620,6 +620,19 @@ def debug_plan_select(handle, cost, success, collision):
     ptr = lambda a: a.ctypes.data_as(C.c_void_p)
     handle._check(fn(handle._h, nq, R, ptr(c), ptr(s), ptr(k), ptr(w)), "debug_plan_select")
     return w
+
+
+def debug_validation_table(params, check_dt, vertex_res, max_spacings=0):
+    """dftpav_debug_validation_table (host only): (return code, sample times [n_t], spacings [n_v]) of the collision re-check's tables;
+    the arrays are None unless the code is OK"""
+    out = np.zeros(8192)
+    n_t, n_v = C.c_int(0), C.c_int(0)
+    fn = lib().dftpav_debug_validation_table
+    fn.argtypes = [C.POINTER(Params), C.c_double, C.c_double, C.c_int, C.c_void_p, c_int_p, c_int_p]
+    rc = fn(C.byref(params), float(check_dt), float(vertex_res), int(max_spacings), out.ctypes.data_as(C.c_void_p), C.byref(n_t), C.byref(n_v))
+    if rc != OK:
+        return rc, None, None
+    return rc, out[:n_t.value].copy(), out[n_t.value:n_t.value + n_v.value].copy()
 
 
 class GridMap(C.Structure):

@@ -1,224 +1,12 @@
-// capi.cpp — host half of the C-ABI declared in include/dftpav_hip.h.
+// capi.cpp — host half of the C-ABI declared in include/dftpav_hip.h: parameters, the handle and its moving obstacles, and a batch
+// from its creation to its results.
 //
 // Holds what PolyTrajOptimizer::OptimizeTrajectory does before and after the
 // L-BFGS call (traj_optimizer.cpp:7-134, 176-201): validation, corridor normal
 // normalisation, boundary clamping, decision-vector packing, status mapping.
 // Everything between (the solve itself) is the kernel in solver.hip.
-// There is deliberately no CPU fallback: without a usable HIP device every
-// entry point that needs one fails with DFTPAV_E_NO_DEVICE.
-#include <hip/hip_runtime.h>
-#include <dlfcn.h>
-#include <atomic>
-#include <mutex>
-
-#include <climits>
-#include <cmath>
-#include <cstdio>
-#include <algorithm>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#include "../../include/dftpav_hip.h"
-#include "device_types.h"
-#include "e4_plan.h"
-#include "traj_math.h"
-#include "cr_trig.h"
-#include "rs_math.h"
-#include "search_args.h"
-#include "plan_args.h"
-
-namespace dftpav {
-hipError_t launch_solver(const DevBatch &D, const DevBatch *d_dev, int mode, int threads, int grid, SchedArgs sched,
-                         hipStream_t stream);
-hipError_t launch_corridor(const unsigned char *cells, const unsigned *bits, int size_x, int size_y, double resolution, double origin_x, double origin_y,
-                           const double *states, int n, double veh_width, double veh_length, double veh_dcr, const double *dl,
-                           int n_dl, double *hpoly, double *batch_cor, int Npts, int NptsPad, int replicate, hipStream_t stream);
-hipError_t launch_frontend(const dftpav_frontend_params &fp, const double *paths, const int *path_len, int max_path,
-                           const double *start_states, const double *end_states, const double *start_ctrl, int n_hyp,
-                           const dftpav_frontend_out &out, hipStream_t stream);
-hipError_t launch_restarts(const double *inner, const double *durs, int n_hyp, int n_restarts, int n_inner, int M, double sigma,
-                           double lo, double hi, unsigned long long seed, double *out_inner, double *out_durs, hipStream_t stream);
-hipError_t launch_fit(const double *states, int S, int n_states, const double *opM, double *dur, double *coef, double *total,
-                      double *start, hipStream_t stream);
-hipError_t launch_validate(const unsigned char *cells, int size_x, int size_y, double resolution, double origin_x, double origin_y,
-                           const double *coeffs, const double *piece_dt, const DevLayout &L, int B, double veh_width,
-                           double veh_length, double veh_dcr, const double *t_tab, int n_t, double sample_dt, const double *v_tab,
-                           int n_v, int *collision, int *first_sample, hipStream_t stream);
-hipError_t launch_states(const double *coeffs, const double *piece_dt, const DevLayout &L, int B, double wheel_base, double t0,
-                         double sample_dt, int n_samples, int filter, double *states, int *n_valid, hipStream_t stream);
-hipError_t launch_shots(const double *from, const double *to, int n, double rho, double checkl, int max_samples,
-                        const unsigned char *cells, int size_x, int size_y, double resolution, double origin_x, double origin_y,
-                        double veh_width, double veh_length, double veh_dcr, const double *v_tab, int n_v, double *length, int *type,
-                        double *seg, double *samples, int *n_samples, int *collides, hipStream_t stream);
-hipError_t launch_search(const SearchArgs &A, int blocks, hipStream_t stream);
-// plan.hip: the kernels between the stages of dftpav_plan_queries
-hipError_t launch_plan_paths(const int *status, const int *path_len, const int *skip, int n, int max_path, double *paths, int *fe_len,
-                             hipStream_t stream);
-hipError_t launch_plan_pack(const PlanPackArgs &A, hipStream_t stream);
-hipError_t launch_plan_select(const PlanSelectArgs &A, hipStream_t stream);
-hipError_t launch_replan_check(const ReplanArgs &A, hipStream_t stream);
-hipError_t launch_exec_adopt(const ExecAdoptArgs &A, hipStream_t stream);
-hipError_t launch_publish(const PublishArgs &A, hipStream_t stream);
-hipError_t launch_pub_reset(const PubResetArgs &A, hipStream_t stream);
-hipError_t launch_corridor_layout(const double *raw, double *out, int B, int Npts, int H, int NptsPad, hipStream_t stream);
-hipError_t launch_adopt(const DevBatch &D, const DevBatch &prev, hipStream_t stream);
-// solver_ref.hip: the same path in the reference's own floating-point order
-bool reference_order_supported(const DevLayout &L, const DevParams &P, int S);
-size_t reference_order_scratch_doubles(const DevLayout &L, int B, int S);
-size_t reference_order_table_doubles(int N);
-void reference_order_pack_tables(int N, const double *full, double *packed);
-int reference_order_interior_mask(int sweep, int row_mod_6);
-RefPlan reference_order_plan(const DevLayout &L, const DevParams &P, int S, int B, int n_cu, bool throughput, const RefOptions &o);
-hipError_t launch_ring_reset(const DevBatch &D, hipStream_t stream);
-hipError_t launch_solver_ref(const DevBatch &D, const DevBatch *d_dev, int mode, const double *tabs, double *scratch, const RefPlan &pl, int scheduled,
-                             hipStream_t stream);
-hipError_t launch_solver_quad(const DevBatch &D, const DevBatch *d_dev, int mode, const double *tabs, const double *cor_t, bool rect, double *scratch,
-                              const RefPlan &pl, int scheduled, bool alone, hipStream_t stream);
-// the QUAD shapes' copy of the corridor (solver_ref4.hip: one gear segment, solver_ref4m.hip: several)
-size_t reference_order_quad_corridor_doubles(const DevLayout &L, int B);
-hipError_t launch_quad_corridor(const DevBatch &D, double *cor_t, bool rect, hipStream_t stream);
-hipError_t launch_quad_rect_check(const double *corridor, int B, int Npts, int NptsPad, int *d_flag, hipStream_t stream);
-hipError_t launch_quadm_corridor(const DevBatch &D, double *cor_t, hipStream_t stream);
-}
-using namespace dftpav;
-
-// An RCCL communicator and the number of handles that hold it (its creator and the handles it was shared with, each on its own
-// host thread at most): the communicator is destroyed by whichever of them lets go last, in whatever order they do.  An RCCL
-// communicator does not take concurrent enqueues: `mu` is held around every call on it (the holders' threads serialise there;
-// the ORDER of the collectives across ranks stays the host's business -- same order on every rank).  Taking and dropping a
-// reference (share / destroy / create) happens under g_comm_mu, so a handle never reads another's comm_ref while that one
-// lets go of it.
-struct CommShared {
-  void *comm;
-  std::atomic<int> holders;
-  std::mutex mu;
-};
-static std::mutex g_comm_mu;
-
-struct dftpav_handle {
-  dftpav_params params;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::string err;
-  // moving obstacles (device copies)
-  int S = 0;
-  int sur_pieces = 0; // pieces of all obstacles together
-  int sur_version = 0; // bumped by dftpav_set_surround so batches refresh their device descriptor
-  int *d_sur_off = nullptr;
-  double *d_sur_dur = nullptr, *d_sur_coef = nullptr, *d_sur_total = nullptr, *d_sur_start = nullptr, *d_sur_theta = nullptr, *d_sur_bbox = nullptr;
-  // obstacle map of the corridor generator (device copy) and the table of sample offsets along a line
-  dftpav_grid_map map{};
-  unsigned char *d_cells = nullptr;
-  unsigned *d_bits = nullptr; // one bit per cell, when the whole map fits in a quarter of the LDS
-  double *d_dl = nullptr;
-  int n_dl = 0;
-  hipEvent_t cev0 = nullptr, cev1 = nullptr; // around the last corridor kernel
-  hipEvent_t mark[2] = {nullptr, nullptr};   // dftpav_mark
-  bool ctimed = false;
-  std::vector<struct dftpav_batch *> batches; // every live batch of this handle (obstacle changes finish their chained stragglers)
-  // RCCL communicator of dftpav_comm_create (one rank per handle = per GPU), and the staging block of this rank's records
-  void *comm = nullptr;
-  struct CommShared *comm_ref = nullptr; // the communicator's holders (dftpav_comm_share): destroyed when the last one lets go
-  int comm_ranks = 0, comm_rank = 0;
-  unsigned char *d_comm_send = nullptr;
-  size_t comm_send_bytes = 0;
-  // workspace of dftpav_kino_search (node pools, heaps, hash tables of the queries in flight), grown on demand
-  void *d_search_ws = nullptr;
-  size_t search_ws_bytes = 0;
-};
-
-struct dftpav_batch {
-  dftpav_handle *h = nullptr;
-  int B = 0;
-  int n_active = 0; // dftpav_plan_queries: the leading trajectories in use this call (0: all B); the kernels see it as the batch size
-  DevLayout L{};
-  DevParams P{};
-  int threads = 0;
-  bool op_in_lds = false, cor_in_lds = false;
-  bool have_corridor = false; // set by dftpav_batch_upload (host corridor) or dftpav_batch_corridor_from_states
-  // time-sliced scheduling (batches larger than the device holds at once): the queue launch runs in the
-  // shape above, the stragglers it hands over finish in the latency shape below
-  bool sched = false;
-  int slots = 0, slice = 0, hand_over = 0;
-  int threads2 = 0;
-  bool op_in_lds2 = false, cor_in_lds2 = false;
-  int *d_queue = nullptr, *d_stragglers = nullptr, *d_stragglers2 = nullptr, *d_sflag = nullptr, *d_iota = nullptr;
-  int qcap = 0;
-  bool pending = false; // a chained solve left this batch's stragglers for the next chained solve (or dftpav_batch_finish)
-  unsigned *d_qctl = nullptr;
-  double *d_state = nullptr;
-  DevBatch *d_dev2 = nullptr;
-  // E4 lane plans (e4_plan.h) of the two launch shapes: host copies of the sizes, device tables
-  E4Sizes e4{}, e4b{};
-  int *d_e4[2][5] = {{nullptr, nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr, nullptr}}; // gtab, ltab, wave, round, piece
-  int NptsPad = 0;
-  std::vector<double> x0_host;
-  bool uploaded = false;
-  double t_now = 0.0, epis = 0.0;
-  // device buffers
-  double *d_x0 = nullptr, *d_iniS = nullptr, *d_finS = nullptr, *d_corridor = nullptr;
-  int16_t *d_pt_piece = nullptr, *d_pt_j = nullptr;
-  double *d_opM[kMaxSeg] = {nullptr}, *d_opMT[kMaxSeg] = {nullptr};
-  double *d_histS = nullptr, *d_histY = nullptr, *d_histU = nullptr, *d_histV = nullptr, *d_histR = nullptr;
-  double *d_histM = nullptr; // QUAD shape of the reference order: the mirrored ends of the history rings (DevBatch::histM)
-  double *d_x_in = nullptr, *d_x_out = nullptr, *d_f = nullptr, *d_g = nullptr;
-  int *d_status = nullptr, *d_success = nullptr, *d_iters = nullptr, *d_evals = nullptr;
-  long long *d_hist = nullptr, *d_ticks = nullptr, *d_prof = nullptr;
-  unsigned char *d_records = nullptr; // [B + 1][16] result records written by the solver's epilogue (+ one zero record of padding)
-  unsigned char *h_records = nullptr; // [B][16] the same in pinned host memory, written by the epilogues too (DevBatch::records_host)
-  DevBatch *d_dev = nullptr; // device copy of the launch descriptor
-  int dev_version = -1;
-  // pinned host staging of the two descriptors and the event behind their last copy: refreshing the device copies then
-  // needs no stream synchronisation (dftpav_plan_cycle enqueues the corridor kernel in front of the solve and must not wait for it)
-  DevBatch *h_stage = nullptr;
-  hipEvent_t stage_ev = nullptr;
-  bool stage_busy = false;
-  bool prof_on = false;
-  double *d_coef = nullptr, *d_dt = nullptr;
-  double *d_f_eval = nullptr; // costs of dftpav_batch_eval (kept apart from the solve's final costs)
-  double *d_trace = nullptr;  // dftpav_batch_trace
-  double *d_cor_raw = nullptr; // the caller's hPoly columns as uploaded (normalised and laid out on the device)
-  // dftpav_batch_set_order(DFTPAV_ORDER_REFERENCE): the substitution tables of the band system and the term records (solver_ref.hip)
-  int order = DFTPAV_ORDER_DEVICE;
-  int ref_S = 0; // moving obstacles on the handle when the reference order was chosen (the term records are sized for them)
-  double *d_ref_tab = nullptr, *d_ref_scratch = nullptr;
-  RefPlan ref_plan{}; // its launch plan (chosen with the order)
-  double *d_cor_t = nullptr; // QUAD shapes: the corridor as [B][4 H][Kmax + 1][16] (solver_ref4.hip), refreshed when the corridor changes
-  bool cor_t_dirty = true;
-  // Rectangles (solver_ref4.hip: RECT).  cor_rect: every corridor in d_corridor is known to be one -- learned by dftpav_batch_upload,
-  // which waits for the device anyway; the corridors the device makes from the map (dftpav_batch_corridor_from_hypotheses,
-  // dftpav_plan_cycle: no wait, none added) leave it false and run the sixteen-double layout.  cor_t_rect: the layout d_cor_t is in.
-  bool cor_rect = false, cor_t_rect = false;
-  int *d_rect_flag = nullptr;
-  bool coef_override = false; // test hook dftpav_debug_batch_set_coeffs: validate / sample_states take the coefficients as they are
-  int residency = -1; // the caller's residency hint (dftpav_batch_create_shaped); 2 = many such batches in flight: the throughput shapes whatever B
-  // dftpav_plan_cycle: work buffers that live from the call to dftpav_plan_cycle_fetch (reused by the next cycle)
-  struct PlanCycle {
-    double *d_poses = nullptr, *d_t = nullptr, *d_v = nullptr, *d_rd = nullptr;
-    int *d_col = nullptr, *d_first = nullptr, *d_valid = nullptr;
-    size_t n_poses = 0, n_t = 0, n_v = 0, n_rd = 0;
-    std::vector<double> poses, tt, vv; // host sources of the asynchronous copies
-    int n_samples = 0;
-    bool in_flight = false;
-  } pc;
-  int trace_b = -1, trace_cap = 0, trace_n = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool timed = false;  // a solve was enqueued: ev0 / ev1 are recorded
-  bool solved = false; // results of a solve of the CURRENT inputs exist (cleared by dftpav_batch_upload)
-};
-
-#define HIPCHK(h, call)                                                                  \
-  do {                                                                                   \
-    hipError_t e_ = (call);                                                              \
-    if (e_ != hipSuccess) {                                                              \
-      (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);                      \
-      return DFTPAV_E_HIP;                                                               \
-    }                                                                                    \
-  } while (0)
-
-extern "C" int dftpav_comm_destroy(dftpav_handle *h);
+// The other host units are listed in capi_internal.h.
+#include "capi_internal.h"
 
 // ------------------------------------------------------------------ params
 extern "C" void dftpav_default_params(dftpav_params *p) {
@@ -309,7 +97,6 @@ extern "C" int dftpav_create(const dftpav_params *params, int device, dftpav_han
   return DFTPAV_OK;
 }
 
-static int finish_pending(dftpav_batch *b);
 // The obstacle set is captured by every batch's launch descriptor: suspended stragglers of a chained solve must finish
 // against the obstacles they started with, so they are finished before the set changes.
 static int finish_batches_of(dftpav_handle *h) {
@@ -478,106 +265,6 @@ extern "C" void *dftpav_stream(dftpav_handle *h) { return h ? (void *)h->stream 
 
 static void minco_operator(int N, std::vector<double> &Mop, std::vector<double> &MopT);
 
-extern "C" int dftpav_sample_restarts(dftpav_handle *h, const double *inner_pts, const double *durations, int n_hyp, int n_restarts,
-                                      int n_inner, int M, double sigma, double dur_lo, double dur_hi, unsigned long long seed,
-                                      double *out_inner_pts, double *out_durations) {
-  if (!h || !inner_pts || !durations || !out_inner_pts || !out_durations || n_hyp < 0 || n_restarts < 1 || n_inner < 0 ||
-      (n_inner & 1) || M < 1 || !(sigma >= 0.0) || !(dur_lo > 0.0) || !(dur_hi >= dur_lo))
-    return DFTPAV_E_INVALID;
-  if (n_hyp == 0) return DFTPAV_OK;
-  HIPCHK(h, hipSetDevice(h->device));
-  const size_t B = (size_t)n_hyp * n_restarts;
-  double *d_in = nullptr, *d_du = nullptr, *d_oi = nullptr, *d_od = nullptr;
-  int rc = DFTPAV_OK;
-  auto chk = [&](hipError_t e) {
-    if (e != hipSuccess && rc == DFTPAV_OK) {
-      h->err = hipGetErrorString(e);
-      rc = DFTPAV_E_HIP;
-    }
-  };
-  chk(hipMalloc(&d_in, sizeof(double) * std::max<size_t>(1, (size_t)n_hyp * n_inner)));
-  chk(hipMalloc(&d_du, sizeof(double) * (size_t)n_hyp * M));
-  chk(hipMalloc(&d_oi, sizeof(double) * std::max<size_t>(1, B * n_inner)));
-  chk(hipMalloc(&d_od, sizeof(double) * B * M));
-  if (rc == DFTPAV_OK) {
-    chk(hipMemcpyAsync(d_in, inner_pts, sizeof(double) * (size_t)n_hyp * n_inner, hipMemcpyHostToDevice, h->stream));
-    chk(hipMemcpyAsync(d_du, durations, sizeof(double) * (size_t)n_hyp * M, hipMemcpyHostToDevice, h->stream));
-    chk(launch_restarts(d_in, d_du, n_hyp, n_restarts, n_inner, M, sigma, dur_lo, dur_hi, seed, d_oi, d_od, h->stream));
-    chk(hipMemcpyAsync(out_inner_pts, d_oi, sizeof(double) * B * n_inner, hipMemcpyDeviceToHost, h->stream));
-    chk(hipMemcpyAsync(out_durations, d_od, sizeof(double) * B * M, hipMemcpyDeviceToHost, h->stream));
-    chk(hipStreamSynchronize(h->stream));
-  }
-  for (double *p : {d_in, d_du, d_oi, d_od})
-    if (p) (void)hipFree(p);
-  return rc;
-}
-
-extern "C" int dftpav_frontend_resample(dftpav_handle *h, const dftpav_frontend_params *fp, const double *paths, const int *path_len,
-                                        int max_path, const double *start_states, const double *end_states,
-                                        const double *start_ctrl, int n_hyp, const dftpav_frontend_out *out) {
-  if (!h || !fp || !paths || !path_len || !start_states || !end_states || !start_ctrl || !out || n_hyp < 0 || max_path < 2)
-    return DFTPAV_E_INVALID;
-  if (out->max_seg < 1 || out->max_seg > 16 || out->max_pieces < 2 || out->max_states < 1) return DFTPAV_E_UNSUPPORTED;
-  if (fp->traj_res < 1 || fp->dense_traj_res < 1 || !(fp->piece_duration > 0.0)) return DFTPAV_E_INVALID;
-  for (int i = 0; i < n_hyp; i++)
-    if (path_len[i] < 2 || path_len[i] > max_path) return DFTPAV_E_INVALID;
-  if (n_hyp == 0) return DFTPAV_OK;
-  HIPCHK(h, hipSetDevice(h->device));
-  const size_t nh = (size_t)n_hyp, MS = (size_t)out->max_seg, MP = (size_t)out->max_pieces, MST = (size_t)out->max_states;
-  struct Buf {
-    void **dev;
-    const void *src; // host input (nullptr for outputs)
-    void *dst;       // host output
-    size_t bytes;
-  };
-  double *d_paths = nullptr, *d_ss = nullptr, *d_es = nullptr, *d_sc = nullptr;
-  int *d_len = nullptr;
-  dftpav_frontend_out D = *out; // device pointers below
-  D.n_seg = nullptr; D.singul = nullptr; D.piece_nums = nullptr; D.piece_dt = nullptr; D.ini_states = nullptr;
-  D.fin_states = nullptr; D.inner_pts = nullptr; D.n_states = nullptr; D.states = nullptr;
-  Buf bufs[] = {
-      {(void **)&d_paths, paths, nullptr, sizeof(double) * nh * max_path * 3},
-      {(void **)&d_len, path_len, nullptr, sizeof(int) * nh},
-      {(void **)&d_ss, start_states, nullptr, sizeof(double) * nh * 4},
-      {(void **)&d_es, end_states, nullptr, sizeof(double) * nh * 4},
-      {(void **)&d_sc, start_ctrl, nullptr, sizeof(double) * nh * 2},
-      {(void **)&D.n_seg, nullptr, out->n_seg, sizeof(int) * nh},
-      {(void **)&D.singul, nullptr, out->singul, sizeof(int) * nh * MS},
-      {(void **)&D.piece_nums, nullptr, out->piece_nums, sizeof(int) * nh * MS},
-      {(void **)&D.piece_dt, nullptr, out->piece_dt, sizeof(double) * nh * MS},
-      {(void **)&D.ini_states, nullptr, out->ini_states, sizeof(double) * nh * MS * 6},
-      {(void **)&D.fin_states, nullptr, out->fin_states, sizeof(double) * nh * MS * 6},
-      {(void **)&D.inner_pts, nullptr, out->inner_pts, sizeof(double) * nh * MS * (MP - 1) * 2},
-      {(void **)&D.n_states, nullptr, out->n_states, sizeof(int) * nh * MS},
-      {(void **)&D.states, nullptr, out->states, sizeof(double) * nh * MS * MST * 3},
-  };
-  int rc = DFTPAV_OK;
-  auto chk = [&](hipError_t e) {
-    if (e != hipSuccess && rc == DFTPAV_OK) {
-      h->err = hipGetErrorString(e);
-      rc = DFTPAV_E_HIP;
-    }
-  };
-  for (Buf &b : bufs) {
-    if (!b.src && !b.dst) {
-      rc = DFTPAV_E_INVALID;
-      break;
-    }
-    chk(hipMalloc(b.dev, b.bytes));
-    if (rc != DFTPAV_OK) break;
-    if (b.src) chk(hipMemcpyAsync(*b.dev, b.src, b.bytes, hipMemcpyHostToDevice, h->stream));
-    else chk(hipMemsetAsync(*b.dev, 0, b.bytes, h->stream));
-  }
-  if (rc == DFTPAV_OK) chk(launch_frontend(*fp, d_paths, d_len, max_path, d_ss, d_es, d_sc, n_hyp, D, h->stream));
-  if (rc == DFTPAV_OK)
-    for (Buf &b : bufs)
-      if (b.dst) chk(hipMemcpyAsync(b.dst, *b.dev, b.bytes, hipMemcpyDeviceToHost, h->stream));
-  chk(hipStreamSynchronize(h->stream));
-  for (Buf &b : bufs)
-    if (*b.dev) (void)hipFree(*b.dev);
-  return rc;
-}
-
 // The solver numbers (constraint point, obstacle) pairs with 16 bits and keeps a 16-bit mask of obstacles per point; its
 // tables of the obstacles' pieces live in LDS.  A set beyond that is refused where it is installed, not at the first solve.
 static int check_surround_limits(dftpav_handle *h, int S, long long pieces) {
@@ -585,6 +272,41 @@ static int check_surround_limits(dftpav_handle *h, int S, long long pieces) {
     h->err = "too many moving obstacles (at most DFTPAV_MAX_SURROUND = 16 with DFTPAV_MAX_SURROUND_PIECES = 512 pieces in all)";
     return DFTPAV_E_UNSUPPORTED;
   }
+  return DFTPAV_OK;
+}
+// the fit itself: the obstacles' pieces into the handle's (freshly freed) tables, then the host's tables from them
+static int fit_surround_tables(dftpav_handle *h, const double *states, int S, int n_states) {
+  const int N = n_states - 1, np = S * N;
+  std::vector<int> off(S + 1);
+  for (int i = 0; i <= S; i++) off[i] = i * N;
+  std::vector<double> Mop, MopT;
+  minco_operator(N, Mop, MopT);
+  HIPCHK(h, hipMalloc(&h->d_sur_off, sizeof(int) * (S + 1)));
+  HIPCHK(h, hipMalloc(&h->d_sur_dur, sizeof(double) * np));
+  HIPCHK(h, hipMalloc(&h->d_sur_coef, sizeof(double) * 12 * np));
+  HIPCHK(h, hipMalloc(&h->d_sur_total, sizeof(double) * S));
+  HIPCHK(h, hipMalloc(&h->d_sur_start, sizeof(double) * S));
+  {
+    DevScratch tmp(h);
+    double *d_states = nullptr, *d_op = nullptr;
+    HIPCHK(h, tmp.alloc(d_states, 7 * (size_t)S * n_states));
+    HIPCHK(h, tmp.alloc(d_op, Mop.size()));
+    HIPCHK(h, hipMemcpyAsync(h->d_sur_off, off.data(), sizeof(int) * (S + 1), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_states, states, sizeof(double) * 7 * (size_t)S * n_states, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_op, Mop.data(), sizeof(double) * Mop.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, launch_fit(d_states, S, n_states, d_op, h->d_sur_dur, h->d_sur_coef, h->d_sur_total, h->d_sur_start, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream)); // off / Mop live on this stack frame
+  }
+  std::vector<double> dur(np);
+  HIPCHK(h, hipMemcpy(dur.data(), h->d_sur_dur, sizeof(double) * np, hipMemcpyDeviceToHost));
+  if (int rc = upload_theta(h, off, dur)) return rc;
+  if (h->d_sur_theta) {
+    std::vector<double> coef(12 * (size_t)np);
+    HIPCHK(h, hipMemcpy(coef.data(), h->d_sur_coef, sizeof(double) * coef.size(), hipMemcpyDeviceToHost));
+    if (int rc = upload_boxes(h, dur, coef)) return rc;
+  }
+  h->S = S;
+  h->sur_pieces = np;
   return DFTPAV_OK;
 }
 extern "C" int dftpav_fit_surround(dftpav_handle *h, const double *states, int S, int n_states) {
@@ -597,54 +319,8 @@ extern "C" int dftpav_fit_surround(dftpav_handle *h, const double *states, int S
   free_surround(h);
   h->sur_version++;
   if (S == 0) return DFTPAV_OK; // ConverSurroundTrajFromPoints returns without obstacles, traj_manager.cpp:750-752
-  const int N = n_states - 1, np = S * N;
-  std::vector<int> off(S + 1);
-  for (int i = 0; i <= S; i++) off[i] = i * N;
-  std::vector<double> Mop, MopT;
-  minco_operator(N, Mop, MopT);
-  double *d_states = nullptr, *d_op = nullptr;
-  HIPCHK(h, hipMalloc(&h->d_sur_off, sizeof(int) * (S + 1)));
-  HIPCHK(h, hipMalloc(&h->d_sur_dur, sizeof(double) * np));
-  HIPCHK(h, hipMalloc(&h->d_sur_coef, sizeof(double) * 12 * np));
-  HIPCHK(h, hipMalloc(&h->d_sur_total, sizeof(double) * S));
-  HIPCHK(h, hipMalloc(&h->d_sur_start, sizeof(double) * S));
-  HIPCHK(h, hipMalloc(&d_states, sizeof(double) * 7 * (size_t)S * n_states));
-  if (hipMalloc(&d_op, sizeof(double) * Mop.size()) != hipSuccess) {
-    (void)hipFree(d_states);
-    h->err = "hipMalloc";
-    return DFTPAV_E_HIP;
-  }
-  int rc = DFTPAV_OK;
-  auto chk = [&](hipError_t e) {
-    if (e != hipSuccess && rc == DFTPAV_OK) {
-      h->err = hipGetErrorString(e);
-      rc = DFTPAV_E_HIP;
-    }
-  };
-  chk(hipMemcpyAsync(h->d_sur_off, off.data(), sizeof(int) * (S + 1), hipMemcpyHostToDevice, h->stream));
-  chk(hipMemcpyAsync(d_states, states, sizeof(double) * 7 * (size_t)S * n_states, hipMemcpyHostToDevice, h->stream));
-  chk(hipMemcpyAsync(d_op, Mop.data(), sizeof(double) * Mop.size(), hipMemcpyHostToDevice, h->stream));
-  if (rc == DFTPAV_OK)
-    chk(launch_fit(d_states, S, n_states, d_op, h->d_sur_dur, h->d_sur_coef, h->d_sur_total, h->d_sur_start, h->stream));
-  chk(hipStreamSynchronize(h->stream)); // off / Mop live on this stack frame
-  (void)hipFree(d_states);
-  (void)hipFree(d_op);
-  if (rc == DFTPAV_OK) {
-    std::vector<double> dur(np);
-    if (hipMemcpy(dur.data(), h->d_sur_dur, sizeof(double) * np, hipMemcpyDeviceToHost) != hipSuccess) rc = DFTPAV_E_HIP;
-    if (rc == DFTPAV_OK) rc = upload_theta(h, off, dur);
-    if (rc == DFTPAV_OK && h->d_sur_theta) {
-      std::vector<double> coef(12 * (size_t)np);
-      if (hipMemcpy(coef.data(), h->d_sur_coef, sizeof(double) * coef.size(), hipMemcpyDeviceToHost) != hipSuccess) rc = DFTPAV_E_HIP;
-      if (rc == DFTPAV_OK) rc = upload_boxes(h, dur, coef);
-    }
-  }
-  if (rc == DFTPAV_OK) {
-    h->S = S;
-    h->sur_pieces = np;
-  } else {
-    free_surround(h);
-  }
+  const int rc = fit_surround_tables(h, states, S, n_states);
+  if (rc) free_surround(h);
   return rc;
 }
 
@@ -662,411 +338,6 @@ extern "C" int dftpav_get_surround(dftpav_handle *h, int *S, int *n_pieces, int 
   if (total_duration) HIPCHK(h, hipMemcpy(total_duration, h->d_sur_total, sizeof(double) * h->S, hipMemcpyDeviceToHost));
   if (start_time) HIPCHK(h, hipMemcpy(start_time, h->d_sur_start, sizeof(double) * h->S, hipMemcpyDeviceToHost));
   return DFTPAV_OK;
-}
-
-// ------------------------------------------------- Reeds-Shepp shots
-extern "C" int dftpav_reeds_shepp_shots(dftpav_handle *h, const double *from, const double *to, int n, double max_cur,
-                                        double checkl, int max_samples, double vertex_res, double *length, int *type, double *seg,
-                                        double *samples, int *n_samples, int *collides) {
-  if (!h || n < 0 || !(max_cur > 0.0) || !(checkl > 0.0) || max_samples < 1 || max_samples > 4096) return DFTPAV_E_INVALID;
-  if (n == 0) return DFTPAV_OK;
-  if (!from || !to) return DFTPAV_E_INVALID;
-  if (collides && (!h->d_cells || !(vertex_res > 0.0))) return DFTPAV_E_INVALID; // a collision check needs the map
-  HIPCHK(h, hipSetDevice(h->device));
-  if (!h->cev0) HIPCHK(h, hipEventCreate(&h->cev0));
-  if (!h->cev1) HIPCHK(h, hipEventCreate(&h->cev1));
-  std::vector<double> vv; // spacing of the outline points as the reference's running sum (shapes.cc:128)
-  if (collides) {
-    const double longest = std::max(h->params.veh_length, h->params.veh_width) + 1.0;
-    for (double dl = vertex_res; dl < longest; dl += vertex_res) vv.push_back(dl);
-  }
-  if (vv.empty()) vv.push_back(1.0);
-  double *d_from = nullptr, *d_to = nullptr, *d_len = nullptr, *d_seg = nullptr, *d_smp = nullptr, *d_v = nullptr;
-  int *d_type = nullptr, *d_ns = nullptr, *d_col = nullptr;
-  int rc = DFTPAV_OK;
-  auto chk = [&](hipError_t e) {
-    if (e != hipSuccess && rc == DFTPAV_OK) {
-      h->err = hipGetErrorString(e);
-      rc = DFTPAV_E_HIP;
-    }
-  };
-  const size_t nsmp = (size_t)n * max_samples * 3;
-  chk(hipMalloc(&d_from, sizeof(double) * 3 * (size_t)n));
-  chk(hipMalloc(&d_to, sizeof(double) * 3 * (size_t)n));
-  chk(hipMalloc(&d_len, sizeof(double) * (size_t)n));
-  chk(hipMalloc(&d_seg, sizeof(double) * 5 * (size_t)n));
-  chk(hipMalloc(&d_smp, sizeof(double) * nsmp));
-  chk(hipMalloc(&d_v, sizeof(double) * vv.size()));
-  chk(hipMalloc(&d_type, sizeof(int) * (size_t)n));
-  chk(hipMalloc(&d_ns, sizeof(int) * (size_t)n));
-  chk(hipMalloc(&d_col, sizeof(int) * (size_t)n));
-  if (rc == DFTPAV_OK) {
-    chk(hipMemcpyAsync(d_from, from, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    chk(hipMemcpyAsync(d_to, to, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, h->stream));
-    chk(hipMemcpyAsync(d_v, vv.data(), sizeof(double) * vv.size(), hipMemcpyHostToDevice, h->stream));
-    chk(hipEventRecord(h->cev0, h->stream));
-    chk(launch_shots(d_from, d_to, n, 1.0 / max_cur, checkl, max_samples, collides ? h->d_cells : nullptr, h->map.size_x,
-                     h->map.size_y, h->map.resolution, h->map.origin_x, h->map.origin_y, h->params.veh_width, h->params.veh_length,
-                     h->params.veh_d_cr, d_v, (int)vv.size(), d_len, d_type, d_seg, d_smp, d_ns, d_col, h->stream));
-    chk(hipEventRecord(h->cev1, h->stream));
-    if (length) chk(hipMemcpyAsync(length, d_len, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    if (type) chk(hipMemcpyAsync(type, d_type, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    if (seg) chk(hipMemcpyAsync(seg, d_seg, sizeof(double) * 5 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    if (samples) chk(hipMemcpyAsync(samples, d_smp, sizeof(double) * nsmp, hipMemcpyDeviceToHost, h->stream));
-    if (n_samples) chk(hipMemcpyAsync(n_samples, d_ns, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    if (collides) chk(hipMemcpyAsync(collides, d_col, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    chk(hipStreamSynchronize(h->stream));
-    h->ctimed = rc == DFTPAV_OK;
-  }
-  for (void *p : {(void *)d_from, (void *)d_to, (void *)d_len, (void *)d_seg, (void *)d_smp, (void *)d_v, (void *)d_type, (void *)d_ns,
-                  (void *)d_col})
-    if (p) (void)hipFree(p);
-  return rc;
-}
-
-// ------------------------------------------------- hybrid A* front-end search (search.hip)
-extern "C" void dftpav_default_search_params(dftpav_search_params *sp) {
-  std::memset(sp, 0, sizeof(*sp));
-  // config/minco_config.pb.txt:13-59 (map_cfg), :81 (max_frontend_cur); kino_astar.h:167; kino_astar.cpp:426-427
-  sp->map_size_x = 1000.0;
-  sp->map_size_y = 1000.0;
-  sp->map_resl = 0.3;
-  sp->phi_grid_resolution = 0.3;
-  sp->lambda_heu = 5.0;
-  sp->tie_breaker = 1.0 + 1.0 / 10000;
-  sp->allocate_num = 100000;
-  sp->check_num = 5;
-  sp->step_arc = 0.9;
-  sp->max_frontend_cur = 1.0;
-  sp->checkl = 0.2;
-  sp->traj_forward_penalty = 1.0;
-  sp->traj_back_penalty = 2.5;
-  sp->traj_gear_switch_penalty = 15.0;
-  sp->traj_steer_penalty = 0.5;
-  sp->traj_steer_change_penalty = 0.0;
-  sp->veh_width = 1.90 + 0.2;
-  sp->veh_length = 4.88 + 0.2;
-  sp->veh_d_cr = 1.015;
-  sp->wheel_base = 2.85;
-  sp->vertex_res = 0.1;
-  sp->max_iters = 20000;
-  sp->use3d = 1;
-  sp->retry_2d = 1;
-}
-
-// the inputs of one expansion as the reference's loops build them (kino_astar.cpp:143-171): running sums, tabulated here
-static int search_inputs(const dftpav_search_params &sp, double max_steer, int which, double *tab) {
-  const double res = 0.5;
-  int n = 0;
-  auto steers = [&](double arc) {
-    for (double steer = -max_steer; steer <= max_steer + 1e-3; steer += res * max_steer * 1.0) {
-      if (n < kSearchMaxIn) {
-        tab[2 * n] = steer;
-        tab[2 * n + 1] = arc;
-      }
-      if (++n > 4 * kSearchMaxIn) return;
-    }
-  };
-  if (which == 0) {
-    for (double arc = sp.map_resl; arc <= 2 * sp.map_resl + 1e-3 && n <= kSearchMaxIn; arc += sp.map_resl) steers(arc);
-  } else if (which == 1) {
-    for (double arc = -sp.map_resl; arc >= -2 * sp.map_resl - 1e-3 && n <= kSearchMaxIn; arc -= sp.map_resl) steers(arc);
-  } else {
-    for (double arc = -sp.step_arc; arc <= sp.step_arc + 1e-3 && n <= kSearchMaxIn; arc += 0.5 * sp.step_arc) {
-      if (std::fabs(arc) < 1.0e-2) continue;
-      steers(arc);
-    }
-  }
-  return n;
-}
-
-// What a launch of the search needs besides the queries and the outputs: the checked parameters, the tables of the running sums
-// (inputs, outline point spacing, shot sample offsets; `tabs` is their host copy, in_tab | v_tab | l_tab) and the handle's
-// workspace for `slots` queries in flight.  Shared by dftpav_kino_search and dftpav_plan_queries.
-struct SearchSetup {
-  SearchArgs S{};
-  std::vector<double> tabs;
-  size_t n_in_tab = 0, n_vv = 0, n_ll = 0;
-  int slots = 0;
-};
-
-// The workspace of a search of n queries: per query in flight a node pool, the heap (node, key, position), the path list and the
-// hash table (the power of two >= 2 allocate_num); `slots` queries in flight, n or as many as 6 GiB hold -- the queries beyond run
-// in further launches over the same slots.  Each array holds every slot's part and starts on a 256-byte boundary: off[] in the
-// order pool, h_node, h_pos, path_idx, h_key, table, and `bytes` for all of them.
-struct SearchWorkspace {
-  int hcap = 0, slots = 0;
-  size_t per = 0, off[6] = {}, bytes = 0;
-};
-static SearchWorkspace search_workspace(const dftpav_search_params &P, int n) {
-  SearchWorkspace W;
-  W.hcap = 1;
-  while (W.hcap < 2 * P.allocate_num) W.hcap <<= 1;
-  const size_t A = (size_t)P.allocate_num;
-  W.per = A * sizeof(SearchNode) + A * (3 * sizeof(int) + sizeof(double)) + (size_t)W.hcap * sizeof(int) + 256;
-  const size_t budget = ((size_t)6 << 30) - 6 * 256; // 6 GiB at most, the arrays' alignment included
-  W.slots = (int)std::min<size_t>((size_t)n, std::max<size_t>(1, budget / W.per));
-  const size_t S = (size_t)W.slots;
-  const size_t sizes[6] = {A * S * sizeof(SearchNode), A * S * sizeof(int), A * S * sizeof(int), A * S * sizeof(int),
-                           A * S * sizeof(double), (size_t)W.hcap * S * sizeof(int)};
-  for (int k = 0; k < 6; k++) {
-    W.off[k] = W.bytes;
-    W.bytes += (sizes[k] + 255) / 256 * 256;
-  }
-  return W;
-}
-extern "C" int dftpav_debug_search_slots(const dftpav_search_params *sp, int n, int *slots, size_t *bytes_per_query) {
-  if (!sp || n < 1 || sp->allocate_num < 2) return DFTPAV_E_INVALID;
-  const SearchWorkspace W = search_workspace(*sp, n);
-  if (slots) *slots = W.slots;
-  if (bytes_per_query) *bytes_per_query = W.per;
-  return DFTPAV_OK;
-}
-
-static int search_setup(dftpav_handle *h, const dftpav_search_params *sp, int n, SearchSetup &U) {
-  const dftpav_search_params &P = *sp;
-  if (P.allocate_num < 2 || P.check_num < 1 || P.max_iters < 0 || !(P.map_resl > 0.0) || !(P.phi_grid_resolution > 0.0) ||
-      !(P.step_arc > 0.0) || !(P.max_frontend_cur > 0.0) || !(P.checkl > 0.0) || !(P.vertex_res > 0.0) || !(P.wheel_base > 0.0))
-    return DFTPAV_E_INVALID;
-  // the tables of the running sums: inputs, outline point spacing, shot sample offsets
-  const double max_steer = crt::atan(P.wheel_base * P.max_frontend_cur); // kino_astar.cpp:419 (correctly rounded)
-  std::vector<double> in_tab(3 * kSearchMaxIn * 2, 0.0);
-  int n_in[3];
-  for (int w = 0; w < 3; w++) {
-    n_in[w] = search_inputs(P, max_steer, w, in_tab.data() + (size_t)w * kSearchMaxIn * 2);
-    if (n_in[w] > kSearchMaxIn || n_in[w] * P.check_num > kSearchThreads) return DFTPAV_E_UNSUPPORTED;
-  }
-  if (P.check_num > kSearchMaxCheck) return DFTPAV_E_UNSUPPORTED;
-  std::vector<double> vv;
-  const double longest = std::max(P.veh_length, P.veh_width) + 1.0;
-  for (double dl = P.vertex_res; dl < longest; dl += P.vertex_res) vv.push_back(dl);
-  if (vv.empty()) vv.push_back(longest);
-  // a shot is tried within 15 m of the goal (kino_astar.cpp:90); an LSL path, which always exists, is no longer than
-  // d + 2 r + 4 pi r, and the shortest path is no longer than it.  getKinoNode's second shot starts from a pose of the
-  // terminal node's last arc: one step_arc more.  The table holds every offset up to that bound and a margin.
-  const double rho = 1.0 / P.max_frontend_cur;
-  const double bound = 15.0 + std::max(P.step_arc, 2 * P.map_resl) + (2.0 + 4.0 * rs::kPi) * rho;
-  const double n_l_need = bound / P.checkl + 8.0;
-  if (!(n_l_need < (double)kSearchMaxShot)) return DFTPAV_E_UNSUPPORTED;
-  std::vector<double> ll;
-  for (double l = 0.0; (int)ll.size() < (int)n_l_need; l += P.checkl) ll.push_back(l); // kino_astar.cpp:338, 594
-  HIPCHK(h, hipSetDevice(h->device));
-  if (!h->cev0) HIPCHK(h, hipEventCreate(&h->cev0));
-  if (!h->cev1) HIPCHK(h, hipEventCreate(&h->cev1));
-  const SearchWorkspace W = search_workspace(P, n);
-  const int hcap = W.hcap, slots = W.slots;
-  const size_t ws = W.bytes;
-  if (h->search_ws_bytes < ws) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->d_search_ws) (void)hipFree(h->d_search_ws);
-    h->d_search_ws = nullptr;
-    h->search_ws_bytes = 0;
-    const hipError_t e = hipMalloc(&h->d_search_ws, ws);
-    if (e != hipSuccess) { // the handle stays usable: no workspace, and no error left for the next launch's hipGetLastError
-      (void)hipGetLastError();
-      h->d_search_ws = nullptr;
-      h->err = std::string("hipMalloc of the search workspace: ") + hipGetErrorString(e);
-      return DFTPAV_E_HIP;
-    }
-    h->search_ws_bytes = ws;
-  }
-  unsigned char *w = (unsigned char *)h->d_search_ws;
-  SearchArgs &S = U.S;
-  S = SearchArgs{};
-  S.pool = (SearchNode *)(w + W.off[0]);
-  S.h_node = (int *)(w + W.off[1]);
-  S.h_pos = (int *)(w + W.off[2]);
-  S.path_idx = (int *)(w + W.off[3]);
-  S.h_key = (double *)(w + W.off[4]);
-  S.table = (int *)(w + W.off[5]);
-  S.hcap = hcap;
-  S.sp = P;
-  S.cells = h->d_cells;
-  S.size_x = h->map.size_x;
-  S.size_y = h->map.size_y;
-  S.resolution = h->map.resolution;
-  S.origin_x = h->map.origin_x;
-  S.origin_y = h->map.origin_y;
-  S.inv_yaw_res = 1.0 / P.phi_grid_resolution; // kino_astar.cpp:421
-  S.origin_sx = -0.5 * P.map_size_x;
-  S.origin_sy = -0.5 * P.map_size_y;
-  S.half_size_x = P.map_size_x * 0.5;
-  S.half_size_y = P.map_size_y * 0.5;
-  S.rho = rho;
-  for (int k = 0; k < 3; k++) S.n_in[k] = n_in[k];
-  S.n = n;
-  S.n_v = (int)vv.size();
-  S.n_l = (int)ll.size();
-  U.tabs = in_tab;
-  U.tabs.insert(U.tabs.end(), vv.begin(), vv.end());
-  U.tabs.insert(U.tabs.end(), ll.begin(), ll.end());
-  U.n_in_tab = in_tab.size();
-  U.n_vv = vv.size();
-  U.n_ll = ll.size();
-  U.slots = slots;
-  return DFTPAV_OK;
-}
-
-extern "C" int dftpav_kino_search(dftpav_handle *h, const dftpav_search_params *sp, const double *start_states,
-                                  const double *start_ctrl, const double *end_states, int n, const dftpav_search_out *out) {
-  (void)start_ctrl; // kept by search (kino_astar.cpp:54) for getKinoNode's flat states: dftpav_frontend_resample takes it
-  if (!h || !sp || !out || n < 0 || out->max_nodes < 0 || out->max_path < 0) return DFTPAV_E_INVALID;
-  if (!h->d_cells) return DFTPAV_E_INVALID; // no map
-  if (n == 0) return DFTPAV_OK;
-  if (!start_states || !end_states || !out->status || !out->shot_success || !out->used_3d || !out->budget_hit || !out->iters ||
-      !out->nodes_used || !out->n_nodes || !out->path_len || (out->max_nodes > 0 && !out->nodes) || (out->max_path > 0 && !out->paths))
-    return DFTPAV_E_INVALID;
-  SearchSetup U;
-  if (int rc0 = search_setup(h, sp, n, U)) return rc0;
-  SearchArgs &S = U.S;
-  const std::vector<double> &tabs = U.tabs;
-  const int slots = U.slots;
-  int rc = DFTPAV_OK;
-  auto chk = [&](hipError_t e) {
-    if (e != hipSuccess && rc == DFTPAV_OK) {
-      h->err = hipGetErrorString(e);
-      rc = DFTPAV_E_HIP;
-    }
-  };
-  const size_t nn = (size_t)n;
-  double *d_tabs = nullptr, *d_st = nullptr, *d_en = nullptr, *d_nodes = nullptr, *d_paths = nullptr;
-  int *d_ints = nullptr;
-  const size_t ntab = tabs.size();
-  chk(hipMalloc(&d_tabs, sizeof(double) * ntab));
-  chk(hipMalloc(&d_st, sizeof(double) * 4 * nn));
-  chk(hipMalloc(&d_en, sizeof(double) * 4 * nn));
-  chk(hipMalloc(&d_ints, sizeof(int) * 9 * nn));
-  if (out->max_nodes > 0) chk(hipMalloc(&d_nodes, sizeof(double) * 6 * nn * out->max_nodes));
-  if (out->max_path > 0) chk(hipMalloc(&d_paths, sizeof(double) * 3 * nn * out->max_path));
-  if (rc == DFTPAV_OK) {
-    chk(hipMemcpyAsync(d_tabs, tabs.data(), sizeof(double) * ntab, hipMemcpyHostToDevice, h->stream));
-    chk(hipMemcpyAsync(d_st, start_states, sizeof(double) * 4 * nn, hipMemcpyHostToDevice, h->stream));
-    chk(hipMemcpyAsync(d_en, end_states, sizeof(double) * 4 * nn, hipMemcpyHostToDevice, h->stream));
-    // rows past n_nodes / path_len read back as zeros
-    if (d_nodes) chk(hipMemsetAsync(d_nodes, 0, sizeof(double) * 6 * nn * out->max_nodes, h->stream));
-    if (d_paths) chk(hipMemsetAsync(d_paths, 0, sizeof(double) * 3 * nn * out->max_path, h->stream));
-    S.in_tab = d_tabs;
-    S.v_tab = d_tabs + U.n_in_tab;
-    S.l_tab = d_tabs + U.n_in_tab + U.n_vv;
-    S.start = d_st;
-    S.end = d_en;
-    int *const fields[9] = {out->status, out->shot_success, out->used_3d, out->budget_hit, out->iters, out->nodes_used,
-                            out->n_nodes, out->path_len, nullptr};
-    dftpav_search_out &O = S.out;
-    O.max_nodes = out->max_nodes;
-    O.max_path = out->max_path;
-    O.status = d_ints;
-    O.shot_success = d_ints + nn;
-    O.used_3d = d_ints + 2 * nn;
-    O.budget_hit = d_ints + 3 * nn;
-    O.iters = d_ints + 4 * nn;
-    O.nodes_used = d_ints + 5 * nn;
-    O.n_nodes = d_ints + 6 * nn;
-    O.path_len = d_ints + 7 * nn;
-    O.nodes = d_nodes;
-    O.paths = d_paths;
-    chk(hipEventRecord(h->cev0, h->stream));
-    for (int q0 = 0; q0 < n && rc == DFTPAV_OK; q0 += slots) {
-      S.q0 = q0;
-      chk(launch_search(S, std::min(slots, n - q0), h->stream));
-    }
-    chk(hipEventRecord(h->cev1, h->stream));
-    for (int f = 0; f < 8; f++) chk(hipMemcpyAsync(fields[f], d_ints + f * nn, sizeof(int) * nn, hipMemcpyDeviceToHost, h->stream));
-    if (d_nodes) chk(hipMemcpyAsync(out->nodes, d_nodes, sizeof(double) * 6 * nn * out->max_nodes, hipMemcpyDeviceToHost, h->stream));
-    if (d_paths) chk(hipMemcpyAsync(out->paths, d_paths, sizeof(double) * 3 * nn * out->max_path, hipMemcpyDeviceToHost, h->stream));
-    chk(hipStreamSynchronize(h->stream));
-    h->ctimed = rc == DFTPAV_OK;
-  }
-  for (void *p : {(void *)d_tabs, (void *)d_st, (void *)d_en, (void *)d_ints, (void *)d_nodes, (void *)d_paths})
-    if (p) (void)hipFree(p);
-  if (rc == DFTPAV_OK)
-    for (int q = 0; q < n; q++)
-      if (out->status[q] == 0) return DFTPAV_E_UNSUPPORTED; // a shot beyond the sample table (not reached: see the bound)
-  return rc;
-}
-
-extern "C" int dftpav_set_grid_map(dftpav_handle *h, const dftpav_grid_map *map) {
-  if (!h || !map || !map->cells || map->size_x <= 0 || map->size_y <= 0 || !(map->resolution > 0.0)) return DFTPAV_E_INVALID;
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (h->d_cells) (void)hipFree(h->d_cells);
-  if (h->d_bits) (void)hipFree(h->d_bits);
-  if (h->d_dl) (void)hipFree(h->d_dl);
-  h->d_cells = nullptr;
-  h->d_bits = nullptr;
-  h->d_dl = nullptr;
-  const size_t ncell = (size_t)map->size_x * map->size_y;
-  HIPCHK(h, hipMalloc(&h->d_cells, ncell));
-  HIPCHK(h, hipMemcpy(h->d_cells, map->cells, ncell, hipMemcpyHostToDevice));
-  h->map = *map;
-  h->map.cells = nullptr;
-  if (ncell <= (size_t)8 * 40 * 1024) { // <= 40 KB of bits per workgroup: four workgroups per CU
-    std::vector<unsigned> bits((ncell + 31) / 32, 0u);
-    for (size_t i = 0; i < ncell; i++)
-      if (map->cells[i] == 80) bits[i >> 5] |= 1u << (i & 31);
-    HIPCHK(h, hipMalloc(&h->d_bits, sizeof(unsigned) * bits.size()));
-    HIPCHK(h, hipMemcpy(h->d_bits, bits.data(), sizeof(unsigned) * bits.size(), hipMemcpyHostToDevice));
-  }
-  // sample offsets of CheckIfCollisionUsingLine (map_adapter.cpp:119): dl = 0, then dl += checkl; the longest
-  // segment is the far edge of a fully grown rectangle
-  const double checkl = map->resolution / 2.0;
-  const double longest = std::max(h->params.veh_length, h->params.veh_width) + 2.0 * (10.0 + map->resolution) + 1.0;
-  std::vector<double> dl;
-  for (double v = 0.0; v < longest; v += checkl) dl.push_back(v);
-  h->n_dl = (int)dl.size();
-  HIPCHK(h, hipMalloc(&h->d_dl, sizeof(double) * dl.size()));
-  HIPCHK(h, hipMemcpy(h->d_dl, dl.data(), sizeof(double) * dl.size(), hipMemcpyHostToDevice));
-  if (!h->cev0) HIPCHK(h, hipEventCreate(&h->cev0));
-  if (!h->cev1) HIPCHK(h, hipEventCreate(&h->cev1));
-  return DFTPAV_OK;
-}
-
-// uploads the states and runs the corridor kernel into `hpoly` (device, [n][16]) or into a batch's corridor
-static int run_corridor(dftpav_handle *h, const double *states, int n_states, double *d_hpoly, double *batch_cor, int Npts,
-                        int NptsPad, int replicate) {
-  double *d_states = nullptr;
-  HIPCHK(h, hipMalloc(&d_states, sizeof(double) * 3 * (size_t)n_states));
-  int rc = DFTPAV_OK;
-  auto chk = [&](hipError_t e) {
-    if (e != hipSuccess && rc == DFTPAV_OK) {
-      h->err = hipGetErrorString(e);
-      rc = DFTPAV_E_HIP;
-    }
-  };
-  chk(hipMemcpyAsync(d_states, states, sizeof(double) * 3 * (size_t)n_states, hipMemcpyHostToDevice, h->stream));
-  chk(hipEventRecord(h->cev0, h->stream));
-  if (rc == DFTPAV_OK)
-    chk(launch_corridor(h->d_cells, h->d_bits, h->map.size_x, h->map.size_y, h->map.resolution, h->map.origin_x, h->map.origin_y, d_states,
-                        n_states, h->params.veh_width, h->params.veh_length, h->params.veh_d_cr, h->d_dl, h->n_dl, d_hpoly,
-                        batch_cor, Npts, NptsPad, replicate, h->stream));
-  chk(hipEventRecord(h->cev1, h->stream));
-  chk(hipStreamSynchronize(h->stream));
-  h->ctimed = rc == DFTPAV_OK;
-  (void)hipFree(d_states);
-  return rc;
-}
-
-extern "C" int dftpav_corridor_last_ms(dftpav_handle *h, float *ms) {
-  if (!h || !ms || !h->ctimed) return DFTPAV_E_INVALID;
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipEventElapsedTime(ms, h->cev0, h->cev1));
-  return DFTPAV_OK;
-}
-
-extern "C" int dftpav_corridor_rectangles(dftpav_handle *h, const double *states, int n_states, double *hpoly) {
-  if (!h || !states || !hpoly || n_states < 0) return DFTPAV_E_INVALID;
-  if (!h->d_cells) return DFTPAV_E_INVALID; // no map
-  if (n_states == 0) return DFTPAV_OK;
-  HIPCHK(h, hipSetDevice(h->device));
-  double *d_hpoly = nullptr;
-  HIPCHK(h, hipMalloc(&d_hpoly, sizeof(double) * 16 * (size_t)n_states));
-  int rc = run_corridor(h, states, n_states, d_hpoly, nullptr, 1, 1, 1);
-  if (rc == DFTPAV_OK && hipMemcpy(hpoly, d_hpoly, sizeof(double) * 16 * (size_t)n_states, hipMemcpyDeviceToHost) != hipSuccess) {
-    h->err = "hipMemcpy";
-    rc = DFTPAV_E_HIP;
-  }
-  (void)hipFree(d_hpoly);
-  return rc;
 }
 
 extern "C" int dftpav_set_surround(dftpav_handle *h, const dftpav_surround *s) {
@@ -1143,7 +414,7 @@ extern "C" int dftpav_debug_minco_operator(int N, double *out) {
 }
 
 // -------------------------------------------------------------------- batch
-static void fill_dev_params(const dftpav_params &p, DevParams &P) {
+void dftpav::fill_dev_params(const dftpav_params &p, DevParams &P) {
   P.wei_obs = p.wei_obs;
   P.wei_surround = p.wei_surround;
   P.wei_feas = p.wei_feas;
@@ -1186,7 +457,7 @@ extern "C" void dftpav_batch_destroy(dftpav_batch *b) {
                   b->d_x_in, b->d_x_out, b->d_f, b->d_g, b->d_status, b->d_success, b->d_iters, b->d_evals,
                   b->d_hist, b->d_ticks, b->d_prof, b->d_dev, b->d_coef, b->d_dt, b->d_records,
                   b->d_queue, b->d_stragglers, b->d_stragglers2, b->d_sflag, b->d_iota, b->d_qctl, b->d_state, b->d_dev2,
-                  b->d_f_eval, b->d_trace, b->d_cor_raw, b->d_ref_tab, b->d_ref_scratch, b->d_cor_t, b->d_rect_flag, b->pc.d_poses, b->pc.d_t, b->pc.d_v, b->pc.d_rd, b->pc.d_col, b->pc.d_first,
+                  b->d_f_eval, b->d_trace, b->d_cor_raw, b->d_ref_tab, b->d_ref_scratch, b->d_cor_t, b->d_rect_flag, b->pc.d_poses, b->pc.d_tab, b->pc.d_rd, b->pc.d_col, b->pc.d_first,
                   b->pc.d_valid};
   {
     auto &v = b->h->batches;
@@ -1211,7 +482,7 @@ extern "C" void dftpav_batch_destroy(dftpav_batch *b) {
 
 // the kernels' view of a layout: offsets of the segments' pieces, waypoints, right-hand-side rows and constraint points, and of
 // tau | gear xy | gear angle inside x (traj_optimizer.cpp:96-115)
-static void fill_dev_layout(const dftpav_layout &layout, int K, int Kd, DevLayout &L) {
+void dftpav::fill_dev_layout(const dftpav_layout &layout, int K, int Kd, DevLayout &L) {
   L = DevLayout{};
   L.M = layout.M;
   L.H = layout.H;
@@ -1607,26 +878,6 @@ extern "C" int dftpav_batch_upload(dftpav_batch *b, const dftpav_batch_data *d) 
   return DFTPAV_OK;
 }
 
-extern "C" int dftpav_batch_corridor_from_hypotheses(dftpav_batch *b, const double *states, int n_restarts) {
-  if (!b || !states || n_restarts < 1 || b->B % n_restarts) return DFTPAV_E_INVALID;
-  b->pending = false; // as dftpav_batch_upload
-  dftpav_handle *h = b->h;
-  if (!h->d_cells) return DFTPAV_E_INVALID;       // no map
-  if (b->L.H != 4) return DFTPAV_E_UNSUPPORTED;   // rectangles
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  int rc = run_corridor(h, states, (b->B / n_restarts) * b->L.Npts, nullptr, b->d_corridor, b->L.Npts, b->NptsPad, n_restarts);
-  if (rc == DFTPAV_OK) {
-    b->have_corridor = true;
-    b->cor_t_dirty = true;
-    b->cor_rect = false; // (not asked: see dftpav_batch::cor_rect)
-  }
-  return rc;
-}
-extern "C" int dftpav_batch_corridor_from_states(dftpav_batch *b, const double *states) {
-  return dftpav_batch_corridor_from_hypotheses(b, states, 1);
-}
-
 extern "C" int dftpav_batch_get_x0(dftpav_batch *b, double *x0) {
   if (!b || !x0 || !b->uploaded) return DFTPAV_E_INVALID;
   std::memcpy(x0, b->x0_host.data(), sizeof(double) * b->x0_host.size());
@@ -1728,7 +979,7 @@ static DevBatch make_dev(dftpav_batch *b) {
 }
 
 // refreshes the device copy of the launch descriptor when something it captures changed
-static int sync_dev(dftpav_batch *b, DevBatch &D) {
+int dftpav::sync_dev(dftpav_batch *b, DevBatch &D) {
   dftpav_handle *h = b->h;
   // the kernel numbers (constraint point, obstacle) pairs with 16 bits and keeps a 16-bit mask of obstacles per point
   if (h->S > 16 || (long long)b->L.Npts * h->S > 65535 || h->sur_pieces > 512) {
@@ -1870,7 +1121,7 @@ extern "C" int dftpav_debug_batch_corridor_layout(const dftpav_batch *b) {
   if (!b || b->order != DFTPAV_ORDER_REFERENCE || b->ref_plan.kind < kRefQuad || b->cor_t_dirty) return -1;
   return b->cor_t_rect ? 1 : 0;
 }
-static hipError_t launch_for(dftpav_batch *b, const DevBatch &D, int mode) {
+hipError_t dftpav::launch_for(dftpav_batch *b, const DevBatch &D, int mode) {
   if (b->order == DFTPAV_ORDER_REFERENCE) return launch_ref(b, D, mode, 0);
   return launch_solver(D, b->d_dev, mode, b->threads, b->B, SchedArgs{0, 0, 0, nullptr}, b->h->stream);
 }
@@ -1971,37 +1222,27 @@ extern "C" int dftpav_debug_reference_tables_packed(int N, double *out, int *n_d
 }
 
 // the ring, the flags and the state records of a scheduled solve, for a batch whose device-order plan did not need them
-static hipError_t ensure_ring_buffers(dftpav_batch *b) {
-  if (b->d_queue && b->d_sflag && b->d_iota && b->d_qctl && b->d_state) return hipSuccess;
+static int ensure_ring_buffers(dftpav_batch *b) {
+  if (b->d_queue && b->d_sflag && b->d_iota && b->d_qctl && b->d_state) return DFTPAV_OK;
+  dftpav_handle *h = b->h;
   const int B = b->B;
   const size_t stride = (size_t)solver_state_doubles(b->L, b->P);
   int *q = nullptr, *fl = nullptr, *io = nullptr;
   unsigned *ctl = nullptr;
   double *st = nullptr;
-  hipError_t e = hipSuccess;
-  auto chk = [&](hipError_t r) {
-    if (e == hipSuccess && r != hipSuccess) e = r;
-  };
   const int qcap = 2 * B;
-  chk(hipMalloc(&q, sizeof(int) * (size_t)qcap));
-  chk(hipMalloc(&fl, sizeof(int) * (size_t)B));
-  chk(hipMalloc(&io, sizeof(int) * (size_t)B));
-  chk(hipMalloc(&ctl, sizeof(unsigned) * 16));
-  chk(hipMalloc(&st, sizeof(double) * stride * (size_t)B));
-  if (e == hipSuccess) {
-    const unsigned ctl0[8] = {0u, (unsigned)B, (unsigned)B, (unsigned)B, 0u, 0u, 0u, 0u};
-    chk(hipMemcpy(ctl + 8, ctl0, sizeof(ctl0), hipMemcpyHostToDevice));
-    std::vector<int> iota(B);
-    for (int i = 0; i < B; i++) iota[i] = i;
-    chk(hipMemcpy(io, iota.data(), sizeof(int) * (size_t)B, hipMemcpyHostToDevice));
-  }
-  if (e != hipSuccess) {
-    for (void *p : {(void *)q, (void *)fl, (void *)io, (void *)ctl, (void *)st})
-      if (p) (void)hipFree(p);
-    (void)hipGetLastError();
-    return e;
-  }
-  // (a batch either has all of them -- its device-order plan is scheduled -- or none)
+  DevScratch tmp(h); // (a batch either has all of them -- its device-order plan is scheduled -- or none)
+  HIPCHK(h, tmp.alloc(q, (size_t)qcap));
+  HIPCHK(h, tmp.alloc(fl, (size_t)B));
+  HIPCHK(h, tmp.alloc(io, (size_t)B));
+  HIPCHK(h, tmp.alloc(ctl, 16));
+  HIPCHK(h, tmp.alloc(st, stride * (size_t)B));
+  const unsigned ctl0[8] = {0u, (unsigned)B, (unsigned)B, (unsigned)B, 0u, 0u, 0u, 0u};
+  HIPCHK(h, hipMemcpy(ctl + 8, ctl0, sizeof(ctl0), hipMemcpyHostToDevice));
+  std::vector<int> iota(B);
+  for (int i = 0; i < B; i++) iota[i] = i;
+  HIPCHK(h, hipMemcpy(io, iota.data(), sizeof(int) * (size_t)B, hipMemcpyHostToDevice));
+  tmp.keep();
   b->d_queue = q;
   b->d_sflag = fl;
   b->d_iota = io;
@@ -2009,7 +1250,7 @@ static hipError_t ensure_ring_buffers(dftpav_batch *b) {
   b->d_state = st;
   b->qcap = qcap;
   b->dev_version = -1; // the device descriptor carries these pointers
-  return hipSuccess;
+  return DFTPAV_OK;
 }
 
 extern "C" int dftpav_batch_set_order(dftpav_batch *b, int order) {
@@ -2032,7 +1273,8 @@ extern "C" int dftpav_batch_set_order(dftpav_batch *b, int order) {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, h->device) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
     const RefPlan pl = reference_order_plan(b->L, b->P, h->S, b->B, n_cu, b->residency == 2, ref_options_from_env());
-    if (pl.kind != kRefTeam && ensure_ring_buffers(b) != hipSuccess) {
+    if (pl.kind != kRefTeam && ensure_ring_buffers(b) != DFTPAV_OK) {
+      (void)hipGetLastError();
       h->err = "reference order: no device memory for the ring of this batch";
       return DFTPAV_E_HIP;
     }
@@ -2127,7 +1369,7 @@ static int launch_stragglers(dftpav_batch *b, const DevBatch &D, int source) {
 }
 
 // a chained solve left the stragglers of `b` suspended: finish them now (no-op otherwise)
-static int finish_pending(dftpav_batch *b) {
+int dftpav::finish_pending(dftpav_batch *b) {
   if (!b->pending) return DFTPAV_OK;
   dftpav_handle *h = b->h;
   HIPCHK(h, hipSetDevice(h->device));
@@ -2148,7 +1390,7 @@ static bool chain_compatible(const dftpav_batch *a, const dftpav_batch *b) {
          a->t_now == b->t_now && a->epis == b->epis;
 }
 
-static int solve_impl(dftpav_batch *b, dftpav_batch *prev, bool chained) {
+int dftpav::solve_impl(dftpav_batch *b, dftpav_batch *prev, bool chained) {
   if (!b || !b->uploaded || !b->have_corridor || prev == b) return DFTPAV_E_INVALID;
   dftpav_handle *h = b->h;
   HIPCHK(h, hipSetDevice(h->device));
@@ -2283,183 +1525,6 @@ extern "C" int dftpav_batch_results(dftpav_batch *b, double *x, double *final_co
   return DFTPAV_OK;
 }
 
-// ------------------------------------------------------------------ RCCL behind the C-ABI
-// The one collective of the path: an all-gather of 16-byte result records over xGMI.  RCCL is loaded at the first use
-// (dlopen by its soname: inside a process that already holds an RCCL -- PyTorch ships one -- this is that same copy, so a
-// process never runs two), which keeps the library loadable where no RCCL is installed: only these entry points fail there.
-namespace {
-struct RcclUniqueId {
-  char internal[DFTPAV_UNIQUE_ID_BYTES];
-};
-struct RcclApi {
-  void *lib = nullptr;
-  int (*GetUniqueId)(RcclUniqueId *) = nullptr;
-  int (*CommInitRank)(void **, int, RcclUniqueId, int) = nullptr;
-  int (*CommDestroy)(void *) = nullptr;
-  int (*AllGather)(const void *, void *, size_t, int, void *, hipStream_t) = nullptr;
-  const char *(*GetErrorString)(int) = nullptr;
-  bool ok = false;
-};
-RcclApi &rccl() {
-  static RcclApi api;
-  static std::once_flag once;
-  std::call_once(once, [] {
-    for (const char *name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
-      api.lib = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
-      if (api.lib) break;
-    }
-    if (!api.lib) return;
-    api.GetUniqueId = reinterpret_cast<int (*)(RcclUniqueId *)>(dlsym(api.lib, "ncclGetUniqueId"));
-    api.CommInitRank = reinterpret_cast<int (*)(void **, int, RcclUniqueId, int)>(dlsym(api.lib, "ncclCommInitRank"));
-    api.CommDestroy = reinterpret_cast<int (*)(void *)>(dlsym(api.lib, "ncclCommDestroy"));
-    api.AllGather = reinterpret_cast<int (*)(const void *, void *, size_t, int, void *, hipStream_t)>(dlsym(api.lib, "ncclAllGather"));
-    api.GetErrorString = reinterpret_cast<const char *(*)(int)>(dlsym(api.lib, "ncclGetErrorString"));
-    api.ok = api.GetUniqueId && api.CommInitRank && api.CommDestroy && api.AllGather;
-  });
-  return api;
-}
-constexpr int kNcclUint8 = 1; // ncclUint8 == ncclChar + 1 (rccl.h)
-} // namespace
-#define RCCLCHK(h, call)                                                                                        \
-  do {                                                                                                          \
-    int e_ = (call);                                                                                            \
-    if (e_ != 0) {                                                                                              \
-      (h)->err = std::string(#call) + ": " + (rccl().GetErrorString ? rccl().GetErrorString(e_) : "rccl error"); \
-      return DFTPAV_E_COMM;                                                                                     \
-    }                                                                                                           \
-  } while (0)
-
-extern "C" int dftpav_comm_unique_id(void *id) {
-  if (!id) return DFTPAV_E_INVALID;
-  if (!rccl().ok) return DFTPAV_E_COMM;
-  RcclUniqueId u;
-  if (rccl().GetUniqueId(&u) != 0) return DFTPAV_E_COMM;
-  std::memcpy(id, u.internal, DFTPAV_UNIQUE_ID_BYTES);
-  return DFTPAV_OK;
-}
-// Is RCCL loadable here?  (dlopen + dlsym only: no bootstrap root is started, unlike dftpav_comm_unique_id.)
-extern "C" int dftpav_comm_available(void) { return rccl().ok ? 1 : 0; }
-// lets go of h's reference to its communicator; g_comm_mu is held by the caller, h's stream is drained
-static void comm_release_locked(dftpav_handle *h) {
-  if (h->comm_ref && h->comm_ref->holders.fetch_sub(1) == 1) { // the last holder (every holder has drained its own stream)
-    {
-      std::lock_guard<std::mutex> lk(h->comm_ref->mu);
-      (void)rccl().CommDestroy(h->comm_ref->comm);
-    }
-    delete h->comm_ref;
-  }
-  h->comm = nullptr;
-  h->comm_ref = nullptr;
-}
-extern "C" int dftpav_comm_destroy(dftpav_handle *h) {
-  if (!h) return DFTPAV_E_INVALID;
-  if (h->comm) {
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    std::lock_guard<std::mutex> reg(g_comm_mu);
-    comm_release_locked(h);
-  }
-  if (h->d_comm_send) (void)hipFree(h->d_comm_send);
-  h->d_comm_send = nullptr;
-  h->comm_send_bytes = 0;
-  h->comm_ranks = 0;
-  return DFTPAV_OK;
-}
-extern "C" int dftpav_comm_create(dftpav_handle *h, int nranks, int rank, const void *unique_id) {
-  if (!h || nranks < 1 || rank < 0 || rank >= nranks || !unique_id) return DFTPAV_E_INVALID;
-  if (!rccl().ok) {
-    h->err = "RCCL (librccl.so.1) is not loadable";
-    return DFTPAV_E_COMM;
-  }
-  if (int rc = dftpav_comm_destroy(h)) return rc;
-  HIPCHK(h, hipSetDevice(h->device));
-  RcclUniqueId u;
-  std::memcpy(u.internal, unique_id, DFTPAV_UNIQUE_ID_BYTES);
-  RCCLCHK(h, rccl().CommInitRank(&h->comm, nranks, u, rank));
-  {
-    std::lock_guard<std::mutex> reg(g_comm_mu);
-    h->comm_ref = new CommShared;
-    h->comm_ref->comm = h->comm;
-    h->comm_ref->holders.store(1);
-  }
-  h->comm_ranks = nranks;
-  h->comm_rank = rank;
-  return DFTPAV_OK;
-}
-// Several handles (= HIP streams) of one process on one communicator: a host that keeps k batches in flight on k handles sets
-// ONE communicator up per rank instead of k (k ncclCommInitRank rendezvous and k sets of RCCL buffers per rank otherwise).
-// RCCL orders successive operations of a communicator among the streams they are enqueued on; what the host owes it is the
-// same order of collectives on every rank -- which a round-robin over the handles is.
-extern "C" int dftpav_comm_share(dftpav_handle *h, dftpav_handle *owner) {
-  if (!h || !owner || h == owner) return DFTPAV_E_INVALID;
-  // h's stream is drained BEFORE the registry lock is taken (its collectives may still be in flight on the communicator it gives up)
-  if (h->comm) {
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
-  }
-  std::lock_guard<std::mutex> reg(g_comm_mu);
-  if (owner->comm && owner->comm_ref && owner->comm_ref == h->comm_ref) return DFTPAV_OK; // already the same communicator
-  // the owner is checked and the new reference taken FIRST: a share that fails leaves h as it was (round 5 released h's own
-  // communicator before the check -- a failed share could then destroy it on this rank alone and hang the other ranks)
-  if (!owner->comm || !owner->comm_ref || owner->device != h->device) { // read under the lock: the owner may be letting go
-    h->err = "dftpav_comm_share: the other handle needs a communicator (dftpav_comm_create, or shared itself) on the same device";
-    return DFTPAV_E_INVALID;
-  }
-  owner->comm_ref->holders.fetch_add(1);
-  if (h->comm) comm_release_locked(h); // ... only then the old one goes
-  if (h->d_comm_send) (void)hipFree(h->d_comm_send); // (sized for the communicator it belonged to)
-  h->d_comm_send = nullptr;
-  h->comm_send_bytes = 0;
-  h->comm = owner->comm;
-  h->comm_ref = owner->comm_ref;
-  h->comm_ranks = owner->comm_ranks;
-  h->comm_rank = owner->comm_rank;
-  return DFTPAV_OK;
-}
-extern "C" int dftpav_comm_layout(int global_B, int nranks, int rank, int *first, int *count, int *block) {
-  if (global_B < 1 || nranks < 1 || rank < 0 || rank >= nranks) return DFTPAV_E_INVALID;
-  const long long lo = (long long)global_B * rank / nranks, hi = (long long)global_B * (rank + 1) / nranks;
-  if (first) *first = (int)lo;
-  if (count) *count = (int)(hi - lo);
-  if (block) *block = (global_B + nranks - 1) / nranks; // the largest shard: every rank's block in the gathered buffer
-  return DFTPAV_OK;
-}
-extern "C" int dftpav_batch_allgather_results(dftpav_batch *b, int global_B, void *all_records) {
-  if (!b || !all_records || !b->uploaded || !b->solved) return DFTPAV_E_INVALID;
-  dftpav_handle *h = b->h;
-  if (!h->comm) {
-    h->err = "dftpav_comm_create first";
-    return DFTPAV_E_INVALID;
-  }
-  int first = 0, count = 0, block = 0;
-  if (int rc = dftpav_comm_layout(global_B, h->comm_ranks, h->comm_rank, &first, &count, &block)) return rc;
-  if (count != b->B) {
-    h->err = "this batch is not the shard dftpav_comm_layout assigns to the rank";
-    return DFTPAV_E_INVALID;
-  }
-  HIPCHK(h, hipSetDevice(h->device));
-  if (int rc = finish_pending(b)) return rc;
-  const size_t bytes = (size_t)block * 16;
-  if (block <= b->B + 1) {
-    // the send buffer IS the batch's record array (its epilogue-written records, one zero record of padding behind them for
-    // the ranks whose shard is one short of the block): nothing of ours runs between the solve and the collective
-    std::lock_guard<std::mutex> lk(h->comm_ref->mu);
-    RCCLCHK(h, rccl().AllGather(b->d_records, all_records, bytes, kNcclUint8, h->comm, h->stream));
-    return DFTPAV_OK;
-  }
-  if (h->comm_send_bytes < bytes) {
-    if (h->d_comm_send) (void)hipFree(h->d_comm_send);
-    h->d_comm_send = nullptr;
-    HIPCHK(h, hipMalloc(&h->d_comm_send, bytes));
-    h->comm_send_bytes = bytes;
-  }
-  HIPCHK(h, hipMemsetAsync(h->d_comm_send, 0, bytes, h->stream));
-  HIPCHK(h, hipMemcpyAsync(h->d_comm_send, b->d_records, (size_t)16 * count, hipMemcpyDeviceToDevice, h->stream));
-  std::lock_guard<std::mutex> lk(h->comm_ref->mu);
-  RCCLCHK(h, rccl().AllGather(h->d_comm_send, all_records, bytes, kNcclUint8, h->comm, h->stream));
-  return DFTPAV_OK;
-}
-
 extern "C" int dftpav_batch_pack_results(dftpav_batch *b, void *device_dst) {
   if (!b || !device_dst || !b->solved) return DFTPAV_E_INVALID;
   dftpav_handle *h = b->h;
@@ -2487,1561 +1552,5 @@ extern "C" int dftpav_batch_records(dftpav_batch *b, void *host_dst) {
   }
   HIPCHK(h, hipMemcpyAsync(host_dst, b->d_records, (size_t)16 * b->B, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  return DFTPAV_OK;
-}
-
-// test hook: the steps after the solve (dftpav_batch_validate, dftpav_batch_sample_states) on GIVEN coefficients [B][Ntot][6][2] and piece
-// durations [B][M] instead of a solution's -- so that the kernels can be held against committed vectors of arbitrary trajectories
-// (tests/golden/steps.npz).  Cleared by the next upload or solve.
-extern "C" int dftpav_debug_batch_set_coeffs(dftpav_batch *b, const double *coeffs, const double *piece_dt) {
-  if (!b || !coeffs || !piece_dt) return DFTPAV_E_INVALID;
-  dftpav_handle *h = b->h;
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  HIPCHK(h, hipMemcpy(b->d_coef, coeffs, sizeof(double) * (size_t)b->B * 12 * b->L.Ntot, hipMemcpyHostToDevice));
-  HIPCHK(h, hipMemcpy(b->d_dt, piece_dt, sizeof(double) * (size_t)b->B * b->L.M, hipMemcpyHostToDevice));
-  b->coef_override = true;
-  b->uploaded = true;
-  b->solved = true;
-  return DFTPAV_OK;
-}
-extern "C" int dftpav_batch_coeffs(dftpav_batch *b, double *coeffs, double *piece_dt) {
-  if (!b || !b->uploaded || !b->solved) return DFTPAV_E_INVALID; // the coefficients are those of the solution x
-  dftpav_handle *h = b->h;
-  HIPCHK(h, hipSetDevice(h->device));
-  if (int rc = finish_pending(b)) return rc;
-  DevBatch D;
-  if (int rc = sync_dev(b, D)) return rc;
-  HIPCHK(h, launch_for(b, D, kModeCoeffs));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (coeffs)
-    HIPCHK(h, hipMemcpy(coeffs, b->d_coef, sizeof(double) * (size_t)b->B * 12 * b->L.Ntot, hipMemcpyDeviceToHost));
-  if (piece_dt) HIPCHK(h, hipMemcpy(piece_dt, b->d_dt, sizeof(double) * (size_t)b->B * b->L.M, hipMemcpyDeviceToHost));
-  return DFTPAV_OK;
-}
-
-extern "C" int dftpav_batch_validate(dftpav_batch *b, double sample_dt, double vertex_res, int *collision, int *first_sample) {
-  if (!b || !b->uploaded || !b->solved || !(sample_dt > 0.0) || !(vertex_res > 0.0)) return DFTPAV_E_INVALID; // nothing solved yet
-  dftpav_handle *h = b->h;
-  if (!h->d_cells) return DFTPAV_E_INVALID; // no map
-  HIPCHK(h, hipSetDevice(h->device));
-  // coefficients and piece durations of the solutions, regenerated on the device from x (as dftpav_batch_coeffs)
-  if (int rc = finish_pending(b)) return rc;
-  DevBatch D;
-  if (int rc = sync_dev(b, D)) return rc;
-  if (!b->coef_override) HIPCHK(h, launch_for(b, D, kModeCoeffs));
-  // the two running sums of the reference, tabulated: sample times (traj_server_ros.cpp:387) and the spacing of the
-  // outline points (shapes.cc:128)
-  std::vector<double> tt, vv;
-  {
-    double t = 0.0;
-    for (int k = 0; k < 4096; k++, t += sample_dt) tt.push_back(t);
-    const double longest = std::max(h->params.veh_length, h->params.veh_width) + 1.0;
-    for (double dl = vertex_res; dl < longest; dl += vertex_res) vv.push_back(dl);
-    if (vv.empty()) vv.push_back(vertex_res);
-  }
-  double *d_t = nullptr, *d_v = nullptr;
-  int *d_col = nullptr, *d_first = nullptr;
-  int rc = DFTPAV_OK;
-  auto chk = [&](hipError_t e) {
-    if (e != hipSuccess && rc == DFTPAV_OK) {
-      h->err = hipGetErrorString(e);
-      rc = DFTPAV_E_HIP;
-    }
-  };
-  chk(hipMalloc(&d_t, sizeof(double) * tt.size()));
-  chk(hipMalloc(&d_v, sizeof(double) * vv.size()));
-  chk(hipMalloc(&d_col, sizeof(int) * (size_t)b->B));
-  chk(hipMalloc(&d_first, sizeof(int) * (size_t)b->B));
-  if (rc == DFTPAV_OK) {
-    chk(hipMemcpyAsync(d_t, tt.data(), sizeof(double) * tt.size(), hipMemcpyHostToDevice, h->stream));
-    chk(hipMemcpyAsync(d_v, vv.data(), sizeof(double) * vv.size(), hipMemcpyHostToDevice, h->stream));
-    chk(hipEventRecord(h->cev0, h->stream));
-    chk(launch_validate(h->d_cells, h->map.size_x, h->map.size_y, h->map.resolution, h->map.origin_x, h->map.origin_y, b->d_coef,
-                        b->d_dt, b->L, b->B, h->params.veh_width, h->params.veh_length, h->params.veh_d_cr, d_t, (int)tt.size(),
-                        sample_dt, d_v, (int)vv.size(), d_col, d_first, h->stream));
-    chk(hipEventRecord(h->cev1, h->stream));
-    if (collision) chk(hipMemcpyAsync(collision, d_col, sizeof(int) * (size_t)b->B, hipMemcpyDeviceToHost, h->stream));
-    if (first_sample) chk(hipMemcpyAsync(first_sample, d_first, sizeof(int) * (size_t)b->B, hipMemcpyDeviceToHost, h->stream));
-    chk(hipStreamSynchronize(h->stream));
-    h->ctimed = rc == DFTPAV_OK;
-  }
-  for (void *p : {(void *)d_t, (void *)d_v, (void *)d_col, (void *)d_first})
-    if (p) (void)hipFree(p);
-  return rc;
-}
-
-extern "C" int dftpav_batch_sample_states(dftpav_batch *b, double t0, double sample_dt, int n_samples, int filter_singularity,
-                                          double *states, int *n_valid) {
-  if (!b || !b->uploaded || !b->solved || !(sample_dt > 0.0) || n_samples <= 0 || !states) return DFTPAV_E_INVALID;
-  dftpav_handle *h = b->h;
-  HIPCHK(h, hipSetDevice(h->device));
-  if (int rc = finish_pending(b)) return rc;
-  DevBatch D;
-  if (int rc = sync_dev(b, D)) return rc;
-  if (!b->coef_override) HIPCHK(h, launch_for(b, D, kModeCoeffs));
-  double *d_states = nullptr;
-  int *d_valid = nullptr;
-  int rc = DFTPAV_OK;
-  auto chk = [&](hipError_t e) {
-    if (e != hipSuccess && rc == DFTPAV_OK) {
-      h->err = hipGetErrorString(e);
-      rc = DFTPAV_E_HIP;
-    }
-  };
-  if (!h->cev0) chk(hipEventCreate(&h->cev0));
-  if (!h->cev1) chk(hipEventCreate(&h->cev1));
-  const size_t nst = (size_t)b->B * (size_t)n_samples * 8;
-  chk(hipMalloc(&d_states, sizeof(double) * nst));
-  chk(hipMalloc(&d_valid, sizeof(int) * (size_t)b->B));
-  if (rc == DFTPAV_OK) {
-    chk(hipEventRecord(h->cev0, h->stream));
-    chk(launch_states(b->d_coef, b->d_dt, b->L, b->B, h->params.veh_wheel_base, t0, sample_dt, n_samples, filter_singularity != 0,
-                      d_states, d_valid, h->stream));
-    chk(hipEventRecord(h->cev1, h->stream));
-    chk(hipMemcpyAsync(states, d_states, sizeof(double) * nst, hipMemcpyDeviceToHost, h->stream));
-    if (n_valid) chk(hipMemcpyAsync(n_valid, d_valid, sizeof(int) * (size_t)b->B, hipMemcpyDeviceToHost, h->stream));
-    chk(hipStreamSynchronize(h->stream));
-    h->ctimed = rc == DFTPAV_OK;
-  }
-  if (d_states) (void)hipFree(d_states);
-  if (d_valid) (void)hipFree(d_valid);
-  return rc;
-}
-
-// ------------------------------------------------- one planning cycle, stream-ordered
-// TrajPlanner::RunMINCOParking from getRectangleConst on (traj_manager.cpp:551-626) and the consumers of its result
-// (CheckReplan's collision re-check, traj_server_ros.cpp:385-397; the state playback, :244-259,335-356) as ONE enqueue:
-// upload of the boundary states / waypoints / durations, then on the handle's stream and without the host in between
-//   constraint-point poses -> rectangles of every hypothesis (corridor.hip) -> solve (solver.hip) -> coefficients of the
-//   solutions -> collision re-check (validate.hip) -> state read-out (states.hip).
-// dftpav_plan_cycle returns when everything is enqueued; dftpav_plan_cycle_fetch waits and copies the results out.
-static int grow(dftpav_handle *h, void **p, size_t *have, size_t want, size_t elem) {
-  if (*have >= want && *p) return DFTPAV_OK;
-  if (*p) HIPCHK(h, hipFree(*p));
-  *p = nullptr;
-  HIPCHK(h, hipMalloc(p, elem * want));
-  *have = want;
-  return DFTPAV_OK;
-}
-
-extern "C" int dftpav_plan_cycle(dftpav_batch *b, const dftpav_batch_data *d, const double *states, int n_restarts, double check_dt,
-                                 double vertex_res, double t0, double state_dt, int n_samples, int filter_singularity) {
-  if (!b || !d || !states || n_restarts < 1 || b->B % n_restarts || !(check_dt > 0.0) || !(vertex_res > 0.0) || !(state_dt > 0.0) ||
-      n_samples < 1)
-    return DFTPAV_E_INVALID;
-  dftpav_handle *h = b->h;
-  if (!h->d_cells) return DFTPAV_E_INVALID;     // no map
-  if (b->L.H != 4) return DFTPAV_E_UNSUPPORTED; // rectangles
-  dftpav_batch_data dd = *d;
-  dd.corridor = nullptr; // the half-planes come from the map
-  if (int rc = dftpav_batch_upload(b, &dd)) return rc; // waits for the previous cycle of this handle, then copies the small inputs
-  HIPCHK(h, hipSetDevice(h->device));
-  auto &pc = b->pc;
-  const int B = b->B, n_hyp = B / n_restarts;
-  const size_t n_poses = (size_t)n_hyp * b->L.Npts;
-  pc.poses.assign(states, states + 3 * n_poses);
-  {
-    void *p = pc.d_poses;
-    if (int rc = grow(h, &p, &pc.n_poses, 3 * n_poses, sizeof(double))) return rc;
-    pc.d_poses = (double *)p;
-  }
-  if (!h->cev0) HIPCHK(h, hipEventCreate(&h->cev0));
-  if (!h->cev1) HIPCHK(h, hipEventCreate(&h->cev1));
-  HIPCHK(h, hipMemcpyAsync(pc.d_poses, pc.poses.data(), sizeof(double) * 3 * n_poses, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, launch_corridor(h->d_cells, h->d_bits, h->map.size_x, h->map.size_y, h->map.resolution, h->map.origin_x, h->map.origin_y,
-                            pc.d_poses, (int)n_poses, h->params.veh_width, h->params.veh_length, h->params.veh_d_cr, h->d_dl, h->n_dl,
-                            nullptr, b->d_corridor, b->L.Npts, b->NptsPad, n_restarts, h->stream));
-  b->have_corridor = true;
-  b->cor_t_dirty = true;
-  b->cor_rect = false; // (nothing here waits for the device: the sixteen-double layout)
-  if (int rc = solve_impl(b, nullptr, false)) return rc;
-  DevBatch D;
-  if (int rc = sync_dev(b, D)) return rc;
-  HIPCHK(h, launch_for(b, D, kModeCoeffs));
-  // the two running sums of the reference, tabulated (as dftpav_batch_validate)
-  pc.tt.clear();
-  pc.vv.clear();
-  {
-    double t = 0.0;
-    for (int k = 0; k < 4096; k++, t += check_dt) pc.tt.push_back(t);
-    const double longest = std::max(h->params.veh_length, h->params.veh_width) + 1.0;
-    for (double dl = vertex_res; dl < longest; dl += vertex_res) pc.vv.push_back(dl);
-    if (pc.vv.empty()) pc.vv.push_back(vertex_res);
-  }
-  {
-    void *p = pc.d_t;
-    if (int rc = grow(h, &p, &pc.n_t, pc.tt.size(), sizeof(double))) return rc;
-    pc.d_t = (double *)p;
-    p = pc.d_v;
-    if (int rc = grow(h, &p, &pc.n_v, pc.vv.size(), sizeof(double))) return rc;
-    pc.d_v = (double *)p;
-    size_t nb = pc.d_col ? (size_t)B : 0;
-    p = pc.d_col;
-    if (int rc = grow(h, &p, &nb, (size_t)B, sizeof(int))) return rc;
-    pc.d_col = (int *)p;
-    nb = pc.d_first ? (size_t)B : 0;
-    p = pc.d_first;
-    if (int rc = grow(h, &p, &nb, (size_t)B, sizeof(int))) return rc;
-    pc.d_first = (int *)p;
-    nb = pc.d_valid ? (size_t)B : 0;
-    p = pc.d_valid;
-    if (int rc = grow(h, &p, &nb, (size_t)B, sizeof(int))) return rc;
-    pc.d_valid = (int *)p;
-    p = pc.d_rd;
-    if (int rc = grow(h, &p, &pc.n_rd, (size_t)B * n_samples * 8, sizeof(double))) return rc;
-    pc.d_rd = (double *)p;
-  }
-  HIPCHK(h, hipMemcpyAsync(pc.d_t, pc.tt.data(), sizeof(double) * pc.tt.size(), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(pc.d_v, pc.vv.data(), sizeof(double) * pc.vv.size(), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, launch_validate(h->d_cells, h->map.size_x, h->map.size_y, h->map.resolution, h->map.origin_x, h->map.origin_y, b->d_coef, b->d_dt,
-                            b->L, b->B, h->params.veh_width, h->params.veh_length, h->params.veh_d_cr, pc.d_t, (int)pc.tt.size(), check_dt,
-                            pc.d_v, (int)pc.vv.size(), pc.d_col, pc.d_first, h->stream));
-  HIPCHK(h, launch_states(b->d_coef, b->d_dt, b->L, b->B, h->params.veh_wheel_base, t0, state_dt, n_samples, filter_singularity != 0,
-                          pc.d_rd, pc.d_valid, h->stream));
-  pc.n_samples = n_samples;
-  pc.in_flight = true;
-  return DFTPAV_OK;
-}
-
-extern "C" int dftpav_plan_cycle_fetch(dftpav_batch *b, double *x, double *final_cost, int *status, int *success, int *iters, int *collision,
-                                       int *first_sample, double *states, int *n_valid) {
-  if (!b || !b->pc.in_flight) return DFTPAV_E_INVALID;
-  dftpav_handle *h = b->h;
-  if (int rc = dftpav_batch_results(b, x, final_cost, status, success, iters, nullptr, nullptr, nullptr)) return rc; // waits for the stream
-  const size_t B = (size_t)b->B;
-  if (collision) HIPCHK(h, hipMemcpy(collision, b->pc.d_col, sizeof(int) * B, hipMemcpyDeviceToHost));
-  if (first_sample) HIPCHK(h, hipMemcpy(first_sample, b->pc.d_first, sizeof(int) * B, hipMemcpyDeviceToHost));
-  if (states) HIPCHK(h, hipMemcpy(states, b->pc.d_rd, sizeof(double) * B * b->pc.n_samples * 8, hipMemcpyDeviceToHost));
-  if (n_valid) HIPCHK(h, hipMemcpy(n_valid, b->pc.d_valid, sizeof(int) * B, hipMemcpyDeviceToHost));
-  b->pc.in_flight = false;
-  return DFTPAV_OK;
-}
-
-// ------------------------------------------------- serialised trajectories (include/dftpav_hip.h, "DPTJ" v1)
-namespace {
-constexpr size_t kWireHeader = 32, kWireSegment = 24, kWirePiece = 104;
-template <class T> inline void put(unsigned char *&p, T v) {
-  std::memcpy(p, &v, sizeof(T));
-  p += sizeof(T);
-}
-template <class T> inline T get(const unsigned char *&p) {
-  T v;
-  std::memcpy(&v, p, sizeof(T));
-  p += sizeof(T);
-  return v;
-}
-} // namespace
-
-extern "C" size_t dftpav_wire_size(int n_segments, const int *piece_nums) {
-  if (n_segments <= 0 || n_segments > kMaxSeg || !piece_nums) return 0;
-  size_t n = kWireHeader;
-  for (int i = 0; i < n_segments; i++) {
-    if (piece_nums[i] <= 0) return 0;
-    n += kWireSegment + kWirePiece * (size_t)piece_nums[i];
-  }
-  return n;
-}
-
-extern "C" int dftpav_wire_pack(const dftpav_layout *layout, const double *coeffs, const double *piece_dt, int drone_id,
-                                int traj_id, double start_time, void *buf, size_t capacity, size_t *written) {
-  if (!layout || !coeffs || !piece_dt || !buf) return DFTPAV_E_INVALID;
-  const size_t need = dftpav_wire_size(layout->M, layout->piece_nums);
-  if (need == 0 || capacity < need) return DFTPAV_E_INVALID;
-  unsigned char *p = (unsigned char *)buf;
-  std::memcpy(p, "DPTJ", 4);
-  p += 4;
-  put<unsigned short>(p, 1);
-  put<unsigned char>(p, 5);
-  put<unsigned char>(p, 2);
-  put<int>(p, drone_id);
-  put<int>(p, traj_id);
-  put<int>(p, layout->M);
-  put<int>(p, 0);
-  put<double>(p, start_time);
-  double world = start_time; // addSingulTraj: each segment starts where the previous one ended
-  int piece = 0;
-  for (int i = 0; i < layout->M; i++) {
-    const int N = layout->piece_nums[i];
-    double dur = 0.0; // getTotalDuration: piece durations summed in order
-    for (int q = 0; q < N; q++) dur += piece_dt[i];
-    put<int>(p, layout->singuls ? layout->singuls[i] : 1);
-    put<int>(p, N);
-    put<double>(p, world);
-    put<double>(p, dur);
-    world = world + dur;
-    for (int q = 0; q < N; q++, piece++) {
-      put<double>(p, piece_dt[i]);
-      const double *c = coeffs + (size_t)piece * 12; // [k][d], k = power
-      for (int k = 5; k >= 0; k--) {                   // column 0 of CoefficientMat multiplies t^5
-        put<double>(p, c[2 * k]);
-        put<double>(p, c[2 * k + 1]);
-      }
-    }
-  }
-  if (written) *written = need;
-  return DFTPAV_OK;
-}
-
-extern "C" int dftpav_wire_info(const void *buf, size_t size, int *drone_id, int *traj_id, double *start_time, int *n_segments,
-                                int *n_pieces) {
-  if (!buf || size < kWireHeader) return DFTPAV_E_INVALID;
-  const unsigned char *p = (const unsigned char *)buf;
-  if (std::memcmp(p, "DPTJ", 4) != 0) return DFTPAV_E_INVALID;
-  p += 4;
-  if (get<unsigned short>(p) != 1 || get<unsigned char>(p) != 5 || get<unsigned char>(p) != 2) return DFTPAV_E_INVALID;
-  const int did = get<int>(p), tid = get<int>(p), M = get<int>(p);
-  (void)get<int>(p);
-  const double st = get<double>(p);
-  if (M <= 0 || M > kMaxSeg) return DFTPAV_E_INVALID;
-  size_t off = kWireHeader;
-  int pieces = 0;
-  for (int i = 0; i < M; i++) {
-    if (size < off + kWireSegment) return DFTPAV_E_INVALID;
-    const unsigned char *q = (const unsigned char *)buf + off;
-    const int sg = get<int>(q), N = get<int>(q);
-    if ((sg != 1 && sg != -1) || N <= 0 || N > 4096) return DFTPAV_E_INVALID;
-    off += kWireSegment + kWirePiece * (size_t)N;
-    pieces += N;
-  }
-  if (size < off) return DFTPAV_E_INVALID;
-  if (drone_id) *drone_id = did;
-  if (traj_id) *traj_id = tid;
-  if (start_time) *start_time = st;
-  if (n_segments) *n_segments = M;
-  if (n_pieces) *n_pieces = pieces;
-  return DFTPAV_OK;
-}
-
-extern "C" int dftpav_wire_unpack(const void *buf, size_t size, int *singuls, int *piece_nums, double *seg_start,
-                                  double *seg_duration, double *durations, double *coeffs) {
-  int M = 0;
-  if (int rc = dftpav_wire_info(buf, size, nullptr, nullptr, nullptr, &M, nullptr)) return rc;
-  const unsigned char *p = (const unsigned char *)buf + kWireHeader;
-  int piece = 0;
-  for (int i = 0; i < M; i++) {
-    const int sg = get<int>(p), N = get<int>(p);
-    const double st = get<double>(p), du = get<double>(p);
-    if (singuls) singuls[i] = sg;
-    if (piece_nums) piece_nums[i] = N;
-    if (seg_start) seg_start[i] = st;
-    if (seg_duration) seg_duration[i] = du;
-    for (int q = 0; q < N; q++, piece++) {
-      const double d = get<double>(p);
-      if (durations) durations[piece] = d;
-      for (int k = 0; k < 12; k++) {
-        const double c = get<double>(p);
-        if (coeffs) coeffs[(size_t)piece * 12 + k] = c;
-      }
-    }
-  }
-  return DFTPAV_OK;
-}
-
-extern "C" int dftpav_set_surround_wire(dftpav_handle *h, const void *const *bufs, const size_t *sizes, int S) {
-  if (!h) return DFTPAV_E_INVALID;
-  if (S <= 0) return dftpav_set_surround(h, nullptr);
-  if (!bufs || !sizes) return DFTPAV_E_INVALID;
-  std::vector<int> off(1, 0);
-  std::vector<double> dur, coef, total, start;
-  for (int s = 0; s < S; s++) {
-    int M = 0, np = 0;
-    double st = 0.0;
-    if (int rc = dftpav_wire_info(bufs[s], sizes[s], nullptr, nullptr, &st, &M, &np)) return rc;
-    std::vector<int> sg(M), pn(M);
-    const size_t at = dur.size();
-    dur.resize(at + np);
-    coef.resize((at + np) * 12);
-    if (int rc = dftpav_wire_unpack(bufs[s], sizes[s], sg.data(), pn.data(), nullptr, nullptr, dur.data() + at, coef.data() + at * 12))
-      return rc;
-    for (int i = 0; i < M; i++)
-      if (sg[i] != 1) return DFTPAV_E_INVALID; // the obstacle model is forward-only (traj_manager.cpp:726,775)
-    double tot = 0.0; // LocalTrajData::duration = Trajectory::getTotalDuration of the joined pieces
-    for (int q = 0; q < np; q++) tot += dur[at + q];
-    off.push_back((int)(at + np));
-    total.push_back(tot);
-    start.push_back(st);
-  }
-  dftpav_surround sur{S, off.data(), dur.data(), coef.data(), total.data(), start.data()};
-  return dftpav_set_surround(h, &sur);
-}
-
-extern "C" int dftpav_solve_batch(dftpav_handle *h, const dftpav_layout *layout, int B, const dftpav_batch_data *d,
-                                  double *x, double *final_cost, int *status, int *success, int *iters, int *evals) {
-  dftpav_batch *b = nullptr;
-  int rc = dftpav_batch_create(h, layout, B, &b);
-  if (rc != DFTPAV_OK) return rc;
-  rc = dftpav_batch_upload(b, d);
-  if (rc == DFTPAV_OK) rc = dftpav_batch_solve_async(b);
-  if (rc == DFTPAV_OK) rc = dftpav_batch_results(b, x, final_cost, status, success, iters, evals, nullptr, nullptr);
-  dftpav_batch_destroy(b);
-  return rc;
-}
-
-// ------------------------------------------------- a batch of queries to their plans (plan.hip)
-// TrajPlanner::RunOnceParking from the arrival test on (traj_manager.cpp:194-217) for Q queries: search -> resampling on the device,
-// one read-back of the tables that decide the layouts, then per layout group pack -> rectangles -> reference-order solve ->
-// coefficients -> collision re-check -> selection, all enqueued on the handle's stream with no wait between stages or groups.
-extern "C" void dftpav_default_plan_params(dftpav_plan_params *pp) {
-  std::memset(pp, 0, sizeof(*pp));
-  dftpav_default_search_params(&pp->search);
-  // minco_config.pb.txt:66-67, 76-80; kino_astar.h:207; semantics.h:68 (the defaults of dftpav_frontend_resample's callers)
-  pp->frontend.max_forward_vel = 5.0;
-  pp->frontend.max_forward_acc = 8.0;
-  pp->frontend.max_backward_vel = 2.0;
-  pp->frontend.max_backward_acc = 4.0;
-  pp->frontend.non_siguav = 0.2;
-  pp->frontend.wheel_base = 2.85;
-  pp->frontend.piece_duration = 1.0;
-  pp->frontend.traj_res = 16;
-  pp->frontend.dense_traj_res = 32;
-  pp->sigma = 0.3;
-  pp->dur_lo = 0.8;
-  pp->dur_hi = 1.25;
-  pp->seed = 0;
-  pp->check_dt = 0.05;  // traj_server_ros.cpp:387
-  pp->vertex_res = 0.1; // shapes.h:201
-  pp->max_seg = 8;
-  pp->max_pieces = 64;
-  pp->max_path = 4096;
-}
-extern "C" int dftpav_abi_sizeof_plan_params(void) { return (int)sizeof(dftpav_plan_params); }
-extern "C" int dftpav_abi_sizeof_plan_out(void) { return (int)sizeof(dftpav_plan_out); }
-
-extern "C" int dftpav_plan_group_layouts(int Q, int max_seg, const int *search_status, const int *n_seg, const int *singul,
-                                         const int *piece_nums, int *group, int *group_first, int *n_groups, int *plan_status) {
-  if (Q < 0 || max_seg < 1 || !n_groups || (Q > 0 && (!search_status || !n_seg || !singul || !piece_nums || !group || !group_first)))
-    return DFTPAV_E_INVALID;
-  int ng = 0;
-  for (int q = 0; q < Q; q++) {
-    group[q] = -1;
-    if (search_status[q] != DFTPAV_SEARCH_REACH_END) {
-      if (plan_status) plan_status[q] = DFTPAV_PLAN_NO_PATH;
-      continue;
-    }
-    const int M = n_seg[q];
-    if (M < 1 || M > max_seg) {
-      if (plan_status) plan_status[q] = DFTPAV_PLAN_TOO_MANY_SEGMENTS;
-      continue;
-    }
-    const int *sg = singul + (size_t)q * max_seg, *pn = piece_nums + (size_t)q * max_seg;
-    int g = 0;
-    for (; g < ng; g++) {
-      const int f = group_first[g];
-      if (n_seg[f] == M && std::memcmp(singul + (size_t)f * max_seg, sg, sizeof(int) * M) == 0 &&
-          std::memcmp(piece_nums + (size_t)f * max_seg, pn, sizeof(int) * M) == 0)
-        break;
-    }
-    if (g == ng) group_first[ng++] = q;
-    group[q] = g;
-    if (plan_status) plan_status[q] = DFTPAV_PLAN_OK;
-  }
-  *n_groups = ng;
-  return DFTPAV_OK;
-}
-
-struct dftpav_planner {
-  dftpav_handle *h = nullptr;
-  int max_queries = 0, R = 0;
-  struct Entry {
-    std::vector<int> key; // M, singul[M], piece_nums[M]
-    dftpav_batch *b;
-  };
-  std::vector<Entry> cache; // one batch per layout met so far
-  // device work buffers: one allocation, carved up for the paddings of the last call (kept while they do not change)
-  unsigned char *d_arena = nullptr;
-  size_t arena_bytes = 0;
-  long long sig[6] = {0, 0, 0, 0, 0, 0}; // max_seg, max_pieces, max_path, max_states, doubles of the search tables, of the validation tables
-  double *d_st = nullptr, *d_en = nullptr, *d_ct = nullptr, *d_tabs = nullptr, *d_paths = nullptr, *d_vt = nullptr;
-  int *d_skip = nullptr, *d_sints = nullptr, *d_fe_len = nullptr, *d_members = nullptr, *d_minit = nullptr, *d_col = nullptr, *d_first = nullptr;
-  dftpav_frontend_out fe{}; // device pointers
-  double *d_poses = nullptr;
-  size_t fe_zero_bytes = 0; // the front-end outputs are one stretch of the arena, zeroed per call (as dftpav_frontend_resample does)
-  unsigned char *d_fe0 = nullptr;
-  // compact outputs (zeroed per call): one stretch too
-  unsigned char *d_out0 = nullptr;
-  size_t out_zero_bytes = 0;
-  int *d_winner = nullptr, *d_witers = nullptr, *d_rint[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  double *d_wcost = nullptr, *d_wx = nullptr, *d_wcoef = nullptr, *d_wdt = nullptr, *d_rcost = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool timed = false;
-  std::vector<int> group_sizes;
-  // host staging of the tables that decide the grouping
-  std::vector<int> h_sints, h_nseg, h_singul, h_pn, h_nstates, h_skip, h_members, h_minit;
-  std::vector<double> h_dt, h_vt;
-  // ---- the replan loop (dftpav_planner_install ... dftpav_replan_tick)
-  // what the last dftpav_plan_queries call left behind for dftpav_planner_adopt: its size and paddings, per query the final
-  // plan_status and winner, and the goals
-  int last_Q = 0, last_MS = 0, last_MP = 0;
-  std::vector<int> last_status, last_winner;
-  std::vector<double> last_goal;
-  // the executing table: one allocation of its own (the arena above is carved again when the paddings of a call change)
-  unsigned char *d_exec = nullptr;
-  ExecTable T{};
-  std::vector<int> h_occupied;  // host mirror: n_seg of every slot
-  std::vector<double> h_goal;   // host mirror: the stored goals [slots][4]
-  // outputs of the check, its two tables and its inputs: one allocation
-  unsigned char *d_rc = nullptr;
-  int *d_rc_int = nullptr, *d_pairs = nullptr;
-  double *d_rc_des = nullptr, *d_rc_st = nullptr, *d_rc_ct = nullptr, *d_rc_goal = nullptr, *d_rc_ego = nullptr, *d_rc_tab = nullptr;
-  int rc_n_t = 0, rc_n_v = 0;
-  double rc_dt = 0.0, rc_res = 0.0; // what d_rc_tab was tabulated for
-  hipEvent_t rev[4] = {nullptr, nullptr, nullptr, nullptr}; // check start / end, tick start / end
-  bool check_timed = false, tick_timed = false;
-  // ---- the publisher (dftpav_planner_publish): its state per slot lives in d_exec beside the table; clocks and outputs grow on demand
-  PubTable P{};
-  int *d_pub_mode = nullptr; // [slots] of d_rc: what an adoption does to the control history of each adopted pair
-  unsigned char *d_pub = nullptr;
-  size_t pub_ticks = 0; // d_pub holds the clocks and outputs of this many ticks
-  double *d_pub_t = nullptr, *d_pub_states = nullptr;
-  int *d_pub_code = nullptr;
-  hipEvent_t pev[2] = {nullptr, nullptr};
-  bool pub_timed = false;
-};
-
-extern "C" int dftpav_planner_create(dftpav_handle *h, int max_queries, int n_restarts, dftpav_planner **out) {
-  if (out) *out = nullptr;
-  if (!h || !out) return DFTPAV_E_INVALID;
-  if (max_queries < 1 || n_restarts < 1 || n_restarts > 65535 || (long long)max_queries * n_restarts > (1 << 24)) return DFTPAV_E_INVALID;
-  HIPCHK(h, hipSetDevice(h->device));
-  auto *p = new dftpav_planner();
-  p->h = h;
-  p->max_queries = max_queries;
-  p->R = n_restarts;
-  for (auto &e : p->ev)
-    if (hipEventCreate(&e) != hipSuccess) {
-      h->err = "dftpav_planner_create: hipEventCreate";
-      for (auto &f : p->ev)
-        if (f) (void)hipEventDestroy(f);
-      delete p;
-      return DFTPAV_E_HIP;
-    }
-  for (auto &e : p->rev)
-    if (hipEventCreate(&e) != hipSuccess) {
-      h->err = "dftpav_planner_create: hipEventCreate";
-      for (auto &f : p->ev) (void)hipEventDestroy(f);
-      for (auto &f : p->rev)
-        if (f) (void)hipEventDestroy(f);
-      delete p;
-      return DFTPAV_E_HIP;
-    }
-  *out = p;
-  return DFTPAV_OK;
-}
-extern "C" void dftpav_planner_destroy(dftpav_planner *p) {
-  if (!p) return;
-  (void)hipSetDevice(p->h->device);
-  (void)hipStreamSynchronize(p->h->stream);
-  for (auto &e : p->cache) dftpav_batch_destroy(e.b);
-  if (p->d_arena) (void)hipFree(p->d_arena);
-  if (p->d_exec) (void)hipFree(p->d_exec);
-  if (p->d_rc) (void)hipFree(p->d_rc);
-  if (p->d_pub) (void)hipFree(p->d_pub);
-  for (auto &e : p->pev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto &e : p->ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto &e : p->rev)
-    if (e) (void)hipEventDestroy(e);
-  delete p;
-}
-
-extern "C" int dftpav_planner_info(dftpav_planner *p, int *n_batches, int *n_groups, int *group_sizes, float *stage_ms) {
-  if (!p) return DFTPAV_E_INVALID;
-  if (n_batches) *n_batches = (int)p->cache.size();
-  if (n_groups) *n_groups = (int)p->group_sizes.size();
-  if (group_sizes)
-    for (size_t g = 0; g < p->group_sizes.size(); g++) group_sizes[g] = p->group_sizes[g];
-  if (stage_ms) {
-    dftpav_handle *h = p->h;
-    for (int k = 0; k < 4; k++) stage_ms[k] = 0.0f;
-    if (p->timed) {
-      HIPCHK(h, hipSetDevice(h->device));
-      HIPCHK(h, hipEventSynchronize(p->ev[3]));
-      HIPCHK(h, hipEventElapsedTime(&stage_ms[0], p->ev[0], p->ev[1]));
-      HIPCHK(h, hipEventElapsedTime(&stage_ms[1], p->ev[1], p->ev[2]));
-      HIPCHK(h, hipEventElapsedTime(&stage_ms[2], p->ev[2], p->ev[3]));
-      HIPCHK(h, hipEventElapsedTime(&stage_ms[3], p->ev[0], p->ev[3]));
-    }
-  }
-  return DFTPAV_OK;
-}
-
-// carves the planner's arena for these paddings (a no-op while they are those of the previous call)
-static int planner_buffers(dftpav_planner *p, const dftpav_plan_params &pp, int max_states, size_t n_tabs, size_t n_vt) {
-  dftpav_handle *h = p->h;
-  const long long sig[6] = {pp.max_seg, pp.max_pieces, pp.max_path, max_states, (long long)n_tabs, (long long)n_vt};
-  if (p->d_arena && std::memcmp(sig, p->sig, sizeof(sig)) == 0) return DFTPAV_OK;
-  const size_t Q = (size_t)p->max_queries, R = (size_t)p->R, MS = (size_t)pp.max_seg, MP = (size_t)pp.max_pieces, MST = (size_t)max_states;
-  for (int pass = 0; pass < 2; pass++) { // measure, then carve
-    unsigned char *w = p->d_arena;
-    size_t used = 0;
-    auto take = [&](size_t bytes) {
-      void *r = pass ? (void *)(w + used) : nullptr;
-      used += (bytes + 255) / 256 * 256;
-      return r;
-    };
-    p->d_st = (double *)take(sizeof(double) * 4 * Q);
-    p->d_en = (double *)take(sizeof(double) * 4 * Q);
-    p->d_ct = (double *)take(sizeof(double) * 2 * Q);
-    p->d_tabs = (double *)take(sizeof(double) * n_tabs);
-    p->d_vt = (double *)take(sizeof(double) * n_vt);
-    p->d_paths = (double *)take(sizeof(double) * 3 * Q * (size_t)pp.max_path);
-    p->d_skip = (int *)take(sizeof(int) * Q);
-    p->d_sints = (int *)take(sizeof(int) * 9 * Q);
-    p->d_fe_len = (int *)take(sizeof(int) * Q);
-    p->d_members = (int *)take(sizeof(int) * Q);
-    p->d_col = (int *)take(sizeof(int) * Q * R);
-    p->d_first = (int *)take(sizeof(int) * Q * R);
-    p->d_poses = (double *)take(sizeof(double) * 3 * Q * MS * MST);
-    const size_t fe0 = used;
-    p->d_fe0 = (unsigned char *)take(0);
-    p->fe.max_seg = pp.max_seg;
-    p->fe.max_pieces = pp.max_pieces;
-    p->fe.max_states = max_states;
-    p->fe.n_seg = (int *)take(sizeof(int) * Q);
-    p->fe.singul = (int *)take(sizeof(int) * Q * MS);
-    p->fe.piece_nums = (int *)take(sizeof(int) * Q * MS);
-    p->fe.piece_dt = (double *)take(sizeof(double) * Q * MS);
-    p->fe.ini_states = (double *)take(sizeof(double) * Q * MS * 6);
-    p->fe.fin_states = (double *)take(sizeof(double) * Q * MS * 6);
-    p->fe.inner_pts = (double *)take(sizeof(double) * Q * MS * (MP - 1) * 2);
-    p->fe.n_states = (int *)take(sizeof(int) * Q * MS);
-    p->fe.states = (double *)take(sizeof(double) * Q * MS * MST * 3);
-    p->fe_zero_bytes = used - fe0;
-    const size_t out0 = used;
-    p->d_out0 = (unsigned char *)take(0);
-    p->d_minit = (int *)take(sizeof(int) * Q);
-    p->d_winner = (int *)take(sizeof(int) * Q);
-    p->d_witers = (int *)take(sizeof(int) * Q);
-    p->d_wcost = (double *)take(sizeof(double) * Q);
-    p->d_wx = (double *)take(sizeof(double) * Q * DFTPAV_PLAN_MAX_VARS);
-    p->d_wcoef = (double *)take(sizeof(double) * Q * MS * MP * 12);
-    p->d_wdt = (double *)take(sizeof(double) * Q * MS);
-    p->d_rcost = (double *)take(sizeof(double) * Q * R);
-    for (int k = 0; k < 6; k++) p->d_rint[k] = (int *)take(sizeof(int) * Q * R);
-    p->out_zero_bytes = used - out0;
-    if (pass == 0) {
-      HIPCHK(h, hipStreamSynchronize(h->stream));
-      if (p->d_arena && p->arena_bytes < used) {
-        (void)hipFree(p->d_arena);
-        p->d_arena = nullptr;
-        p->arena_bytes = 0;
-      }
-      if (!p->d_arena) {
-        HIPCHK(h, hipMalloc(&p->d_arena, used));
-        p->arena_bytes = used;
-      }
-    }
-  }
-  std::memcpy(p->sig, sig, sizeof(sig));
-  return DFTPAV_OK;
-}
-
-// the batch of a layout: from the cache, or created with room for max_queries * n_restarts trajectories in the reference order.
-// *out == nullptr with DFTPAV_OK: the layout is outside the reference order's limits.
-static int planner_batch(dftpav_planner *p, const dftpav_layout &lay, dftpav_batch **out) {
-  dftpav_handle *h = p->h;
-  *out = nullptr;
-  std::vector<int> key;
-  key.push_back(lay.M);
-  key.insert(key.end(), lay.singuls, lay.singuls + lay.M);
-  key.insert(key.end(), lay.piece_nums, lay.piece_nums + lay.M);
-  dftpav_batch *b = nullptr;
-  for (auto &e : p->cache)
-    if (e.key == key) b = e.b;
-  if (lay.M > kMaxSeg) return DFTPAV_OK;
-  for (int i = 0; i < lay.M; i++)
-    if (lay.piece_nums[i] < 2) return DFTPAV_OK;
-  DevLayout L;
-  fill_dev_layout(lay, h->params.traj_resolution, h->params.des_traj_resolution, L);
-  DevParams P;
-  fill_dev_params(h->params, P);
-  if (L.n > DFTPAV_PLAN_MAX_VARS || L.Ntot > 1024 || L.Npts > 32767 || (long long)L.Npts * h->S > 65535 || !reference_order_supported(L, P, h->S))
-    return DFTPAV_OK;
-  const bool fresh = b == nullptr;
-  if (fresh) {
-    const int rc = dftpav_batch_create(h, &lay, p->max_queries * p->R, &b);
-    if (rc == DFTPAV_E_UNSUPPORTED) return DFTPAV_OK;
-    if (rc) return rc;
-  }
-  const int rc = dftpav_batch_set_order(b, DFTPAV_ORDER_REFERENCE); // (nothing to do for a cached batch unless the obstacles changed)
-  if (rc) {
-    if (fresh) dftpav_batch_destroy(b);
-    return rc == DFTPAV_E_UNSUPPORTED ? DFTPAV_OK : rc;
-  }
-  if (fresh) p->cache.push_back({key, b});
-  *out = b;
-  return DFTPAV_OK;
-}
-
-extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *pp, const double *start_states, const double *start_ctrl,
-                                   const double *end_states, int Q, double t_now, const dftpav_plan_out *out) {
-  if (!p || !pp || !out || Q < 0 || Q > p->max_queries) return DFTPAV_E_INVALID;
-  dftpav_handle *h = p->h;
-  if (!h->d_cells) return DFTPAV_E_INVALID; // no map
-  const dftpav_frontend_params &fp = pp->frontend;
-  if (pp->max_seg < 1 || pp->max_seg > kMaxSeg || pp->max_pieces < 2 || pp->max_pieces > 1024 || pp->max_path < 2 || pp->max_path > (1 << 20) ||
-      !(pp->sigma >= 0.0) || !(pp->dur_lo > 0.0) || !(pp->dur_hi >= pp->dur_lo) || !(pp->check_dt > 0.0) || !(pp->vertex_res > 0.0) ||
-      fp.traj_res != h->params.traj_resolution || fp.dense_traj_res != h->params.des_traj_resolution || fp.traj_res < 1 || fp.dense_traj_res < 1 ||
-      !(fp.piece_duration > 0.0) || !(fp.max_forward_vel > 0.0) || !(fp.max_forward_acc > 0.0) || !(fp.max_backward_vel > 0.0) ||
-      !(fp.max_backward_acc > 0.0))
-    return DFTPAV_E_INVALID;
-  p->group_sizes.clear();
-  p->timed = false;
-  p->last_Q = 0; // nothing to adopt until this call has ended well
-  if (Q == 0) return DFTPAV_OK;
-  if (!start_states || !start_ctrl || !end_states) return DFTPAV_E_INVALID;
-  SearchSetup U;
-  if (int rc = search_setup(h, &pp->search, Q, U)) return rc;
-  const int R = p->R, MS = pp->max_seg, MP = pp->max_pieces;
-  const int MST = (MP - 2) * (fp.traj_res + 1) + 2 * (fp.dense_traj_res + 1); // poses of a segment of max_pieces pieces
-  // the two running sums of the collision re-check, tabulated (as dftpav_batch_validate): sample times | outline point spacing
-  std::vector<double> &vt = p->h_vt;
-  vt.clear();
-  {
-    double t = 0.0;
-    for (int k = 0; k < 4096; k++, t += pp->check_dt) vt.push_back(t);
-    const double longest = std::max(h->params.veh_length, h->params.veh_width) + 1.0;
-    for (double dl = pp->vertex_res; dl < longest; dl += pp->vertex_res) vt.push_back(dl);
-    if (vt.size() == 4096) vt.push_back(pp->vertex_res);
-  }
-  const int n_t = 4096, n_v = (int)vt.size() - 4096;
-  if (int rc = planner_buffers(p, *pp, MST, U.tabs.size(), vt.size())) return rc;
-  const size_t nq = (size_t)Q;
-  // ---- arrival test (traj_manager.cpp:196), uploads, search, resampling
-  p->h_skip.assign(Q, 0);
-  for (int q = 0; q < Q; q++) {
-    const double dx = end_states[4 * q] - start_states[4 * q], dy = end_states[4 * q + 1] - start_states[4 * q + 1];
-    if (std::sqrt(dx * dx + dy * dy) < 1.0) p->h_skip[q] = 1;
-  }
-  HIPCHK(h, hipMemcpyAsync(p->d_st, start_states, sizeof(double) * 4 * nq, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(p->d_en, end_states, sizeof(double) * 4 * nq, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(p->d_ct, start_ctrl, sizeof(double) * 2 * nq, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(p->d_skip, p->h_skip.data(), sizeof(int) * nq, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(p->d_tabs, U.tabs.data(), sizeof(double) * U.tabs.size(), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(p->d_vt, vt.data(), sizeof(double) * vt.size(), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemsetAsync(p->d_paths, 0, sizeof(double) * 3 * nq * pp->max_path, h->stream));
-  HIPCHK(h, hipMemsetAsync(p->d_fe0, 0, p->fe_zero_bytes, h->stream));
-  HIPCHK(h, hipMemsetAsync(p->d_out0, 0, p->out_zero_bytes, h->stream));
-  SearchArgs &S = U.S;
-  S.in_tab = p->d_tabs;
-  S.v_tab = p->d_tabs + U.n_in_tab;
-  S.l_tab = p->d_tabs + U.n_in_tab + U.n_vv;
-  S.start = p->d_st;
-  S.end = p->d_en;
-  {
-    dftpav_search_out &O = S.out;
-    int *d = p->d_sints;
-    O.max_nodes = 0;
-    O.max_path = pp->max_path;
-    O.status = d;
-    O.shot_success = d + nq;
-    O.used_3d = d + 2 * nq;
-    O.budget_hit = d + 3 * nq;
-    O.iters = d + 4 * nq;
-    O.nodes_used = d + 5 * nq;
-    O.n_nodes = d + 6 * nq;
-    O.path_len = d + 7 * nq;
-    O.nodes = nullptr;
-    O.paths = p->d_paths;
-  }
-  HIPCHK(h, hipEventRecord(p->ev[0], h->stream));
-  for (int q0 = 0; q0 < Q; q0 += U.slots) {
-    S.q0 = q0;
-    HIPCHK(h, launch_search(S, std::min(U.slots, Q - q0), h->stream));
-  }
-  HIPCHK(h, hipEventRecord(p->ev[1], h->stream));
-  HIPCHK(h, launch_plan_paths(S.out.status, S.out.path_len, p->d_skip, Q, pp->max_path, p->d_paths, p->d_fe_len, h->stream));
-  HIPCHK(h, launch_frontend(fp, p->d_paths, p->d_fe_len, pp->max_path, p->d_st, p->d_en, p->d_ct, Q, p->fe, h->stream));
-  HIPCHK(h, hipEventRecord(p->ev[2], h->stream));
-  // ---- the one read-back before the end: the tables that decide the grouping
-  p->h_sints.assign(8 * nq, 0);
-  p->h_nseg.assign(nq, 0);
-  p->h_singul.assign(nq * MS, 0);
-  p->h_pn.assign(nq * MS, 0);
-  p->h_nstates.assign(nq * MS, 0);
-  p->h_dt.assign(nq * MS, 0.0);
-  for (int f = 0; f < 8; f++)
-    HIPCHK(h, hipMemcpyAsync(p->h_sints.data() + f * nq, p->d_sints + f * nq, sizeof(int) * nq, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(p->h_nseg.data(), p->fe.n_seg, sizeof(int) * nq, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(p->h_singul.data(), p->fe.singul, sizeof(int) * nq * MS, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(p->h_pn.data(), p->fe.piece_nums, sizeof(int) * nq * MS, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(p->h_nstates.data(), p->fe.n_states, sizeof(int) * nq * MS, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(p->h_dt.data(), p->fe.piece_dt, sizeof(double) * nq * MS, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  const int *s_status = p->h_sints.data(), *s_iters = p->h_sints.data() + 4 * nq, *s_len = p->h_sints.data() + 7 * nq;
-  for (int q = 0; q < Q; q++)
-    if (s_status[q] == 0) return DFTPAV_E_UNSUPPORTED; // a shot beyond the sample table (as dftpav_kino_search)
-  // ---- grouping.  Queries that were not resampled (arrived, a path beyond its padding) are kept out of it, as those without a path are
-  std::vector<int> gate(nq), group(nq), first(nq), status(nq);
-  for (int q = 0; q < Q; q++) {
-    const bool usable = s_status[q] == DFTPAV_SEARCH_REACH_END && s_len[q] >= 2 && s_len[q] <= pp->max_path && !p->h_skip[q];
-    gate[q] = usable ? DFTPAV_SEARCH_REACH_END : DFTPAV_SEARCH_NO_PATH;
-    if (!usable) {
-      p->h_nseg[q] = 0;
-      for (int i = 0; i < MS; i++) p->h_singul[(size_t)q * MS + i] = p->h_pn[(size_t)q * MS + i] = p->h_nstates[(size_t)q * MS + i] = 0, p->h_dt[(size_t)q * MS + i] = 0.0;
-    } else if (p->h_nseg[q] >= 1 && p->h_nseg[q] <= MS) {
-      for (int i = 0; i < p->h_nseg[q]; i++) // a segment of more pieces than the padding: its waypoints and poses were cut
-        if (p->h_pn[(size_t)q * MS + i] > MP || p->h_nstates[(size_t)q * MS + i] > MST) gate[q] = -1;
-    }
-  }
-  int ng = 0;
-  if (int rc = dftpav_plan_group_layouts(Q, MS, gate.data(), p->h_nseg.data(), p->h_singul.data(), p->h_pn.data(), group.data(), first.data(), &ng,
-                                         status.data()))
-    return rc;
-  for (int q = 0; q < Q; q++) {
-    if (p->h_skip[q]) status[q] = DFTPAV_PLAN_ARRIVED;
-    else if (gate[q] == -1 || (s_status[q] == DFTPAV_SEARCH_REACH_END && s_len[q] > pp->max_path)) status[q] = DFTPAV_PLAN_TOO_MANY_SEGMENTS;
-  }
-  // ---- the groups' batches (created on first use), the members in group order
-  std::vector<dftpav_batch *> batch(ng, nullptr);
-  std::vector<int> g_off(ng + 1, 0);
-  p->h_members.clear();
-  for (int g = 0; g < ng; g++) {
-    const int f = first[g];
-    dftpav_layout lay{p->h_nseg[f], p->h_pn.data() + (size_t)f * MS, p->h_singul.data() + (size_t)f * MS, 4};
-    if (int rc = planner_batch(p, lay, &batch[g])) return rc;
-    g_off[g] = (int)p->h_members.size();
-    for (int q = 0; q < Q; q++)
-      if (group[q] == g) {
-        if (batch[g]) p->h_members.push_back(q);
-        else status[q] = DFTPAV_PLAN_LAYOUT_UNSUPPORTED;
-      }
-    g_off[g + 1] = (int)p->h_members.size();
-    p->group_sizes.push_back(g_off[g + 1] - g_off[g]);
-  }
-  HIPCHK(h, hipSetDevice(h->device));
-  if (!p->h_members.empty())
-    HIPCHK(h, hipMemcpyAsync(p->d_members, p->h_members.data(), sizeof(int) * p->h_members.size(), hipMemcpyHostToDevice, h->stream));
-  // ---- per group: pack -> rectangles -> solve -> coefficients -> collision re-check -> selection; nothing waits in between
-  size_t pose_off = 0;
-  for (int g = 0; g < ng; g++) {
-    dftpav_batch *b = batch[g];
-    const int nm = g_off[g + 1] - g_off[g];
-    if (!b || nm == 0) continue;
-    const DevLayout &L = b->L;
-    b->pending = false;
-    b->n_active = nm * R;
-    b->t_now = t_now;
-    b->epis = 0.0; // help_eps of the live call, traj_manager.cpp:610
-    b->uploaded = true;
-    b->solved = false;
-    b->coef_override = false;
-    b->dev_version = -1; // n_active / t_now live in the device copy of the launch descriptor
-    PlanPackArgs A{};
-    A.L = L;
-    A.fe = p->fe;
-    A.members = p->d_members + g_off[g];
-    A.n_members = nm;
-    A.n_restarts = R;
-    A.sigma = pp->sigma;
-    A.lo = pp->dur_lo;
-    A.hi = pp->dur_hi;
-    A.seed = pp->seed;
-    A.mini_T = h->params.mini_T;
-    A.max_vel[0] = h->params.max_forward_vel;
-    A.max_vel[1] = h->params.max_backward_vel;
-    A.max_acc[0] = h->params.max_forward_acc;
-    A.max_acc[1] = h->params.max_backward_acc;
-    A.x0 = b->d_x0;
-    A.iniS = b->d_iniS;
-    A.finS = b->d_finS;
-    A.poses = p->d_poses + 3 * pose_off;
-    A.mini_t_flag = p->d_minit;
-    HIPCHK(h, launch_plan_pack(A, h->stream));
-    HIPCHK(h, launch_corridor(h->d_cells, h->d_bits, h->map.size_x, h->map.size_y, h->map.resolution, h->map.origin_x, h->map.origin_y, A.poses,
-                              nm * L.Npts, h->params.veh_width, h->params.veh_length, h->params.veh_d_cr, h->d_dl, h->n_dl, nullptr, b->d_corridor,
-                              L.Npts, b->NptsPad, R, h->stream));
-    pose_off += (size_t)nm * L.Npts;
-    b->have_corridor = true;
-    b->cor_t_dirty = true;
-    b->cor_rect = false; // (nothing here waits for the device: the sixteen-double layout)
-    if (int rc = solve_impl(b, nullptr, false)) return rc;
-    DevBatch D;
-    if (int rc = sync_dev(b, D)) return rc;
-    HIPCHK(h, launch_for(b, D, kModeCoeffs));
-    int *col = p->d_col + (size_t)g_off[g] * R, *fst = p->d_first + (size_t)g_off[g] * R;
-    HIPCHK(h, launch_validate(h->d_cells, h->map.size_x, h->map.size_y, h->map.resolution, h->map.origin_x, h->map.origin_y, b->d_coef, b->d_dt, L,
-                              nm * R, h->params.veh_width, h->params.veh_length, h->params.veh_d_cr, p->d_vt, n_t, pp->check_dt, p->d_vt + n_t, n_v,
-                              col, fst, h->stream));
-    PlanSelectArgs Z{};
-    Z.cost = b->d_f;
-    Z.success = b->d_success;
-    Z.collision = col;
-    Z.status = b->d_status;
-    Z.iters = b->d_iters;
-    Z.evals = b->d_evals;
-    Z.first_sample = fst;
-    Z.x = b->d_x_out;
-    Z.coef = b->d_coef;
-    Z.dt = b->d_dt;
-    Z.n = L.n;
-    Z.n_coef = 12 * L.Ntot;
-    Z.M = L.M;
-    Z.members = A.members;
-    Z.n_members = nm;
-    Z.R = R;
-    Z.winner = p->d_winner;
-    Z.w_cost = p->d_wcost;
-    Z.w_iters = p->d_witers;
-    Z.w_x = p->d_wx;
-    Z.w_coef = p->d_wcoef;
-    Z.w_dt = p->d_wdt;
-    Z.x_stride = DFTPAV_PLAN_MAX_VARS;
-    Z.coef_stride = MS * MP * 12;
-    Z.dt_stride = MS;
-    Z.r_cost = p->d_rcost;
-    Z.r_status = p->d_rint[0];
-    Z.r_success = p->d_rint[1];
-    Z.r_iters = p->d_rint[2];
-    Z.r_evals = p->d_rint[3];
-    Z.r_collision = p->d_rint[4];
-    Z.r_first_sample = p->d_rint[5];
-    HIPCHK(h, launch_plan_select(Z, h->stream));
-  }
-  HIPCHK(h, hipEventRecord(p->ev[3], h->stream));
-  p->timed = true;
-  // ---- the compact results
-  std::vector<int> winner(nq, -1);
-  p->h_minit.assign(nq, 0);
-  auto fetch = [&](void *dst, const void *src, size_t bytes) { return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess; };
-  HIPCHK(h, fetch(winner.data(), p->d_winner, sizeof(int) * nq));
-  HIPCHK(h, fetch(p->h_minit.data(), p->d_minit, sizeof(int) * nq));
-  HIPCHK(h, fetch(out->final_cost, p->d_wcost, sizeof(double) * nq));
-  HIPCHK(h, fetch(out->iters, p->d_witers, sizeof(int) * nq));
-  HIPCHK(h, fetch(out->x, p->d_wx, sizeof(double) * nq * DFTPAV_PLAN_MAX_VARS));
-  HIPCHK(h, fetch(out->coeffs, p->d_wcoef, sizeof(double) * nq * MS * MP * 12));
-  HIPCHK(h, fetch(out->coeff_dt, p->d_wdt, sizeof(double) * nq * MS));
-  HIPCHK(h, fetch(out->r_final_cost, p->d_rcost, sizeof(double) * nq * R));
-  int *const r_out[6] = {out->r_status, out->r_success, out->r_iters, out->r_evals, out->r_collision, out->r_first_sample};
-  for (int k = 0; k < 6; k++) HIPCHK(h, fetch(r_out[k], p->d_rint[k], sizeof(int) * nq * R));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  for (int q = 0; q < Q; q++) {
-    if (status[q] != DFTPAV_PLAN_OK) {
-      winner[q] = -1;
-      continue;
-    }
-    if (p->h_minit[q]) { // a restart below mini_T: OptimizeTrajectory refuses the call (see the header); no plan is reported
-      winner[q] = -1;
-      if (out->final_cost) out->final_cost[q] = 0.0;
-      if (out->iters) out->iters[q] = 0;
-      if (out->x) std::memset(out->x + (size_t)q * DFTPAV_PLAN_MAX_VARS, 0, sizeof(double) * DFTPAV_PLAN_MAX_VARS);
-      if (out->coeffs) std::memset(out->coeffs + (size_t)q * MS * MP * 12, 0, sizeof(double) * MS * MP * 12);
-      if (out->coeff_dt) std::memset(out->coeff_dt + (size_t)q * MS, 0, sizeof(double) * MS);
-    }
-    if (winner[q] < 0) status[q] = DFTPAV_PLAN_NO_VALID_RESTART;
-  }
-  if (out->plan_status) std::memcpy(out->plan_status, status.data(), sizeof(int) * nq);
-  if (out->winner) std::memcpy(out->winner, winner.data(), sizeof(int) * nq);
-  if (out->n_seg) std::memcpy(out->n_seg, p->h_nseg.data(), sizeof(int) * nq);
-  if (out->singul) std::memcpy(out->singul, p->h_singul.data(), sizeof(int) * nq * MS);
-  if (out->piece_nums) std::memcpy(out->piece_nums, p->h_pn.data(), sizeof(int) * nq * MS);
-  if (out->piece_dt) std::memcpy(out->piece_dt, p->h_dt.data(), sizeof(double) * nq * MS);
-  if (out->search_status) std::memcpy(out->search_status, s_status, sizeof(int) * nq);
-  if (out->search_iters) std::memcpy(out->search_iters, s_iters, sizeof(int) * nq);
-  if (out->search_path_len) std::memcpy(out->search_path_len, s_len, sizeof(int) * nq);
-  // what dftpav_planner_adopt needs of this call (the winners' pieces stay where they are, in the arena)
-  p->last_status = status;
-  p->last_winner = winner;
-  p->last_goal.assign(end_states, end_states + 4 * nq);
-  p->last_MS = MS;
-  p->last_MP = MP;
-  p->last_Q = Q;
-  return DFTPAV_OK;
-}
-
-extern "C" int dftpav_debug_plan_select(dftpav_handle *h, int n_query, int n_restarts, const double *cost, const int *success,
-                                        const int *collision, int *winner_out) {
-  if (!h || n_query < 0 || n_restarts < 1 || (n_query > 0 && (!cost || !success || !collision || !winner_out))) return DFTPAV_E_INVALID;
-  if (n_query == 0) return DFTPAV_OK;
-  HIPCHK(h, hipSetDevice(h->device));
-  const size_t nt = (size_t)n_query * n_restarts;
-  double *d_cost = nullptr;
-  int *d_int = nullptr; // success | collision | winner
-  int rc = DFTPAV_OK;
-  auto chk = [&](hipError_t e) {
-    if (e != hipSuccess && rc == DFTPAV_OK) {
-      h->err = hipGetErrorString(e);
-      rc = DFTPAV_E_HIP;
-    }
-  };
-  chk(hipMalloc(&d_cost, sizeof(double) * nt));
-  chk(hipMalloc(&d_int, sizeof(int) * (2 * nt + n_query)));
-  if (rc == DFTPAV_OK) {
-    chk(hipMemcpyAsync(d_cost, cost, sizeof(double) * nt, hipMemcpyHostToDevice, h->stream));
-    chk(hipMemcpyAsync(d_int, success, sizeof(int) * nt, hipMemcpyHostToDevice, h->stream));
-    chk(hipMemcpyAsync(d_int + nt, collision, sizeof(int) * nt, hipMemcpyHostToDevice, h->stream));
-    PlanSelectArgs Z{};
-    Z.cost = d_cost;
-    Z.success = d_int;
-    Z.collision = d_int + nt;
-    Z.n_members = n_query;
-    Z.R = n_restarts;
-    Z.winner = d_int + 2 * nt;
-    chk(launch_plan_select(Z, h->stream));
-    chk(hipMemcpyAsync(winner_out, d_int + 2 * nt, sizeof(int) * n_query, hipMemcpyDeviceToHost, h->stream));
-    chk(hipStreamSynchronize(h->stream));
-  }
-  if (d_cost) (void)hipFree(d_cost);
-  if (d_int) (void)hipFree(d_int);
-  return rc;
-}
-
-// ------------------------------------------------- the replan loop: the executing table, its check and the tick (replan.hip)
-// TrajPlannerServer's 20 Hz loop (traj_server_ros.cpp:130-192, 359-501) for every slot of a planner at once.  The table lives in
-// device memory; the host mirrors what it needs to pack queries without a read-back: which slots are occupied, and their goals.
-extern "C" int dftpav_abi_sizeof_replan_out(void) { return (int)sizeof(dftpav_replan_out); }
-
-// the table, allocated (and zeroed: every slot empty) by the first call that fills it; later calls must bring the same padding
-static int exec_table(dftpav_planner *p, int MS, int MP) {
-  dftpav_handle *h = p->h;
-  if (MS < 1 || MS > kMaxSeg || MP < 1 || MP > 1024) return DFTPAV_E_INVALID;
-  if (p->d_exec) return (p->T.max_seg == MS && p->T.max_pieces == MP) ? DFTPAV_OK : DFTPAV_E_INVALID;
-  HIPCHK(h, hipSetDevice(h->device));
-  const size_t S = (size_t)p->max_queries, ms = (size_t)MS, mp = (size_t)MP;
-  ExecTable T{};
-  PubTable P{};
-  T.n_slots = p->max_queries;
-  T.max_seg = MS;
-  T.max_pieces = MP;
-  unsigned char *base = nullptr;
-  size_t used = 0;
-  for (int pass = 0; pass < 2; pass++) { // measure, then carve
-    used = 0;
-    auto take = [&](size_t bytes) {
-      void *r = pass ? (void *)(base + used) : nullptr;
-      used += (bytes + 255) / 256 * 256;
-      return r;
-    };
-    T.coeffs = (double *)take(sizeof(double) * S * ms * mp * 12);
-    T.coeff_dt = (double *)take(sizeof(double) * S * ms);
-    T.duration = (double *)take(sizeof(double) * S * ms);
-    T.start_time = (double *)take(sizeof(double) * S * ms);
-    T.end_time = (double *)take(sizeof(double) * S * ms);
-    T.end_state = (double *)take(sizeof(double) * S * 4);
-    T.hist = (double *)take(sizeof(double) * S * 2);
-    T.n_seg = (int *)take(sizeof(int) * S);
-    T.singul = (int *)take(sizeof(int) * S * ms);
-    T.piece_nums = (int *)take(sizeof(int) * S * ms);
-    T.have_hist = (int *)take(sizeof(int) * S);
-    P.hist = (double *)take(sizeof(double) * S * 2);
-    P.exe_index = (int *)take(sizeof(int) * S);
-    P.have = (int *)take(sizeof(int) * S);
-    if (pass == 0) {
-      HIPCHK(h, hipMalloc(&base, used));
-      if (hipMemsetAsync(base, 0, used, h->stream) != hipSuccess) {
-        (void)hipFree(base);
-        h->err = "dftpav_planner: hipMemsetAsync of the executing table";
-        return DFTPAV_E_HIP;
-      }
-    }
-  }
-  p->d_exec = base;
-  p->T = T;
-  p->P = P;
-  p->h_occupied.assign(S, 0);
-  p->h_goal.assign(4 * S, 0.0);
-  return DFTPAV_OK;
-}
-
-// slots [n]: each inside the table, none twice
-static bool slots_valid(const dftpav_planner *p, int n, const int *slots) {
-  std::vector<char> seen((size_t)p->max_queries, 0);
-  for (int i = 0; i < n; i++) {
-    if (slots[i] < 0 || slots[i] >= p->max_queries || seen[slots[i]]) return false;
-    seen[slots[i]] = 1;
-  }
-  return true;
-}
-
-extern "C" int dftpav_planner_install(dftpav_planner *p, int n, const int *slots, int max_seg, int max_pieces, const int *n_seg,
-                                      const int *singul, const int *piece_nums, const double *coeff_dt, const double *coeffs,
-                                      const double *end_states, double t_start) {
-  if (!p || n < 0 || n > p->max_queries) return DFTPAV_E_INVALID;
-  if (n > 0 && (!slots || !n_seg || !singul || !piece_nums || !coeff_dt || !coeffs || !end_states)) return DFTPAV_E_INVALID;
-  if (max_seg < 1 || max_seg > kMaxSeg || max_pieces < 1 || max_pieces > 1024) return DFTPAV_E_INVALID;
-  if (p->d_exec && (p->T.max_seg != max_seg || p->T.max_pieces != max_pieces)) return DFTPAV_E_INVALID;
-  if (!slots_valid(p, n, slots)) return DFTPAV_E_INVALID;
-  const size_t MS = (size_t)max_seg, MP = (size_t)max_pieces;
-  for (int i = 0; i < n; i++) {
-    if (n_seg[i] < 1 || n_seg[i] > max_seg) return DFTPAV_E_INVALID;
-    for (int j = 0; j < n_seg[i]; j++) {
-      const int N = piece_nums[(size_t)i * MS + j];
-      if (N < 1 || N > max_pieces) return DFTPAV_E_INVALID; // so the pieces of a plan fit its row of max_seg * max_pieces
-    }
-  }
-  if (int rc = exec_table(p, max_seg, max_pieces)) return rc;
-  if (n == 0) return DFTPAV_OK;
-  dftpav_handle *h = p->h;
-  HIPCHK(h, hipSetDevice(h->device));
-  const ExecTable &T = p->T;
-  std::vector<int> sg(MS), pn(MS);
-  std::vector<double> dtv(MS), dur(MS), st(MS), en(MS);
-  for (int i = 0; i < n; i++) {
-    const size_t s = (size_t)slots[i];
-    const int M = n_seg[i];
-    double world = t_start;
-    for (size_t j = 0; j < MS; j++) {
-      const bool used = (int)j < M;
-      sg[j] = used ? singul[(size_t)i * MS + j] : 0;
-      pn[j] = used ? piece_nums[(size_t)i * MS + j] : 0;
-      dtv[j] = used ? coeff_dt[(size_t)i * MS + j] : 0.0;
-      double d = 0.0; // Trajectory::getTotalDuration: the piece durations summed in order
-      for (int k = 0; k < pn[j]; k++) d += dtv[j];
-      dur[j] = used ? d : 0.0;
-      st[j] = used ? world : 0.0;          // traj_container.hpp:58-73: start_time, then end_time = start_time + duration
-      en[j] = used ? world + d : 0.0;
-      if (used) world = world + d;         // traj_manager.cpp:618-625: the next segment starts at that end
-    }
-    const int zero = 0;
-    const double hist0[2] = {0.0, 0.0};
-    // (pageable host memory: each copy has left its source when the call returns)
-    HIPCHK(h, hipMemcpyAsync(T.coeffs + s * MS * MP * 12, coeffs + (size_t)i * MS * MP * 12, sizeof(double) * MS * MP * 12, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(T.coeff_dt + s * MS, dtv.data(), sizeof(double) * MS, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(T.duration + s * MS, dur.data(), sizeof(double) * MS, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(T.start_time + s * MS, st.data(), sizeof(double) * MS, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(T.end_time + s * MS, en.data(), sizeof(double) * MS, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(T.end_state + s * 4, end_states + 4 * (size_t)i, sizeof(double) * 4, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(T.hist + s * 2, hist0, sizeof(double) * 2, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(T.singul + s * MS, sg.data(), sizeof(int) * MS, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(T.piece_nums + s * MS, pn.data(), sizeof(int) * MS, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(T.have_hist + s, &zero, sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(T.n_seg + s, &M, sizeof(int), hipMemcpyHostToDevice, h->stream));
-    // the publisher starts on segment 0 without control history
-    HIPCHK(h, hipMemsetAsync(p->P.exe_index + s, 0, sizeof(int), h->stream));
-    HIPCHK(h, hipMemsetAsync(p->P.have + s, 0, sizeof(int), h->stream));
-    HIPCHK(h, hipMemsetAsync(p->P.hist + s * 2, 0, sizeof(double) * 2, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream)); // the staging vectors are reused by the next plan
-    p->h_occupied[s] = M;
-    std::memcpy(&p->h_goal[4 * s], end_states + 4 * (size_t)i, sizeof(double) * 4);
-  }
-  return DFTPAV_OK;
-}
-
-// the winners of the last call into their slots; d_desired: the slots' new filter history, or nullptr for none
-static int adopt_impl(dftpav_planner *p, int n, const int *queries, const int *slots, double t_start, const double *d_desired, int *adopted) {
-  dftpav_handle *h = p->h;
-  if (p->last_Q <= 0) return DFTPAV_E_INVALID; // no call of dftpav_plan_queries to adopt from
-  if (!slots_valid(p, n, slots)) return DFTPAV_E_INVALID;
-  for (int i = 0; i < n; i++)
-    if (queries[i] < 0 || queries[i] >= p->last_Q) return DFTPAV_E_INVALID;
-  if (int rc = exec_table(p, p->last_MS, p->last_MP)) return rc;
-  std::vector<int> pairs, mode;
-  for (int i = 0; i < n; i++) {
-    const int q = queries[i];
-    const bool ok = p->last_status[q] == DFTPAV_PLAN_OK && p->last_winner[q] >= 0;
-    if (adopted) adopted[i] = ok ? 1 : 0;
-    if (!ok) continue;
-    pairs.push_back(q);
-    pairs.push_back(slots[i]);
-    // ctrl_state_hist_ outlives a replan; a first plan starts it from the tick's desired state (the ego state), or without one
-    mode.push_back(p->h_occupied[slots[i]] ? kPubKeep : (d_desired ? kPubSeed : kPubDrop));
-  }
-  const int na = (int)pairs.size() / 2;
-  if (na == 0) return DFTPAV_OK;
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipMemcpyAsync(p->d_pairs, pairs.data(), sizeof(int) * pairs.size(), hipMemcpyHostToDevice, h->stream));
-  ExecAdoptArgs A{};
-  A.T = p->T;
-  A.pairs = p->d_pairs;
-  A.n = na;
-  A.q_n_seg = p->fe.n_seg;
-  A.q_singul = p->fe.singul;
-  A.q_piece_nums = p->fe.piece_nums;
-  A.q_dt = p->d_wdt;
-  A.q_coeffs = p->d_wcoef;
-  A.q_goal = p->d_en;
-  A.desired = d_desired;
-  A.t_start = t_start;
-  HIPCHK(h, launch_exec_adopt(A, h->stream));
-  HIPCHK(h, hipMemcpyAsync(p->d_pub_mode, mode.data(), sizeof(int) * mode.size(), hipMemcpyHostToDevice, h->stream));
-  PubResetArgs R{};
-  R.P = p->P;
-  R.pairs = p->d_pairs;
-  R.mode = p->d_pub_mode;
-  R.n = na;
-  R.desired = d_desired;
-  HIPCHK(h, launch_pub_reset(R, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream)); // `pairs` and `mode` have left the host; the table is current when the call returns
-  for (int k = 0; k < na; k++) {
-    const int q = pairs[2 * k], s = pairs[2 * k + 1];
-    p->h_occupied[s] = p->h_nseg[q];
-    std::memcpy(&p->h_goal[4 * (size_t)s], &p->last_goal[4 * (size_t)q], sizeof(double) * 4);
-  }
-  return DFTPAV_OK;
-}
-
-// the device buffers of the check: outputs, inputs and the (query, slot) pairs of an adoption
-static int replan_buffers(dftpav_planner *p) {
-  if (p->d_rc) return DFTPAV_OK;
-  dftpav_handle *h = p->h;
-  HIPCHK(h, hipSetDevice(h->device));
-  const size_t S = (size_t)p->max_queries;
-  unsigned char *base = nullptr;
-  size_t used = 0;
-  for (int pass = 0; pass < 2; pass++) {
-    used = 0;
-    auto take = [&](size_t bytes) {
-      void *r = pass ? (void *)(base + used) : nullptr;
-      used += (bytes + 255) / 256 * 256;
-      return r;
-    };
-    p->d_rc_des = (double *)take(sizeof(double) * 8 * S);
-    p->d_rc_st = (double *)take(sizeof(double) * 4 * S);
-    p->d_rc_ct = (double *)take(sizeof(double) * 2 * S);
-    p->d_rc_goal = (double *)take(sizeof(double) * 4 * S);
-    p->d_rc_ego = (double *)take(sizeof(double) * 6 * S);
-    p->d_rc_tab = (double *)take(sizeof(double) * (4096 + 4096));
-    p->d_rc_int = (int *)take(sizeof(int) * kRcInts * S);
-    p->d_pairs = (int *)take(sizeof(int) * 2 * S);
-    p->d_pub_mode = (int *)take(sizeof(int) * S);
-    if (pass == 0) HIPCHK(h, hipMalloc(&base, used));
-  }
-  p->d_rc = base;
-  return DFTPAV_OK;
-}
-
-extern "C" int dftpav_planner_adopt(dftpav_planner *p, int n, const int *queries, const int *slots, double t_start, int *adopted) {
-  if (!p || n < 0 || n > p->max_queries || (n > 0 && (!queries || !slots))) return DFTPAV_E_INVALID;
-  if (p->d_exec && p->last_Q > 0 && (p->T.max_seg != p->last_MS || p->T.max_pieces != p->last_MP)) return DFTPAV_E_INVALID;
-  if (int rc = replan_buffers(p)) return rc;
-  return adopt_impl(p, n, queries, slots, t_start, nullptr, adopted);
-}
-
-extern "C" int dftpav_planner_set_history(dftpav_planner *p, int n, const int *slots, const double *stamps, const double *angles) {
-  if (!p || n < 0 || n > p->max_queries || (n > 0 && (!slots || !stamps || !angles))) return DFTPAV_E_INVALID;
-  if (!p->d_exec || !slots_valid(p, n, slots)) return DFTPAV_E_INVALID;
-  for (int i = 0; i < n; i++)
-    if (!p->h_occupied[slots[i]]) return DFTPAV_E_INVALID;
-  dftpav_handle *h = p->h;
-  HIPCHK(h, hipSetDevice(h->device));
-  const int one = 1;
-  for (int i = 0; i < n; i++) {
-    const double hv[2] = {stamps[i], angles[i]};
-    HIPCHK(h, hipMemcpyAsync(p->T.hist + 2 * (size_t)slots[i], hv, sizeof(hv), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(p->T.have_hist + slots[i], &one, sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  return DFTPAV_OK;
-}
-
-extern "C" int dftpav_planner_clear(dftpav_planner *p, int n, const int *slots) {
-  if (!p || n < 0 || n > p->max_queries || (n > 0 && !slots)) return DFTPAV_E_INVALID;
-  if (!slots_valid(p, n, slots)) return DFTPAV_E_INVALID;
-  if (!p->d_exec) return DFTPAV_OK; // nothing was ever installed: every slot is empty
-  dftpav_handle *h = p->h;
-  HIPCHK(h, hipSetDevice(h->device));
-  const ExecTable &T = p->T;
-  const size_t MS = (size_t)T.max_seg, MP = (size_t)T.max_pieces;
-  for (int i = 0; i < n; i++) {
-    const size_t s = (size_t)slots[i];
-    HIPCHK(h, hipMemsetAsync(T.n_seg + s, 0, sizeof(int), h->stream));
-    HIPCHK(h, hipMemsetAsync(T.have_hist + s, 0, sizeof(int), h->stream));
-    HIPCHK(h, hipMemsetAsync(T.singul + s * MS, 0, sizeof(int) * MS, h->stream));
-    HIPCHK(h, hipMemsetAsync(T.piece_nums + s * MS, 0, sizeof(int) * MS, h->stream));
-    HIPCHK(h, hipMemsetAsync(T.coeff_dt + s * MS, 0, sizeof(double) * MS, h->stream));
-    HIPCHK(h, hipMemsetAsync(T.duration + s * MS, 0, sizeof(double) * MS, h->stream));
-    HIPCHK(h, hipMemsetAsync(T.start_time + s * MS, 0, sizeof(double) * MS, h->stream));
-    HIPCHK(h, hipMemsetAsync(T.end_time + s * MS, 0, sizeof(double) * MS, h->stream));
-    HIPCHK(h, hipMemsetAsync(T.end_state + s * 4, 0, sizeof(double) * 4, h->stream));
-    HIPCHK(h, hipMemsetAsync(T.hist + s * 2, 0, sizeof(double) * 2, h->stream));
-    HIPCHK(h, hipMemsetAsync(T.coeffs + s * MS * MP * 12, 0, sizeof(double) * MS * MP * 12, h->stream));
-    HIPCHK(h, hipMemsetAsync(p->P.exe_index + s, 0, sizeof(int), h->stream));
-    HIPCHK(h, hipMemsetAsync(p->P.have + s, 0, sizeof(int), h->stream));
-    HIPCHK(h, hipMemsetAsync(p->P.hist + s * 2, 0, sizeof(double) * 2, h->stream));
-    p->h_occupied[s] = 0;
-    for (int k = 0; k < 4; k++) p->h_goal[4 * s + k] = 0.0;
-  }
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return DFTPAV_OK;
-}
-
-extern "C" int dftpav_planner_executing(dftpav_planner *p, int slot, int *n_seg, int *singul, int *piece_nums, double *coeff_dt,
-                                        double *coeffs, double *duration, double *start_time, double *end_time, double *end_state,
-                                        double *hist, int *have_hist) {
-  if (!p || slot < 0 || slot >= p->max_queries) return DFTPAV_E_INVALID;
-  if (!p->d_exec) { // nothing was ever installed: the slot is empty, and no padding is known to size the arrays by
-    if (n_seg) *n_seg = 0;
-    if (have_hist) *have_hist = 0;
-    return DFTPAV_OK;
-  }
-  dftpav_handle *h = p->h;
-  HIPCHK(h, hipSetDevice(h->device));
-  const ExecTable &T = p->T;
-  const size_t MS = (size_t)T.max_seg, MP = (size_t)T.max_pieces, s = (size_t)slot;
-  auto fetch = [&](void *dst, const void *src, size_t bytes) { return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess; };
-  HIPCHK(h, fetch(n_seg, T.n_seg + s, sizeof(int)));
-  HIPCHK(h, fetch(singul, T.singul + s * MS, sizeof(int) * MS));
-  HIPCHK(h, fetch(piece_nums, T.piece_nums + s * MS, sizeof(int) * MS));
-  HIPCHK(h, fetch(coeff_dt, T.coeff_dt + s * MS, sizeof(double) * MS));
-  HIPCHK(h, fetch(coeffs, T.coeffs + s * MS * MP * 12, sizeof(double) * MS * MP * 12));
-  HIPCHK(h, fetch(duration, T.duration + s * MS, sizeof(double) * MS));
-  HIPCHK(h, fetch(start_time, T.start_time + s * MS, sizeof(double) * MS));
-  HIPCHK(h, fetch(end_time, T.end_time + s * MS, sizeof(double) * MS));
-  HIPCHK(h, fetch(end_state, T.end_state + s * 4, sizeof(double) * 4));
-  HIPCHK(h, fetch(hist, T.hist + s * 2, sizeof(double) * 2));
-  HIPCHK(h, fetch(have_hist, T.have_hist + s, sizeof(int)));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return DFTPAV_OK;
-}
-
-extern "C" int dftpav_planner_padding(dftpav_planner *p, int *max_seg, int *max_pieces) {
-  if (!p) return DFTPAV_E_INVALID;
-  if (max_seg) *max_seg = p->d_exec ? p->T.max_seg : 0;
-  if (max_pieces) *max_pieces = p->d_exec ? p->T.max_pieces : 0;
-  return DFTPAV_OK;
-}
-
-// enqueues the check on the handle's stream (results stay in the planner's device buffers)
-static int replan_check_enqueue(dftpav_planner *p, double t_now, double budget, const double *end_states, const double *ego_states,
-                                double check_dt, double vertex_res) {
-  dftpav_handle *h = p->h;
-  if (!h->d_cells || !p->d_exec) return DFTPAV_E_INVALID; // no map; no table
-  if (!(check_dt > 0.0) || !(vertex_res > 0.0) || !(t_now == t_now) || !(budget == budget)) return DFTPAV_E_INVALID;
-  HIPCHK(h, hipSetDevice(h->device));
-  if (int rc = replan_buffers(p)) return rc;
-  const size_t S = (size_t)p->max_queries;
-  if (p->rc_dt != check_dt || p->rc_res != vertex_res) {
-    // the two running sums of the reference, tabulated (as dftpav_batch_validate): sample times | outline point spacing
-    std::vector<double> tab;
-    double t = 0.0;
-    for (int k = 0; k < 4096; k++, t += check_dt) tab.push_back(t);
-    const double longest = std::max(h->params.veh_length, h->params.veh_width) + 1.0;
-    for (double dl = vertex_res; dl < longest && tab.size() < 8192; dl += vertex_res) tab.push_back(dl);
-    if (tab.size() == 4096) tab.push_back(vertex_res);
-    if (tab.size() >= 8192) return DFTPAV_E_UNSUPPORTED; // an outline of 4096 points and more
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(p->d_rc_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
-    p->rc_n_t = 4096;
-    p->rc_n_v = (int)tab.size() - 4096;
-    p->rc_dt = check_dt;
-    p->rc_res = vertex_res;
-  }
-  if (end_states) HIPCHK(h, hipMemcpyAsync(p->d_rc_goal, end_states, sizeof(double) * 4 * S, hipMemcpyHostToDevice, h->stream));
-  if (ego_states) HIPCHK(h, hipMemcpyAsync(p->d_rc_ego, ego_states, sizeof(double) * 6 * S, hipMemcpyHostToDevice, h->stream));
-  ReplanArgs A{};
-  A.T = p->T;
-  A.cells = h->d_cells;
-  A.size_x = h->map.size_x;
-  A.size_y = h->map.size_y;
-  A.resolution = h->map.resolution;
-  A.origin_x = h->map.origin_x;
-  A.origin_y = h->map.origin_y;
-  A.veh_width = h->params.veh_width;
-  A.veh_length = h->params.veh_length;
-  A.veh_dcr = h->params.veh_d_cr;
-  A.wheel_base = h->params.veh_wheel_base;
-  A.t_tab = p->d_rc_tab;
-  A.n_t = p->rc_n_t;
-  A.sample_dt = check_dt;
-  A.v_tab = p->d_rc_tab + p->rc_n_t;
-  A.n_v = p->rc_n_v;
-  A.t_now = t_now;
-  A.budget = budget;
-  A.goals = end_states ? p->d_rc_goal : nullptr;
-  A.ego = ego_states ? p->d_rc_ego : nullptr;
-  A.o_int = p->d_rc_int;
-  A.desired = p->d_rc_des;
-  A.start_state = p->d_rc_st;
-  A.start_ctrl = p->d_rc_ct;
-  HIPCHK(h, hipEventRecord(p->rev[0], h->stream));
-  HIPCHK(h, launch_replan_check(A, h->stream));
-  HIPCHK(h, hipEventRecord(p->rev[1], h->stream));
-  p->check_timed = true;
-  return DFTPAV_OK;
-}
-
-// copies of the check's results for the caller (enqueued; the caller of this function waits for the stream)
-static int replan_check_fetch(dftpav_planner *p, const dftpav_replan_out *out) {
-  if (!out) return DFTPAV_OK;
-  dftpav_handle *h = p->h;
-  const size_t S = (size_t)p->max_queries;
-  auto fetch = [&](void *dst, const void *src, size_t bytes) { return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess; };
-  int *const io[kRcInts] = {out->occupied, out->complete, out->exe_index, out->is_close_turnpoint, out->is_near, out->target_moved,
-                            out->collision, out->first_sample, out->replan};
-  for (int k = 0; k < kRcInts; k++) HIPCHK(h, fetch(io[k], p->d_rc_int + (size_t)k * S, sizeof(int) * S));
-  HIPCHK(h, fetch(out->desired, p->d_rc_des, sizeof(double) * 8 * S));
-  HIPCHK(h, fetch(out->start_state, p->d_rc_st, sizeof(double) * 4 * S));
-  HIPCHK(h, fetch(out->start_ctrl, p->d_rc_ct, sizeof(double) * 2 * S));
-  return DFTPAV_OK;
-}
-
-extern "C" int dftpav_replan_check(dftpav_planner *p, double t_now, double budget, const double *end_states, const double *ego_states,
-                                   double check_dt, double vertex_res, const dftpav_replan_out *out) {
-  if (!p) return DFTPAV_E_INVALID;
-  dftpav_handle *h = p->h;
-  if (int rc = replan_check_enqueue(p, t_now, budget, end_states, ego_states, check_dt, vertex_res)) return rc;
-  if (int rc = replan_check_fetch(p, out)) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return DFTPAV_OK;
-}
-
-extern "C" int dftpav_replan_tick(dftpav_planner *p, const dftpav_plan_params *pp, double t_now, double budget, const double *end_states,
-                                  const double *ego_states, const dftpav_replan_out *check_out, int *query_slot, int *n_queries,
-                                  const dftpav_plan_out *plan_out) {
-  if (n_queries) *n_queries = 0;
-  if (!p || !pp) return DFTPAV_E_INVALID;
-  if (ego_states && !end_states) return DFTPAV_E_INVALID; // an empty slot has no stored goal
-  dftpav_handle *h = p->h;
-  // the padding of the plans to come must be the table's: checked before anything runs
-  if (p->d_exec && (p->T.max_seg != pp->max_seg || p->T.max_pieces != pp->max_pieces)) return DFTPAV_E_INVALID;
-  if (!p->d_exec) { // an all-empty table is a valid start (every vehicle waits for its first plan)
-    if (int rc = exec_table(p, pp->max_seg, pp->max_pieces)) return rc;
-  }
-  p->tick_timed = false;
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipEventRecord(p->rev[2], h->stream));
-  if (int rc = replan_check_enqueue(p, t_now, budget, end_states, ego_states, pp->check_dt, pp->vertex_res)) return rc;
-  // ---- the tick's one extra wait: replan, start_state, start_ctrl (with whatever else of the check the caller asked for)
-  const size_t S = (size_t)p->max_queries;
-  std::vector<int> flag(S, 0);
-  std::vector<double> st(4 * S), ct(2 * S);
-  HIPCHK(h, hipMemcpyAsync(flag.data(), p->d_rc_int + (size_t)kRcReplan * S, sizeof(int) * S, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(st.data(), p->d_rc_st, sizeof(double) * 4 * S, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(ct.data(), p->d_rc_ct, sizeof(double) * 2 * S, hipMemcpyDeviceToHost, h->stream));
-  if (int rc = replan_check_fetch(p, check_out)) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  // ---- the flagged slots, in rising slot order, are the queries
-  std::vector<int> slot_of;
-  std::vector<double> qs, qc, qe;
-  for (size_t s = 0; s < S; s++) {
-    if (!flag[s]) continue;
-    slot_of.push_back((int)s);
-    qs.insert(qs.end(), st.begin() + 4 * s, st.begin() + 4 * s + 4);
-    qc.insert(qc.end(), ct.begin() + 2 * s, ct.begin() + 2 * s + 2);
-    const double *g = end_states ? end_states + 4 * s : &p->h_goal[4 * s];
-    qe.insert(qe.end(), g, g + 4);
-  }
-  const int nq = (int)slot_of.size();
-  if (n_queries) *n_queries = nq;
-  if (query_slot)
-    for (int q = 0; q < nq; q++) query_slot[q] = slot_of[q];
-  if (nq > 0) {
-    static const dftpav_plan_out none{};
-    const double stamp = t_now + budget; // desired_state.time_stamp, traj_server_ros.cpp:414; `now` of the plan, traj_manager.cpp:520
-    if (int rc = dftpav_plan_queries(p, pp, qs.data(), qc.data(), qe.data(), nq, stamp, plan_out ? plan_out : &none)) return rc;
-    std::vector<int> qi(nq);
-    for (int q = 0; q < nq; q++) qi[q] = q;
-    if (int rc = adopt_impl(p, nq, qi.data(), slot_of.data(), stamp, p->d_rc_des, nullptr)) return rc;
-  }
-  HIPCHK(h, hipEventRecord(p->rev[3], h->stream));
-  p->tick_timed = true;
-  return DFTPAV_OK;
-}
-
-extern "C" int dftpav_replan_last_ms(dftpav_planner *p, float *check_ms, float *tick_ms) {
-  if (!p) return DFTPAV_E_INVALID;
-  dftpav_handle *h = p->h;
-  if (check_ms) *check_ms = 0.0f;
-  if (tick_ms) *tick_ms = 0.0f;
-  HIPCHK(h, hipSetDevice(h->device));
-  if (check_ms && p->check_timed) {
-    HIPCHK(h, hipEventSynchronize(p->rev[1]));
-    HIPCHK(h, hipEventElapsedTime(check_ms, p->rev[0], p->rev[1]));
-  }
-  if (tick_ms && p->tick_timed) {
-    HIPCHK(h, hipEventSynchronize(p->rev[3]));
-    HIPCHK(h, hipEventElapsedTime(tick_ms, p->rev[2], p->rev[3]));
-  }
-  return DFTPAV_OK;
-}
-
-// ------------------------------------------------- the publisher: PublishData (traj_server_ros.cpp:195-318) for every slot (replan.hip)
-extern "C" int dftpav_planner_publish(dftpav_planner *p, int K, const double *t, double *states, int *published) {
-  if (!p || !p->d_exec || !t || K < 1 || K > DFTPAV_PUBLISH_MAX_TICKS) return DFTPAV_E_INVALID;
-  for (int k = 0; k < K; k++)
-    if (!(t[k] == t[k])) return DFTPAV_E_INVALID;
-  dftpav_handle *h = p->h;
-  HIPCHK(h, hipSetDevice(h->device));
-  const size_t S = (size_t)p->max_queries;
-  for (auto &e : p->pev)
-    if (!e) HIPCHK(h, hipEventCreate(&e));
-  if ((size_t)K > p->pub_ticks) { // the clocks and the outputs of K ticks: one allocation, grown to the largest K met
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (p->d_pub) (void)hipFree(p->d_pub);
-    p->d_pub = nullptr;
-    p->pub_ticks = 0;
-    unsigned char *base = nullptr;
-    size_t used = 0;
-    for (int pass = 0; pass < 2; pass++) {
-      used = 0;
-      auto take = [&](size_t bytes) {
-        void *r = pass ? (void *)(base + used) : nullptr;
-        used += (bytes + 255) / 256 * 256;
-        return r;
-      };
-      p->d_pub_states = (double *)take(sizeof(double) * 8 * S * (size_t)K);
-      p->d_pub_t = (double *)take(sizeof(double) * (size_t)K);
-      p->d_pub_code = (int *)take(sizeof(int) * S * (size_t)K);
-      if (pass == 0) HIPCHK(h, hipMalloc(&base, used));
-    }
-    p->d_pub = base;
-    p->pub_ticks = (size_t)K;
-  }
-  p->pub_timed = false;
-  HIPCHK(h, hipMemcpyAsync(p->d_pub_t, t, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, h->stream));
-  PublishArgs A{};
-  A.T = p->T;
-  A.P = p->P;
-  A.K = K;
-  A.t = p->d_pub_t;
-  A.wheel_base = h->params.veh_wheel_base;
-  A.states = states ? p->d_pub_states : nullptr;
-  A.published = published ? p->d_pub_code : nullptr;
-  HIPCHK(h, hipEventRecord(p->pev[0], h->stream));
-  HIPCHK(h, launch_publish(A, h->stream));
-  HIPCHK(h, hipEventRecord(p->pev[1], h->stream));
-  p->pub_timed = true;
-  if (states) HIPCHK(h, hipMemcpyAsync(states, p->d_pub_states, sizeof(double) * 8 * S * (size_t)K, hipMemcpyDeviceToHost, h->stream));
-  if (published) HIPCHK(h, hipMemcpyAsync(published, p->d_pub_code, sizeof(int) * S * (size_t)K, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream)); // the one wait: `t` has left the host, the outputs have arrived
-  return DFTPAV_OK;
-}
-
-extern "C" int dftpav_planner_publisher_state(dftpav_planner *p, int slot, int *exe_index, double *hist, int *have_hist) {
-  if (!p || slot < 0 || slot >= p->max_queries) return DFTPAV_E_INVALID;
-  if (!p->d_exec) { // nothing was ever installed
-    if (exe_index) *exe_index = 0;
-    if (hist) hist[0] = hist[1] = 0.0;
-    if (have_hist) *have_hist = 0;
-    return DFTPAV_OK;
-  }
-  dftpav_handle *h = p->h;
-  HIPCHK(h, hipSetDevice(h->device));
-  const size_t s = (size_t)slot;
-  auto fetch = [&](void *dst, const void *src, size_t bytes) { return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess; };
-  HIPCHK(h, fetch(exe_index, p->P.exe_index + s, sizeof(int)));
-  HIPCHK(h, fetch(hist, p->P.hist + s * 2, sizeof(double) * 2));
-  HIPCHK(h, fetch(have_hist, p->P.have + s, sizeof(int)));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return DFTPAV_OK;
-}
-
-extern "C" int dftpav_planner_set_ctrl_history(dftpav_planner *p, int n, const int *slots, const double *stamps, const double *angles) {
-  if (!p || n < 0 || n > p->max_queries || (n > 0 && (!slots || !stamps || !angles))) return DFTPAV_E_INVALID;
-  if (!p->d_exec || !slots_valid(p, n, slots)) return DFTPAV_E_INVALID;
-  for (int i = 0; i < n; i++)
-    if (!p->h_occupied[slots[i]]) return DFTPAV_E_INVALID;
-  dftpav_handle *h = p->h;
-  HIPCHK(h, hipSetDevice(h->device));
-  const int one = 1;
-  for (int i = 0; i < n; i++) {
-    const double hv[2] = {stamps[i], angles[i]};
-    HIPCHK(h, hipMemcpyAsync(p->P.hist + 2 * (size_t)slots[i], hv, sizeof(hv), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(p->P.have + slots[i], &one, sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  return DFTPAV_OK;
-}
-
-extern "C" int dftpav_publish_last_ms(dftpav_planner *p, float *ms) {
-  if (!p || !ms) return DFTPAV_E_INVALID;
-  dftpav_handle *h = p->h;
-  *ms = 0.0f;
-  if (!p->pub_timed) return DFTPAV_OK;
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipEventSynchronize(p->pev[1]));
-  HIPCHK(h, hipEventElapsedTime(ms, p->pev[0], p->pev[1]));
   return DFTPAV_OK;
 }

@@ -1,0 +1,357 @@
+// capi_internal.h — what the host translation units behind libdftpav_hip.so share (capi*.cpp; no kernel file includes it): the
+// objects behind the C-ABI's opaque pointers, the kernels' launch functions, and the helpers that more than one unit calls.
+//   capi.cpp          parameters, handle, moving obstacles, batch create / upload / order / solve / results / trace
+//   capi_steps.cpp    the steps around a solve: restarts, resampling, shots, search, map, corridor, re-check, read-out, plan cycle
+//   capi_planner.cpp  dftpav_plan_queries, the executing table, the replan check / tick, the publisher
+//   capi_comm.cpp     RCCL                capi_wire.cpp     the "DPTJ" serialisation
+// There is deliberately no CPU fallback: without a usable HIP device every entry point that needs one fails with DFTPAV_E_NO_DEVICE.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cmath>
+#include <cstdio>
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/dftpav_hip.h"
+#include "device_types.h"
+#include "e4_plan.h"
+#include "traj_math.h"
+#include "cr_trig.h"
+#include "rs_math.h"
+#include "search_args.h"
+#include "plan_args.h"
+
+namespace dftpav {
+hipError_t launch_solver(const DevBatch &D, const DevBatch *d_dev, int mode, int threads, int grid, SchedArgs sched,
+                         hipStream_t stream);
+hipError_t launch_corridor(const unsigned char *cells, const unsigned *bits, int size_x, int size_y, double resolution, double origin_x, double origin_y,
+                           const double *states, int n, double veh_width, double veh_length, double veh_dcr, const double *dl,
+                           int n_dl, double *hpoly, double *batch_cor, int Npts, int NptsPad, int replicate, hipStream_t stream);
+hipError_t launch_frontend(const dftpav_frontend_params &fp, const double *paths, const int *path_len, int max_path,
+                           const double *start_states, const double *end_states, const double *start_ctrl, int n_hyp,
+                           const dftpav_frontend_out &out, hipStream_t stream);
+hipError_t launch_restarts(const double *inner, const double *durs, int n_hyp, int n_restarts, int n_inner, int M, double sigma,
+                           double lo, double hi, unsigned long long seed, double *out_inner, double *out_durs, hipStream_t stream);
+hipError_t launch_fit(const double *states, int S, int n_states, const double *opM, double *dur, double *coef, double *total,
+                      double *start, hipStream_t stream);
+hipError_t launch_validate(const unsigned char *cells, int size_x, int size_y, double resolution, double origin_x, double origin_y,
+                           const double *coeffs, const double *piece_dt, const DevLayout &L, int B, double veh_width,
+                           double veh_length, double veh_dcr, const double *t_tab, int n_t, double sample_dt, const double *v_tab,
+                           int n_v, int *collision, int *first_sample, hipStream_t stream);
+hipError_t launch_states(const double *coeffs, const double *piece_dt, const DevLayout &L, int B, double wheel_base, double t0,
+                         double sample_dt, int n_samples, int filter, double *states, int *n_valid, hipStream_t stream);
+hipError_t launch_shots(const double *from, const double *to, int n, double rho, double checkl, int max_samples,
+                        const unsigned char *cells, int size_x, int size_y, double resolution, double origin_x, double origin_y,
+                        double veh_width, double veh_length, double veh_dcr, const double *v_tab, int n_v, double *length, int *type,
+                        double *seg, double *samples, int *n_samples, int *collides, hipStream_t stream);
+hipError_t launch_search(const SearchArgs &A, int blocks, hipStream_t stream);
+// plan.hip: the kernels between the stages of dftpav_plan_queries
+hipError_t launch_plan_paths(const int *status, const int *path_len, const int *skip, int n, int max_path, double *paths, int *fe_len,
+                             hipStream_t stream);
+hipError_t launch_plan_pack(const PlanPackArgs &A, hipStream_t stream);
+hipError_t launch_plan_select(const PlanSelectArgs &A, hipStream_t stream);
+hipError_t launch_replan_check(const ReplanArgs &A, hipStream_t stream);
+hipError_t launch_exec_adopt(const ExecAdoptArgs &A, hipStream_t stream);
+hipError_t launch_publish(const PublishArgs &A, hipStream_t stream);
+hipError_t launch_pub_reset(const PubResetArgs &A, hipStream_t stream);
+hipError_t launch_corridor_layout(const double *raw, double *out, int B, int Npts, int H, int NptsPad, hipStream_t stream);
+hipError_t launch_adopt(const DevBatch &D, const DevBatch &prev, hipStream_t stream);
+// solver_ref.hip: the same path in the reference's own floating-point order
+bool reference_order_supported(const DevLayout &L, const DevParams &P, int S);
+size_t reference_order_scratch_doubles(const DevLayout &L, int B, int S);
+size_t reference_order_table_doubles(int N);
+void reference_order_pack_tables(int N, const double *full, double *packed);
+int reference_order_interior_mask(int sweep, int row_mod_6);
+RefPlan reference_order_plan(const DevLayout &L, const DevParams &P, int S, int B, int n_cu, bool throughput, const RefOptions &o);
+hipError_t launch_ring_reset(const DevBatch &D, hipStream_t stream);
+hipError_t launch_solver_ref(const DevBatch &D, const DevBatch *d_dev, int mode, const double *tabs, double *scratch, const RefPlan &pl, int scheduled,
+                             hipStream_t stream);
+hipError_t launch_solver_quad(const DevBatch &D, const DevBatch *d_dev, int mode, const double *tabs, const double *cor_t, bool rect, double *scratch,
+                              const RefPlan &pl, int scheduled, bool alone, hipStream_t stream);
+// the QUAD shapes' copy of the corridor (solver_ref4.hip: one gear segment, solver_ref4m.hip: several)
+size_t reference_order_quad_corridor_doubles(const DevLayout &L, int B);
+hipError_t launch_quad_corridor(const DevBatch &D, double *cor_t, bool rect, hipStream_t stream);
+hipError_t launch_quad_rect_check(const double *corridor, int B, int Npts, int NptsPad, int *d_flag, hipStream_t stream);
+hipError_t launch_quadm_corridor(const DevBatch &D, double *cor_t, hipStream_t stream);
+}
+using namespace dftpav;
+
+struct CommShared; // capi_comm.cpp: an RCCL communicator and its holders
+
+struct dftpav_handle {
+  dftpav_params params;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  std::string err;
+  // moving obstacles (device copies)
+  int S = 0;
+  int sur_pieces = 0; // pieces of all obstacles together
+  int sur_version = 0; // bumped by dftpav_set_surround so batches refresh their device descriptor
+  int *d_sur_off = nullptr;
+  double *d_sur_dur = nullptr, *d_sur_coef = nullptr, *d_sur_total = nullptr, *d_sur_start = nullptr, *d_sur_theta = nullptr, *d_sur_bbox = nullptr;
+  // obstacle map of the corridor generator (device copy) and the table of sample offsets along a line
+  dftpav_grid_map map{};
+  unsigned char *d_cells = nullptr;
+  unsigned *d_bits = nullptr; // one bit per cell, when the whole map fits in a quarter of the LDS
+  double *d_dl = nullptr;
+  int n_dl = 0;
+  hipEvent_t cev0 = nullptr, cev1 = nullptr; // around the last corridor kernel
+  hipEvent_t mark[2] = {nullptr, nullptr};   // dftpav_mark
+  bool ctimed = false;
+  std::vector<struct dftpav_batch *> batches; // every live batch of this handle (obstacle changes finish their chained stragglers)
+  // RCCL communicator of dftpav_comm_create (one rank per handle = per GPU), and the staging block of this rank's records
+  void *comm = nullptr;
+  struct CommShared *comm_ref = nullptr; // the communicator's holders (dftpav_comm_share): destroyed when the last one lets go
+  int comm_ranks = 0, comm_rank = 0;
+  unsigned char *d_comm_send = nullptr;
+  size_t comm_send_bytes = 0;
+  // workspace of dftpav_kino_search (node pools, heaps, hash tables of the queries in flight), grown on demand
+  void *d_search_ws = nullptr;
+  size_t search_ws_bytes = 0;
+};
+
+struct dftpav_batch {
+  dftpav_handle *h = nullptr;
+  int B = 0;
+  int n_active = 0; // dftpav_plan_queries: the leading trajectories in use this call (0: all B); the kernels see it as the batch size
+  DevLayout L{};
+  DevParams P{};
+  int threads = 0;
+  bool op_in_lds = false, cor_in_lds = false;
+  bool have_corridor = false; // set by dftpav_batch_upload (host corridor) or dftpav_batch_corridor_from_states
+  // time-sliced scheduling (batches larger than the device holds at once): the queue launch runs in the
+  // shape above, the stragglers it hands over finish in the latency shape below
+  bool sched = false;
+  int slots = 0, slice = 0, hand_over = 0;
+  int threads2 = 0;
+  bool op_in_lds2 = false, cor_in_lds2 = false;
+  int *d_queue = nullptr, *d_stragglers = nullptr, *d_stragglers2 = nullptr, *d_sflag = nullptr, *d_iota = nullptr;
+  int qcap = 0;
+  bool pending = false; // a chained solve left this batch's stragglers for the next chained solve (or dftpav_batch_finish)
+  unsigned *d_qctl = nullptr;
+  double *d_state = nullptr;
+  DevBatch *d_dev2 = nullptr;
+  // E4 lane plans (e4_plan.h) of the two launch shapes: host copies of the sizes, device tables
+  E4Sizes e4{}, e4b{};
+  int *d_e4[2][5] = {{nullptr, nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr, nullptr}}; // gtab, ltab, wave, round, piece
+  int NptsPad = 0;
+  std::vector<double> x0_host;
+  bool uploaded = false;
+  double t_now = 0.0, epis = 0.0;
+  // device buffers
+  double *d_x0 = nullptr, *d_iniS = nullptr, *d_finS = nullptr, *d_corridor = nullptr;
+  int16_t *d_pt_piece = nullptr, *d_pt_j = nullptr;
+  double *d_opM[kMaxSeg] = {nullptr}, *d_opMT[kMaxSeg] = {nullptr};
+  double *d_histS = nullptr, *d_histY = nullptr, *d_histU = nullptr, *d_histV = nullptr, *d_histR = nullptr;
+  double *d_histM = nullptr; // QUAD shape of the reference order: the mirrored ends of the history rings (DevBatch::histM)
+  double *d_x_in = nullptr, *d_x_out = nullptr, *d_f = nullptr, *d_g = nullptr;
+  int *d_status = nullptr, *d_success = nullptr, *d_iters = nullptr, *d_evals = nullptr;
+  long long *d_hist = nullptr, *d_ticks = nullptr, *d_prof = nullptr;
+  unsigned char *d_records = nullptr; // [B + 1][16] result records written by the solver's epilogue (+ one zero record of padding)
+  unsigned char *h_records = nullptr; // [B][16] the same in pinned host memory, written by the epilogues too (DevBatch::records_host)
+  DevBatch *d_dev = nullptr; // device copy of the launch descriptor
+  int dev_version = -1;
+  // pinned host staging of the two descriptors and the event behind their last copy: refreshing the device copies then
+  // needs no stream synchronisation (dftpav_plan_cycle enqueues the corridor kernel in front of the solve and must not wait for it)
+  DevBatch *h_stage = nullptr;
+  hipEvent_t stage_ev = nullptr;
+  bool stage_busy = false;
+  bool prof_on = false;
+  double *d_coef = nullptr, *d_dt = nullptr;
+  double *d_f_eval = nullptr; // costs of dftpav_batch_eval (kept apart from the solve's final costs)
+  double *d_trace = nullptr;  // dftpav_batch_trace
+  double *d_cor_raw = nullptr; // the caller's hPoly columns as uploaded (normalised and laid out on the device)
+  // dftpav_batch_set_order(DFTPAV_ORDER_REFERENCE): the substitution tables of the band system and the term records (solver_ref.hip)
+  int order = DFTPAV_ORDER_DEVICE;
+  int ref_S = 0; // moving obstacles on the handle when the reference order was chosen (the term records are sized for them)
+  double *d_ref_tab = nullptr, *d_ref_scratch = nullptr;
+  RefPlan ref_plan{}; // its launch plan (chosen with the order)
+  double *d_cor_t = nullptr; // QUAD shapes: the corridor as [B][4 H][Kmax + 1][16] (solver_ref4.hip), refreshed when the corridor changes
+  bool cor_t_dirty = true;
+  // Rectangles (solver_ref4.hip: RECT).  cor_rect: every corridor in d_corridor is known to be one -- learned by dftpav_batch_upload,
+  // which waits for the device anyway; the corridors the device makes from the map (dftpav_batch_corridor_from_hypotheses,
+  // dftpav_plan_cycle: no wait, none added) leave it false and run the sixteen-double layout.  cor_t_rect: the layout d_cor_t is in.
+  bool cor_rect = false, cor_t_rect = false;
+  int *d_rect_flag = nullptr;
+  bool coef_override = false; // test hook dftpav_debug_batch_set_coeffs: validate / sample_states take the coefficients as they are
+  int residency = -1; // the caller's residency hint (dftpav_batch_create_shaped); 2 = many such batches in flight: the throughput shapes whatever B
+  // dftpav_plan_cycle: work buffers that live from the call to dftpav_plan_cycle_fetch (reused by the next cycle)
+  struct PlanCycle {
+    double *d_poses = nullptr, *d_tab = nullptr, *d_rd = nullptr; // d_tab: the validation_table of the re-check
+    int *d_col = nullptr, *d_first = nullptr, *d_valid = nullptr;
+    size_t n_poses = 0, n_tab = 0, n_rd = 0;
+    std::vector<double> poses, tab; // host sources of the asynchronous copies
+    int n_samples = 0;
+    bool in_flight = false;
+  } pc;
+  int trace_b = -1, trace_cap = 0, trace_n = 0;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  bool timed = false;  // a solve was enqueued: ev0 / ev1 are recorded
+  bool solved = false; // results of a solve of the CURRENT inputs exist (cleared by dftpav_batch_upload)
+};
+
+#define HIPCHK(h, call)                                                                  \
+  do {                                                                                   \
+    hipError_t e_ = (call);                                                              \
+    if (e_ != hipSuccess) {                                                              \
+      (h)->err = std::string(#call) + ": " + hipGetErrorString(e_);                      \
+      return DFTPAV_E_HIP;                                                               \
+    }                                                                                    \
+  } while (0)
+
+// What a launch of the search needs besides the queries and the outputs: the checked parameters, the tables of the running sums
+// (inputs, outline point spacing, shot sample offsets; `tabs` is their host copy, in_tab | v_tab | l_tab) and the handle's
+// workspace for `slots` queries in flight.  Shared by dftpav_kino_search and dftpav_plan_queries.
+struct SearchSetup {
+  SearchArgs S{};
+  std::vector<double> tabs;
+  size_t n_in_tab = 0, n_vv = 0, n_ll = 0;
+  int slots = 0;
+};
+
+struct dftpav_planner {
+  dftpav_handle *h = nullptr;
+  int max_queries = 0, R = 0;
+  struct Entry {
+    std::vector<int> key; // M, singul[M], piece_nums[M]
+    dftpav_batch *b;
+  };
+  std::vector<Entry> cache; // one batch per layout met so far
+  // device work buffers: one allocation, carved up for the paddings of the last call (kept while they do not change)
+  unsigned char *d_arena = nullptr;
+  size_t arena_bytes = 0;
+  long long sig[6] = {0, 0, 0, 0, 0, 0}; // max_seg, max_pieces, max_path, max_states, doubles of the search tables, of the validation tables
+  double *d_st = nullptr, *d_en = nullptr, *d_ct = nullptr, *d_tabs = nullptr, *d_paths = nullptr, *d_vt = nullptr;
+  int *d_skip = nullptr, *d_sints = nullptr, *d_fe_len = nullptr, *d_members = nullptr, *d_minit = nullptr, *d_col = nullptr, *d_first = nullptr;
+  dftpav_frontend_out fe{}; // device pointers
+  double *d_poses = nullptr;
+  size_t fe_zero_bytes = 0; // the front-end outputs are one stretch of the arena, zeroed per call (as dftpav_frontend_resample does)
+  unsigned char *d_fe0 = nullptr;
+  // compact outputs (zeroed per call): one stretch too
+  unsigned char *d_out0 = nullptr;
+  size_t out_zero_bytes = 0;
+  int *d_winner = nullptr, *d_witers = nullptr, *d_rint[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  double *d_wcost = nullptr, *d_wx = nullptr, *d_wcoef = nullptr, *d_wdt = nullptr, *d_rcost = nullptr;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool timed = false;
+  std::vector<int> group_sizes;
+  // host staging of the tables that decide the grouping
+  std::vector<int> h_sints, h_nseg, h_singul, h_pn, h_nstates, h_skip, h_members, h_minit;
+  std::vector<double> h_dt, h_vt;
+  // ---- the replan loop (dftpav_planner_install ... dftpav_replan_tick)
+  // what the last dftpav_plan_queries call left behind for dftpav_planner_adopt: its size and paddings, per query the final
+  // plan_status and winner, and the goals
+  int last_Q = 0, last_MS = 0, last_MP = 0;
+  std::vector<int> last_status, last_winner;
+  std::vector<double> last_goal;
+  // the executing table: one allocation of its own (the arena above is carved again when the paddings of a call change)
+  unsigned char *d_exec = nullptr;
+  ExecTable T{};
+  std::vector<int> h_occupied;  // host mirror: n_seg of every slot
+  std::vector<double> h_goal;   // host mirror: the stored goals [slots][4]
+  // outputs of the check, its two tables and its inputs: one allocation
+  unsigned char *d_rc = nullptr;
+  int *d_rc_int = nullptr, *d_pairs = nullptr;
+  double *d_rc_des = nullptr, *d_rc_st = nullptr, *d_rc_ct = nullptr, *d_rc_goal = nullptr, *d_rc_ego = nullptr, *d_rc_tab = nullptr;
+  int rc_n_t = 0, rc_n_v = 0;
+  double rc_dt = 0.0, rc_res = 0.0; // what d_rc_tab was tabulated for
+  hipEvent_t rev[4] = {nullptr, nullptr, nullptr, nullptr}; // check start / end, tick start / end
+  bool check_timed = false, tick_timed = false;
+  // ---- the publisher (dftpav_planner_publish): its state per slot lives in d_exec beside the table; clocks and outputs grow on demand
+  PubTable P{};
+  int *d_pub_mode = nullptr; // [slots] of d_rc: what an adoption does to the control history of each adopted pair
+  unsigned char *d_pub = nullptr;
+  size_t pub_ticks = 0; // d_pub holds the clocks and outputs of this many ticks
+  double *d_pub_t = nullptr, *d_pub_states = nullptr;
+  int *d_pub_code = nullptr;
+  hipEvent_t pev[2] = {nullptr, nullptr};
+  bool pub_timed = false;
+};
+
+namespace dftpav {
+// ---- capi.cpp
+int finish_pending(dftpav_batch *b);                          // finishes the stragglers a chained solve left suspended (no-op otherwise)
+int solve_impl(dftpav_batch *b, dftpav_batch *prev, bool chained);
+int sync_dev(dftpav_batch *b, DevBatch &D);                   // refreshes the device copy of the launch descriptor
+hipError_t launch_for(dftpav_batch *b, const DevBatch &D, int mode);
+void fill_dev_layout(const dftpav_layout &layout, int K, int Kd, DevLayout &L);
+void fill_dev_params(const dftpav_params &p, DevParams &P);
+// ---- capi_steps.cpp
+int search_setup(dftpav_handle *h, const dftpav_search_params *sp, int n, SearchSetup &U);
+// the outputs of a search wired into U.S: the tables in d_tabs (in_tab | v_tab | l_tab), the queries, the eight int rows [n] of d_ints
+// in the order of dftpav_search_out, and the node / path lists (null with a padding of 0)
+void wire_search(SearchSetup &U, double *d_tabs, double *d_start, double *d_end, int *d_ints, size_t n, int max_nodes, double *d_nodes,
+                 int max_path, double *d_paths);
+// The two running sums of the collision re-check, tabulated into `tab`: 4096 sample times t += check_dt from 0.0
+// (traj_server_ros.cpp:387), then the spacings of the outline points dl += vertex_res while dl < max(veh_length, veh_width) + 1.0
+// (shapes.cc:128), one entry vertex_res if that leaves none.  max_spacings > 0: DFTPAV_E_UNSUPPORTED where that many or more are needed.
+int validation_table(const dftpav_params &p, double check_dt, double vertex_res, int max_spacings, std::vector<double> &tab, int *n_t, int *n_v);
+// rectangles of n_poses poses (device) from the handle's map into the batch's corridor, each `replicate` times.  Nothing waits for the
+// device: the batch keeps the sixteen-double layout (dftpav_batch::cor_rect)
+int corridor_into_batch(dftpav_batch *b, const double *d_poses, int n_poses, int replicate);
+// coefficients and piece durations of the solutions, regenerated on the device from x (unless the test hook overrode them)
+int ensure_coeffs(dftpav_batch *b, DevBatch &D);
+// the collision re-check of the first n_traj trajectories against the handle's map; d_tab: a validation_table on the device
+int validate_on_stream(dftpav_batch *b, int n_traj, const double *d_tab, int n_t, int n_v, double check_dt, int *d_col, int *d_first);
+
+// One allocation for many arrays, measured and carved by the same list: fields(take) names every array in order, take(bytes) is its
+// address -- null while `base` is null, the measuring pass -- and advances by the size rounded up to 256 bytes.  Returns the bytes used.
+template <class F> size_t carve(unsigned char *base, F &&fields) {
+  size_t used = 0;
+  auto take = [&](size_t bytes) {
+    void *r = base ? (void *)(base + used) : nullptr;
+    used += (bytes + 255) / 256 * 256;
+    return r;
+  };
+  fields(take);
+  return used;
+}
+
+// The temporary device buffers of one call.  They are freed when the call ends, after a wait for the handle's stream: whatever the
+// call enqueued -- a copy into the caller's memory included -- has ended by then, on the error paths too.
+struct DevScratch {
+  dftpav_handle *h;
+  std::vector<void *> ptrs;
+  explicit DevScratch(dftpav_handle *h_) : h(h_) {}
+  DevScratch(const DevScratch &) = delete;
+  DevScratch &operator=(const DevScratch &) = delete;
+  ~DevScratch() {
+    if (ptrs.empty()) return;
+    (void)hipStreamSynchronize(h->stream);
+    for (void *p : ptrs) (void)hipFree(p);
+  }
+  hipError_t alloc_bytes(void **p, size_t bytes) {
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) ptrs.push_back(*p);
+    else *p = nullptr;
+    return e;
+  }
+  template <class T> hipError_t alloc(T *&p, size_t n) {
+    void *v = nullptr;
+    const hipError_t e = alloc_bytes(&v, sizeof(T) * n);
+    p = (T *)v;
+    return e;
+  }
+  void keep() { ptrs.clear(); } // the buffers now belong to the caller
+};
+
+// a copy to the host on the handle's stream, unless the caller did not ask for that output
+inline hipError_t fetch_async(dftpav_handle *h, void *dst, const void *src, size_t bytes) {
+  return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
+}
+
+// a work buffer that lives from call to call: reallocated only when it is too small (contents are not kept)
+template <class T> int grow(dftpav_handle *h, T *&p, size_t &have, size_t want) {
+  if (have >= want && p) return DFTPAV_OK;
+  if (p) HIPCHK(h, hipFree(p));
+  p = nullptr;
+  HIPCHK(h, hipMalloc(&p, sizeof(T) * want));
+  have = want;
+  return DFTPAV_OK;
+}
+} // namespace dftpav

@@ -1,0 +1,684 @@
+// capi_steps.cpp — the steps of a planning cycle around the solve, each a service of its own and chained on the stream by
+// dftpav_plan_cycle: restarts, front-end resampling, Reeds-Shepp shots, the hybrid A* search, the map and its corridors, the
+// collision re-check, the state read-out.
+#include "capi_internal.h"
+
+extern "C" int dftpav_sample_restarts(dftpav_handle *h, const double *inner_pts, const double *durations, int n_hyp, int n_restarts,
+                                      int n_inner, int M, double sigma, double dur_lo, double dur_hi, unsigned long long seed,
+                                      double *out_inner_pts, double *out_durations) {
+  if (!h || !inner_pts || !durations || !out_inner_pts || !out_durations || n_hyp < 0 || n_restarts < 1 || n_inner < 0 ||
+      (n_inner & 1) || M < 1 || !(sigma >= 0.0) || !(dur_lo > 0.0) || !(dur_hi >= dur_lo))
+    return DFTPAV_E_INVALID;
+  if (n_hyp == 0) return DFTPAV_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t B = (size_t)n_hyp * n_restarts;
+  double *d_in = nullptr, *d_du = nullptr, *d_oi = nullptr, *d_od = nullptr;
+  DevScratch tmp(h);
+  HIPCHK(h, tmp.alloc(d_in, std::max<size_t>(1, (size_t)n_hyp * n_inner)));
+  HIPCHK(h, tmp.alloc(d_du, (size_t)n_hyp * M));
+  HIPCHK(h, tmp.alloc(d_oi, std::max<size_t>(1, B * n_inner)));
+  HIPCHK(h, tmp.alloc(d_od, B * M));
+  HIPCHK(h, hipMemcpyAsync(d_in, inner_pts, sizeof(double) * (size_t)n_hyp * n_inner, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_du, durations, sizeof(double) * (size_t)n_hyp * M, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, launch_restarts(d_in, d_du, n_hyp, n_restarts, n_inner, M, sigma, dur_lo, dur_hi, seed, d_oi, d_od, h->stream));
+  HIPCHK(h, hipMemcpyAsync(out_inner_pts, d_oi, sizeof(double) * B * n_inner, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(out_durations, d_od, sizeof(double) * B * M, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_frontend_resample(dftpav_handle *h, const dftpav_frontend_params *fp, const double *paths, const int *path_len,
+                                        int max_path, const double *start_states, const double *end_states,
+                                        const double *start_ctrl, int n_hyp, const dftpav_frontend_out *out) {
+  if (!h || !fp || !paths || !path_len || !start_states || !end_states || !start_ctrl || !out || n_hyp < 0 || max_path < 2)
+    return DFTPAV_E_INVALID;
+  if (out->max_seg < 1 || out->max_seg > 16 || out->max_pieces < 2 || out->max_states < 1) return DFTPAV_E_UNSUPPORTED;
+  if (fp->traj_res < 1 || fp->dense_traj_res < 1 || !(fp->piece_duration > 0.0)) return DFTPAV_E_INVALID;
+  for (int i = 0; i < n_hyp; i++)
+    if (path_len[i] < 2 || path_len[i] > max_path) return DFTPAV_E_INVALID;
+  if (n_hyp == 0) return DFTPAV_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t nh = (size_t)n_hyp, MS = (size_t)out->max_seg, MP = (size_t)out->max_pieces, MST = (size_t)out->max_states;
+  struct Buf {
+    void **dev;
+    const void *src; // host input (nullptr for outputs)
+    void *dst;       // host output
+    size_t bytes;
+  };
+  double *d_paths = nullptr, *d_ss = nullptr, *d_es = nullptr, *d_sc = nullptr;
+  int *d_len = nullptr;
+  dftpav_frontend_out D = *out; // device pointers below
+  D.n_seg = nullptr; D.singul = nullptr; D.piece_nums = nullptr; D.piece_dt = nullptr; D.ini_states = nullptr;
+  D.fin_states = nullptr; D.inner_pts = nullptr; D.n_states = nullptr; D.states = nullptr;
+  Buf bufs[] = {
+      {(void **)&d_paths, paths, nullptr, sizeof(double) * nh * max_path * 3},
+      {(void **)&d_len, path_len, nullptr, sizeof(int) * nh},
+      {(void **)&d_ss, start_states, nullptr, sizeof(double) * nh * 4},
+      {(void **)&d_es, end_states, nullptr, sizeof(double) * nh * 4},
+      {(void **)&d_sc, start_ctrl, nullptr, sizeof(double) * nh * 2},
+      {(void **)&D.n_seg, nullptr, out->n_seg, sizeof(int) * nh},
+      {(void **)&D.singul, nullptr, out->singul, sizeof(int) * nh * MS},
+      {(void **)&D.piece_nums, nullptr, out->piece_nums, sizeof(int) * nh * MS},
+      {(void **)&D.piece_dt, nullptr, out->piece_dt, sizeof(double) * nh * MS},
+      {(void **)&D.ini_states, nullptr, out->ini_states, sizeof(double) * nh * MS * 6},
+      {(void **)&D.fin_states, nullptr, out->fin_states, sizeof(double) * nh * MS * 6},
+      {(void **)&D.inner_pts, nullptr, out->inner_pts, sizeof(double) * nh * MS * (MP - 1) * 2},
+      {(void **)&D.n_states, nullptr, out->n_states, sizeof(int) * nh * MS},
+      {(void **)&D.states, nullptr, out->states, sizeof(double) * nh * MS * MST * 3},
+  };
+  DevScratch tmp(h);
+  for (Buf &b : bufs) {
+    if (!b.src && !b.dst) return DFTPAV_E_INVALID;
+    HIPCHK(h, tmp.alloc_bytes(b.dev, b.bytes));
+    if (b.src) HIPCHK(h, hipMemcpyAsync(*b.dev, b.src, b.bytes, hipMemcpyHostToDevice, h->stream));
+    else HIPCHK(h, hipMemsetAsync(*b.dev, 0, b.bytes, h->stream));
+  }
+  HIPCHK(h, launch_frontend(*fp, d_paths, d_len, max_path, d_ss, d_es, d_sc, n_hyp, D, h->stream));
+  for (Buf &b : bufs)
+    if (b.dst) HIPCHK(h, hipMemcpyAsync(b.dst, *b.dev, b.bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return DFTPAV_OK;
+}
+
+// ------------------------------------------------- Reeds-Shepp shots
+extern "C" int dftpav_reeds_shepp_shots(dftpav_handle *h, const double *from, const double *to, int n, double max_cur,
+                                        double checkl, int max_samples, double vertex_res, double *length, int *type, double *seg,
+                                        double *samples, int *n_samples, int *collides) {
+  if (!h || n < 0 || !(max_cur > 0.0) || !(checkl > 0.0) || max_samples < 1 || max_samples > 4096) return DFTPAV_E_INVALID;
+  if (n == 0) return DFTPAV_OK;
+  if (!from || !to) return DFTPAV_E_INVALID;
+  if (collides && (!h->d_cells || !(vertex_res > 0.0))) return DFTPAV_E_INVALID; // a collision check needs the map
+  HIPCHK(h, hipSetDevice(h->device));
+  if (!h->cev0) HIPCHK(h, hipEventCreate(&h->cev0));
+  if (!h->cev1) HIPCHK(h, hipEventCreate(&h->cev1));
+  std::vector<double> vv; // spacing of the outline points as the reference's running sum (shapes.cc:128)
+  if (collides) {
+    const double longest = std::max(h->params.veh_length, h->params.veh_width) + 1.0;
+    for (double dl = vertex_res; dl < longest; dl += vertex_res) vv.push_back(dl);
+  }
+  if (vv.empty()) vv.push_back(1.0);
+  double *d_from = nullptr, *d_to = nullptr, *d_len = nullptr, *d_seg = nullptr, *d_smp = nullptr, *d_v = nullptr;
+  int *d_type = nullptr, *d_ns = nullptr, *d_col = nullptr;
+  const size_t nn = (size_t)n, nsmp = nn * max_samples * 3;
+  DevScratch tmp(h);
+  HIPCHK(h, tmp.alloc(d_from, 3 * nn));
+  HIPCHK(h, tmp.alloc(d_to, 3 * nn));
+  HIPCHK(h, tmp.alloc(d_len, nn));
+  HIPCHK(h, tmp.alloc(d_seg, 5 * nn));
+  HIPCHK(h, tmp.alloc(d_smp, nsmp));
+  HIPCHK(h, tmp.alloc(d_v, vv.size()));
+  HIPCHK(h, tmp.alloc(d_type, nn));
+  HIPCHK(h, tmp.alloc(d_ns, nn));
+  HIPCHK(h, tmp.alloc(d_col, nn));
+  h->ctimed = false; // until the whole chain has run
+  HIPCHK(h, hipMemcpyAsync(d_from, from, sizeof(double) * 3 * nn, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_to, to, sizeof(double) * 3 * nn, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_v, vv.data(), sizeof(double) * vv.size(), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipEventRecord(h->cev0, h->stream));
+  HIPCHK(h, launch_shots(d_from, d_to, n, 1.0 / max_cur, checkl, max_samples, collides ? h->d_cells : nullptr, h->map.size_x,
+                         h->map.size_y, h->map.resolution, h->map.origin_x, h->map.origin_y, h->params.veh_width, h->params.veh_length,
+                         h->params.veh_d_cr, d_v, (int)vv.size(), d_len, d_type, d_seg, d_smp, d_ns, d_col, h->stream));
+  HIPCHK(h, hipEventRecord(h->cev1, h->stream));
+  HIPCHK(h, fetch_async(h, length, d_len, sizeof(double) * nn));
+  HIPCHK(h, fetch_async(h, type, d_type, sizeof(int) * nn));
+  HIPCHK(h, fetch_async(h, seg, d_seg, sizeof(double) * 5 * nn));
+  HIPCHK(h, fetch_async(h, samples, d_smp, sizeof(double) * nsmp));
+  HIPCHK(h, fetch_async(h, n_samples, d_ns, sizeof(int) * nn));
+  HIPCHK(h, fetch_async(h, collides, d_col, sizeof(int) * nn));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->ctimed = true;
+  return DFTPAV_OK;
+}
+
+// ------------------------------------------------- hybrid A* front-end search (search.hip)
+extern "C" void dftpav_default_search_params(dftpav_search_params *sp) {
+  std::memset(sp, 0, sizeof(*sp));
+  // config/minco_config.pb.txt:13-59 (map_cfg), :81 (max_frontend_cur); kino_astar.h:167; kino_astar.cpp:426-427
+  sp->map_size_x = 1000.0;
+  sp->map_size_y = 1000.0;
+  sp->map_resl = 0.3;
+  sp->phi_grid_resolution = 0.3;
+  sp->lambda_heu = 5.0;
+  sp->tie_breaker = 1.0 + 1.0 / 10000;
+  sp->allocate_num = 100000;
+  sp->check_num = 5;
+  sp->step_arc = 0.9;
+  sp->max_frontend_cur = 1.0;
+  sp->checkl = 0.2;
+  sp->traj_forward_penalty = 1.0;
+  sp->traj_back_penalty = 2.5;
+  sp->traj_gear_switch_penalty = 15.0;
+  sp->traj_steer_penalty = 0.5;
+  sp->traj_steer_change_penalty = 0.0;
+  sp->veh_width = 1.90 + 0.2;
+  sp->veh_length = 4.88 + 0.2;
+  sp->veh_d_cr = 1.015;
+  sp->wheel_base = 2.85;
+  sp->vertex_res = 0.1;
+  sp->max_iters = 20000;
+  sp->use3d = 1;
+  sp->retry_2d = 1;
+}
+
+// the inputs of one expansion as the reference's loops build them (kino_astar.cpp:143-171): running sums, tabulated here
+static int search_inputs(const dftpav_search_params &sp, double max_steer, int which, double *tab) {
+  const double res = 0.5;
+  int n = 0;
+  auto steers = [&](double arc) {
+    for (double steer = -max_steer; steer <= max_steer + 1e-3; steer += res * max_steer * 1.0) {
+      if (n < kSearchMaxIn) {
+        tab[2 * n] = steer;
+        tab[2 * n + 1] = arc;
+      }
+      if (++n > 4 * kSearchMaxIn) return;
+    }
+  };
+  if (which == 0) {
+    for (double arc = sp.map_resl; arc <= 2 * sp.map_resl + 1e-3 && n <= kSearchMaxIn; arc += sp.map_resl) steers(arc);
+  } else if (which == 1) {
+    for (double arc = -sp.map_resl; arc >= -2 * sp.map_resl - 1e-3 && n <= kSearchMaxIn; arc -= sp.map_resl) steers(arc);
+  } else {
+    for (double arc = -sp.step_arc; arc <= sp.step_arc + 1e-3 && n <= kSearchMaxIn; arc += 0.5 * sp.step_arc) {
+      if (std::fabs(arc) < 1.0e-2) continue;
+      steers(arc);
+    }
+  }
+  return n;
+}
+
+
+// The workspace of a search of n queries: per query in flight a node pool, the heap (node, key, position), the path list and the
+// hash table (the power of two >= 2 allocate_num); `slots` queries in flight, n or as many as 6 GiB hold -- the queries beyond run
+// in further launches over the same slots.  Each array holds every slot's part and starts on a 256-byte boundary: off[] in the
+// order pool, h_node, h_pos, path_idx, h_key, table, and `bytes` for all of them.
+struct SearchWorkspace {
+  int hcap = 0, slots = 0;
+  size_t per = 0, off[6] = {}, bytes = 0;
+};
+static SearchWorkspace search_workspace(const dftpav_search_params &P, int n) {
+  SearchWorkspace W;
+  W.hcap = 1;
+  while (W.hcap < 2 * P.allocate_num) W.hcap <<= 1;
+  const size_t A = (size_t)P.allocate_num;
+  W.per = A * sizeof(SearchNode) + A * (3 * sizeof(int) + sizeof(double)) + (size_t)W.hcap * sizeof(int) + 256;
+  const size_t budget = ((size_t)6 << 30) - 6 * 256; // 6 GiB at most, the arrays' alignment included
+  W.slots = (int)std::min<size_t>((size_t)n, std::max<size_t>(1, budget / W.per));
+  const size_t S = (size_t)W.slots;
+  const size_t sizes[6] = {A * S * sizeof(SearchNode), A * S * sizeof(int), A * S * sizeof(int), A * S * sizeof(int),
+                           A * S * sizeof(double), (size_t)W.hcap * S * sizeof(int)};
+  for (int k = 0; k < 6; k++) {
+    W.off[k] = W.bytes;
+    W.bytes += (sizes[k] + 255) / 256 * 256;
+  }
+  return W;
+}
+extern "C" int dftpav_debug_search_slots(const dftpav_search_params *sp, int n, int *slots, size_t *bytes_per_query) {
+  if (!sp || n < 1 || sp->allocate_num < 2) return DFTPAV_E_INVALID;
+  const SearchWorkspace W = search_workspace(*sp, n);
+  if (slots) *slots = W.slots;
+  if (bytes_per_query) *bytes_per_query = W.per;
+  return DFTPAV_OK;
+}
+
+int dftpav::search_setup(dftpav_handle *h, const dftpav_search_params *sp, int n, SearchSetup &U) {
+  const dftpav_search_params &P = *sp;
+  if (P.allocate_num < 2 || P.check_num < 1 || P.max_iters < 0 || !(P.map_resl > 0.0) || !(P.phi_grid_resolution > 0.0) ||
+      !(P.step_arc > 0.0) || !(P.max_frontend_cur > 0.0) || !(P.checkl > 0.0) || !(P.vertex_res > 0.0) || !(P.wheel_base > 0.0))
+    return DFTPAV_E_INVALID;
+  // the tables of the running sums: inputs, outline point spacing, shot sample offsets
+  const double max_steer = crt::atan(P.wheel_base * P.max_frontend_cur); // kino_astar.cpp:419 (correctly rounded)
+  std::vector<double> in_tab(3 * kSearchMaxIn * 2, 0.0);
+  int n_in[3];
+  for (int w = 0; w < 3; w++) {
+    n_in[w] = search_inputs(P, max_steer, w, in_tab.data() + (size_t)w * kSearchMaxIn * 2);
+    if (n_in[w] > kSearchMaxIn || n_in[w] * P.check_num > kSearchThreads) return DFTPAV_E_UNSUPPORTED;
+  }
+  if (P.check_num > kSearchMaxCheck) return DFTPAV_E_UNSUPPORTED;
+  std::vector<double> vv;
+  const double longest = std::max(P.veh_length, P.veh_width) + 1.0;
+  for (double dl = P.vertex_res; dl < longest; dl += P.vertex_res) vv.push_back(dl);
+  if (vv.empty()) vv.push_back(longest);
+  // a shot is tried within 15 m of the goal (kino_astar.cpp:90); an LSL path, which always exists, is no longer than
+  // d + 2 r + 4 pi r, and the shortest path is no longer than it.  getKinoNode's second shot starts from a pose of the
+  // terminal node's last arc: one step_arc more.  The table holds every offset up to that bound and a margin.
+  const double rho = 1.0 / P.max_frontend_cur;
+  const double bound = 15.0 + std::max(P.step_arc, 2 * P.map_resl) + (2.0 + 4.0 * rs::kPi) * rho;
+  const double n_l_need = bound / P.checkl + 8.0;
+  if (!(n_l_need < (double)kSearchMaxShot)) return DFTPAV_E_UNSUPPORTED;
+  std::vector<double> ll;
+  for (double l = 0.0; (int)ll.size() < (int)n_l_need; l += P.checkl) ll.push_back(l); // kino_astar.cpp:338, 594
+  HIPCHK(h, hipSetDevice(h->device));
+  if (!h->cev0) HIPCHK(h, hipEventCreate(&h->cev0));
+  if (!h->cev1) HIPCHK(h, hipEventCreate(&h->cev1));
+  const SearchWorkspace W = search_workspace(P, n);
+  const int hcap = W.hcap, slots = W.slots;
+  const size_t ws = W.bytes;
+  if (h->search_ws_bytes < ws) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->d_search_ws) (void)hipFree(h->d_search_ws);
+    h->d_search_ws = nullptr;
+    h->search_ws_bytes = 0;
+    const hipError_t e = hipMalloc(&h->d_search_ws, ws);
+    if (e != hipSuccess) { // the handle stays usable: no workspace, and no error left for the next launch's hipGetLastError
+      (void)hipGetLastError();
+      h->d_search_ws = nullptr;
+      h->err = std::string("hipMalloc of the search workspace: ") + hipGetErrorString(e);
+      return DFTPAV_E_HIP;
+    }
+    h->search_ws_bytes = ws;
+  }
+  unsigned char *w = (unsigned char *)h->d_search_ws;
+  SearchArgs &S = U.S;
+  S = SearchArgs{};
+  S.pool = (SearchNode *)(w + W.off[0]);
+  S.h_node = (int *)(w + W.off[1]);
+  S.h_pos = (int *)(w + W.off[2]);
+  S.path_idx = (int *)(w + W.off[3]);
+  S.h_key = (double *)(w + W.off[4]);
+  S.table = (int *)(w + W.off[5]);
+  S.hcap = hcap;
+  S.sp = P;
+  S.cells = h->d_cells;
+  S.size_x = h->map.size_x;
+  S.size_y = h->map.size_y;
+  S.resolution = h->map.resolution;
+  S.origin_x = h->map.origin_x;
+  S.origin_y = h->map.origin_y;
+  S.inv_yaw_res = 1.0 / P.phi_grid_resolution; // kino_astar.cpp:421
+  S.origin_sx = -0.5 * P.map_size_x;
+  S.origin_sy = -0.5 * P.map_size_y;
+  S.half_size_x = P.map_size_x * 0.5;
+  S.half_size_y = P.map_size_y * 0.5;
+  S.rho = rho;
+  for (int k = 0; k < 3; k++) S.n_in[k] = n_in[k];
+  S.n = n;
+  S.n_v = (int)vv.size();
+  S.n_l = (int)ll.size();
+  U.tabs = in_tab;
+  U.tabs.insert(U.tabs.end(), vv.begin(), vv.end());
+  U.tabs.insert(U.tabs.end(), ll.begin(), ll.end());
+  U.n_in_tab = in_tab.size();
+  U.n_vv = vv.size();
+  U.n_ll = ll.size();
+  U.slots = slots;
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_kino_search(dftpav_handle *h, const dftpav_search_params *sp, const double *start_states,
+                                  const double *start_ctrl, const double *end_states, int n, const dftpav_search_out *out) {
+  (void)start_ctrl; // kept by search (kino_astar.cpp:54) for getKinoNode's flat states: dftpav_frontend_resample takes it
+  if (!h || !sp || !out || n < 0 || out->max_nodes < 0 || out->max_path < 0) return DFTPAV_E_INVALID;
+  if (!h->d_cells) return DFTPAV_E_INVALID; // no map
+  if (n == 0) return DFTPAV_OK;
+  if (!start_states || !end_states || !out->status || !out->shot_success || !out->used_3d || !out->budget_hit || !out->iters ||
+      !out->nodes_used || !out->n_nodes || !out->path_len || (out->max_nodes > 0 && !out->nodes) || (out->max_path > 0 && !out->paths))
+    return DFTPAV_E_INVALID;
+  SearchSetup U;
+  if (int rc = search_setup(h, sp, n, U)) return rc;
+  const size_t nn = (size_t)n, n_nodes = 6 * nn * out->max_nodes, n_paths = 3 * nn * out->max_path;
+  double *d_tabs = nullptr, *d_st = nullptr, *d_en = nullptr, *d_nodes = nullptr, *d_paths = nullptr;
+  int *d_ints = nullptr;
+  DevScratch tmp(h);
+  HIPCHK(h, tmp.alloc(d_tabs, U.tabs.size()));
+  HIPCHK(h, tmp.alloc(d_st, 4 * nn));
+  HIPCHK(h, tmp.alloc(d_en, 4 * nn));
+  HIPCHK(h, tmp.alloc(d_ints, 9 * nn));
+  if (out->max_nodes > 0) HIPCHK(h, tmp.alloc(d_nodes, n_nodes));
+  if (out->max_path > 0) HIPCHK(h, tmp.alloc(d_paths, n_paths));
+  h->ctimed = false; // until the whole chain has run
+  HIPCHK(h, hipMemcpyAsync(d_tabs, U.tabs.data(), sizeof(double) * U.tabs.size(), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_st, start_states, sizeof(double) * 4 * nn, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_en, end_states, sizeof(double) * 4 * nn, hipMemcpyHostToDevice, h->stream));
+  // rows past n_nodes / path_len read back as zeros
+  if (d_nodes) HIPCHK(h, hipMemsetAsync(d_nodes, 0, sizeof(double) * n_nodes, h->stream));
+  if (d_paths) HIPCHK(h, hipMemsetAsync(d_paths, 0, sizeof(double) * n_paths, h->stream));
+  wire_search(U, d_tabs, d_st, d_en, d_ints, nn, out->max_nodes, d_nodes, out->max_path, d_paths);
+  HIPCHK(h, hipEventRecord(h->cev0, h->stream));
+  for (int q0 = 0; q0 < n; q0 += U.slots) {
+    U.S.q0 = q0;
+    HIPCHK(h, launch_search(U.S, std::min(U.slots, n - q0), h->stream));
+  }
+  HIPCHK(h, hipEventRecord(h->cev1, h->stream));
+  int *const fields[8] = {out->status, out->shot_success, out->used_3d, out->budget_hit, out->iters, out->nodes_used, out->n_nodes, out->path_len};
+  for (int f = 0; f < 8; f++) HIPCHK(h, hipMemcpyAsync(fields[f], d_ints + f * nn, sizeof(int) * nn, hipMemcpyDeviceToHost, h->stream));
+  if (d_nodes) HIPCHK(h, hipMemcpyAsync(out->nodes, d_nodes, sizeof(double) * n_nodes, hipMemcpyDeviceToHost, h->stream));
+  if (d_paths) HIPCHK(h, hipMemcpyAsync(out->paths, d_paths, sizeof(double) * n_paths, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->ctimed = true;
+  for (int q = 0; q < n; q++)
+    if (out->status[q] == 0) return DFTPAV_E_UNSUPPORTED; // a shot beyond the sample table (not reached: see the bound)
+  return DFTPAV_OK;
+}
+
+void dftpav::wire_search(SearchSetup &U, double *d_tabs, double *d_start, double *d_end, int *d_ints, size_t n, int max_nodes,
+                         double *d_nodes, int max_path, double *d_paths) {
+  SearchArgs &S = U.S;
+  S.in_tab = d_tabs;
+  S.v_tab = d_tabs + U.n_in_tab;
+  S.l_tab = d_tabs + U.n_in_tab + U.n_vv;
+  S.start = d_start;
+  S.end = d_end;
+  dftpav_search_out &O = S.out;
+  O.max_nodes = max_nodes;
+  O.max_path = max_path;
+  O.status = d_ints;
+  O.shot_success = d_ints + n;
+  O.used_3d = d_ints + 2 * n;
+  O.budget_hit = d_ints + 3 * n;
+  O.iters = d_ints + 4 * n;
+  O.nodes_used = d_ints + 5 * n;
+  O.n_nodes = d_ints + 6 * n;
+  O.path_len = d_ints + 7 * n;
+  O.nodes = d_nodes;
+  O.paths = d_paths;
+}
+
+extern "C" int dftpav_set_grid_map(dftpav_handle *h, const dftpav_grid_map *map) {
+  if (!h || !map || !map->cells || map->size_x <= 0 || map->size_y <= 0 || !(map->resolution > 0.0)) return DFTPAV_E_INVALID;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (h->d_cells) (void)hipFree(h->d_cells);
+  if (h->d_bits) (void)hipFree(h->d_bits);
+  if (h->d_dl) (void)hipFree(h->d_dl);
+  h->d_cells = nullptr;
+  h->d_bits = nullptr;
+  h->d_dl = nullptr;
+  const size_t ncell = (size_t)map->size_x * map->size_y;
+  HIPCHK(h, hipMalloc(&h->d_cells, ncell));
+  HIPCHK(h, hipMemcpy(h->d_cells, map->cells, ncell, hipMemcpyHostToDevice));
+  h->map = *map;
+  h->map.cells = nullptr;
+  if (ncell <= (size_t)8 * 40 * 1024) { // <= 40 KB of bits per workgroup: four workgroups per CU
+    std::vector<unsigned> bits((ncell + 31) / 32, 0u);
+    for (size_t i = 0; i < ncell; i++)
+      if (map->cells[i] == 80) bits[i >> 5] |= 1u << (i & 31);
+    HIPCHK(h, hipMalloc(&h->d_bits, sizeof(unsigned) * bits.size()));
+    HIPCHK(h, hipMemcpy(h->d_bits, bits.data(), sizeof(unsigned) * bits.size(), hipMemcpyHostToDevice));
+  }
+  // sample offsets of CheckIfCollisionUsingLine (map_adapter.cpp:119): dl = 0, then dl += checkl; the longest
+  // segment is the far edge of a fully grown rectangle
+  const double checkl = map->resolution / 2.0;
+  const double longest = std::max(h->params.veh_length, h->params.veh_width) + 2.0 * (10.0 + map->resolution) + 1.0;
+  std::vector<double> dl;
+  for (double v = 0.0; v < longest; v += checkl) dl.push_back(v);
+  h->n_dl = (int)dl.size();
+  HIPCHK(h, hipMalloc(&h->d_dl, sizeof(double) * dl.size()));
+  HIPCHK(h, hipMemcpy(h->d_dl, dl.data(), sizeof(double) * dl.size(), hipMemcpyHostToDevice));
+  if (!h->cev0) HIPCHK(h, hipEventCreate(&h->cev0));
+  if (!h->cev1) HIPCHK(h, hipEventCreate(&h->cev1));
+  return DFTPAV_OK;
+}
+
+// uploads the states and runs the corridor kernel into `hpoly` (device, [n][16]) or into a batch's corridor
+static int run_corridor(dftpav_handle *h, const double *states, int n_states, double *d_hpoly, double *batch_cor, int Npts,
+                        int NptsPad, int replicate) {
+  double *d_states = nullptr;
+  DevScratch tmp(h);
+  HIPCHK(h, tmp.alloc(d_states, 3 * (size_t)n_states));
+  h->ctimed = false; // until the whole chain has run
+  HIPCHK(h, hipMemcpyAsync(d_states, states, sizeof(double) * 3 * (size_t)n_states, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipEventRecord(h->cev0, h->stream));
+  HIPCHK(h, launch_corridor(h->d_cells, h->d_bits, h->map.size_x, h->map.size_y, h->map.resolution, h->map.origin_x, h->map.origin_y, d_states,
+                            n_states, h->params.veh_width, h->params.veh_length, h->params.veh_d_cr, h->d_dl, h->n_dl, d_hpoly, batch_cor,
+                            Npts, NptsPad, replicate, h->stream));
+  HIPCHK(h, hipEventRecord(h->cev1, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->ctimed = true;
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_corridor_last_ms(dftpav_handle *h, float *ms) {
+  if (!h || !ms || !h->ctimed) return DFTPAV_E_INVALID;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipEventElapsedTime(ms, h->cev0, h->cev1));
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_corridor_rectangles(dftpav_handle *h, const double *states, int n_states, double *hpoly) {
+  if (!h || !states || !hpoly || n_states < 0) return DFTPAV_E_INVALID;
+  if (!h->d_cells) return DFTPAV_E_INVALID; // no map
+  if (n_states == 0) return DFTPAV_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  double *d_hpoly = nullptr;
+  DevScratch tmp(h);
+  HIPCHK(h, tmp.alloc(d_hpoly, 16 * (size_t)n_states));
+  if (int rc = run_corridor(h, states, n_states, d_hpoly, nullptr, 1, 1, 1)) return rc;
+  HIPCHK(h, hipMemcpy(hpoly, d_hpoly, sizeof(double) * 16 * (size_t)n_states, hipMemcpyDeviceToHost));
+  return DFTPAV_OK;
+}
+
+int dftpav::corridor_into_batch(dftpav_batch *b, const double *d_poses, int n_poses, int replicate) {
+  dftpav_handle *h = b->h;
+  HIPCHK(h, launch_corridor(h->d_cells, h->d_bits, h->map.size_x, h->map.size_y, h->map.resolution, h->map.origin_x, h->map.origin_y, d_poses,
+                            n_poses, h->params.veh_width, h->params.veh_length, h->params.veh_d_cr, h->d_dl, h->n_dl, nullptr, b->d_corridor,
+                            b->L.Npts, b->NptsPad, replicate, h->stream));
+  b->have_corridor = true;
+  b->cor_t_dirty = true;
+  b->cor_rect = false;
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_batch_corridor_from_hypotheses(dftpav_batch *b, const double *states, int n_restarts) {
+  if (!b || !states || n_restarts < 1 || b->B % n_restarts) return DFTPAV_E_INVALID;
+  b->pending = false; // as dftpav_batch_upload
+  dftpav_handle *h = b->h;
+  if (!h->d_cells) return DFTPAV_E_INVALID;       // no map
+  if (b->L.H != 4) return DFTPAV_E_UNSUPPORTED;   // rectangles
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  int rc = run_corridor(h, states, (b->B / n_restarts) * b->L.Npts, nullptr, b->d_corridor, b->L.Npts, b->NptsPad, n_restarts);
+  if (rc == DFTPAV_OK) {
+    b->have_corridor = true;
+    b->cor_t_dirty = true;
+    b->cor_rect = false; // (not asked: see dftpav_batch::cor_rect)
+  }
+  return rc;
+}
+extern "C" int dftpav_batch_corridor_from_states(dftpav_batch *b, const double *states) {
+  return dftpav_batch_corridor_from_hypotheses(b, states, 1);
+}
+
+// test hook: the steps after the solve (dftpav_batch_validate, dftpav_batch_sample_states) on GIVEN coefficients [B][Ntot][6][2] and piece
+// durations [B][M] instead of a solution's -- so that the kernels can be held against committed vectors of arbitrary trajectories
+// (tests/golden/steps.npz).  Cleared by the next upload or solve.
+extern "C" int dftpav_debug_batch_set_coeffs(dftpav_batch *b, const double *coeffs, const double *piece_dt) {
+  if (!b || !coeffs || !piece_dt) return DFTPAV_E_INVALID;
+  dftpav_handle *h = b->h;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemcpy(b->d_coef, coeffs, sizeof(double) * (size_t)b->B * 12 * b->L.Ntot, hipMemcpyHostToDevice));
+  HIPCHK(h, hipMemcpy(b->d_dt, piece_dt, sizeof(double) * (size_t)b->B * b->L.M, hipMemcpyHostToDevice));
+  b->coef_override = true;
+  b->uploaded = true;
+  b->solved = true;
+  return DFTPAV_OK;
+}
+int dftpav::ensure_coeffs(dftpav_batch *b, DevBatch &D) {
+  dftpav_handle *h = b->h;
+  if (int rc = finish_pending(b)) return rc;
+  if (int rc = sync_dev(b, D)) return rc;
+  if (!b->coef_override) HIPCHK(h, launch_for(b, D, kModeCoeffs));
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_batch_coeffs(dftpav_batch *b, double *coeffs, double *piece_dt) {
+  if (!b || !b->uploaded || !b->solved) return DFTPAV_E_INVALID; // the coefficients are those of the solution x
+  dftpav_handle *h = b->h;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (int rc = finish_pending(b)) return rc;
+  DevBatch D;
+  if (int rc = sync_dev(b, D)) return rc;
+  HIPCHK(h, launch_for(b, D, kModeCoeffs)); // (always: this call reports what follows from x, whatever the test hook installed)
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (coeffs)
+    HIPCHK(h, hipMemcpy(coeffs, b->d_coef, sizeof(double) * (size_t)b->B * 12 * b->L.Ntot, hipMemcpyDeviceToHost));
+  if (piece_dt) HIPCHK(h, hipMemcpy(piece_dt, b->d_dt, sizeof(double) * (size_t)b->B * b->L.M, hipMemcpyDeviceToHost));
+  return DFTPAV_OK;
+}
+
+int dftpav::validation_table(const dftpav_params &p, double check_dt, double vertex_res, int max_spacings, std::vector<double> &tab, int *n_t,
+                             int *n_v) {
+  tab.clear();
+  double t = 0.0;
+  for (int k = 0; k < 4096; k++, t += check_dt) tab.push_back(t);
+  const size_t nt = tab.size();
+  const double longest = std::max(p.veh_length, p.veh_width) + 1.0;
+  for (double dl = vertex_res; dl < longest; dl += vertex_res) {
+    tab.push_back(dl);
+    if (max_spacings > 0 && tab.size() - nt >= (size_t)max_spacings) return DFTPAV_E_UNSUPPORTED; // an outline of that many points and more
+  }
+  if (tab.size() == nt) tab.push_back(vertex_res);
+  *n_t = (int)nt;
+  *n_v = (int)(tab.size() - nt);
+  return DFTPAV_OK;
+}
+// test hook (host only, no device): the tables of the collision re-check as every caller of it gets them, out = sample times [*n_t] |
+// spacings [*n_v].  A table beyond out's 8192 doubles (possible without a cap only) is refused with DFTPAV_E_UNSUPPORTED.
+extern "C" int dftpav_debug_validation_table(const dftpav_params *p, double check_dt, double vertex_res, int max_spacings, double *out,
+                                             int *n_t, int *n_v) {
+  if (!p || !out || !n_t || !n_v || !(check_dt > 0.0) || !(vertex_res > 0.0) || max_spacings < 0) return DFTPAV_E_INVALID;
+  std::vector<double> tab;
+  if (int rc = validation_table(*p, check_dt, vertex_res, max_spacings, tab, n_t, n_v)) return rc;
+  if (tab.size() > 8192) return DFTPAV_E_UNSUPPORTED;
+  std::memcpy(out, tab.data(), sizeof(double) * tab.size());
+  return DFTPAV_OK;
+}
+
+int dftpav::validate_on_stream(dftpav_batch *b, int n_traj, const double *d_tab, int n_t, int n_v, double check_dt, int *d_col, int *d_first) {
+  dftpav_handle *h = b->h;
+  HIPCHK(h, launch_validate(h->d_cells, h->map.size_x, h->map.size_y, h->map.resolution, h->map.origin_x, h->map.origin_y, b->d_coef, b->d_dt,
+                            b->L, n_traj, h->params.veh_width, h->params.veh_length, h->params.veh_d_cr, d_tab, n_t, check_dt, d_tab + n_t, n_v,
+                            d_col, d_first, h->stream));
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_batch_validate(dftpav_batch *b, double sample_dt, double vertex_res, int *collision, int *first_sample) {
+  if (!b || !b->uploaded || !b->solved || !(sample_dt > 0.0) || !(vertex_res > 0.0)) return DFTPAV_E_INVALID; // nothing solved yet
+  dftpav_handle *h = b->h;
+  if (!h->d_cells) return DFTPAV_E_INVALID; // no map
+  HIPCHK(h, hipSetDevice(h->device));
+  DevBatch D;
+  if (int rc = ensure_coeffs(b, D)) return rc;
+  std::vector<double> tab;
+  int n_t = 0, n_v = 0;
+  if (int rc = validation_table(h->params, sample_dt, vertex_res, 0, tab, &n_t, &n_v)) return rc;
+  const size_t B = (size_t)b->B;
+  double *d_tab = nullptr;
+  int *d_col = nullptr, *d_first = nullptr;
+  DevScratch tmp(h);
+  HIPCHK(h, tmp.alloc(d_tab, tab.size()));
+  HIPCHK(h, tmp.alloc(d_col, B));
+  HIPCHK(h, tmp.alloc(d_first, B));
+  h->ctimed = false; // until the whole chain has run
+  HIPCHK(h, hipMemcpyAsync(d_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipEventRecord(h->cev0, h->stream));
+  if (int rc = validate_on_stream(b, b->B, d_tab, n_t, n_v, sample_dt, d_col, d_first)) return rc;
+  HIPCHK(h, hipEventRecord(h->cev1, h->stream));
+  HIPCHK(h, fetch_async(h, collision, d_col, sizeof(int) * B));
+  HIPCHK(h, fetch_async(h, first_sample, d_first, sizeof(int) * B));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->ctimed = true;
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_batch_sample_states(dftpav_batch *b, double t0, double sample_dt, int n_samples, int filter_singularity,
+                                          double *states, int *n_valid) {
+  if (!b || !b->uploaded || !b->solved || !(sample_dt > 0.0) || n_samples <= 0 || !states) return DFTPAV_E_INVALID;
+  dftpav_handle *h = b->h;
+  HIPCHK(h, hipSetDevice(h->device));
+  DevBatch D;
+  if (int rc = ensure_coeffs(b, D)) return rc;
+  if (!h->cev0) HIPCHK(h, hipEventCreate(&h->cev0));
+  if (!h->cev1) HIPCHK(h, hipEventCreate(&h->cev1));
+  const size_t nst = (size_t)b->B * (size_t)n_samples * 8;
+  double *d_states = nullptr;
+  int *d_valid = nullptr;
+  DevScratch tmp(h);
+  HIPCHK(h, tmp.alloc(d_states, nst));
+  HIPCHK(h, tmp.alloc(d_valid, (size_t)b->B));
+  h->ctimed = false; // until the whole chain has run
+  HIPCHK(h, hipEventRecord(h->cev0, h->stream));
+  HIPCHK(h, launch_states(b->d_coef, b->d_dt, b->L, b->B, h->params.veh_wheel_base, t0, sample_dt, n_samples, filter_singularity != 0,
+                          d_states, d_valid, h->stream));
+  HIPCHK(h, hipEventRecord(h->cev1, h->stream));
+  HIPCHK(h, hipMemcpyAsync(states, d_states, sizeof(double) * nst, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, fetch_async(h, n_valid, d_valid, sizeof(int) * (size_t)b->B));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->ctimed = true;
+  return DFTPAV_OK;
+}
+
+// ------------------------------------------------- one planning cycle, stream-ordered
+// TrajPlanner::RunMINCOParking from getRectangleConst on (traj_manager.cpp:551-626) and the consumers of its result
+// (CheckReplan's collision re-check, traj_server_ros.cpp:385-397; the state playback, :244-259,335-356) as ONE enqueue:
+// upload of the boundary states / waypoints / durations, then on the handle's stream and without the host in between
+//   constraint-point poses -> rectangles of every hypothesis (corridor.hip) -> solve (solver.hip) -> coefficients of the
+//   solutions -> collision re-check (validate.hip) -> state read-out (states.hip).
+// dftpav_plan_cycle returns when everything is enqueued; dftpav_plan_cycle_fetch waits and copies the results out.
+
+extern "C" int dftpav_plan_cycle(dftpav_batch *b, const dftpav_batch_data *d, const double *states, int n_restarts, double check_dt,
+                                 double vertex_res, double t0, double state_dt, int n_samples, int filter_singularity) {
+  if (!b || !d || !states || n_restarts < 1 || b->B % n_restarts || !(check_dt > 0.0) || !(vertex_res > 0.0) || !(state_dt > 0.0) ||
+      n_samples < 1)
+    return DFTPAV_E_INVALID;
+  dftpav_handle *h = b->h;
+  if (!h->d_cells) return DFTPAV_E_INVALID;     // no map
+  if (b->L.H != 4) return DFTPAV_E_UNSUPPORTED; // rectangles
+  dftpav_batch_data dd = *d;
+  dd.corridor = nullptr; // the half-planes come from the map
+  if (int rc = dftpav_batch_upload(b, &dd)) return rc; // waits for the previous cycle of this handle, then copies the small inputs
+  HIPCHK(h, hipSetDevice(h->device));
+  auto &pc = b->pc;
+  const int B = b->B, n_hyp = B / n_restarts;
+  const size_t n_poses = (size_t)n_hyp * b->L.Npts;
+  pc.poses.assign(states, states + 3 * n_poses);
+  if (int rc = grow(h, pc.d_poses, pc.n_poses, 3 * n_poses)) return rc;
+  if (!h->cev0) HIPCHK(h, hipEventCreate(&h->cev0));
+  if (!h->cev1) HIPCHK(h, hipEventCreate(&h->cev1));
+  HIPCHK(h, hipMemcpyAsync(pc.d_poses, pc.poses.data(), sizeof(double) * 3 * n_poses, hipMemcpyHostToDevice, h->stream));
+  if (int rc = corridor_into_batch(b, pc.d_poses, (int)n_poses, n_restarts)) return rc; // (nothing waits between here and the solve)
+  if (int rc = solve_impl(b, nullptr, false)) return rc;
+  DevBatch D;
+  if (int rc = ensure_coeffs(b, D)) return rc;
+  int n_t = 0, n_v = 0;
+  if (int rc = validation_table(h->params, check_dt, vertex_res, 0, pc.tab, &n_t, &n_v)) return rc;
+  if (int rc = grow(h, pc.d_tab, pc.n_tab, pc.tab.size())) return rc;
+  for (int **buf : {&pc.d_col, &pc.d_first, &pc.d_valid}) { // [B] each: a batch's size does not change
+    size_t have = *buf ? (size_t)B : 0;
+    if (int rc = grow(h, *buf, have, (size_t)B)) return rc;
+  }
+  if (int rc = grow(h, pc.d_rd, pc.n_rd, (size_t)B * n_samples * 8)) return rc;
+  HIPCHK(h, hipMemcpyAsync(pc.d_tab, pc.tab.data(), sizeof(double) * pc.tab.size(), hipMemcpyHostToDevice, h->stream));
+  if (int rc = validate_on_stream(b, b->B, pc.d_tab, n_t, n_v, check_dt, pc.d_col, pc.d_first)) return rc;
+  HIPCHK(h, launch_states(b->d_coef, b->d_dt, b->L, b->B, h->params.veh_wheel_base, t0, state_dt, n_samples, filter_singularity != 0,
+                          pc.d_rd, pc.d_valid, h->stream));
+  pc.n_samples = n_samples;
+  pc.in_flight = true;
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_plan_cycle_fetch(dftpav_batch *b, double *x, double *final_cost, int *status, int *success, int *iters, int *collision,
+                                       int *first_sample, double *states, int *n_valid) {
+  if (!b || !b->pc.in_flight) return DFTPAV_E_INVALID;
+  dftpav_handle *h = b->h;
+  if (int rc = dftpav_batch_results(b, x, final_cost, status, success, iters, nullptr, nullptr, nullptr)) return rc; // waits for the stream
+  const size_t B = (size_t)b->B;
+  if (collision) HIPCHK(h, hipMemcpy(collision, b->pc.d_col, sizeof(int) * B, hipMemcpyDeviceToHost));
+  if (first_sample) HIPCHK(h, hipMemcpy(first_sample, b->pc.d_first, sizeof(int) * B, hipMemcpyDeviceToHost));
+  if (states) HIPCHK(h, hipMemcpy(states, b->pc.d_rd, sizeof(double) * B * b->pc.n_samples * 8, hipMemcpyDeviceToHost));
+  if (n_valid) HIPCHK(h, hipMemcpy(n_valid, b->pc.d_valid, sizeof(int) * B, hipMemcpyDeviceToHost));
+  b->pc.in_flight = false;
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_solve_batch(dftpav_handle *h, const dftpav_layout *layout, int B, const dftpav_batch_data *d,
+                                  double *x, double *final_cost, int *status, int *success, int *iters, int *evals) {
+  dftpav_batch *b = nullptr;
+  int rc = dftpav_batch_create(h, layout, B, &b);
+  if (rc != DFTPAV_OK) return rc;
+  rc = dftpav_batch_upload(b, d);
+  if (rc == DFTPAV_OK) rc = dftpav_batch_solve_async(b);
+  if (rc == DFTPAV_OK) rc = dftpav_batch_results(b, x, final_cost, status, success, iters, evals, nullptr, nullptr);
+  dftpav_batch_destroy(b);
+  return rc;
+}

@@ -639,6 +639,14 @@ int dftpav_kino_search(dftpav_handle *h, const dftpav_search_params *sp, const d
  * least 1) -- the queries beyond run in further launches over the same slots.  Either pointer may be NULL.
  * DFTPAV_E_INVALID for n < 1 or allocate_num < 2. */
 int dftpav_debug_search_slots(const dftpav_search_params *sp, int n, int *slots, size_t *bytes_per_query);
+/* Test hook, pure host code: the two tables every collision re-check reads (dftpav_batch_validate, dftpav_plan_cycle,
+ * dftpav_plan_queries, dftpav_replan_check), out = 4096 sample times (the running sum t += check_dt from 0.0) | the spacings of
+ * the outline points (the running sum dl += vertex_res while dl < max(veh_length, veh_width) + 1.0; one entry vertex_res if that
+ * leaves none); *n_t and *n_v their counts.  max_spacings > 0: DFTPAV_E_UNSUPPORTED where that many spacings or more are needed
+ * (dftpav_replan_check: 4096); 0: no cap, and DFTPAV_E_UNSUPPORTED for a table beyond out's 8192 doubles.  DFTPAV_E_INVALID for
+ * a NULL pointer, increments that are not positive, or max_spacings < 0. */
+int dftpav_debug_validation_table(const dftpav_params *p, double check_dt, double vertex_res, int max_spacings, double *out /*[8192]*/,
+                                  int *n_t, int *n_v);
 
 /* ---- a batch of start / goal queries to their plans, mixed layouts included --------------
  * Replaces TrajPlanner::RunOnceParking from the arrival test on (traj_manager.cpp:194-217): per query the

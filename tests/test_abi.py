@@ -223,3 +223,58 @@ def test_launch_shapes_of_the_reference_order(hiplib):
     assert plan([8], [1], 8, 8, 0, 1, H=13)["supported"] == 0
     assert plan([8], [1], 8, 8, 45, 1)["supported"] == 0
     assert plan([130], [1], 4, 4, 0, 1)["supported"] == 0
+
+
+# ---- the tables of the collision re-check (dftpav_debug_validation_table: host code, no device).  Python floats are doubles, so a
+# plain loop replays the reference's running sums (traj_server_ros.cpp:387, shapes.cc:128) bit for bit.
+def _running_sums(p, check_dt, vertex_res):
+    times, t = [], 0.0
+    for _ in range(4096):
+        times.append(t)
+        t += check_dt
+    longest = max(p.veh_length, p.veh_width) + 1.0
+    spacings, dl = [], vertex_res
+    while dl < longest:
+        spacings.append(dl)
+        dl += vertex_res
+    return times, spacings or [vertex_res]
+
+
+@pytest.mark.parametrize("check_dt,vertex_res", [(0.05, 0.1), (0.21, 0.37)])
+def test_validation_table_replays_the_running_sums(hiplib, check_dt, vertex_res):
+    """The ordinary case and the odd increments of tests/test_gpu_parity.py (where rounding in the sums matters): every entry ==."""
+    p = hiplib.default_params()
+    rc, times, spacings = hiplib.debug_validation_table(p, check_dt, vertex_res)
+    want_t, want_v = _running_sums(p, check_dt, vertex_res)
+    assert rc == hiplib.OK and len(times) == 4096 and len(want_v) > 1
+    assert times.tolist() == want_t
+    assert spacings.tolist() == want_v
+
+
+def test_validation_table_fallback_is_one_spacing(hiplib):
+    p = hiplib.default_params()
+    for vertex_res in (max(p.veh_length, p.veh_width) + 1.0, 50.0):   # at the length itself, and beyond it
+        rc, times, spacings = hiplib.debug_validation_table(p, 0.05, vertex_res)
+        assert rc == hiplib.OK and len(times) == 4096 and spacings.tolist() == [vertex_res]
+
+
+def test_validation_table_cap(hiplib):
+    """max_spacings = 4096 (dftpav_replan_check): an outline that needs 4096 spacings or more is refused, one that needs fewer is
+    tabulated as without the cap."""
+    p = hiplib.default_params()
+    longest = max(p.veh_length, p.veh_width) + 1.0
+    n_of = lambda res: len(_running_sums(p, 0.05, res)[1])
+    res = longest / 4096.5           # about 4096 spacings; stepped to both sides of the threshold below
+    while n_of(res) < 4096:
+        res *= 1.0 - 1e-6
+    too_fine = res
+    while n_of(res) >= 4096:
+        res *= 1.0 + 1e-6
+    fine = res
+    assert n_of(too_fine) >= 4096 > n_of(fine) >= 4090
+    assert hiplib.debug_validation_table(p, 0.05, too_fine, 4096)[0] == hiplib.E_UNSUPPORTED
+    rc, times, spacings = hiplib.debug_validation_table(p, 0.05, fine, 4096)
+    rc0, times0, spacings0 = hiplib.debug_validation_table(p, 0.05, fine, 0)
+    assert rc == rc0 == hiplib.OK
+    assert spacings.tolist() == spacings0.tolist() == _running_sums(p, 0.05, fine)[1]
+    assert times.tolist() == times0.tolist()

@@ -123,6 +123,28 @@ def test_check_equals_the_oracle_and_the_validation(hiplib, scene):
     h.close()
 
 
+def test_check_refuses_an_outline_beyond_its_table_and_stays_usable(hiplib, scene):
+    """A vertex_res that needs 4096 outline spacings or more is refused with E_UNSUPPORTED before anything is enqueued; the next
+    check with the ordinary values returns exactly what it returned before the refused one."""
+    h = hiplib.Handle()
+    h.set_grid_map(scene["grid"], scene["resolution"], scene["origin"])
+    pl = hiplib.Planner(h, rs.N_SLOTS, R)
+    _install_scene(pl, scene)
+    before = pl.check(scene["t_now"], scene["budget"], ego_states=scene["ego_states"])
+    p = h.params
+    too_fine = (max(p.veh_length, p.veh_width) + 1.0) / 5000.0
+    assert hiplib.debug_validation_table(p, 0.05, too_fine, 4096)[0] == hiplib.E_UNSUPPORTED
+    with pytest.raises(hiplib.DftpavError) as e:
+        pl.check(scene["t_now"], scene["budget"], ego_states=scene["ego_states"], vertex_res=too_fine)
+    assert e.value.code == hiplib.E_UNSUPPORTED
+    after = pl.check(scene["t_now"], scene["budget"], ego_states=scene["ego_states"])
+    for k in CHECK_KEYS:
+        assert np.array_equal(before[k], after[k]), k
+    assert before["collision"].sum() >= 1   # (the scene's check is not trivially empty)
+    pl.close()
+    h.close()
+
+
 def test_install_executing_round_trip_and_refusals(hiplib, scene):
     h = hiplib.Handle()
     pl = hiplib.Planner(h, rs.N_SLOTS, R)
