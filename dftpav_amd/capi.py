@@ -46,6 +46,8 @@ EXPORTS = [
     "dftpav_planner_padding",
     "dftpav_replan_check", "dftpav_replan_tick", "dftpav_replan_last_ms",
     "dftpav_planner_publish", "dftpav_planner_publisher_state", "dftpav_planner_set_ctrl_history", "dftpav_publish_last_ms",
+    "dftpav_default_limits", "dftpav_batch_check_limits", "dftpav_planner_check_limits", "dftpav_planner_set_limit_filter",
+    "dftpav_planner_last_limits", "dftpav_limits_last_ms",
 ]
 
 
@@ -152,6 +154,40 @@ def default_params():
     p = Params()
     lib().dftpav_default_params(C.byref(p))
     return p
+
+
+class Limits(C.Structure):
+    """dftpav_limits: every limit > 0; +inf switches a test off"""
+    _fields_ = [(k, C.c_double) for k in ("max_forward_vel", "max_backward_vel", "max_forward_acc", "max_backward_acc",
+                                          "max_forward_cur", "max_backward_cur", "max_latacc", "max_steer")]
+
+
+class _LimitsOutC(C.Structure):
+    _fields_ = [("max_abs", C.c_void_p), ("arg", C.c_void_p), ("violated", C.c_void_p), ("feasible", C.c_void_p)]
+
+
+class LimitsOut:
+    """the caller-allocated arrays of dftpav_limits_out for `shape` rows: max_abs / arg / violated [shape][5] (velocity, longitudinal
+    acceleration, lateral acceleration, curvature, steer), feasible [shape]"""
+
+    def __init__(self, *shape):
+        self.a = dict(max_abs=np.zeros(shape + (5,)), arg=np.zeros(shape + (5,), dtype=np.int32),
+                      violated=np.zeros(shape + (5,), dtype=np.int32), feasible=np.zeros(shape, dtype=np.int32))
+        self.c = _LimitsOutC(*[self.a[k].ctypes.data for k in ("max_abs", "arg", "violated", "feasible")])
+
+    def arrays(self):
+        return self.a
+
+
+def default_limits(params=None):
+    """dftpav_default_limits: the parameters' limits (minco_config.pb.txt:83-91); max_steer = +inf"""
+    params = params if params is not None else default_params()
+    l = Limits()
+    fn = lib().dftpav_default_limits
+    fn.restype = None
+    fn.argtypes = [C.POINTER(Params), C.POINTER(Limits)]
+    fn(C.byref(params), C.byref(l))
+    return l
 
 
 class Handle:
@@ -338,6 +374,14 @@ class Handle:
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         self._check(fn(self._h, st.ctypes.data_as(C.c_void_p), st.shape[0], out.ctypes.data_as(C.c_void_p)), "corridor_rectangles")
         return out
+
+    def limits_last_ms(self):
+        """device time in ms of the last limits kernel of a check_limits call"""
+        ms = C.c_float(0.0)
+        fn = lib().dftpav_limits_last_ms
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        self._check(fn(self._h, C.byref(ms)), "limits_last_ms")
+        return float(ms.value)
 
     def corridor_last_ms(self):
         ms = C.c_float(0.0)
@@ -585,6 +629,31 @@ class Planner:
         fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         self.handle._check(fn(self._p, sl.shape[0], self._ip(sl), self._ip(ts), self._ip(an)), "planner_set_ctrl_history")
 
+    # ---- solved plans against the kinematic limits
+    def check_limits(self, check_dt=0.05, limits=None):
+        """dftpav_planner_check_limits: a row per slot of the executing table -> dict(max_abs, arg, violated [slots][5], feasible
+        [slots]); empty slots: zero rows, arg -1"""
+        limits = limits if limits is not None else default_limits(self.handle.params)
+        out = LimitsOut(self.max_queries)
+        fn = lib().dftpav_planner_check_limits
+        fn.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+        self.handle._check(fn(self._p, float(check_dt), C.byref(limits), C.byref(out.c)), "planner_check_limits")
+        return out.arrays()
+
+    def set_limit_filter(self, limits=None, check_dt=0.05):
+        """dftpav_planner_set_limit_filter: None switches the filter off (the default)"""
+        fn = lib().dftpav_planner_set_limit_filter
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_double]
+        self.handle._check(fn(self._p, C.byref(limits) if limits is not None else None, float(check_dt)), "planner_set_limit_filter")
+
+    def last_limits(self, Q):
+        """dftpav_planner_last_limits: the rows [Q][R] of the last plan() of Q queries that ran with the filter on"""
+        out = LimitsOut(int(Q), self.n_restarts)
+        fn = lib().dftpav_planner_last_limits
+        fn.argtypes = [C.c_void_p, C.c_void_p]
+        self.handle._check(fn(self._p, C.byref(out.c)), "planner_last_limits")
+        return out.arrays()
+
     def publish_last_ms(self):
         """dftpav_publish_last_ms: device ms of the last publish kernel (0.0 before the first)"""
         a = C.c_float(0.0)
@@ -688,6 +757,16 @@ class Batch:
         self.handle._check(fn(self._b, float(sample_dt), float(vertex_res), col.ctypes.data_as(C.c_void_p),
                               first.ctypes.data_as(C.c_void_p)), "batch_validate")
         return col, first
+
+    def check_limits(self, check_dt=0.05, limits=None):
+        """dftpav_batch_check_limits: the solved trajectories against the kinematic limits over CheckReplan's samples -> dict(max_abs,
+        arg, violated [B][5] (velocity, longitudinal / lateral acceleration, curvature, steer), feasible [B])"""
+        limits = limits if limits is not None else default_limits(self.handle.params)
+        out = LimitsOut(self.B)
+        fn = lib().dftpav_batch_check_limits
+        fn.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+        self.handle._check(fn(self._b, float(check_dt), C.byref(limits), C.byref(out.c)), "batch_check_limits")
+        return out.arrays()
 
     def sample_states(self, t0=0.0, sample_dt=0.01, n_samples=None, filter_singularity=True):
         """Trajectory::GetState over the grid t0 + k * sample_dt for every solved trajectory, played back as the

@@ -256,6 +256,8 @@ extern "C" void dftpav_destroy(dftpav_handle *h) {
     if (e) (void)hipEventDestroy(e);
   if (h->cev0) (void)hipEventDestroy(h->cev0);
   if (h->cev1) (void)hipEventDestroy(h->cev1);
+  if (h->lev0) (void)hipEventDestroy(h->lev0);
+  if (h->lev1) (void)hipEventDestroy(h->lev1);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }

@@ -25,6 +25,7 @@
 #include "rs_math.h"
 #include "search_args.h"
 #include "plan_args.h"
+#include "limits_args.h"
 
 namespace dftpav {
 hipError_t launch_solver(const DevBatch &D, const DevBatch *d_dev, int mode, int threads, int grid, SchedArgs sched,
@@ -59,6 +60,9 @@ hipError_t launch_replan_check(const ReplanArgs &A, hipStream_t stream);
 hipError_t launch_exec_adopt(const ExecAdoptArgs &A, hipStream_t stream);
 hipError_t launch_publish(const PublishArgs &A, hipStream_t stream);
 hipError_t launch_pub_reset(const PubResetArgs &A, hipStream_t stream);
+// limits.hip: solved plans against the kinematic limits
+hipError_t launch_limits_batch(const LimitsBatchArgs &A, hipStream_t stream);
+hipError_t launch_limits_table(const LimitsTableArgs &A, hipStream_t stream);
 hipError_t launch_corridor_layout(const double *raw, double *out, int B, int Npts, int H, int NptsPad, hipStream_t stream);
 hipError_t launch_adopt(const DevBatch &D, const DevBatch &prev, hipStream_t stream);
 // solver_ref.hip: the same path in the reference's own floating-point order
@@ -103,6 +107,8 @@ struct dftpav_handle {
   hipEvent_t cev0 = nullptr, cev1 = nullptr; // around the last corridor kernel
   hipEvent_t mark[2] = {nullptr, nullptr};   // dftpav_mark
   bool ctimed = false;
+  hipEvent_t lev0 = nullptr, lev1 = nullptr; // around the last limits kernel of a check_limits call
+  bool ltimed = false;
   std::vector<struct dftpav_batch *> batches; // every live batch of this handle (obstacle changes finish their chained stragglers)
   // RCCL communicator of dftpav_comm_create (one rank per handle = per GPU), and the staging block of this rank's records
   void *comm = nullptr;
@@ -271,6 +277,16 @@ struct dftpav_planner {
   int *d_pub_code = nullptr;
   hipEvent_t pev[2] = {nullptr, nullptr};
   bool pub_timed = false;
+  // ---- the limit filter (dftpav_planner_set_limit_filter): off by default, and then none of this is touched
+  bool lim_on = false;
+  dftpav_limits lim{};
+  double lim_dt = 0.0;
+  unsigned char *d_lim = nullptr; // one allocation: the sample times, the rows [max_queries * R] of a call, the selection's input
+  double *d_lim_tab = nullptr, *d_lim_max = nullptr;
+  int lim_n_t = 0;
+  double lim_tab_dt = 0.0; // what d_lim_tab was tabulated for
+  int *d_lim_arg = nullptr, *d_lim_viol = nullptr, *d_lim_feas = nullptr, *d_lim_reject = nullptr, *d_lim_col = nullptr;
+  bool last_lim = false; // the last dftpav_plan_queries call ran with the filter
 };
 
 namespace dftpav {
@@ -298,6 +314,8 @@ int corridor_into_batch(dftpav_batch *b, const double *d_poses, int n_poses, int
 int ensure_coeffs(dftpav_batch *b, DevBatch &D);
 // the collision re-check of the first n_traj trajectories against the handle's map; d_tab: a validation_table on the device
 int validate_on_stream(dftpav_batch *b, int n_traj, const double *d_tab, int n_t, int n_v, double check_dt, int *d_col, int *d_first);
+// dftpav_limits as the kernels of limits.hip read it; false: a limit that is not > 0 (a NaN included)
+bool limits_common(const dftpav_params &p, const dftpav_limits &l, LimitsCommon &C);
 
 // One allocation for many arrays, measured and carved by the same list: fields(take) names every array in order, take(bytes) is its
 // address -- null while `base` is null, the measuring pass -- and advances by the size rounded up to 256 bytes.  Returns the bytes used.

@@ -92,6 +92,7 @@ extern "C" void dftpav_planner_destroy(dftpav_planner *p) {
   if (p->d_exec) (void)hipFree(p->d_exec);
   if (p->d_rc) (void)hipFree(p->d_rc);
   if (p->d_pub) (void)hipFree(p->d_pub);
+  if (p->d_lim) (void)hipFree(p->d_lim);
   for (auto &e : p->pev)
     if (e) (void)hipEventDestroy(e);
   for (auto &e : p->ev)
@@ -237,6 +238,8 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
   p->group_sizes.clear();
   p->timed = false;
   p->last_Q = 0; // nothing to adopt until this call has ended well
+  p->last_lim = false;
+  const bool filt = p->lim_on; // dftpav_planner_set_limit_filter; off: nothing below differs from a planner that never had one
   if (Q == 0) return DFTPAV_OK;
   if (!start_states || !start_ctrl || !end_states) return DFTPAV_E_INVALID;
   SearchSetup U;
@@ -334,8 +337,16 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
   HIPCHK(h, hipSetDevice(h->device));
   if (!p->h_members.empty())
     HIPCHK(h, hipMemcpyAsync(p->d_members, p->h_members.data(), sizeof(int) * p->h_members.size(), hipMemcpyHostToDevice, h->stream));
-  // ---- per group: pack -> rectangles -> solve -> coefficients -> collision re-check -> selection; nothing waits in between
+  // ---- per group: pack -> rectangles -> solve -> coefficients -> collision re-check (-> limits) -> selection; nothing waits in between
   size_t pose_off = 0;
+  if (filt) { // the rows of the queries no restart is solved for: zero, arg -1
+    const size_t rows = nq * (size_t)R;
+    HIPCHK(h, hipMemsetAsync(p->d_lim_max, 0, sizeof(double) * kLimQ * rows, h->stream));
+    HIPCHK(h, hipMemsetAsync(p->d_lim_arg, 0xff, sizeof(int) * kLimQ * rows, h->stream));
+    HIPCHK(h, hipMemsetAsync(p->d_lim_viol, 0, sizeof(int) * kLimQ * rows, h->stream));
+    HIPCHK(h, hipMemsetAsync(p->d_lim_feas, 0, sizeof(int) * rows, h->stream));
+    HIPCHK(h, hipMemsetAsync(p->d_lim_col, 0, sizeof(int) * rows, h->stream));
+  }
   for (int g = 0; g < ng; g++) {
     dftpav_batch *b = batch[g];
     const int nm = g_off[g + 1] - g_off[g];
@@ -377,10 +388,33 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
     if (int rc = ensure_coeffs(b, D)) return rc;
     int *col = p->d_col + (size_t)g_off[g] * R, *fst = p->d_first + (size_t)g_off[g] * R;
     if (int rc = validate_on_stream(b, nm * R, p->d_vt, n_t, n_v, pp->check_dt, col, fst)) return rc;
+    const int *sel_col = col;
+    if (filt) { // the selection reads collision | !feasible; the collision flags themselves go to d_lim_col by (query, restart)
+      LimitsBatchArgs LA{};
+      if (!limits_common(h->params, p->lim, LA.C)) return DFTPAV_E_INVALID; // (checked when the filter was set)
+      LA.C.t_tab = p->d_lim_tab;
+      LA.C.n_t = p->lim_n_t;
+      LA.C.sample_dt = p->lim_dt;
+      LA.C.max_abs = p->d_lim_max;
+      LA.C.arg = p->d_lim_arg;
+      LA.C.violated = p->d_lim_viol;
+      LA.C.feasible = p->d_lim_feas;
+      LA.coeffs = b->d_coef;
+      LA.piece_dt = b->d_dt;
+      LA.L = L;
+      LA.B = nm * R;
+      LA.members = A.members;
+      LA.R = R;
+      LA.collision = col;
+      LA.reject = p->d_lim_reject + (size_t)g_off[g] * R;
+      LA.collision_rows = p->d_lim_col;
+      HIPCHK(h, launch_limits_batch(LA, h->stream));
+      sel_col = LA.reject;
+    }
     PlanSelectArgs Z{};
     Z.cost = b->d_f;
     Z.success = b->d_success;
-    Z.collision = col;
+    Z.collision = sel_col;
     Z.status = b->d_status;
     Z.iters = b->d_iters;
     Z.evals = b->d_evals;
@@ -426,7 +460,8 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
   HIPCHK(h, fetch_async(h, out->coeff_dt, p->d_wdt, sizeof(double) * nq * MS));
   HIPCHK(h, fetch_async(h, out->r_final_cost, p->d_rcost, sizeof(double) * nq * R));
   int *const r_out[6] = {out->r_status, out->r_success, out->r_iters, out->r_evals, out->r_collision, out->r_first_sample};
-  for (int k = 0; k < 6; k++) HIPCHK(h, fetch_async(h, r_out[k], p->d_rint[k], sizeof(int) * nq * R));
+  for (int k = 0; k < 6; k++) // (with the filter the selection copied its own input into d_rint[4]: the pure flags are in d_lim_col)
+    HIPCHK(h, fetch_async(h, r_out[k], (filt && k == 4) ? p->d_lim_col : p->d_rint[k], sizeof(int) * nq * R));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   for (int q = 0; q < Q; q++) {
     if (status[q] != DFTPAV_PLAN_OK) {
@@ -459,6 +494,7 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
   p->last_MS = MS;
   p->last_MP = MP;
   p->last_Q = Q;
+  p->last_lim = filt;
   return DFTPAV_OK;
 }
 
@@ -1009,5 +1045,115 @@ extern "C" int dftpav_publish_last_ms(dftpav_planner *p, float *ms) {
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipEventSynchronize(p->pev[1]));
   HIPCHK(h, hipEventElapsedTime(ms, p->pev[0], p->pev[1]));
+  return DFTPAV_OK;
+}
+
+// ------------------------------------------------- solved plans against the kinematic limits (limits.hip)
+static int fetch_limits(dftpav_handle *h, const dftpav_limits_out *out, const LimitsCommon &C, size_t rows) {
+  HIPCHK(h, fetch_async(h, out->max_abs, C.max_abs, sizeof(double) * kLimQ * rows));
+  HIPCHK(h, fetch_async(h, out->arg, C.arg, sizeof(int) * kLimQ * rows));
+  HIPCHK(h, fetch_async(h, out->violated, C.violated, sizeof(int) * kLimQ * rows));
+  HIPCHK(h, fetch_async(h, out->feasible, C.feasible, sizeof(int) * rows));
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_planner_check_limits(dftpav_planner *p, double check_dt, const dftpav_limits *l, const dftpav_limits_out *out) {
+  if (!p || !l || !out || !(check_dt > 0.0) || !std::isfinite(check_dt)) return DFTPAV_E_INVALID;
+  dftpav_handle *h = p->h;
+  LimitsTableArgs A{};
+  if (!limits_common(h->params, *l, A.C)) return DFTPAV_E_INVALID;
+  const size_t S = (size_t)p->max_queries;
+  if (!p->d_exec) { // nothing was ever installed: every slot is empty
+    if (out->max_abs) std::fill(out->max_abs, out->max_abs + kLimQ * S, 0.0);
+    if (out->arg) std::fill(out->arg, out->arg + kLimQ * S, -1);
+    if (out->violated) std::fill(out->violated, out->violated + kLimQ * S, 0);
+    if (out->feasible) std::fill(out->feasible, out->feasible + S, 0);
+    return DFTPAV_OK;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  std::vector<double> tab;
+  int n_t = 0, n_v = 0;
+  if (int rc = validation_table(h->params, check_dt, 1.0, 0, tab, &n_t, &n_v)) return rc; // (the sample times are its first n_t entries)
+  if (!h->lev0) HIPCHK(h, hipEventCreate(&h->lev0));
+  if (!h->lev1) HIPCHK(h, hipEventCreate(&h->lev1));
+  double *d_tab = nullptr, *d_max = nullptr;
+  int *d_int = nullptr; // arg | violated | feasible
+  DevScratch tmp(h);
+  HIPCHK(h, tmp.alloc(d_tab, (size_t)n_t));
+  HIPCHK(h, tmp.alloc(d_max, kLimQ * S));
+  HIPCHK(h, tmp.alloc(d_int, (2 * kLimQ + 1) * S));
+  A.C.t_tab = d_tab;
+  A.C.n_t = n_t;
+  A.C.sample_dt = check_dt;
+  A.C.max_abs = d_max;
+  A.C.arg = d_int;
+  A.C.violated = d_int + kLimQ * S;
+  A.C.feasible = d_int + 2 * kLimQ * S;
+  A.T = p->T;
+  h->ltimed = false; // until the whole chain has run
+  HIPCHK(h, hipMemcpyAsync(d_tab, tab.data(), sizeof(double) * (size_t)n_t, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipEventRecord(h->lev0, h->stream));
+  HIPCHK(h, launch_limits_table(A, h->stream));
+  HIPCHK(h, hipEventRecord(h->lev1, h->stream));
+  if (int rc = fetch_limits(h, out, A.C, S)) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->ltimed = true;
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_planner_set_limit_filter(dftpav_planner *p, const dftpav_limits *l, double check_dt) {
+  if (!p) return DFTPAV_E_INVALID;
+  if (!l) { // off: the buffers stay, nothing reads them
+    p->lim_on = false;
+    return DFTPAV_OK;
+  }
+  if (!(check_dt > 0.0) || !std::isfinite(check_dt)) return DFTPAV_E_INVALID;
+  dftpav_handle *h = p->h;
+  LimitsCommon C{};
+  if (!limits_common(h->params, *l, C)) return DFTPAV_E_INVALID;
+  HIPCHK(h, hipSetDevice(h->device));
+  std::vector<double> tab;
+  int n_t = 0, n_v = 0;
+  if (int rc = validation_table(h->params, check_dt, 1.0, 0, tab, &n_t, &n_v)) return rc; // (the sample times are its first n_t entries)
+  if (!p->d_lim) {
+    const size_t rows = (size_t)p->max_queries * p->R;
+    auto fields = [&](auto &take) {
+      p->d_lim_tab = (double *)take(sizeof(double) * (size_t)n_t);
+      p->d_lim_max = (double *)take(sizeof(double) * kLimQ * rows);
+      p->d_lim_arg = (int *)take(sizeof(int) * kLimQ * rows);
+      p->d_lim_viol = (int *)take(sizeof(int) * kLimQ * rows);
+      p->d_lim_feas = (int *)take(sizeof(int) * rows);
+      p->d_lim_reject = (int *)take(sizeof(int) * rows);
+      p->d_lim_col = (int *)take(sizeof(int) * rows);
+    };
+    unsigned char *base = nullptr;
+    HIPCHK(h, hipMalloc(&base, carve(nullptr, fields)));
+    carve(base, fields);
+    p->d_lim = base;
+    p->lim_tab_dt = 0.0;
+  }
+  if (p->lim_tab_dt != check_dt) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(p->d_lim_tab, tab.data(), sizeof(double) * (size_t)n_t, hipMemcpyHostToDevice));
+    p->lim_tab_dt = check_dt;
+    p->lim_n_t = n_t;
+  }
+  p->lim = *l;
+  p->lim_dt = check_dt;
+  p->lim_on = true;
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_planner_last_limits(dftpav_planner *p, const dftpav_limits_out *out) {
+  if (!p || !out || !p->last_lim || p->last_Q <= 0) return DFTPAV_E_INVALID;
+  dftpav_handle *h = p->h;
+  HIPCHK(h, hipSetDevice(h->device));
+  LimitsCommon C{};
+  C.max_abs = p->d_lim_max;
+  C.arg = p->d_lim_arg;
+  C.violated = p->d_lim_viol;
+  C.feasible = p->d_lim_feas;
+  if (int rc = fetch_limits(h, out, C, (size_t)p->last_Q * p->R)) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
   return DFTPAV_OK;
 }

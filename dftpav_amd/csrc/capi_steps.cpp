@@ -581,6 +581,84 @@ extern "C" int dftpav_batch_validate(dftpav_batch *b, double sample_dt, double v
   return DFTPAV_OK;
 }
 
+// ------------------------------------------------- solved plans against the kinematic limits (limits.hip)
+extern "C" void dftpav_default_limits(const dftpav_params *p, dftpav_limits *l) {
+  // minco_config.pb.txt:83-85 (forward), :87-89 (backward), :91 (max_latacc); the reference has no steer limit of its own
+  l->max_forward_vel = p->max_forward_vel;
+  l->max_backward_vel = p->max_backward_vel;
+  l->max_forward_acc = p->max_forward_acc;
+  l->max_backward_acc = p->max_backward_acc;
+  l->max_forward_cur = p->max_forward_cur;
+  l->max_backward_cur = p->max_backward_cur;
+  l->max_latacc = p->max_latacc;
+  l->max_steer = HUGE_VAL;
+}
+
+bool dftpav::limits_common(const dftpav_params &p, const dftpav_limits &l, LimitsCommon &C) {
+  const double both[kLimQ][2] = {{l.max_forward_vel, l.max_backward_vel}, {l.max_forward_acc, l.max_backward_acc}, {l.max_latacc, l.max_latacc},
+                                 {l.max_forward_cur, l.max_backward_cur}, {l.max_steer, l.max_steer}};
+  for (int q = 0; q < kLimQ; q++)
+    for (int d = 0; d < 2; d++) {
+      if (!(both[q][d] > 0.0)) return false;
+      C.lim[q][d] = both[q][d];
+    }
+  C.wheel_base = p.veh_wheel_base;
+  return true;
+}
+
+extern "C" int dftpav_batch_check_limits(dftpav_batch *b, double check_dt, const dftpav_limits *l, const dftpav_limits_out *out) {
+  if (!b || !l || !out || !b->uploaded || !b->solved || !(check_dt > 0.0) || !std::isfinite(check_dt)) return DFTPAV_E_INVALID;
+  dftpav_handle *h = b->h;
+  LimitsBatchArgs A{};
+  if (!limits_common(h->params, *l, A.C)) return DFTPAV_E_INVALID;
+  HIPCHK(h, hipSetDevice(h->device));
+  DevBatch D;
+  if (int rc = ensure_coeffs(b, D)) return rc;
+  std::vector<double> tab;
+  int n_t = 0, n_v = 0;
+  if (int rc = validation_table(h->params, check_dt, 1.0, 0, tab, &n_t, &n_v)) return rc; // (the sample times are its first n_t entries)
+  if (!h->lev0) HIPCHK(h, hipEventCreate(&h->lev0));
+  if (!h->lev1) HIPCHK(h, hipEventCreate(&h->lev1));
+  const size_t B = (size_t)b->B;
+  double *d_tab = nullptr, *d_max = nullptr;
+  int *d_int = nullptr; // arg | violated | feasible
+  DevScratch tmp(h);
+  HIPCHK(h, tmp.alloc(d_tab, (size_t)n_t));
+  HIPCHK(h, tmp.alloc(d_max, kLimQ * B));
+  HIPCHK(h, tmp.alloc(d_int, (2 * kLimQ + 1) * B));
+  A.C.t_tab = d_tab;
+  A.C.n_t = n_t;
+  A.C.sample_dt = check_dt;
+  A.C.max_abs = d_max;
+  A.C.arg = d_int;
+  A.C.violated = d_int + kLimQ * B;
+  A.C.feasible = d_int + 2 * kLimQ * B;
+  A.coeffs = b->d_coef;
+  A.piece_dt = b->d_dt;
+  A.L = b->L;
+  A.B = b->B;
+  A.R = 1;
+  h->ltimed = false; // until the whole chain has run
+  HIPCHK(h, hipMemcpyAsync(d_tab, tab.data(), sizeof(double) * (size_t)n_t, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipEventRecord(h->lev0, h->stream));
+  HIPCHK(h, launch_limits_batch(A, h->stream));
+  HIPCHK(h, hipEventRecord(h->lev1, h->stream));
+  HIPCHK(h, fetch_async(h, out->max_abs, A.C.max_abs, sizeof(double) * kLimQ * B));
+  HIPCHK(h, fetch_async(h, out->arg, A.C.arg, sizeof(int) * kLimQ * B));
+  HIPCHK(h, fetch_async(h, out->violated, A.C.violated, sizeof(int) * kLimQ * B));
+  HIPCHK(h, fetch_async(h, out->feasible, A.C.feasible, sizeof(int) * B));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->ltimed = true;
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_limits_last_ms(dftpav_handle *h, float *ms) {
+  if (!h || !ms || !h->ltimed) return DFTPAV_E_INVALID;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipEventElapsedTime(ms, h->lev0, h->lev1));
+  return DFTPAV_OK;
+}
+
 extern "C" int dftpav_batch_sample_states(dftpav_batch *b, double t0, double sample_dt, int n_samples, int filter_singularity,
                                           double *states, int *n_valid) {
   if (!b || !b->uploaded || !b->solved || !(sample_dt > 0.0) || n_samples <= 0 || !states) return DFTPAV_E_INVALID;

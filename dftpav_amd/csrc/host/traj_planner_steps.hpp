@@ -13,6 +13,8 @@
 //   TrajPlanner::getRectangleConst(statelist)       MGR:1213-1469      getRectangleConst(statelist) -> hPolys_
 //   TrajPlanner::ConverSurroundTrajFromPoints(...)  MGR:743-789        ConverSurroundTrajFromPoints(sur_trajs) (installs them)
 //   collision part of CheckReplan                   SRV:385-397        CheckCollision(batch) -> per trajectory bool
+//   Trajectory::getVel / getAcc / getLatAcc /       PTU:606-645,       CheckLimits(batch, B, limits, feasible, max_abs) -- the reference reads
+//     getCurv / getSteer over CheckReplan's samples   247-300, SRV:385-386  these off a plan but tests none of them after the solve
 //   Trajectory::GetState as PublishData plays it    PTU:378-406,       GetStates(batch, t0, dt, n) -> common::State rows per trajectory
 //     back, FilterSingularityState                  SRV:244-259,335-356
 //   LocalTrajData as bytes (PolyTraj.msg, unused)   msg/PolyTraj.msg   SerializeTraj(...) / setSurroundTrajsFromWire(blobs)
@@ -168,6 +170,20 @@ class TrajPlannerSteps {
   bool CheckCollision(dftpav_batch *batch, int B, std::vector<int> &is_collision) {
     is_collision.assign(B, 0);
     return ok(dftpav_batch_validate(batch, 0.05, 0.1, is_collision.data(), nullptr));
+  }
+
+  // every trajectory of a solved batch against the kinematic limits, over the samples of that loop: feasible[t] == 1 when none of
+  // |velocity|, |longitudinal acceleration|, |lateral acceleration|, |curvature|, |steer| exceeds its limit; max_abs (optional) gets
+  // the five maxima per trajectory.  limits == nullptr: dftpav_default_limits of `params`
+  bool CheckLimits(dftpav_batch *batch, int B, const dftpav_params &params, const dftpav_limits *limits, std::vector<int> &feasible,
+                   std::vector<std::array<double, 5>> *max_abs = nullptr) {
+    dftpav_limits l;
+    if (limits) l = *limits;
+    else dftpav_default_limits(&params, &l);
+    feasible.assign(B, 0);
+    if (max_abs) max_abs->assign(B, {});
+    const dftpav_limits_out out{max_abs ? max_abs->data()->data() : nullptr, nullptr, nullptr, feasible.data()};
+    return ok(dftpav_batch_check_limits(batch, 0.05, &l, &out));
   }
 
   // the states the server would publish for every trajectory of a solved batch at t0, t0 + dt, ...;

@@ -1,0 +1,42 @@
+// limits_args.h — what the host half of dftpav_batch_check_limits / dftpav_planner_check_limits hands the kernels of limits.hip.
+#pragma once
+#include "../../include/dftpav_hip.h"
+#include "device_types.h"
+#include "plan_args.h"
+
+namespace dftpav {
+
+enum { kLimVel = 0, kLimAcc, kLimLatAcc, kLimCur, kLimSteer, kLimQ }; // the columns of dftpav_limits_out
+
+// what both kernels share: the sample times, the limits and the result rows
+struct LimitsCommon {
+  const double *t_tab; // 0, dt, dt + dt, ... (validation_table)
+  int n_t;
+  double sample_dt, wheel_base;
+  double lim[kLimQ][2]; // [quantity][0] forward (singul > 0), [1] backward; one value twice where the limit has no direction
+  double *max_abs;      // [rows][5]
+  int *arg, *violated;  // [rows][5]
+  int *feasible;        // [rows]
+};
+
+// limits_batch_kernel: the first B trajectories of a solved batch
+struct LimitsBatchArgs {
+  LimitsCommon C;
+  const double *coeffs;   // [B][Ntot][6][2]
+  const double *piece_dt; // [B][M]
+  DevLayout L;
+  int B;
+  const int *members; // nullptr: trajectory b writes row b; else row members[b / R] * R + b % R (the [Q][R] rows of a call)
+  int R;
+  const int *collision; // [B] or nullptr; with it:
+  int *reject;          //   [B]    collision | !feasible, what the selection reads in place of the collision flags
+  int *collision_rows;  //   [rows] the collision flags as they are, by result row
+};
+
+// limits_table_kernel: every slot of the executing table (read only)
+struct LimitsTableArgs {
+  LimitsCommon C;
+  ExecTable T;
+};
+
+} // namespace dftpav

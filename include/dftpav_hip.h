@@ -863,6 +863,64 @@ int dftpav_planner_publisher_state(dftpav_planner *p, int slot, int *exe_index, 
 int dftpav_planner_set_ctrl_history(dftpav_planner *p, int n, const int *slots, const double *stamps, const double *angles);
 int dftpav_publish_last_ms(dftpav_planner *p, float *ms);
 
+/* ---- solved plans against the kinematic limits ------------------------------------------------------------------
+ * The reference checks no plan against the vehicle's limits after the solve: velocity, longitudinal acceleration and curvature
+ * enter OptimizeTrajectory as soft penalties only (wei_feas, traj_optimizer.cpp:422-779), the lateral-acceleration and
+ * steering-rate penalties are switched off, and `success` means "status accepted and cost < fail_cost".  These calls evaluate,
+ * on the device (limits.hip), what the reference can compute but never tests:
+ *   Trajectory::getVel / getAcc / getLatAcc / getCurv / getSteer   plan_utils/poly_traj_utils.hpp:606-645
+ *   Piece::getVel / getAcc / getLatAcc / getCurv / getSteer        poly_traj_utils.hpp:247-300, each with its |dsigma| < 1e-6 -> 0.0
+ *                                                                  branch where the reference has one (getVel and getSteer have none)
+ * over the samples CheckReplan walks (traj_server_ros.cpp:385-386: per gear segment t = 0.0; t < duration; t += check_dt), with
+ * Trajectory::locatePieceIdx's subtraction walk for the local time (:510-528).  The sample times are the running sums of
+ * dftpav_debug_validation_table, a sample's global index is the one `first_sample` of dftpav_batch_validate uses.  fp64 in the
+ * reference's statements and order, dsigma.norm() as sqrt(x * x + y * y); pow(., 3) and std::atan are correctly rounded
+ * (cr_trig.h) where the reference calls libm.  Held bit for bit by oracle_limits/limits_oracle.cpp in order 2.
+ *
+ * Per trajectory and quantity q (columns: velocity, longitudinal acceleration, lateral acceleration, curvature, steer):
+ *   max_abs   the maximum of |q| over the samples.
+ *   arg       the global sample index where that maximum is FIRST reached: ties go to the lowest index.
+ *   violated  1 if |q| > limit, strictly, at any sample.  The limit of a sample is chosen by its segment's singul (> 0: the
+ *             max_forward_* value, else max_backward_*) for velocity, acceleration and curvature; max_latacc and max_steer are one
+ *             value each.
+ *   NaN       a NaN sample violates its limit whatever the limit (+inf included) and is reported as the maximum, max_abs NaN, at
+ *             the FIRST NaN sample of the trajectory.
+ *   A trajectory without a sample reports max_abs 0, arg -1, nothing violated.  feasible: none of the five violated.
+ * dftpav_default_limits: the parameters' values (config/minco_config.pb.txt:83-85 forward, :87-89 backward, :91 max_latacc);
+ *   max_steer = +inf, the reference has no steer limit of its own.  Every limit must be > 0; +inf switches a test off.
+ * dftpav_batch_check_limits: the B trajectories of a solved batch, from the coefficients dftpav_batch_coeffs produces (or those of
+ *   dftpav_debug_batch_set_coeffs).  Rows [B].
+ * dftpav_planner_check_limits: a row per slot of the executing table; empty slots (and every slot before the table was filled
+ *   once) give zero rows, feasible included, with arg -1.  The table is not written.
+ * dftpav_planner_set_limit_filter: l == NULL (the default): dftpav_plan_queries and dftpav_replan_tick do exactly what they do
+ *   without this call -- the same launches, the same bits.  With limits: per layout group the limits kernel runs after the
+ *   collision re-check and before the selection, and the selection sees collision | !feasible in place of collision, so the
+ *   winner is the cheapest restart that succeeded, does not collide and respects every limit; a query whose every restart is
+ *   rejected ends DFTPAV_PLAN_NO_VALID_RESTART (a tick then keeps the slot's old plan).  r_collision / r_first_sample of
+ *   dftpav_plan_out stay the pure collision results.  The limits and check_dt are copied.
+ * dftpav_planner_last_limits: the rows [Q][R] (query, restart) of the last dftpav_plan_queries call that ran with the filter on;
+ *   zero rows with arg -1 for the queries no restart was solved for.  DFTPAV_E_INVALID when that call ran without the filter.
+ * dftpav_limits_last_ms: device time in ms (the handle's HIP events) of the last limits kernel of one of the two check_limits calls.
+ * Every pointer of dftpav_limits_out may be NULL.  A refused call changes nothing and returns DFTPAV_E_INVALID: no solved
+ * coefficients (for the planner's filter: nothing), check_dt <= 0 or NaN, a check_dt that is not finite (its table of sample
+ * times is not one validate's kernel can continue), a limit that is <= 0 or NaN, l or out NULL. */
+typedef struct dftpav_limits {           /* every limit > 0; +inf switches a test off */
+  double max_forward_vel, max_backward_vel, max_forward_acc, max_backward_acc,
+         max_forward_cur, max_backward_cur, max_latacc, max_steer;
+} dftpav_limits;
+void dftpav_default_limits(const dftpav_params *p, dftpav_limits *l);
+typedef struct dftpav_limits_out {        /* caller-allocated, any pointer may be NULL */
+  double *max_abs;   /* [n][5] vel, acc, latacc, cur, steer */
+  int *arg;          /* [n][5] */
+  int *violated;     /* [n][5] */
+  int *feasible;     /* [n]   none of the five violated */
+} dftpav_limits_out;
+int dftpav_batch_check_limits(dftpav_batch *b, double check_dt, const dftpav_limits *l, const dftpav_limits_out *out);
+int dftpav_planner_check_limits(dftpav_planner *p, double check_dt, const dftpav_limits *l, const dftpav_limits_out *out);
+int dftpav_planner_set_limit_filter(dftpav_planner *p, const dftpav_limits *l, double check_dt);
+int dftpav_planner_last_limits(dftpav_planner *p, const dftpav_limits_out *out);
+int dftpav_limits_last_ms(dftpav_handle *h, float *ms);
+
 /* One-shot convenience == OptimizeTrajectory for B trajectories. */
 int dftpav_solve_batch(dftpav_handle *h, const dftpav_layout *layout, int B,
                        const dftpav_batch_data *d, double *x, double *final_cost,
