@@ -23,6 +23,7 @@
 #include "traj_math.h"
 #include "cr_trig.h"
 #include "rs_math.h"
+#include "step_args.h"
 #include "search_args.h"
 #include "plan_args.h"
 #include "limits_args.h"
@@ -30,9 +31,7 @@
 namespace dftpav {
 hipError_t launch_solver(const DevBatch &D, const DevBatch *d_dev, int mode, int threads, int grid, SchedArgs sched,
                          hipStream_t stream);
-hipError_t launch_corridor(const unsigned char *cells, const unsigned *bits, int size_x, int size_y, double resolution, double origin_x, double origin_y,
-                           const double *states, int n, double veh_width, double veh_length, double veh_dcr, const double *dl,
-                           int n_dl, double *hpoly, double *batch_cor, int Npts, int NptsPad, int replicate, hipStream_t stream);
+hipError_t launch_corridor(const CorridorArgs &A, hipStream_t stream); // (A.res_rcp is set there)
 hipError_t launch_frontend(const dftpav_frontend_params &fp, const double *paths, const int *path_len, int max_path,
                            const double *start_states, const double *end_states, const double *start_ctrl, int n_hyp,
                            const dftpav_frontend_out &out, hipStream_t stream);
@@ -40,16 +39,10 @@ hipError_t launch_restarts(const double *inner, const double *durs, int n_hyp, i
                            double lo, double hi, unsigned long long seed, double *out_inner, double *out_durs, hipStream_t stream);
 hipError_t launch_fit(const double *states, int S, int n_states, const double *opM, double *dur, double *coef, double *total,
                       double *start, hipStream_t stream);
-hipError_t launch_validate(const unsigned char *cells, int size_x, int size_y, double resolution, double origin_x, double origin_y,
-                           const double *coeffs, const double *piece_dt, const DevLayout &L, int B, double veh_width,
-                           double veh_length, double veh_dcr, const double *t_tab, int n_t, double sample_dt, const double *v_tab,
-                           int n_v, int *collision, int *first_sample, hipStream_t stream);
+hipError_t launch_validate(const ValidateArgs &A, hipStream_t stream);
 hipError_t launch_states(const double *coeffs, const double *piece_dt, const DevLayout &L, int B, double wheel_base, double t0,
                          double sample_dt, int n_samples, int filter, double *states, int *n_valid, hipStream_t stream);
-hipError_t launch_shots(const double *from, const double *to, int n, double rho, double checkl, int max_samples,
-                        const unsigned char *cells, int size_x, int size_y, double resolution, double origin_x, double origin_y,
-                        double veh_width, double veh_length, double veh_dcr, const double *v_tab, int n_v, double *length, int *type,
-                        double *seg, double *samples, int *n_samples, int *collides, hipStream_t stream);
+hipError_t launch_shots(const ShotArgs &A, hipStream_t stream);
 hipError_t launch_search(const SearchArgs &A, int blocks, hipStream_t stream);
 // plan.hip: the kernels between the stages of dftpav_plan_queries
 hipError_t launch_plan_paths(const int *status, const int *path_len, const int *skip, int n, int max_path, double *paths, int *fe_len,
@@ -209,6 +202,14 @@ struct dftpav_batch {
       return DFTPAV_E_HIP;                                                               \
     }                                                                                    \
   } while (0)
+
+// the handle's map and vehicle as the kernels take them (footprint.h); v_tab: the spacings of the outline points on the device
+inline DevGrid dev_grid(const dftpav_handle *h) {
+  return DevGrid{h->d_cells, h->map.size_x, h->map.size_y, h->map.resolution, h->map.origin_x, h->map.origin_y};
+}
+inline DevFootprint dev_footprint(const dftpav_handle *h, const double *v_tab, int n_v) {
+  return DevFootprint{h->params.veh_width, h->params.veh_length, h->params.veh_d_cr, v_tab, n_v};
+}
 
 // What a launch of the search needs besides the queries and the outputs: the checked parameters, the tables of the running sums
 // (inputs, outline point spacing, shot sample offsets; `tabs` is their host copy, in_tab | v_tab | l_tab) and the handle's

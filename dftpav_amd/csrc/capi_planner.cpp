@@ -392,9 +392,7 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
     if (filt) { // the selection reads collision | !feasible; the collision flags themselves go to d_lim_col by (query, restart)
       LimitsBatchArgs LA{};
       if (!limits_common(h->params, p->lim, LA.C)) return DFTPAV_E_INVALID; // (checked when the filter was set)
-      LA.C.t_tab = p->d_lim_tab;
-      LA.C.n_t = p->lim_n_t;
-      LA.C.sample_dt = p->lim_dt;
+      LA.C.tab = SampleTable{p->d_lim_tab, p->lim_n_t, p->lim_dt};
       LA.C.max_abs = p->d_lim_max;
       LA.C.arg = p->d_lim_arg;
       LA.C.violated = p->d_lim_viol;
@@ -849,21 +847,10 @@ static int replan_check_enqueue(dftpav_planner *p, double t_now, double budget, 
   if (ego_states) HIPCHK(h, hipMemcpyAsync(p->d_rc_ego, ego_states, sizeof(double) * 6 * S, hipMemcpyHostToDevice, h->stream));
   ReplanArgs A{};
   A.T = p->T;
-  A.cells = h->d_cells;
-  A.size_x = h->map.size_x;
-  A.size_y = h->map.size_y;
-  A.resolution = h->map.resolution;
-  A.origin_x = h->map.origin_x;
-  A.origin_y = h->map.origin_y;
-  A.veh_width = h->params.veh_width;
-  A.veh_length = h->params.veh_length;
-  A.veh_dcr = h->params.veh_d_cr;
+  A.grid = dev_grid(h);
+  A.fp = dev_footprint(h, p->d_rc_tab + p->rc_n_t, p->rc_n_v);
   A.wheel_base = h->params.veh_wheel_base;
-  A.t_tab = p->d_rc_tab;
-  A.n_t = p->rc_n_t;
-  A.sample_dt = check_dt;
-  A.v_tab = p->d_rc_tab + p->rc_n_t;
-  A.n_v = p->rc_n_v;
+  A.tab = SampleTable{p->d_rc_tab, p->rc_n_t, check_dt};
   A.t_now = t_now;
   A.budget = budget;
   A.goals = end_states ? p->d_rc_goal : nullptr;
@@ -1082,9 +1069,7 @@ extern "C" int dftpav_planner_check_limits(dftpav_planner *p, double check_dt, c
   HIPCHK(h, tmp.alloc(d_tab, (size_t)n_t));
   HIPCHK(h, tmp.alloc(d_max, kLimQ * S));
   HIPCHK(h, tmp.alloc(d_int, (2 * kLimQ + 1) * S));
-  A.C.t_tab = d_tab;
-  A.C.n_t = n_t;
-  A.C.sample_dt = check_dt;
+  A.C.tab = SampleTable{d_tab, n_t, check_dt};
   A.C.max_abs = d_max;
   A.C.arg = d_int;
   A.C.violated = d_int + kLimQ * S;

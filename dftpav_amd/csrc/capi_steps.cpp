@@ -115,9 +115,10 @@ extern "C" int dftpav_reeds_shepp_shots(dftpav_handle *h, const double *from, co
   HIPCHK(h, hipMemcpyAsync(d_to, to, sizeof(double) * 3 * nn, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(d_v, vv.data(), sizeof(double) * vv.size(), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipEventRecord(h->cev0, h->stream));
-  HIPCHK(h, launch_shots(d_from, d_to, n, 1.0 / max_cur, checkl, max_samples, collides ? h->d_cells : nullptr, h->map.size_x,
-                         h->map.size_y, h->map.resolution, h->map.origin_x, h->map.origin_y, h->params.veh_width, h->params.veh_length,
-                         h->params.veh_d_cr, d_v, (int)vv.size(), d_len, d_type, d_seg, d_smp, d_ns, d_col, h->stream));
+  ShotArgs A{d_from, d_to, n, 1.0 / max_cur, checkl, max_samples, dev_grid(h), dev_footprint(h, d_v, (int)vv.size()),
+             d_len, d_type, d_seg, d_smp, d_ns, d_col};
+  if (!collides) A.grid.cells = nullptr; // no collision check
+  HIPCHK(h, launch_shots(A, h->stream));
   HIPCHK(h, hipEventRecord(h->cev1, h->stream));
   HIPCHK(h, fetch_async(h, length, d_len, sizeof(double) * nn));
   HIPCHK(h, fetch_async(h, type, d_type, sizeof(int) * nn));
@@ -278,12 +279,8 @@ int dftpav::search_setup(dftpav_handle *h, const dftpav_search_params *sp, int n
   S.table = (int *)(w + W.off[5]);
   S.hcap = hcap;
   S.sp = P;
-  S.cells = h->d_cells;
-  S.size_x = h->map.size_x;
-  S.size_y = h->map.size_y;
-  S.resolution = h->map.resolution;
-  S.origin_x = h->map.origin_x;
-  S.origin_y = h->map.origin_y;
+  S.grid = dev_grid(h);
+  S.fp = DevFootprint{P.veh_width, P.veh_length, P.veh_d_cr, nullptr, (int)vv.size()}; // (v_tab: wire_search)
   S.inv_yaw_res = 1.0 / P.phi_grid_resolution; // kino_astar.cpp:421
   S.origin_sx = -0.5 * P.map_size_x;
   S.origin_sy = -0.5 * P.map_size_y;
@@ -292,7 +289,6 @@ int dftpav::search_setup(dftpav_handle *h, const dftpav_search_params *sp, int n
   S.rho = rho;
   for (int k = 0; k < 3; k++) S.n_in[k] = n_in[k];
   S.n = n;
-  S.n_v = (int)vv.size();
   S.n_l = (int)ll.size();
   U.tabs = in_tab;
   U.tabs.insert(U.tabs.end(), vv.begin(), vv.end());
@@ -354,7 +350,7 @@ void dftpav::wire_search(SearchSetup &U, double *d_tabs, double *d_start, double
                          double *d_nodes, int max_path, double *d_paths) {
   SearchArgs &S = U.S;
   S.in_tab = d_tabs;
-  S.v_tab = d_tabs + U.n_in_tab;
+  S.fp.v_tab = d_tabs + U.n_in_tab;
   S.l_tab = d_tabs + U.n_in_tab + U.n_vv;
   S.start = d_start;
   S.end = d_end;
@@ -410,6 +406,13 @@ extern "C" int dftpav_set_grid_map(dftpav_handle *h, const dftpav_grid_map *map)
 }
 
 // uploads the states and runs the corridor kernel into `hpoly` (device, [n][16]) or into a batch's corridor
+// the corridor kernel's arguments for n states (device) of the handle's map and vehicle
+static CorridorArgs corridor_args(const dftpav_handle *h, const double *d_states, int n, double *d_hpoly, double *batch_cor, int Npts,
+                                  int NptsPad, int replicate) {
+  return CorridorArgs{dev_grid(h), h->d_bits, 0.0, d_states, n, h->params.veh_width, h->params.veh_length, h->params.veh_d_cr,
+                      h->d_dl, h->n_dl, d_hpoly, batch_cor, Npts, NptsPad, replicate};
+}
+
 static int run_corridor(dftpav_handle *h, const double *states, int n_states, double *d_hpoly, double *batch_cor, int Npts,
                         int NptsPad, int replicate) {
   double *d_states = nullptr;
@@ -418,9 +421,7 @@ static int run_corridor(dftpav_handle *h, const double *states, int n_states, do
   h->ctimed = false; // until the whole chain has run
   HIPCHK(h, hipMemcpyAsync(d_states, states, sizeof(double) * 3 * (size_t)n_states, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipEventRecord(h->cev0, h->stream));
-  HIPCHK(h, launch_corridor(h->d_cells, h->d_bits, h->map.size_x, h->map.size_y, h->map.resolution, h->map.origin_x, h->map.origin_y, d_states,
-                            n_states, h->params.veh_width, h->params.veh_length, h->params.veh_d_cr, h->d_dl, h->n_dl, d_hpoly, batch_cor,
-                            Npts, NptsPad, replicate, h->stream));
+  HIPCHK(h, launch_corridor(corridor_args(h, d_states, n_states, d_hpoly, batch_cor, Npts, NptsPad, replicate), h->stream));
   HIPCHK(h, hipEventRecord(h->cev1, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->ctimed = true;
@@ -449,9 +450,7 @@ extern "C" int dftpav_corridor_rectangles(dftpav_handle *h, const double *states
 
 int dftpav::corridor_into_batch(dftpav_batch *b, const double *d_poses, int n_poses, int replicate) {
   dftpav_handle *h = b->h;
-  HIPCHK(h, launch_corridor(h->d_cells, h->d_bits, h->map.size_x, h->map.size_y, h->map.resolution, h->map.origin_x, h->map.origin_y, d_poses,
-                            n_poses, h->params.veh_width, h->params.veh_length, h->params.veh_d_cr, h->d_dl, h->n_dl, nullptr, b->d_corridor,
-                            b->L.Npts, b->NptsPad, replicate, h->stream));
+  HIPCHK(h, launch_corridor(corridor_args(h, d_poses, n_poses, nullptr, b->d_corridor, b->L.Npts, b->NptsPad, replicate), h->stream));
   b->have_corridor = true;
   b->cor_t_dirty = true;
   b->cor_rect = false;
@@ -546,9 +545,9 @@ extern "C" int dftpav_debug_validation_table(const dftpav_params *p, double chec
 
 int dftpav::validate_on_stream(dftpav_batch *b, int n_traj, const double *d_tab, int n_t, int n_v, double check_dt, int *d_col, int *d_first) {
   dftpav_handle *h = b->h;
-  HIPCHK(h, launch_validate(h->d_cells, h->map.size_x, h->map.size_y, h->map.resolution, h->map.origin_x, h->map.origin_y, b->d_coef, b->d_dt,
-                            b->L, n_traj, h->params.veh_width, h->params.veh_length, h->params.veh_d_cr, d_tab, n_t, check_dt, d_tab + n_t, n_v,
-                            d_col, d_first, h->stream));
+  const ValidateArgs A{dev_grid(h), dev_footprint(h, d_tab + n_t, n_v), SampleTable{d_tab, n_t, check_dt}, b->d_coef, b->d_dt, b->L, n_traj,
+                       d_col, d_first};
+  HIPCHK(h, launch_validate(A, h->stream));
   return DFTPAV_OK;
 }
 
@@ -626,9 +625,7 @@ extern "C" int dftpav_batch_check_limits(dftpav_batch *b, double check_dt, const
   HIPCHK(h, tmp.alloc(d_tab, (size_t)n_t));
   HIPCHK(h, tmp.alloc(d_max, kLimQ * B));
   HIPCHK(h, tmp.alloc(d_int, (2 * kLimQ + 1) * B));
-  A.C.t_tab = d_tab;
-  A.C.n_t = n_t;
-  A.C.sample_dt = check_dt;
+  A.C.tab = SampleTable{d_tab, n_t, check_dt};
   A.C.max_abs = d_max;
   A.C.arg = d_int;
   A.C.violated = d_int + kLimQ * B;

@@ -15,29 +15,9 @@
 // fp64 throughout, no contraction: bit-identical to oracle/corridor_oracle.cpp in order 1.
 #include <hip/hip_runtime.h>
 
-#include "device_types.h"
-#include "traj_math.h"
+#include "step_args.h"
 
 namespace dftpav {
-
-struct CorridorArgs {
-  const unsigned char *cells;
-  const unsigned *bits; // the same map, one bit per cell (set = OCCUPIED), or nullptr when it does not fit in LDS
-  int size_x, size_y;
-  double resolution, origin_x, origin_y;
-  double res_rcp; // 1.0 / resolution
-  const double *states; // [n][3]
-  int n;
-  double veh_width, veh_length, veh_dcr;
-  const double *dl; // running sum 0, checkl, checkl + checkl, ...
-  int n_dl;
-  double *hpoly; // [n][4][4], or nullptr:
-  // the solve path's own layout, [trajectory][4 * plane + component][NptsPad] with unit normals
-  // (traj_optimizer.cpp:49-52), state i being point i % Npts of trajectory i / Npts
-  double *batch_cor;
-  int Npts, NptsPad;
-  int replicate; // every trajectory i / Npts is written `replicate` times: trajectories t * replicate + r (restarts share a corridor)
-};
 
 // GridMapND::CheckIfEqualUsingGlobalPosition(p, OCCUPIED): coord = round((p - origin) / resolution), out of range
 // counts as free (semantics.cc:169-179, 214-221).  BITS: the map is the 1-bit-per-cell copy staged in LDS.
@@ -50,12 +30,13 @@ __device__ inline double div_by_rcp(double a, double b, double y) {
 }
 template <bool BITS>
 __device__ inline bool cell_occupied(const CorridorArgs &A, const unsigned *bits, double x, double y) {
-  const double cx = round(div_by_rcp(x - A.origin_x, A.resolution, A.res_rcp));
-  const double cy = round(div_by_rcp(y - A.origin_y, A.resolution, A.res_rcp));
-  if (!(cx >= 0.0 && cx < (double)A.size_x && cy >= 0.0 && cy < (double)A.size_y)) return false;
-  const int idx = (int)cx + A.size_x * (int)cy;
+  const DevGrid &g = A.grid;
+  const double cx = round(div_by_rcp(x - g.origin_x, g.resolution, A.res_rcp));
+  const double cy = round(div_by_rcp(y - g.origin_y, g.resolution, A.res_rcp));
+  if (!(cx >= 0.0 && cx < (double)g.size_x && cy >= 0.0 && cy < (double)g.size_y)) return false;
+  const int idx = (int)cx + g.size_x * (int)cy;
   if (BITS) return (bits[idx >> 5] >> (idx & 31)) & 1u;
-  return A.cells[idx] == 80; // GridMapND::OCCUPIED
+  return g.cells[idx] == 80; // GridMapND::OCCUPIED
 }
 
 // One growth step asks whether any sample of point1 -> newpoint1 -> newpoint2 -> point2 is occupied
@@ -111,7 +92,7 @@ __global__ void __launch_bounds__(256) corridor_kernel(CorridorArgs A) {
   extern __shared__ unsigned lds_bits[];
   const int lane = threadIdx.x & 63;
   if (BITS) { // the whole map, one bit per cell
-    const int words = (A.size_x * A.size_y + 31) >> 5;
+    const int words = (A.grid.size_x * A.grid.size_y + 31) >> 5;
     for (int w = threadIdx.x; w < words; w += blockDim.x) lds_bits[w] = A.bits[w];
     __syncthreads();
   }
@@ -121,7 +102,7 @@ __global__ void __launch_bounds__(256) corridor_kernel(CorridorArgs A) {
   double c, s;
   crt::sincos(yaw, s, c); // (the reference: libm cos / sin; here the correctly rounded ones, as oracle order 2)
   const double ns = -s; // egoR = [c -s; s c], traj_manager.cpp:1233-1234
-  const double step = A.resolution * 1.0, limit = 10.0; // :1218-1219
+  const double step = A.grid.resolution * 1.0, limit = 10.0; // :1218-1219
   const double dcr = A.veh_dcr;
   double sx = rx, sy = ry, W = A.veh_width, L = A.veh_length; // sourcePt, sourceVp
   double expand[4] = {0.0, 0.0, 0.0, 0.0};
@@ -197,15 +178,14 @@ __global__ void __launch_bounds__(256) corridor_kernel(CorridorArgs A) {
   }
 }
 
-hipError_t launch_corridor(const unsigned char *cells, const unsigned *bits, int size_x, int size_y, double resolution, double origin_x, double origin_y,
-                           const double *states, int n, double veh_width, double veh_length, double veh_dcr, const double *dl,
-                           int n_dl, double *hpoly, double *batch_cor, int Npts, int NptsPad, int replicate, hipStream_t stream) {
-  CorridorArgs A{cells, bits, size_x, size_y, resolution, origin_x, origin_y, 1.0 / resolution, states, n, veh_width, veh_length, veh_dcr, dl, n_dl,
-                 hpoly, batch_cor, Npts, NptsPad, replicate};
+hipError_t launch_corridor(const CorridorArgs &args, hipStream_t stream) {
+  CorridorArgs A = args;
+  A.res_rcp = 1.0 / A.grid.resolution;
+  const int n = A.n;
   const int waves_per_block = 4;
   const dim3 grid((n + waves_per_block - 1) / waves_per_block), block(64 * waves_per_block);
-  if (bits) {
-    const size_t lds = (((size_t)size_x * size_y + 31) / 32) * sizeof(unsigned);
+  if (A.bits) {
+    const size_t lds = (((size_t)A.grid.size_x * A.grid.size_y + 31) / 32) * sizeof(unsigned);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&corridor_kernel<true>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;

@@ -24,13 +24,12 @@
 //             feasible included, with arg -1).
 // Two entry kernels share one device function: limits_batch_kernel reads a solved batch (launch-wide DevLayout, the coefficients
 // dftpav_batch_coeffs produces), limits_table_kernel the rows of the executing table (layout per slot, as replan_check_kernel).
-// Neither writes what it reads.  The pose-free piece evaluation is restated here rather than shared with validate.hip /
-// states.hip / replan.hip.
+// Neither writes what it reads.  The piece evaluators and the sample table are piece_eval.h's; the quantities are Piece::getVel
+// ... getSteer, which divide by the norm and branch on it, not GetState's tail.
 #include <hip/hip_runtime.h>
 
 #include <climits>
 
-#include "cr_trig.h"
 #include "limits_args.h"
 
 namespace dftpav {
@@ -47,21 +46,6 @@ struct LimRed { // what lane 0 of each wave leaves for the last step
   int i[4][kLimQ];
   int mask[4];
 };
-
-// number of samples t_k < dur: the table is increasing; past its end the running sum is continued (validate.hip)
-__device__ inline int lm_samples(const LimitsCommon &C, double dur) {
-  int lo = 0, hi = C.n_t;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (C.t_tab[mid] < dur) lo = mid + 1;
-    else hi = mid;
-  }
-  int cnt = lo;
-  if (cnt == C.n_t) {
-    for (double t = C.t_tab[C.n_t - 1] + C.sample_dt; t < dur; t += C.sample_dt) cnt++;
-  }
-  return cnt;
-}
 
 // (b, ib) into (a, ia): the larger value, a NaN before every number, the lower index between equals (and between NaNs).
 // (-1.0, INT_MAX) is "no sample yet": every |q| replaces it.
@@ -86,45 +70,13 @@ __device__ inline int lm_trajectory(const LimitsCommon &C, const LimSeg &S, LimR
   }
   int mask = 0;
   for (int q = tid; q < total; q += blockDim.x) {
-    int i = 0;
-    while (i + 1 < M && q >= S.count[i + 1]) i++;
-    const int k = q - S.count[i];
-    double t;
-    if (k < C.n_t) {
-      t = C.t_tab[k];
-    } else {
-      t = C.t_tab[C.n_t - 1];
-      for (int j = C.n_t - 1; j < k; j++) t += C.sample_dt;
-    }
-    const int N = S.pn[i];
-    const double dtp = S.dt[i];
-    // locatePieceIdx, poly_traj_utils.hpp:510-528
-    double tt = t;
-    int idx = 0;
-    while (idx < N && tt > dtp) {
-      tt -= dtp;
-      idx++;
-    }
-    if (idx == N) {
-      idx--;
-      tt += dtp;
-    }
+    const int i = pe::sample_segment(S.count, M, q);
+    double tt = pe::sample_time(C.tab, q - S.count[i]);
+    const int idx = pe::locate_piece(S.pn[i], S.dt[i], tt);
     const double *c = cb + (size_t)(S.piece0[i] + idx) * 12;
-    double vx = 0.0, vy = 0.0, tn = 1.0;
-#pragma unroll
-    for (int kk = 1; kk <= 5; kk++) { // Piece::getdSigma
-      vx += (double)kk * tn * c[2 * kk];
-      vy += (double)kk * tn * c[2 * kk + 1];
-      tn *= tt;
-    }
-    double ax = 0.0, ay = 0.0;
-    tn = 1.0;
-#pragma unroll
-    for (int kk = 2; kk <= 5; kk++) { // Piece::getddSigma
-      ax += (double)((kk - 1) * kk) * tn * c[2 * kk];
-      ay += (double)((kk - 1) * kk) * tn * c[2 * kk + 1];
-      tn *= tt;
-    }
+    double vx, vy, ax, ay;
+    pe::piece_vel(c, tt, vx, vy);
+    pe::piece_acc(c, tt, ax, ay);
     const double sg = (double)S.sg[i];
     const double norm = sqrt(vx * vx + vy * vy); // dsigma.norm()
     double v[kLimQ];
@@ -200,14 +152,12 @@ __global__ void __launch_bounds__(256) limits_batch_kernel(LimitsBatchArgs A) {
     int acc = 0;
     for (int i = 0; i < M; i++) {
       const double dtp = A.piece_dt[(size_t)b * M + i];
-      double dur = 0.0; // Trajectory::getTotalDuration: piece durations summed in order
-      for (int p = 0; p < L.piece_nums[i]; p++) dur += dtp;
       S.piece0[i] = L.seg_piece0[i];
       S.pn[i] = L.piece_nums[i];
       S.sg[i] = L.singuls[i];
       S.dt[i] = dtp;
       S.count[i] = acc;
-      acc += lm_samples(A.C, dur);
+      acc += pe::samples_below(A.C.tab, pe::segment_duration(L.piece_nums[i], dtp));
     }
     S.count[M] = acc;
   }
@@ -246,7 +196,7 @@ __global__ void __launch_bounds__(256) limits_table_kernel(LimitsTableArgs A) {
       S.dt[i] = T.coeff_dt[(size_t)s * MS + i];
       p0 += S.pn[i];
       S.count[i] = acc;
-      acc += lm_samples(A.C, T.duration[(size_t)s * MS + i]);
+      acc += pe::samples_below(A.C.tab, T.duration[(size_t)s * MS + i]);
     }
     S.count[M] = acc;
   }

@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/dftpav_hip.h"
 #include "device_types.h"
+#include "piece_eval.h"
 #include "plan_args.h"
 
 namespace dftpav {
@@ -10,9 +11,8 @@ enum { kLimVel = 0, kLimAcc, kLimLatAcc, kLimCur, kLimSteer, kLimQ }; // the col
 
 // what both kernels share: the sample times, the limits and the result rows
 struct LimitsCommon {
-  const double *t_tab; // 0, dt, dt + dt, ... (validation_table)
-  int n_t;
-  double sample_dt, wheel_base;
+  SampleTable tab; // (validation_table)
+  double wheel_base;
   double lim[kLimQ][2]; // [quantity][0] forward (singul > 0), [1] backward; one value twice where the limit has no direction
   double *max_abs;      // [rows][5]
   int *arg, *violated;  // [rows][5]

@@ -2,6 +2,8 @@
 #pragma once
 #include "../../include/dftpav_hip.h"
 #include "device_types.h"
+#include "footprint.h"
+#include "piece_eval.h"
 
 namespace dftpav {
 
@@ -76,15 +78,10 @@ struct ExecAdoptArgs {
 enum { kRcOccupied = 0, kRcComplete, kRcExeIndex, kRcCloseTurn, kRcNear, kRcTargetMoved, kRcCollision, kRcFirstSample, kRcReplan, kRcInts };
 struct ReplanArgs {
   ExecTable T;
-  const unsigned char *cells;
-  int size_x, size_y;
-  double resolution, origin_x, origin_y;
-  double veh_width, veh_length, veh_dcr, wheel_base;
-  const double *t_tab; // 0, dt, dt + dt, ...
-  int n_t;
-  double sample_dt;
-  const double *v_tab; // res, res + res, ...
-  int n_v;
+  DevGrid grid;
+  DevFootprint fp;
+  double wheel_base;
+  SampleTable tab;
   double t_now, budget;
   const double *goals; // [slots][4] or nullptr: the stored goals
   const double *ego;   // [slots][6] x, y, angle, v, steer, acc, or nullptr

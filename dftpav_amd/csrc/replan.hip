@@ -14,94 +14,17 @@
 // table, so plans of different layouts are checked in one launch.  Thread 0 makes the scalar decisions in the reference's
 // statements and order and reads the desired state; all threads then take the collision samples of CheckReplan exactly as
 // validate.hip takes them (tabulated running sums, an atomic minimum over the samples), so collision / first_sample are the
-// bits dftpav_batch_validate gives for the same plan.  The pose evaluation and the outline walk are restated here rather
-// than shared with validate.hip / states.hip: those kernels read a launch-wide DevLayout, this one a row of the table.
+// bits dftpav_batch_validate gives for the same plan.  The read-out and the outline walk are piece_eval.h's and footprint.h's,
+// as in validate.hip / states.hip: those kernels read a launch-wide DevLayout, this one a row of the table.
 // fp64, no contraction, cr_trig.h wherever the reference calls libm: bit-identical to oracle_replan/replan_oracle.cpp in
 // order 2.  The kernel writes nothing into the table.
 //
 // publish_kernel, further down, is the other half of the server's loop: the 100 Hz publisher (PublishData, traj_server_ros.cpp:195-318).
 #include <hip/hip_runtime.h>
 
-#include "cr_trig.h"
 #include "plan_args.h"
 
 namespace dftpav {
-
-namespace {
-
-__device__ inline double rp_normalize_angle(double theta) { // calculations.cc:18-23
-  const double pi = 3.14159265358979323846;
-  double tmp = theta;
-  tmp -= (double)((theta >= pi) * 2) * pi;
-  tmp += (double)((theta < -pi) * 2) * pi;
-  return tmp;
-}
-
-__device__ inline bool rp_occupied(const ReplanArgs &A, double x, double y) {
-  const double cx = round((x - A.origin_x) / A.resolution), cy = round((y - A.origin_y) / A.resolution);
-  if (!(cx >= 0.0 && cx < (double)A.size_x && cy >= 0.0 && cy < (double)A.size_y)) return false;
-  return A.cells[(int)cx + A.size_x * (int)cy] == 80;
-}
-__device__ inline bool rp_edge_hits(const ReplanArgs &A, double ax, double ay, double bx, double by) {
-  const double dx = bx - ax, dy = by - ay;
-  const double norm = sqrt(dx * dx + dy * dy);
-  for (int j = 0; j < A.n_v; j++) {
-    const double dl = A.v_tab[j];
-    if (!(dl < norm)) break;
-    const double f = dl / norm;
-    if (rp_occupied(A, f * dx + ax, f * dy + ay)) return true;
-  }
-  return false;
-}
-
-// locatePieceIdx, poly_traj_utils.hpp:510-528, for a segment of N pieces of duration dtp each
-__device__ inline int rp_locate(int N, double dtp, double &tt) {
-  int idx = 0;
-  while (idx < N && tt > dtp) {
-    tt -= dtp;
-    idx++;
-  }
-  if (idx == N) {
-    idx--;
-    tt += dtp;
-  }
-  return idx;
-}
-__device__ inline void rp_pos(const double *c, double tt, double &px, double &py) { // Piece::getPos
-  px = 0.0;
-  py = 0.0;
-  double tn = 1.0;
-#pragma unroll
-  for (int k = 0; k <= 5; k++) {
-    px += tn * c[2 * k];
-    py += tn * c[2 * k + 1];
-    tn *= tt;
-  }
-}
-__device__ inline void rp_vel(const double *c, double tt, double &vx, double &vy) { // Piece::getdSigma
-  vx = 0.0;
-  vy = 0.0;
-  double tn = 1.0;
-#pragma unroll
-  for (int k = 1; k <= 5; k++) {
-    vx += (double)k * tn * c[2 * k];
-    vy += (double)k * tn * c[2 * k + 1];
-    tn *= tt;
-  }
-}
-__device__ inline void rp_acc(const double *c, double tt, double &ax, double &ay) { // Piece::getddSigma
-  ax = 0.0;
-  ay = 0.0;
-  double tn = 1.0;
-#pragma unroll
-  for (int k = 2; k <= 5; k++) {
-    ax += (double)((k - 1) * k) * tn * c[2 * k];
-    ay += (double)((k - 1) * k) * tn * c[2 * k + 1];
-    tn *= tt;
-  }
-}
-
-} // namespace
 
 __global__ void __launch_bounds__(256) replan_check_kernel(ReplanArgs A) {
   __shared__ int s_count[kMaxSeg + 1];  // samples of the segments before segment i
@@ -145,20 +68,8 @@ __global__ void __launch_bounds__(256) replan_check_kernel(ReplanArgs A) {
         for (int i = 0; i < M; i++) {
           s_piece0[i] = p0;
           p0 += pn[i];
-          // number of samples t_k < dur: the table is increasing; past its end the running sum is continued (validate.hip)
-          const double d = dur[i];
-          int lo = 0, hi = A.n_t;
-          while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (A.t_tab[mid] < d) lo = mid + 1;
-            else hi = mid;
-          }
-          int cnt = lo;
-          if (cnt == A.n_t) {
-            for (double t = A.t_tab[A.n_t - 1] + A.sample_dt; t < d; t += A.sample_dt) cnt++;
-          }
           s_count[i] = acc;
-          acc += cnt;
+          acc += pe::samples_below(A.tab, dur[i]);
         }
         s_count[M] = acc;
         s_piece0[M] = p0;
@@ -167,8 +78,8 @@ __global__ void __launch_bounds__(256) replan_check_kernel(ReplanArgs A) {
         double ltx, lty;
         {
           double tt = dur[last];
-          const int idx = rp_locate(pn[last], dtv[last], tt);
-          rp_pos(cb + (size_t)(s_piece0[last] + idx) * 12, tt, ltx, lty);
+          const int idx = pe::locate_piece(pn[last], dtv[last], tt);
+          pe::piece_pos(cb + (size_t)(s_piece0[last] + idx) * 12, tt, ltx, lty);
         }
         double total = 0.0;
         for (int i = 0; i < M; i++) total += dur[i];
@@ -200,29 +111,18 @@ __global__ void __launch_bounds__(256) replan_check_kernel(ReplanArgs A) {
         // Trajectory::GetState, poly_traj_utils.hpp:378-406
         double inner = t;
         if (inner > dur[pidx]) inner = dur[pidx];
-        const int idx = rp_locate(pn[pidx], dtv[pidx], inner);
+        const int idx = pe::locate_piece(pn[pidx], dtv[pidx], inner);
         const double *c = cb + (size_t)(s_piece0[pidx] + idx) * 12;
         double px, py, vx, vy, ax, ay;
-        rp_pos(c, inner, px, py);
-        rp_vel(c, inner, vx, vy);
-        rp_acc(c, inner, ax, ay);
-        const double sgn = (double)sg[pidx];
-        double angle = crt::atan2(sgn * vy, sgn * vx); // (the reference: libm; here correctly rounded, as oracle order 2)
-        const double vel = sgn * sqrt(vx * vx + vy * vy);
-        double curv = 0.0, ac = 0.0, steer = 0.0;
-        if (!(fabs(vel) < 1e-6)) {
-          curv = (vx * ay - vy * ax) / crt::cube_cr(vel); // (the reference: pow(vel, 3) of libm; here the correctly rounded cube)
-          ac = (vx * ax + vy * ay) / vel;
-          steer = crt::atan(A.wheel_base * curv);
-        }
+        pe::piece_pos(c, inner, px, py);
+        pe::piece_vel(c, inner, vx, vy);
+        pe::piece_acc(c, inner, ax, ay);
+        pe::StateTail g = pe::get_state_tail(vx, vy, ax, ay, (double)sg[pidx], A.wheel_base);
         if (T.have_hist[s]) { // FilterSingularityState against desired_state_hist_.back(), :335-356, :460
-          const double duration = stamp - T.hist[2 * (size_t)s];
           const double hist_angle = T.hist[2 * (size_t)s + 1];
-          const double max_rate = 0x1.fffffffffffffp-1 / 2.85 * 0.1; // tan(M_PI / 4) correctly rounded (what glibc returns)
-          const double max_change = max_rate * duration;
-          if (fabs(vel) < 0.1 && fabs(rp_normalize_angle(angle - hist_angle)) > max_change) angle = hist_angle;
+          if (pe::filter_singularity(g.angle, g.vel, hist_angle, stamp - T.hist[2 * (size_t)s])) g.angle = hist_angle;
         }
-        des[0] = stamp; des[1] = px; des[2] = py; des[3] = angle; des[4] = curv; des[5] = vel; des[6] = ac; des[7] = steer;
+        des[0] = stamp; des[1] = px; des[2] = py; des[3] = g.angle; des[4] = g.curv; des[5] = g.vel; des[6] = g.acc; des[7] = g.steer;
         have_des = true;
         go = 1;
       }
@@ -245,36 +145,18 @@ __global__ void __launch_bounds__(256) replan_check_kernel(ReplanArgs A) {
   // the collision loop of CheckReplan, :385-397, sample by sample as validate.hip
   const int total = s_count[M];
   for (int q = tid; q < total; q += blockDim.x) {
-    int i = 0;
-    while (i + 1 < M && q >= s_count[i + 1]) i++;
-    const int k = q - s_count[i];
-    double t;
-    if (k < A.n_t) {
-      t = A.t_tab[k];
-    } else {
-      t = A.t_tab[A.n_t - 1];
-      for (int j = A.n_t - 1; j < k; j++) t += A.sample_dt;
-    }
-    double tt = t;
-    const int idx = rp_locate(pn[i], dtv[i], tt);
+    const int i = pe::sample_segment(s_count, M, q);
+    double tt = pe::sample_time(A.tab, q - s_count[i]);
+    const int idx = pe::locate_piece(pn[i], dtv[i], tt);
     const double *c = cb + (size_t)(s_piece0[i] + idx) * 12;
     double px, py, vx, vy;
-    rp_pos(c, tt, px, py);
-    rp_vel(c, tt, vx, vy);
+    pe::piece_pos(c, tt, px, py);
+    pe::piece_vel(c, tt, vx, vy);
     const double sgn = (double)sg[i];
     const double yaw = crt::atan2(sgn * vy, sgn * vx);
-    // CheckCollisionUsingPosAndYaw, semantic_map_manager.cc:639-662 + shapes.cc:116-147
     double cs, sn;
     crt::sincos(yaw, sn, cs);
-    const double W = A.veh_width, Lv = A.veh_length;
-    const double x = px + A.veh_dcr * cs, y = py + A.veh_dcr * sn;
-    const double c1x = x + 0.5 * Lv * cs + 0.5 * W * sn, c1y = y + 0.5 * Lv * sn - 0.5 * W * cs;
-    const double c2x = x + 0.5 * Lv * cs - 0.5 * W * sn, c2y = y + 0.5 * Lv * sn + 0.5 * W * cs;
-    const double c3x = x - 0.5 * Lv * cs - 0.5 * W * sn, c3y = y - 0.5 * Lv * sn + 0.5 * W * cs;
-    const double c4x = x - 0.5 * Lv * cs + 0.5 * W * sn, c4y = y - 0.5 * Lv * sn - 0.5 * W * cs;
-    const bool hit = rp_edge_hits(A, c1x, c1y, c2x, c2y) || rp_edge_hits(A, c2x, c2y, c3x, c3y) ||
-                     rp_edge_hits(A, c3x, c3y, c4x, c4y) || rp_edge_hits(A, c4x, c4y, c1x, c1y) || rp_occupied(A, c1x, c1y) ||
-                     rp_occupied(A, c2x, c2y) || rp_occupied(A, c3x, c3y) || rp_occupied(A, c4x, c4y);
+    const bool hit = footprint_hits(A.grid, A.fp, px, py, cs, sn);
     if (hit) atomicMin(&s_first, q);
   }
   __syncthreads();
@@ -309,8 +191,7 @@ __global__ void __launch_bounds__(256) exec_adopt_kernel(ExecAdoptArgs A) {
       T.singul[(size_t)s * MS + i] = used ? A.q_singul[(size_t)q * MS + i] : 0;
       T.piece_nums[(size_t)s * MS + i] = N;
       T.coeff_dt[(size_t)s * MS + i] = dtp;
-      double d = 0.0; // Trajectory::getTotalDuration
-      for (int p = 0; p < N; p++) d += dtp;
+      const double d = pe::segment_duration(N, dtp);
       T.duration[(size_t)s * MS + i] = used ? d : 0.0;
       T.start_time[(size_t)s * MS + i] = used ? world : 0.0;
       T.end_time[(size_t)s * MS + i] = used ? world + d : 0.0;
@@ -395,30 +276,21 @@ __global__ void __launch_bounds__(kPubChunk) publish_kernel(PublishArgs A) {
       // Trajectory::GetState(t - start_time), poly_traj_utils.hpp:378-406
       double inner = t - st[seg];
       if (inner > dur[seg]) inner = dur[seg];
-      const int idx = rp_locate(pn[seg], dtv[seg], inner);
+      const int idx = pe::locate_piece(pn[seg], dtv[seg], inner);
       const double *c = cb + (size_t)(s_piece0[seg] + idx) * 12;
       double px, py, vx, vy, ax, ay;
-      rp_pos(c, inner, px, py);
-      rp_vel(c, inner, vx, vy);
-      rp_acc(c, inner, ax, ay);
-      const double sgn = (double)sg[seg];
-      const double angle = crt::atan2(sgn * vy, sgn * vx);
-      const double vel = sgn * sqrt(vx * vx + vy * vy);
-      double curv = 0.0, ac = 0.0, steer = 0.0;
-      if (!(fabs(vel) < 1e-6)) {
-        curv = (vx * ay - vy * ax) / crt::cube_cr(vel);
-        ac = (vx * ax + vy * ay) / vel;
-        steer = crt::atan(A.wheel_base * curv);
-      }
-      row[0] = t; row[1] = px; row[2] = py; row[3] = angle; row[4] = curv; row[5] = vel; row[6] = ac; row[7] = steer;
-      s_ang[tid] = angle;
-      s_vel[tid] = vel;
+      pe::piece_pos(c, inner, px, py);
+      pe::piece_vel(c, inner, vx, vy);
+      pe::piece_acc(c, inner, ax, ay);
+      const pe::StateTail g = pe::get_state_tail(vx, vy, ax, ay, (double)sg[seg], A.wheel_base);
+      row[0] = t; row[1] = px; row[2] = py; row[3] = g.angle; row[4] = g.curv; row[5] = g.vel; row[6] = g.acc; row[7] = g.steer;
+      s_ang[tid] = g.angle;
+      s_vel[tid] = g.vel;
     }
     __syncthreads();
     if (tid == 0) { // the filter chain: FilterSingularityState against ctrl_state_hist_.back(), then push_back (:257-258)
       int have = s_have;
       double h_stamp = s_hist[0], h_angle = s_hist[1];
-      const double max_rate = 0x1.fffffffffffffp-1 / 2.85 * 0.1; // tan(M_PI / 4) correctly rounded, as replan_check_kernel
       for (int j = 0; j < nk; j++) {
         int code = 0;
         if (s_seg[j] >= 0) {
@@ -426,9 +298,7 @@ __global__ void __launch_bounds__(kPubChunk) publish_kernel(PublishArgs A) {
           double angle = s_ang[j];
           code = 1;
           if (have) {
-            const double duration = t - h_stamp;
-            const double max_change = max_rate * duration;
-            if (fabs(s_vel[j]) < 0.1 && fabs(rp_normalize_angle(angle - h_angle)) > max_change) {
+            if (pe::filter_singularity(angle, s_vel[j], h_angle, t - h_stamp)) {
               angle = h_angle;
               code = 2;
             }

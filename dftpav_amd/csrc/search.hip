@@ -24,7 +24,6 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/dftpav_hip.h"
-#include "cr_trig.h"
 #include "device_types.h"
 #include "kino_heap.h"
 #include "rs_math.h"
@@ -41,13 +40,6 @@ struct CrMath { // the shot's elementary functions, correctly rounded
   DFTPAV_HD static double atan2(double y, double x) { return crt::atan2(y, x); }
 };
 
-__device__ inline double sr_normalize_angle(double theta) { // calculations.cc:18-23
-  const double pi = 3.14159265358979323846;
-  double tmp = theta;
-  tmp -= (double)((theta >= pi) * 2) * pi;
-  tmp += (double)((theta < -pi) * 2) * pi;
-  return tmp;
-}
 // stateTransit, kino_astar.cpp:21-36 (psi != 0 takes the curved branch, however small psi is)
 __device__ inline void sr_transit(const SearchArgs &A, double x0, double y0, double yaw0, double psi, double s, double *o) {
   if (psi != 0) {
@@ -61,38 +53,14 @@ __device__ inline void sr_transit(const SearchArgs &A, double x0, double y0, dou
     o[2] = yaw0;
   }
 }
-__device__ inline bool sr_occupied(const SearchArgs &A, double x, double y) {
-  const double cx = round((x - A.origin_x) / A.resolution), cy = round((y - A.origin_y) / A.resolution);
-  if (!(cx >= 0.0 && cx < (double)A.size_x && cy >= 0.0 && cy < (double)A.size_y)) return false;
-  return A.cells[(int)cx + A.size_x * (int)cy] == 80;
-}
-__device__ inline bool sr_edge_hits(const SearchArgs &A, double ax, double ay, double bx, double by) {
-  const double dx = bx - ax, dy = by - ay;
-  const double norm = sqrt(dx * dx + dy * dy);
-  for (int j = 0; j < A.n_v; j++) {
-    const double dl = A.v_tab[j];
-    if (!(dl < norm)) break;
-    const double f = dl / norm;
-    if (sr_occupied(A, f * dx + ax, f * dy + ay)) return true;
-  }
-  return false;
-}
-// CheckIfCollisionUsingPosAndYaw with the search's vehicle (vp_ + 0.2 m, kino_astar.cpp:426-427)
+// CheckIfCollisionUsingPosAndYaw with the search's vehicle (A.fp: vp_ + 0.2 m, kino_astar.cpp:426-427)
 __device__ inline bool sr_collides(const SearchArgs &A, double px, double py, double yaw) {
   double cs, sn;
   crt::sincos(yaw, sn, cs);
-  const double W = A.sp.veh_width, Lv = A.sp.veh_length;
-  const double x = px + A.sp.veh_d_cr * cs, y = py + A.sp.veh_d_cr * sn;
-  const double c1x = x + 0.5 * Lv * cs + 0.5 * W * sn, c1y = y + 0.5 * Lv * sn - 0.5 * W * cs;
-  const double c2x = x + 0.5 * Lv * cs - 0.5 * W * sn, c2y = y + 0.5 * Lv * sn + 0.5 * W * cs;
-  const double c3x = x - 0.5 * Lv * cs - 0.5 * W * sn, c3y = y - 0.5 * Lv * sn + 0.5 * W * cs;
-  const double c4x = x - 0.5 * Lv * cs + 0.5 * W * sn, c4y = y - 0.5 * Lv * sn - 0.5 * W * cs;
-  return sr_edge_hits(A, c1x, c1y, c2x, c2y) || sr_edge_hits(A, c2x, c2y, c3x, c3y) || sr_edge_hits(A, c3x, c3y, c4x, c4y) ||
-         sr_edge_hits(A, c4x, c4y, c1x, c1y) || sr_occupied(A, c1x, c1y) || sr_occupied(A, c2x, c2y) || sr_occupied(A, c3x, c3y) ||
-         sr_occupied(A, c4x, c4y);
+  return footprint_hits(A.grid, A.fp, px, py, cs, sn);
 }
 __device__ inline int sr_yaw_index(const SearchArgs &A, double yaw) { // yawToIndex, kino_astar.cpp:811-816
-  yaw = sr_normalize_angle(yaw);
+  yaw = pe::normalize_angle(yaw);
   return (int)floor((yaw - (-3.14159265358979323846)) * A.inv_yaw_res);
 }
 __device__ inline unsigned sr_hash(int ix, int iy, int iyaw) {
@@ -448,11 +416,11 @@ __global__ void __launch_bounds__(kSearchThreads) search_kernel(SearchArgs A) {
       sr_transit(A, pa.x, pa.y, pa.yaw, nd.steer, nd.arc * double(P.check_num) / double(P.check_num), o);
       S.last[0] = o[0];
       S.last[1] = o[1];
-      S.last[2] = sr_normalize_angle(o[2]);
+      S.last[2] = pe::normalize_angle(o[2]);
     } else {
       S.last[0] = st[0];
       S.last[1] = st[1];
-      S.last[2] = sr_normalize_angle(st[2]);
+      S.last[2] = pe::normalize_angle(st[2]);
     }
   }
   __syncthreads();
@@ -473,7 +441,7 @@ __global__ void __launch_bounds__(kSearchThreads) search_kernel(SearchArgs A) {
   if (lane == 0 && O.max_path > 0) {
     path[0] = st[0];
     path[1] = st[1];
-    path[2] = sr_normalize_angle(st[2]);
+    path[2] = pe::normalize_angle(st[2]);
   }
   for (int w = lane; w < (m - 1) * cn; w += kSearchThreads) {
     const int idx = 1 + w;
@@ -484,7 +452,7 @@ __global__ void __launch_bounds__(kSearchThreads) search_kernel(SearchArgs A) {
     sr_transit(A, pa.x, pa.y, pa.yaw, nd.steer, nd.arc * double(k) / double(cn), o);
     path[3 * idx] = o[0];
     path[3 * idx + 1] = o[1];
-    path[3 * idx + 2] = sr_normalize_angle(o[2]);
+    path[3 * idx + 2] = pe::normalize_angle(o[2]);
   }
   int len = base;
   if (S.shot) {
@@ -521,12 +489,12 @@ __global__ void __launch_bounds__(kSearchThreads) search_kernel(SearchArgs A) {
       }
       path[3 * idx] = s[0];
       path[3 * idx + 1] = s[1];
-      path[3 * idx + 2] = sr_normalize_angle(s[2]);
+      path[3 * idx + 2] = pe::normalize_angle(s[2]);
     }
     if (lane == 0 && base + n2 < O.max_path) {
       path[3 * (base + n2)] = en[0];
       path[3 * (base + n2) + 1] = en[1];
-      path[3 * (base + n2) + 2] = sr_normalize_angle(en[2]);
+      path[3 * (base + n2) + 2] = pe::normalize_angle(en[2]);
     }
     len = base + n2 + 1;
   }

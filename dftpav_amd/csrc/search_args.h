@@ -1,6 +1,8 @@
 // search_args.h — what the host half of dftpav_kino_search (capi.cpp) hands the search kernel (search.hip).
 #pragma once
 #include "../../include/dftpav_hip.h"
+#include "footprint.h"
+#include "piece_eval.h"
 
 namespace dftpav {
 
@@ -17,11 +19,8 @@ struct SearchNode { // PathNode, kino_astar.h:42-61
 
 struct SearchArgs {
   dftpav_search_params sp;
-  const unsigned char *cells;
-  int size_x, size_y;
-  double resolution, origin_x, origin_y;
-  const double *v_tab; // outline point spacing: vertex_res, + vertex_res, ...
-  int n_v;
+  DevGrid grid;
+  DevFootprint fp; // the search's own vehicle, from sp (veh_*: vp_ + 0.2 m, kino_astar.cpp:426-427)
   const double *l_tab; // shot sample offsets: 0, checkl, checkl + checkl, ...
   int n_l;
   const double *in_tab; // [3][kSearchMaxIn][2] (steer, arc): first expansion forward, backward, later expansions

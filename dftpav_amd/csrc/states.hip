@@ -11,12 +11,13 @@
 // piece come from L1/L2).  The server's singularity filter is the only sequential part: it holds the
 // heading of a near-standstill sample at the previously *published* heading.  A sample moving faster than
 // 0.1 m/s is never touched, so the chain only runs inside a run of consecutive slow samples; the first
-// thread of each run replays its run in order, all runs in parallel.  fp64, no contraction, portable
-// atan2 / atan: bit-identical to oracle/states_oracle.cpp in order 1.
+// thread of each run replays its run in order, all runs in parallel.  fp64, no contraction, cr_trig.h's
+// atan2 / cube / atan where the reference calls libm: bit-identical to oracle/states_oracle.cpp in order 2.
+// GetState and the filter's rule are piece_eval.h's.
 #include <hip/hip_runtime.h>
 
 #include "device_types.h"
-#include "traj_math.h"
+#include "piece_eval.h"
 
 namespace dftpav {
 
@@ -31,14 +32,6 @@ struct StatesArgs {
   int *n_valid;   // [B]
 };
 
-__device__ inline double s_normalize_angle(double theta) { // calculations.cc:18-23
-  const double pi = 3.14159265358979323846;
-  double tmp = theta;
-  tmp -= (double)((theta >= pi) * 2) * pi;
-  tmp += (double)((theta < -pi) * 2) * pi;
-  return tmp;
-}
-
 __global__ void __launch_bounds__(256) states_kernel(StatesArgs A) {
   __shared__ double s_start[kMaxSeg], s_dur[kMaxSeg], s_end[kMaxSeg];
   __shared__ int s_valid;
@@ -49,8 +42,7 @@ __global__ void __launch_bounds__(256) states_kernel(StatesArgs A) {
     double world = 0.0;
     for (int i = 0; i < M; i++) {
       const double dtp = A.piece_dt[(size_t)b * M + i];
-      double d = 0.0;
-      for (int p = 0; p < L.piece_nums[i]; p++) d += dtp;
+      const double d = pe::segment_duration(L.piece_nums[i], dtp);
       s_start[i] = world;
       s_dur[i] = d;
       s_end[i] = world + d;
@@ -74,51 +66,14 @@ __global__ void __launch_bounds__(256) states_kernel(StatesArgs A) {
     atomicMax(&s_valid, k + 1);
     double inner = t - s_start[i];
     if (inner > s_dur[i]) inner = s_dur[i];
-    const int N = L.piece_nums[i];
-    const double dtp = A.piece_dt[(size_t)b * M + i];
-    int idx = 0;
-    while (idx < N && inner > dtp) {
-      inner -= dtp;
-      idx++;
-    }
-    if (idx == N) {
-      idx--;
-      inner += dtp;
-    }
+    const int idx = pe::locate_piece(L.piece_nums[i], A.piece_dt[(size_t)b * M + i], inner);
     const double *c = cb + (size_t)(L.seg_piece0[i] + idx) * 12;
-    double px = 0.0, py = 0.0, tn = 1.0;
-#pragma unroll
-    for (int q = 0; q <= 5; q++) {
-      px += tn * c[2 * q];
-      py += tn * c[2 * q + 1];
-      tn *= inner;
-    }
-    double vx = 0.0, vy = 0.0;
-    tn = 1.0;
-#pragma unroll
-    for (int q = 1; q <= 5; q++) {
-      vx += (double)q * tn * c[2 * q];
-      vy += (double)q * tn * c[2 * q + 1];
-      tn *= inner;
-    }
-    double ax = 0.0, ay = 0.0;
-    tn = 1.0;
-#pragma unroll
-    for (int q = 2; q <= 5; q++) {
-      ax += (double)((q - 1) * q) * tn * c[2 * q];
-      ay += (double)((q - 1) * q) * tn * c[2 * q + 1];
-      tn *= inner;
-    }
-    const double sg = (double)L.singuls[i];
-    const double angle = crt::atan2(sg * vy, sg * vx); // (the reference: libm; here correctly rounded, as oracle order 2)
-    const double vel = sg * sqrt(vx * vx + vy * vy);
-    double curv = 0.0, acc = 0.0, steer = 0.0;
-    if (!(fabs(vel) < 1e-6)) {
-      curv = (vx * ay - vy * ax) / crt::cube_cr(vel); // (the reference: pow(vel, 3) of libm; here the correctly rounded cube)
-      acc = (vx * ax + vy * ay) / vel;
-      steer = crt::atan(A.wheel_base * curv);
-    }
-    s[0] = t; s[1] = px; s[2] = py; s[3] = angle; s[4] = curv; s[5] = vel; s[6] = acc; s[7] = steer;
+    double px, py, vx, vy, ax, ay;
+    pe::piece_pos(c, inner, px, py);
+    pe::piece_vel(c, inner, vx, vy);
+    pe::piece_acc(c, inner, ax, ay);
+    const pe::StateTail g = pe::get_state_tail(vx, vy, ax, ay, (double)L.singuls[i], A.wheel_base);
+    s[0] = t; s[1] = px; s[2] = py; s[3] = g.angle; s[4] = g.curv; s[5] = g.vel; s[6] = g.acc; s[7] = g.steer;
   }
   __syncthreads(); // the raw samples of this trajectory are visible to the whole workgroup
   const int valid = s_valid;
@@ -126,18 +81,18 @@ __global__ void __launch_bounds__(256) states_kernel(StatesArgs A) {
   if (!A.filter) return;
   // FilterSingularityState: a slow sample (|v| < kBigEPS) takes the previous published heading when its own
   // differs from it by more than the steering limit allows.  Run heads replay their runs.
-  const double max_rate = 0x1.fffffffffffffp-1 / 2.85 * 0.1; // tan(M_PI / 4) as glibc returns it
   for (int k = tid; k < valid; k += blockDim.x) {
     if (k == 0) continue; // empty history: the first sample is published as it is
     const bool slow = fabs(out[8 * (size_t)k + 5]) < 0.1;
     const bool prev_slow = k > 1 && fabs(out[8 * (size_t)(k - 1) + 5]) < 0.1; // sample 0 is never rewritten: it can feed, not join
     if (!slow || prev_slow) continue;
     double hist_angle = out[8 * (size_t)(k - 1) + 3], hist_t = out[8 * (size_t)(k - 1)];
-    for (int j = k; j < valid && fabs(out[8 * (size_t)j + 5]) < 0.1; j++) {
+    for (int j = k; j < valid; j++) {
+      const double vel = out[8 * (size_t)j + 5];
+      if (!(fabs(vel) < 0.1)) break; // the run ends
       const double t = out[8 * (size_t)j];
       double angle = out[8 * (size_t)j + 3];
-      const double max_change = max_rate * (t - hist_t);
-      if (fabs(s_normalize_angle(angle - hist_angle)) > max_change) {
+      if (pe::filter_singularity(angle, vel, hist_angle, t - hist_t)) {
         angle = hist_angle;
         out[8 * (size_t)j + 3] = angle;
       }

@@ -134,6 +134,28 @@ def test_crafted_coefficients(hiplib):
     h.close()
 
 
+def test_samples_past_the_table_of_sample_times(hiplib):
+    """A segment with more samples than the 4096 the host tabulates: the count and the times past the table's end are the running
+    sum continued on the device.  |velocity| rises to the end (1 m/s + 0.5 m/s^2 over 4 pieces of 1 s), so its arg lies there."""
+    n_pieces, dT, v0, a, check_dt = 4, 1.0, 1.0, 0.5, 0.0009
+    co = np.zeros((1, n_pieces, 6, 2))
+    for p in range(n_pieces):
+        t = p * dT
+        co[0, p, :3, 0] = (v0 * t + 0.5 * a * t * t, v0 + a * t, 0.5 * a)
+    h = hiplib.Handle()
+    got, ref = _crafted(hiplib, h, [n_pieces], [1], co, [[dT]], check_dt, hiplib.default_limits())
+    print("n_samples", ref["n_samples"].tolist(), "max", got["max_abs"][0].tolist(), "arg", got["arg"][0].tolist())
+    duration, t, n = 0.0, 0.0, 0
+    for _ in range(n_pieces):
+        duration += dT
+    while t < duration:
+        t += check_dt
+        n += 1
+    assert n > 4096 and ref["n_samples"][0] == n
+    assert ref["arg"][0, 0] > 4096 and got["arg"][0, 0] == n - 1 and got["feasible"][0] == 1
+    h.close()
+
+
 def _oracle_on_table(pl, n_slots, check_dt, limits):
     """the oracle on dftpav_planner_executing's read-back of every slot"""
     ex = [pl.executing(s) for s in range(n_slots)]

@@ -64,7 +64,7 @@ def _oracle_table(scene):
     return T
 
 
-def _validate_on_device(hiplib, h, singul, piece_nums, coeffs, coeff_dt):
+def _validate_on_device(hiplib, h, singul, piece_nums, coeffs, coeff_dt, sample_dt=0.05):
     """dftpav_batch_validate of one plan uploaded as a batch of its layout (test hook dftpav_debug_batch_set_coeffs)"""
     lay = LayoutSpec([int(v) for v in piece_nums], [int(v) for v in singul], 4)
     bt = hiplib.Batch(h, lay, 1)
@@ -73,7 +73,7 @@ def _validate_on_device(hiplib, h, singul, piece_nums, coeffs, coeff_dt):
     co = np.ascontiguousarray(coeffs[:lay.n_pieces], dtype=np.float64)
     dt = np.ascontiguousarray(coeff_dt[:lay.M], dtype=np.float64)
     assert fn(bt._b, co.ctypes.data_as(C.c_void_p), dt.ctypes.data_as(C.c_void_p)) == 0
-    col, first = bt.validate(sample_dt=0.05, vertex_res=0.1)
+    col, first = bt.validate(sample_dt=sample_dt, vertex_res=0.1)
     bt.close()
     return int(col[0]), int(first[0])
 
@@ -141,6 +141,78 @@ def test_check_refuses_an_outline_beyond_its_table_and_stays_usable(hiplib, scen
     for k in CHECK_KEYS:
         assert np.array_equal(before[k], after[k]), k
     assert before["collision"].sum() >= 1   # (the scene's check is not trivially empty)
+    pl.close()
+    h.close()
+
+
+N_TABLE = 4096      # sample times the host tabulates (validation_table); later ones continue the running sum on the device
+LONG_DT = 0.0009    # 4 s of plan: 4445 samples
+
+
+@pytest.fixture(scope="module")
+def long_plan(oracle):
+    """One plan whose collision samples run past the table of sample times: 4 pieces of 1 s straight along +x at 2 m/s from the
+    origin, and a wall across the map that the front of the vehicle (3.455 m ahead of the pose) only reaches at t ~ 3.82 s.  With
+    the oracle's verdict (order 2) at LONG_DT, computed once."""
+    co = np.zeros((4, 6, 2))
+    co[:, 0, 0] = 2.0 * np.arange(4)
+    co[:, 1, 0] = 2.0
+    plan = dict(singul=[1], piece_nums=[4], coeff_dt=[1.0], coeffs=co, end_state=[8.0, 0.0, 0.0, 0.0], t_start=0.0, hist=None)
+    grid = np.zeros((50, 120), dtype=np.uint8)       # 0.2 m cells from (-5, -5): x up to 19 m
+    grid[:, 81] = 80                                 # x in [11.1, 11.3)
+    scene = dict(slots=[plan], grid=grid, resolution=0.2, origin=(-5.0, -5.0))
+    col, first = oracle.validate_trajectories(grid, 0.2, (-5.0, -5.0), co[None], [[1.0]], [4], [1], sample_dt=LONG_DT, order=2)
+    scene["validate"] = (int(col[0]), int(first[0]))
+    assert col[0] == 1 and first[0] > N_TABLE         # the verdict cannot come from the table alone
+    return scene
+
+
+def _samples_below(duration, dt):
+    t, k = 0.0, 0
+    while t < duration:                               # traj_server_ros.cpp:386
+        t += dt
+        k += 1
+    return k
+
+
+def test_validate_past_the_sample_table(hiplib, long_plan):
+    """dftpav_batch_validate where a segment has more samples than the host tabulates: the count and the times past the table's end
+    are the continued running sum, the first colliding sample lies there, equal to oracle.validate in order 2."""
+    h = hiplib.Handle()
+    h.set_grid_map(long_plan["grid"], long_plan["resolution"], long_plan["origin"])
+    pl = hiplib.Planner(h, 1, R)
+    _install_long(pl, long_plan)
+    assert _samples_below(float(pl.executing(0)["duration"][0]), LONG_DT) > N_TABLE
+    p = long_plan["slots"][0]
+    got = _validate_on_device(hiplib, h, p["singul"], p["piece_nums"], p["coeffs"], np.array(p["coeff_dt"]), sample_dt=LONG_DT)
+    print("validate:", got, "oracle:", long_plan["validate"])
+    assert got == long_plan["validate"]
+    pl.close()
+    h.close()
+
+
+def _install_long(pl, long_plan):
+    pad = rs.padded(long_plan)
+    pl.install(pad["slots"], pad["n_seg"], pad["singul"], pad["piece_nums"], pad["coeff_dt"], pad["coeffs"], pad["end_states"], t_start=0.0)
+
+
+def test_check_past_the_sample_table(hiplib, long_plan):
+    """dftpav_replan_check on the same plan in a slot of the table: every field equal to oracle_replan, the collision fields to
+    the validation's."""
+    h = hiplib.Handle()
+    h.set_grid_map(long_plan["grid"], long_plan["resolution"], long_plan["origin"])
+    pl = hiplib.Planner(h, 1, R)
+    _install_long(pl, long_plan)
+    assert _samples_below(float(pl.executing(0)["duration"][0]), LONG_DT) > N_TABLE
+    p = long_plan["slots"][0]
+    T = pr.Table(1)
+    T.install(0, p["singul"], p["piece_nums"], p["coeff_dt"], p["coeffs"], p["end_state"], p["t_start"])
+    got = pl.check(0.5, 0.5, check_dt=LONG_DT)
+    ref = pr.replan_check(long_plan["grid"], long_plan["resolution"], long_plan["origin"], T, 0.5, 0.5, check_dt=LONG_DT, order=2)
+    print("check:", int(got["collision"][0]), int(got["first_sample"][0]), "oracle_replan:", int(ref["collision"][0]), int(ref["first_sample"][0]))
+    for k in CHECK_KEYS:
+        assert np.array_equal(got[k], ref[k]), k
+    assert (int(got["collision"][0]), int(got["first_sample"][0])) == long_plan["validate"]
     pl.close()
     h.close()
 
