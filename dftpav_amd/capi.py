@@ -24,6 +24,8 @@ PUBLISH_CHUNK, PUBLISH_MAX_TICKS = 256, 4096   # DFTPAV_PUBLISH_CHUNK, DFTPAV_PU
 # plan_status of dftpav_plan_queries (DFTPAV_PLAN_*); search status (DFTPAV_SEARCH_*)
 PLAN_OK, PLAN_NO_PATH, PLAN_TOO_MANY_SEGMENTS, PLAN_LAYOUT_UNSUPPORTED, PLAN_NO_VALID_RESTART, PLAN_ARRIVED = 0, 1, 2, 3, 4, 5
 SEARCH_REACH_END, SEARCH_NO_PATH = 2, 3
+# columns of dftpav_batch_cost_terms (DFTPAV_TERM_*)
+TERM_SMOOTH, TERM_TIME, TERM_CORRIDOR, TERM_SURROUND, TERM_FEAS, COST_TERMS = 0, 1, 2, 3, 4, 5
 
 # every symbol include/dftpav_hip.h declares
 EXPORTS = [
@@ -48,6 +50,7 @@ EXPORTS = [
     "dftpav_planner_publish", "dftpav_planner_publisher_state", "dftpav_planner_set_ctrl_history", "dftpav_publish_last_ms",
     "dftpav_default_limits", "dftpav_batch_check_limits", "dftpav_planner_check_limits", "dftpav_planner_set_limit_filter",
     "dftpav_planner_last_limits", "dftpav_limits_last_ms",
+    "dftpav_batch_cost_terms", "dftpav_planner_set_penalty_filter", "dftpav_planner_last_cost_terms", "dftpav_debug_penalty_gate",
 ]
 
 
@@ -177,6 +180,14 @@ class LimitsOut:
 
     def arrays(self):
         return self.a
+
+
+class PenaltyCaps(C.Structure):
+    """dftpav_penalty_caps: the most a solved restart may keep of each penalty sum; +inf: not judged"""
+    _fields_ = [("corridor", C.c_double), ("surround", C.c_double), ("feasibility", C.c_double)]
+
+    def __init__(self, corridor=float("inf"), surround=float("inf"), feasibility=float("inf")):
+        super().__init__(float(corridor), float(surround), float(feasibility))
 
 
 def default_limits(params=None):
@@ -654,6 +665,23 @@ class Planner:
         self.handle._check(fn(self._p, C.byref(out.c)), "planner_last_limits")
         return out.arrays()
 
+    # ---- the residual penalties of solved plans
+    def set_penalty_filter(self, caps=None):
+        """dftpav_planner_set_penalty_filter: None switches the filter off (the default)"""
+        fn = lib().dftpav_planner_set_penalty_filter
+        fn.argtypes = [C.c_void_p, C.c_void_p]
+        self.handle._check(fn(self._p, C.byref(caps) if caps is not None else None), "planner_set_penalty_filter")
+
+    def last_cost_terms(self, Q):
+        """dftpav_planner_last_cost_terms: (r_terms [Q][R][5], r_rejected [Q][R]) of the last plan() of Q queries that ran with the
+        penalty filter on"""
+        terms = np.zeros((int(Q), self.n_restarts, COST_TERMS))
+        rej = np.zeros((int(Q), self.n_restarts), dtype=np.int32)
+        fn = lib().dftpav_planner_last_cost_terms
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        self.handle._check(fn(self._p, terms.ctypes.data_as(C.c_void_p), rej.ctypes.data_as(C.c_void_p)), "planner_last_cost_terms")
+        return terms, rej
+
     def publish_last_ms(self):
         """dftpav_publish_last_ms: device ms of the last publish kernel (0.0 before the first)"""
         a = C.c_float(0.0)
@@ -689,6 +717,20 @@ def debug_plan_select(handle, cost, success, collision):
     ptr = lambda a: a.ctypes.data_as(C.c_void_p)
     handle._check(fn(handle._h, nq, R, ptr(c), ptr(s), ptr(k), ptr(w)), "debug_plan_select")
     return w
+
+
+def debug_penalty_gate(handle, terms, caps, flags_in):
+    """dftpav_debug_penalty_gate: the gate kernel on terms [n][5] and flags_in [n] -> (flags_out [n], rejected [n])"""
+    t = np.ascontiguousarray(terms, dtype=np.float64).reshape(-1, COST_TERMS)
+    fi = np.ascontiguousarray(flags_in, dtype=np.int32).reshape(-1)
+    n = t.shape[0]
+    assert fi.shape[0] == n
+    fo, rj = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    fn = lib().dftpav_debug_penalty_gate
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    handle._check(fn(handle._h, n, ptr(t), C.byref(caps), ptr(fi), ptr(fo), ptr(rj)), "debug_penalty_gate")
+    return fo, rj
 
 
 def debug_validation_table(params, check_dt, vertex_res, max_spacings=0):
@@ -804,6 +846,19 @@ class Batch:
         g = np.zeros((self.B, self.n))
         self.handle._check(lib().dftpav_batch_eval(self._b, dptr(x), dptr(f), dptr(g)), "batch_eval")
         return f, g
+
+    def cost_terms(self, x=None):
+        """dftpav_batch_cost_terms (reference order): the cost of eval(x) term by term -> (terms [B][5], seg_terms [B][M][5]);
+        x None: at the solution of the last solve"""
+        if x is not None:
+            x = np.ascontiguousarray(x, dtype=np.float64).reshape(self.B, self.n)
+        terms = np.zeros((self.B, COST_TERMS))
+        seg = np.zeros((self.B, self.layout.M, COST_TERMS))
+        fn = lib().dftpav_batch_cost_terms
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        self.handle._check(fn(self._b, ptr(x) if x is not None else None, ptr(terms), ptr(seg)), "batch_cost_terms")
+        return terms, seg
 
     def solve_async(self):
         self.handle._check(lib().dftpav_batch_solve_async(self._b), "solve_async")

@@ -459,7 +459,7 @@ extern "C" void dftpav_batch_destroy(dftpav_batch *b) {
                   b->d_x_in, b->d_x_out, b->d_f, b->d_g, b->d_status, b->d_success, b->d_iters, b->d_evals,
                   b->d_hist, b->d_ticks, b->d_prof, b->d_dev, b->d_coef, b->d_dt, b->d_records,
                   b->d_queue, b->d_stragglers, b->d_stragglers2, b->d_sflag, b->d_iota, b->d_qctl, b->d_state, b->d_dev2,
-                  b->d_f_eval, b->d_trace, b->d_cor_raw, b->d_ref_tab, b->d_ref_scratch, b->d_cor_t, b->d_rect_flag, b->pc.d_poses, b->pc.d_tab, b->pc.d_rd, b->pc.d_col, b->pc.d_first,
+                  b->d_f_eval, b->d_terms, b->d_trace, b->d_cor_raw, b->d_ref_tab, b->d_ref_scratch, b->d_cor_t, b->d_rect_flag, b->pc.d_poses, b->pc.d_tab, b->pc.d_rd, b->pc.d_col, b->pc.d_first,
                   b->pc.d_valid};
   {
     auto &v = b->h->batches;
@@ -747,6 +747,7 @@ static int batch_create_impl(dftpav_handle *h, const dftpav_layout *layout, int 
   }
   BCHK(hipMalloc(&b->d_coef, sizeof(double) * (size_t)B * 12 * L.Ntot));
   BCHK(hipMalloc(&b->d_dt, sizeof(double) * (size_t)B * M));
+  BCHK(hipMalloc(&b->d_terms, sizeof(double) * (size_t)B * kCostTerms * (M + 1))); // terms [B][5] | seg_terms [B][M][5]
   BCHK(hipEventCreate(&b->ev0));
   BCHK(hipEventCreate(&b->ev1));
   // constraint point -> (piece, j) tables, the pointid order of traj_optimizer.cpp:486-514
@@ -973,6 +974,8 @@ static DevBatch make_dev(dftpav_batch *b) {
   D.prof = b->prof_on ? b->d_prof : nullptr;
   D.coef_out = b->d_coef;
   D.dt_out = b->d_dt;
+  D.terms_out = b->d_terms;
+  D.seg_terms_out = b->d_terms + (size_t)b->B * kCostTerms;
   D.trace = b->d_trace;
   D.trace_b = b->trace_b;
   D.trace_cap = b->trace_cap;
@@ -1100,7 +1103,7 @@ extern "C" int dftpav_batch_get_trace(dftpav_batch *b, double *out, int *n_evals
 // every launch of the solve kernel for a batch goes through here: the reference-order kernel when the batch asks for it
 static hipError_t launch_ref(dftpav_batch *b, const DevBatch &D, int mode, int scheduled) {
   const RefPlan &pl = b->ref_plan;
-  if (pl.kind < kRefQuad || mode == kModeCoeffs)
+  if (pl.kind < kRefQuad || mode == kModeCoeffs || mode >= kModeTerms) // (the read-outs: the TEAM / WAVE kernel for every plan)
     return launch_solver_ref(D, b->d_dev, mode, b->d_ref_tab, b->d_ref_scratch, pl, scheduled, b->h->stream);
   // the QUAD shapes read their own layout of the corridor; the one-segment kernel's fast instance (H = 4, help_eps == 0.0) reads a
   // batch of rectangles as 10 doubles per point (solver_ref4.hip: RECT)
@@ -1346,6 +1349,42 @@ extern "C" int dftpav_batch_eval(dftpav_batch *b, const double *x, double *f, do
   HIPCHK(h, launch_for(b, D, kModeEval));
   if (f) HIPCHK(h, hipMemcpyAsync(f, b->d_f_eval, sizeof(double) * b->B, hipMemcpyDeviceToHost, h->stream));
   if (g) HIPCHK(h, hipMemcpyAsync(g, b->d_g, sizeof(double) * nb, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return DFTPAV_OK;
+}
+
+static_assert(DFTPAV_COST_TERMS == kCostTerms && DFTPAV_TERM_SMOOTH == kTermSmooth && DFTPAV_TERM_TIME == kTermTime &&
+                  DFTPAV_TERM_CORRIDOR == kTermCorridor && DFTPAV_TERM_SURROUND == kTermSurround && DFTPAV_TERM_FEAS == kTermFeas,
+              "the kernels' order of the cost's terms is the C-ABI's");
+// the terms launch of a reference-order batch on the handle's stream, nothing waits: d_x == nullptr: at the solution (x_out), else at
+// d_x [B][n] in device memory.  The results are b->d_terms (terms [B][5], then seg_terms [B][M][5] from B * 5 doubles on, B the
+// batch's capacity).
+int dftpav::cost_terms_on_stream(dftpav_batch *b, const double *d_x) {
+  dftpav_handle *h = b->h;
+  if (b->order != DFTPAV_ORDER_REFERENCE) return DFTPAV_E_UNSUPPORTED;
+  const int nb = b->n_active > 0 ? b->n_active : b->B;
+  if (d_x && d_x != b->d_x_in)
+    HIPCHK(h, hipMemcpyAsync(b->d_x_in, d_x, sizeof(double) * (size_t)nb * b->L.n, hipMemcpyDeviceToDevice, h->stream));
+  DevBatch D;
+  if (int rc = sync_dev(b, D)) return rc;
+  HIPCHK(h, launch_for(b, D, d_x ? kModeTerms : kModeTermsSolved));
+  return DFTPAV_OK;
+}
+extern "C" int dftpav_batch_cost_terms(dftpav_batch *b, const double *x, double *terms, double *seg_terms) {
+  if (!b) return DFTPAV_E_INVALID;
+  if (b->order != DFTPAV_ORDER_REFERENCE) return DFTPAV_E_UNSUPPORTED; // the device order does not keep the penalty classes apart
+  if (!b->uploaded || !b->have_corridor || (!x && !b->solved)) return DFTPAV_E_INVALID;
+  dftpav_handle *h = b->h;
+  const size_t nb = (size_t)(b->n_active > 0 ? b->n_active : b->B);
+  HIPCHK(h, hipSetDevice(h->device));
+  if (!x) {
+    if (int rc = finish_pending(b)) return rc;
+  } else {
+    HIPCHK(h, hipMemcpyAsync(b->d_x_in, x, sizeof(double) * nb * b->L.n, hipMemcpyHostToDevice, h->stream));
+  }
+  if (int rc = cost_terms_on_stream(b, x ? b->d_x_in : nullptr)) return rc;
+  HIPCHK(h, fetch_async(h, terms, b->d_terms, sizeof(double) * nb * kCostTerms));
+  HIPCHK(h, fetch_async(h, seg_terms, b->d_terms + (size_t)b->B * kCostTerms, sizeof(double) * nb * b->L.M * kCostTerms));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return DFTPAV_OK;
 }

@@ -49,6 +49,7 @@ hipError_t launch_plan_paths(const int *status, const int *path_len, const int *
                              hipStream_t stream);
 hipError_t launch_plan_pack(const PlanPackArgs &A, hipStream_t stream);
 hipError_t launch_plan_select(const PlanSelectArgs &A, hipStream_t stream);
+hipError_t launch_penalty_gate(const PenaltyGateArgs &A, hipStream_t stream);
 hipError_t launch_replan_check(const ReplanArgs &A, hipStream_t stream);
 hipError_t launch_exec_adopt(const ExecAdoptArgs &A, hipStream_t stream);
 hipError_t launch_publish(const PublishArgs &A, hipStream_t stream);
@@ -163,6 +164,7 @@ struct dftpav_batch {
   bool prof_on = false;
   double *d_coef = nullptr, *d_dt = nullptr;
   double *d_f_eval = nullptr; // costs of dftpav_batch_eval (kept apart from the solve's final costs)
+  double *d_terms = nullptr;  // dftpav_batch_cost_terms: terms [B][5], then seg_terms [B][M][5]
   double *d_trace = nullptr;  // dftpav_batch_trace
   double *d_cor_raw = nullptr; // the caller's hPoly columns as uploaded (normalised and laid out on the device)
   // dftpav_batch_set_order(DFTPAV_ORDER_REFERENCE): the substitution tables of the band system and the term records (solver_ref.hip)
@@ -288,6 +290,13 @@ struct dftpav_planner {
   double lim_tab_dt = 0.0; // what d_lim_tab was tabulated for
   int *d_lim_arg = nullptr, *d_lim_viol = nullptr, *d_lim_feas = nullptr, *d_lim_reject = nullptr, *d_lim_col = nullptr;
   bool last_lim = false; // the last dftpav_plan_queries call ran with the filter
+  // ---- the penalty filter (dftpav_planner_set_penalty_filter): off by default, and then none of this is touched
+  bool pen_on = false;
+  dftpav_penalty_caps pen{};
+  unsigned char *d_pen = nullptr; // one allocation: the rows [max_queries * R] of a call, the selection's input
+  double *d_pen_terms = nullptr;
+  int *d_pen_rej = nullptr, *d_pen_flags = nullptr, *d_pen_col = nullptr;
+  bool last_pen = false; // the last dftpav_plan_queries call ran with the filter
 };
 
 namespace dftpav {
@@ -296,6 +305,7 @@ int finish_pending(dftpav_batch *b);                          // finishes the st
 int solve_impl(dftpav_batch *b, dftpav_batch *prev, bool chained);
 int sync_dev(dftpav_batch *b, DevBatch &D);                   // refreshes the device copy of the launch descriptor
 hipError_t launch_for(dftpav_batch *b, const DevBatch &D, int mode);
+int cost_terms_on_stream(dftpav_batch *b, const double *d_x); // the terms of the cost into b->d_terms; nothing waits
 void fill_dev_layout(const dftpav_layout &layout, int K, int Kd, DevLayout &L);
 void fill_dev_params(const dftpav_params &p, DevParams &P);
 // ---- capi_steps.cpp

@@ -93,6 +93,7 @@ extern "C" void dftpav_planner_destroy(dftpav_planner *p) {
   if (p->d_rc) (void)hipFree(p->d_rc);
   if (p->d_pub) (void)hipFree(p->d_pub);
   if (p->d_lim) (void)hipFree(p->d_lim);
+  if (p->d_pen) (void)hipFree(p->d_pen);
   for (auto &e : p->pev)
     if (e) (void)hipEventDestroy(e);
   for (auto &e : p->ev)
@@ -239,6 +240,8 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
   p->timed = false;
   p->last_Q = 0; // nothing to adopt until this call has ended well
   p->last_lim = false;
+  p->last_pen = false;
+  const bool pen = p->pen_on; // dftpav_planner_set_penalty_filter; off: likewise
   const bool filt = p->lim_on; // dftpav_planner_set_limit_filter; off: nothing below differs from a planner that never had one
   if (Q == 0) return DFTPAV_OK;
   if (!start_states || !start_ctrl || !end_states) return DFTPAV_E_INVALID;
@@ -347,6 +350,12 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
     HIPCHK(h, hipMemsetAsync(p->d_lim_feas, 0, sizeof(int) * rows, h->stream));
     HIPCHK(h, hipMemsetAsync(p->d_lim_col, 0, sizeof(int) * rows, h->stream));
   }
+  if (pen) { // likewise: zero rows
+    const size_t rows = nq * (size_t)R;
+    HIPCHK(h, hipMemsetAsync(p->d_pen_terms, 0, sizeof(double) * kCostTerms * rows, h->stream));
+    HIPCHK(h, hipMemsetAsync(p->d_pen_rej, 0, sizeof(int) * rows, h->stream));
+    HIPCHK(h, hipMemsetAsync(p->d_pen_col, 0, sizeof(int) * rows, h->stream));
+  }
   for (int g = 0; g < ng; g++) {
     dftpav_batch *b = batch[g];
     const int nm = g_off[g + 1] - g_off[g];
@@ -409,6 +418,25 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
       HIPCHK(h, launch_limits_batch(LA, h->stream));
       sel_col = LA.reject;
     }
+    if (pen) { // the selection reads its flag | a penalty sum above its cap; without the limit filter the pure collision flags go to d_pen_col
+      if (int rc = cost_terms_on_stream(b, nullptr)) return rc;
+      PenaltyGateArgs G{};
+      G.terms = b->d_terms;
+      G.flags_in = sel_col;
+      G.members = A.members;
+      G.n = nm * R;
+      G.R = R;
+      G.cap_corridor = p->pen.corridor;
+      G.cap_surround = p->pen.surround;
+      G.cap_feas = p->pen.feasibility;
+      G.r_terms = p->d_pen_terms;
+      G.r_rejected = p->d_pen_rej;
+      G.flags_out = p->d_pen_flags + (size_t)g_off[g] * R;
+      G.collision = filt ? nullptr : col;
+      G.collision_rows = p->d_pen_col;
+      HIPCHK(h, launch_penalty_gate(G, h->stream));
+      sel_col = G.flags_out;
+    }
     PlanSelectArgs Z{};
     Z.cost = b->d_f;
     Z.success = b->d_success;
@@ -458,8 +486,9 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
   HIPCHK(h, fetch_async(h, out->coeff_dt, p->d_wdt, sizeof(double) * nq * MS));
   HIPCHK(h, fetch_async(h, out->r_final_cost, p->d_rcost, sizeof(double) * nq * R));
   int *const r_out[6] = {out->r_status, out->r_success, out->r_iters, out->r_evals, out->r_collision, out->r_first_sample};
-  for (int k = 0; k < 6; k++) // (with the filter the selection copied its own input into d_rint[4]: the pure flags are in d_lim_col)
-    HIPCHK(h, fetch_async(h, r_out[k], (filt && k == 4) ? p->d_lim_col : p->d_rint[k], sizeof(int) * nq * R));
+  const int *pure_col = filt ? p->d_lim_col : (pen ? p->d_pen_col : p->d_rint[4]);
+  for (int k = 0; k < 6; k++) // (with a filter the selection copied its own input into d_rint[4]: the pure flags are in d_lim_col / d_pen_col)
+    HIPCHK(h, fetch_async(h, r_out[k], k == 4 ? pure_col : p->d_rint[k], sizeof(int) * nq * R));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   for (int q = 0; q < Q; q++) {
     if (status[q] != DFTPAV_PLAN_OK) {
@@ -493,6 +522,7 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
   p->last_MP = MP;
   p->last_Q = Q;
   p->last_lim = filt;
+  p->last_pen = pen;
   return DFTPAV_OK;
 }
 
@@ -519,6 +549,36 @@ extern "C" int dftpav_debug_plan_select(dftpav_handle *h, int n_query, int n_res
   Z.winner = d_int + 2 * nt;
   HIPCHK(h, launch_plan_select(Z, h->stream));
   HIPCHK(h, hipMemcpyAsync(winner_out, d_int + 2 * nt, sizeof(int) * n_query, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_debug_penalty_gate(dftpav_handle *h, int n, const double *terms, const dftpav_penalty_caps *caps, const int *flags_in,
+                                         int *flags_out, int *rejected) {
+  if (!h || !caps || n < 0 || (n > 0 && (!terms || !flags_in || !flags_out))) return DFTPAV_E_INVALID;
+  if (!(caps->corridor >= 0.0) || !(caps->surround >= 0.0) || !(caps->feasibility >= 0.0)) return DFTPAV_E_INVALID;
+  if (n == 0) return DFTPAV_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  double *d_terms = nullptr;
+  int *d_int = nullptr; // flags_in | flags_out | rejected
+  DevScratch tmp(h);
+  HIPCHK(h, tmp.alloc(d_terms, (size_t)n * kCostTerms));
+  HIPCHK(h, tmp.alloc(d_int, 3 * (size_t)n));
+  HIPCHK(h, hipMemcpyAsync(d_terms, terms, sizeof(double) * (size_t)n * kCostTerms, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_int, flags_in, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  PenaltyGateArgs G{};
+  G.terms = d_terms;
+  G.flags_in = d_int;
+  G.n = n;
+  G.R = 1;
+  G.cap_corridor = caps->corridor;
+  G.cap_surround = caps->surround;
+  G.cap_feas = caps->feasibility;
+  G.r_rejected = d_int + 2 * (size_t)n;
+  G.flags_out = d_int + n;
+  HIPCHK(h, launch_penalty_gate(G, h->stream));
+  HIPCHK(h, hipMemcpyAsync(flags_out, d_int + n, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, fetch_async(h, rejected, d_int + 2 * (size_t)n, sizeof(int) * (size_t)n));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return DFTPAV_OK;
 }
@@ -1139,6 +1199,45 @@ extern "C" int dftpav_planner_last_limits(dftpav_planner *p, const dftpav_limits
   C.violated = p->d_lim_viol;
   C.feasible = p->d_lim_feas;
   if (int rc = fetch_limits(h, out, C, (size_t)p->last_Q * p->R)) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return DFTPAV_OK;
+}
+
+// ------------------------------------------------- the residual penalties of solved plans (solver_ref.hip: kModeTerms, plan.hip)
+extern "C" int dftpav_planner_set_penalty_filter(dftpav_planner *p, const dftpav_penalty_caps *caps) {
+  if (!p) return DFTPAV_E_INVALID;
+  if (!caps) { // off: the buffers stay, nothing reads them
+    p->pen_on = false;
+    return DFTPAV_OK;
+  }
+  if (!(caps->corridor >= 0.0) || !(caps->surround >= 0.0) || !(caps->feasibility >= 0.0)) return DFTPAV_E_INVALID; // negative, NaN
+  dftpav_handle *h = p->h;
+  if (!p->d_pen) {
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t rows = (size_t)p->max_queries * p->R;
+    auto fields = [&](auto &take) {
+      p->d_pen_terms = (double *)take(sizeof(double) * kCostTerms * rows);
+      p->d_pen_rej = (int *)take(sizeof(int) * rows);
+      p->d_pen_flags = (int *)take(sizeof(int) * rows);
+      p->d_pen_col = (int *)take(sizeof(int) * rows);
+    };
+    unsigned char *base = nullptr;
+    HIPCHK(h, hipMalloc(&base, carve(nullptr, fields)));
+    carve(base, fields);
+    p->d_pen = base;
+  }
+  p->pen = *caps;
+  p->pen_on = true;
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_planner_last_cost_terms(dftpav_planner *p, double *r_terms, int *r_rejected) {
+  if (!p || (!r_terms && !r_rejected) || !p->last_pen || p->last_Q <= 0) return DFTPAV_E_INVALID;
+  dftpav_handle *h = p->h;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t rows = (size_t)p->last_Q * p->R;
+  HIPCHK(h, fetch_async(h, r_terms, p->d_pen_terms, sizeof(double) * kCostTerms * rows));
+  HIPCHK(h, fetch_async(h, r_rejected, p->d_pen_rej, sizeof(int) * rows));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return DFTPAV_OK;
 }

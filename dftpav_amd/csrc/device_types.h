@@ -167,12 +167,18 @@ struct DevBatch {
   // {f, stp, k, count}
   double *trace;
   int trace_b, trace_cap, trace_n;
+  // kModeTerms (the reference order's kernel only): the five terms of the cost (CostTerm) -- chained over the segments in order
+  // from 0.0 [B][5], and every segment's operands of those chains [B][M][5]
+  double *terms_out, *seg_terms_out;
 };
 
 constexpr int kQuadMirrorRows = 16; // rows of DevBatch::histM per trajectory (twice solver_ref4.hip's register block of stored pairs)
 inline size_t quad_mirror_doubles(const DevLayout &L, int B) { return (size_t)B * kQuadMirrorRows * L.npad * 2; }
 
-enum KernelMode { kModeSolve = 0, kModeEval = 1, kModeCoeffs = 2 };
+// the terms of the cost (DFTPAV_TERM_* of the C-ABI, in its order)
+enum CostTerm { kTermSmooth = 0, kTermTime, kTermCorridor, kTermSurround, kTermFeas, kCostTerms };
+// kModeTerms: the terms of the cost at x_in; kModeTermsSolved: at x_out, the solution (as kModeCoeffs)
+enum KernelMode { kModeSolve = 0, kModeEval = 1, kModeCoeffs = 2, kModeTerms = 3, kModeTermsSolved = 4 };
 
 // how a solve launch picks its trajectories
 constexpr int kAltTag = 1 << 30; // queue entry of a trajectory that belongs to SchedArgs::alt, not to the launched batch

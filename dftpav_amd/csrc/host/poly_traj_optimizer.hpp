@@ -105,6 +105,12 @@ class PolyTrajOptimizer {
   double last_cost() const { return cost_; }
   int last_iterations() const { return iters_; }
   int last_error() const { return err_; } // DFTPAV_E_* of the last call (0 if it reached the solver)
+  // the last solution's cost term by term (dftpav_batch_cost_terms: DFTPAV_TERM_* columns; terms [5], seg_terms [M][5], either may
+  // be NULL), evaluated on demand on the batch that stays on the device.  DFTPAV_E_UNSUPPORTED unless the solve ran in the
+  // reference order, DFTPAV_E_INVALID without a solved problem.
+  int last_cost_terms(double *terms, double *seg_terms) const {
+    return batch_ ? dftpav_batch_cost_terms(batch_, nullptr, terms, seg_terms) : DFTPAV_E_INVALID;
+  }
   // the solved problem stays on the device until the next call, for the steps that consume it there
   // (TrajPlannerSteps::CheckCollision / GetStates); NULL before the first successful upload
   dftpav_batch *solved_batch() const { return batch_; }

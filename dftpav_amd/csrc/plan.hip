@@ -12,6 +12,8 @@
 //                        RealT2VirtualT, the junction position and its angle); gathers the constraint-point poses
 //   plan_select_kernel   per query the cheapest restart that succeeded and does not collide, and its x / coefficients into the
 //                        compact per-query outputs
+//   penalty_gate_kernel  with dftpav_planner_set_penalty_filter, in front of the selection: per (query, restart) the five terms of
+//                        the solution's cost into their row, and the selection's flag |= a penalty sum above its cap
 //
 // fp64, no contraction, the host code's statements in the host code's order; atan2 is the correctly rounded one (cr_trig.h),
 // as the oracle's order 2.  Plain vector stores only.
@@ -180,6 +182,21 @@ __global__ void __launch_bounds__(64) plan_select_kernel(PlanSelectArgs A) {
     for (int k = lane; k < A.M; k += 64) A.w_dt[(size_t)q * A.dt_stride + k] = A.dt[t * A.M + k];
 }
 
+// The residual-penalty gate between the terms launch and the selection.  !(t <= cap): a NaN term is rejected, +inf caps reject
+// no finite term, -0.0 <= 0.0 holds.
+__global__ void __launch_bounds__(256) penalty_gate_kernel(PenaltyGateArgs A) {
+  const int t = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (t >= A.n) return;
+  const size_t row = A.members ? (size_t)A.members[t / A.R] * A.R + t % A.R : (size_t)t;
+  const double *tm = A.terms + (size_t)t * kCostTerms;
+  if (A.r_terms)
+    for (int k = 0; k < kCostTerms; k++) A.r_terms[row * kCostTerms + k] = tm[k];
+  const int rejected = (!(tm[kTermCorridor] <= A.cap_corridor) | !(tm[kTermSurround] <= A.cap_surround) | !(tm[kTermFeas] <= A.cap_feas)) ? 1 : 0;
+  if (A.r_rejected) A.r_rejected[row] = rejected;
+  A.flags_out[t] = (A.flags_in[t] != 0 || rejected) ? 1 : 0;
+  if (A.collision) A.collision_rows[row] = A.collision[t];
+}
+
 hipError_t launch_plan_paths(const int *status, const int *path_len, const int *skip, int n, int max_path, double *paths, int *fe_len,
                              hipStream_t stream) {
   hipLaunchKernelGGL(plan_paths_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, status, path_len, skip, n, max_path, paths, fe_len);
@@ -187,6 +204,10 @@ hipError_t launch_plan_paths(const int *status, const int *path_len, const int *
 }
 hipError_t launch_plan_pack(const PlanPackArgs &A, hipStream_t stream) {
   hipLaunchKernelGGL(plan_pack_kernel, dim3(A.n_members), dim3(256), 0, stream, A);
+  return hipGetLastError();
+}
+hipError_t launch_penalty_gate(const PenaltyGateArgs &A, hipStream_t stream) {
+  hipLaunchKernelGGL(penalty_gate_kernel, dim3((A.n + 255) / 256), dim3(256), 0, stream, A);
   return hipGetLastError();
 }
 hipError_t launch_plan_select(const PlanSelectArgs &A, hipStream_t stream) {

@@ -40,6 +40,20 @@ struct PlanSelectArgs {
   int *r_status, *r_success, *r_iters, *r_evals, *r_collision, *r_first_sample;
 };
 
+// penalty_gate_kernel: one thread per trajectory t = member * R + restart of a group; row = (query, restart)
+struct PenaltyGateArgs {
+  const double *terms;    // [n][5] the terms of the cost per trajectory (CostTerm)
+  const int *flags_in;    // [n] what the selection would read without the gate
+  const int *members;     // [n / R] query of each member; nullptr: row = t
+  int n, R;
+  double cap_corridor, cap_surround, cap_feas;
+  double *r_terms;        // [rows][5] or nullptr
+  int *r_rejected;        // [rows] or nullptr
+  int *flags_out;         // [n] (flags_in != 0) | rejected
+  const int *collision;   // [n] or nullptr: the pure collision flags, copied to collision_rows [rows]
+  int *collision_rows;
+};
+
 // the executing table of a planner (capi.cpp: dftpav_planner_install / _adopt): one row per slot, device pointers.  n_seg == 0: empty.
 // Padded as dftpav_plan_out: the pieces of a slot's segments follow one another in `coeffs`.
 struct ExecTable {

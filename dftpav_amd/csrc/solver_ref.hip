@@ -1864,7 +1864,7 @@ __global__ void __launch_bounds__((WAVE && CAP <= kNarrowCap && !SUR) ? 512 : 25
     if (resume) {
       state_io(D, sm, b, tid, sh.nl, false);
     } else {
-      const double *xsrc = (mode == kModeSolve) ? D.x0 : (mode == kModeEval ? D.x_in : D.x_out);
+      const double *xsrc = (mode == kModeSolve) ? D.x0 : ((mode == kModeEval || mode == kModeTerms) ? D.x_in : D.x_out);
       for (int e = tid; e < sh.nl; e += T) {
         sm.x[e] = e < n ? xsrc[(size_t)b * n + e] : 0.0;
         sm.xp[e] = 0.0;
@@ -1898,6 +1898,21 @@ __global__ void __launch_bounds__((WAVE && CAP <= kNarrowCap && !SUR) ? 512 : 25
       if (mode == kModeCoeffs) {
         for (int w = tid; w < 12 * L.Ntot; w += T) D.coef_out[(size_t)b * 12 * L.Ntot + w] = sm.c[w];
         for (int sg = tid; sg < L.M; sg += T) D.dt_out[(size_t)b * L.M + sg] = sm.seg[16 * sg + 1];
+        return;
+      }
+      if (mode >= kModeTerms) { // the operands of the cost's sums above (ref_eval, :292-297, :328-330), and each sum on its own
+        const int M = L.M;
+        for (int w = tid; w < kCostTerms * (M + 1); w += T) {
+          const int row = w / kCostTerms, k = w - kCostTerms * row; // rows 0 .. M-1: the segments; row M: the chains
+          const int slot = k == kTermSmooth ? gENERGY : (k == kTermCorridor ? gCOST0 : (k == kTermSurround ? gCOST1 : gCOST2));
+          double acc = 0.0;
+          for (int sg = 0; sg < M; sg++) {
+            const double v = k == kTermTime ? sm.seg[16 * sg] * D.P.wei_time : sm.segsum[gNUM * sg + slot];
+            acc += v;
+            if (sg == row) D.seg_terms_out[((size_t)b * M + sg) * kCostTerms + k] = v;
+          }
+          if (row == M) D.terms_out[(size_t)b * kCostTerms + k] = acc;
+        }
         return;
       }
       if (tid < 64) {

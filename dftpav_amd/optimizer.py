@@ -66,6 +66,13 @@ class PolyTrajOptimizer:
     def getMinJerkOptPtr(self):  # traj_optimizer.h:112
         return self._mjo
 
+    def last_cost_terms(self):
+        """(terms [B][5], seg_terms [B][M][5]) of the last solve's solutions (dftpav_batch_cost_terms; columns capi.TERM_*), or None
+        unless that solve ran in the reference order"""
+        if self.last is None or "terms" not in self.last:
+            return None
+        return self.last["terms"], self.last["seg_terms"]
+
     def _ensure(self):
         if self._handle is None:
             self._handle = capi.Handle(self._params, self._device)  # raises without a GPU: no fallback
@@ -143,6 +150,8 @@ class PolyTrajOptimizer:
                     raise
         r = bt.solve()
         r["order"] = order
+        if order == capi.ORDER_REFERENCE:  # the solution's cost term by term (the device order does not keep the terms apart)
+            r["terms"], r["seg_terms"] = bt.cost_terms()
         c, dt = bt.coeffs()
         # results stay inside the optimiser until the next call (traj_optimizer.h:91,112); B=1 view for the ROS path
         off = 0

@@ -358,6 +358,26 @@ int dftpav_batch_get_x0(dftpav_batch *b, double *x0);
  * vectors at once: x [B][n] -> f [B], g [B][n].  Host buffers. */
 int dftpav_batch_eval(dftpav_batch *b, const double *x, double *f, double *g);
 
+/* The cost of dftpav_batch_eval term by term.  The reference forms it as a sum of five (traj_optimizer.cpp:292-297 per gear
+ * segment: the jerk energy, and costs(0) corridor, costs(1) moving obstacles, costs(2) feasibility -- velocity, longitudinal
+ * acceleration, curvature; :328-344 the time term and the total) and prints the per-segment jerk cost after a solve
+ * (traj_manager.cpp:623); the terms are the operands of those very sums, taken from the evaluation kernel's own per-segment
+ * records (solver_ref.hip) -- no second penalty integral:
+ *   seg_terms [B][M][5]  per gear segment: jerk energy, T * wei_time, costs(0), costs(1), costs(2)
+ *   terms     [B][5]     each column chained over the segments in order from 0.0
+ * so that  f == terms[SMOOTH] + terms[TIME] + sum over segments in order of ((costs(0) + costs(1)) + costs(2))  in the bits of
+ * dftpav_batch_eval.  x [B][n], or NULL: the solution of the last solve (DFTPAV_E_INVALID if there is none).  Either output may be
+ * NULL.  DFTPAV_ORDER_REFERENCE only: DFTPAV_E_UNSUPPORTED in the device order, whose sums do not keep the penalty classes apart.
+ * Refuses what dftpav_batch_eval refuses; a refused call changes nothing.  Every launch shape of the order is served by the
+ * TEAM / WAVE kernel, as dftpav_batch_coeffs is; the results of a solve are not touched. */
+#define DFTPAV_TERM_SMOOTH 0
+#define DFTPAV_TERM_TIME 1
+#define DFTPAV_TERM_CORRIDOR 2
+#define DFTPAV_TERM_SURROUND 3
+#define DFTPAV_TERM_FEAS 4
+#define DFTPAV_COST_TERMS 5
+int dftpav_batch_cost_terms(dftpav_batch *b, const double *x, double *terms, double *seg_terms);
+
 /* Observation of one trajectory's solve, the role of lbfgs_progress_t
  * (lbfgs.hpp:242-249; the reference passes NULL, traj_optimizer.cpp:164) at
  * the granularity of the evaluation callback (lbfgs.hpp:200-202): during the
@@ -920,6 +940,29 @@ int dftpav_planner_check_limits(dftpav_planner *p, double check_dt, const dftpav
 int dftpav_planner_set_limit_filter(dftpav_planner *p, const dftpav_limits *l, double check_dt);
 int dftpav_planner_last_limits(dftpav_planner *p, const dftpav_limits_out *out);
 int dftpav_limits_last_ms(dftpav_handle *h, float *ms);
+
+/* ---- the residual penalties of solved plans, and a selection filter on them -------------------------------------
+ * `success` means "status accepted and cost < fail_cost": the cheapest collision-free restart may still lean on an active
+ * corridor or moving-obstacle penalty.  The three penalty sums of dftpav_batch_cost_terms say how far, in the reference's own
+ * arithmetic; no other criterion is judged.
+ * dftpav_planner_set_penalty_filter: caps == NULL (the default): dftpav_plan_queries and dftpav_replan_tick do exactly what
+ *   they do without this call -- the same launches, the same bits.  With caps: per layout group, after the collision re-check
+ *   (and the limits kernel, when that filter is set), the terms launch runs on the group's solutions and penalty_gate_kernel
+ *   (plan.hip) rejects a restart unless  corridor <= caps.corridor && surround <= caps.surround && feasibility <=
+ *   caps.feasibility  (a NaN term is rejected; a cap of +inf never rejects a finite term; a cap of 0.0 is legal: no residual
+ *   penalty at all).  The selection sees collision | (!feasible) | rejected; a query whose every restart is rejected ends
+ *   DFTPAV_PLAN_NO_VALID_RESTART (a tick then keeps the slot's old plan).  r_collision / r_first_sample of dftpav_plan_out stay
+ *   the pure collision results.  The caps are copied.  A negative or NaN cap is DFTPAV_E_INVALID, and nothing changes.
+ * dftpav_planner_last_cost_terms: r_terms [Q][R][5] and r_rejected [Q][R] (query, restart) of the last dftpav_plan_queries call
+ *   that ran with the filter on; zero rows for the queries no restart was solved for.  Either may be NULL (both: DFTPAV_E_INVALID).
+ *   DFTPAV_E_INVALID when that call ran without the filter.
+ * dftpav_debug_penalty_gate: test hook, the gate on caller-supplied terms [n][5] and flags_in [n]: rejected [n] by the rule above,
+ *   flags_out [n] = (flags_in != 0) | rejected.  rejected may be NULL. */
+typedef struct dftpav_penalty_caps { double corridor, surround, feasibility; } dftpav_penalty_caps; /* +inf: not judged */
+int dftpav_planner_set_penalty_filter(dftpav_planner *p, const dftpav_penalty_caps *caps);
+int dftpav_planner_last_cost_terms(dftpav_planner *p, double *r_terms, int *r_rejected);
+int dftpav_debug_penalty_gate(dftpav_handle *h, int n, const double *terms, const dftpav_penalty_caps *caps, const int *flags_in,
+                              int *flags_out, int *rejected);
 
 /* One-shot convenience == OptimizeTrajectory for B trajectories. */
 int dftpav_solve_batch(dftpav_handle *h, const dftpav_layout *layout, int B,
