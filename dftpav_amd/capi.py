@@ -25,6 +25,7 @@ PUBLISH_CHUNK, PUBLISH_MAX_TICKS = 256, 4096   # DFTPAV_PUBLISH_CHUNK, DFTPAV_PU
 PLAN_OK, PLAN_NO_PATH, PLAN_TOO_MANY_SEGMENTS, PLAN_LAYOUT_UNSUPPORTED, PLAN_NO_VALID_RESTART, PLAN_ARRIVED = 0, 1, 2, 3, 4, 5
 SEARCH_REACH_END, SEARCH_NO_PATH = 2, 3
 # columns of dftpav_batch_cost_terms (DFTPAV_TERM_*)
+DIST_FAR = 2147483647   # DFTPAV_DIST_FAR
 TERM_SMOOTH, TERM_TIME, TERM_CORRIDOR, TERM_SURROUND, TERM_FEAS, COST_TERMS = 0, 1, 2, 3, 4, 5
 
 # every symbol include/dftpav_hip.h declares
@@ -51,6 +52,8 @@ EXPORTS = [
     "dftpav_default_limits", "dftpav_batch_check_limits", "dftpav_planner_check_limits", "dftpav_planner_set_limit_filter",
     "dftpav_planner_last_limits", "dftpav_limits_last_ms",
     "dftpav_batch_cost_terms", "dftpav_planner_set_penalty_filter", "dftpav_planner_last_cost_terms", "dftpav_debug_penalty_gate",
+    "dftpav_grid_distance_field", "dftpav_batch_check_clearance", "dftpav_planner_check_clearance", "dftpav_planner_set_clearance_filter",
+    "dftpav_planner_last_clearance", "dftpav_clearance_last_ms",
 ]
 
 
@@ -190,6 +193,22 @@ class PenaltyCaps(C.Structure):
         super().__init__(float(corridor), float(surround), float(feasibility))
 
 
+class _ClearanceOutC(C.Structure):
+    _fields_ = [("min_d2", C.c_void_p), ("arg", C.c_void_p), ("clearance", C.c_void_p)]
+
+
+class ClearanceOut:
+    """the caller-allocated arrays of dftpav_clearance_out for `shape` rows: min_d2 (squared cell distance, DIST_FAR: none), arg (the
+    first sample where it is reached, -1: none), clearance (metres, +inf: none)"""
+
+    def __init__(self, *shape):
+        self.a = dict(min_d2=np.zeros(shape, dtype=np.int32), arg=np.zeros(shape, dtype=np.int32), clearance=np.zeros(shape))
+        self.c = _ClearanceOutC(*[self.a[k].ctypes.data for k in ("min_d2", "arg", "clearance")])
+
+    def arrays(self):
+        return self.a
+
+
 def default_limits(params=None):
     """dftpav_default_limits: the parameters' limits (minco_config.pb.txt:83-91); max_steer = +inf"""
     params = params if params is not None else default_params()
@@ -206,6 +225,7 @@ class Handle:
 
     def __init__(self, params=None, device=0):
         self.params = params if params is not None else default_params()
+        self._map_shape = None   # (size_y, size_x) of the installed grid map
         self._h = C.c_void_p()
         rc = lib().dftpav_create(C.byref(self.params), device, C.byref(self._h))
         if rc != OK:
@@ -376,6 +396,7 @@ class Handle:
         fn = lib().dftpav_set_grid_map
         fn.argtypes = [C.c_void_p, C.c_void_p]
         self._check(fn(self._h, C.byref(m)), "set_grid_map")
+        self._map_shape = g.shape
 
     def corridor_rectangles(self, states):
         """getRectangleConst on the device: states [n][3] (x, y, yaw) -> [n][4][4] columns (n_x, n_y, p_x, p_y)."""
@@ -385,6 +406,28 @@ class Handle:
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         self._check(fn(self._h, st.ctypes.data_as(C.c_void_p), st.shape[0], out.ctypes.data_as(C.c_void_p)), "corridor_rectangles")
         return out
+
+    def distance_field(self, fetch=True):
+        """dftpav_grid_distance_field: int32 [size_y][size_x], the squared distance in cells of every cell of the installed map to its
+        nearest occupied cell (DIST_FAR on a map without one); built on the device when the map changed.  fetch=False: build only"""
+        fn = lib().dftpav_grid_distance_field
+        fn.argtypes = [C.c_void_p, C.c_void_p]
+        if not fetch:
+            self._check(fn(self._h, None), "grid_distance_field")
+            return None
+        if self._map_shape is None:
+            raise DftpavError(E_INVALID, "grid_distance_field: no map")
+        out = np.zeros(self._map_shape, dtype=np.int32)
+        self._check(fn(self._h, out.ctypes.data_as(C.c_void_p)), "grid_distance_field")
+        return out
+
+    def clearance_last_ms(self):
+        """dftpav_clearance_last_ms: device ms of (the last field build, the last clearance kernel of a check_clearance call)"""
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        fn = lib().dftpav_clearance_last_ms
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        self._check(fn(self._h, C.byref(a), C.byref(b)), "clearance_last_ms")
+        return float(a.value), float(b.value)
 
     def limits_last_ms(self):
         """device time in ms of the last limits kernel of a check_limits call"""
@@ -682,6 +725,30 @@ class Planner:
         self.handle._check(fn(self._p, terms.ctypes.data_as(C.c_void_p), rej.ctypes.data_as(C.c_void_p)), "planner_last_cost_terms")
         return terms, rej
 
+    # ---- solved plans' clearance from the map's occupied cells
+    def check_clearance(self, check_dt=0.05):
+        """dftpav_planner_check_clearance: a row per slot of the executing table -> dict(min_d2, arg, clearance [slots]); empty slots:
+        DIST_FAR, -1, +inf"""
+        out = ClearanceOut(self.max_queries)
+        fn = lib().dftpav_planner_check_clearance
+        fn.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
+        self.handle._check(fn(self._p, float(check_dt), C.byref(out.c)), "planner_check_clearance")
+        return out.arrays()
+
+    def set_clearance_filter(self, min_clearance=None, check_dt=0.05):
+        """dftpav_planner_set_clearance_filter: None (or a negative value) switches the filter off (the default)"""
+        fn = lib().dftpav_planner_set_clearance_filter
+        fn.argtypes = [C.c_void_p, C.c_double, C.c_double]
+        self.handle._check(fn(self._p, -1.0 if min_clearance is None else float(min_clearance), float(check_dt)), "planner_set_clearance_filter")
+
+    def last_clearance(self, Q):
+        """dftpav_planner_last_clearance: the rows [Q][R] of the last plan() of Q queries that ran with the filter on"""
+        out = ClearanceOut(int(Q), self.n_restarts)
+        fn = lib().dftpav_planner_last_clearance
+        fn.argtypes = [C.c_void_p, C.c_void_p]
+        self.handle._check(fn(self._p, C.byref(out.c)), "planner_last_clearance")
+        return out.arrays()
+
     def publish_last_ms(self):
         """dftpav_publish_last_ms: device ms of the last publish kernel (0.0 before the first)"""
         a = C.c_float(0.0)
@@ -808,6 +875,15 @@ class Batch:
         fn = lib().dftpav_batch_check_limits
         fn.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
         self.handle._check(fn(self._b, float(check_dt), C.byref(limits), C.byref(out.c)), "batch_check_limits")
+        return out.arrays()
+
+    def check_clearance(self, check_dt=0.05):
+        """dftpav_batch_check_clearance: how close the outline of each solved trajectory comes to the map's occupied cells over
+        CheckReplan's samples -> dict(min_d2, arg, clearance [B])"""
+        out = ClearanceOut(self.B)
+        fn = lib().dftpav_batch_check_clearance
+        fn.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
+        self.handle._check(fn(self._b, float(check_dt), C.byref(out.c)), "batch_check_clearance")
         return out.arrays()
 
     def sample_states(self, t0=0.0, sample_dt=0.01, n_samples=None, filter_singularity=True):

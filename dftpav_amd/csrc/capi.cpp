@@ -258,6 +258,9 @@ extern "C" void dftpav_destroy(dftpav_handle *h) {
   if (h->cev1) (void)hipEventDestroy(h->cev1);
   if (h->lev0) (void)hipEventDestroy(h->lev0);
   if (h->lev1) (void)hipEventDestroy(h->lev1);
+  if (h->d_dist) (void)hipFree(h->d_dist);
+  for (hipEvent_t e : {h->fev0, h->fev1, h->kev0, h->kev1})
+    if (e) (void)hipEventDestroy(e);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }

@@ -27,6 +27,7 @@
 #include "search_args.h"
 #include "plan_args.h"
 #include "limits_args.h"
+#include "clearance_args.h"
 
 namespace dftpav {
 hipError_t launch_solver(const DevBatch &D, const DevBatch *d_dev, int mode, int threads, int grid, SchedArgs sched,
@@ -57,6 +58,10 @@ hipError_t launch_pub_reset(const PubResetArgs &A, hipStream_t stream);
 // limits.hip: solved plans against the kinematic limits
 hipError_t launch_limits_batch(const LimitsBatchArgs &A, hipStream_t stream);
 hipError_t launch_limits_table(const LimitsTableArgs &A, hipStream_t stream);
+// distfield.hip, clearance.hip: the distance field of the map, the clearance of solved plans
+hipError_t launch_dist_field(const DistFieldArgs &A, hipStream_t stream);
+hipError_t launch_clearance_batch(const ClearanceBatchArgs &A, hipStream_t stream);
+hipError_t launch_clearance_table(const ClearanceTableArgs &A, hipStream_t stream);
 hipError_t launch_corridor_layout(const double *raw, double *out, int B, int Npts, int H, int NptsPad, hipStream_t stream);
 hipError_t launch_adopt(const DevBatch &D, const DevBatch &prev, hipStream_t stream);
 // solver_ref.hip: the same path in the reference's own floating-point order
@@ -103,6 +108,12 @@ struct dftpav_handle {
   bool ctimed = false;
   hipEvent_t lev0 = nullptr, lev1 = nullptr; // around the last limits kernel of a check_limits call
   bool ltimed = false;
+  // the distance field of the map (distfield.hip): built by the first clearance call after a dftpav_set_grid_map, never otherwise
+  int *d_dist = nullptr; // one allocation: d2 [cells], then the row pass's g [cells]
+  size_t dist_cells = 0; // what d_dist holds room for
+  bool dist_stale = true;
+  hipEvent_t fev0 = nullptr, fev1 = nullptr, kev0 = nullptr, kev1 = nullptr; // around the last field build / the last clearance kernel of a check call
+  bool ftimed = false, ktimed = false;
   std::vector<struct dftpav_batch *> batches; // every live batch of this handle (obstacle changes finish their chained stragglers)
   // RCCL communicator of dftpav_comm_create (one rank per handle = per GPU), and the staging block of this rank's records
   void *comm = nullptr;
@@ -297,6 +308,16 @@ struct dftpav_planner {
   double *d_pen_terms = nullptr;
   int *d_pen_rej = nullptr, *d_pen_flags = nullptr, *d_pen_col = nullptr;
   bool last_pen = false; // the last dftpav_plan_queries call ran with the filter
+  // ---- the clearance filter (dftpav_planner_set_clearance_filter): off by default, and then none of this is touched
+  bool clr_on = false;
+  double clr_min = -1.0, clr_dt = 0.0;
+  unsigned char *d_clr = nullptr; // one allocation: the two tables, the rows [max_queries * R] of a call, the selection's input
+  double *d_clr_tab = nullptr, *d_clr_m = nullptr;
+  int clr_n_t = 0, clr_n_v = 0;
+  double clr_tab_dt = 0.0; // what d_clr_tab was tabulated for
+  int *d_clr_d2 = nullptr, *d_clr_arg = nullptr, *d_clr_flags = nullptr, *d_clr_col = nullptr;
+  std::vector<double> h_clr_inf; // +inf, the rows' clearance before a call's kernels run
+  bool last_clr = false; // the last dftpav_plan_queries call ran with the filter
 };
 
 namespace dftpav {
@@ -327,6 +348,13 @@ int ensure_coeffs(dftpav_batch *b, DevBatch &D);
 int validate_on_stream(dftpav_batch *b, int n_traj, const double *d_tab, int n_t, int n_v, double check_dt, int *d_col, int *d_first);
 // dftpav_limits as the kernels of limits.hip read it; false: a limit that is not > 0 (a NaN included)
 bool limits_common(const dftpav_params &p, const dftpav_limits &l, LimitsCommon &C);
+// the distance field of the handle's map, built on the handle's stream if the map changed since the last build (nothing waits);
+// DFTPAV_E_INVALID without a map, DFTPAV_E_UNSUPPORTED for a side above 16384 cells
+int ensure_dist_field(dftpav_handle *h);
+// the outline spacing of the clearance calls: the reference's own (shapes.h:200-201), which dftpav_batch_validate's callers pass as 0.1
+constexpr double kClearanceVertexRes = 0.1;
+// the map, its field, the vehicle and the tables (d_tab: a validation_table of kClearanceVertexRes on the device) as clearance.hip reads them
+ClearanceCommon clearance_common(const dftpav_handle *h, const double *d_tab, int n_t, int n_v, double check_dt);
 
 // One allocation for many arrays, measured and carved by the same list: fields(take) names every array in order, take(bytes) is its
 // address -- null while `base` is null, the measuring pass -- and advances by the size rounded up to 256 bytes.  Returns the bytes used.

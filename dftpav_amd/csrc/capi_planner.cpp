@@ -94,6 +94,7 @@ extern "C" void dftpav_planner_destroy(dftpav_planner *p) {
   if (p->d_pub) (void)hipFree(p->d_pub);
   if (p->d_lim) (void)hipFree(p->d_lim);
   if (p->d_pen) (void)hipFree(p->d_pen);
+  if (p->d_clr) (void)hipFree(p->d_clr);
   for (auto &e : p->pev)
     if (e) (void)hipEventDestroy(e);
   for (auto &e : p->ev)
@@ -241,6 +242,8 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
   p->last_Q = 0; // nothing to adopt until this call has ended well
   p->last_lim = false;
   p->last_pen = false;
+  p->last_clr = false;
+  const bool clr = p->clr_on; // dftpav_planner_set_clearance_filter; off: likewise
   const bool pen = p->pen_on; // dftpav_planner_set_penalty_filter; off: likewise
   const bool filt = p->lim_on; // dftpav_planner_set_limit_filter; off: nothing below differs from a planner that never had one
   if (Q == 0) return DFTPAV_OK;
@@ -340,8 +343,17 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
   HIPCHK(h, hipSetDevice(h->device));
   if (!p->h_members.empty())
     HIPCHK(h, hipMemcpyAsync(p->d_members, p->h_members.data(), sizeof(int) * p->h_members.size(), hipMemcpyHostToDevice, h->stream));
-  // ---- per group: pack -> rectangles -> solve -> coefficients -> collision re-check (-> limits) -> selection; nothing waits in between
+  // ---- per group: pack -> rectangles -> solve -> coefficients -> collision re-check (-> limits) (-> clearance) (-> penalty gate)
+  // -> selection; nothing waits in between
   size_t pose_off = 0;
+  if (clr) { // the map's distance field if the map changed since its last build; the rows no restart is solved for: FAR, -1, +inf
+    if (int rc = ensure_dist_field(h)) return rc;
+    const size_t rows = nq * (size_t)R;
+    HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)p->d_clr_d2, DFTPAV_DIST_FAR, rows, h->stream));
+    HIPCHK(h, hipMemsetAsync(p->d_clr_arg, 0xff, sizeof(int) * rows, h->stream));
+    HIPCHK(h, hipMemcpyAsync(p->d_clr_m, p->h_clr_inf.data(), sizeof(double) * rows, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemsetAsync(p->d_clr_col, 0, sizeof(int) * rows, h->stream));
+  }
   if (filt) { // the rows of the queries no restart is solved for: zero, arg -1
     const size_t rows = nq * (size_t)R;
     HIPCHK(h, hipMemsetAsync(p->d_lim_max, 0, sizeof(double) * kLimQ * rows, h->stream));
@@ -418,7 +430,27 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
       HIPCHK(h, launch_limits_batch(LA, h->stream));
       sel_col = LA.reject;
     }
-    if (pen) { // the selection reads its flag | a penalty sum above its cap; without the limit filter the pure collision flags go to d_pen_col
+    if (clr) { // the selection reads its flag | clearance < min_clearance; without the limit filter the pure collision flags go to d_clr_col
+      ClearanceBatchArgs CA{};
+      CA.C = clearance_common(h, p->d_clr_tab, p->clr_n_t, p->clr_n_v, p->clr_dt);
+      CA.C.min_d2 = p->d_clr_d2;
+      CA.C.arg = p->d_clr_arg;
+      CA.C.clearance = p->d_clr_m;
+      CA.coeffs = b->d_coef;
+      CA.piece_dt = b->d_dt;
+      CA.L = L;
+      CA.B = nm * R;
+      CA.members = A.members;
+      CA.R = R;
+      CA.flags_in = sel_col;
+      CA.min_clearance = p->clr_min;
+      CA.flags_out = p->d_clr_flags + (size_t)g_off[g] * R;
+      CA.collision = filt ? nullptr : col;
+      CA.collision_rows = p->d_clr_col;
+      HIPCHK(h, launch_clearance_batch(CA, h->stream));
+      sel_col = CA.flags_out;
+    }
+    if (pen) { // the selection reads its flag | a penalty sum above its cap; without the other filters the pure collision flags go to d_pen_col
       if (int rc = cost_terms_on_stream(b, nullptr)) return rc;
       PenaltyGateArgs G{};
       G.terms = b->d_terms;
@@ -432,7 +464,7 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
       G.r_terms = p->d_pen_terms;
       G.r_rejected = p->d_pen_rej;
       G.flags_out = p->d_pen_flags + (size_t)g_off[g] * R;
-      G.collision = filt ? nullptr : col;
+      G.collision = (filt || clr) ? nullptr : col;
       G.collision_rows = p->d_pen_col;
       HIPCHK(h, launch_penalty_gate(G, h->stream));
       sel_col = G.flags_out;
@@ -486,8 +518,8 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
   HIPCHK(h, fetch_async(h, out->coeff_dt, p->d_wdt, sizeof(double) * nq * MS));
   HIPCHK(h, fetch_async(h, out->r_final_cost, p->d_rcost, sizeof(double) * nq * R));
   int *const r_out[6] = {out->r_status, out->r_success, out->r_iters, out->r_evals, out->r_collision, out->r_first_sample};
-  const int *pure_col = filt ? p->d_lim_col : (pen ? p->d_pen_col : p->d_rint[4]);
-  for (int k = 0; k < 6; k++) // (with a filter the selection copied its own input into d_rint[4]: the pure flags are in d_lim_col / d_pen_col)
+  const int *pure_col = filt ? p->d_lim_col : (clr ? p->d_clr_col : (pen ? p->d_pen_col : p->d_rint[4]));
+  for (int k = 0; k < 6; k++) // (with a filter the selection copied its own input into d_rint[4]: the pure flags are in d_lim_col / d_clr_col / d_pen_col)
     HIPCHK(h, fetch_async(h, r_out[k], k == 4 ? pure_col : p->d_rint[k], sizeof(int) * nq * R));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   for (int q = 0; q < Q; q++) {
@@ -523,6 +555,7 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
   p->last_Q = Q;
   p->last_lim = filt;
   p->last_pen = pen;
+  p->last_clr = clr;
   return DFTPAV_OK;
 }
 
@@ -1238,6 +1271,106 @@ extern "C" int dftpav_planner_last_cost_terms(dftpav_planner *p, double *r_terms
   const size_t rows = (size_t)p->last_Q * p->R;
   HIPCHK(h, fetch_async(h, r_terms, p->d_pen_terms, sizeof(double) * kCostTerms * rows));
   HIPCHK(h, fetch_async(h, r_rejected, p->d_pen_rej, sizeof(int) * rows));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return DFTPAV_OK;
+}
+
+// ------------------------------------------------- the clearance of executing plans, and the clearance filter (clearance.hip)
+static int fetch_clearance(dftpav_handle *h, const dftpav_clearance_out *out, const int *d_d2, const int *d_arg, const double *d_m, size_t rows) {
+  HIPCHK(h, fetch_async(h, out->min_d2, d_d2, sizeof(int) * rows));
+  HIPCHK(h, fetch_async(h, out->arg, d_arg, sizeof(int) * rows));
+  HIPCHK(h, fetch_async(h, out->clearance, d_m, sizeof(double) * rows));
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_planner_check_clearance(dftpav_planner *p, double check_dt, const dftpav_clearance_out *out) {
+  if (!p || !out || !(check_dt > 0.0) || !std::isfinite(check_dt)) return DFTPAV_E_INVALID;
+  dftpav_handle *h = p->h;
+  if (!h->d_cells) return DFTPAV_E_INVALID; // no map
+  const size_t S = (size_t)p->max_queries;
+  if (!p->d_exec) { // nothing was ever installed: every slot is empty
+    if (out->min_d2) std::fill(out->min_d2, out->min_d2 + S, DFTPAV_DIST_FAR);
+    if (out->arg) std::fill(out->arg, out->arg + S, -1);
+    if (out->clearance) std::fill(out->clearance, out->clearance + S, HUGE_VAL);
+    return DFTPAV_OK;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  if (int rc = ensure_dist_field(h)) return rc;
+  std::vector<double> tab;
+  int n_t = 0, n_v = 0;
+  if (int rc = validation_table(h->params, check_dt, kClearanceVertexRes, 0, tab, &n_t, &n_v)) return rc;
+  for (hipEvent_t *e : {&h->kev0, &h->kev1})
+    if (!*e) HIPCHK(h, hipEventCreate(e));
+  double *d_tab = nullptr, *d_m = nullptr;
+  int *d_int = nullptr; // min_d2 | arg
+  DevScratch tmp(h);
+  HIPCHK(h, tmp.alloc(d_tab, tab.size()));
+  HIPCHK(h, tmp.alloc(d_m, S));
+  HIPCHK(h, tmp.alloc(d_int, 2 * S));
+  ClearanceTableArgs A{};
+  A.C = clearance_common(h, d_tab, n_t, n_v, check_dt);
+  A.C.min_d2 = d_int;
+  A.C.arg = d_int + S;
+  A.C.clearance = d_m;
+  A.T = p->T;
+  h->ktimed = false; // until the whole chain has run
+  HIPCHK(h, hipMemcpyAsync(d_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipEventRecord(h->kev0, h->stream));
+  HIPCHK(h, launch_clearance_table(A, h->stream));
+  HIPCHK(h, hipEventRecord(h->kev1, h->stream));
+  if (int rc = fetch_clearance(h, out, A.C.min_d2, A.C.arg, A.C.clearance, S)) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->ktimed = true;
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_planner_set_clearance_filter(dftpav_planner *p, double min_clearance, double check_dt) {
+  if (!p) return DFTPAV_E_INVALID;
+  if (min_clearance < 0.0) { // off: the buffers stay, nothing reads them
+    p->clr_on = false;
+    return DFTPAV_OK;
+  }
+  if (!std::isfinite(min_clearance) || !(check_dt > 0.0) || !std::isfinite(check_dt)) return DFTPAV_E_INVALID; // NaN, +inf
+  dftpav_handle *h = p->h;
+  HIPCHK(h, hipSetDevice(h->device));
+  std::vector<double> tab;
+  int n_t = 0, n_v = 0;
+  if (int rc = validation_table(h->params, check_dt, kClearanceVertexRes, 0, tab, &n_t, &n_v)) return rc;
+  if (!p->d_clr) {
+    const size_t rows = (size_t)p->max_queries * p->R;
+    auto fields = [&](auto &take) {
+      p->d_clr_tab = (double *)take(sizeof(double) * tab.size()); // (its size follows from the parameters alone)
+      p->d_clr_m = (double *)take(sizeof(double) * rows);
+      p->d_clr_d2 = (int *)take(sizeof(int) * rows);
+      p->d_clr_arg = (int *)take(sizeof(int) * rows);
+      p->d_clr_flags = (int *)take(sizeof(int) * rows);
+      p->d_clr_col = (int *)take(sizeof(int) * rows);
+    };
+    unsigned char *base = nullptr;
+    HIPCHK(h, hipMalloc(&base, carve(nullptr, fields)));
+    carve(base, fields);
+    p->d_clr = base;
+    p->clr_tab_dt = 0.0;
+    p->h_clr_inf.assign(rows, HUGE_VAL);
+  }
+  if (p->clr_tab_dt != check_dt) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(p->d_clr_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
+    p->clr_tab_dt = check_dt;
+    p->clr_n_t = n_t;
+    p->clr_n_v = n_v;
+  }
+  p->clr_min = min_clearance;
+  p->clr_dt = check_dt;
+  p->clr_on = true;
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_planner_last_clearance(dftpav_planner *p, const dftpav_clearance_out *out) {
+  if (!p || !out || !p->last_clr || p->last_Q <= 0) return DFTPAV_E_INVALID;
+  dftpav_handle *h = p->h;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (int rc = fetch_clearance(h, out, p->d_clr_d2, p->d_clr_arg, p->d_clr_m, (size_t)p->last_Q * p->R)) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return DFTPAV_OK;
 }

@@ -384,6 +384,7 @@ extern "C" int dftpav_set_grid_map(dftpav_handle *h, const dftpav_grid_map *map)
   HIPCHK(h, hipMemcpy(h->d_cells, map->cells, ncell, hipMemcpyHostToDevice));
   h->map = *map;
   h->map.cells = nullptr;
+  h->dist_stale = true; // the distance field, if a clearance call ever asks for one, is built again by that call
   if (ncell <= (size_t)8 * 40 * 1024) { // <= 40 KB of bits per workgroup: four workgroups per CU
     std::vector<unsigned> bits((ncell + 31) / 32, 0u);
     for (size_t i = 0; i < ncell; i++)
@@ -653,6 +654,107 @@ extern "C" int dftpav_limits_last_ms(dftpav_handle *h, float *ms) {
   if (!h || !ms || !h->ltimed) return DFTPAV_E_INVALID;
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, hipEventElapsedTime(ms, h->lev0, h->lev1));
+  return DFTPAV_OK;
+}
+
+// ------------------------------------------------- the distance field of the map, the clearance of solved plans (distfield.hip, clearance.hip)
+int dftpav::ensure_dist_field(dftpav_handle *h) {
+  if (!h->d_cells) return DFTPAV_E_INVALID; // no map
+  if (h->map.size_x > kDistMaxSide || h->map.size_y > kDistMaxSide) return DFTPAV_E_UNSUPPORTED;
+  if (!h->dist_stale) return DFTPAV_OK;
+  const size_t ncell = (size_t)h->map.size_x * h->map.size_y;
+  for (hipEvent_t *e : {&h->fev0, &h->fev1})
+    if (!*e) HIPCHK(h, hipEventCreate(e));
+  if (h->dist_cells < ncell) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->d_dist) (void)hipFree(h->d_dist);
+    h->d_dist = nullptr;
+    h->dist_cells = 0;
+    HIPCHK(h, hipMalloc(&h->d_dist, sizeof(int) * 2 * ncell));
+    h->dist_cells = ncell;
+  }
+  const DistFieldArgs A{h->d_cells, h->map.size_x, h->map.size_y, h->d_dist + h->dist_cells, h->d_dist};
+  h->ftimed = false;
+  HIPCHK(h, hipEventRecord(h->fev0, h->stream));
+  HIPCHK(h, launch_dist_field(A, h->stream));
+  HIPCHK(h, hipEventRecord(h->fev1, h->stream));
+  h->ftimed = true;
+  h->dist_stale = false;
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_grid_distance_field(dftpav_handle *h, int *d2) {
+  if (!h) return DFTPAV_E_INVALID;
+  if (!h->d_cells) return DFTPAV_E_INVALID; // no map
+  HIPCHK(h, hipSetDevice(h->device));
+  if (int rc = ensure_dist_field(h)) return rc;
+  HIPCHK(h, fetch_async(h, d2, h->d_dist, sizeof(int) * (size_t)h->map.size_x * h->map.size_y));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return DFTPAV_OK;
+}
+
+ClearanceCommon dftpav::clearance_common(const dftpav_handle *h, const double *d_tab, int n_t, int n_v, double check_dt) {
+  ClearanceCommon C{};
+  C.grid = dev_grid(h);
+  C.d2 = h->d_dist;
+  C.fp = dev_footprint(h, d_tab + n_t, n_v);
+  C.tab = SampleTable{d_tab, n_t, check_dt};
+  return C;
+}
+
+extern "C" int dftpav_batch_check_clearance(dftpav_batch *b, double check_dt, const dftpav_clearance_out *out) {
+  if (!b || !out || !b->uploaded || !b->solved || !(check_dt > 0.0) || !std::isfinite(check_dt)) return DFTPAV_E_INVALID;
+  dftpav_handle *h = b->h;
+  if (!h->d_cells) return DFTPAV_E_INVALID; // no map
+  HIPCHK(h, hipSetDevice(h->device));
+  if (int rc = ensure_dist_field(h)) return rc;
+  DevBatch D;
+  if (int rc = ensure_coeffs(b, D)) return rc;
+  std::vector<double> tab;
+  int n_t = 0, n_v = 0;
+  if (int rc = validation_table(h->params, check_dt, kClearanceVertexRes, 0, tab, &n_t, &n_v)) return rc;
+  for (hipEvent_t *e : {&h->kev0, &h->kev1})
+    if (!*e) HIPCHK(h, hipEventCreate(e));
+  const size_t B = (size_t)b->B;
+  double *d_tab = nullptr, *d_m = nullptr;
+  int *d_int = nullptr; // min_d2 | arg
+  DevScratch tmp(h);
+  HIPCHK(h, tmp.alloc(d_tab, tab.size()));
+  HIPCHK(h, tmp.alloc(d_m, B));
+  HIPCHK(h, tmp.alloc(d_int, 2 * B));
+  ClearanceBatchArgs A{};
+  A.C = clearance_common(h, d_tab, n_t, n_v, check_dt);
+  A.C.min_d2 = d_int;
+  A.C.arg = d_int + B;
+  A.C.clearance = d_m;
+  A.coeffs = b->d_coef;
+  A.piece_dt = b->d_dt;
+  A.L = b->L;
+  A.B = b->B;
+  A.R = 1;
+  h->ktimed = false; // until the whole chain has run
+  HIPCHK(h, hipMemcpyAsync(d_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipEventRecord(h->kev0, h->stream));
+  HIPCHK(h, launch_clearance_batch(A, h->stream));
+  HIPCHK(h, hipEventRecord(h->kev1, h->stream));
+  HIPCHK(h, fetch_async(h, out->min_d2, A.C.min_d2, sizeof(int) * B));
+  HIPCHK(h, fetch_async(h, out->arg, A.C.arg, sizeof(int) * B));
+  HIPCHK(h, fetch_async(h, out->clearance, A.C.clearance, sizeof(double) * B));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->ktimed = true;
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_clearance_last_ms(dftpav_handle *h, float *field_ms, float *check_ms) {
+  if (!h) return DFTPAV_E_INVALID;
+  if (field_ms) *field_ms = 0.0f;
+  if (check_ms) *check_ms = 0.0f;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (field_ms && h->ftimed) {
+    HIPCHK(h, hipEventSynchronize(h->fev1));
+    HIPCHK(h, hipEventElapsedTime(field_ms, h->fev0, h->fev1));
+  }
+  if (check_ms && h->ktimed) HIPCHK(h, hipEventElapsedTime(check_ms, h->kev0, h->kev1));
   return DFTPAV_OK;
 }
 

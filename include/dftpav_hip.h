@@ -964,6 +964,58 @@ int dftpav_planner_last_cost_terms(dftpav_planner *p, double *r_terms, int *r_re
 int dftpav_debug_penalty_gate(dftpav_handle *h, int n, const double *terms, const dftpav_penalty_caps *caps, const int *flags_in,
                               int *flags_out, int *rejected);
 
+/* ---- the distance field of the grid map, the clearance of solved plans, and a selection filter on it -------------------
+ * The collision re-check answers yes or no; these calls say how close a plan comes to the map's occupied cells.
+ *
+ * The field.  For the map of dftpav_set_grid_map, cell (ix, iy) gets
+ *   d2[ix + size_x * iy] = min over cells (jx, jy) with cells[jx + size_x * jy] == 80 of (ix - jx)^2 + (iy - jy)^2,
+ * int32 in cell units, exact (an exact Euclidean distance transform, distfield.hip); DFTPAV_DIST_FAR everywhere on a map without
+ * an occupied cell.  It belongs to the handle and is built lazily, on the handle's stream, by the first call of this section that
+ * needs it after a dftpav_set_grid_map; that call itself launches nothing new and only marks the field stale, and a handle that
+ * never asks for clearance never allocates or launches any of this.  A map with a side above 16384 cells is refused by every
+ * call here with DFTPAV_E_UNSUPPORTED (every sum then fits in 32 bits).
+ * dftpav_grid_distance_field: builds the field if the map changed and copies it to d2 [size_y][size_x]; d2 == NULL: build only.
+ *
+ * The clearance of a plan.  Samples: exactly those of dftpav_batch_validate and dftpav_batch_check_limits -- per gear segment
+ * t = 0.0; t < duration; t += check_dt, from the tabulated running sum of dftpav_debug_validation_table, with the global sample
+ * indices of `first_sample`; the pose as the re-check forms it (yaw from the correctly rounded atan2, then sincos).  Probe points:
+ * exactly those of the re-check's CheckCollisionUsingPosAndYaw -- the dense vertices of the four edges of the outline at the
+ * reference's own spacing 0.1 (shapes.h:200-201), then its four corners.  A point's value is d2 at round((p - origin) / resolution);
+ * a point outside the grid is SKIPPED, consistent with "out of range counts as free".  Per trajectory:
+ *   min_d2     the minimum over all probe points of all samples; DFTPAV_DIST_FAR if there is no sample, every probe is out of
+ *              range, or the map has no occupied cell
+ *   arg        the lowest global sample index at which min_d2 is reached; -1 when min_d2 is DFTPAV_DIST_FAR
+ *   clearance  resolution * sqrt((double)min_d2), +inf for DFTPAV_DIST_FAR
+ * The meaning is grid-quantised: distances are between CELL CENTRES -- the cell a probe point rounds to and the nearest occupied
+ * cell -- so the real distance from the outline to occupied area differs from `clearance` by at most one cell diagonal
+ * (resolution * sqrt(2)); and only the outline is probed, not the footprint's interior (the reference's check has no interior
+ * probes either).  min_d2 == 0 holds exactly when the re-check with vertex_res 0.1 and the same check_dt reports a collision, and
+ * arg is then its first_sample.
+ * dftpav_batch_check_clearance: the B trajectories of a solved batch (or the coefficients of dftpav_debug_batch_set_coeffs).  Rows [B].
+ * dftpav_planner_check_clearance: a row per slot of the executing table; empty slots (and every slot before the table was filled
+ *   once) give DFTPAV_DIST_FAR, -1, +inf.  The table is not written.
+ * dftpav_planner_set_clearance_filter: min_clearance < 0 (the default): dftpav_plan_queries and dftpav_replan_tick do exactly what
+ *   they do without this call -- the same launches, the same bits.  Otherwise: per layout group the clearance kernel runs after
+ *   the collision re-check (and after the limits kernel, when that filter is set) and before the terms launch / penalty gate; a
+ *   restart is rejected unless clearance >= min_clearance, and the selection sees the OR of collision, the other filters' flags
+ *   and this one.  A query whose every restart is rejected ends DFTPAV_PLAN_NO_VALID_RESTART (a tick then keeps the slot's old
+ *   plan).  r_collision / r_first_sample of dftpav_plan_out stay the pure collision results.  min_clearance = 0.0 is legal and
+ *   rejects nothing that does not already collide at the spacing 0.1.  The device buffers of the rows are allocated by this call.
+ * dftpav_planner_last_clearance: the rows [Q][R] (query, restart) of the last dftpav_plan_queries call that ran with the filter
+ *   on; DFTPAV_DIST_FAR, -1, +inf for the queries no restart was solved for.  DFTPAV_E_INVALID when that call ran without it.
+ * dftpav_clearance_last_ms: device time in ms (the handle's HIP events) of the last field build (both passes) and of the last
+ *   clearance kernel of one of the two check_clearance calls; 0.0 for what has not run.  Either pointer may be NULL.
+ * Every pointer of dftpav_clearance_out may be NULL.  A refused call changes nothing and returns DFTPAV_E_INVALID: no grid map
+ * installed, no solved coefficients, check_dt <= 0, NaN or infinite, out NULL, a min_clearance that is NaN or +inf. */
+#define DFTPAV_DIST_FAR 2147483647
+int dftpav_grid_distance_field(dftpav_handle *h, int *d2 /*[size_y][size_x] or NULL: build only*/);
+typedef struct dftpav_clearance_out { int *min_d2; int *arg; double *clearance; } dftpav_clearance_out; /* [n], any may be NULL */
+int dftpav_batch_check_clearance(dftpav_batch *b, double check_dt, const dftpav_clearance_out *out);
+int dftpav_planner_check_clearance(dftpav_planner *p, double check_dt, const dftpav_clearance_out *out);
+int dftpav_planner_set_clearance_filter(dftpav_planner *p, double min_clearance, double check_dt); /* min_clearance < 0: off (default) */
+int dftpav_planner_last_clearance(dftpav_planner *p, const dftpav_clearance_out *out);            /* rows [Q][R] */
+int dftpav_clearance_last_ms(dftpav_handle *h, float *field_ms, float *check_ms);
+
 /* One-shot convenience == OptimizeTrajectory for B trajectories. */
 int dftpav_solve_batch(dftpav_handle *h, const dftpav_layout *layout, int B,
                        const dftpav_batch_data *d, double *x, double *final_cost,
