@@ -234,6 +234,13 @@ struct SearchSetup {
   int slots = 0;
 };
 
+// a validation_table kept on the device by a selection filter, and the check_dt it was tabulated for
+struct CachedTable {
+  double *d = nullptr;
+  int n_t = 0, n_v = 0;
+  double dt = 0.0;
+};
+
 struct dftpav_planner {
   dftpav_handle *h = nullptr;
   int max_queries = 0, R = 0;
@@ -248,6 +255,9 @@ struct dftpav_planner {
   long long sig[6] = {0, 0, 0, 0, 0, 0}; // max_seg, max_pieces, max_path, max_states, doubles of the search tables, of the validation tables
   double *d_st = nullptr, *d_en = nullptr, *d_ct = nullptr, *d_tabs = nullptr, *d_paths = nullptr, *d_vt = nullptr;
   int *d_skip = nullptr, *d_sints = nullptr, *d_fe_len = nullptr, *d_members = nullptr, *d_minit = nullptr, *d_col = nullptr, *d_first = nullptr;
+  // what the selection filters set, indexed like d_col (trajectory order, a group at g_off[g] * R): cleared once per call that runs with a
+  // filter, written by the filters' kernels only where they reject, read by the selection beside d_col.  Never touched with every filter off.
+  int *d_reject = nullptr;
   dftpav_frontend_out fe{}; // device pointers
   double *d_poses = nullptr;
   size_t fe_zero_bytes = 0; // the front-end outputs are one stretch of the arena, zeroed per call (as dftpav_frontend_resample does)
@@ -295,27 +305,25 @@ struct dftpav_planner {
   bool lim_on = false;
   dftpav_limits lim{};
   double lim_dt = 0.0;
-  unsigned char *d_lim = nullptr; // one allocation: the sample times, the rows [max_queries * R] of a call, the selection's input
-  double *d_lim_tab = nullptr, *d_lim_max = nullptr;
-  int lim_n_t = 0;
-  double lim_tab_dt = 0.0; // what d_lim_tab was tabulated for
-  int *d_lim_arg = nullptr, *d_lim_viol = nullptr, *d_lim_feas = nullptr, *d_lim_reject = nullptr, *d_lim_col = nullptr;
+  unsigned char *d_lim = nullptr; // one allocation: the sample table, the rows [max_queries * R] of a call
+  CachedTable lim_tab;
+  double *d_lim_max = nullptr;
+  int *d_lim_arg = nullptr, *d_lim_viol = nullptr, *d_lim_feas = nullptr;
   bool last_lim = false; // the last dftpav_plan_queries call ran with the filter
   // ---- the penalty filter (dftpav_planner_set_penalty_filter): off by default, and then none of this is touched
   bool pen_on = false;
   dftpav_penalty_caps pen{};
-  unsigned char *d_pen = nullptr; // one allocation: the rows [max_queries * R] of a call, the selection's input
+  unsigned char *d_pen = nullptr; // one allocation: the rows [max_queries * R] of a call
   double *d_pen_terms = nullptr;
-  int *d_pen_rej = nullptr, *d_pen_flags = nullptr, *d_pen_col = nullptr;
+  int *d_pen_rej = nullptr;
   bool last_pen = false; // the last dftpav_plan_queries call ran with the filter
   // ---- the clearance filter (dftpav_planner_set_clearance_filter): off by default, and then none of this is touched
   bool clr_on = false;
   double clr_min = -1.0, clr_dt = 0.0;
-  unsigned char *d_clr = nullptr; // one allocation: the two tables, the rows [max_queries * R] of a call, the selection's input
-  double *d_clr_tab = nullptr, *d_clr_m = nullptr;
-  int clr_n_t = 0, clr_n_v = 0;
-  double clr_tab_dt = 0.0; // what d_clr_tab was tabulated for
-  int *d_clr_d2 = nullptr, *d_clr_arg = nullptr, *d_clr_flags = nullptr, *d_clr_col = nullptr;
+  unsigned char *d_clr = nullptr; // one allocation: the two tables, the rows [max_queries * R] of a call
+  CachedTable clr_tab;
+  double *d_clr_m = nullptr;
+  int *d_clr_d2 = nullptr, *d_clr_arg = nullptr;
   std::vector<double> h_clr_inf; // +inf, the rows' clearance before a call's kernels run
   bool last_clr = false; // the last dftpav_plan_queries call ran with the filter
 };

@@ -144,6 +144,7 @@ static int planner_buffers(dftpav_planner *p, const dftpav_plan_params &pp, int 
     p->d_members = (int *)take(sizeof(int) * Q);
     p->d_col = (int *)take(sizeof(int) * Q * R);
     p->d_first = (int *)take(sizeof(int) * Q * R);
+    p->d_reject = (int *)take(sizeof(int) * Q * R);
     p->d_poses = (double *)take(sizeof(double) * 3 * Q * MS * MST);
     p->d_fe0 = (unsigned char *)take(0);
     p->fe.max_seg = pp.max_seg;
@@ -352,7 +353,6 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
     HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)p->d_clr_d2, DFTPAV_DIST_FAR, rows, h->stream));
     HIPCHK(h, hipMemsetAsync(p->d_clr_arg, 0xff, sizeof(int) * rows, h->stream));
     HIPCHK(h, hipMemcpyAsync(p->d_clr_m, p->h_clr_inf.data(), sizeof(double) * rows, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemsetAsync(p->d_clr_col, 0, sizeof(int) * rows, h->stream));
   }
   if (filt) { // the rows of the queries no restart is solved for: zero, arg -1
     const size_t rows = nq * (size_t)R;
@@ -360,14 +360,15 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
     HIPCHK(h, hipMemsetAsync(p->d_lim_arg, 0xff, sizeof(int) * kLimQ * rows, h->stream));
     HIPCHK(h, hipMemsetAsync(p->d_lim_viol, 0, sizeof(int) * kLimQ * rows, h->stream));
     HIPCHK(h, hipMemsetAsync(p->d_lim_feas, 0, sizeof(int) * rows, h->stream));
-    HIPCHK(h, hipMemsetAsync(p->d_lim_col, 0, sizeof(int) * rows, h->stream));
   }
   if (pen) { // likewise: zero rows
     const size_t rows = nq * (size_t)R;
     HIPCHK(h, hipMemsetAsync(p->d_pen_terms, 0, sizeof(double) * kCostTerms * rows, h->stream));
     HIPCHK(h, hipMemsetAsync(p->d_pen_rej, 0, sizeof(int) * rows, h->stream));
-    HIPCHK(h, hipMemsetAsync(p->d_pen_col, 0, sizeof(int) * rows, h->stream));
   }
+  const bool any_filter = filt || clr || pen;
+  if (any_filter) // the reject flags, trajectory order as d_col: the filters only set them
+    HIPCHK(h, hipMemsetAsync(p->d_reject, 0, sizeof(int) * nq * (size_t)R, h->stream));
   for (int g = 0; g < ng; g++) {
     dftpav_batch *b = batch[g];
     const int nm = g_off[g + 1] - g_off[g];
@@ -409,11 +410,11 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
     if (int rc = ensure_coeffs(b, D)) return rc;
     int *col = p->d_col + (size_t)g_off[g] * R, *fst = p->d_first + (size_t)g_off[g] * R;
     if (int rc = validate_on_stream(b, nm * R, p->d_vt, n_t, n_v, pp->check_dt, col, fst)) return rc;
-    const int *sel_col = col;
-    if (filt) { // the selection reads collision | !feasible; the collision flags themselves go to d_lim_col by (query, restart)
+    int *rej = any_filter ? p->d_reject + (size_t)g_off[g] * R : nullptr;
+    if (filt) { // rejects a trajectory that is not feasible
       LimitsBatchArgs LA{};
       if (!limits_common(h->params, p->lim, LA.C)) return DFTPAV_E_INVALID; // (checked when the filter was set)
-      LA.C.tab = SampleTable{p->d_lim_tab, p->lim_n_t, p->lim_dt};
+      LA.C.tab = SampleTable{p->lim_tab.d, p->lim_tab.n_t, p->lim_dt};
       LA.C.max_abs = p->d_lim_max;
       LA.C.arg = p->d_lim_arg;
       LA.C.violated = p->d_lim_viol;
@@ -424,15 +425,12 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
       LA.B = nm * R;
       LA.members = A.members;
       LA.R = R;
-      LA.collision = col;
-      LA.reject = p->d_lim_reject + (size_t)g_off[g] * R;
-      LA.collision_rows = p->d_lim_col;
+      LA.reject = rej;
       HIPCHK(h, launch_limits_batch(LA, h->stream));
-      sel_col = LA.reject;
     }
-    if (clr) { // the selection reads its flag | clearance < min_clearance; without the limit filter the pure collision flags go to d_clr_col
+    if (clr) { // rejects a trajectory unless clearance >= min_clearance
       ClearanceBatchArgs CA{};
-      CA.C = clearance_common(h, p->d_clr_tab, p->clr_n_t, p->clr_n_v, p->clr_dt);
+      CA.C = clearance_common(h, p->clr_tab.d, p->clr_tab.n_t, p->clr_tab.n_v, p->clr_dt);
       CA.C.min_d2 = p->d_clr_d2;
       CA.C.arg = p->d_clr_arg;
       CA.C.clearance = p->d_clr_m;
@@ -442,19 +440,14 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
       CA.B = nm * R;
       CA.members = A.members;
       CA.R = R;
-      CA.flags_in = sel_col;
+      CA.reject = rej;
       CA.min_clearance = p->clr_min;
-      CA.flags_out = p->d_clr_flags + (size_t)g_off[g] * R;
-      CA.collision = filt ? nullptr : col;
-      CA.collision_rows = p->d_clr_col;
       HIPCHK(h, launch_clearance_batch(CA, h->stream));
-      sel_col = CA.flags_out;
     }
-    if (pen) { // the selection reads its flag | a penalty sum above its cap; without the other filters the pure collision flags go to d_pen_col
+    if (pen) { // rejects a trajectory with a penalty sum above its cap
       if (int rc = cost_terms_on_stream(b, nullptr)) return rc;
       PenaltyGateArgs G{};
       G.terms = b->d_terms;
-      G.flags_in = sel_col;
       G.members = A.members;
       G.n = nm * R;
       G.R = R;
@@ -463,16 +456,14 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
       G.cap_feas = p->pen.feasibility;
       G.r_terms = p->d_pen_terms;
       G.r_rejected = p->d_pen_rej;
-      G.flags_out = p->d_pen_flags + (size_t)g_off[g] * R;
-      G.collision = (filt || clr) ? nullptr : col;
-      G.collision_rows = p->d_pen_col;
+      G.reject = rej;
       HIPCHK(h, launch_penalty_gate(G, h->stream));
-      sel_col = G.flags_out;
     }
     PlanSelectArgs Z{};
     Z.cost = b->d_f;
     Z.success = b->d_success;
-    Z.collision = sel_col;
+    Z.collision = col;
+    Z.reject = rej;
     Z.status = b->d_status;
     Z.iters = b->d_iters;
     Z.evals = b->d_evals;
@@ -518,9 +509,7 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
   HIPCHK(h, fetch_async(h, out->coeff_dt, p->d_wdt, sizeof(double) * nq * MS));
   HIPCHK(h, fetch_async(h, out->r_final_cost, p->d_rcost, sizeof(double) * nq * R));
   int *const r_out[6] = {out->r_status, out->r_success, out->r_iters, out->r_evals, out->r_collision, out->r_first_sample};
-  const int *pure_col = filt ? p->d_lim_col : (clr ? p->d_clr_col : (pen ? p->d_pen_col : p->d_rint[4]));
-  for (int k = 0; k < 6; k++) // (with a filter the selection copied its own input into d_rint[4]: the pure flags are in d_lim_col / d_clr_col / d_pen_col)
-    HIPCHK(h, fetch_async(h, r_out[k], k == 4 ? pure_col : p->d_rint[k], sizeof(int) * nq * R));
+  for (int k = 0; k < 6; k++) HIPCHK(h, fetch_async(h, r_out[k], p->d_rint[k], sizeof(int) * nq * R));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   for (int q = 0; q < Q; q++) {
     if (status[q] != DFTPAV_PLAN_OK) {
@@ -593,25 +582,26 @@ extern "C" int dftpav_debug_penalty_gate(dftpav_handle *h, int n, const double *
   if (n == 0) return DFTPAV_OK;
   HIPCHK(h, hipSetDevice(h->device));
   double *d_terms = nullptr;
-  int *d_int = nullptr; // flags_in | flags_out | rejected
+  int *d_int = nullptr; // flags (flags_in != 0 going in, flags_out coming back) | rejected
   DevScratch tmp(h);
   HIPCHK(h, tmp.alloc(d_terms, (size_t)n * kCostTerms));
-  HIPCHK(h, tmp.alloc(d_int, 3 * (size_t)n));
+  HIPCHK(h, tmp.alloc(d_int, 2 * (size_t)n));
+  std::vector<int> flags((size_t)n);
+  for (int t = 0; t < n; t++) flags[t] = flags_in[t] != 0 ? 1 : 0;
   HIPCHK(h, hipMemcpyAsync(d_terms, terms, sizeof(double) * (size_t)n * kCostTerms, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(d_int, flags_in, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_int, flags.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice, h->stream));
   PenaltyGateArgs G{};
   G.terms = d_terms;
-  G.flags_in = d_int;
   G.n = n;
   G.R = 1;
   G.cap_corridor = caps->corridor;
   G.cap_surround = caps->surround;
   G.cap_feas = caps->feasibility;
-  G.r_rejected = d_int + 2 * (size_t)n;
-  G.flags_out = d_int + n;
+  G.r_rejected = d_int + n;
+  G.reject = d_int;
   HIPCHK(h, launch_penalty_gate(G, h->stream));
-  HIPCHK(h, hipMemcpyAsync(flags_out, d_int + n, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, fetch_async(h, rejected, d_int + 2 * (size_t)n, sizeof(int) * (size_t)n));
+  HIPCHK(h, hipMemcpyAsync(flags_out, d_int, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, fetch_async(h, rejected, d_int + n, sizeof(int) * (size_t)n));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return DFTPAV_OK;
 }
@@ -1128,6 +1118,37 @@ extern "C" int dftpav_publish_last_ms(dftpav_planner *p, float *ms) {
   return DFTPAV_OK;
 }
 
+// ------------------------------------------------- the sample table of a selection filter
+// A validation_table for (check_dt, vertex_res) kept on the device.  It lies at the head of the filter's one allocation `base`, made by
+// the first call (rows(take) names the filter's other arrays), and is uploaded again only when check_dt is not the one T holds.  A
+// refusal changes nothing.
+template <class F> static int cached_table(dftpav_planner *p, double check_dt, double vertex_res, unsigned char *&base, CachedTable &T, F &&rows) {
+  dftpav_handle *h = p->h;
+  HIPCHK(h, hipSetDevice(h->device));
+  std::vector<double> tab;
+  int n_t = 0, n_v = 0;
+  if (int rc = validation_table(h->params, check_dt, vertex_res, 0, tab, &n_t, &n_v)) return rc;
+  if (!base) {
+    auto fields = [&](auto &take) {
+      T.d = (double *)take(sizeof(double) * tab.size()); // (its size follows from the parameters alone)
+      rows(take);
+    };
+    unsigned char *fresh = nullptr;
+    HIPCHK(h, hipMalloc(&fresh, carve(nullptr, fields)));
+    carve(fresh, fields);
+    base = fresh;
+    T.dt = 0.0;
+  }
+  if (T.dt != check_dt) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpy(T.d, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
+    T.dt = check_dt;
+    T.n_t = n_t;
+    T.n_v = n_v;
+  }
+  return DFTPAV_OK;
+}
+
 // ------------------------------------------------- solved plans against the kinematic limits (limits.hip)
 static int fetch_limits(dftpav_handle *h, const dftpav_limits_out *out, const LimitsCommon &C, size_t rows) {
   HIPCHK(h, fetch_async(h, out->max_abs, C.max_abs, sizeof(double) * kLimQ * rows));
@@ -1189,33 +1210,14 @@ extern "C" int dftpav_planner_set_limit_filter(dftpav_planner *p, const dftpav_l
   dftpav_handle *h = p->h;
   LimitsCommon C{};
   if (!limits_common(h->params, *l, C)) return DFTPAV_E_INVALID;
-  HIPCHK(h, hipSetDevice(h->device));
-  std::vector<double> tab;
-  int n_t = 0, n_v = 0;
-  if (int rc = validation_table(h->params, check_dt, 1.0, 0, tab, &n_t, &n_v)) return rc; // (the sample times are its first n_t entries)
-  if (!p->d_lim) {
-    const size_t rows = (size_t)p->max_queries * p->R;
-    auto fields = [&](auto &take) {
-      p->d_lim_tab = (double *)take(sizeof(double) * (size_t)n_t);
-      p->d_lim_max = (double *)take(sizeof(double) * kLimQ * rows);
-      p->d_lim_arg = (int *)take(sizeof(int) * kLimQ * rows);
-      p->d_lim_viol = (int *)take(sizeof(int) * kLimQ * rows);
-      p->d_lim_feas = (int *)take(sizeof(int) * rows);
-      p->d_lim_reject = (int *)take(sizeof(int) * rows);
-      p->d_lim_col = (int *)take(sizeof(int) * rows);
-    };
-    unsigned char *base = nullptr;
-    HIPCHK(h, hipMalloc(&base, carve(nullptr, fields)));
-    carve(base, fields);
-    p->d_lim = base;
-    p->lim_tab_dt = 0.0;
-  }
-  if (p->lim_tab_dt != check_dt) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(p->d_lim_tab, tab.data(), sizeof(double) * (size_t)n_t, hipMemcpyHostToDevice));
-    p->lim_tab_dt = check_dt;
-    p->lim_n_t = n_t;
-  }
+  const size_t rows = (size_t)p->max_queries * p->R;
+  if (int rc = cached_table(p, check_dt, 1.0, p->d_lim, p->lim_tab, [&](auto &take) { // (the kernel reads the sample times only)
+        p->d_lim_max = (double *)take(sizeof(double) * kLimQ * rows);
+        p->d_lim_arg = (int *)take(sizeof(int) * kLimQ * rows);
+        p->d_lim_viol = (int *)take(sizeof(int) * kLimQ * rows);
+        p->d_lim_feas = (int *)take(sizeof(int) * rows);
+      }))
+    return rc;
   p->lim = *l;
   p->lim_dt = check_dt;
   p->lim_on = true;
@@ -1251,8 +1253,6 @@ extern "C" int dftpav_planner_set_penalty_filter(dftpav_planner *p, const dftpav
     auto fields = [&](auto &take) {
       p->d_pen_terms = (double *)take(sizeof(double) * kCostTerms * rows);
       p->d_pen_rej = (int *)take(sizeof(int) * rows);
-      p->d_pen_flags = (int *)take(sizeof(int) * rows);
-      p->d_pen_col = (int *)take(sizeof(int) * rows);
     };
     unsigned char *base = nullptr;
     HIPCHK(h, hipMalloc(&base, carve(nullptr, fields)));
@@ -1331,35 +1331,14 @@ extern "C" int dftpav_planner_set_clearance_filter(dftpav_planner *p, double min
     return DFTPAV_OK;
   }
   if (!std::isfinite(min_clearance) || !(check_dt > 0.0) || !std::isfinite(check_dt)) return DFTPAV_E_INVALID; // NaN, +inf
-  dftpav_handle *h = p->h;
-  HIPCHK(h, hipSetDevice(h->device));
-  std::vector<double> tab;
-  int n_t = 0, n_v = 0;
-  if (int rc = validation_table(h->params, check_dt, kClearanceVertexRes, 0, tab, &n_t, &n_v)) return rc;
-  if (!p->d_clr) {
-    const size_t rows = (size_t)p->max_queries * p->R;
-    auto fields = [&](auto &take) {
-      p->d_clr_tab = (double *)take(sizeof(double) * tab.size()); // (its size follows from the parameters alone)
-      p->d_clr_m = (double *)take(sizeof(double) * rows);
-      p->d_clr_d2 = (int *)take(sizeof(int) * rows);
-      p->d_clr_arg = (int *)take(sizeof(int) * rows);
-      p->d_clr_flags = (int *)take(sizeof(int) * rows);
-      p->d_clr_col = (int *)take(sizeof(int) * rows);
-    };
-    unsigned char *base = nullptr;
-    HIPCHK(h, hipMalloc(&base, carve(nullptr, fields)));
-    carve(base, fields);
-    p->d_clr = base;
-    p->clr_tab_dt = 0.0;
-    p->h_clr_inf.assign(rows, HUGE_VAL);
-  }
-  if (p->clr_tab_dt != check_dt) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, hipMemcpy(p->d_clr_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
-    p->clr_tab_dt = check_dt;
-    p->clr_n_t = n_t;
-    p->clr_n_v = n_v;
-  }
+  const size_t rows = (size_t)p->max_queries * p->R;
+  if (int rc = cached_table(p, check_dt, kClearanceVertexRes, p->d_clr, p->clr_tab, [&](auto &take) {
+        p->d_clr_m = (double *)take(sizeof(double) * rows);
+        p->d_clr_d2 = (int *)take(sizeof(int) * rows);
+        p->d_clr_arg = (int *)take(sizeof(int) * rows);
+      }))
+    return rc;
+  if (p->h_clr_inf.empty()) p->h_clr_inf.assign(rows, HUGE_VAL);
   p->clr_min = min_clearance;
   p->clr_dt = check_dt;
   p->clr_on = true;

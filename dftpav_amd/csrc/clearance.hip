@@ -25,16 +25,12 @@
 #include <climits>
 
 #include "clearance_args.h"
+#include "traj_segments.h"
 
 namespace dftpav {
 
 namespace {
 
-struct ClrSeg { // the segments of one trajectory, in LDS
-  int count[kMaxSeg + 1]; // samples of the segments before segment i
-  int piece0[kMaxSeg], pn[kMaxSeg], sg[kMaxSeg];
-  double dt[kMaxSeg];
-};
 struct ClrRed { // what lane 0 of each wave leaves for the last step
   int d[4], i[4];
 };
@@ -52,7 +48,7 @@ __device__ inline double cl_metres(const ClearanceCommon &C, int d2) {
 }
 
 // the samples of one trajectory (its segments in S, its pieces at cb) into result row `row`; returns min_d2 (thread 0 only)
-__device__ inline int cl_trajectory(const ClearanceCommon &C, const ClrSeg &S, ClrRed &Rd, int M, const double *cb, size_t row) {
+__device__ inline int cl_trajectory(const ClearanceCommon &C, const SegTable &S, ClrRed &Rd, int M, const double *cb, size_t row) {
   const int tid = threadIdx.x;
   const int total = S.count[M];
   int best = INT_MAX, bi = INT_MAX;
@@ -98,36 +94,20 @@ __device__ inline int cl_trajectory(const ClearanceCommon &C, const ClrSeg &S, C
 } // namespace
 
 __global__ void __launch_bounds__(256) clearance_batch_kernel(ClearanceBatchArgs A) {
-  __shared__ ClrSeg S;
+  __shared__ SegTable S;
   __shared__ ClrRed Rd;
   const int b = blockIdx.x, tid = threadIdx.x;
   const DevLayout &L = A.L;
   const int M = L.M;
-  if (tid == 0) {
-    int acc = 0;
-    for (int i = 0; i < M; i++) {
-      const double dtp = A.piece_dt[(size_t)b * M + i];
-      S.piece0[i] = L.seg_piece0[i];
-      S.pn[i] = L.piece_nums[i];
-      S.sg[i] = L.singuls[i];
-      S.dt[i] = dtp;
-      S.count[i] = acc;
-      acc += pe::samples_below(A.C.tab, pe::segment_duration(L.piece_nums[i], dtp));
-    }
-    S.count[M] = acc;
-  }
+  if (tid == 0) fill_from_batch(S, A.C.tab, L, A.piece_dt + (size_t)b * M);
   __syncthreads();
   const size_t row = A.members ? (size_t)A.members[b / A.R] * A.R + b % A.R : (size_t)b;
   const int d2 = cl_trajectory(A.C, S, Rd, M, A.coeffs + (size_t)b * L.Ntot * 12, row);
-  if (tid == 0 && A.flags_in) {
-    const bool ok = cl_metres(A.C, d2) >= A.min_clearance;
-    A.flags_out[b] = (A.flags_in[b] != 0 || !ok) ? 1 : 0;
-    if (A.collision) A.collision_rows[row] = A.collision[b];
-  }
+  if (tid == 0 && A.reject && !(cl_metres(A.C, d2) >= A.min_clearance)) A.reject[b] = 1;
 }
 
 __global__ void __launch_bounds__(256) clearance_table_kernel(ClearanceTableArgs A) {
-  __shared__ ClrSeg S;
+  __shared__ SegTable S;
   __shared__ ClrRed Rd;
   const int s = blockIdx.x, tid = threadIdx.x;
   const ExecTable &T = A.T;
@@ -141,19 +121,7 @@ __global__ void __launch_bounds__(256) clearance_table_kernel(ClearanceTableArgs
     }
     return;
   }
-  if (tid == 0) {
-    int acc = 0, p0 = 0;
-    for (int i = 0; i < M; i++) {
-      S.piece0[i] = p0; // the pieces of a slot's segments follow one another
-      S.pn[i] = T.piece_nums[(size_t)s * MS + i];
-      S.sg[i] = T.singul[(size_t)s * MS + i];
-      S.dt[i] = T.coeff_dt[(size_t)s * MS + i];
-      p0 += S.pn[i];
-      S.count[i] = acc;
-      acc += pe::samples_below(A.C.tab, T.duration[(size_t)s * MS + i]);
-    }
-    S.count[M] = acc;
-  }
+  if (tid == 0) fill_from_slot(S, A.C.tab, T, s);
   __syncthreads();
   (void)cl_trajectory(A.C, S, Rd, M, T.coeffs + (size_t)s * MS * T.max_pieces * 12, (size_t)s);
 }

@@ -39,11 +39,8 @@ struct ClearanceBatchArgs {
   int B;
   const int *members; // nullptr: trajectory b writes row b; else row members[b / R] * R + b % R (the [Q][R] rows of a call)
   int R;
-  const int *flags_in;  // [B] or nullptr; with it (the filter):
-  double min_clearance; //   a trajectory is rejected unless clearance >= min_clearance
-  int *flags_out;       //   [B] (flags_in != 0) | rejected, what the selection reads in place of flags_in
-  const int *collision; //   [B] or nullptr: the pure collision flags, copied to collision_rows [rows]
-  int *collision_rows;
+  int *reject;          // [B] or nullptr (the read-out call); the filter: set to 1 unless clearance >= min_clearance, never read or cleared
+  double min_clearance;
 };
 
 // clearance_table_kernel: every slot of the executing table (read only)

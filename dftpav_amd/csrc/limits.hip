@@ -31,16 +31,12 @@
 #include <climits>
 
 #include "limits_args.h"
+#include "traj_segments.h"
 
 namespace dftpav {
 
 namespace {
 
-struct LimSeg { // the segments of one trajectory, in LDS
-  int count[kMaxSeg + 1]; // samples of the segments before segment i
-  int piece0[kMaxSeg], pn[kMaxSeg], sg[kMaxSeg];
-  double dt[kMaxSeg];
-};
 struct LimRed { // what lane 0 of each wave leaves for the last step
   double m[4][kLimQ];
   int i[4][kLimQ];
@@ -58,7 +54,7 @@ __device__ inline void lm_merge(double &a, int &ia, double b, int ib) {
 }
 
 // the samples of one trajectory (its segments in S, its pieces at cb) into result row `row`; returns feasible (thread 0 only)
-__device__ inline int lm_trajectory(const LimitsCommon &C, const LimSeg &S, LimRed &Rd, int M, const double *cb, size_t row) {
+__device__ inline int lm_trajectory(const LimitsCommon &C, const SegTable &S, LimRed &Rd, int M, const double *cb, size_t row) {
   const int tid = threadIdx.x;
   const int total = S.count[M];
   double m[kLimQ];
@@ -143,36 +139,20 @@ __device__ inline int lm_trajectory(const LimitsCommon &C, const LimSeg &S, LimR
 } // namespace
 
 __global__ void __launch_bounds__(256) limits_batch_kernel(LimitsBatchArgs A) {
-  __shared__ LimSeg S;
+  __shared__ SegTable S;
   __shared__ LimRed Rd;
   const int b = blockIdx.x, tid = threadIdx.x;
   const DevLayout &L = A.L;
   const int M = L.M;
-  if (tid == 0) {
-    int acc = 0;
-    for (int i = 0; i < M; i++) {
-      const double dtp = A.piece_dt[(size_t)b * M + i];
-      S.piece0[i] = L.seg_piece0[i];
-      S.pn[i] = L.piece_nums[i];
-      S.sg[i] = L.singuls[i];
-      S.dt[i] = dtp;
-      S.count[i] = acc;
-      acc += pe::samples_below(A.C.tab, pe::segment_duration(L.piece_nums[i], dtp));
-    }
-    S.count[M] = acc;
-  }
+  if (tid == 0) fill_from_batch(S, A.C.tab, L, A.piece_dt + (size_t)b * M);
   __syncthreads();
   const size_t row = A.members ? (size_t)A.members[b / A.R] * A.R + b % A.R : (size_t)b;
   const int feasible = lm_trajectory(A.C, S, Rd, M, A.coeffs + (size_t)b * L.Ntot * 12, row);
-  if (tid == 0 && A.collision) {
-    const int col = A.collision[b];
-    A.reject[b] = (col != 0 || !feasible) ? 1 : 0;
-    A.collision_rows[row] = col;
-  }
+  if (tid == 0 && A.reject && !feasible) A.reject[b] = 1;
 }
 
 __global__ void __launch_bounds__(256) limits_table_kernel(LimitsTableArgs A) {
-  __shared__ LimSeg S;
+  __shared__ SegTable S;
   __shared__ LimRed Rd;
   const int s = blockIdx.x, tid = threadIdx.x;
   const ExecTable &T = A.T;
@@ -187,19 +167,7 @@ __global__ void __launch_bounds__(256) limits_table_kernel(LimitsTableArgs A) {
     }
     return;
   }
-  if (tid == 0) {
-    int acc = 0, p0 = 0;
-    for (int i = 0; i < M; i++) {
-      S.piece0[i] = p0; // the pieces of a slot's segments follow one another
-      S.pn[i] = T.piece_nums[(size_t)s * MS + i];
-      S.sg[i] = T.singul[(size_t)s * MS + i];
-      S.dt[i] = T.coeff_dt[(size_t)s * MS + i];
-      p0 += S.pn[i];
-      S.count[i] = acc;
-      acc += pe::samples_below(A.C.tab, T.duration[(size_t)s * MS + i]);
-    }
-    S.count[M] = acc;
-  }
+  if (tid == 0) fill_from_slot(S, A.C.tab, T, s);
   __syncthreads();
   (void)lm_trajectory(A.C, S, Rd, M, T.coeffs + (size_t)s * MS * T.max_pieces * 12, (size_t)s);
 }

@@ -28,9 +28,7 @@ struct LimitsBatchArgs {
   int B;
   const int *members; // nullptr: trajectory b writes row b; else row members[b / R] * R + b % R (the [Q][R] rows of a call)
   int R;
-  const int *collision; // [B] or nullptr; with it:
-  int *reject;          //   [B]    collision | !feasible, what the selection reads in place of the collision flags
-  int *collision_rows;  //   [rows] the collision flags as they are, by result row
+  int *reject; // [B] or nullptr (the read-out call); the filter: set to 1 where the trajectory is not feasible, never read or cleared
 };
 
 // limits_table_kernel: every slot of the executing table (read only)

@@ -10,10 +10,13 @@
 //                        restart)) and does the set-up half of OptimizeTrajectory that dftpav_batch_upload does on the host
 //                        (traj_optimizer.cpp:30-33 mini_T, :65-76 clamping of the boundary |v| and |a|, :96-115 x0 with
 //                        RealT2VirtualT, the junction position and its angle); gathers the constraint-point poses
-//   plan_select_kernel   per query the cheapest restart that succeeded and does not collide, and its x / coefficients into the
-//                        compact per-query outputs
+//   plan_select_kernel   per query the cheapest restart that succeeded, does not collide and carries no reject flag, and its x /
+//                        coefficients into the compact per-query outputs
 //   penalty_gate_kernel  with dftpav_planner_set_penalty_filter, in front of the selection: per (query, restart) the five terms of
-//                        the solution's cost into their row, and the selection's flag |= a penalty sum above its cap
+//                        the solution's cost into their row, and the reject flag set where a penalty sum is above its cap
+//
+// The reject flags are one array per call, cleared by the host: each post-solve filter (limits.hip, clearance.hip, the gate) only
+// sets the flag of a trajectory it rejects, by the one thread that owns that trajectory, so their order does not show.
 //
 // fp64, no contraction, the host code's statements in the host code's order; atan2 is the correctly rounded one (cr_trig.h),
 // as the oracle's order 2.  Plain vector stores only.
@@ -145,7 +148,7 @@ __global__ void __launch_bounds__(64) plan_select_kernel(PlanSelectArgs A) {
     const size_t t = (size_t)m * R + r, o = (size_t)q * R + r;
     const double c = A.cost[t];
     const int suc = A.success[t], col = A.collision[t];
-    if (suc != 0 && col == 0 && c == c && (idx == INT_MAX || c < best)) {
+    if (suc != 0 && col == 0 && (A.reject == nullptr || A.reject[t] == 0) && c == c && (idx == INT_MAX || c < best)) {
       best = c;
       idx = r;
     }
@@ -193,8 +196,7 @@ __global__ void __launch_bounds__(256) penalty_gate_kernel(PenaltyGateArgs A) {
     for (int k = 0; k < kCostTerms; k++) A.r_terms[row * kCostTerms + k] = tm[k];
   const int rejected = (!(tm[kTermCorridor] <= A.cap_corridor) | !(tm[kTermSurround] <= A.cap_surround) | !(tm[kTermFeas] <= A.cap_feas)) ? 1 : 0;
   if (A.r_rejected) A.r_rejected[row] = rejected;
-  A.flags_out[t] = (A.flags_in[t] != 0 || rejected) ? 1 : 0;
-  if (A.collision) A.collision_rows[row] = A.collision[t];
+  if (A.reject && rejected) A.reject[t] = 1;
 }
 
 hipError_t launch_plan_paths(const int *status, const int *path_len, const int *skip, int n, int max_path, double *paths, int *fe_len,

@@ -21,10 +21,11 @@ struct PlanPackArgs {
   int *mini_t_flag;                      // [Q] set where a restart of the query fails the mini_T test
 };
 
-// plan_select_kernel: per member the cheapest restart that succeeded and does not collide; trajectory t = member * R + restart
+// plan_select_kernel: per member the cheapest restart that succeeded, does not collide and is not rejected; trajectory t = member * R + restart
 struct PlanSelectArgs {
   const double *cost;                 // [n_members * R]
-  const int *success, *collision;     // [n_members * R]
+  const int *success, *collision;     // [n_members * R]; collision is the re-check's own output and is copied to r_collision as it is
+  const int *reject;                  // [n_members * R] or nullptr: what the post-solve filters set (limits.hip, clearance.hip, the penalty gate)
   const int *status, *iters, *evals, *first_sample; // [n_members * R], may be nullptr (then nothing per restart is copied)
   const double *x, *coef, *dt;        // [..][n], [..][n_coef], [..][M]; may be nullptr
   int n, n_coef, M;
@@ -43,15 +44,12 @@ struct PlanSelectArgs {
 // penalty_gate_kernel: one thread per trajectory t = member * R + restart of a group; row = (query, restart)
 struct PenaltyGateArgs {
   const double *terms;    // [n][5] the terms of the cost per trajectory (CostTerm)
-  const int *flags_in;    // [n] what the selection would read without the gate
   const int *members;     // [n / R] query of each member; nullptr: row = t
   int n, R;
   double cap_corridor, cap_surround, cap_feas;
   double *r_terms;        // [rows][5] or nullptr
   int *r_rejected;        // [rows] or nullptr
-  int *flags_out;         // [n] (flags_in != 0) | rejected
-  const int *collision;   // [n] or nullptr: the pure collision flags, copied to collision_rows [rows]
-  int *collision_rows;
+  int *reject;            // [n] or nullptr: set to 1 where rejected, never read or cleared
 };
 
 // the executing table of a planner (capi.cpp: dftpav_planner_install / _adopt): one row per slot, device pointers.  n_seg == 0: empty.

@@ -914,7 +914,7 @@ int dftpav_publish_last_ms(dftpav_planner *p, float *ms);
  *   once) give zero rows, feasible included, with arg -1.  The table is not written.
  * dftpav_planner_set_limit_filter: l == NULL (the default): dftpav_plan_queries and dftpav_replan_tick do exactly what they do
  *   without this call -- the same launches, the same bits.  With limits: per layout group the limits kernel runs after the
- *   collision re-check and before the selection, and the selection sees collision | !feasible in place of collision, so the
+ *   collision re-check and before the selection, and the selection passes over a restart that is not feasible, so the
  *   winner is the cheapest restart that succeeded, does not collide and respects every limit; a query whose every restart is
  *   rejected ends DFTPAV_PLAN_NO_VALID_RESTART (a tick then keeps the slot's old plan).  r_collision / r_first_sample of
  *   dftpav_plan_out stay the pure collision results.  The limits and check_dt are copied.
@@ -950,7 +950,8 @@ int dftpav_limits_last_ms(dftpav_handle *h, float *ms);
  *   (and the limits kernel, when that filter is set), the terms launch runs on the group's solutions and penalty_gate_kernel
  *   (plan.hip) rejects a restart unless  corridor <= caps.corridor && surround <= caps.surround && feasibility <=
  *   caps.feasibility  (a NaN term is rejected; a cap of +inf never rejects a finite term; a cap of 0.0 is legal: no residual
- *   penalty at all).  The selection sees collision | (!feasible) | rejected; a query whose every restart is rejected ends
+ *   penalty at all).  The selection passes over a restart that collides, is not feasible or is rejected here (one reject flag
+ *   per restart, set by whichever filter rejects it; the order of the filters does not show); a query whose every restart is rejected ends
  *   DFTPAV_PLAN_NO_VALID_RESTART (a tick then keeps the slot's old plan).  r_collision / r_first_sample of dftpav_plan_out stay
  *   the pure collision results.  The caps are copied.  A negative or NaN cap is DFTPAV_E_INVALID, and nothing changes.
  * dftpav_planner_last_cost_terms: r_terms [Q][R][5] and r_rejected [Q][R] (query, restart) of the last dftpav_plan_queries call
@@ -997,8 +998,8 @@ int dftpav_debug_penalty_gate(dftpav_handle *h, int n, const double *terms, cons
  * dftpav_planner_set_clearance_filter: min_clearance < 0 (the default): dftpav_plan_queries and dftpav_replan_tick do exactly what
  *   they do without this call -- the same launches, the same bits.  Otherwise: per layout group the clearance kernel runs after
  *   the collision re-check (and after the limits kernel, when that filter is set) and before the terms launch / penalty gate; a
- *   restart is rejected unless clearance >= min_clearance, and the selection sees the OR of collision, the other filters' flags
- *   and this one.  A query whose every restart is rejected ends DFTPAV_PLAN_NO_VALID_RESTART (a tick then keeps the slot's old
+ *   restart is rejected unless clearance >= min_clearance, and the selection passes over a restart that collides or that any
+ *   filter rejected.  A query whose every restart is rejected ends DFTPAV_PLAN_NO_VALID_RESTART (a tick then keeps the slot's old
  *   plan).  r_collision / r_first_sample of dftpav_plan_out stay the pure collision results.  min_clearance = 0.0 is legal and
  *   rejects nothing that does not already collide at the spacing 0.1.  The device buffers of the rows are allocated by this call.
  * dftpav_planner_last_clearance: the rows [Q][R] (query, restart) of the last dftpav_plan_queries call that ran with the filter

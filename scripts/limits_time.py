@@ -4,7 +4,7 @@ beside the time of what it replaces on the host's side: dftpav_batch_sample_stat
 
     python scripts/limits_time.py [--batch 4096] [--check-dt 0.05]
 
-Prints one JSON line.  NOT MEASURED until this has run on an MI355X: no figure from it is quoted anywhere in the repository."""
+Prints one JSON line.  Its figures are quoted in docs/NEXT_ROWS.md 4.17 only."""
 import argparse
 import json
 import os
