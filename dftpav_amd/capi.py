@@ -26,6 +26,7 @@ PLAN_OK, PLAN_NO_PATH, PLAN_TOO_MANY_SEGMENTS, PLAN_LAYOUT_UNSUPPORTED, PLAN_NO_
 SEARCH_REACH_END, SEARCH_NO_PATH = 2, 3
 # columns of dftpav_batch_cost_terms (DFTPAV_TERM_*)
 DIST_FAR = 2147483647   # DFTPAV_DIST_FAR
+FIELD_UNREACHED = 2147483647   # DFTPAV_FIELD_UNREACHED
 TERM_SMOOTH, TERM_TIME, TERM_CORRIDOR, TERM_SURROUND, TERM_FEAS, COST_TERMS = 0, 1, 2, 3, 4, 5
 
 # every symbol include/dftpav_hip.h declares
@@ -54,6 +55,7 @@ EXPORTS = [
     "dftpav_batch_cost_terms", "dftpav_planner_set_penalty_filter", "dftpav_planner_last_cost_terms", "dftpav_debug_penalty_gate",
     "dftpav_grid_distance_field", "dftpav_batch_check_clearance", "dftpav_planner_check_clearance", "dftpav_planner_set_clearance_filter",
     "dftpav_planner_last_clearance", "dftpav_clearance_last_ms",
+    "dftpav_default_goal_field_params", "dftpav_set_search_heuristic", "dftpav_grid_goal_field", "dftpav_goal_field_last_ms",
 ]
 
 
@@ -207,6 +209,21 @@ class ClearanceOut:
 
     def arrays(self):
         return self.a
+
+
+class GoalFieldParams(C.Structure):
+    """dftpav_goal_field_params: the search heuristic of dftpav_set_search_heuristic"""
+    _fields_ = [("enabled", C.c_int), ("inflate_radius", C.c_double), ("scale", C.c_double)]
+
+
+def default_goal_field_params():
+    """dftpav_default_goal_field_params: off, no inflation, scale 1 / sqrt(1.16)"""
+    gp = GoalFieldParams()
+    fn = lib().dftpav_default_goal_field_params
+    fn.argtypes = [C.c_void_p]
+    fn.restype = None
+    fn(C.byref(gp))
+    return gp
 
 
 def default_limits(params=None):
@@ -428,6 +445,39 @@ class Handle:
         fn.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         self._check(fn(self._h, C.byref(a), C.byref(b)), "clearance_last_ms")
         return float(a.value), float(b.value)
+
+    def goal_field(self, goals_xy, inflate_radius=0.0, fetch=True):
+        """dftpav_grid_goal_field: for goals [n][2] (x, y) on the installed map, (field int32 [n][size_y][size_x], n_reached [n]): the
+        cost of the cheapest 8-connected path (5 axial, 7 diagonal) between every cell and the goal's cell round cells within
+        inflate_radius of an occupied one; FIELD_UNREACHED where there is none.  fetch=False: build only, n_reached alone"""
+        xy = np.ascontiguousarray(goals_xy, dtype=np.float64).reshape(-1, 2)
+        n = xy.shape[0]
+        fn = lib().dftpav_grid_goal_field
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p]
+        reached = np.zeros(n, dtype=np.int32)
+        field = np.zeros((n,) + tuple(self._map_shape), dtype=np.int32) if fetch and self._map_shape is not None else None
+        self._check(fn(self._h, xy.ctypes.data_as(C.c_void_p), n, float(inflate_radius),
+                       field.ctypes.data_as(C.c_void_p) if field is not None else None, reached.ctypes.data_as(C.c_void_p)), "grid_goal_field")
+        return (field, reached) if fetch else reached
+
+    def set_search_heuristic(self, enabled=True, inflate_radius=0.0, scale=None):
+        """dftpav_set_search_heuristic: kino_search, Planner.plan and Planner.tick search with max(getHeu, the goal field's cost-to-go)
+        when enabled; off (the default state of a handle) they do what they do without this call.  scale None: 1 / sqrt(1.16)"""
+        gp = default_goal_field_params()
+        gp.enabled, gp.inflate_radius = int(bool(enabled)), float(inflate_radius)
+        if scale is not None:
+            gp.scale = float(scale)
+        fn = lib().dftpav_set_search_heuristic
+        fn.argtypes = [C.c_void_p, C.c_void_p]
+        self._check(fn(self._h, C.byref(gp)), "set_search_heuristic")
+
+    def goal_field_last_ms(self):
+        """dftpav_goal_field_last_ms: device ms of the goal-field builds of the last call that built any"""
+        ms = C.c_float(0.0)
+        fn = lib().dftpav_goal_field_last_ms
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        self._check(fn(self._h, C.byref(ms)), "goal_field_last_ms")
+        return float(ms.value)
 
     def limits_last_ms(self):
         """device time in ms of the last limits kernel of a check_limits call"""

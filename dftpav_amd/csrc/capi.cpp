@@ -261,6 +261,9 @@ extern "C" void dftpav_destroy(dftpav_handle *h) {
   if (h->d_dist) (void)hipFree(h->d_dist);
   for (hipEvent_t e : {h->fev0, h->fev1, h->kev0, h->kev1})
     if (e) (void)hipEventDestroy(e);
+  if (h->d_gf) (void)hipFree(h->d_gf);
+  if (h->d_gf_meta) (void)hipFree(h->d_gf_meta);
+  for (hipEvent_t e : h->gf_ev) (void)hipEventDestroy(e);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }

@@ -28,6 +28,7 @@
 #include "plan_args.h"
 #include "limits_args.h"
 #include "clearance_args.h"
+#include "goalfield_args.h"
 
 namespace dftpav {
 hipError_t launch_solver(const DevBatch &D, const DevBatch *d_dev, int mode, int threads, int grid, SchedArgs sched,
@@ -62,6 +63,8 @@ hipError_t launch_limits_table(const LimitsTableArgs &A, hipStream_t stream);
 hipError_t launch_dist_field(const DistFieldArgs &A, hipStream_t stream);
 hipError_t launch_clearance_batch(const ClearanceBatchArgs &A, hipStream_t stream);
 hipError_t launch_clearance_table(const ClearanceTableArgs &A, hipStream_t stream);
+// goalfield.hip: the cost-to-go fields of n goal cells, one workgroup each
+hipError_t launch_goal_fields(const GoalFieldArgs &A, int n, hipStream_t stream);
 hipError_t launch_corridor_layout(const double *raw, double *out, int B, int Npts, int H, int NptsPad, hipStream_t stream);
 hipError_t launch_adopt(const DevBatch &D, const DevBatch &prev, hipStream_t stream);
 // solver_ref.hip: the same path in the reference's own floating-point order
@@ -114,6 +117,16 @@ struct dftpav_handle {
   bool dist_stale = true;
   hipEvent_t fev0 = nullptr, fev1 = nullptr, kev0 = nullptr, kev1 = nullptr; // around the last field build / the last clearance kernel of a check call
   bool ftimed = false, ktimed = false;
+  // the search heuristic (dftpav_set_search_heuristic) and the workspace of the goal fields (goalfield.hip): nothing of it is
+  // allocated or launched until a call asks for a field
+  dftpav_goal_field_params heu{0, 0.0, 0.0};
+  int *d_gf = nullptr;      // the fields of one turn [goals][cells], then their dirty maps [goals][tiles]
+  size_t gf_ints = 0;
+  int *d_gf_meta = nullptr; // of a whole call: field_of [queries], goal cells [goals][2], n_reached [goals]
+  size_t gf_meta_ints = 0;
+  std::vector<int> gf_host; // the host copy of field_of | goal cells (the source of an asynchronous copy)
+  std::vector<hipEvent_t> gf_ev; // a pair around every turn's build
+  int gf_timed = 0;              // pairs recorded by the last call that built fields
   std::vector<struct dftpav_batch *> batches; // every live batch of this handle (obstacle changes finish their chained stragglers)
   // RCCL communicator of dftpav_comm_create (one rank per handle = per GPU), and the staging block of this rank's records
   void *comm = nullptr;
@@ -241,6 +254,18 @@ struct CachedTable {
   double dt = 0.0;
 };
 
+// The goal fields of one call's queries (the heuristic on): which field each query reads and which cells are built, turn by turn.
+// A turn is one launch of the search over `per_turn` queries (the search's slots, or fewer where the workspace cap holds fewer
+// fields); its distinct goal cells are goals [turn_off[t], turn_off[t + 1]) and field_of is relative to the turn.
+struct GoalFieldPlan {
+  int per_turn = 0, T = 0;
+  std::vector<int> turn_off;
+  size_t n_goals = 0;
+  const int *d_field_of = nullptr, *d_cells = nullptr;
+  int *d_reached = nullptr;
+  double unit = 0.0;
+};
+
 struct dftpav_planner {
   dftpav_handle *h = nullptr;
   int max_queries = 0, R = 0;
@@ -363,6 +388,13 @@ int ensure_dist_field(dftpav_handle *h);
 constexpr double kClearanceVertexRes = 0.1;
 // the map, its field, the vehicle and the tables (d_tab: a validation_table of kClearanceVertexRes on the device) as clearance.hip reads them
 ClearanceCommon clearance_common(const dftpav_handle *h, const double *d_tab, int n_t, int n_v, double check_dt);
+// The goal fields of n goals (xy: their x, y at a stride of `stride` doubles), blocked by inflate_radius, planned in turns of at most
+// `slots` queries: the distance field is ensured, the workspace grown, field_of and the cells uploaded on the handle's stream.
+int goal_field_plan(dftpav_handle *h, const double *xy, int stride, int n, int slots, double inflate_radius, GoalFieldPlan &G);
+// builds turn t's fields on the handle's stream (nothing waits) and returns their base; with S, wires them into a search launch
+int goal_field_turn(dftpav_handle *h, const GoalFieldPlan &G, int t, SearchArgs *S, int **fields);
+// search_setup's slots with the heuristic: a plan for the queries' goals when it is on (G.per_turn replaces U.slots), nothing otherwise
+int search_heuristic_plan(dftpav_handle *h, const double *end_states, int n, SearchSetup &U, GoalFieldPlan &G);
 
 // One allocation for many arrays, measured and carved by the same list: fields(take) names every array in order, take(bytes) is its
 // address -- null while `base` is null, the measuring pass -- and advances by the size rounded up to 256 bytes.  Returns the bytes used.

@@ -251,6 +251,8 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
   if (!start_states || !start_ctrl || !end_states) return DFTPAV_E_INVALID;
   SearchSetup U;
   if (int rc = search_setup(h, &pp->search, Q, U)) return rc;
+  GoalFieldPlan G; // dftpav_set_search_heuristic; off: G.per_turn == 0 and nothing below differs
+  if (int rc = search_heuristic_plan(h, end_states, Q, U, G)) return rc;
   const int R = p->R, MS = pp->max_seg, MP = pp->max_pieces;
   const int MST = (MP - 2) * (fp.traj_res + 1) + 2 * (fp.dense_traj_res + 1); // poses of a segment of max_pieces pieces
   // the two running sums of the collision re-check, tabulated (as dftpav_batch_validate): sample times | outline point spacing
@@ -279,6 +281,8 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
   HIPCHK(h, hipEventRecord(p->ev[0], h->stream));
   for (int q0 = 0; q0 < Q; q0 += U.slots) {
     S.q0 = q0;
+    if (G.per_turn)
+      if (int rc = goal_field_turn(h, G, q0 / U.slots, &S, nullptr)) return rc;
     HIPCHK(h, launch_search(S, std::min(U.slots, Q - q0), h->stream));
   }
   HIPCHK(h, hipEventRecord(p->ev[1], h->stream));

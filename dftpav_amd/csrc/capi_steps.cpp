@@ -311,6 +311,8 @@ extern "C" int dftpav_kino_search(dftpav_handle *h, const dftpav_search_params *
     return DFTPAV_E_INVALID;
   SearchSetup U;
   if (int rc = search_setup(h, sp, n, U)) return rc;
+  GoalFieldPlan G; // dftpav_set_search_heuristic; off: G.per_turn == 0 and nothing below differs
+  if (int rc = search_heuristic_plan(h, end_states, n, U, G)) return rc;
   const size_t nn = (size_t)n, n_nodes = 6 * nn * out->max_nodes, n_paths = 3 * nn * out->max_path;
   double *d_tabs = nullptr, *d_st = nullptr, *d_en = nullptr, *d_nodes = nullptr, *d_paths = nullptr;
   int *d_ints = nullptr;
@@ -332,6 +334,8 @@ extern "C" int dftpav_kino_search(dftpav_handle *h, const dftpav_search_params *
   HIPCHK(h, hipEventRecord(h->cev0, h->stream));
   for (int q0 = 0; q0 < n; q0 += U.slots) {
     U.S.q0 = q0;
+    if (G.per_turn)
+      if (int rc = goal_field_turn(h, G, q0 / U.slots, &U.S, nullptr)) return rc;
     HIPCHK(h, launch_search(U.S, std::min(U.slots, n - q0), h->stream));
   }
   HIPCHK(h, hipEventRecord(h->cev1, h->stream));
@@ -858,4 +862,170 @@ extern "C" int dftpav_solve_batch(dftpav_handle *h, const dftpav_layout *layout,
   if (rc == DFTPAV_OK) rc = dftpav_batch_results(b, x, final_cost, status, success, iters, evals, nullptr, nullptr);
   dftpav_batch_destroy(b);
   return rc;
+}
+
+// ------------------------------------------------- the goal fields of the map and the search heuristic on them (goalfield.hip)
+// The fields of one turn share the handle's workspace: 2 GiB of fields at most (one field, whatever its size, always fits).
+static constexpr size_t kGoalFieldCapBytes = (size_t)2 << 30;
+
+int dftpav::goal_field_plan(dftpav_handle *h, const double *xy, int stride, int n, int slots, double inflate_radius, GoalFieldPlan &G) {
+  if (!h->d_cells) return DFTPAV_E_INVALID; // no map
+  if (!(inflate_radius >= 0.0) || !std::isfinite(inflate_radius) || n < 1 || slots < 1) return DFTPAV_E_INVALID;
+  if (int rc = ensure_dist_field(h)) return rc;
+  const dftpav_grid_map &m = h->map;
+  const size_t cells = (size_t)m.size_x * m.size_y;
+  const int tiles_x = (m.size_x + kGfTileX - 1) / kGfTileX, tiles_y = (m.size_y + kGfTileY - 1) / kGfTileY;
+  const size_t per_field = cells + (size_t)tiles_x * tiles_y;
+  G = GoalFieldPlan{};
+  G.per_turn = (int)std::min<size_t>((size_t)slots, std::max<size_t>(1, kGoalFieldCapBytes / (sizeof(int) * cells)));
+  // d2 <= T blocks; T stays below DFTPAV_DIST_FAR, what a map without an occupied cell holds everywhere
+  const double t = std::floor(inflate_radius * inflate_radius / (m.resolution * m.resolution));
+  G.T = t >= 2147483646.0 ? 2147483646 : (int)t;
+  // per turn: the distinct goal cells inside the grid, in the order of their first query
+  std::vector<int> &H = h->gf_host;
+  H.assign((size_t)n, -1);
+  std::vector<int> cell_list;
+  G.turn_off.assign(1, 0);
+  size_t most = 0;
+  for (int q0 = 0; q0 < n; q0 += G.per_turn) {
+    const size_t base = cell_list.size() / 2;
+    for (int q = q0; q < std::min(n, q0 + G.per_turn); q++) {
+      const double cx = std::round((xy[(size_t)stride * q] - m.origin_x) / m.resolution),
+                   cy = std::round((xy[(size_t)stride * q + 1] - m.origin_y) / m.resolution); // (grid_occupied, footprint.h)
+      if (!(cx >= 0.0 && cx < (double)m.size_x && cy >= 0.0 && cy < (double)m.size_y)) continue; // seeds nothing: no field
+      const int ix = (int)cx, iy = (int)cy;
+      size_t f = base;
+      while (f < cell_list.size() / 2 && (cell_list[2 * f] != ix || cell_list[2 * f + 1] != iy)) f++;
+      if (f == cell_list.size() / 2) {
+        cell_list.push_back(ix);
+        cell_list.push_back(iy);
+      }
+      H[q] = (int)(f - base);
+    }
+    G.turn_off.push_back((int)(cell_list.size() / 2));
+    most = std::max(most, cell_list.size() / 2 - base);
+  }
+  G.n_goals = cell_list.size() / 2;
+  H.insert(H.end(), cell_list.begin(), cell_list.end());
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t want_meta = H.size() + G.n_goals + 1, want_ws = std::max<size_t>(1, most) * per_field;
+  if (h->gf_meta_ints < want_meta || h->gf_ints < want_ws) HIPCHK(h, hipStreamSynchronize(h->stream)); // nothing in flight reads what is freed
+  if (int rc = grow(h, h->d_gf_meta, h->gf_meta_ints, want_meta)) return rc;
+  if (int rc = grow(h, h->d_gf, h->gf_ints, want_ws)) return rc;
+  const size_t turns = G.turn_off.size() - 1;
+  while (h->gf_ev.size() < 2 * turns) {
+    hipEvent_t e = nullptr;
+    HIPCHK(h, hipEventCreate(&e));
+    h->gf_ev.push_back(e);
+  }
+  h->gf_timed = 0;
+  HIPCHK(h, hipMemcpyAsync(h->d_gf_meta, H.data(), sizeof(int) * H.size(), hipMemcpyHostToDevice, h->stream));
+  G.d_field_of = h->d_gf_meta;
+  G.d_cells = h->d_gf_meta + n;
+  G.d_reached = h->d_gf_meta + H.size();
+  return DFTPAV_OK;
+}
+
+int dftpav::goal_field_turn(dftpav_handle *h, const GoalFieldPlan &G, int t, SearchArgs *S, int **fields) {
+  const dftpav_grid_map &m = h->map;
+  const size_t cells = (size_t)m.size_x * m.size_y;
+  const int ng = G.turn_off[t + 1] - G.turn_off[t];
+  GoalFieldArgs A{};
+  A.d2 = h->d_dist;
+  A.size_x = m.size_x;
+  A.size_y = m.size_y;
+  A.T = G.T;
+  A.tiles_x = (m.size_x + kGfTileX - 1) / kGfTileX;
+  A.tiles_y = (m.size_y + kGfTileY - 1) / kGfTileY;
+  A.goal_cell = G.d_cells + 2 * (size_t)G.turn_off[t];
+  A.fields = h->d_gf;
+  A.dirty = h->d_gf + (size_t)ng * cells;
+  A.n_reached = G.d_reached + G.turn_off[t];
+  if (ng > 0) {
+    const size_t tiles = (size_t)A.tiles_x * A.tiles_y;
+    HIPCHK(h, hipEventRecord(h->gf_ev[2 * (size_t)h->gf_timed], h->stream));
+    HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)A.fields, DFTPAV_FIELD_UNREACHED, (size_t)ng * cells, h->stream));
+    HIPCHK(h, hipMemsetAsync(A.dirty, 0, sizeof(int) * (size_t)ng * tiles, h->stream));
+    HIPCHK(h, launch_goal_fields(A, ng, h->stream));
+    HIPCHK(h, hipEventRecord(h->gf_ev[2 * (size_t)h->gf_timed + 1], h->stream));
+    h->gf_timed++;
+  }
+  if (S) {
+    S->fields = h->d_gf; // (queries of a turn without a goal inside the grid have field_of -1 and read nothing)
+    S->field_of = G.d_field_of;
+    S->unit = G.unit;
+  }
+  if (fields) *fields = h->d_gf;
+  return DFTPAV_OK;
+}
+
+int dftpav::search_heuristic_plan(dftpav_handle *h, const double *end_states, int n, SearchSetup &U, GoalFieldPlan &G) {
+  G = GoalFieldPlan{};
+  if (!h->heu.enabled) return DFTPAV_OK;
+  if (int rc = goal_field_plan(h, end_states, 4, n, U.slots, h->heu.inflate_radius, G)) return rc;
+  G.unit = h->heu.scale * h->map.resolution / 5.0;
+  U.slots = G.per_turn;
+  return DFTPAV_OK;
+}
+
+extern "C" void dftpav_default_goal_field_params(dftpav_goal_field_params *gp) {
+  if (!gp) return;
+  gp->enabled = 0;
+  gp->inflate_radius = 0.0;
+  gp->scale = 1.0 / std::sqrt(1.16);
+}
+
+extern "C" int dftpav_set_search_heuristic(dftpav_handle *h, const dftpav_goal_field_params *gp) {
+  if (!h) return DFTPAV_E_INVALID;
+  if (!h->d_cells) return DFTPAV_E_INVALID; // no map
+  if (!gp || !gp->enabled) {
+    h->heu.enabled = 0;
+    return DFTPAV_OK;
+  }
+  if (!(gp->inflate_radius >= 0.0) || !std::isfinite(gp->inflate_radius) || !(gp->scale >= 0.0) || !std::isfinite(gp->scale))
+    return DFTPAV_E_INVALID;
+  if (h->map.size_x > kDistMaxSide || h->map.size_y > kDistMaxSide) return DFTPAV_E_UNSUPPORTED;
+  h->heu = *gp;
+  h->heu.enabled = 1;
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_grid_goal_field(dftpav_handle *h, const double *goals_xy, int n, double inflate_radius, int *field, int *n_reached) {
+  if (!h || n < 0 || (n > 0 && !goals_xy)) return DFTPAV_E_INVALID;
+  if (!h->d_cells) return DFTPAV_E_INVALID; // no map
+  if (!(inflate_radius >= 0.0) || !std::isfinite(inflate_radius)) return DFTPAV_E_INVALID;
+  if (n == 0) return DFTPAV_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  GoalFieldPlan G;
+  if (int rc = goal_field_plan(h, goals_xy, 2, n, n, inflate_radius, G)) return rc;
+  const size_t cells = (size_t)h->map.size_x * h->map.size_y;
+  const std::vector<int> field_of(h->gf_host.begin(), h->gf_host.begin() + n);
+  const int turns = (int)G.turn_off.size() - 1;
+  for (int t = 0; t < turns; t++) {
+    int *F = nullptr;
+    if (int rc = goal_field_turn(h, G, t, nullptr, &F)) return rc;
+    for (int q = t * G.per_turn; field && q < std::min(n, (t + 1) * G.per_turn); q++) {
+      int *dst = field + (size_t)q * cells;
+      if (field_of[q] < 0) std::fill(dst, dst + cells, DFTPAV_FIELD_UNREACHED);
+      else HIPCHK(h, hipMemcpyAsync(dst, F + (size_t)field_of[q] * cells, sizeof(int) * cells, hipMemcpyDeviceToHost, h->stream));
+    }
+  }
+  std::vector<int> reached(G.n_goals + 1, 0);
+  if (n_reached && G.n_goals) HIPCHK(h, hipMemcpyAsync(reached.data(), G.d_reached, sizeof(int) * G.n_goals, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (int q = 0; n_reached && q < n; q++) n_reached[q] = field_of[q] < 0 ? 0 : reached[(size_t)G.turn_off[q / G.per_turn] + field_of[q]];
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_goal_field_last_ms(dftpav_handle *h, float *ms) {
+  if (!h || !ms || h->gf_timed < 1) return DFTPAV_E_INVALID;
+  HIPCHK(h, hipSetDevice(h->device));
+  float sum = 0.0f;
+  for (int k = 0; k < h->gf_timed; k++) {
+    float one = 0.0f;
+    HIPCHK(h, hipEventElapsedTime(&one, h->gf_ev[2 * (size_t)k], h->gf_ev[2 * (size_t)k + 1]));
+    sum += one;
+  }
+  *ms = sum;
+  return DFTPAV_OK;
 }

@@ -123,6 +123,17 @@ class TrajPlannerSteps {
     return ok(dftpav_fit_surround(h_, st.data(), (int)sur_trajs.size(), (int)n));
   }
 
+  // The term the reference left commented out at kino_astar.cpp:247 (lambda_heu_ * getObsHeu): search() below, and every plan
+  // through this handle, then steer by max(getHeu, the cost-to-go round the map's obstacles inflated by inflate_radius metres).
+  // Off by default, and off again with enabled = false.  Needs the map of setObstacleMap.
+  bool setObstacleHeuristic(bool enabled, double inflate_radius = 0.0) {
+    dftpav_goal_field_params gp;
+    dftpav_default_goal_field_params(&gp);
+    gp.enabled = enabled ? 1 : 0;
+    gp.inflate_radius = inflate_radius;
+    return ok(dftpav_set_search_heuristic(h_, &gp));
+  }
+
   // KinoAstar::search as getKinoPath runs it (3D, then the 2D retry) followed by getKinoNode up to SampleTraj, one query:
   // returns the reference's status (DFTPAV_SEARCH_REACH_END / _NO_PATH, or a negative DFTPAV_E_* code); SampleTraj is what
   // getKinoNode above takes

@@ -21,6 +21,13 @@
 // Documented deviation: the reference's wall-clock budget max_seach_time (1.0 s) is a deterministic iteration budget
 // max_iters here; when iter_num_ reaches it at the budget check the reference's time-out branch is taken (:115-132).
 // fp64, no contraction, correctly rounded tan / sin / cos (cr_trig.h): bit-identical to oracle_search/ in order 2.
+//
+// The heuristic.  getHeu (kino_astar.h:221-226) is tie_breaker * |p - goal|.  The kernel is a template on FIELD: without a field
+// (the default) it is the code above and nothing else; with the goal field F_q of the query's goal (goalfield.hip,
+// dftpav_set_search_heuristic) both places that form a heuristic -- the start node and every input -- take
+//   lambda_heu * fmax(tie_breaker * |p - goal|, (double)F_q[cell of p] * unit),
+// the term of kino_astar.cpp:247's commented-out line as a maximum with getHeu; the cell by grid_occupied's rounding, 0 for a point
+// outside the grid or an unreached cell.  The 3D search and its 2D retry read the same field.
 #include <hip/hip_runtime.h>
 
 #include "../../include/dftpav_hip.h"
@@ -141,9 +148,19 @@ __device__ int sr_shot_free(const SearchArgs &A, SShared &S, const double *from,
   return S.hit == 0 ? 1 : 0;
 }
 
+// the goal field's term of the heuristic at (x, y), in metres: 0 outside the grid and where the field did not reach
+__device__ inline double sr_field_heu(const SearchArgs &A, const int *Fq, double x, double y) {
+  const DevGrid &g = A.grid;
+  const double cx = round((x - g.origin_x) / g.resolution), cy = round((y - g.origin_y) / g.resolution);
+  if (!(cx >= 0.0 && cx < (double)g.size_x && cy >= 0.0 && cy < (double)g.size_y)) return 0.0;
+  const int v = Fq[(size_t)(int)cx + (size_t)g.size_x * (size_t)(int)cy];
+  return v == DFTPAV_FIELD_UNREACHED ? 0.0 : (double)v * A.unit;
+}
+
 // one call of KinoAstar::search(start, ctrl, end, use3d) after reset(); result in S.status / shot / budget / iters / used / terminal
+template <bool FIELD>
 __device__ void sr_search(const SearchArgs &A, SShared &S, SearchNode *pool, KinoHeap &heap, int *table, const double *st,
-                          const double *en, bool use3d, int lane) {
+                          const double *en, bool use3d, int lane, const int *Fq) {
   const dftpav_search_params &P = A.sp;
   for (int s = lane; s < A.hcap; s += kSearchThreads) table[s] = -1;
   if (lane == 0) {
@@ -188,7 +205,8 @@ __device__ void sr_search(const SearchArgs &A, SShared &S, SearchNode *pool, Kin
     n0.arc = 0.0;
     n0.singul = singul0;
     const double dx = fabs(st[0] - en[0]), dy = fabs(st[1] - en[1]);
-    n0.f = P.lambda_heu * (P.tie_breaker * sqrt(dx * dx + dy * dy));
+    if constexpr (FIELD) n0.f = P.lambda_heu * fmax(P.tie_breaker * sqrt(dx * dx + dy * dy), Fq ? sr_field_heu(A, Fq, st[0], st[1]) : 0.0);
+    else n0.f = P.lambda_heu * (P.tie_breaker * sqrt(dx * dx + dy * dy));
     n0.state = kInOpen;
     heap.size = 0;
     heap.push(0, n0.f);
@@ -266,7 +284,8 @@ __device__ void sr_search(const SearchArgs &A, SShared &S, SearchNode *pool, Kin
       S.iy[lane] = (int)round((o[1] - A.origin_sy) / P.map_resl);
       S.yid[lane] = sr_yaw_index(A, o[2]);
       const double dx = fabs(o[0] - en[0]), dy = fabs(o[1] - en[1]);
-      S.heu[lane] = P.lambda_heu * (P.tie_breaker * sqrt(dx * dx + dy * dy));
+      if constexpr (FIELD) S.heu[lane] = P.lambda_heu * fmax(P.tie_breaker * sqrt(dx * dx + dy * dy), Fq ? sr_field_heu(A, Fq, o[0], o[1]) : 0.0);
+      else S.heu[lane] = P.lambda_heu * (P.tie_breaker * sqrt(dx * dx + dy * dy));
     }
     if (lane < n_in * P.check_num) {
       const int i = lane / P.check_num, k = lane % P.check_num + 1;
@@ -347,7 +366,7 @@ __device__ void sr_search(const SearchArgs &A, SShared &S, SearchNode *pool, Kin
   __syncthreads();
 }
 
-__global__ void __launch_bounds__(kSearchThreads) search_kernel(SearchArgs A) {
+template <bool FIELD> __global__ void __launch_bounds__(kSearchThreads) search_kernel(SearchArgs A) {
   __shared__ SShared S;
   const int slot = blockIdx.x, q = A.q0 + blockIdx.x, lane = threadIdx.x;
   if (q >= A.n) return;
@@ -362,15 +381,20 @@ __global__ void __launch_bounds__(kSearchThreads) search_kernel(SearchArgs A) {
     st[k] = A.start[4 * (size_t)q + k];
     en[k] = A.end[4 * (size_t)q + k];
   }
+  const int *Fq = nullptr; // the goal field of this query's goal
+  if constexpr (FIELD) {
+    const int f = A.field_of[q];
+    if (f >= 0) Fq = A.fields + (size_t)f * A.grid.size_x * A.grid.size_y;
+  }
   if (lane == 0) S.overflow = 0;
   __syncthreads();
   // getKinoPath, traj_manager.cpp:85-103: the first pass, then (NO_PATH, 3D) the 2D retry
   bool use3d = P.use3d != 0;
-  sr_search(A, S, pool, heap, table, st, en, use3d, lane);
+  sr_search<FIELD>(A, S, pool, heap, table, st, en, use3d, lane, Fq);
   if (!S.overflow && S.status == kNoPath && use3d && P.retry_2d) {
     __syncthreads();
     use3d = false;
-    sr_search(A, S, pool, heap, table, st, en, false, lane);
+    sr_search<FIELD>(A, S, pool, heap, table, st, en, false, lane, Fq);
   }
   __syncthreads();
   const dftpav_search_out &O = A.out;
@@ -502,7 +526,8 @@ __global__ void __launch_bounds__(kSearchThreads) search_kernel(SearchArgs A) {
 }
 
 hipError_t launch_search(const SearchArgs &A, int blocks, hipStream_t stream) {
-  hipLaunchKernelGGL(search_kernel, dim3(blocks), dim3(kSearchThreads), 0, stream, A);
+  if (A.fields) hipLaunchKernelGGL(search_kernel<true>, dim3(blocks), dim3(kSearchThreads), 0, stream, A);
+  else hipLaunchKernelGGL(search_kernel<false>, dim3(blocks), dim3(kSearchThreads), 0, stream, A);
   return hipGetLastError();
 }
 

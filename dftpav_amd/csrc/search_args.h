@@ -35,6 +35,10 @@ struct SearchArgs {
   int *table; // [slots][hcap]
   int hcap;
   dftpav_search_out out; // device pointers
+  // the goal fields of dftpav_set_search_heuristic (goalfield.hip); read only by the kernel launched with a field
+  const int *fields;   // [distinct goals of this launch][size_y][size_x]
+  const int *field_of; // [n] the field of query q, -1: none (a goal outside the grid)
+  double unit;         // metres of heuristic per unit of the field: scale * resolution / 5
 };
 
 } // namespace dftpav

@@ -117,3 +117,56 @@ def arena_plan_queries():
                       [start[0] + 0.6, start[1] + 0.3, start[2], 0.0]])
     goals = np.concatenate([goals, extra])
     return grid, res, origin, np.repeat(start[None], len(goals), 0), goals
+
+
+# ---- maps for the goal field (dftpav_grid_goal_field, tests/test_goalfield_oracle.py and tests/test_gpu_goalfield.py).  Each is
+# (name, grid [size_y][size_x] uint8, resolution, origin); cell (ix, iy) has its centre at origin + resolution * (ix, iy).
+FIELD_RES = 0.25
+FIELD_ORIGIN = (-3.0, 2.0)
+FIELD_EXACT_RADIUS = 0.75       # r^2 / res^2 = 9 exactly: cells at the cell distance 3 from an occupied one have d2 == T
+
+
+def cell_centre(ix, iy, res=FIELD_RES, origin=FIELD_ORIGIN):
+    return (origin[0] + res * ix, origin[1] + res * iy)
+
+
+def field_free(size_x, size_y):
+    """no occupied cell: the distance field is FAR everywhere and nothing is blocked, whatever the radius"""
+    return "free-%dx%d" % (size_x, size_y), np.full((size_y, size_x), 127, dtype=np.uint8), FIELD_RES, FIELD_ORIGIN
+
+
+def field_random(size_x, size_y, density, seed):
+    rng = np.random.default_rng(seed)
+    g = np.where(rng.random((size_y, size_x)) < density, 80, 127).astype(np.uint8)
+    return "random-%dx%d-%g" % (size_x, size_y, density), g, FIELD_RES, FIELD_ORIGIN
+
+
+def field_pocket(size_x=67, size_y=35):
+    """a ring of occupied cells round a free pocket: the pocket stays unreached from outside, and the outside from within"""
+    g = np.full((size_y, size_x), 127, dtype=np.uint8)
+    x0, y0, x1, y1 = size_x // 2 - 4, size_y // 2 - 3, size_x // 2 + 4, size_y // 2 + 3
+    g[y0:y1 + 1, x0:x1 + 1] = 80
+    g[y0 + 1:y1, x0 + 1:x1] = 127
+    return "pocket", g, FIELD_RES, FIELD_ORIGIN
+
+
+def field_corner_pair(size_x=65, size_y=33):
+    """two occupied cells that touch at a corner, across the corner where four tiles of 64 x 32 would meet: the diagonal between
+    them is not taken"""
+    g = np.full((size_y, size_x), 127, dtype=np.uint8)
+    g[31, 63] = 80
+    g[32, 64] = 80
+    return "corner-pair", g, FIELD_RES, FIELD_ORIGIN
+
+
+def field_serpentine(size_x=130, size_y=70):
+    """walls every fourth row, open at alternating ends: the only path from the bottom row to the top runs the full width of every
+    corridor, through every tile of 64 x 32 several times, and the walls stop any other spreading -- a tile is revisited"""
+    g = np.full((size_y, size_x), 127, dtype=np.uint8)
+    for k, y in enumerate(range(3, size_y, 4)):
+        g[y, :] = 80
+        if k % 2 == 0:
+            g[y, size_x - 2:] = 127
+        else:
+            g[y, :2] = 127
+    return "serpentine", g, FIELD_RES, FIELD_ORIGIN

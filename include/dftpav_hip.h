@@ -1017,6 +1017,47 @@ int dftpav_planner_set_clearance_filter(dftpav_planner *p, double min_clearance,
 int dftpav_planner_last_clearance(dftpav_planner *p, const dftpav_clearance_out *out);            /* rows [Q][R] */
 int dftpav_clearance_last_ms(dftpav_handle *h, float *field_ms, float *check_ms);
 
+/* ---- the goal field of the grid map, and the obstacle-aware heuristic of the hybrid A* search -------------------------
+ * The search steers by getHeu (kino_astar.h:221-226), tie_breaker * |p - goal|: the straight line, whatever stands in it.  The
+ * reference carries the other term as a commented-out line, kino_astar.cpp:247,
+ *   tmp_f_score = tmp_g_score + lambda_heu_ * getObsHeu(pro_state.head(2));
+ * and no getObsHeu anywhere.  These calls supply it: the cost-to-go around the obstacles on the grid, as a maximum with getHeu.
+ *
+ * The field.  For a goal at (x, y), whose cell c* is round((p - origin) / resolution) as everywhere here, F[c] is the cost of
+ * the cheapest 8-connected path between c and c* -- an axial step 5, a diagonal step 7 -- int32, integer arithmetic, exact
+ * (goalfield.hip).  A cell is BLOCKED iff d2[c] <= T, d2 the distance field above and T = (int)floor(r * r / (resolution *
+ * resolution)) for the inflation radius r >= 0 in metres (r = 0: exactly the occupied cells; a map without one: nothing).  The
+ * field spreads from c*: a step enters a cell inside the grid that is not blocked, and a diagonal step needs both cells it passes
+ * between not blocked as well (no corner cutting).  c* holds 0 whether it is blocked or not; a goal outside the grid seeds
+ * nothing; a cell never reached holds DFTPAV_FIELD_UNREACHED.  The distance field is built lazily as by the clearance calls, and
+ * a side above 16384 cells is refused likewise (7 * 16384^2 < 2^31).
+ * dftpav_grid_goal_field: the fields of n goals (x, y) into field [n][size_y][size_x] and the number of cells with a value into
+ *   n_reached [n]; either may be NULL.  Goals that share a cell share one build.
+ *
+ * The heuristic.  dftpav_set_search_heuristic keeps its state on the handle.  Off (the default; gp == NULL or enabled == 0):
+ * dftpav_kino_search, dftpav_plan_queries and dftpav_replan_tick launch what they launch without this call and return the same
+ * bits.  On: each of them builds, on the handle's stream in front of its search launches, one field per distinct goal cell of the
+ * call (blocked by inflate_radius), into a workspace the handle owns -- 2 GiB of fields at most, more goals than that are built
+ * and searched in turns -- and the search forms, for the start node and for every expanded input at (x, y),
+ *   h = lambda_heu * fmax(tie_breaker * |p - goal|, (double)F[cell of (x, y)] * unit),   unit = scale * resolution / 5.0,
+ * a point outside the grid or an unreached cell counting as F = 0.  The 3D search and its 2D retry use the same field;
+ * stage_ms[0] of dftpav_planner_info then includes the builds.  The default scale 1 / sqrt(1.16): a 5 / 7 path in the direction
+ * theta costs 5 (cos theta + 0.4 sin theta) per cell of Euclidean length, at most 5 sqrt(1.16), so with this scale the field's
+ * term never exceeds the straight-line distance where nothing is in the way.  Nothing more is claimed about admissibility: the
+ * detour round an obstacle is an 8-connected one, inflation blocks cells the vehicle may cross, and outside the grid the search
+ * treats space as free while the field knows nothing of it.
+ * dftpav_goal_field_last_ms: device time in ms of the field builds (the fills and the kernel) of the last call that built any.
+ * DFTPAV_E_INVALID, and nothing changed: no grid map, a radius that is negative or not finite, a scale that is negative or not
+ * finite, n < 0, goals_xy NULL with n > 0; dftpav_goal_field_last_ms before any build.  dftpav_set_grid_map invalidates nothing
+ * here: the fields are built per call. */
+#define DFTPAV_FIELD_UNREACHED 0x7fffffff
+typedef struct dftpav_goal_field_params { int enabled; double inflate_radius; double scale; } dftpav_goal_field_params;
+void dftpav_default_goal_field_params(dftpav_goal_field_params *gp); /* 0, 0.0, 1 / sqrt(1.16) */
+int dftpav_set_search_heuristic(dftpav_handle *h, const dftpav_goal_field_params *gp); /* NULL or enabled == 0: off (default) */
+int dftpav_grid_goal_field(dftpav_handle *h, const double *goals_xy /*[n][2]*/, int n, double inflate_radius,
+                           int *field /*[n][size_y][size_x] or NULL*/, int *n_reached /*[n] or NULL*/);
+int dftpav_goal_field_last_ms(dftpav_handle *h, float *ms);
+
 /* One-shot convenience == OptimizeTrajectory for B trajectories. */
 int dftpav_solve_batch(dftpav_handle *h, const dftpav_layout *layout, int B,
                        const dftpav_batch_data *d, double *x, double *final_cost,

@@ -20,6 +20,10 @@
 // order 0: libm tan / sin / cos / atan2 / atan, as the reference calls them; order 1: the kernel's correctly rounded
 // functions (cr_trig.h) replayed on the host; order 2: correctly rounded from binary128 (libquadmath) -- the kernel's
 // results must equal order 2's bit for bit.  Everything else is IEEE fp64 in the reference's order, no contraction.
+//
+// oracle_kino_search_field is the same search with an optional goal field per query (dftpav_set_search_heuristic; the fields are
+// the caller's, from oracle_goalfield/): getHeu's two call sites take fmax(getHeu, (double)F[cell] * unit), the term of
+// kino_astar.cpp:247's commented-out getObsHeu line.  Without a field every statement is the one oracle_kino_search runs.
 #include <algorithm>
 #include <array>
 #include <cmath>
@@ -102,6 +106,8 @@ template <int O> struct KinoAstar {
   bool is_shot_succ_ = false;
   bool budget_hit = false;
   double resolution_, inv_yaw_resolution_, origin_[2], map_size_3d_[2], max_steer_, yaw_origin_ = -kPi;
+  const int *field_ = nullptr; // the goal field of this query's goal [sy][sx], or none
+  double unit_ = 0.0;
 
   KinoAstar(const dftpav_search_params &p, const Grid &grid) : P(p), g(grid) { // init, kino_astar.cpp:372-442
     storage.resize(P.allocate_num);
@@ -168,6 +174,19 @@ template <int O> struct KinoAstar {
     double dx = std::abs(x1[0] - x2[0]);
     double dy = std::abs(x1[1] - x2[1]);
     return P.tie_breaker * std::sqrt(dx * dx + dy * dy);
+  }
+  // getHeu, and with a goal field the maximum with the field's term: the cell by occupied()'s rounding, 0 outside the grid and
+  // where the field did not reach
+  double heu(const double *x1, const double *x2) const {
+    const double e = getHeu(x1, x2);
+    if (!field_) return e;
+    const double cx = std::round((x1[0] - g.ox) / g.res), cy = std::round((x1[1] - g.oy) / g.res);
+    double hobs = 0.0;
+    if (cx >= 0.0 && cx < (double)g.sx && cy >= 0.0 && cy < (double)g.sy) {
+      const int v = field_[(size_t)(int)cx + (size_t)g.sx * (size_t)(int)cy];
+      if (v != 0x7fffffff) hobs = (double)v * unit_;
+    }
+    return std::fmax(e, hobs);
   }
   void posToIndex(const double *pt, int *idx) const { // kino_astar.cpp:804-809
     idx[0] = std::round((pt[0] - origin_[0]) / resolution_);
@@ -248,7 +267,7 @@ template <int O> struct KinoAstar {
     cur_node->input[0] = 0.0;
     cur_node->input[1] = 0.0;
     cur_node->singul = getSingularity(start_state[3]);
-    cur_node->f_score = P.lambda_heu * getHeu(cur_node->state, end_state);
+    cur_node->f_score = P.lambda_heu * heu(cur_node->state, end_state);
     cur_node->node_state = IN_OPEN_SET;
     open_set_.push(cur_node);
     use_node_num_ += 1;
@@ -323,7 +342,7 @@ template <int O> struct KinoAstar {
         tmp_g_score += P.traj_steer_penalty * std::fabs(input[0]) * std::fabs(input[1]);
         tmp_g_score += P.traj_steer_change_penalty * std::fabs(input[0] - cur_node->input[0]);
         tmp_g_score += cur_node->g_score;
-        tmp_f_score = tmp_g_score + P.lambda_heu * getHeu(pro_state, end_state);
+        tmp_f_score = tmp_g_score + P.lambda_heu * heu(pro_state, end_state);
         if (pro_node == nullptr) { // :252-275
           pro_node = path_node_pool_[use_node_num_];
           pro_node->index[0] = pro_id[0];
@@ -398,10 +417,14 @@ template <int O> struct KinoAstar {
 
 template <int O>
 void run_queries(const Grid &g, const dftpav_search_params &P, const double *start, const double *end, int n, int nthreads,
-                 const dftpav_search_out &out) {
+                 const dftpav_search_out &out, const int *fields = nullptr, const int *field_of = nullptr, double unit = 0.0) {
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads)
   for (int q = 0; q < n; q++) {
     KinoAstar<O> ka(P, g);
+    if (fields && field_of && field_of[q] >= 0) {
+      ka.field_ = fields + (size_t)field_of[q] * g.sx * g.sy;
+      ka.unit_ = unit;
+    }
     const double *st = start + 4 * (size_t)q, *en = end + 4 * (size_t)q;
     // getKinoPath, traj_manager.cpp:79-103
     ka.reset();
@@ -450,6 +473,18 @@ extern "C" void oracle_kino_search(const unsigned char *grid, int size_x, int si
   if (order == 0) run_queries<0>(g, *sp, start_states, end_states, n, nthreads, *out);
   else if (order == 1) run_queries<1>(g, *sp, start_states, end_states, n, nthreads, *out);
   else run_queries<2>(g, *sp, start_states, end_states, n, nthreads, *out);
+}
+
+// the same with goal fields: fields [k][size_y][size_x], field_of [n] (the field of query q, -1: none), unit; fields == NULL: none
+extern "C" void oracle_kino_search_field(const unsigned char *grid, int size_x, int size_y, double resolution, double origin_x,
+                                         double origin_y, const dftpav_search_params *sp, const double *start_states,
+                                         const double *end_states, int n, int order, int nthreads, const dftpav_search_out *out,
+                                         const int *fields, const int *field_of, double unit) {
+  const Grid g{grid, size_x, size_y, resolution, origin_x, origin_y};
+  if (nthreads < 1) nthreads = 1;
+  if (order == 0) run_queries<0>(g, *sp, start_states, end_states, n, nthreads, *out, fields, field_of, unit);
+  else if (order == 1) run_queries<1>(g, *sp, start_states, end_states, n, nthreads, *out, fields, field_of, unit);
+  else run_queries<2>(g, *sp, start_states, end_states, n, nthreads, *out, fields, field_of, unit);
 }
 
 // stateTransit of one order, for checking every returned node against its parent and input
