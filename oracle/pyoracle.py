@@ -46,7 +46,8 @@ class Result(C.Structure):
 def build(force=False):
     so = os.path.join(_HERE, "libdftpav_oracle.so")
     srcs = [os.path.join(_HERE, f) for f in ("dftpav_oracle.c", "dftpav_oracle_dev.cpp", "dftpav_oracle.h",
-                                             "oracle_internal.h")]
+                                             "oracle_internal.h", "validate_oracle.cpp", "states_oracle.cpp",
+                                             "../oracle_shared/ref_objects.h")]
     srcs.append(os.path.join(_HERE, "..", "dftpav_amd", "csrc", "traj_math.h"))
     if force or not os.path.exists(so) or any(os.path.getmtime(so) < os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["make", "-C", _HERE, "-s"])

@@ -6,15 +6,9 @@
 // time", 2000) in integer arithmetic, the column phase FIRST and the lower envelope of parabolas along the rows second -- the
 // kernels scan the rows first and then walk the columns outward, so neither the axis order nor the second phase is theirs.
 //
-// The clearance.  The reference's objects, restated from the cited lines:
-//   TrajPlannerServer::CheckReplan, the sampling loop   traj_planner/src/traj_server_ros.cpp:385-387
-//   Piece::getPos / getdSigma                           plan_utils/poly_traj_utils.hpp:77-87, 179-192
-//   Trajectory::getTotalDuration / locatePieceIdx       poly_traj_utils.hpp:425-434, 510-528
-//   Trajectory::getPos / getAngle, Piece::getAngle      poly_traj_utils.hpp:554-558, 626-630, 237-244
-//   TrajContainer::addSingulTraj, the chained segments  plan_utils/traj_container.hpp:58-73
-//   SemanticMapManager::CheckCollisionUsingPosAndYaw    semantic_map_manager.cc:639-662
-//   ShapeUtils::GetDenseVerticesOfOrientedBoundingBox   common/src/common/basics/shapes.cc:110-149 (res = 0.1, shapes.h:200-201)
-//   GridMapND::GetCoordUsingGlobalPosition              common/src/common/basics/semantics.cc:169-179, 214-221
+// The clearance.  The reference's objects -- Piece, Trajectory (getPos, getAngle), the container of chained segments, the grid's cell
+// rule and the dense outline CheckCollisionUsingPosAndYaw walks -- are oracle_shared/ref_objects.h's, cited there (that header shares none
+// with the kernels either); the sampling loop is TrajPlannerServer::CheckReplan's, traj_planner/src/traj_server_ros.cpp:385-387.
 // The reference asks each vertex "is this cell OCCUPIED"; here the same vertex, in the same cell, reads the field instead, and the
 // running minimum over vertices and samples is kept in sample order, replaced only on `<`.  A vertex outside the grid is skipped.
 // Nothing is tabulated, strided or reduced.  order 0: the host's libm, as the reference calls it; order 2: correctly rounded from
@@ -26,7 +20,7 @@
 #include <limits>
 #include <vector>
 
-#include "../oracle/step_trig.h"
+#include "../oracle_shared/ref_objects.h"
 
 namespace {
 
@@ -95,115 +89,17 @@ void field_meijster(const unsigned char *cells, int sx, int sy, int *d2) {
 }
 
 // ---------------------------------------------------------------- the clearance
-using step_trig::Trig;
+using namespace ref_objects;
 
-struct Vec2 {
-  double x, y;
-};
-
-struct Piece { // plan_utils::Piece.  c[k][0] / c[k][1]: the coefficient of t^k of x / y (the layout of dftpav_batch_coeffs)
-  double duration;
-  const double *c;
-  Vec2 getPos(double t) const { // :77-87
-    Vec2 pos{0.0, 0.0};
-    double tn = 1.0;
-    for (int i = 0; i <= 5; i++) {
-      pos.x += tn * c[2 * i];
-      pos.y += tn * c[2 * i + 1];
-      tn *= t;
-    }
-    return pos;
-  }
-  Vec2 getdSigma(double t) const { // :179-192
-    Vec2 vel{0.0, 0.0};
-    double tn = 1.0;
-    int n = 1;
-    for (int i = 1; i <= 5; i++) {
-      vel.x += n * tn * c[2 * i];
-      vel.y += n * tn * c[2 * i + 1];
-      tn *= t;
-      n++;
-    }
-    return vel;
-  }
-};
-
-struct Trajectory {
-  std::vector<Piece> pieces;
-  int singul;
-  const Trig *T;
-  double getTotalDuration() const { // :425-434
-    double totalDuration = 0.0;
-    for (size_t i = 0; i < pieces.size(); i++) totalDuration += pieces[i].duration;
-    return totalDuration;
-  }
-  int locatePieceIdx(double &t) const { // :510-528
-    const int N = (int)pieces.size();
-    int idx;
-    double dur;
-    for (idx = 0; idx < N && t > (dur = pieces[idx].duration); idx++) t -= dur;
-    if (idx == N) {
-      idx--;
-      t += pieces[idx].duration;
-    }
-    return idx;
-  }
-  Vec2 getPos(double t) const { // :554-558 (t by value: locatePieceIdx rewrites the copy)
-    int pieceIdx = locatePieceIdx(t);
-    return pieces[pieceIdx].getPos(t);
-  }
-  double getAngle(double t) const { // :626-630, with Piece::getAngle (:237-244) written out
-    int pieceIdx = locatePieceIdx(t);
-    Vec2 dsigma = pieces[pieceIdx].getdSigma(t);
-    return T->atan2(singul * dsigma.y, singul * dsigma.x);
-  }
-};
-
-struct LocalTrajData { // traj_container.hpp:28-38
-  Trajectory traj;
-  double duration, start_time, end_time;
-};
-
-struct GridMap {
-  const unsigned char *cells;
-  const int *d2;
-  int sx, sy;
-  double res, ox, oy;
-};
-
-// GetDenseVerticesOfOrientedBoundingBox, shapes.cc:110-149: the dense points of the four edges, then the four corners
-void dense_vertices(double x, double y, double angle, double W, double L, double res, const Trig &T, std::vector<Vec2> *vertices) {
-  const double cs = T.cos(angle), sn = T.sin(angle);
-  Vec2 corner[4];
-  corner[0] = Vec2{x + 0.5 * L * cs + 0.5 * W * sn, y + 0.5 * L * sn - 0.5 * W * cs};
-  corner[1] = Vec2{x + 0.5 * L * cs - 0.5 * W * sn, y + 0.5 * L * sn + 0.5 * W * cs};
-  corner[2] = Vec2{x - 0.5 * L * cs - 0.5 * W * sn, y - 0.5 * L * sn + 0.5 * W * cs};
-  corner[3] = Vec2{x - 0.5 * L * cs + 0.5 * W * sn, y - 0.5 * L * sn - 0.5 * W * cs};
-  vertices->clear();
-  for (int e = 0; e < 4; e++) {
-    const Vec2 a = corner[e], b = corner[(e + 1) % 4];
-    const double dx = b.x - a.x, dy = b.y - a.y;
-    const double norm = std::sqrt(dx * dx + dy * dy);
-    for (double dl = res; dl < norm; dl += res) {
-      const double f = dl / norm;
-      vertices->push_back(Vec2{f * dx + a.x, f * dy + a.y});
-    }
-  }
-  for (int e = 0; e < 4; e++) vertices->push_back(corner[e]);
-}
-
-// CheckCollisionUsingPosAndYaw's walk over the vertices (semantic_map_manager.cc:639-662), reading the field: the smallest d2 of
-// the vertices inside the grid, FAR if none is
-int pose_min_d2(const GridMap &g, Vec2 pos, double yaw, double W, double L, double dcr, double vres, const Trig &T, std::vector<Vec2> *scratch) {
-  const double cx = pos.x + dcr * T.cos(yaw), cy = pos.y + dcr * T.sin(yaw); // the obb centre, :645-646
-  dense_vertices(cx, cy, yaw, W, L, vres, T, scratch);
+// CheckCollisionUsingPosAndYaw's walk over the vertices (semantic_map_manager.cc:639-662), reading the field at the cell the
+// reference would probe: the smallest d2 of the vertices inside the grid, FAR if none is
+int pose_min_d2(const Grid &g, const int *d2, Vec2 pos, double yaw, const Vehicle &vp, double vres, const Trig &T) {
   int m = FAR;
-  for (const Vec2 &v : *scratch) {
-    const double gx = std::round((v.x - g.ox) / g.res), gy = std::round((v.y - g.oy) / g.res);
-    if (!(gx >= 0.0 && gx < (double)g.sx && gy >= 0.0 && gy < (double)g.sy)) continue;
-    const int d = g.d2[(int)gx + (size_t)g.sx * (int)gy];
-    if (d < m) m = d;
-  }
+  visit_outline(pos.x, pos.y, yaw, vp, vres, T, [&](Vec2 v) {
+    const ptrdiff_t i = g.cell_index(v.x, v.y);
+    if (i >= 0 && d2[i] < m) m = d2[i];
+    return false;
+  });
   return m;
 }
 
@@ -221,32 +117,19 @@ extern "C" void oracle_clearance(const unsigned char *cells, int size_x, int siz
   const Trig T{order};
   std::vector<int> field((size_t)size_x * size_y);
   field_meijster(cells, size_x, size_y, field.data());
-  const GridMap g{cells, field.data(), size_x, size_y, resolution, origin_x, origin_y};
-  std::vector<Vec2> vertices;
+  const Grid g{cells, size_x, size_y, resolution, origin_x, origin_y};
+  const Vehicle vp{veh[0], veh[1], veh[2]};
   for (int s = 0; s < n; s++) {
-    std::vector<LocalTrajData> executing_traj_; // the container as RunMINCOParking fills it (traj_manager.cpp:618-625)
-    double world = 0.0;
-    int p0 = 0;
-    for (int i = 0; i < n_seg[s]; i++) {
-      LocalTrajData d;
-      d.traj.singul = singul[s * max_seg + i];
-      d.traj.T = &T;
-      for (int k = 0; k < piece_nums[s * max_seg + i]; k++)
-        d.traj.pieces.push_back(Piece{coeff_dt[s * max_seg + i], coeffs + ((size_t)s * row_pieces + p0 + k) * 12});
-      p0 += piece_nums[s * max_seg + i];
-      d.duration = d.traj.getTotalDuration();
-      d.start_time = world;
-      d.end_time = d.start_time + d.duration;
-      world = d.end_time;
-      executing_traj_.push_back(d);
-    }
+    // the container as RunMINCOParking fills it (traj_manager.cpp:618-625)
+    const std::vector<LocalTrajData> executing_traj_ = fill_container(n_seg[s], singul + (size_t)s * max_seg, piece_nums + (size_t)s * max_seg,
+                                                                      coeff_dt + (size_t)s * max_seg, coeffs + (size_t)s * row_pieces * 12, 0.0);
     int best = FAR, where = -1, k = 0;
     for (size_t i = 0; i < executing_traj_.size(); i++) {                           // traj_server_ros.cpp:385
       for (double t = 0.0; t < executing_traj_.at(i).duration; t += check_dt) {     // :386-387
         const Trajectory &traj = executing_traj_.at(i).traj;
         const Vec2 pos = traj.getPos(t);
-        const double yaw = traj.getAngle(t);
-        const int d = pose_min_d2(g, pos, yaw, veh[0], veh[1], veh[2], vertex_res, T, &vertices);
+        const double yaw = traj.getAngle(t, T);
+        const int d = pose_min_d2(g, field.data(), pos, yaw, vp, vertex_res, T);
         if (d < best) {
           best = d;
           where = k;

@@ -3,39 +3,29 @@
 Only tests/ and scripts/ import this."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SO = os.path.join(_HERE, "libclearance_oracle.so")
-_LIB = None
-_SRCS = ("clearance_oracle.cpp", "../oracle/step_trig.h", "../dftpav_amd/csrc/cr_trig.h")
+from oracle_shared.loader import Loader
+
 
 FAR = 2147483647
 FIELDS = ("min_d2", "arg", "clearance")
 VEH = (1.90, 4.88, 1.015)     # veh_width, veh_length, veh_d_cr of the default parameters
 
 
-def build(force=False):
-    if force or not os.path.exists(_SO) or any(os.path.getmtime(_SO) < os.path.getmtime(os.path.join(_HERE, s)) for s in _SRCS):
-        subprocess.check_call(["make", "-C", _HERE, "-s"])
-    return _SO
+def _declare(L):
+    for f in (L.oracle_field, L.oracle_field_brute):
+        f.restype = None
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.oracle_clearance.restype = None
+    L.oracle_clearance.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_double] * 3 + [C.c_int] * 3 + [C.c_void_p] * 5 + \
+        [C.c_double, C.c_void_p, C.c_double, C.c_int] + [C.c_void_p] * 4
 
 
-def lib():
-    global _LIB
-    if _LIB is None:
-        build()
-        L = C.CDLL(_SO)
-        for f in (L.oracle_field, L.oracle_field_brute):
-            f.restype = None
-            f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-        L.oracle_clearance.restype = None
-        L.oracle_clearance.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_double] * 3 + [C.c_int] * 3 + [C.c_void_p] * 5 + \
-            [C.c_double, C.c_void_p, C.c_double, C.c_int] + [C.c_void_p] * 4
-        _LIB = L
-    return _LIB
+_load = Loader(os.path.dirname(os.path.abspath(__file__)), "libclearance_oracle.so",
+               ("clearance_oracle.cpp", "../oracle_shared/ref_objects.h", "../oracle/step_trig.h", "../dftpav_amd/csrc/cr_trig.h"), _declare)
+build, lib = _load.build, _load.lib
 
 
 def _field(fn, grid):

@@ -4,38 +4,28 @@ Only tests/ and scripts/ import this."""
 import ctypes as C
 import math
 import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SO = os.path.join(_HERE, "libgoalfield_oracle.so")
-_LIB = None
-_SRCS = ("goalfield_oracle.cpp",)
+from oracle_shared.loader import Loader
+
 
 UNREACHED = 2147483647            # DFTPAV_FIELD_UNREACHED
 AXIAL, DIAGONAL = 5, 7
 DEFAULT_SCALE = 1.0 / math.sqrt(1.16)
 
 
-def build(force=False):
-    if force or not os.path.exists(_SO) or any(os.path.getmtime(_SO) < os.path.getmtime(os.path.join(_HERE, s)) for s in _SRCS):
-        subprocess.check_call(["make", "-C", _HERE, "-s"])
-    return _SO
+def _declare(L):
+    L.oracle_goal_threshold.restype = C.c_int
+    L.oracle_goal_threshold.argtypes = [C.c_double, C.c_double]
+    L.oracle_goal_field.restype = None
+    L.oracle_goal_field.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_double,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]
 
 
-def lib():
-    global _LIB
-    if _LIB is None:
-        build()
-        L = C.CDLL(_SO)
-        L.oracle_goal_threshold.restype = C.c_int
-        L.oracle_goal_threshold.argtypes = [C.c_double, C.c_double]
-        L.oracle_goal_field.restype = None
-        L.oracle_goal_field.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int, C.c_double,
-                                        C.c_void_p, C.c_void_p, C.c_void_p]
-        _LIB = L
-    return _LIB
+_load = Loader(os.path.dirname(os.path.abspath(__file__)), "libgoalfield_oracle.so",
+               ("goalfield_oracle.cpp",), _declare)
+build, lib = _load.build, _load.lib
 
 
 def threshold(inflate_radius, resolution):

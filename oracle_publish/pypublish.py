@@ -3,31 +3,20 @@
 Only tests/ and scripts/ import this."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SO = os.path.join(_HERE, "libpublish_oracle.so")
-_LIB = None
-_SRCS = ("publish_oracle.cpp", "../oracle/step_trig.h", "../dftpav_amd/csrc/cr_trig.h")
+from oracle_shared.loader import Loader
 
 
-def build(force=False):
-    if force or not os.path.exists(_SO) or any(os.path.getmtime(_SO) < os.path.getmtime(os.path.join(_HERE, s)) for s in _SRCS):
-        subprocess.check_call(["make", "-C", _HERE, "-s"])
-    return _SO
+def _declare(L):
+    L.oracle_publish.restype = None
+    L.oracle_publish.argtypes = [C.c_int] * 3 + [C.c_void_p] * 9 + [C.c_int, C.c_void_p, C.c_double, C.c_int] + [C.c_void_p] * 5
 
 
-def lib():
-    global _LIB
-    if _LIB is None:
-        build()
-        L = C.CDLL(_SO)
-        L.oracle_publish.restype = None
-        L.oracle_publish.argtypes = [C.c_int] * 3 + [C.c_void_p] * 9 + [C.c_int, C.c_void_p, C.c_double, C.c_int] + [C.c_void_p] * 5
-        _LIB = L
-    return _LIB
+_load = Loader(os.path.dirname(os.path.abspath(__file__)), "libpublish_oracle.so",
+               ("publish_oracle.cpp", "../oracle_shared/ref_objects.h", "../oracle/step_trig.h", "../dftpav_amd/csrc/cr_trig.h"), _declare)
+build, lib = _load.build, _load.lib
 
 
 class Table:

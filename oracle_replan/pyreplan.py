@@ -3,35 +3,25 @@
 Only tests/ and scripts/ import this."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SO = os.path.join(_HERE, "libreplan_oracle.so")
-_LIB = None
-_SRCS = ("replan_oracle.cpp", "../oracle/step_trig.h", "../dftpav_amd/csrc/cr_trig.h")
+from oracle_shared.loader import Loader
+
 
 INTS = ("occupied", "complete", "exe_index", "is_close_turnpoint", "is_near", "target_moved", "collision", "first_sample", "replan")
 
 
-def build(force=False):
-    if force or not os.path.exists(_SO) or any(os.path.getmtime(_SO) < os.path.getmtime(os.path.join(_HERE, s)) for s in _SRCS):
-        subprocess.check_call(["make", "-C", _HERE, "-s"])
-    return _SO
+def _declare(L):
+    L.oracle_replan_check.restype = None
+    L.oracle_replan_check.argtypes = ([C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int]
+                                      + [C.c_void_p] * 9 + [C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+                                      + [C.c_double] * 6 + [C.c_int] + [C.c_void_p] * 7)
 
 
-def lib():
-    global _LIB
-    if _LIB is None:
-        build()
-        L = C.CDLL(_SO)
-        L.oracle_replan_check.restype = None
-        L.oracle_replan_check.argtypes = ([C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int]
-                                          + [C.c_void_p] * 9 + [C.c_double, C.c_double, C.c_void_p, C.c_void_p]
-                                          + [C.c_double] * 6 + [C.c_int] + [C.c_void_p] * 7)
-        _LIB = L
-    return _LIB
+_load = Loader(os.path.dirname(os.path.abspath(__file__)), "libreplan_oracle.so",
+               ("replan_oracle.cpp", "../oracle_shared/ref_objects.h", "../oracle/step_trig.h", "../dftpav_amd/csrc/cr_trig.h"), _declare)
+build, lib = _load.build, _load.lib
 
 
 class Table:

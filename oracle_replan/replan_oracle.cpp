@@ -5,15 +5,10 @@
 //   TrajPlannerServer::PublishData, exe_traj_index_    traj_server_ros.cpp:248-252
 //   TrajPlannerServer::CheckReplan                     traj_server_ros.cpp:359-402
 //   TrajPlannerServer::Replan (stamp, pidx, GetState)  traj_server_ros.cpp:414, 445-461
-//   TrajPlannerServer::FilterSingularityState          traj_server_ros.cpp:335-356
-//   normalize_angle, kPi, kBigEPS                      common/src/common/math/calculations.cc:18-23, basics.h:76
-//   Trajectory::GetState / getPos / getAngle / getTotalDuration / locatePieceIdx   plan_utils/poly_traj_utils.hpp:378-406, 425-434, 510-528
-//   Piece::getPos / getdSigma / getddSigma / getAngle / getStateExpPos             poly_traj_utils.hpp:77-87, 179-211, 237-244, 303-340
-//   TrajContainer::addSingulTraj, the chain of times   plan_utils/traj_container.hpp:58-73, traj_manager.cpp:618-625
 //   TrajPlanner::getKinoPath, start state and control  traj_manager.cpp:74-75
-//   SemanticMapManager::CheckCollisionUsingPosAndYaw   semantic_map_manager.cc:639-662
-//   ShapeUtils::GetDenseVerticesOfOrientedBoundingBox  common/src/common/basics/shapes.cc:110-149
-//   GridMapND::CheckIfEqualUsingGlobalPosition         common/src/common/basics/semantics.cc:169-179, 214-221
+//
+// The objects it walks -- Piece, Trajectory (GetState), the container and its chain of times, the grid probe, the dense outline of
+// CheckCollisionUsingPosAndYaw, normalize_angle and the rule of FilterSingularityState -- are oracle_shared/ref_objects.h's, cited there.
 //
 // The program is laid out as the reference's objects are: a Piece (duration, six coefficient columns, direction), a Trajectory
 // of pieces, a container entry per gear segment (duration, start_time, end_time), a server holding the executing container, its
@@ -24,185 +19,11 @@
 #include <cstddef>
 #include <vector>
 
-#include "../oracle/step_trig.h"
+#include "../oracle_shared/ref_objects.h"
 
 namespace {
 
-using step_trig::Trig;
-
-constexpr double kPi = 3.14159265358979323846; // acos(-1.0), basics.h
-constexpr double kBigEPS = 1e-1;               // basics.h:76
-
-struct Vec2 {
-  double x, y;
-};
-
-// plan_utils::Piece: coefficient of t^k in column k of `c` (c[k][0] x, c[k][1] y) -- the layout dftpav_batch_coeffs returns;
-// the reference keeps the columns in the opposite order and walks them from the constant term upwards, as here
-struct Piece {
-  double duration;
-  const double *c; // [6][2]
-  int singul;
-  Vec2 getPos(double t) const { // poly_traj_utils.hpp:77-87
-    Vec2 pos{0.0, 0.0};
-    double tn = 1.0;
-    for (int i = 0; i <= 5; i++) {
-      pos.x += tn * c[2 * i];
-      pos.y += tn * c[2 * i + 1];
-      tn *= t;
-    }
-    return pos;
-  }
-  Vec2 getdSigma(double t) const { // :179-192
-    Vec2 d{0.0, 0.0};
-    double tn = 1.0;
-    int n = 1;
-    for (int i = 1; i <= 5; i++) {
-      d.x += n * tn * c[2 * i];
-      d.y += n * tn * c[2 * i + 1];
-      tn *= t;
-      n++;
-    }
-    return d;
-  }
-  Vec2 getddSigma(double t) const { // :194-211
-    Vec2 dd{0.0, 0.0};
-    double tn = 1.0;
-    int m = 1, n = 2;
-    for (int i = 2; i <= 5; i++) {
-      dd.x += m * n * tn * c[2 * i];
-      dd.y += m * n * tn * c[2 * i + 1];
-      tn *= t;
-      m++;
-      n++;
-    }
-    return dd;
-  }
-  double getAngle(double t, const Trig &T) const { // :237-244
-    const Vec2 d = getdSigma(t);
-    return T.atan2(singul * d.y, singul * d.x);
-  }
-};
-
-struct State { // common::State, the fields the server reads
-  double time_stamp, x, y, angle, curvature, velocity, acceleration, steer;
-};
-
-struct Trajectory {
-  std::vector<Piece> pieces;
-  double getTotalDuration() const { // :425-434
-    double total = 0.0;
-    for (size_t i = 0; i < pieces.size(); i++) total += pieces[i].duration;
-    return total;
-  }
-  int locatePieceIdx(double &t) const { // :510-528
-    const int N = (int)pieces.size();
-    int idx;
-    double dur;
-    for (idx = 0; idx < N && t > (dur = pieces[idx].duration); idx++) t -= dur;
-    if (idx == N) {
-      idx--;
-      t += pieces[idx].duration;
-    }
-    return idx;
-  }
-  Vec2 getPos(double t) const {
-    const int idx = locatePieceIdx(t);
-    return pieces[idx].getPos(t);
-  }
-  double getAngle(double t, const Trig &T) const {
-    const int idx = locatePieceIdx(t);
-    return pieces[idx].getAngle(t, T);
-  }
-  void GetState(double t, State *state, double wheel_base, const Trig &T) const { // :378-406 with getStateExpPos :303-340
-    double inner_t = t;
-    if (inner_t > getTotalDuration()) inner_t = getTotalDuration();
-    const int idx = locatePieceIdx(inner_t);
-    const Piece &p = pieces[idx];
-    const Vec2 pos = p.getPos(inner_t);
-    const Vec2 ds = p.getdSigma(inner_t), dds = p.getddSigma(inner_t);
-    const double theta = T.atan2(p.singul * ds.y, p.singul * ds.x);
-    const double vel = p.singul * std::sqrt(ds.x * ds.x + ds.y * ds.y);
-    double curv, acc, phi;
-    if (std::fabs(vel) < 1e-6) {
-      curv = 0.0;
-      acc = 0.0;
-      phi = 0.0;
-    } else {
-      curv = (ds.x * dds.y - ds.y * dds.x) / T.cube(vel);
-      acc = (ds.x * dds.x + ds.y * dds.y) / vel;
-      phi = T.atan(wheel_base * curv);
-    }
-    state->x = pos.x;
-    state->y = pos.y;
-    state->angle = theta;
-    state->curvature = curv;
-    state->velocity = vel;
-    state->acceleration = acc;
-    state->steer = phi;
-  }
-};
-
-struct LocalTrajData { // traj_container.hpp:28-38
-  Trajectory traj;
-  double duration, start_time, end_time;
-};
-
-struct Map {
-  const unsigned char *data;
-  int sx, sy;
-  double res, ox, oy;
-  bool occupied(double x, double y) const { // semantics.cc:169-179, 214-221: round to the cell, outside is not occupied
-    const double cx = std::round((x - ox) / res), cy = std::round((y - oy) / res);
-    if (!(cx >= 0.0 && cx < (double)sx && cy >= 0.0 && cy < (double)sy)) return false;
-    return data[(int)cx + sx * (int)cy] == 80;
-  }
-};
-
-struct Vehicle {
-  double width, length, d_cr, wheel_base;
-};
-
-// CheckCollisionUsingPosAndYaw: the dense outline of the oriented box (edges first, then the corners), first hit returns
-bool collides(const Map &map, const Vehicle &vp, double px, double py, double yaw, double res, const Trig &T) {
-  const double cos_theta = T.cos(yaw), sin_theta = T.sin(yaw);
-  const double x = px + vp.d_cr * cos_theta, y = py + vp.d_cr * sin_theta; // semantic_map_manager.cc:645-646
-  const double L = vp.length, W = vp.width;
-  const Vec2 corner[4] = {{x + 0.5 * L * cos_theta + 0.5 * W * sin_theta, y + 0.5 * L * sin_theta - 0.5 * W * cos_theta},
-                          {x + 0.5 * L * cos_theta - 0.5 * W * sin_theta, y + 0.5 * L * sin_theta + 0.5 * W * cos_theta},
-                          {x - 0.5 * L * cos_theta - 0.5 * W * sin_theta, y - 0.5 * L * sin_theta + 0.5 * W * cos_theta},
-                          {x - 0.5 * L * cos_theta + 0.5 * W * sin_theta, y - 0.5 * L * sin_theta - 0.5 * W * cos_theta}};
-  for (int e = 0; e < 4; e++) { // shapes.cc:128-143
-    const Vec2 a = corner[e], b = corner[(e + 1) % 4];
-    const double dx = b.x - a.x, dy = b.y - a.y;
-    const double len = std::sqrt(dx * dx + dy * dy);
-    for (double dl = res; dl < len; dl += res) {
-      const double f = dl / len;
-      if (map.occupied(f * dx + a.x, f * dy + a.y)) return true;
-    }
-  }
-  for (int e = 0; e < 4; e++)
-    if (map.occupied(corner[e].x, corner[e].y)) return true;
-  return false;
-}
-
-inline double normalize_angle(double theta) { // calculations.cc:18-23
-  double tmp = theta;
-  tmp -= (double)((theta >= kPi) * 2) * kPi;
-  tmp += (double)((theta < -kPi) * 2) * kPi;
-  return tmp;
-}
-
-// FilterSingularityState against hist.back() = (hist_stamp, hist_angle)
-void filter_singularity(double hist_stamp, double hist_angle, State *s, const Trig &T) {
-  const double duration = s->time_stamp - hist_stamp;
-  const double max_steer = kPi / 4.0; // M_PI / 4.0: the same double
-  const double singular_velocity = kBigEPS;
-  const double max_orientation_rate = T.tan(max_steer) / 2.85 * singular_velocity;
-  const double max_orientation_change = max_orientation_rate * duration;
-  if (std::fabs(s->velocity) < singular_velocity && std::fabs(normalize_angle(s->angle - hist_angle)) > max_orientation_change)
-    s->angle = hist_angle;
-}
+using namespace ref_objects;
 
 enum { kOccupied = 0, kComplete, kExeIndex, kCloseTurn, kNear, kTargetMoved, kCollision, kFirstSample, kReplan, kInts };
 
@@ -221,8 +42,8 @@ extern "C" void oracle_replan_check(const unsigned char *grid, int size_x, int s
                                     double check_dt, double vertex_res, int order, int *o_int, double *desired, double *start_state,
                                     double *start_ctrl, double *times, int *pidx_out, double *t_local) {
   const Trig T{order};
-  const Map map{grid, size_x, size_y, resolution, origin_x, origin_y};
-  const Vehicle vp{veh_width, veh_length, veh_dcr, wheel_base};
+  const Grid map{grid, size_x, size_y, resolution, origin_x, origin_y};
+  const Vehicle vp{veh_width, veh_length, veh_dcr};
   for (int s = 0; s < slots; s++) {
     int *o[kInts];
     for (int k = 0; k < kInts; k++) {
@@ -236,15 +57,15 @@ extern "C" void oracle_replan_check(const unsigned char *grid, int size_x, int s
     for (int k = 0; k < 3 * max_seg; k++) times[(size_t)s * 3 * max_seg + k] = 0.0;
     pidx_out[s] = -1;
     t_local[s] = 0.0;
-    State desired_state{};
+    State desired_state;
     bool have_desired = false;
     desired_state.time_stamp = t_now + budget; // traj_server_ros.cpp:414
     if (n_seg[s] == 0) {
       // executing_traj_ == nullptr: CheckReplan returns true (:361); Replan plans from the ego state (:411-416)
       if (ego) {
         const double *e = ego + 6 * s;
-        desired_state.x = e[0];
-        desired_state.y = e[1];
+        desired_state.vec_position.x = e[0];
+        desired_state.vec_position.y = e[1];
         desired_state.angle = e[2];
         desired_state.velocity = e[3];
         desired_state.steer = e[4];
@@ -256,24 +77,13 @@ extern "C" void oracle_replan_check(const unsigned char *grid, int size_x, int s
     } else {
       *o[kOccupied] = 1;
       // the executing container, as RunMINCOParking fills it (traj_manager.cpp:618-625)
-      std::vector<LocalTrajData> executing_traj;
-      {
-        double world = t_start[s];
-        int p0 = 0;
-        for (int i = 0; i < n_seg[s]; i++) {
-          LocalTrajData d;
-          for (int k = 0; k < piece_nums[s * max_seg + i]; k++)
-            d.traj.pieces.push_back(Piece{coeff_dt[s * max_seg + i], coeffs + ((size_t)s * max_seg * max_pieces + p0 + k) * 12, singul[s * max_seg + i]});
-          p0 += piece_nums[s * max_seg + i];
-          d.duration = d.traj.getTotalDuration();
-          d.start_time = world;
-          d.end_time = d.start_time + d.duration;
-          world = d.end_time;
-          executing_traj.push_back(d);
-          times[((size_t)s * max_seg + i) * 3] = d.duration;
-          times[((size_t)s * max_seg + i) * 3 + 1] = d.start_time;
-          times[((size_t)s * max_seg + i) * 3 + 2] = d.end_time;
-        }
+      const size_t row = (size_t)s * max_seg;
+      std::vector<LocalTrajData> executing_traj =
+          fill_container(n_seg[s], singul + row, piece_nums + row, coeff_dt + row, coeffs + row * max_pieces * 12, t_start[s]);
+      for (size_t i = 0; i < executing_traj.size(); i++) {
+        times[(row + i) * 3] = executing_traj[i].duration;
+        times[(row + i) * 3 + 1] = executing_traj[i].start_time;
+        times[(row + i) * 3 + 2] = executing_traj[i].end_time;
       }
       const int final_traj_index = (int)executing_traj.size() - 1;
       const double current_time = t_now;
@@ -332,8 +142,8 @@ extern "C" void oracle_replan_check(const unsigned char *grid, int size_x, int s
           }
         }
         const double t = desired_state.time_stamp - executing_traj.at(pidx).start_time;
-        executing_traj.at(pidx).traj.GetState(t, &desired_state, vp.wheel_base, T);
-        if (have_hist[s]) filter_singularity(hist[2 * s], hist[2 * s + 1], &desired_state, T); // hist.empty(): kWrongStatus, untouched
+        executing_traj.at(pidx).traj.GetState(t, &desired_state, wheel_base, T);
+        if (have_hist[s]) FilterSingularityState(hist[2 * s], hist[2 * s + 1], &desired_state, T); // hist.empty(): kWrongStatus, untouched
         have_desired = true;
         pidx_out[s] = pidx;
         t_local[s] = t;
@@ -342,16 +152,16 @@ extern "C" void oracle_replan_check(const unsigned char *grid, int size_x, int s
     if (have_desired) {
       double *d = desired + 8 * s;
       d[0] = desired_state.time_stamp;
-      d[1] = desired_state.x;
-      d[2] = desired_state.y;
+      d[1] = desired_state.vec_position.x;
+      d[2] = desired_state.vec_position.y;
       d[3] = desired_state.angle;
       d[4] = desired_state.curvature;
       d[5] = desired_state.velocity;
       d[6] = desired_state.acceleration;
       d[7] = desired_state.steer;
       // getKinoPath, traj_manager.cpp:74-75
-      start_state[4 * s] = desired_state.x;
-      start_state[4 * s + 1] = desired_state.y;
+      start_state[4 * s] = desired_state.vec_position.x;
+      start_state[4 * s + 1] = desired_state.vec_position.y;
       start_state[4 * s + 2] = desired_state.angle;
       start_state[4 * s + 3] = desired_state.velocity;
       start_ctrl[2 * s] = desired_state.steer;

@@ -3,41 +3,29 @@
 Only tests/ and scripts/ import this."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
 from dftpav_amd.pods import SearchOut, SearchParams
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SO = os.path.join(_HERE, "libkino_search_oracle.so")
-_LIB = None
-_SRCS = ("kino_search_oracle.cpp", "../oracle/step_trig.h", "../dftpav_amd/csrc/kino_heap.h", "../dftpav_amd/csrc/rs_math.h",
-         "../dftpav_amd/csrc/cr_trig.h", "../include/dftpav_hip.h")
+from oracle_shared.loader import Loader
 
 
-def build(force=False):
-    if force or not os.path.exists(_SO) or any(os.path.getmtime(_SO) < os.path.getmtime(os.path.join(_HERE, s)) for s in _SRCS):
-        subprocess.check_call(["make", "-C", _HERE, "-s"])
-    return _SO
+def _declare(L):
+    L.oracle_kino_search.restype = None
+    L.oracle_kino_search.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.oracle_kino_search_field.restype = None
+    L.oracle_kino_search_field.argtypes = L.oracle_kino_search.argtypes + [C.c_void_p, C.c_void_p, C.c_double]
+    L.oracle_state_transit.restype = None
+    L.oracle_state_transit.argtypes = [C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.heap_selftest.restype = C.c_longlong
+    L.heap_selftest.argtypes = [C.c_ulonglong, C.c_longlong]
 
 
-def lib():
-    global _LIB
-    if _LIB is None:
-        build()
-        L = C.CDLL(_SO)
-        L.oracle_kino_search.restype = None
-        L.oracle_kino_search.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        L.oracle_kino_search_field.restype = None
-        L.oracle_kino_search_field.argtypes = L.oracle_kino_search.argtypes + [C.c_void_p, C.c_void_p, C.c_double]
-        L.oracle_state_transit.restype = None
-        L.oracle_state_transit.argtypes = [C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.heap_selftest.restype = C.c_longlong
-        L.heap_selftest.argtypes = [C.c_ulonglong, C.c_longlong]
-        _LIB = L
-    return _LIB
+_load = Loader(os.path.dirname(os.path.abspath(__file__)), "libkino_search_oracle.so",
+               ("kino_search_oracle.cpp", "../oracle/step_trig.h", "../dftpav_amd/csrc/kino_heap.h", "../dftpav_amd/csrc/rs_math.h",
+                "../dftpav_amd/csrc/cr_trig.h", "../include/dftpav_hip.h"), _declare)
+build, lib = _load.build, _load.lib
 
 
 def kino_search(grid, resolution, origin, start_states, end_states, sp=None, order=2, max_nodes=512, max_path=4096,
