@@ -56,6 +56,7 @@ EXPORTS = [
     "dftpav_grid_distance_field", "dftpav_batch_check_clearance", "dftpav_planner_check_clearance", "dftpav_planner_set_clearance_filter",
     "dftpav_planner_last_clearance", "dftpav_clearance_last_ms",
     "dftpav_default_goal_field_params", "dftpav_set_search_heuristic", "dftpav_grid_goal_field", "dftpav_goal_field_last_ms",
+    "dftpav_default_rs_heuristic_params", "dftpav_set_search_rs_heuristic", "dftpav_rs_table", "dftpav_rs_table_last_ms",
 ]
 
 
@@ -223,6 +224,30 @@ def default_goal_field_params():
     fn.argtypes = [C.c_void_p]
     fn.restype = None
     fn(C.byref(gp))
+    return gp
+
+
+class RsHeuristicParams(C.Structure):
+    """dftpav_rs_heuristic_params: the Reeds-Shepp term of the search heuristic (dftpav_set_search_rs_heuristic) and its table"""
+    _fields_ = [("enabled", C.c_int), ("n_yaw", C.c_int), ("extent", C.c_double), ("cell", C.c_double), ("scale", C.c_double)]
+
+
+def default_rs_heuristic_params():
+    """dftpav_default_rs_heuristic_params: off, 72 headings, 15 m, cells of 0.25 m, scale 1"""
+    gp = RsHeuristicParams()
+    fn = lib().dftpav_default_rs_heuristic_params
+    fn.argtypes = [C.c_void_p]
+    fn.restype = None
+    fn(C.byref(gp))
+    return gp
+
+
+def _rs_params(enabled, n_yaw, extent, cell, scale):
+    gp = default_rs_heuristic_params()
+    gp.enabled = int(bool(enabled))
+    for k, v in (("n_yaw", n_yaw), ("extent", extent), ("cell", cell), ("scale", scale)):
+        if v is not None:
+            setattr(gp, k, int(v) if k == "n_yaw" else float(v))
     return gp
 
 
@@ -470,6 +495,41 @@ class Handle:
         fn = lib().dftpav_set_search_heuristic
         fn.argtypes = [C.c_void_p, C.c_void_p]
         self._check(fn(self._h, C.byref(gp)), "set_search_heuristic")
+
+    def set_search_rs_heuristic(self, enabled=True, n_yaw=None, extent=None, cell=None, scale=None):
+        """dftpav_set_search_rs_heuristic: kino_search, Planner.plan and Planner.tick also take the maximum with scale * the
+        Reeds-Shepp length to the goal, read from the handle's table, when enabled; off (the default state of a handle) they do what
+        they do without this call.  None: the default of dftpav_default_rs_heuristic_params"""
+        gp = _rs_params(enabled, n_yaw, extent, cell, scale)
+        fn = lib().dftpav_set_search_rs_heuristic
+        fn.argtypes = [C.c_void_p, C.c_void_p]
+        self._check(fn(self._h, C.byref(gp)), "set_search_rs_heuristic")
+
+    def rs_table(self, max_cur=None, n_yaw=None, extent=None, cell=None, fetch=True):
+        """dftpav_rs_table: the Reeds-Shepp cost-to-go table double [n_yaw][n][n] of rho = 1 / max_cur (None: the default search
+        parameters' max_frontend_cur) and the given geometry; fetch=False: its shape (n_yaw, n, n) alone, nothing built"""
+        gp = _rs_params(False, n_yaw, extent, cell, None)
+        if max_cur is None:
+            from .pods import SearchParams
+            max_cur = SearchParams.default().max_frontend_cur
+        fn = lib().dftpav_rs_table
+        fn.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+        dims = (C.c_int * 3)()
+        self._check(fn(self._h, float(max_cur), C.byref(gp), None, dims), "rs_table")
+        shape = tuple(int(v) for v in dims)
+        if not fetch:
+            return shape
+        out = np.zeros(shape, dtype=np.float64)
+        self._check(fn(self._h, float(max_cur), C.byref(gp), out.ctypes.data_as(C.c_void_p), dims), "rs_table")
+        return out
+
+    def rs_table_last_ms(self):
+        """dftpav_rs_table_last_ms: (device ms of the handle's last table build, tables built over the handle's life)"""
+        ms, nb = C.c_float(0.0), C.c_int(0)
+        fn = lib().dftpav_rs_table_last_ms
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]
+        self._check(fn(self._h, C.byref(ms), C.byref(nb)), "rs_table_last_ms")
+        return float(ms.value), int(nb.value)
 
     def goal_field_last_ms(self):
         """dftpav_goal_field_last_ms: device ms of the goal-field builds of the last call that built any"""

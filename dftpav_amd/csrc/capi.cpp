@@ -264,6 +264,9 @@ extern "C" void dftpav_destroy(dftpav_handle *h) {
   if (h->d_gf) (void)hipFree(h->d_gf);
   if (h->d_gf_meta) (void)hipFree(h->d_gf_meta);
   for (hipEvent_t e : h->gf_ev) (void)hipEventDestroy(e);
+  if (h->d_rs) (void)hipFree(h->d_rs);
+  for (hipEvent_t e : {h->rs_ev0, h->rs_ev1})
+    if (e) (void)hipEventDestroy(e);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }

@@ -65,6 +65,8 @@ hipError_t launch_clearance_batch(const ClearanceBatchArgs &A, hipStream_t strea
 hipError_t launch_clearance_table(const ClearanceTableArgs &A, hipStream_t stream);
 // goalfield.hip: the cost-to-go fields of n goal cells, one workgroup each
 hipError_t launch_goal_fields(const GoalFieldArgs &A, int n, hipStream_t stream);
+// rstable.hip: every entry of the Reeds-Shepp cost-to-go table
+hipError_t launch_rs_table(const RsTableArgs &A, hipStream_t stream);
 hipError_t launch_corridor_layout(const double *raw, double *out, int B, int Npts, int H, int NptsPad, hipStream_t stream);
 hipError_t launch_adopt(const DevBatch &D, const DevBatch &prev, hipStream_t stream);
 // solver_ref.hip: the same path in the reference's own floating-point order
@@ -127,6 +129,15 @@ struct dftpav_handle {
   std::vector<int> gf_host; // the host copy of field_of | goal cells (the source of an asynchronous copy)
   std::vector<hipEvent_t> gf_ev; // a pair around every turn's build
   int gf_timed = 0;              // pairs recorded by the last call that built fields
+  // the Reeds-Shepp term of the search heuristic (dftpav_set_search_rs_heuristic) and its table (rstable.hip): built in front of
+  // the first search launch that needs it, kept until a call asks for another key (rho, n_yaw, extent, cell)
+  dftpav_rs_heuristic_params rsh{0, 0, 0.0, 0.0, 0.0};
+  double *d_rs = nullptr;
+  size_t rs_doubles = 0;
+  double rs_rho = 0.0, rs_extent = 0.0, rs_cell = 0.0; // the key of what d_rs holds; rs_n_yaw == 0: nothing
+  int rs_n_yaw = 0;
+  int rs_builds = 0; // launches of rs_table_kernel over the handle's life
+  hipEvent_t rs_ev0 = nullptr, rs_ev1 = nullptr; // around the last build
   std::vector<struct dftpav_batch *> batches; // every live batch of this handle (obstacle changes finish their chained stragglers)
   // RCCL communicator of dftpav_comm_create (one rank per handle = per GPU), and the staging block of this rank's records
   void *comm = nullptr;
@@ -395,6 +406,12 @@ int goal_field_plan(dftpav_handle *h, const double *xy, int stride, int n, int s
 int goal_field_turn(dftpav_handle *h, const GoalFieldPlan &G, int t, SearchArgs *S, int **fields);
 // search_setup's slots with the heuristic: a plan for the queries' goals when it is on (G.per_turn replaces U.slots), nothing otherwise
 int search_heuristic_plan(dftpav_handle *h, const double *end_states, int n, SearchSetup &U, GoalFieldPlan &G);
+// The Reeds-Shepp table.  rs_geometry: the checked geometry of a parameter set (DFTPAV_E_INVALID / _UNSUPPORTED as the header
+// says).  ensure_rs_table: the table of (rho, gp) on the device, built on the handle's stream if the handle holds another.
+// search_rs_plan: with the heuristic on, the table of the launch's rho wired into U.S; off, nothing.
+int rs_geometry(const dftpav_rs_heuristic_params &gp, RsGeometry &g, size_t &entries);
+int ensure_rs_table(dftpav_handle *h, double rho, const dftpav_rs_heuristic_params &gp, RsGeometry &g);
+int search_rs_plan(dftpav_handle *h, SearchSetup &U);
 
 // One allocation for many arrays, measured and carved by the same list: fields(take) names every array in order, take(bytes) is its
 // address -- null while `base` is null, the measuring pass -- and advances by the size rounded up to 256 bytes.  Returns the bytes used.

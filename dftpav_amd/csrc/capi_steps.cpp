@@ -961,6 +961,7 @@ int dftpav::goal_field_turn(dftpav_handle *h, const GoalFieldPlan &G, int t, Sea
 
 int dftpav::search_heuristic_plan(dftpav_handle *h, const double *end_states, int n, SearchSetup &U, GoalFieldPlan &G) {
   G = GoalFieldPlan{};
+  if (int rc = search_rs_plan(h, U)) return rc; // dftpav_set_search_rs_heuristic; off: nothing
   if (!h->heu.enabled) return DFTPAV_OK;
   if (int rc = goal_field_plan(h, end_states, 4, n, U.slots, h->heu.inflate_radius, G)) return rc;
   G.unit = h->heu.scale * h->map.resolution / 5.0;
@@ -1027,5 +1028,110 @@ extern "C" int dftpav_goal_field_last_ms(dftpav_handle *h, float *ms) {
     sum += one;
   }
   *ms = sum;
+  return DFTPAV_OK;
+}
+
+// ------------------------------------------------- the Reeds-Shepp cost-to-go table and the search heuristic on it (rstable.hip)
+static constexpr size_t kRsTableCapBytes = (size_t)256 << 20;
+
+int dftpav::rs_geometry(const dftpav_rs_heuristic_params &gp, RsGeometry &g, size_t &entries) {
+  if (gp.n_yaw < 1 || !std::isfinite(gp.cell) || !(gp.cell > 0.0) || !std::isfinite(gp.extent) || !(gp.extent >= 0.0) ||
+      !std::isfinite(gp.scale) || !(gp.scale >= 0.0))
+    return DFTPAV_E_INVALID;
+  const double halfd = std::ceil(gp.extent / gp.cell);
+  if (!(halfd < 32768.0)) return DFTPAV_E_UNSUPPORTED; // (a side beyond any table of 256 MiB; also keeps n an int)
+  g.n_yaw = gp.n_yaw;
+  g.half = (int)halfd;
+  g.n = 2 * g.half + 1;
+  g.cell = gp.cell;
+  g.dth = 2.0 * M_PI / (double)gp.n_yaw;
+  const double want = (double)g.n_yaw * (double)g.n * (double)g.n;
+  if (want * sizeof(double) > (double)kRsTableCapBytes) return DFTPAV_E_UNSUPPORTED;
+  entries = (size_t)g.n_yaw * g.n * g.n;
+  return DFTPAV_OK;
+}
+
+int dftpav::ensure_rs_table(dftpav_handle *h, double rho, const dftpav_rs_heuristic_params &gp, RsGeometry &g) {
+  size_t entries = 0;
+  if (int rc = rs_geometry(gp, g, entries)) return rc;
+  if (h->d_rs && h->rs_n_yaw == gp.n_yaw && h->rs_rho == rho && h->rs_extent == gp.extent && h->rs_cell == gp.cell) return DFTPAV_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  h->rs_n_yaw = 0; // nothing valid until the build below is in the stream
+  if (h->rs_doubles < entries) HIPCHK(h, hipStreamSynchronize(h->stream)); // nothing in flight reads what is freed
+  if (int rc = grow(h, h->d_rs, h->rs_doubles, entries)) return rc;
+  if (!h->rs_ev0) HIPCHK(h, hipEventCreate(&h->rs_ev0));
+  if (!h->rs_ev1) HIPCHK(h, hipEventCreate(&h->rs_ev1));
+  RsTableArgs A{};
+  A.T = h->d_rs;
+  A.entries = (long long)entries;
+  A.g = g;
+  A.rho = rho;
+  HIPCHK(h, hipEventRecord(h->rs_ev0, h->stream));
+  HIPCHK(h, launch_rs_table(A, h->stream));
+  HIPCHK(h, hipEventRecord(h->rs_ev1, h->stream));
+  h->rs_builds++;
+  h->rs_rho = rho;
+  h->rs_extent = gp.extent;
+  h->rs_cell = gp.cell;
+  h->rs_n_yaw = gp.n_yaw;
+  return DFTPAV_OK;
+}
+
+int dftpav::search_rs_plan(dftpav_handle *h, SearchSetup &U) {
+  if (!h->rsh.enabled) return DFTPAV_OK;
+  RsGeometry g{};
+  if (int rc = ensure_rs_table(h, U.S.rho, h->rsh, g)) return rc;
+  U.S.rs.tab = h->d_rs;
+  U.S.rs.g = g;
+  U.S.rs.scale = h->rsh.scale;
+  return DFTPAV_OK;
+}
+
+extern "C" void dftpav_default_rs_heuristic_params(dftpav_rs_heuristic_params *gp) {
+  if (!gp) return;
+  gp->enabled = 0;
+  gp->n_yaw = 72;
+  gp->extent = 15.0; // the radius inside which the search tries the shot (kino_astar.cpp:91)
+  gp->cell = 0.25;
+  gp->scale = 1.0;
+}
+
+extern "C" int dftpav_set_search_rs_heuristic(dftpav_handle *h, const dftpav_rs_heuristic_params *gp) {
+  if (!h) return DFTPAV_E_INVALID;
+  if (!gp || !gp->enabled) {
+    h->rsh.enabled = 0;
+    return DFTPAV_OK;
+  }
+  RsGeometry g{};
+  size_t entries = 0;
+  if (int rc = rs_geometry(*gp, g, entries)) return rc;
+  h->rsh = *gp;
+  h->rsh.enabled = 1;
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_rs_table(dftpav_handle *h, double max_cur, const dftpav_rs_heuristic_params *gp, double *out, int *dims) {
+  if (!h || !gp || !std::isfinite(max_cur) || !(max_cur > 0.0)) return DFTPAV_E_INVALID;
+  RsGeometry g{};
+  size_t entries = 0;
+  if (int rc = rs_geometry(*gp, g, entries)) return rc;
+  if (dims) {
+    dims[0] = g.n_yaw;
+    dims[1] = g.n;
+    dims[2] = g.n;
+  }
+  if (!out) return DFTPAV_OK;
+  if (int rc = ensure_rs_table(h, 1.0 / max_cur, *gp, g)) return rc;
+  HIPCHK(h, hipMemcpyAsync(out, h->d_rs, sizeof(double) * entries, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_rs_table_last_ms(dftpav_handle *h, float *ms, int *n_builds) {
+  if (!h || !ms || h->rs_builds < 1) return DFTPAV_E_INVALID;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipEventSynchronize(h->rs_ev1));
+  HIPCHK(h, hipEventElapsedTime(ms, h->rs_ev0, h->rs_ev1));
+  if (n_builds) *n_builds = h->rs_builds;
   return DFTPAV_OK;
 }

@@ -134,6 +134,17 @@ class TrajPlannerSteps {
     return ok(dftpav_set_search_heuristic(h_, &gp));
   }
 
+  // The non-holonomic half of the heuristic: search() below, and every plan through this handle, then also take the maximum with
+  // the Reeds-Shepp length to the goal, read from a table of the default geometry (72 headings, 15 m, cells of 0.25 m) that the
+  // handle builds once.  Off by default, and off again with enabled = false.  Independent of setObstacleHeuristic; needs no map.
+  bool setReedsSheppHeuristic(bool enabled, double scale = 1.0) {
+    dftpav_rs_heuristic_params gp;
+    dftpav_default_rs_heuristic_params(&gp);
+    gp.enabled = enabled ? 1 : 0;
+    gp.scale = scale;
+    return ok(dftpav_set_search_rs_heuristic(h_, &gp));
+  }
+
   // KinoAstar::search as getKinoPath runs it (3D, then the 2D retry) followed by getKinoNode up to SampleTraj, one query:
   // returns the reference's status (DFTPAV_SEARCH_REACH_END / _NO_PATH, or a negative DFTPAV_E_* code); SampleTraj is what
   // getKinoNode above takes

@@ -28,6 +28,14 @@
 //   lambda_heu * fmax(tie_breaker * |p - goal|, (double)F_q[cell of p] * unit),
 // the term of kino_astar.cpp:247's commented-out line as a maximum with getHeu; the cell by grid_occupied's rounding, 0 for a point
 // outside the grid or an unreached cell.  The 3D search and its 2D retry read the same field.
+//
+// The second template flag, TABLE, adds the non-holonomic, obstacle-free term (dftpav_set_search_rs_heuristic): the Reeds-Shepp
+// cost-to-go table T of rstable.hip, read at the nearest cell of the state in the goal's frame.  Per query, once: c = cos(goal
+// yaw), s = sin(goal yaw), correctly rounded.  For a state (x, y, yaw): lx = c (x - gx) + s (y - gy), ly = c (y - gy) - s (x - gx),
+// fi = round(lx / cell) + half, fj = round(ly / cell) + half as doubles; outside [0, n) in either (or NaN) the term is 0; the yaw
+// slice is k = (int)round((yaw - goal yaw) / dth) reduced into [0, n_yaw) by integer remainder; the term is scale * T[k][fj][fi].
+// The heuristic is then lambda_heu * fmax(fmax(tie_breaker * |p - goal|, the field's term where there is one), the table's term).
+// search_kernel<false, false> and <true, false> are the kernels of before; launch_search picks the instance.
 #include <hip/hip_runtime.h>
 
 #include "../../include/dftpav_hip.h"
@@ -40,12 +48,6 @@ namespace dftpav {
 
 constexpr char kInClose = 'a', kInOpen = 'b'; // kino_astar.h:36-38
 constexpr int kReachEnd = 2, kNoPath = 3;
-
-struct CrMath { // the shot's elementary functions, correctly rounded
-  DFTPAV_HD static double sin(double x) { return crt::sin(x); }
-  DFTPAV_HD static double cos(double x) { return crt::cos(x); }
-  DFTPAV_HD static double atan2(double y, double x) { return crt::atan2(y, x); }
-};
 
 // stateTransit, kino_astar.cpp:21-36 (psi != 0 takes the curved branch, however small psi is)
 __device__ inline void sr_transit(const SearchArgs &A, double x0, double y0, double yaw0, double psi, double s, double *o) {
@@ -157,10 +159,41 @@ __device__ inline double sr_field_heu(const SearchArgs &A, const int *Fq, double
   return v == DFTPAV_FIELD_UNREACHED ? 0.0 : (double)v * A.unit;
 }
 
+// the Reeds-Shepp table's term of the heuristic at (x, y, yaw), in metres: 0 outside the table's extent (and for a NaN).
+// gc / gs: cos / sin of the goal's yaw
+__device__ inline double sr_rs_heu(const RsLookup &R, const double *en, double gc, double gs, double x, double y, double yaw) {
+  const RsGeometry &g = R.g;
+  const double ddx = x - en[0], ddy = y - en[1];
+  const double lx = gc * ddx + gs * ddy, ly = gc * ddy - gs * ddx;
+  const double fi = round(lx / g.cell) + (double)g.half, fj = round(ly / g.cell) + (double)g.half;
+  if (!(fi >= 0.0 && fi < (double)g.n && fj >= 0.0 && fj < (double)g.n)) return 0.0;
+  const double kd = round((yaw - en[2]) / g.dth);
+  if (!(fabs(kd) < 9.0e18)) return 0.0; // (a yaw that is not finite, or beyond any int: nothing to read)
+  int k = (int)((long long)kd % (long long)g.n_yaw);
+  if (k < 0) k += g.n_yaw;
+  return R.scale * R.tab[((size_t)k * g.n + (size_t)(int)fj) * g.n + (size_t)(int)fi];
+}
+
+// the heuristic of a state: getHeu, and the maximum with the terms the instance has
+template <bool FIELD, bool TABLE>
+__device__ inline double sr_heu(const SearchArgs &A, const double *en, const int *Fq, double gc, double gs, double x, double y, double yaw) {
+  const dftpav_search_params &P = A.sp;
+  const double dx = fabs(x - en[0]), dy = fabs(y - en[1]);
+  if constexpr (TABLE) {
+    double m = P.tie_breaker * sqrt(dx * dx + dy * dy);
+    if constexpr (FIELD) m = fmax(m, Fq ? sr_field_heu(A, Fq, x, y) : 0.0);
+    return P.lambda_heu * fmax(m, sr_rs_heu(A.rs, en, gc, gs, x, y, yaw));
+  } else if constexpr (FIELD) {
+    return P.lambda_heu * fmax(P.tie_breaker * sqrt(dx * dx + dy * dy), Fq ? sr_field_heu(A, Fq, x, y) : 0.0);
+  } else {
+    return P.lambda_heu * (P.tie_breaker * sqrt(dx * dx + dy * dy));
+  }
+}
+
 // one call of KinoAstar::search(start, ctrl, end, use3d) after reset(); result in S.status / shot / budget / iters / used / terminal
-template <bool FIELD>
+template <bool FIELD, bool TABLE>
 __device__ void sr_search(const SearchArgs &A, SShared &S, SearchNode *pool, KinoHeap &heap, int *table, const double *st,
-                          const double *en, bool use3d, int lane, const int *Fq) {
+                          const double *en, bool use3d, int lane, const int *Fq, double gc, double gs) {
   const dftpav_search_params &P = A.sp;
   for (int s = lane; s < A.hcap; s += kSearchThreads) table[s] = -1;
   if (lane == 0) {
@@ -204,9 +237,7 @@ __device__ void sr_search(const SearchArgs &A, SShared &S, SearchNode *pool, Kin
     n0.steer = 0.0;
     n0.arc = 0.0;
     n0.singul = singul0;
-    const double dx = fabs(st[0] - en[0]), dy = fabs(st[1] - en[1]);
-    if constexpr (FIELD) n0.f = P.lambda_heu * fmax(P.tie_breaker * sqrt(dx * dx + dy * dy), Fq ? sr_field_heu(A, Fq, st[0], st[1]) : 0.0);
-    else n0.f = P.lambda_heu * (P.tie_breaker * sqrt(dx * dx + dy * dy));
+    n0.f = sr_heu<FIELD, TABLE>(A, en, Fq, gc, gs, st[0], st[1], st[2]);
     n0.state = kInOpen;
     heap.size = 0;
     heap.push(0, n0.f);
@@ -283,9 +314,7 @@ __device__ void sr_search(const SearchArgs &A, SShared &S, SearchNode *pool, Kin
       S.ix[lane] = (int)round((o[0] - A.origin_sx) / P.map_resl);
       S.iy[lane] = (int)round((o[1] - A.origin_sy) / P.map_resl);
       S.yid[lane] = sr_yaw_index(A, o[2]);
-      const double dx = fabs(o[0] - en[0]), dy = fabs(o[1] - en[1]);
-      if constexpr (FIELD) S.heu[lane] = P.lambda_heu * fmax(P.tie_breaker * sqrt(dx * dx + dy * dy), Fq ? sr_field_heu(A, Fq, o[0], o[1]) : 0.0);
-      else S.heu[lane] = P.lambda_heu * (P.tie_breaker * sqrt(dx * dx + dy * dy));
+      S.heu[lane] = sr_heu<FIELD, TABLE>(A, en, Fq, gc, gs, o[0], o[1], o[2]);
     }
     if (lane < n_in * P.check_num) {
       const int i = lane / P.check_num, k = lane % P.check_num + 1;
@@ -366,7 +395,7 @@ __device__ void sr_search(const SearchArgs &A, SShared &S, SearchNode *pool, Kin
   __syncthreads();
 }
 
-template <bool FIELD> __global__ void __launch_bounds__(kSearchThreads) search_kernel(SearchArgs A) {
+template <bool FIELD, bool TABLE> __global__ void __launch_bounds__(kSearchThreads) search_kernel(SearchArgs A) {
   __shared__ SShared S;
   const int slot = blockIdx.x, q = A.q0 + blockIdx.x, lane = threadIdx.x;
   if (q >= A.n) return;
@@ -386,15 +415,20 @@ template <bool FIELD> __global__ void __launch_bounds__(kSearchThreads) search_k
     const int f = A.field_of[q];
     if (f >= 0) Fq = A.fields + (size_t)f * A.grid.size_x * A.grid.size_y;
   }
+  double gc = 1.0, gs = 0.0; // cos / sin of the goal's yaw: the goal's frame, in which the table is read
+  if constexpr (TABLE) {
+    gc = crt::cos(en[2]);
+    gs = crt::sin(en[2]);
+  }
   if (lane == 0) S.overflow = 0;
   __syncthreads();
   // getKinoPath, traj_manager.cpp:85-103: the first pass, then (NO_PATH, 3D) the 2D retry
   bool use3d = P.use3d != 0;
-  sr_search<FIELD>(A, S, pool, heap, table, st, en, use3d, lane, Fq);
+  sr_search<FIELD, TABLE>(A, S, pool, heap, table, st, en, use3d, lane, Fq, gc, gs);
   if (!S.overflow && S.status == kNoPath && use3d && P.retry_2d) {
     __syncthreads();
     use3d = false;
-    sr_search<FIELD>(A, S, pool, heap, table, st, en, false, lane, Fq);
+    sr_search<FIELD, TABLE>(A, S, pool, heap, table, st, en, false, lane, Fq, gc, gs);
   }
   __syncthreads();
   const dftpav_search_out &O = A.out;
@@ -526,8 +560,11 @@ template <bool FIELD> __global__ void __launch_bounds__(kSearchThreads) search_k
 }
 
 hipError_t launch_search(const SearchArgs &A, int blocks, hipStream_t stream) {
-  if (A.fields) hipLaunchKernelGGL(search_kernel<true>, dim3(blocks), dim3(kSearchThreads), 0, stream, A);
-  else hipLaunchKernelGGL(search_kernel<false>, dim3(blocks), dim3(kSearchThreads), 0, stream, A);
+  const dim3 grid(blocks), block(kSearchThreads);
+  if (A.rs.tab && A.fields) hipLaunchKernelGGL((search_kernel<true, true>), grid, block, 0, stream, A);
+  else if (A.rs.tab) hipLaunchKernelGGL((search_kernel<false, true>), grid, block, 0, stream, A);
+  else if (A.fields) hipLaunchKernelGGL((search_kernel<true, false>), grid, block, 0, stream, A);
+  else hipLaunchKernelGGL((search_kernel<false, false>), grid, block, 0, stream, A);
   return hipGetLastError();
 }
 

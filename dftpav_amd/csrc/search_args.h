@@ -3,6 +3,7 @@
 #include "../../include/dftpav_hip.h"
 #include "footprint.h"
 #include "piece_eval.h"
+#include "rstable_args.h"
 
 namespace dftpav {
 
@@ -39,6 +40,8 @@ struct SearchArgs {
   const int *fields;   // [distinct goals of this launch][size_y][size_x]
   const int *field_of; // [n] the field of query q, -1: none (a goal outside the grid)
   double unit;         // metres of heuristic per unit of the field: scale * resolution / 5
+  // the Reeds-Shepp table of dftpav_set_search_rs_heuristic (rstable.hip); read only by the kernel launched with a table
+  RsLookup rs;
 };
 
 } // namespace dftpav

@@ -84,6 +84,21 @@ def maze():
     return "maze", g, RES, ORIGIN, np.array([-15.0, -5.0, 0.0, 0.0]), np.array([3.0, 0.0, 0.0, 0.0])
 
 
+PARALLEL_SLOT_MAX_ITERS = 2000  # the oracle (order 2) ends by a free shot after 506 pops (1713 nodes) without the Reeds-Shepp table
+RS_SMALL = dict(n_yaw=16, extent=6.0, cell=0.5)   # the table geometry of the tests: 16 x 25 x 25 entries
+
+
+def parallel_slot():
+    """a bay 10 m long between two blocks with a wall behind it, beside the lane the vehicle stands in; the goal is the start moved
+    3.5 m sideways into the bay, heading unchanged.  Straight-line distance and goal field are small from the first node on; what is
+    left to do is all heading.  The shot from the start collides with the rear block.  Not one of small_scenes(); run it with
+    max_iters = PARALLEL_SLOT_MAX_ITERS."""
+    g = _box(_grid(), 6.0, -6.5, 11.0, -1.5)
+    g = _box(g, -9.0, -6.5, -4.0, -1.5)
+    g = _box(g, -9.0, -6.5, 11.0, -4.9)
+    return "parallel-slot", g, RES, ORIGIN, np.array([0.0, 0.0, 0.0, 0.0]), np.array([0.0, -3.5, 0.0, 0.0])
+
+
 # goals on the default arena (sc.default_sim_map): free poses near the ego vehicle whose direct shot from the ego start
 # collides (checked by tests/test_search_oracle.py)
 ARENA_GOALS = np.array([

@@ -1058,6 +1058,46 @@ int dftpav_grid_goal_field(dftpav_handle *h, const double *goals_xy /*[n][2]*/, 
                            int *field /*[n][size_y][size_x] or NULL*/, int *n_reached /*[n] or NULL*/);
 int dftpav_goal_field_last_ms(dftpav_handle *h, float *ms);
 
+/* ---- the Reeds-Shepp cost-to-go table, and the non-holonomic term of the hybrid A* heuristic ----------------------------
+ * getHeu and the goal field above know positions only: neither knows that the vehicle cannot turn on the spot, nor that the goal
+ * has a heading.  This is the other half of the usual pair (Dolgov et al.): the length of the shortest Reeds-Shepp path to the
+ * goal, without obstacles, from a table.  It depends on the turning radius and the table's geometry only -- not on the map, not
+ * on the goal's position -- so a handle builds it once and the search reads one double per heuristic.
+ *
+ * The table.  rho = 1 / max_frontend_cur of the search parameters in force (the rho of the shot); half = (int)ceil(extent /
+ * cell), n = 2 half + 1, dth = 2 pi / (double)n_yaw.  T is double [n_yaw][n][n]:
+ *   T[k][j][i] = rho * (normalised length of the shortest Reeds-Shepp path from ((i - half) cell, (j - half) cell, k dth) to
+ *   (0, 0, 0)),
+ * the expression the search forms for the length of its shot, by the same solver (rs_math.h; rstable.hip), fp64.  The handle owns
+ * it, keyed by (rho, n_yaw, extent, cell): built on the handle's stream in front of the first search launch that needs it (or by
+ * dftpav_rs_table), kept, and rebuilt only when a call asks for another key.  A handle holds one table.
+ *
+ * The heuristic.  dftpav_set_search_rs_heuristic keeps its state on the handle, beside and independent of
+ * dftpav_set_search_heuristic; it needs no map.  Off (the default; gp == NULL or enabled == 0): dftpav_kino_search,
+ * dftpav_plan_queries and dftpav_replan_tick launch what they launch without this call and return the same bits.  On: with c =
+ * cos(goal yaw), s = sin(goal yaw) (correctly rounded), a state (x, y, yaw) has, in the goal's frame,
+ *   lx = c (x - gx) + s (y - gy),  ly = c (y - gy) - s (x - gx),  fi = round(lx / cell) + half,  fj = round(ly / cell) + half,
+ *   k = (int)round((yaw - goal yaw) / dth) reduced into [0, n_yaw) by integer remainder,
+ * the term is scale * T[k][fj][fi] where 0 <= fi < n and 0 <= fj < n, and 0 elsewhere, and the search forms, for the start node
+ * and for every expanded input,
+ *   h = lambda_heu * fmax(fmax(tie_breaker * |p - goal|, the goal field's term if that heuristic is on), the table's term).
+ * The 3D search and its 2D retry read the same table.  Not claimed: the table is obstacle-free; it is read at the nearest cell
+ * and heading, so it is not a lower bound of the state's own Reeds-Shepp distance and no admissibility is claimed; beyond the
+ * extent the term is 0.
+ * dftpav_rs_table: builds (if the handle does not hold it) and reads out the table of rho = 1 / max_cur and gp's geometry,
+ *   whether or not the heuristic is on (gp->enabled is not read); dims = (n_yaw, n, n); out == NULL: dims only, nothing built.
+ * dftpav_rs_table_last_ms: device time in ms of the handle's last table build, and (n_builds, may be NULL) how many tables the
+ *   handle has built in its life.
+ * DFTPAV_E_INVALID, and nothing changed: a NULL handle (or gp, for dftpav_rs_table), n_yaw < 1, cell <= 0, extent < 0, scale < 0,
+ * any of them not finite, max_cur not positive and finite; dftpav_rs_table_last_ms before any build.  DFTPAV_E_UNSUPPORTED, and
+ * nothing changed: a table above 256 MiB (n_yaw * n * n * 8 bytes). */
+typedef struct dftpav_rs_heuristic_params { int enabled; int n_yaw; double extent; double cell; double scale; } dftpav_rs_heuristic_params;
+void dftpav_default_rs_heuristic_params(dftpav_rs_heuristic_params *gp); /* 0, 72, 15.0 (kino_astar.cpp:91), 0.25, 1.0 */
+int dftpav_set_search_rs_heuristic(dftpav_handle *h, const dftpav_rs_heuristic_params *gp); /* NULL or enabled == 0: off (default) */
+int dftpav_rs_table(dftpav_handle *h, double max_cur, const dftpav_rs_heuristic_params *gp, double *out /*[n_yaw][n][n] or NULL*/,
+                    int *dims /*[3] or NULL*/);
+int dftpav_rs_table_last_ms(dftpav_handle *h, float *ms, int *n_builds /* or NULL */);
+
 /* One-shot convenience == OptimizeTrajectory for B trajectories. */
 int dftpav_solve_batch(dftpav_handle *h, const dftpav_layout *layout, int B,
                        const dftpav_batch_data *d, double *x, double *final_cost,

@@ -24,6 +24,10 @@
 // oracle_kino_search_field is the same search with an optional goal field per query (dftpav_set_search_heuristic; the fields are
 // the caller's, from oracle_goalfield/): getHeu's two call sites take fmax(getHeu, (double)F[cell] * unit), the term of
 // kino_astar.cpp:247's commented-out getObsHeu line.  Without a field every statement is the one oracle_kino_search runs.
+//
+// oracle_kino_search_heu is that entry plus an optional Reeds-Shepp cost-to-go table (dftpav_set_search_rs_heuristic; the table is
+// the caller's, from oracle_rs_table below): the heuristic becomes the maximum of the above and scale * the table's entry nearest
+// the state as seen from the goal (RsTable::slot).  oracle_rs_table fills such a table through rs::Solver<TM<order>>.
 #include <algorithm>
 #include <array>
 #include <cmath>
@@ -85,6 +89,37 @@ struct KeyHash { // matrix_hash, kino_astar.h:75-85 (any hash gives the same fin
   }
 };
 
+// The Reeds-Shepp cost-to-go table: `headings` slices of `side` x `side` poses around a goal at the origin heading along +x.
+// Slice a, row b, column c is the pose ((c - reach) * pitch, (b - reach) * pitch, a * turn).
+struct RsTable {
+  const double *cost = nullptr;
+  int headings = 0, reach = 0, side = 0;
+  double pitch = 0.0, turn = 0.0, weight = 0.0;
+  void shape(int n_yaw, double extent, double cell) {
+    headings = n_yaw;
+    reach = (int)std::ceil(extent / cell);
+    side = reach + reach + 1;
+    pitch = cell;
+    turn = 2.0 * M_PI / (double)n_yaw;
+  }
+  // where a pose is filed, seen from a goal whose heading has cosine gc and sine gs: the flat offset, or -1 for a pose the table
+  // does not cover (a NaN covers nothing)
+  long long slot(const double *pose, const double *goal, double gc, double gs) const {
+    const double ex = pose[0] - goal[0], ey = pose[1] - goal[1];
+    const double ahead = gc * ex + gs * ey;   // along the goal's heading
+    const double aside = gc * ey - gs * ex;   // to its left
+    const double col = std::round(ahead / pitch) + (double)reach;
+    const double row = std::round(aside / pitch) + (double)reach;
+    const bool covered = col >= 0.0 && col < (double)side && row >= 0.0 && row < (double)side;
+    if (!covered) return -1;
+    const double steps = std::round((pose[2] - goal[2]) / turn);
+    if (!(std::fabs(steps) < 9.0e18)) return -1;
+    long long a = (long long)steps % (long long)headings;
+    if (a < 0) a += headings;
+    return (a * side + (long long)row) * side + (long long)col;
+  }
+};
+
 struct Grid {
   const unsigned char *data;
   int sx, sy;
@@ -108,6 +143,8 @@ template <int O> struct KinoAstar {
   double resolution_, inv_yaw_resolution_, origin_[2], map_size_3d_[2], max_steer_, yaw_origin_ = -kPi;
   const int *field_ = nullptr; // the goal field of this query's goal [sy][sx], or none
   double unit_ = 0.0;
+  RsTable rs_;                       // the Reeds-Shepp table, or none (cost == nullptr)
+  double goal_c_ = 1.0, goal_s_ = 0.0; // cos / sin of the goal's heading, set by search() when there is a table
 
   KinoAstar(const dftpav_search_params &p, const Grid &grid) : P(p), g(grid) { // init, kino_astar.cpp:372-442
     storage.resize(P.allocate_num);
@@ -179,14 +216,23 @@ template <int O> struct KinoAstar {
   // where the field did not reach
   double heu(const double *x1, const double *x2) const {
     const double e = getHeu(x1, x2);
+    if (rs_.cost) {
+      double m = e;
+      if (field_) m = std::fmax(m, fieldTerm(x1));
+      const long long at = rs_.slot(x1, x2, goal_c_, goal_s_);
+      return std::fmax(m, at < 0 ? 0.0 : rs_.weight * rs_.cost[at]);
+    }
     if (!field_) return e;
+    return std::fmax(e, fieldTerm(x1));
+  }
+  double fieldTerm(const double *x1) const {
     const double cx = std::round((x1[0] - g.ox) / g.res), cy = std::round((x1[1] - g.oy) / g.res);
     double hobs = 0.0;
     if (cx >= 0.0 && cx < (double)g.sx && cy >= 0.0 && cy < (double)g.sy) {
       const int v = field_[(size_t)(int)cx + (size_t)g.sx * (size_t)(int)cy];
       if (v != 0x7fffffff) hobs = (double)v * unit_;
     }
-    return std::fmax(e, hobs);
+    return hobs;
   }
   void posToIndex(const double *pt, int *idx) const { // kino_astar.cpp:804-809
     idx[0] = std::round((pt[0] - origin_[0]) / resolution_);
@@ -258,6 +304,10 @@ template <int O> struct KinoAstar {
     if (collides(end_state)) return NO_PATH;   // :48-52
     std::memcpy(start_state_, start_state, sizeof start_state_);
     std::memcpy(end_state_, end_state, sizeof end_state_);
+    if (rs_.cost) {
+      goal_c_ = M::cos(end_state[2]);
+      goal_s_ = M::sin(end_state[2]);
+    }
     PathNode *cur_node = path_node_pool_[0]; // :59-76
     cur_node->parent = nullptr;
     std::memcpy(cur_node->state, start_state, 3 * sizeof(double));
@@ -417,7 +467,8 @@ template <int O> struct KinoAstar {
 
 template <int O>
 void run_queries(const Grid &g, const dftpav_search_params &P, const double *start, const double *end, int n, int nthreads,
-                 const dftpav_search_out &out, const int *fields = nullptr, const int *field_of = nullptr, double unit = 0.0) {
+                 const dftpav_search_out &out, const int *fields = nullptr, const int *field_of = nullptr, double unit = 0.0,
+                 const RsTable *rs = nullptr) {
 #pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads)
   for (int q = 0; q < n; q++) {
     KinoAstar<O> ka(P, g);
@@ -425,6 +476,7 @@ void run_queries(const Grid &g, const dftpav_search_params &P, const double *sta
       ka.field_ = fields + (size_t)field_of[q] * g.sx * g.sy;
       ka.unit_ = unit;
     }
+    if (rs && rs->cost) ka.rs_ = *rs;
     const double *st = start + 4 * (size_t)q, *en = end + 4 * (size_t)q;
     // getKinoPath, traj_manager.cpp:79-103
     ka.reset();
@@ -485,6 +537,54 @@ extern "C" void oracle_kino_search_field(const unsigned char *grid, int size_x, 
   if (order == 0) run_queries<0>(g, *sp, start_states, end_states, n, nthreads, *out, fields, field_of, unit);
   else if (order == 1) run_queries<1>(g, *sp, start_states, end_states, n, nthreads, *out, fields, field_of, unit);
   else run_queries<2>(g, *sp, start_states, end_states, n, nthreads, *out, fields, field_of, unit);
+}
+
+// the same with, besides, a Reeds-Shepp table rs_tab [n_yaw][n][n] of (extent, cell) weighted by scale; rs_tab == NULL: none
+extern "C" void oracle_kino_search_heu(const unsigned char *grid, int size_x, int size_y, double resolution, double origin_x,
+                                       double origin_y, const dftpav_search_params *sp, const double *start_states,
+                                       const double *end_states, int n, int order, int nthreads, const dftpav_search_out *out,
+                                       const int *fields, const int *field_of, double unit, const double *rs_tab, int n_yaw,
+                                       double extent, double cell, double scale) {
+  const Grid g{grid, size_x, size_y, resolution, origin_x, origin_y};
+  if (nthreads < 1) nthreads = 1;
+  RsTable rs;
+  if (rs_tab) {
+    rs.shape(n_yaw, extent, cell);
+    rs.cost = rs_tab;
+    rs.weight = scale;
+  }
+  if (order == 0) run_queries<0>(g, *sp, start_states, end_states, n, nthreads, *out, fields, field_of, unit, &rs);
+  else if (order == 1) run_queries<1>(g, *sp, start_states, end_states, n, nthreads, *out, fields, field_of, unit, &rs);
+  else run_queries<2>(g, *sp, start_states, end_states, n, nthreads, *out, fields, field_of, unit, &rs);
+}
+
+// the table itself: out [n_yaw][n][n], entry (k, j, i) = rho * the normalised length of the shortest Reeds-Shepp path from
+// ((i - half) cell, (j - half) cell, k dth) to the origin heading along +x -- is_shot_sucess's `len` for that pair of poses
+template <int O> static void fill_rs_table(double rho, const RsTable &t, double *out) {
+  const double goal[3] = {0.0, 0.0, 0.0};
+  for (int a = 0; a < t.headings; a++)
+    for (int b = 0; b < t.side; b++)
+      for (int c = 0; c < t.side; c++) {
+        const double pose[3] = {(double)(c - t.reach) * t.pitch, (double)(b - t.reach) * t.pitch, (double)a * t.turn};
+        out[((size_t)a * t.side + b) * t.side + c] = rho * dftpav::rs::Solver<TM<O>>::between(pose, goal, rho).total;
+      }
+}
+extern "C" void oracle_rs_table(int order, double rho, int n_yaw, double extent, double cell, double *out) {
+  RsTable t;
+  t.shape(n_yaw, extent, cell);
+  if (order == 0) fill_rs_table<0>(rho, t, out);
+  else if (order == 1) fill_rs_table<1>(rho, t, out);
+  else fill_rs_table<2>(rho, t, out);
+}
+
+// RsTable::slot for m poses [m][3] seen from `goal` [3]: the flat offset of each, or -1 (the lookup rule, for its own test)
+extern "C" void oracle_rs_slot(int order, int n_yaw, double extent, double cell, const double *goal, const double *poses, int m,
+                               long long *slot) {
+  RsTable t;
+  t.shape(n_yaw, extent, cell);
+  const step_trig::Trig tr{order};
+  const double gc = tr.cos(goal[2]), gs = tr.sin(goal[2]);
+  for (int p = 0; p < m; p++) slot[p] = t.slot(poses + 3 * (size_t)p, goal, gc, gs);
 }
 
 // stateTransit of one order, for checking every returned node against its parent and input
