@@ -202,55 +202,63 @@ __device__ __forceinline__ void q4_unsplit(const double (&X)[6], const double (&
     bq[2 * r + 1] = nb_dpp<0x128>(lo ? Y[r] : X[r]); // this piece's dimension 1, from the lane eight around the row
   }
 }
+// The traversal: the first end block, seven interior steps on the first set, seven on the second, the last end block.  The two end
+// blocks (24 table reads and a test per coefficient each) stand outside the loops, so a loop's body is one interior step and nothing
+// else: 55-64 instructions where the loop that also held the end block had 78-104 per interior step (profiles/sweep_step_static.txt).
 template <int Q>
 __device__ __forceinline__ void sweep4_split(ldscd_t tab, double (&X)[6], double (&Y)[6], int l) {
   constexpr bool DESC = Q == 1 || Q == 3, DIV = Q == 1 || Q == 2;
   constexpr int N = 16;
   ldscd_t ip = tab + 48;
   const int l8 = l & 7;
-  // eight steps of the traversal on one set: pieces p0, p0 + dp, ...; first: the rows the first step starts from
-  auto phase = [&](double (&R)[6], int s0, const double (&first)[6]) {
-    // the table of this lane's own block of the set (an interior block: pk_size(Q) doubles), read once
+  // the previous block's six results, in traversal order: the neighbour lane's rows of the same set
+  auto fetch = [&](const double (&R)[6], double (&w)[6]) {
+#pragma unroll
+    for (int r = 0; r < 6; r++) w[r] = DESC ? nb_dpp<0x101>(R[5 - r]) : nb_dpp<0x111>(R[r]);
+  };
+  // a block of the ends (step 0 and step N - 1 of the traversal, outside the loops): every coefficient is tested, as the reference
+  // does (`if (a != 0.0)`).  For the owner lanes only (the caller's branch).
+  auto end_step = [&](double (&R)[6], double (&w)[6], ldscv2_t a) {
+    // the block's six table rows, requested together in front of the first row (one wait, not one per row)
+    v2d_t cb[6][4];
+#pragma unroll
+    for (int r = 0; r < 6; r++)
+#pragma unroll
+      for (int u = 0; u < (DIV ? 4 : 3); u++) cb[r][u] = a[4 * r + u];
+    asm volatile("" ::: "memory"); // (keeps the reads ahead of the arithmetic)
+#pragma unroll
+    for (int r = 0; r < 6; r++) {
+      const v2d_t(&ce)[4] = cb[r];
+      const int rr = DESC ? 5 - r : r;
+      double acc = R[rr];
+#pragma unroll
+      for (int k = 0; k < 6; k++) {
+        const double ck = (k & 1) ? ce[k >> 1].y : ce[k >> 1].x;
+        const double t = ck * w[(r + k) % 6];
+        acc = ck != 0.0 ? acc - t : acc;
+      }
+      if (DIV) acc = div_by_rcp(acc, ce[3].x, ce[3].y);
+      w[r] = acc;
+      R[rr] = acc;
+    }
+  };
+  // the seven interior steps s1 .. s1 + 6 of one set: the non-zero terms only, no test.  w: what step s1 starts from; on return,
+  // what the step behind the last one starts from (each step ends by fetching for the next)
+  auto interior = [&](double (&R)[6], int s1, double (&w)[6]) {
+    // the table of this lane's own block of the set (pk_size(Q) doubles), read once
     v2d_t c[pk_size(Q) / 2];
     {
-      const int sl = s0 + (DESC ? 7 - l8 : l8); // the step this lane's block of the set is taken in
+      const int sl = (s1 & 8) + (DESC ? 7 - l8 : l8); // the step this lane's block of the set is taken in
       const int bi = sl >= 1 && sl <= N - 2 ? sl - 1 : 0;
       const ldscv2_t a = (ldscv2_t)(ip + bi * pk_size(Q));
 #pragma unroll
       for (int u = 0; u < pk_size(Q) / 2; u++) c[u] = a[u];
     }
+    auto at = [&](int o) { return (o & 1) ? c[o >> 1].y : c[o >> 1].x; };
 #pragma unroll 1
-    for (int s = s0; s < s0 + 8; s++) {
-      const int p8 = (DESC ? N - 1 - s : s) & 7;
-      double w[6];
-#pragma unroll
-      for (int r = 0; r < 6; r++) w[r] = DESC ? nb_dpp<0x101>(R[5 - r]) : nb_dpp<0x111>(R[r]);
-      if (s == s0) { // (uniform)
-#pragma unroll
-        for (int r = 0; r < 6; r++) w[r] = first[r];
-      }
-      if (l8 != p8) continue;
-      if (s == 0 || s == N - 1) { // a block of the ends: every coefficient is tested, as the reference does (`if (a != 0.0)`)
-        const ldscv2_t a = (ldscv2_t)(s == 0 ? tab : ip + (N - 2) * pk_size(Q));
-#pragma unroll
-        for (int r = 0; r < 6; r++) {
-          v2d_t ce[4];
-#pragma unroll
-          for (int u = 0; u < 4; u++) ce[u] = a[4 * r + u];
-          const int rr = DESC ? 5 - r : r;
-          double acc = R[rr];
-#pragma unroll
-          for (int k = 0; k < 6; k++) {
-            const double ck = (k & 1) ? ce[k >> 1].y : ce[k >> 1].x;
-            const double t = ck * w[(r + k) % 6];
-            acc = ck != 0.0 ? acc - t : acc;
-          }
-          if (DIV) acc = div_by_rcp(acc, ce[3].x, ce[3].y);
-          w[r] = acc;
-          R[rr] = acc;
-        }
-      } else { // an interior block: the non-zero terms only, no test
-        auto at = [&](int o) { return (o & 1) ? c[o >> 1].y : c[o >> 1].x; };
+    for (int s = s1; s < s1 + 7; s++) {
+      const bool own = l8 == ((DESC ? N - 1 - s : s) & 7);
+      if (own) {
 #pragma unroll
         for (int r = 0; r < 6; r++) {
           const int rr = DESC ? 5 - r : r;
@@ -263,21 +271,22 @@ __device__ __forceinline__ void sweep4_split(ldscd_t tab, double (&X)[6], double
           R[rr] = acc;
         }
       }
+      fetch(R, w);
     }
   };
-  const double zeros[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  double mid[6]; // what the ninth step starts from: the eighth block's results, from the other set one lane around the row
-  if (!DESC) {
-    phase(X, 0, zeros);
+  double (&A)[6] = DESC ? Y : X; // the set of the traversal's first eight blocks
+  double (&B)[6] = DESC ? X : Y; // and of its last eight
+  double w[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}; // the traversal starts from six zeros
+  if (l8 == (DESC ? 7 : 0)) end_step(A, w, (ldscv2_t)tab);
+  fetch(A, w);
+  interior(A, 1, w);
+  // the ninth step starts from the eighth block's results: the other set, one lane around the row
 #pragma unroll
-    for (int r = 0; r < 6; r++) mid[r] = nb_dpp<0x121>(X[r]); // lane 8 <- lane 7 (piece 7, dimension 0), lane 0 <- lane 15 (piece 7, dimension 1)
-    phase(Y, 8, mid);
-  } else {
-    phase(Y, 0, zeros);
-#pragma unroll
-    for (int r = 0; r < 6; r++) mid[r] = nb_dpp<0x12F>(Y[5 - r]); // lane 7 <- lane 8 (piece 8, dimension 0), lane 15 <- lane 0 (piece 8, dimension 1)
-    phase(X, 8, mid);
-  }
+  for (int r = 0; r < 6; r++)
+    w[r] = DESC ? nb_dpp<0x12F>(A[5 - r])  // lane 7 <- lane 8 (piece 8, dimension 0), lane 15 <- lane 0 (piece 8, dimension 1)
+                : nb_dpp<0x121>(A[r]);     // lane 8 <- lane 7 (piece 7, dimension 0), lane 0 <- lane 15 (piece 7, dimension 1)
+  interior(B, 8, w);
+  if (l8 == (DESC ? 0 : 7)) end_step(B, w, (ldscv2_t)(ip + (N - 2) * pk_size(Q)));
 }
 
 // ------------------------------------------------ costFunctionCallback (traj_optimizer.cpp:206-350), one gear segment
