@@ -17,7 +17,8 @@
 //     s1 += step of :513 is a register), and what an active term adds to gdC goes straight into the lane's own gdC registers --
 //     the order a gdC entry receives its additions in is (point, term) order within the piece, which is all the reference's order
 //     says about it.  No 16-double records, no chain pass.  Only what the term adds to the segment's gdT and to the two costs
-//     (three doubles) is parked, per piece, and chained afterwards over the pieces in order.  The active terms themselves are
+//     (three doubles) is parked -- in one pool per trajectory, in arrival order -- and chained afterwards in (piece, point, term)
+//     order through a permutation of the pool's slots (q4_eval: the chain pass).  The active terms themselves are
 //     EVALUATED densely packed: listed by the lanes that find them, taken 24 at a time one per lane, their results handed back to
 //     the owners through LDS in list order (quad_common.h: DenseLds; q4_eval: flush);
 //   * the corridor is read from a copy laid out [component][j][piece]: the 16 lanes of a row read 128 contiguous bytes; a batch whose
@@ -33,8 +34,8 @@
 //
 // Residency: ONE wave per SIMD (the kernel takes 460 registers; built for two waves per SIMD it spilled 205 of them and its scratch
 // traffic alone was HBM-sized), four waves = 16 trajectories per CU (8 in the WAVE shape), each wave at the speed of a wave that has
-// its SIMD to itself; 5.7 KB of LDS per trajectory (x, g, the boundary states, the scalars of the line search, alpha[mem], the first
-// seven parked terms of every piece) and 3.9 KB per wave for the list of active terms, workgroups of one wave with a copy of the sweep
+// its SIMD to itself; 4.6 KB of LDS per trajectory (x, g, the boundary states, the scalars of the line search, alpha[mem], a pool
+// of 64 parked terms and its permutation) and 3.9 KB per wave for the list of active terms, workgroups of one wave with a copy of the sweep
 // tables each (39 KB; a wave that has nothing
 // left to do frees its slot at once).  Scheduling as the WAVE shape: the rows pop trajectories from the batch's ring, run them a
 // slice of evaluations and push them back unfinished, so that a wave's rows stay filled until the batch runs out.
@@ -49,7 +50,12 @@
 namespace dftpav {
 namespace reford {
 
-constexpr int kQLcap = 7; // parked terms of a piece kept in LDS (the rest in global scratch)
+// Parked terms of a trajectory kept in LDS, in one pool filled in arrival order (the rest in global scratch).  A slot's number is a
+// bit of a lane's 64-bit mask and a byte of the row's permutation table.
+constexpr int kQPool = 64;
+static_assert(kQPool <= 64 && kQPool % 8 == 0, "a lane's pool slots are the bits of a 64-bit mask; the chain pass reads the permutation eight bytes at a time");
+typedef unsigned char __attribute__((address_space(3))) *ldsb_t;
+typedef const unsigned long long __attribute__((address_space(3))) *ldscu64_t;
 // Waves per SIMD the kernel is built for.  At 2 (256 registers) it spills 205 of them and its scratch traffic alone is HBM-sized
 // (measured: the point loop 3 x slower than at 1); at 1 the allocator takes 455 registers, nothing goes to scratch, and four waves
 // per CU hold 16 trajectories -- twice the WAVE shape's 8 -- each of them at the speed of a wave that has its SIMD to itself.
@@ -65,12 +71,12 @@ struct Q4 {
   ldsd_t tw;      // [6] 1 / t^k of the piece duration of the evaluation in progress
   ldsd_t st;      // [sNUM]
   ldsd_t alpha;   // [mem]
-  ldsd_t tl;      // [16][kQLcap][3] parked terms of a piece: what they add to gdT, to the corridor cost, to the feasibility cost
+  ldsd_t pool;    // [kQPool][3] parked terms in arrival order: what they add to gdT, to the corridor cost, to the feasibility cost
+  ldsb_t perm;    // [kQPool] the pool slots in (piece, point, term) order, a byte each
   ldsi_t ist;     // [iNUM]
-  ldsi_t tcnt;    // [16] parked terms of a piece
 };
-__host__ __device__ inline size_t q4_team_doubles(int mem) { return 32 + 32 + 12 + 6 + sNUM + (size_t)mem + 16 * kQLcap * 3; }
-__host__ __device__ inline size_t q4_team_bytes(int mem) { return (q4_team_doubles(mem) * sizeof(double) + (iNUM + 16) * sizeof(int) + 15) & ~(size_t)15; }
+__host__ __device__ inline size_t q4_team_doubles(int mem) { return 32 + 32 + 12 + 6 + sNUM + (size_t)mem + kQPool * 3 + kQPool / 8; }
+__host__ __device__ inline size_t q4_team_bytes(int mem) { return (q4_team_doubles(mem) * sizeof(double) + iNUM * sizeof(int) + 15) & ~(size_t)15; }
 __host__ __device__ inline size_t q4_shared_bytes(int N) { return ((size_t)pk_segment_doubles(N) * sizeof(double) + 15) & ~(size_t)15; }
 __device__ inline void q4_carve(Q4 &q, char *team, int mem) {
   ldsd_t p = (ldsd_t)reinterpret_cast<double *>(team);
@@ -80,10 +86,9 @@ __device__ inline void q4_carve(Q4 &q, char *team, int mem) {
   q.tw = p; p += 6;
   q.st = p; p += sNUM;
   q.alpha = p; p += mem;
-  q.tl = p; p += 16 * kQLcap * 3;
-  ldsi_t i = (ldsi_t)p;
-  q.ist = i; i += iNUM;
-  q.tcnt = i;
+  q.pool = p; p += kQPool * 3;
+  q.perm = (ldsb_t)p; p += kQPool / 8;
+  q.ist = (ldsi_t)p;
 }
 
 // 0.0 + p[0] + p[1] + ... + p[n-1] for a vector held as (element l, element 16 + l); elements from n on contribute -0.0, and
@@ -406,7 +411,9 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
   const double step = t1 / Kl;
   const int singul_ = L.singuls[0];
   double s1 = 0.0;
-  int cnt = 0;
+  int cnt = 0;                     // parked terms of this lane's piece
+  int rcnt = 0;                    // parked terms of the row so far (the same in its sixteen lanes): the next pool slot
+  unsigned long long pmask = 0ull; // the pool slots that hold terms of this lane's piece
   const gd_t ovf_l = ovf + (size_t)pt0 * nterm * 3;
   // a round's half-planes are requested one round ahead (the copy holds zeros where a piece has no such point: every lane
   // loads, whatever its piece): 33 rounds of a dependent HBM round trip each were 3/4 of this kernel's time
@@ -420,14 +427,17 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
   // next round's, requested a few hundred instructions earlier: the request ahead bought half a round instead of a whole one)
   __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0)
   // what an active term adds: to the lane's gdC in place, to gdT and to its cost parked (the other cost gets -0.0: x + (-0.0) == x)
-  auto take = [&](const double (&r12)[12], double e0, double e1, double e2) {
+  // slot: the term's number among its row's terms in arrival order -- (round, lane, term) order, so a piece's slots ascend in (point,
+  // term) order, and its terms in the pool all arrive before its terms beyond it (those go to the piece's own place in global scratch)
+  auto take = [&](const double (&r12)[12], double e0, double e1, double e2, int slot) {
 #pragma unroll
     for (int u = 0; u < 12; u++) gdC[u] += r12[u];
-    if (cnt < kQLcap) {
-      ldsd_t e = q.tl + (l * kQLcap + cnt) * 3;
+    if (slot < kQPool) {
+      ldsd_t e = q.pool + slot * 3;
       e[0] = e0;
       e[1] = e1;
       e[2] = e2;
+      pmask |= 1ull << slot;
     } else {
       gd_t e = ovf_l + (size_t)cnt * 3;
       e[0] = e0;
@@ -447,12 +457,14 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
   const int rank = ((my_row > 0 ? row_here[0] : 0) + (my_row > 1 ? row_here[1] : 0) + (my_row > 2 ? row_here[2] : 0)) * 16 + l; // among the lanes here
   const int n_here = 16 * (row_here[0] + row_here[1] + row_here[2] + row_here[3]);
   // inclusive prefix sum of c over the lanes that are here, and its total (wave_incl_scan_i32 wants all 64 lanes)
-  auto scan_here = [&](int c, int &total) {
+  // (row_incl: the prefix within the lane's own row, which numbers the pool slots of a round taken in place)
+  auto scan_here = [&](int c, int &total, int &row_incl) {
     int v = c;
     v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);
     v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);
     v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);
     v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);
+    row_incl = v;
     const int t0_ = row_here[0] ? __builtin_amdgcn_readlane(v, 15) : 0, t1_ = row_here[1] ? __builtin_amdgcn_readlane(v, 31) : 0;
     const int t2_ = row_here[2] ? __builtin_amdgcn_readlane(v, 47) : 0, t3_ = row_here[3] ? __builtin_amdgcn_readlane(v, 63) : 0;
     total = t0_ + t1_ + t2_ + t3_;
@@ -490,6 +502,13 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
     }
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    // the list's slots that hold terms of this lane's ROW (an OR around the row): list order is arrival order, so an entry's pool
+    // slot is the row's count plus the row's entries in front of it
+    unsigned rowm = mine;
+    rowm |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)rowm, 0x121, 0xf, 0xf, false);
+    rowm |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)rowm, 0x122, 0xf, 0xf, false);
+    rowm |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)rowm, 0x124, 0xf, 0xf, false);
+    rowm |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)rowm, 0x128, 0xf, 0xf, false);
     for (unsigned mm = mine; mm;) { // the owner adds its terms in list order: (point, term) order
       const int i = __builtin_ctz(mm);
       mm &= mm - 1;
@@ -497,8 +516,9 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
       double r12[12];
 #pragma unroll
       for (int u = 0; u < 12; u++) r12[u] = w[u];
-      take(r12, w[12], w[13], w[14]);
+      take(r12, w[12], w[13], w[14], rcnt + __builtin_popcount(rowm & ((1u << i) - 1u)));
     }
+    rcnt += __builtin_popcount(rowm);
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); // the list is written again below
     listed = 0;
     mine = 0u;
@@ -546,8 +566,8 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
     bool in_place = false;
     const int c = __builtin_popcount(m);
     const bool any = __builtin_amdgcn_ballot_w64(c != 0) != 0ull; // (uniform) some point of this round has active terms
-    int incl = 0, total = 0;
-    if (any) incl = scan_here(c, total);
+    int incl = 0, total = 0, row_incl = 0;
+    if (any) incl = scan_here(c, total, row_incl);
     // the list is emptied when this round's terms do not fit behind what it holds, and by the extra round
     if (listed > 0 && (extra || listed + total > kDense)) flush(); // (uniform)
     if (any && total > kDense) { // (uniform, rare) more than a list's worth in one round: in place, behind the earlier points' terms
@@ -576,7 +596,9 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
       }
       listed += total;
     }
-    if (in_place) {
+    if (in_place) { // (the list is empty here: the row's count is up to date)
+      int slot = rcnt + row_incl - c;
+      rcnt += __builtin_amdgcn_update_dpp(0, row_incl, 0x15F, 0xf, 0xf, false); // the row's terms of this round (lane 15's prefix)
       for (unsigned mm = m; mm;) {
         const int t = __builtin_ctz(mm);
         mm &= mm - 1;
@@ -586,7 +608,7 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
         double r12[12];
 #pragma unroll
         for (int u = 0; u < 12; u++) r12[u] = r_[u];
-        take(r12, r_[12], corr ? r_[13] : -0.0, corr ? -0.0 : r_[13]);
+        take(r12, r_[12], corr ? r_[13] : -0.0, corr ? -0.0 : r_[13], slot++);
       }
     }
 #ifdef DFTPAV_PROF_EMIT_CYCLES
@@ -599,8 +621,7 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
       for (int u = 0; u < 20; u++) pl[u] = nx[u];
     }
   }
-  q.tcnt[l] = piece ? cnt : 0;
-  __threadfence_block(); // parked terms beyond the LDS window went to global memory; the counts are read by the other lanes
+  __threadfence_block(); // the parked terms are read by the other lanes of the row: the pool, and what went beyond it to global memory
   pr.tick(2);
   // ---- the per-segment chains: `gdT +=`, `energy +=` over the pieces in order from 0.0, then the parked terms in (piece, point,
   // term) order (every lane of the row forms them for itself: the same bits)
@@ -610,31 +631,69 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
   // (round 6, measured and taken out: the first three terms of a piece kept in the lane's registers and chained by DPP when no piece of the
   // row has more -- on this workload a piece that has terms has more than three)
   {
-    int total = 0;
-    for (int p = 0; p < N; p++) total += q.tcnt[p];
+    // a piece's start in (piece, point, term) order: the prefix sum of the counts along the row; lane 15's is the row's total
+    const int pc = piece ? cnt : 0;
+    int incl = pc;
+    incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xf, 0xf, false);
+    incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xf, 0xf, false);
+    incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xf, 0xf, false);
+    incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xf, 0xf, false);
+    const int total = __builtin_amdgcn_update_dpp(0, incl, 0x15F, 0xf, 0xf, false);
     pr.count(9, total);
-    if (total > 0) {
+    int kmax = 0; // (uniform) the largest total among the rows of the wave
+#pragma unroll
+    for (int r = 0; r < 4; r++)
+      if (row_here[r]) kmax = max(kmax, __builtin_amdgcn_readlane(incl, 16 * r + 15));
+    // a row's terms are all in its pool unless it has more than the pool holds
+    const bool slow = kmax > kQPool; // (uniform)
+    if (D.prof != nullptr) pr.count(11, slow ? 1ll << 32 : 0ll); // (profiling only) evaluations on the slow path: the upper half of slot 11
+    if (kmax > 0 && !slow) {
+      // the row's permutation: its pool slots in chain order (a lane's slots ascend in (point, term) order)
+      {
+        int at = incl - pc;
+        for (unsigned long long mm = pmask; mm;) {
+          q.perm[at++] = (unsigned char)__builtin_ctzll(mm);
+          mm &= mm - 1;
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+      // eight terms at a time: their slots, then their 24 doubles with the reads in flight together, then the additions in order.
+      // The four rows of the wave run in step; what lies beyond a row's total adds -0.0 (x + (-0.0) == x for every x)
+      for (int k0 = 0; k0 < kmax; k0 += 8) {
+        const unsigned long long pb = *(ldscu64_t)(q.perm + k0);
+        double e[8][3];
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+          const int sl = k0 + u < total ? (int)((pb >> (8 * u)) & 255ull) : 0;
+#pragma unroll
+          for (int w = 0; w < 3; w++) e[u][w] = q.pool[sl * 3 + w];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+          const bool in = k0 + u < total;
+          gdT += in ? e[u][0] : -0.0;
+          cost0 += in ? e[u][1] : -0.0;
+          cost2 += in ? e[u][2] : -0.0;
+        }
+      }
+    } else if (slow) {
+      // some row of the wave overflowed its pool: piece by piece, a piece's pool entries in slot order, then its entries in global
+      // scratch in count order (they all arrived behind the pool's)
       for (int p = 0; p < N; p++) {
-        const int c = q.tcnt[p];
+        const int src = (lane64 & 48) | p; // the lane of this row that owns piece p
+        const int c = __shfl(pc, src);
         if (__builtin_amdgcn_ballot_w64(c != 0) == 0ull) continue; // (uniform: no row of this wave has a term in this piece)
+        const unsigned long long pm = ((unsigned long long)(unsigned)__shfl((int)(pmask >> 32), src) << 32) | (unsigned)__shfl((int)pmask, src);
+        for (unsigned long long mm = pm; mm;) {
+          ldscd_t e = q.pool + __builtin_ctzll(mm) * 3;
+          mm &= mm - 1;
+          gdT += e[0];
+          cost0 += e[1];
+          cost2 += e[2];
+        }
         const int pp0 = p == 0 ? 0 : (L.Kd + 1) + (p - 1) * (L.K + 1);
         const gcd_t og = (gcd_t)(ovf + (size_t)pp0 * nterm * 3);
-        // the piece's LDS window in one go (the eight entries' reads go out together; what lies beyond the piece's count adds -0.0),
-        // the four rows of the wave in step: a loop over the count would run each row's trips one after the other
-        {
-          double e[kQLcap][3];
-#pragma unroll
-          for (int i = 0; i < kQLcap; i++)
-#pragma unroll
-            for (int w = 0; w < 3; w++) e[i][w] = q.tl[(p * kQLcap + i) * 3 + w];
-#pragma unroll
-          for (int i = 0; i < kQLcap; i++) {
-            gdT += i < c ? e[i][0] : -0.0;
-            cost0 += i < c ? e[i][1] : -0.0;
-            cost2 += i < c ? e[i][2] : -0.0;
-          }
-        }
-        for (int i0 = kQLcap; i0 < c; i0 += 8) { // beyond the LDS window: eight terms' loads in flight, then their additions in order
+        for (int i0 = __builtin_popcountll(pm); i0 < c; i0 += 8) { // eight terms' loads in flight, then their additions in order
           double e[8][3];
 #pragma unroll
           for (int u = 0; u < 8; u++) {

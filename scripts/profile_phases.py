@@ -21,8 +21,14 @@ for _ in range(3):
 bt.profile(True)
 bt.solve_async(); bt.sync(); ms1 = bt.last_solve_ms()
 r = bt.results()
-pr = bt.read_profile().astype(np.float64)
+pri = bt.read_profile()
 REF = os.environ.get("ORDER") == "ref"
+# the QUAD shape (solver_ref4.hip) counts in the upper half of slot 11 the evaluations whose parked-term chain took the slow path (a row
+# of the wave had more terms than its LDS pool holds); the lower half is the slot's own figure
+slow = (pri[:, 11] >> 32) if REF else np.zeros(len(pri), dtype=np.int64)
+if REF:
+    pri[:, 11] &= 0xffffffff
+pr = pri.astype(np.float64)
 # the reference-order kernel keeps COUNTS in some slots (solver_ref.hip): slot 9 = active terms (both launch shapes); in the WAVE
 # shape slots 10 / 11 = evaluations beyond the LDS window and their terms, in the TEAM shape they are cycles (numbering, the
 # window's list).  Counts are kept out of the cycle totals and printed under their own names.
@@ -51,6 +57,8 @@ if REF:
         big = pr[:, 10].sum()
         print("   evaluations with more terms than the LDS window holds:", round(float(100 * big / ev.sum()), 1), "% of all, with",
               round(float(pr[:, 11].sum() / max(1.0, big)), 1), "active terms on average")
+if REF and not wave_counts:
+    print("QUAD shape: evaluations on the slow path of the parked-term chain:", int(slow.sum()), "=", round(float(100 * slow.sum() / ev.sum()), 2), "% of all")
 print("two-loop cycles per history step (2 per entry per iteration):", round(float(np.median(pr[:, 8] / (2 * hs))), 1),
       " mean depth", round(float((hs / it).mean()), 1))
 print("solves/s (kernel)", B / (np.mean(ms0) * 1e-3))
