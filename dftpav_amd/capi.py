@@ -56,6 +56,7 @@ EXPORTS = [
     "dftpav_grid_distance_field", "dftpav_batch_check_clearance", "dftpav_planner_check_clearance", "dftpav_planner_set_clearance_filter",
     "dftpav_planner_last_clearance", "dftpav_clearance_last_ms",
     "dftpav_default_goal_field_params", "dftpav_set_search_heuristic", "dftpav_grid_goal_field", "dftpav_goal_field_last_ms",
+    "dftpav_goal_window", "dftpav_set_search_heuristic_window", "dftpav_grid_goal_field_windowed",
     "dftpav_default_rs_heuristic_params", "dftpav_set_search_rs_heuristic", "dftpav_rs_table", "dftpav_rs_table_last_ms",
 ]
 
@@ -225,6 +226,21 @@ def default_goal_field_params():
     fn.restype = None
     fn(C.byref(gp))
     return gp
+
+
+def goal_window(size_x, size_y, resolution, origin, start_xy, goal_xy, margin):
+    """dftpav_goal_window, pure host code: the window (X0, Y0, WX, WY) in cells of the goal field of a (start, goal) pair on a grid
+    of size_x x size_y cells -- the box of the two cells grown by ceil(margin / resolution), clipped to the grid and snapped outwards
+    to the field's tiles of 64 x 32 -- or None for a goal outside the grid (no field)"""
+    m = GridMap(None, int(size_x), int(size_y), float(resolution), float(origin[0]), float(origin[1]))
+    st, go = (C.c_double * 2)(*[float(v) for v in start_xy[:2]]), (C.c_double * 2)(*[float(v) for v in goal_xy[:2]])
+    win = (C.c_int * 4)()
+    fn = lib().dftpav_goal_window
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
+    rc = fn(C.byref(m), st, go, float(margin), win)
+    if rc < 0:
+        raise DftpavError(rc, "goal_window")
+    return tuple(int(v) for v in win) if rc else None
 
 
 class RsHeuristicParams(C.Structure):
@@ -495,6 +511,38 @@ class Handle:
         fn = lib().dftpav_set_search_heuristic
         fn.argtypes = [C.c_void_p, C.c_void_p]
         self._check(fn(self._h, C.byref(gp)), "set_search_heuristic")
+
+    def set_search_heuristic_window(self, margin):
+        """dftpav_set_search_heuristic_window: with set_search_heuristic on, every query's goal field is limited to goal_window of its
+        own start and goal with this margin in metres; margin < 0 (the default state of a handle): whole-map fields"""
+        fn = lib().dftpav_set_search_heuristic_window
+        fn.argtypes = [C.c_void_p, C.c_double]
+        self._check(fn(self._h, float(margin)), "set_search_heuristic_window")
+
+    def goal_field_windowed(self, starts_xy, goals_xy, inflate_radius=0.0, margin=0.0, fetch=True):
+        """dftpav_grid_goal_field_windowed: for starts and goals [n][2] (x, y) on the installed map, (windows int32 [n][4] (X0, Y0, WX,
+        WY), a list of n fields int32 [WY][WX], n_reached [n]): goal_field of the map cropped to each pair's window, blocked by the
+        whole map's inflation.  A goal outside the grid has the window (0, 0, 0, 0) and a field of shape (0, 0).  fetch=False: build
+        only, (windows, n_reached)"""
+        st = np.ascontiguousarray(starts_xy, dtype=np.float64).reshape(-1, 2)
+        xy = np.ascontiguousarray(goals_xy, dtype=np.float64).reshape(-1, 2)
+        if st.shape != xy.shape:
+            raise DftpavError(E_INVALID, "goal_field_windowed: as many starts as goals")
+        n = xy.shape[0]
+        fn = lib().dftpav_grid_goal_field_windowed
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        win, off, reached = np.zeros((n, 4), dtype=np.int32), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int32)
+        head = (self._h, st.ctypes.data_as(C.c_void_p), xy.ctypes.data_as(C.c_void_p), n, float(inflate_radius), float(margin),
+                win.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p))
+        if not fetch:
+            self._check(fn(*head, None, reached.ctypes.data_as(C.c_void_p)), "grid_goal_field_windowed")
+            return win, reached
+        self._check(fn(*head, None, None), "grid_goal_field_windowed")          # the sizes
+        sizes = win[:, 2].astype(np.int64) * win[:, 3]
+        packed = np.zeros(max(1, int(sizes.sum())), dtype=np.int32)
+        self._check(fn(*head, packed.ctypes.data_as(C.c_void_p), reached.ctypes.data_as(C.c_void_p)), "grid_goal_field_windowed")
+        fields = [packed[off[q]:off[q] + sizes[q]].reshape(win[q, 3], win[q, 2]) for q in range(n)]
+        return win, fields, reached
 
     def set_search_rs_heuristic(self, enabled=True, n_yaw=None, extent=None, cell=None, scale=None):
         """dftpav_set_search_rs_heuristic: kino_search, Planner.plan and Planner.tick also take the maximum with scale * the

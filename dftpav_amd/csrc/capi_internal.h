@@ -122,11 +122,14 @@ struct dftpav_handle {
   // the search heuristic (dftpav_set_search_heuristic) and the workspace of the goal fields (goalfield.hip): nothing of it is
   // allocated or launched until a call asks for a field
   dftpav_goal_field_params heu{0, 0.0, 0.0};
-  int *d_gf = nullptr;      // the fields of one turn [goals][cells], then their dirty maps [goals][tiles]
+  double heu_margin = -1.0; // dftpav_set_search_heuristic_window; < 0: whole-map fields.  Read only while heu.enabled
+  int *d_gf = nullptr;      // the fields of one turn [goals][cells], then their dirty maps [goals][tiles]; windowed: each field
+                            // [WY][WX] at its offset, then the dirty maps at the stride of the turn's largest
   size_t gf_ints = 0;
-  int *d_gf_meta = nullptr; // of a whole call: field_of [queries], goal cells [goals][2], n_reached [goals]
+  int *d_gf_meta = nullptr; // of a whole call: field_of [queries], goal cells [goals][2], (windowed: windows [goals][4], a pad to an
+                            // even count, offsets [goals] as 64-bit,) n_reached [goals]
   size_t gf_meta_ints = 0;
-  std::vector<int> gf_host; // the host copy of field_of | goal cells (the source of an asynchronous copy)
+  std::vector<int> gf_host; // the host copy of all of it but n_reached (the source of an asynchronous copy)
   std::vector<hipEvent_t> gf_ev; // a pair around every turn's build
   int gf_timed = 0;              // pairs recorded by the last call that built fields
   // the Reeds-Shepp term of the search heuristic (dftpav_set_search_rs_heuristic) and its table (rstable.hip): built in front of
@@ -268,6 +271,9 @@ struct CachedTable {
 // The goal fields of one call's queries (the heuristic on): which field each query reads and which cells are built, turn by turn.
 // A turn is one launch of the search over `per_turn` queries (the search's slots, or fewer where the workspace cap holds fewer
 // fields); its distinct goal cells are goals [turn_off[t], turn_off[t + 1]) and field_of is relative to the turn.
+// Windowed (dftpav_set_search_heuristic_window, dftpav_grid_goal_field_windowed): a field belongs to a (goal cell, window) pair,
+// win / off are every field's window and its offset in ints inside its turn's workspace, and a turn uses turn_ints[t] ints of
+// fields and a dirty map of turn_tiles[t] words per field behind them.
 struct GoalFieldPlan {
   int per_turn = 0, T = 0;
   std::vector<int> turn_off;
@@ -275,6 +281,13 @@ struct GoalFieldPlan {
   const int *d_field_of = nullptr, *d_cells = nullptr;
   int *d_reached = nullptr;
   double unit = 0.0;
+  bool windowed = false;
+  std::vector<int> win;       // [n_goals][4]
+  std::vector<long long> off; // [n_goals]
+  std::vector<size_t> turn_ints;
+  std::vector<int> turn_tiles;
+  const int *d_win = nullptr;
+  const long long *d_off = nullptr;
 };
 
 struct dftpav_planner {
@@ -401,11 +414,14 @@ constexpr double kClearanceVertexRes = 0.1;
 ClearanceCommon clearance_common(const dftpav_handle *h, const double *d_tab, int n_t, int n_v, double check_dt);
 // The goal fields of n goals (xy: their x, y at a stride of `stride` doubles), blocked by inflate_radius, planned in turns of at most
 // `slots` queries: the distance field is ensured, the workspace grown, field_of and the cells uploaded on the handle's stream.
-int goal_field_plan(dftpav_handle *h, const double *xy, int stride, int n, int slots, double inflate_radius, GoalFieldPlan &G);
+// margin >= 0: windowed, every query's field limited to dftpav_goal_window of its start (start_xy, at the same stride) and goal;
+// margin < 0: whole-map fields, and start_xy is not read.
+int goal_field_plan(dftpav_handle *h, const double *start_xy, const double *xy, int stride, int n, int slots, double inflate_radius,
+                    double margin, GoalFieldPlan &G);
 // builds turn t's fields on the handle's stream (nothing waits) and returns their base; with S, wires them into a search launch
 int goal_field_turn(dftpav_handle *h, const GoalFieldPlan &G, int t, SearchArgs *S, int **fields);
 // search_setup's slots with the heuristic: a plan for the queries' goals when it is on (G.per_turn replaces U.slots), nothing otherwise
-int search_heuristic_plan(dftpav_handle *h, const double *end_states, int n, SearchSetup &U, GoalFieldPlan &G);
+int search_heuristic_plan(dftpav_handle *h, const double *start_states, const double *end_states, int n, SearchSetup &U, GoalFieldPlan &G);
 // The Reeds-Shepp table.  rs_geometry: the checked geometry of a parameter set (DFTPAV_E_INVALID / _UNSUPPORTED as the header
 // says).  ensure_rs_table: the table of (rho, gp) on the device, built on the handle's stream if the handle holds another.
 // search_rs_plan: with the heuristic on, the table of the launch's rho wired into U.S; off, nothing.

@@ -252,7 +252,7 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
   SearchSetup U;
   if (int rc = search_setup(h, &pp->search, Q, U)) return rc;
   GoalFieldPlan G; // dftpav_set_search_heuristic; off: G.per_turn == 0 and nothing below differs
-  if (int rc = search_heuristic_plan(h, end_states, Q, U, G)) return rc;
+  if (int rc = search_heuristic_plan(h, start_states, end_states, Q, U, G)) return rc;
   const int R = p->R, MS = pp->max_seg, MP = pp->max_pieces;
   const int MST = (MP - 2) * (fp.traj_res + 1) + 2 * (fp.dense_traj_res + 1); // poses of a segment of max_pieces pieces
   // the two running sums of the collision re-check, tabulated (as dftpav_batch_validate): sample times | outline point spacing

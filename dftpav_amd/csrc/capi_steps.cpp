@@ -312,7 +312,7 @@ extern "C" int dftpav_kino_search(dftpav_handle *h, const dftpav_search_params *
   SearchSetup U;
   if (int rc = search_setup(h, sp, n, U)) return rc;
   GoalFieldPlan G; // dftpav_set_search_heuristic; off: G.per_turn == 0 and nothing below differs
-  if (int rc = search_heuristic_plan(h, end_states, n, U, G)) return rc;
+  if (int rc = search_heuristic_plan(h, start_states, end_states, n, U, G)) return rc;
   const size_t nn = (size_t)n, n_nodes = 6 * nn * out->max_nodes, n_paths = 3 * nn * out->max_path;
   double *d_tabs = nullptr, *d_st = nullptr, *d_en = nullptr, *d_nodes = nullptr, *d_paths = nullptr;
   int *d_ints = nullptr;
@@ -865,50 +865,130 @@ extern "C" int dftpav_solve_batch(dftpav_handle *h, const dftpav_layout *layout,
 }
 
 // ------------------------------------------------- the goal fields of the map and the search heuristic on them (goalfield.hip)
-// The fields of one turn share the handle's workspace: 2 GiB of fields at most (one field, whatever its size, always fits).
+// The fields of one turn share the handle's workspace: 2 GiB of fields at most (one field, whatever its size, always fits).  A turn
+// is a fixed range of queries, so what it may hold is decided by the call's largest field: the map's cells, or with windows the
+// cells of the call's largest window.
 static constexpr size_t kGoalFieldCapBytes = (size_t)2 << 30;
+static int goal_field_per_turn(int slots, size_t largest_cells) {
+  return (int)std::min<size_t>((size_t)slots, std::max<size_t>(1, kGoalFieldCapBytes / (sizeof(int) * std::max<size_t>(1, largest_cells))));
+}
 
-int dftpav::goal_field_plan(dftpav_handle *h, const double *xy, int stride, int n, int slots, double inflate_radius, GoalFieldPlan &G) {
+// the cell of a point by grid_occupied's rounding (footprint.h), as doubles; false: outside the grid (or NaN)
+static bool goal_field_cell(const dftpav_grid_map &m, const double *xy, double &cx, double &cy) {
+  cx = std::round((xy[0] - m.origin_x) / m.resolution);
+  cy = std::round((xy[1] - m.origin_y) / m.resolution);
+  return cx >= 0.0 && cx < (double)m.size_x && cy >= 0.0 && cy < (double)m.size_y;
+}
+
+extern "C" int dftpav_goal_window(const dftpav_grid_map *map_geometry, const double *start_xy, const double *goal_xy, double margin, int *win) {
+  if (!map_geometry || !start_xy || !goal_xy || !win) return DFTPAV_E_INVALID;
+  const dftpav_grid_map &m = *map_geometry;
+  if (m.size_x < 1 || m.size_y < 1 || !(m.resolution > 0.0) || !std::isfinite(m.resolution) || !std::isfinite(m.origin_x) ||
+      !std::isfinite(m.origin_y) || !(margin >= 0.0) || !std::isfinite(margin))
+    return DFTPAV_E_INVALID;
+  win[0] = win[1] = win[2] = win[3] = 0;
+  double gx, gy, sx, sy;
+  if (!goal_field_cell(m, goal_xy, gx, gy)) return 0; // seeds nothing: no window, no field
+  (void)goal_field_cell(m, start_xy, sx, sy);          // a start may lie outside the grid: clamped into it
+  sx = sx >= 0.0 ? std::min(sx, (double)(m.size_x - 1)) : 0.0;
+  sy = sy >= 0.0 ? std::min(sy, (double)(m.size_y - 1)) : 0.0;
+  const double md = std::ceil(margin / m.resolution);
+  const long long mc = md < 2147483648.0 ? (long long)md : 2147483648ll; // (beyond any grid)
+  const long long side[2] = {m.size_x, m.size_y}, tile[2] = {kGfTileX, kGfTileY};
+  const long long s[2] = {(long long)sx, (long long)sy}, g[2] = {(long long)gx, (long long)gy};
+  for (int k = 0; k < 2; k++) {
+    const long long lo = std::max(0ll, std::min(s[k], g[k]) - mc), hi = std::min(side[k] - 1, std::max(s[k], g[k]) + mc);
+    const long long c0 = lo / tile[k] * tile[k], c1 = std::min(side[k], (hi / tile[k] + 1) * tile[k]); // out to the field's tiles
+    win[k] = (int)c0;
+    win[2 + k] = (int)(c1 - c0);
+  }
+  return 1;
+}
+
+int dftpav::goal_field_plan(dftpav_handle *h, const double *start_xy, const double *xy, int stride, int n, int slots, double inflate_radius,
+                            double margin, GoalFieldPlan &G) {
   if (!h->d_cells) return DFTPAV_E_INVALID; // no map
   if (!(inflate_radius >= 0.0) || !std::isfinite(inflate_radius) || n < 1 || slots < 1) return DFTPAV_E_INVALID;
+  const bool windowed = margin >= 0.0;
+  if (windowed && (!start_xy || !std::isfinite(margin))) return DFTPAV_E_INVALID;
   if (int rc = ensure_dist_field(h)) return rc;
   const dftpav_grid_map &m = h->map;
   const size_t cells = (size_t)m.size_x * m.size_y;
   const int tiles_x = (m.size_x + kGfTileX - 1) / kGfTileX, tiles_y = (m.size_y + kGfTileY - 1) / kGfTileY;
   const size_t per_field = cells + (size_t)tiles_x * tiles_y;
   G = GoalFieldPlan{};
-  G.per_turn = (int)std::min<size_t>((size_t)slots, std::max<size_t>(1, kGoalFieldCapBytes / (sizeof(int) * cells)));
+  G.windowed = windowed;
+  // every query's window (windowed), and the largest of them: what a turn is sized by
+  std::vector<int> qwin;
+  size_t largest = cells;
+  if (windowed) {
+    qwin.assign(4 * (size_t)n, 0);
+    largest = 0;
+    for (int q = 0; q < n; q++) {
+      int *w = qwin.data() + 4 * (size_t)q;
+      if (dftpav_goal_window(&m, start_xy + (size_t)stride * q, xy + (size_t)stride * q, margin, w) < 0) return DFTPAV_E_INVALID;
+      largest = std::max(largest, (size_t)w[2] * (size_t)w[3]);
+    }
+  }
+  G.per_turn = goal_field_per_turn(slots, largest);
   // d2 <= T blocks; T stays below DFTPAV_DIST_FAR, what a map without an occupied cell holds everywhere
   const double t = std::floor(inflate_radius * inflate_radius / (m.resolution * m.resolution));
   G.T = t >= 2147483646.0 ? 2147483646 : (int)t;
-  // per turn: the distinct goal cells inside the grid, in the order of their first query
+  // per turn: the distinct goal cells inside the grid (windowed: the distinct pairs of goal cell and window), in the order of their
+  // first query
   std::vector<int> &H = h->gf_host;
   H.assign((size_t)n, -1);
   std::vector<int> cell_list;
   G.turn_off.assign(1, 0);
-  size_t most = 0;
+  size_t most = 0, want_ws = 1;
   for (int q0 = 0; q0 < n; q0 += G.per_turn) {
     const size_t base = cell_list.size() / 2;
+    size_t used = 0;
+    int turn_tiles = 0;
     for (int q = q0; q < std::min(n, q0 + G.per_turn); q++) {
-      const double cx = std::round((xy[(size_t)stride * q] - m.origin_x) / m.resolution),
-                   cy = std::round((xy[(size_t)stride * q + 1] - m.origin_y) / m.resolution); // (grid_occupied, footprint.h)
-      if (!(cx >= 0.0 && cx < (double)m.size_x && cy >= 0.0 && cy < (double)m.size_y)) continue; // seeds nothing: no field
+      double cx, cy;
+      if (!goal_field_cell(m, xy + (size_t)stride * q, cx, cy)) continue; // seeds nothing: no field
       const int ix = (int)cx, iy = (int)cy;
+      const int *w = windowed ? qwin.data() + 4 * (size_t)q : nullptr;
       size_t f = base;
-      while (f < cell_list.size() / 2 && (cell_list[2 * f] != ix || cell_list[2 * f + 1] != iy)) f++;
+      while (f < cell_list.size() / 2 &&
+             (cell_list[2 * f] != ix || cell_list[2 * f + 1] != iy || (w && !std::equal(w, w + 4, G.win.begin() + 4 * f))))
+        f++;
       if (f == cell_list.size() / 2) {
         cell_list.push_back(ix);
         cell_list.push_back(iy);
+        if (w) {
+          G.win.insert(G.win.end(), w, w + 4);
+          G.off.push_back((long long)used);
+          used += (size_t)w[2] * (size_t)w[3];
+          turn_tiles = std::max(turn_tiles, ((w[2] + kGfTileX - 1) / kGfTileX) * ((w[3] + kGfTileY - 1) / kGfTileY));
+        }
       }
       H[q] = (int)(f - base);
     }
     G.turn_off.push_back((int)(cell_list.size() / 2));
-    most = std::max(most, cell_list.size() / 2 - base);
+    const size_t ng = cell_list.size() / 2 - base;
+    most = std::max(most, ng);
+    if (windowed) {
+      G.turn_ints.push_back(used);
+      G.turn_tiles.push_back(turn_tiles);
+      want_ws = std::max(want_ws, used + ng * (size_t)turn_tiles);
+    }
   }
+  if (!windowed) want_ws = std::max<size_t>(1, most) * per_field;
   G.n_goals = cell_list.size() / 2;
   H.insert(H.end(), cell_list.begin(), cell_list.end());
+  size_t win_at = 0, off_at = 0;
+  if (windowed) {
+    win_at = H.size();
+    H.insert(H.end(), G.win.begin(), G.win.end());
+    if (H.size() % 2) H.push_back(0); // the offsets are 64-bit
+    off_at = H.size();
+    H.resize(H.size() + 2 * G.n_goals);
+    if (G.n_goals) std::memcpy(H.data() + off_at, G.off.data(), sizeof(long long) * G.n_goals);
+  }
   HIPCHK(h, hipSetDevice(h->device));
-  const size_t want_meta = H.size() + G.n_goals + 1, want_ws = std::max<size_t>(1, most) * per_field;
+  const size_t want_meta = H.size() + G.n_goals + 1;
   if (h->gf_meta_ints < want_meta || h->gf_ints < want_ws) HIPCHK(h, hipStreamSynchronize(h->stream)); // nothing in flight reads what is freed
   if (int rc = grow(h, h->d_gf_meta, h->gf_meta_ints, want_meta)) return rc;
   if (int rc = grow(h, h->d_gf, h->gf_ints, want_ws)) return rc;
@@ -923,6 +1003,10 @@ int dftpav::goal_field_plan(dftpav_handle *h, const double *xy, int stride, int 
   G.d_field_of = h->d_gf_meta;
   G.d_cells = h->d_gf_meta + n;
   G.d_reached = h->d_gf_meta + H.size();
+  if (windowed) {
+    G.d_win = h->d_gf_meta + win_at;
+    G.d_off = (const long long *)(h->d_gf_meta + off_at);
+  }
   return DFTPAV_OK;
 }
 
@@ -941,11 +1025,20 @@ int dftpav::goal_field_turn(dftpav_handle *h, const GoalFieldPlan &G, int t, Sea
   A.fields = h->d_gf;
   A.dirty = h->d_gf + (size_t)ng * cells;
   A.n_reached = G.d_reached + G.turn_off[t];
+  // what the fills cover: the turn's fields, and their dirty maps behind them
+  size_t field_ints = (size_t)ng * cells, dirty_ints = (size_t)ng * A.tiles_x * A.tiles_y;
+  if (G.windowed) {
+    A.window = G.d_win + 4 * (size_t)G.turn_off[t];
+    A.offset = G.d_off + G.turn_off[t];
+    A.dirty_stride = G.turn_tiles[t];
+    A.dirty = h->d_gf + G.turn_ints[t];
+    field_ints = G.turn_ints[t];
+    dirty_ints = (size_t)ng * G.turn_tiles[t];
+  }
   if (ng > 0) {
-    const size_t tiles = (size_t)A.tiles_x * A.tiles_y;
     HIPCHK(h, hipEventRecord(h->gf_ev[2 * (size_t)h->gf_timed], h->stream));
-    HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)A.fields, DFTPAV_FIELD_UNREACHED, (size_t)ng * cells, h->stream));
-    HIPCHK(h, hipMemsetAsync(A.dirty, 0, sizeof(int) * (size_t)ng * tiles, h->stream));
+    HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)A.fields, DFTPAV_FIELD_UNREACHED, field_ints, h->stream));
+    HIPCHK(h, hipMemsetAsync(A.dirty, 0, sizeof(int) * dirty_ints, h->stream));
     HIPCHK(h, launch_goal_fields(A, ng, h->stream));
     HIPCHK(h, hipEventRecord(h->gf_ev[2 * (size_t)h->gf_timed + 1], h->stream));
     h->gf_timed++;
@@ -954,16 +1047,19 @@ int dftpav::goal_field_turn(dftpav_handle *h, const GoalFieldPlan &G, int t, Sea
     S->fields = h->d_gf; // (queries of a turn without a goal inside the grid have field_of -1 and read nothing)
     S->field_of = G.d_field_of;
     S->unit = G.unit;
+    S->field_win = A.window; // (null without windows: the whole-map instance)
+    S->field_off = A.offset;
   }
   if (fields) *fields = h->d_gf;
   return DFTPAV_OK;
 }
 
-int dftpav::search_heuristic_plan(dftpav_handle *h, const double *end_states, int n, SearchSetup &U, GoalFieldPlan &G) {
+int dftpav::search_heuristic_plan(dftpav_handle *h, const double *start_states, const double *end_states, int n, SearchSetup &U,
+                                  GoalFieldPlan &G) {
   G = GoalFieldPlan{};
   if (int rc = search_rs_plan(h, U)) return rc; // dftpav_set_search_rs_heuristic; off: nothing
   if (!h->heu.enabled) return DFTPAV_OK;
-  if (int rc = goal_field_plan(h, end_states, 4, n, U.slots, h->heu.inflate_radius, G)) return rc;
+  if (int rc = goal_field_plan(h, start_states, end_states, 4, n, U.slots, h->heu.inflate_radius, h->heu_margin, G)) return rc;
   G.unit = h->heu.scale * h->map.resolution / 5.0;
   U.slots = G.per_turn;
   return DFTPAV_OK;
@@ -998,7 +1094,7 @@ extern "C" int dftpav_grid_goal_field(dftpav_handle *h, const double *goals_xy, 
   if (n == 0) return DFTPAV_OK;
   HIPCHK(h, hipSetDevice(h->device));
   GoalFieldPlan G;
-  if (int rc = goal_field_plan(h, goals_xy, 2, n, n, inflate_radius, G)) return rc;
+  if (int rc = goal_field_plan(h, nullptr, goals_xy, 2, n, n, inflate_radius, -1.0, G)) return rc;
   const size_t cells = (size_t)h->map.size_x * h->map.size_y;
   const std::vector<int> field_of(h->gf_host.begin(), h->gf_host.begin() + n);
   const int turns = (int)G.turn_off.size() - 1;
@@ -1009,6 +1105,54 @@ extern "C" int dftpav_grid_goal_field(dftpav_handle *h, const double *goals_xy, 
       int *dst = field + (size_t)q * cells;
       if (field_of[q] < 0) std::fill(dst, dst + cells, DFTPAV_FIELD_UNREACHED);
       else HIPCHK(h, hipMemcpyAsync(dst, F + (size_t)field_of[q] * cells, sizeof(int) * cells, hipMemcpyDeviceToHost, h->stream));
+    }
+  }
+  std::vector<int> reached(G.n_goals + 1, 0);
+  if (n_reached && G.n_goals) HIPCHK(h, hipMemcpyAsync(reached.data(), G.d_reached, sizeof(int) * G.n_goals, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (int q = 0; n_reached && q < n; q++) n_reached[q] = field_of[q] < 0 ? 0 : reached[(size_t)G.turn_off[q / G.per_turn] + field_of[q]];
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_set_search_heuristic_window(dftpav_handle *h, double margin) {
+  if (!h) return DFTPAV_E_INVALID;
+  if (!h->d_cells) return DFTPAV_E_INVALID; // no map
+  if (std::isnan(margin) || margin == HUGE_VAL) return DFTPAV_E_INVALID;
+  h->heu_margin = margin < 0.0 ? -1.0 : margin;
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_grid_goal_field_windowed(dftpav_handle *h, const double *starts_xy, const double *goals_xy, int n, double inflate_radius,
+                                               double margin, int *windows, long long *offsets, int *field, int *n_reached) {
+  if (!h || n < 0 || (n > 0 && (!goals_xy || !starts_xy))) return DFTPAV_E_INVALID;
+  if (!h->d_cells) return DFTPAV_E_INVALID; // no map
+  if (!(inflate_radius >= 0.0) || !std::isfinite(inflate_radius) || !(margin >= 0.0) || !std::isfinite(margin)) return DFTPAV_E_INVALID;
+  if (n == 0) return DFTPAV_OK;
+  // the packed layout: query q's rows [WY][WX] start at offsets[q], one after the other in query order
+  std::vector<int> win(4 * (size_t)n, 0);
+  std::vector<long long> off((size_t)n, 0);
+  long long total = 0;
+  for (int q = 0; q < n; q++) {
+    int *w = win.data() + 4 * (size_t)q;
+    if (dftpav_goal_window(&h->map, starts_xy + 2 * (size_t)q, goals_xy + 2 * (size_t)q, margin, w) < 0) return DFTPAV_E_INVALID;
+    off[q] = total;
+    total += (long long)w[2] * w[3];
+  }
+  if (windows) std::copy(win.begin(), win.end(), windows);
+  if (offsets) std::copy(off.begin(), off.end(), offsets);
+  if (!field && !n_reached) return DFTPAV_OK; // the sizes alone: nothing is built
+  HIPCHK(h, hipSetDevice(h->device));
+  GoalFieldPlan G;
+  if (int rc = goal_field_plan(h, starts_xy, goals_xy, 2, n, n, inflate_radius, margin, G)) return rc;
+  const std::vector<int> field_of(h->gf_host.begin(), h->gf_host.begin() + n);
+  const int turns = (int)G.turn_off.size() - 1;
+  for (int t = 0; t < turns; t++) {
+    int *F = nullptr;
+    if (int rc = goal_field_turn(h, G, t, nullptr, &F)) return rc;
+    for (int q = t * G.per_turn; field && q < std::min(n, (t + 1) * G.per_turn); q++) {
+      if (field_of[q] < 0) continue; // a window of no cells
+      const size_t f = (size_t)G.turn_off[t] + field_of[q], ints = (size_t)win[4 * (size_t)q + 2] * win[4 * (size_t)q + 3];
+      HIPCHK(h, hipMemcpyAsync(field + off[q], F + G.off[f], sizeof(int) * ints, hipMemcpyDeviceToHost, h->stream));
     }
   }
   std::vector<int> reached(G.n_goals + 1, 0);

@@ -34,8 +34,24 @@
 // finitely many sweeps.  Exactness at the end: no tile is dirty, so every tile was relaxed to its fixed point against halo values
 // that have not changed since (a change would have marked it); hence no move anywhere lowers a value.
 //
-// Resources (gfx950, the code object's notes): goal_field_kernel 121 VGPRs, 62 SGPRs, 9256 bytes of LDS (the tile's 8976,
-// the votes), no scratch, 4 waves per SIMD.
+// The windowed instance, goal_field_kernel<true> (dftpav_set_search_heuristic_window, docs/NEXT_ROWS.md §4.22): the field of a
+// window (X0, Y0, WX, WY) of the grid that dftpav_goal_window chose -- a rectangle of whole tiles of the tiling above (X0 a
+// multiple of 64, Y0 of 32; its last column and row of tiles partial only where the grid's are), the goal cell inside it --
+// stored compactly as [WY][WX].  It is the field above of the cropped map: every rule is the same, a cell outside the window
+// is what a cell outside the grid is (blocked and unreached in a halo, never written), and blocked is still d2 <= T with d2 the
+// distance field of the WHOLE map, read at the cell's grid coordinates, so an obstacle outside the window inflates into it.  A
+// cell whose only way to c* leaves the window stays unreached.  The kernel runs in the window's own coordinates: tile t of the
+// window is tile (X0 / 64 + t % tiles_x, Y0 / 32 + t / tiles_x) of the grid, its dirty map has one word per tile of the window,
+// and the grid's coordinates appear in the one expression that reads d2.  Still one workgroup per field and nothing between
+// workgroups.  goal_field_kernel<false> is the kernel of before: the same instructions, registers and LDS, but for one
+// constant, the offset of the implicit arguments behind GoalFieldArgs, which is 24 bytes longer; launch_goal_fields picks.
+//
+// Termination, windowed: the argument above names the grid nowhere.  The window has finitely many cells, every store lowers an
+// int32 that is bounded below by 0, a sweep pair repeats and a tile is marked only after a store; so finitely many tile passes
+// over a finite tile set.  Exactness likewise, for the moves that stay inside the window.
+//
+// Resources (gfx950, the code object's notes): goal_field_kernel<false> 121 VGPRs, 62 SGPRs, 9256 bytes of LDS (the tile's 8976,
+// the votes), no scratch, 4 waves per SIMD; goal_field_kernel<true> 122 VGPRs, 64 SGPRs, the same LDS, no scratch, 4 waves per SIMD.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -91,22 +107,27 @@ template <int ALONG, int ACROSS> __device__ inline int gf_sweep(unsigned *base) 
   return changed;
 }
 
-__global__ void __launch_bounds__(kGfThreads) goal_field_kernel(GoalFieldArgs A) {
+// WINDOW: the field of a window of the grid (see the header).  (x, y), sx, sy, the tiles and the dirty map below are then the
+// window's own -- cell (x, y) of the field is cell (wx0 + x, wy0 + y) of the grid -- and the grid is met in one place, where d2 is read.
+template <bool WINDOW> __global__ void __launch_bounds__(kGfThreads) goal_field_kernel(GoalFieldArgs A) {
   __shared__ unsigned tile[kGfRows * kGfStride];
   __shared__ int s_ahead, s_min, s_max, s_mark, s_count;
   const int lane = threadIdx.x, g = blockIdx.x;
-  const int sx = A.size_x, sy = A.size_y, n_tiles = A.tiles_x * A.tiles_y;
-  int *F = A.fields + (size_t)g * sx * sy;
-  int *dirty = A.dirty + (size_t)g * n_tiles;
-  if (lane == 0) { // the seed (inside the grid: the host's check)
-    const int gx = A.goal_cell[2 * g], gy = A.goal_cell[2 * g + 1];
+  const int wx0 = WINDOW ? A.window[4 * g] : 0, wy0 = WINDOW ? A.window[4 * g + 1] : 0;
+  const int sx = WINDOW ? A.window[4 * g + 2] : A.size_x, sy = WINDOW ? A.window[4 * g + 3] : A.size_y;
+  const int tiles_x = WINDOW ? (sx + kGfTileX - 1) / kGfTileX : A.tiles_x, tiles_y = WINDOW ? (sy + kGfTileY - 1) / kGfTileY : A.tiles_y;
+  const int n_tiles = tiles_x * tiles_y;
+  int *F = WINDOW ? A.fields + A.offset[g] : A.fields + (size_t)g * sx * sy;
+  int *dirty = A.dirty + (WINDOW ? (size_t)g * A.dirty_stride : (size_t)g * n_tiles);
+  if (lane == 0) { // the seed (inside the grid, and inside its window: the host's check)
+    const int gx = A.goal_cell[2 * g] - wx0, gy = A.goal_cell[2 * g + 1] - wy0;
     F[(size_t)gy * sx + gx] = 0;
     // every tile that holds the seed, in its cells or in its halo: the seed's own tile does not "change" it, so a seed on a tile's
     // border would never mark the tile beside it
     for (int dy = -1; dy <= 1; dy++)
       for (int dx = -1; dx <= 1; dx++) {
         const int x = gx + dx, y = gy + dy;
-        if (x >= 0 && x < sx && y >= 0 && y < sy) dirty[(y / kGfTileY) * A.tiles_x + x / kGfTileX] = 1;
+        if (x >= 0 && x < sx && y >= 0 && y < sy) dirty[(y / kGfTileY) * tiles_x + x / kGfTileX] = 1;
       }
     s_count = 0;
   }
@@ -143,7 +164,7 @@ __global__ void __launch_bounds__(kGfThreads) goal_field_kernel(GoalFieldArgs A)
       t = s_min;
     }
     cursor = t + dir;
-    const int tx = t % A.tiles_x, ty = t / A.tiles_x;
+    const int tx = t % tiles_x, ty = t / tiles_x;
     const int x0 = tx * kGfTileX, y0 = ty * kGfTileY;
     if (lane == 0) dirty[t] = 0;
     for (int c = lane; c < kGfRows * kGfStride; c += kGfThreads) {
@@ -152,7 +173,8 @@ __global__ void __launch_bounds__(kGfThreads) goal_field_kernel(GoalFieldArgs A)
       unsigned v = kGfBlockedBit | kGfValueMask;
       if (x >= 0 && x < sx && y >= 0 && y < sy) {
         const size_t idx = (size_t)y * sx + x;
-        v = (unsigned)F[idx] | (A.d2[idx] <= A.T ? kGfBlockedBit : 0u);
+        const size_t map_idx = WINDOW ? (size_t)(wy0 + y) * A.size_x + (size_t)(wx0 + x) : idx; // d2 is the whole map's
+        v = (unsigned)F[idx] | (A.d2[map_idx] <= A.T ? kGfBlockedBit : 0u);
       }
       tile[c] = v;
     }
@@ -185,7 +207,7 @@ __global__ void __launch_bounds__(kGfThreads) goal_field_kernel(GoalFieldArgs A)
     if (lane < 8 && ((s_mark >> lane) & 1)) {
       const int k = lane + (lane >= 4 ? 1 : 0);
       const int nx = tx + k % 3 - 1, ny = ty + k / 3 - 1;
-      if (nx >= 0 && nx < A.tiles_x && ny >= 0 && ny < A.tiles_y) dirty[ny * A.tiles_x + nx] = 1;
+      if (nx >= 0 && nx < tiles_x && ny >= 0 && ny < tiles_y) dirty[ny * tiles_x + nx] = 1;
     }
   }
   if (reached) atomicAdd(&s_count, reached);
@@ -194,7 +216,8 @@ __global__ void __launch_bounds__(kGfThreads) goal_field_kernel(GoalFieldArgs A)
 }
 
 hipError_t launch_goal_fields(const GoalFieldArgs &A, int n, hipStream_t stream) {
-  hipLaunchKernelGGL(goal_field_kernel, dim3((unsigned)n), dim3(kGfThreads), 0, stream, A);
+  if (A.window) hipLaunchKernelGGL(goal_field_kernel<true>, dim3((unsigned)n), dim3(kGfThreads), 0, stream, A);
+  else hipLaunchKernelGGL(goal_field_kernel<false>, dim3((unsigned)n), dim3(kGfThreads), 0, stream, A);
   return hipGetLastError();
 }
 

@@ -134,6 +134,12 @@ class TrajPlannerSteps {
     return ok(dftpav_set_search_heuristic(h_, &gp));
   }
 
+  // With setObstacleHeuristic on, limits every query's cost-to-go field to a window of the map: the box of its start and goal cells
+  // grown by margin metres, snapped outwards to the field's tiles (dftpav_goal_window) -- what makes the heuristic affordable on an
+  // arena-sized map.  A detour that leaves the window is not seen: the term is then 0 at the start and the search the plain one.
+  // margin < 0: off (the default), whole-map fields.  Independent of `enabled` above; needs the map of setObstacleMap.
+  bool setObstacleHeuristicWindow(double margin) { return ok(dftpav_set_search_heuristic_window(h_, margin)); }
+
   // The non-holonomic half of the heuristic: search() below, and every plan through this handle, then also take the maximum with
   // the Reeds-Shepp length to the goal, read from a table of the default geometry (72 headings, 15 m, cells of 0.25 m) that the
   // handle builds once.  Off by default, and off again with enabled = false.  Independent of setObstacleHeuristic; needs no map.

@@ -36,6 +36,11 @@
 // slice is k = (int)round((yaw - goal yaw) / dth) reduced into [0, n_yaw) by integer remainder; the term is scale * T[k][fj][fi].
 // The heuristic is then lambda_heu * fmax(fmax(tie_breaker * |p - goal|, the field's term where there is one), the table's term).
 // search_kernel<false, false> and <true, false> are the kernels of before; launch_search picks the instance.
+//
+// FIELD has a third value, kFieldWindow (dftpav_set_search_heuristic_window, docs/NEXT_ROWS.md §4.22): the query's field covers a
+// window (X0, Y0, WX, WY) of the grid only and is stored [WY][WX].  The cell (cx, cy) is rounded as above; outside the window the
+// term is 0, as outside the grid; inside it the value is read at (cx - X0) + WX * (cy - Y0).  Nothing else differs, the maximum
+// with the table's term included.  The instances with FIELD = kFieldNone and kFieldMap are the four of before, their code unchanged.
 #include <hip/hip_runtime.h>
 
 #include "../../include/dftpav_hip.h"
@@ -150,12 +155,33 @@ __device__ int sr_shot_free(const SearchArgs &A, SShared &S, const double *from,
   return S.hit == 0 ? 1 : 0;
 }
 
+enum { kFieldNone = 0, kFieldMap = 1, kFieldWindow = 2 }; // the template parameter FIELD
+
+// a windowed goal field: its cells [wy][wx] and the window's corner in the grid; F == nullptr: the query has none
+struct SrWindowField {
+  const int *F;
+  int x0, y0, wx, wy;
+  __device__ explicit operator bool() const { return F != nullptr; }
+};
+// what a search carries as its query's field: the whole-map field's cells, or a windowed field
+template <int FIELD> struct SrFieldOf { typedef const int *type; };
+template <> struct SrFieldOf<kFieldWindow> { typedef SrWindowField type; };
+
 // the goal field's term of the heuristic at (x, y), in metres: 0 outside the grid and where the field did not reach
 __device__ inline double sr_field_heu(const SearchArgs &A, const int *Fq, double x, double y) {
   const DevGrid &g = A.grid;
   const double cx = round((x - g.origin_x) / g.resolution), cy = round((y - g.origin_y) / g.resolution);
   if (!(cx >= 0.0 && cx < (double)g.size_x && cy >= 0.0 && cy < (double)g.size_y)) return 0.0;
   const int v = Fq[(size_t)(int)cx + (size_t)g.size_x * (size_t)(int)cy];
+  return v == DFTPAV_FIELD_UNREACHED ? 0.0 : (double)v * A.unit;
+}
+
+// the same of a windowed field: 0 outside the window (which lies inside the grid) and where the field did not reach
+__device__ inline double sr_field_heu(const SearchArgs &A, const SrWindowField &W, double x, double y) {
+  const DevGrid &g = A.grid;
+  const double cx = round((x - g.origin_x) / g.resolution), cy = round((y - g.origin_y) / g.resolution);
+  if (!(cx >= (double)W.x0 && cx < (double)(W.x0 + W.wx) && cy >= (double)W.y0 && cy < (double)(W.y0 + W.wy))) return 0.0;
+  const int v = W.F[(size_t)((int)cx - W.x0) + (size_t)W.wx * (size_t)((int)cy - W.y0)];
   return v == DFTPAV_FIELD_UNREACHED ? 0.0 : (double)v * A.unit;
 }
 
@@ -175,8 +201,9 @@ __device__ inline double sr_rs_heu(const RsLookup &R, const double *en, double g
 }
 
 // the heuristic of a state: getHeu, and the maximum with the terms the instance has
-template <bool FIELD, bool TABLE>
-__device__ inline double sr_heu(const SearchArgs &A, const double *en, const int *Fq, double gc, double gs, double x, double y, double yaw) {
+template <int FIELD, bool TABLE>
+__device__ inline double sr_heu(const SearchArgs &A, const double *en, typename SrFieldOf<FIELD>::type Fq, double gc, double gs, double x,
+                                double y, double yaw) {
   const dftpav_search_params &P = A.sp;
   const double dx = fabs(x - en[0]), dy = fabs(y - en[1]);
   if constexpr (TABLE) {
@@ -191,9 +218,9 @@ __device__ inline double sr_heu(const SearchArgs &A, const double *en, const int
 }
 
 // one call of KinoAstar::search(start, ctrl, end, use3d) after reset(); result in S.status / shot / budget / iters / used / terminal
-template <bool FIELD, bool TABLE>
+template <int FIELD, bool TABLE>
 __device__ void sr_search(const SearchArgs &A, SShared &S, SearchNode *pool, KinoHeap &heap, int *table, const double *st,
-                          const double *en, bool use3d, int lane, const int *Fq, double gc, double gs) {
+                          const double *en, bool use3d, int lane, typename SrFieldOf<FIELD>::type Fq, double gc, double gs) {
   const dftpav_search_params &P = A.sp;
   for (int s = lane; s < A.hcap; s += kSearchThreads) table[s] = -1;
   if (lane == 0) {
@@ -395,7 +422,7 @@ __device__ void sr_search(const SearchArgs &A, SShared &S, SearchNode *pool, Kin
   __syncthreads();
 }
 
-template <bool FIELD, bool TABLE> __global__ void __launch_bounds__(kSearchThreads) search_kernel(SearchArgs A) {
+template <int FIELD, bool TABLE> __global__ void __launch_bounds__(kSearchThreads) search_kernel(SearchArgs A) {
   __shared__ SShared S;
   const int slot = blockIdx.x, q = A.q0 + blockIdx.x, lane = threadIdx.x;
   if (q >= A.n) return;
@@ -410,8 +437,14 @@ template <bool FIELD, bool TABLE> __global__ void __launch_bounds__(kSearchThrea
     st[k] = A.start[4 * (size_t)q + k];
     en[k] = A.end[4 * (size_t)q + k];
   }
-  const int *Fq = nullptr; // the goal field of this query's goal
-  if constexpr (FIELD) {
+  typename SrFieldOf<FIELD>::type Fq{}; // the goal field of this query's goal
+  if constexpr (FIELD == kFieldWindow) {
+    const int f = A.field_of[q];
+    if (f >= 0) {
+      const int *w = A.field_win + 4 * (size_t)f;
+      Fq = SrWindowField{A.fields + A.field_off[f], w[0], w[1], w[2], w[3]};
+    }
+  } else if constexpr (FIELD) {
     const int f = A.field_of[q];
     if (f >= 0) Fq = A.fields + (size_t)f * A.grid.size_x * A.grid.size_y;
   }
@@ -561,10 +594,13 @@ template <bool FIELD, bool TABLE> __global__ void __launch_bounds__(kSearchThrea
 
 hipError_t launch_search(const SearchArgs &A, int blocks, hipStream_t stream) {
   const dim3 grid(blocks), block(kSearchThreads);
-  if (A.rs.tab && A.fields) hipLaunchKernelGGL((search_kernel<true, true>), grid, block, 0, stream, A);
-  else if (A.rs.tab) hipLaunchKernelGGL((search_kernel<false, true>), grid, block, 0, stream, A);
-  else if (A.fields) hipLaunchKernelGGL((search_kernel<true, false>), grid, block, 0, stream, A);
-  else hipLaunchKernelGGL((search_kernel<false, false>), grid, block, 0, stream, A);
+  if (A.fields && A.field_win) { // windowed fields
+    if (A.rs.tab) hipLaunchKernelGGL((search_kernel<kFieldWindow, true>), grid, block, 0, stream, A);
+    else hipLaunchKernelGGL((search_kernel<kFieldWindow, false>), grid, block, 0, stream, A);
+  } else if (A.rs.tab && A.fields) hipLaunchKernelGGL((search_kernel<kFieldMap, true>), grid, block, 0, stream, A);
+  else if (A.rs.tab) hipLaunchKernelGGL((search_kernel<kFieldNone, true>), grid, block, 0, stream, A);
+  else if (A.fields) hipLaunchKernelGGL((search_kernel<kFieldMap, false>), grid, block, 0, stream, A);
+  else hipLaunchKernelGGL((search_kernel<kFieldNone, false>), grid, block, 0, stream, A);
   return hipGetLastError();
 }
 

@@ -42,6 +42,10 @@ struct SearchArgs {
   double unit;         // metres of heuristic per unit of the field: scale * resolution / 5
   // the Reeds-Shepp table of dftpav_set_search_rs_heuristic (rstable.hip); read only by the kernel launched with a table
   RsLookup rs;
+  // windowed fields (dftpav_set_search_heuristic_window): field f covers the window field_win[f] = (X0, Y0, WX, WY) of the grid
+  // and is [WY][WX] at fields + field_off[f].  nullptr: whole-map fields, as `fields` says; read only by the kernel launched with windowed fields
+  const int *field_win;       // [distinct fields of this launch][4]
+  const long long *field_off; // [distinct fields of this launch], in ints
 };
 
 } // namespace dftpav

@@ -1058,6 +1058,49 @@ int dftpav_grid_goal_field(dftpav_handle *h, const double *goals_xy /*[n][2]*/, 
                            int *field /*[n][size_y][size_x] or NULL*/, int *n_reached /*[n] or NULL*/);
 int dftpav_goal_field_last_ms(dftpav_handle *h, float *ms);
 
+/* ---- goal fields limited to a window round start and goal --------------------------------------------------------------
+ * A whole-map field costs what the map costs, however short the query: on an arena of 1500 x 1500 cells one field is 9 MB and
+ * tens of milliseconds.  These calls build the field of the part of the map a query can use, and the search reads that.
+ *
+ * The window rule.  dftpav_goal_window is pure host code and the only place a window is computed; of the map it reads the sizes,
+ * the resolution and the origin (cells may be NULL).  In cells: the goal cell (gx, gy) = round((p - origin) / resolution), as
+ * above; a goal outside the grid has no window and no field (returns 0, win = 0, 0, 0, 0).  The start cell (sx, sy) by the same
+ * rounding, each coordinate then clamped into the grid (a start may lie outside it).  m = (int)ceil(margin / resolution);
+ *   x0 = max(0, min(sx, gx) - m),  x1 = min(size_x - 1, max(sx, gx) + m),  y0 and y1 likewise;
+ * the box is then snapped outwards to the field's tiles of 64 x 32 cells:
+ *   X0 = x0 / 64 * 64,  X1 = min(size_x, (x1 / 64 + 1) * 64),  WX = X1 - X0;  Y0, Y1, WY likewise with 32,
+ * so a window is a rectangle of the whole-map field's own tiles, and queries near each other share windows.  A margin that
+ * covers the grid gives (0, 0, size_x, size_y).  Returns 1 with win = (X0, Y0, WX, WY); DFTPAV_E_INVALID for a NULL pointer,
+ * a side < 1, a resolution that is not positive and finite, an origin that is not finite, a margin that is negative or not finite.
+ *
+ * The windowed field is the field above of the CROPPED map, stored [WY][WX]: inside the window every rule is unchanged -- the
+ * seed, the step costs 5 and 7, no corner cutting -- and a cell outside the window is what a cell outside the grid is: never
+ * entered, never written.  Blocked is still d2[c] <= T with d2 the distance field of the WHOLE map at the cell's grid
+ * coordinates, so an obstacle just outside the window inflates into it.  A cell whose only way to the goal leaves the window
+ * holds DFTPAV_FIELD_UNREACHED; every other value is >= the whole-map field's, the cost of a path that also exists there.
+ * dftpav_grid_goal_field_windowed: the windowed fields of n (start, goal) pairs, margin >= 0.  windows [n][4] and offsets [n]
+ *   (either may be NULL) are written first: query q's rows [WY][WX] start at field + offsets[q], the queries packed in order
+ *   (offsets[q + 1] = offsets[q] + WX * WY of q); with field == NULL and n_reached == NULL nothing is built, so a first call
+ *   sizes the buffer.  A goal outside the grid has window (0, 0, 0, 0), no rows, and n_reached 0.  Pairs that share goal cell
+ *   and window share one build.
+ *
+ * The heuristic.  dftpav_set_search_heuristic_window keeps a margin on the handle, beside and independent of
+ * dftpav_set_search_heuristic's state: margin < 0 is off (the default), and then -- or while that heuristic is off -- every call
+ * launches what it launched without this one and returns the same bits.  With both on, dftpav_kino_search, dftpav_plan_queries
+ * and dftpav_replan_tick build one field per distinct (goal cell, window) of a turn, the window of each query's own start and
+ * goal; the turns are sized by the call's largest window, not by the map (the 2 GiB cap stays); and the field's term of h at
+ * (x, y) is read at (cx - X0) + WX * (cy - Y0), a point outside the window counting as F = 0 like a point outside the grid.
+ * Not claimed: the window can cut off the only detour -- then the start's cell is unreached, the term is 0 there and the search
+ * is the plain one; inside the window the field is an upper bound of the whole-map field; and still nothing about admissibility.
+ * DFTPAV_E_INVALID, and nothing changed: a NULL handle, no grid map, a margin that is NaN or +inf (dftpav_grid_goal_field_windowed:
+ * negative or not finite), a radius that is negative or not finite, n < 0, starts_xy or goals_xy NULL with n > 0. */
+int dftpav_goal_window(const dftpav_grid_map *map_geometry, const double *start_xy /*[2]*/, const double *goal_xy /*[2]*/, double margin,
+                       int *win /*[4]: X0, Y0, WX, WY*/); /* 1: a window; 0: the goal is outside the grid (no field); < 0: error */
+int dftpav_set_search_heuristic_window(dftpav_handle *h, double margin); /* margin < 0: off (default), whole-map fields as before */
+int dftpav_grid_goal_field_windowed(dftpav_handle *h, const double *starts_xy /*[n][2]*/, const double *goals_xy /*[n][2]*/, int n,
+                                    double inflate_radius, double margin, int *windows /*[n][4] or NULL*/,
+                                    long long *offsets /*[n] or NULL*/, int *field /*packed, or NULL*/, int *n_reached /*[n] or NULL*/);
+
 /* ---- the Reeds-Shepp cost-to-go table, and the non-holonomic term of the hybrid A* heuristic ----------------------------
  * getHeu and the goal field above know positions only: neither knows that the vehicle cannot turn on the spot, nor that the goal
  * has a heading.  This is the other half of the usual pair (Dolgov et al.): the length of the shortest Reeds-Shepp path to the
