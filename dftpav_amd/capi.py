@@ -21,6 +21,7 @@ OK = 0
 ORDER_DEVICE, ORDER_REFERENCE = 0, 1
 E_INVALID, E_MINI_T, E_ONE_PIECE, E_NO_DEVICE, E_HIP, E_UNSUPPORTED, E_COMM = -1, -2, -3, -4, -5, -6, -7
 PUBLISH_CHUNK, PUBLISH_MAX_TICKS = 256, 4096   # DFTPAV_PUBLISH_CHUNK, DFTPAV_PUBLISH_MAX_TICKS
+CONFLICT_MAX_SAMPLES = 4096   # DFTPAV_CONFLICT_MAX_SAMPLES
 # plan_status of dftpav_plan_queries (DFTPAV_PLAN_*); search status (DFTPAV_SEARCH_*)
 PLAN_OK, PLAN_NO_PATH, PLAN_TOO_MANY_SEGMENTS, PLAN_LAYOUT_UNSUPPORTED, PLAN_NO_VALID_RESTART, PLAN_ARRIVED = 0, 1, 2, 3, 4, 5
 SEARCH_REACH_END, SEARCH_NO_PATH = 2, 3
@@ -58,6 +59,7 @@ EXPORTS = [
     "dftpav_default_goal_field_params", "dftpav_set_search_heuristic", "dftpav_grid_goal_field", "dftpav_goal_field_last_ms",
     "dftpav_goal_window", "dftpav_set_search_heuristic_window", "dftpav_grid_goal_field_windowed",
     "dftpav_default_rs_heuristic_params", "dftpav_set_search_rs_heuristic", "dftpav_rs_table", "dftpav_rs_table_last_ms",
+    "dftpav_planner_check_conflicts", "dftpav_planner_sample_poses", "dftpav_conflicts_last_ms",
 ]
 
 
@@ -211,6 +213,36 @@ class ClearanceOut:
 
     def arrays(self):
         return self.a
+
+
+class _ConflictOutC(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("min_sep", "sep_sample", "sep_partner", "conflict_sample", "conflict_partner")]
+
+
+class ConflictOut:
+    """the caller-allocated arrays of dftpav_conflict_out for `shape` rows: min_sep (metres, 0.0: the footprints overlap, +inf: no
+    partner inside the broad phase), sep_sample / sep_partner (where and with whom it is reached), conflict_sample /
+    conflict_partner (the first sample with a separation <= margin and the partner there); -1: none"""
+    KEYS = ("min_sep", "sep_sample", "sep_partner", "conflict_sample", "conflict_partner")
+
+    def __init__(self, *shape):
+        self.a = dict(min_sep=np.zeros(shape), **{k: np.zeros(shape, dtype=np.int32) for k in self.KEYS[1:]})
+        self.c = _ConflictOutC(*[self.a[k].ctypes.data for k in self.KEYS])
+
+    def arrays(self):
+        return self.a
+
+
+def conflict_args(t0, dt, K, margin=0.0, range=None):
+    """the arguments of dftpav_planner_check_conflicts / _sample_poses as the library takes them, (t0, dt, K, margin, range) with
+    range = margin when None; what the library would refuse raises DftpavError(E_INVALID) here, before any library call"""
+    t0, dt, margin = float(t0), float(dt), float(margin)
+    range = margin if range is None else float(range)
+    ok = int(K) == K and 1 <= K <= CONFLICT_MAX_SAMPLES and dt > 0.0 and np.isfinite(dt) and np.isfinite(t0)
+    ok = ok and margin >= 0.0 and np.isfinite(range) and range >= margin
+    if not ok:
+        raise DftpavError(E_INVALID, "conflicts: K in [1, %d], dt > 0, t0 finite, margin >= 0, range finite and >= margin" % CONFLICT_MAX_SAMPLES)
+    return t0, dt, int(K), margin, range
 
 
 class GoalFieldParams(C.Structure):
@@ -485,6 +517,15 @@ class Handle:
         fn = lib().dftpav_clearance_last_ms
         fn.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         self._check(fn(self._h, C.byref(a), C.byref(b)), "clearance_last_ms")
+        return float(a.value), float(b.value)
+
+    def conflicts_last_ms(self):
+        """dftpav_conflicts_last_ms: device ms of (the pose kernel, the pair and reduce kernels) of the last check_conflicts /
+        sample_poses call of a planner of this handle; 0.0 for what has not run"""
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        fn = lib().dftpav_conflicts_last_ms
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        self._check(fn(self._h, C.byref(a), C.byref(b)), "conflicts_last_ms")
         return float(a.value), float(b.value)
 
     def goal_field(self, goals_xy, inflate_radius=0.0, fetch=True):
@@ -906,6 +947,28 @@ class Planner:
         fn.argtypes = [C.c_void_p, C.c_void_p]
         self.handle._check(fn(self._p, C.byref(out.c)), "planner_last_clearance")
         return out.arrays()
+
+    # ---- footprint conflicts between the executing plans, slot against slot
+    def check_conflicts(self, t0, dt, K, margin=0.0, range=None):
+        """dftpav_planner_check_conflicts at the clocks t0 + k dt, k < K: a row per slot -> dict(min_sep, sep_sample, sep_partner,
+        conflict_sample, conflict_partner [slots]); a slot that is empty or has no partner inside the broad phase: +inf, -1, -1, -1,
+        -1.  range None: margin"""
+        t0, dt, K, margin, range = conflict_args(t0, dt, K, margin, range)
+        out = ConflictOut(self.max_queries)
+        fn = lib().dftpav_planner_check_conflicts
+        fn.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_void_p]
+        self.handle._check(fn(self._p, t0, dt, K, margin, range, C.byref(out.c)), "planner_check_conflicts")
+        return out.arrays()
+
+    def sample_poses(self, t0, dt, K):
+        """dftpav_planner_sample_poses: the pose half of check_conflicts alone -> [K][slots][4] = the footprint's centre cx, cy and
+        the heading's cosine and sine; NaN rows for empty slots"""
+        t0, dt, K, _, _ = conflict_args(t0, dt, K)
+        out = np.zeros((K, self.max_queries, 4))
+        fn = lib().dftpav_planner_sample_poses
+        fn.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p]
+        self.handle._check(fn(self._p, t0, dt, K, self._ip(out)), "planner_sample_poses")
+        return out
 
     def publish_last_ms(self):
         """dftpav_publish_last_ms: device ms of the last publish kernel (0.0 before the first)"""

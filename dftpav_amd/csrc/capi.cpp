@@ -259,7 +259,7 @@ extern "C" void dftpav_destroy(dftpav_handle *h) {
   if (h->lev0) (void)hipEventDestroy(h->lev0);
   if (h->lev1) (void)hipEventDestroy(h->lev1);
   if (h->d_dist) (void)hipFree(h->d_dist);
-  for (hipEvent_t e : {h->fev0, h->fev1, h->kev0, h->kev1})
+  for (hipEvent_t e : {h->fev0, h->fev1, h->kev0, h->kev1, h->qev[0], h->qev[1], h->qev[2]})
     if (e) (void)hipEventDestroy(e);
   if (h->d_gf) (void)hipFree(h->d_gf);
   if (h->d_gf_meta) (void)hipFree(h->d_gf_meta);

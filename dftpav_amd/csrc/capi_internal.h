@@ -28,6 +28,7 @@
 #include "plan_args.h"
 #include "limits_args.h"
 #include "clearance_args.h"
+#include "conflict_args.h"
 #include "goalfield_args.h"
 
 namespace dftpav {
@@ -63,6 +64,10 @@ hipError_t launch_limits_table(const LimitsTableArgs &A, hipStream_t stream);
 hipError_t launch_dist_field(const DistFieldArgs &A, hipStream_t stream);
 hipError_t launch_clearance_batch(const ClearanceBatchArgs &A, hipStream_t stream);
 hipError_t launch_clearance_table(const ClearanceTableArgs &A, hipStream_t stream);
+// conflict.hip: the poses of the executing plans at K clocks, their pairwise separation per (I-tile, J-tile), the rows per slot
+hipError_t launch_conflict_poses(const ConflictPoseArgs &A, hipStream_t stream);
+hipError_t launch_conflict_pairs(const ConflictPairArgs &A, hipStream_t stream);
+hipError_t launch_conflict_reduce(const ConflictReduceArgs &A, hipStream_t stream);
 // goalfield.hip: the cost-to-go fields of n goal cells, one workgroup each
 hipError_t launch_goal_fields(const GoalFieldArgs &A, int n, hipStream_t stream);
 // rstable.hip: every entry of the Reeds-Shepp cost-to-go table
@@ -119,6 +124,8 @@ struct dftpav_handle {
   bool dist_stale = true;
   hipEvent_t fev0 = nullptr, fev1 = nullptr, kev0 = nullptr, kev1 = nullptr; // around the last field build / the last clearance kernel of a check call
   bool ftimed = false, ktimed = false;
+  hipEvent_t qev[3] = {nullptr, nullptr, nullptr}; // conflict.hip: in front of the pose kernel, between it and the pair kernel, behind the reduce kernel
+  bool qpose_timed = false, qpair_timed = false;   // of the last dftpav_planner_sample_poses / _check_conflicts call
   // the search heuristic (dftpav_set_search_heuristic) and the workspace of the goal fields (goalfield.hip): nothing of it is
   // allocated or launched until a call asks for a field
   dftpav_goal_field_params heu{0, 0.0, 0.0};

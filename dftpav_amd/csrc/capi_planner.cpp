@@ -1357,3 +1357,122 @@ extern "C" int dftpav_planner_last_clearance(dftpav_planner *p, const dftpav_cle
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return DFTPAV_OK;
 }
+
+// ------------------------------------------------- footprint conflicts between the executing plans (conflict.hip)
+static bool conflict_clocks_ok(double t0, double dt, int K) {
+  return K >= 1 && K <= DFTPAV_CONFLICT_MAX_SAMPLES && dt > 0.0 && std::isfinite(dt) && std::isfinite(t0);
+}
+
+// the poses of every slot at the K clocks into buffers of `tmp`, on the handle's stream between qev[0] and qev[1] (nothing waits)
+static int conflict_poses_on_stream(dftpav_planner *p, DevScratch &tmp, double t0, double dt, int K, ConflictPoses &P) {
+  dftpav_handle *h = p->h;
+  for (hipEvent_t &e : h->qev)
+    if (!e) HIPCHK(h, hipEventCreate(&e));
+  const int S_pad = (p->max_queries + kConflictTile - 1) / kConflictTile * kConflictTile;
+  const size_t n = (size_t)K * S_pad;
+  double *d_pose = nullptr;
+  HIPCHK(h, tmp.alloc(d_pose, 4 * n));
+  HIPCHK(h, tmp.alloc(P.occupied, (size_t)S_pad));
+  P.cx = d_pose;
+  P.cy = d_pose + n;
+  P.cs = d_pose + 2 * n;
+  P.sn = d_pose + 3 * n;
+  P.K = K;
+  P.S_pad = S_pad;
+  ConflictPoseArgs A{};
+  A.T = p->T;
+  A.P = P;
+  A.t0 = t0;
+  A.dt = dt;
+  A.dcr = h->params.veh_d_cr;
+  h->qpose_timed = h->qpair_timed = false; // until the whole chain has run
+  HIPCHK(h, hipEventRecord(h->qev[0], h->stream));
+  HIPCHK(h, launch_conflict_poses(A, h->stream));
+  HIPCHK(h, hipEventRecord(h->qev[1], h->stream));
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_planner_sample_poses(dftpav_planner *p, double t0, double dt, int K, double *poses) {
+  if (!p || !poses || !conflict_clocks_ok(t0, dt, K)) return DFTPAV_E_INVALID;
+  dftpav_handle *h = p->h;
+  const size_t S = (size_t)p->max_queries;
+  if (!p->d_exec) { // nothing was ever installed: every slot is empty
+    std::fill(poses, poses + (size_t)K * S * 4, std::nan(""));
+    return DFTPAV_OK;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  DevScratch tmp(h);
+  ConflictPoses P{};
+  if (int rc = conflict_poses_on_stream(p, tmp, t0, dt, K, P)) return rc;
+  const size_t n = (size_t)K * P.S_pad;
+  std::vector<double> soa(4 * n); // cx | cy | cs | sn, each [K][S_pad]
+  HIPCHK(h, hipMemcpyAsync(soa.data(), P.cx, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (size_t k = 0; k < (size_t)K; k++)
+    for (size_t s = 0; s < S; s++)
+      for (size_t c = 0; c < 4; c++) poses[(k * S + s) * 4 + c] = soa[c * n + k * P.S_pad + s];
+  h->qpose_timed = true;
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_planner_check_conflicts(dftpav_planner *p, double t0, double dt, int K, double margin, double range,
+                                              const dftpav_conflict_out *out) {
+  if (!p || !out || !conflict_clocks_ok(t0, dt, K)) return DFTPAV_E_INVALID;
+  if (!(margin >= 0.0) || !std::isfinite(range) || range < margin) return DFTPAV_E_INVALID; // (a NaN margin; +inf fails range < margin)
+  dftpav_handle *h = p->h;
+  const size_t S = (size_t)p->max_queries;
+  if (!p->d_exec) { // nothing was ever installed: every slot is empty
+    if (out->min_sep) std::fill(out->min_sep, out->min_sep + S, HUGE_VAL);
+    for (int *row : {out->sep_sample, out->sep_partner, out->conflict_sample, out->conflict_partner})
+      if (row) std::fill(row, row + S, -1);
+    return DFTPAV_OK;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  DevScratch tmp(h);
+  ConflictPoses P{};
+  if (int rc = conflict_poses_on_stream(p, tmp, t0, dt, K, P)) return rc;
+  const size_t tiles = (size_t)P.S_pad / kConflictTile;
+  const size_t rows = tiles * P.S_pad; // the partial rows [tiles][S_pad]; behind them the outputs [S]
+  double *d_sep = nullptr;
+  int *d_int = nullptr;
+  HIPCHK(h, tmp.alloc(d_sep, rows + S));
+  HIPCHK(h, tmp.alloc(d_int, 4 * (rows + S)));
+  const double L = h->params.veh_length, W = h->params.veh_width;
+  const double rad = std::sqrt(0.25 * L * L + 0.25 * W * W);
+  const double R = range + 2.0 * rad;
+  ConflictPairArgs A{};
+  A.P = P;
+  A.part = ConflictRows{d_sep, d_int, d_int + rows, d_int + 2 * rows, d_int + 3 * rows};
+  A.half_l = 0.5 * L;
+  A.half_w = 0.5 * W;
+  A.margin = margin;
+  A.reach2 = R * R;
+  ConflictReduceArgs Rd{};
+  Rd.part = A.part;
+  int *o_int = d_int + 4 * rows;
+  Rd.out = ConflictRows{d_sep + rows, o_int, o_int + S, o_int + 2 * S, o_int + 3 * S};
+  Rd.n_slots = p->max_queries;
+  Rd.S_pad = P.S_pad;
+  Rd.tiles = (int)tiles;
+  HIPCHK(h, launch_conflict_pairs(A, h->stream));
+  HIPCHK(h, launch_conflict_reduce(Rd, h->stream));
+  HIPCHK(h, hipEventRecord(h->qev[2], h->stream));
+  HIPCHK(h, fetch_async(h, out->min_sep, Rd.out.min_sep, sizeof(double) * S));
+  HIPCHK(h, fetch_async(h, out->sep_sample, Rd.out.sep_sample, sizeof(int) * S));
+  HIPCHK(h, fetch_async(h, out->sep_partner, Rd.out.sep_partner, sizeof(int) * S));
+  HIPCHK(h, fetch_async(h, out->conflict_sample, Rd.out.conflict_sample, sizeof(int) * S));
+  HIPCHK(h, fetch_async(h, out->conflict_partner, Rd.out.conflict_partner, sizeof(int) * S));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->qpose_timed = h->qpair_timed = true;
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_conflicts_last_ms(dftpav_handle *h, float *pose_ms, float *pair_ms) {
+  if (!h) return DFTPAV_E_INVALID;
+  if (pose_ms) *pose_ms = 0.0f;
+  if (pair_ms) *pair_ms = 0.0f;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (pose_ms && h->qpose_timed) HIPCHK(h, hipEventElapsedTime(pose_ms, h->qev[0], h->qev[1])); // (both calls waited for the stream)
+  if (pair_ms && h->qpair_timed) HIPCHK(h, hipEventElapsedTime(pair_ms, h->qev[1], h->qev[2]));
+  return DFTPAV_OK;
+}

@@ -214,6 +214,21 @@ class TrajPlannerSteps {
     return ok(dftpav_batch_check_limits(batch, 0.05, &l, &out));
   }
 
+  // the executing plans of a planner's table against one another at the clocks t0 + k dt, k < K: conflict[s] == 1 when the footprint
+  // of slot s comes within `margin` of another slot's at one of them; min_sep / partner (optional) get the smallest separation of
+  // slot s inside `range` (+inf: none) and the slot it is reached with (-1: none).  slots: the planner's max_queries
+  bool CheckConflicts(dftpav_planner *planner, int slots, double t0, double dt, int K, double margin, double range,
+                      std::vector<int> &conflict, std::vector<double> *min_sep = nullptr, std::vector<int> *partner = nullptr) {
+    std::vector<int> first(slots, -1);
+    conflict.assign(slots, 0);
+    if (min_sep) min_sep->assign(slots, 0.0);
+    if (partner) partner->assign(slots, -1);
+    const dftpav_conflict_out out{min_sep ? min_sep->data() : nullptr, nullptr, partner ? partner->data() : nullptr, first.data(), nullptr};
+    if (!ok(dftpav_planner_check_conflicts(planner, t0, dt, K, margin, range, &out))) return false;
+    for (int s = 0; s < slots; s++) conflict[s] = first[s] >= 0 ? 1 : 0;
+    return true;
+  }
+
   // the states the server would publish for every trajectory of a solved batch at t0, t0 + dt, ...;
   // states[t] holds the samples that fall inside trajectory t
   bool GetStates(dftpav_batch *batch, int B, double t0, double dt, int n_samples, std::vector<std::vector<State>> &states,

@@ -1141,6 +1141,66 @@ int dftpav_rs_table(dftpav_handle *h, double max_cur, const dftpav_rs_heuristic_
                     int *dims /*[3] or NULL*/);
 int dftpav_rs_table_last_ms(dftpav_handle *h, float *ms, int *n_builds /* or NULL */);
 
+/* ---- footprint conflicts between the executing plans, slot against slot ------------------------------------------------
+ * Every other check of the executing table looks at one slot at a time.  This one relates two: do the vehicles of two slots come
+ * within `margin` of one another at the same clock, when first, and who with.  A read-out beside limits and clearance (conflict.hip);
+ * nothing of it feeds the solve or the tick.  No grid map is needed.
+ *
+ * The clocks.  t_k = t0 + (double)k * dt, k = 0 .. K - 1: absolute, on the clock of the table's start_time / end_time.
+ *
+ * The pose of an occupied slot at clock t: the vehicle as the publisher would drive it, held still outside its plan.
+ *   segment e   the first i in [0, n_seg) with !(end_time[i] <= t), else n_seg - 1 (exe_traj_index_ derived from the clock as
+ *               dftpav_replan_check derives it, traj_server_ros.cpp:248-252)
+ *   local time  tt = t - start_time[e]; tt < 0 becomes 0; tt > duration[e] becomes duration[e]
+ *   position    Trajectory::getPos(tt) of segment e (locatePieceIdx's subtraction walk, Piece::getPos)
+ *   heading     Trajectory::getAngle(tt) = atan2(singul * sigma'_y, singul * sigma'_x), correctly rounded; cs, sn its cosine and sine
+ *   footprint   the oriented box of the collision re-check (semantic_map_manager.cc:645-646, shapes.cc:110-149): centre
+ *               c = pos + veh_d_cr * (cs, sn) and the four corners c +- 0.5 veh_length (cs, sn) +- 0.5 veh_width (sn, -cs), in the
+ *               re-check's expressions and corner order; veh_width, veh_length, veh_d_cr are the handle's parameters.
+ *
+ * The separation of two occupied slots i != j at sample k, fp64 without contraction:
+ *   1. broad phase: dx = cx_i - cx_j, dy = cy_i - cy_j, d2 = dx * dx + dy * dy; R = range + 2.0 * rad with rad = sqrt(0.25 * L * L +
+ *      0.25 * W * W), L = veh_length, W = veh_width.  The pair-sample contributes NOTHING when !(d2 <= R * R).  This is part of
+ *      the definition, not an optimisation: a pair further apart than that is not reported even to a slot with no nearer
+ *      partner, and a pose that is not finite contributes nothing.
+ *   2. overlap: the separating-axis test on the four axes, (cs, sn) and (-sn, cs) of both boxes.  For the axis owner A the other
+ *      box's four corners p are taken into A's frame, lx = cs * (px - cx) + sn * (py - cy), ly = cs * (py - cy) - sn * (px - cx);
+ *      A's x axis separates when all four lx > L / 2 or all four lx < -L / 2, its y axis likewise with ly and W / 2.  No axis
+ *      separates: sep = 0.0.
+ *   3. otherwise sep = sqrt(m), m the minimum of the 32 squared point-to-segment distances, each box's four corners p against the
+ *      other's four edges a -> b (corner 1 -> 2 -> 3 -> 4 -> 1): u = ((p - a) . (b - a)) / ((b - a) . (b - a)), clamped to [0, 1]
+ *      (!(u > 0) gives 0), q = a + u * (b - a), e = p - q, and the distance is ex * ex + ey * ey.
+ *   4. sep(i, j, k) and sep(j, i, k) are the SAME BITS: dx and dy are only squared, and steps 2 and 3 are conjunctions and minima
+ *      over one set of values whichever box is named first.
+ *
+ * Per slot i, each a lexicographic minimum, so no order of reduction shows:
+ *   min_sep, sep_sample, sep_partner     the minimum of (sep, k, j) over all contributing pair-samples
+ *   conflict_sample, conflict_partner    the minimum of (k, j) over the pair-samples with sep <= margin (an overlap always
+ *                                        conflicts; margin = 0 is legal)
+ * An empty slot, a slot with nothing inside the broad phase, and every slot before the table was filled once give +inf, -1, -1,
+ * -1, -1.  Neither the table nor the publisher's state is written.
+ *
+ * dftpav_planner_check_conflicts(p, t0, dt, K, margin, range, out): the five rows [max_queries]; any pointer of out may be NULL.
+ * dftpav_planner_sample_poses(p, t0, dt, K, poses): the pose half alone, poses [K][max_queries][4] = cx, cy, cs, sn; NaN rows for
+ *   empty slots (and for every slot before the table was filled once).
+ * dftpav_conflicts_last_ms: device time in ms (the handle's HIP events) of the pose kernel and of the pair and reduce kernels
+ *   together, of the last of the two calls above; 0.0 for what has not run.  Either pointer may be NULL.
+ * DFTPAV_E_INVALID, and nothing changed: p, out or poses NULL; K < 1 or K > DFTPAV_CONFLICT_MAX_SAMPLES; dt <= 0 or not finite;
+ * t0 not finite; margin < 0 or NaN; range < margin or not finite (so a margin of +inf is refused with every range).
+ *
+ * Not claimed.  The heading is getAngle's: a plan sampled exactly at rest has the heading atan2(0, 0) = 0, as in the collision
+ * re-check.  Between samples nothing is tested: choose dt against margin and the speed limit (two vehicles closing at 2 v_max move
+ * 2 v_max dt between clocks).  Every slot is the handle's one vehicle size.  The moving obstacles of dftpav_set_surround take no
+ * part. */
+#define DFTPAV_CONFLICT_MAX_SAMPLES 4096 /* the cap on K, as the publisher's (the poses are 32 K * slots bytes of device memory) */
+typedef struct dftpav_conflict_out {
+  double *min_sep;                                                      /* [max_queries] */
+  int *sep_sample, *sep_partner, *conflict_sample, *conflict_partner;   /* [max_queries] */
+} dftpav_conflict_out; /* any may be NULL */
+int dftpav_planner_check_conflicts(dftpav_planner *p, double t0, double dt, int K, double margin, double range, const dftpav_conflict_out *out);
+int dftpav_planner_sample_poses(dftpav_planner *p, double t0, double dt, int K, double *poses /*[K][max_queries][4]*/);
+int dftpav_conflicts_last_ms(dftpav_handle *h, float *pose_ms, float *pair_ms);
+
 /* One-shot convenience == OptimizeTrajectory for B trajectories. */
 int dftpav_solve_batch(dftpav_handle *h, const dftpav_layout *layout, int B,
                        const dftpav_batch_data *d, double *x, double *final_cost,
