@@ -254,21 +254,13 @@ extern "C" void dftpav_destroy(dftpav_handle *h) {
   if (h->d_search_ws) (void)hipFree(h->d_search_ws);
   for (hipEvent_t &e : h->mark)
     if (e) (void)hipEventDestroy(e);
-  if (h->cev0) (void)hipEventDestroy(h->cev0);
-  if (h->cev1) (void)hipEventDestroy(h->cev1);
-  if (h->lev0) (void)hipEventDestroy(h->lev0);
-  if (h->lev1) (void)hipEventDestroy(h->lev1);
   if (h->d_dist) (void)hipFree(h->d_dist);
-  for (hipEvent_t e : {h->fev0, h->fev1, h->kev0, h->kev1, h->qev[0], h->qev[1], h->qev[2]})
-    if (e) (void)hipEventDestroy(e);
   if (h->d_gf) (void)hipFree(h->d_gf);
   if (h->d_gf_meta) (void)hipFree(h->d_gf_meta);
-  for (hipEvent_t e : h->gf_ev) (void)hipEventDestroy(e);
   if (h->d_rs) (void)hipFree(h->d_rs);
-  for (hipEvent_t e : {h->rs_ev0, h->rs_ev1})
-    if (e) (void)hipEventDestroy(e);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  const hipStream_t stream = h->stream;
+  delete h; // every EventMarks of the handle releases its events here: in front of their stream
+  if (stream) (void)hipStreamDestroy(stream);
 }
 
 extern "C" const char *dftpav_last_error(const dftpav_handle *h) { return h ? h->err.c_str() : "null handle"; }
@@ -486,9 +478,7 @@ extern "C" void dftpav_batch_destroy(dftpav_batch *b) {
   }
   if (b->h_stage) (void)hipHostFree(b->h_stage);
   if (b->stage_ev) (void)hipEventDestroy(b->stage_ev);
-  if (b->ev0) (void)hipEventDestroy(b->ev0);
-  if (b->ev1) (void)hipEventDestroy(b->ev1);
-  delete b;
+  delete b; // (solve_ev's events with it)
 }
 
 // the kernels' view of a layout: offsets of the segments' pieces, waypoints, right-hand-side rows and constraint points, and of
@@ -757,8 +747,6 @@ static int batch_create_impl(dftpav_handle *h, const dftpav_layout *layout, int 
   BCHK(hipMalloc(&b->d_coef, sizeof(double) * (size_t)B * 12 * L.Ntot));
   BCHK(hipMalloc(&b->d_dt, sizeof(double) * (size_t)B * M));
   BCHK(hipMalloc(&b->d_terms, sizeof(double) * (size_t)B * kCostTerms * (M + 1))); // terms [B][5] | seg_terms [B][M][5]
-  BCHK(hipEventCreate(&b->ev0));
-  BCHK(hipEventCreate(&b->ev1));
   // constraint point -> (piece, j) tables, the pointid order of traj_optimizer.cpp:486-514
   {
     std::vector<int16_t> pp(L.Npts), pj(L.Npts);
@@ -1427,7 +1415,7 @@ int dftpav::finish_pending(dftpav_batch *b) {
   if (int rc = sync_dev(b, D)) return rc;
   if (b->hand_over > 0)
     if (int rc = launch_stragglers(b, D, 2)) return rc;
-  HIPCHK(h, hipEventRecord(b->ev1, h->stream));
+  HIPCHK(h, b->solve_ev.record(1, h->stream));
   b->pending = false;
   return DFTPAV_OK;
 }
@@ -1449,7 +1437,7 @@ int dftpav::solve_impl(dftpav_batch *b, dftpav_batch *prev, bool chained) {
     if (int rc = finish_pending(prev)) return rc;
   DevBatch D;
   if (int rc = sync_dev(b, D)) return rc;
-  HIPCHK(h, hipEventRecord(b->ev0, h->stream));
+  HIPCHK(h, b->solve_ev.record(0, h->stream));
   if (b->order == DFTPAV_ORDER_REFERENCE) {
     if (b->ref_plan.ring) {
       // more trajectories than resident waves: persistent workgroups whose waves pop trajectories from the ring and run them a
@@ -1476,7 +1464,7 @@ int dftpav::solve_impl(dftpav_batch *b, dftpav_batch *prev, bool chained) {
       // whatever of the adopted trajectories met this batch's end game: finished in the latency shape (normally none:
       // the workgroups of this launch leave at once)
       if (int rc = launch_stragglers(prev, Dprev, 3)) return rc;
-      HIPCHK(h, hipEventRecord(prev->ev1, h->stream));
+      HIPCHK(h, prev->solve_ev.record(1, h->stream));
       prev->pending = false;
     } else {
       HIPCHK(h, launch_solver(D, b->d_dev, kModeSolve, b->threads, grid, SchedArgs{1, b->slice, b->hand_over, nullptr}, h->stream));
@@ -1487,8 +1475,8 @@ int dftpav::solve_impl(dftpav_batch *b, dftpav_batch *prev, bool chained) {
       if (int rc = launch_stragglers(b, D, 2)) return rc;
     }
   }
-  HIPCHK(h, hipEventRecord(b->ev1, h->stream));
-  b->timed = true;
+  HIPCHK(h, b->solve_ev.record(1, h->stream));
+  b->solve_ev.complete();
   b->solved = true;
   b->coef_override = false;
   return DFTPAV_OK;
@@ -1544,11 +1532,10 @@ extern "C" int dftpav_batch_sync(dftpav_batch *b) {
 }
 
 extern "C" int dftpav_batch_last_solve_ms(dftpav_batch *b, float *ms) {
-  if (!b || !ms || !b->timed) return DFTPAV_E_INVALID;
+  if (!b || !ms || !b->solve_ev.reached()) return DFTPAV_E_INVALID;
   dftpav_handle *h = b->h;
   HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipEventSynchronize(b->ev1));
-  HIPCHK(h, hipEventElapsedTime(ms, b->ev0, b->ev1));
+  HIPCHK(h, b->solve_ev.elapsed(ms, 0, 1, true));
   return DFTPAV_OK;
 }
 

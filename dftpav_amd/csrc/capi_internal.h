@@ -5,6 +5,8 @@
 //   capi_planner.cpp  dftpav_plan_queries, the executing table, the replan check / tick, the publisher
 //   capi_comm.cpp     RCCL                capi_wire.cpp     the "DPTJ" serialisation
 // There is deliberately no CPU fallback: without a usable HIP device every entry point that needs one fails with DFTPAV_E_NO_DEVICE.
+// Device times are taken with EventMarks<N> (below) alone: the events exist from their first record on, complete(k) is the one flag a
+// read-out tests before it asks for elapsed(), and the owner's `delete` releases them (dftpav_destroy: in front of the stream).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,6 +16,8 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -94,6 +98,38 @@ hipError_t launch_quadm_corridor(const DevBatch &D, double *cor_t, hipStream_t s
 }
 using namespace dftpav;
 
+// N marks on a stream and the time between any two of them.  A chain of enqueued work records mark k in front of or behind its
+// kernels; reset() at its start and complete(k) at its end -- "the last chain that used these marks ran up to mark k" -- make the
+// flag that a read-out tests with reached(k).  A chain that never calls reset() keeps reporting its last complete run.  The events
+// are created by their first record and destroyed with the object: the owner is deleted with its device current and, where it
+// owns the stream, in front of the stream's destruction.
+template <int N> struct EventMarks {
+  hipEvent_t ev[N] = {};
+  int done = 0; // marks [0, done) are those of a complete chain
+  EventMarks() = default;
+  EventMarks(const EventMarks &) = delete;
+  EventMarks &operator=(const EventMarks &) = delete;
+  ~EventMarks() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  hipError_t record(int k, hipStream_t stream) {
+    if (!ev[k])
+      if (hipError_t e = hipEventCreate(&ev[k])) return e;
+    return hipEventRecord(ev[k], stream);
+  }
+  void reset() { done = 0; }
+  void complete(int k = N - 1) { done = k + 1; }
+  bool reached(int k = N - 1) const { return done > k; }
+  // ms from mark a to mark b.  wait: synchronises on mark b first -- for the chains that return without a wait for the stream; the
+  // read-outs of chains that end with one pass false.  The caller has tested reached(b).
+  hipError_t elapsed(float *ms, int a, int b, bool wait) const {
+    if (wait)
+      if (hipError_t e = hipEventSynchronize(ev[b])) return e;
+    return hipEventElapsedTime(ms, ev[a], ev[b]);
+  }
+};
+
 struct CommShared; // capi_comm.cpp: an RCCL communicator and its holders
 
 struct dftpav_handle {
@@ -113,19 +149,16 @@ struct dftpav_handle {
   unsigned *d_bits = nullptr; // one bit per cell, when the whole map fits in a quarter of the LDS
   double *d_dl = nullptr;
   int n_dl = 0;
-  hipEvent_t cev0 = nullptr, cev1 = nullptr; // around the last corridor kernel
-  hipEvent_t mark[2] = {nullptr, nullptr};   // dftpav_mark
-  bool ctimed = false;
-  hipEvent_t lev0 = nullptr, lev1 = nullptr; // around the last limits kernel of a check_limits call
-  bool ltimed = false;
+  EventMarks<2> cor_ev;                    // around the last kernel of the corridor family (dftpav_corridor_last_ms)
+  hipEvent_t mark[2] = {nullptr, nullptr}; // dftpav_mark
+  EventMarks<2> lim_ev;                    // around the last limits kernel of a check_limits call
   // the distance field of the map (distfield.hip): built by the first clearance call after a dftpav_set_grid_map, never otherwise
   int *d_dist = nullptr; // one allocation: d2 [cells], then the row pass's g [cells]
   size_t dist_cells = 0; // what d_dist holds room for
   bool dist_stale = true;
-  hipEvent_t fev0 = nullptr, fev1 = nullptr, kev0 = nullptr, kev1 = nullptr; // around the last field build / the last clearance kernel of a check call
-  bool ftimed = false, ktimed = false;
-  hipEvent_t qev[3] = {nullptr, nullptr, nullptr}; // conflict.hip: in front of the pose kernel, between it and the pair kernel, behind the reduce kernel
-  bool qpose_timed = false, qpair_timed = false;   // of the last dftpav_planner_sample_poses / _check_conflicts call
+  EventMarks<2> field_ev, clr_ev; // around the last field build / the last clearance kernel of a check call
+  EventMarks<3> conf_ev; // conflict.hip: in front of the pose kernel, between it and the pair kernel, behind the reduce kernel; of the
+                         // last dftpav_planner_sample_poses (complete to mark 1) / _check_conflicts (to mark 2) call
   // the search heuristic (dftpav_set_search_heuristic) and the workspace of the goal fields (goalfield.hip): nothing of it is
   // allocated or launched until a call asks for a field
   dftpav_goal_field_params heu{0, 0.0, 0.0};
@@ -137,8 +170,8 @@ struct dftpav_handle {
                             // even count, offsets [goals] as 64-bit,) n_reached [goals]
   size_t gf_meta_ints = 0;
   std::vector<int> gf_host; // the host copy of all of it but n_reached (the source of an asynchronous copy)
-  std::vector<hipEvent_t> gf_ev; // a pair around every turn's build
-  int gf_timed = 0;              // pairs recorded by the last call that built fields
+  std::deque<EventMarks<2>> gf_ev; // a pair around every turn's build
+  int gf_timed = 0;                // pairs recorded by the last call that built fields
   // the Reeds-Shepp term of the search heuristic (dftpav_set_search_rs_heuristic) and its table (rstable.hip): built in front of
   // the first search launch that needs it, kept until a call asks for another key (rho, n_yaw, extent, cell)
   dftpav_rs_heuristic_params rsh{0, 0, 0.0, 0.0, 0.0};
@@ -147,7 +180,7 @@ struct dftpav_handle {
   double rs_rho = 0.0, rs_extent = 0.0, rs_cell = 0.0; // the key of what d_rs holds; rs_n_yaw == 0: nothing
   int rs_n_yaw = 0;
   int rs_builds = 0; // launches of rs_table_kernel over the handle's life
-  hipEvent_t rs_ev0 = nullptr, rs_ev1 = nullptr; // around the last build
+  EventMarks<2> rs_ev; // around the last build
   std::vector<struct dftpav_batch *> batches; // every live batch of this handle (obstacle changes finish their chained stragglers)
   // RCCL communicator of dftpav_comm_create (one rank per handle = per GPU), and the staging block of this rank's records
   void *comm = nullptr;
@@ -236,8 +269,7 @@ struct dftpav_batch {
     bool in_flight = false;
   } pc;
   int trace_b = -1, trace_cap = 0, trace_n = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool timed = false;  // a solve was enqueued: ev0 / ev1 are recorded
+  EventMarks<2> solve_ev; // around the last solve; complete once one was enqueued
   bool solved = false; // results of a solve of the CURRENT inputs exist (cleared by dftpav_batch_upload)
 };
 
@@ -323,8 +355,7 @@ struct dftpav_planner {
   size_t out_zero_bytes = 0;
   int *d_winner = nullptr, *d_witers = nullptr, *d_rint[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   double *d_wcost = nullptr, *d_wx = nullptr, *d_wcoef = nullptr, *d_wdt = nullptr, *d_rcost = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool timed = false;
+  EventMarks<4> plan_ev; // dftpav_plan_queries: in front of the search, behind it, behind the resampling, at the end
   std::vector<int> group_sizes;
   // host staging of the tables that decide the grouping
   std::vector<int> h_sints, h_nseg, h_singul, h_pn, h_nstates, h_skip, h_members, h_minit;
@@ -346,8 +377,7 @@ struct dftpav_planner {
   double *d_rc_des = nullptr, *d_rc_st = nullptr, *d_rc_ct = nullptr, *d_rc_goal = nullptr, *d_rc_ego = nullptr, *d_rc_tab = nullptr;
   int rc_n_t = 0, rc_n_v = 0;
   double rc_dt = 0.0, rc_res = 0.0; // what d_rc_tab was tabulated for
-  hipEvent_t rev[4] = {nullptr, nullptr, nullptr, nullptr}; // check start / end, tick start / end
-  bool check_timed = false, tick_timed = false;
+  EventMarks<2> check_ev, tick_ev; // around the last check kernel / the last tick
   // ---- the publisher (dftpav_planner_publish): its state per slot lives in d_exec beside the table; clocks and outputs grow on demand
   PubTable P{};
   int *d_pub_mode = nullptr; // [slots] of d_rc: what an adoption does to the control history of each adopted pair
@@ -355,8 +385,7 @@ struct dftpav_planner {
   size_t pub_ticks = 0; // d_pub holds the clocks and outputs of this many ticks
   double *d_pub_t = nullptr, *d_pub_states = nullptr;
   int *d_pub_code = nullptr;
-  hipEvent_t pev[2] = {nullptr, nullptr};
-  bool pub_timed = false;
+  EventMarks<2> pub_ev; // around the last publish kernel
   // ---- the limit filter (dftpav_planner_set_limit_filter): off by default, and then none of this is touched
   bool lim_on = false;
   dftpav_limits lim{};
@@ -412,6 +441,17 @@ int ensure_coeffs(dftpav_batch *b, DevBatch &D);
 int validate_on_stream(dftpav_batch *b, int n_traj, const double *d_tab, int n_t, int n_v, double check_dt, int *d_col, int *d_first);
 // dftpav_limits as the kernels of limits.hip read it; false: a limit that is not > 0 (a NaN included)
 bool limits_common(const dftpav_params &p, const dftpav_limits &l, LimitsCommon &C);
+// The part the batch and the table form of a check share.  check_limits_rows: C from limits_common; the sample times of check_dt
+// are tabulated and uploaded, n rows max_abs | arg | violated | feasible allocated and wired into C, `launch` runs with the finished
+// C between the marks of h->lim_ev, the rows are fetched into out, and the call waits.  check_clearance_rows likewise: the distance
+// field is ensured, `launch` gets clearance_common with n rows min_d2 | arg | clearance, between the marks of h->clr_ev.
+int check_limits_rows(dftpav_handle *h, double check_dt, size_t n, const dftpav_limits_out *out, LimitsCommon C,
+                      const std::function<hipError_t(const LimitsCommon &)> &launch);
+int check_clearance_rows(dftpav_handle *h, double check_dt, size_t n, const dftpav_clearance_out *out,
+                         const std::function<hipError_t(const ClearanceCommon &)> &launch);
+// copies of n rows to the host on the handle's stream, each unless the caller did not ask for it (nothing waits)
+int fetch_limits(dftpav_handle *h, const dftpav_limits_out *out, const LimitsCommon &C, size_t n);
+int fetch_clearance(dftpav_handle *h, const dftpav_clearance_out *out, const int *d_d2, const int *d_arg, const double *d_m, size_t n);
 // the distance field of the handle's map, built on the handle's stream if the map changed since the last build (nothing waits);
 // DFTPAV_E_INVALID without a map, DFTPAV_E_UNSUPPORTED for a side above 16384 cells
 int ensure_dist_field(dftpav_handle *h);

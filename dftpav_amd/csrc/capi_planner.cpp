@@ -73,13 +73,6 @@ extern "C" int dftpav_planner_create(dftpav_handle *h, int max_queries, int n_re
   p->h = h;
   p->max_queries = max_queries;
   p->R = n_restarts;
-  for (hipEvent_t *evs : {p->ev, p->rev})
-    for (int k = 0; k < 4; k++)
-      if (hipEventCreate(&evs[k]) != hipSuccess) {
-        h->err = "dftpav_planner_create: hipEventCreate";
-        dftpav_planner_destroy(p); // (destroys the events that exist)
-        return DFTPAV_E_HIP;
-      }
   *out = p;
   return DFTPAV_OK;
 }
@@ -95,13 +88,7 @@ extern "C" void dftpav_planner_destroy(dftpav_planner *p) {
   if (p->d_lim) (void)hipFree(p->d_lim);
   if (p->d_pen) (void)hipFree(p->d_pen);
   if (p->d_clr) (void)hipFree(p->d_clr);
-  for (auto &e : p->pev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto &e : p->ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto &e : p->rev)
-    if (e) (void)hipEventDestroy(e);
-  delete p;
+  delete p; // (its EventMarks' events with it)
 }
 
 extern "C" int dftpav_planner_info(dftpav_planner *p, int *n_batches, int *n_groups, int *group_sizes, float *stage_ms) {
@@ -113,13 +100,10 @@ extern "C" int dftpav_planner_info(dftpav_planner *p, int *n_batches, int *n_gro
   if (stage_ms) {
     dftpav_handle *h = p->h;
     for (int k = 0; k < 4; k++) stage_ms[k] = 0.0f;
-    if (p->timed) {
+    if (p->plan_ev.reached()) {
       HIPCHK(h, hipSetDevice(h->device));
-      HIPCHK(h, hipEventSynchronize(p->ev[3]));
-      HIPCHK(h, hipEventElapsedTime(&stage_ms[0], p->ev[0], p->ev[1]));
-      HIPCHK(h, hipEventElapsedTime(&stage_ms[1], p->ev[1], p->ev[2]));
-      HIPCHK(h, hipEventElapsedTime(&stage_ms[2], p->ev[2], p->ev[3]));
-      HIPCHK(h, hipEventElapsedTime(&stage_ms[3], p->ev[0], p->ev[3]));
+      HIPCHK(h, p->plan_ev.elapsed(&stage_ms[3], 0, 3, true)); // (the one wait: mark 3 is the last)
+      for (int k = 0; k < 3; k++) HIPCHK(h, p->plan_ev.elapsed(&stage_ms[k], k, k + 1, false));
     }
   }
   return DFTPAV_OK;
@@ -239,7 +223,7 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
       !(fp.max_backward_acc > 0.0))
     return DFTPAV_E_INVALID;
   p->group_sizes.clear();
-  p->timed = false;
+  p->plan_ev.reset();
   p->last_Q = 0; // nothing to adopt until this call has ended well
   p->last_lim = false;
   p->last_pen = false;
@@ -278,17 +262,17 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
   HIPCHK(h, hipMemsetAsync(p->d_out0, 0, p->out_zero_bytes, h->stream));
   SearchArgs &S = U.S;
   wire_search(U, p->d_tabs, p->d_st, p->d_en, p->d_sints, nq, 0, nullptr, pp->max_path, p->d_paths);
-  HIPCHK(h, hipEventRecord(p->ev[0], h->stream));
+  HIPCHK(h, p->plan_ev.record(0, h->stream));
   for (int q0 = 0; q0 < Q; q0 += U.slots) {
     S.q0 = q0;
     if (G.per_turn)
       if (int rc = goal_field_turn(h, G, q0 / U.slots, &S, nullptr)) return rc;
     HIPCHK(h, launch_search(S, std::min(U.slots, Q - q0), h->stream));
   }
-  HIPCHK(h, hipEventRecord(p->ev[1], h->stream));
+  HIPCHK(h, p->plan_ev.record(1, h->stream));
   HIPCHK(h, launch_plan_paths(S.out.status, S.out.path_len, p->d_skip, Q, pp->max_path, p->d_paths, p->d_fe_len, h->stream));
   HIPCHK(h, launch_frontend(fp, p->d_paths, p->d_fe_len, pp->max_path, p->d_st, p->d_en, p->d_ct, Q, p->fe, h->stream));
-  HIPCHK(h, hipEventRecord(p->ev[2], h->stream));
+  HIPCHK(h, p->plan_ev.record(2, h->stream));
   // ---- the one read-back before the end: the tables that decide the grouping
   p->h_sints.assign(8 * nq, 0);
   p->h_nseg.assign(nq, 0);
@@ -499,8 +483,8 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
     Z.r_first_sample = p->d_rint[5];
     HIPCHK(h, launch_plan_select(Z, h->stream));
   }
-  HIPCHK(h, hipEventRecord(p->ev[3], h->stream));
-  p->timed = true;
+  HIPCHK(h, p->plan_ev.record(3, h->stream));
+  p->plan_ev.complete();
   // ---- the compact results
   std::vector<int> winner(nq, -1);
   p->h_minit.assign(nq, 0);
@@ -946,10 +930,10 @@ static int replan_check_enqueue(dftpav_planner *p, double t_now, double budget, 
   A.desired = p->d_rc_des;
   A.start_state = p->d_rc_st;
   A.start_ctrl = p->d_rc_ct;
-  HIPCHK(h, hipEventRecord(p->rev[0], h->stream));
+  HIPCHK(h, p->check_ev.record(0, h->stream));
   HIPCHK(h, launch_replan_check(A, h->stream));
-  HIPCHK(h, hipEventRecord(p->rev[1], h->stream));
-  p->check_timed = true;
+  HIPCHK(h, p->check_ev.record(1, h->stream));
+  p->check_ev.complete(); // (never reset: a check that fails leaves the read-out answering)
   return DFTPAV_OK;
 }
 
@@ -989,9 +973,9 @@ extern "C" int dftpav_replan_tick(dftpav_planner *p, const dftpav_plan_params *p
   if (!p->d_exec) { // an all-empty table is a valid start (every vehicle waits for its first plan)
     if (int rc = exec_table(p, pp->max_seg, pp->max_pieces)) return rc;
   }
-  p->tick_timed = false;
+  p->tick_ev.reset();
   HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipEventRecord(p->rev[2], h->stream));
+  HIPCHK(h, p->tick_ev.record(0, h->stream));
   if (int rc = replan_check_enqueue(p, t_now, budget, end_states, ego_states, pp->check_dt, pp->vertex_res)) return rc;
   // ---- the tick's one extra wait: replan, start_state, start_ctrl (with whatever else of the check the caller asked for)
   const size_t S = (size_t)p->max_queries;
@@ -1025,8 +1009,8 @@ extern "C" int dftpav_replan_tick(dftpav_planner *p, const dftpav_plan_params *p
     for (int q = 0; q < nq; q++) qi[q] = q;
     if (int rc = adopt_impl(p, nq, qi.data(), slot_of.data(), stamp, p->d_rc_des, nullptr)) return rc;
   }
-  HIPCHK(h, hipEventRecord(p->rev[3], h->stream));
-  p->tick_timed = true;
+  HIPCHK(h, p->tick_ev.record(1, h->stream));
+  p->tick_ev.complete();
   return DFTPAV_OK;
 }
 
@@ -1036,14 +1020,8 @@ extern "C" int dftpav_replan_last_ms(dftpav_planner *p, float *check_ms, float *
   if (check_ms) *check_ms = 0.0f;
   if (tick_ms) *tick_ms = 0.0f;
   HIPCHK(h, hipSetDevice(h->device));
-  if (check_ms && p->check_timed) {
-    HIPCHK(h, hipEventSynchronize(p->rev[1]));
-    HIPCHK(h, hipEventElapsedTime(check_ms, p->rev[0], p->rev[1]));
-  }
-  if (tick_ms && p->tick_timed) {
-    HIPCHK(h, hipEventSynchronize(p->rev[3]));
-    HIPCHK(h, hipEventElapsedTime(tick_ms, p->rev[2], p->rev[3]));
-  }
+  if (check_ms && p->check_ev.reached()) HIPCHK(h, p->check_ev.elapsed(check_ms, 0, 1, true));
+  if (tick_ms && p->tick_ev.reached()) HIPCHK(h, p->tick_ev.elapsed(tick_ms, 0, 1, true));
   return DFTPAV_OK;
 }
 
@@ -1055,8 +1033,6 @@ extern "C" int dftpav_planner_publish(dftpav_planner *p, int K, const double *t,
   dftpav_handle *h = p->h;
   HIPCHK(h, hipSetDevice(h->device));
   const size_t S = (size_t)p->max_queries;
-  for (auto &e : p->pev)
-    if (!e) HIPCHK(h, hipEventCreate(&e));
   if ((size_t)K > p->pub_ticks) { // the clocks and the outputs of K ticks: one allocation, grown to the largest K met
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (p->d_pub) (void)hipFree(p->d_pub);
@@ -1073,7 +1049,7 @@ extern "C" int dftpav_planner_publish(dftpav_planner *p, int K, const double *t,
     p->d_pub = base;
     p->pub_ticks = (size_t)K;
   }
-  p->pub_timed = false;
+  p->pub_ev.reset();
   HIPCHK(h, hipMemcpyAsync(p->d_pub_t, t, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, h->stream));
   PublishArgs A{};
   A.T = p->T;
@@ -1083,10 +1059,10 @@ extern "C" int dftpav_planner_publish(dftpav_planner *p, int K, const double *t,
   A.wheel_base = h->params.veh_wheel_base;
   A.states = states ? p->d_pub_states : nullptr;
   A.published = published ? p->d_pub_code : nullptr;
-  HIPCHK(h, hipEventRecord(p->pev[0], h->stream));
+  HIPCHK(h, p->pub_ev.record(0, h->stream));
   HIPCHK(h, launch_publish(A, h->stream));
-  HIPCHK(h, hipEventRecord(p->pev[1], h->stream));
-  p->pub_timed = true;
+  HIPCHK(h, p->pub_ev.record(1, h->stream));
+  p->pub_ev.complete();
   if (states) HIPCHK(h, hipMemcpyAsync(states, p->d_pub_states, sizeof(double) * 8 * S * (size_t)K, hipMemcpyDeviceToHost, h->stream));
   if (published) HIPCHK(h, hipMemcpyAsync(published, p->d_pub_code, sizeof(int) * S * (size_t)K, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream)); // the one wait: `t` has left the host, the outputs have arrived
@@ -1115,10 +1091,9 @@ extern "C" int dftpav_publish_last_ms(dftpav_planner *p, float *ms) {
   if (!p || !ms) return DFTPAV_E_INVALID;
   dftpav_handle *h = p->h;
   *ms = 0.0f;
-  if (!p->pub_timed) return DFTPAV_OK;
+  if (!p->pub_ev.reached()) return DFTPAV_OK;
   HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipEventSynchronize(p->pev[1]));
-  HIPCHK(h, hipEventElapsedTime(ms, p->pev[0], p->pev[1]));
+  HIPCHK(h, p->pub_ev.elapsed(ms, 0, 1, true));
   return DFTPAV_OK;
 }
 
@@ -1154,19 +1129,11 @@ template <class F> static int cached_table(dftpav_planner *p, double check_dt, d
 }
 
 // ------------------------------------------------- solved plans against the kinematic limits (limits.hip)
-static int fetch_limits(dftpav_handle *h, const dftpav_limits_out *out, const LimitsCommon &C, size_t rows) {
-  HIPCHK(h, fetch_async(h, out->max_abs, C.max_abs, sizeof(double) * kLimQ * rows));
-  HIPCHK(h, fetch_async(h, out->arg, C.arg, sizeof(int) * kLimQ * rows));
-  HIPCHK(h, fetch_async(h, out->violated, C.violated, sizeof(int) * kLimQ * rows));
-  HIPCHK(h, fetch_async(h, out->feasible, C.feasible, sizeof(int) * rows));
-  return DFTPAV_OK;
-}
-
 extern "C" int dftpav_planner_check_limits(dftpav_planner *p, double check_dt, const dftpav_limits *l, const dftpav_limits_out *out) {
   if (!p || !l || !out || !(check_dt > 0.0) || !std::isfinite(check_dt)) return DFTPAV_E_INVALID;
   dftpav_handle *h = p->h;
-  LimitsTableArgs A{};
-  if (!limits_common(h->params, *l, A.C)) return DFTPAV_E_INVALID;
+  LimitsCommon C{};
+  if (!limits_common(h->params, *l, C)) return DFTPAV_E_INVALID;
   const size_t S = (size_t)p->max_queries;
   if (!p->d_exec) { // nothing was ever installed: every slot is empty
     if (out->max_abs) std::fill(out->max_abs, out->max_abs + kLimQ * S, 0.0);
@@ -1176,32 +1143,9 @@ extern "C" int dftpav_planner_check_limits(dftpav_planner *p, double check_dt, c
     return DFTPAV_OK;
   }
   HIPCHK(h, hipSetDevice(h->device));
-  std::vector<double> tab;
-  int n_t = 0, n_v = 0;
-  if (int rc = validation_table(h->params, check_dt, 1.0, 0, tab, &n_t, &n_v)) return rc; // (the sample times are its first n_t entries)
-  if (!h->lev0) HIPCHK(h, hipEventCreate(&h->lev0));
-  if (!h->lev1) HIPCHK(h, hipEventCreate(&h->lev1));
-  double *d_tab = nullptr, *d_max = nullptr;
-  int *d_int = nullptr; // arg | violated | feasible
-  DevScratch tmp(h);
-  HIPCHK(h, tmp.alloc(d_tab, (size_t)n_t));
-  HIPCHK(h, tmp.alloc(d_max, kLimQ * S));
-  HIPCHK(h, tmp.alloc(d_int, (2 * kLimQ + 1) * S));
-  A.C.tab = SampleTable{d_tab, n_t, check_dt};
-  A.C.max_abs = d_max;
-  A.C.arg = d_int;
-  A.C.violated = d_int + kLimQ * S;
-  A.C.feasible = d_int + 2 * kLimQ * S;
-  A.T = p->T;
-  h->ltimed = false; // until the whole chain has run
-  HIPCHK(h, hipMemcpyAsync(d_tab, tab.data(), sizeof(double) * (size_t)n_t, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipEventRecord(h->lev0, h->stream));
-  HIPCHK(h, launch_limits_table(A, h->stream));
-  HIPCHK(h, hipEventRecord(h->lev1, h->stream));
-  if (int rc = fetch_limits(h, out, A.C, S)) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->ltimed = true;
-  return DFTPAV_OK;
+  return check_limits_rows(h, check_dt, S, out, C, [&](const LimitsCommon &done) {
+    return launch_limits_table(LimitsTableArgs{done, p->T}, h->stream);
+  });
 }
 
 extern "C" int dftpav_planner_set_limit_filter(dftpav_planner *p, const dftpav_limits *l, double check_dt) {
@@ -1280,13 +1224,6 @@ extern "C" int dftpav_planner_last_cost_terms(dftpav_planner *p, double *r_terms
 }
 
 // ------------------------------------------------- the clearance of executing plans, and the clearance filter (clearance.hip)
-static int fetch_clearance(dftpav_handle *h, const dftpav_clearance_out *out, const int *d_d2, const int *d_arg, const double *d_m, size_t rows) {
-  HIPCHK(h, fetch_async(h, out->min_d2, d_d2, sizeof(int) * rows));
-  HIPCHK(h, fetch_async(h, out->arg, d_arg, sizeof(int) * rows));
-  HIPCHK(h, fetch_async(h, out->clearance, d_m, sizeof(double) * rows));
-  return DFTPAV_OK;
-}
-
 extern "C" int dftpav_planner_check_clearance(dftpav_planner *p, double check_dt, const dftpav_clearance_out *out) {
   if (!p || !out || !(check_dt > 0.0) || !std::isfinite(check_dt)) return DFTPAV_E_INVALID;
   dftpav_handle *h = p->h;
@@ -1299,33 +1236,9 @@ extern "C" int dftpav_planner_check_clearance(dftpav_planner *p, double check_dt
     return DFTPAV_OK;
   }
   HIPCHK(h, hipSetDevice(h->device));
-  if (int rc = ensure_dist_field(h)) return rc;
-  std::vector<double> tab;
-  int n_t = 0, n_v = 0;
-  if (int rc = validation_table(h->params, check_dt, kClearanceVertexRes, 0, tab, &n_t, &n_v)) return rc;
-  for (hipEvent_t *e : {&h->kev0, &h->kev1})
-    if (!*e) HIPCHK(h, hipEventCreate(e));
-  double *d_tab = nullptr, *d_m = nullptr;
-  int *d_int = nullptr; // min_d2 | arg
-  DevScratch tmp(h);
-  HIPCHK(h, tmp.alloc(d_tab, tab.size()));
-  HIPCHK(h, tmp.alloc(d_m, S));
-  HIPCHK(h, tmp.alloc(d_int, 2 * S));
-  ClearanceTableArgs A{};
-  A.C = clearance_common(h, d_tab, n_t, n_v, check_dt);
-  A.C.min_d2 = d_int;
-  A.C.arg = d_int + S;
-  A.C.clearance = d_m;
-  A.T = p->T;
-  h->ktimed = false; // until the whole chain has run
-  HIPCHK(h, hipMemcpyAsync(d_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipEventRecord(h->kev0, h->stream));
-  HIPCHK(h, launch_clearance_table(A, h->stream));
-  HIPCHK(h, hipEventRecord(h->kev1, h->stream));
-  if (int rc = fetch_clearance(h, out, A.C.min_d2, A.C.arg, A.C.clearance, S)) return rc;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->ktimed = true;
-  return DFTPAV_OK;
+  return check_clearance_rows(h, check_dt, S, out, [&](const ClearanceCommon &C) {
+    return launch_clearance_table(ClearanceTableArgs{C, p->T}, h->stream);
+  });
 }
 
 extern "C" int dftpav_planner_set_clearance_filter(dftpav_planner *p, double min_clearance, double check_dt) {
@@ -1363,11 +1276,9 @@ static bool conflict_clocks_ok(double t0, double dt, int K) {
   return K >= 1 && K <= DFTPAV_CONFLICT_MAX_SAMPLES && dt > 0.0 && std::isfinite(dt) && std::isfinite(t0);
 }
 
-// the poses of every slot at the K clocks into buffers of `tmp`, on the handle's stream between qev[0] and qev[1] (nothing waits)
+// the poses of every slot at the K clocks into buffers of `tmp`, on the handle's stream between marks 0 and 1 of conf_ev (nothing waits)
 static int conflict_poses_on_stream(dftpav_planner *p, DevScratch &tmp, double t0, double dt, int K, ConflictPoses &P) {
   dftpav_handle *h = p->h;
-  for (hipEvent_t &e : h->qev)
-    if (!e) HIPCHK(h, hipEventCreate(&e));
   const int S_pad = (p->max_queries + kConflictTile - 1) / kConflictTile * kConflictTile;
   const size_t n = (size_t)K * S_pad;
   double *d_pose = nullptr;
@@ -1385,10 +1296,10 @@ static int conflict_poses_on_stream(dftpav_planner *p, DevScratch &tmp, double t
   A.t0 = t0;
   A.dt = dt;
   A.dcr = h->params.veh_d_cr;
-  h->qpose_timed = h->qpair_timed = false; // until the whole chain has run
-  HIPCHK(h, hipEventRecord(h->qev[0], h->stream));
+  h->conf_ev.reset(); // until the whole chain has run
+  HIPCHK(h, h->conf_ev.record(0, h->stream));
   HIPCHK(h, launch_conflict_poses(A, h->stream));
-  HIPCHK(h, hipEventRecord(h->qev[1], h->stream));
+  HIPCHK(h, h->conf_ev.record(1, h->stream));
   return DFTPAV_OK;
 }
 
@@ -1411,7 +1322,7 @@ extern "C" int dftpav_planner_sample_poses(dftpav_planner *p, double t0, double 
   for (size_t k = 0; k < (size_t)K; k++)
     for (size_t s = 0; s < S; s++)
       for (size_t c = 0; c < 4; c++) poses[(k * S + s) * 4 + c] = soa[c * n + k * P.S_pad + s];
-  h->qpose_timed = true;
+  h->conf_ev.complete(1); // the poses alone
   return DFTPAV_OK;
 }
 
@@ -1456,14 +1367,14 @@ extern "C" int dftpav_planner_check_conflicts(dftpav_planner *p, double t0, doub
   Rd.tiles = (int)tiles;
   HIPCHK(h, launch_conflict_pairs(A, h->stream));
   HIPCHK(h, launch_conflict_reduce(Rd, h->stream));
-  HIPCHK(h, hipEventRecord(h->qev[2], h->stream));
+  HIPCHK(h, h->conf_ev.record(2, h->stream));
   HIPCHK(h, fetch_async(h, out->min_sep, Rd.out.min_sep, sizeof(double) * S));
   HIPCHK(h, fetch_async(h, out->sep_sample, Rd.out.sep_sample, sizeof(int) * S));
   HIPCHK(h, fetch_async(h, out->sep_partner, Rd.out.sep_partner, sizeof(int) * S));
   HIPCHK(h, fetch_async(h, out->conflict_sample, Rd.out.conflict_sample, sizeof(int) * S));
   HIPCHK(h, fetch_async(h, out->conflict_partner, Rd.out.conflict_partner, sizeof(int) * S));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->qpose_timed = h->qpair_timed = true;
+  h->conf_ev.complete();
   return DFTPAV_OK;
 }
 
@@ -1472,7 +1383,7 @@ extern "C" int dftpav_conflicts_last_ms(dftpav_handle *h, float *pose_ms, float 
   if (pose_ms) *pose_ms = 0.0f;
   if (pair_ms) *pair_ms = 0.0f;
   HIPCHK(h, hipSetDevice(h->device));
-  if (pose_ms && h->qpose_timed) HIPCHK(h, hipEventElapsedTime(pose_ms, h->qev[0], h->qev[1])); // (both calls waited for the stream)
-  if (pair_ms && h->qpair_timed) HIPCHK(h, hipEventElapsedTime(pair_ms, h->qev[1], h->qev[2]));
+  if (pose_ms && h->conf_ev.reached(1)) HIPCHK(h, h->conf_ev.elapsed(pose_ms, 0, 1, false)); // (both calls waited for the stream)
+  if (pair_ms && h->conf_ev.reached(2)) HIPCHK(h, h->conf_ev.elapsed(pair_ms, 1, 2, false));
   return DFTPAV_OK;
 }

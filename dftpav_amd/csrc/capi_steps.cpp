@@ -89,8 +89,6 @@ extern "C" int dftpav_reeds_shepp_shots(dftpav_handle *h, const double *from, co
   if (!from || !to) return DFTPAV_E_INVALID;
   if (collides && (!h->d_cells || !(vertex_res > 0.0))) return DFTPAV_E_INVALID; // a collision check needs the map
   HIPCHK(h, hipSetDevice(h->device));
-  if (!h->cev0) HIPCHK(h, hipEventCreate(&h->cev0));
-  if (!h->cev1) HIPCHK(h, hipEventCreate(&h->cev1));
   std::vector<double> vv; // spacing of the outline points as the reference's running sum (shapes.cc:128)
   if (collides) {
     const double longest = std::max(h->params.veh_length, h->params.veh_width) + 1.0;
@@ -110,16 +108,16 @@ extern "C" int dftpav_reeds_shepp_shots(dftpav_handle *h, const double *from, co
   HIPCHK(h, tmp.alloc(d_type, nn));
   HIPCHK(h, tmp.alloc(d_ns, nn));
   HIPCHK(h, tmp.alloc(d_col, nn));
-  h->ctimed = false; // until the whole chain has run
+  h->cor_ev.reset(); // until the whole chain has run
   HIPCHK(h, hipMemcpyAsync(d_from, from, sizeof(double) * 3 * nn, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(d_to, to, sizeof(double) * 3 * nn, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(d_v, vv.data(), sizeof(double) * vv.size(), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipEventRecord(h->cev0, h->stream));
+  HIPCHK(h, h->cor_ev.record(0, h->stream));
   ShotArgs A{d_from, d_to, n, 1.0 / max_cur, checkl, max_samples, dev_grid(h), dev_footprint(h, d_v, (int)vv.size()),
              d_len, d_type, d_seg, d_smp, d_ns, d_col};
   if (!collides) A.grid.cells = nullptr; // no collision check
   HIPCHK(h, launch_shots(A, h->stream));
-  HIPCHK(h, hipEventRecord(h->cev1, h->stream));
+  HIPCHK(h, h->cor_ev.record(1, h->stream));
   HIPCHK(h, fetch_async(h, length, d_len, sizeof(double) * nn));
   HIPCHK(h, fetch_async(h, type, d_type, sizeof(int) * nn));
   HIPCHK(h, fetch_async(h, seg, d_seg, sizeof(double) * 5 * nn));
@@ -127,7 +125,7 @@ extern "C" int dftpav_reeds_shepp_shots(dftpav_handle *h, const double *from, co
   HIPCHK(h, fetch_async(h, n_samples, d_ns, sizeof(int) * nn));
   HIPCHK(h, fetch_async(h, collides, d_col, sizeof(int) * nn));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->ctimed = true;
+  h->cor_ev.complete();
   return DFTPAV_OK;
 }
 
@@ -249,8 +247,6 @@ int dftpav::search_setup(dftpav_handle *h, const dftpav_search_params *sp, int n
   std::vector<double> ll;
   for (double l = 0.0; (int)ll.size() < (int)n_l_need; l += P.checkl) ll.push_back(l); // kino_astar.cpp:338, 594
   HIPCHK(h, hipSetDevice(h->device));
-  if (!h->cev0) HIPCHK(h, hipEventCreate(&h->cev0));
-  if (!h->cev1) HIPCHK(h, hipEventCreate(&h->cev1));
   const SearchWorkspace W = search_workspace(P, n);
   const int hcap = W.hcap, slots = W.slots;
   const size_t ws = W.bytes;
@@ -323,7 +319,7 @@ extern "C" int dftpav_kino_search(dftpav_handle *h, const dftpav_search_params *
   HIPCHK(h, tmp.alloc(d_ints, 9 * nn));
   if (out->max_nodes > 0) HIPCHK(h, tmp.alloc(d_nodes, n_nodes));
   if (out->max_path > 0) HIPCHK(h, tmp.alloc(d_paths, n_paths));
-  h->ctimed = false; // until the whole chain has run
+  h->cor_ev.reset(); // until the whole chain has run
   HIPCHK(h, hipMemcpyAsync(d_tabs, U.tabs.data(), sizeof(double) * U.tabs.size(), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(d_st, start_states, sizeof(double) * 4 * nn, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(d_en, end_states, sizeof(double) * 4 * nn, hipMemcpyHostToDevice, h->stream));
@@ -331,20 +327,20 @@ extern "C" int dftpav_kino_search(dftpav_handle *h, const dftpav_search_params *
   if (d_nodes) HIPCHK(h, hipMemsetAsync(d_nodes, 0, sizeof(double) * n_nodes, h->stream));
   if (d_paths) HIPCHK(h, hipMemsetAsync(d_paths, 0, sizeof(double) * n_paths, h->stream));
   wire_search(U, d_tabs, d_st, d_en, d_ints, nn, out->max_nodes, d_nodes, out->max_path, d_paths);
-  HIPCHK(h, hipEventRecord(h->cev0, h->stream));
+  HIPCHK(h, h->cor_ev.record(0, h->stream));
   for (int q0 = 0; q0 < n; q0 += U.slots) {
     U.S.q0 = q0;
     if (G.per_turn)
       if (int rc = goal_field_turn(h, G, q0 / U.slots, &U.S, nullptr)) return rc;
     HIPCHK(h, launch_search(U.S, std::min(U.slots, n - q0), h->stream));
   }
-  HIPCHK(h, hipEventRecord(h->cev1, h->stream));
+  HIPCHK(h, h->cor_ev.record(1, h->stream));
   int *const fields[8] = {out->status, out->shot_success, out->used_3d, out->budget_hit, out->iters, out->nodes_used, out->n_nodes, out->path_len};
   for (int f = 0; f < 8; f++) HIPCHK(h, hipMemcpyAsync(fields[f], d_ints + f * nn, sizeof(int) * nn, hipMemcpyDeviceToHost, h->stream));
   if (d_nodes) HIPCHK(h, hipMemcpyAsync(out->nodes, d_nodes, sizeof(double) * n_nodes, hipMemcpyDeviceToHost, h->stream));
   if (d_paths) HIPCHK(h, hipMemcpyAsync(out->paths, d_paths, sizeof(double) * n_paths, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->ctimed = true;
+  h->cor_ev.complete();
   for (int q = 0; q < n; q++)
     if (out->status[q] == 0) return DFTPAV_E_UNSUPPORTED; // a shot beyond the sample table (not reached: see the bound)
   return DFTPAV_OK;
@@ -405,8 +401,6 @@ extern "C" int dftpav_set_grid_map(dftpav_handle *h, const dftpav_grid_map *map)
   h->n_dl = (int)dl.size();
   HIPCHK(h, hipMalloc(&h->d_dl, sizeof(double) * dl.size()));
   HIPCHK(h, hipMemcpy(h->d_dl, dl.data(), sizeof(double) * dl.size(), hipMemcpyHostToDevice));
-  if (!h->cev0) HIPCHK(h, hipEventCreate(&h->cev0));
-  if (!h->cev1) HIPCHK(h, hipEventCreate(&h->cev1));
   return DFTPAV_OK;
 }
 
@@ -423,20 +417,20 @@ static int run_corridor(dftpav_handle *h, const double *states, int n_states, do
   double *d_states = nullptr;
   DevScratch tmp(h);
   HIPCHK(h, tmp.alloc(d_states, 3 * (size_t)n_states));
-  h->ctimed = false; // until the whole chain has run
+  h->cor_ev.reset(); // until the whole chain has run
   HIPCHK(h, hipMemcpyAsync(d_states, states, sizeof(double) * 3 * (size_t)n_states, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipEventRecord(h->cev0, h->stream));
+  HIPCHK(h, h->cor_ev.record(0, h->stream));
   HIPCHK(h, launch_corridor(corridor_args(h, d_states, n_states, d_hpoly, batch_cor, Npts, NptsPad, replicate), h->stream));
-  HIPCHK(h, hipEventRecord(h->cev1, h->stream));
+  HIPCHK(h, h->cor_ev.record(1, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->ctimed = true;
+  h->cor_ev.complete();
   return DFTPAV_OK;
 }
 
 extern "C" int dftpav_corridor_last_ms(dftpav_handle *h, float *ms) {
-  if (!h || !ms || !h->ctimed) return DFTPAV_E_INVALID;
+  if (!h || !ms || !h->cor_ev.reached()) return DFTPAV_E_INVALID;
   HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipEventElapsedTime(ms, h->cev0, h->cev1));
+  HIPCHK(h, h->cor_ev.elapsed(ms, 0, 1, false));
   return DFTPAV_OK;
 }
 
@@ -573,15 +567,15 @@ extern "C" int dftpav_batch_validate(dftpav_batch *b, double sample_dt, double v
   HIPCHK(h, tmp.alloc(d_tab, tab.size()));
   HIPCHK(h, tmp.alloc(d_col, B));
   HIPCHK(h, tmp.alloc(d_first, B));
-  h->ctimed = false; // until the whole chain has run
+  h->cor_ev.reset(); // until the whole chain has run
   HIPCHK(h, hipMemcpyAsync(d_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipEventRecord(h->cev0, h->stream));
+  HIPCHK(h, h->cor_ev.record(0, h->stream));
   if (int rc = validate_on_stream(b, b->B, d_tab, n_t, n_v, sample_dt, d_col, d_first)) return rc;
-  HIPCHK(h, hipEventRecord(h->cev1, h->stream));
+  HIPCHK(h, h->cor_ev.record(1, h->stream));
   HIPCHK(h, fetch_async(h, collision, d_col, sizeof(int) * B));
   HIPCHK(h, fetch_async(h, first_sample, d_first, sizeof(int) * B));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->ctimed = true;
+  h->cor_ev.complete();
   return DFTPAV_OK;
 }
 
@@ -610,54 +604,55 @@ bool dftpav::limits_common(const dftpav_params &p, const dftpav_limits &l, Limit
   return true;
 }
 
-extern "C" int dftpav_batch_check_limits(dftpav_batch *b, double check_dt, const dftpav_limits *l, const dftpav_limits_out *out) {
-  if (!b || !l || !out || !b->uploaded || !b->solved || !(check_dt > 0.0) || !std::isfinite(check_dt)) return DFTPAV_E_INVALID;
-  dftpav_handle *h = b->h;
-  LimitsBatchArgs A{};
-  if (!limits_common(h->params, *l, A.C)) return DFTPAV_E_INVALID;
-  HIPCHK(h, hipSetDevice(h->device));
-  DevBatch D;
-  if (int rc = ensure_coeffs(b, D)) return rc;
-  std::vector<double> tab;
-  int n_t = 0, n_v = 0;
-  if (int rc = validation_table(h->params, check_dt, 1.0, 0, tab, &n_t, &n_v)) return rc; // (the sample times are its first n_t entries)
-  if (!h->lev0) HIPCHK(h, hipEventCreate(&h->lev0));
-  if (!h->lev1) HIPCHK(h, hipEventCreate(&h->lev1));
-  const size_t B = (size_t)b->B;
-  double *d_tab = nullptr, *d_max = nullptr;
-  int *d_int = nullptr; // arg | violated | feasible
-  DevScratch tmp(h);
-  HIPCHK(h, tmp.alloc(d_tab, (size_t)n_t));
-  HIPCHK(h, tmp.alloc(d_max, kLimQ * B));
-  HIPCHK(h, tmp.alloc(d_int, (2 * kLimQ + 1) * B));
-  A.C.tab = SampleTable{d_tab, n_t, check_dt};
-  A.C.max_abs = d_max;
-  A.C.arg = d_int;
-  A.C.violated = d_int + kLimQ * B;
-  A.C.feasible = d_int + 2 * kLimQ * B;
-  A.coeffs = b->d_coef;
-  A.piece_dt = b->d_dt;
-  A.L = b->L;
-  A.B = b->B;
-  A.R = 1;
-  h->ltimed = false; // until the whole chain has run
-  HIPCHK(h, hipMemcpyAsync(d_tab, tab.data(), sizeof(double) * (size_t)n_t, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipEventRecord(h->lev0, h->stream));
-  HIPCHK(h, launch_limits_batch(A, h->stream));
-  HIPCHK(h, hipEventRecord(h->lev1, h->stream));
-  HIPCHK(h, fetch_async(h, out->max_abs, A.C.max_abs, sizeof(double) * kLimQ * B));
-  HIPCHK(h, fetch_async(h, out->arg, A.C.arg, sizeof(int) * kLimQ * B));
-  HIPCHK(h, fetch_async(h, out->violated, A.C.violated, sizeof(int) * kLimQ * B));
-  HIPCHK(h, fetch_async(h, out->feasible, A.C.feasible, sizeof(int) * B));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->ltimed = true;
+int dftpav::fetch_limits(dftpav_handle *h, const dftpav_limits_out *out, const LimitsCommon &C, size_t n) {
+  HIPCHK(h, fetch_async(h, out->max_abs, C.max_abs, sizeof(double) * kLimQ * n));
+  HIPCHK(h, fetch_async(h, out->arg, C.arg, sizeof(int) * kLimQ * n));
+  HIPCHK(h, fetch_async(h, out->violated, C.violated, sizeof(int) * kLimQ * n));
+  HIPCHK(h, fetch_async(h, out->feasible, C.feasible, sizeof(int) * n));
   return DFTPAV_OK;
 }
 
-extern "C" int dftpav_limits_last_ms(dftpav_handle *h, float *ms) {
-  if (!h || !ms || !h->ltimed) return DFTPAV_E_INVALID;
+int dftpav::check_limits_rows(dftpav_handle *h, double check_dt, size_t n, const dftpav_limits_out *out, LimitsCommon C,
+                              const std::function<hipError_t(const LimitsCommon &)> &launch) {
+  std::vector<double> tab;
+  int n_t = 0, n_v = 0;
+  if (int rc = validation_table(h->params, check_dt, 1.0, 0, tab, &n_t, &n_v)) return rc; // (the sample times are its first n_t entries)
+  double *d_tab = nullptr;
+  DevScratch tmp(h);
+  HIPCHK(h, tmp.alloc(d_tab, (size_t)n_t));
+  HIPCHK(h, tmp.alloc(C.max_abs, kLimQ * n));
+  HIPCHK(h, tmp.alloc(C.arg, (2 * kLimQ + 1) * n)); // arg | violated | feasible
+  C.violated = C.arg + kLimQ * n;
+  C.feasible = C.arg + 2 * kLimQ * n;
+  C.tab = SampleTable{d_tab, n_t, check_dt};
+  h->lim_ev.reset(); // until the whole chain has run
+  HIPCHK(h, hipMemcpyAsync(d_tab, tab.data(), sizeof(double) * (size_t)n_t, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, h->lim_ev.record(0, h->stream));
+  HIPCHK(h, launch(C));
+  HIPCHK(h, h->lim_ev.record(1, h->stream));
+  if (int rc = fetch_limits(h, out, C, n)) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->lim_ev.complete();
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_batch_check_limits(dftpav_batch *b, double check_dt, const dftpav_limits *l, const dftpav_limits_out *out) {
+  if (!b || !l || !out || !b->uploaded || !b->solved || !(check_dt > 0.0) || !std::isfinite(check_dt)) return DFTPAV_E_INVALID;
+  dftpav_handle *h = b->h;
+  LimitsCommon C{};
+  if (!limits_common(h->params, *l, C)) return DFTPAV_E_INVALID;
   HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipEventElapsedTime(ms, h->lev0, h->lev1));
+  DevBatch D;
+  if (int rc = ensure_coeffs(b, D)) return rc;
+  return check_limits_rows(h, check_dt, (size_t)b->B, out, C, [&](const LimitsCommon &done) {
+    return launch_limits_batch(LimitsBatchArgs{done, b->d_coef, b->d_dt, b->L, b->B, nullptr, 1, nullptr}, h->stream);
+  });
+}
+
+extern "C" int dftpav_limits_last_ms(dftpav_handle *h, float *ms) {
+  if (!h || !ms || !h->lim_ev.reached()) return DFTPAV_E_INVALID;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, h->lim_ev.elapsed(ms, 0, 1, false));
   return DFTPAV_OK;
 }
 
@@ -667,8 +662,6 @@ int dftpav::ensure_dist_field(dftpav_handle *h) {
   if (h->map.size_x > kDistMaxSide || h->map.size_y > kDistMaxSide) return DFTPAV_E_UNSUPPORTED;
   if (!h->dist_stale) return DFTPAV_OK;
   const size_t ncell = (size_t)h->map.size_x * h->map.size_y;
-  for (hipEvent_t *e : {&h->fev0, &h->fev1})
-    if (!*e) HIPCHK(h, hipEventCreate(e));
   if (h->dist_cells < ncell) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (h->d_dist) (void)hipFree(h->d_dist);
@@ -678,11 +671,11 @@ int dftpav::ensure_dist_field(dftpav_handle *h) {
     h->dist_cells = ncell;
   }
   const DistFieldArgs A{h->d_cells, h->map.size_x, h->map.size_y, h->d_dist + h->dist_cells, h->d_dist};
-  h->ftimed = false;
-  HIPCHK(h, hipEventRecord(h->fev0, h->stream));
+  h->field_ev.reset();
+  HIPCHK(h, h->field_ev.record(0, h->stream));
   HIPCHK(h, launch_dist_field(A, h->stream));
-  HIPCHK(h, hipEventRecord(h->fev1, h->stream));
-  h->ftimed = true;
+  HIPCHK(h, h->field_ev.record(1, h->stream));
+  h->field_ev.complete();
   h->dist_stale = false;
   return DFTPAV_OK;
 }
@@ -706,47 +699,50 @@ ClearanceCommon dftpav::clearance_common(const dftpav_handle *h, const double *d
   return C;
 }
 
+int dftpav::fetch_clearance(dftpav_handle *h, const dftpav_clearance_out *out, const int *d_d2, const int *d_arg, const double *d_m, size_t n) {
+  HIPCHK(h, fetch_async(h, out->min_d2, d_d2, sizeof(int) * n));
+  HIPCHK(h, fetch_async(h, out->arg, d_arg, sizeof(int) * n));
+  HIPCHK(h, fetch_async(h, out->clearance, d_m, sizeof(double) * n));
+  return DFTPAV_OK;
+}
+
+int dftpav::check_clearance_rows(dftpav_handle *h, double check_dt, size_t n, const dftpav_clearance_out *out,
+                                 const std::function<hipError_t(const ClearanceCommon &)> &launch) {
+  if (int rc = ensure_dist_field(h)) return rc;
+  std::vector<double> tab;
+  int n_t = 0, n_v = 0;
+  if (int rc = validation_table(h->params, check_dt, kClearanceVertexRes, 0, tab, &n_t, &n_v)) return rc;
+  double *d_tab = nullptr, *d_m = nullptr;
+  int *d_int = nullptr; // min_d2 | arg
+  DevScratch tmp(h);
+  HIPCHK(h, tmp.alloc(d_tab, tab.size()));
+  HIPCHK(h, tmp.alloc(d_m, n));
+  HIPCHK(h, tmp.alloc(d_int, 2 * n));
+  ClearanceCommon C = clearance_common(h, d_tab, n_t, n_v, check_dt);
+  C.min_d2 = d_int;
+  C.arg = d_int + n;
+  C.clearance = d_m;
+  h->clr_ev.reset(); // until the whole chain has run
+  HIPCHK(h, hipMemcpyAsync(d_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, h->clr_ev.record(0, h->stream));
+  HIPCHK(h, launch(C));
+  HIPCHK(h, h->clr_ev.record(1, h->stream));
+  if (int rc = fetch_clearance(h, out, C.min_d2, C.arg, C.clearance, n)) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->clr_ev.complete();
+  return DFTPAV_OK;
+}
+
 extern "C" int dftpav_batch_check_clearance(dftpav_batch *b, double check_dt, const dftpav_clearance_out *out) {
   if (!b || !out || !b->uploaded || !b->solved || !(check_dt > 0.0) || !std::isfinite(check_dt)) return DFTPAV_E_INVALID;
   dftpav_handle *h = b->h;
   if (!h->d_cells) return DFTPAV_E_INVALID; // no map
   HIPCHK(h, hipSetDevice(h->device));
-  if (int rc = ensure_dist_field(h)) return rc;
   DevBatch D;
   if (int rc = ensure_coeffs(b, D)) return rc;
-  std::vector<double> tab;
-  int n_t = 0, n_v = 0;
-  if (int rc = validation_table(h->params, check_dt, kClearanceVertexRes, 0, tab, &n_t, &n_v)) return rc;
-  for (hipEvent_t *e : {&h->kev0, &h->kev1})
-    if (!*e) HIPCHK(h, hipEventCreate(e));
-  const size_t B = (size_t)b->B;
-  double *d_tab = nullptr, *d_m = nullptr;
-  int *d_int = nullptr; // min_d2 | arg
-  DevScratch tmp(h);
-  HIPCHK(h, tmp.alloc(d_tab, tab.size()));
-  HIPCHK(h, tmp.alloc(d_m, B));
-  HIPCHK(h, tmp.alloc(d_int, 2 * B));
-  ClearanceBatchArgs A{};
-  A.C = clearance_common(h, d_tab, n_t, n_v, check_dt);
-  A.C.min_d2 = d_int;
-  A.C.arg = d_int + B;
-  A.C.clearance = d_m;
-  A.coeffs = b->d_coef;
-  A.piece_dt = b->d_dt;
-  A.L = b->L;
-  A.B = b->B;
-  A.R = 1;
-  h->ktimed = false; // until the whole chain has run
-  HIPCHK(h, hipMemcpyAsync(d_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipEventRecord(h->kev0, h->stream));
-  HIPCHK(h, launch_clearance_batch(A, h->stream));
-  HIPCHK(h, hipEventRecord(h->kev1, h->stream));
-  HIPCHK(h, fetch_async(h, out->min_d2, A.C.min_d2, sizeof(int) * B));
-  HIPCHK(h, fetch_async(h, out->arg, A.C.arg, sizeof(int) * B));
-  HIPCHK(h, fetch_async(h, out->clearance, A.C.clearance, sizeof(double) * B));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->ktimed = true;
-  return DFTPAV_OK;
+  return check_clearance_rows(h, check_dt, (size_t)b->B, out, [&](const ClearanceCommon &C) {
+    return launch_clearance_batch(ClearanceBatchArgs{C, b->d_coef, b->d_dt, b->L, b->B, nullptr, 1, nullptr, 0.0}, h->stream);
+  });
 }
 
 extern "C" int dftpav_clearance_last_ms(dftpav_handle *h, float *field_ms, float *check_ms) {
@@ -754,11 +750,8 @@ extern "C" int dftpav_clearance_last_ms(dftpav_handle *h, float *field_ms, float
   if (field_ms) *field_ms = 0.0f;
   if (check_ms) *check_ms = 0.0f;
   HIPCHK(h, hipSetDevice(h->device));
-  if (field_ms && h->ftimed) {
-    HIPCHK(h, hipEventSynchronize(h->fev1));
-    HIPCHK(h, hipEventElapsedTime(field_ms, h->fev0, h->fev1));
-  }
-  if (check_ms && h->ktimed) HIPCHK(h, hipEventElapsedTime(check_ms, h->kev0, h->kev1));
+  if (field_ms && h->field_ev.reached()) HIPCHK(h, h->field_ev.elapsed(field_ms, 0, 1, true)); // (a build alone waits for nothing)
+  if (check_ms && h->clr_ev.reached()) HIPCHK(h, h->clr_ev.elapsed(check_ms, 0, 1, false));
   return DFTPAV_OK;
 }
 
@@ -769,23 +762,21 @@ extern "C" int dftpav_batch_sample_states(dftpav_batch *b, double t0, double sam
   HIPCHK(h, hipSetDevice(h->device));
   DevBatch D;
   if (int rc = ensure_coeffs(b, D)) return rc;
-  if (!h->cev0) HIPCHK(h, hipEventCreate(&h->cev0));
-  if (!h->cev1) HIPCHK(h, hipEventCreate(&h->cev1));
   const size_t nst = (size_t)b->B * (size_t)n_samples * 8;
   double *d_states = nullptr;
   int *d_valid = nullptr;
   DevScratch tmp(h);
   HIPCHK(h, tmp.alloc(d_states, nst));
   HIPCHK(h, tmp.alloc(d_valid, (size_t)b->B));
-  h->ctimed = false; // until the whole chain has run
-  HIPCHK(h, hipEventRecord(h->cev0, h->stream));
+  h->cor_ev.reset(); // until the whole chain has run
+  HIPCHK(h, h->cor_ev.record(0, h->stream));
   HIPCHK(h, launch_states(b->d_coef, b->d_dt, b->L, b->B, h->params.veh_wheel_base, t0, sample_dt, n_samples, filter_singularity != 0,
                           d_states, d_valid, h->stream));
-  HIPCHK(h, hipEventRecord(h->cev1, h->stream));
+  HIPCHK(h, h->cor_ev.record(1, h->stream));
   HIPCHK(h, hipMemcpyAsync(states, d_states, sizeof(double) * nst, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, fetch_async(h, n_valid, d_valid, sizeof(int) * (size_t)b->B));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->ctimed = true;
+  h->cor_ev.complete();
   return DFTPAV_OK;
 }
 
@@ -814,8 +805,6 @@ extern "C" int dftpav_plan_cycle(dftpav_batch *b, const dftpav_batch_data *d, co
   const size_t n_poses = (size_t)n_hyp * b->L.Npts;
   pc.poses.assign(states, states + 3 * n_poses);
   if (int rc = grow(h, pc.d_poses, pc.n_poses, 3 * n_poses)) return rc;
-  if (!h->cev0) HIPCHK(h, hipEventCreate(&h->cev0));
-  if (!h->cev1) HIPCHK(h, hipEventCreate(&h->cev1));
   HIPCHK(h, hipMemcpyAsync(pc.d_poses, pc.poses.data(), sizeof(double) * 3 * n_poses, hipMemcpyHostToDevice, h->stream));
   if (int rc = corridor_into_batch(b, pc.d_poses, (int)n_poses, n_restarts)) return rc; // (nothing waits between here and the solve)
   if (int rc = solve_impl(b, nullptr, false)) return rc;
@@ -993,11 +982,7 @@ int dftpav::goal_field_plan(dftpav_handle *h, const double *start_xy, const doub
   if (int rc = grow(h, h->d_gf_meta, h->gf_meta_ints, want_meta)) return rc;
   if (int rc = grow(h, h->d_gf, h->gf_ints, want_ws)) return rc;
   const size_t turns = G.turn_off.size() - 1;
-  while (h->gf_ev.size() < 2 * turns) {
-    hipEvent_t e = nullptr;
-    HIPCHK(h, hipEventCreate(&e));
-    h->gf_ev.push_back(e);
-  }
+  while (h->gf_ev.size() < turns) h->gf_ev.emplace_back();
   h->gf_timed = 0;
   HIPCHK(h, hipMemcpyAsync(h->d_gf_meta, H.data(), sizeof(int) * H.size(), hipMemcpyHostToDevice, h->stream));
   G.d_field_of = h->d_gf_meta;
@@ -1036,11 +1021,11 @@ int dftpav::goal_field_turn(dftpav_handle *h, const GoalFieldPlan &G, int t, Sea
     dirty_ints = (size_t)ng * G.turn_tiles[t];
   }
   if (ng > 0) {
-    HIPCHK(h, hipEventRecord(h->gf_ev[2 * (size_t)h->gf_timed], h->stream));
+    HIPCHK(h, h->gf_ev[(size_t)h->gf_timed].record(0, h->stream));
     HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)A.fields, DFTPAV_FIELD_UNREACHED, field_ints, h->stream));
     HIPCHK(h, hipMemsetAsync(A.dirty, 0, sizeof(int) * dirty_ints, h->stream));
     HIPCHK(h, launch_goal_fields(A, ng, h->stream));
-    HIPCHK(h, hipEventRecord(h->gf_ev[2 * (size_t)h->gf_timed + 1], h->stream));
+    HIPCHK(h, h->gf_ev[(size_t)h->gf_timed].record(1, h->stream));
     h->gf_timed++;
   }
   if (S) {
@@ -1168,7 +1153,7 @@ extern "C" int dftpav_goal_field_last_ms(dftpav_handle *h, float *ms) {
   float sum = 0.0f;
   for (int k = 0; k < h->gf_timed; k++) {
     float one = 0.0f;
-    HIPCHK(h, hipEventElapsedTime(&one, h->gf_ev[2 * (size_t)k], h->gf_ev[2 * (size_t)k + 1]));
+    HIPCHK(h, h->gf_ev[(size_t)k].elapsed(&one, 0, 1, false)); // (every call that builds fields waits for the stream)
     sum += one;
   }
   *ms = sum;
@@ -1203,16 +1188,15 @@ int dftpav::ensure_rs_table(dftpav_handle *h, double rho, const dftpav_rs_heuris
   h->rs_n_yaw = 0; // nothing valid until the build below is in the stream
   if (h->rs_doubles < entries) HIPCHK(h, hipStreamSynchronize(h->stream)); // nothing in flight reads what is freed
   if (int rc = grow(h, h->d_rs, h->rs_doubles, entries)) return rc;
-  if (!h->rs_ev0) HIPCHK(h, hipEventCreate(&h->rs_ev0));
-  if (!h->rs_ev1) HIPCHK(h, hipEventCreate(&h->rs_ev1));
   RsTableArgs A{};
   A.T = h->d_rs;
   A.entries = (long long)entries;
   A.g = g;
   A.rho = rho;
-  HIPCHK(h, hipEventRecord(h->rs_ev0, h->stream));
+  HIPCHK(h, h->rs_ev.record(0, h->stream));
   HIPCHK(h, launch_rs_table(A, h->stream));
-  HIPCHK(h, hipEventRecord(h->rs_ev1, h->stream));
+  HIPCHK(h, h->rs_ev.record(1, h->stream));
+  h->rs_ev.complete(); // (never reset: the read-out goes on answering after a build that failed)
   h->rs_builds++;
   h->rs_rho = rho;
   h->rs_extent = gp.extent;
@@ -1272,10 +1256,9 @@ extern "C" int dftpav_rs_table(dftpav_handle *h, double max_cur, const dftpav_rs
 }
 
 extern "C" int dftpav_rs_table_last_ms(dftpav_handle *h, float *ms, int *n_builds) {
-  if (!h || !ms || h->rs_builds < 1) return DFTPAV_E_INVALID;
+  if (!h || !ms || !h->rs_ev.reached()) return DFTPAV_E_INVALID;
   HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipEventSynchronize(h->rs_ev1));
-  HIPCHK(h, hipEventElapsedTime(ms, h->rs_ev0, h->rs_ev1));
+  HIPCHK(h, h->rs_ev.elapsed(ms, 0, 1, true));
   if (n_builds) *n_builds = h->rs_builds;
   return DFTPAV_OK;
 }
