@@ -60,6 +60,7 @@ EXPORTS = [
     "dftpav_goal_window", "dftpav_set_search_heuristic_window", "dftpav_grid_goal_field_windowed",
     "dftpav_default_rs_heuristic_params", "dftpav_set_search_rs_heuristic", "dftpav_rs_table", "dftpav_rs_table_last_ms",
     "dftpav_planner_check_conflicts", "dftpav_planner_sample_poses", "dftpav_conflicts_last_ms",
+    "dftpav_grid_stamp_poses", "dftpav_planner_stamp_slots", "dftpav_grid_clear_stamps", "dftpav_grid_read_cells", "dftpav_stamp_last_ms",
 ]
 
 
@@ -528,6 +529,39 @@ class Handle:
         self._check(fn(self._h, C.byref(a), C.byref(b)), "conflicts_last_ms")
         return float(a.value), float(b.value)
 
+    # ---- the stamps: vehicle footprints written into the installed map on the device
+    def stamp_poses(self, poses, inflate=0.0):
+        """dftpav_grid_stamp_poses: boxes [n][4] = cx, cy, cs, sn (rows of Planner.sample_poses) become occupied cells of the
+        working map, the vehicle's box grown by `inflate` on every side"""
+        b = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 4)
+        fn = lib().dftpav_grid_stamp_poses
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double]
+        self._check(fn(self._h, b.ctypes.data_as(C.c_void_p), b.shape[0], float(inflate)), "grid_stamp_poses")
+
+    def clear_stamps(self):
+        """dftpav_grid_clear_stamps: the working map is the uploaded one again"""
+        fn = lib().dftpav_grid_clear_stamps
+        fn.argtypes = [C.c_void_p]
+        self._check(fn(self._h), "grid_clear_stamps")
+
+    def read_cells(self):
+        """dftpav_grid_read_cells: (the working map uint8 [size_y][size_x], the cells that are 80 in it and not in the uploaded map)"""
+        if self._map_shape is None:
+            raise DftpavError(E_INVALID, "grid_read_cells: no map")
+        out, n = np.zeros(self._map_shape, dtype=np.uint8), C.c_int(-1)
+        fn = lib().dftpav_grid_read_cells
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        self._check(fn(self._h, out.ctypes.data_as(C.c_void_p), C.byref(n)), "grid_read_cells")
+        return out, n.value
+
+    def stamp_last_ms(self):
+        """dftpav_stamp_last_ms: device ms of (the pose kernel, the box kernel) of the last stamp call; 0.0 for what has not run"""
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        fn = lib().dftpav_stamp_last_ms
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        self._check(fn(self._h, C.byref(a), C.byref(b)), "stamp_last_ms")
+        return float(a.value), float(b.value)
+
     def goal_field(self, goals_xy, inflate_radius=0.0, fetch=True):
         """dftpav_grid_goal_field: for goals [n][2] (x, y) on the installed map, (field int32 [n][size_y][size_x], n_reached [n]): the
         cost of the cheapest 8-connected path (5 axial, 7 diagonal) between every cell and the goal's cell round cells within
@@ -969,6 +1003,18 @@ class Planner:
         fn.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_void_p]
         self.handle._check(fn(self._p, t0, dt, K, self._ip(out)), "planner_sample_poses")
         return out
+
+    def stamp_slots(self, t0, dt, K, inflate=0.0, select=None):
+        """dftpav_planner_stamp_slots: the footprints of the selected slots (select [slots], 0: not this one; None: every occupied
+        slot) at the clocks t0 + k dt, k < K -- the rows of sample_poses -- become occupied cells of the handle's working map"""
+        sel = None
+        if select is not None:
+            sel = np.ascontiguousarray(np.asarray(select) != 0, dtype=np.uint8).reshape(-1)
+            if sel.shape[0] != self.max_queries:
+                raise DftpavError(E_INVALID, "planner_stamp_slots: select has a byte per slot")
+        fn = lib().dftpav_planner_stamp_slots
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_double]
+        self.handle._check(fn(self._p, self._ip(sel), float(t0), float(dt), int(K), float(inflate)), "planner_stamp_slots")
 
     def publish_last_ms(self):
         """dftpav_publish_last_ms: device ms of the last publish kernel (0.0 before the first)"""

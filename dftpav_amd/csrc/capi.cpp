@@ -258,6 +258,9 @@ extern "C" void dftpav_destroy(dftpav_handle *h) {
   if (h->d_gf) (void)hipFree(h->d_gf);
   if (h->d_gf_meta) (void)hipFree(h->d_gf_meta);
   if (h->d_rs) (void)hipFree(h->d_rs);
+  if (h->d_cells_base) (void)hipFree(h->d_cells_base);
+  if (h->d_stamp_ws) (void)hipFree(h->d_stamp_ws);
+  if (h->stamp_sel_ev) (void)hipEventDestroy(h->stamp_sel_ev);
   const hipStream_t stream = h->stream;
   delete h; // every EventMarks of the handle releases its events here: in front of their stream
   if (stream) (void)hipStreamDestroy(stream);

@@ -33,6 +33,7 @@
 #include "limits_args.h"
 #include "clearance_args.h"
 #include "conflict_args.h"
+#include "stamp_args.h"
 #include "goalfield_args.h"
 
 namespace dftpav {
@@ -72,6 +73,11 @@ hipError_t launch_clearance_table(const ClearanceTableArgs &A, hipStream_t strea
 hipError_t launch_conflict_poses(const ConflictPoseArgs &A, hipStream_t stream);
 hipError_t launch_conflict_pairs(const ConflictPairArgs &A, hipStream_t stream);
 hipError_t launch_conflict_reduce(const ConflictReduceArgs &A, hipStream_t stream);
+// stamp.hip: boxes into the working map, the bit map from the bytes again, the cells stamped since the base copy
+hipError_t launch_stamp_boxes(const StampBoxArgs &A, hipStream_t stream);
+hipError_t launch_stamp_bits(const StampBitsArgs &A, hipStream_t stream);
+hipError_t launch_stamp_count(const StampCountArgs &A, hipStream_t stream);
+int stamp_count_blocks(size_t n_cells); // the partial counts launch_stamp_count writes
 // goalfield.hip: the cost-to-go fields of n goal cells, one workgroup each
 hipError_t launch_goal_fields(const GoalFieldArgs &A, int n, hipStream_t stream);
 // rstable.hip: every entry of the Reeds-Shepp cost-to-go table
@@ -159,6 +165,14 @@ struct dftpav_handle {
   EventMarks<2> field_ev, clr_ev; // around the last field build / the last clearance kernel of a check call
   EventMarks<3> conf_ev; // conflict.hip: in front of the pose kernel, between it and the pair kernel, behind the reduce kernel; of the
                          // last dftpav_planner_sample_poses (complete to mark 1) / _check_conflicts (to mark 2) call
+  // the stamps (stamp.hip): nothing of it exists until a stamp call.  d_cells stays the working map every call reads
+  unsigned char *d_cells_base = nullptr; // the map as uploaded: copied by the first stamp after a dftpav_set_grid_map, which drops it
+  unsigned char *d_stamp_ws = nullptr;   // dftpav_planner_stamp_slots: the poses 4 x [K][S_pad], occupied [S_pad], select [S_pad];
+  size_t stamp_ws_bytes = 0;             // kept from call to call, so the call waits for nothing
+  std::vector<unsigned char> stamp_sel;  // the host source of select's asynchronous copy, and the event behind that copy: the
+  hipEvent_t stamp_sel_ev = nullptr;     // next call waits for it before it writes the vector again
+  EventMarks<3> stamp_ev; // of the last stamp call: in front of the pose kernel, between it and the box kernel, behind the box kernel
+  bool stamp_posed = false; // that call ran the pose kernel (dftpav_planner_stamp_slots); dftpav_grid_stamp_poses records marks 1 and 2
   // the search heuristic (dftpav_set_search_heuristic) and the workspace of the goal fields (goalfield.hip): nothing of it is
   // allocated or launched until a call asks for a field
   dftpav_goal_field_params heu{0, 0.0, 0.0};
@@ -455,6 +469,11 @@ int fetch_clearance(dftpav_handle *h, const dftpav_clearance_out *out, const int
 // the distance field of the handle's map, built on the handle's stream if the map changed since the last build (nothing waits);
 // DFTPAV_E_INVALID without a map, DFTPAV_E_UNSUPPORTED for a side above 16384 cells
 int ensure_dist_field(dftpav_handle *h);
+// The boxes (four device arrays [n_boxes]; select [S_pad] on the device or null) stamped into the working map on the handle's stream,
+// between marks 1 and 2 of h->stamp_ev: the base copy is made if the map has none, the distance field goes stale.  Nothing waits.
+// The caller has checked the map and inflate.
+int stamp_boxes_on_stream(dftpav_handle *h, const double *cx, const double *cy, const double *cs, const double *sn, int n_boxes,
+                          const unsigned char *d_select, int S_pad, double inflate);
 // the outline spacing of the clearance calls: the reference's own (shapes.h:200-201), which dftpav_batch_validate's callers pass as 0.1
 constexpr double kClearanceVertexRes = 0.1;
 // the map, its field, the vehicle and the tables (d_tab: a validation_table of kClearanceVertexRes on the device) as clearance.hip reads them

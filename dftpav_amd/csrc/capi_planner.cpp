@@ -1276,14 +1276,16 @@ static bool conflict_clocks_ok(double t0, double dt, int K) {
   return K >= 1 && K <= DFTPAV_CONFLICT_MAX_SAMPLES && dt > 0.0 && std::isfinite(dt) && std::isfinite(t0);
 }
 
-// the poses of every slot at the K clocks into buffers of `tmp`, on the handle's stream between marks 0 and 1 of conf_ev (nothing waits)
-static int conflict_poses_on_stream(dftpav_planner *p, DevScratch &tmp, double t0, double dt, int K, ConflictPoses &P) {
+static int conflict_s_pad(const dftpav_planner *p) { return (p->max_queries + kConflictTile - 1) / kConflictTile * kConflictTile; }
+
+// the poses of every slot at the K clocks into d_pose (4 x [K][S_pad]) and d_occupied [S_pad], on the handle's stream between marks 0
+// and 1 of `ev` (nothing waits)
+static int conflict_poses_into(dftpav_planner *p, double *d_pose, unsigned char *d_occupied, EventMarks<3> &ev, double t0, double dt,
+                               int K, ConflictPoses &P) {
   dftpav_handle *h = p->h;
-  const int S_pad = (p->max_queries + kConflictTile - 1) / kConflictTile * kConflictTile;
+  const int S_pad = conflict_s_pad(p);
   const size_t n = (size_t)K * S_pad;
-  double *d_pose = nullptr;
-  HIPCHK(h, tmp.alloc(d_pose, 4 * n));
-  HIPCHK(h, tmp.alloc(P.occupied, (size_t)S_pad));
+  P.occupied = d_occupied;
   P.cx = d_pose;
   P.cy = d_pose + n;
   P.cs = d_pose + 2 * n;
@@ -1296,11 +1298,20 @@ static int conflict_poses_on_stream(dftpav_planner *p, DevScratch &tmp, double t
   A.t0 = t0;
   A.dt = dt;
   A.dcr = h->params.veh_d_cr;
-  h->conf_ev.reset(); // until the whole chain has run
-  HIPCHK(h, h->conf_ev.record(0, h->stream));
+  ev.reset(); // until the whole chain has run
+  HIPCHK(h, ev.record(0, h->stream));
   HIPCHK(h, launch_conflict_poses(A, h->stream));
-  HIPCHK(h, h->conf_ev.record(1, h->stream));
+  HIPCHK(h, ev.record(1, h->stream));
   return DFTPAV_OK;
+}
+// the same into buffers of `tmp`, between the marks of conf_ev
+static int conflict_poses_on_stream(dftpav_planner *p, DevScratch &tmp, double t0, double dt, int K, ConflictPoses &P) {
+  dftpav_handle *h = p->h;
+  double *d_pose = nullptr;
+  unsigned char *d_occupied = nullptr;
+  HIPCHK(h, tmp.alloc(d_pose, 4 * (size_t)K * conflict_s_pad(p)));
+  HIPCHK(h, tmp.alloc(d_occupied, (size_t)conflict_s_pad(p)));
+  return conflict_poses_into(p, d_pose, d_occupied, h->conf_ev, t0, dt, K, P);
 }
 
 extern "C" int dftpav_planner_sample_poses(dftpav_planner *p, double t0, double dt, int K, double *poses) {
@@ -1386,4 +1397,36 @@ extern "C" int dftpav_conflicts_last_ms(dftpav_handle *h, float *pose_ms, float 
   if (pose_ms && h->conf_ev.reached(1)) HIPCHK(h, h->conf_ev.elapsed(pose_ms, 0, 1, false)); // (both calls waited for the stream)
   if (pair_ms && h->conf_ev.reached(2)) HIPCHK(h, h->conf_ev.elapsed(pair_ms, 1, 2, false));
   return DFTPAV_OK;
+}
+
+// ------------------------------------------------- the executing plans' swept footprints stamped into the map (stamp.hip)
+extern "C" int dftpav_planner_stamp_slots(dftpav_planner *p, const unsigned char *select, double t0, double dt, int K, double inflate) {
+  if (!p || !conflict_clocks_ok(t0, dt, K) || !(inflate >= 0.0) || !std::isfinite(inflate)) return DFTPAV_E_INVALID;
+  dftpav_handle *h = p->h;
+  if (!h->d_cells || !p->d_exec) return DFTPAV_E_INVALID; // no map; no table
+  HIPCHK(h, hipSetDevice(h->device));
+  const int S_pad = conflict_s_pad(p);
+  const size_t n = (size_t)K * S_pad;
+  if (n > (size_t)INT_MAX) return DFTPAV_E_UNSUPPORTED; // the box kernel counts its boxes in an int
+  double *d_pose = nullptr;
+  unsigned char *d_occupied = nullptr, *d_select = nullptr;
+  auto fields = [&](auto take) {
+    d_pose = (double *)take(sizeof(double) * 4 * n);
+    d_occupied = (unsigned char *)take((size_t)S_pad);
+    d_select = (unsigned char *)take((size_t)S_pad);
+  };
+  if (int rc = grow(h, h->d_stamp_ws, h->stamp_ws_bytes, carve(nullptr, fields))) return rc;
+  carve(h->d_stamp_ws, fields);
+  if (select) {
+    if (h->stamp_sel_ev) HIPCHK(h, hipEventSynchronize(h->stamp_sel_ev)); // the last call's copy has read the vector
+    else HIPCHK(h, hipEventCreateWithFlags(&h->stamp_sel_ev, hipEventDisableTiming));
+    h->stamp_sel.assign((size_t)S_pad, 0); // the padding behind the last slot is unselected
+    std::copy(select, select + p->max_queries, h->stamp_sel.begin());
+    HIPCHK(h, hipMemcpyAsync(d_select, h->stamp_sel.data(), (size_t)S_pad, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipEventRecord(h->stamp_sel_ev, h->stream));
+  }
+  ConflictPoses P{};
+  if (int rc = conflict_poses_into(p, d_pose, d_occupied, h->stamp_ev, t0, dt, K, P)) return rc;
+  h->stamp_posed = true;
+  return stamp_boxes_on_stream(h, P.cx, P.cy, P.cs, P.sn, (int)n, select ? d_select : nullptr, S_pad, inflate);
 }

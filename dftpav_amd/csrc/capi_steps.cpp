@@ -376,9 +376,11 @@ extern "C" int dftpav_set_grid_map(dftpav_handle *h, const dftpav_grid_map *map)
   if (h->d_cells) (void)hipFree(h->d_cells);
   if (h->d_bits) (void)hipFree(h->d_bits);
   if (h->d_dl) (void)hipFree(h->d_dl);
+  if (h->d_cells_base) (void)hipFree(h->d_cells_base); // a new map has no stamps
   h->d_cells = nullptr;
   h->d_bits = nullptr;
   h->d_dl = nullptr;
+  h->d_cells_base = nullptr;
   const size_t ncell = (size_t)map->size_x * map->size_y;
   HIPCHK(h, hipMalloc(&h->d_cells, ncell));
   HIPCHK(h, hipMemcpy(h->d_cells, map->cells, ncell, hipMemcpyHostToDevice));
@@ -752,6 +754,101 @@ extern "C" int dftpav_clearance_last_ms(dftpav_handle *h, float *field_ms, float
   HIPCHK(h, hipSetDevice(h->device));
   if (field_ms && h->field_ev.reached()) HIPCHK(h, h->field_ev.elapsed(field_ms, 0, 1, true)); // (a build alone waits for nothing)
   if (check_ms && h->clr_ev.reached()) HIPCHK(h, h->clr_ev.elapsed(check_ms, 0, 1, false));
+  return DFTPAV_OK;
+}
+
+// ------------------------------------------------- vehicle footprints stamped into the map (stamp.hip)
+int dftpav::stamp_boxes_on_stream(dftpav_handle *h, const double *cx, const double *cy, const double *cs, const double *sn, int n_boxes,
+                                  const unsigned char *d_select, int S_pad, double inflate) {
+  const size_t ncell = (size_t)h->map.size_x * h->map.size_y;
+  if (!h->d_cells_base) { // the first stamp of this map: what was uploaded is kept aside
+    HIPCHK(h, hipMalloc(&h->d_cells_base, ncell));
+    HIPCHK(h, hipMemcpyAsync(h->d_cells_base, h->d_cells, ncell, hipMemcpyDeviceToDevice, h->stream));
+  }
+  StampBoxArgs A{};
+  A.cells = h->d_cells;
+  A.bits = h->d_bits;
+  A.size_x = h->map.size_x;
+  A.size_y = h->map.size_y;
+  A.resolution = h->map.resolution;
+  A.origin_x = h->map.origin_x;
+  A.origin_y = h->map.origin_y;
+  A.cx = cx;
+  A.cy = cy;
+  A.cs = cs;
+  A.sn = sn;
+  A.n_boxes = n_boxes;
+  A.select = d_select;
+  A.S_pad = S_pad;
+  A.hl = 0.5 * h->params.veh_length + inflate;
+  A.hw = 0.5 * h->params.veh_width + inflate;
+  h->dist_stale = true;
+  HIPCHK(h, h->stamp_ev.record(1, h->stream));
+  HIPCHK(h, launch_stamp_boxes(A, h->stream));
+  HIPCHK(h, h->stamp_ev.record(2, h->stream));
+  h->stamp_ev.complete();
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_grid_stamp_poses(dftpav_handle *h, const double *poses, int n, double inflate) {
+  if (!h || !poses || n < 0 || !(inflate >= 0.0) || !std::isfinite(inflate)) return DFTPAV_E_INVALID;
+  if (!h->d_cells) return DFTPAV_E_INVALID; // no map
+  if (n == 0) return DFTPAV_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  std::vector<double> soa(4 * (size_t)n); // cx | cy | cs | sn, as the kernel reads the slot form's
+  for (size_t i = 0; i < (size_t)n; i++)
+    for (size_t c = 0; c < 4; c++) soa[c * n + i] = poses[4 * i + c];
+  double *d = nullptr;
+  DevScratch tmp(h); // (the call takes its boxes from the host: it ends with a wait, behind which the buffer goes)
+  HIPCHK(h, tmp.alloc(d, soa.size()));
+  HIPCHK(h, hipMemcpyAsync(d, soa.data(), sizeof(double) * soa.size(), hipMemcpyHostToDevice, h->stream));
+  h->stamp_ev.reset();
+  h->stamp_posed = false;
+  return stamp_boxes_on_stream(h, d, d + n, d + 2 * (size_t)n, d + 3 * (size_t)n, n, nullptr, 0, inflate);
+}
+
+extern "C" int dftpav_grid_clear_stamps(dftpav_handle *h) {
+  if (!h || !h->d_cells) return DFTPAV_E_INVALID; // no map
+  if (!h->d_cells_base) return DFTPAV_OK;         // nothing was stamped into this map
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t ncell = (size_t)h->map.size_x * h->map.size_y;
+  HIPCHK(h, hipMemcpyAsync(h->d_cells, h->d_cells_base, ncell, hipMemcpyDeviceToDevice, h->stream));
+  if (h->d_bits) HIPCHK(h, launch_stamp_bits(StampBitsArgs{h->d_cells, h->d_bits, ncell}, h->stream));
+  h->dist_stale = true;
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_grid_read_cells(dftpav_handle *h, unsigned char *cells, int *n_stamped) {
+  if (!h || !h->d_cells) return DFTPAV_E_INVALID; // no map
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t ncell = (size_t)h->map.size_x * h->map.size_y;
+  std::vector<unsigned> partial; // (in front of tmp: it outlives the wait of tmp's destructor)
+  DevScratch tmp(h);
+  if (n_stamped && h->d_cells_base) {
+    unsigned *d_partial = nullptr;
+    partial.resize((size_t)stamp_count_blocks(ncell));
+    HIPCHK(h, tmp.alloc(d_partial, partial.size()));
+    HIPCHK(h, launch_stamp_count(StampCountArgs{h->d_cells, h->d_cells_base, ncell, d_partial}, h->stream));
+    HIPCHK(h, hipMemcpyAsync(partial.data(), d_partial, sizeof(unsigned) * partial.size(), hipMemcpyDeviceToHost, h->stream));
+  }
+  HIPCHK(h, fetch_async(h, cells, h->d_cells, ncell));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (n_stamped) {
+    unsigned n = 0;
+    for (unsigned v : partial) n += v; // in the order of the workgroups
+    *n_stamped = (int)n;
+  }
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_stamp_last_ms(dftpav_handle *h, float *pose_ms, float *stamp_ms) {
+  if (!h) return DFTPAV_E_INVALID;
+  if (pose_ms) *pose_ms = 0.0f;
+  if (stamp_ms) *stamp_ms = 0.0f;
+  if (!h->stamp_ev.reached()) return DFTPAV_OK; // nothing was stamped yet
+  HIPCHK(h, hipSetDevice(h->device));
+  if (pose_ms && h->stamp_posed) HIPCHK(h, h->stamp_ev.elapsed(pose_ms, 0, 1, true)); // (a stamp waits for nothing)
+  if (stamp_ms) HIPCHK(h, h->stamp_ev.elapsed(stamp_ms, 1, 2, true));
   return DFTPAV_OK;
 }
 

@@ -229,6 +229,13 @@ class TrajPlannerSteps {
     return true;
   }
 
+  // the footprints of the selected slots (select: a byte per slot, empty: every occupied slot) at the clocks t0 + k dt, k < K, grown by
+  // `inflate`, become occupied cells of the handle's map, for whatever is planned or checked next; ClearStamps puts the uploaded map back
+  bool StampSlots(dftpav_planner *planner, const std::vector<unsigned char> &select, double t0, double dt, int K, double inflate) {
+    return ok(dftpav_planner_stamp_slots(planner, select.empty() ? nullptr : select.data(), t0, dt, K, inflate));
+  }
+  bool ClearStamps() { return ok(dftpav_grid_clear_stamps(h_)); }
+
   // the states the server would publish for every trajectory of a solved batch at t0, t0 + dt, ...;
   // states[t] holds the samples that fall inside trajectory t
   bool GetStates(dftpav_batch *batch, int B, double t0, double dt, int n_samples, std::vector<std::vector<State>> &states,

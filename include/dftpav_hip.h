@@ -1201,6 +1201,57 @@ int dftpav_planner_check_conflicts(dftpav_planner *p, double t0, double dt, int 
 int dftpav_planner_sample_poses(dftpav_planner *p, double t0, double dt, int K, double *poses /*[K][max_queries][4]*/);
 int dftpav_conflicts_last_ms(dftpav_handle *h, float *pose_ms, float *pair_ms);
 
+/* ---- the stamps: vehicle footprints written into the grid map on the device -------------------------------------------
+ * Every stage that plans or checks a plan (search, goal field, rectangle corridor, collision re-check, replan check, distance
+ * field, clearance) looks at the occupancy grid of dftpav_set_grid_map alone.  A stamp makes cells of that grid occupied where a
+ * vehicle is or will be, so that a plan made afterwards goes round it: stamp what has right of way, plan the rest, clear.  Off until
+ * called: a handle that never stamped launches, allocates and computes what it did without this section (stamp.hip).
+ *
+ * A box is (cx, cy, cs, sn): the centre, cosine and sine of a row of dftpav_planner_sample_poses.  L, W are the handle's veh_length,
+ * veh_width.  All arithmetic is fp64 without contraction.
+ *   cell (ix, iy) has the centre   X = origin_x + (double)ix * resolution, Y = origin_y + (double)iy * resolution
+ *   dx = X - cx, dy = Y - cy
+ *   lx = cs * dx + sn * dy, ly = cs * dy - sn * dx          (the frame of the conflict check's step 2)
+ *   hl = 0.5 * L + inflate, hw = 0.5 * W + inflate
+ *   the box COVERS the cell iff fabs(lx) <= hl && fabs(ly) <= hw
+ *   a box with a member that is not finite covers nothing
+ *   a covered cell of the working map becomes 80
+ * This is defined over all cells of the grid; what range of cells the device walks does not show.  inflate >= 0, finite.  With
+ * inflate >= resolution / sqrt(2) every cell that the collision re-check can name for a point of the uninflated box (coord =
+ * round((p - origin) / resolution): at most half a cell from p on either axis) is covered.
+ *
+ * State.  The map every call reads is the WORKING map.  The first stamp after a dftpav_set_grid_map keeps a BASE copy of the map as
+ * uploaded; stamps accumulate in the working map until dftpav_grid_clear_stamps puts the base back (stamping a box twice changes
+ * nothing).  Maps of up to 327 680 cells have a bit map beside the bytes (the rectangle corridor reads it): a stamp sets the same
+ * bits, a clear makes them again from the bytes.  Every stamp and every clear marks the distance field stale, so the next call that
+ * needs it builds it again.  dftpav_set_grid_map drops base and stamps.  Nothing else of a handle keeps state derived from the map
+ * from one call to the next.
+ *
+ * dftpav_grid_stamp_poses(h, poses, n, inflate): n boxes from the host; n == 0 does nothing.
+ * dftpav_planner_stamp_slots(p, select, t0, dt, K, inflate): the swept footprint of the selected slots of p's executing table, the
+ *   boxes being the poses of dftpav_planner_sample_poses(p, t0, dt, K) on the device: t_k = t0 + (double)k * dt, held still outside
+ *   the plan.  select [max_queries], 0: the slot stamps nothing; NULL: every occupied slot.  Empty slots stamp nothing.  K = 1 is
+ *   "the vehicle where it stands at t0".  Neither the table nor the publisher's state is written.
+ * dftpav_grid_clear_stamps(h): the working map is the base again, bytes other than 0 and 80 included; OK where nothing was stamped.
+ * dftpav_grid_read_cells(h, cells, n_stamped): the working map [size_y][size_x], and the number of cells that are 80 in it and not
+ *   80 in the base (0 where nothing was stamped); either pointer may be NULL.
+ * dftpav_stamp_last_ms(h, pose_ms, stamp_ms): device time in ms (the handle's HIP events) of the pose kernel and of the box kernel
+ *   of the last stamp call; pose_ms is 0.0 after dftpav_grid_stamp_poses, both before the first stamp.  Either pointer may be NULL.
+ * All work goes on the handle's stream.  dftpav_planner_stamp_slots and dftpav_grid_clear_stamps return without a wait for it;
+ * dftpav_grid_stamp_poses (its boxes come from the host) and dftpav_grid_read_cells end with one.
+ * DFTPAV_E_INVALID, and nothing changed: h, p or poses NULL; no map; n < 0; K < 1 or K > DFTPAV_CONFLICT_MAX_SAMPLES; dt <= 0 or not
+ * finite; t0 not finite; inflate < 0 or not finite; a planner whose table was never filled.
+ *
+ * Not claimed.  Between clocks nothing is stamped: choose dt against the speed and the inflation.  A slot stamped into the map is an
+ * obstacle to every later check, the replan check of that slot itself included; select the slots that have right of way.  Every
+ * box is the handle's one vehicle size. */
+int dftpav_grid_stamp_poses(dftpav_handle *h, const double *poses /*[n][4] cx, cy, cs, sn*/, int n, double inflate);
+int dftpav_planner_stamp_slots(dftpav_planner *p, const unsigned char *select /*[max_queries] or NULL: every occupied slot*/, double t0,
+                               double dt, int K, double inflate);
+int dftpav_grid_clear_stamps(dftpav_handle *h);
+int dftpav_grid_read_cells(dftpav_handle *h, unsigned char *cells /*[size_y][size_x] or NULL*/, int *n_stamped /*or NULL*/);
+int dftpav_stamp_last_ms(dftpav_handle *h, float *pose_ms, float *stamp_ms);
+
 /* One-shot convenience == OptimizeTrajectory for B trajectories. */
 int dftpav_solve_batch(dftpav_handle *h, const dftpav_layout *layout, int B,
                        const dftpav_batch_data *d, double *x, double *final_cost,
