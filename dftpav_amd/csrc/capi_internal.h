@@ -343,6 +343,66 @@ struct GoalFieldPlan {
   const long long *d_off = nullptr;
 };
 
+// n rows of a limits check wired into C: max_abs [n][5] at d_max, then arg [n][5] | violated [n][5] | feasible [n] from d_int on
+inline void limit_rows(LimitsCommon &C, double *d_max, int *d_int, size_t n) {
+  C.max_abs = d_max;
+  C.arg = d_int;
+  C.violated = d_int + kLimQ * n;
+  C.feasible = d_int + 2 * kLimQ * n;
+}
+
+// The selection filters of dftpav_plan_queries: three structs of one shape (capi_planner.cpp).  Each holds its switch (`on`, and
+// `last`: the last dftpav_plan_queries call ran with it), its parameters and its one allocation `d` -- the sample table at its head
+// where the filter has one, then the rows [cap = max_queries * R] of a call -- and states the same operations once:
+//   configure  the set_*_filter entry behind its argument checks: allocates on first use, switches on; a refusal changes nothing
+//   clear      the rows of a call (rows = Q * R) as a trajectory that no kernel visits reports them
+//   run        one group's launch: the batch's first nm * R trajectories into the rows of `members`, `reject` set where it rejects
+//   fetch      the rows of the last call into the caller's arrays (nothing waits)
+//   release    the allocation (dftpav_planner_destroy)
+// Off by default, and then a call allocates, clears and launches nothing of it.
+struct LimitFilter {
+  bool on = false, last = false;
+  dftpav_limits lim{};
+  unsigned char *d = nullptr;
+  CachedTable tab; // (its dt is the filter's check_dt)
+  size_t cap = 0;
+  double *d_max = nullptr; // max_abs
+  int *d_int = nullptr;    // arg | violated | feasible (limit_rows)
+  LimitsCommon rows() const { LimitsCommon C{}; limit_rows(C, d_max, d_int, cap); return C; } // the rows alone: the one place they are wired
+  bool common(const dftpav_handle *h, LimitsCommon &C) const; // limits, sample table and rows; false: limits_common refused
+  int configure(dftpav_handle *h, size_t rows_cap, const dftpav_limits &l, double check_dt);
+  int clear(dftpav_handle *h, size_t rows);
+  int run(dftpav_handle *h, dftpav_batch *b, const int *members, int nm, int R, int *reject);
+  int fetch(dftpav_handle *h, const dftpav_limits_out *out, size_t rows);
+  void release() { if (d) (void)hipFree(d); }
+};
+struct PenaltyFilter {
+  bool on = false, last = false;
+  dftpav_penalty_caps caps{};
+  unsigned char *d = nullptr;
+  double *d_terms = nullptr;
+  int *d_rej = nullptr;
+  int configure(dftpav_handle *h, size_t rows_cap, const dftpav_penalty_caps &c);
+  int clear(dftpav_handle *h, size_t rows);
+  int run(dftpav_handle *h, dftpav_batch *b, const int *members, int nm, int R, int *reject);
+  int fetch(dftpav_handle *h, double *r_terms, int *r_rejected, size_t rows);
+  void release() { if (d) (void)hipFree(d); }
+};
+struct ClearanceFilter {
+  bool on = false, last = false;
+  double min = -1.0;
+  unsigned char *d = nullptr;
+  CachedTable tab; // (both tables; its dt is the filter's check_dt)
+  double *d_m = nullptr;
+  int *d_d2 = nullptr, *d_arg = nullptr;
+  std::vector<double> h_inf; // +inf, the rows' clearance before a call's kernels run
+  int configure(dftpav_handle *h, size_t rows_cap, double min_clearance, double check_dt);
+  int clear(dftpav_handle *h, size_t rows);
+  int run(dftpav_handle *h, dftpav_batch *b, const int *members, int nm, int R, int *reject);
+  int fetch(dftpav_handle *h, const dftpav_clearance_out *out, size_t rows);
+  void release() { if (d) (void)hipFree(d); }
+};
+
 struct dftpav_planner {
   dftpav_handle *h = nullptr;
   int max_queries = 0, R = 0;
@@ -374,9 +434,14 @@ struct dftpav_planner {
   // host staging of the tables that decide the grouping
   std::vector<int> h_sints, h_nseg, h_singul, h_pn, h_nstates, h_skip, h_members, h_minit;
   std::vector<double> h_dt, h_vt;
+  // the host side of every copy from the device that a planner call enqueues and is not the caller's own memory lives here, not in
+  // the call's scope: a call that leaves early leaves nothing behind that the stream still writes.  The winners of a call are
+  // fetched into last_winner (below); these are the tick's: the replan flags [slots], the start states [slots][4], controls [slots][2]
+  std::vector<int> h_rc_flag;
+  std::vector<double> h_rc_st, h_rc_ct;
   // ---- the replan loop (dftpav_planner_install ... dftpav_replan_tick)
   // what the last dftpav_plan_queries call left behind for dftpav_planner_adopt: its size and paddings, per query the final
-  // plan_status and winner, and the goals
+  // plan_status and winner, and the goals (read only while last_Q > 0: a call that fails leaves them half written)
   int last_Q = 0, last_MS = 0, last_MP = 0;
   std::vector<int> last_status, last_winner;
   std::vector<double> last_goal;
@@ -400,31 +465,10 @@ struct dftpav_planner {
   double *d_pub_t = nullptr, *d_pub_states = nullptr;
   int *d_pub_code = nullptr;
   EventMarks<2> pub_ev; // around the last publish kernel
-  // ---- the limit filter (dftpav_planner_set_limit_filter): off by default, and then none of this is touched
-  bool lim_on = false;
-  dftpav_limits lim{};
-  double lim_dt = 0.0;
-  unsigned char *d_lim = nullptr; // one allocation: the sample table, the rows [max_queries * R] of a call
-  CachedTable lim_tab;
-  double *d_lim_max = nullptr;
-  int *d_lim_arg = nullptr, *d_lim_viol = nullptr, *d_lim_feas = nullptr;
-  bool last_lim = false; // the last dftpav_plan_queries call ran with the filter
-  // ---- the penalty filter (dftpav_planner_set_penalty_filter): off by default, and then none of this is touched
-  bool pen_on = false;
-  dftpav_penalty_caps pen{};
-  unsigned char *d_pen = nullptr; // one allocation: the rows [max_queries * R] of a call
-  double *d_pen_terms = nullptr;
-  int *d_pen_rej = nullptr;
-  bool last_pen = false; // the last dftpav_plan_queries call ran with the filter
-  // ---- the clearance filter (dftpav_planner_set_clearance_filter): off by default, and then none of this is touched
-  bool clr_on = false;
-  double clr_min = -1.0, clr_dt = 0.0;
-  unsigned char *d_clr = nullptr; // one allocation: the two tables, the rows [max_queries * R] of a call
-  CachedTable clr_tab;
-  double *d_clr_m = nullptr;
-  int *d_clr_d2 = nullptr, *d_clr_arg = nullptr;
-  std::vector<double> h_clr_inf; // +inf, the rows' clearance before a call's kernels run
-  bool last_clr = false; // the last dftpav_plan_queries call ran with the filter
+  // ---- the selection filters (dftpav_planner_set_limit_filter / _penalty_filter / _clearance_filter)
+  LimitFilter lim;
+  PenaltyFilter pen;
+  ClearanceFilter clr;
 };
 
 namespace dftpav {

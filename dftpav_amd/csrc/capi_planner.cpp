@@ -85,9 +85,9 @@ extern "C" void dftpav_planner_destroy(dftpav_planner *p) {
   if (p->d_exec) (void)hipFree(p->d_exec);
   if (p->d_rc) (void)hipFree(p->d_rc);
   if (p->d_pub) (void)hipFree(p->d_pub);
-  if (p->d_lim) (void)hipFree(p->d_lim);
-  if (p->d_pen) (void)hipFree(p->d_pen);
-  if (p->d_clr) (void)hipFree(p->d_clr);
+  p->lim.release();
+  p->pen.release();
+  p->clr.release();
   delete p; // (its EventMarks' events with it)
 }
 
@@ -210,10 +210,28 @@ static int planner_batch(dftpav_planner *p, const dftpav_layout &lay, dftpav_bat
   return DFTPAV_OK;
 }
 
-extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *pp, const double *start_states, const double *start_ctrl,
-                                   const double *end_states, int Q, double t_now, const dftpav_plan_out *out) {
+// One call of dftpav_plan_queries: what its stages (below, in the order the exported function runs them) hand to one another.
+struct PlanCall {
+  dftpav_planner *p;
+  dftpav_handle *h;
+  const dftpav_plan_params *pp;
+  const double *start_states, *start_ctrl, *end_states;
+  int Q;
+  double t_now;
+  const dftpav_plan_out *out;
+  int R = 0, MS = 0, MP = 0, MST = 0; // restarts; the paddings: segments, pieces of a segment, poses of a segment of max_pieces pieces
+  int n_t = 0, n_v = 0;               // the validation table (p->h_vt, p->d_vt): sample times | outline point spacings
+  SearchSetup U;
+  GoalFieldPlan G; // dftpav_set_search_heuristic; off: G.per_turn == 0 and nothing differs
+  std::vector<int> gate, group, first, status; // per query: what the grouping saw, its group, per group its first query, plan_status
+  std::vector<dftpav_batch *> batch;           // per group (nullptr: a layout outside the reference order's limits)
+  std::vector<int> g_off;                      // group g's members are p->h_members [g_off[g], g_off[g + 1])
+  size_t pose_off = 0;                         // poses of p->d_poses the groups so far have used
+};
+
+static int plan_check_params(const dftpav_planner *p, const dftpav_plan_params *pp, const dftpav_plan_out *out, int Q) {
   if (!p || !pp || !out || Q < 0 || Q > p->max_queries) return DFTPAV_E_INVALID;
-  dftpav_handle *h = p->h;
+  const dftpav_handle *h = p->h;
   if (!h->d_cells) return DFTPAV_E_INVALID; // no map
   const dftpav_frontend_params &fp = pp->frontend;
   if (pp->max_seg < 1 || pp->max_seg > kMaxSeg || pp->max_pieces < 2 || pp->max_pieces > 1024 || pp->max_path < 2 || pp->max_path > (1 << 20) ||
@@ -222,38 +240,33 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
       !(fp.piece_duration > 0.0) || !(fp.max_forward_vel > 0.0) || !(fp.max_forward_acc > 0.0) || !(fp.max_backward_vel > 0.0) ||
       !(fp.max_backward_acc > 0.0))
     return DFTPAV_E_INVALID;
-  p->group_sizes.clear();
-  p->plan_ev.reset();
-  p->last_Q = 0; // nothing to adopt until this call has ended well
-  p->last_lim = false;
-  p->last_pen = false;
-  p->last_clr = false;
-  const bool clr = p->clr_on; // dftpav_planner_set_clearance_filter; off: likewise
-  const bool pen = p->pen_on; // dftpav_planner_set_penalty_filter; off: likewise
-  const bool filt = p->lim_on; // dftpav_planner_set_limit_filter; off: nothing below differs from a planner that never had one
-  if (Q == 0) return DFTPAV_OK;
-  if (!start_states || !start_ctrl || !end_states) return DFTPAV_E_INVALID;
-  SearchSetup U;
+  return DFTPAV_OK;
+}
+
+// arrival test (traj_manager.cpp:196), tables and buffers, uploads, search, resampling: marks 0 to 2
+static int plan_search(PlanCall &c) {
+  dftpav_planner *p = c.p;
+  dftpav_handle *h = c.h;
+  const dftpav_plan_params *pp = c.pp;
+  const int Q = c.Q;
+  SearchSetup &U = c.U;
   if (int rc = search_setup(h, &pp->search, Q, U)) return rc;
-  GoalFieldPlan G; // dftpav_set_search_heuristic; off: G.per_turn == 0 and nothing below differs
-  if (int rc = search_heuristic_plan(h, start_states, end_states, Q, U, G)) return rc;
-  const int R = p->R, MS = pp->max_seg, MP = pp->max_pieces;
-  const int MST = (MP - 2) * (fp.traj_res + 1) + 2 * (fp.dense_traj_res + 1); // poses of a segment of max_pieces pieces
+  if (int rc = search_heuristic_plan(h, c.start_states, c.end_states, Q, U, c.G)) return rc;
+  c.R = p->R, c.MS = pp->max_seg, c.MP = pp->max_pieces;
+  c.MST = (c.MP - 2) * (pp->frontend.traj_res + 1) + 2 * (pp->frontend.dense_traj_res + 1);
   // the two running sums of the collision re-check, tabulated (as dftpav_batch_validate): sample times | outline point spacing
   std::vector<double> &vt = p->h_vt;
-  int n_t = 0, n_v = 0;
-  if (int rc = validation_table(h->params, pp->check_dt, pp->vertex_res, 0, vt, &n_t, &n_v)) return rc;
-  if (int rc = planner_buffers(p, *pp, MST, U.tabs.size(), vt.size())) return rc;
+  if (int rc = validation_table(h->params, pp->check_dt, pp->vertex_res, 0, vt, &c.n_t, &c.n_v)) return rc;
+  if (int rc = planner_buffers(p, *pp, c.MST, U.tabs.size(), vt.size())) return rc;
   const size_t nq = (size_t)Q;
-  // ---- arrival test (traj_manager.cpp:196), uploads, search, resampling
   p->h_skip.assign(Q, 0);
   for (int q = 0; q < Q; q++) {
-    const double dx = end_states[4 * q] - start_states[4 * q], dy = end_states[4 * q + 1] - start_states[4 * q + 1];
+    const double dx = c.end_states[4 * q] - c.start_states[4 * q], dy = c.end_states[4 * q + 1] - c.start_states[4 * q + 1];
     if (std::sqrt(dx * dx + dy * dy) < 1.0) p->h_skip[q] = 1;
   }
-  HIPCHK(h, hipMemcpyAsync(p->d_st, start_states, sizeof(double) * 4 * nq, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(p->d_en, end_states, sizeof(double) * 4 * nq, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h, hipMemcpyAsync(p->d_ct, start_ctrl, sizeof(double) * 2 * nq, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(p->d_st, c.start_states, sizeof(double) * 4 * nq, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(p->d_en, c.end_states, sizeof(double) * 4 * nq, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(p->d_ct, c.start_ctrl, sizeof(double) * 2 * nq, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(p->d_skip, p->h_skip.data(), sizeof(int) * nq, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(p->d_tabs, U.tabs.data(), sizeof(double) * U.tabs.size(), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(p->d_vt, vt.data(), sizeof(double) * vt.size(), hipMemcpyHostToDevice, h->stream));
@@ -265,15 +278,22 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
   HIPCHK(h, p->plan_ev.record(0, h->stream));
   for (int q0 = 0; q0 < Q; q0 += U.slots) {
     S.q0 = q0;
-    if (G.per_turn)
-      if (int rc = goal_field_turn(h, G, q0 / U.slots, &S, nullptr)) return rc;
+    if (c.G.per_turn)
+      if (int rc = goal_field_turn(h, c.G, q0 / U.slots, &S, nullptr)) return rc;
     HIPCHK(h, launch_search(S, std::min(U.slots, Q - q0), h->stream));
   }
   HIPCHK(h, p->plan_ev.record(1, h->stream));
   HIPCHK(h, launch_plan_paths(S.out.status, S.out.path_len, p->d_skip, Q, pp->max_path, p->d_paths, p->d_fe_len, h->stream));
-  HIPCHK(h, launch_frontend(fp, p->d_paths, p->d_fe_len, pp->max_path, p->d_st, p->d_en, p->d_ct, Q, p->fe, h->stream));
+  HIPCHK(h, launch_frontend(pp->frontend, p->d_paths, p->d_fe_len, pp->max_path, p->d_st, p->d_en, p->d_ct, Q, p->fe, h->stream));
   HIPCHK(h, p->plan_ev.record(2, h->stream));
-  // ---- the one read-back before the end: the tables that decide the grouping
+  return DFTPAV_OK;
+}
+
+// the one read-back before the end: the tables that decide the grouping
+static int plan_read_layouts(PlanCall &c) {
+  dftpav_planner *p = c.p;
+  dftpav_handle *h = c.h;
+  const size_t nq = (size_t)c.Q, MS = (size_t)c.MS;
   p->h_sints.assign(8 * nq, 0);
   p->h_nseg.assign(nq, 0);
   p->h_singul.assign(nq * MS, 0);
@@ -288,205 +308,196 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
   HIPCHK(h, hipMemcpyAsync(p->h_nstates.data(), p->fe.n_states, sizeof(int) * nq * MS, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipMemcpyAsync(p->h_dt.data(), p->fe.piece_dt, sizeof(double) * nq * MS, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  const int *s_status = p->h_sints.data(), *s_iters = p->h_sints.data() + 4 * nq, *s_len = p->h_sints.data() + 7 * nq;
-  for (int q = 0; q < Q; q++)
-    if (s_status[q] == 0) return DFTPAV_E_UNSUPPORTED; // a shot beyond the sample table (as dftpav_kino_search)
-  // ---- grouping.  Queries that were not resampled (arrived, a path beyond its padding) are kept out of it, as those without a path are
-  std::vector<int> gate(nq), group(nq), first(nq), status(nq);
+  for (int q = 0; q < c.Q; q++)
+    if (p->h_sints[q] == 0) return DFTPAV_E_UNSUPPORTED; // a search status of 0: a shot beyond the sample table (as dftpav_kino_search)
+  return DFTPAV_OK;
+}
+
+// The layout groups, their batches (created on first use) and their members in group order.  Queries that were not resampled
+// (arrived, a path beyond its padding) are kept out of the grouping, as those without a path are.
+static int plan_group(PlanCall &c) {
+  dftpav_planner *p = c.p;
+  dftpav_handle *h = c.h;
+  const int Q = c.Q, MS = c.MS;
+  const size_t nq = (size_t)Q;
+  const int *s_status = p->h_sints.data(), *s_len = p->h_sints.data() + 7 * nq;
+  c.gate.resize(nq), c.group.resize(nq), c.first.resize(nq), c.status.resize(nq);
   for (int q = 0; q < Q; q++) {
-    const bool usable = s_status[q] == DFTPAV_SEARCH_REACH_END && s_len[q] >= 2 && s_len[q] <= pp->max_path && !p->h_skip[q];
-    gate[q] = usable ? DFTPAV_SEARCH_REACH_END : DFTPAV_SEARCH_NO_PATH;
+    const bool usable = s_status[q] == DFTPAV_SEARCH_REACH_END && s_len[q] >= 2 && s_len[q] <= c.pp->max_path && !p->h_skip[q];
+    c.gate[q] = usable ? DFTPAV_SEARCH_REACH_END : DFTPAV_SEARCH_NO_PATH;
     if (!usable) {
       p->h_nseg[q] = 0;
       for (int i = 0; i < MS; i++) p->h_singul[(size_t)q * MS + i] = p->h_pn[(size_t)q * MS + i] = p->h_nstates[(size_t)q * MS + i] = 0, p->h_dt[(size_t)q * MS + i] = 0.0;
     } else if (p->h_nseg[q] >= 1 && p->h_nseg[q] <= MS) {
       for (int i = 0; i < p->h_nseg[q]; i++) // a segment of more pieces than the padding: its waypoints and poses were cut
-        if (p->h_pn[(size_t)q * MS + i] > MP || p->h_nstates[(size_t)q * MS + i] > MST) gate[q] = -1;
+        if (p->h_pn[(size_t)q * MS + i] > c.MP || p->h_nstates[(size_t)q * MS + i] > c.MST) c.gate[q] = -1;
     }
   }
   int ng = 0;
-  if (int rc = dftpav_plan_group_layouts(Q, MS, gate.data(), p->h_nseg.data(), p->h_singul.data(), p->h_pn.data(), group.data(), first.data(), &ng,
-                                         status.data()))
+  if (int rc = dftpav_plan_group_layouts(Q, MS, c.gate.data(), p->h_nseg.data(), p->h_singul.data(), p->h_pn.data(), c.group.data(),
+                                         c.first.data(), &ng, c.status.data()))
     return rc;
   for (int q = 0; q < Q; q++) {
-    if (p->h_skip[q]) status[q] = DFTPAV_PLAN_ARRIVED;
-    else if (gate[q] == -1 || (s_status[q] == DFTPAV_SEARCH_REACH_END && s_len[q] > pp->max_path)) status[q] = DFTPAV_PLAN_TOO_MANY_SEGMENTS;
+    if (p->h_skip[q]) c.status[q] = DFTPAV_PLAN_ARRIVED;
+    else if (c.gate[q] == -1 || (s_status[q] == DFTPAV_SEARCH_REACH_END && s_len[q] > c.pp->max_path)) c.status[q] = DFTPAV_PLAN_TOO_MANY_SEGMENTS;
   }
-  // ---- the groups' batches (created on first use), the members in group order
-  std::vector<dftpav_batch *> batch(ng, nullptr);
-  std::vector<int> g_off(ng + 1, 0);
+  c.batch.assign(ng, nullptr);
+  c.g_off.assign(ng + 1, 0);
   p->h_members.clear();
   for (int g = 0; g < ng; g++) {
-    const int f = first[g];
+    const int f = c.first[g];
     dftpav_layout lay{p->h_nseg[f], p->h_pn.data() + (size_t)f * MS, p->h_singul.data() + (size_t)f * MS, 4};
-    if (int rc = planner_batch(p, lay, &batch[g])) return rc;
-    g_off[g] = (int)p->h_members.size();
+    if (int rc = planner_batch(p, lay, &c.batch[g])) return rc;
+    c.g_off[g] = (int)p->h_members.size();
     for (int q = 0; q < Q; q++)
-      if (group[q] == g) {
-        if (batch[g]) p->h_members.push_back(q);
-        else status[q] = DFTPAV_PLAN_LAYOUT_UNSUPPORTED;
+      if (c.group[q] == g) {
+        if (c.batch[g]) p->h_members.push_back(q);
+        else c.status[q] = DFTPAV_PLAN_LAYOUT_UNSUPPORTED;
       }
-    g_off[g + 1] = (int)p->h_members.size();
-    p->group_sizes.push_back(g_off[g + 1] - g_off[g]);
+    c.g_off[g + 1] = (int)p->h_members.size();
+    p->group_sizes.push_back(c.g_off[g + 1] - c.g_off[g]);
   }
   HIPCHK(h, hipSetDevice(h->device));
   if (!p->h_members.empty())
     HIPCHK(h, hipMemcpyAsync(p->d_members, p->h_members.data(), sizeof(int) * p->h_members.size(), hipMemcpyHostToDevice, h->stream));
-  // ---- per group: pack -> rectangles -> solve -> coefficients -> collision re-check (-> limits) (-> clearance) (-> penalty gate)
-  // -> selection; nothing waits in between
-  size_t pose_off = 0;
-  if (clr) { // the map's distance field if the map changed since its last build; the rows no restart is solved for: FAR, -1, +inf
+  return DFTPAV_OK;
+}
+
+// the filters' rows of the queries no restart is solved for, and the reject flags (trajectory order as d_col: the filters only set them)
+static int plan_clear_filter_rows(PlanCall &c) {
+  dftpav_planner *p = c.p;
+  dftpav_handle *h = c.h;
+  const size_t rows = (size_t)c.Q * c.R;
+  if (p->clr.on) { // the map's distance field if the map changed since its last build
     if (int rc = ensure_dist_field(h)) return rc;
-    const size_t rows = nq * (size_t)R;
-    HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)p->d_clr_d2, DFTPAV_DIST_FAR, rows, h->stream));
-    HIPCHK(h, hipMemsetAsync(p->d_clr_arg, 0xff, sizeof(int) * rows, h->stream));
-    HIPCHK(h, hipMemcpyAsync(p->d_clr_m, p->h_clr_inf.data(), sizeof(double) * rows, hipMemcpyHostToDevice, h->stream));
+    if (int rc = p->clr.clear(h, rows)) return rc;
   }
-  if (filt) { // the rows of the queries no restart is solved for: zero, arg -1
-    const size_t rows = nq * (size_t)R;
-    HIPCHK(h, hipMemsetAsync(p->d_lim_max, 0, sizeof(double) * kLimQ * rows, h->stream));
-    HIPCHK(h, hipMemsetAsync(p->d_lim_arg, 0xff, sizeof(int) * kLimQ * rows, h->stream));
-    HIPCHK(h, hipMemsetAsync(p->d_lim_viol, 0, sizeof(int) * kLimQ * rows, h->stream));
-    HIPCHK(h, hipMemsetAsync(p->d_lim_feas, 0, sizeof(int) * rows, h->stream));
-  }
-  if (pen) { // likewise: zero rows
-    const size_t rows = nq * (size_t)R;
-    HIPCHK(h, hipMemsetAsync(p->d_pen_terms, 0, sizeof(double) * kCostTerms * rows, h->stream));
-    HIPCHK(h, hipMemsetAsync(p->d_pen_rej, 0, sizeof(int) * rows, h->stream));
-  }
-  const bool any_filter = filt || clr || pen;
-  if (any_filter) // the reject flags, trajectory order as d_col: the filters only set them
-    HIPCHK(h, hipMemsetAsync(p->d_reject, 0, sizeof(int) * nq * (size_t)R, h->stream));
-  for (int g = 0; g < ng; g++) {
-    dftpav_batch *b = batch[g];
-    const int nm = g_off[g + 1] - g_off[g];
-    if (!b || nm == 0) continue;
-    const DevLayout &L = b->L;
-    b->pending = false;
-    b->n_active = nm * R;
-    b->t_now = t_now;
-    b->epis = 0.0; // help_eps of the live call, traj_manager.cpp:610
-    b->uploaded = true;
-    b->solved = false;
-    b->coef_override = false;
-    b->dev_version = -1; // n_active / t_now live in the device copy of the launch descriptor
-    PlanPackArgs A{};
-    A.L = L;
-    A.fe = p->fe;
-    A.members = p->d_members + g_off[g];
-    A.n_members = nm;
-    A.n_restarts = R;
-    A.sigma = pp->sigma;
-    A.lo = pp->dur_lo;
-    A.hi = pp->dur_hi;
-    A.seed = pp->seed;
-    A.mini_T = h->params.mini_T;
-    A.max_vel[0] = h->params.max_forward_vel;
-    A.max_vel[1] = h->params.max_backward_vel;
-    A.max_acc[0] = h->params.max_forward_acc;
-    A.max_acc[1] = h->params.max_backward_acc;
-    A.x0 = b->d_x0;
-    A.iniS = b->d_iniS;
-    A.finS = b->d_finS;
-    A.poses = p->d_poses + 3 * pose_off;
-    A.mini_t_flag = p->d_minit;
-    HIPCHK(h, launch_plan_pack(A, h->stream));
-    if (int rc = corridor_into_batch(b, A.poses, nm * L.Npts, R)) return rc;
-    pose_off += (size_t)nm * L.Npts;
-    if (int rc = solve_impl(b, nullptr, false)) return rc;
-    DevBatch D;
-    if (int rc = ensure_coeffs(b, D)) return rc;
-    int *col = p->d_col + (size_t)g_off[g] * R, *fst = p->d_first + (size_t)g_off[g] * R;
-    if (int rc = validate_on_stream(b, nm * R, p->d_vt, n_t, n_v, pp->check_dt, col, fst)) return rc;
-    int *rej = any_filter ? p->d_reject + (size_t)g_off[g] * R : nullptr;
-    if (filt) { // rejects a trajectory that is not feasible
-      LimitsBatchArgs LA{};
-      if (!limits_common(h->params, p->lim, LA.C)) return DFTPAV_E_INVALID; // (checked when the filter was set)
-      LA.C.tab = SampleTable{p->lim_tab.d, p->lim_tab.n_t, p->lim_dt};
-      LA.C.max_abs = p->d_lim_max;
-      LA.C.arg = p->d_lim_arg;
-      LA.C.violated = p->d_lim_viol;
-      LA.C.feasible = p->d_lim_feas;
-      LA.coeffs = b->d_coef;
-      LA.piece_dt = b->d_dt;
-      LA.L = L;
-      LA.B = nm * R;
-      LA.members = A.members;
-      LA.R = R;
-      LA.reject = rej;
-      HIPCHK(h, launch_limits_batch(LA, h->stream));
-    }
-    if (clr) { // rejects a trajectory unless clearance >= min_clearance
-      ClearanceBatchArgs CA{};
-      CA.C = clearance_common(h, p->clr_tab.d, p->clr_tab.n_t, p->clr_tab.n_v, p->clr_dt);
-      CA.C.min_d2 = p->d_clr_d2;
-      CA.C.arg = p->d_clr_arg;
-      CA.C.clearance = p->d_clr_m;
-      CA.coeffs = b->d_coef;
-      CA.piece_dt = b->d_dt;
-      CA.L = L;
-      CA.B = nm * R;
-      CA.members = A.members;
-      CA.R = R;
-      CA.reject = rej;
-      CA.min_clearance = p->clr_min;
-      HIPCHK(h, launch_clearance_batch(CA, h->stream));
-    }
-    if (pen) { // rejects a trajectory with a penalty sum above its cap
-      if (int rc = cost_terms_on_stream(b, nullptr)) return rc;
-      PenaltyGateArgs G{};
-      G.terms = b->d_terms;
-      G.members = A.members;
-      G.n = nm * R;
-      G.R = R;
-      G.cap_corridor = p->pen.corridor;
-      G.cap_surround = p->pen.surround;
-      G.cap_feas = p->pen.feasibility;
-      G.r_terms = p->d_pen_terms;
-      G.r_rejected = p->d_pen_rej;
-      G.reject = rej;
-      HIPCHK(h, launch_penalty_gate(G, h->stream));
-    }
-    PlanSelectArgs Z{};
-    Z.cost = b->d_f;
-    Z.success = b->d_success;
-    Z.collision = col;
-    Z.reject = rej;
-    Z.status = b->d_status;
-    Z.iters = b->d_iters;
-    Z.evals = b->d_evals;
-    Z.first_sample = fst;
-    Z.x = b->d_x_out;
-    Z.coef = b->d_coef;
-    Z.dt = b->d_dt;
-    Z.n = L.n;
-    Z.n_coef = 12 * L.Ntot;
-    Z.M = L.M;
-    Z.members = A.members;
-    Z.n_members = nm;
-    Z.R = R;
-    Z.winner = p->d_winner;
-    Z.w_cost = p->d_wcost;
-    Z.w_iters = p->d_witers;
-    Z.w_x = p->d_wx;
-    Z.w_coef = p->d_wcoef;
-    Z.w_dt = p->d_wdt;
-    Z.x_stride = DFTPAV_PLAN_MAX_VARS;
-    Z.coef_stride = MS * MP * 12;
-    Z.dt_stride = MS;
-    Z.r_cost = p->d_rcost;
-    Z.r_status = p->d_rint[0];
-    Z.r_success = p->d_rint[1];
-    Z.r_iters = p->d_rint[2];
-    Z.r_evals = p->d_rint[3];
-    Z.r_collision = p->d_rint[4];
-    Z.r_first_sample = p->d_rint[5];
-    HIPCHK(h, launch_plan_select(Z, h->stream));
-  }
-  HIPCHK(h, p->plan_ev.record(3, h->stream));
-  p->plan_ev.complete();
-  // ---- the compact results
-  std::vector<int> winner(nq, -1);
+  if (p->lim.on)
+    if (int rc = p->lim.clear(h, rows)) return rc;
+  if (p->pen.on)
+    if (int rc = p->pen.clear(h, rows)) return rc;
+  if (p->lim.on || p->clr.on || p->pen.on) HIPCHK(h, hipMemsetAsync(p->d_reject, 0, sizeof(int) * rows, h->stream));
+  return DFTPAV_OK;
+}
+
+// a group's queries out of the front-end arrays into its batch, their restarts drawn; *poses: the group's constraint-point poses
+static int plan_pack_group(PlanCall &c, int g, double **poses) {
+  dftpav_planner *p = c.p;
+  dftpav_handle *h = c.h;
+  dftpav_batch *b = c.batch[g];
+  const int nm = c.g_off[g + 1] - c.g_off[g];
+  b->pending = false;
+  b->n_active = nm * c.R;
+  b->t_now = c.t_now;
+  b->epis = 0.0; // help_eps of the live call, traj_manager.cpp:610
+  b->uploaded = true;
+  b->solved = false;
+  b->coef_override = false;
+  b->dev_version = -1; // n_active / t_now live in the device copy of the launch descriptor
+  PlanPackArgs A{};
+  A.L = b->L;
+  A.fe = p->fe;
+  A.members = p->d_members + c.g_off[g];
+  A.n_members = nm;
+  A.n_restarts = c.R;
+  A.sigma = c.pp->sigma;
+  A.lo = c.pp->dur_lo;
+  A.hi = c.pp->dur_hi;
+  A.seed = c.pp->seed;
+  A.mini_T = h->params.mini_T;
+  A.max_vel[0] = h->params.max_forward_vel;
+  A.max_vel[1] = h->params.max_backward_vel;
+  A.max_acc[0] = h->params.max_forward_acc;
+  A.max_acc[1] = h->params.max_backward_acc;
+  A.x0 = b->d_x0;
+  A.iniS = b->d_iniS;
+  A.finS = b->d_finS;
+  A.poses = *poses = p->d_poses + 3 * c.pose_off;
+  A.mini_t_flag = p->d_minit;
+  HIPCHK(h, launch_plan_pack(A, h->stream));
+  c.pose_off += (size_t)nm * b->L.Npts;
+  return DFTPAV_OK;
+}
+
+// per query of a group the cheapest restart that may win, its plan into the compact outputs, every restart's row
+static int plan_select_group(PlanCall &c, int g, int *col, int *fst, int *rej) {
+  dftpav_planner *p = c.p;
+  const dftpav_batch *b = c.batch[g];
+  PlanSelectArgs Z{};
+  Z.cost = b->d_f;
+  Z.success = b->d_success;
+  Z.collision = col;
+  Z.reject = rej;
+  Z.status = b->d_status;
+  Z.iters = b->d_iters;
+  Z.evals = b->d_evals;
+  Z.first_sample = fst;
+  Z.x = b->d_x_out;
+  Z.coef = b->d_coef;
+  Z.dt = b->d_dt;
+  Z.n = b->L.n;
+  Z.n_coef = 12 * b->L.Ntot;
+  Z.M = b->L.M;
+  Z.members = p->d_members + c.g_off[g];
+  Z.n_members = c.g_off[g + 1] - c.g_off[g];
+  Z.R = c.R;
+  Z.winner = p->d_winner;
+  Z.w_cost = p->d_wcost;
+  Z.w_iters = p->d_witers;
+  Z.w_x = p->d_wx;
+  Z.w_coef = p->d_wcoef;
+  Z.w_dt = p->d_wdt;
+  Z.x_stride = DFTPAV_PLAN_MAX_VARS;
+  Z.coef_stride = c.MS * c.MP * 12;
+  Z.dt_stride = c.MS;
+  Z.r_cost = p->d_rcost;
+  Z.r_status = p->d_rint[0];
+  Z.r_success = p->d_rint[1];
+  Z.r_iters = p->d_rint[2];
+  Z.r_evals = p->d_rint[3];
+  Z.r_collision = p->d_rint[4];
+  Z.r_first_sample = p->d_rint[5];
+  HIPCHK(c.h, launch_plan_select(Z, c.h->stream));
+  return DFTPAV_OK;
+}
+
+// one group: pack -> rectangles -> solve -> coefficients -> collision re-check (-> limits) (-> clearance) (-> penalty gate) -> selection;
+// nothing waits in between, or between groups
+static int plan_one_group(PlanCall &c, int g) {
+  dftpav_planner *p = c.p;
+  dftpav_handle *h = c.h;
+  dftpav_batch *b = c.batch[g];
+  const int nm = c.g_off[g + 1] - c.g_off[g], R = c.R;
+  if (!b || nm == 0) return DFTPAV_OK;
+  double *poses = nullptr;
+  if (int rc = plan_pack_group(c, g, &poses)) return rc;
+  if (int rc = corridor_into_batch(b, poses, nm * b->L.Npts, R)) return rc;
+  if (int rc = solve_impl(b, nullptr, false)) return rc;
+  DevBatch D;
+  if (int rc = ensure_coeffs(b, D)) return rc;
+  const size_t row0 = (size_t)c.g_off[g] * R;
+  const int *members = p->d_members + c.g_off[g];
+  int *col = p->d_col + row0, *fst = p->d_first + row0;
+  if (int rc = validate_on_stream(b, nm * R, p->d_vt, c.n_t, c.n_v, c.pp->check_dt, col, fst)) return rc;
+  int *rej = p->lim.on || p->clr.on || p->pen.on ? p->d_reject + row0 : nullptr;
+  if (p->lim.on) // rejects a trajectory that is not feasible
+    if (int rc = p->lim.run(h, b, members, nm, R, rej)) return rc;
+  if (p->clr.on) // rejects a trajectory unless clearance >= min_clearance
+    if (int rc = p->clr.run(h, b, members, nm, R, rej)) return rc;
+  if (p->pen.on) // rejects a trajectory with a penalty sum above its cap
+    if (int rc = p->pen.run(h, b, members, nm, R, rej)) return rc;
+  return plan_select_group(c, g, col, fst, rej);
+}
+
+// the compact results, the final wait, the statuses that depend on them, and what dftpav_planner_adopt needs of this call
+static int plan_results(PlanCall &c) {
+  dftpav_planner *p = c.p;
+  dftpav_handle *h = c.h;
+  const dftpav_plan_out *out = c.out;
+  const int Q = c.Q;
+  const size_t nq = (size_t)Q, R = (size_t)c.R, MS = (size_t)c.MS, MP = (size_t)c.MP;
+  std::vector<int> &winner = p->last_winner, &status = c.status;
+  winner.assign(nq, -1);
   p->h_minit.assign(nq, 0);
   HIPCHK(h, fetch_async(h, winner.data(), p->d_winner, sizeof(int) * nq));
   HIPCHK(h, fetch_async(h, p->h_minit.data(), p->d_minit, sizeof(int) * nq));
@@ -520,20 +531,40 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
   if (out->singul) std::memcpy(out->singul, p->h_singul.data(), sizeof(int) * nq * MS);
   if (out->piece_nums) std::memcpy(out->piece_nums, p->h_pn.data(), sizeof(int) * nq * MS);
   if (out->piece_dt) std::memcpy(out->piece_dt, p->h_dt.data(), sizeof(double) * nq * MS);
-  if (out->search_status) std::memcpy(out->search_status, s_status, sizeof(int) * nq);
-  if (out->search_iters) std::memcpy(out->search_iters, s_iters, sizeof(int) * nq);
-  if (out->search_path_len) std::memcpy(out->search_path_len, s_len, sizeof(int) * nq);
-  // what dftpav_planner_adopt needs of this call (the winners' pieces stay where they are, in the arena)
+  if (out->search_status) std::memcpy(out->search_status, p->h_sints.data(), sizeof(int) * nq);
+  if (out->search_iters) std::memcpy(out->search_iters, p->h_sints.data() + 4 * nq, sizeof(int) * nq);
+  if (out->search_path_len) std::memcpy(out->search_path_len, p->h_sints.data() + 7 * nq, sizeof(int) * nq);
+  // what dftpav_planner_adopt needs of this call (the winners' pieces stay where they are, in the arena; last_winner: above)
   p->last_status = status;
-  p->last_winner = winner;
-  p->last_goal.assign(end_states, end_states + 4 * nq);
-  p->last_MS = MS;
-  p->last_MP = MP;
+  p->last_goal.assign(c.end_states, c.end_states + 4 * nq);
+  p->last_MS = c.MS;
+  p->last_MP = c.MP;
   p->last_Q = Q;
-  p->last_lim = filt;
-  p->last_pen = pen;
-  p->last_clr = clr;
+  p->lim.last = p->lim.on;
+  p->pen.last = p->pen.on;
+  p->clr.last = p->clr.on;
   return DFTPAV_OK;
+}
+
+extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *pp, const double *start_states, const double *start_ctrl,
+                                   const double *end_states, int Q, double t_now, const dftpav_plan_out *out) {
+  if (int rc = plan_check_params(p, pp, out, Q)) return rc;
+  p->group_sizes.clear();
+  p->plan_ev.reset();
+  p->last_Q = 0; // nothing to adopt, no filter rows to read, until this call has ended well
+  p->lim.last = p->pen.last = p->clr.last = false;
+  if (Q == 0) return DFTPAV_OK;
+  if (!start_states || !start_ctrl || !end_states) return DFTPAV_E_INVALID;
+  PlanCall c{p, p->h, pp, start_states, start_ctrl, end_states, Q, t_now, out};
+  if (int rc = plan_search(c)) return rc;            // marks 0, 1, 2
+  if (int rc = plan_read_layouts(c)) return rc;      // the one wait before the end
+  if (int rc = plan_group(c)) return rc;
+  if (int rc = plan_clear_filter_rows(c)) return rc; // (nothing with every filter off)
+  for (size_t g = 0; g < c.batch.size(); g++)
+    if (int rc = plan_one_group(c, (int)g)) return rc;
+  HIPCHK(c.h, p->plan_ev.record(3, c.h->stream));
+  p->plan_ev.complete();
+  return plan_results(c);
 }
 
 extern "C" int dftpav_debug_plan_select(dftpav_handle *h, int n_query, int n_restarts, const double *cost, const int *success,
@@ -979,8 +1010,11 @@ extern "C" int dftpav_replan_tick(dftpav_planner *p, const dftpav_plan_params *p
   if (int rc = replan_check_enqueue(p, t_now, budget, end_states, ego_states, pp->check_dt, pp->vertex_res)) return rc;
   // ---- the tick's one extra wait: replan, start_state, start_ctrl (with whatever else of the check the caller asked for)
   const size_t S = (size_t)p->max_queries;
-  std::vector<int> flag(S, 0);
-  std::vector<double> st(4 * S), ct(2 * S);
+  std::vector<int> &flag = p->h_rc_flag; // (the planner's: a failing fetch below returns with these copies enqueued)
+  std::vector<double> &st = p->h_rc_st, &ct = p->h_rc_ct;
+  flag.assign(S, 0);
+  st.resize(4 * S);
+  ct.resize(2 * S);
   HIPCHK(h, hipMemcpyAsync(flag.data(), p->d_rc_int + (size_t)kRcReplan * S, sizeof(int) * S, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipMemcpyAsync(st.data(), p->d_rc_st, sizeof(double) * 4 * S, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipMemcpyAsync(ct.data(), p->d_rc_ct, sizeof(double) * 2 * S, hipMemcpyDeviceToHost, h->stream));
@@ -1101,8 +1135,7 @@ extern "C" int dftpav_publish_last_ms(dftpav_planner *p, float *ms) {
 // A validation_table for (check_dt, vertex_res) kept on the device.  It lies at the head of the filter's one allocation `base`, made by
 // the first call (rows(take) names the filter's other arrays), and is uploaded again only when check_dt is not the one T holds.  A
 // refusal changes nothing.
-template <class F> static int cached_table(dftpav_planner *p, double check_dt, double vertex_res, unsigned char *&base, CachedTable &T, F &&rows) {
-  dftpav_handle *h = p->h;
+template <class F> static int cached_table(dftpav_handle *h, double check_dt, double vertex_res, unsigned char *&base, CachedTable &T, F &&rows) {
   HIPCHK(h, hipSetDevice(h->device));
   std::vector<double> tab;
   int n_t = 0, n_v = 0;
@@ -1148,77 +1181,127 @@ extern "C" int dftpav_planner_check_limits(dftpav_planner *p, double check_dt, c
   });
 }
 
+// the limit filter (LimitFilter, capi_internal.h)
+bool LimitFilter::common(const dftpav_handle *h, LimitsCommon &C) const {
+  C = rows();
+  C.tab = SampleTable{tab.d, tab.n_t, tab.dt};
+  return limits_common(h->params, lim, C);
+}
+int LimitFilter::configure(dftpav_handle *h, size_t rows_cap, const dftpav_limits &l, double check_dt) {
+  if (int rc = cached_table(h, check_dt, 1.0, d, tab, [&](auto &take) { // (the kernel reads the sample times only)
+        d_max = (double *)take(sizeof(double) * kLimQ * rows_cap);
+        d_int = (int *)take(sizeof(int) * (2 * kLimQ + 1) * rows_cap);
+      }))
+    return rc;
+  cap = rows_cap;
+  lim = l;
+  on = true;
+  return DFTPAV_OK;
+}
+int LimitFilter::clear(dftpav_handle *h, size_t rows) { // zero, arg -1
+  const LimitsCommon C = this->rows();
+  HIPCHK(h, hipMemsetAsync(C.max_abs, 0, sizeof(double) * kLimQ * rows, h->stream));
+  HIPCHK(h, hipMemsetAsync(C.arg, 0xff, sizeof(int) * kLimQ * rows, h->stream));
+  HIPCHK(h, hipMemsetAsync(C.violated, 0, sizeof(int) * kLimQ * rows, h->stream));
+  HIPCHK(h, hipMemsetAsync(C.feasible, 0, sizeof(int) * rows, h->stream));
+  return DFTPAV_OK;
+}
+int LimitFilter::run(dftpav_handle *h, dftpav_batch *b, const int *members, int nm, int R, int *reject) {
+  LimitsBatchArgs A{};
+  if (!common(h, A.C)) return DFTPAV_E_INVALID; // (checked when the filter was set)
+  A.coeffs = b->d_coef;
+  A.piece_dt = b->d_dt;
+  A.L = b->L;
+  A.B = nm * R;
+  A.members = members;
+  A.R = R;
+  A.reject = reject;
+  HIPCHK(h, launch_limits_batch(A, h->stream));
+  return DFTPAV_OK;
+}
+int LimitFilter::fetch(dftpav_handle *h, const dftpav_limits_out *out, size_t rows) { return fetch_limits(h, out, this->rows(), rows); }
+
 extern "C" int dftpav_planner_set_limit_filter(dftpav_planner *p, const dftpav_limits *l, double check_dt) {
   if (!p) return DFTPAV_E_INVALID;
   if (!l) { // off: the buffers stay, nothing reads them
-    p->lim_on = false;
+    p->lim.on = false;
     return DFTPAV_OK;
   }
   if (!(check_dt > 0.0) || !std::isfinite(check_dt)) return DFTPAV_E_INVALID;
-  dftpav_handle *h = p->h;
   LimitsCommon C{};
-  if (!limits_common(h->params, *l, C)) return DFTPAV_E_INVALID;
-  const size_t rows = (size_t)p->max_queries * p->R;
-  if (int rc = cached_table(p, check_dt, 1.0, p->d_lim, p->lim_tab, [&](auto &take) { // (the kernel reads the sample times only)
-        p->d_lim_max = (double *)take(sizeof(double) * kLimQ * rows);
-        p->d_lim_arg = (int *)take(sizeof(int) * kLimQ * rows);
-        p->d_lim_viol = (int *)take(sizeof(int) * kLimQ * rows);
-        p->d_lim_feas = (int *)take(sizeof(int) * rows);
-      }))
-    return rc;
-  p->lim = *l;
-  p->lim_dt = check_dt;
-  p->lim_on = true;
-  return DFTPAV_OK;
+  if (!limits_common(p->h->params, *l, C)) return DFTPAV_E_INVALID;
+  return p->lim.configure(p->h, (size_t)p->max_queries * p->R, *l, check_dt);
 }
 
 extern "C" int dftpav_planner_last_limits(dftpav_planner *p, const dftpav_limits_out *out) {
-  if (!p || !out || !p->last_lim || p->last_Q <= 0) return DFTPAV_E_INVALID;
+  if (!p || !out || !p->lim.last || p->last_Q <= 0) return DFTPAV_E_INVALID;
   dftpav_handle *h = p->h;
   HIPCHK(h, hipSetDevice(h->device));
-  LimitsCommon C{};
-  C.max_abs = p->d_lim_max;
-  C.arg = p->d_lim_arg;
-  C.violated = p->d_lim_viol;
-  C.feasible = p->d_lim_feas;
-  if (int rc = fetch_limits(h, out, C, (size_t)p->last_Q * p->R)) return rc;
+  if (int rc = p->lim.fetch(h, out, (size_t)p->last_Q * p->R)) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return DFTPAV_OK;
 }
 
 // ------------------------------------------------- the residual penalties of solved plans (solver_ref.hip: kModeTerms, plan.hip)
-extern "C" int dftpav_planner_set_penalty_filter(dftpav_planner *p, const dftpav_penalty_caps *caps) {
-  if (!p) return DFTPAV_E_INVALID;
-  if (!caps) { // off: the buffers stay, nothing reads them
-    p->pen_on = false;
-    return DFTPAV_OK;
-  }
-  if (!(caps->corridor >= 0.0) || !(caps->surround >= 0.0) || !(caps->feasibility >= 0.0)) return DFTPAV_E_INVALID; // negative, NaN
-  dftpav_handle *h = p->h;
-  if (!p->d_pen) {
+// the penalty filter (PenaltyFilter, capi_internal.h)
+int PenaltyFilter::configure(dftpav_handle *h, size_t rows_cap, const dftpav_penalty_caps &c) {
+  if (!d) {
     HIPCHK(h, hipSetDevice(h->device));
-    const size_t rows = (size_t)p->max_queries * p->R;
     auto fields = [&](auto &take) {
-      p->d_pen_terms = (double *)take(sizeof(double) * kCostTerms * rows);
-      p->d_pen_rej = (int *)take(sizeof(int) * rows);
+      d_terms = (double *)take(sizeof(double) * kCostTerms * rows_cap);
+      d_rej = (int *)take(sizeof(int) * rows_cap);
     };
     unsigned char *base = nullptr;
     HIPCHK(h, hipMalloc(&base, carve(nullptr, fields)));
     carve(base, fields);
-    p->d_pen = base;
+    d = base;
   }
-  p->pen = *caps;
-  p->pen_on = true;
+  caps = c;
+  on = true;
+  return DFTPAV_OK;
+}
+int PenaltyFilter::clear(dftpav_handle *h, size_t rows) { // zero
+  HIPCHK(h, hipMemsetAsync(d_terms, 0, sizeof(double) * kCostTerms * rows, h->stream));
+  HIPCHK(h, hipMemsetAsync(d_rej, 0, sizeof(int) * rows, h->stream));
+  return DFTPAV_OK;
+}
+int PenaltyFilter::run(dftpav_handle *h, dftpav_batch *b, const int *members, int nm, int R, int *reject) {
+  if (int rc = cost_terms_on_stream(b, nullptr)) return rc;
+  PenaltyGateArgs G{};
+  G.terms = b->d_terms;
+  G.members = members;
+  G.n = nm * R;
+  G.R = R;
+  G.cap_corridor = caps.corridor;
+  G.cap_surround = caps.surround;
+  G.cap_feas = caps.feasibility;
+  G.r_terms = d_terms;
+  G.r_rejected = d_rej;
+  G.reject = reject;
+  HIPCHK(h, launch_penalty_gate(G, h->stream));
+  return DFTPAV_OK;
+}
+int PenaltyFilter::fetch(dftpav_handle *h, double *r_terms, int *r_rejected, size_t rows) {
+  HIPCHK(h, fetch_async(h, r_terms, d_terms, sizeof(double) * kCostTerms * rows));
+  HIPCHK(h, fetch_async(h, r_rejected, d_rej, sizeof(int) * rows));
   return DFTPAV_OK;
 }
 
+extern "C" int dftpav_planner_set_penalty_filter(dftpav_planner *p, const dftpav_penalty_caps *caps) {
+  if (!p) return DFTPAV_E_INVALID;
+  if (!caps) { // off: the buffers stay, nothing reads them
+    p->pen.on = false;
+    return DFTPAV_OK;
+  }
+  if (!(caps->corridor >= 0.0) || !(caps->surround >= 0.0) || !(caps->feasibility >= 0.0)) return DFTPAV_E_INVALID; // negative, NaN
+  return p->pen.configure(p->h, (size_t)p->max_queries * p->R, *caps);
+}
+
 extern "C" int dftpav_planner_last_cost_terms(dftpav_planner *p, double *r_terms, int *r_rejected) {
-  if (!p || (!r_terms && !r_rejected) || !p->last_pen || p->last_Q <= 0) return DFTPAV_E_INVALID;
+  if (!p || (!r_terms && !r_rejected) || !p->pen.last || p->last_Q <= 0) return DFTPAV_E_INVALID;
   dftpav_handle *h = p->h;
   HIPCHK(h, hipSetDevice(h->device));
-  const size_t rows = (size_t)p->last_Q * p->R;
-  HIPCHK(h, fetch_async(h, r_terms, p->d_pen_terms, sizeof(double) * kCostTerms * rows));
-  HIPCHK(h, fetch_async(h, r_rejected, p->d_pen_rej, sizeof(int) * rows));
+  if (int rc = p->pen.fetch(h, r_terms, r_rejected, (size_t)p->last_Q * p->R)) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return DFTPAV_OK;
 }
@@ -1241,32 +1324,59 @@ extern "C" int dftpav_planner_check_clearance(dftpav_planner *p, double check_dt
   });
 }
 
+// the clearance filter (ClearanceFilter, capi_internal.h)
+int ClearanceFilter::configure(dftpav_handle *h, size_t rows_cap, double min_clearance, double check_dt) {
+  if (int rc = cached_table(h, check_dt, kClearanceVertexRes, d, tab, [&](auto &take) {
+        d_m = (double *)take(sizeof(double) * rows_cap);
+        d_d2 = (int *)take(sizeof(int) * rows_cap);
+        d_arg = (int *)take(sizeof(int) * rows_cap);
+      }))
+    return rc;
+  if (h_inf.empty()) h_inf.assign(rows_cap, HUGE_VAL);
+  min = min_clearance;
+  on = true;
+  return DFTPAV_OK;
+}
+int ClearanceFilter::clear(dftpav_handle *h, size_t rows) { // FAR, -1, +inf
+  HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)d_d2, DFTPAV_DIST_FAR, rows, h->stream));
+  HIPCHK(h, hipMemsetAsync(d_arg, 0xff, sizeof(int) * rows, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_m, h_inf.data(), sizeof(double) * rows, hipMemcpyHostToDevice, h->stream));
+  return DFTPAV_OK;
+}
+int ClearanceFilter::run(dftpav_handle *h, dftpav_batch *b, const int *members, int nm, int R, int *reject) {
+  ClearanceBatchArgs A{};
+  A.C = clearance_common(h, tab.d, tab.n_t, tab.n_v, tab.dt);
+  A.C.min_d2 = d_d2;
+  A.C.arg = d_arg;
+  A.C.clearance = d_m;
+  A.coeffs = b->d_coef;
+  A.piece_dt = b->d_dt;
+  A.L = b->L;
+  A.B = nm * R;
+  A.members = members;
+  A.R = R;
+  A.reject = reject;
+  A.min_clearance = min;
+  HIPCHK(h, launch_clearance_batch(A, h->stream));
+  return DFTPAV_OK;
+}
+int ClearanceFilter::fetch(dftpav_handle *h, const dftpav_clearance_out *out, size_t rows) { return fetch_clearance(h, out, d_d2, d_arg, d_m, rows); }
+
 extern "C" int dftpav_planner_set_clearance_filter(dftpav_planner *p, double min_clearance, double check_dt) {
   if (!p) return DFTPAV_E_INVALID;
   if (min_clearance < 0.0) { // off: the buffers stay, nothing reads them
-    p->clr_on = false;
+    p->clr.on = false;
     return DFTPAV_OK;
   }
   if (!std::isfinite(min_clearance) || !(check_dt > 0.0) || !std::isfinite(check_dt)) return DFTPAV_E_INVALID; // NaN, +inf
-  const size_t rows = (size_t)p->max_queries * p->R;
-  if (int rc = cached_table(p, check_dt, kClearanceVertexRes, p->d_clr, p->clr_tab, [&](auto &take) {
-        p->d_clr_m = (double *)take(sizeof(double) * rows);
-        p->d_clr_d2 = (int *)take(sizeof(int) * rows);
-        p->d_clr_arg = (int *)take(sizeof(int) * rows);
-      }))
-    return rc;
-  if (p->h_clr_inf.empty()) p->h_clr_inf.assign(rows, HUGE_VAL);
-  p->clr_min = min_clearance;
-  p->clr_dt = check_dt;
-  p->clr_on = true;
-  return DFTPAV_OK;
+  return p->clr.configure(p->h, (size_t)p->max_queries * p->R, min_clearance, check_dt);
 }
 
 extern "C" int dftpav_planner_last_clearance(dftpav_planner *p, const dftpav_clearance_out *out) {
-  if (!p || !out || !p->last_clr || p->last_Q <= 0) return DFTPAV_E_INVALID;
+  if (!p || !out || !p->clr.last || p->last_Q <= 0) return DFTPAV_E_INVALID;
   dftpav_handle *h = p->h;
   HIPCHK(h, hipSetDevice(h->device));
-  if (int rc = fetch_clearance(h, out, p->d_clr_d2, p->d_clr_arg, p->d_clr_m, (size_t)p->last_Q * p->R)) return rc;
+  if (int rc = p->clr.fetch(h, out, (size_t)p->last_Q * p->R)) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return DFTPAV_OK;
 }
@@ -1323,11 +1433,11 @@ extern "C" int dftpav_planner_sample_poses(dftpav_planner *p, double t0, double 
     return DFTPAV_OK;
   }
   HIPCHK(h, hipSetDevice(h->device));
+  const size_t n = (size_t)K * conflict_s_pad(p);
+  std::vector<double> soa(4 * n); // cx | cy | cs | sn, each [K][S_pad]; declared in front of tmp, whose end waits for the stream
   DevScratch tmp(h);
   ConflictPoses P{};
   if (int rc = conflict_poses_on_stream(p, tmp, t0, dt, K, P)) return rc;
-  const size_t n = (size_t)K * P.S_pad;
-  std::vector<double> soa(4 * n); // cx | cy | cs | sn, each [K][S_pad]
   HIPCHK(h, hipMemcpyAsync(soa.data(), P.cx, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   for (size_t k = 0; k < (size_t)K; k++)

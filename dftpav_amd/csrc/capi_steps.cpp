@@ -622,10 +622,11 @@ int dftpav::check_limits_rows(dftpav_handle *h, double check_dt, size_t n, const
   double *d_tab = nullptr;
   DevScratch tmp(h);
   HIPCHK(h, tmp.alloc(d_tab, (size_t)n_t));
-  HIPCHK(h, tmp.alloc(C.max_abs, kLimQ * n));
-  HIPCHK(h, tmp.alloc(C.arg, (2 * kLimQ + 1) * n)); // arg | violated | feasible
-  C.violated = C.arg + kLimQ * n;
-  C.feasible = C.arg + 2 * kLimQ * n;
+  double *d_max = nullptr;
+  int *d_int = nullptr; // arg | violated | feasible
+  HIPCHK(h, tmp.alloc(d_max, kLimQ * n));
+  HIPCHK(h, tmp.alloc(d_int, (2 * kLimQ + 1) * n));
+  limit_rows(C, d_max, d_int, n);
   C.tab = SampleTable{d_tab, n_t, check_dt};
   h->lim_ev.reset(); // until the whole chain has run
   HIPCHK(h, hipMemcpyAsync(d_tab, tab.data(), sizeof(double) * (size_t)n_t, hipMemcpyHostToDevice, h->stream));

@@ -407,6 +407,52 @@ def test_composition_with_the_limit_and_penalty_filters(hiplib, arena):
     pl.close()
 
 
+def test_filter_rows_do_not_leak_between_calls(hiplib, arena):
+    """all three filters on: after a call of Q queries, a call of the first Q // 2 on the same planner leaves the rows and the plans
+    of a fresh planner given that second call alone; a read-out of a filter the latest call ran without is refused"""
+    Q, S, E = arena["Q"], arena["S"], arena["E"]
+    n = Q // 2
+    caps = hiplib.PenaltyCaps(**tc.CAPS)
+    lim = hiplib.default_limits()
+    lim.max_forward_vel, lim.max_backward_vel, lim.max_forward_cur, lim.max_backward_cur = 5.01, 2.01, 1.01, 1.01   # tests/test_gpu_limits.py: FILTER
+
+    def planner():
+        pl = hiplib.Planner(arena["h"], Q, lc.R)
+        pl.set_limit_filter(lim, lc.CHECK_DT)
+        pl.set_clearance_filter(0.25, lc.CHECK_DT)
+        pl.set_penalty_filter(caps)
+        return pl
+
+    def rows(pl):
+        terms, rej = pl.last_cost_terms(n)
+        return dict(limits=pl.last_limits(n), clearance=pl.last_clearance(n), terms=dict(terms=terms, rejected=rej))
+
+    pl, fresh = planner(), planner()
+    whole = pl.plan(S, E, pp=_pp(hiplib))
+    assert (pl.last_limits(Q)["feasible"][n:] != 0).any() and np.isfinite(pl.last_clearance(Q)["clearance"][n:]).any()   # rows behind n were written
+    second, alone = pl.plan(S[:n], E[:n], pp=_pp(hiplib)), fresh.plan(S[:n], E[:n], pp=_pp(hiplib))
+    _same_outputs(second, alone)
+    for k in whole:
+        assert np.array_equal(second[k], whole[k][:n], equal_nan=True), k
+    got, ref = rows(pl), rows(fresh)
+    for name in ref:
+        assert set(got[name]) == set(ref[name])
+        for k in ref[name]:
+            assert np.array_equal(got[name][k], ref[name][k], equal_nan=True), (name, k)
+    assert np.isin(second["plan_status"], (hiplib.PLAN_OK, hiplib.PLAN_NO_VALID_RESTART)).any()
+    fresh.close()
+    # the latest call ran without a filter: its rows are not there to read, whatever an earlier call left
+    reads = dict(limits=lambda: pl.last_limits(n), terms=lambda: pl.last_cost_terms(n), clearance=lambda: pl.last_clearance(n))
+    for off, name in ((lambda: pl.set_limit_filter(None), "limits"), (lambda: pl.set_penalty_filter(None), "terms"),
+                      (lambda: pl.set_clearance_filter(None), "clearance")):
+        off()
+        pl.plan(S[:n], E[:n], pp=_pp(hiplib))
+        with pytest.raises(hiplib.DftpavError) as e:
+            reads[name]()
+        assert e.value.code == hiplib.E_INVALID, name
+    pl.close()
+
+
 def test_refusals_leave_outputs_untouched(hiplib, oracle):
     h = hiplib.Handle()
     bt = hiplib.Batch(h, LayoutSpec([4], [1], 4), 2)

@@ -357,6 +357,42 @@ def test_permuted_queries_with_one_restart_permute_bit_for_bit(hiplib, scene):
     h.close()
 
 
+def test_a_restart_below_mini_T_refuses_the_query(hiplib, scene):
+    """dur_lo = dur_hi = 1e-3 with two restarts: restart 0 keeps its durations, restart 1 of every solved query falls below mini_T
+    (plan.hip: mini_t_flag) -- the query is reported without a plan, its compact outputs zero, its restart 0 as in a plain call;
+    the queries that never reach a solve, and a plain call afterwards, are untouched by it"""
+    grid, res, org, S, E = scene
+    h = hiplib.Handle()
+    h.set_grid_map(grid, res, org)
+    pl = hiplib.Planner(h, len(E), 2)
+    plain = pl.plan(S, E, pp=_pp(hiplib))
+    short = _pp(hiplib)
+    short.dur_lo = short.dur_hi = 1e-3
+    out = pl.plan(S, E, pp=short)
+    solved = np.isin(plain["plan_status"], (hiplib.PLAN_OK, hiplib.PLAN_NO_VALID_RESTART))
+    print("solved by the plain call:", np.flatnonzero(solved).tolist(), "status", plain["plan_status"].tolist(), "->", out["plan_status"].tolist())
+    assert solved.sum() >= 3 and (~solved).sum() >= 2 and (plain["plan_status"] == hiplib.PLAN_OK).sum() >= 3
+    # the bound of the scene: a segment shorter than 100 s times 1e-3 is below the default mini_T
+    assert h.params.mini_T == 0.1
+    seg = out["piece_dt"] * out["piece_nums"]
+    for q in np.flatnonzero(solved):
+        M = int(out["n_seg"][q])
+        assert M >= 1 and (seg[q, :M] > 0.0).all() and (seg[q, :M] < 100.0).all(), (q, seg[q, :M])
+    for q in np.flatnonzero(solved):
+        assert out["plan_status"][q] == hiplib.PLAN_NO_VALID_RESTART and out["winner"][q] == -1, q
+        assert out["final_cost"][q] == 0.0 and out["iters"][q] == 0, q
+        assert not out["x"][q].any() and not out["coeffs"][q].any() and not out["coeff_dt"][q].any(), q
+        for k in PER_RESTART:
+            assert np.array_equal(out[k][q, 0], plain[k][q, 0], equal_nan=True), (q, k)
+    for k in plain:
+        assert np.array_equal(out[k][~solved], plain[k][~solved], equal_nan=True), k
+    again = pl.plan(S, E, pp=_pp(hiplib))
+    for k in plain:
+        assert np.array_equal(again[k], plain[k], equal_nan=True), k
+    pl.close()
+    h.close()
+
+
 def test_errors_leave_the_planner_usable(hiplib, scene):
     grid, res, org, S, E = scene
     h = hiplib.Handle()
