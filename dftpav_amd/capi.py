@@ -22,6 +22,7 @@ ORDER_DEVICE, ORDER_REFERENCE = 0, 1
 E_INVALID, E_MINI_T, E_ONE_PIECE, E_NO_DEVICE, E_HIP, E_UNSUPPORTED, E_COMM = -1, -2, -3, -4, -5, -6, -7
 PUBLISH_CHUNK, PUBLISH_MAX_TICKS = 256, 4096   # DFTPAV_PUBLISH_CHUNK, DFTPAV_PUBLISH_MAX_TICKS
 CONFLICT_MAX_SAMPLES = 4096   # DFTPAV_CONFLICT_MAX_SAMPLES
+RENDER_MAX_VERTS = 64   # DFTPAV_RENDER_MAX_VERTS
 # plan_status of dftpav_plan_queries (DFTPAV_PLAN_*); search status (DFTPAV_SEARCH_*)
 PLAN_OK, PLAN_NO_PATH, PLAN_TOO_MANY_SEGMENTS, PLAN_LAYOUT_UNSUPPORTED, PLAN_NO_VALID_RESTART, PLAN_ARRIVED = 0, 1, 2, 3, 4, 5
 SEARCH_REACH_END, SEARCH_NO_PATH = 2, 3
@@ -61,6 +62,7 @@ EXPORTS = [
     "dftpav_default_rs_heuristic_params", "dftpav_set_search_rs_heuristic", "dftpav_rs_table", "dftpav_rs_table_last_ms",
     "dftpav_planner_check_conflicts", "dftpav_planner_sample_poses", "dftpav_conflicts_last_ms",
     "dftpav_grid_stamp_poses", "dftpav_planner_stamp_slots", "dftpav_grid_clear_stamps", "dftpav_grid_read_cells", "dftpav_stamp_last_ms",
+    "dftpav_grid_render", "dftpav_grid_origin_centred", "dftpav_render_last_ms",
 ]
 
 
@@ -561,6 +563,26 @@ class Handle:
         fn.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         self._check(fn(self._h, C.byref(a), C.byref(b)), "stamp_last_ms")
         return float(a.value), float(b.value)
+
+    # ---- the rendered map: the grid map made on the device from an obstacle set
+    def render_map(self, size_x, size_y, resolution, origin, background=127, poly_xy=None, poly_off=None, circles=None, points=None):
+        """dftpav_grid_render: the map of size_x x size_y cells at `origin`, wiped to `background`, with the polygons (poly_xy [n][2],
+        poly_off [n_poly + 1]), circles [n][3] = cx, cy, radius and points [n][2] of the obstacle set as cells of 80, becomes the
+        handle's map as set_grid_map would install it"""
+        obs = obstacle_set(poly_xy, poly_off, circles, points)
+        fn = lib().dftpav_grid_render
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_ubyte, C.c_void_p]
+        self._check(fn(self._h, int(size_x), int(size_y), float(resolution), float(origin[0]), float(origin[1]), int(background),
+                       C.byref(obs)), "grid_render")
+        self._map_shape = (int(size_y), int(size_x))
+
+    def render_last_ms(self):
+        """dftpav_render_last_ms: device ms of the kernels of the last render_map"""
+        a = C.c_float(0.0)
+        fn = lib().dftpav_render_last_ms
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        self._check(fn(self._h, C.byref(a)), "render_last_ms")
+        return float(a.value)
 
     def goal_field(self, goals_xy, inflate_radius=0.0, fetch=True):
         """dftpav_grid_goal_field: for goals [n][2] (x, y) on the installed map, (field int32 [n][size_y][size_x], n_reached [n]): the
@@ -1078,6 +1100,46 @@ def debug_validation_table(params, check_dt, vertex_res, max_spacings=0):
     if rc != OK:
         return rc, None, None
     return rc, out[:n_t.value].copy(), out[n_t.value:n_t.value + n_v.value].copy()
+
+
+class ObstacleSet(C.Structure):
+    """dftpav_obstacle_set (include/dftpav_hip.h)."""
+    _fields_ = [("n_poly", C.c_int), ("poly_off", C.c_void_p), ("poly_xy", C.c_void_p), ("n_circle", C.c_int), ("circles", C.c_void_p),
+                ("n_point", C.c_int), ("points", C.c_void_p)]
+
+
+def obstacle_set(poly_xy=None, poly_off=None, circles=None, points=None):
+    """a dftpav_obstacle_set over contiguous copies of the arrays (kept alive by the structure); None: none of that kind"""
+    o = ObstacleSet()
+    keep = []
+
+    def arr(a, dtype, cols):
+        if a is None:
+            return None, 0
+        a = np.ascontiguousarray(a, dtype=dtype)
+        a = a.reshape(-1, cols) if cols else a.reshape(-1)
+        keep.append(a)
+        return a.ctypes.data_as(C.c_void_p), a.shape[0]
+
+    o.poly_xy, _ = arr(poly_xy, np.float64, 2)
+    o.poly_off, n_off = arr(poly_off, np.int32, 0)
+    o.n_poly = max(n_off - 1, 0)
+    o.circles, o.n_circle = arr(circles, np.float64, 3)
+    o.points, o.n_point = arr(points, np.float64, 2)
+    o._keep = keep
+    return o
+
+
+def origin_centred(ego_x, ego_y, extent_x, extent_y):
+    """dftpav_grid_origin_centred (host only): the origin (x, y) of a grid of that extent in metres centred on the ego vehicle,
+    round(ego - extent / 2) as DataRenderer::GetObstacleMap aligns it"""
+    out = (C.c_double * 2)()
+    fn = lib().dftpav_grid_origin_centred
+    fn.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]
+    rc = fn(float(ego_x), float(ego_y), float(extent_x), float(extent_y), out)
+    if rc != OK:
+        raise DftpavError(rc, "grid_origin_centred")
+    return float(out[0]), float(out[1])
 
 
 class GridMap(C.Structure):

@@ -260,6 +260,7 @@ extern "C" void dftpav_destroy(dftpav_handle *h) {
   if (h->d_rs) (void)hipFree(h->d_rs);
   if (h->d_cells_base) (void)hipFree(h->d_cells_base);
   if (h->d_stamp_ws) (void)hipFree(h->d_stamp_ws);
+  if (h->d_render_ws) (void)hipFree(h->d_render_ws);
   if (h->stamp_sel_ev) (void)hipEventDestroy(h->stamp_sel_ev);
   const hipStream_t stream = h->stream;
   delete h; // every EventMarks of the handle releases its events here: in front of their stream

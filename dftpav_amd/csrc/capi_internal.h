@@ -34,6 +34,7 @@
 #include "clearance_args.h"
 #include "conflict_args.h"
 #include "stamp_args.h"
+#include "render_args.h"
 #include "goalfield_args.h"
 
 namespace dftpav {
@@ -78,6 +79,8 @@ hipError_t launch_stamp_boxes(const StampBoxArgs &A, hipStream_t stream);
 hipError_t launch_stamp_bits(const StampBitsArgs &A, hipStream_t stream);
 hipError_t launch_stamp_count(const StampCountArgs &A, hipStream_t stream);
 int stamp_count_blocks(size_t n_cells); // the partial counts launch_stamp_count writes
+// render.hip: the background, then the polygons (interior, outline), circles and points of an obstacle set into the map
+hipError_t launch_render(const RenderArgs &A, hipStream_t stream);
 // goalfield.hip: the cost-to-go fields of n goal cells, one workgroup each
 hipError_t launch_goal_fields(const GoalFieldArgs &A, int n, hipStream_t stream);
 // rstable.hip: every entry of the Reeds-Shepp cost-to-go table
@@ -173,6 +176,10 @@ struct dftpav_handle {
   hipEvent_t stamp_sel_ev = nullptr;     // next call waits for it before it writes the vector again
   EventMarks<3> stamp_ev; // of the last stamp call: in front of the pose kernel, between it and the box kernel, behind the box kernel
   bool stamp_posed = false; // that call ran the pose kernel (dftpav_planner_stamp_slots); dftpav_grid_stamp_poses records marks 1 and 2
+  // the rendered map (render.hip): nothing of it exists until a dftpav_grid_render
+  unsigned char *d_render_ws = nullptr; // the snapped obstacle set of one call: poly_off | boxes | edges | circles | points; kept from
+  size_t render_ws_bytes = 0;           // call to call (every call ends with a wait, so the next finds it idle)
+  EventMarks<2> render_ev;              // in front of the background kernel, behind the last kernel of the last render
   // the search heuristic (dftpav_set_search_heuristic) and the workspace of the goal fields (goalfield.hip): nothing of it is
   // allocated or launched until a call asks for a field
   dftpav_goal_field_params heu{0, 0.0, 0.0};

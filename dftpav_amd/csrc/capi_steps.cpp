@@ -369,6 +369,22 @@ void dftpav::wire_search(SearchSetup &U, double *d_tabs, double *d_start, double
   O.paths = d_paths;
 }
 
+// the maps that get the corridor's bit map: <= 40 KB of bits per workgroup, four workgroups per CU
+static constexpr size_t kBitMapMaxCells = (size_t)8 * 40 * 1024;
+
+// the table of a map's resolution on the device (h->d_dl is null): the sample offsets of CheckIfCollisionUsingLine
+// (map_adapter.cpp:119): dl = 0, then dl += checkl; the longest segment is the far edge of a fully grown rectangle
+static int map_line_table(dftpav_handle *h, double resolution) {
+  const double checkl = resolution / 2.0;
+  const double longest = std::max(h->params.veh_length, h->params.veh_width) + 2.0 * (10.0 + resolution) + 1.0;
+  std::vector<double> dl;
+  for (double v = 0.0; v < longest; v += checkl) dl.push_back(v);
+  h->n_dl = (int)dl.size();
+  HIPCHK(h, hipMalloc(&h->d_dl, sizeof(double) * dl.size()));
+  HIPCHK(h, hipMemcpy(h->d_dl, dl.data(), sizeof(double) * dl.size(), hipMemcpyHostToDevice));
+  return DFTPAV_OK;
+}
+
 extern "C" int dftpav_set_grid_map(dftpav_handle *h, const dftpav_grid_map *map) {
   if (!h || !map || !map->cells || map->size_x <= 0 || map->size_y <= 0 || !(map->resolution > 0.0)) return DFTPAV_E_INVALID;
   HIPCHK(h, hipSetDevice(h->device));
@@ -387,23 +403,14 @@ extern "C" int dftpav_set_grid_map(dftpav_handle *h, const dftpav_grid_map *map)
   h->map = *map;
   h->map.cells = nullptr;
   h->dist_stale = true; // the distance field, if a clearance call ever asks for one, is built again by that call
-  if (ncell <= (size_t)8 * 40 * 1024) { // <= 40 KB of bits per workgroup: four workgroups per CU
+  if (ncell <= kBitMapMaxCells) {
     std::vector<unsigned> bits((ncell + 31) / 32, 0u);
     for (size_t i = 0; i < ncell; i++)
       if (map->cells[i] == 80) bits[i >> 5] |= 1u << (i & 31);
     HIPCHK(h, hipMalloc(&h->d_bits, sizeof(unsigned) * bits.size()));
     HIPCHK(h, hipMemcpy(h->d_bits, bits.data(), sizeof(unsigned) * bits.size(), hipMemcpyHostToDevice));
   }
-  // sample offsets of CheckIfCollisionUsingLine (map_adapter.cpp:119): dl = 0, then dl += checkl; the longest
-  // segment is the far edge of a fully grown rectangle
-  const double checkl = map->resolution / 2.0;
-  const double longest = std::max(h->params.veh_length, h->params.veh_width) + 2.0 * (10.0 + map->resolution) + 1.0;
-  std::vector<double> dl;
-  for (double v = 0.0; v < longest; v += checkl) dl.push_back(v);
-  h->n_dl = (int)dl.size();
-  HIPCHK(h, hipMalloc(&h->d_dl, sizeof(double) * dl.size()));
-  HIPCHK(h, hipMemcpy(h->d_dl, dl.data(), sizeof(double) * dl.size(), hipMemcpyHostToDevice));
-  return DFTPAV_OK;
+  return map_line_table(h, map->resolution);
 }
 
 // uploads the states and runs the corridor kernel into `hpoly` (device, [n][16]) or into a batch's corridor
@@ -850,6 +857,145 @@ extern "C" int dftpav_stamp_last_ms(dftpav_handle *h, float *pose_ms, float *sta
   HIPCHK(h, hipSetDevice(h->device));
   if (pose_ms && h->stamp_posed) HIPCHK(h, h->stamp_ev.elapsed(pose_ms, 0, 1, true)); // (a stamp waits for nothing)
   if (stamp_ms) HIPCHK(h, h->stamp_ev.elapsed(stamp_ms, 1, 2, true));
+  return DFTPAV_OK;
+}
+
+// ------------------------------------------------- the map rendered from the arena's obstacle set (render.hip)
+extern "C" int dftpav_grid_origin_centred(double ego_x, double ego_y, double extent_x, double extent_y, double out[2]) {
+  if (!out || !std::isfinite(ego_x) || !std::isfinite(ego_y) || !std::isfinite(extent_x) || !std::isfinite(extent_y)) return DFTPAV_E_INVALID;
+  out[0] = std::round(ego_x - extent_x / 2.0); // data_renderer.cc:156-160
+  out[1] = std::round(ego_y - extent_y / 2.0);
+  return DFTPAV_OK;
+}
+
+// the cell coordinate of a world coordinate: rint((p - origin) / resolution), halves to even; false beyond +-2^30 and for a NaN
+static bool render_snap(double p, double origin, double resolution, int &out) {
+  const double c = std::nearbyint((p - origin) / resolution);
+  if (!(std::fabs(c) <= 1073741824.0)) return false;
+  out = (int)c;
+  return true;
+}
+
+extern "C" int dftpav_grid_render(dftpav_handle *h, int size_x, int size_y, double resolution, double origin_x, double origin_y,
+                                  unsigned char background, const dftpav_obstacle_set *obs) {
+  if (!h || size_x <= 0 || size_y <= 0 || !(resolution > 0.0) || !std::isfinite(resolution) || !std::isfinite(origin_x) ||
+      !std::isfinite(origin_y))
+    return DFTPAV_E_INVALID;
+  static const dftpav_obstacle_set none{};
+  const dftpav_obstacle_set &O = obs ? *obs : none;
+  if (O.n_poly < 0 || O.n_circle < 0 || O.n_point < 0) return DFTPAV_E_INVALID;
+  if ((O.n_poly > 0 && !O.poly_off) || (O.n_circle > 0 && !O.circles) || (O.n_point > 0 && !O.points)) return DFTPAV_E_INVALID;
+  // everything is checked and snapped before the handle changes: poly_off | boxes | edges | circles | points, as the kernels read them
+  int n_vert = 0;
+  if (O.n_poly > 0) {
+    if (O.poly_off[0] != 0) return DFTPAV_E_INVALID;
+    for (int p = 0; p < O.n_poly; p++) {
+      const long long nv = (long long)O.poly_off[p + 1] - O.poly_off[p];
+      if (nv < 0 || nv > DFTPAV_RENDER_MAX_VERTS) return DFTPAV_E_INVALID;
+    }
+    n_vert = O.poly_off[O.n_poly];
+    if (n_vert > 0 && !O.poly_xy) return DFTPAV_E_INVALID;
+  }
+  std::vector<int> snapped((size_t)n_vert * 2);
+  for (size_t i = 0; i < snapped.size(); i++) {
+    if (!std::isfinite(O.poly_xy[i])) return DFTPAV_E_INVALID;
+    if (!render_snap(O.poly_xy[i], i & 1 ? origin_y : origin_x, resolution, snapped[i])) return DFTPAV_E_INVALID;
+  }
+  std::vector<int4> boxes((size_t)O.n_poly), edges((size_t)n_vert), circles((size_t)O.n_circle);
+  std::vector<int2> points((size_t)O.n_point);
+  long long poly_rows = 0, circle_rows = 0; // the most rows of the grid that one polygon / circle spans
+  const auto rows_inside = [&](long long lo, long long hi) { return std::min<long long>(hi, size_y - 1) - std::max<long long>(lo, 0) + 1; };
+  for (int p = 0; p < O.n_poly; p++) {
+    const int first = O.poly_off[p], nv = O.poly_off[p + 1] - first;
+    int4 box = make_int4(INT_MAX, INT_MIN, INT_MAX, INT_MIN);
+    for (int v = 0; v < nv; v++) {
+      const int *a = &snapped[2 * (size_t)(first + v)], *b = &snapped[2 * (size_t)(first + (v + 1) % nv)];
+      edges[(size_t)first + v] = make_int4(a[0], a[1], b[0], b[1]);
+      box = make_int4(std::min(box.x, a[0]), std::max(box.y, a[0]), std::min(box.z, a[1]), std::max(box.w, a[1]));
+    }
+    boxes[p] = box;
+    if (nv > 0) poly_rows = std::max(poly_rows, rows_inside(box.z, box.w));
+  }
+  for (int c = 0; c < O.n_circle; c++) {
+    const double *q = O.circles + 3 * (size_t)c;
+    int cx = 0, cy = 0;
+    if (!std::isfinite(q[0]) || !std::isfinite(q[1]) || !std::isfinite(q[2]) || q[2] < 0.0) return DFTPAV_E_INVALID;
+    if (!render_snap(q[0], origin_x, resolution, cx) || !render_snap(q[1], origin_y, resolution, cy)) return DFTPAV_E_INVALID;
+    const double r = q[2] / resolution; // data_renderer.cc:178: truncated
+    if (!(r <= 1073741824.0)) return DFTPAV_E_INVALID;
+    circles[c] = make_int4(cx, cy, (int)r, 0);
+    circle_rows = std::max(circle_rows, rows_inside((long long)cy - (int)r, (long long)cy + (int)r));
+  }
+  for (int i = 0; i < O.n_point; i++) {
+    const double *q = O.points + 2 * (size_t)i;
+    if (!std::isfinite(q[0]) || !std::isfinite(q[1])) return DFTPAV_E_INVALID;
+    if (!render_snap(q[0], origin_x, resolution, points[i].x) || !render_snap(q[1], origin_y, resolution, points[i].y)) return DFTPAV_E_INVALID;
+  }
+  const auto chunks = [](long long rows) { return (int)std::min<long long>(kRenderMaxChunks, std::max<long long>(1, (rows + 3) / 4)); };
+
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream)); // as dftpav_set_grid_map: what was enqueued read the map that goes
+  RenderArgs A{};
+  const auto fields = [&](auto take) {
+    A.poly_off = (const int *)take(sizeof(int) * ((size_t)O.n_poly + 1));
+    A.poly_box = (const int4 *)take(sizeof(int4) * boxes.size());
+    A.edges = (const int4 *)take(sizeof(int4) * edges.size());
+    A.circles = (const int4 *)take(sizeof(int4) * circles.size());
+    A.points = (const int2 *)take(sizeof(int2) * points.size());
+  };
+  const size_t ws = carve(nullptr, fields);
+  if (int rc = grow(h, h->d_render_ws, h->render_ws_bytes, ws)) return rc;
+  carve(h->d_render_ws, fields);
+  const size_t ncell = (size_t)size_x * (size_t)size_y;
+  if (!h->d_cells || (size_t)h->map.size_x * (size_t)h->map.size_y != ncell) { // a map of the same size keeps its allocations
+    if (h->d_cells) (void)hipFree(h->d_cells);
+    if (h->d_bits) (void)hipFree(h->d_bits);
+    h->d_cells = nullptr;
+    h->d_bits = nullptr;
+    HIPCHK(h, hipMalloc(&h->d_cells, ncell));
+    if (ncell <= kBitMapMaxCells) HIPCHK(h, hipMalloc(&h->d_bits, sizeof(unsigned) * ((ncell + 31) / 32)));
+  }
+  if (h->d_cells_base) (void)hipFree(h->d_cells_base); // a new map has no stamps
+  h->d_cells_base = nullptr;
+  if (!h->d_dl || h->map.resolution != resolution) {
+    if (h->d_dl) (void)hipFree(h->d_dl);
+    h->d_dl = nullptr;
+    if (int rc = map_line_table(h, resolution)) return rc;
+  }
+  h->map = dftpav_grid_map{nullptr, size_x, size_y, resolution, origin_x, origin_y};
+  h->dist_stale = true;
+  A.cells = h->d_cells;
+  A.size_x = size_x;
+  A.size_y = size_y;
+  A.background = background;
+  A.n_poly = O.n_poly;
+  A.n_vert = n_vert;
+  A.poly_chunks = chunks(poly_rows);
+  A.n_circle = O.n_circle;
+  A.circle_chunks = chunks(circle_rows);
+  A.n_point = O.n_point;
+  const auto upload = [&](const void *dst, const void *src, size_t bytes) {
+    return bytes ? hipMemcpyAsync((void *)dst, src, bytes, hipMemcpyHostToDevice, h->stream) : hipSuccess;
+  };
+  h->render_ev.reset(); // until the whole chain has run
+  HIPCHK(h, upload(A.poly_off, O.poly_off, sizeof(int) * (O.n_poly > 0 ? (size_t)O.n_poly + 1 : 0)));
+  HIPCHK(h, upload(A.poly_box, boxes.data(), sizeof(int4) * boxes.size()));
+  HIPCHK(h, upload(A.edges, edges.data(), sizeof(int4) * edges.size()));
+  HIPCHK(h, upload(A.circles, circles.data(), sizeof(int4) * circles.size()));
+  HIPCHK(h, upload(A.points, points.data(), sizeof(int2) * points.size()));
+  HIPCHK(h, h->render_ev.record(0, h->stream));
+  HIPCHK(h, launch_render(A, h->stream));
+  if (h->d_bits) HIPCHK(h, launch_stamp_bits(StampBitsArgs{h->d_cells, h->d_bits, ncell}, h->stream));
+  HIPCHK(h, h->render_ev.record(1, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream)); // the sources of the copies are this call's
+  h->render_ev.complete();
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_render_last_ms(dftpav_handle *h, float *ms) {
+  if (!h || !ms || !h->render_ev.reached()) return DFTPAV_E_INVALID;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, h->render_ev.elapsed(ms, 0, 1, false));
   return DFTPAV_OK;
 }
 

@@ -1252,6 +1252,70 @@ int dftpav_grid_clear_stamps(dftpav_handle *h);
 int dftpav_grid_read_cells(dftpav_handle *h, unsigned char *cells /*[size_y][size_x] or NULL*/, int *n_stamped /*or NULL*/);
 int dftpav_stamp_last_ms(dftpav_handle *h, float *pose_ms, float *stamp_ms);
 
+/* ---- the rendered map: the grid map made on the device from the arena's obstacle set -----------------------------------
+ * The reference's world model makes the grid again every cycle (DataRenderer::GetObstacleMap and FakeMapper,
+ * data_renderer.cc:146-259): the origin follows the ego vehicle, the grid is wiped to a background byte, the obstacle circles and
+ * polygons of /arena_info_static are filled in, the remembered obstacle points are set.  dftpav_grid_render does the same from a few
+ * kilobytes of vertices, so that a cycle is "render, stamp, plan, clear" and no map crosses the bus.  Off until called: a handle
+ * that never renders launches, allocates and computes what it did without this section (render.hip).
+ *
+ * The definition.  A grid (size_x, size_y, resolution, origin_x, origin_y), a background byte and an obstacle set.  Every cell
+ * starts as `background`; a covered cell becomes 80; every writer writes 80, so order and overlap do not show.  All arithmetic is
+ * fp64 without contraction.
+ *   Snapping: a world coordinate p becomes the cell coordinate rint((p - origin) / resolution), halves to even (numpy's rint).
+ *   Polygon p has the vertices poly_xy[poly_off[p] .. poly_off[p + 1]), snapped to integers (X_v, Y_v); edge e runs from vertex e
+ *   to vertex e + 1, cyclic.  A polygon whose snapped bounding box misses the grid covers nothing.
+ *     interior, for each row y in [max(minY, 0), min(maxY, size_y - 1)]:
+ *       edge e crosses row y iff (Y0 <= y && Y1 > y) || (Y1 <= y && Y0 > y)
+ *       its abscissa is t = (double)(y - Y0) / (double)(Y1 - Y0), x = (double)X0 + t * (double)(X1 - X0)
+ *       the abscissae of the row are sorted ascending (equal values are interchangeable); each pair (a, b) at the positions
+ *       (2k, 2k + 1) covers ix in [max(ceil(a), 0), min(floor(b), size_x - 1)]
+ *     outline, for each edge: n = max(|X1 - X0|, |Y1 - Y0|) + 1 steps; step k is the cell
+ *       (rint((double)k * sx + (double)X0), rint((double)k * sy + (double)Y0)) with sx = (double)(X1 - X0) / (double)(n - 1) and
+ *       sy likewise; the last step is exactly (X1, Y1); n == 1 is the single cell (X0, Y0); steps outside the grid are dropped
+ *     A polygon of 0, 1 or 2 vertices is legal: the rule gives it no interior beyond its outline (0 vertices: nothing).
+ *   Circle (cx, cy, radius): the centre snapped as above, r = (int)(radius / resolution), truncated (data_renderer.cc:178); the
+ *   cells with integer dx * dx + dy * dy <= r * r round the centre, clipped to the grid.
+ *   Point (x, y): its snapped cell becomes 80 if it lies inside the grid (SetValueUsingGlobalPosition, data_renderer.cc:253).
+ * The polygon rule is, operation by operation, the one that made this project's default arena map (tests/golden/default_map.npz).
+ *
+ * State.  After dftpav_grid_render the handle is as dftpav_set_grid_map leaves it, given the rendered bytes: the rendered map is
+ * the working map and the base of later stamps; stamps and the base copy of the map before are dropped; the distance field is
+ * stale; the table of line sample offsets is that of `resolution`; maps of up to 327 680 cells have the corridor's bit map, made
+ * from the bytes on the device.  A map of as many cells as the one before keeps its device allocations.
+ *
+ * dftpav_grid_render: all work goes on the handle's stream; the call waits for that stream before it changes the map (as
+ *   dftpav_set_grid_map does) and ENDS WITH A WAIT for it: the obstacle set comes from the caller's memory.  obs NULL is the empty
+ *   set, which renders the background alone.
+ * dftpav_grid_origin_centred: host only.  out = (round(ego_x - extent_x / 2), round(ego_y - extent_y / 2)), C's round
+ *   (data_renderer.cc:156-160): the origin that follows the ego vehicle, extent = cells * resolution.
+ * dftpav_render_last_ms: device time in ms (the handle's HIP events) of the kernels of the last render, the bit map's included,
+ *   without the copies of the obstacle set.
+ * DFTPAV_E_INVALID, and nothing changed: h NULL; a count < 0; a count > 0 with its array NULL; size_x or size_y <= 0; resolution
+ * not > 0 or not finite; origin, a coordinate or a radius not finite; radius < 0; a snapped coordinate, or a radius in cells, beyond
+ * +-2^30; poly_off not non-decreasing from 0; a polygon of more than DFTPAV_RENDER_MAX_VERTS vertices (a wave holds an edge per
+ * lane); dftpav_grid_origin_centred with out NULL or an argument not finite; dftpav_render_last_ms before any render.
+ *
+ * Not claimed.  OpenCV's choice of outline and rim cells: a cell on the outline of a polygon or on the rim of a disc may differ
+ * from cv::fillPoly's / cv::circle's by one cell (OpenCV is not part of this project; the rules above are its documented ones).
+ * The FOV ray casting of RayCastingOnObstacleMap (data_renderer.cc:264-): it marks scanned cells and remembers points, and adds
+ * nothing to the cells equal to 80 that the planner reads; pass the remembered points as `points`.  Obstacles are not drawn into
+ * an existing map: a render makes the whole map (boxes into an existing map: the stamps above). */
+#define DFTPAV_RENDER_MAX_VERTS 64
+typedef struct dftpav_obstacle_set {
+  int n_poly;
+  const int *poly_off;    /* [n_poly + 1], from 0, non-decreasing */
+  const double *poly_xy;  /* [poly_off[n_poly]][2] world x, y */
+  int n_circle;
+  const double *circles;  /* [n_circle][3] cx, cy, radius */
+  int n_point;
+  const double *points;   /* [n_point][2] x, y */
+} dftpav_obstacle_set;
+int dftpav_grid_render(dftpav_handle *h, int size_x, int size_y, double resolution, double origin_x, double origin_y,
+                       unsigned char background, const dftpav_obstacle_set *obs);
+int dftpav_grid_origin_centred(double ego_x, double ego_y, double extent_x, double extent_y, double out[2]);
+int dftpav_render_last_ms(dftpav_handle *h, float *ms);
+
 /* One-shot convenience == OptimizeTrajectory for B trajectories. */
 int dftpav_solve_batch(dftpav_handle *h, const dftpav_layout *layout, int B,
                        const dftpav_batch_data *d, double *x, double *final_cost,
