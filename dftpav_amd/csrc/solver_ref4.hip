@@ -19,8 +19,11 @@
 //     says about it.  No 16-double records, no chain pass.  Only what the term adds to the segment's gdT and to the two costs
 //     (three doubles) is parked -- in one pool per trajectory, in arrival order -- and chained afterwards in (piece, point, term)
 //     order through a permutation of the pool's slots (q4_eval: the chain pass).  The active terms themselves are
-//     EVALUATED densely packed: listed by the lanes that find them, taken 24 at a time one per lane, their results handed back to
-//     the owners through LDS in list order (quad_common.h: DenseLds; q4_eval: flush);
+//     EVALUATED densely packed: listed by the lanes that find them, taken up to kDense = 64 at a time one per lane (a whole wave in one
+//     pass: the list is as long as the LDS left beside four workgroups' rows and tables allows, quad_common.h), their results handed
+//     back to the owners through LDS in list order (quad_common.h: DenseLds; q4_eval: flush).  An entry's half-plane and its result
+//     share their LDS: 132 bytes per entry.  With 24 entries of 164 bytes the list was emptied 3.9 times per evaluation of the bench's
+//     batch at some 7 k cycles each (profiles/dense_list_phases.txt);
 //   * the corridor is read from a copy laid out [component][j][piece]: the 16 lanes of a row read 128 contiguous bytes; a batch whose
 //     corridors are all rectangles (q4_rect_check_kernel) reads a copy of 10 doubles per point instead of 16 (RECT, below);
 //   * lbfgs_optimize / line_search_lewisoverton (lbfgs.hpp:276-390, 440-751): solver_ref.hip's lbfgs_advance, per row; a vector of
@@ -35,7 +38,7 @@
 // Residency: ONE wave per SIMD (the kernel takes 460 registers; built for two waves per SIMD it spilled 205 of them and its scratch
 // traffic alone was HBM-sized), four waves = 16 trajectories per CU (8 in the WAVE shape), each wave at the speed of a wave that has
 // its SIMD to itself; 4.6 KB of LDS per trajectory (x, g, the boundary states, the scalars of the line search, alpha[mem], a pool
-// of 64 parked terms and its permutation) and 3.9 KB per wave for the list of active terms, workgroups of one wave with a copy of the sweep
+// of 64 parked terms and its permutation) and 8.3 KB per wave for the list of active terms (38.7 of the 40 KB a workgroup may take at 16 pieces and a history of 256), workgroups of one wave with a copy of the sweep
 // tables each (39 KB; a wave that has nothing
 // left to do frees its slot at once).  Scheduling as the WAVE shape: the rows pop trajectories from the batch's ring, run them a
 // slice of evaluations and push them back unfinished, so that a wave's rows stay filled until the batch runs out.
@@ -51,8 +54,7 @@ namespace dftpav {
 namespace reford {
 
 // Parked terms of a trajectory kept in LDS, in one pool filled in arrival order (the rest in global scratch).  A slot's number is a
-// bit of a lane's 64-bit mask and a byte of the row's permutation table.
-constexpr int kQPool = 64;
+// bit of a lane's 64-bit mask and a byte of the row's permutation table.  (kQPool = 64: quad_common.h, with the sizes of the LDS)
 static_assert(kQPool <= 64 && kQPool % 8 == 0, "a lane's pool slots are the bits of a 64-bit mask; the chain pass reads the permutation eight bytes at a time");
 typedef unsigned char __attribute__((address_space(3))) *ldsb_t;
 typedef const unsigned long long __attribute__((address_space(3))) *ldscu64_t;
@@ -75,9 +77,7 @@ struct Q4 {
   ldsb_t perm;    // [kQPool] the pool slots in (piece, point, term) order, a byte each
   ldsi_t ist;     // [iNUM]
 };
-__host__ __device__ inline size_t q4_team_doubles(int mem) { return 32 + 32 + 12 + 6 + sNUM + (size_t)mem + kQPool * 3 + kQPool / 8; }
-__host__ __device__ inline size_t q4_team_bytes(int mem) { return (q4_team_doubles(mem) * sizeof(double) + iNUM * sizeof(int) + 15) & ~(size_t)15; }
-__host__ __device__ inline size_t q4_shared_bytes(int N) { return ((size_t)pk_segment_doubles(N) * sizeof(double) + 15) & ~(size_t)15; }
+// (q4_team_doubles / q4_team_bytes / q4_shared_bytes: quad_common.h -- the length of the list of active terms follows from them)
 __device__ inline void q4_carve(Q4 &q, char *team, int mem) {
   ldsd_t p = (ldsd_t)reinterpret_cast<double *>(team);
   q.xs = p; p += 32;
@@ -449,7 +449,7 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
   // the list of the wave
   const int lane64 = (int)(threadIdx.x & 63);
   int listed = 0;       // (uniform) entries in the list
-  unsigned mine = 0u;   // the list's slots that hold terms of this lane's piece
+  dmask_t mine = 0ull;  // the list's slots that hold terms of this lane's piece
   // (the rows of a wave that have no trajectory are not here: EXEC holds whole rows of 16 lanes, any of the four)
   const unsigned long long here = __builtin_amdgcn_ballot_w64(true);
   const int row_here[4] = {(int)(here & 1ull), (int)((here >> 16) & 1ull), (int)((here >> 32) & 1ull), (int)((here >> 48) & 1ull)};
@@ -471,7 +471,7 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
     return v + (my_row > 0 ? t0_ : 0) + (my_row > 1 ? t1_ : 0) + (my_row > 2 ? t2_ : 0);
   };
   auto flush = [&]() {
-    for (int first = 0; first < listed; first += n_here) { // (uniform; one pass unless a single row is here and the list is longer than 16)
+    for (int first = 0; first < listed; first += n_here) { // (uniform; a pass serves the n_here lanes that are here: one pass of a full wave, up to kDense / 16 where a single row is here)
     const int slot = first + rank;
     const bool work = slot < listed;
     const int id = dl.id[work ? slot : 0];
@@ -490,11 +490,12 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
       // the state of the owner's point by the expressions that found the term (its tests are not needed again: no half-planes)
       (void)point_masks<false>(P, cco, lo, N, jo, Ko, stepo, dl.s1[slot], singul_, epis, H, nopl, (gd_t) nullptr, D.sur, 0.0, 0.0, 0, 0.0, ps);
       double r_[16];
-      const ldscd_t pk = dl.pl + 4 * slot;
+      // the entry's half-plane lies where its result goes: read whole, here, in front of the writes below
+      ldsd_t w = dl.out + 15 * slot;
+      const double pk[4] = {w[0], w[1], w[2], w[3]};
       point_emit_pf(P, ps, t, H, t0, [&](int, double &on0, double &on1, double &q0, double &q1) { on0 = pk[0]; on1 = pk[1]; q0 = pk[2]; q1 = pk[3]; },
                     (double *)r_);
       const bool corr = t < t0;
-      ldsd_t w = dl.out + 15 * slot;
 #pragma unroll
       for (int u = 0; u < 13; u++) w[u] = r_[u];
       w[13] = corr ? r_[13] : -0.0;
@@ -504,24 +505,29 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     // the list's slots that hold terms of this lane's ROW (an OR around the row): list order is arrival order, so an entry's pool
     // slot is the row's count plus the row's entries in front of it
-    unsigned rowm = mine;
-    rowm |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)rowm, 0x121, 0xf, 0xf, false);
-    rowm |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)rowm, 0x122, 0xf, 0xf, false);
-    rowm |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)rowm, 0x124, 0xf, 0xf, false);
-    rowm |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)rowm, 0x128, 0xf, 0xf, false);
-    for (unsigned mm = mine; mm;) { // the owner adds its terms in list order: (point, term) order
-      const int i = __builtin_ctz(mm);
+    unsigned rlo = (unsigned)mine, rhi = (unsigned)(mine >> 32); // (the two halves of the 64 slots, a DPP each)
+    rlo |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)rlo, 0x121, 0xf, 0xf, false);
+    rhi |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)rhi, 0x121, 0xf, 0xf, false);
+    rlo |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)rlo, 0x122, 0xf, 0xf, false);
+    rhi |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)rhi, 0x122, 0xf, 0xf, false);
+    rlo |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)rlo, 0x124, 0xf, 0xf, false);
+    rhi |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)rhi, 0x124, 0xf, 0xf, false);
+    rlo |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)rlo, 0x128, 0xf, 0xf, false);
+    rhi |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)rhi, 0x128, 0xf, 0xf, false);
+    const dmask_t rowm = ((dmask_t)rhi << 32) | rlo;
+    for (dmask_t mm = mine; mm;) { // the owner adds its terms in list order: (point, term) order
+      const int i = __builtin_ctzll(mm);
       mm &= mm - 1;
       ldscd_t w = dl.out + 15 * i;
       double r12[12];
 #pragma unroll
       for (int u = 0; u < 12; u++) r12[u] = w[u];
-      take(r12, w[12], w[13], w[14], rcnt + __builtin_popcount(rowm & ((1u << i) - 1u)));
+      take(r12, w[12], w[13], w[14], rcnt + __builtin_popcountll(rowm & ((1ull << i) - 1ull)));
     }
-    rcnt += __builtin_popcount(rowm);
+    rcnt += __builtin_popcountll(rowm);
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); // the list is written again below
     listed = 0;
-    mine = 0u;
+    mine = 0ull;
   };
   // (one more round than the pieces have points -- it only empties the list: the emission's code exists once)
 #pragma unroll 1
@@ -544,8 +550,10 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
     [[maybe_unused]] long long emit_t0 = 0;
     if (D.prof != nullptr) { // (profiling only) trips of the loop below for the wave: the longest list of active terms among its 64 points;
       // DFTPAV_PROF_EMIT_CYCLES (a build flag): the cycles of that loop instead -- the clock behind it is read when the wave has reconverged
-#ifdef DFTPAV_PROF_EMIT_CYCLES
+      // DFTPAV_PROF_FLUSH_CYCLES (a build flag): the cycles of the list's flushes alone, read where the flush is called
+#if defined(DFTPAV_PROF_EMIT_CYCLES)
       emit_t0 = clock64();
+#elif defined(DFTPAV_PROF_FLUSH_CYCLES)
 #else
       const int pc = __builtin_popcount(m);
       int trips = 0;
@@ -569,7 +577,18 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
     int incl = 0, total = 0, row_incl = 0;
     if (any) incl = scan_here(c, total, row_incl);
     // the list is emptied when this round's terms do not fit behind what it holds, and by the extra round
-    if (listed > 0 && (extra || listed + total > kDense)) flush(); // (uniform)
+    if (listed > 0 && (extra || listed + total > kDense)) { // (uniform)
+#ifdef DFTPAV_PROF_FLUSH_CYCLES
+      const long long flush_t0 = D.prof != nullptr ? clock64() : 0;
+#endif
+      flush();
+      if (D.prof != nullptr) { // (profiling only) flushes of the wave: the upper half of slot 9; the clock is read when the wave has reconverged
+        pr.count(9, 1ll << 32);
+#ifdef DFTPAV_PROF_FLUSH_CYCLES
+        pr.count(11, clock64() - flush_t0);
+#endif
+      }
+    }
     if (any && total > kDense) { // (uniform, rare) more than a list's worth in one round: in place, behind the earlier points' terms
       in_place = true;
     } else if (any) {
@@ -585,13 +604,13 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
           for (int qv = 1; qv < 5; qv++) v += t >= qv * H ? 1 : 0;
           double on0, on1, q0, q1;
           plane_of(t - v * H, on0, on1, q0, q1);
-          ldsd_t w = dl.pl + 4 * e;
+          ldsd_t w = dl.out + 15 * e; // (where the term's result will go: the worker reads it first)
           w[0] = on0;
           w[1] = on1;
           w[2] = q0;
           w[3] = q1;
         }
-        mine |= 1u << e;
+        mine |= 1ull << e;
         e++;
       }
       listed += total;
@@ -1514,8 +1533,12 @@ bool reference_order_quad_supported(const DevLayout &L, const DevParams &P, int 
   if (L.M != 1 || S != 0 || L.n > 32 || L.Ntot > 16 || L.Ntot < 2 || L.H < 1 || L.H > 5) return false;
   // (the recursion reads blocks of kQB consecutive history rows at pitch kQNpad, the ring's ends from a mirror of 2 kQB rows)
   if (L.npad != reford::kQNpad || P.mem_size < reford::kQB) return false;
+  // (a workgroup of one wave must fit; the list's length kDense is what leaves room for FOUR of them at 16 pieces and a history of 256 --
+  // quad_common.h: q4_dense_capacity, the same sum, asserted there)
   return reford::q4_shared_bytes(L.Ntot) + 4 * reford::q4_team_bytes(P.mem_size) + reford::q4_dense_bytes() <= 160 * 1024;
 }
+// Test hook: kDense, the entries of a wave's list of active terms (tests/test_gpu_quad_dense_list.py builds its cases round it)
+extern "C" int dftpav_debug_quad_list_capacity(void) { return reford::kDense; }
 size_t reference_order_quad_corridor_doubles(const DevLayout &L, int B) { return (size_t)B * L.H * 4 * (L.Kmax + 1) * 16; }
 // the QUAD shape's LDS (a row: its part of a wave and a quarter of the wave's list of active terms), eight waves per CU at most
 // (256 registers); a batch alone on the device hands its last 768 trajectories to the WAVE shape

@@ -7,5 +7,5 @@ for B in (8, 4096):
     p = capi.default_params(); s = sc.baseline_config(3, B=B); s.apply_resolution(p)
     h = capi.Handle(p); bt = capi.Batch(h, s.layout, B); bt.upload(s); bt.set_order(capi.ORDER_REFERENCE)
     bt.solve_async(); bt.sync(); bt.profile(True); bt.solve_async(); bt.sync()
-    r = bt.results(); pr = bt.read_profile(); pr[:, 11] &= 0xffffffff; pr = pr.astype(np.float64)  # (slot 11's upper half: slow-path evaluations, solver_ref4.hip)
+    r = bt.results(); pr = bt.read_profile(); pr[:, 11] &= 0xffffffff; pr[:, 9] &= 0xffffffff; pr = pr.astype(np.float64)  # (slot 11's upper half: slow-path evaluations, slot 9's: flushes of the list, solver_ref4.hip)
     print("B", B, "emit-loop trips of the wave per evaluation (mean over rows):", (pr[:, 11] / r["evals"]).mean(), "active terms per eval", (pr[:, 9] / r["evals"]).mean())

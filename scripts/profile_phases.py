@@ -26,8 +26,14 @@ REF = os.environ.get("ORDER") == "ref"
 # the QUAD shape (solver_ref4.hip) counts in the upper half of slot 11 the evaluations whose parked-term chain took the slow path (a row
 # of the wave had more terms than its LDS pool holds); the lower half is the slot's own figure
 slow = (pri[:, 11] >> 32) if REF else np.zeros(len(pri), dtype=np.int64)
+# ... and in the upper half of slot 9 the flushes of its list of active terms (q4_eval: flush), each counted by the four rows of the wave.
+# SLOT11=flush / emit names what a library built with -DDFTPAV_PROF_FLUSH_CYCLES / -DDFTPAV_PROF_EMIT_CYCLES keeps in slot 11: the cycles of
+# the flushes / of the whole emission instead of the emit loop's trips
+flushes = (pri[:, 9] >> 32) if REF else np.zeros(len(pri), dtype=np.int64)
+SLOT11 = os.environ.get("SLOT11", "")
 if REF:
     pri[:, 11] &= 0xffffffff
+    pri[:, 9] &= 0xffffffff
 pr = pri.astype(np.float64)
 # the reference-order kernel keeps COUNTS in some slots (solver_ref.hip): slot 9 = active terms (both launch shapes); in the WAVE
 # shape slots 10 / 11 = evaluations beyond the LDS window and their terms, in the TEAM shape they are cycles (numbering, the
@@ -35,7 +41,7 @@ pr = pri.astype(np.float64)
 wave_counts = REF and bool((pr[:, 10] <= r["evals"]).all())
 count_slots = ([9, 10, 11] if wave_counts else [9]) if REF else []
 if REF:
-    NAMES[9], NAMES[10], NAMES[11] = "(count) active terms", "numbering" if not wave_counts else "(count)", "window list" if not wave_counts else "(count)"
+    NAMES[9], NAMES[10], NAMES[11] = "(count) active terms", "numbering" if not wave_counts else "(count)", ("list flushes" if SLOT11 == "flush" else "emission" if SLOT11 == "emit" else "window list") if not wave_counts else "(count)"
 cyc = pr.copy()
 cyc[:, count_slots] = 0.0
 tot = cyc.sum(axis=1)
@@ -57,6 +63,9 @@ if REF:
         big = pr[:, 10].sum()
         print("   evaluations with more terms than the LDS window holds:", round(float(100 * big / ev.sum()), 1), "% of all, with",
               round(float(pr[:, 11].sum() / max(1.0, big)), 1), "active terms on average")
+if REF and not wave_counts and flushes.sum() > 0:
+    print("QUAD shape: flushes of the list of active terms per evaluation, mean", round(float(flushes.sum() / ev.sum()), 2),
+          "-- active terms per flush of a wave (four rows):", round(float(4 * pr[:, 9].sum() / flushes.sum()), 1))
 if REF and not wave_counts:
     print("QUAD shape: evaluations on the slow path of the parked-term chain:", int(slow.sum()), "=", round(float(100 * slow.sum() / ev.sum()), 2), "% of all")
 print("two-loop cycles per history step (2 per entry per iteration):", round(float(np.median(pr[:, 8] / (2 * hs))), 1),
