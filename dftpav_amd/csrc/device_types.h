@@ -236,7 +236,8 @@ struct QuadSizes {
   size_t shared, row;
   int waves_per_cu, hand;
 };
-// a QUAD kernel's instance (solver_ref4.hip: ref4_kernel_for, solver_ref4m.hip: ref4m_kernel_for; the two share one signature)
+// a QUAD kernel's instance (solver_ref4.hip: ref4_kernel_for, solver_ref4m.hip: ref4m_kernel_for; the two share one signature, and
+// quad_lbfgs.h: the L-BFGS state machine and the shape-free pieces of their loops)
 using QuadKernel = void (*)(const DevBatch *, int, const double *, const double *, double *, int, int, int);
 
 // host-side E4 lane plan of a layout for a workgroup size (tables of DevBatch::e4_*)

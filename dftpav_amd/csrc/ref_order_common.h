@@ -1119,6 +1119,40 @@ __device__ inline void ring_push(unsigned *ctl, int *ring, int cap, int id) {
     if (__hip_atomic_compare_exchange_strong(&ctl[1], &expect, t + 1, __ATOMIC_RELEASE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
   }
 }
+// What one lane writes for a finished trajectory b (the epilogue of every reference-order kernel; solver.hip keeps its own): the
+// results, the 16-byte all-gather record and its host copy, the time in service (spent: this slice's), success, the ring's count.
+// st, ist: the trajectory's scalar solver state.
+__device__ __forceinline__ void write_results(const DevBatch &D, int b, ldscd_t st, ldsi_t ist, bool resumed, long long spent, bool ring) {
+  const double fx = st[sFX];
+  const int ret = ist[iRET];
+  D.f_out[b] = fx;
+  D.status[b] = ret;
+  D.iters[b] = ist[iK];
+  D.evals[b] = ist[iEVALS];
+  D.hist_sum[b] = ((long long)ist[iHISTHI] << 32) | (unsigned int)ist[iHISTLO];
+  {
+    double *rec = reinterpret_cast<double *>(D.records + (size_t)16 * b); // the all-gather record (as solver.hip's epilogue)
+    rec[0] = fx;
+    int *ri = reinterpret_cast<int *>(rec + 1);
+    ri[0] = ret;
+    ri[1] = ist[iK];
+  }
+  if (D.records_host != nullptr) { // (see device_types.h)
+    double *rh = reinterpret_cast<double *>(D.records_host + (size_t)16 * b);
+    rh[0] = fx;
+    int *rj = reinterpret_cast<int *>(rh + 1);
+    rj[0] = ret;
+    rj[1] = ist[iK];
+  }
+  D.ticks[b] = (resumed ? D.ticks[b] : 0) + spent; // time in service
+  int ok = (ret == 0 || ret == 1 || ret == 2 || ret == -1008 || ret == -1009) ? 1 : 0; // traj_optimizer.cpp:176-201
+  if (fx >= D.P.fail_cost) ok = 0;
+  D.success[b] = ok;
+  if (ring) {
+    D.sflag[b] = 2;
+    atomicSub(&D.qctl[3], 1u);
+  }
+}
 // (s, y) pairs of the history, (ys, 1 / ys) of a stored pair
 typedef double __attribute__((ext_vector_type(2))) d2_t;
 typedef const d2_t __attribute__((address_space(1))) *gcd2_t;

@@ -1929,37 +1929,7 @@ __global__ void __launch_bounds__((WAVE && CAP <= kNarrowCap && !SUR) ? 512 : 25
     const long long spent = wall_clock64() - tick0;
     if (finished) {
       for (int e = tid; e < n; e += T) D.x_out[(size_t)b * n + e] = sm.x[e];
-      if (tid == 0) {
-        const double fx = sm.st[sFX];
-        const int ret = sm.ist[iRET];
-        D.f_out[b] = fx;
-        D.status[b] = ret;
-        D.iters[b] = sm.ist[iK];
-        D.evals[b] = sm.ist[iEVALS];
-        D.hist_sum[b] = ((long long)sm.ist[iHISTHI] << 32) | (unsigned int)sm.ist[iHISTLO];
-        {
-          double *rec = reinterpret_cast<double *>(D.records + (size_t)16 * b); // the all-gather record (as solver.hip's epilogue)
-          rec[0] = fx;
-          int *ri = reinterpret_cast<int *>(rec + 1);
-          ri[0] = ret;
-          ri[1] = sm.ist[iK];
-        }
-        if (D.records_host != nullptr) { // (see device_types.h)
-          double *rh = reinterpret_cast<double *>(D.records_host + (size_t)16 * b);
-          rh[0] = fx;
-          int *rj = reinterpret_cast<int *>(rh + 1);
-          rj[0] = ret;
-          rj[1] = sm.ist[iK];
-        }
-        D.ticks[b] = (resume ? D.ticks[b] : 0) + spent; // time in service
-        int ok = (ret == 0 || ret == 1 || ret == 2 || ret == -1008 || ret == -1009) ? 1 : 0; // traj_optimizer.cpp:176-201
-        if (fx >= D.P.fail_cost) ok = 0;
-        D.success[b] = ok;
-        if (ring) {
-          D.sflag[b] = 2;
-          atomicSub(&D.qctl[3], 1u);
-        }
-      }
+      if (tid == 0) write_results(D, b, sm.st, sm.ist, resume, spent, ring);
     } else {
       state_io(D, sm, b, tid, sh.nl, true);
       __threadfence(); // the record and the history rows of this slice are out before the id is handed on

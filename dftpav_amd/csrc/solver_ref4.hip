@@ -26,7 +26,9 @@
 //     batch at some 7 k cycles each (profiles/dense_list_phases.txt);
 //   * the corridor is read from a copy laid out [component][j][piece]: the 16 lanes of a row read 128 contiguous bytes; a batch whose
 //     corridors are all rectangles (q4_rect_check_kernel) reads a copy of 10 doubles per point instead of 16 (RECT, below);
-//   * lbfgs_optimize / line_search_lewisoverton (lbfgs.hpp:276-390, 440-751): solver_ref.hip's lbfgs_advance, per row; a vector of
+//   * lbfgs_optimize / line_search_lewisoverton (lbfgs.hpp:276-390, 440-751): solver_ref.hip's lbfgs_advance, per row (quad_lbfgs.h:
+//     the state machine, the record of a suspended trajectory and the shape-free pieces of the loop, shared with solver_ref4m.hip;
+//     this file: Q4Shape, the recursion and the mirror of the ring's ends); a vector of
 //     n <= 32 variables is two registers per lane (elements l and 16 + l), a sequential dot product is the 32-step DPP chain --
 //     each row chains its own sixteen lanes, no permlane swap -- and the two-loop recursion (:716-739) runs the four rows' history
 //     steps in the same instructions (a row that is still in its line search, or has the shorter history, is masked).
@@ -48,7 +50,7 @@
 #include <algorithm>
 
 #include "ref_order_common.h"
-#include "quad_common.h"
+#include "quad_lbfgs.h"
 
 namespace dftpav {
 namespace reford {
@@ -803,44 +805,7 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
   return total_smcost + total_timecost + penalty_cost;
 }
 
-// ------------------------------------------------ L-BFGS, per row
-struct QVec { // the solver's vectors that live in registers: element l and element 16 + l
-  double xp0, xp1, gp0, gp1, d0, d1;
-};
-
-// Start of an outer iteration (lbfgs.hpp:559-574, 290-315): xp = x, gp = g, dginit = gp . d, first trial point
-__device__ __forceinline__ bool q4_begin_iteration(const DevParams &P, const Q4 &q, QVec &v, int n, int l) {
-  const bool e0 = l < n, e1 = 16 + l < n;
-  v.xp0 = e0 ? q.xs[l] : 0.0;
-  v.xp1 = e1 ? q.xs[16 + l] : 0.0;
-  v.gp0 = e0 ? q.gs[l] : 0.0;
-  v.gp1 = e1 ? q.gs[16 + l] : 0.0;
-  const double dginit = row_sum32(v.gp0 * v.d0, v.gp1 * v.d1, n, l);
-  const double step = q.st[sSTEP];
-  if (!(step > 0.0)) {
-    if (l == 0) q.ist[iRET] = -1006;
-    return false;
-  }
-  if (0.0 < dginit) {
-    if (l == 0) q.ist[iRET] = -1005;
-    return false;
-  }
-  if (l == 0) {
-    q.st[sFINIT] = q.st[sFX];
-    q.st[sDGINIT] = dginit;
-    q.st[sDGTEST] = P.f_dec_coeff * dginit;
-    q.st[sDSTEST] = P.s_curv_coeff * dginit;
-    q.st[sMU] = 0.0;
-    q.st[sNU] = P.max_step;
-    q.st[sSTP] = step;
-    q.ist[iCOUNT] = 0;
-    q.ist[iBRACKT] = 0;
-    q.ist[iTOUCHED] = 0;
-  }
-  if (e0) q.xs[l] = v.xp0 + step * v.d0;
-  if (e1) q.xs[16 + l] = v.xp1 + step * v.d1;
-  return true;
-}
+// ------------------------------------------------ L-BFGS, per row: the state machine is quad_lbfgs.h's; the recursion is this file's
 
 // The two-loop recursion (lbfgs.hpp:716-739) over `bound` stored pairs of this row's trajectory, the newest in slot ne - 1;
 // d = -g on entry (elements from n on: 0.0).  The four rows run their steps in the same instructions; bound, the ring position
@@ -865,7 +830,7 @@ template <bool Y3> struct QBlk {
 typedef double __attribute__((ext_vector_type(2))) qd2_t;
 
 // 0.0 + p[0] + ... + p[n-1] in the recursion: row_sum32 without its selects.  The elements from n on of d are +-0.0 wherever this is
-// called (q4_state_io, q4_begin_iteration's callers and q4_advance set them to 0.0, and a step adds coefficient * 0.0 to them: the
+// called (quad_lbfgs.h: quad_state_io, quad_take and quad_advance set them to 0.0, and a step adds coefficient * 0.0 to them: the
 // elements from n on of every stored s and y are +0.0 -- the buffers are cleared when they are allocated and no lane >= n stores),
 // so their products are +-0.0 as long as the coefficients are finite.  The chain starts from +0.0, and a sum rounded to nearest is
 // -0.0 only if both operands are: the accumulator is never -0.0, and adding +0.0 or -0.0 leaves it as it is -- what row_sum32's
@@ -1005,307 +970,30 @@ __device__ __forceinline__ void q4_store_pair(gd_t hS, gd_t hM, int m, int end, 
   if (end >= m - kQB) ((gd2_t)hM)[(end - (m - kQB)) * kQNpad + e] = v;
 }
 
-// Everything lbfgs_optimize does between two evaluations (lbfgs.hpp:524-745 with the line search of :312-389 unrolled into it):
-// solver_ref.hip's lbfgs_advance for the trajectory of this row; f: the cost of the evaluation just made; sets iACTION.
-__device__ __forceinline__ void q4_advance(const DevBatch &D, const Q4 &q, QVec &v, double f, gd_t hS, gd_t hM, gd_t hR, int l, Prof &pr) {
-  const DevParams &P = D.P;
-  const int n = D.L.n, m = P.mem_size;
-  const bool e0 = l < n, e1 = 16 + l < n;
-  int action = kActEval;
-  if (q.ist[iPHASE] == 0) { // after the first evaluation: lbfgs.hpp:524-551
-    const double g0 = e0 ? q.gs[l] : 0.0, g1 = e1 ? q.gs[16 + l] : 0.0;
-    const double x0 = e0 ? q.xs[l] : 0.0, x1 = e1 ? q.xs[16 + l] : 0.0;
-    v.d0 = e0 ? -g0 : 0.0;
-    v.d1 = e1 ? -g1 : 0.0;
-    const double gmax = row_max16(fmax(fabs(g0), fabs(g1))), xmax = row_max16(fmax(fabs(x0), fabs(x1)));
-    const double dd = row_sum32((-g0) * (-g0), (-g1) * (-g1), n, l);
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    if (l == 0) {
-      q.st[sFX] = f;
-      q.st[sPF0] = f;
-      q.ist[iEVALS] = 1;
-      q.ist[iEND] = 0;
-      q.ist[iBOUND] = 0;
-      q.ist[iHISTLO] = 0;
-      q.ist[iHISTHI] = 0;
-      q.ist[iPHASE] = 1;
-    }
-    if (gmax / fmax(1.0, xmax) < P.g_epsilon) {
-      if (l == 0) {
-        q.ist[iRET] = 0;
-        q.ist[iK] = 0;
-      }
-      action = kActDone;
-    } else {
-      if (l == 0) {
-        q.st[sSTEP] = 1.0 / sqrt(dd);
-        q.ist[iK] = 1;
-      }
-      __threadfence_block();
-      if (!q4_begin_iteration(P, q, v, n, l)) action = kActDone;
-    }
-    if (l == 0) q.ist[iACTION] = action;
-    return;
+// What quad_lbfgs.h's state machine needs to know of this kernel: a vector in two registers, the 32-step chain, a pair stored to
+// the ring and to the mirror, the recursion above.  hS, hM, hR: the history of the row's trajectory.
+struct Q4Shape {
+  static constexpr int NV = 2;
+  typedef Q4 Row;
+  gd_t hS, hM, hR;
+  __device__ __forceinline__ double row_sum(const double (&p)[2], int n, int l) const { return row_sum32(p[0], p[1], n, l); }
+  __device__ __forceinline__ void store_pair(int m, int end, int e, d2_t sy) const { q4_store_pair(hS, hM, m, end, e, sy); }
+  // histR as the WAVE shape reads it; n <= 31: (ys, 1 / ys) travel in the row too, as its element 31 (q4_two_loop)
+  __device__ __forceinline__ void store_ys(int m, int end, int n, int l, d2_t yr) const {
+    if (l == 0) ((gd2_t)hR)[end] = yr;
+    if (l == 15 && n <= 31) q4_store_pair(hS, hM, m, end, 31, yr);
   }
-
-  // ---- after a line-search trial: lbfgs.hpp:317-389
-  const double fx = f;
-  const double finit = q.st[sFINIT];
-  double stp = q.st[sSTP];
-  const int count = q.ist[iCOUNT] + 1;
-  int ls = 0;
-  bool decided = false;
-  const int evals_before = q.ist[iEVALS];
-  __threadfence_block();
-  if (l == 0) {
-    q.st[sFX] = fx;
-    q.ist[iEVALS] = evals_before + 1;
-    q.ist[iCOUNT] = count;
-  }
-  if (isinf(fx) || isnan(fx)) {
-    ls = -1012;
-    decided = true;
-  } else if (P.past > 0 && fabs(finit - fx) / (fabs(finit) + 1.0) < P.delta / P.past) { // lbfgs.hpp:326-329
-    ls = count;
-    decided = true;
-  } else {
-    double mu = q.st[sMU], nu = q.st[sNU];
-    bool brackt = q.ist[iBRACKT] != 0;
-    const int touched = q.ist[iTOUCHED];
-    if (fx > finit + stp * q.st[sDGTEST]) {
-      nu = stp;
-      brackt = true;
-    } else {
-      const double g0 = e0 ? q.gs[l] : 0.0, g1 = e1 ? q.gs[16 + l] : 0.0;
-      const double gs = row_sum32(g0 * v.d0, g1 * v.d1, n, l);
-      if (gs < q.st[sDSTEST]) {
-        mu = stp;
-      } else {
-        ls = count;
-        decided = true;
-      }
-    }
-    bool touch_now = false;
-    if (!decided) {
-      if (P.max_linesearch <= count) {
-        ls = -1009;
-        decided = true;
-      } else if (brackt && (nu - mu) < P.machine_prec * nu) {
-        ls = -1007;
-        decided = true;
-      } else {
-        if (brackt) stp = 0.5 * (mu + nu);
-        else stp *= 2.0;
-        if (stp < P.min_step) {
-          ls = -1011;
-          decided = true;
-        } else if (stp > P.max_step) {
-          if (touched) {
-            ls = -1010;
-            decided = true;
-          } else {
-            touch_now = true;
-            stp = P.max_step;
-          }
-        }
-      }
-    }
-    __threadfence_block();
-    if (l == 0) {
-      q.st[sMU] = mu;
-      q.st[sNU] = nu;
-      q.ist[iBRACKT] = brackt ? 1 : 0;
-      q.st[sSTP] = stp;
-      if (touch_now) q.ist[iTOUCHED] = 1;
-    }
-    if (!decided) {
-      if (e0) q.xs[l] = v.xp0 + stp * v.d0;
-      if (e1) q.xs[16 + l] = v.xp1 + stp * v.d1;
-      if (l == 0) q.ist[iACTION] = kActEval;
-      pr.tick(6);
-      return;
-    }
-  }
-  if (l == 0) q.st[sSTEP] = stp; // lbfgs.hpp:574 passes `step` by reference
-  if (ls < 0) { // lbfgs.hpp:604-611: x, g reverted; fx is not
-    if (e0) {
-      q.xs[l] = v.xp0;
-      q.gs[l] = v.gp0;
-    }
-    if (e1) {
-      q.xs[16 + l] = v.xp1;
-      q.gs[16 + l] = v.gp1;
-    }
-    if (l == 0) {
-      q.ist[iRET] = ls;
-      q.ist[iACTION] = kActDone;
-    }
-    return;
-  }
-
-  // ---- convergence / stopping tests (lbfgs.hpp:628-666)
-  const double x0 = e0 ? q.xs[l] : 0.0, x1 = e1 ? q.xs[16 + l] : 0.0;
-  const double g0 = e0 ? q.gs[l] : 0.0, g1 = e1 ? q.gs[16 + l] : 0.0;
-  int k = q.ist[iK];
-  {
-    const double gmax = row_max16(fmax(fabs(g0), fabs(g1))), xmax = row_max16(fmax(fabs(x0), fabs(x1)));
-    const int kGoOn = 12345;
-    int ret = kGoOn;
-    if (gmax / fmax(1.0, xmax) < P.g_epsilon) {
-      ret = 0;
-    } else {
-      if (0 < P.past) {
-        const int slot = k % P.past;
-        const double pf = q.st[sPF0 + slot];
-        __threadfence_block();
-        if (P.past <= k) {
-          const double rate = fabs(pf - fx) / fmax(1.0, fabs(fx));
-          if (rate < P.delta) ret = 1;
-        }
-        if (ret == kGoOn && l == 0) q.st[sPF0 + slot] = fx;
-      }
-      if (ret == kGoOn && P.max_iterations != 0 && P.max_iterations <= k) ret = -1008;
-    }
-    if (ret != kGoOn) {
-      if (l == 0) {
-        q.ist[iRET] = ret;
-        q.ist[iACTION] = kActDone;
-      }
-      return;
-    }
-  }
-  ++k;
-  pr.tick(6);
-  const int end = q.ist[iEND];
-  int bound = q.ist[iBOUND];
-  __threadfence_block();
-  if (l == 0) q.ist[iK] = k;
-
-  // ---- history update + two-loop recursion (lbfgs.hpp:676-740); (s, y) interleaved per element
-  const double sv0 = e0 ? x0 - v.xp0 : 0.0, sv1 = e1 ? x1 - v.xp1 : 0.0;
-  const double yv0 = e0 ? g0 - v.gp0 : 0.0, yv1 = e1 ? g1 - v.gp1 : 0.0;
-  if (e0) {
-    d2_t sy;
-    sy.x = sv0;
-    sy.y = yv0;
-    q4_store_pair(hS, hM, m, end, l, sy);
-  }
-  if (e1) {
-    d2_t sy;
-    sy.x = sv1;
-    sy.y = yv1;
-    q4_store_pair(hS, hM, m, end, 16 + l, sy);
-  }
-  v.d0 = e0 ? -g0 : 0.0;
-  v.d1 = e1 ? -g1 : 0.0;
-  // the four dot products of lbfgs.hpp:683-694
-  const double ys = row_sum32(yv0 * sv0, yv1 * sv1, n, l);
-  const double yy = row_sum32(yv0 * yv0, yv1 * yv1, n, l);
-  const double ss = row_sum32(sv0 * sv0, sv1 * sv1, n, l);
-  const double gpgp = row_sum32(v.gp0 * v.gp0, v.gp1 * v.gp1, n, l);
-  if (l == 0) {
-    d2_t yr;
-    yr.x = ys;
-    yr.y = 1.0 / ys;
-    ((gd2_t)hR)[end] = yr;
-    if (!rcp_route_ok(ys)) q.ist[iSLOWDIV] = 1; // from here on the recursion divides (see div_by_rcp)
-  }
-  const bool y3 = n > 31; // (uniform) element 31 is a variable: (ys, 1 / ys) come from histR
-  if (l == 15 && !y3) { // ... otherwise they travel in the row, as its element 31 (every lane of the row holds ys)
-    d2_t yr;
-    yr.x = ys;
-    yr.y = 1.0 / ys;
-    q4_store_pair(hS, hM, m, end, 31, yr);
-  }
-  const double cau = ss * sqrt(gpgp) * P.cautious_factor;
-  pr.tick(7);
-  if (ys > cau) {
-    ++bound;
-    bound = m < bound ? m : bound;
-    const int ne = end + 1 == m ? 0 : end + 1;
-    __threadfence_block(); // the newest pair's row and (ys, 1 / ys) are read back below
-    const bool exact = q.ist[iSLOWDIV] != 0;
-    double d0 = v.d0, d1 = v.d1;
+  template <bool EXACT>
+  __device__ __forceinline__ void two_loop(const Q4 &q, int m, int n, int l, int bound, int ne, bool exact, double sc0, double (&d)[2]) const {
     const gcd2_t cS = (gcd2_t)hS, cM = (gcd2_t)hM, cR = (gcd2_t)hR;
-    // (the division mode is a wave-level choice of code: the reciprocal route has no branch in its steps)
-    if (__builtin_amdgcn_ballot_w64(exact) != 0ull) {
-      if (y3) q4_two_loop<true, true>(q, cS, cM, cR, m, n, l, bound, ne, exact, ys / yy, d0, d1);
-      else q4_two_loop<true, false>(q, cS, cM, cR, m, n, l, bound, ne, exact, ys / yy, d0, d1);
-    } else {
-      if (y3) q4_two_loop<false, true>(q, cS, cM, cR, m, n, l, bound, ne, exact, ys / yy, d0, d1);
-      else q4_two_loop<false, false>(q, cS, cM, cR, m, n, l, bound, ne, exact, ys / yy, d0, d1);
-    }
-    v.d0 = e0 ? d0 : 0.0;
-    v.d1 = e1 ? d1 : 0.0;
-    if (l == 0) {
-      q.ist[iEND] = ne;
-      q.ist[iBOUND] = bound;
-      long long hs = ((long long)q.ist[iHISTHI] << 32) | (unsigned int)q.ist[iHISTLO];
-      hs += bound;
-      q.ist[iHISTLO] = (int)(hs & 0xffffffffLL);
-      q.ist[iHISTHI] = (int)(hs >> 32);
-    }
+    if (n > 31) q4_two_loop<EXACT, true>(q, cS, cM, cR, m, n, l, bound, ne, exact, sc0, d[0], d[1]); // (uniform) element 31 is a variable
+    else q4_two_loop<EXACT, false>(q, cS, cM, cR, m, n, l, bound, ne, exact, sc0, d[0], d[1]);
   }
-  if (l == 0) q.st[sSTEP] = 1.0; // lbfgs.hpp:743
-  pr.tick(8);
-  __threadfence_block();
-  const bool ok = q4_begin_iteration(P, q, v, n, l);
-  if (l == 0) q.ist[iACTION] = ok ? kActEval : kActDone;
-  pr.tick(6);
-}
-
-// solver state of a suspended trajectory <-> its record in DevBatch::state (the layout of solver_ref.hip's state_io: five vectors at
-// pitch npad -- x, xp, g, gp, d --, the scalars, the integers)
-__device__ inline void q4_state_io(const DevBatch &D, const Q4 &q, QVec &v, int b, int l, bool save) {
-  const int n = D.L.n, npad = D.L.npad;
-  double *rec = D.state + (size_t)b * D.state_stride;
-  for (int h = 0; h < 2; h++) {
-    const int e = 16 * h + l;
-    if (e >= n) {
-      if (!save) {
-        q.xs[e] = 0.0;
-        q.gs[e] = 0.0;
-        if (h == 0) { v.xp0 = 0.0; v.gp0 = 0.0; v.d0 = 0.0; } else { v.xp1 = 0.0; v.gp1 = 0.0; v.d1 = 0.0; }
-      }
-      continue;
-    }
-    if (save) {
-      rec[0 * npad + e] = q.xs[e];
-      rec[1 * npad + e] = h == 0 ? v.xp0 : v.xp1;
-      rec[2 * npad + e] = q.gs[e];
-      rec[3 * npad + e] = h == 0 ? v.gp0 : v.gp1;
-      rec[4 * npad + e] = h == 0 ? v.d0 : v.d1;
-    } else {
-      q.xs[e] = rec[0 * npad + e];
-      q.gs[e] = rec[2 * npad + e];
-      if (h == 0) {
-        v.xp0 = rec[1 * npad + e];
-        v.gp0 = rec[3 * npad + e];
-        v.d0 = rec[4 * npad + e];
-      } else {
-        v.xp1 = rec[1 * npad + e];
-        v.gp1 = rec[3 * npad + e];
-        v.d1 = rec[4 * npad + e];
-      }
-    }
-  }
-  double *r2 = rec + 5 * npad;
-  for (int w = l; w < sNUM; w += 16) {
-    if (save) r2[w] = q.st[w];
-    else q.st[w] = r2[w];
-  }
-  int *ri = reinterpret_cast<int *>(r2 + 24);
-  for (int w = l; w < iNUM; w += 16) {
-    if (save) ri[w] = q.ist[w];
-    else q.ist[w] = ri[w];
-  }
-}
+};
 
 // ------------------------------------------------ the kernel
-// source bit 0: the rows pop trajectories from the batch's ring (solves; DevBatch::queue as solver_ref.hip uses it) -- otherwise row
-// r of wave w of workgroup i takes trajectory (i W + w) 4 + r; bit 1: test hook, true divisions in the recursion from the start.
-// slice: evaluations of a wave after which its unfinished trajectories go back to the ring (all four rows together, so that the
-// rows of a wave are refilled together and the last trajectories of a batch gather in few waves).  hand: see the slice's end.
+// source, hand: quad_lbfgs.h (quad_take, quad_end_slice).  slice: evaluations of a wave after which its unfinished trajectories go
+// back to the ring.
 template <bool FAST, bool RECT>
 __global__ void __launch_bounds__(256, DFTPAV_Q4_WAVES_PER_EU)
     ref4_kernel(const DevBatch *__restrict__ Dp, int mode, const double *__restrict__ tabs, const double *__restrict__ cor_t, double *__restrict__ scratch, int source,
@@ -1331,48 +1019,18 @@ __global__ void __launch_bounds__(256, DFTPAV_Q4_WAVES_PER_EU)
   pr.on = false;
   pr.acc = nullptr;
   pr.last = 0;
-  QVec v{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  int b = -1;
-  bool act = false, resumed = false;
-  long long tick0 = 0;
+  QuadVec<2> v{};
+  QuadRun r{-1, false, false, 0};
   int steps = 0;
 
   for (int pass = 0;; pass++) {
-    // ---- rows without a trajectory take one
-    if (!act) {
-      int id = -1;
-      if (ring) {
-        for (int r = 0; r < 4; r++) // one row after the other (the rows of a wave would otherwise race each other for the head)
-          if (row == r && l == 0) id = ring_pop(D.qctl, D.queue, D.qcap);
-        id = __shfl(id, lane & 48);
-      } else if (pass == 0) {
-        id = ((int)blockIdx.x * W + wv) * 4 + row;
-        if (id >= D.B) id = -1;
-      }
-      if (id >= 0) {
-        b = id;
-        act = true;
-        resumed = ring && D.sflag[b] == 1;
-        if (resumed) {
-          q4_state_io(D, q, v, b, l, false);
-        } else {
-          const double *xsrc = (mode == kModeSolve) ? D.x0 : D.x_in;
-          for (int h = 0; h < 2; h++) {
-            const int e = 16 * h + l;
-            q.xs[e] = e < n ? xsrc[(size_t)b * n + e] : 0.0;
-            q.gs[e] = 0.0;
-          }
-          v = QVec{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-          q.ist[l] = (l == iSLOWDIV && force_exact_div) ? 1 : 0; // (iNUM == 16 lanes)
-        }
-        if (l < 12) q.bnd[l] = l < 6 ? D.iniS[(size_t)b * 6 + l] : D.finS[(size_t)b * 6 + (l - 6)];
-        tick0 = wall_clock64();
-        pr.start(D.prof != nullptr && mode == kModeSolve && l == 0, D.prof + (size_t)b * 12, resumed);
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      }
+    if (!r.act && quad_take(D, q, v, r, mode, ring, force_exact_div, pass, pr)) {
+      if (l < 12) q.bnd[l] = l < 6 ? D.iniS[(size_t)r.b * 6 + l] : D.finS[(size_t)r.b * 6 + (l - 6)];
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     }
-    if (__builtin_amdgcn_ballot_w64(act) == 0ull) break; // (uniform) this wave has nothing left to do
-    if (act) {
+    if (__builtin_amdgcn_ballot_w64(r.act) == 0ull) break; // (uniform) this wave has nothing left to do
+    if (r.act) {
+      const int b = r.b;
       // (RECT: the copy of 16-byte units [b][j][unit 5][piece 16], q4_corridor_rect_kernel)
       const gcd_t cor = RECT ? (gcd_t)(cor_t + ((size_t)b * JP * 80 + l) * 2) : (gcd_t)(cor_t + (size_t)b * L.H * 4 * cpitch + l);
       const gd_t ovf = (gd_t)(scratch + (size_t)b * scratch_per_traj);
@@ -1383,77 +1041,23 @@ __global__ void __launch_bounds__(256, DFTPAV_Q4_WAVES_PER_EU)
           if (e < n) D.g_out[(size_t)b * n + e] = q.gs[e];
         }
         if (l == 0) D.f_eval[b] = f;
-        act = false;
+        r.act = false;
       } else {
-        const gd_t hS = (gd_t)(D.histS + (size_t)b * mem * kQNpad * 2);
-        const gd_t hM = (gd_t)(D.histM + (size_t)b * kQuadMirrorRows * kQNpad * 2);
-        const gd_t hR = (gd_t)(D.histR + (size_t)b * mem * 2);
-        q4_advance(D, q, v, f, hS, hM, hR, l, pr);
+        const Q4Shape sh{(gd_t)(D.histS + (size_t)b * mem * kQNpad * 2), (gd_t)(D.histM + (size_t)b * kQuadMirrorRows * kQNpad * 2),
+                         (gd_t)(D.histR + (size_t)b * mem * 2)};
+        quad_advance(D, sh, q, v, f, l, pr);
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        if (q.ist[iACTION] == kActDone) { // the epilogue of solver_ref.hip
-          for (int h = 0; h < 2; h++) {
-            const int e = 16 * h + l;
-            if (e < n) D.x_out[(size_t)b * n + e] = q.xs[e];
-          }
-          if (l == 0) {
-            const double fx = q.st[sFX];
-            const int ret = q.ist[iRET];
-            D.f_out[b] = fx;
-            D.status[b] = ret;
-            D.iters[b] = q.ist[iK];
-            D.evals[b] = q.ist[iEVALS];
-            D.hist_sum[b] = ((long long)q.ist[iHISTHI] << 32) | (unsigned int)q.ist[iHISTLO];
-            {
-              double *rec = reinterpret_cast<double *>(D.records + (size_t)16 * b); // the all-gather record
-              rec[0] = fx;
-              int *ri = reinterpret_cast<int *>(rec + 1);
-              ri[0] = ret;
-              ri[1] = q.ist[iK];
-            }
-            if (D.records_host != nullptr) { // (see device_types.h)
-              double *rh = reinterpret_cast<double *>(D.records_host + (size_t)16 * b);
-              rh[0] = fx;
-              int *rj = reinterpret_cast<int *>(rh + 1);
-              rj[0] = ret;
-              rj[1] = q.ist[iK];
-            }
-            D.ticks[b] = (resumed ? D.ticks[b] : 0) + (wall_clock64() - tick0); // time in service
-            int ok = (ret == 0 || ret == 1 || ret == 2 || ret == -1008 || ret == -1009) ? 1 : 0; // traj_optimizer.cpp:176-201
-            if (fx >= D.P.fail_cost) ok = 0;
-            D.success[b] = ok;
-            if (ring) {
-              D.sflag[b] = 2;
-              atomicSub(&D.qctl[3], 1u);
-            }
-          }
-          act = false;
-        }
+        if (q.ist[iACTION] == kActDone) quad_results<2>(D, q, r, ring);
       }
     }
     if (!ring) {
       if (mode == kModeEval) break;
       continue;
     }
-    // ---- end of a slice: the wave's unfinished trajectories go back to the ring
     steps++;
     if (slice > 0 && steps >= slice) { // (uniform)
       steps = 0;
-      // hand: once no more than this many trajectories of the batch are unfinished, the waves put theirs back and LEAVE -- the host
-      // has a launch of the WAVE shape (solver_ref.hip: a wave per trajectory, 2-3 x faster per iteration on a device that is
-      // emptying) queued behind this one, which pops them from the same ring and resumes them from the same records
-      const bool leave = hand > 0 && __hip_atomic_load(&D.qctl[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= (unsigned)hand;
-      if (act) {
-        q4_state_io(D, q, v, b, l, true);
-        __threadfence(); // the record and the history rows of this slice are out before the id is handed on
-        if (l == 0) {
-          D.ticks[b] = (resumed ? D.ticks[b] : 0) + (wall_clock64() - tick0);
-          D.sflag[b] = 1;
-        }
-      }
-      for (int r = 0; r < 4; r++)
-        if (act && row == r && l == 0) ring_push(D.qctl, D.queue, D.qcap, b);
-      act = false;
-      if (leave) break;
+      if (quad_end_slice(D, q, v, r, hand)) break;
     }
   }
 }

@@ -15,6 +15,8 @@
 //   * the per-segment chains (gdT, energy, the parked terms' shares) are formed per segment with the other segments' lanes masked to
 //     -0.0; the gradients of a junction's position and angle come from two neighbouring lanes (the last piece of one segment, the
 //     first of the next: one DPP step).
+// What is NOT here: the L-BFGS state machine, the record of a suspended trajectory and the shape-free pieces of the persistent loop
+// are quad_lbfgs.h's, the ones ref4_kernel runs; this file gives them Q4MShape<TAIL> (three registers, row_sum48, q4m_two_loop).
 // Same bits as the TEAM / WAVE shapes and the restatement with correctly rounded cos / sin (oracle order 2).
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -22,7 +24,7 @@
 #include <algorithm>
 
 #include "ref_order_common.h"
-#include "quad_common.h"
+#include "quad_lbfgs.h"
 
 namespace dftpav {
 namespace reford {
@@ -548,48 +550,7 @@ __device__ __forceinline__ double q4m_eval(const DevBatch &D, const Q4M &q, ldsc
   return total_smcost + total_timecost + penalty_cost;
 }
 
-// ------------------------------------------------ L-BFGS, per row (solver_ref4.hip's, a vector in three registers)
-struct QVecM {
-  double xp[kMV], gp[kMV], d[kMV];
-};
-__device__ __forceinline__ void q4m_read(ldscd_t a, int n, int l, double (&o)[kMV]) {
-#pragma unroll
-  for (int h = 0; h < kMV; h++) o[h] = 16 * h + l < n ? a[16 * h + l] : 0.0;
-}
-template <int TAIL>
-__device__ __forceinline__ bool q4m_begin_iteration(const DevParams &P, const Q4M &q, QVecM &v, int n, int l) {
-  q4m_read(q.xs, n, l, v.xp);
-  q4m_read(q.gs, n, l, v.gp);
-  double pr_[kMV];
-#pragma unroll
-  for (int h = 0; h < kMV; h++) pr_[h] = v.gp[h] * v.d[h];
-  const double dginit = row_sum48<TAIL>(pr_, n, l);
-  const double step = q.st[sSTEP];
-  if (!(step > 0.0)) {
-    if (l == 0) q.ist[iRET] = -1006;
-    return false;
-  }
-  if (0.0 < dginit) {
-    if (l == 0) q.ist[iRET] = -1005;
-    return false;
-  }
-  if (l == 0) {
-    q.st[sFINIT] = q.st[sFX];
-    q.st[sDGINIT] = dginit;
-    q.st[sDGTEST] = P.f_dec_coeff * dginit;
-    q.st[sDSTEST] = P.s_curv_coeff * dginit;
-    q.st[sMU] = 0.0;
-    q.st[sNU] = P.max_step;
-    q.st[sSTP] = step;
-    q.ist[iCOUNT] = 0;
-    q.ist[iBRACKT] = 0;
-    q.ist[iTOUCHED] = 0;
-  }
-#pragma unroll
-  for (int h = 0; h < kMV; h++)
-    if (16 * h + l < n) q.xs[16 * h + l] = v.xp[h] + step * v.d[h];
-  return true;
-}
+// ------------------------------------------------ L-BFGS, per row: the state machine is quad_lbfgs.h's; the recursion is this file's
 
 constexpr int kMB = 4; // stored pairs per register block
 struct MBlk {
@@ -689,291 +650,25 @@ __device__ __forceinline__ void q4m_two_loop(const Q4M &q, gcd2_t hS, gcd2_t hR,
   }
 }
 
-// Everything lbfgs_optimize does between two evaluations: solver_ref4.hip's q4_advance with three registers per vector
-template <int TAIL>
-__device__ __forceinline__ void q4m_advance(const DevBatch &D, const Q4M &q, QVecM &v, double f, gd_t hS, gd_t hR, int l, Prof &pr) {
-  const DevParams &P = D.P;
-  const int n = D.L.n, m = P.mem_size, npad = D.L.npad;
-  int action = kActEval;
-  auto vmax = [&](const double (&a)[kMV]) {
-    double mx = 0.0;
-#pragma unroll
-    for (int h = 0; h < kMV; h++) mx = fmax(mx, fabs(a[h]));
-    return row_max16(mx);
-  };
-  if (q.ist[iPHASE] == 0) { // after the first evaluation: lbfgs.hpp:524-551
-    double g[kMV], x[kMV], sq[kMV];
-    q4m_read(q.gs, n, l, g);
-    q4m_read(q.xs, n, l, x);
-#pragma unroll
-    for (int h = 0; h < kMV; h++) {
-      v.d[h] = 16 * h + l < n ? -g[h] : 0.0;
-      sq[h] = (-g[h]) * (-g[h]);
-    }
-    const double gmax = vmax(g), xmax = vmax(x);
-    const double dd = row_sum48<TAIL>(sq, n, l);
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    if (l == 0) {
-      q.st[sFX] = f;
-      q.st[sPF0] = f;
-      q.ist[iEVALS] = 1;
-      q.ist[iEND] = 0;
-      q.ist[iBOUND] = 0;
-      q.ist[iHISTLO] = 0;
-      q.ist[iHISTHI] = 0;
-      q.ist[iPHASE] = 1;
-    }
-    if (gmax / fmax(1.0, xmax) < P.g_epsilon) {
-      if (l == 0) {
-        q.ist[iRET] = 0;
-        q.ist[iK] = 0;
-      }
-      action = kActDone;
-    } else {
-      if (l == 0) {
-        q.st[sSTEP] = 1.0 / sqrt(dd);
-        q.ist[iK] = 1;
-      }
-      __threadfence_block();
-      if (!q4m_begin_iteration<TAIL>(P, q, v, n, l)) action = kActDone;
-    }
-    if (l == 0) q.ist[iACTION] = action;
-    return;
+// What quad_lbfgs.h's state machine needs to know of this kernel: a vector in three registers, the 48-step chain (TAIL: row_sum48),
+// a pair stored to the ring at pitch npad, the recursion above.  hS, hR: the history of the row's trajectory.
+template <int TAIL> struct Q4MShape {
+  static constexpr int NV = kMV;
+  typedef Q4M Row;
+  gd_t hS, hR;
+  int npad;
+  __device__ __forceinline__ double row_sum(const double (&p)[kMV], int n, int l) const { return row_sum48<TAIL>(p, n, l); }
+  __device__ __forceinline__ void store_pair(int m, int end, int e, d2_t sy) const { ((gd2_t)hS)[(size_t)end * npad + e] = sy; }
+  __device__ __forceinline__ void store_ys(int m, int end, int n, int l, d2_t yr) const {
+    if (l == 0) ((gd2_t)hR)[end] = yr;
   }
-  // ---- after a line-search trial: lbfgs.hpp:317-389
-  const double fx = f;
-  const double finit = q.st[sFINIT];
-  double stp = q.st[sSTP];
-  const int count = q.ist[iCOUNT] + 1;
-  int ls = 0;
-  bool decided = false;
-  const int evals_before = q.ist[iEVALS];
-  __threadfence_block();
-  if (l == 0) {
-    q.st[sFX] = fx;
-    q.ist[iEVALS] = evals_before + 1;
-    q.ist[iCOUNT] = count;
+  template <bool EXACT>
+  __device__ __forceinline__ void two_loop(const Q4M &q, int m, int n, int l, int bound, int ne, bool exact, double sc0, double (&d)[kMV]) const {
+    q4m_two_loop<EXACT, TAIL>(q, (gcd2_t)hS, (gcd2_t)hR, npad, m, n, l, bound, ne, exact, sc0, d);
   }
-  if (isinf(fx) || isnan(fx)) {
-    ls = -1012;
-    decided = true;
-  } else if (P.past > 0 && fabs(finit - fx) / (fabs(finit) + 1.0) < P.delta / P.past) { // lbfgs.hpp:326-329
-    ls = count;
-    decided = true;
-  } else {
-    double mu = q.st[sMU], nu = q.st[sNU];
-    bool brackt = q.ist[iBRACKT] != 0;
-    const int touched = q.ist[iTOUCHED];
-    if (fx > finit + stp * q.st[sDGTEST]) {
-      nu = stp;
-      brackt = true;
-    } else {
-      double g[kMV], pr_[kMV];
-      q4m_read(q.gs, n, l, g);
-#pragma unroll
-      for (int h = 0; h < kMV; h++) pr_[h] = g[h] * v.d[h];
-      const double gs = row_sum48<TAIL>(pr_, n, l);
-      if (gs < q.st[sDSTEST]) {
-        mu = stp;
-      } else {
-        ls = count;
-        decided = true;
-      }
-    }
-    bool touch_now = false;
-    if (!decided) {
-      if (P.max_linesearch <= count) {
-        ls = -1009;
-        decided = true;
-      } else if (brackt && (nu - mu) < P.machine_prec * nu) {
-        ls = -1007;
-        decided = true;
-      } else {
-        if (brackt) stp = 0.5 * (mu + nu);
-        else stp *= 2.0;
-        if (stp < P.min_step) {
-          ls = -1011;
-          decided = true;
-        } else if (stp > P.max_step) {
-          if (touched) {
-            ls = -1010;
-            decided = true;
-          } else {
-            touch_now = true;
-            stp = P.max_step;
-          }
-        }
-      }
-    }
-    __threadfence_block();
-    if (l == 0) {
-      q.st[sMU] = mu;
-      q.st[sNU] = nu;
-      q.ist[iBRACKT] = brackt ? 1 : 0;
-      q.st[sSTP] = stp;
-      if (touch_now) q.ist[iTOUCHED] = 1;
-    }
-    if (!decided) {
-#pragma unroll
-      for (int h = 0; h < kMV; h++)
-        if (16 * h + l < n) q.xs[16 * h + l] = v.xp[h] + stp * v.d[h];
-      if (l == 0) q.ist[iACTION] = kActEval;
-      pr.tick(6);
-      return;
-    }
-  }
-  if (l == 0) q.st[sSTEP] = stp; // lbfgs.hpp:574 passes `step` by reference
-  if (ls < 0) { // lbfgs.hpp:604-611: x, g reverted; fx is not
-#pragma unroll
-    for (int h = 0; h < kMV; h++)
-      if (16 * h + l < n) {
-        q.xs[16 * h + l] = v.xp[h];
-        q.gs[16 * h + l] = v.gp[h];
-      }
-    if (l == 0) {
-      q.ist[iRET] = ls;
-      q.ist[iACTION] = kActDone;
-    }
-    return;
-  }
-  // ---- convergence / stopping tests (lbfgs.hpp:628-666)
-  double x[kMV], g[kMV];
-  q4m_read(q.xs, n, l, x);
-  q4m_read(q.gs, n, l, g);
-  int k = q.ist[iK];
-  {
-    const double gmax = vmax(g), xmax = vmax(x);
-    const int kGoOn = 12345;
-    int ret = kGoOn;
-    if (gmax / fmax(1.0, xmax) < P.g_epsilon) {
-      ret = 0;
-    } else {
-      if (0 < P.past) {
-        const int slot = k % P.past;
-        const double pf = q.st[sPF0 + slot];
-        __threadfence_block();
-        if (P.past <= k) {
-          const double rate = fabs(pf - fx) / fmax(1.0, fabs(fx));
-          if (rate < P.delta) ret = 1;
-        }
-        if (ret == kGoOn && l == 0) q.st[sPF0 + slot] = fx;
-      }
-      if (ret == kGoOn && P.max_iterations != 0 && P.max_iterations <= k) ret = -1008;
-    }
-    if (ret != kGoOn) {
-      if (l == 0) {
-        q.ist[iRET] = ret;
-        q.ist[iACTION] = kActDone;
-      }
-      return;
-    }
-  }
-  ++k;
-  pr.tick(6);
-  const int end = q.ist[iEND];
-  int bound = q.ist[iBOUND];
-  __threadfence_block();
-  if (l == 0) q.ist[iK] = k;
-  // ---- history update + two-loop recursion (lbfgs.hpp:676-740)
-  double sv[kMV], yv[kMV], p0[kMV], p1[kMV], p2[kMV], p3[kMV];
-#pragma unroll
-  for (int h = 0; h < kMV; h++) {
-    const bool in = 16 * h + l < n;
-    sv[h] = in ? x[h] - v.xp[h] : 0.0;
-    yv[h] = in ? g[h] - v.gp[h] : 0.0;
-    if (in) {
-      d2_t sy;
-      sy.x = sv[h];
-      sy.y = yv[h];
-      ((gd2_t)hS)[(size_t)end * npad + 16 * h + l] = sy;
-    }
-    v.d[h] = in ? -g[h] : 0.0;
-    p0[h] = yv[h] * sv[h];
-    p1[h] = yv[h] * yv[h];
-    p2[h] = sv[h] * sv[h];
-    p3[h] = v.gp[h] * v.gp[h];
-  }
-  const double ys = row_sum48<TAIL>(p0, n, l), yy = row_sum48<TAIL>(p1, n, l), ss = row_sum48<TAIL>(p2, n, l), gpgp = row_sum48<TAIL>(p3, n, l);
-  if (l == 0) {
-    d2_t yr;
-    yr.x = ys;
-    yr.y = 1.0 / ys;
-    ((gd2_t)hR)[end] = yr;
-    if (!rcp_route_ok(ys)) q.ist[iSLOWDIV] = 1;
-  }
-  const double cau = ss * sqrt(gpgp) * P.cautious_factor;
-  pr.tick(7);
-  if (ys > cau) {
-    ++bound;
-    bound = m < bound ? m : bound;
-    const int ne = end + 1 == m ? 0 : end + 1;
-    __threadfence_block(); // the newest pair's row and (ys, 1 / ys) are read back below
-    const bool exact = q.ist[iSLOWDIV] != 0;
-    double d[kMV];
-#pragma unroll
-    for (int h = 0; h < kMV; h++) d[h] = v.d[h];
-    if (__builtin_amdgcn_ballot_w64(exact) != 0ull) q4m_two_loop<true, TAIL>(q, (gcd2_t)hS, (gcd2_t)hR, npad, m, n, l, bound, ne, exact, ys / yy, d);
-    else q4m_two_loop<false, TAIL>(q, (gcd2_t)hS, (gcd2_t)hR, npad, m, n, l, bound, ne, exact, ys / yy, d);
-#pragma unroll
-    for (int h = 0; h < kMV; h++) v.d[h] = 16 * h + l < n ? d[h] : 0.0;
-    if (l == 0) {
-      q.ist[iEND] = ne;
-      q.ist[iBOUND] = bound;
-      long long hs = ((long long)q.ist[iHISTHI] << 32) | (unsigned int)q.ist[iHISTLO];
-      hs += bound;
-      q.ist[iHISTLO] = (int)(hs & 0xffffffffLL);
-      q.ist[iHISTHI] = (int)(hs >> 32);
-    }
-  }
-  if (l == 0) q.st[sSTEP] = 1.0; // lbfgs.hpp:743
-  pr.tick(8);
-  __threadfence_block();
-  const bool ok = q4m_begin_iteration<TAIL>(P, q, v, n, l);
-  if (l == 0) q.ist[iACTION] = ok ? kActEval : kActDone;
-  pr.tick(6);
-}
+};
 
-// solver state of a suspended trajectory <-> its record in DevBatch::state (solver_ref.hip's state_io layout)
-__device__ inline void q4m_state_io(const DevBatch &D, const Q4M &q, QVecM &v, int b, int l, bool save) {
-  const int n = D.L.n, npad = D.L.npad;
-  double *rec = D.state + (size_t)b * D.state_stride;
-  for (int h = 0; h < kMV; h++) {
-    const int e = 16 * h + l;
-    if (e >= n) {
-      if (!save) {
-        q.xs[e] = 0.0;
-        q.gs[e] = 0.0;
-        v.xp[h] = v.gp[h] = v.d[h] = 0.0;
-      }
-      continue;
-    }
-    if (save) {
-      rec[0 * npad + e] = q.xs[e];
-      rec[1 * npad + e] = v.xp[h];
-      rec[2 * npad + e] = q.gs[e];
-      rec[3 * npad + e] = v.gp[h];
-      rec[4 * npad + e] = v.d[h];
-    } else {
-      q.xs[e] = rec[0 * npad + e];
-      v.xp[h] = rec[1 * npad + e];
-      q.gs[e] = rec[2 * npad + e];
-      v.gp[h] = rec[3 * npad + e];
-      v.d[h] = rec[4 * npad + e];
-    }
-  }
-  double *r2 = rec + 5 * npad;
-  for (int w = l; w < sNUM; w += 16) {
-    if (save) r2[w] = q.st[w];
-    else q.st[w] = r2[w];
-  }
-  int *ri = reinterpret_cast<int *>(r2 + 24);
-  for (int w = l; w < iNUM; w += 16) {
-    if (save) ri[w] = q.ist[w];
-    else q.ist[w] = ri[w];
-  }
-}
-
-// ------------------------------------------------ the kernel (solver_ref4.hip's loop)
+// ------------------------------------------------ the kernel (source, slice, hand: as ref4_kernel's)
 template <bool FAST, int TAIL>
 __global__ void __launch_bounds__(256, 1)
     ref4m_kernel(const DevBatch *__restrict__ Dp, int mode, const double *__restrict__ tabs, const double *__restrict__ cor_t, double *__restrict__ scratch, int source,
@@ -981,7 +676,7 @@ __global__ void __launch_bounds__(256, 1)
   extern __shared__ double lds_raw[];
   const DevBatch &D = *Dp;
   const DevLayout &L = D.L;
-  const int tidb = threadIdx.x, Tb = blockDim.x, lane = tidb & 63, wv = tidb >> 6, W = Tb >> 6, row = lane >> 4, l = lane & 15;
+  const int tidb = threadIdx.x, Tb = blockDim.x, lane = tidb & 63, wv = tidb >> 6, row = lane >> 4, l = lane & 15;
   const int n = L.n, H = L.H, mem = D.P.mem_size;
   Q4M q;
   q4m_carve(q, reinterpret_cast<char *>(lds_raw) + q4m_shared_bytes(L) + (size_t)(wv * 4 + row) * q4m_team_bytes(mem), mem);
@@ -1011,50 +706,21 @@ __global__ void __launch_bounds__(256, 1)
   pr.on = false;
   pr.acc = nullptr;
   pr.last = 0;
-  QVecM v{};
-  int b = -1;
-  bool act = false, resumed = false;
-  long long tick0 = 0;
+  QuadVec<kMV> v{};
+  QuadRun r{-1, false, false, 0};
   int steps = 0;
 
   for (int pass = 0;; pass++) {
-    if (!act) {
-      int id = -1;
-      if (ring) {
-        for (int r = 0; r < 4; r++)
-          if (row == r && l == 0) id = ring_pop(D.qctl, D.queue, D.qcap);
-        id = __shfl(id, lane & 48);
-      } else if (pass == 0) {
-        id = ((int)blockIdx.x * W + wv) * 4 + row;
-        if (id >= D.B) id = -1;
+    if (!r.act && quad_take(D, q, v, r, mode, ring, force_exact_div, pass, pr)) {
+      for (int w = l; w < 12 * L.M; w += 16) {
+        const int s_ = w / 12, u = w - 12 * s_;
+        q.bnd[w] = u < 6 ? D.iniS[((size_t)r.b * L.M + s_) * 6 + u] : D.finS[((size_t)r.b * L.M + s_) * 6 + (u - 6)];
       }
-      if (id >= 0) {
-        b = id;
-        act = true;
-        resumed = ring && D.sflag[b] == 1;
-        if (resumed) {
-          q4m_state_io(D, q, v, b, l, false);
-        } else {
-          const double *xsrc = (mode == kModeSolve) ? D.x0 : D.x_in;
-          for (int h = 0; h < kMV; h++) {
-            const int e = 16 * h + l;
-            q.xs[e] = e < n ? xsrc[(size_t)b * n + e] : 0.0;
-            q.gs[e] = 0.0;
-            v.xp[h] = v.gp[h] = v.d[h] = 0.0;
-          }
-          q.ist[l] = (l == iSLOWDIV && force_exact_div) ? 1 : 0; // (iNUM == 16 lanes)
-        }
-        for (int w = l; w < 12 * L.M; w += 16) {
-          const int s_ = w / 12, u = w - 12 * s_;
-          q.bnd[w] = u < 6 ? D.iniS[((size_t)b * L.M + s_) * 6 + u] : D.finS[((size_t)b * L.M + s_) * 6 + (u - 6)];
-        }
-        tick0 = wall_clock64();
-        pr.start(D.prof != nullptr && mode == kModeSolve && l == 0, D.prof + (size_t)b * 12, resumed);
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-      }
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     }
-    if (__builtin_amdgcn_ballot_w64(act) == 0ull) break; // (uniform) this wave has nothing left to do
-    if (act) {
+    if (__builtin_amdgcn_ballot_w64(r.act) == 0ull) break; // (uniform) this wave has nothing left to do
+    if (r.act) {
+      const int b = r.b;
       const gcd_t cor = (gcd_t)(cor_t + (size_t)b * L.H * 4 * cpitch + l);
       const gd_t ovf = (gd_t)(scratch + (size_t)b * scratch_per_traj);
       const double f = q4m_eval<FAST>(D, q, tab, cor, cpitch, ovf, l, S, Nmax, pr);
@@ -1064,50 +730,12 @@ __global__ void __launch_bounds__(256, 1)
           if (e < n) D.g_out[(size_t)b * n + e] = q.gs[e];
         }
         if (l == 0) D.f_eval[b] = f;
-        act = false;
+        r.act = false;
       } else {
-        const gd_t hS = (gd_t)(D.histS + (size_t)b * mem * L.npad * 2);
-        const gd_t hR = (gd_t)(D.histR + (size_t)b * mem * 2);
-        q4m_advance<TAIL>(D, q, v, f, hS, hR, l, pr);
+        const Q4MShape<TAIL> sh{(gd_t)(D.histS + (size_t)b * mem * L.npad * 2), (gd_t)(D.histR + (size_t)b * mem * 2), L.npad};
+        quad_advance(D, sh, q, v, f, l, pr);
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-        if (q.ist[iACTION] == kActDone) { // the epilogue of solver_ref.hip
-          for (int h = 0; h < kMV; h++) {
-            const int e = 16 * h + l;
-            if (e < n) D.x_out[(size_t)b * n + e] = q.xs[e];
-          }
-          if (l == 0) {
-            const double fx = q.st[sFX];
-            const int ret = q.ist[iRET];
-            D.f_out[b] = fx;
-            D.status[b] = ret;
-            D.iters[b] = q.ist[iK];
-            D.evals[b] = q.ist[iEVALS];
-            D.hist_sum[b] = ((long long)q.ist[iHISTHI] << 32) | (unsigned int)q.ist[iHISTLO];
-            {
-              double *rec = reinterpret_cast<double *>(D.records + (size_t)16 * b); // the all-gather record
-              rec[0] = fx;
-              int *ri = reinterpret_cast<int *>(rec + 1);
-              ri[0] = ret;
-              ri[1] = q.ist[iK];
-            }
-            if (D.records_host != nullptr) { // (see device_types.h)
-              double *rh = reinterpret_cast<double *>(D.records_host + (size_t)16 * b);
-              rh[0] = fx;
-              int *rj = reinterpret_cast<int *>(rh + 1);
-              rj[0] = ret;
-              rj[1] = q.ist[iK];
-            }
-            D.ticks[b] = (resumed ? D.ticks[b] : 0) + (wall_clock64() - tick0); // time in service
-            int ok = (ret == 0 || ret == 1 || ret == 2 || ret == -1008 || ret == -1009) ? 1 : 0; // traj_optimizer.cpp:176-201
-            if (fx >= D.P.fail_cost) ok = 0;
-            D.success[b] = ok;
-            if (ring) {
-              D.sflag[b] = 2;
-              atomicSub(&D.qctl[3], 1u);
-            }
-          }
-          act = false;
-        }
+        if (q.ist[iACTION] == kActDone) quad_results<kMV>(D, q, r, ring);
       }
     }
     if (!ring) {
@@ -1115,21 +743,9 @@ __global__ void __launch_bounds__(256, 1)
       continue;
     }
     steps++;
-    if (slice > 0 && steps >= slice) { // (uniform) end of a slice: the wave's unfinished trajectories go back to the ring
+    if (slice > 0 && steps >= slice) { // (uniform)
       steps = 0;
-      const bool leave = hand > 0 && __hip_atomic_load(&D.qctl[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= (unsigned)hand;
-      if (act) {
-        q4m_state_io(D, q, v, b, l, true);
-        __threadfence();
-        if (l == 0) {
-          D.ticks[b] = (resumed ? D.ticks[b] : 0) + (wall_clock64() - tick0);
-          D.sflag[b] = 1;
-        }
-      }
-      for (int r = 0; r < 4; r++)
-        if (act && row == r && l == 0) ring_push(D.qctl, D.queue, D.qcap, b);
-      act = false;
-      if (leave) break;
+      if (quad_end_slice(D, q, v, r, hand)) break;
     }
   }
 }

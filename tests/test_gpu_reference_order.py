@@ -439,6 +439,41 @@ def test_quad_shape_with_gear_shifts_is_bit_identical(hiplib, oracle, monkeypatc
     h.close()
 
 
+@pytest.mark.parametrize("case,B", [("cfg2", 12), ("6-5-5", 10)])
+def test_quad_shape_with_gear_shifts_and_true_divisions_gives_the_same_bits(hiplib, oracle, monkeypatch, case, B):
+    """The recursion of the QUAD shape for several gear segments (solver_ref4m.hip: q4m_two_loop) with true divisions from the first
+    iteration on (DFTPAV_REF_EXACT_DIV=1), at n = 33 (BASELINE configs[1]: the one-element tail of the chain) and at n > 33 (6 + 5 + 5
+    pieces: the 48-step chain).  One persistent wave with slices of 11 evaluations: a suspended trajectory carries iSLOWDIV through its
+    record (quad_lbfgs.h: quad_state_io) into quad_advance's choice of the dividing recursion.  Every field of every solve equal to
+    the restatement's (oracle order 2), in which some trajectory of either batch stores a pair; the plan says which kernel ran."""
+    p = hiplib.default_params()
+    if case == "cfg2":
+        s = sc.baseline_config(2, B=B)
+    else:
+        pieces = [int(t) for t in case.split("-")]
+        sing = [1 if i % 2 == 0 else -1 for i in range(len(pieces))]
+        s = sc.make_scenario(pieces, sing, 9, 14, B, seed=4242 + len(pieces), n_obs=30)
+    s.apply_resolution(p)
+    want = oracle.solve_batch(p, s, nthreads=8, order=2)
+    assert (want["hist_sum"] > 0).any(), "no trajectory of the batch stores a pair: the recursion would not run"
+    monkeypatch.setenv("DFTPAV_REF_EXACT_DIV", "1")
+    monkeypatch.setenv("DFTPAV_REF_SHAPE", "quad")
+    monkeypatch.setenv("DFTPAV_REF_SLOTS", "1")
+    monkeypatch.setenv("DFTPAV_REF_SLICE", "11")
+    h, bt = _batch(hiplib, s, p)
+    import ctypes as C
+    fn = hiplib.lib().dftpav_debug_reference_plan
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong)]
+    out = (C.c_longlong * 8)()
+    assert fn(C.byref(s.layout.c_struct()), C.byref(p), 0, s.B, 256, out) == 0
+    assert int(out[1]) == 5, "the plan did not pick the QUAD shape for several segments"
+    r = bt.solve()
+    for k in ("final_cost", "x", "status", "iters", "evals", "hist_sum", "success"):
+        assert np.array_equal(r[k], want[k]), (case, k)
+    bt.close()
+    h.close()
+
+
 @pytest.mark.parametrize("shape", ["team", "wave", "quad"])
 def test_recursion_with_true_divisions_gives_the_same_bits(hiplib, oracle, monkeypatch, shape):
     """The two-loop recursion divides by the stored y . s of a pair through its stored reciprocal (Markstein's correctly rounded
