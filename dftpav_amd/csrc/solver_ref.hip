@@ -15,7 +15,9 @@
 //     gdC (12 entries), gdT and the cost is parked in a record, and chain lanes -- one per (piece, entry), one for gdT, one
 //     per cost -- add the records in the reference's sample -> vertex -> plane order;
 //   * lbfgs_optimize / line_search_lewisoverton (lbfgs.hpp:276-390, 440-751): sequential dot products (the products are
-//     formed by the lanes, the sum is one chain from the first element) and the plain two-loop recursion (:716-739);
+//     formed by the lanes, the sum is one chain from the first element) and the plain two-loop recursion (:716-739); the control
+//     between two evaluations is lbfgs_control.h's, stated once for every shape of this order (this file gives it LaneVec<CAP>
+//     and StridedVec, the QUAD kernels quad_lbfgs.h's QuadRowVec);
 //   * no fused multiply-add anywhere except inside a division by a stored reciprocal (div_by_rcp: equal to a / b on everything
 //     it has been compared on -- an empirical claim, see there; DFTPAV_REF_EXACT_DIV=1 divides); contraction is off for the file.
 //
@@ -54,6 +56,7 @@
 #endif
 
 #include "ref_order_common.h"
+#include "lbfgs_control.h"
 
 namespace dftpav {
 namespace reford {
@@ -1206,227 +1209,63 @@ __device__ DFTPAV_REF_TL_ATTR double two_loop(ldsd_t dot_buf_, ldsd_t alpha_buf_
   return dreg;
 }
 
-// Start of an outer iteration (lbfgs.hpp:559-574, 290-315): xp = x, gp = g, dginit = gp . d, first trial point
-template <int CAP>
-__device__ __forceinline__ bool begin_iteration(const DevParams &P, const Sm &sm, int n, int lane) {
-  double pr = 0.0;
-  if (lane < n) {
-    sm.xp[lane] = sm.x[lane];
-    const double gv = sm.g[lane];
-    sm.gp[lane] = gv;
-    pr = gv * sm.d[lane];
-  }
-  const double dginit = seq_sum<CAP>(pr, n, sm.dot, lane);
-  const double step = sm.st[sSTEP];
-  if (!(step > 0.0)) {
-    if (lane == 0) sm.ist[iRET] = -1006;
-    return false;
-  }
-  if (0.0 < dginit) {
-    if (lane == 0) sm.ist[iRET] = -1005;
-    return false;
-  }
-  if (lane == 0) {
-    sm.st[sFINIT] = sm.st[sFX];
-    sm.st[sDGINIT] = dginit;
-    sm.st[sDGTEST] = P.f_dec_coeff * dginit;
-    sm.st[sDSTEST] = P.s_curv_coeff * dginit;
-    sm.st[sMU] = 0.0;
-    sm.st[sNU] = P.max_step;
-    sm.st[sSTP] = step;
-    sm.ist[iCOUNT] = 0;
-    sm.ist[iBRACKT] = 0;
-    sm.ist[iTOUCHED] = 0;
-  }
-  if (lane < n) sm.x[lane] = sm.xp[lane] + step * sm.d[lane];
-  return true;
-}
-
-// Everything lbfgs_optimize does between two evaluations (lbfgs.hpp:524-745 with the line search of :312-389 unrolled into
-// it), on wave 0, one decision variable per lane (n <= 64); sets iACTION.
-template <int CAP>
-__device__ __forceinline__ void lbfgs_advance(const DevBatch &D, const Sm &sm, gd_t hS, gd_t hR, int lane, Prof &pr) {
-  const DevParams &P = D.P;
-  const int n = D.L.n, m = P.mem_size, npad = D.L.npad;
-  const double f = sm.st[sF];
-  int action = kActEval;
-  if (sm.ist[iPHASE] == 0) { // after the first evaluation: lbfgs.hpp:524-551
+// ------------------------------------------------ L-BFGS: the state machine is lbfgs_control.h's (lbfgs_advance), on wave 0
+// How its vector operations run here, the vectors in LDS either way -- same state, same scalars, same history layout.
+//
+// LaneVec<CAP>: one decision variable per lane (n <= 64), a sequential sum as the DPP chain (seq_sum<CAP>), max |v| across the wave.
+template <int CAP> struct LaneVec {
+  const Sm &sm;
+  gd_t hS, hR; // the trajectory's history: (s, y) interleaved per element as solver.hip stores them, at pitch npad; (ys, 1 / ys) per pair
+  int npad;
+  ldsd_t st;
+  ldsi_t ist;
+  __device__ __forceinline__ bool leader(int lane) const { return lane == 0; }
+  __device__ __forceinline__ void first_direction(int n, int lane, double &gmax, double &xmax, double &dd) {
     double gv = 0.0, xv = 0.0;
     if (lane < n) {
       gv = sm.g[lane];
       xv = sm.x[lane];
       sm.d[lane] = -gv;
     }
-    const double gmax = wave_max64(lane < n ? fabs(gv) : 0.0), xmax = wave_max64(lane < n ? fabs(xv) : 0.0);
-    const double dd = seq_sum<CAP>((-gv) * (-gv), n, sm.dot, lane);
-    if (lane == 0) {
-      sm.st[sFX] = f;
-      sm.st[sPF0] = f;
-      sm.ist[iEVALS] = 1;
-      sm.ist[iEND] = 0;
-      sm.ist[iBOUND] = 0;
-      sm.ist[iHISTLO] = 0;
-      sm.ist[iHISTHI] = 0;
-      sm.ist[iPHASE] = 1;
-    }
-    if (gmax / fmax(1.0, xmax) < P.g_epsilon) {
-      if (lane == 0) {
-        sm.ist[iRET] = 0;
-        sm.ist[iK] = 0;
-      }
-      action = kActDone;
-    } else {
-      if (lane == 0) {
-        sm.st[sSTEP] = 1.0 / sqrt(dd);
-        sm.ist[iK] = 1;
-      }
-      __threadfence_block();
-      if (!begin_iteration<CAP>(P, sm, n, lane)) action = kActDone;
-    }
-    if (lane == 0) sm.ist[iACTION] = action;
-    return;
+    gmax = wave_max64(lane < n ? fabs(gv) : 0.0), xmax = wave_max64(lane < n ? fabs(xv) : 0.0);
+    dd = seq_sum<CAP>((-gv) * (-gv), n, sm.dot, lane);
   }
-
-  // ---- after a line-search trial: lbfgs.hpp:317-389
-  const double fx = f;
-  const double finit = sm.st[sFINIT];
-  double stp = sm.st[sSTP];
-  const int count = sm.ist[iCOUNT] + 1;
-  int ls = 0;
-  bool decided = false;
-  const int evals_before = sm.ist[iEVALS];
-  __threadfence_block();
-  if (lane == 0) {
-    sm.st[sFX] = fx;
-    sm.ist[iEVALS] = evals_before + 1;
-    sm.ist[iCOUNT] = count;
+  __device__ __forceinline__ double save_point(int n, int lane) {
+    double pr = 0.0;
+    if (lane < n) {
+      sm.xp[lane] = sm.x[lane];
+      const double gv = sm.g[lane];
+      sm.gp[lane] = gv;
+      pr = gv * sm.d[lane];
+    }
+    return seq_sum<CAP>(pr, n, sm.dot, lane);
   }
-  if (isinf(fx) || isnan(fx)) {
-    ls = -1012;
-    decided = true;
-  } else if (P.past > 0 && fabs(finit - fx) / (fabs(finit) + 1.0) < P.delta / P.past) { // lbfgs.hpp:326-329
-    ls = count;
-    decided = true;
-  } else {
-    double mu = sm.st[sMU], nu = sm.st[sNU];
-    bool brackt = sm.ist[iBRACKT] != 0;
-    const int touched = sm.ist[iTOUCHED];
-    if (fx > finit + stp * sm.st[sDGTEST]) {
-      nu = stp;
-      brackt = true;
-    } else {
-      const double gs = seq_sum<CAP>(lane < n ? sm.g[lane] * sm.d[lane] : 0.0, n, sm.dot, lane);
-      if (gs < sm.st[sDSTEST]) {
-        mu = stp;
-      } else {
-        ls = count;
-        decided = true;
-      }
-    }
-    bool touch_now = false;
-    if (!decided) {
-      if (P.max_linesearch <= count) {
-        ls = -1009;
-        decided = true;
-      } else if (brackt && (nu - mu) < P.machine_prec * nu) {
-        ls = -1007;
-        decided = true;
-      } else {
-        if (brackt) stp = 0.5 * (mu + nu);
-        else stp *= 2.0;
-        if (stp < P.min_step) {
-          ls = -1011;
-          decided = true;
-        } else if (stp > P.max_step) {
-          if (touched) {
-            ls = -1010;
-            decided = true;
-          } else {
-            touch_now = true;
-            stp = P.max_step;
-          }
-        }
-      }
-    }
-    __threadfence_block();
-    if (lane == 0) {
-      sm.st[sMU] = mu;
-      sm.st[sNU] = nu;
-      sm.ist[iBRACKT] = brackt ? 1 : 0;
-      sm.st[sSTP] = stp;
-      if (touch_now) sm.ist[iTOUCHED] = 1;
-    }
-    if (!decided) {
-      if (lane < n) sm.x[lane] = sm.xp[lane] + stp * sm.d[lane];
-      if (lane == 0) sm.ist[iACTION] = kActEval;
-      pr.tick(6);
-      return;
-    }
+  __device__ __forceinline__ void trial_point(int n, int lane, double stp) {
+    if (lane < n) sm.x[lane] = sm.xp[lane] + stp * sm.d[lane];
   }
-  if (lane == 0) sm.st[sSTEP] = stp; // lbfgs.hpp:574 passes `step` by reference
-  if (ls < 0) { // lbfgs.hpp:604-611: x, g reverted; fx is not
+  __device__ __forceinline__ double slope(int n, int lane) { return seq_sum<CAP>(lane < n ? sm.g[lane] * sm.d[lane] : 0.0, n, sm.dot, lane); }
+  __device__ __forceinline__ void revert(int n, int lane) {
     if (lane < n) {
       sm.x[lane] = sm.xp[lane];
       sm.g[lane] = sm.gp[lane];
     }
-    if (lane == 0) {
-      sm.ist[iRET] = ls;
-      sm.ist[iACTION] = kActDone;
-    }
-    return;
   }
-
-  // ---- convergence / stopping tests (lbfgs.hpp:628-666)
-  int k = sm.ist[iK];
-  {
-    const double gmax = wave_max64(lane < n ? fabs(sm.g[lane]) : 0.0), xmax = wave_max64(lane < n ? fabs(sm.x[lane]) : 0.0);
-    const int kGoOn = 12345;
-    int ret = kGoOn;
-    if (gmax / fmax(1.0, xmax) < P.g_epsilon) {
-      ret = 0;
-    } else {
-      if (0 < P.past) {
-        const int slot = k % P.past;
-        const double pf = sm.st[sPF0 + slot];
-        __threadfence_block();
-        if (P.past <= k) {
-          const double rate = fabs(pf - fx) / fmax(1.0, fabs(fx));
-          if (rate < P.delta) ret = 1;
-        }
-        if (ret == kGoOn && lane == 0) sm.st[sPF0 + slot] = fx;
-      }
-      if (ret == kGoOn && P.max_iterations != 0 && P.max_iterations <= k) ret = -1008;
-    }
-    if (ret != kGoOn) {
-      if (lane == 0) {
-        sm.ist[iRET] = ret;
-        sm.ist[iACTION] = kActDone;
-      }
-      return;
-    }
+  __device__ __forceinline__ void absmax(int n, int lane, double &gmax, double &xmax) {
+    gmax = wave_max64(lane < n ? fabs(sm.g[lane]) : 0.0), xmax = wave_max64(lane < n ? fabs(sm.x[lane]) : 0.0);
   }
-  ++k;
-  pr.tick(6);
-  const int end = sm.ist[iEND];
-  int bound = sm.ist[iBOUND];
-  __threadfence_block();
-  if (lane == 0) sm.ist[iK] = k;
-
-  // ---- history update + two-loop recursion (lbfgs.hpp:676-740); (s, y) interleaved per element as solver.hip stores them
-  double sv = 0.0, yv = 0.0, gpv = 0.0;
-  if (lane < n) {
-    sv = sm.x[lane] - sm.xp[lane];
-    yv = sm.g[lane] - sm.gp[lane];
-    gpv = sm.gp[lane];
-    d2_t sy;
-    sy.x = sv;
-    sy.y = yv;
-    ((gd2_t)hS)[(size_t)end * npad + lane] = sy;
-    sm.d[lane] = -sm.g[lane];
-  }
-  // the four dot products of lbfgs.hpp:683-694, their chains side by side
-  double ys, yy, ss, gpgp;
-  {
+  __device__ __forceinline__ void new_pair(int m, int end, int n, int lane, double &ys, double &yy, double &ss, double &gpgp) {
+    double sv = 0.0, yv = 0.0, gpv = 0.0;
+    if (lane < n) {
+      sv = sm.x[lane] - sm.xp[lane];
+      yv = sm.g[lane] - sm.gp[lane];
+      gpv = sm.gp[lane];
+      d2_t sy;
+      sy.x = sv;
+      sy.y = yv;
+      ((gd2_t)hS)[(size_t)end * npad + lane] = sy;
+      sm.d[lane] = -sm.g[lane];
+    }
+    // the four dot products of lbfgs.hpp:683-694, their chains side by side
     if (lane < CAP) {
       sm.dot[lane] = yv * sv;
       sm.dot[CAP + lane] = yv * yv;
@@ -1444,52 +1283,29 @@ __device__ __forceinline__ void lbfgs_advance(const DevBatch &D, const Sm &sm, g
     }
     wave_lds_order();
     ys = a0; yy = a1; ss = a2; gpgp = a3;
-  }
-  if (lane == 0) {
-    d2_t yr;
-    yr.x = ys;
-    yr.y = 1.0 / ys;
-    ((gd2_t)hR)[end] = yr;
-    if (!rcp_route_ok(ys)) sm.ist[iSLOWDIV] = 1; // from here on the recursion divides (see div_by_rcp)
-  }
-  const double cau = ss * sqrt(gpgp) * P.cautious_factor;
-  pr.tick(7);
-  if (ys > cau) {
-    ++bound;
-    bound = m < bound ? m : bound;
-    const int ne = end + 1 == m ? 0 : end + 1;
-    __threadfence_block(); // lane 0's (ys, 1 / ys) of the newest pair is read by every lane below
-    double dreg = lane < n ? -sm.g[lane] : 0.0;
-    if (__builtin_expect(sm.ist[iSLOWDIV] != 0, 0)) // (uniform; lane 0 wrote it at most a fence ago)
-      dreg = two_loop<CAP, true>(sm.dot, sm.alpha, (gcd2_t)hS, (gcd2_t)hR, npad, m, n, lane, bound, ne, dreg, ys / yy);
-    else
-      dreg = two_loop<CAP, false>(sm.dot, sm.alpha, (gcd2_t)hS, (gcd2_t)hR, npad, m, n, lane, bound, ne, dreg, ys / yy);
-    if (lane < n) sm.d[lane] = dreg;
     if (lane == 0) {
-      sm.ist[iEND] = ne;
-      sm.ist[iBOUND] = bound;
-      long long hs = ((long long)sm.ist[iHISTHI] << 32) | (unsigned int)sm.ist[iHISTLO];
-      hs += bound;
-      sm.ist[iHISTLO] = (int)(hs & 0xffffffffLL);
-      sm.ist[iHISTHI] = (int)(hs >> 32);
+      d2_t yr;
+      yr.x = ys;
+      yr.y = 1.0 / ys;
+      ((gd2_t)hR)[end] = yr;
+      if (!rcp_route_ok(ys)) ist[iSLOWDIV] = 1; // from here on the recursion divides (see div_by_rcp)
     }
   }
-  if (lane == 0) sm.st[sSTEP] = 1.0; // lbfgs.hpp:743
-  pr.tick(8);
-  __threadfence_block();
-  const bool ok = begin_iteration<CAP>(P, sm, n, lane);
-  if (lane == 0) sm.ist[iACTION] = ok ? kActEval : kActDone;
-  pr.tick(6);
-}
+  __device__ __forceinline__ void two_loop(int m, int n, int lane, int bound, int ne, double sc0) {
+    double dreg = lane < n ? -sm.g[lane] : 0.0;
+    if (__builtin_expect(ist[iSLOWDIV] != 0, 0)) // (uniform; lane 0 wrote it at most a fence ago)
+      dreg = reford::two_loop<CAP, true>(sm.dot, sm.alpha, (gcd2_t)hS, (gcd2_t)hR, npad, m, n, lane, bound, ne, dreg, sc0);
+    else
+      dreg = reford::two_loop<CAP, false>(sm.dot, sm.alpha, (gcd2_t)hS, (gcd2_t)hR, npad, m, n, lane, bound, ne, dreg, sc0);
+    if (lane < n) sm.d[lane] = dreg;
+  }
+};
 
-
-// ------------------------------------------------ the same step for ANY number of variables (TEAM shape, n > 64)
-// lbfgs_advance keeps one decision variable per lane and chains a dot product through the lanes; a plan of more than 32 pieces
-// (traj_manager.cpp:543 sets no limit, lbfgs.hpp:512-513 none either) has more variables than a wave has lanes.  This is the slow,
-// plain form for those: the vectors live in LDS (they do anyway), a lane takes the elements lane, lane + 64, ..., and a sequential
-// sum is what it is in the reference -- one chain over the n products, read back from LDS by every lane (the same bits in each).
-// True divisions throughout.  Same state, same scalars, same history layout as lbfgs_advance: ring, slices and suspend / resume
-// are not used in this path (it runs in the TEAM shape only).
+// StridedVec: ANY number of variables (TEAM shape, n > 64).  A plan of more than 32 pieces (traj_manager.cpp:543 sets no limit,
+// lbfgs.hpp:512-513 none either) has more variables than a wave has lanes.  This is the slow, plain form for those: a lane takes the
+// elements lane, lane + 64, ..., and a sequential sum is what it is in the reference -- one chain over the n products, read back
+// from LDS by every lane (the same bits in each).  True divisions throughout (iSLOWDIV is never set), the plain recursion loops.
+// Ring, slices and suspend / resume are not used in this path (it runs in the TEAM shape only).
 __device__ __forceinline__ double gen_sum(ldsd_t buf, int n) { // 0.0 + buf[0] + buf[1] + ... (the products were written by this wave)
   wave_lds_order();
   double s_ = 0.0;
@@ -1497,210 +1313,52 @@ __device__ __forceinline__ double gen_sum(ldsd_t buf, int n) { // 0.0 + buf[0] +
   wave_lds_order();
   return s_;
 }
-__device__ __forceinline__ bool gen_begin_iteration(const DevParams &P, const Sm &sm, int n, int lane) {
-  for (int e = lane; e < n; e += 64) {
-    sm.xp[e] = sm.x[e];
-    const double gv = sm.g[e];
-    sm.gp[e] = gv;
-    sm.dot[e] = gv * sm.d[e];
-  }
-  const double dginit = gen_sum(sm.dot, n);
-  const double step = sm.st[sSTEP];
-  if (!(step > 0.0)) {
-    if (lane == 0) sm.ist[iRET] = -1006;
-    return false;
-  }
-  if (0.0 < dginit) {
-    if (lane == 0) sm.ist[iRET] = -1005;
-    return false;
-  }
-  if (lane == 0) {
-    sm.st[sFINIT] = sm.st[sFX];
-    sm.st[sDGINIT] = dginit;
-    sm.st[sDGTEST] = P.f_dec_coeff * dginit;
-    sm.st[sDSTEST] = P.s_curv_coeff * dginit;
-    sm.st[sMU] = 0.0;
-    sm.st[sNU] = P.max_step;
-    sm.st[sSTP] = step;
-    sm.ist[iCOUNT] = 0;
-    sm.ist[iBRACKT] = 0;
-    sm.ist[iTOUCHED] = 0;
-  }
-  for (int e = lane; e < n; e += 64) sm.x[e] = sm.xp[e] + step * sm.d[e];
-  return true;
-}
-__device__ __noinline__ void lbfgs_advance_generic(const DevBatch &D, const Sm &sm, gd_t hS, gd_t hR, int lane, Prof &pr) {
-  const DevParams &P = D.P;
-  const int n = D.L.n, m = P.mem_size, npad = D.L.npad;
-  const double f = sm.st[sF];
-  int action = kActEval;
-  auto vmax = [&](ldscd_t v) { // max |v[e]| (order-free)
+struct StridedVec {
+  const Sm &sm;
+  gd_t hS, hR;
+  int npad;
+  ldsd_t st;
+  ldsi_t ist;
+  __device__ __forceinline__ bool leader(int lane) const { return lane == 0; }
+  __device__ __forceinline__ double vmax(ldscd_t v, int n, int lane) const { // max |v[e]| (order-free)
     double mx = 0.0;
     for (int e = lane; e < n; e += 64) mx = fmax(mx, fabs(v[e]));
     return wave_max64(mx);
-  };
-  if (sm.ist[iPHASE] == 0) { // after the first evaluation: lbfgs.hpp:524-551
+  }
+  __device__ __forceinline__ void first_direction(int n, int lane, double &gmax, double &xmax, double &dd) {
     for (int e = lane; e < n; e += 64) {
       const double gv = sm.g[e];
       sm.d[e] = -gv;
       sm.dot[e] = (-gv) * (-gv);
     }
-    const double gmax = vmax(sm.g), xmax = vmax(sm.x);
-    const double dd = gen_sum(sm.dot, n);
-    if (lane == 0) {
-      sm.st[sFX] = f;
-      sm.st[sPF0] = f;
-      sm.ist[iEVALS] = 1;
-      sm.ist[iEND] = 0;
-      sm.ist[iBOUND] = 0;
-      sm.ist[iHISTLO] = 0;
-      sm.ist[iHISTHI] = 0;
-      sm.ist[iPHASE] = 1;
-    }
-    if (gmax / fmax(1.0, xmax) < P.g_epsilon) {
-      if (lane == 0) {
-        sm.ist[iRET] = 0;
-        sm.ist[iK] = 0;
-      }
-      action = kActDone;
-    } else {
-      if (lane == 0) {
-        sm.st[sSTEP] = 1.0 / sqrt(dd);
-        sm.ist[iK] = 1;
-      }
-      __threadfence_block();
-      if (!gen_begin_iteration(P, sm, n, lane)) action = kActDone;
-    }
-    if (lane == 0) sm.ist[iACTION] = action;
-    return;
+    gmax = vmax(sm.g, n, lane), xmax = vmax(sm.x, n, lane);
+    dd = gen_sum(sm.dot, n);
   }
-  // ---- after a line-search trial: lbfgs.hpp:317-389
-  const double fx = f;
-  const double finit = sm.st[sFINIT];
-  double stp = sm.st[sSTP];
-  const int count = sm.ist[iCOUNT] + 1;
-  int ls = 0;
-  bool decided = false;
-  const int evals_before = sm.ist[iEVALS];
-  __threadfence_block();
-  if (lane == 0) {
-    sm.st[sFX] = fx;
-    sm.ist[iEVALS] = evals_before + 1;
-    sm.ist[iCOUNT] = count;
+  __device__ __forceinline__ double save_point(int n, int lane) {
+    for (int e = lane; e < n; e += 64) {
+      sm.xp[e] = sm.x[e];
+      const double gv = sm.g[e];
+      sm.gp[e] = gv;
+      sm.dot[e] = gv * sm.d[e];
+    }
+    return gen_sum(sm.dot, n);
   }
-  if (isinf(fx) || isnan(fx)) {
-    ls = -1012;
-    decided = true;
-  } else if (P.past > 0 && fabs(finit - fx) / (fabs(finit) + 1.0) < P.delta / P.past) { // lbfgs.hpp:326-329
-    ls = count;
-    decided = true;
-  } else {
-    double mu = sm.st[sMU], nu = sm.st[sNU];
-    bool brackt = sm.ist[iBRACKT] != 0;
-    const int touched = sm.ist[iTOUCHED];
-    if (fx > finit + stp * sm.st[sDGTEST]) {
-      nu = stp;
-      brackt = true;
-    } else {
-      for (int e = lane; e < n; e += 64) sm.dot[e] = sm.g[e] * sm.d[e];
-      const double gs = gen_sum(sm.dot, n);
-      if (gs < sm.st[sDSTEST]) {
-        mu = stp;
-      } else {
-        ls = count;
-        decided = true;
-      }
-    }
-    bool touch_now = false;
-    if (!decided) {
-      if (P.max_linesearch <= count) {
-        ls = -1009;
-        decided = true;
-      } else if (brackt && (nu - mu) < P.machine_prec * nu) {
-        ls = -1007;
-        decided = true;
-      } else {
-        if (brackt) stp = 0.5 * (mu + nu);
-        else stp *= 2.0;
-        if (stp < P.min_step) {
-          ls = -1011;
-          decided = true;
-        } else if (stp > P.max_step) {
-          if (touched) {
-            ls = -1010;
-            decided = true;
-          } else {
-            touch_now = true;
-            stp = P.max_step;
-          }
-        }
-      }
-    }
-    __threadfence_block();
-    if (lane == 0) {
-      sm.st[sMU] = mu;
-      sm.st[sNU] = nu;
-      sm.ist[iBRACKT] = brackt ? 1 : 0;
-      sm.st[sSTP] = stp;
-      if (touch_now) sm.ist[iTOUCHED] = 1;
-    }
-    if (!decided) {
-      for (int e = lane; e < n; e += 64) sm.x[e] = sm.xp[e] + stp * sm.d[e];
-      if (lane == 0) sm.ist[iACTION] = kActEval;
-      pr.tick(6);
-      return;
-    }
+  __device__ __forceinline__ void trial_point(int n, int lane, double stp) {
+    for (int e = lane; e < n; e += 64) sm.x[e] = sm.xp[e] + stp * sm.d[e];
   }
-  if (lane == 0) sm.st[sSTEP] = stp; // lbfgs.hpp:574 passes `step` by reference
-  if (ls < 0) { // lbfgs.hpp:604-611: x, g reverted; fx is not
+  __device__ __forceinline__ double slope(int n, int lane) {
+    for (int e = lane; e < n; e += 64) sm.dot[e] = sm.g[e] * sm.d[e];
+    return gen_sum(sm.dot, n);
+  }
+  __device__ __forceinline__ void revert(int n, int lane) {
     for (int e = lane; e < n; e += 64) {
       sm.x[e] = sm.xp[e];
       sm.g[e] = sm.gp[e];
     }
-    if (lane == 0) {
-      sm.ist[iRET] = ls;
-      sm.ist[iACTION] = kActDone;
-    }
-    return;
   }
-  // ---- convergence / stopping tests (lbfgs.hpp:628-666)
-  int k = sm.ist[iK];
-  {
-    const double gmax = vmax(sm.g), xmax = vmax(sm.x);
-    const int kGoOn = 12345;
-    int ret = kGoOn;
-    if (gmax / fmax(1.0, xmax) < P.g_epsilon) {
-      ret = 0;
-    } else {
-      if (0 < P.past) {
-        const int slot = k % P.past;
-        const double pf = sm.st[sPF0 + slot];
-        __threadfence_block();
-        if (P.past <= k) {
-          const double rate = fabs(pf - fx) / fmax(1.0, fabs(fx));
-          if (rate < P.delta) ret = 1;
-        }
-        if (ret == kGoOn && lane == 0) sm.st[sPF0 + slot] = fx;
-      }
-      if (ret == kGoOn && P.max_iterations != 0 && P.max_iterations <= k) ret = -1008;
-    }
-    if (ret != kGoOn) {
-      if (lane == 0) {
-        sm.ist[iRET] = ret;
-        sm.ist[iACTION] = kActDone;
-      }
-      return;
-    }
-  }
-  ++k;
-  pr.tick(6);
-  const int end = sm.ist[iEND];
-  int bound = sm.ist[iBOUND];
-  __threadfence_block();
-  if (lane == 0) sm.ist[iK] = k;
-  // ---- history update (lbfgs.hpp:676-694): s = x - xp, y = g - gp, the four dot products
-  double ys, yy, ss, gpgp;
-  {
+  __device__ __forceinline__ void absmax(int n, int lane, double &gmax, double &xmax) { gmax = vmax(sm.g, n, lane), xmax = vmax(sm.x, n, lane); }
+  // lbfgs.hpp:676-694: s = x - xp, y = g - gp, the four dot products
+  __device__ __forceinline__ void new_pair(int m, int end, int n, int lane, double &ys, double &yy, double &ss, double &gpgp) {
     for (int e = lane; e < n; e += 64) {
       const double sv = sm.x[e] - sm.xp[e], yv = sm.g[e] - sm.gp[e];
       d2_t sy;
@@ -1723,20 +1381,15 @@ __device__ __noinline__ void lbfgs_advance_generic(const DevBatch &D, const Sm &
     ss = gen_sum(sm.dot, n);
     for (int e = lane; e < n; e += 64) sm.dot[e] = sm.gp[e] * sm.gp[e];
     gpgp = gen_sum(sm.dot, n);
+    if (lane == 0) {
+      d2_t yr;
+      yr.x = ys;
+      yr.y = 1.0 / ys;
+      ((gd2_t)hR)[end] = yr;
+    }
   }
-  if (lane == 0) {
-    d2_t yr;
-    yr.x = ys;
-    yr.y = 1.0 / ys;
-    ((gd2_t)hR)[end] = yr;
-  }
-  const double cau = ss * sqrt(gpgp) * P.cautious_factor;
-  pr.tick(7);
-  if (ys > cau) { // ---- the two-loop recursion (lbfgs.hpp:716-739), plain
-    ++bound;
-    bound = m < bound ? m : bound;
-    const int ne = end + 1 == m ? 0 : end + 1;
-    __threadfence_block(); // the newest pair's row and y . s are read back below
+  // the two-loop recursion (lbfgs.hpp:716-739), plain
+  __device__ __forceinline__ void two_loop(int m, int n, int lane, int bound, int ne, double sc0) {
     const gcd2_t cS = (gcd2_t)hS, cR = (gcd2_t)hR;
     int j = ne;
     for (int i = 0; i < bound; i++) {
@@ -1747,7 +1400,6 @@ __device__ __noinline__ void lbfgs_advance_generic(const DevBatch &D, const Sm &
       const double na = -a;
       for (int e = lane; e < n; e += 64) sm.d[e] = sm.d[e] + na * cS[(size_t)j * npad + e].y; // d += (-alpha) * lm_y.col(j)
     }
-    const double sc0 = ys / yy;
     for (int e = lane; e < n; e += 64) sm.d[e] = sm.d[e] * sc0;
     wave_lds_order();
     for (int i = 0; i < bound; i++) {
@@ -1757,21 +1409,12 @@ __device__ __noinline__ void lbfgs_advance_generic(const DevBatch &D, const Sm &
       for (int e = lane; e < n; e += 64) sm.d[e] = sm.d[e] + cf * cS[(size_t)j * npad + e].x; // d += (alpha - beta) * lm_s.col(j)
       j = j == m - 1 ? 0 : j + 1;
     }
-    if (lane == 0) {
-      sm.ist[iEND] = ne;
-      sm.ist[iBOUND] = bound;
-      long long hs = ((long long)sm.ist[iHISTHI] << 32) | (unsigned int)sm.ist[iHISTLO];
-      hs += bound;
-      sm.ist[iHISTLO] = (int)(hs & 0xffffffffLL);
-      sm.ist[iHISTHI] = (int)(hs >> 32);
-    }
   }
-  if (lane == 0) sm.st[sSTEP] = 1.0; // lbfgs.hpp:743
-  pr.tick(8);
-  __threadfence_block();
-  const bool ok = gen_begin_iteration(P, sm, n, lane);
-  if (lane == 0) sm.ist[iACTION] = ok ? kActEval : kActDone;
-  pr.tick(6);
+};
+// the state machine over StridedVec, out of line in the GEN kernels
+__device__ __noinline__ void lbfgs_advance_strided(const DevBatch &D, const Sm &sm, gd_t hS, gd_t hR, int lane, Prof &pr) {
+  StridedVec v{sm, hS, hR, D.L.npad, sm.st, sm.ist};
+  lbfgs_advance(D, v, sm.st[sF], lane, pr);
 }
 
 // ------------------------------------------------ the kernel
@@ -1807,7 +1450,7 @@ __device__ inline void state_io(const DevBatch &D, const Sm &sm, int b, int lane
 // runs each for `slice` iterations and pushes it back unfinished.
 // Registers: 256 per lane (two waves per SIMD) for the kernels that fit them -- a second trajectory fills the issue slots the
 // dependent chains of the first leave empty; the wide (n > 32) and the moving-obstacle kernels take 512.
-// GEN (TEAM shape only): more variables than a wave has lanes (lbfgs_advance_generic) and / or more than five half-planes per point
+// GEN (TEAM shape only): more variables than a wave has lanes (StridedVec) and / or more than five half-planes per point
 // (twelve plane slots per point, the 64-bit test mask)
 template <int CAP, bool SUR, bool WAVE, bool GEN = false>
 __global__ void __launch_bounds__((WAVE && CAP <= kNarrowCap && !SUR) ? 512 : 256, (!WAVE && CAP <= 32 && !SUR) ? 2 : 1)
@@ -1916,8 +1559,12 @@ __global__ void __launch_bounds__((WAVE && CAP <= kNarrowCap && !SUR) ? 512 : 25
         return;
       }
       if (tid < 64) {
-        if constexpr (GEN) lbfgs_advance_generic(D, sm, hS, hR, lane, pr);
-        else lbfgs_advance<CAP>(D, sm, hS, hR, lane, pr);
+        if constexpr (GEN) {
+          lbfgs_advance_strided(D, sm, hS, hR, lane, pr);
+        } else {
+          LaneVec<CAP> v{sm, hS, hR, L.npad, sm.st, sm.ist};
+          lbfgs_advance(D, v, sm.st[sF], lane, pr);
+        }
       }
       team_sync<WAVE>();
       if (sm.ist[iACTION] == kActDone) break;
@@ -1961,7 +1608,7 @@ QuadKernel ref4m_kernel_for(bool fast, bool tail1);   // solver_ref4m.hip
 #if DFTPAV_REF_PART != 2
 // what the layout must satisfy for the reference-order kernel (solver_ref.hip header)
 bool reference_order_supported(const DevLayout &L, const DevParams &P, int S) {
-  if (L.M < 1 || L.n > 256 || L.Npts >= (1 << 25)) return false; // (n > 64: the plain L-BFGS step of lbfgs_advance_generic, TEAM shape; its sums use the 256-double buffer)
+  if (L.M < 1 || L.n > 256 || L.Npts >= (1 << 25)) return false; // (n > 64: the plain vector operations of StridedVec, TEAM shape; its sums use the 256-double buffer)
   if (L.H < 1 || L.H > 12) return false; // (H > 5: the generic TEAM kernel with twelve plane slots per point; rectangles: H = 4)
   if (S < 0 || 5 * L.H + S + 4 > 64) return false; // the mask of a point's active terms has 64 bits
   for (int i = 0; i < L.M; i++)

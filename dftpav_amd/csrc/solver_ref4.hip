@@ -26,8 +26,8 @@
 //     batch at some 7 k cycles each (profiles/dense_list_phases.txt);
 //   * the corridor is read from a copy laid out [component][j][piece]: the 16 lanes of a row read 128 contiguous bytes; a batch whose
 //     corridors are all rectangles (q4_rect_check_kernel) reads a copy of 10 doubles per point instead of 16 (RECT, below);
-//   * lbfgs_optimize / line_search_lewisoverton (lbfgs.hpp:276-390, 440-751): solver_ref.hip's lbfgs_advance, per row (quad_lbfgs.h:
-//     the state machine, the record of a suspended trajectory and the shape-free pieces of the loop, shared with solver_ref4m.hip;
+//   * lbfgs_optimize / line_search_lewisoverton (lbfgs.hpp:276-390, 440-751): lbfgs_control.h's lbfgs_advance, per row (quad_lbfgs.h:
+//     the row's vector operations under it, the record of a suspended trajectory and the shape-free pieces of the loop, shared with solver_ref4m.hip;
 //     this file: Q4Shape, the recursion and the mirror of the ring's ends); a vector of
 //     n <= 32 variables is two registers per lane (elements l and 16 + l), a sequential dot product is the 32-step DPP chain --
 //     each row chains its own sixteen lanes, no permlane swap -- and the two-loop recursion (:716-739) runs the four rows' history
@@ -805,7 +805,7 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
   return total_smcost + total_timecost + penalty_cost;
 }
 
-// ------------------------------------------------ L-BFGS, per row: the state machine is quad_lbfgs.h's; the recursion is this file's
+// ------------------------------------------------ L-BFGS, per row: the state machine is lbfgs_control.h's; the recursion is this file's
 
 // The two-loop recursion (lbfgs.hpp:716-739) over `bound` stored pairs of this row's trajectory, the newest in slot ne - 1;
 // d = -g on entry (elements from n on: 0.0).  The four rows run their steps in the same instructions; bound, the ring position
@@ -830,7 +830,7 @@ template <bool Y3> struct QBlk {
 typedef double __attribute__((ext_vector_type(2))) qd2_t;
 
 // 0.0 + p[0] + ... + p[n-1] in the recursion: row_sum32 without its selects.  The elements from n on of d are +-0.0 wherever this is
-// called (quad_lbfgs.h: quad_state_io, quad_take and quad_advance set them to 0.0, and a step adds coefficient * 0.0 to them: the
+// called (quad_lbfgs.h: quad_state_io, quad_take and QuadRowVec set them to 0.0, and a step adds coefficient * 0.0 to them: the
 // elements from n on of every stored s and y are +0.0 -- the buffers are cleared when they are allocated and no lane >= n stores),
 // so their products are +-0.0 as long as the coefficients are finite.  The chain starts from +0.0, and a sum rounded to nearest is
 // -0.0 only if both operands are: the accumulator is never -0.0, and adding +0.0 or -0.0 leaves it as it is -- what row_sum32's
@@ -970,7 +970,7 @@ __device__ __forceinline__ void q4_store_pair(gd_t hS, gd_t hM, int m, int end, 
   if (end >= m - kQB) ((gd2_t)hM)[(end - (m - kQB)) * kQNpad + e] = v;
 }
 
-// What quad_lbfgs.h's state machine needs to know of this kernel: a vector in two registers, the 32-step chain, a pair stored to
+// What quad_lbfgs.h's QuadRowVec needs to know of this kernel: a vector in two registers, the 32-step chain, a pair stored to
 // the ring and to the mirror, the recursion above.  hS, hM, hR: the history of the row's trajectory.
 struct Q4Shape {
   static constexpr int NV = 2;
@@ -1045,7 +1045,8 @@ __global__ void __launch_bounds__(256, DFTPAV_Q4_WAVES_PER_EU)
       } else {
         const Q4Shape sh{(gd_t)(D.histS + (size_t)b * mem * kQNpad * 2), (gd_t)(D.histM + (size_t)b * kQuadMirrorRows * kQNpad * 2),
                          (gd_t)(D.histR + (size_t)b * mem * 2)};
-        quad_advance(D, sh, q, v, f, l, pr);
+        QuadRowVec<Q4Shape> rv(sh, q, v);
+        lbfgs_advance(D, rv, f, l, pr);
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         if (q.ist[iACTION] == kActDone) quad_results<2>(D, q, r, ring);
       }

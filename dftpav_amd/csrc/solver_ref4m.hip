@@ -15,8 +15,8 @@
 //   * the per-segment chains (gdT, energy, the parked terms' shares) are formed per segment with the other segments' lanes masked to
 //     -0.0; the gradients of a junction's position and angle come from two neighbouring lanes (the last piece of one segment, the
 //     first of the next: one DPP step).
-// What is NOT here: the L-BFGS state machine, the record of a suspended trajectory and the shape-free pieces of the persistent loop
-// are quad_lbfgs.h's, the ones ref4_kernel runs; this file gives them Q4MShape<TAIL> (three registers, row_sum48, q4m_two_loop).
+// What is NOT here: the L-BFGS state machine (lbfgs_control.h), the row's vector operations under it, the record of a suspended
+// trajectory and the shape-free pieces of the persistent loop (quad_lbfgs.h), the ones ref4_kernel runs; this file gives them Q4MShape<TAIL> (three registers, row_sum48, q4m_two_loop).
 // Same bits as the TEAM / WAVE shapes and the restatement with correctly rounded cos / sin (oracle order 2).
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -650,7 +650,7 @@ __device__ __forceinline__ void q4m_two_loop(const Q4M &q, gcd2_t hS, gcd2_t hR,
   }
 }
 
-// What quad_lbfgs.h's state machine needs to know of this kernel: a vector in three registers, the 48-step chain (TAIL: row_sum48),
+// What quad_lbfgs.h's QuadRowVec needs to know of this kernel: a vector in three registers, the 48-step chain (TAIL: row_sum48),
 // a pair stored to the ring at pitch npad, the recursion above.  hS, hR: the history of the row's trajectory.
 template <int TAIL> struct Q4MShape {
   static constexpr int NV = kMV;
@@ -733,7 +733,8 @@ __global__ void __launch_bounds__(256, 1)
         r.act = false;
       } else {
         const Q4MShape<TAIL> sh{(gd_t)(D.histS + (size_t)b * mem * L.npad * 2), (gd_t)(D.histR + (size_t)b * mem * 2), L.npad};
-        quad_advance(D, sh, q, v, f, l, pr);
+        QuadRowVec<Q4MShape<TAIL>> rv(sh, q, v);
+        lbfgs_advance(D, rv, f, l, pr);
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         if (q.ist[iACTION] == kActDone) quad_results<kMV>(D, q, r, ring);
       }

@@ -34,7 +34,7 @@ REGIONS = {
     "dynamic_pair_math": "traj_math.h",
     "ref_eval": "solver_ref.hip",
     "surround_terms": "solver_ref.hip",
-    "lbfgs_advance": None,
+    "lbfgs_advance": None,  # solver.hip's own; the reference order's: lbfgs_control.h
 }
 
 
@@ -112,7 +112,7 @@ def main():
     p = subprocess.run([LLVM + "/llvm-symbolizer", "--obj=" + elf, "--inlines", "--output-style=JSON"], input="\n".join("0x%x" % a for a in addrs) + "\n",
                        capture_output=True, text=True, check=True)
     syms = [json.loads(ln) for ln in p.stdout.splitlines() if ln.strip()]
-    heads = {f: headings(os.path.join(CSRC, f)) for f in ("solver.hip", "solver_ref.hip", "traj_math.h")}
+    heads = {f: headings(os.path.join(CSRC, f)) for f in ("solver.hip", "solver_ref.hip", "traj_math.h", "lbfgs_control.h")}
 
     def region(fname, line):
         hs = heads.get(os.path.basename(fname), [])

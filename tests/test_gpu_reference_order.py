@@ -444,7 +444,7 @@ def test_quad_shape_with_gear_shifts_and_true_divisions_gives_the_same_bits(hipl
     """The recursion of the QUAD shape for several gear segments (solver_ref4m.hip: q4m_two_loop) with true divisions from the first
     iteration on (DFTPAV_REF_EXACT_DIV=1), at n = 33 (BASELINE configs[1]: the one-element tail of the chain) and at n > 33 (6 + 5 + 5
     pieces: the 48-step chain).  One persistent wave with slices of 11 evaluations: a suspended trajectory carries iSLOWDIV through its
-    record (quad_lbfgs.h: quad_state_io) into quad_advance's choice of the dividing recursion.  Every field of every solve equal to
+    record (quad_lbfgs.h: quad_state_io) into QuadRowVec's choice of the dividing recursion.  Every field of every solve equal to
     the restatement's (oracle order 2), in which some trajectory of either batch stores a pair; the plan says which kernel ran."""
     p = hiplib.default_params()
     if case == "cfg2":
@@ -666,7 +666,7 @@ def _extra_planes(base, H):
 def test_beyond_a_wave_of_variables_and_five_half_planes(hiplib, oracle, case):
     """What the reference accepts and the fast kernels do not -- more decision variables than a wave has lanes (N_i = max(round(dur / 1.0),
     2) is unbounded, traj_manager.cpp:543; lbfgs.hpp:512-513 sizes its history for any n) and more than four or five half-planes per point
-    (H is the column count of hPoly, traj_optimizer.cpp:592-622) -- runs in the generic TEAM kernel (solver_ref.hip: lbfgs_advance_generic,
+    (H is the column count of hPoly, traj_optimizer.cpp:592-622) -- runs in the generic TEAM kernel (solver_ref.hip: StridedVec,
     twelve plane slots): every evaluation and every whole solve bit-equal to the restatement."""
     p = hiplib.default_params()
     order = 0
