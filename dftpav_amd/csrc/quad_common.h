@@ -1,5 +1,6 @@
 // quad_common.h -- row-of-16-lanes primitives of the QUAD shapes of the reference order (solver_ref4.hip: one gear segment;
-// solver_ref4m.hip: several): a row of a wave is a trajectory, its sixteen lanes are its pieces.
+// solver_ref4m.hip: several): a row of a wave is a trajectory, its sixteen lanes are its pieces.  The substitution sweeps with the
+// rows in registers (quad_sweep and its two row updates), and the sizes of solver_ref4.hip's LDS.
 #pragma once
 #include "ref_order_common.h"
 
@@ -36,6 +37,101 @@ template <int CTRL> __device__ __forceinline__ double nb_dpp(double v) {
   return __hiloint2double(hi, lo);
 }
 
+// ---- BandedSystem::solve / solveAdj (poly_traj_utils.hpp:805-852) with the rows in registers: sweep Q of ref_order_common.h's packed
+// tables (0: forward substitution of solve, 1: its back substitution, 2, 3: solveAdj's), a block of six rows per piece.  A lane holds D
+// dimensions of a block: R[D rr + d] = natural row rr, dimension d; w[D r + d]: the six previous results in traversal order
+// (traversal row r is natural row r in the ascending sweeps, 5 - r in the descending ones); a finished row takes its place in w.
+// Traversal row r of a block of the ends (ce: the whole row, four coefficient pairs): every coefficient is tested, as the reference
+// does (`if (a != 0.0)`); the row's multiply-subtract pairs in the reference's order
+template <int Q, int D>
+__device__ __forceinline__ void sweep_row_end(int r, const v2d_t (&ce)[4], double (&w)[6 * D], double (&R)[6 * D]) {
+  constexpr bool DESC = Q == 1 || Q == 3, DIV = Q == 1 || Q == 2;
+  const int rr = DESC ? 5 - r : r;
+#pragma unroll
+  for (int d = 0; d < D; d++) {
+    double acc = R[D * rr + d];
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+      const double ck = (k & 1) ? ce[k >> 1].y : ce[k >> 1].x;
+      const double t = ck * w[D * ((r + k) % 6) + d];
+      acc = ck != 0.0 ? acc - t : acc;
+    }
+    if (DIV) acc = div_by_rcp(acc, ce[3].x, ce[3].y);
+    w[D * r + d] = acc;
+    R[D * rr + d] = acc;
+  }
+}
+// Traversal row r of an interior block (c: the lane's own block of the table): the non-zero terms only, no test
+template <int Q, int D>
+__device__ __forceinline__ void sweep_row_interior(int r, const v2d_t (&c)[pk_size(Q) / 2], double (&w)[6 * D], double (&R)[6 * D]) {
+  constexpr bool DESC = Q == 1 || Q == 3, DIV = Q == 1 || Q == 2;
+  auto at = [&](int o) { return (o & 1) ? c[o >> 1].y : c[o >> 1].x; };
+  const int rr = DESC ? 5 - r : r;
+#pragma unroll
+  for (int d = 0; d < D; d++) {
+    double acc = R[D * rr + d];
+#pragma unroll
+    for (int k = 0; k < 6; k++)
+      if (pk_mask(Q, r) & (1 << k)) acc = acc - at(pk_off(Q, r, k)) * w[D * ((r + k) % 6) + d];
+    if (DIV) acc = div_by_rcp(acc, at(pk_diag0(Q) + 2 * r), at(pk_diag0(Q) + 2 * r + 1));
+    w[D * r + d] = acc;
+    R[D * rr + d] = acc;
+  }
+}
+// One substitution sweep with a piece per lane, both dimensions (D = 2): bq[2 r + d] = row 6 lp + r, dimension d, of this lane's piece
+// (solver_ref.hip: sweep / rows_end / rows_pack -- the same rows, the same order of a row's updates).  Step s of the traversal belongs
+// to piece s (ascending sweeps) or N - 1 - s (descending) of every segment on the row, the segments side by side; the six previous
+// results it starts from are the finished rows of the previous step's piece, i.e. the neighbour lane's registers; a segment's first
+// block starts from zeros, whatever the neighbour lane (another segment's last piece) holds.
+// tabq: sweep Q of this lane's segment's tables (blocks in traversal order: whole rows at the two ends, the interior pattern's
+// coefficients in between); lp, N: the lane's piece inside its segment, the segment's pieces; piece: the lane has one at all; Nmax: the
+// largest segment's pieces.  (One segment, solver_ref4.hip: lp = l, piece = l < N, Nmax = N.)
+template <int Q>
+__device__ __forceinline__ void quad_sweep(ldscd_t tabq, double (&bq)[12], int lp, int N, bool piece, int Nmax) {
+  constexpr bool DESC = Q == 1 || Q == 3;
+  ldscd_t ip = tabq + 48;
+  // the table of this lane's own block (an interior block: pk_size(Q) doubles), read once, in front of the traversal
+  v2d_t c[pk_size(Q) / 2];
+  {
+    const int sl = DESC ? N - 1 - lp : lp; // the step this lane's piece is taken in
+    const int bi = sl >= 1 && sl <= N - 2 ? sl - 1 : 0;
+    const ldscv2_t a = (ldscv2_t)(ip + bi * pk_size(Q));
+    if (N > 2) {
+#pragma unroll
+      for (int u = 0; u < pk_size(Q) / 2; u++) c[u] = a[u];
+    } else {
+#pragma unroll
+      for (int u = 0; u < pk_size(Q) / 2; u++) c[u] = v2d_t{0.0, 0.0};
+    }
+  }
+#pragma unroll 1
+  for (int s = 0; s < Nmax; s++) {
+    const int p = DESC ? N - 1 - s : s;
+    double w[12];
+#pragma unroll
+    for (int r = 0; r < 6; r++)
+#pragma unroll
+      for (int d = 0; d < 2; d++) w[2 * r + d] = DESC ? nb_dpp<0x101>(bq[2 * (5 - r) + d]) : nb_dpp<0x111>(bq[2 * r + d]);
+    if (s == 0) { // (uniform) every segment's traversal starts from six zeros, whatever the neighbour lane holds
+#pragma unroll
+      for (int u = 0; u < 12; u++) w[u] = 0.0;
+    }
+    const bool mine = piece && s < N && lp == p;
+    if (mine && (s == 0 || s == N - 1)) { // a block of the ends, its table rows loaded row by row
+      const ldscv2_t a = (ldscv2_t)(s == 0 ? tabq : ip + (N - 2) * pk_size(Q));
+#pragma unroll
+      for (int r = 0; r < 6; r++) {
+        v2d_t ce[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) ce[u] = a[4 * r + u];
+        sweep_row_end<Q, 2>(r, ce, w, bq);
+      }
+    } else if (mine) { // an interior block
+#pragma unroll
+      for (int r = 0; r < 6; r++) sweep_row_interior<Q, 2>(r, c, w, bq);
+    }
+  }
+}
 
 // DENSE emission (round 6): the active terms the lanes of a wave find in the point loop are listed -- (owner lane, point, term, the
 // point's running offset s1, the half-plane of a corridor term) -- and evaluated kDense at a time, one per lane, by whichever lanes

@@ -1,6 +1,7 @@
 // ref_order_common.h -- what the reference-order kernels share (solver_ref.hip: TEAM / WAVE shapes; solver_ref4.hip: QUAD shape):
 // the address-space typedefs, div_by_rcp, the DPP helpers, the packed sweep tables, positiveSmoothedL1, the moving-obstacle
-// terms and the per-point tests / records (point_masks, point_emit) -- every expression in the order the reference executes it.
+// terms, the per-point tests / records (point_masks, point_emit) and the per-piece MINCO steps of the evaluation (virtual_to_real_T ...
+// duration_grad_ends) -- every expression in the order the reference executes it.
 // Moved out of solver_ref.hip unchanged (round 6).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -1081,6 +1082,70 @@ __device__ __forceinline__ mask_t point_terms(const DevParams &P, const double c
     point_emit(P, st, t, H, t0, cor, pitch, rec + (size_t)t * kRec);
   }
   return mask;
+}
+
+// ------------------------------------------------ the per-piece MINCO steps of costFunctionCallback, once for ref_eval and q4m_eval
+// (solver_ref4.hip's q4_eval keeps its own copy, see there).  An operand is whatever holds it there: an array in registers or a pointer into LDS (the template parameters say no more).
+// VirtualT2RealT (traj_optimizer.cpp:371-379)
+__device__ __forceinline__ double virtual_to_real_T(double vt, double mini_T) {
+  return vt > 0.0 ? ((0.5 * vt + 1.0) * vt + 1.0) + mini_T : 1.0 / ((0.5 * vt - 1.0) * vt + 1.0) + mini_T;
+}
+// gdVT2Rt of VirtualTGradCost (:405-419)
+__device__ __forceinline__ double virtual_T_grad_factor(double vt) {
+  double gdVT2Rt;
+  if (vt > 0) {
+    gdVT2Rt = vt + 1.0;
+  } else {
+    const double denSqrt = (0.5 * vt - 1.0) * vt + 1.0;
+    gdVT2Rt = (1.0 - vt) / (denSqrt * denSqrt);
+  }
+  return gdVT2Rt;
+}
+// a piece's six rows (both dimensions) times 1 / t^k of their row: c = b * tInv (poly_traj_utils.hpp:979-984), adj = gdC * tInv (:1038-1041)
+__device__ __forceinline__ void rows_times_tinv(const double (&v)[12], const double (&tI)[6], double (&out)[12]) {
+#pragma unroll
+  for (int u = 0; u < 12; u++) out[u] = v[u] * tI[u >> 1];
+}
+// initSmGradCost / getTrajJerkCost of one piece (poly_traj_utils.hpp:998-1035): its energy, what it adds to gdT, its rows of gdC.
+// c: the piece's coefficients; t: 1, t, .. t^5
+template <typename C, typename T, typename E, typename G>
+__device__ __forceinline__ void piece_jerk(C c, T t, E &pE, E &pG, G gc) {
+  const double n33 = c[6] * c[6] + c[7] * c[7], n44 = c[8] * c[8] + c[9] * c[9], n55 = c[10] * c[10] + c[11] * c[11];
+  const double d43 = c[8] * c[6] + c[9] * c[7], d53 = c[10] * c[6] + c[11] * c[7], d54 = c[10] * c[8] + c[11] * c[9];
+  pE = 36.0 * n33 * t[1] + 144.0 * d43 * t[2] + 192.0 * n44 * t[3] + 240.0 * d53 * t[3] + 720.0 * d54 * t[4] + 720.0 * n55 * t[5];
+  pG = 36.0 * n33 + 288.0 * d43 * t[1] + 576.0 * n44 * t[2] + 720.0 * d53 * t[2] + 2880.0 * d54 * t[3] + 3600.0 * n55 * t[4];
+#pragma unroll
+  for (int d = 0; d < 2; d++) {
+    const double c3 = c[6 + d], c4 = c[8 + d], c5 = c[10 + d];
+    gc[10 + d] = 240.0 * c3 * t[3] + 720.0 * c4 * t[4] + 1440.0 * c5 * t[5];
+    gc[8 + d] = 144.0 * c3 * t[2] + 384.0 * c4 * t[3] + 720.0 * c5 * t[4];
+    gc[6 + d] = 72.0 * c3 * t[1] + 144.0 * c4 * t[2] + 240.0 * c5 * t[3];
+    gc[d] = 0.0;
+    gc[2 + d] = 0.0;
+    gc[4 + d] = 0.0;
+  }
+}
+// what a piece adds to the duration gradient through tInv (calGrads_PT, poly_traj_utils.hpp:1054-1064): tInv: 1 / t^k; b: the piece's
+// rows of the solved system (b, not c)
+template <typename T, typename G, typename B>
+__device__ __forceinline__ double piece_gdtinv_sum(T tInv, G gdC, B b) {
+  const double gdtInv[6] = {0.0, -1.0 * tInv[2], -2.0 * tInv[3], -3.0 * tInv[4], -4.0 * tInv[5], -5.0 * tInv[5] * tInv[1]};
+  double acc = 0.0;
+#pragma unroll
+  for (int k = 0; k < 6; k++) {
+    const double gdcol = gdC[2 * k] * b[2 * k] + gdC[2 * k + 1] * b[2 * k + 1];
+    acc += gdtInv[k] * gdcol;
+  }
+  return acc;
+}
+// the head and tail terms of a segment's duration gradient (poly_traj_utils.hpp:1050-1053), in the order gdT receives them.
+// hv, tv: the head / tail state in force; ah, at: the adjoint rows of the segment's first / last piece
+template <typename V, typename A>
+__device__ __forceinline__ void duration_grad_ends(V hv, V tv, A ah, A at, double t1, double &h1, double &h2, double &g1, double &g2) {
+  h1 = hv[2] * ah[2] + hv[3] * ah[3];
+  h2 = (hv[4] * ah[4] + hv[5] * ah[5]) * 2.0 * t1;
+  g1 = tv[2] * at[8] + tv[3] * at[9];
+  g2 = (tv[4] * at[10] + tv[5] * at[11]) * 2.0 * t1;
 }
 
 // ---- the sequential sums as DPP chains (see solver_ref.hip: seq_sum_dpp): v_fmac_f64_dpp ... row_newbcast:K makes every lane of a

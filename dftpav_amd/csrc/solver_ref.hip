@@ -10,6 +10,9 @@
 //   * MinJerkOpt::generate / calGrads_PT: the banded forward / backward substitutions of BandedSystem::solve / solveAdj
 //     (poly_traj_utils.hpp:805-852) row by row, each row's updates in the reference's order (a row is the unit: its six
 //     multiply-subtract pairs are those the reference's column loops apply to it, in that order);
+//     the per-piece steps around them (VirtualT2RealT and its gradient factor, the jerk energy with its gdC / gdT parts, the gdtInv
+//     sum, the head / tail terms of the duration gradient) are ref_order_common.h's functions on operands in LDS, the ones the QUAD
+//     kernels call on registers; c = b * tInv and adj = gdC * tInv stay one element per lane here;
 //   * addPVAGradCost2CT (traj_optimizer.cpp:486-705): every constraint point is evaluated by its own lane, term by term
 //     (vertex x half-plane, velocity, acceleration, curvature left / right) exactly as written; what an ACTIVE term adds to
 //     gdC (12 entries), gdT and the cost is parked in a record, and chain lanes -- one per (piece, entry), one for gdT, one
@@ -236,7 +239,7 @@ __device__ DFTPAV_REF_EVAL_ATTR void ref_eval(const DevBatch &D, gcd_t cor_b, gd
   if (tid < M) {
     const int sg = tid;
     const double vt = x[L.x_tau0 + sg];
-    const double Tr = vt > 0.0 ? ((0.5 * vt + 1.0) * vt + 1.0) + P.mini_T : 1.0 / ((0.5 * vt - 1.0) * vt + 1.0) + P.mini_T;
+    const double Tr = virtual_to_real_T(vt, P.mini_T);
     int N = 0;
     for (int q = 0; q < M; q++) N = q == sg ? L.piece_nums[q] : N;
     const double t1 = Tr / N, t2 = t1 * t1, t3 = t2 * t1, t4 = t2 * t2, t5 = t4 * t1;
@@ -345,20 +348,7 @@ __device__ DFTPAV_REF_EVAL_ATTR void ref_eval(const DevBatch &D, gcd_t cor_b, gd
   for (int i = tid; i < Ntot; i += T) {
     ldscd_t c = sm.c + 12 * i;
     ldscd_t t = sm.seg + 16 * sm.pinfo[4 * i] + 2;
-    const double n33 = c[6] * c[6] + c[7] * c[7], n44 = c[8] * c[8] + c[9] * c[9], n55 = c[10] * c[10] + c[11] * c[11];
-    const double d43 = c[8] * c[6] + c[9] * c[7], d53 = c[10] * c[6] + c[11] * c[7], d54 = c[10] * c[8] + c[11] * c[9];
-    sm.pE[i] = 36.0 * n33 * t[1] + 144.0 * d43 * t[2] + 192.0 * n44 * t[3] + 240.0 * d53 * t[3] + 720.0 * d54 * t[4] + 720.0 * n55 * t[5];
-    sm.pG[i] = 36.0 * n33 + 288.0 * d43 * t[1] + 576.0 * n44 * t[2] + 720.0 * d53 * t[2] + 2880.0 * d54 * t[3] + 3600.0 * n55 * t[4];
-    ldsd_t gc = sm.gdC + 12 * i;
-    for (int d = 0; d < 2; d++) {
-      const double c3 = c[6 + d], c4 = c[8 + d], c5 = c[10 + d];
-      gc[10 + d] = 240.0 * c3 * t[3] + 720.0 * c4 * t[4] + 1440.0 * c5 * t[5];
-      gc[8 + d] = 144.0 * c3 * t[2] + 384.0 * c4 * t[3] + 720.0 * c5 * t[4];
-      gc[6 + d] = 72.0 * c3 * t[1] + 144.0 * c4 * t[2] + 240.0 * c5 * t[3];
-      gc[d] = 0.0;
-      gc[2 + d] = 0.0;
-      gc[4 + d] = 0.0;
-    }
+    piece_jerk(c, t, sm.pE[i], sm.pG[i], sm.gdC + 12 * i);
   }
   pr.tick(1);
   if (WAVE) {
@@ -927,14 +917,7 @@ __device__ DFTPAV_REF_EVAL_ATTR void ref_eval(const DevBatch &D, gcd_t cor_b, gd
   }
   for (int i = u2; i >= 0 && i < Ntot; i += (WAVE ? 64 : T - 64)) { // the per-piece chain-rule terms (they only need gdC and b)
     ldscd_t tInv = sm.seg + 16 * sm.pinfo[4 * i] + 8;
-    const double gdtInv[6] = {0.0, -1.0 * tInv[2], -2.0 * tInv[3], -3.0 * tInv[4], -4.0 * tInv[5], -5.0 * tInv[5] * tInv[1]};
-    double acc = 0.0;
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-      const double gdcol = sm.gdC[12 * i + 2 * k] * sm.b[12 * i + 2 * k] + sm.gdC[12 * i + 2 * k + 1] * sm.b[12 * i + 2 * k + 1];
-      acc += gdtInv[k] * gdcol;
-    }
-    sm.pA[i] = acc;
+    sm.pA[i] = piece_gdtinv_sum(tInv, (ldscd_t)(sm.gdC + 12 * i), (ldscd_t)(sm.b + 12 * i));
   }
   team_sync<WAVE>();
   pr.tick(4);
@@ -958,23 +941,16 @@ __device__ DFTPAV_REF_EVAL_ATTR void ref_eval(const DevBatch &D, gcd_t cor_b, gd
     }
     ldscd_t adj = sm.adj + 12 * p0;
     ldscd_t hv = sm.pva + 12 * sg, tv = hv + 6;
-    const int n6 = 6 * N;
     const double t1 = sm.seg[16 * sg + 3];
     double gdT = sm.segsum[gNUM * sg + gGDT];
-    gdT += hv[2] * adj[2 * 1] + hv[3] * adj[2 * 1 + 1];
-    gdT += (hv[4] * adj[2 * 2] + hv[5] * adj[2 * 2 + 1]) * 2.0 * t1;
-    gdT += tv[2] * adj[2 * (n6 - 2)] + tv[3] * adj[2 * (n6 - 2) + 1];
-    gdT += (tv[4] * adj[2 * (n6 - 1)] + tv[5] * adj[2 * (n6 - 1) + 1]) * 2.0 * t1;
+    double h1, h2, g1, g2;
+    duration_grad_ends(hv, tv, adj, adj + 12 * (N - 1), t1, h1, h2, g1, g2);
+    gdT += h1;
+    gdT += h2;
+    gdT += g1;
+    gdT += g2;
     for (int i = 0; i < N; i++) gdT += sm.pA[p0 + i];
-    const double VT = x[L.x_tau0 + sg];
-    double gdVT2Rt;
-    if (VT > 0) {
-      gdVT2Rt = VT + 1.0;
-    } else {
-      const double denSqrt = (0.5 * VT - 1.0) * VT + 1.0;
-      gdVT2Rt = (1.0 - VT) / (denSqrt * denSqrt);
-    }
-    g[L.x_tau0 + sg] = (gdT / N + P.wei_time) * gdVT2Rt;
+    g[L.x_tau0 + sg] = (gdT / N + P.wei_time) * virtual_T_grad_factor(x[L.x_tau0 + sg]);
   }
   if (u2 >= 0 && u2 < M - 1 && P.gear_opt) { // junction i: position and angle (traj_optimizer.cpp:307-320)
     const int i = u2;

@@ -12,7 +12,8 @@
 //   * BandedSystem::solve / solveAdj (poly_traj_utils.hpp:805-852): the row sweeps of solver_ref.hip, piece by piece -- at step s
 //     the lane that owns block s takes the six results of the previous block from its neighbour's registers (DPP row_shr / row_shl)
 //     and computes its own six rows, both dimensions side by side; the row's multiply-subtract pairs in the reference's order
-//     (16 pieces: the two dimensions of a piece on two lanes, six rows per step -- sweep4_split below);
+//     (quad_common.h: quad_sweep, the traversal solver_ref4m.hip runs too, and the two row updates sweep_row_end / sweep_row_interior;
+//     16 pieces: the two dimensions of a piece on two lanes, six rows per step -- sweep4_split below, over the same row updates);
 //   * addPVAGradCost2CT (traj_optimizer.cpp:486-705): lane l walks the K + 1 constraint points of ITS piece in order (the running
 //     s1 += step of :513 is a register), and what an active term adds to gdC goes straight into the lane's own gdC registers --
 //     the order a gdC entry receives its additions in is (point, term) order within the piece, which is all the reference's order
@@ -100,91 +101,7 @@ __device__ __forceinline__ double row_sum32(double p0, double p1, int n, int l) 
   if (n > 16) acc = row_chain16(acc, 16 + l < n ? p1 : -0.0); // (uniform)
   return acc;
 }
-// One substitution sweep over the 6 N rows of the band system (solver_ref.hip: sweep / rows_end / rows_pack -- the same rows, the
-// same order of a row's updates), the rows in registers: bq[2 r + d] = row 6 l + r, dimension d, of this lane's piece.  Step s of
-// the traversal belongs to piece s (ascending sweeps) or N - 1 - s (descending); the six previous results it starts from are the
-// finished rows of the previous step's piece, i.e. the neighbour lane's registers.  tab: this sweep's table (blocks in traversal
-// order: whole rows at the two ends, the interior pattern's coefficients in between).
-template <int Q>
-__device__ __forceinline__ void sweep4(ldscd_t tab, double (&bq)[12], int N, int l) {
-  constexpr bool DESC = Q == 1 || Q == 3, DIV = Q == 1 || Q == 2;
-  ldscd_t ip = tab + 48;
-  // the table of this lane's own block (an interior block: pk_size(Q) doubles), read once, in front of the traversal
-  v2d_t c[pk_size(Q) / 2];
-  {
-    const int sl = DESC ? N - 1 - l : l; // the step this lane's piece is taken in
-    const int bi = sl >= 1 && sl <= N - 2 ? sl - 1 : 0;
-    const ldscv2_t a = (ldscv2_t)(ip + bi * pk_size(Q));
-    if (N > 2) {
-#pragma unroll
-      for (int u = 0; u < pk_size(Q) / 2; u++) c[u] = a[u];
-    } else {
-#pragma unroll
-      for (int u = 0; u < pk_size(Q) / 2; u++) c[u] = v2d_t{0.0, 0.0};
-    }
-  }
-#pragma unroll 1
-  for (int s = 0; s < N; s++) {
-    const int p = DESC ? N - 1 - s : s;
-    // traversal row r of a block is natural row r (ascending) or 5 - r (descending) of the piece
-    double w[6][2];
-#pragma unroll
-    for (int r = 0; r < 6; r++)
-#pragma unroll
-      for (int d = 0; d < 2; d++) {
-        w[r][d] = DESC ? nb_dpp<0x101>(bq[2 * (5 - r) + d]) : nb_dpp<0x111>(bq[2 * r + d]);
-      }
-    if (s == 0 || s == N - 1) { // (uniform) a block of the ends: every coefficient is tested, as the reference does (`if (a != 0.0)`)
-      const ldscv2_t a = (ldscv2_t)(s == 0 ? tab : ip + (N - 2) * pk_size(Q));
-      if (s == 0) { // (uniform) the traversal starts from six zeros, whatever the neighbour holds
-#pragma unroll
-        for (int r = 0; r < 6; r++) w[r][0] = w[r][1] = 0.0;
-      }
-      if (l == p) {
-#pragma unroll
-        for (int r = 0; r < 6; r++) {
-          v2d_t ce[4];
-#pragma unroll
-          for (int u = 0; u < 4; u++) ce[u] = a[4 * r + u];
-          const int rr = DESC ? 5 - r : r;
-#pragma unroll
-          for (int d = 0; d < 2; d++) {
-            double acc = bq[2 * rr + d];
-#pragma unroll
-            for (int k = 0; k < 6; k++) {
-              const double ck = (k & 1) ? ce[k >> 1].y : ce[k >> 1].x;
-              const double t = ck * w[(r + k) % 6][d];
-              acc = ck != 0.0 ? acc - t : acc;
-            }
-            if (DIV) acc = div_by_rcp(acc, ce[3].x, ce[3].y);
-            w[r][d] = acc;
-            bq[2 * rr + d] = acc;
-          }
-        }
-      }
-    } else { // an interior block: the non-zero terms only, no test
-      if (l == p) {
-        auto at = [&](int o) { return (o & 1) ? c[o >> 1].y : c[o >> 1].x; };
-#pragma unroll
-        for (int r = 0; r < 6; r++) {
-          const int rr = DESC ? 5 - r : r;
-#pragma unroll
-          for (int d = 0; d < 2; d++) {
-            double acc = bq[2 * rr + d];
-#pragma unroll
-            for (int k = 0; k < 6; k++)
-              if (pk_mask(Q, r) & (1 << k)) acc = acc - at(pk_off(Q, r, k)) * w[(r + k) % 6][d];
-            if (DIV) acc = div_by_rcp(acc, at(pk_diag0(Q) + 2 * r), at(pk_diag0(Q) + 2 * r + 1));
-            w[r][d] = acc;
-            bq[2 * rr + d] = acc;
-          }
-        }
-      }
-    }
-  }
-}
-
-// The same sweep for N = 16 with the two DIMENSIONS of a piece on two LANES (round 6).  In sweep4 the lane that owns block s computes its
+// The same sweep for N = 16 with the two DIMENSIONS of a piece on two LANES (round 6).  In quad_sweep (quad_common.h) the lane that owns block s computes its
 // twelve rows -- six per dimension, two independent chains -- while fifteen lanes wait; here a lane holds two SETS of six rows:
 //   X = (piece l, dimension 0) for l < 8, (piece l - 8, dimension 1) for l >= 8;   Y = (piece l + 8, dimension 1) for l < 8, (piece l, dimension 0) for l >= 8
 // so that block p of both dimensions is in one set on the two lanes p mod 8 and p mod 8 + 8, and a step of the traversal is SIX rows of
@@ -234,20 +151,7 @@ __device__ __forceinline__ void sweep4_split(ldscd_t tab, double (&X)[6], double
       for (int u = 0; u < (DIV ? 4 : 3); u++) cb[r][u] = a[4 * r + u];
     asm volatile("" ::: "memory"); // (keeps the reads ahead of the arithmetic)
 #pragma unroll
-    for (int r = 0; r < 6; r++) {
-      const v2d_t(&ce)[4] = cb[r];
-      const int rr = DESC ? 5 - r : r;
-      double acc = R[rr];
-#pragma unroll
-      for (int k = 0; k < 6; k++) {
-        const double ck = (k & 1) ? ce[k >> 1].y : ce[k >> 1].x;
-        const double t = ck * w[(r + k) % 6];
-        acc = ck != 0.0 ? acc - t : acc;
-      }
-      if (DIV) acc = div_by_rcp(acc, ce[3].x, ce[3].y);
-      w[r] = acc;
-      R[rr] = acc;
-    }
+    for (int r = 0; r < 6; r++) sweep_row_end<Q, 1>(r, cb[r], w, R);
   };
   // the seven interior steps s1 .. s1 + 6 of one set: the non-zero terms only, no test.  w: what step s1 starts from; on return,
   // what the step behind the last one starts from (each step ends by fetching for the next)
@@ -261,22 +165,12 @@ __device__ __forceinline__ void sweep4_split(ldscd_t tab, double (&X)[6], double
 #pragma unroll
       for (int u = 0; u < pk_size(Q) / 2; u++) c[u] = a[u];
     }
-    auto at = [&](int o) { return (o & 1) ? c[o >> 1].y : c[o >> 1].x; };
 #pragma unroll 1
     for (int s = s1; s < s1 + 7; s++) {
       const bool own = l8 == ((DESC ? N - 1 - s : s) & 7);
       if (own) {
 #pragma unroll
-        for (int r = 0; r < 6; r++) {
-          const int rr = DESC ? 5 - r : r;
-          double acc = R[rr];
-#pragma unroll
-          for (int k = 0; k < 6; k++)
-            if (pk_mask(Q, r) & (1 << k)) acc = acc - at(pk_off(Q, r, k)) * w[(r + k) % 6];
-          if (DIV) acc = div_by_rcp(acc, at(pk_diag0(Q) + 2 * r), at(pk_diag0(Q) + 2 * r + 1));
-          w[r] = acc;
-          R[rr] = acc;
-        }
+        for (int r = 0; r < 6; r++) sweep_row_interior<Q, 1>(r, c, w, R);
       }
       fetch(R, w);
     }
@@ -298,7 +192,9 @@ __device__ __forceinline__ void sweep4_split(ldscd_t tab, double (&X)[6], double
 
 // ------------------------------------------------ costFunctionCallback (traj_optimizer.cpp:206-350), one gear segment
 // x (q.xs) -> g (q.gs), returns f.  The statements are solver_ref.hip's ref_eval, stage by stage; what changes is where a value
-// lives.  cor: &cor_t[b][0][0][l] (component pitch cpitch = 16 (Kmax + 1), a round's 16 pieces contiguous); ovf: this
+// lives.  (The per-piece MINCO steps -- durations, jerk energy, gdtInv sum, the duration gradient's head / tail terms -- are written out
+// here although ref_eval and q4m_eval call ref_order_common.h's functions for them: with the calls this kernel kept its registers but
+// the headline lost 2 % on the device, docs/HISTORY.md.)  cor: &cor_t[b][0][0][l] (component pitch cpitch = 16 (Kmax + 1), a round's 16 pieces contiguous); ovf: this
 // trajectory's global scratch for the parked terms beyond the LDS window.
 // FAST: the live path's constants known at compile time -- H = 4 half-planes per point (rectangles, traj_manager.cpp:1225) and
 // help_eps = 0.0 (:610): the fifth plane slot and the second reciprocal of the curvature term drop out of the point loop.
@@ -370,8 +266,8 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
     sweep4_split<1>(tab + pk_sweep_offset(1, 16), X, Y, l);
     q4_unsplit(X, Y, bq, l);
   } else {
-    sweep4<0>(tab, bq, N, l);
-    sweep4<1>(tab + pk_sweep_offset(1, N), bq, N, l);
+    quad_sweep<0>(tab, bq, l, N, l < N, N);
+    quad_sweep<1>(tab + pk_sweep_offset(1, N), bq, l, N, l < N, N);
   }
   pr.tick(0);
   // ---- c = b * tInv (:979-984)
@@ -760,8 +656,8 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
     sweep4_split<3>(tab + pk_sweep_offset(3, 16), X, Y, l);
     q4_unsplit(X, Y, adj, l);
   } else {
-    sweep4<2>(tab + pk_sweep_offset(2, N), adj, N, l);
-    sweep4<3>(tab + pk_sweep_offset(3, N), adj, N, l);
+    quad_sweep<2>(tab + pk_sweep_offset(2, N), adj, l, N, l < N, N);
+    quad_sweep<3>(tab + pk_sweep_offset(3, N), adj, l, N, l < N, N);
   }
   pr.tick(4);
   // ---- gradient and cost (traj_optimizer.cpp:299-344)
@@ -929,6 +825,7 @@ __device__ __forceinline__ void q4_second_steps(const QBlk<Y3> &R, ldscd_t al, i
     }
   }
 }
+// (the block loop of solver_ref.hip's two_loop / q4m_two_loop, except: alpha by step number, the second loop's first slot from ne - bound)
 template <bool EXACT, bool Y3>
 __device__ __forceinline__ void q4_two_loop(const Q4 &q, gcd2_t hS, gcd2_t hM, gcd2_t hR, int m, int n, int l, int bound, int ne, bool exact, double sc0, double &d0,
                                             double &d1) {

@@ -11,11 +11,12 @@
 //   * cos / sin of the junction angles by the correctly rounded functions (cr_trig.h), one junction per lane, shared through LDS;
 //     the boundary states in force (junction position from x, junction velocity from the angle) per segment in LDS;
 //   * the four substitution sweeps run all segments side by side: at step s the lanes that own block s of THEIR segment work; a
-//     segment's first block starts from zeros, whatever the neighbour lane (another segment's last piece) holds;
+//     segment's first block starts from zeros, whatever the neighbour lane (another segment's last piece) holds (quad_common.h:
+//     quad_sweep -- the traversal lives there, ref4_kernel runs it with one segment);
 //   * the per-segment chains (gdT, energy, the parked terms' shares) are formed per segment with the other segments' lanes masked to
 //     -0.0; the gradients of a junction's position and angle come from two neighbouring lanes (the last piece of one segment, the
 //     first of the next: one DPP step).
-// What is NOT here: the L-BFGS state machine (lbfgs_control.h), the row's vector operations under it, the record of a suspended
+// What is NOT here: the per-piece MINCO steps of the evaluation (ref_order_common.h), the L-BFGS state machine (lbfgs_control.h), the row's vector operations under it, the record of a suspended
 // trajectory and the shape-free pieces of the persistent loop (quad_lbfgs.h), the ones ref4_kernel runs; this file gives them Q4MShape<TAIL> (three registers, row_sum48, q4m_two_loop).
 // Same bits as the TEAM / WAVE shapes and the restatement with correctly rounded cos / sin (oracle order 2).
 #include <hip/hip_runtime.h>
@@ -129,81 +130,6 @@ __device__ __forceinline__ double row_sum48(const double (&p)[kMV], int n, int l
   return acc;
 }
 
-// One substitution sweep of every segment's band system, the segments side by side (solver_ref4.hip: sweep4).  tabq: the start of
-// sweep Q inside this lane's segment's tables.  Nmax: the largest segment's pieces.
-template <int Q>
-__device__ __forceinline__ void sweep4m(ldscd_t tabq, double (&bq)[12], const LaneSeg &S, int Nmax) {
-  constexpr bool DESC = Q == 1 || Q == 3, DIV = Q == 1 || Q == 2;
-  const int N = S.N;
-  ldscd_t ip = tabq + 48;
-  v2d_t c[pk_size(Q) / 2];
-  {
-    const int sl = DESC ? N - 1 - S.lp : S.lp; // the step this lane's piece is taken in
-    const int bi = sl >= 1 && sl <= N - 2 ? sl - 1 : 0;
-    const ldscv2_t a = (ldscv2_t)(ip + bi * pk_size(Q));
-    if (N > 2) {
-#pragma unroll
-      for (int u = 0; u < pk_size(Q) / 2; u++) c[u] = a[u];
-    } else {
-#pragma unroll
-      for (int u = 0; u < pk_size(Q) / 2; u++) c[u] = v2d_t{0.0, 0.0};
-    }
-  }
-#pragma unroll 1
-  for (int s = 0; s < Nmax; s++) {
-    const int p = DESC ? N - 1 - s : s;
-    double w[6][2];
-#pragma unroll
-    for (int r = 0; r < 6; r++)
-#pragma unroll
-      for (int d = 0; d < 2; d++) w[r][d] = DESC ? nb_dpp<0x101>(bq[2 * (5 - r) + d]) : nb_dpp<0x111>(bq[2 * r + d]);
-    if (s == 0) { // (uniform) every segment's traversal starts from six zeros, whatever the neighbour lane holds
-#pragma unroll
-      for (int r = 0; r < 6; r++) w[r][0] = w[r][1] = 0.0;
-    }
-    const bool mine = S.piece && s < N && S.lp == p;
-    if (mine && (s == 0 || s == N - 1)) { // a block of the ends: every coefficient is tested, as the reference does (`if (a != 0.0)`)
-      const ldscv2_t a = (ldscv2_t)(s == 0 ? tabq : ip + (N - 2) * pk_size(Q));
-#pragma unroll
-      for (int r = 0; r < 6; r++) {
-        v2d_t ce[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) ce[u] = a[4 * r + u];
-        const int rr = DESC ? 5 - r : r;
-#pragma unroll
-        for (int d = 0; d < 2; d++) {
-          double acc = bq[2 * rr + d];
-#pragma unroll
-          for (int k = 0; k < 6; k++) {
-            const double ck = (k & 1) ? ce[k >> 1].y : ce[k >> 1].x;
-            const double t = ck * w[(r + k) % 6][d];
-            acc = ck != 0.0 ? acc - t : acc;
-          }
-          if (DIV) acc = div_by_rcp(acc, ce[3].x, ce[3].y);
-          w[r][d] = acc;
-          bq[2 * rr + d] = acc;
-        }
-      }
-    } else if (mine) { // an interior block: the non-zero terms only, no test
-      auto at = [&](int o) { return (o & 1) ? c[o >> 1].y : c[o >> 1].x; };
-#pragma unroll
-      for (int r = 0; r < 6; r++) {
-        const int rr = DESC ? 5 - r : r;
-#pragma unroll
-        for (int d = 0; d < 2; d++) {
-          double acc = bq[2 * rr + d];
-#pragma unroll
-          for (int k = 0; k < 6; k++)
-            if (pk_mask(Q, r) & (1 << k)) acc = acc - at(pk_off(Q, r, k)) * w[(r + k) % 6][d];
-          if (DIV) acc = div_by_rcp(acc, at(pk_diag0(Q) + 2 * r), at(pk_diag0(Q) + 2 * r + 1));
-          w[r][d] = acc;
-          bq[2 * rr + d] = acc;
-        }
-      }
-    }
-  }
-}
-
 // ------------------------------------------------ costFunctionCallback (traj_optimizer.cpp:206-350), several gear segments
 template <bool FAST>
 __device__ __forceinline__ double q4m_eval(const DevBatch &D, const Q4M &q, ldscd_t tab, gcd_t cor, size_t cpitch, gd_t ovf, int l, const LaneSeg &S, int Nmax,
@@ -216,7 +142,7 @@ __device__ __forceinline__ double q4m_eval(const DevBatch &D, const Q4M &q, ldsc
   const bool piece = S.piece;
   // ---- durations (VirtualT2RealT, :371-379), their powers (poly_traj_utils.hpp:961-966): the lane's own segment's
   const double vt = q.xs[L.x_tau0 + sg];
-  const double Tr = vt > 0.0 ? ((0.5 * vt + 1.0) * vt + 1.0) + P.mini_T : 1.0 / ((0.5 * vt - 1.0) * vt + 1.0) + P.mini_T;
+  const double Tr = virtual_to_real_T(vt, P.mini_T);
   const double t1 = Tr / N, t2 = t1 * t1, t3 = t2 * t1, t4 = t2 * t2, t5 = t4 * t1;
   // ---- cos / sin of the junction angles: the reference calls libm's (host-dependent bits); here the correctly rounded ones
   if (l < M - 1) {
@@ -277,15 +203,14 @@ __device__ __forceinline__ double q4m_eval(const DevBatch &D, const Q4M &q, ldsc
   }
   // ---- BandedSystem::solve (poly_traj_utils.hpp:805-826)
   ldscd_t tabs_ = tab + S.toff;
-  sweep4m<0>(tabs_, bq, S, Nmax);
-  sweep4m<1>(tabs_ + pk_sweep_offset(1, N), bq, S, Nmax);
+  quad_sweep<0>(tabs_, bq, lp, N, piece, Nmax);
+  quad_sweep<1>(tabs_ + pk_sweep_offset(1, N), bq, lp, N, piece, Nmax);
   pr.tick(0);
   // ---- c = b * tInv (:979-984)
   double cc[12];
   {
     const double tI[6] = {1.0 / 1.0, 1.0 / t1, 1.0 / t2, 1.0 / t3, 1.0 / t4, 1.0 / t5};
-#pragma unroll
-    for (int u = 0; u < 12; u++) cc[u] = bq[u] * tI[u >> 1];
+    rows_times_tinv(bq, tI, cc);
     if (piece && lp == 0) {
 #pragma unroll
       for (int u = 0; u < 6; u++) q.tw[8 * sg + u] = tI[u]; // kept for calGrads_PT
@@ -294,22 +219,8 @@ __device__ __forceinline__ double q4m_eval(const DevBatch &D, const Q4M &q, ldsc
   // ---- initSmGradCost / getTrajJerkCost per piece (poly_traj_utils.hpp:998-1035)
   double gdC[12], pE, pG;
   {
-    const double *c = cc;
     const double t[6] = {1.0, t1, t2, t3, t4, t5};
-    const double n33 = c[6] * c[6] + c[7] * c[7], n44 = c[8] * c[8] + c[9] * c[9], n55 = c[10] * c[10] + c[11] * c[11];
-    const double d43 = c[8] * c[6] + c[9] * c[7], d53 = c[10] * c[6] + c[11] * c[7], d54 = c[10] * c[8] + c[11] * c[9];
-    pE = 36.0 * n33 * t[1] + 144.0 * d43 * t[2] + 192.0 * n44 * t[3] + 240.0 * d53 * t[3] + 720.0 * d54 * t[4] + 720.0 * n55 * t[5];
-    pG = 36.0 * n33 + 288.0 * d43 * t[1] + 576.0 * n44 * t[2] + 720.0 * d53 * t[2] + 2880.0 * d54 * t[3] + 3600.0 * n55 * t[4];
-#pragma unroll
-    for (int d = 0; d < 2; d++) {
-      const double c3 = c[6 + d], c4 = c[8 + d], c5 = c[10 + d];
-      gdC[10 + d] = 240.0 * c3 * t[3] + 720.0 * c4 * t[4] + 1440.0 * c5 * t[5];
-      gdC[8 + d] = 144.0 * c3 * t[2] + 384.0 * c4 * t[3] + 720.0 * c5 * t[4];
-      gdC[6 + d] = 72.0 * c3 * t[1] + 144.0 * c4 * t[2] + 240.0 * c5 * t[3];
-      gdC[d] = 0.0;
-      gdC[2 + d] = 0.0;
-      gdC[4 + d] = 0.0;
-    }
+    piece_jerk(cc, t, pE, pG, gdC);
   }
   pr.tick(1);
   // ---- the constraint points of this lane's piece, in order (traj_optimizer.cpp:486-705)
@@ -444,25 +355,14 @@ __device__ __forceinline__ double q4m_eval(const DevBatch &D, const Q4M &q, ldsc
   }
   pr.tick(3);
   // ---- calGrads_PT (poly_traj_utils.hpp:1037-1066): adj = gdC * tInv, solveAdj, the duration gradient
-  double pA;
   double tI[6];
 #pragma unroll
   for (int u = 0; u < 6; u++) tI[u] = q.tw[8 * sg + u];
-  {
-    const double gdtInv[6] = {0.0, -1.0 * tI[2], -2.0 * tI[3], -3.0 * tI[4], -4.0 * tI[5], -5.0 * tI[5] * tI[1]};
-    double acc = 0.0;
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-      const double gdcol = gdC[2 * k] * bq[2 * k] + gdC[2 * k + 1] * bq[2 * k + 1];
-      acc += gdtInv[k] * gdcol;
-    }
-    pA = acc;
-  }
+  const double pA = piece_gdtinv_sum(tI, gdC, bq);
   double adj[12];
-#pragma unroll
-  for (int u = 0; u < 12; u++) adj[u] = gdC[u] * tI[u >> 1];
-  sweep4m<2>(tabs_ + pk_sweep_offset(2, N), adj, S, Nmax);
-  sweep4m<3>(tabs_ + pk_sweep_offset(3, N), adj, S, Nmax);
+  rows_times_tinv(gdC, tI, adj);
+  quad_sweep<2>(tabs_ + pk_sweep_offset(2, N), adj, lp, N, piece, Nmax);
+  quad_sweep<3>(tabs_ + pk_sweep_offset(3, N), adj, lp, N, piece, Nmax);
   pr.tick(4);
   // ---- gradient and cost (traj_optimizer.cpp:299-344)
   if (piece && lp < N - 1) { // gdP: rows 6 i + 5 of the segment's adjoint
@@ -472,10 +372,8 @@ __device__ __forceinline__ double q4m_eval(const DevBatch &D, const Q4M &q, ldsc
   {
     // the duration gradient of every segment (poly_traj_utils.hpp:1050-1064, VirtualTGradCost :405-419): its head terms live in
     // its first lane, its tail terms in its last (every other lane hands the chain a -0.0)
-    const double h1 = hvs[2] * adj[2] + hvs[3] * adj[3];
-    const double h2 = (hvs[4] * adj[4] + hvs[5] * adj[5]) * 2.0 * t1;
-    const double g1 = tvs[2] * adj[8] + tvs[3] * adj[9];
-    const double g2 = (tvs[4] * adj[10] + tvs[5] * adj[11]) * 2.0 * t1;
+    double h1, h2, g1, g2;
+    duration_grad_ends(hvs, tvs, adj, adj, t1, h1, h2, g1, g2);
     double mine_gdT = 0.0;
     const int rb = (int)(threadIdx.x & 48); // the row's first lane
 #pragma unroll
@@ -496,14 +394,7 @@ __device__ __forceinline__ double q4m_eval(const DevBatch &D, const Q4M &q, ldsc
         mine_gdT = sg == s_ ? a : mine_gdT;
       }
     }
-    double gdVT2Rt;
-    if (vt > 0) {
-      gdVT2Rt = vt + 1.0;
-    } else {
-      const double denSqrt = (0.5 * vt - 1.0) * vt + 1.0;
-      gdVT2Rt = (1.0 - vt) / (denSqrt * denSqrt);
-    }
-    if (piece && lp == 0) q.gs[L.x_tau0 + sg] = (mine_gdT / N + P.wei_time) * gdVT2Rt;
+    if (piece && lp == 0) q.gs[L.x_tau0 + sg] = (mine_gdT / N + P.wei_time) * virtual_T_grad_factor(vt);
   }
   {
     // junction i between segment i and i + 1 (traj_optimizer.cpp:307-320): gdTail of segment i (the neighbour lane: its last piece)

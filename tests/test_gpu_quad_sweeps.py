@@ -8,8 +8,10 @@ success), BIT-EQUAL to the restatement of the reference (oracle/pyoracle.py, ord
 
 Shapes: the smallest at which the split sweep can go wrong -- 16 pieces with K = 4 points per piece (n = 31), so that both end blocks
 and the hand-over between the two sets at the ninth step (row_ror) run in every row that is there; 4 and 8 trajectories (one full wave,
-two), 1 and 3 (a wave with rows that are not there: EXEC holds whole rows only), 5 (a full wave and one with a single row).  15 and 8
-pieces take the generic sweep4 beside it: the neighbouring path is unchanged.  A memory of 8 and a handful of iterations per solve.
+two), 1 and 3 (a wave with rows that are not there: EXEC holds whole rows only), 5 (a full wave and one with a single row).  Other
+piece counts take the plain traversal beside it (quad_common.h: quad_sweep, the one solver_ref4m.hip runs for several segments): 15
+(its longest), 8, 3 (one interior block) and 2 (both blocks are end blocks, and the prefetched interior table is its zero branch).
+A memory of 8 and a handful of iterations per solve.
 """
 import ctypes as C
 
@@ -24,7 +26,7 @@ KEYS = ("final_cost", "x", "status", "iters", "evals", "hist_sum", "success")
 MAX_ITER = 6
 
 
-def _check(hiplib, oracle, monkeypatch, pieces, B):
+def _check(hiplib, oracle, monkeypatch, pieces, B, order2_too=False):
     p = hiplib.default_params()
     s = sc.make_scenario([pieces], [1], 4, 4, B, seed=1600 + 16 * pieces + B, n_obs=30)
     s.apply_resolution(p)
@@ -57,6 +59,12 @@ def _check(hiplib, oracle, monkeypatch, pieces, B):
     for k in KEYS:
         assert np.array_equal(r[k], want[k]), (pieces, B, k)
     assert (r["evals"] >= 2).all(), r["evals"]  # (a solve is more than its first evaluation)
+    if order2_too:  # the restatement with correctly rounded cos / sin: one segment has no junction angle, so the same solves
+        want2 = oracle.solve_batch(p, s, nthreads=8, order=2)
+        for k in KEYS:
+            assert np.array_equal(r[k], want2[k]), (pieces, B, k, "order 2")
+        # not vacuous: the adjoint sweeps ran on a gradient that the point terms touched (the oracle alone: 6 iterations in every row)
+        assert (want2["iters"] >= 2).all() and (r["iters"] >= 2).all(), r["iters"]
     bt.close()
     h.close()
 
@@ -77,7 +85,8 @@ def test_a_full_wave_and_a_single_row(hiplib, oracle, monkeypatch):
     _check(hiplib, oracle, monkeypatch, 16, 5)
 
 
-@pytest.mark.parametrize("pieces", [15, 8])
+@pytest.mark.parametrize("pieces", [15, 8, 2, 3])
 def test_other_piece_counts_take_the_generic_sweep(hiplib, oracle, monkeypatch, pieces):
-    """N != 16: sweep4, one lane per piece and both dimensions on it -- untouched, and still the restatement's bits."""
-    _check(hiplib, oracle, monkeypatch, pieces, 5)
+    """N != 16: quad_sweep with one segment, one lane per piece and both dimensions on it -- the restatement's bits (order 0 and
+    order 2), at least two iterations in every row."""
+    _check(hiplib, oracle, monkeypatch, pieces, 5, order2_too=True)

@@ -383,7 +383,8 @@ def test_quad_shape_is_what_a_full_batch_takes_and_equals_the_other_shapes(hipli
 
 
 @pytest.mark.parametrize("case,B,slots,slice_", [("cfg2", 24, 0, 0), ("cfg2", 37, 3, 2), ("5-4-6", 21, 2, 5), ("3-2-4-3", 18, 1, 64), ("2-2", 9, 0, 0),
-                                                 ("8-8-mem40", 13, 1, 7), ("6-5-5", 10, 2, 9), ("4-4-4-4", 7, 1, 33)])
+                                                 ("8-8-mem40", 13, 1, 7), ("6-5-5", 10, 2, 9), ("4-4-4-4", 7, 1, 33),
+                                                 ("2-14", 5, 0, 0), ("14-2", 5, 0, 0)])
 def test_quad_shape_with_gear_shifts_is_bit_identical(hiplib, oracle, monkeypatch, case, B, slots, slice_):
     """The QUAD shape for several gear segments (solver_ref4m.hip): the pieces of up to four segments side by side on a row's sixteen
     lanes, the junction position / angle variables and their gradients, vectors of up to 48 variables in three registers per lane.
@@ -391,7 +392,9 @@ def test_quad_shape_with_gear_shifts_is_bit_identical(hiplib, oracle, monkeypatc
     variables (the third register of a vector holds more than one element: the 48-step chain), forced on
     small batches: every evaluation and every field of every solve equal to the restatement with correctly rounded cos / sin (oracle
     order 2), from rows of their own and through the ring with slices of 2 / 5 / 7 / 64 evaluations, with and without the hand-over of
-    the last trajectories to the WAVE shape; the plan says which kernel ran."""
+    the last trajectories to the WAVE shape; the plan says which kernel ran.  2-14 and 14-2: the traversal of the sweeps (quad_common.h:
+    quad_sweep) is as long as the 14-piece segment's, the two-piece segment's lanes sit out twelve of its steps, first or last on the
+    row; every trajectory of both runs at least 2 iterations (58 ... 366 in the oracle)."""
     p = hiplib.default_params()
     if case == "cfg2":
         s = sc.baseline_config(2, B=B)
@@ -404,6 +407,8 @@ def test_quad_shape_with_gear_shifts_is_bit_identical(hiplib, oracle, monkeypatc
     s.apply_resolution(p)
     want = oracle.solve_batch(p, s, nthreads=8, order=2)
     keys = ("final_cost", "x", "status", "iters", "evals", "hist_sum", "success")
+    if case in ("2-14", "14-2"):
+        assert (want["iters"] >= 2).all(), want["iters"]  # not vacuous: the adjoint sweeps ran on gradients the point terms touched
     monkeypatch.setenv("DFTPAV_REF_SHAPE", "quad")
     if slots:
         monkeypatch.setenv("DFTPAV_REF_SLOTS", str(slots))
