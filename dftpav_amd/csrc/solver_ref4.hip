@@ -88,7 +88,7 @@ __device__ inline void q4_carve(Q4 &q, char *team, int mem) {
   q.bnd = p; p += 12;
   q.tw = p; p += 6;
   q.st = p; p += sNUM;
-  q.alpha = p; p += mem;
+  q.alpha = p; p += mem; // (16-byte aligned: q4_first_block stores two doubles at a time)
   q.pool = p; p += kQPool * 3;
   q.perm = (ldsb_t)p; p += kQPool / 8;
   q.ist = (ldsi_t)p;
@@ -716,9 +716,14 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
 //     second load and go to the row by DPP; histR is written as before (the WAVE shape reads it) but not read here.  n = 32 (Y3):
 //     they are loaded from histR.
 //   * alpha is kept by step number, not by ring slot: a compile-time offset from the block's first step.
+//   * a row's bound falls inside at most one block per loop.  A block in which no row's bound falls (q4_blk_partial) runs its kQB steps
+//     as one body under one mask, with no test between them: lane 0 of the row stores the block's alphas behind its last step in
+//     16-byte writes (first loop), they are read at the block's head (second loop), and n > 16 is decided in front of the body.
+//     Only a block with a bound inside it asks step by step.  Same products, same chains, same order in both forms.
 constexpr int kQB = 8;     // stored pairs per register block (the next block is in flight while one is worked on)
 constexpr int kQNpad = 64; // pitch of a history row: DevLayout::npad of every layout in scope (n <= 32; reference_order_quad_supported)
 static_assert(kQuadMirrorRows == 2 * kQB, "DevBatch::histM holds kQB rows of either end of a ring");
+static_assert((32 + 32 + 12 + 6 + sNUM) % 2 == 0 && kQB % 2 == 0, "a block's alphas start at a multiple of 16 bytes (q4_carve, q4_team_bytes)");
 template <bool Y3> struct QBlk {
   d2_t a[kQB], b[kQB];    // (s, y) of elements l and 16 + l
   d2_t yr[Y3 ? kQB : 1];  // Y3: (ys, 1 / ys)
@@ -741,9 +746,12 @@ __device__ __forceinline__ double row_chain15(double acc, double v) {
   asm volatile("s_nop 1\n\t" DFTPAV_FMAC_BCAST15 : "+v"(acc) : "v"(v), "v"(one));
   return acc;
 }
-template <bool Y3> __device__ __forceinline__ double q4_rec_sum(double p0, double p1, int n) {
+template <bool Y3> __device__ __forceinline__ double q4_rec_sum(double p0, double p1, bool wide) { // wide: n > 16
+  // both products in front of the first chain: without this the compiler forms the second behind the first chain, in the step's
+  // dependent path (in both block forms; where n <= 16 the product is formed and not used, one v_mul_f64 per step)
+  asm volatile("" : "+v"(p1));
   double acc = row_chain16(0.0, p0);
-  if (n > 16) acc = Y3 ? row_chain16(acc, p1) : row_chain15(acc, p1); // (uniform)
+  if (wide) acc = Y3 ? row_chain16(acc, p1) : row_chain15(acc, p1); // (uniform)
   return acc;
 }
 
@@ -792,37 +800,90 @@ template <bool Y3> __device__ __forceinline__ d2_t q4_blk_yr(const QBlk<Y3> &R, 
   yr.y = mov_dpp<0x15F>(R.b[u].y);
   return yr;
 }
+// One step of the first loop with pair u of a block; returns its alpha
+template <bool EXACT, bool Y3>
+__device__ __forceinline__ double q4_first_step(const QBlk<Y3> &R, int u, d2_t yr, bool wide, bool exact, double &d0, double &d1) {
+  const double dot = q4_rec_sum<Y3>(R.a[u].x * d0, R.b[u].x * d1, wide);
+  // lm_alpha[j] = lm_s.col(j).dot(d) / lm_ys[j]  (EXACT: some row of the wave divides -- only its lanes take the division's result)
+  const double a = EXACT && exact ? dot / yr.x : div_by_rcp<false>(dot, yr.x, yr.y);
+  const double na = -a;
+  d0 = d0 + na * R.a[u].y; // d += (-alpha) * lm_y.col(j)
+  d1 = d1 + na * R.b[u].y;
+  return a;
+}
+// One step of the second loop with pair u of a block; av: the pair's alpha
+template <bool EXACT, bool Y3>
+__device__ __forceinline__ void q4_second_step(const QBlk<Y3> &R, int u, d2_t yr, double av, bool wide, bool exact, double &d0, double &d1) {
+  const double dot = q4_rec_sum<Y3>(R.a[u].y * d0, R.b[u].y * d1, wide);
+  const double beta = EXACT && exact ? dot / yr.x : div_by_rcp<false>(dot, yr.x, yr.y);
+  const double cf = av - beta;
+  d0 = d0 + cf * R.a[u].x; // d += (alpha - beta) * lm_s.col(j)
+  d1 = d1 + cf * R.b[u].x;
+}
+// Does the bound of a row that is here fall INSIDE the block of steps i0 .. i0 + kQB - 1?  (uniform: rows that are not in the recursion,
+// or have left its loop, have no lane in the ballot.)  Where it does not, a row takes all of the block's steps or none, and the block
+// runs as one body under one mask; else every step asks for itself, as each of them did before.
+__device__ __forceinline__ bool q4_blk_partial(int i0, int bound) {
+  return __builtin_amdgcn_ballot_w64(i0 < bound && bound < i0 + kQB) != 0ull;
+}
+// The full-block bodies: all kQB steps of a block under the mask of the rows that take them, no test between the steps.
+// wide: n > 16 (uniform), a constant where these are called.  al as in q4_first_steps / q4_second_steps.
+template <bool EXACT, bool Y3>
+__device__ __forceinline__ void q4_first_block(const QBlk<Y3> &R, ldsd_t al, bool wide, int l, bool exact, double &d0, double &d1) {
+  double a[kQB];
+#pragma unroll
+  for (int u = 0; u < kQB; u++) a[u] = q4_first_step<EXACT>(R, u, q4_blk_yr<Y3>(R, u), wide, exact, d0, d1);
+  // the block's alphas behind its last step, 16 bytes at a time (al is 16-byte aligned: q4_carve, i0 a multiple of kQB)
+  if (l == 0) {
+#pragma unroll
+    for (int u = 0; u < kQB; u += 2) {
+      qd2_t v;
+      v.x = a[u];
+      v.y = a[u + 1];
+      *(__attribute__((address_space(3))) qd2_t *)(al + u) = v;
+    }
+  }
+}
+template <bool EXACT, bool Y3>
+__device__ __forceinline__ void q4_second_block(const QBlk<Y3> &R, ldscd_t al, bool wide, bool exact, double &d0, double &d1) {
+  double av[kQB]; // the block's alphas at its head (all kQB steps are taken: al .. al + kQB - 1 lie inside alpha)
+#pragma unroll
+  for (int u = 0; u < kQB; u++) av[u] = al[kQB - 1 - u];
+#pragma unroll
+  for (int u = 0; u < kQB; u++) q4_second_step<EXACT>(R, u, q4_blk_yr<Y3>(R, u), av[u], wide, exact, d0, d1);
+}
 // al: alpha of step i0 (first loop: step i of the recursion takes the i-th newest pair)
 template <bool EXACT, bool Y3>
 __device__ __forceinline__ void q4_first_steps(const QBlk<Y3> &R, ldsd_t al, int i0, int bound, int n, int l, bool exact, double &d0, double &d1) {
+  if (!q4_blk_partial(i0, bound)) { // (uniform)
+    if (i0 < bound) {               // (row-uniform) all kQB steps
+      if (Y3 || n > 16) q4_first_block<EXACT>(R, al, true, l, exact, d0, d1); // (uniform)
+      else q4_first_block<EXACT>(R, al, false, l, exact, d0, d1);
+    }
+    return;
+  }
 #pragma unroll
   for (int u = 0; u < kQB; u++) {
     if (i0 + u < bound) { // (row-uniform)
-      const d2_t yr = q4_blk_yr<Y3>(R, u);
-      const double dot = q4_rec_sum<Y3>(R.a[u].x * d0, R.b[u].x * d1, n);
-      // lm_alpha[j] = lm_s.col(j).dot(d) / lm_ys[j]  (EXACT: some row of the wave divides -- only its lanes take the division's result)
-      const double a = EXACT && exact ? dot / yr.x : div_by_rcp<false>(dot, yr.x, yr.y);
+      const double a = q4_first_step<EXACT>(R, u, q4_blk_yr<Y3>(R, u), n > 16, exact, d0, d1);
       if (l == 0) al[u] = a;
-      const double na = -a;
-      d0 = d0 + na * R.a[u].y; // d += (-alpha) * lm_y.col(j)
-      d1 = d1 + na * R.b[u].y;
     }
   }
 }
 // al: alpha of the pair of this block's LAST step (the second loop takes the pairs in the opposite order: step u reads al[kQB - 1 - u])
 template <bool EXACT, bool Y3>
 __device__ __forceinline__ void q4_second_steps(const QBlk<Y3> &R, ldscd_t al, int i0, int bound, int n, int l, bool exact, double &d0, double &d1) {
+  if (!q4_blk_partial(i0, bound)) { // (uniform)
+    if (i0 < bound) {               // (row-uniform) all kQB steps
+      if (Y3 || n > 16) q4_second_block<EXACT>(R, al, true, exact, d0, d1); // (uniform)
+      else q4_second_block<EXACT>(R, al, false, exact, d0, d1);
+    }
+    return;
+  }
 #pragma unroll
   for (int u = 0; u < kQB; u++) {
-    if (i0 + u < bound) { // (row-uniform)
-      const double av = al[kQB - 1 - u];
-      const d2_t yr = q4_blk_yr<Y3>(R, u);
-      const double dot = q4_rec_sum<Y3>(R.a[u].y * d0, R.b[u].y * d1, n);
-      const double beta = EXACT && exact ? dot / yr.x : div_by_rcp<false>(dot, yr.x, yr.y);
-      const double cf = av - beta;
-      d0 = d0 + cf * R.a[u].x; // d += (alpha - beta) * lm_s.col(j)
-      d1 = d1 + cf * R.b[u].x;
-    }
+    if (i0 + u < bound) // (row-uniform)
+      q4_second_step<EXACT>(R, u, q4_blk_yr<Y3>(R, u), al[kQB - 1 - u], n > 16, exact, d0, d1);
   }
 }
 // (the block loop of solver_ref.hip's two_loop / q4m_two_loop, except: alpha by step number, the second loop's first slot from ne - bound)

@@ -41,7 +41,10 @@ pr = pri.astype(np.float64)
 wave_counts = REF and bool((pr[:, 10] <= r["evals"]).all())
 count_slots = ([9, 10, 11] if wave_counts else [9]) if REF else []
 if REF:
-    NAMES[9], NAMES[10], NAMES[11] = "(count) active terms", "numbering" if not wave_counts else "(count)", ("list flushes" if SLOT11 == "flush" else "emission" if SLOT11 == "emit" else "window list") if not wave_counts else "(count)"
+    # slot 10: the TEAM shape's numbering; in a QUAD shape the time between a row's lbfgs_advance and its next evaluation, which it
+    # spends masked off while other rows of its wave run their recursion
+    quad = not wave_counts and flushes.sum() > 0  # (only a QUAD kernel counts flushes of its list)
+    NAMES[9], NAMES[10], NAMES[11] = "(count) active terms", ("between passes, masked wait" if quad else "numbering") if not wave_counts else "(count)", ("list flushes" if SLOT11 == "flush" else "emission" if SLOT11 == "emit" else "window list") if not wave_counts else "(count)"
 cyc = pr.copy()
 cyc[:, count_slots] = 0.0
 tot = cyc.sum(axis=1)
