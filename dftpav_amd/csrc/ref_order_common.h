@@ -113,6 +113,59 @@ constexpr int kRecWave = 48;        // WAVE shape: records kept in LDS per evalu
 typedef unsigned long long mask_t;  // active terms of a constraint point, bit t = term t (5 H + S + 4 <= 64 terms)
 typedef unsigned short __attribute__((address_space(3))) *ldsh_t;
 
+// What a gear segment's entries of the layout's per-segment arrays are.  The layout is a kernel argument, uniform, and `sg` is usually a
+// lane's own: an indexed read L.arr[sg] would go to scratch, so each entry is SELECTED in one walk over the segments (what a caller does
+// not use of the result costs nothing).
+struct SegInfo {
+  int N, singul;      // pieces, direction
+  int piece0, piece1; // first piece, first piece of the next segment
+  int pt0, pt1;       // first constraint point, first of the next segment
+  int x0;             // offset of its waypoints inside x
+};
+__device__ __forceinline__ SegInfo seg_info(const DevLayout &L, int sg) {
+  SegInfo s{0, 1, 0, 0, 0, 0, 0};
+  for (int q = 0; q < L.M; q++) {
+    const bool is = q == sg;
+    s.N = is ? L.piece_nums[q] : s.N;
+    s.singul = is ? L.singuls[q] : s.singul;
+    s.piece0 = is ? L.seg_piece0[q] : s.piece0;
+    s.piece1 = is ? L.seg_piece0[q + 1] : s.piece1;
+    s.pt0 = is ? L.seg_pt0[q] : s.pt0;
+    s.pt1 = is ? L.seg_pt0[q + 1] : s.pt1;
+    s.x0 = is ? L.seg_x0[q] : s.x0;
+  }
+  return s;
+}
+
+// What active term t adds to one of the four per-segment chains of an evaluation (the chain passes of solver_ref.hip differ in how they
+// walk the terms, never in this).  va: slot 12 (gdT) / 13 (cost) of the term's record.  tS0, t0: the first moving-obstacle term, the first
+// term behind them.  first_sur: the term is the first ACTIVE moving-obstacle term of its point (each pass knows that its own way).
+// sur(vb, vc, pieceid): slots 14 / 15 of the record and the index of the term's piece inside its segment, asked for by the gdT chain of a
+// moving-obstacle term only.  Nseg, sg: the pieces of the chain's segment, its index.
+enum { kChainGdT = 0, kChainCost0, kChainCost2, kChainCost1 };
+template <typename SurAddends>
+__device__ __forceinline__ void chain_add(double &acc, int kind, int t, int tS0, int t0, bool first_sur, double va, int Nseg, int sg, SurAddends sur) {
+  const bool sur_term = t >= tS0 && t < t0;
+  if (kind == kChainGdT) { // gdT: one `+=` per term; a moving-obstacle term: three, and one more per previous segment (traj_optimizer.cpp:1663-1676)
+    acc += va;
+    if (sur_term) {
+      double vb, vc;
+      int pieceid;
+      sur(vb, vc, pieceid);
+      acc += vb * pieceid;
+      acc += vc;
+      const double prev = vb * Nseg; // ... * piece_num_container[trajid]
+      for (int idx = 0; idx < sg; idx++) acc += prev;
+    }
+  } else if (kind == kChainCost0) { // costs(0): the corridor terms
+    if (t < tS0) acc += va;
+  } else if (kind == kChainCost2) { // costs(2): the feasibility terms
+    if (t >= t0) acc += va;
+  } else if (sur_term && first_sur) { // costs(1) += the point's penalty, once per point: carried by its first active obstacle term
+    acc += va;
+  }
+}
+
 // One lane, one dimension: a substitution sweep over the 6N rows of the band system, row by row.  Row i (ascending
 // sweeps: i = 0, 1, ...; descending: i = 6N-1, ...) takes its updates  acc -= c[k] * (result of the k-th row of its
 // window)  in the order the reference's column loops apply them to it (k = 0..5; ascending: rows i-6 .. i-1, descending:

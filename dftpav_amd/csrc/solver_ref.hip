@@ -225,23 +225,32 @@ template <bool WAVE> __device__ __forceinline__ void team_sync() {
 // ------------------------------------------------ costFunctionCallback (traj_optimizer.cpp:206-350)
 // x -> g (LDS), f in st[sF].  rec_b: this trajectory's term records [Npts][nterm][kRec].  The gear segments are independent
 // up to the sums of :292-297 and the junction variables' gradients (:307-320), so every stage runs them side by side.
-template <bool SUR, bool WAVE, int HMAX = 5>
-__device__ DFTPAV_REF_EVAL_ATTR void ref_eval(const DevBatch &D, gcd_t cor_b, gd_t rec_b, const Sm &sm, ldscd_t x, ldsd_t g, Prof &pr) {
-  const DevLayout &L = D.L;
-  const DevParams &P = D.P;
-  // the team: the workgroup, or (WAVE) this wave alone.  Stages with two independent jobs give the second one to the lanes of
-  // wave 1 in a workgroup and to the same lanes, afterwards, in a lone wave (u2: the index inside the second job).
-  const int tid = WAVE ? (int)(threadIdx.x & 63) : (int)threadIdx.x, T = WAVE ? 64 : (int)blockDim.x;
-  const int u2 = WAVE ? tid : tid - 64;
-  const int M = L.M, Ntot = L.Ntot, Npts = L.Npts, H = L.H, nS = SUR ? D.sur.S : 0, nterm = 5 * H + nS + 4, Kmax1 = L.Kmax + 1;
+// ref_eval (below) is the sequence of the stages with the team's barriers and the profile ticks between them; a stage is a function
+// over the team: the workgroup, or (WAVE) one wave alone -- tid: the lane inside the team, T: its lanes.  Stages with two independent
+// jobs give the second one to the lanes of wave 1 in a workgroup and to the same lanes, afterwards, in a lone wave (u2: the index
+// inside the second job).
 
-  // ---- durations (VirtualT2RealT, :371-379), their powers (poly_traj_utils.hpp:961-966); cos / sin of the junction angles
+// lane (segment, dimension) = (w >> 1, w & 1) runs the substitution sweeps Q0, then Q1, over the segment's rows of `rows` ([6 Ntot][2]);
+// the sweep tables of a layout's segments follow one another
+template <int Q0, int Q1> __device__ __forceinline__ void seg_sweeps(const DevLayout &L, const Sm &sm, ldsd_t rows, int w) {
+  const int sg = w >> 1, d = w & 1;
+  const SegInfo si = seg_info(L, sg);
+  int toff = 0;
+  for (int q = 0; q < L.M; q++) toff += q < sg ? pk_segment_doubles(L.piece_nums[q]) : 0;
+  ldscd_t tb = sm.tab + toff;
+  sweep<Q0>(tb + pk_sweep_offset(Q0, si.N), rows + 12 * si.piece0, 6 * si.N, d);
+  sweep<Q1>(tb + pk_sweep_offset(Q1, si.N), rows + 12 * si.piece0, 6 * si.N, d);
+}
+
+// ---- durations (VirtualT2RealT, :371-379), their powers (poly_traj_utils.hpp:961-966); second job: cos / sin of the junction angles
+__device__ __forceinline__ void eval_durations_trig(const DevBatch &D, const Sm &sm, ldscd_t x, int tid, int u2) {
+  const DevLayout &L = D.L;
+  const int M = L.M;
   if (tid < M) {
     const int sg = tid;
     const double vt = x[L.x_tau0 + sg];
-    const double Tr = virtual_to_real_T(vt, P.mini_T);
-    int N = 0;
-    for (int q = 0; q < M; q++) N = q == sg ? L.piece_nums[q] : N;
+    const double Tr = virtual_to_real_T(vt, D.P.mini_T);
+    const int N = seg_info(L, sg).N;
     const double t1 = Tr / N, t2 = t1 * t1, t3 = t2 * t1, t4 = t2 * t2, t5 = t4 * t1;
     ldsd_t se = sm.seg + 16 * sg;
     se[0] = Tr;
@@ -256,8 +265,13 @@ __device__ DFTPAV_REF_EVAL_ATTR void ref_eval(const DevBatch &D, gcd_t cor_b, gd
     sm.trig[2 * i] = cs;
     sm.trig[2 * i + 1] = sn;
   }
-  team_sync<WAVE>();
-  // ---- boundary states in force (IniS / FinS of :270-282): junction position from x, junction velocity from the angle
+}
+
+// ---- boundary states in force (IniS / FinS of :270-282): junction position from x, junction velocity from the angle
+__device__ __forceinline__ void eval_boundary_states(const DevBatch &D, const Sm &sm, ldscd_t x, int tid) {
+  const DevLayout &L = D.L;
+  const DevParams &P = D.P;
+  const int M = L.M;
   if (tid < M) {
     const int sg = tid;
     ldscd_t ini = sm.bnd + 12 * sg, fin = ini + 6;
@@ -279,87 +293,163 @@ __device__ DFTPAV_REF_EVAL_ATTR void ref_eval(const DevBatch &D, gcd_t cor_b, gd
       tv[3] = P.non_sinv * sm.trig[2 * sg + 1];
     }
   }
-  team_sync<WAVE>();
-  // ---- right-hand sides (poly_traj_utils.hpp:968-977)
-  for (int w = tid; w < 12 * Ntot; w += T) {
+}
+
+// ---- right-hand sides (poly_traj_utils.hpp:968-977)
+__device__ __forceinline__ void eval_rhs(const DevBatch &D, const Sm &sm, ldscd_t x, int tid, int T) {
+  const DevLayout &L = D.L;
+  for (int w = tid; w < 12 * L.Ntot; w += T) {
     const int p = w / 12, q = w - 12 * p, k = q >> 1, d = q & 1;
     const int sg = sm.pinfo[4 * p], lp = sm.pinfo[4 * p + 1];
-    int N = 0, x0 = 0;
-    for (int q2 = 0; q2 < M; q2++) {
-      N = q2 == sg ? L.piece_nums[q2] : N;
-      x0 = q2 == sg ? L.seg_x0[q2] : x0;
-    }
+    const SegInfo si = seg_info(L, sg);
     const double t1 = sm.seg[16 * sg + 3], t2 = sm.seg[16 * sg + 4];
     ldscd_t hv = sm.pva + 12 * sg, tv = hv + 6;
     double v = 0.0;
     if (lp == 0 && k < 3) v = k == 0 ? hv[d] : (k == 1 ? hv[2 + d] * t1 : hv[4 + d] * t2);
-    else if (lp == N - 1 && k >= 3) v = k == 3 ? tv[d] : (k == 4 ? tv[2 + d] * t1 : tv[4 + d] * t2);
-    else if (k == 5) v = x[x0 + 2 * lp + d];
+    else if (lp == si.N - 1 && k >= 3) v = k == 3 ? tv[d] : (k == 4 ? tv[2 + d] * t1 : tv[4 + d] * t2);
+    else if (k == 5) v = x[si.x0 + 2 * lp + d];
     sm.b[w] = v;
   }
-  team_sync<WAVE>();
-  // ---- BandedSystem::solve (poly_traj_utils.hpp:805-826), one lane per (segment, dimension); second job: the running sample
-  // offsets s1 += step (traj_optimizer.cpp:513), one lane per table
-  if (tid < 2 * M) {
-    const int sg = tid >> 1, d = tid & 1;
-    int N = 0, p0 = 0;
-    for (int q = 0; q < M; q++) {
-      N = q == sg ? L.piece_nums[q] : N;
-      p0 = q == sg ? L.seg_piece0[q] : p0;
-    }
-    int toff = 0;
-    for (int q = 0; q < M; q++) toff += q < sg ? pk_segment_doubles(L.piece_nums[q]) : 0;
-    ldscd_t tb = sm.tab + toff;
-    sweep<0>(tb, sm.b + 12 * p0, 6 * N, d);
-    sweep<1>(tb + pk_sweep_offset(1, N), sm.b + 12 * p0, 6 * N, d);
-  }
+}
+
+// ---- BandedSystem::solve (poly_traj_utils.hpp:805-826), one lane per (segment, dimension); second job: the running sample
+// offsets s1 += step (traj_optimizer.cpp:513), one lane per table
+__device__ __forceinline__ void eval_forward_solve(const DevBatch &D, const Sm &sm, int tid, int u2, int nS) {
+  const DevLayout &L = D.L;
+  const int M = L.M;
+  if (tid < 2 * M) seg_sweeps<0, 1>(L, sm, sm.b, tid);
   if (u2 >= 0 && u2 < 2 * M) {
     const int sg = u2 >> 1, which = u2 & 1;
     const int K = which ? L.Kd : L.K;
     const double step = sm.seg[16 * sg + 1] / K;
-    ldsd_t tab = sm.spow + (2 * sg + which) * Kmax1;
+    ldsd_t tab = sm.spow + (2 * sg + which) * (L.Kmax + 1);
     double s1 = 0.0;
     for (int j = 0; j <= K; j++) {
       tab[j] = s1;
       s1 += step;
     }
     if (which == 0 && nS > 0) { // start time of every piece: the running sum t += dt of traj_optimizer.cpp:775 (pA is free until calGrads_PT)
-      int p0 = 0, p1 = 0;
-      for (int q = 0; q < M; q++) {
-        p0 = q == sg ? L.seg_piece0[q] : p0;
-        p1 = q == sg ? L.seg_piece0[q + 1] : p1;
-      }
+      const SegInfo si = seg_info(L, sg);
       double tt = 0.0;
-      for (int i = p0; i < p1; i++) {
+      for (int i = si.piece0; i < si.piece1; i++) {
         sm.pA[i] = tt;
         tt += sm.seg[16 * sg + 1];
       }
     }
   }
-  team_sync<WAVE>();
-  pr.tick(0);
-  // ---- c = b * tInv (:979-984)
-  for (int w = tid; w < 12 * Ntot; w += T) {
+}
+
+// ---- every piece's six rows times 1 / t^k of their row, one element per lane: c = b * tInv (poly_traj_utils.hpp:979-984) and, in
+// calGrads_PT (:1037-1041), adj = gdC * tInv
+__device__ __forceinline__ void eval_rows_times_tinv(const DevBatch &D, const Sm &sm, ldscd_t in, ldsd_t out, int tid, int T) {
+  for (int w = tid; w < 12 * D.L.Ntot; w += T) {
     const int p = w / 12, k = (w - 12 * p) >> 1;
-    sm.c[w] = sm.b[w] * sm.seg[16 * sm.pinfo[4 * p] + 8 + k];
+    out[w] = in[w] * sm.seg[16 * sm.pinfo[4 * p] + 8 + k];
   }
-  team_sync<WAVE>();
-  // ---- initSmGradCost / getTrajJerkCost per piece (poly_traj_utils.hpp:998-1035); the sums over the pieces are chained below
-  for (int i = tid; i < Ntot; i += T) {
+}
+// ---- initSmGradCost / getTrajJerkCost per piece (poly_traj_utils.hpp:998-1035); the sums over the pieces are chained by seg_chain_starts
+__device__ __forceinline__ void eval_piece_jerk(const DevBatch &D, const Sm &sm, int tid, int T) {
+  for (int i = tid; i < D.L.Ntot; i += T) {
     ldscd_t c = sm.c + 12 * i;
     ldscd_t t = sm.seg + 16 * sm.pinfo[4 * i] + 2;
     piece_jerk(c, t, sm.pE[i], sm.pG[i], sm.gdC + 12 * i);
   }
-  pr.tick(1);
-  if (WAVE) {
-  // ================= WAVE shape: tests, numbering and records in one pass over the points; chains from LDS
-  // The points are taken 64 at a time IN ORDER, so the running number of active terms is known at the end of every round: a
-  // lane numbers its point's active terms (exclusive prefix over the wave + the running base) and writes each record straight
-  // to its place in (point, term) order -- the first `nrec` of an evaluation in LDS (an evaluation of BASELINE configs[2] has
-  // 24 active terms on average), the rest in global scratch.  No mask table, no second pass.
-  const int nrec = sm.nrec, tS0 = 5 * H, t0 = tS0 + nS;
-  const gd_t stage_b = rec_b + (size_t)Npts * nterm * kRec;                         // moving obstacles: a point's records as surround_terms leaves them
-  int *glist = reinterpret_cast<int *>((double *)(stage_b + (size_t)Npts * nS * kRec)); // entries beyond the LDS window
+}
+
+// the start values of the per-segment chains of segment sg (`gdT +=`, `energy +=` over the pieces in order, from 0.0)
+__device__ __forceinline__ void seg_chain_starts(const Sm &sm, const DevLayout &L, int sg) {
+  const SegInfo si = seg_info(L, sg);
+  double gdT = 0.0, en = 0.0;
+  for (int i = si.piece0; i < si.piece1; i++) {
+    gdT += sm.pG[i];
+    en += sm.pE[i];
+  }
+  sm.segsum[gNUM * sg + gGDT] = gdT;
+  sm.segsum[gNUM * sg + gENERGY] = en;
+  sm.segsum[gNUM * sg + gCOST0] = 0.0;
+  sm.segsum[gNUM * sg + gCOST2] = 0.0;
+  sm.segsum[gNUM * sg + gCOST1] = 0.0;
+}
+
+// ---- one constraint point: what it needs from its piece and segment, the same expressions for whoever evaluates it (a point's own
+// lane, or the lane that holds one of its (point, obstacle) pairs)
+struct PointCtx {
+  int p, j;              // its piece, its index inside it
+  int sg, lp, K, N, singul;
+  double cc[12], step, s1;
+  double trajtime;       // trajtimes[sg] of traj_optimizer.cpp:230-234: 0, then the real duration of the PREVIOUS segment
+  double t_piece;        // start time of its piece (moving obstacles only)
+};
+template <bool SUR> __device__ __forceinline__ void point_ctx(const DevBatch &D, const Sm &sm, int pt, PointCtx &c) {
+  const DevLayout &L = D.L;
+  c.p = D.pt_piece[pt];
+  c.j = D.pt_j[pt];
+  c.sg = sm.pinfo[4 * c.p];
+  c.lp = sm.pinfo[4 * c.p + 1];
+  c.K = sm.pinfo[4 * c.p + 3];
+  const SegInfo si = seg_info(L, c.sg);
+  c.N = si.N;
+  c.singul = si.singul;
+  const bool edge = c.lp == 0 || c.lp == c.N - 1;
+#pragma unroll
+  for (int k = 0; k < 12; k++) c.cc[k] = sm.c[12 * c.p + k];
+  c.step = sm.seg[16 * c.sg + 1] / c.K;
+  c.s1 = sm.spow[(2 * c.sg + (edge ? 1 : 0)) * (L.Kmax + 1) + c.j];
+  c.trajtime = (SUR && c.sg > 0) ? sm.seg[16 * (c.sg - 1)] : 0.0;
+  c.t_piece = SUR ? sm.pA[c.p] : 0.0;
+}
+
+// ================= WAVE shape: tests, numbering and records in one pass over the points; chains from LDS
+// where the WAVE shape keeps what does not fit its LDS window, behind the trajectory's records
+struct WaveScratch {
+  gd_t stage; // moving obstacles: a point's records as surround_terms leaves them [Npts][nS][kRec]
+  int *glist; // (entry, piece) of the terms beyond the LDS window
+};
+__device__ __forceinline__ WaveScratch wave_scratch(const DevLayout &L, gd_t rec_b, int nS) {
+  const int nterm = 5 * L.H + nS + 4;
+  WaveScratch ws;
+  ws.stage = rec_b + (size_t)L.Npts * nterm * kRec;
+  ws.glist = reinterpret_cast<int *>((double *)(ws.stage + (size_t)L.Npts * nS * kRec));
+  return ws;
+}
+// the active terms m of point pt (piece p), numbered from e on: entry and record of each to its place in (point, term) order
+__device__ __forceinline__ void wave_emit_terms(const DevBatch &D, gcd_t cor_b, gd_t rec_b, const Sm &sm, const WaveScratch &ws, const PtState &st, mask_t m, int pt, int p,
+                                                int e, int nS) {
+  const int nrec = sm.nrec, H = D.L.H, tS0 = 5 * H, t0 = tS0 + nS;
+  bool sur_seen = false;
+  for (mask_t mm = m; mm;) {
+    const int t = __builtin_ctzll(mm);
+    mm &= mm - 1;
+    const bool sur_term = t >= tS0 && t < t0;
+    int entry = (pt << 6) | t;
+    if (sur_term && !sur_seen) entry |= (int)0x80000000u; // carries the point's moving-obstacle penalty (costs(1) += once per point)
+    sur_seen = sur_seen || sur_term;
+    double *r_ = e < nrec ? (double *)(sm.lrec + (size_t)e * kRec) : (double *)(rec_b + (size_t)e * kRec);
+    if (e < nrec) {
+      sm.list[e] = entry;
+      sm.list[nrec + e] = p; // its piece
+    } else {
+      ws.glist[2 * e] = entry;
+      ws.glist[2 * e + 1] = p;
+    }
+    if (sur_term) {
+      const gcd_t src = (gcd_t)(ws.stage + ((size_t)pt * nS + (t - tS0)) * kRec);
+#pragma unroll
+      for (int q = 0; q < kRec; q++) r_[q] = src[q];
+    } else {
+      point_emit(D.P, st, t, H, t0, cor_b + pt, (size_t)D.NptsPad, r_);
+    }
+    e++;
+  }
+}
+// The points are taken 64 at a time IN ORDER, so the running number of active terms is known at the end of every round: a
+// lane numbers its point's active terms (exclusive prefix over the wave + the running base) and writes each record straight
+// to its place in (point, term) order -- the first `nrec` of an evaluation in LDS (an evaluation of BASELINE configs[2] has
+// 24 active terms on average), the rest in global scratch.  No mask table, no second pass.  Returns the number of active terms.
+template <bool SUR> __device__ __forceinline__ int wave_point_pass(const DevBatch &D, gcd_t cor_b, gd_t rec_b, const Sm &sm, int tid, int nS) {
+  const DevLayout &L = D.L;
+  const int Npts = L.Npts, H = L.H;
+  const WaveScratch ws = wave_scratch(L, rec_b, nS);
   int base = 0;
   // (requesting the half-planes one round ahead was tried twice: 40 more live registers; round 4: 100 -> 116 k cycles per evaluation,
   // round 5 on the DPP-chain kernel: 92.6 -> 112.7 k, 310 -> 317 ms per 4096 -- docs/HISTORY.md)
@@ -368,563 +458,296 @@ __device__ DFTPAV_REF_EVAL_ATTR void ref_eval(const DevBatch &D, gcd_t cor_b, gd
     const bool in = pt < Npts;
     mask_t m = 0ull;
     PtState st;
-    int p = 0, j = 1;
+    PointCtx c;
+    c.p = 0;
+    c.j = 1;
     if (in) {
       double pl[20];
       load_planes(cor_b + pt, (size_t)D.NptsPad, H, pl);
-      p = D.pt_piece[pt];
-      j = D.pt_j[pt];
-      const int sg = sm.pinfo[4 * p], lp = sm.pinfo[4 * p + 1], K = sm.pinfo[4 * p + 3];
-      int N = 0, singul_ = 1;
-      for (int q = 0; q < M; q++) {
-        N = q == sg ? L.piece_nums[q] : N;
-        singul_ = q == sg ? L.singuls[q] : singul_;
-      }
-      const bool edge = lp == 0 || lp == N - 1;
-      double cc[12];
-#pragma unroll
-      for (int k = 0; k < 12; k++) cc[k] = sm.c[12 * p + k];
-      const double step = sm.seg[16 * sg + 1] / K;
-      const double s1 = sm.spow[(2 * sg + (edge ? 1 : 0)) * Kmax1 + j];
-      const double trajtime = (SUR && sg > 0) ? sm.seg[16 * (sg - 1)] : 0.0;
-      m = point_masks<SUR>(P, cc, lp, N, j, K, step, s1, singul_, D.epis, H, pl, stage_b + (size_t)pt * nS * kRec, D.sur, D.t_now, SUR ? sm.pA[p] : 0.0, sg,
-                           trajtime, st);
+      point_ctx<SUR>(D, sm, pt, c);
+      m = point_masks<SUR>(D.P, c.cc, c.lp, c.N, c.j, c.K, c.step, c.s1, c.singul, D.epis, H, pl, ws.stage + (size_t)pt * nS * kRec, D.sur, D.t_now, c.t_piece, c.sg,
+                           c.trajtime, st);
     }
-    const int c = __builtin_popcountll(m);
-    if (__builtin_amdgcn_ballot_w64(c != 0) == 0ull) { // (uniform) nothing active in this round
-      if (in && j == 0) sm.pstart[p] = base;
+    const int cnt = __builtin_popcountll(m);
+    if (__builtin_amdgcn_ballot_w64(cnt != 0) == 0ull) { // (uniform) nothing active in this round
+      if (in && c.j == 0) sm.pstart[c.p] = base;
       continue;
     }
-    const int incl = wave_incl_scan_i32(c);
-    int e = base + incl - c;
-    if (in && j == 0) sm.pstart[p] = e; // a piece's terms start where its first point's do
-    if (SUR && c != 0) __threadfence_block(); // this lane reads its moving-obstacle records back below
-    bool sur_seen = false;
-    for (mask_t mm = m; mm;) {
-      const int t = __builtin_ctzll(mm);
-      mm &= mm - 1;
-      const bool sur_term = t >= tS0 && t < t0;
-      int entry = (pt << 6) | t;
-      if (sur_term && !sur_seen) entry |= (int)0x80000000u; // carries the point's moving-obstacle penalty (costs(1) += once per point)
-      sur_seen = sur_seen || sur_term;
-      double *r_ = e < nrec ? (double *)(sm.lrec + (size_t)e * kRec) : (double *)(rec_b + (size_t)e * kRec);
-      if (e < nrec) {
-        sm.list[e] = entry;
-        sm.list[nrec + e] = p; // its piece
-      } else {
-        glist[2 * e] = entry;
-        glist[2 * e + 1] = p;
-      }
-      if (sur_term) {
-        const gcd_t src = (gcd_t)(stage_b + ((size_t)pt * nS + (t - tS0)) * kRec);
-#pragma unroll
-        for (int q = 0; q < kRec; q++) r_[q] = src[q];
-      } else {
-        point_emit(P, st, t, H, t0, cor_b + pt, (size_t)D.NptsPad, r_);
-      }
-      e++;
-    }
+    const int incl = wave_incl_scan_i32(cnt);
+    const int e = base + incl - cnt;
+    if (in && c.j == 0) sm.pstart[c.p] = e; // a piece's terms start where its first point's do
+    if (SUR && cnt != 0) __threadfence_block(); // this lane reads its moving-obstacle records back below
+    wave_emit_terms(D, cor_b, rec_b, sm, ws, st, m, pt, c.p, e, nS);
     base += __builtin_amdgcn_readlane(incl, 63);
   }
-  if (tid == 0) sm.pstart[Ntot] = base;
-  // the start values of the per-segment chains (`gdT +=`, `energy +=` over the pieces in order, from 0.0)
-  if (tid < M) {
-    const int sg = tid;
-    int p0 = 0, p1 = 0;
-    for (int q = 0; q < M; q++) {
-      p0 = q == sg ? L.seg_piece0[q] : p0;
-      p1 = q == sg ? L.seg_piece0[q + 1] : p1;
+  if (tid == 0) sm.pstart[L.Ntot] = base;
+  return base;
+}
+
+// ---- chains: what the active terms add to gdC (12 entries per piece) and, per segment, to gdT, the corridor cost, the feasibility cost
+// and the moving-obstacle cost (chain_add), in (point, term) order.
+// A job of the two passes that give every chain a lane of its own: chain w of the 12 Ntot + 4 M adds the terms [e0, e1) to *dst.
+struct ChainJob {
+  int e0, e1;
+  int q;    // the record's slot: the entry of gdC, 12 (gdT) or 13 (a cost)
+  int kind; // -1: an entry of gdC (every term of the piece); otherwise the segment's chain (kChainGdT ...)
+  int sg;   // the segment of a per-segment chain
+  ldsd_t dst;
+};
+// WAVE takes the 4 M per-segment jobs first (theirs are the long walks), TEAM last: the order decides which lanes take them.  A piece's
+// (segment's) terms: WAVE numbers them by piece (pstart), TEAM by point (first).
+template <bool WAVE> __device__ __forceinline__ ChainJob decode_chain_job(const DevLayout &L, const Sm &sm, int w) {
+  const int n_seg = 4 * L.M, n_piece = 12 * L.Ntot;
+  const bool piece_job = WAVE ? w >= n_seg : w < n_piece;
+  ChainJob jb;
+  jb.kind = -1;
+  jb.sg = 0;
+  if (piece_job) {
+    const int v = WAVE ? w - n_seg : w, p = v / 12;
+    jb.q = v - 12 * p;
+    if (WAVE) {
+      jb.e0 = sm.pstart[p];
+      jb.e1 = sm.pstart[p + 1];
+    } else {
+      const int pt0 = sm.pinfo[4 * p + 2], pt1 = pt0 + sm.pinfo[4 * p + 3] + 1;
+      jb.e0 = sm.first(pt0);
+      jb.e1 = sm.first(pt1);
     }
-    double gdT = 0.0, en = 0.0;
-    for (int i = p0; i < p1; i++) {
-      gdT += sm.pG[i];
-      en += sm.pE[i];
-    }
-    sm.segsum[gNUM * sg + gGDT] = gdT;
-    sm.segsum[gNUM * sg + gENERGY] = en;
-    sm.segsum[gNUM * sg + gCOST0] = 0.0;
-    sm.segsum[gNUM * sg + gCOST2] = 0.0;
-    sm.segsum[gNUM * sg + gCOST1] = 0.0;
+    jb.dst = sm.gdC + v;
+  } else {
+    const int v = WAVE ? w : w - n_piece, sg = v >> 2, kd = v & 3; // per segment: 0 gdT, 1 corridor cost, 2 feasibility cost, 3 moving-obstacle cost
+    const SegInfo si = seg_info(L, sg);
+    jb.e0 = WAVE ? sm.pstart[si.piece0] : sm.first(si.pt0);
+    jb.e1 = WAVE ? sm.pstart[si.piece1] : sm.first(si.pt1);
+    jb.q = kd == 0 ? 12 : 13;
+    jb.dst = sm.segsum + gNUM * sg + (kd == 0 ? gGDT : (kd == 1 ? gCOST0 : (kd == 2 ? gCOST2 : gCOST1)));
+    jb.kind = kd == 0 ? kChainGdT : (kd == 1 ? kChainCost0 : (kd == 2 ? kChainCost2 : kChainCost1));
+    jb.sg = sg;
   }
-  __threadfence_block(); // records beyond the LDS window went to global memory
-  team_sync<WAVE>();
-  pr.tick(2);
-  pr.count(9, base); // active terms of this evaluation (a count, not cycles)
-  pr.count(10, base > nrec ? 1 : 0);   // evaluations whose records do not all fit the LDS window ...
-  pr.count(11, base > nrec ? base : 0); // ... and their active terms
-  // ---- chains: lane (piece, entry) adds its piece's records in order; four more lanes per segment walk all of the segment's
-  // for gdT, the corridor cost, the feasibility cost and the moving-obstacle cost (they go first: theirs are the long walks)
-  if (base > 0 && base <= kSerialMax) {
-    // Up to a few hundred active terms (nearly every evaluation; most have all their records in LDS): ONE pass over the terms in
-    // order on 16 lanes -- lane q < 12 carries entry q of gdC of the piece the terms belong to, lane 12 that segment's gdT,
-    // lane 13 its three costs -- each term one read and one addition per lane, the reads of sixteen terms in flight (the ones
-    // beyond the LDS window come from L2: one round trip per sixteen terms for all the sums together); a change of piece
-    // (segment) stores the sums and fetches the next piece's (segment's).  Same chains as the lanes per (piece, entry) below,
-    // term after term.
-    if (tid < 16) {
-      constexpr int kU = 16;
-      int curp = -1, cursg = -1, Nseg = 0;
-      double acc = 0.0, c2 = 0.0, c1 = 0.0; // lane < 12: gdC entry; 12: gdT; 13: corridor cost (acc), feasibility (c2), moving obstacles (c1)
-      for (int e0 = 0; e0 < base; e0 += kU) {
-        int ent[kU], pc[kU];
-        double v[kU];
+  return jb;
+}
+
+// WAVE: slot q of the record of term e (the first nrec of an evaluation in LDS, the rest in global scratch)
+__device__ __forceinline__ double wave_rec(const Sm &sm, gd_t rec_b, int e, int q) {
+  return e < sm.nrec ? sm.lrec[(size_t)e * kRec + q] : rec_b[(size_t)e * kRec + q];
+}
+// the serial pass's per-segment sums: lane 12 carries gdT (acc), lane 13 the corridor cost (acc), feasibility (c2), moving obstacles (c1)
+__device__ __forceinline__ void serial_seg_store(const Sm &sm, int tid, int sg, double acc, double c2, double c1) {
+  if (tid == 12) sm.segsum[gNUM * sg + gGDT] = acc;
+  if (tid == 13) {
+    sm.segsum[gNUM * sg + gCOST0] = acc;
+    sm.segsum[gNUM * sg + gCOST2] = c2;
+    sm.segsum[gNUM * sg + gCOST1] = c1;
+  }
+}
+__device__ __forceinline__ void serial_seg_fetch(const Sm &sm, int tid, int sg, double &acc, double &c2, double &c1) {
+  if (tid == 12) acc = sm.segsum[gNUM * sg + gGDT];
+  if (tid == 13) {
+    acc = sm.segsum[gNUM * sg + gCOST0];
+    c2 = sm.segsum[gNUM * sg + gCOST2];
+    c1 = sm.segsum[gNUM * sg + gCOST1];
+  }
+}
+// More active terms than that: a lane per chain (decode_chain_job), each walks its own terms
+__device__ __forceinline__ void wave_chain_wide(const DevBatch &D, gd_t rec_b, const Sm &sm, int tid, int nS) {
+  const DevLayout &L = D.L;
+  const int nrec = sm.nrec, tS0 = 5 * L.H, t0 = tS0 + nS;
+  const int *glist = wave_scratch(L, rec_b, nS).glist;
+  const int n_chain = 4 * L.M + 12 * L.Ntot;
+  for (int w = tid; w < n_chain; w += 64) {
+    const ChainJob jb = decode_chain_job<true>(L, sm, w);
+    const int e0 = jb.e0, e1 = jb.e1, q = jb.q;
+    if (e1 <= e0) continue;
+    double acc = *jb.dst;
+    if (jb.kind < 0) { // an entry of gdC: every term of the piece, in order
+      int e = e0;
+      const int eL = e1 < nrec ? e1 : nrec; // the part in LDS
+      for (; e < eL; e++) acc += sm.lrec[(size_t)e * kRec + q];
+      for (; e + 8 <= e1; e += 8) {
+        double v[8];
 #pragma unroll
-        for (int u = 0; u < kU; u++) {
-          const int e = e0 + u < base ? e0 + u : base - 1;
-          if (e < nrec) { // (uniform)
+        for (int u = 0; u < 8; u++) v[u] = rec_b[(size_t)(e + u) * kRec + q];
+#pragma unroll
+        for (int u = 0; u < 8; u++) acc += v[u];
+      }
+      for (; e < e1; e++) acc += rec_b[(size_t)e * kRec + q];
+    } else {
+      const int Nseg = seg_info(L, jb.sg).N;
+      for (int eb = e0; eb < e1; eb += 8) { // what the next eight terms add is requested in front of the additions
+        int ent[8];
+        double va8[8], vb8[8], vc8[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+          const int e = eb + u < e1 ? eb + u : e1 - 1;
+          if (e < nrec) {
             ent[u] = sm.list[e];
-            pc[u] = sm.list[nrec + e];
-            v[u] = sm.lrec[(size_t)e * kRec + tid];
+            ldscd_t r_ = sm.lrec + (size_t)e * kRec;
+            va8[u] = r_[q]; vb8[u] = r_[14]; vc8[u] = r_[15];
           } else {
             ent[u] = glist[2 * e];
-            pc[u] = glist[2 * e + 1];
-            v[u] = rec_b[(size_t)e * kRec + tid];
+            gcd_t r_ = (gcd_t)(rec_b + (size_t)e * kRec);
+            va8[u] = r_[q]; vb8[u] = r_[14]; vc8[u] = r_[15];
           }
         }
 #pragma unroll
-        for (int u = 0; u < kU; u++) {
-          if (e0 + u >= base) break; // uniform
-          const int p = pc[u];
-          if (p != curp) { // uniform: the terms come piece after piece, segment after segment
-            const int sg = sm.pinfo[4 * p];
-            if (tid < 12) {
-              if (curp >= 0) sm.gdC[12 * curp + tid] = acc;
-              acc = sm.gdC[12 * p + tid];
-            } else if (sg != cursg) {
-              if (cursg >= 0) {
-                if (tid == 12) sm.segsum[gNUM * cursg + gGDT] = acc;
-                if (tid == 13) {
-                  sm.segsum[gNUM * cursg + gCOST0] = acc;
-                  sm.segsum[gNUM * cursg + gCOST2] = c2;
-                  sm.segsum[gNUM * cursg + gCOST1] = c1;
-                }
-              }
-              if (tid == 12) acc = sm.segsum[gNUM * sg + gGDT];
-              if (tid == 13) {
-                acc = sm.segsum[gNUM * sg + gCOST0];
-                c2 = sm.segsum[gNUM * sg + gCOST2];
-                c1 = sm.segsum[gNUM * sg + gCOST1];
-              }
-            }
-            if (sg != cursg) {
-              Nseg = 0;
-              for (int q2 = 0; q2 < M; q2++) Nseg = q2 == sg ? L.piece_nums[q2] : Nseg;
-            }
-            curp = p;
-            cursg = sg;
-          }
-          const int t = ent[u] & 63;
-          const bool sur_term = t >= tS0 && t < t0;
-          if (tid < 12) {
-            acc += v[u];
-          } else if (tid == 12) { // gdT: one `+=` per term; a moving-obstacle term: three, and one more per previous segment (traj_optimizer.cpp:1663-1676)
-            acc += v[u];
-            if (sur_term) {
-              const int e = e0 + u;
-              const double vb = e < nrec ? sm.lrec[(size_t)e * kRec + 14] : rec_b[(size_t)e * kRec + 14];
-              const double vc = e < nrec ? sm.lrec[(size_t)e * kRec + 15] : rec_b[(size_t)e * kRec + 15];
-              acc += vb * sm.pinfo[4 * p + 1]; // * pieceid
-              acc += vc;
-              const double prev = vb * Nseg; // * piece_num_container[trajid]
-              for (int idx = 0; idx < cursg; idx++) acc += prev;
-            }
-          } else if (tid == 13) {
-            if (t < tS0) acc += v[u];
-            else if (t >= t0) c2 += v[u];
-            else if (ent[u] < 0) c1 += v[u]; // costs(1) += the point's penalty, once per point: carried by its first active obstacle term
-          }
-        }
-      }
-      if (tid < 12) sm.gdC[12 * curp + tid] = acc;
-      if (tid == 12) sm.segsum[gNUM * cursg + gGDT] = acc;
-      if (tid == 13) {
-        sm.segsum[gNUM * cursg + gCOST0] = acc;
-        sm.segsum[gNUM * cursg + gCOST2] = c2;
-        sm.segsum[gNUM * cursg + gCOST1] = c1;
-      }
-    }
-    team_sync<WAVE>();
-  } else if (base > 0) {
-    const int n_chain = 4 * M + 12 * Ntot;
-    for (int w = tid; w < n_chain; w += 64) {
-      int e0, e1, q, kind = -1, csg = 0;
-      ldsd_t dst;
-      if (w >= 4 * M) {
-        const int p = (w - 4 * M) / 12;
-        q = (w - 4 * M) - 12 * p;
-        e0 = sm.pstart[p];
-        e1 = sm.pstart[p + 1];
-        dst = sm.gdC + (w - 4 * M);
-      } else {
-        const int sg = w >> 2, kd = w & 3; // per segment: 0 gdT, 1 corridor cost, 2 feasibility cost, 3 moving-obstacle cost
-        int a0 = 0, a1 = 0;
-        for (int q2 = 0; q2 < M; q2++) {
-          a0 = q2 == sg ? L.seg_piece0[q2] : a0;
-          a1 = q2 == sg ? L.seg_piece0[q2 + 1] : a1;
-        }
-        e0 = sm.pstart[a0];
-        e1 = sm.pstart[a1];
-        q = kd == 0 ? 12 : 13;
-        dst = sm.segsum + gNUM * sg + (kd == 0 ? gGDT : (kd == 1 ? gCOST0 : (kd == 2 ? gCOST2 : gCOST1)));
-        kind = kd;
-        csg = sg;
-      }
-      if (e1 <= e0) continue;
-      double acc = *dst;
-      if (kind < 0) { // an entry of gdC: every term of the piece, in order
-        int e = e0;
-        const int eL = e1 < nrec ? e1 : nrec; // the part in LDS
-        for (; e < eL; e++) acc += sm.lrec[(size_t)e * kRec + q];
-        for (; e + 8 <= e1; e += 8) {
-          double v[8];
-#pragma unroll
-          for (int u = 0; u < 8; u++) v[u] = rec_b[(size_t)(e + u) * kRec + q];
-#pragma unroll
-          for (int u = 0; u < 8; u++) acc += v[u];
-        }
-        for (; e < e1; e++) acc += rec_b[(size_t)e * kRec + q];
-      } else {
-        int Nseg = 0;
-        for (int q2 = 0; q2 < M; q2++) Nseg = q2 == csg ? L.piece_nums[q2] : Nseg;
-        for (int eb = e0; eb < e1; eb += 8) { // what the next eight terms add is requested in front of the additions
-          int ent[8];
-          double va8[8], vb8[8], vc8[8];
-#pragma unroll
-          for (int u = 0; u < 8; u++) {
-            const int e = eb + u < e1 ? eb + u : e1 - 1;
-            if (e < nrec) {
-              ent[u] = sm.list[e];
-              ldscd_t r_ = sm.lrec + (size_t)e * kRec;
-              va8[u] = r_[q]; vb8[u] = r_[14]; vc8[u] = r_[15];
-            } else {
-              ent[u] = glist[2 * e];
-              gcd_t r_ = (gcd_t)(rec_b + (size_t)e * kRec);
-              va8[u] = r_[q]; vb8[u] = r_[14]; vc8[u] = r_[15];
-            }
-          }
-#pragma unroll
-          for (int u = 0; u < 8; u++) {
+        for (int u = 0; u < 8; u++) {
           if (eb + u >= e1) break;
           const int entry = ent[u];
-          const double va = va8[u], vb = vb8[u], vc = vc8[u];
-          const int t = entry & 63;
-          const bool sur_term = t >= tS0 && t < t0;
-          if (kind == 0) { // gdT: one `+=` per term; a moving-obstacle term: three, and one more per previous segment (traj_optimizer.cpp:1663-1676)
-            acc += va;
-            if (sur_term) {
-              const int lp = sm.pinfo[4 * (int)D.pt_piece[(entry >> 6) & 0x1ffffff] + 1]; // pieceid
-              acc += vb * lp;
-              acc += vc;
-              const double prev = vb * Nseg; // ... * piece_num_container[trajid]
-              for (int idx = 0; idx < csg; idx++) acc += prev;
-            }
-          } else if (kind == 1) {
-            if (t < tS0) acc += va;
-          } else if (kind == 2) {
-            if (t >= t0) acc += va;
-          } else if (sur_term && entry < 0) { // costs(1) += the point's penalty, once per point: carried by its first active obstacle term
-            acc += va;
-          }
-          }
-        }
-      }
-      *dst = acc;
-    }
-    team_sync<WAVE>();
-  }
-  } else {
-  // ================= TEAM shape
-  // ---- the constraint points, each on a lane of its own
-  // what a point needs from its piece and segment
-  auto point_ctx = [&](int pt, int &p, int &j, int &sg, int &lp, int &K, int &N, int &singul_, double (&cc)[12], double &step, double &s1, double &trajtime) {
-    p = D.pt_piece[pt];
-    j = D.pt_j[pt];
-    sg = sm.pinfo[4 * p];
-    lp = sm.pinfo[4 * p + 1];
-    K = sm.pinfo[4 * p + 3];
-    N = 0;
-    singul_ = 1;
-    for (int q = 0; q < M; q++) {
-      N = q == sg ? L.piece_nums[q] : N;
-      singul_ = q == sg ? L.singuls[q] : singul_;
-    }
-    const bool edge = lp == 0 || lp == N - 1;
-#pragma unroll
-    for (int k = 0; k < 12; k++) cc[k] = sm.c[12 * p + k];
-    step = sm.seg[16 * sg + 1] / K;
-    s1 = sm.spow[(2 * sg + (edge ? 1 : 0)) * Kmax1 + j];
-    // trajtimes[sg] of traj_optimizer.cpp:230-234: 0, then the real duration of the PREVIOUS segment
-    trajtime = (SUR && sg > 0) ? sm.seg[16 * (sg - 1)] : 0.0;
-  };
-  if (SUR && nS > 0) {
-    // Moving obstacles: a (point, obstacle) pair that reaches its forty correctly rounded exponentials costs 40 k cycles, and one such
-    // lane holds its whole wave.  So the pairs are COLLECTED first -- every point runs its static tests and, per obstacle, the cheap tests
-    // (hull box, distance gate, the bound before any exponential) -- and then evaluated densely packed, one pair per lane; a pair's record
-    // has a place of its own, so who evaluates it changes nothing, and the point's penalty (the reference's sum over the obstacles in
-    // order) is formed afterwards from the pairs' shares.  (round 6: configs[4] at 1024 1.90 -> see docs/HISTORY.md)
-    const int tS0 = 5 * H, cap = sm.list_cap;
-    int *npairs = (int *)(sm.ist + 15);
-    if (tid == 0) *npairs = 0;
-    team_sync<WAVE>();
-    // a pair, evaluated in full by whoever holds it: the point's state is formed again from scratch (the same expressions, the same bits)
-    auto pair_eval = [&](int pt, int sur_id) {
-      int p, j, sg, lp, K, N, singul_;
-      double cc[12], step, s1, trajtime;
-      point_ctx(pt, p, j, sg, lp, K, N, singul_, cc, step, s1, trajtime);
-      PtState st;
-      double pl[4 * HMAX];
-      load_planes<HMAX>(cor_b + pt, (size_t)D.NptsPad, H, pl);
-      (void)point_masks<SUR, HMAX, true>(P, cc, lp, N, j, K, step, s1, singul_, D.epis, H, pl, (gd_t) nullptr, D.sur, D.t_now, sm.pA[p], sg, trajtime, st);
-      const gd_t rec_pt = rec_b + (size_t)pt * nterm * kRec;
-      double pen;
-      if (point_surround_one<false>(P, D.sur, st, sur_id, D.t_now, j, lp, N, sm.pA[p], singul_, sg, trajtime, tS0, rec_pt, pen)) {
-        rec_pt[(size_t)(tS0 + sur_id) * kRec + 13] = pen; // (the pair's share; the point's sum is formed below)
-        const int bit = tS0 + sur_id;
-        atomicOr((int *)(sm.pmask + (sm.mw == 2 ? 2 * pt + (bit >> 5) : pt)), 1 << (bit & 31));
-      }
-    };
-    for (int pt = tid; pt < Npts; pt += T) {
-      int p, j, sg, lp, K, N, singul_;
-      double cc[12], step, s1, trajtime;
-      point_ctx(pt, p, j, sg, lp, K, N, singul_, cc, step, s1, trajtime);
-      PtState st;
-      st.K = -1; // (stays -1 for a point the reference skips, traj_optimizer.cpp:550-553)
-      double pl[4 * HMAX];
-      load_planes<HMAX>(cor_b + pt, (size_t)D.NptsPad, H, pl);
-      const mask_t mask = point_masks<SUR, HMAX, true>(P, cc, lp, N, j, K, step, s1, singul_, D.epis, H, pl, (gd_t) nullptr, D.sur, D.t_now, sm.pA[p], sg, trajtime, st);
-      const gd_t rec_pt = rec_b + (size_t)pt * nterm * kRec;
-      for (mask_t mm = mask; mm;) {
-        const int t = __builtin_ctzll(mm);
-        mm &= mm - 1;
-        point_emit(P, st, t, H, tS0 + nS, cor_b + pt, (size_t)D.NptsPad, rec_pt + (size_t)t * kRec);
-      }
-      sm.set_mask(pt, mask);
-      if (st.K >= 0) {
-        for (int sur_id = 0; sur_id < nS; sur_id++) {
-          double pen;
-          if (!point_surround_one<true>(P, D.sur, st, sur_id, D.t_now, j, lp, N, sm.pA[p], singul_, sg, trajtime, tS0, rec_pt, pen)) continue;
-          const int slot = atomicAdd(npairs, 1);
-          if (slot < cap) sm.list[slot] = (pt << 4) | sur_id;
-          else pair_eval(pt, sur_id); // (more pairs than the list holds: this one at once)
+          chain_add(acc, jb.kind, entry & 63, tS0, t0, entry < 0, va8[u], Nseg, jb.sg, [&](double &vb, double &vc, int &pieceid) {
+            vb = vb8[u];
+            vc = vc8[u];
+            pieceid = sm.pinfo[4 * (int)D.pt_piece[(entry >> 6) & 0x1ffffff] + 1];
+          });
         }
       }
     }
-    __threadfence_block();
-    team_sync<WAVE>();
-    const int np = *npairs < cap ? *npairs : cap;
-    for (int q = tid; q < np; q += T) pair_eval(sm.list[q] >> 4, sm.list[q] & 15);
-    __threadfence_block(); // the pairs' records and shares are read by other lanes below
-    team_sync<WAVE>();
-    // the point's penalty: the shares of its active obstacles added in obstacle order from 0.0, kept in slot [13] of the first one
-    for (int pt = tid; pt < Npts; pt += T) {
-      const mask_t m = sm.mask(pt);
-      const unsigned sb = (unsigned)((m >> tS0) & (((mask_t)1 << nS) - 1ull));
-      if (!sb) continue;
-      const gd_t rec_pt = rec_b + (size_t)pt * nterm * kRec;
-      double total = 0.0;
-      for (int sur_id = 0; sur_id < nS; sur_id++)
-        if (sb & (1u << sur_id)) {
-          total += rec_pt[(size_t)(tS0 + sur_id) * kRec + 13];
-          rec_pt[(size_t)(tS0 + sur_id) * kRec + 13] = 0.0;
-        }
-      rec_pt[(size_t)(tS0 + __builtin_ctz(sb)) * kRec + 13] = total;
-    }
-  } else {
-    for (int pt = tid; pt < Npts; pt += T) {
-      int p, j, sg, lp, K, N, singul_;
-      double cc[12], step, s1, trajtime;
-      point_ctx(pt, p, j, sg, lp, K, N, singul_, cc, step, s1, trajtime);
-      sm.set_mask(pt, point_terms<SUR, HMAX>(P, cc, lp, N, j, K, step, s1, singul_, D.epis, H, cor_b + pt, (size_t)D.NptsPad,
-                                             rec_b + (size_t)pt * nterm * kRec, D.sur, D.t_now, SUR ? sm.pA[p] : 0.0, sg, trajtime));
-    }
+    *jb.dst = acc;
   }
-  __threadfence_block(); // the records are read back by other lanes of this team
-  team_sync<WAVE>();
-  pr.tick(2);
-  // ---- number the active terms in (point, term) order: exclusive prefix sum of the counts (wave 0); second job: the start
-  // values of the per-segment chains (`gdT +=`, `energy +=` over the pieces in order, from 0.0)
-  if (tid < 64) {
-    const int per = (Npts + 63) >> 6, start = tid * per;
-    int sum = 0;
-    for (int i = start; i < start + per && i < Npts; i++) sum += __builtin_popcountll(sm.mask(i));
-    int incl = sum;
+}
+
+// ================= TEAM shape: the constraint points, each on a lane of its own; a record per active term in the point's own slots
+// rec_b[pt][t][kRec] (global scratch), the point's mask of active terms in LDS
+template <bool SUR, int HMAX>
+__device__ __forceinline__ void team_point_pass(const DevBatch &D, gcd_t cor_b, gd_t rec_b, const Sm &sm, int tid, int T, int nS) {
+  const int Npts = D.L.Npts, H = D.L.H, nterm = 5 * H + nS + 4;
+  for (int pt = tid; pt < Npts; pt += T) {
+    PointCtx c;
+    point_ctx<SUR>(D, sm, pt, c);
+    sm.set_mask(pt, point_terms<SUR, HMAX>(D.P, c.cc, c.lp, c.N, c.j, c.K, c.step, c.s1, c.singul, D.epis, H, cor_b + pt, (size_t)D.NptsPad,
+                                           rec_b + (size_t)pt * nterm * kRec, D.sur, D.t_now, c.t_piece, c.sg, c.trajtime));
+  }
+}
+
+// the number of collected pairs, in the team's integer state
+__device__ __forceinline__ int *team_npairs(const Sm &sm) { return (int *)(sm.ist + 15); }
+// the point's penalty: the shares of its active obstacles added in obstacle order from 0.0, kept in slot [13] of the first one
+__device__ __forceinline__ void team_point_penalties(const DevBatch &D, gd_t rec_b, const Sm &sm, int tid, int T) {
+  const int Npts = D.L.Npts, nS = D.sur.S, tS0 = 5 * D.L.H, nterm = tS0 + nS + 4;
+  for (int pt = tid; pt < Npts; pt += T) {
+    const mask_t m = sm.mask(pt);
+    const unsigned sb = (unsigned)((m >> tS0) & (((mask_t)1 << nS) - 1ull));
+    if (!sb) continue;
+    const gd_t rec_pt = rec_b + (size_t)pt * nterm * kRec;
+    double total = 0.0;
+    for (int sur_id = 0; sur_id < nS; sur_id++)
+      if (sb & (1u << sur_id)) {
+        total += rec_pt[(size_t)(tS0 + sur_id) * kRec + 13];
+        rec_pt[(size_t)(tS0 + sur_id) * kRec + 13] = 0.0;
+      }
+    rec_pt[(size_t)(tS0 + __builtin_ctz(sb)) * kRec + 13] = total;
+  }
+}
+
+// ---- number the active terms in (point, term) order: exclusive prefix sum of the counts (wave 0 calls it)
+__device__ __forceinline__ void team_number_terms(const Sm &sm, int Npts, int tid) {
+  const int per = (Npts + 63) >> 6, start = tid * per;
+  int sum = 0;
+  for (int i = start; i < start + per && i < Npts; i++) sum += __builtin_popcountll(sm.mask(i));
+  int incl = sum;
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int up = __shfl_up(incl, o);
-      if (tid >= o) incl += up;
-    }
-    int run = incl - sum;
-    for (int i = start; i < start + per && i < Npts; i++) {
-      sm.set_first(i, run);
-      run += __builtin_popcountll(sm.mask(i));
-    }
-    if (tid == 63) sm.set_first(Npts, incl);
+  for (int o = 1; o < 64; o <<= 1) {
+    const int up = __shfl_up(incl, o);
+    if (tid >= o) incl += up;
   }
-  if (u2 >= 0 && u2 < M) {
-    const int sg = u2;
-    int p0 = 0, p1 = 0;
-    for (int q = 0; q < M; q++) {
-      p0 = q == sg ? L.seg_piece0[q] : p0;
-      p1 = q == sg ? L.seg_piece0[q + 1] : p1;
-    }
-    double gdT = 0.0, en = 0.0;
-    for (int i = p0; i < p1; i++) {
-      gdT += sm.pG[i];
-      en += sm.pE[i];
-    }
-    sm.segsum[gNUM * sg + gGDT] = gdT;
-    sm.segsum[gNUM * sg + gENERGY] = en;
-    sm.segsum[gNUM * sg + gCOST0] = 0.0;
-    sm.segsum[gNUM * sg + gCOST2] = 0.0;
-    sm.segsum[gNUM * sg + gCOST1] = 0.0;
+  int run = incl - sum;
+  for (int i = start; i < start + per && i < Npts; i++) {
+    sm.set_first(i, run);
+    run += __builtin_popcountll(sm.mask(i));
   }
-  team_sync<WAVE>();
-  // ---- chains: the active terms in windows of list_cap; lane (piece, entry) adds its piece's records in order, four more
-  // lanes per segment walk all of the segment's for gdT, the corridor cost, the feasibility cost and the moving-obstacle cost
-  const int n_act = sm.first(Npts);
-  const int n_chain = 12 * Ntot + 4 * M;
-  const int cap = sm.list_cap;
-  pr.tick(10);     // numbering
-  pr.count(9, n_act); // active terms of this evaluation (a count, not cycles)
-  for (int c0 = 0; c0 < n_act; c0 += cap) {
-    const int c1 = c0 + cap < n_act ? c0 + cap : n_act;
-    for (int pt = tid; pt < Npts; pt += T) {
-      mask_t m = sm.mask(pt);
-      int e = sm.first(pt);
-      while (m) {
-        const int t = __builtin_ctzll(m);
-        m &= m - 1;
-        if (e >= c0 && e < c1) sm.list[e - c0] = (pt << 6) | t;
-        e++;
+  if (tid == 63) sm.set_first(Npts, incl);
+}
+
+// ---- chains: the active terms in windows of list_cap.  The list of window [c0, c1): (point << 6 | term) of its terms
+__device__ __forceinline__ void team_window_list(const Sm &sm, int Npts, int tid, int T, int c0, int c1) {
+  for (int pt = tid; pt < Npts; pt += T) {
+    mask_t m = sm.mask(pt);
+    int e = sm.first(pt);
+    while (m) {
+      const int t = __builtin_ctzll(m);
+      m &= m - 1;
+      if (e >= c0 && e < c1) sm.list[e - c0] = (pt << 6) | t;
+      e++;
+    }
+  }
+}
+// a lane per chain (decode_chain_job) adds the part of its terms that lies in the window
+__device__ __forceinline__ void team_chain_window(const DevBatch &D, gd_t rec_b, const Sm &sm, int tid, int T, int nS, int c0, int c1) {
+  const DevLayout &L = D.L;
+  const int n_chain = 12 * L.Ntot + 4 * L.M, tS0 = 5 * L.H, tS1 = tS0 + nS, nterm = tS1 + 4;
+  for (int w = tid; w < n_chain; w += T) {
+    const ChainJob jb = decode_chain_job<false>(L, sm, w);
+    const int e0 = jb.e0 > c0 ? jb.e0 : c0, e1 = jb.e1 < c1 ? jb.e1 : c1, q = jb.q;
+    if (e1 <= e0) continue;
+    double acc = *jb.dst;
+    if (jb.kind < 0) { // an entry of gdC: every term of the piece, in order
+      int e = e0;
+      for (; e + 8 <= e1; e += 8) {
+        int id[8];
+        double v[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) id[u] = sm.list[e + u - c0];
+#pragma unroll
+        for (int u = 0; u < 8; u++) v[u] = rec_b[((size_t)(id[u] >> 6) * nterm + (id[u] & 63)) * kRec + q];
+#pragma unroll
+        for (int u = 0; u < 8; u++) acc += v[u];
+      }
+      for (; e < e1; e++) {
+        const int id = sm.list[e - c0];
+        acc += rec_b[((size_t)(id >> 6) * nterm + (id & 63)) * kRec + q];
+      }
+    } else {
+      // the per-segment chains: what an entry adds depends on its kind of term; its values are requested eight entries at
+      // a time in front of the additions (slots 14 / 15 only mean something for a moving-obstacle term and are only used there)
+      const mask_t smask = nS > 0 ? (((mask_t)1 << nS) - 1ull) : 0ull;
+      const int Nseg = seg_info(L, jb.sg).N;
+      for (int e = e0; e < e1; e += 8) {
+        int id[8];
+        double va[8], vb8[8], vc8[8];
+        mask_t pm[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) id[u] = sm.list[(e + u < e1 ? e + u : e1 - 1) - c0];
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+          gcd_t r_ = (gcd_t)(rec_b + ((size_t)(id[u] >> 6) * nterm + (id[u] & 63)) * kRec);
+          va[u] = r_[q];
+          vb8[u] = r_[14];
+          vc8[u] = r_[15];
+          pm[u] = sm.mask(id[u] >> 6);
+        }
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+          if (e + u >= e1) break;
+          const int t = id[u] & 63;
+          // the first active obstacle term of its point: the lowest obstacle bit of the point's mask
+          const bool first_sur = jb.kind == kChainCost1 && t >= tS0 && t < tS1 && (int)__builtin_ctzll((pm[u] >> tS0) & smask) == t - tS0;
+          chain_add(acc, jb.kind, t, tS0, tS1, first_sur, va[u], Nseg, jb.sg, [&](double &vb, double &vc, int &pieceid) {
+            vb = vb8[u];
+            vc = vc8[u];
+            pieceid = sm.pinfo[4 * (int)D.pt_piece[id[u] >> 6] + 1];
+          });
+        }
       }
     }
-    team_sync<WAVE>();
-    pr.tick(11);   // the window's list
-    for (int w = tid; w < n_chain; w += T) {
-      int e0, e1, q, kind = -1, csg = 0;
-      ldsd_t dst;
-      if (w < 12 * Ntot) {
-        const int p = w / 12;
-        q = w - 12 * p;
-        const int pt0 = sm.pinfo[4 * p + 2], pt1 = pt0 + sm.pinfo[4 * p + 3] + 1;
-        e0 = sm.first(pt0);
-        e1 = sm.first(pt1);
-        dst = sm.gdC + w;
-      } else {
-        const int v = w - 12 * Ntot, sg = v >> 2, kd = v & 3; // per segment: 0 gdT, 1 corridor cost, 2 feasibility cost, 3 moving-obstacle cost
-        int a0 = 0, a1 = 0;
-        for (int q2 = 0; q2 < M; q2++) {
-          a0 = q2 == sg ? L.seg_pt0[q2] : a0;
-          a1 = q2 == sg ? L.seg_pt0[q2 + 1] : a1;
-        }
-        e0 = sm.first(a0);
-        e1 = sm.first(a1);
-        q = kd == 0 ? 12 : 13;
-        dst = sm.segsum + gNUM * sg + (kd == 0 ? gGDT : (kd == 1 ? gCOST0 : (kd == 2 ? gCOST2 : gCOST1)));
-        kind = kd;
-        csg = sg;
-      }
-      e0 = e0 > c0 ? e0 : c0;
-      e1 = e1 < c1 ? e1 : c1;
-      if (e1 <= e0) continue;
-      double acc = *dst;
-      const int tS0 = 5 * H, tS1 = 5 * H + nS;
-      if (kind < 0) { // an entry of gdC: every term of the piece, in order
-        int e = e0;
-        for (; e + 8 <= e1; e += 8) {
-          int id[8];
-          double v[8];
-#pragma unroll
-          for (int u = 0; u < 8; u++) id[u] = sm.list[e + u - c0];
-#pragma unroll
-          for (int u = 0; u < 8; u++) v[u] = rec_b[((size_t)(id[u] >> 6) * nterm + (id[u] & 63)) * kRec + q];
-#pragma unroll
-          for (int u = 0; u < 8; u++) acc += v[u];
-        }
-        for (; e < e1; e++) {
-          const int id = sm.list[e - c0];
-          acc += rec_b[((size_t)(id >> 6) * nterm + (id & 63)) * kRec + q];
-        }
-      } else {
-        // the per-segment chains: what an entry adds depends on its kind of term; its values are requested eight entries at
-        // a time in front of the additions (slots 14 / 15 only mean something for a moving-obstacle term and are only used there)
-        const mask_t smask = nS > 0 ? (((mask_t)1 << nS) - 1ull) : 0ull;
-        int Nseg = 0;
-        for (int q2 = 0; q2 < M; q2++) Nseg = q2 == csg ? L.piece_nums[q2] : Nseg;
-        for (int e = e0; e < e1; e += 8) {
-          int id[8];
-          double va[8], vb[8], vc[8];
-          mask_t pm[8];
-#pragma unroll
-          for (int u = 0; u < 8; u++) id[u] = sm.list[(e + u < e1 ? e + u : e1 - 1) - c0];
-#pragma unroll
-          for (int u = 0; u < 8; u++) {
-            gcd_t r_ = (gcd_t)(rec_b + ((size_t)(id[u] >> 6) * nterm + (id[u] & 63)) * kRec);
-            va[u] = r_[kind == 0 ? 12 : 13];
-            vb[u] = r_[14];
-            vc[u] = r_[15];
-            pm[u] = sm.mask(id[u] >> 6);
-          }
-#pragma unroll
-          for (int u = 0; u < 8; u++) {
-            if (e + u >= e1) break;
-            const int t = id[u] & 63;
-            const bool sur_term = t >= tS0 && t < tS1;
-            if (kind == 0) { // gdT: one `+=` per term; a moving-obstacle term: three, and one more per previous segment (traj_optimizer.cpp:1663-1676)
-              acc += va[u];
-              if (sur_term) {
-                const int lp = sm.pinfo[4 * (int)D.pt_piece[id[u] >> 6] + 1]; // pieceid
-                acc += vb[u] * lp;
-                acc += vc[u];
-                const double prev = vb[u] * Nseg; // ... * piece_num_container[trajid]
-                for (int idx = 0; idx < csg; idx++) acc += prev;
-              }
-            } else if (kind == 1) {
-              if (t < tS0) acc += va[u];
-            } else if (kind == 2) {
-              if (t >= tS1) acc += va[u];
-            } else if (sur_term) { // costs(1) += the point's penalty, once per point: carried by its first active obstacle term
-              const mask_t sb = (pm[u] >> tS0) & smask;
-              if ((int)__builtin_ctzll(sb) == t - tS0) acc += va[u];
-            }
-          }
-        }
-      }
-      *dst = acc;
-    }
-    team_sync<WAVE>();
+    *jb.dst = acc;
   }
-  } // TEAM shape
-  pr.tick(3);
-  // ---- calGrads_PT (poly_traj_utils.hpp:1037-1066): adj = gdC * tInv, solveAdj, the duration gradient
-  for (int w = tid; w < 12 * Ntot; w += T) {
-    const int p = w / 12, k = (w - 12 * p) >> 1;
-    sm.adj[w] = sm.gdC[w] * sm.seg[16 * sm.pinfo[4 * p] + 8 + k];
-  }
-  team_sync<WAVE>();
-  if (tid < 2 * M) {
-    const int sg = tid >> 1, d = tid & 1;
-    int N = 0, p0 = 0;
-    for (int q = 0; q < M; q++) {
-      N = q == sg ? L.piece_nums[q] : N;
-      p0 = q == sg ? L.seg_piece0[q] : p0;
-    }
-    int toff = 0;
-    for (int q = 0; q < M; q++) toff += q < sg ? pk_segment_doubles(L.piece_nums[q]) : 0;
-    ldscd_t tb = sm.tab + toff;
-    sweep<2>(tb + pk_sweep_offset(2, N), sm.adj + 12 * p0, 6 * N, d);
-    sweep<3>(tb + pk_sweep_offset(3, N), sm.adj + 12 * p0, 6 * N, d);
-  }
-  for (int i = u2; i >= 0 && i < Ntot; i += (WAVE ? 64 : T - 64)) { // the per-piece chain-rule terms (they only need gdC and b)
+}
+
+// ---- calGrads_PT (poly_traj_utils.hpp:1037-1066) behind adj = gdC * tInv: solveAdj; second job: the per-piece chain-rule terms of
+// the duration gradient (they only need gdC and b)
+template <bool WAVE> __device__ __forceinline__ void eval_adjoint_solve(const DevBatch &D, const Sm &sm, int tid, int T, int u2) {
+  const DevLayout &L = D.L;
+  if (tid < 2 * L.M) seg_sweeps<2, 3>(L, sm, sm.adj, tid);
+  for (int i = u2; i >= 0 && i < L.Ntot; i += (WAVE ? 64 : T - 64)) {
     ldscd_t tInv = sm.seg + 16 * sm.pinfo[4 * i] + 8;
     sm.pA[i] = piece_gdtinv_sum(tInv, (ldscd_t)(sm.gdC + 12 * i), (ldscd_t)(sm.b + 12 * i));
   }
-  team_sync<WAVE>();
-  pr.tick(4);
-  // ---- gradient and cost (traj_optimizer.cpp:299-344)
-  for (int e = tid; e < L.x_tau0; e += T) { // gdP of every segment: rows 6 i + 5 of its adjoint
+}
+
+// ---- gradient and cost (traj_optimizer.cpp:299-344), four jobs side by side.  gdP of every segment: rows 6 i + 5 of its adjoint
+__device__ __forceinline__ void grad_waypoints(const DevLayout &L, const Sm &sm, ldsd_t g, int tid, int T) {
+  for (int e = tid; e < L.x_tau0; e += T) {
     int x0 = 0, p0 = 0;
-    for (int q = 0; q < M; q++) {
+    for (int q = 0; q < L.M; q++) { // (the segment whose waypoints hold element e: a search, not seg_info's pick)
       const bool in = e >= L.seg_x0[q];
       x0 = in ? L.seg_x0[q] : x0;
       p0 = in ? L.seg_piece0[q] : p0;
@@ -932,67 +755,269 @@ __device__ DFTPAV_REF_EVAL_ATTR void ref_eval(const DevBatch &D, gcd_t cor_b, gd
     const int w = e - x0;
     g[e] = sm.adj[12 * p0 + 2 * (6 * (w >> 1) + 5) + (w & 1)];
   }
-  if (tid < M) { // the duration gradient of segment tid (poly_traj_utils.hpp:1050-1064, VirtualTGradCost :405-419)
-    const int sg = tid;
-    int N = 0, p0 = 0;
-    for (int q = 0; q < M; q++) {
-      N = q == sg ? L.piece_nums[q] : N;
-      p0 = q == sg ? L.seg_piece0[q] : p0;
-    }
-    ldscd_t adj = sm.adj + 12 * p0;
-    ldscd_t hv = sm.pva + 12 * sg, tv = hv + 6;
-    const double t1 = sm.seg[16 * sg + 3];
-    double gdT = sm.segsum[gNUM * sg + gGDT];
-    double h1, h2, g1, g2;
-    duration_grad_ends(hv, tv, adj, adj + 12 * (N - 1), t1, h1, h2, g1, g2);
-    gdT += h1;
-    gdT += h2;
-    gdT += g1;
-    gdT += g2;
-    for (int i = 0; i < N; i++) gdT += sm.pA[p0 + i];
-    g[L.x_tau0 + sg] = (gdT / N + P.wei_time) * virtual_T_grad_factor(x[L.x_tau0 + sg]);
-  }
-  if (u2 >= 0 && u2 < M - 1 && P.gear_opt) { // junction i: position and angle (traj_optimizer.cpp:307-320)
-    const int i = u2;
-    int Ni = 0, p0i = 0, p0n = 0;
-    for (int q = 0; q < M; q++) {
-      Ni = q == i ? L.piece_nums[q] : Ni;
-      p0i = q == i ? L.seg_piece0[q] : p0i;
-      p0n = q == i + 1 ? L.seg_piece0[q] : p0n;
-    }
-    ldscd_t adji = sm.adj + 12 * p0i, adjn = sm.adj + 12 * p0n;
-    const int r3 = 6 * Ni - 3;
-    const double t1i = sm.seg[16 * i + 3], t1n = sm.seg[16 * (i + 1) + 3];
-    // gdTail of segment i and gdHead of segment i + 1 (poly_traj_utils.hpp:1045-1049: adj row * t^k)
-    const double fin0[2] = {adji[2 * r3] * 1.0, adji[2 * r3 + 1] * 1.0}, fin1[2] = {adji[2 * (r3 + 1)] * t1i, adji[2 * (r3 + 1) + 1] * t1i};
-    const double ini0[2] = {adjn[0] * 1.0, adjn[1] * 1.0}, ini1[2] = {adjn[2] * t1n, adjn[3] * t1n};
-    const double cs = sm.trig[2 * i], sn = sm.trig[2 * i + 1];
-    // grad is zeroed, then segment i adds its tail term, then segment i + 1 its head term (trajid ascending)
-    for (int d = 0; d < 2; d++) {
-      double v = 0.0;
-      v += fin0[d];
-      v += ini0[d];
-      g[L.x_gear0 + 2 * i + d] = v;
-    }
-    double va = 0.0;
-    va += fin1[0] * (-P.non_sinv * sn) + fin1[1] * (P.non_sinv * cs);
-    va += ini1[0] * (P.non_sinv * sn) + ini1[1] * (-P.non_sinv * cs);
-    g[L.x_ang0 + i] = va;
-  } else if (u2 >= 0 && u2 < M - 1) { // gear_opt off: the junction variables keep a zero gradient
-    const int i = u2;
+}
+// the duration gradient of segment sg (poly_traj_utils.hpp:1050-1064, VirtualTGradCost :405-419)
+__device__ __forceinline__ void grad_duration(const DevBatch &D, const Sm &sm, ldscd_t x, ldsd_t g, int sg) {
+  const DevLayout &L = D.L;
+  const SegInfo si = seg_info(L, sg);
+  const int N = si.N, p0 = si.piece0;
+  ldscd_t adj = sm.adj + 12 * p0;
+  ldscd_t hv = sm.pva + 12 * sg, tv = hv + 6;
+  const double t1 = sm.seg[16 * sg + 3];
+  double gdT = sm.segsum[gNUM * sg + gGDT];
+  double h1, h2, g1, g2;
+  duration_grad_ends(hv, tv, adj, adj + 12 * (N - 1), t1, h1, h2, g1, g2);
+  gdT += h1;
+  gdT += h2;
+  gdT += g1;
+  gdT += g2;
+  for (int i = 0; i < N; i++) gdT += sm.pA[p0 + i];
+  g[L.x_tau0 + sg] = (gdT / N + D.P.wei_time) * virtual_T_grad_factor(x[L.x_tau0 + sg]);
+}
+// junction i: position and angle (traj_optimizer.cpp:307-320)
+__device__ __forceinline__ void grad_junction(const DevBatch &D, const Sm &sm, ldsd_t g, int i) {
+  const DevLayout &L = D.L;
+  const DevParams &P = D.P;
+  if (!P.gear_opt) { // the junction variables keep a zero gradient
     g[L.x_gear0 + 2 * i] = 0.0;
     g[L.x_gear0 + 2 * i + 1] = 0.0;
     g[L.x_ang0 + i] = 0.0;
+    return;
   }
-  if (tid == (T > 128 ? 128 : 0)) { // the cost: sums over the segments in order (:292-297, :328-330)
-    double total_smcost = 0.0, total_timecost = 0.0, penalty_cost = 0.0;
-    for (int sg = 0; sg < M; sg++) {
-      total_smcost += sm.segsum[gNUM * sg + gENERGY];
-      penalty_cost += (sm.segsum[gNUM * sg + gCOST0] + sm.segsum[gNUM * sg + gCOST1]) + sm.segsum[gNUM * sg + gCOST2];
+  const SegInfo si = seg_info(L, i);
+  const int Ni = si.N, p0i = si.piece0, p0n = si.piece1; // (segment i + 1 starts where segment i ends)
+  ldscd_t adji = sm.adj + 12 * p0i, adjn = sm.adj + 12 * p0n;
+  const int r3 = 6 * Ni - 3;
+  const double t1i = sm.seg[16 * i + 3], t1n = sm.seg[16 * (i + 1) + 3];
+  // gdTail of segment i and gdHead of segment i + 1 (poly_traj_utils.hpp:1045-1049: adj row * t^k)
+  const double fin0[2] = {adji[2 * r3] * 1.0, adji[2 * r3 + 1] * 1.0}, fin1[2] = {adji[2 * (r3 + 1)] * t1i, adji[2 * (r3 + 1) + 1] * t1i};
+  const double ini0[2] = {adjn[0] * 1.0, adjn[1] * 1.0}, ini1[2] = {adjn[2] * t1n, adjn[3] * t1n};
+  const double cs = sm.trig[2 * i], sn = sm.trig[2 * i + 1];
+  // grad is zeroed, then segment i adds its tail term, then segment i + 1 its head term (trajid ascending)
+  for (int d = 0; d < 2; d++) {
+    double v = 0.0;
+    v += fin0[d];
+    v += ini0[d];
+    g[L.x_gear0 + 2 * i + d] = v;
+  }
+  double va = 0.0;
+  va += fin1[0] * (-P.non_sinv * sn) + fin1[1] * (P.non_sinv * cs);
+  va += ini1[0] * (P.non_sinv * sn) + ini1[1] * (-P.non_sinv * cs);
+  g[L.x_ang0 + i] = va;
+}
+// the cost: sums over the segments in order (:292-297, :328-330)
+__device__ __forceinline__ void eval_cost(const DevBatch &D, const Sm &sm) {
+  const int M = D.L.M;
+  double total_smcost = 0.0, total_timecost = 0.0, penalty_cost = 0.0;
+  for (int sg = 0; sg < M; sg++) {
+    total_smcost += sm.segsum[gNUM * sg + gENERGY];
+    penalty_cost += (sm.segsum[gNUM * sg + gCOST0] + sm.segsum[gNUM * sg + gCOST1]) + sm.segsum[gNUM * sg + gCOST2];
+  }
+  for (int sg = 0; sg < M; sg++) total_timecost += sm.seg[16 * sg] * D.P.wei_time;
+  sm.st[sF] = total_smcost + total_timecost + penalty_cost;
+}
+__device__ __forceinline__ void eval_gradient_and_cost(const DevBatch &D, const Sm &sm, ldscd_t x, ldsd_t g, int tid, int T, int u2) {
+  const int M = D.L.M;
+  grad_waypoints(D.L, sm, g, tid, T);
+  if (tid < M) grad_duration(D, sm, x, g, tid);
+  if (u2 >= 0 && u2 < M - 1) grad_junction(D, sm, g, u2);
+  if (tid == (T > 128 ? 128 : 0)) eval_cost(D, sm);
+}
+
+template <bool SUR, bool WAVE, int HMAX = 5>
+__device__ DFTPAV_REF_EVAL_ATTR void ref_eval(const DevBatch &D, gcd_t cor_b, gd_t rec_b, const Sm &sm, ldscd_t x, ldsd_t g, Prof &pr) {
+  const DevLayout &L = D.L;
+  const int tid = WAVE ? (int)(threadIdx.x & 63) : (int)threadIdx.x, T = WAVE ? 64 : (int)blockDim.x;
+  const int u2 = WAVE ? tid : tid - 64;
+  const int M = L.M, nS = SUR ? D.sur.S : 0;
+  eval_durations_trig(D, sm, x, tid, u2);
+  team_sync<WAVE>();
+  eval_boundary_states(D, sm, x, tid);
+  team_sync<WAVE>();
+  eval_rhs(D, sm, x, tid, T);
+  team_sync<WAVE>();
+  eval_forward_solve(D, sm, tid, u2, nS);
+  team_sync<WAVE>();
+  pr.tick(0);
+  eval_rows_times_tinv(D, sm, sm.b, sm.c, tid, T); // c = b * tInv
+  team_sync<WAVE>();
+  eval_piece_jerk(D, sm, tid, T);
+  pr.tick(1);
+  if (WAVE) {
+    const int base = wave_point_pass<SUR>(D, cor_b, rec_b, sm, tid, nS);
+    if (tid < M) seg_chain_starts(sm, L, tid);
+    __threadfence_block(); // records beyond the LDS window went to global memory
+    team_sync<WAVE>();
+    pr.tick(2);
+    pr.count(9, base);                       // active terms of this evaluation (a count, not cycles)
+    pr.count(10, base > sm.nrec ? 1 : 0);    // evaluations whose records do not all fit the LDS window ...
+    pr.count(11, base > sm.nrec ? base : 0); // ... and their active terms
+    if (base > 0 && base <= kSerialMax) {
+      // Up to a few hundred active terms (nearly every evaluation; most have all their records in LDS): ONE pass over the terms in
+      // order on 16 lanes -- lane q < 12 carries entry q of gdC of the piece the terms belong to, lane 12 that segment's gdT,
+      // lane 13 its three costs -- each term one read and one addition per lane, the reads of sixteen terms in flight (the ones
+      // beyond the LDS window come from L2: one round trip per sixteen terms for all the sums together); a change of piece
+      // (segment) stores the sums and fetches the next piece's (segment's).  Same chains as the lanes per (piece, entry) of
+      // wave_chain_wide, term after term.
+      // (the text stands here: as a function of its own the pass compiles to 1 900 more instructions, docs/HISTORY.md)
+      if (tid < 16) {
+        constexpr int kU = 16;
+        const int nrec = sm.nrec, tS0 = 5 * L.H, t0 = tS0 + nS;
+        const int *glist = wave_scratch(L, rec_b, nS).glist;
+        int curp = -1, cursg = -1, Nseg = 0;
+        double acc = 0.0, c2 = 0.0, c1 = 0.0;
+        for (int e0 = 0; e0 < base; e0 += kU) {
+          int ent[kU], pc[kU];
+          double v[kU];
+#pragma unroll
+          for (int u = 0; u < kU; u++) {
+            const int e = e0 + u < base ? e0 + u : base - 1;
+            if (e < nrec) { // (uniform)
+              ent[u] = sm.list[e];
+              pc[u] = sm.list[nrec + e];
+              v[u] = sm.lrec[(size_t)e * kRec + tid];
+            } else {
+              ent[u] = glist[2 * e];
+              pc[u] = glist[2 * e + 1];
+              v[u] = rec_b[(size_t)e * kRec + tid];
+            }
+          }
+#pragma unroll
+          for (int u = 0; u < kU; u++) {
+            if (e0 + u >= base) break; // uniform
+            const int p = pc[u], e = e0 + u;
+            if (p != curp) { // uniform: the terms come piece after piece, segment after segment
+              const int sg = sm.pinfo[4 * p];
+              if (tid < 12) {
+                if (curp >= 0) sm.gdC[12 * curp + tid] = acc;
+                acc = sm.gdC[12 * p + tid];
+              } else if (sg != cursg) {
+                if (cursg >= 0) serial_seg_store(sm, tid, cursg, acc, c2, c1);
+                serial_seg_fetch(sm, tid, sg, acc, c2, c1);
+              }
+              if (sg != cursg) Nseg = seg_info(L, sg).N;
+              curp = p;
+              cursg = sg;
+            }
+            const int t = ent[u] & 63;
+            const bool first_sur = ent[u] < 0;
+            auto sur = [&](double &vb, double &vc, int &pieceid) {
+              vb = wave_rec(sm, rec_b, e, 14);
+              vc = wave_rec(sm, rec_b, e, 15);
+              pieceid = sm.pinfo[4 * p + 1];
+            };
+            if (tid < 12) {
+              acc += v[u];
+            } else if (tid == 12) {
+              chain_add(acc, kChainGdT, t, tS0, t0, first_sur, v[u], Nseg, cursg, sur);
+            } else if (tid == 13) {
+              chain_add(acc, kChainCost0, t, tS0, t0, first_sur, v[u], Nseg, cursg, sur);
+              chain_add(c2, kChainCost2, t, tS0, t0, first_sur, v[u], Nseg, cursg, sur);
+              chain_add(c1, kChainCost1, t, tS0, t0, first_sur, v[u], Nseg, cursg, sur);
+            }
+          }
+        }
+        if (tid < 12) sm.gdC[12 * curp + tid] = acc;
+        serial_seg_store(sm, tid, cursg, acc, c2, c1);
+      }
+      team_sync<WAVE>();
+    } else if (base > 0) {
+      wave_chain_wide(D, rec_b, sm, tid, nS);
+      team_sync<WAVE>();
     }
-    for (int sg = 0; sg < M; sg++) total_timecost += sm.seg[16 * sg] * P.wei_time;
-    sm.st[sF] = total_smcost + total_timecost + penalty_cost;
+  } else {
+    if (SUR && nS > 0) {
+      // Moving obstacles: a (point, obstacle) pair that reaches its forty correctly rounded exponentials costs 40 k cycles, and one such
+      // lane holds its whole wave.  So the pairs are COLLECTED first -- every point runs its static tests and, per obstacle, the cheap tests
+      // (hull box, distance gate, the bound before any exponential) -- and then evaluated densely packed, one pair per lane; a pair's record
+      // has a place of its own, so who evaluates it changes nothing, and the point's penalty (the reference's sum over the obstacles in
+      // order) is formed afterwards from the pairs' shares.  (round 6: configs[4] at 1024 1.90 -> see docs/HISTORY.md)
+      // (collect / evaluate / sum stand here, the pair's evaluation as a lambda: as functions of their own they cost the five kernels
+      // 70-100 more spilled registers, docs/HISTORY.md)
+      // a pair, evaluated in full by whoever holds it: the point's state is formed again from scratch (the same expressions, the same bits)
+      const int Npts = L.Npts, H = L.H, nterm = 5 * H + nS + 4, tS0 = 5 * H, cap = sm.list_cap;
+      auto pair_eval = [&](int pt, int sur_id) {
+        PointCtx c;
+        point_ctx<true>(D, sm, pt, c);
+        PtState st;
+        double pl[4 * HMAX];
+        load_planes<HMAX>(cor_b + pt, (size_t)D.NptsPad, H, pl);
+        (void)point_masks<true, HMAX, true>(D.P, c.cc, c.lp, c.N, c.j, c.K, c.step, c.s1, c.singul, D.epis, H, pl, (gd_t) nullptr, D.sur, D.t_now, c.t_piece, c.sg, c.trajtime,
+                                            st);
+        const gd_t rec_pt = rec_b + (size_t)pt * nterm * kRec;
+        double pen;
+        if (point_surround_one<false>(D.P, D.sur, st, sur_id, D.t_now, c.j, c.lp, c.N, c.t_piece, c.singul, c.sg, c.trajtime, tS0, rec_pt, pen)) {
+          rec_pt[(size_t)(tS0 + sur_id) * kRec + 13] = pen; // (the pair's share; the point's sum is formed by team_point_penalties)
+          const int bit = tS0 + sur_id;
+          atomicOr((int *)(sm.pmask + (sm.mw == 2 ? 2 * pt + (bit >> 5) : pt)), 1 << (bit & 31));
+        }
+      };
+      int *npairs = team_npairs(sm);
+      if (tid == 0) *npairs = 0;
+      team_sync<WAVE>();
+      { // every point: its static tests and records, its mask; its pairs that pass the cheap tests to the list
+        for (int pt = tid; pt < Npts; pt += T) {
+          PointCtx c;
+          point_ctx<true>(D, sm, pt, c);
+          PtState st;
+          st.K = -1; // (stays -1 for a point the reference skips, traj_optimizer.cpp:550-553)
+          double pl[4 * HMAX];
+          load_planes<HMAX>(cor_b + pt, (size_t)D.NptsPad, H, pl);
+          const mask_t mask = point_masks<true, HMAX, true>(D.P, c.cc, c.lp, c.N, c.j, c.K, c.step, c.s1, c.singul, D.epis, H, pl, (gd_t) nullptr, D.sur, D.t_now, c.t_piece,
+                                                            c.sg, c.trajtime, st);
+          const gd_t rec_pt = rec_b + (size_t)pt * nterm * kRec;
+          for (mask_t mm = mask; mm;) {
+            const int t = __builtin_ctzll(mm);
+            mm &= mm - 1;
+            point_emit(D.P, st, t, H, tS0 + nS, cor_b + pt, (size_t)D.NptsPad, rec_pt + (size_t)t * kRec);
+          }
+          sm.set_mask(pt, mask);
+          if (st.K >= 0) {
+            for (int sur_id = 0; sur_id < nS; sur_id++) {
+              double pen;
+              if (!point_surround_one<true>(D.P, D.sur, st, sur_id, D.t_now, c.j, c.lp, c.N, c.t_piece, c.singul, c.sg, c.trajtime, tS0, rec_pt, pen)) continue;
+              const int slot = atomicAdd(npairs, 1);
+              if (slot < cap) sm.list[slot] = (pt << 4) | sur_id;
+              else pair_eval(pt, sur_id); // (more pairs than the list holds: this one at once)
+            }
+          }
+        }
+      }
+      __threadfence_block();
+      team_sync<WAVE>();
+      const int np = *npairs < cap ? *npairs : cap;
+      for (int q = tid; q < np; q += T) pair_eval(sm.list[q] >> 4, sm.list[q] & 15);
+      __threadfence_block(); // the pairs' records and shares are read by other lanes below
+      team_sync<WAVE>();
+      team_point_penalties(D, rec_b, sm, tid, T);
+    } else {
+      team_point_pass<SUR, HMAX>(D, cor_b, rec_b, sm, tid, T, nS);
+    }
+    __threadfence_block(); // the records are read back by other lanes of this team
+    team_sync<WAVE>();
+    pr.tick(2);
+    if (tid < 64) team_number_terms(sm, L.Npts, tid);
+    if (u2 >= 0 && u2 < M) seg_chain_starts(sm, L, u2); // (second job)
+    team_sync<WAVE>();
+    const int n_act = sm.first(L.Npts), cap = sm.list_cap;
+    pr.tick(10);        // numbering
+    pr.count(9, n_act); // active terms of this evaluation (a count, not cycles)
+    for (int c0 = 0; c0 < n_act; c0 += cap) {
+      const int c1 = c0 + cap < n_act ? c0 + cap : n_act;
+      team_window_list(sm, L.Npts, tid, T, c0, c1);
+      team_sync<WAVE>();
+      pr.tick(11); // the window's list
+      team_chain_window(D, rec_b, sm, tid, T, nS, c0, c1);
+      team_sync<WAVE>();
+    }
   }
+  pr.tick(3);
+  eval_rows_times_tinv(D, sm, sm.gdC, sm.adj, tid, T); // calGrads_PT: adj = gdC * tInv
+  team_sync<WAVE>();
+  eval_adjoint_solve<WAVE>(D, sm, tid, T, u2);
+  team_sync<WAVE>();
+  pr.tick(4);
+  eval_gradient_and_cost(D, sm, x, g, tid, T, u2);
   team_sync<WAVE>();
   pr.tick(5);
 }

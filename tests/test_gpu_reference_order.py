@@ -1,7 +1,8 @@
 """The reference-order device mode (dftpav_batch_set_order(DFTPAV_ORDER_REFERENCE), dftpav_amd/csrc/solver_ref.hip) against
-the reference ITSELF: oracle/_ref is the reference's own traj_optimizer.cpp / poly_traj_utils.hpp / lbfgs.hpp compiled
-unmodified (oracle/Makefile.ref; the .so travels to the GPU box), the literal oracle its statement-by-statement restatement
-(bit-equal to it, tests/test_ref_pin.py).
+the literal oracle: the statement-by-statement restatement of the reference's traj_optimizer.cpp / poly_traj_utils.hpp / lbfgs.hpp
+(oracle/dftpav_oracle.c).  The build of the reference's own sources against stand-in headers (oracle/Makefile.ref -> oracle/_ref) is
+retired: nothing builds it, and _ref() below answers only for a developer who opted in (oracle/pyref.py), in which case the
+comparisons with it run as well.
 
 Bar: BIT-EQUAL -- every evaluation (cost, gradient) and every whole solve (final x, final cost, status, iterations,
 evaluations, flag_success) -- on the single-segment static configurations: BASELINE configs[0] (default arena), the tests'
