@@ -167,6 +167,11 @@ typedef unsigned long long dmask_t; // a lane's / a row's slots of the list
 // DenseLds::id packs an entry into an int: the owner lane in bits 0-5 (lane & 63), the term in bits 6-11, the point from bit 12 on.
 // Term and point are run-time values: the term is < 5 H + 4 <= 29 (reference_order_quad_supported: H <= 5); the point is <= Kmax + 1,
 // which keeps the id positive while Kmax + 1 < 2^19 -- no predicate bounds K.
+constexpr int kDenseIdLaneBits = 6, kDenseIdTermBits = 6; // (solver_ref4.hip: flush reads them back with & 63, >> 6 & 63, >> 12)
+constexpr int kQuadMaxH = 5;                              // reference_order_quad_supported: H <= 5
+static_assert(64 <= (1 << kDenseIdLaneBits), "the owner lane of a wave of 64 fits its field of the id");
+static_assert(5 * kQuadMaxH + 4 <= (1 << kDenseIdTermBits), "a point's 5 H + 4 terms fit the term field of the id");
+static_assert(kDenseIdLaneBits + kDenseIdTermBits == 12, "the point starts at bit 12 of the id");
 struct DenseLds {
   ldsi_t id;   // [kDense] owner lane | term << 6 | point << 12
   ldsd_t s1;   // [kDense]

@@ -141,21 +141,29 @@ __device__ __forceinline__ void sweep4_split(ldscd_t tab, double (&X)[6], double
     for (int r = 0; r < 6; r++) w[r] = DESC ? nb_dpp<0x101>(R[5 - r]) : nb_dpp<0x111>(R[r]);
   };
   // a block of the ends (step 0 and step N - 1 of the traversal, outside the loops): every coefficient is tested, as the reference
-  // does (`if (a != 0.0)`).  For the owner lanes only (the caller's branch).
-  auto end_step = [&](double (&R)[6], double (&w)[6], ldscv2_t a) {
-    // the block's six table rows, requested together in front of the first row (one wait, not one per row)
-    v2d_t cb[6][4];
+  // does (`if (a != 0.0)`).  Its six table rows are requested together (one wait, not one per row) by whoever is here -- the address
+  // is the wave's -- and the rows run for the owner lanes only (the caller's branch).
+  auto end_request = [&](v2d_t (&cb)[6][4], ldscv2_t a) {
 #pragma unroll
     for (int r = 0; r < 6; r++)
 #pragma unroll
       for (int u = 0; u < (DIV ? 4 : 3); u++) cb[r][u] = a[4 * r + u];
-    asm volatile("" ::: "memory"); // (keeps the reads ahead of the arithmetic)
+    asm volatile("" ::: "memory"); // (keeps the reads where they stand: ahead of the arithmetic, ahead of a loop)
+  };
+  auto end_rows = [&](double (&R)[6], double (&w)[6], const v2d_t (&cb)[6][4]) {
 #pragma unroll
     for (int r = 0; r < 6; r++) sweep_row_end<Q, 1>(r, cb[r], w, R);
   };
   // the seven interior steps s1 .. s1 + 6 of one set: the non-zero terms only, no test.  w: what step s1 starts from; on return,
-  // what the step behind the last one starts from (each step ends by fetching for the next)
-  auto interior = [&](double (&R)[6], int s1, double (&w)[6]) {
+  // what the step behind the last one starts from (each step ends by fetching for the next).  ahead: what the caller wants requested
+  // behind this set's table and in front of the loop.
+  // SELECT form: every lane runs every step on its own table block and its own rows, and only the step's owner keeps the result
+  // (twelve v_cndmask): no branch and no EXEC write in a step.  What a lane that is not the owner computes is dropped and touches
+  // nothing else: it reads registers only, c is a whole interior block of the table for every lane (bi below), R holds right-hand
+  // sides or finished rows (zeros where a trajectory has nothing) and w what the neighbour handed over or 0.0, so the operands are
+  // finite; no floating-point exception traps in this kernel, no address and no store depends on the values, and w is fetched
+  // afresh at the end of the step.  The owner's products, differences and div_by_rcp are sweep_row_interior's, in its order.
+  auto interior = [&](double (&R)[6], int s1, double (&w)[6], auto ahead) {
     // the table of this lane's own block of the set (pk_size(Q) doubles), read once
     v2d_t c[pk_size(Q) / 2];
     {
@@ -165,29 +173,41 @@ __device__ __forceinline__ void sweep4_split(ldscd_t tab, double (&X)[6], double
 #pragma unroll
       for (int u = 0; u < pk_size(Q) / 2; u++) c[u] = a[u];
     }
+    ahead();
 #pragma unroll 1
     for (int s = s1; s < s1 + 7; s++) {
       const bool own = l8 == ((DESC ? N - 1 - s : s) & 7);
-      if (own) {
+      double T[6];
 #pragma unroll
-        for (int r = 0; r < 6; r++) sweep_row_interior<Q, 1>(r, c, w, R);
-      }
+      for (int r = 0; r < 6; r++) T[r] = R[r];
+#pragma unroll
+      for (int r = 0; r < 6; r++) sweep_row_interior<Q, 1>(r, c, w, T);
+#pragma unroll
+      for (int r = 0; r < 6; r++) R[r] = own ? T[r] : R[r];
       fetch(R, w);
     }
   };
   double (&A)[6] = DESC ? Y : X; // the set of the traversal's first eight blocks
   double (&B)[6] = DESC ? X : Y; // and of its last eight
   double w[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}; // the traversal starts from six zeros
-  if (l8 == (DESC ? 7 : 0)) end_step(A, w, (ldscv2_t)tab);
+  if (l8 == (DESC ? 7 : 0)) {
+    v2d_t cb[6][4];
+    end_request(cb, (ldscv2_t)tab);
+    end_rows(A, w, cb);
+  }
   fetch(A, w);
-  interior(A, 1, w);
+  interior(A, 1, w, [] {});
   // the ninth step starts from the eighth block's results: the other set, one lane around the row
 #pragma unroll
   for (int r = 0; r < 6; r++)
     w[r] = DESC ? nb_dpp<0x12F>(A[5 - r])  // lane 7 <- lane 8 (piece 8, dimension 0), lane 15 <- lane 0 (piece 8, dimension 1)
                 : nb_dpp<0x121>(A[r]);     // lane 8 <- lane 7 (piece 7, dimension 0), lane 0 <- lane 15 (piece 7, dimension 1)
-  interior(B, 8, w);
-  if (l8 == (DESC ? 0 : 7)) end_step(B, w, (ldscv2_t)(ip + (N - 2) * pk_size(Q)));
+  // the last end block's table rows are requested in front of the second loop, in one request: they have arrived when the loop ends
+  // (by every lane that is here, not by the owner lanes alone: no branch in front of the loop.  Measured: without this request the
+  // select form gains nothing on the value line, docs/HISTORY.md)
+  v2d_t ce[6][4];
+  interior(B, 8, w, [&] { end_request(ce, (ldscv2_t)(ip + (N - 2) * pk_size(Q))); });
+  if (l8 == (DESC ? 0 : 7)) end_rows(B, w, ce);
 }
 
 // ------------------------------------------------ costFunctionCallback (traj_optimizer.cpp:206-350), one gear segment
@@ -449,9 +469,11 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
     if (D.prof != nullptr) { // (profiling only) trips of the loop below for the wave: the longest list of active terms among its 64 points;
       // DFTPAV_PROF_EMIT_CYCLES (a build flag): the cycles of that loop instead -- the clock behind it is read when the wave has reconverged
       // DFTPAV_PROF_FLUSH_CYCLES (a build flag): the cycles of the list's flushes alone, read where the flush is called
+      // DFTPAV_PROF_CHAIN_CYCLES (a build flag): the cycles of the parked-term chains (pr.tick(2) to pr.tick(3)) of the evaluations
+      // on the slow path alone, read in front of pr.tick(3); slot 3 less these is the other evaluations'
 #if defined(DFTPAV_PROF_EMIT_CYCLES)
       emit_t0 = clock64();
-#elif defined(DFTPAV_PROF_FLUSH_CYCLES)
+#elif defined(DFTPAV_PROF_FLUSH_CYCLES) || defined(DFTPAV_PROF_CHAIN_CYCLES)
 #else
       const int pc = __builtin_popcount(m);
       int trips = 0;
@@ -545,6 +567,9 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
   double gdT = row_chain16(0.0, piece ? pG : -0.0);
   const double en = row_chain16(0.0, piece ? pE : -0.0);
   double cost0 = 0.0, cost2 = 0.0;
+#ifdef DFTPAV_PROF_CHAIN_CYCLES
+  bool chain_slow = false; // (uniform)
+#endif
   // (round 6, measured and taken out: the first three terms of a piece kept in the lane's registers and chained by DPP when no piece of the
   // row has more -- on this workload a piece that has terms has more than three)
   {
@@ -564,6 +589,9 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
     // a row's terms are all in its pool unless it has more than the pool holds
     const bool slow = kmax > kQPool; // (uniform)
     if (D.prof != nullptr) pr.count(11, slow ? 1ll << 32 : 0ll); // (profiling only) evaluations on the slow path: the upper half of slot 11
+#ifdef DFTPAV_PROF_CHAIN_CYCLES
+    chain_slow = slow;
+#endif
     if (kmax > 0 && !slow) {
       // the row's permutation: its pool slots in chain order (a lane's slots ascend in (point, term) order)
       {
@@ -630,6 +658,9 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
       }
     }
   }
+#ifdef DFTPAV_PROF_CHAIN_CYCLES
+  if (D.prof != nullptr && chain_slow && pr.on) pr.count(11, clock64() - pr.last); // (pr.last: the clock of pr.tick(2))
+#endif
   pr.tick(3);
   // ---- calGrads_PT (poly_traj_utils.hpp:1037-1066): adj = gdC * tInv, solveAdj, the duration gradient
   double pA;

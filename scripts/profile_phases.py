@@ -28,7 +28,8 @@ REF = os.environ.get("ORDER") == "ref"
 slow = (pri[:, 11] >> 32) if REF else np.zeros(len(pri), dtype=np.int64)
 # ... and in the upper half of slot 9 the flushes of its list of active terms (q4_eval: flush), each counted by the four rows of the wave.
 # SLOT11=flush / emit names what a library built with -DDFTPAV_PROF_FLUSH_CYCLES / -DDFTPAV_PROF_EMIT_CYCLES keeps in slot 11: the cycles of
-# the flushes / of the whole emission instead of the emit loop's trips
+# the flushes / of the whole emission instead of the emit loop's trips; SLOT11=chain: built with -DDFTPAV_PROF_CHAIN_CYCLES, the cycles
+# of "E4 reduce" (the parked-term chains) of the evaluations on the slow path alone
 flushes = (pri[:, 9] >> 32) if REF else np.zeros(len(pri), dtype=np.int64)
 SLOT11 = os.environ.get("SLOT11", "")
 if REF:
@@ -44,7 +45,7 @@ if REF:
     # slot 10: the TEAM shape's numbering; in a QUAD shape the time between a row's lbfgs_advance and its next evaluation, which it
     # spends masked off while other rows of its wave run their recursion
     quad = not wave_counts and flushes.sum() > 0  # (only a QUAD kernel counts flushes of its list)
-    NAMES[9], NAMES[10], NAMES[11] = "(count) active terms", ("between passes, masked wait" if quad else "numbering") if not wave_counts else "(count)", ("list flushes" if SLOT11 == "flush" else "emission" if SLOT11 == "emit" else "window list") if not wave_counts else "(count)"
+    NAMES[9], NAMES[10], NAMES[11] = "(count) active terms", ("between passes, masked wait" if quad else "numbering") if not wave_counts else "(count)", ("list flushes" if SLOT11 == "flush" else "emission" if SLOT11 == "emit" else "E4 reduce, slow path" if SLOT11 == "chain" else "window list") if not wave_counts else "(count)"
 cyc = pr.copy()
 cyc[:, count_slots] = 0.0
 tot = cyc.sum(axis=1)
@@ -71,6 +72,15 @@ if REF and not wave_counts and flushes.sum() > 0:
           "-- active terms per flush of a wave (four rows):", round(float(4 * pr[:, 9].sum() / flushes.sum()), 1))
 if REF and not wave_counts:
     print("QUAD shape: evaluations on the slow path of the parked-term chain:", int(slow.sum()), "=", round(float(100 * slow.sum() / ev.sum()), 2), "% of all")
+if REF and not wave_counts and SLOT11 == "chain":
+    # E4 reduce by arm, cycles per evaluation of a row: slot 3 is every evaluation's, slot 11 the slow path's; a pass: all cycle slots
+    n_slow, n_fast = float(slow.sum()), float(ev.sum() - slow.sum())
+    c_slow, c_all = float(pr[:, 11].sum()), float(pr[:, 3].sum())
+    per_slow, per_fast = c_slow / max(1.0, n_slow), (c_all - c_slow) / max(1.0, n_fast)
+    per_pass = float((tot.sum() - c_slow) / ev.sum())  # (slot 11 repeats part of slot 3)
+    print("QUAD shape: E4 reduce per evaluation, slow path %.0f cycles (%d evaluations), dense chain %.0f cycles (%d); a pass %.0f cycles;"
+          " slow share x (slow - dense) / pass = %.2f %%" % (per_slow, n_slow, per_fast, n_fast, per_pass,
+                                                              100.0 * n_slow / ev.sum() * (per_slow - per_fast) / per_pass))
 print("two-loop cycles per history step (2 per entry per iteration):", round(float(np.median(pr[:, 8] / (2 * hs))), 1),
       " mean depth", round(float((hs / it).mean()), 1))
 print("solves/s (kernel)", B / (np.mean(ms0) * 1e-3))
