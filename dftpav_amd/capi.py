@@ -61,6 +61,8 @@ EXPORTS = [
     "dftpav_goal_window", "dftpav_set_search_heuristic_window", "dftpav_grid_goal_field_windowed",
     "dftpav_default_rs_heuristic_params", "dftpav_set_search_rs_heuristic", "dftpav_rs_table", "dftpav_rs_table_last_ms",
     "dftpav_planner_check_conflicts", "dftpav_planner_sample_poses", "dftpav_conflicts_last_ms",
+    "dftpav_batch_check_conflicts", "dftpav_batch_sample_poses", "dftpav_batch_conflicts_last_ms",
+    "dftpav_planner_set_conflict_filter", "dftpav_planner_set_own_slots", "dftpav_planner_last_conflicts",
     "dftpav_grid_stamp_poses", "dftpav_planner_stamp_slots", "dftpav_grid_clear_stamps", "dftpav_grid_read_cells", "dftpav_stamp_last_ms",
     "dftpav_grid_render", "dftpav_grid_origin_centred", "dftpav_render_last_ms",
 ]
@@ -246,6 +248,20 @@ def conflict_args(t0, dt, K, margin=0.0, range=None):
     if not ok:
         raise DftpavError(E_INVALID, "conflicts: K in [1, %d], dt > 0, t0 finite, margin >= 0, range finite and >= margin" % CONFLICT_MAX_SAMPLES)
     return t0, dt, int(K), margin, range
+
+
+def candidate_conflict_args(t_start, t0, dt, K, margin=0.0, range=None):
+    """the arguments of dftpav_batch_check_conflicts / _sample_poses as the library takes them, (t_start, t0, dt, K, margin, range)
+    with range = margin when None; what the library would refuse raises DftpavError(E_INVALID) here, before any library call.  A
+    negative margin is legal (nothing conflicts)."""
+    t_start, t0, dt, margin = float(t_start), float(t0), float(dt), float(margin)
+    range = margin if range is None else float(range)
+    ok = int(K) == K and 1 <= K <= CONFLICT_MAX_SAMPLES and dt > 0.0 and np.isfinite(dt) and np.isfinite(t0) and np.isfinite(t_start)
+    ok = ok and margin == margin and np.isfinite(range) and range >= margin
+    if not ok:
+        raise DftpavError(E_INVALID, "candidate conflicts: K in [1, %d], dt > 0, t0 and t_start finite, margin a number, range finite and >= margin"
+                          % CONFLICT_MAX_SAMPLES)
+    return t_start, t0, dt, int(K), margin, range
 
 
 class GoalFieldParams(C.Structure):
@@ -520,6 +536,15 @@ class Handle:
         fn = lib().dftpav_clearance_last_ms
         fn.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         self._check(fn(self._h, C.byref(a), C.byref(b)), "clearance_last_ms")
+        return float(a.value), float(b.value)
+
+    def batch_conflicts_last_ms(self):
+        """dftpav_batch_conflicts_last_ms: device ms of (the pose kernel, the pair kernel) of the last Batch.check_conflicts /
+        Batch.sample_poses on this handle; 0.0 for what has not run"""
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        fn = lib().dftpav_batch_conflicts_last_ms
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        self._check(fn(self._h, C.byref(a), C.byref(b)), "batch_conflicts_last_ms")
         return float(a.value), float(b.value)
 
     def conflicts_last_ms(self):
@@ -1026,6 +1051,30 @@ class Planner:
         self.handle._check(fn(self._p, t0, dt, K, self._ip(out)), "planner_sample_poses")
         return out
 
+    # ---- candidate plans against the executing table: the conflict filter
+    def set_conflict_filter(self, margin=None, range=None, dt=0.1, K=50):
+        """dftpav_planner_set_conflict_filter: a restart that comes within `margin` of an executing plan at one of the K clocks
+        t_now + k dt cannot win; None (or a negative margin) switches the filter off (the default).  range None: margin"""
+        fn = lib().dftpav_planner_set_conflict_filter
+        fn.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int]
+        m = -1.0 if margin is None else float(margin)
+        self.handle._check(fn(self._p, m, m if range is None else float(range), float(dt), int(K)), "planner_set_conflict_filter")
+
+    def set_own_slots(self, own):
+        """dftpav_planner_set_own_slots: per query of the NEXT plan() the slot its plan would replace (-1: none); consumed by that call"""
+        ow = np.ascontiguousarray(own, dtype=np.int32).reshape(-1)
+        fn = lib().dftpav_planner_set_own_slots
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        self.handle._check(fn(self._p, self._ip(ow), ow.shape[0]), "planner_set_own_slots")
+
+    def last_conflicts(self, Q):
+        """dftpav_planner_last_conflicts: the rows [Q][R] of the last plan() of Q queries that ran with the conflict filter on"""
+        out = ConflictOut(int(Q), self.n_restarts)
+        fn = lib().dftpav_planner_last_conflicts
+        fn.argtypes = [C.c_void_p, C.c_void_p]
+        self.handle._check(fn(self._p, C.byref(out.c)), "planner_last_conflicts")
+        return out.arrays()
+
     def stamp_slots(self, t0, dt, K, inflate=0.0, select=None):
         """dftpav_planner_stamp_slots: the footprints of the selected slots (select [slots], 0: not this one; None: every occupied
         slot) at the clocks t0 + k dt, k < K -- the rows of sample_poses -- become occupied cells of the handle's working map"""
@@ -1383,6 +1432,44 @@ class Batch:
     def pack_results(self, device_ptr):
         """16-byte {f64 cost, i32 status, i32 iters} records into device memory (async on the handle's stream)."""
         self.handle._check(lib().dftpav_batch_pack_results(self._b, C.c_void_p(device_ptr)), "pack_results")
+
+    # ---- the batch's trajectories as candidates against a planner's executing table
+    def check_conflicts(self, planner, t_start, t0, dt, K, margin=0.0, range=None, own=None):
+        """dftpav_batch_check_conflicts: every trajectory, were it adopted at t_start, against the occupied slots of `planner` at the
+        clocks t0 + k dt, k < K -> dict(min_sep, sep_sample, sep_partner, conflict_sample, conflict_partner [B]); own [B]: the slot
+        each would replace (-1 or None: none), which takes no part.  Nothing within the broad phase: +inf, -1, -1, -1, -1"""
+        t_start, t0, dt, K, margin, range = candidate_conflict_args(t_start, t0, dt, K, margin, range)
+        ow = None
+        if own is not None:
+            ow = np.ascontiguousarray(own, dtype=np.int32).reshape(-1)
+            if ow.shape[0] != self.B:
+                raise DftpavError(E_INVALID, "batch_check_conflicts: own has an entry per trajectory")
+        out = ConflictOut(self.B)
+        fn = lib().dftpav_batch_check_conflicts
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+        self.handle._check(fn(self._b, planner._p, t_start, t0, dt, K, margin, range,
+                              ow.ctypes.data_as(C.c_void_p) if ow is not None else None, C.byref(out.c)), "batch_check_conflicts")
+        return out.arrays()
+
+    def sample_poses(self, t_start, t0, dt, K):
+        """dftpav_batch_sample_poses: the pose half of check_conflicts alone -> [K][B][4] = the footprint's centre cx, cy and the
+        heading's cosine and sine of every trajectory started at t_start"""
+        t_start, t0, dt, K, _, _ = candidate_conflict_args(t_start, t0, dt, K)
+        out = np.zeros((K, self.B, 4))
+        fn = lib().dftpav_batch_sample_poses
+        fn.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p]
+        self.handle._check(fn(self._b, t_start, t0, dt, K, out.ctypes.data_as(C.c_void_p)), "batch_sample_poses")
+        return out
+
+    def set_coeffs(self, coeffs, piece_dt):
+        """test hook dftpav_debug_batch_set_coeffs: the steps after a solve run on these coefficients [B][Ntot][6][2] and piece
+        durations [B][M] instead of a solution's"""
+        co = np.ascontiguousarray(coeffs, dtype=np.float64)
+        dt = np.ascontiguousarray(piece_dt, dtype=np.float64)
+        assert co.shape == (self.B, self.layout.n_pieces, 6, 2) and dt.shape == (self.B, self.layout.M)
+        fn = lib().dftpav_debug_batch_set_coeffs
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        self.handle._check(fn(self._b, co.ctypes.data_as(C.c_void_p), dt.ctypes.data_as(C.c_void_p)), "debug_batch_set_coeffs")
 
     def coeffs(self):
         c = np.zeros((self.B, self.layout.n_pieces, 6, 2))

@@ -33,6 +33,7 @@
 #include "limits_args.h"
 #include "clearance_args.h"
 #include "conflict_args.h"
+#include "cand_conflict_args.h"
 #include "stamp_args.h"
 #include "render_args.h"
 #include "goalfield_args.h"
@@ -74,6 +75,9 @@ hipError_t launch_clearance_table(const ClearanceTableArgs &A, hipStream_t strea
 hipError_t launch_conflict_poses(const ConflictPoseArgs &A, hipStream_t stream);
 hipError_t launch_conflict_pairs(const ConflictPairArgs &A, hipStream_t stream);
 hipError_t launch_conflict_reduce(const ConflictReduceArgs &A, hipStream_t stream);
+// cand_conflict.hip: the poses of a batch's candidates at K clocks; their separation from the table's poses, the rows per candidate
+hipError_t launch_cand_poses(const CandPoseArgs &A, hipStream_t stream);
+hipError_t launch_cand_pairs(const CandPairArgs &A, hipStream_t stream);
 // stamp.hip: boxes into the working map, the bit map from the bytes again, the cells stamped since the base copy
 hipError_t launch_stamp_boxes(const StampBoxArgs &A, hipStream_t stream);
 hipError_t launch_stamp_bits(const StampBitsArgs &A, hipStream_t stream);
@@ -168,6 +172,9 @@ struct dftpav_handle {
   EventMarks<2> field_ev, clr_ev; // around the last field build / the last clearance kernel of a check call
   EventMarks<3> conf_ev; // conflict.hip: in front of the pose kernel, between it and the pair kernel, behind the reduce kernel; of the
                          // last dftpav_planner_sample_poses (complete to mark 1) / _check_conflicts (to mark 2) call
+  EventMarks<3> cand_ev; // cand_conflict.hip: in front of the pose kernel (the table's; dftpav_batch_sample_poses: the candidates'), between it
+                         // and the pair kernel, behind the pair kernel; of the last dftpav_batch_sample_poses (complete to mark 1) /
+                         // dftpav_batch_check_conflicts (to mark 2) call
   // the stamps (stamp.hip): nothing of it exists until a stamp call.  d_cells stays the working map every call reads
   unsigned char *d_cells_base = nullptr; // the map as uploaded: copied by the first stamp after a dftpav_set_grid_map, which drops it
   unsigned char *d_stamp_ws = nullptr;   // dftpav_planner_stamp_slots: the poses 4 x [K][S_pad], occupied [S_pad], select [S_pad];
@@ -358,7 +365,7 @@ inline void limit_rows(LimitsCommon &C, double *d_max, int *d_int, size_t n) {
   C.feasible = d_int + 2 * kLimQ * n;
 }
 
-// The selection filters of dftpav_plan_queries: three structs of one shape (capi_planner.cpp).  Each holds its switch (`on`, and
+// The selection filters of dftpav_plan_queries: four structs of one shape (capi_planner.cpp).  Each holds its switch (`on`, and
 // `last`: the last dftpav_plan_queries call ran with it), its parameters and its one allocation `d` -- the sample table at its head
 // where the filter has one, then the rows [cap = max_queries * R] of a call -- and states the same operations once:
 //   configure  the set_*_filter entry behind its argument checks: allocates on first use, switches on; a refusal changes nothing
@@ -407,6 +414,33 @@ struct ClearanceFilter {
   int clear(dftpav_handle *h, size_t rows);
   int run(dftpav_handle *h, dftpav_batch *b, const int *members, int nm, int R, int *reject);
   int fetch(dftpav_handle *h, const dftpav_clearance_out *out, size_t rows);
+  void release() { if (d) (void)hipFree(d); }
+};
+
+// The conflict filter: rejects a trajectory that comes within `margin` of an executing plan at one of the K clocks t_now + k dt
+// (cand_conflict.hip).  Its allocation holds the table's poses at the call's clocks (4 x [K][S_pad], occupied [S_pad]), the own
+// slots [max_queries] and the rows.  clear also uploads the call's own slots and launches conflict_pose_kernel, once per call; with a
+// table never filled or all empty it launches nothing, and run then launches nothing either: the cleared rows stand.
+struct ConflictFilter {
+  bool on = false, last = false;
+  double margin = -1.0, range = 0.0, dt = 0.0;
+  int K = 0;
+  unsigned char *d = nullptr;
+  int cap_K = 0; // the K the allocation was made for
+  double *d_pose = nullptr, *d_sep = nullptr;
+  unsigned char *d_occupied = nullptr;
+  int *d_own = nullptr, *d_int = nullptr; // d_int: sep_sample | sep_partner | conflict_sample | conflict_partner, each [cap]
+  size_t cap = 0;
+  std::vector<double> h_inf; // +inf, the rows' min_sep before a call's kernels run
+  std::vector<int> h_own;    // the host source of the own slots' copy
+  ConflictPoses P{};         // the table's poses of the running call
+  double t_call = 0.0;       // its t_now
+  bool have_table = false;   // it found an occupied slot
+  ConflictRows rows() const { return ConflictRows{d_sep, d_int, d_int + cap, d_int + 2 * cap, d_int + 3 * cap}; }
+  int configure(struct dftpav_planner *p, double margin_, double range_, double dt_, int K_);
+  int clear(struct dftpav_planner *p, size_t n_rows, double t_now, const std::vector<int> &own);
+  int run(dftpav_handle *h, dftpav_batch *b, const int *members, int nm, int R, int *reject);
+  int fetch(dftpav_handle *h, const dftpav_conflict_out *out, size_t n_rows);
   void release() { if (d) (void)hipFree(d); }
 };
 
@@ -472,10 +506,12 @@ struct dftpav_planner {
   double *d_pub_t = nullptr, *d_pub_states = nullptr;
   int *d_pub_code = nullptr;
   EventMarks<2> pub_ev; // around the last publish kernel
-  // ---- the selection filters (dftpav_planner_set_limit_filter / _penalty_filter / _clearance_filter)
+  // ---- the selection filters (dftpav_planner_set_limit_filter / _penalty_filter / _clearance_filter / _conflict_filter)
   LimitFilter lim;
   PenaltyFilter pen;
   ClearanceFilter clr;
+  ConflictFilter cnf;
+  std::vector<int> own_next; // dftpav_planner_set_own_slots: the own slots [Q] of the next dftpav_plan_queries call, which consumes them
 };
 
 namespace dftpav {

@@ -88,6 +88,7 @@ extern "C" void dftpav_planner_destroy(dftpav_planner *p) {
   p->lim.release();
   p->pen.release();
   p->clr.release();
+  p->cnf.release();
   delete p; // (its EventMarks' events with it)
 }
 
@@ -227,6 +228,7 @@ struct PlanCall {
   std::vector<dftpav_batch *> batch;           // per group (nullptr: a layout outside the reference order's limits)
   std::vector<int> g_off;                      // group g's members are p->h_members [g_off[g], g_off[g + 1])
   size_t pose_off = 0;                         // poses of p->d_poses the groups so far have used
+  std::vector<int> own;                        // dftpav_planner_set_own_slots: per query, or empty for none
 };
 
 static int plan_check_params(const dftpav_planner *p, const dftpav_plan_params *pp, const dftpav_plan_out *out, int Q) {
@@ -376,7 +378,9 @@ static int plan_clear_filter_rows(PlanCall &c) {
     if (int rc = p->lim.clear(h, rows)) return rc;
   if (p->pen.on)
     if (int rc = p->pen.clear(h, rows)) return rc;
-  if (p->lim.on || p->clr.on || p->pen.on) HIPCHK(h, hipMemsetAsync(p->d_reject, 0, sizeof(int) * rows, h->stream));
+  if (p->cnf.on) // with the own slots of the call and the table's poses at its clocks
+    if (int rc = p->cnf.clear(p, rows, c.t_now, c.own)) return rc;
+  if (p->lim.on || p->clr.on || p->pen.on || p->cnf.on) HIPCHK(h, hipMemsetAsync(p->d_reject, 0, sizeof(int) * rows, h->stream));
   return DFTPAV_OK;
 }
 
@@ -461,7 +465,7 @@ static int plan_select_group(PlanCall &c, int g, int *col, int *fst, int *rej) {
   return DFTPAV_OK;
 }
 
-// one group: pack -> rectangles -> solve -> coefficients -> collision re-check (-> limits) (-> clearance) (-> penalty gate) -> selection;
+// one group: pack -> rectangles -> solve -> coefficients -> collision re-check (-> limits) (-> clearance) (-> penalty gate) (-> conflicts) -> selection;
 // nothing waits in between, or between groups
 static int plan_one_group(PlanCall &c, int g) {
   dftpav_planner *p = c.p;
@@ -479,13 +483,15 @@ static int plan_one_group(PlanCall &c, int g) {
   const int *members = p->d_members + c.g_off[g];
   int *col = p->d_col + row0, *fst = p->d_first + row0;
   if (int rc = validate_on_stream(b, nm * R, p->d_vt, c.n_t, c.n_v, c.pp->check_dt, col, fst)) return rc;
-  int *rej = p->lim.on || p->clr.on || p->pen.on ? p->d_reject + row0 : nullptr;
+  int *rej = p->lim.on || p->clr.on || p->pen.on || p->cnf.on ? p->d_reject + row0 : nullptr;
   if (p->lim.on) // rejects a trajectory that is not feasible
     if (int rc = p->lim.run(h, b, members, nm, R, rej)) return rc;
   if (p->clr.on) // rejects a trajectory unless clearance >= min_clearance
     if (int rc = p->clr.run(h, b, members, nm, R, rej)) return rc;
   if (p->pen.on) // rejects a trajectory with a penalty sum above its cap
     if (int rc = p->pen.run(h, b, members, nm, R, rej)) return rc;
+  if (p->cnf.on) // rejects a trajectory that comes within the margin of an executing plan
+    if (int rc = p->cnf.run(h, b, members, nm, R, rej)) return rc;
   return plan_select_group(c, g, col, fst, rej);
 }
 
@@ -543,6 +549,7 @@ static int plan_results(PlanCall &c) {
   p->lim.last = p->lim.on;
   p->pen.last = p->pen.on;
   p->clr.last = p->clr.on;
+  p->cnf.last = p->cnf.on;
   return DFTPAV_OK;
 }
 
@@ -552,10 +559,14 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
   p->group_sizes.clear();
   p->plan_ev.reset();
   p->last_Q = 0; // nothing to adopt, no filter rows to read, until this call has ended well
-  p->lim.last = p->pen.last = p->clr.last = false;
+  p->lim.last = p->pen.last = p->clr.last = p->cnf.last = false;
+  std::vector<int> own;
+  own.swap(p->own_next); // consumed by this call, whatever becomes of it
   if (Q == 0) return DFTPAV_OK;
   if (!start_states || !start_ctrl || !end_states) return DFTPAV_E_INVALID;
+  if (!own.empty() && (int)own.size() != Q) return DFTPAV_E_INVALID; // own slots set for another number of queries
   PlanCall c{p, p->h, pp, start_states, start_ctrl, end_states, Q, t_now, out};
+  c.own.swap(own);
   if (int rc = plan_search(c)) return rc;            // marks 0, 1, 2
   if (int rc = plan_read_layouts(c)) return rc;      // the one wait before the end
   if (int rc = plan_group(c)) return rc;
@@ -1038,7 +1049,10 @@ extern "C" int dftpav_replan_tick(dftpav_planner *p, const dftpav_plan_params *p
   if (nq > 0) {
     static const dftpav_plan_out none{};
     const double stamp = t_now + budget; // desired_state.time_stamp, traj_server_ros.cpp:414; `now` of the plan, traj_manager.cpp:520
-    if (int rc = dftpav_plan_queries(p, pp, qs.data(), qc.data(), qe.data(), nq, stamp, plan_out ? plan_out : &none)) return rc;
+    p->own_next = slot_of; // a query is the replan of its slot: not in conflict with the plan it replaces
+    const int rc_plan = dftpav_plan_queries(p, pp, qs.data(), qc.data(), qe.data(), nq, stamp, plan_out ? plan_out : &none);
+    p->own_next.clear(); // (a call refused before it consumed them)
+    if (rc_plan) return rc_plan;
     std::vector<int> qi(nq);
     for (int q = 0; q < nq; q++) qi[q] = q;
     if (int rc = adopt_impl(p, nq, qi.data(), slot_of.data(), stamp, p->d_rc_des, nullptr)) return rc;
@@ -1390,7 +1404,7 @@ static int conflict_s_pad(const dftpav_planner *p) { return (p->max_queries + kC
 
 // the poses of every slot at the K clocks into d_pose (4 x [K][S_pad]) and d_occupied [S_pad], on the handle's stream between marks 0
 // and 1 of `ev` (nothing waits)
-static int conflict_poses_into(dftpav_planner *p, double *d_pose, unsigned char *d_occupied, EventMarks<3> &ev, double t0, double dt,
+static int conflict_poses_into(dftpav_planner *p, double *d_pose, unsigned char *d_occupied, EventMarks<3> *ev, double t0, double dt,
                                int K, ConflictPoses &P) {
   dftpav_handle *h = p->h;
   const int S_pad = conflict_s_pad(p);
@@ -1408,20 +1422,22 @@ static int conflict_poses_into(dftpav_planner *p, double *d_pose, unsigned char 
   A.t0 = t0;
   A.dt = dt;
   A.dcr = h->params.veh_d_cr;
-  ev.reset(); // until the whole chain has run
-  HIPCHK(h, ev.record(0, h->stream));
+  if (ev) {
+    ev->reset(); // until the whole chain has run
+    HIPCHK(h, ev->record(0, h->stream));
+  }
   HIPCHK(h, launch_conflict_poses(A, h->stream));
-  HIPCHK(h, ev.record(1, h->stream));
+  if (ev) HIPCHK(h, ev->record(1, h->stream));
   return DFTPAV_OK;
 }
-// the same into buffers of `tmp`, between the marks of conf_ev
-static int conflict_poses_on_stream(dftpav_planner *p, DevScratch &tmp, double t0, double dt, int K, ConflictPoses &P) {
+// the same into buffers of `tmp`, between marks 0 and 1 of `ev` (nullptr: no marks)
+static int conflict_poses_on_stream(dftpav_planner *p, DevScratch &tmp, EventMarks<3> &ev, double t0, double dt, int K, ConflictPoses &P) {
   dftpav_handle *h = p->h;
   double *d_pose = nullptr;
   unsigned char *d_occupied = nullptr;
   HIPCHK(h, tmp.alloc(d_pose, 4 * (size_t)K * conflict_s_pad(p)));
   HIPCHK(h, tmp.alloc(d_occupied, (size_t)conflict_s_pad(p)));
-  return conflict_poses_into(p, d_pose, d_occupied, h->conf_ev, t0, dt, K, P);
+  return conflict_poses_into(p, d_pose, d_occupied, &ev, t0, dt, K, P);
 }
 
 extern "C" int dftpav_planner_sample_poses(dftpav_planner *p, double t0, double dt, int K, double *poses) {
@@ -1437,7 +1453,7 @@ extern "C" int dftpav_planner_sample_poses(dftpav_planner *p, double t0, double 
   std::vector<double> soa(4 * n); // cx | cy | cs | sn, each [K][S_pad]; declared in front of tmp, whose end waits for the stream
   DevScratch tmp(h);
   ConflictPoses P{};
-  if (int rc = conflict_poses_on_stream(p, tmp, t0, dt, K, P)) return rc;
+  if (int rc = conflict_poses_on_stream(p, tmp, h->conf_ev, t0, dt, K, P)) return rc;
   HIPCHK(h, hipMemcpyAsync(soa.data(), P.cx, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   for (size_t k = 0; k < (size_t)K; k++)
@@ -1462,7 +1478,7 @@ extern "C" int dftpav_planner_check_conflicts(dftpav_planner *p, double t0, doub
   HIPCHK(h, hipSetDevice(h->device));
   DevScratch tmp(h);
   ConflictPoses P{};
-  if (int rc = conflict_poses_on_stream(p, tmp, t0, dt, K, P)) return rc;
+  if (int rc = conflict_poses_on_stream(p, tmp, h->conf_ev, t0, dt, K, P)) return rc;
   const size_t tiles = (size_t)P.S_pad / kConflictTile;
   const size_t rows = tiles * P.S_pad; // the partial rows [tiles][S_pad]; behind them the outputs [S]
   double *d_sep = nullptr;
@@ -1509,6 +1525,218 @@ extern "C" int dftpav_conflicts_last_ms(dftpav_handle *h, float *pose_ms, float 
   return DFTPAV_OK;
 }
 
+// ------------------------------------------------- footprint conflicts of candidate plans against the executing table (cand_conflict.hip)
+// the first n trajectories of a batch as candidates that start at t_start, at the clocks t0 + k dt
+static CandBatch cand_batch(const dftpav_handle *h, const dftpav_batch *b, int n, double t_start, double t0, double dt) {
+  CandBatch C{};
+  C.coeffs = b->d_coef;
+  C.piece_dt = b->d_dt;
+  C.L = b->L;
+  C.B = n;
+  C.t_start = t_start;
+  C.t0 = t0;
+  C.dt = dt;
+  C.dcr = h->params.veh_d_cr;
+  return C;
+}
+// the vehicle and the two distances of a pair launch (as dftpav_planner_check_conflicts forms them)
+static void cand_pair_consts(const dftpav_handle *h, double margin, double range, CandPairArgs &A) {
+  const double L = h->params.veh_length, W = h->params.veh_width;
+  const double rad = std::sqrt(0.25 * L * L + 0.25 * W * W);
+  const double R = range + 2.0 * rad;
+  A.half_l = 0.5 * L;
+  A.half_w = 0.5 * W;
+  A.margin = margin;
+  A.reach2 = R * R;
+}
+static bool planner_has_plans(const dftpav_planner *p) {
+  if (!p->d_exec) return false;
+  for (int m : p->h_occupied)
+    if (m) return true;
+  return false;
+}
+static bool own_slots_ok(const dftpav_planner *p, const int *own, size_t n) {
+  for (size_t i = 0; i < n; i++)
+    if (own[i] < -1 || own[i] >= p->max_queries) return false;
+  return true;
+}
+
+extern "C" int dftpav_batch_sample_poses(dftpav_batch *b, double t_start, double t0, double dt, int K, double *poses) {
+  if (!b || !poses || !b->uploaded || !b->solved || !conflict_clocks_ok(t0, dt, K) || !std::isfinite(t_start)) return DFTPAV_E_INVALID;
+  dftpav_handle *h = b->h;
+  HIPCHK(h, hipSetDevice(h->device));
+  DevBatch D;
+  if (int rc = ensure_coeffs(b, D)) return rc;
+  const size_t n = (size_t)K * b->B * 4;
+  DevScratch tmp(h);
+  CandPoseArgs A{};
+  A.C = cand_batch(h, b, b->B, t_start, t0, dt);
+  A.K = K;
+  HIPCHK(h, tmp.alloc(A.poses, n));
+  h->cand_ev.reset();
+  HIPCHK(h, h->cand_ev.record(0, h->stream));
+  HIPCHK(h, launch_cand_poses(A, h->stream));
+  HIPCHK(h, h->cand_ev.record(1, h->stream));
+  HIPCHK(h, hipMemcpyAsync(poses, A.poses, sizeof(double) * n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->cand_ev.complete(1); // the poses alone
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_batch_check_conflicts(dftpav_batch *b, dftpav_planner *p, double t_start, double t0, double dt, int K, double margin,
+                                            double range, const int *own, const dftpav_conflict_out *out) {
+  if (!b || !p || !out || b->h != p->h || !b->uploaded || !b->solved) return DFTPAV_E_INVALID;
+  if (!conflict_clocks_ok(t0, dt, K) || !std::isfinite(t_start)) return DFTPAV_E_INVALID;
+  if (margin != margin || !std::isfinite(range) || range < margin) return DFTPAV_E_INVALID; // (+inf fails range < margin)
+  const size_t B = (size_t)b->B;
+  if (own && !own_slots_ok(p, own, B)) return DFTPAV_E_INVALID;
+  dftpav_handle *h = p->h;
+  if (!p->d_exec) { // nothing was ever installed: no slot to come near
+    if (out->min_sep) std::fill(out->min_sep, out->min_sep + B, HUGE_VAL);
+    for (int *row : {out->sep_sample, out->sep_partner, out->conflict_sample, out->conflict_partner})
+      if (row) std::fill(row, row + B, -1);
+    return DFTPAV_OK;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  DevBatch D;
+  if (int rc = ensure_coeffs(b, D)) return rc;
+  DevScratch tmp(h);
+  CandPairArgs A{};
+  if (int rc = conflict_poses_on_stream(p, tmp, h->cand_ev, t0, dt, K, A.P)) return rc;
+  double *d_sep = nullptr;
+  int *d_int = nullptr, *d_own = nullptr;
+  HIPCHK(h, tmp.alloc(d_sep, B));
+  HIPCHK(h, tmp.alloc(d_int, 4 * B));
+  if (own) {
+    HIPCHK(h, tmp.alloc(d_own, B));
+    HIPCHK(h, hipMemcpyAsync(d_own, own, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
+  }
+  A.C = cand_batch(h, b, b->B, t_start, t0, dt);
+  A.rows = ConflictRows{d_sep, d_int, d_int + B, d_int + 2 * B, d_int + 3 * B};
+  A.members = nullptr;
+  A.R = 1;
+  A.own = d_own;
+  A.reject = nullptr;
+  cand_pair_consts(h, margin, range, A);
+  HIPCHK(h, launch_cand_pairs(A, h->stream));
+  HIPCHK(h, h->cand_ev.record(2, h->stream));
+  HIPCHK(h, fetch_async(h, out->min_sep, A.rows.min_sep, sizeof(double) * B));
+  HIPCHK(h, fetch_async(h, out->sep_sample, A.rows.sep_sample, sizeof(int) * B));
+  HIPCHK(h, fetch_async(h, out->sep_partner, A.rows.sep_partner, sizeof(int) * B));
+  HIPCHK(h, fetch_async(h, out->conflict_sample, A.rows.conflict_sample, sizeof(int) * B));
+  HIPCHK(h, fetch_async(h, out->conflict_partner, A.rows.conflict_partner, sizeof(int) * B));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->cand_ev.complete();
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_batch_conflicts_last_ms(dftpav_handle *h, float *pose_ms, float *pair_ms) {
+  if (!h) return DFTPAV_E_INVALID;
+  if (pose_ms) *pose_ms = 0.0f;
+  if (pair_ms) *pair_ms = 0.0f;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (pose_ms && h->cand_ev.reached(1)) HIPCHK(h, h->cand_ev.elapsed(pose_ms, 0, 1, false)); // (both calls waited for the stream)
+  if (pair_ms && h->cand_ev.reached(2)) HIPCHK(h, h->cand_ev.elapsed(pair_ms, 1, 2, false));
+  return DFTPAV_OK;
+}
+
+// the conflict filter (ConflictFilter, capi_internal.h)
+int ConflictFilter::configure(dftpav_planner *p, double margin_, double range_, double dt_, int K_) {
+  dftpav_handle *h = p->h;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (!d || cap_K < K_) { // the poses are sized by K: a larger K takes a new allocation
+    const size_t rows_cap = (size_t)p->max_queries * p->R, S_pad = (size_t)conflict_s_pad(p);
+    double *pose = nullptr, *sep = nullptr;
+    unsigned char *occ = nullptr;
+    int *own = nullptr, *ints = nullptr;
+    auto fields = [&](auto &take) {
+      pose = (double *)take(sizeof(double) * 4 * (size_t)K_ * S_pad);
+      sep = (double *)take(sizeof(double) * rows_cap);
+      ints = (int *)take(sizeof(int) * 4 * rows_cap);
+      own = (int *)take(sizeof(int) * (size_t)p->max_queries);
+      occ = (unsigned char *)take(S_pad);
+    };
+    unsigned char *fresh = nullptr;
+    HIPCHK(h, hipMalloc(&fresh, carve(nullptr, fields)));
+    if (d) { // (nothing of the old one is in flight behind this wait)
+      (void)hipStreamSynchronize(h->stream);
+      (void)hipFree(d);
+    }
+    carve(fresh, fields);
+    d = fresh;
+    d_pose = pose, d_sep = sep, d_int = ints, d_own = own, d_occupied = occ;
+    cap = rows_cap;
+    cap_K = K_;
+    h_inf.assign(rows_cap, HUGE_VAL);
+  }
+  margin = margin_, range = range_, dt = dt_, K = K_;
+  on = true;
+  return DFTPAV_OK;
+}
+int ConflictFilter::clear(dftpav_planner *p, size_t n_rows, double t_now, const std::vector<int> &own) { // +inf, -1
+  dftpav_handle *h = p->h;
+  const ConflictRows r = rows();
+  HIPCHK(h, hipMemcpyAsync(r.min_sep, h_inf.data(), sizeof(double) * n_rows, hipMemcpyHostToDevice, h->stream));
+  for (int *row : {r.sep_sample, r.sep_partner, r.conflict_sample, r.conflict_partner})
+    HIPCHK(h, hipMemsetAsync(row, 0xff, sizeof(int) * n_rows, h->stream));
+  t_call = t_now;
+  have_table = planner_has_plans(p);
+  if (!have_table) return DFTPAV_OK; // nothing to come near: the cleared rows are the result
+  h_own.assign((size_t)p->max_queries, -1);
+  std::copy(own.begin(), own.end(), h_own.begin());
+  HIPCHK(h, hipMemcpyAsync(d_own, h_own.data(), sizeof(int) * h_own.size(), hipMemcpyHostToDevice, h->stream));
+  return conflict_poses_into(p, d_pose, d_occupied, nullptr, t_now, dt, K, P);
+}
+int ConflictFilter::run(dftpav_handle *h, dftpav_batch *b, const int *members, int nm, int R, int *reject) {
+  if (!have_table) return DFTPAV_OK;
+  CandPairArgs A{};
+  A.C = cand_batch(h, b, nm * R, t_call, t_call, dt);
+  A.P = P;
+  A.rows = rows();
+  A.members = members;
+  A.R = R;
+  A.own = d_own;
+  A.reject = reject;
+  cand_pair_consts(h, margin, range, A);
+  HIPCHK(h, launch_cand_pairs(A, h->stream));
+  return DFTPAV_OK;
+}
+int ConflictFilter::fetch(dftpav_handle *h, const dftpav_conflict_out *out, size_t n_rows) {
+  const ConflictRows r = rows();
+  HIPCHK(h, fetch_async(h, out->min_sep, r.min_sep, sizeof(double) * n_rows));
+  HIPCHK(h, fetch_async(h, out->sep_sample, r.sep_sample, sizeof(int) * n_rows));
+  HIPCHK(h, fetch_async(h, out->sep_partner, r.sep_partner, sizeof(int) * n_rows));
+  HIPCHK(h, fetch_async(h, out->conflict_sample, r.conflict_sample, sizeof(int) * n_rows));
+  HIPCHK(h, fetch_async(h, out->conflict_partner, r.conflict_partner, sizeof(int) * n_rows));
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_planner_set_conflict_filter(dftpav_planner *p, double margin, double range, double dt, int K) {
+  if (!p || margin != margin) return DFTPAV_E_INVALID;
+  if (margin < 0.0) { // off: the buffers stay, nothing reads them
+    p->cnf.on = false;
+    return DFTPAV_OK;
+  }
+  if (!conflict_clocks_ok(0.0, dt, K) || !std::isfinite(range) || range < margin) return DFTPAV_E_INVALID;
+  return p->cnf.configure(p, margin, range, dt, K);
+}
+
+extern "C" int dftpav_planner_set_own_slots(dftpav_planner *p, const int *own, int Q) {
+  if (!p || Q < 0 || Q > p->max_queries || (Q > 0 && !own)) return DFTPAV_E_INVALID;
+  if (!own_slots_ok(p, own, (size_t)Q)) return DFTPAV_E_INVALID;
+  p->own_next.assign(own, own + Q);
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_planner_last_conflicts(dftpav_planner *p, const dftpav_conflict_out *out) {
+  if (!p || !out || !p->cnf.last || p->last_Q <= 0) return DFTPAV_E_INVALID;
+  dftpav_handle *h = p->h;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (int rc = p->cnf.fetch(h, out, (size_t)p->last_Q * p->R)) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return DFTPAV_OK;
+}
+
 // ------------------------------------------------- the executing plans' swept footprints stamped into the map (stamp.hip)
 extern "C" int dftpav_planner_stamp_slots(dftpav_planner *p, const unsigned char *select, double t0, double dt, int K, double inflate) {
   if (!p || !conflict_clocks_ok(t0, dt, K) || !(inflate >= 0.0) || !std::isfinite(inflate)) return DFTPAV_E_INVALID;
@@ -1536,7 +1764,7 @@ extern "C" int dftpav_planner_stamp_slots(dftpav_planner *p, const unsigned char
     HIPCHK(h, hipEventRecord(h->stamp_sel_ev, h->stream));
   }
   ConflictPoses P{};
-  if (int rc = conflict_poses_into(p, d_pose, d_occupied, h->stamp_ev, t0, dt, K, P)) return rc;
+  if (int rc = conflict_poses_into(p, d_pose, d_occupied, &h->stamp_ev, t0, dt, K, P)) return rc;
   h->stamp_posed = true;
   return stamp_boxes_on_stream(h, P.cx, P.cy, P.cs, P.sn, (int)n, select ? d_select : nullptr, S_pad, inflate);
 }

@@ -1201,6 +1201,67 @@ int dftpav_planner_check_conflicts(dftpav_planner *p, double t0, double dt, int 
 int dftpav_planner_sample_poses(dftpav_planner *p, double t0, double dt, int K, double *poses /*[K][max_queries][4]*/);
 int dftpav_conflicts_last_ms(dftpav_handle *h, float *pose_ms, float *pair_ms);
 
+/* ---- footprint conflicts of candidate plans against the executing table, and the conflict filter ---------------------------
+ * The check above relates the plans that execute.  This one relates plans that do not execute yet -- the trajectories of a batch --
+ * to those that do, and as a selection filter of dftpav_plan_queries it feeds back: a restart that would drive through the vehicle
+ * of another slot cannot win (cand_conflict.hip).  No grid map is needed by the read-outs.
+ *
+ * A candidate is trajectory c of a batch b: the batch's layout, its piece coefficients and piece durations as dftpav_batch_coeffs
+ * returns them, and an absolute start clock t_start.
+ *
+ * The clocks.  t_k = t0 + (double)k * dt, k < K <= DFTPAV_CONFLICT_MAX_SAMPLES, as above.
+ *
+ * The pose of a candidate at clock t is the pose its slot would have after dftpav_planner_adopt(..., t_start): the segment times
+ * are chained as the adoption chains them -- world = t_start; for every segment d = its piece duration summed piece by piece
+ * (Trajectory::getTotalDuration), start_time = world, end_time = world + d, and the next segment starts at that end -- and segment,
+ * local time, clamping, position, heading and box centre follow the statements of the pose above.  The candidate is held still before
+ * t_start and after its last end_time.  The pose of a slot is the pose above, unchanged.
+ *
+ * The separation of candidate c and occupied slot j != own[c] at sample k is steps 1 to 3 above in the same expressions: the broad
+ * phase on the centres with R = range + 2.0 * rad, the separating-axis test, the 32 corner-to-edge distances.  own[c] is the slot
+ * the candidate would replace, or -1 if it replaces none: that slot takes no part.  An empty slot contributes nothing; so does a
+ * pose that is not finite on either side.
+ *
+ * Per candidate, the lexicographic rules above:
+ *   min_sep, sep_sample, sep_partner     the minimum of (sep, k, j)
+ *   conflict_sample, conflict_partner    the minimum of (k, j) over sep <= margin (a negative margin: never)
+ * A candidate that nothing contributed to, a candidate no kernel visits, and every candidate before the table was filled once give
+ * +inf, -1, -1, -1, -1.  Nothing of the table, the publisher's state or the batch is written.
+ *
+ * dftpav_batch_check_conflicts(b, p, t_start, t0, dt, K, margin, range, own, out): the five rows [B] of the batch's B trajectories,
+ *   on a solved batch (or the coefficients of dftpav_debug_batch_set_coeffs); own [B] or NULL for none; any pointer of out may be NULL.
+ * dftpav_batch_sample_poses(b, t_start, t0, dt, K, poses): the candidates' poses alone, poses [K][B][4] = cx, cy, cs, sn.
+ * dftpav_batch_conflicts_last_ms: device time in ms (the handle's HIP events) of the last of the two calls above: the pose kernel (of
+ *   the table for the check, of the candidates for the poses) and the pair kernel; 0.0 for what has not run.
+ *
+ * The filter.  dftpav_planner_set_conflict_filter(p, margin, range, dt, K): margin < 0 is off (the default).  On, every restart of
+ * a dftpav_plan_queries call is a candidate with t_start = t0 = the call's t_now (in dftpav_replan_tick: t_now + budget, the
+ * adoption clock), tested per layout group after the collision re-check against the table's poses, which are evaluated once per
+ * call; a restart with conflict_sample >= 0 is rejected beside the other filters' rejections, and a query whose every restart is
+ * rejected ends DFTPAV_PLAN_NO_VALID_RESTART, so a tick keeps the old plan.  With a table never filled, or all empty, nothing is
+ * rejected.  Off, a call allocates, clears and launches nothing of it and returns the same bits as before.
+ * dftpav_planner_set_own_slots(p, own, Q): the own slots [Q] (-1: none) of the queries of the NEXT dftpav_plan_queries call only,
+ *   which must bring Q queries (else DFTPAV_E_INVALID); that call consumes them, and the default is none.  dftpav_replan_tick sets
+ *   them itself to its query_slot: a slot that replans is not in conflict with the plan it replaces.
+ * dftpav_planner_last_conflicts(p, out): the rows [Q][n_restarts] of the last dftpav_plan_queries call, if it ran with the filter;
+ *   otherwise DFTPAV_E_INVALID.
+ *
+ * DFTPAV_E_INVALID, and nothing changed, decided before the handle is touched: a NULL b, p, out or poses; b and p on different
+ * handles; batch coefficients not available (nothing solved or set); K < 1 or K > DFTPAV_CONFLICT_MAX_SAMPLES; dt <= 0 or not finite;
+ * t0 or t_start not finite; margin NaN; range < margin or not finite; an own entry outside [-1, max_queries).
+ *
+ * Not claimed.  Candidates of the same call are not tested against each other.  A slot that replans in the same tick is tested as
+ * its old plan.  Between samples nothing is tested.  There is one vehicle size.  The moving obstacles of dftpav_set_surround take no
+ * part.  There is no trigger in dftpav_replan_tick: a caller who wants a slot to yield calls dftpav_replan_check for its start
+ * state, then dftpav_plan_queries and dftpav_planner_adopt. */
+int dftpav_batch_check_conflicts(dftpav_batch *b, dftpav_planner *p, double t_start, double t0, double dt, int K, double margin,
+                                 double range, const int *own /*[B] or NULL = none*/, const dftpav_conflict_out *out /*rows [B]*/);
+int dftpav_batch_sample_poses(dftpav_batch *b, double t_start, double t0, double dt, int K, double *poses /*[K][B][4]*/);
+int dftpav_batch_conflicts_last_ms(dftpav_handle *h, float *pose_ms, float *pair_ms);
+int dftpav_planner_set_conflict_filter(dftpav_planner *p, double margin, double range, double dt, int K); /* margin < 0: off (default) */
+int dftpav_planner_set_own_slots(dftpav_planner *p, const int *own /*[Q]*/, int Q);
+int dftpav_planner_last_conflicts(dftpav_planner *p, const dftpav_conflict_out *out /*rows [Q][n_restarts]*/);
+
 /* ---- the stamps: vehicle footprints written into the grid map on the device -------------------------------------------
  * Every stage that plans or checks a plan (search, goal field, rectangle corridor, collision re-check, replan check, distance
  * field, clearance) looks at the occupancy grid of dftpav_set_grid_map alone.  A stamp makes cells of that grid occupied where a

@@ -25,7 +25,7 @@ def _declare(L):
 
 
 _load = Loader(os.path.dirname(os.path.abspath(__file__)), "libconflict_oracle.so",
-               ("conflict_oracle.cpp", "../oracle_shared/ref_objects.h", "../oracle/step_trig.h", "../dftpav_amd/csrc/cr_trig.h"), _declare)
+               ("conflict_oracle.cpp", "candidate_oracle.cpp", "../oracle_shared/ref_objects.h", "../oracle/step_trig.h", "../dftpav_amd/csrc/cr_trig.h"), _declare)
 build, lib = _load.build, _load.lib
 
 
