@@ -1,4 +1,5 @@
-"""Developer script: the QUAD shape for several gear segments (solver_ref4m.hip) against the restatement on randomly shaped problems (run
+"""(The fixed part of what this script samples -- instances, gear_opt, short memories, workgroup shapes -- is tests/test_gpu_quadm_instances.py.)
+Developer script: the QUAD shape for several gear segments (solver_ref4m.hip) against the restatement on randomly shaped problems (run
 through gpurun).  Two to four gear segments of 2-8 pieces, 16 pieces and 48 variables at most, sample resolutions 3-24 (inner and end
 pieces apart), 1-60 trajectories, random limits / weights / L-BFGS memories (3 ... 300) / stopping rules / help_eps (the generic
 instantiation) / gear_opt, 1-3 persistent waves of 1, 2 or 4 per workgroup, slices of 2-80 evaluations, with and without the hand-over of

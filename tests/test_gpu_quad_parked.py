@@ -6,7 +6,7 @@ takes the piece-by-piece path.
 Bar: every evaluation's cost and gradient, and every output of every solve (x, cost, status, iterations, evaluations, hist_sum,
 success), BIT-EQUAL to the restatement of the reference (oracle/pyoracle.py, order 0).  Reference order, QUAD shape forced.
 
-The term counts a case depends on come from the restatement, not from the kernel: active_terms() below applies the activation tests
+The term counts a case depends on come from the restatement, not from the kernel: active_terms() (tests/quad_cases.py) applies the activation tests
 of addPVAGradCost2CT (oracle/dftpav_oracle.c: violaPos / violaVel / violaAcc / violaCurL / violaCurR > 0) to the coefficients the
 oracle formed at the evaluated point (OracleProblem.coeffs), and the oracle's own corridor and feasibility costs are zero exactly
 when no term is active.  The counts are steered by the durations of the rows under one velocity limit: a row with a third of its nominal duration
@@ -23,6 +23,7 @@ import pytest
 
 from dftpav_amd import scenarios as sc
 from dftpav_amd.pods import LayoutSpec
+from quad_cases import active_terms
 
 pytestmark = pytest.mark.gpu
 
@@ -48,51 +49,6 @@ def classes(counts, costs):
             assert cost == (0.0, 0.0), cost
         out.append("none" if tot == 0 else "over" if tot > POOL else "busy" if per.max() > WINDOW else "few" if tot <= WINDOW else "some")
     return out
-
-
-def active_terms(oracle, p, s, b, x):
-    """[N][Kmax + 1] active terms per (piece, point) of trajectory b at x, from the restatement's coefficients; and the oracle's
-    (corridor cost, feasibility cost) there."""
-    o = oracle.OracleProblem(p, s, b, order=0)
-    o.eval(x)
-    terms = o.cost_terms()
-    c, dt = o.coeffs()
-    N, H, sg = s.layout.piece_nums[0], s.layout.H, s.layout.singuls[0]
-    K, Kd = p.traj_resolution, p.des_traj_resolution
-    fwd = sg > 0
-    vmax, amax, cmax = ((p.max_forward_vel, p.max_forward_acc, p.max_forward_cur) if fwd else
-                        (p.max_backward_vel, p.max_backward_acc, p.max_backward_cur))
-    W, Lg, dcr = p.veh_width + 2 * p.half_margin, p.veh_length + 2 * p.half_margin, p.veh_d_cr
-    le = [(dcr + Lg / 2, W / 2), (dcr + Lg / 2, -W / 2), (dcr - Lg / 2, -W / 2), (dcr - Lg / 2, W / 2), (dcr + Lg / 2, W / 2)]
-    cor = np.array(s.corridor[b], dtype=np.float64)
-    cor[:, :, :2] /= np.linalg.norm(cor[:, :, :2], axis=2, keepdims=True)
-    out = np.zeros((N, max(K, Kd) + 1), dtype=np.int64)
-    pid = -1
-    for i in range(N):
-        Ki = Kd if i in (0, N - 1) else K
-        step, s1 = dt[0] / Ki, 0.0
-        for j in range(Ki + 1):
-            b0 = np.array([1.0, s1, s1 ** 2, s1 ** 3, s1 ** 4, s1 ** 5])
-            b1 = np.array([0.0, 1.0, 2 * s1, 3 * s1 ** 2, 4 * s1 ** 3, 5 * s1 ** 4])
-            b2 = np.array([0.0, 0.0, 2.0, 6 * s1, 12 * s1 ** 2, 20 * s1 ** 3])
-            s1 += step
-            pid += 1
-            sig, ds, dds = b0 @ c[i], b1 @ c[i], b2 @ c[i]
-            v = float(np.hypot(ds[0], ds[1]))
-            if v < 1e-4 or (i == 0 and j == 0) or (i == N - 1 and j == Ki):
-                continue
-            zh1 = float(dds @ ds)
-            zh3 = float(dds[1] * ds[0] - dds[0] * ds[1])
-            cur = zh3 / (v * v + s.help_eps) ** 1.5
-            n = int(v * v - vmax * vmax > 0) + int(zh1 * zh1 / (v * v) - amax * amax > 0) + int(cur - cmax > 0) + int(-cur - cmax > 0)
-            R = sg * np.array([[ds[0], -ds[1]], [ds[1], ds[0]]]) / v
-            for lx, ly in le:
-                bpt = sig + R @ np.array([lx, ly])
-                for k in range(H):
-                    col = cor[pid, k]
-                    n += int(col[0] * (bpt[0] - col[2]) + col[1] * (bpt[1] - col[3]) > 0)
-            out[i, j] = n
-    return out, (terms[2], terms[4])
 
 
 def _scene(pieces, K, Kd, scales, seed, H=4):

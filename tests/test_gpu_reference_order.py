@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from dftpav_amd import scenarios as sc
+from quad_cases import active_terms, extra_planes as _extra_planes
 
 pytestmark = pytest.mark.gpu
 
@@ -425,11 +426,15 @@ def test_quad_shape_with_gear_shifts_is_bit_identical(hiplib, oracle, monkeypatc
     assert fn(C.byref(s.layout.c_struct()), C.byref(p), 0, s.B, 256, out) == 0
     assert int(out[1]) == 5, "the plan did not pick the QUAD shape for several segments"
     rng = np.random.default_rng(4)
+    most = 0  # active terms of a piece, the largest count at a compared point (from the restatement's coefficients)
     for x in (bt.x0(), bt.x0() + rng.normal(0, 0.2, bt.x0().shape), bt.x0() + rng.normal(0, 0.7, bt.x0().shape)):
         f, g = bt.eval(x)
         for b in range(0, s.B, 3):
             fo, go = oracle.OracleProblem(p, s, b, order=2).eval(x[b])
             assert f[b] == fo and np.array_equal(g[b], go), (case, b)
+            most = max(most, int(active_terms(oracle, p, s, b, x[b], order=2)[0].sum(axis=1).max()))
+    # not vacuous for the parked terms: a piece keeps kMLcap = 8 of them in LDS, the rest goes to global scratch in blocks of 8
+    assert most > 8 and most > 16, most
     for rep in range(3):
         bt.set_hand_over(0 if rep == 2 else -1)
         r = bt.solve()
@@ -653,19 +658,6 @@ def test_trace_is_a_device_order_facility(hiplib):
     assert bt.solve()["success"].all()
     bt.close()
     h.close()
-
-
-def _extra_planes(base, H):
-    """the scenario `base` (H = 4 rectangles) with H half-planes per point: the extra ones are copies of the first ones pulled 0.2 m
-    inwards (so that they are the active ones), their normals un-normalised"""
-    cor = np.zeros((base.B, base.n_points, H, 4))
-    cor[:, :, :4] = base.corridor
-    for k in range(4, H):
-        cor[:, :, k] = base.corridor[:, :, k % 4]
-        cor[:, :, k, 2:] -= (0.2 + 0.05 * (k - 4)) * base.corridor[:, :, k % 4, :2]
-        cor[:, :, k, :2] *= 3.0
-    lay = type(base.layout)(base.layout.piece_nums, base.layout.singuls, H=H)
-    return sc.Scenario("planes_%d" % H, lay, base.K, base.Kd, base.B, base.ini_states, base.fin_states, base.inner_pts, base.init_Ts, np.ascontiguousarray(cor))
 
 
 @pytest.mark.parametrize("case", ["n79", "n77_two_segments", "H6", "H11", "n79_H7"])
