@@ -63,6 +63,7 @@ EXPORTS = [
     "dftpav_planner_check_conflicts", "dftpav_planner_sample_poses", "dftpav_conflicts_last_ms",
     "dftpav_batch_check_conflicts", "dftpav_batch_sample_poses", "dftpav_batch_conflicts_last_ms",
     "dftpav_planner_set_conflict_filter", "dftpav_planner_set_own_slots", "dftpav_planner_last_conflicts",
+    "dftpav_planner_set_joint_selection", "dftpav_planner_last_joint", "dftpav_joint_last_ms", "dftpav_debug_joint_select",
     "dftpav_grid_stamp_poses", "dftpav_planner_stamp_slots", "dftpav_grid_clear_stamps", "dftpav_grid_read_cells", "dftpav_stamp_last_ms",
     "dftpav_grid_render", "dftpav_grid_origin_centred", "dftpav_render_last_ms",
 ]
@@ -546,6 +547,15 @@ class Handle:
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         self._check(fn(self._h, C.byref(a), C.byref(b)), "batch_conflicts_last_ms")
         return float(a.value), float(b.value)
+
+    def joint_last_ms(self):
+        """dftpav_joint_last_ms: device ms of (the pose kernels, the pair kernel, the greedy and row kernels) of the last plan() with
+        joint selection or debug_joint_select (which runs no pose kernel); 0.0 for what has not run"""
+        a, b, c = C.c_float(0.0), C.c_float(0.0), C.c_float(0.0)
+        fn = lib().dftpav_joint_last_ms
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._check(fn(self._h, C.byref(a), C.byref(b), C.byref(c)), "joint_last_ms")
+        return float(a.value), float(b.value), float(c.value)
 
     def conflicts_last_ms(self):
         """dftpav_conflicts_last_ms: device ms of (the pose kernel, the pair and reduce kernels) of the last check_conflicts /
@@ -1075,6 +1085,24 @@ class Planner:
         self.handle._check(fn(self._p, C.byref(out.c)), "planner_last_conflicts")
         return out.arrays()
 
+    # ---- joint selection: the candidates of one call against each other
+    def set_joint_selection(self, on=True):
+        """dftpav_planner_set_joint_selection: with the conflict filter on, the restarts of one plan() are also tested against the
+        winners of the queries in front of their own (call order is priority); off by default"""
+        fn = lib().dftpav_planner_set_joint_selection
+        fn.argtypes = [C.c_void_p, C.c_int]
+        self.handle._check(fn(self._p, 1 if on else 0), "planner_set_joint_selection")
+
+    def last_joint(self, Q):
+        """dftpav_planner_last_joint: the rows [Q][R] of the last plan() of Q queries that ran with joint selection (the partner
+        index is a query index), and blocked [Q][R]"""
+        out = ConflictOut(int(Q), self.n_restarts)
+        blocked = np.zeros((int(Q), self.n_restarts), dtype=np.int32)
+        fn = lib().dftpav_planner_last_joint
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        self.handle._check(fn(self._p, C.byref(out.c), self._ip(blocked)), "planner_last_joint")
+        return dict(out.arrays(), blocked=blocked)
+
     def stamp_slots(self, t0, dt, K, inflate=0.0, select=None):
         """dftpav_planner_stamp_slots: the footprints of the selected slots (select [slots], 0: not this one; None: every occupied
         slot) at the clocks t0 + k dt, k < K -- the rows of sample_poses -- become occupied cells of the handle's working map"""
@@ -1108,6 +1136,29 @@ class Planner:
             self.close()
         except Exception:
             pass
+
+
+def debug_joint_select(handle, poses, cost, eligible, margin, range=None):
+    """dftpav_debug_joint_select: the pair, greedy and row kernels of joint selection on poses [K][Q][R][4] = cx, cy, cs, sn, cost and
+    eligible [Q][R] -> dict(winner [Q], blocked [Q][R], min_sep, sep_sample, sep_partner, conflict_sample, conflict_partner [Q][R])"""
+    c = np.ascontiguousarray(cost, dtype=np.float64)
+    e = np.ascontiguousarray(eligible, dtype=np.int32)
+    Q, R = c.shape
+    ps = np.ascontiguousarray(poses, dtype=np.float64)
+    K = ps.shape[0]
+    if ps.shape != (K, Q, R, 4) or e.shape != (Q, R):
+        raise DftpavError(E_INVALID, "debug_joint_select: poses [K][Q][R][4], cost and eligible [Q][R]")
+    w = np.zeros(Q, dtype=np.int32)
+    b = np.zeros((Q, R), dtype=np.int32)
+    out = ConflictOut(Q, R)
+    fn = lib().dftpav_debug_joint_select
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                   C.c_void_p]
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    m = float(margin)
+    handle._check(fn(handle._h, Q, R, K, ptr(ps), ptr(c), ptr(e), m, m if range is None else float(range), ptr(w), ptr(b), C.byref(out.c)),
+                  "debug_joint_select")
+    return dict(out.arrays(), winner=w, blocked=b)
 
 
 def debug_plan_select(handle, cost, success, collision):

@@ -23,9 +23,9 @@
 //               conflict_partner = min (k, j) over sep <= margin.  Nothing contributed: +inf, -1, -1, -1, -1.
 // Nothing of the table, the publisher's state or the batch is written.
 //
-// Not claimed: candidates of one call are not tested against each other; a slot that replans in the same tick is tested as its old
-// plan; between samples nothing is tested; one vehicle size; the moving obstacles of dftpav_set_surround take no part; no trigger
-// in dftpav_replan_tick.
+// Not claimed: candidates of one call are not tested against each other unless joint selection is on (joint_select.hip, §4.28); a
+// slot that replans in the same tick is tested as its old plan; between samples nothing is tested; one vehicle size; the moving
+// obstacles of dftpav_set_surround take no part; no trigger in dftpav_replan_tick.
 //
 // Two kernels.  cand_pair_kernel is conflict_pair_kernel's shape with the I side evaluated instead of loaded: one workgroup of 256
 // threads per 64 candidates, a lane a candidate, the four waves the samples k = wave, wave + 4, ...  Per sample a lane evaluates its
@@ -34,68 +34,15 @@
 // cf_sep in rising j.  A lane visits its (k, j) in rising order, so its minima are replaced on `<` alone; the four waves merge
 // through LDS by the full lexicographic rule and wave 0 writes the row.  The filter's variant writes row members[c / R] * R + c % R
 // and stores 1 into reject[c] where conflict_sample >= 0: only that lane, only where it rejects (§4.17).  cand_pose_kernel writes the
-// poses [K][B][4] for the read-out.  Both take the per-candidate segment durations from LDS (CandSegs), filled once per workgroup.
-// No atomics, no scratch.
+// poses [K][B][4] for the read-out.  Both take the per-candidate segment durations from LDS (CandSegs, cand_pose.h), filled once per
+// workgroup.  No atomics, no scratch.
 #include <hip/hip_runtime.h>
 
 #include "cand_conflict_args.h"
+#include "cand_pose.h"
 #include "conflict_sep.h"
 
 namespace dftpav {
-
-namespace {
-
-// the segments of a workgroup's 64 candidates: the layout's rows, and per candidate the piece duration and the duration of each
-struct CandSegs {
-  double dur[kMaxSeg][kConflictTile], dtp[kMaxSeg][kConflictTile];
-  int pn[kMaxSeg], sg[kMaxSeg], p0[kMaxSeg];
-};
-
-// filled by the whole workgroup of 256 threads for the candidates c0 .. c0 + 63; ends with a barrier
-__device__ inline void cand_fill_segments(CandSegs &S, const CandBatch &C, int c0) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int M = C.L.M, c = c0 + lane;
-  for (int i = wave; i < M; i += 4) {
-    const double dtp = c < C.B ? C.piece_dt[(size_t)c * M + i] : 0.0;
-    S.dtp[i][lane] = dtp;
-    S.dur[i][lane] = pe::segment_duration(C.L.piece_nums[i], dtp);
-  }
-  if ((int)threadIdx.x < M) {
-    S.pn[threadIdx.x] = C.L.piece_nums[threadIdx.x];
-    S.sg[threadIdx.x] = C.L.singuls[threadIdx.x];
-    S.p0[threadIdx.x] = C.L.seg_piece0[threadIdx.x];
-  }
-  __syncthreads();
-}
-
-// the pose of candidate c (< B; its segments in column `lane` of S) at clock t: conflict_pose_kernel's statements over the chained times
-__device__ inline void cand_pose(const CandBatch &C, const CandSegs &S, int c, int lane, double t, double &cx, double &cy, double &cs,
-                                 double &sn) {
-  const int M = C.L.M;
-  int e = 0;
-  double st = C.t_start, d = S.dur[0][lane], en = st + d; // exec_adopt_kernel: world = t_start; end = world + d
-  while (e < M - 1 && en <= t) {
-    e++;
-    st = en; // the next segment starts at that end
-    d = S.dur[e][lane];
-    en = st + d;
-  }
-  double tt = t - st;
-  if (tt < 0.0) tt = 0.0;
-  if (tt > d) tt = d;
-  const int idx = pe::locate_piece(S.pn[e], S.dtp[e][lane], tt);
-  const double *q = C.coeffs + ((size_t)c * C.L.Ntot + (size_t)(S.p0[e] + idx)) * 12;
-  double px, py, vx, vy;
-  pe::piece_pos(q, tt, px, py);
-  pe::piece_vel(q, tt, vx, vy);
-  const double sgn = (double)S.sg[e];
-  const double yaw = crt::atan2(sgn * vy, sgn * vx);
-  crt::sincos(yaw, sn, cs);
-  cx = px + C.dcr * cs;
-  cy = py + C.dcr * sn;
-}
-
-} // namespace
 
 __global__ void __launch_bounds__(256) cand_pose_kernel(CandPoseArgs A) {
   __shared__ CandSegs S;

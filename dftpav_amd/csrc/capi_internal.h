@@ -34,6 +34,7 @@
 #include "clearance_args.h"
 #include "conflict_args.h"
 #include "cand_conflict_args.h"
+#include "joint_args.h"
 #include "stamp_args.h"
 #include "render_args.h"
 #include "goalfield_args.h"
@@ -78,6 +79,12 @@ hipError_t launch_conflict_reduce(const ConflictReduceArgs &A, hipStream_t strea
 // cand_conflict.hip: the poses of a batch's candidates at K clocks; their separation from the table's poses, the rows per candidate
 hipError_t launch_cand_poses(const CandPoseArgs &A, hipStream_t stream);
 hipError_t launch_cand_pairs(const CandPairArgs &A, hipStream_t stream);
+// joint_select.hip: the candidates of a call against each other: their poses per group, the conflict bits per (I-tile, J-tile), the
+// greedy walk over the queries, the rows per candidate
+hipError_t launch_joint_poses(const JointPoseArgs &A, hipStream_t stream);
+hipError_t launch_joint_pairs(const JointPairArgs &A, hipStream_t stream);
+hipError_t launch_joint_greedy(const JointGreedyArgs &A, hipStream_t stream);
+hipError_t launch_joint_rows(const JointRowsArgs &A, hipStream_t stream);
 // stamp.hip: boxes into the working map, the bit map from the bytes again, the cells stamped since the base copy
 hipError_t launch_stamp_boxes(const StampBoxArgs &A, hipStream_t stream);
 hipError_t launch_stamp_bits(const StampBitsArgs &A, hipStream_t stream);
@@ -175,6 +182,9 @@ struct dftpav_handle {
   EventMarks<3> cand_ev; // cand_conflict.hip: in front of the pose kernel (the table's; dftpav_batch_sample_poses: the candidates'), between it
                          // and the pair kernel, behind the pair kernel; of the last dftpav_batch_sample_poses (complete to mark 1) /
                          // dftpav_batch_check_conflicts (to mark 2) call
+  EventMarks<4> joint_ev; // joint_select.hip: in front of the pose kernels, behind them, behind the pair kernel, behind the greedy and row
+                          // kernels; of the last dftpav_plan_queries call with joint selection or dftpav_debug_joint_select (marks 1 to 3)
+  bool joint_posed = false; // that chain ran the pose kernels
   // the stamps (stamp.hip): nothing of it exists until a stamp call.  d_cells stays the working map every call reads
   unsigned char *d_cells_base = nullptr; // the map as uploaded: copied by the first stamp after a dftpav_set_grid_map, which drops it
   unsigned char *d_stamp_ws = nullptr;   // dftpav_planner_stamp_slots: the poses 4 x [K][S_pad], occupied [S_pad], select [S_pad];
@@ -444,6 +454,35 @@ struct ConflictFilter {
   void release() { if (d) (void)hipFree(d); }
 };
 
+// Joint selection, an option of the conflict filter (joint_select.hip): the candidates of a call against each other, the queries in
+// call order.  One allocation: the poses 4 x [cap_K][C_pad], the conflict bits [C_pad][C_pad / 64], per candidate cost, eligibility,
+// flag index, blocked and the five rows, per query the winner and its candidate index.  The filters' shape: configure, clear, run
+// (the joint stage of a call, behind the last group), fetch, release.  It runs only with the conflict filter on.
+struct JointSelect {
+  bool on = false, last = false;
+  unsigned char *d = nullptr;
+  size_t cap = 0, cap_pad = 0; // candidates max_queries * R, and rounded up to whole tiles
+  int cap_K = 0;               // the K the allocation was made for
+  double *d_pose = nullptr, *d_cost = nullptr, *d_sep = nullptr;
+  unsigned long long *d_bits = nullptr;
+  int *d_elig = nullptr, *d_flag = nullptr, *d_blocked = nullptr, *d_winner = nullptr, *d_wcand = nullptr;
+  int *d_int = nullptr; // sep_sample | sep_partner | conflict_sample | conflict_partner, each [cap]
+  std::vector<double> h_inf; // +inf, the rows' min_sep before a call's kernels run
+  JointPoses P{};            // the poses of the running call
+  ConflictRows rows() const { return ConflictRows{d_sep, d_int, d_int + cap, d_int + 2 * cap, d_int + 3 * cap}; }
+  JointCands cands() const { return JointCands{d_cost, d_elig, d_flag}; }
+  static bool fits(size_t candidates, int K) {
+    return candidates <= (size_t)DFTPAV_JOINT_MAX_CANDIDATES && candidates * (size_t)(K > 0 ? K : 1) <= ((size_t)1 << 22);
+  }
+  int configure(struct dftpav_planner *p, int K); // DFTPAV_E_UNSUPPORTED beyond the two design bounds, and nothing changed
+  int clear(struct dftpav_planner *p, int Q, int K);
+  int pose_group(dftpav_handle *h, dftpav_batch *b, const int *members, int nm, int R, int flag0, const int *col, const int *reject,
+                 double t_call, double dt);
+  int run(struct dftpav_planner *p, int Q, double margin, double range); // pair bits, greedy, rows
+  int fetch(dftpav_handle *h, const dftpav_conflict_out *out, int *blocked, size_t n_rows);
+  void release() { if (d) (void)hipFree(d); }
+};
+
 struct dftpav_planner {
   dftpav_handle *h = nullptr;
   int max_queries = 0, R = 0;
@@ -511,6 +550,7 @@ struct dftpav_planner {
   PenaltyFilter pen;
   ClearanceFilter clr;
   ConflictFilter cnf;
+  JointSelect jnt; // dftpav_planner_set_joint_selection
   std::vector<int> own_next; // dftpav_planner_set_own_slots: the own slots [Q] of the next dftpav_plan_queries call, which consumes them
 };
 

@@ -89,6 +89,7 @@ extern "C" void dftpav_planner_destroy(dftpav_planner *p) {
   p->pen.release();
   p->clr.release();
   p->cnf.release();
+  p->jnt.release();
   delete p; // (its EventMarks' events with it)
 }
 
@@ -380,6 +381,8 @@ static int plan_clear_filter_rows(PlanCall &c) {
     if (int rc = p->pen.clear(h, rows)) return rc;
   if (p->cnf.on) // with the own slots of the call and the table's poses at its clocks
     if (int rc = p->cnf.clear(p, rows, c.t_now, c.own)) return rc;
+  if (p->cnf.on && p->jnt.on) // the joint rows, and NaN for the poses of the queries no group holds
+    if (int rc = p->jnt.clear(p, c.Q, p->cnf.K)) return rc;
   if (p->lim.on || p->clr.on || p->pen.on || p->cnf.on) HIPCHK(h, hipMemsetAsync(p->d_reject, 0, sizeof(int) * rows, h->stream));
   return DFTPAV_OK;
 }
@@ -466,7 +469,8 @@ static int plan_select_group(PlanCall &c, int g, int *col, int *fst, int *rej) {
 }
 
 // one group: pack -> rectangles -> solve -> coefficients -> collision re-check (-> limits) (-> clearance) (-> penalty gate) (-> conflicts) -> selection;
-// nothing waits in between, or between groups
+// nothing waits in between, or between groups.  With joint selection on the group ends behind its filters: its batch stays resident,
+// and its candidates' poses and its selection follow the last group (plan_joint_stage)
 static int plan_one_group(PlanCall &c, int g) {
   dftpav_planner *p = c.p;
   dftpav_handle *h = c.h;
@@ -492,7 +496,33 @@ static int plan_one_group(PlanCall &c, int g) {
     if (int rc = p->pen.run(h, b, members, nm, R, rej)) return rc;
   if (p->cnf.on) // rejects a trajectory that comes within the margin of an executing plan
     if (int rc = p->cnf.run(h, b, members, nm, R, rej)) return rc;
+  if (p->cnf.on && p->jnt.on) return DFTPAV_OK; // the selection waits for the joint stage
   return plan_select_group(c, g, col, fst, rej);
+}
+
+// joint selection, behind the last group: the candidates of the call against each other, the blocked ones flagged, then the
+// selection of every group as plan_one_group would have launched it
+static int plan_joint_stage(PlanCall &c) {
+  dftpav_planner *p = c.p;
+  dftpav_handle *h = c.h;
+  h->joint_ev.reset(); // until the whole chain has run
+  h->joint_posed = true;
+  HIPCHK(h, h->joint_ev.record(0, h->stream));
+  for (size_t g = 0; g < c.batch.size(); g++) { // every group's candidates in query order: poses, cost, eligibility, flag index
+    const int nm = c.g_off[g + 1] - c.g_off[g];
+    if (!c.batch[g] || nm == 0) continue;
+    const size_t row0 = (size_t)c.g_off[g] * c.R;
+    if (int rc = p->jnt.pose_group(h, c.batch[g], p->d_members + c.g_off[g], nm, c.R, (int)row0, p->d_col + row0, p->d_reject + row0, c.t_now, p->cnf.dt))
+      return rc;
+  }
+  HIPCHK(h, h->joint_ev.record(1, h->stream));
+  if (int rc = p->jnt.run(p, c.Q, p->cnf.margin, p->cnf.range)) return rc;
+  for (size_t g = 0; g < c.batch.size(); g++) {
+    if (!c.batch[g] || c.g_off[g + 1] == c.g_off[g]) continue;
+    const size_t row0 = (size_t)c.g_off[g] * c.R;
+    if (int rc = plan_select_group(c, (int)g, p->d_col + row0, p->d_first + row0, p->d_reject + row0)) return rc;
+  }
+  return DFTPAV_OK;
 }
 
 // the compact results, the final wait, the statuses that depend on them, and what dftpav_planner_adopt needs of this call
@@ -550,6 +580,8 @@ static int plan_results(PlanCall &c) {
   p->pen.last = p->pen.on;
   p->clr.last = p->clr.on;
   p->cnf.last = p->cnf.on;
+  p->jnt.last = p->cnf.on && p->jnt.on;
+  if (p->jnt.last) h->joint_ev.complete();
   return DFTPAV_OK;
 }
 
@@ -559,7 +591,7 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
   p->group_sizes.clear();
   p->plan_ev.reset();
   p->last_Q = 0; // nothing to adopt, no filter rows to read, until this call has ended well
-  p->lim.last = p->pen.last = p->clr.last = p->cnf.last = false;
+  p->lim.last = p->pen.last = p->clr.last = p->cnf.last = p->jnt.last = false;
   std::vector<int> own;
   own.swap(p->own_next); // consumed by this call, whatever becomes of it
   if (Q == 0) return DFTPAV_OK;
@@ -573,6 +605,8 @@ extern "C" int dftpav_plan_queries(dftpav_planner *p, const dftpav_plan_params *
   if (int rc = plan_clear_filter_rows(c)) return rc; // (nothing with every filter off)
   for (size_t g = 0; g < c.batch.size(); g++)
     if (int rc = plan_one_group(c, (int)g)) return rc;
+  if (p->cnf.on && p->jnt.on)
+    if (int rc = plan_joint_stage(c)) return rc;
   HIPCHK(c.h, p->plan_ev.record(3, c.h->stream));
   p->plan_ev.complete();
   return plan_results(c);
@@ -1718,7 +1752,19 @@ extern "C" int dftpav_planner_set_conflict_filter(dftpav_planner *p, double marg
     return DFTPAV_OK;
   }
   if (!conflict_clocks_ok(0.0, dt, K) || !std::isfinite(range) || range < margin) return DFTPAV_E_INVALID;
-  return p->cnf.configure(p, margin, range, dt, K);
+  // joint selection holds poses at the filter's K: its bound is tested before anything changes; its allocation grows first and alone
+  // (a larger one that the filter then does not use changes nothing a call can see), and the filter's parameters change last
+  if (p->jnt.on && !JointSelect::fits((size_t)p->max_queries * p->R, K)) return DFTPAV_E_UNSUPPORTED;
+  const bool was_on = p->cnf.on;
+  const double m0 = p->cnf.margin, r0 = p->cnf.range, d0 = p->cnf.dt;
+  const int K0 = p->cnf.K;
+  if (int rc = p->cnf.configure(p, margin, range, dt, K)) return rc; // (a failed allocation leaves the filter as it was)
+  if (p->jnt.on)
+    if (int rc = p->jnt.configure(p, K)) { // the filter back to what it was: a refused call changes nothing
+      p->cnf.on = was_on, p->cnf.margin = m0, p->cnf.range = r0, p->cnf.dt = d0, p->cnf.K = K0;
+      return rc;
+    }
+  return DFTPAV_OK;
 }
 
 extern "C" int dftpav_planner_set_own_slots(dftpav_planner *p, const int *own, int Q) {
@@ -1734,6 +1780,211 @@ extern "C" int dftpav_planner_last_conflicts(dftpav_planner *p, const dftpav_con
   HIPCHK(h, hipSetDevice(h->device));
   if (int rc = p->cnf.fetch(h, out, (size_t)p->last_Q * p->R)) return rc;
   HIPCHK(h, hipStreamSynchronize(h->stream));
+  return DFTPAV_OK;
+}
+
+// ------------------------------------------------- joint selection: the candidates of one call against each other (joint_select.hip)
+int JointSelect::configure(dftpav_planner *p, int K_) {
+  dftpav_handle *h = p->h;
+  const size_t C = (size_t)p->max_queries * p->R;
+  if (!fits(C, K_)) return DFTPAV_E_UNSUPPORTED;
+  const int K = K_ > 0 ? K_ : 1;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (!d || cap_K < K) { // the poses are sized by K: a larger K takes a new allocation
+    const size_t C_pad = (C + kConflictTile - 1) / kConflictTile * kConflictTile, Q = (size_t)p->max_queries;
+    double *pose = nullptr, *cost = nullptr, *sep = nullptr;
+    unsigned long long *bits = nullptr;
+    int *elig = nullptr, *flag = nullptr, *blk = nullptr, *win = nullptr, *wc = nullptr, *ints = nullptr;
+    auto fields = [&](auto &take) {
+      pose = (double *)take(sizeof(double) * 4 * (size_t)K * C_pad);
+      bits = (unsigned long long *)take(sizeof(unsigned long long) * C_pad * (C_pad / kConflictTile));
+      cost = (double *)take(sizeof(double) * C);
+      sep = (double *)take(sizeof(double) * C);
+      ints = (int *)take(sizeof(int) * 4 * C);
+      elig = (int *)take(sizeof(int) * C);
+      flag = (int *)take(sizeof(int) * C);
+      blk = (int *)take(sizeof(int) * C);
+      win = (int *)take(sizeof(int) * Q);
+      wc = (int *)take(sizeof(int) * Q);
+    };
+    unsigned char *fresh = nullptr;
+    HIPCHK(h, hipMalloc(&fresh, carve(nullptr, fields)));
+    if (d) { // (nothing of the old one is in flight behind this wait)
+      (void)hipStreamSynchronize(h->stream);
+      (void)hipFree(d);
+    }
+    carve(fresh, fields);
+    d = fresh;
+    d_pose = pose, d_bits = bits, d_cost = cost, d_sep = sep, d_int = ints, d_elig = elig, d_flag = flag, d_blocked = blk, d_winner = win, d_wcand = wc;
+    cap = C;
+    cap_pad = C_pad;
+    cap_K = K;
+    h_inf.assign(C, HUGE_VAL);
+  }
+  on = true;
+  return DFTPAV_OK;
+}
+// the rows +inf, -1; nobody eligible, no flag, nobody blocked; NaN (all bits set) for every pose of the call
+int JointSelect::clear(dftpav_planner *p, int Q, int K) {
+  dftpav_handle *h = p->h;
+  const size_t C = (size_t)Q * p->R, C_pad = (C + kConflictTile - 1) / kConflictTile * kConflictTile, n = (size_t)K * C_pad;
+  if (C > cap || K > cap_K) return DFTPAV_E_INVALID; // (configure sized it for the planner and the filter)
+  P = JointPoses{d_pose, d_pose + n, d_pose + 2 * n, d_pose + 3 * n, K, (int)C_pad};
+  const ConflictRows r = rows();
+  HIPCHK(h, hipMemcpyAsync(r.min_sep, h_inf.data(), sizeof(double) * C, hipMemcpyHostToDevice, h->stream));
+  for (int *row : {r.sep_sample, r.sep_partner, r.conflict_sample, r.conflict_partner, d_flag})
+    HIPCHK(h, hipMemsetAsync(row, 0xff, sizeof(int) * C, h->stream));
+  HIPCHK(h, hipMemsetAsync(d_elig, 0, sizeof(int) * C, h->stream));
+  HIPCHK(h, hipMemsetAsync(d_blocked, 0, sizeof(int) * C, h->stream));
+  HIPCHK(h, hipMemsetAsync(d_cost, 0, sizeof(double) * C, h->stream));
+  HIPCHK(h, hipMemsetAsync(d_pose, 0xff, sizeof(double) * 4 * n, h->stream));
+  return DFTPAV_OK;
+}
+int JointSelect::pose_group(dftpav_handle *h, dftpav_batch *b, const int *members, int nm, int R, int flag0, const int *col,
+                            const int *reject, double t_call, double dt) {
+  JointPoseArgs A{};
+  A.C = cand_batch(h, b, nm * R, t_call, t_call, dt);
+  A.P = P;
+  A.J = cands();
+  A.members = members;
+  A.R = R;
+  A.flag0 = flag0;
+  A.f = b->d_f;
+  A.success = b->d_success;
+  A.collision = col;
+  A.reject = reject;
+  HIPCHK(h, launch_joint_poses(A, h->stream));
+  return DFTPAV_OK;
+}
+// the three stages behind the poses on the handle's stream: marks 2 and 3 of joint_ev (nothing waits)
+static int joint_stages(dftpav_handle *h, const JointPoses &P, const JointCands &J, unsigned long long *bits, int Q, int R, double margin,
+                        double range, const int *minit, int *reject, int *winner, int *wcand, int *blocked, const ConflictRows &rows) {
+  CandPairArgs V{}; // the vehicle and the two distances, as every pair launch forms them
+  cand_pair_consts(h, margin, range, V);
+  JointPairArgs A{};
+  A.P = P;
+  A.bits = bits;
+  A.C = Q * R;
+  A.R = R;
+  A.tiles = P.C_pad / kConflictTile;
+  A.half_l = V.half_l, A.half_w = V.half_w, A.margin = V.margin, A.reach2 = V.reach2;
+  HIPCHK(h, launch_joint_pairs(A, h->stream));
+  HIPCHK(h, h->joint_ev.record(2, h->stream));
+  JointGreedyArgs G{};
+  G.bits = bits;
+  G.J = J;
+  G.minit = minit;
+  G.Q = Q;
+  G.R = R;
+  G.tiles = A.tiles;
+  G.winner = winner;
+  G.wcand = wcand;
+  G.blocked = blocked;
+  G.reject = reject;
+  HIPCHK(h, launch_joint_greedy(G, h->stream));
+  JointRowsArgs W{};
+  W.P = P;
+  W.wcand = wcand;
+  W.rows = rows;
+  W.C = A.C;
+  W.Q = Q;
+  W.R = R;
+  W.half_l = V.half_l, W.half_w = V.half_w, W.margin = V.margin, W.reach2 = V.reach2;
+  HIPCHK(h, launch_joint_rows(W, h->stream));
+  HIPCHK(h, h->joint_ev.record(3, h->stream));
+  return DFTPAV_OK;
+}
+int JointSelect::run(dftpav_planner *p, int Q, double margin, double range) {
+  return joint_stages(p->h, P, cands(), d_bits, Q, p->R, margin, range, p->d_minit, p->d_reject, d_winner, d_wcand, d_blocked, rows());
+}
+int JointSelect::fetch(dftpav_handle *h, const dftpav_conflict_out *out, int *blocked, size_t n_rows) {
+  const ConflictRows r = rows();
+  HIPCHK(h, fetch_async(h, out->min_sep, r.min_sep, sizeof(double) * n_rows));
+  HIPCHK(h, fetch_async(h, out->sep_sample, r.sep_sample, sizeof(int) * n_rows));
+  HIPCHK(h, fetch_async(h, out->sep_partner, r.sep_partner, sizeof(int) * n_rows));
+  HIPCHK(h, fetch_async(h, out->conflict_sample, r.conflict_sample, sizeof(int) * n_rows));
+  HIPCHK(h, fetch_async(h, out->conflict_partner, r.conflict_partner, sizeof(int) * n_rows));
+  HIPCHK(h, fetch_async(h, blocked, d_blocked, sizeof(int) * n_rows));
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_planner_set_joint_selection(dftpav_planner *p, int on) {
+  if (!p || (on != 0 && on != 1)) return DFTPAV_E_INVALID;
+  if (!on) { // off: the buffers stay, nothing reads them
+    p->jnt.on = false;
+    return DFTPAV_OK;
+  }
+  return p->jnt.configure(p, p->cnf.K);
+}
+
+extern "C" int dftpav_planner_last_joint(dftpav_planner *p, const dftpav_conflict_out *out, int *blocked) {
+  if (!p || !out || !p->jnt.last || p->last_Q <= 0) return DFTPAV_E_INVALID;
+  dftpav_handle *h = p->h;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (int rc = p->jnt.fetch(h, out, blocked, (size_t)p->last_Q * p->R)) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_joint_last_ms(dftpav_handle *h, float *pose_ms, float *pair_ms, float *select_ms) {
+  if (!h) return DFTPAV_E_INVALID;
+  for (float *ms : {pose_ms, pair_ms, select_ms})
+    if (ms) *ms = 0.0f;
+  if (!h->joint_ev.reached(3)) return DFTPAV_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (pose_ms && h->joint_posed) HIPCHK(h, h->joint_ev.elapsed(pose_ms, 0, 1, false)); // (both chains waited for the stream)
+  if (pair_ms) HIPCHK(h, h->joint_ev.elapsed(pair_ms, 1, 2, false));
+  if (select_ms) HIPCHK(h, h->joint_ev.elapsed(select_ms, 2, 3, false));
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_debug_joint_select(dftpav_handle *h, int Q, int R, int K, const double *poses, const double *cost, const int *eligible,
+                                         double margin, double range, int *winner, int *blocked, const dftpav_conflict_out *out) {
+  if (!h || !poses || !cost || !eligible || Q < 1 || R < 1 || !conflict_clocks_ok(0.0, 1.0, K)) return DFTPAV_E_INVALID;
+  if (margin != margin || !std::isfinite(range) || range < margin) return DFTPAV_E_INVALID; // (+inf fails range < margin)
+  if ((long long)Q * R > DFTPAV_JOINT_MAX_CANDIDATES || !JointSelect::fits((size_t)Q * R, K)) return DFTPAV_E_UNSUPPORTED;
+  HIPCHK(h, hipSetDevice(h->device));
+  const size_t C = (size_t)Q * R, C_pad = (C + kConflictTile - 1) / kConflictTile * kConflictTile, n = (size_t)K * C_pad;
+  // cx | cy | cs | sn, each [K][C_pad], NaN behind the last candidate; declared in front of tmp, whose end waits for the stream
+  std::vector<double> soa(4 * n, std::nan(""));
+  std::vector<int> elig(C);
+  for (size_t k = 0; k < (size_t)K; k++)
+    for (size_t i = 0; i < C; i++) {
+      const double *ps = poses + (k * C + i) * 4; // a pose with a component that is not finite takes no part: NaN throughout
+      if (!(std::isfinite(ps[0]) && std::isfinite(ps[1]) && std::isfinite(ps[2]) && std::isfinite(ps[3]))) continue;
+      for (size_t f = 0; f < 4; f++) soa[f * n + k * C_pad + i] = ps[f];
+    }
+  for (size_t i = 0; i < C; i++) elig[i] = eligible[i] != 0 ? 1 : 0;
+  DevScratch tmp(h);
+  double *d_pose = nullptr, *d_dbl = nullptr; // d_dbl: cost | min_sep
+  unsigned long long *d_bits = nullptr;
+  int *d_int = nullptr; // eligible | blocked | four rows, each [C]; winner | wcand, each [Q]
+  HIPCHK(h, tmp.alloc(d_pose, 4 * n));
+  HIPCHK(h, tmp.alloc(d_dbl, 2 * C));
+  HIPCHK(h, tmp.alloc(d_bits, C_pad * (C_pad / kConflictTile)));
+  HIPCHK(h, tmp.alloc(d_int, 6 * C + 2 * (size_t)Q));
+  HIPCHK(h, hipMemcpyAsync(d_pose, soa.data(), sizeof(double) * 4 * n, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_dbl, cost, sizeof(double) * C, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_int, elig.data(), sizeof(int) * C, hipMemcpyHostToDevice, h->stream));
+  const JointPoses P{d_pose, d_pose + n, d_pose + 2 * n, d_pose + 3 * n, K, (int)C_pad};
+  const JointCands J{d_dbl, d_int, nullptr};
+  int *d_blocked = d_int + C, *d_rows = d_int + 2 * C, *d_winner = d_int + 6 * C, *d_wcand = d_winner + Q;
+  const ConflictRows rows{d_dbl + C, d_rows, d_rows + C, d_rows + 2 * C, d_rows + 3 * C};
+  h->joint_ev.reset();
+  h->joint_posed = false;
+  HIPCHK(h, h->joint_ev.record(1, h->stream));
+  if (int rc = joint_stages(h, P, J, d_bits, Q, R, margin, range, nullptr, nullptr, d_winner, d_wcand, d_blocked, rows)) return rc;
+  HIPCHK(h, fetch_async(h, winner, d_winner, sizeof(int) * (size_t)Q));
+  HIPCHK(h, fetch_async(h, blocked, d_blocked, sizeof(int) * C));
+  if (out) {
+    HIPCHK(h, fetch_async(h, out->min_sep, rows.min_sep, sizeof(double) * C));
+    HIPCHK(h, fetch_async(h, out->sep_sample, rows.sep_sample, sizeof(int) * C));
+    HIPCHK(h, fetch_async(h, out->sep_partner, rows.sep_partner, sizeof(int) * C));
+    HIPCHK(h, fetch_async(h, out->conflict_sample, rows.conflict_sample, sizeof(int) * C));
+    HIPCHK(h, fetch_async(h, out->conflict_partner, rows.conflict_partner, sizeof(int) * C));
+  }
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->joint_ev.complete();
   return DFTPAV_OK;
 }
 

@@ -1250,10 +1250,10 @@ int dftpav_conflicts_last_ms(dftpav_handle *h, float *pose_ms, float *pair_ms);
  * handles; batch coefficients not available (nothing solved or set); K < 1 or K > DFTPAV_CONFLICT_MAX_SAMPLES; dt <= 0 or not finite;
  * t0 or t_start not finite; margin NaN; range < margin or not finite; an own entry outside [-1, max_queries).
  *
- * Not claimed.  Candidates of the same call are not tested against each other.  A slot that replans in the same tick is tested as
- * its old plan.  Between samples nothing is tested.  There is one vehicle size.  The moving obstacles of dftpav_set_surround take no
- * part.  There is no trigger in dftpav_replan_tick: a caller who wants a slot to yield calls dftpav_replan_check for its start
- * state, then dftpav_plan_queries and dftpav_planner_adopt. */
+ * Not claimed.  Candidates of the same call are not tested against each other unless joint selection is on (below).  A slot that
+ * replans in the same tick is tested as its old plan.  Between samples nothing is tested.  There is one vehicle size.  The moving
+ * obstacles of dftpav_set_surround take no part.  There is no trigger in dftpav_replan_tick: a caller who wants a slot to yield
+ * calls dftpav_replan_check for its start state, then dftpav_plan_queries and dftpav_planner_adopt. */
 int dftpav_batch_check_conflicts(dftpav_batch *b, dftpav_planner *p, double t_start, double t0, double dt, int K, double margin,
                                  double range, const int *own /*[B] or NULL = none*/, const dftpav_conflict_out *out /*rows [B]*/);
 int dftpav_batch_sample_poses(dftpav_batch *b, double t_start, double t0, double dt, int K, double *poses /*[K][B][4]*/);
@@ -1261,6 +1261,69 @@ int dftpav_batch_conflicts_last_ms(dftpav_handle *h, float *pose_ms, float *pair
 int dftpav_planner_set_conflict_filter(dftpav_planner *p, double margin, double range, double dt, int K); /* margin < 0: off (default) */
 int dftpav_planner_set_own_slots(dftpav_planner *p, const int *own /*[Q]*/, int Q);
 int dftpav_planner_last_conflicts(dftpav_planner *p, const dftpav_conflict_out *out /*rows [Q][n_restarts]*/);
+
+/* ---- joint selection: the candidate plans of one call tested against each other ------------------------------------------
+ * The conflict filter tests a candidate against the plans that execute.  When two queries of one call replan, each new plan is
+ * tested against the other's OLD plan only, and both winners may cross at the same clock.  Joint selection closes that hole: it
+ * is an option of the conflict filter (joint_select.hip) and uses the filter's margin, range, dt, K, its clocks
+ * t_k = t_call + (double)k * dt, and its candidate pose: the pose after an adoption at t_start = t_call, held still before and
+ * after.  Take a call of Q queries with R restarts each.
+ *
+ *   priority        the call's query order: query q' has priority over q when q' < q.  In dftpav_replan_tick this is the order of
+ *                   the tick's query list.
+ *   eligible(q, r)  the selection's test: succeeded, not colliding, no reject flag from the limit / clearance / penalty / conflict
+ *                   filters, and a cost that is not NaN.  A query outside every layout group (no path, arrived, an unsupported
+ *                   layout) has no eligible restart; neither has a query with a restart below mini_T (no plan is reported for it,
+ *                   so it blocks nobody).
+ *   conf(a, b)      for two candidates a = (q, r), b = (q', r') with q != q': there is a k < K with sep_k(a, b) <= margin.  sep_k is
+ *                   steps 1 to 3 of the conflict check in the same expressions: the broad phase on the centres against
+ *                   range + 2.0 * rad, the separating-axis test, the 32 corner-to-edge distances.  A pair outside the broad phase
+ *                   contributes nothing; so does a pose that is not finite on either side.
+ *   for q = 0, 1, ..., Q - 1 in turn:
+ *     blocked(q, r) holds when a q' < q with a winner w(q') >= 0 exists and conf((q, r), (q', w(q'))).
+ *     w(q)          the cheapest restart that is eligible and not blocked; ties go to the lowest r; -1 if there is none.
+ *     Only WINNERS block: a rejected or dearer restart of q' blocks nobody.
+ *   rows            per candidate (q, r), by the lexicographic rules above; the partners are the winners (q', w(q')) with q' < q and
+ *                   the partner index is the QUERY index q':
+ *                     min_sep, sep_sample, sep_partner     the minimum of (sep, k, q')
+ *                     conflict_sample, conflict_partner    the minimum of (k, q') over sep <= margin
+ *                   +inf, -1, -1, -1, -1 where nothing contributed.  blocked(q, r) == (conflict_sample >= 0), and both are reported.
+ *   effect          a blocked restart gets the call's reject flag; the selection then runs unchanged and arrives at w(q).  With
+ *                   joint selection on, the per-group selections run behind the joint stage, which runs once after the last
+ *                   group.  A query with every restart blocked ends DFTPAV_PLAN_NO_VALID_RESTART, so a tick keeps its old plan.
+ *   The table test stays as it is: a candidate is still tested against the old plan of every other occupied slot, replanning or
+ *   not.  This is conservative: the other slot may fail to replan and keep that plan.
+ *
+ * Off by default.  Off, or with the conflict filter off, a call allocates, clears and launches nothing of it; the order of launches
+ * and every returned bit are those of a planner without it.
+ *
+ * dftpav_planner_set_joint_selection(p, on): on is 0 or 1 (else DFTPAV_E_INVALID).  It makes its one allocation here (poses,
+ *   conflict bits, rows), sized by max_queries * n_restarts and the filter's K, and reallocates when the filter is configured with a
+ *   larger K.  Two design bounds: max_queries * n_restarts <= DFTPAV_JOINT_MAX_CANDIDATES (the conflict bits are then 8 MiB), and
+ *   candidates x K <= 2^22 (128 MiB of poses).  Beyond either it refuses with DFTPAV_E_UNSUPPORTED and changes nothing; so does
+ *   dftpav_planner_set_conflict_filter when, with joint selection on, its K would pass the second bound.
+ * dftpav_planner_last_joint(p, out, blocked): the rows [Q][n_restarts] and blocked [Q][n_restarts] (or NULL) of the last
+ *   dftpav_plan_queries call, if it ran with joint selection (and so with the conflict filter); otherwise DFTPAV_E_INVALID.
+ * dftpav_joint_last_ms(h, pose_ms, pair_ms, select_ms): device time in ms (the handle's HIP events) of the pose kernels, of the pair
+ *   kernel, and of the greedy and row kernels, of the last such call or dftpav_debug_joint_select (which runs no pose kernel); 0.0
+ *   for what has not run.  Any pointer may be NULL.
+ * dftpav_debug_joint_select (test hook): the pair, greedy and row kernels on caller-given poses [K][Q * R][4] = cx, cy, cs, sn, cost
+ *   [Q * R] and eligible [Q * R] (0 / not 0), with the handle's vehicle size.  winner [Q], blocked [Q * R], out (rows [Q * R]) and
+ *   every pointer of out may be NULL.  DFTPAV_E_INVALID, and nothing written: h, poses, cost or eligible NULL; Q < 1 or R < 1; K < 1
+ *   or K > DFTPAV_CONFLICT_MAX_SAMPLES; margin NaN; range < margin or not finite.  DFTPAV_E_UNSUPPORTED, and nothing written, beyond
+ *   the two design bounds.
+ *
+ * Not claimed.  Priorities other than call order.  No excusing of a replanning slot's old plan.  Nothing between samples.  One
+ * vehicle size.  Greedy, not jointly optimal: a lower-priority query can end without a plan where a different choice for a higher
+ * one would have served both. */
+#define DFTPAV_JOINT_MAX_CANDIDATES 8192 /* the cap on max_queries * n_restarts of joint selection */
+int dftpav_planner_set_joint_selection(dftpav_planner *p, int on); /* off by default */
+int dftpav_planner_last_joint(dftpav_planner *p, const dftpav_conflict_out *out /*rows [Q][n_restarts]*/,
+                              int *blocked /*[Q][n_restarts] or NULL*/);
+int dftpav_joint_last_ms(dftpav_handle *h, float *pose_ms, float *pair_ms, float *select_ms);
+int dftpav_debug_joint_select(dftpav_handle *h, int Q, int R, int K, const double *poses /*[K][Q*R][4]*/, const double *cost /*[Q*R]*/,
+                              const int *eligible /*[Q*R]*/, double margin, double range, int *winner /*[Q]*/, int *blocked /*[Q*R]*/,
+                              const dftpav_conflict_out *out /*rows [Q*R]*/);
 
 /* ---- the stamps: vehicle footprints written into the grid map on the device -------------------------------------------
  * Every stage that plans or checks a plan (search, goal field, rectangle corridor, collision re-check, replan check, distance
