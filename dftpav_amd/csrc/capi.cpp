@@ -1316,6 +1316,7 @@ extern "C" int dftpav_batch_set_order(dftpav_batch *b, int order) {
         (hipMalloc(&hist_m, sizeof(double) * quad_mirror_doubles(b->L, b->B)) != hipSuccess ||
          hipMemset(hist_m, 0, sizeof(double) * quad_mirror_doubles(b->L, b->B)) != hipSuccess))
       return undo("reference order: no device memory for the QUAD shape's mirror of the history ends");
+    if (prepare_solver_quad(pl) != hipSuccess) return undo("reference order: the QUAD kernel does not take the plan's dynamic LDS");
     if (new_tab && (hipMalloc(&d_tab, sizeof(double) * tab.size()) != hipSuccess ||
                     hipMalloc(&d_scr, sizeof(double) * reference_order_scratch_doubles(b->L, b->B, h->S)) != hipSuccess ||
                     hipMemcpy(d_tab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice) != hipSuccess))

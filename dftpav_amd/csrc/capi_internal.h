@@ -108,6 +108,7 @@ RefPlan reference_order_plan(const DevLayout &L, const DevParams &P, int S, int 
 hipError_t launch_ring_reset(const DevBatch &D, hipStream_t stream);
 hipError_t launch_solver_ref(const DevBatch &D, const DevBatch *d_dev, int mode, const double *tabs, double *scratch, const RefPlan &pl, int scheduled,
                              hipStream_t stream);
+hipError_t prepare_solver_quad(const RefPlan &pl); // once per plan, in front of its first launch_solver_quad
 hipError_t launch_solver_quad(const DevBatch &D, const DevBatch *d_dev, int mode, const double *tabs, const double *cor_t, bool rect, double *scratch,
                               const RefPlan &pl, int scheduled, bool alone, hipStream_t stream);
 // the QUAD shapes' copy of the corridor (solver_ref4.hip: one gear segment, solver_ref4m.hip: several)

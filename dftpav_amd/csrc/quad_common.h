@@ -2,6 +2,8 @@
 // solver_ref4m.hip: several): a row of a wave is a trajectory, its sixteen lanes are its pieces.  The substitution sweeps with the
 // rows in registers (quad_sweep and its two row updates), and the sizes of solver_ref4.hip's LDS.
 #pragma once
+#include <utility>
+
 #include "ref_order_common.h"
 
 namespace dftpav {
@@ -15,6 +17,27 @@ __device__ __forceinline__ double row_chain16(double acc, double v) {
   asm volatile("s_nop 1\n\t" DFTPAV_FMAC_BCAST16 : "+v"(acc) : "v"(v), "v"(one));
   return acc;
 }
+// three such chains, link by link side by side: a0 += v0[lane k], a1 += v1[lane k], a2 += v2[lane k] for k = 0 .. 15.  Each sum takes
+// its sixteen additions in row_chain16's order, one rounding per link; a link waits for its own chain's previous one only, so the
+// three dependent latencies overlap.  (A -0.0 in v leaves its sum as it is: fma(-0.0, 1.0, a) rounds a + (-0.0) once, which is a for
+// every a -- for a = +0.0 too, the sum of +0.0 and -0.0 being +0.0 in round-to-nearest -- and no sum here starts from -0.0.)
+#define DFTPAV_FMAC_BCAST3(K)                                                    \
+  "v_fmac_f64_dpp %0, %3, %6 row_newbcast:" #K " row_mask:0xf bank_mask:0xf\n\t" \
+  "v_fmac_f64_dpp %1, %4, %6 row_newbcast:" #K " row_mask:0xf bank_mask:0xf\n\t" \
+  "v_fmac_f64_dpp %2, %5, %6 row_newbcast:" #K " row_mask:0xf bank_mask:0xf\n\t"
+__device__ __forceinline__ void row_chain16x3(double &a0, double &a1, double &a2, double v0, double v1, double v2) {
+  const double one = 1.0;
+  asm volatile("s_nop 1\n\t" DFTPAV_FMAC_BCAST3(0) DFTPAV_FMAC_BCAST3(1) DFTPAV_FMAC_BCAST3(2) DFTPAV_FMAC_BCAST3(3) DFTPAV_FMAC_BCAST3(4)
+               DFTPAV_FMAC_BCAST3(5) DFTPAV_FMAC_BCAST3(6) DFTPAV_FMAC_BCAST3(7) DFTPAV_FMAC_BCAST3(8) DFTPAV_FMAC_BCAST3(9) DFTPAV_FMAC_BCAST3(10)
+               DFTPAV_FMAC_BCAST3(11) DFTPAV_FMAC_BCAST3(12) DFTPAV_FMAC_BCAST3(13) DFTPAV_FMAC_BCAST3(14) DFTPAV_FMAC_BCAST3(15)
+               : "+v"(a0), "+v"(a1), "+v"(a2)
+               : "v"(v0), "v"(v1), "v"(v2), "v"(one));
+}
+// how many of the row's sixteen values v are <= k (k the lane's own): sixteen compare-adds over row_newbcast, no LDS and no branch
+template <int... U> __device__ __forceinline__ int row_count_le_(int v, int k, std::integer_sequence<int, U...>) {
+  return (0 + ... + (__builtin_amdgcn_update_dpp(0, v, 0x150 + U, 0xf, 0xf, false) <= k ? 1 : 0));
+}
+__device__ __forceinline__ int row_count_le(int v, int k) { return row_count_le_(v, k, std::make_integer_sequence<int, 16>{}); }
 // acc + v[lane 0 of the row]
 __device__ __forceinline__ double row_add_lane0(double acc, double v) {
   const double one = 1.0;

@@ -44,6 +44,9 @@
 //     does), runs one for a slice of iterations and puts it back unfinished, so that all trajectories advance together
 //     and the launch ends without a tail of long solves on an empty device.
 #include <hip/hip_runtime.h>
+#include <map>
+#include <mutex>
+#include <utility>
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
@@ -1872,6 +1875,31 @@ hipError_t launch_solver_ref(const DevBatch &D, const DevBatch *d_dev, int mode,
   }
 }
 
+// Once per plan of a QUAD kind, on the plan's device (dftpav_batch_set_order, where the plan is committed to its batch): the dynamic
+// LDS limit of every instance launch_solver_quad may pick for it -- the instance follows help_eps and the corridor, which change
+// with an upload, so all of the plan's are prepared.  The limit belongs to the kernel, not to the plan: it is only ever raised, so
+// that a plan with the smaller LDS prepared later takes nothing from one prepared earlier.
+hipError_t prepare_solver_quad(const RefPlan &pl) {
+  if (pl.kind < kRefQuad) return hipSuccess;
+  static std::mutex mu;
+  static std::map<std::pair<int, const void *>, size_t> limit; // (device, instance) -> what it was last raised to
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  const QuadKernel fns[3] = {pl.kind == kRefQuad ? ref4_kernel_for(false, false) : ref4m_kernel_for(false, pl.tail1),
+                             pl.kind == kRefQuad ? ref4_kernel_for(pl.fast, false) : ref4m_kernel_for(pl.fast, pl.tail1),
+                             pl.kind == kRefQuad ? ref4_kernel_for(pl.fast, pl.fast) : ref4m_kernel_for(pl.fast, pl.tail1)};
+  std::lock_guard<std::mutex> lock(mu);
+  for (const QuadKernel fn : fns) {
+    size_t &have = limit[{dev, reinterpret_cast<const void *>(fn)}];
+    if (have >= pl.lds) continue;
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+    if (e != hipSuccess) return e;
+    have = pl.lds;
+  }
+  return hipSuccess;
+}
+
 // the QUAD kernels (solver_ref4.hip, solver_ref4m.hip); scheduled != 0: a solve whose rows pop from the batch's ring (the caller has
 // reset it).  alone: a scheduled solve of a batch that has the device to itself -- every wave slot, and once RefShape::hand
 // trajectories are unfinished its waves leave theirs to a launch in the WAVE shape queued behind, which pops them from the same ring
@@ -1894,10 +1922,9 @@ hipError_t launch_solver_quad(const DevBatch &D, const DevBatch *d_dev, int mode
   const bool fast = pl.fast && D.epis == 0.0; // the live path's constants (solver_ref4.hip: q4_eval)
   if (rect && !(fast && pl.kind == kRefQuad)) return hipErrorInvalidValue; // (the caller makes that copy for this instance only)
   const QuadKernel fn = pl.kind == kRefQuad ? ref4_kernel_for(fast, rect) : ref4m_kernel_for(fast, pl.tail1);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
-  if (e != hipSuccess) return e;
+  // (the instance's dynamic LDS limit: prepare_solver_quad, once per plan)
   hipLaunchKernelGGL(fn, dim3(grid), dim3(pl.threads), pl.lds, stream, d_dev, mode, tabs, cor_t, scratch, source, slice, hand);
-  e = hipGetLastError();
+  hipError_t e = hipGetLastError();
   if (e == hipSuccess && hand > 0) e = launch_solver_ref(D, d_dev, kModeSolve, tabs, scratch, pl, 1, stream);
   return e;
 }

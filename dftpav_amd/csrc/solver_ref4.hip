@@ -622,39 +622,54 @@ __device__ __forceinline__ double q4_eval(const DevBatch &D, const Q4 &q, const 
         }
       }
     } else if (slow) {
-      // some row of the wave overflowed its pool: piece by piece, a piece's pool entries in slot order, then its entries in global
-      // scratch in count order (they all arrived behind the pool's)
-      for (int p = 0; p < N; p++) {
-        const int src = (lane64 & 48) | p; // the lane of this row that owns piece p
-        const int c = __shfl(pc, src);
-        if (__builtin_amdgcn_ballot_w64(c != 0) == 0ull) continue; // (uniform: no row of this wave has a term in this piece)
-        const unsigned long long pm = ((unsigned long long)(unsigned)__shfl((int)(pmask >> 32), src) << 32) | (unsigned)__shfl((int)pmask, src);
-        for (unsigned long long mm = pm; mm;) {
-          ldscd_t e = q.pool + __builtin_ctzll(mm) * 3;
+      // some row of the wave overflowed its pool.  Piece p's terms stand in the chain as its pool entries in slot order, then its
+      // entries in global scratch in count order (they all arrived behind the pool's): positions start_p .. start_p + cnt_p - 1, the
+      // first a_p = popcount(pmask_p) of them in the pool.  The sixteen lanes of a row fetch sixteen consecutive positions at once
+      // and the row adds them in order by its DPP chain; the four rows run in step, as on the dense arm.
+      // The table, as on the dense arm: a row's pool slots in piece order, a piece's slots ascending.  A piece's first entry is not
+      // at its start in the chain here (pieces in front of it have entries in scratch) but at the count of the pool entries in
+      // front of it; a row's pool holds kQPool entries at most, and so does its table.
+      const int a = __builtin_popcountll(pmask);
+      int pin = a;
+      pin += __builtin_amdgcn_update_dpp(0, pin, 0x111, 0xf, 0xf, false);
+      pin += __builtin_amdgcn_update_dpp(0, pin, 0x112, 0xf, 0xf, false);
+      pin += __builtin_amdgcn_update_dpp(0, pin, 0x114, 0xf, 0xf, false);
+      pin += __builtin_amdgcn_update_dpp(0, pin, 0x118, 0xf, 0xf, false);
+      const int pstart = pin - a;
+      {
+        int at = pstart;
+        for (unsigned long long mm = pmask; mm;) {
+          q.perm[at++] = (unsigned char)__builtin_ctzll(mm);
           mm &= mm - 1;
-          gdT += e[0];
-          cost0 += e[1];
-          cost2 += e[2];
         }
-        const int pp0 = p == 0 ? 0 : (L.Kd + 1) + (p - 1) * (L.K + 1);
-        const gcd_t og = (gcd_t)(ovf + (size_t)pp0 * nterm * 3);
-        for (int i0 = __builtin_popcountll(pm); i0 < c; i0 += 8) { // eight terms' loads in flight, then their additions in order
-          double e[8][3];
-#pragma unroll
-          for (int u = 0; u < 8; u++) {
-            const int i = i0 + u < c ? i0 + u : c - 1;
-#pragma unroll
-            for (int w = 0; w < 3; w++) e[u][w] = og[(size_t)i * 3 + w];
-          }
-#pragma unroll
-          for (int u = 0; u < 8; u++) {
-            if (i0 + u < c) {
-              gdT += e[u][0];
-              cost0 += e[u][1];
-              cost2 += e[u][2];
-            }
-          }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+      const int start = incl - pc;        // (a lane beyond the last piece: the row's total, which no position reaches)
+      const int ap = a | (pstart << 8);   // (both kQPool at most)
+      for (int k0 = 0; k0 < kmax; k0 += 16) {
+        const int k = k0 + l; // this lane's position of the block
+        // its piece: the last one that starts at or in front of k (a piece without terms starts where the next one does)
+        const int p = row_count_le(start, k) - 1;
+        const int src = (lane64 & 48) | p; // the lane of this row that owns piece p
+        const int i = k - __shfl(start, src), apo = __shfl(ap, src);
+        const bool in = k < total, pooled = in && i < (apo & 255);
+        // the block's loads, all requested in front of its first addition; what lies beyond a row's total adds -0.0
+        double e0 = -0.0, e1 = -0.0, e2 = -0.0;
+        if (in && !pooled) {
+          const int pp0 = p == 0 ? 0 : (L.Kd + 1) + (p - 1) * (L.K + 1);
+          const gcd_t og = (gcd_t)(ovf + (size_t)pp0 * nterm * 3) + (size_t)i * 3;
+          e0 = og[0];
+          e1 = og[1];
+          e2 = og[2];
         }
+        // (every lane reads: one that has no pool entry reads the table's first byte and drops what it finds; & (kQPool - 1) keeps
+        // a byte of a table that was not written inside the pool)
+        ldscd_t pe = q.pool + ((int)q.perm[pooled ? (apo >> 8) + i : 0] & (kQPool - 1)) * 3;
+        const double p0 = pe[0], p1 = pe[1], p2 = pe[2];
+        e0 = pooled ? p0 : e0;
+        e1 = pooled ? p1 : e1;
+        e2 = pooled ? p2 : e2;
+        row_chain16x3(gdT, cost0, cost2, e0, e1, e2);
       }
     }
   }
