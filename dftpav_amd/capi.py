@@ -64,6 +64,8 @@ EXPORTS = [
     "dftpav_batch_check_conflicts", "dftpav_batch_sample_poses", "dftpav_batch_conflicts_last_ms",
     "dftpav_planner_set_conflict_filter", "dftpav_planner_set_own_slots", "dftpav_planner_last_conflicts",
     "dftpav_planner_set_joint_selection", "dftpav_planner_last_joint", "dftpav_joint_last_ms", "dftpav_debug_joint_select",
+    "dftpav_planner_check_yield", "dftpav_planner_set_conflict_trigger", "dftpav_planner_last_trigger", "dftpav_trigger_last_ms",
+    "dftpav_debug_conflict_trigger",
     "dftpav_grid_stamp_poses", "dftpav_planner_stamp_slots", "dftpav_grid_clear_stamps", "dftpav_grid_read_cells", "dftpav_stamp_last_ms",
     "dftpav_grid_render", "dftpav_grid_origin_centred", "dftpav_render_last_ms",
 ]
@@ -249,6 +251,32 @@ def conflict_args(t0, dt, K, margin=0.0, range=None):
     if not ok:
         raise DftpavError(E_INVALID, "conflicts: K in [1, %d], dt > 0, t0 finite, margin >= 0, range finite and >= margin" % CONFLICT_MAX_SAMPLES)
     return t0, dt, int(K), margin, range
+
+
+class _YieldOutC(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("yield", "yield_sample", "yield_partner")]
+
+
+class YieldOut:
+    """the caller-allocated arrays of dftpav_yield_out for `shape` rows: yield (1: the slot gives way), yield_sample / yield_partner
+    (the first sample at which it comes within the margin of a slot that precedes it, and that slot); -1: none"""
+    KEYS = ("yield", "yield_sample", "yield_partner")
+
+    def __init__(self, *shape):
+        self.a = {k: np.zeros(shape, dtype=np.int32) for k in self.KEYS}
+        self.c = _YieldOutC(*[self.a[k].ctypes.data for k in self.KEYS])
+
+    def arrays(self):
+        return self.a
+
+
+def yield_args(t_now, t0, dt, K, margin=0.0, range=None):
+    """the arguments of dftpav_planner_check_yield as the library takes them, (t_now, t0, dt, K, margin, range) with range = margin
+    when None; what the library would refuse raises DftpavError(E_INVALID) here, before any library call"""
+    t_now = float(t_now)
+    if not np.isfinite(t_now):
+        raise DftpavError(E_INVALID, "yield: t_now finite")
+    return (t_now,) + conflict_args(t0, dt, K, margin, range)
 
 
 def candidate_conflict_args(t_start, t0, dt, K, margin=0.0, range=None):
@@ -556,6 +584,15 @@ class Handle:
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         self._check(fn(self._h, C.byref(a), C.byref(b), C.byref(c)), "joint_last_ms")
         return float(a.value), float(b.value), float(c.value)
+
+    def trigger_last_ms(self):
+        """dftpav_trigger_last_ms: device ms of (the pose kernel, the pair and reduce kernels) of the last check_yield, tick with the
+        conflict trigger on or debug_conflict_trigger (which runs no pose kernel); 0.0 for what has not run"""
+        a, b = C.c_float(0.0), C.c_float(0.0)
+        fn = lib().dftpav_trigger_last_ms
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        self._check(fn(self._h, C.byref(a), C.byref(b)), "trigger_last_ms")
+        return float(a.value), float(b.value)
 
     def conflicts_last_ms(self):
         """dftpav_conflicts_last_ms: device ms of (the pose kernel, the pair and reduce kernels) of the last check_conflicts /
@@ -1061,6 +1098,35 @@ class Planner:
         self.handle._check(fn(self._p, t0, dt, K, self._ip(out)), "planner_sample_poses")
         return out
 
+    # ---- the conflict trigger: which of two executing plans that meet gives way
+    def check_yield(self, t_now, t0, dt, K, margin=0.0, range=None):
+        """dftpav_planner_check_yield at the clocks t0 + k dt, k < K, with the completion test at t_now: a row per slot ->
+        dict(yield, yield_sample, yield_partner [slots]); 0, -1, -1 for a slot that is empty or meets nobody that precedes it.
+        range None: margin"""
+        t_now, t0, dt, K, margin, range = yield_args(t_now, t0, dt, K, margin, range)
+        out = YieldOut(self.max_queries)
+        fn = lib().dftpav_planner_check_yield
+        fn.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_void_p]
+        self.handle._check(fn(self._p, t_now, t0, dt, K, margin, range, C.byref(out.c)), "planner_check_yield")
+        return out.arrays()
+
+    def set_conflict_trigger(self, margin=None, range=None, dt=0.1, K=50):
+        """dftpav_planner_set_conflict_trigger: tick() also replans the slot without precedence of two executing plans that come
+        within `margin` of one another at one of the K clocks t_now + budget + k dt; None (or a negative margin) switches the trigger
+        off (the default).  range None: margin.  Keep margin at or below the conflict filter's."""
+        fn = lib().dftpav_planner_set_conflict_trigger
+        fn.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int]
+        m = -1.0 if margin is None else float(margin)
+        self.handle._check(fn(self._p, m, m if range is None else float(range), float(dt), int(K)), "planner_set_conflict_trigger")
+
+    def last_trigger(self):
+        """dftpav_planner_last_trigger: the rows [slots] of the last tick(), if it ran with the conflict trigger on"""
+        out = YieldOut(self.max_queries)
+        fn = lib().dftpav_planner_last_trigger
+        fn.argtypes = [C.c_void_p, C.c_void_p]
+        self.handle._check(fn(self._p, C.byref(out.c)), "planner_last_trigger")
+        return out.arrays()
+
     # ---- candidate plans against the executing table: the conflict filter
     def set_conflict_filter(self, margin=None, range=None, dt=0.1, K=50):
         """dftpav_planner_set_conflict_filter: a restart that comes within `margin` of an executing plan at one of the K clocks
@@ -1159,6 +1225,23 @@ def debug_joint_select(handle, poses, cost, eligible, margin, range=None):
     handle._check(fn(handle._h, Q, R, K, ptr(ps), ptr(c), ptr(e), m, m if range is None else float(range), ptr(w), ptr(b), C.byref(out.c)),
                   "debug_joint_select")
     return dict(out.arrays(), winner=w, blocked=b)
+
+
+def debug_conflict_trigger(handle, poses, can_yield, margin, range=None):
+    """dftpav_debug_conflict_trigger: the pair and reduce kernels of the conflict trigger on poses [K][S][4] = cx, cy, cs, sn (a NaN row
+    at k = 0: an empty slot) and can_yield [S] -> dict(yield, yield_sample, yield_partner [S])"""
+    ps = np.ascontiguousarray(poses, dtype=np.float64)
+    cy = np.ascontiguousarray(can_yield, dtype=np.int32).reshape(-1)
+    if ps.ndim != 3 or ps.shape[2] != 4 or ps.shape[1] != cy.shape[0]:
+        raise DftpavError(E_INVALID, "debug_conflict_trigger: poses [K][S][4], can_yield [S]")
+    K, S = ps.shape[0], ps.shape[1]
+    out = YieldOut(S)
+    fn = lib().dftpav_debug_conflict_trigger
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p]
+    m = float(margin)
+    handle._check(fn(handle._h, S, K, ps.ctypes.data_as(C.c_void_p), cy.ctypes.data_as(C.c_void_p), m, m if range is None else float(range),
+                     C.byref(out.c)), "debug_conflict_trigger")
+    return out.arrays()
 
 
 def debug_plan_select(handle, cost, success, collision):

@@ -25,7 +25,8 @@
 //
 // Not claimed: candidates of one call are not tested against each other unless joint selection is on (joint_select.hip, §4.28); a
 // slot that replans in the same tick is tested as its old plan; between samples nothing is tested; one vehicle size; the moving
-// obstacles of dftpav_set_surround take no part; no trigger in dftpav_replan_tick.
+// obstacles of dftpav_set_surround take no part.  The filter only rejects: what starts a replanning when two executing plans meet is
+// the conflict trigger of dftpav_replan_tick (conflict_trigger.hip, §4.29).
 //
 // Two kernels.  cand_pair_kernel is conflict_pair_kernel's shape with the I side evaluated instead of loaded: one workgroup of 256
 // threads per 64 candidates, a lane a candidate, the four waves the samples k = wave, wave + 4, ...  Per sample a lane evaluates its

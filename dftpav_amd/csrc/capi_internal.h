@@ -34,6 +34,7 @@
 #include "clearance_args.h"
 #include "conflict_args.h"
 #include "cand_conflict_args.h"
+#include "conflict_trigger_args.h"
 #include "joint_args.h"
 #include "stamp_args.h"
 #include "render_args.h"
@@ -85,6 +86,9 @@ hipError_t launch_joint_poses(const JointPoseArgs &A, hipStream_t stream);
 hipError_t launch_joint_pairs(const JointPairArgs &A, hipStream_t stream);
 hipError_t launch_joint_greedy(const JointGreedyArgs &A, hipStream_t stream);
 hipError_t launch_joint_rows(const JointRowsArgs &A, hipStream_t stream);
+// conflict_trigger.hip: behind launch_conflict_poses, the pair-samples that make a slot yield per (I-tile, J-tile), the rows per slot
+hipError_t launch_trigger_pairs(const TriggerPairArgs &A, hipStream_t stream);
+hipError_t launch_trigger_reduce(const TriggerReduceArgs &A, hipStream_t stream);
 // stamp.hip: boxes into the working map, the bit map from the bytes again, the cells stamped since the base copy
 hipError_t launch_stamp_boxes(const StampBoxArgs &A, hipStream_t stream);
 hipError_t launch_stamp_bits(const StampBitsArgs &A, hipStream_t stream);
@@ -186,6 +190,9 @@ struct dftpav_handle {
   EventMarks<4> joint_ev; // joint_select.hip: in front of the pose kernels, behind them, behind the pair kernel, behind the greedy and row
                           // kernels; of the last dftpav_plan_queries call with joint selection or dftpav_debug_joint_select (marks 1 to 3)
   bool joint_posed = false; // that chain ran the pose kernels
+  EventMarks<3> trig_ev; // conflict_trigger.hip: in front of the pose kernel, between it and the pair kernel, behind the reduce kernel; of the
+                         // last dftpav_planner_check_yield, dftpav_replan_tick with the trigger on, or dftpav_debug_conflict_trigger
+  bool trig_posed = false; // that chain ran the pose kernel (the debug hook records marks 1 and 2)
   // the stamps (stamp.hip): nothing of it exists until a stamp call.  d_cells stays the working map every call reads
   unsigned char *d_cells_base = nullptr; // the map as uploaded: copied by the first stamp after a dftpav_set_grid_map, which drops it
   unsigned char *d_stamp_ws = nullptr;   // dftpav_planner_stamp_slots: the poses 4 x [K][S_pad], occupied [S_pad], select [S_pad];
@@ -484,6 +491,25 @@ struct JointSelect {
   void release() { if (d) (void)hipFree(d); }
 };
 
+// The conflict trigger of the tick (conflict_trigger.hip): which executing plans meet at the adoption clock, and which of the two
+// slots gives way.  One allocation, made by configure: the table's poses 4 x [cap_K][S_pad], occupied [S_pad], the partial rows
+// sample | partner, each [tiles][S_pad], and the rows yield | sample | partner, each [max_queries].  A tick allocates nothing.
+struct ConflictTrigger {
+  bool on = false, last = false; // last: the last tick ran with it, and d_rows holds that tick's rows
+  double margin = -1.0, range = 0.0, dt = 0.0;
+  int K = 0;
+  unsigned char *d = nullptr;
+  int cap_K = 0; // the K the allocation was made for
+  double *d_pose = nullptr;
+  unsigned char *d_occupied = nullptr;
+  int *d_part = nullptr, *d_rows = nullptr;
+  std::vector<int> h_yield; // the tick's copy of yield [max_queries] (the planner's: a failing call leaves nothing the stream still writes)
+  int configure(struct dftpav_planner *p, double margin_, double range_, double dt_, int K_);
+  int run(struct dftpav_planner *p, double t_now, double t0); // poses at t0 + k dt, pairs, rows: enqueued, nothing waits
+  int fetch(struct dftpav_planner *p, const dftpav_yield_out *out);
+  void release() { if (d) (void)hipFree(d); }
+};
+
 struct dftpav_planner {
   dftpav_handle *h = nullptr;
   int max_queries = 0, R = 0;
@@ -552,6 +578,7 @@ struct dftpav_planner {
   ClearanceFilter clr;
   ConflictFilter cnf;
   JointSelect jnt; // dftpav_planner_set_joint_selection
+  ConflictTrigger trg; // dftpav_planner_set_conflict_trigger
   std::vector<int> own_next; // dftpav_planner_set_own_slots: the own slots [Q] of the next dftpav_plan_queries call, which consumes them
 };
 

@@ -90,6 +90,7 @@ extern "C" void dftpav_planner_destroy(dftpav_planner *p) {
   p->clr.release();
   p->cnf.release();
   p->jnt.release();
+  p->trg.release();
   delete p; // (its EventMarks' events with it)
 }
 
@@ -1046,6 +1047,9 @@ extern "C" int dftpav_replan_tick(dftpav_planner *p, const dftpav_plan_params *p
   dftpav_handle *h = p->h;
   // the padding of the plans to come must be the table's: checked before anything runs
   if (p->d_exec && (p->T.max_seg != pp->max_seg || p->T.max_pieces != pp->max_pieces)) return DFTPAV_E_INVALID;
+  const bool trigger = p->trg.on;
+  if (trigger && !std::isfinite(t_now + budget)) return DFTPAV_E_INVALID; // the trigger's first clock is the adoption clock
+  p->trg.last = false;
   if (!p->d_exec) { // an all-empty table is a valid start (every vehicle waits for its first plan)
     if (int rc = exec_table(p, pp->max_seg, pp->max_pieces)) return rc;
   }
@@ -1053,6 +1057,9 @@ extern "C" int dftpav_replan_tick(dftpav_planner *p, const dftpav_plan_params *p
   HIPCHK(h, hipSetDevice(h->device));
   HIPCHK(h, p->tick_ev.record(0, h->stream));
   if (int rc = replan_check_enqueue(p, t_now, budget, end_states, ego_states, pp->check_dt, pp->vertex_res)) return rc;
+  // ---- the conflict trigger, behind the check on the same stream: the table's poses from the adoption clock on, then who yields
+  if (trigger)
+    if (int rc = p->trg.run(p, t_now, t_now + budget)) return rc;
   // ---- the tick's one extra wait: replan, start_state, start_ctrl (with whatever else of the check the caller asked for)
   const size_t S = (size_t)p->max_queries;
   std::vector<int> &flag = p->h_rc_flag; // (the planner's: a failing fetch below returns with these copies enqueued)
@@ -1064,12 +1071,20 @@ extern "C" int dftpav_replan_tick(dftpav_planner *p, const dftpav_plan_params *p
   HIPCHK(h, hipMemcpyAsync(st.data(), p->d_rc_st, sizeof(double) * 4 * S, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipMemcpyAsync(ct.data(), p->d_rc_ct, sizeof(double) * 2 * S, hipMemcpyDeviceToHost, h->stream));
   if (int rc = replan_check_fetch(p, check_out)) return rc;
+  if (trigger) { // yield joins the read-back in front of the one wait
+    p->trg.h_yield.assign(S, 0);
+    HIPCHK(h, hipMemcpyAsync(p->trg.h_yield.data(), p->trg.d_rows, sizeof(int) * S, hipMemcpyDeviceToHost, h->stream));
+  }
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  // ---- the flagged slots, in rising slot order, are the queries
+  if (trigger) {
+    h->trig_ev.complete();
+    p->trg.last = true;
+  }
+  // ---- the flagged slots (the check's flag, or the trigger's yield), in rising slot order, are the queries
   std::vector<int> slot_of;
   std::vector<double> qs, qc, qe;
   for (size_t s = 0; s < S; s++) {
-    if (!flag[s]) continue;
+    if (!flag[s] && !(trigger && p->trg.h_yield[s])) continue;
     slot_of.push_back((int)s);
     qs.insert(qs.end(), st.begin() + 4 * s, st.begin() + 4 * s + 4);
     qc.insert(qc.end(), ct.begin() + 2 * s, ct.begin() + 2 * s + 2);
@@ -1985,6 +2000,185 @@ extern "C" int dftpav_debug_joint_select(dftpav_handle *h, int Q, int R, int K, 
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->joint_ev.complete();
+  return DFTPAV_OK;
+}
+
+// ------------------------------------------------- the conflict trigger: who yields to whom (conflict_trigger.hip)
+static bool trigger_args_ok(double t_now, double t0, double dt, int K, double margin, double range) {
+  if (!conflict_clocks_ok(t0, dt, K) || !std::isfinite(t_now)) return false;
+  return margin >= 0.0 && std::isfinite(range) && !(range < margin); // (a NaN margin; +inf fails range < margin)
+}
+// the pair and reduce kernels behind the poses on the handle's stream, up to mark 2 of trig_ev (nothing waits).  d_part: sample |
+// partner, each [tiles][S_pad]; d_rows: yield | sample | partner, each [n_slots]
+static int trigger_stages(dftpav_handle *h, const ConflictPoses &P, const TriggerYield &Y, int n_slots, double margin, double range,
+                          int *d_part, int *d_rows) {
+  const size_t tiles = (size_t)P.S_pad / kConflictTile, rows = tiles * P.S_pad;
+  CandPairArgs V{}; // the vehicle and the two distances, as every pair launch forms them
+  cand_pair_consts(h, margin, range, V);
+  TriggerPairArgs A{};
+  A.P = P;
+  A.Y = Y;
+  A.part = TriggerRows{d_part, d_part + rows};
+  A.half_l = V.half_l, A.half_w = V.half_w, A.margin = V.margin, A.reach2 = V.reach2;
+  TriggerReduceArgs Rd{};
+  Rd.part = A.part;
+  Rd.yield = d_rows;
+  Rd.out = TriggerRows{d_rows + n_slots, d_rows + 2 * (size_t)n_slots};
+  Rd.Y = Y;
+  Rd.occupied = P.occupied;
+  Rd.n_slots = n_slots;
+  Rd.S_pad = P.S_pad;
+  Rd.tiles = (int)tiles;
+  HIPCHK(h, launch_trigger_pairs(A, h->stream));
+  HIPCHK(h, launch_trigger_reduce(Rd, h->stream));
+  HIPCHK(h, h->trig_ev.record(2, h->stream));
+  return DFTPAV_OK;
+}
+static int fetch_yield(dftpav_handle *h, const dftpav_yield_out *out, const int *d_rows, size_t S) {
+  if (!out) return DFTPAV_OK;
+  HIPCHK(h, fetch_async(h, out->yield, d_rows, sizeof(int) * S));
+  HIPCHK(h, fetch_async(h, out->yield_sample, d_rows + S, sizeof(int) * S));
+  HIPCHK(h, fetch_async(h, out->yield_partner, d_rows + 2 * S, sizeof(int) * S));
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_planner_check_yield(dftpav_planner *p, double t_now, double t0, double dt, int K, double margin, double range,
+                                          const dftpav_yield_out *out) {
+  if (!p || !out || !trigger_args_ok(t_now, t0, dt, K, margin, range)) return DFTPAV_E_INVALID;
+  dftpav_handle *h = p->h;
+  const size_t S = (size_t)p->max_queries;
+  if (!p->d_exec) { // nothing was ever installed: every slot is empty
+    if (out->yield) std::fill(out->yield, out->yield + S, 0);
+    for (int *row : {out->yield_sample, out->yield_partner})
+      if (row) std::fill(row, row + S, -1);
+    return DFTPAV_OK;
+  }
+  HIPCHK(h, hipSetDevice(h->device));
+  DevScratch tmp(h);
+  ConflictPoses P{};
+  if (int rc = conflict_poses_on_stream(p, tmp, h->trig_ev, t0, dt, K, P)) return rc;
+  h->trig_posed = true;
+  int *d_part = nullptr, *d_rows = nullptr;
+  HIPCHK(h, tmp.alloc(d_part, 2 * ((size_t)P.S_pad / kConflictTile) * P.S_pad));
+  HIPCHK(h, tmp.alloc(d_rows, 3 * S));
+  if (int rc = trigger_stages(h, P, TriggerYield{p->T, t_now, nullptr}, p->max_queries, margin, range, d_part, d_rows)) return rc;
+  if (int rc = fetch_yield(h, out, d_rows, S)) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->trig_ev.complete();
+  return DFTPAV_OK;
+}
+
+int ConflictTrigger::configure(dftpav_planner *p, double margin_, double range_, double dt_, int K_) {
+  dftpav_handle *h = p->h;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (!d || cap_K < K_) { // the poses are sized by K: a larger K takes a new allocation
+    const size_t S_pad = (size_t)conflict_s_pad(p), tiles = S_pad / kConflictTile;
+    double *pose = nullptr;
+    unsigned char *occ = nullptr;
+    int *part = nullptr, *rows = nullptr;
+    auto fields = [&](auto &take) {
+      pose = (double *)take(sizeof(double) * 4 * (size_t)K_ * S_pad);
+      part = (int *)take(sizeof(int) * 2 * tiles * S_pad);
+      rows = (int *)take(sizeof(int) * 3 * (size_t)p->max_queries);
+      occ = (unsigned char *)take(S_pad);
+    };
+    unsigned char *fresh = nullptr;
+    HIPCHK(h, hipMalloc(&fresh, carve(nullptr, fields)));
+    if (d) { // (nothing of the old one is in flight behind this wait)
+      (void)hipStreamSynchronize(h->stream);
+      (void)hipFree(d);
+    }
+    carve(fresh, fields);
+    d = fresh;
+    d_pose = pose, d_part = part, d_rows = rows, d_occupied = occ;
+    cap_K = K_;
+    last = false; // the rows of the last tick went with the old allocation
+  }
+  margin = margin_, range = range_, dt = dt_, K = K_;
+  on = true;
+  return DFTPAV_OK;
+}
+int ConflictTrigger::run(dftpav_planner *p, double t_now, double t0) {
+  dftpav_handle *h = p->h;
+  ConflictPoses P{};
+  if (int rc = conflict_poses_into(p, d_pose, d_occupied, &h->trig_ev, t0, dt, K, P)) return rc;
+  h->trig_posed = true;
+  return trigger_stages(h, P, TriggerYield{p->T, t_now, nullptr}, p->max_queries, margin, range, d_part, d_rows);
+}
+int ConflictTrigger::fetch(dftpav_planner *p, const dftpav_yield_out *out) { return fetch_yield(p->h, out, d_rows, (size_t)p->max_queries); }
+
+extern "C" int dftpav_planner_set_conflict_trigger(dftpav_planner *p, double margin, double range, double dt, int K) {
+  if (!p || margin != margin) return DFTPAV_E_INVALID;
+  if (margin < 0.0) { // off: the buffers stay, nothing reads them
+    p->trg.on = false;
+    return DFTPAV_OK;
+  }
+  if (!conflict_clocks_ok(0.0, dt, K) || !std::isfinite(range) || range < margin) return DFTPAV_E_INVALID;
+  return p->trg.configure(p, margin, range, dt, K); // (a failed allocation leaves the trigger as it was)
+}
+
+extern "C" int dftpav_planner_last_trigger(dftpav_planner *p, const dftpav_yield_out *out) {
+  if (!p || !out || !p->trg.last) return DFTPAV_E_INVALID;
+  dftpav_handle *h = p->h;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (int rc = p->trg.fetch(p, out)) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_trigger_last_ms(dftpav_handle *h, float *pose_ms, float *pair_ms) {
+  if (!h) return DFTPAV_E_INVALID;
+  if (pose_ms) *pose_ms = 0.0f;
+  if (pair_ms) *pair_ms = 0.0f;
+  if (!h->trig_ev.reached(2)) return DFTPAV_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  if (pose_ms && h->trig_posed) HIPCHK(h, h->trig_ev.elapsed(pose_ms, 0, 1, false)); // (every chain waited for the stream)
+  if (pair_ms) HIPCHK(h, h->trig_ev.elapsed(pair_ms, 1, 2, false));
+  return DFTPAV_OK;
+}
+
+extern "C" int dftpav_debug_conflict_trigger(dftpav_handle *h, int S, int K, const double *poses, const int *can_yield, double margin,
+                                             double range, const dftpav_yield_out *out) {
+  if (!h || !poses || !can_yield || S < 1 || !conflict_clocks_ok(0.0, 1.0, K)) return DFTPAV_E_INVALID;
+  if (!(margin >= 0.0) || !std::isfinite(range) || range < margin) return DFTPAV_E_INVALID; // (a NaN margin; +inf fails range < margin)
+  const size_t S_pad = ((size_t)S + kConflictTile - 1) / kConflictTile * kConflictTile, n = (size_t)K * S_pad;
+  if (n > ((size_t)1 << 26)) return DFTPAV_E_UNSUPPORTED; // 2 GiB of poses
+  HIPCHK(h, hipSetDevice(h->device));
+  // cx | cy | cs | sn, each [K][S_pad], NaN behind the last slot; occupied | can_yield, each [S_pad]; declared in front of tmp, whose
+  // end waits for the stream
+  std::vector<double> soa(4 * n, std::nan(""));
+  std::vector<unsigned char> bytes(2 * S_pad, 0);
+  auto finite4 = [](const double *ps) { return std::isfinite(ps[0]) && std::isfinite(ps[1]) && std::isfinite(ps[2]) && std::isfinite(ps[3]); };
+  for (size_t s = 0; s < (size_t)S; s++) {
+    bytes[s] = finite4(poses + s * 4) ? 1 : 0; // the row at k = 0 decides whether the slot holds a plan
+    bytes[S_pad + s] = bytes[s] && can_yield[s] != 0 ? 1 : 0;
+  }
+  for (size_t k = 0; k < (size_t)K; k++)
+    for (size_t s = 0; s < (size_t)S; s++) {
+      const double *ps = poses + (k * (size_t)S + s) * 4; // a pose with a component that is not finite takes no part: NaN throughout
+      if (!bytes[s] || !finite4(ps)) continue;
+      for (size_t f = 0; f < 4; f++) soa[f * n + k * S_pad + s] = ps[f];
+    }
+  DevScratch tmp(h);
+  double *d_pose = nullptr;
+  unsigned char *d_bytes = nullptr;
+  int *d_part = nullptr, *d_rows = nullptr;
+  HIPCHK(h, tmp.alloc(d_pose, 4 * n));
+  HIPCHK(h, tmp.alloc(d_bytes, 2 * S_pad));
+  HIPCHK(h, tmp.alloc(d_part, 2 * (S_pad / kConflictTile) * S_pad));
+  HIPCHK(h, tmp.alloc(d_rows, 3 * (size_t)S));
+  HIPCHK(h, hipMemcpyAsync(d_pose, soa.data(), sizeof(double) * 4 * n, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_bytes, bytes.data(), 2 * S_pad, hipMemcpyHostToDevice, h->stream));
+  const ConflictPoses P{d_pose, d_pose + n, d_pose + 2 * n, d_pose + 3 * n, d_bytes, K, (int)S_pad};
+  TriggerYield Y{};
+  Y.flags = d_bytes + S_pad;
+  h->trig_ev.reset();
+  h->trig_posed = false;
+  HIPCHK(h, h->trig_ev.record(1, h->stream));
+  if (int rc = trigger_stages(h, P, Y, S, margin, range, d_part, d_rows)) return rc;
+  if (int rc = fetch_yield(h, out, d_rows, (size_t)S)) return rc;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->trig_ev.complete();
   return DFTPAV_OK;
 }
 

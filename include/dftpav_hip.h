@@ -832,7 +832,11 @@ int dftpav_replan_check(dftpav_planner *p, double t_now, double budget, const do
  * (next_traj_ stays null).  plan_out is indexed by query, as in a plain call.  check_out, query_slot, n_queries and plan_out
  * may be NULL.  With ego_states given, end_states must be given too (an empty slot has no stored goal).
  * Restarts stay keyed by (seed, query index in the call, restart): the restarts of a slot therefore depend on which other
- * slots replan in the same tick (restart 0, the searched hypothesis itself, does not). */
+ * slots replan in the same tick (restart 0, the searched hypothesis itself, does not).
+ * With the conflict trigger on (dftpav_planner_set_conflict_trigger, below; off by default) a slot is also a query when the
+ * trigger says it yields to another slot's executing plan: its kernels run behind the check, their yield row joins the one
+ * read-back, and the replan row of check_out stays the check's own flag.  With the trigger on the call also refuses
+ * (DFTPAV_E_INVALID, nothing changed) a t_now + budget that is not finite: it is the trigger's first clock. */
 int dftpav_replan_tick(dftpav_planner *p, const dftpav_plan_params *pp, double t_now, double budget, const double *end_states,
                        const double *ego_states, const dftpav_replan_out *check_out, int *query_slot, int *n_queries,
                        const dftpav_plan_out *plan_out);
@@ -1144,7 +1148,8 @@ int dftpav_rs_table_last_ms(dftpav_handle *h, float *ms, int *n_builds /* or NUL
 /* ---- footprint conflicts between the executing plans, slot against slot ------------------------------------------------
  * Every other check of the executing table looks at one slot at a time.  This one relates two: do the vehicles of two slots come
  * within `margin` of one another at the same clock, when first, and who with.  A read-out beside limits and clearance (conflict.hip);
- * nothing of it feeds the solve or the tick.  No grid map is needed.
+ * nothing of it feeds the solve.  What the tick does about two plans that meet is the conflict trigger's (below).  No grid map is
+ * needed.
  *
  * The clocks.  t_k = t0 + (double)k * dt, k = 0 .. K - 1: absolute, on the clock of the table's start_time / end_time.
  *
@@ -1252,8 +1257,9 @@ int dftpav_conflicts_last_ms(dftpav_handle *h, float *pose_ms, float *pair_ms);
  *
  * Not claimed.  Candidates of the same call are not tested against each other unless joint selection is on (below).  A slot that
  * replans in the same tick is tested as its old plan.  Between samples nothing is tested.  There is one vehicle size.  The moving
- * obstacles of dftpav_set_surround take no part.  There is no trigger in dftpav_replan_tick: a caller who wants a slot to yield
- * calls dftpav_replan_check for its start state, then dftpav_plan_queries and dftpav_planner_adopt. */
+ * obstacles of dftpav_set_surround take no part.  What starts a replanning when two executing plans meet is the conflict trigger of
+ * dftpav_replan_tick (below): the filter only rejects, and the search and the corridor of the slot that yields do not see the other
+ * vehicle. */
 int dftpav_batch_check_conflicts(dftpav_batch *b, dftpav_planner *p, double t_start, double t0, double dt, int K, double margin,
                                  double range, const int *own /*[B] or NULL = none*/, const dftpav_conflict_out *out /*rows [B]*/);
 int dftpav_batch_sample_poses(dftpav_batch *b, double t_start, double t0, double dt, int K, double *poses /*[K][B][4]*/);
@@ -1324,6 +1330,75 @@ int dftpav_joint_last_ms(dftpav_handle *h, float *pose_ms, float *pair_ms, float
 int dftpav_debug_joint_select(dftpav_handle *h, int Q, int R, int K, const double *poses /*[K][Q*R][4]*/, const double *cost /*[Q*R]*/,
                               const int *eligible /*[Q*R]*/, double margin, double range, int *winner /*[Q]*/, int *blocked /*[Q*R]*/,
                               const dftpav_conflict_out *out /*rows [Q*R]*/);
+
+/* ---- the conflict trigger: two executing plans that meet, and the slot without precedence replans ------------------------
+ * The conflict check relates two executing plans, the conflict filter keeps a new plan away from those that execute, joint selection
+ * keeps the new plans of one call apart.  None of them starts anything: dftpav_replan_tick flags a slot for the near / target rule,
+ * a collision with the map, or an empty slot with an ego state.  With the trigger on the tick itself finds the pairs of executing
+ * plans that conflict at the adoption clock, decides by a fixed precedence which slot gives way, and replans that slot in the same
+ * call (conflict_trigger.hip).  Off, which is the default, nothing changes.
+ *
+ * Everything not named here is the definition of the conflict check above, in the same expressions: the clocks
+ * t_k = t0 + (double)k * dt, k < K <= DFTPAV_CONFLICT_MAX_SAMPLES; the pose of an occupied slot, held still outside its plan; steps 1 to
+ * 3 of the separation (the broad phase on the centres against range + 2.0 * rad, the separating-axis test, the 32 corner-to-edge
+ * distances); a pair outside the broad phase, or with a pose that is not finite, contributes nothing.
+ *
+ *   can_yield(s)     the slot holds a plan and !(t_now > end_time[n_seg - 1]): the completion test of dftpav_replan_check
+ *                    (traj_server_ros.cpp:150), read from the table's row.  A completed slot stands where its plan ended and the tick
+ *                    plans nothing for it.  It cannot give way, so whoever meets it must.
+ *   precedes(j, i)   for occupied i != j: !can_yield(j) || j < i.  A lower slot index is a higher priority: the order of the tick's
+ *                    query list, and therefore the priority joint selection uses.
+ *   per occupied i   yield_sample, yield_partner: the lexicographic minimum of (k, j) over the pair-samples with
+ *                    sep(i, j, k) <= margin and precedes(j, i); -1, -1 when there is none.
+ *                    yield = can_yield(i) && yield_sample >= 0.
+ *   Empty slots, and every slot before the table was filled once, give 0, -1, -1.
+ * The rows are existential and lexicographic, so no order of reduction shows; every output is an integer.  With every slot able to
+ * yield, slot 0 never yields and the highest slot of a conflicting set always does.  When every conflicting partner of a slot
+ * precedes it, its (yield_sample, yield_partner) are the (conflict_sample, conflict_partner) of dftpav_planner_check_conflicts at the
+ * same arguments.
+ *
+ * dftpav_planner_check_yield(p, t_now, t0, dt, K, margin, range, out): a read-out: the three rows [max_queries]; any pointer of out
+ *   may be NULL.  Nothing of the table, of the publisher's state or of the check's buffers is written.  No grid map is needed.
+ * dftpav_planner_set_conflict_trigger(p, margin, range, dt, K): margin < 0 is off (the default).  The trigger makes its one
+ *   allocation here (the table's poses 4 x [K][slots rounded up to 64], the partial rows, the rows); a tick allocates nothing.  The
+ *   parameters are the trigger's own, not the filter's: a trigger margin ABOVE the filter's margin makes a plan that has just passed
+ *   the filter trigger again on the next tick, so keep the trigger's margin at or below the filter's.
+ * In dftpav_replan_tick, with the trigger on: behind the check and on the same stream the poses of the table are taken at
+ *   t0 = t_now + budget -- the adoption clock and the clock of the filter's candidates; nothing before it can still be changed -- and
+ *   the trigger's kernels follow with the tick's t_now.  yield [slots] joins the tick's read-back in front of its one wait; no second
+ *   wait is added.  A slot becomes a query when replan || yield, in rising slot order.  A yielding slot has a start state (the check
+ *   writes start_state and start_ctrl for every occupied, uncompleted slot whether or not it flagged it); its goal is end_states' row,
+ *   or the stored one.  The replan row of check_out stays the check's own flag: the caller tells a yield from query_slot and
+ *   dftpav_planner_last_trigger.  Own slots, planning, adoption, history and "a failed replanning keeps the old plan" are the
+ *   tick's, unchanged.  With the trigger off the tick enqueues, copies and returns exactly what it did without this section.
+ * dftpav_planner_last_trigger(p, out): the rows of the last dftpav_replan_tick, if it ran with the trigger; otherwise
+ *   DFTPAV_E_INVALID.
+ * dftpav_trigger_last_ms(h, pose_ms, pair_ms): device time in ms (the handle's HIP events) of the pose kernel and of the pair and
+ *   reduce kernels together, of the last read-out, tick with the trigger, or dftpav_debug_conflict_trigger (which runs no pose kernel:
+ *   0.0); 0.0 for what has not run.  Either pointer may be NULL.
+ * dftpav_debug_conflict_trigger (test hook): the pair and reduce kernels on caller-given poses [K][S][4] = cx, cy, cs, sn and
+ *   can_yield [S] (0 / not 0), with the handle's vehicle size; no pose kernel, no planner.  A slot whose row at k = 0 has a component
+ *   that is not finite is an empty slot (it cannot yield, whatever its flag); a later row of an occupied slot that is not finite
+ *   contributes nothing.  out and every pointer of it may be NULL.
+ * DFTPAV_E_INVALID, and nothing changed, decided before the handle is touched: p, h, out, poses or can_yield NULL; S < 1; K < 1 or
+ * K > DFTPAV_CONFLICT_MAX_SAMPLES; dt <= 0 or not finite; t0 or t_now not finite; margin < 0 or NaN (dftpav_planner_set_conflict_trigger:
+ * NaN; < 0 is off); range < margin or not finite.
+ *
+ * Not claimed.  Between samples nothing is tested.  There is one vehicle size.  The moving obstacles of dftpav_set_surround take no
+ * part.  Precedence is by slot index only.  The search and the corridor of the slot that yields do not see the other vehicle: only
+ * the conflict filter rejects, so a yielder may end DFTPAV_PLAN_NO_VALID_RESTART every tick and keep its plan (with the filter off
+ * it may adopt a plan that conflicts again).  dftpav_planner_stamp_slots (below) remains the way to make parked vehicles visible to
+ * the search. */
+typedef struct dftpav_yield_out {
+  int *yield, *yield_sample, *yield_partner; /* [max_queries] */
+} dftpav_yield_out; /* any may be NULL */
+int dftpav_planner_check_yield(dftpav_planner *p, double t_now, double t0, double dt, int K, double margin, double range,
+                               const dftpav_yield_out *out);
+int dftpav_planner_set_conflict_trigger(dftpav_planner *p, double margin, double range, double dt, int K); /* margin < 0: off (default) */
+int dftpav_planner_last_trigger(dftpav_planner *p, const dftpav_yield_out *out);
+int dftpav_trigger_last_ms(dftpav_handle *h, float *pose_ms, float *pair_ms);
+int dftpav_debug_conflict_trigger(dftpav_handle *h, int S, int K, const double *poses /*[K][S][4]*/, const int *can_yield /*[S]*/,
+                                  double margin, double range, const dftpav_yield_out *out /*rows [S]*/);
 
 /* ---- the stamps: vehicle footprints written into the grid map on the device -------------------------------------------
  * Every stage that plans or checks a plan (search, goal field, rectangle corridor, collision re-check, replan check, distance
