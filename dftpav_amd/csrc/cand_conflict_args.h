@@ -34,9 +34,9 @@ struct CandPairArgs {
   int R;
   const int *own; // nullptr: none; else the own slot (-1: none) of row c (no members) or of query members[c / R]
   int *reject;    // [B] or nullptr (the read-out); the filter: set to 1 where conflict_sample >= 0, never read or cleared
-  double half_l, half_w; // 0.5 * veh_length, 0.5 * veh_width
-  double margin;
-  double reach2; // R * R of the broad phase
+  PairConsts V;
 };
+static_assert(offsetof(CandPairArgs, V) == offsetof(CandPairArgs, reject) + 8 && sizeof(CandPairArgs) == offsetof(CandPairArgs, V) + 32,
+              "the four doubles lie where they lay");
 
 } // namespace dftpav

@@ -2,7 +2,10 @@
 // objects behind the C-ABI's opaque pointers, the kernels' launch functions, and the helpers that more than one unit calls.
 //   capi.cpp          parameters, handle, moving obstacles, batch create / upload / order / solve / results / trace
 //   capi_steps.cpp    the steps around a solve: restarts, resampling, shots, search, map, corridor, re-check, read-out, plan cycle
-//   capi_planner.cpp  dftpav_plan_queries, the executing table, the replan check / tick, the publisher
+//   capi_planner.cpp  dftpav_plan_queries, the executing table, the replan check / tick, the publisher, the limit / penalty / clearance
+//                     filters, the stamps of the executing plans
+//   capi_conflicts.cpp  the footprint conflicts: between executing plans, of candidates against them (the conflict filter), joint
+//                     selection, the conflict trigger
 //   capi_comm.cpp     RCCL                capi_wire.cpp     the "DPTJ" serialisation
 // There is deliberately no CPU fallback: without a usable HIP device every entry point that needs one fails with DFTPAV_E_NO_DEVICE.
 // Device times are taken with EventMarks<N> (below) alone: the events exist from their first record on, complete(k) is the one flag a
@@ -383,7 +386,13 @@ inline void limit_rows(LimitsCommon &C, double *d_max, int *d_int, size_t n) {
   C.feasible = d_int + 2 * kLimQ * n;
 }
 
-// The selection filters of dftpav_plan_queries: four structs of one shape (capi_planner.cpp).  Each holds its switch (`on`, and
+// five rows [n] wired from their two bases: min_sep at d_sep; sep_sample | sep_partner | conflict_sample | conflict_partner from d_int on
+inline ConflictRows conflict_rows(double *d_sep, int *d_int, size_t n) {
+  return ConflictRows{d_sep, d_int, d_int + n, d_int + 2 * n, d_int + 3 * n};
+}
+
+// The selection filters of dftpav_plan_queries: four structs of one shape (capi_planner.cpp; the conflict filter, joint selection and
+// the trigger behind it: capi_conflicts.cpp).  Each holds its switch (`on`, and
 // `last`: the last dftpav_plan_queries call ran with it), its parameters and its one allocation `d` -- the sample table at its head
 // where the filter has one, then the rows [cap = max_queries * R] of a call -- and states the same operations once:
 //   configure  the set_*_filter entry behind its argument checks: allocates on first use, switches on; a refusal changes nothing
@@ -454,7 +463,7 @@ struct ConflictFilter {
   ConflictPoses P{};         // the table's poses of the running call
   double t_call = 0.0;       // its t_now
   bool have_table = false;   // it found an occupied slot
-  ConflictRows rows() const { return ConflictRows{d_sep, d_int, d_int + cap, d_int + 2 * cap, d_int + 3 * cap}; }
+  ConflictRows rows() const { return conflict_rows(d_sep, d_int, cap); }
   int configure(struct dftpav_planner *p, double margin_, double range_, double dt_, int K_);
   int clear(struct dftpav_planner *p, size_t n_rows, double t_now, const std::vector<int> &own);
   int run(dftpav_handle *h, dftpav_batch *b, const int *members, int nm, int R, int *reject);
@@ -477,7 +486,7 @@ struct JointSelect {
   int *d_int = nullptr; // sep_sample | sep_partner | conflict_sample | conflict_partner, each [cap]
   std::vector<double> h_inf; // +inf, the rows' min_sep before a call's kernels run
   JointPoses P{};            // the poses of the running call
-  ConflictRows rows() const { return ConflictRows{d_sep, d_int, d_int + cap, d_int + 2 * cap, d_int + 3 * cap}; }
+  ConflictRows rows() const { return conflict_rows(d_sep, d_int, cap); }
   JointCands cands() const { return JointCands{d_cost, d_elig, d_flag}; }
   static bool fits(size_t candidates, int K) {
     return candidates <= (size_t)DFTPAV_JOINT_MAX_CANDIDATES && candidates * (size_t)(K > 0 ? K : 1) <= ((size_t)1 << 22);
@@ -649,6 +658,16 @@ int search_heuristic_plan(dftpav_handle *h, const double *start_states, const do
 int rs_geometry(const dftpav_rs_heuristic_params &gp, RsGeometry &g, size_t &entries);
 int ensure_rs_table(dftpav_handle *h, double rho, const dftpav_rs_heuristic_params &gp, RsGeometry &g);
 int search_rs_plan(dftpav_handle *h, SearchSetup &U);
+// ---- capi_conflicts.cpp (hidden: the split adds nothing to the library's dynamic symbols)
+#define DFTPAV_HIDDEN __attribute__((visibility("hidden")))
+// the K clocks t0 + k dt of a conflict call: 1 <= K <= DFTPAV_CONFLICT_MAX_SAMPLES, dt > 0 and finite, t0 finite
+DFTPAV_HIDDEN bool conflict_clocks_ok(double t0, double dt, int K);
+// the planner's slots rounded up to whole tiles of kConflictTile
+DFTPAV_HIDDEN int conflict_s_pad(const dftpav_planner *p);
+// the poses of every slot at the K clocks into d_pose (4 x [K][S_pad]) and d_occupied [S_pad], wired into P, on the handle's stream
+// between marks 0 and 1 of `ev` (nullptr: no marks; nothing waits)
+DFTPAV_HIDDEN int conflict_poses_into(dftpav_planner *p, double *d_pose, unsigned char *d_occupied, EventMarks<3> *ev, double t0, double dt,
+                                      int K, ConflictPoses &P);
 
 // One allocation for many arrays, measured and carved by the same list: fields(take) names every array in order, take(bytes) is its
 // address -- null while `base` is null, the measuring pass -- and advances by the size rounded up to 256 bytes.  Returns the bytes used.
@@ -661,6 +680,21 @@ template <class F> size_t carve(unsigned char *base, F &&fields) {
   };
   fields(take);
   return used;
+}
+
+// A carved allocation `d` made, or made again for a larger `fields`: measured, allocated, and only then the old block freed, behind a
+// wait for the handle's stream (nothing of it is in flight after that); carved, d set.  A refused allocation leaves d and its block
+// alone -- a caller that must stay as it was lets `fields` write locals and copies them behind a success.
+template <class F> int regrow(dftpav_handle *h, unsigned char *&d, F &&fields) {
+  unsigned char *fresh = nullptr;
+  HIPCHK(h, hipMalloc(&fresh, carve(nullptr, fields)));
+  if (d) {
+    (void)hipStreamSynchronize(h->stream);
+    (void)hipFree(d);
+  }
+  carve(fresh, fields);
+  d = fresh;
+  return DFTPAV_OK;
 }
 
 // The temporary device buffers of one call.  They are freed when the call ends, after a wait for the handle's stream: whatever the

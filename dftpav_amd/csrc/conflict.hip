@@ -122,19 +122,19 @@ __global__ void __launch_bounds__(256) conflict_pair_kernel(ConflictPairArgs A) 
     for (int j = 0; j < kConflictTile; j++) {
       const double dx = xi - sp[0][j], dy = yi - sp[1][j];
       const double d2 = dx * dx + dy * dy;
-      if (d2 <= A.reach2) cand |= 1ull << j;
+      if (d2 <= A.V.reach2) cand |= 1ull << j;
     }
     if (blockIdx.x == blockIdx.y) cand &= ~(1ull << lane); // the tile against itself: not i against i
     while (cand) {
       const int j = __ffsll((long long)cand) - 1;
       cand &= cand - 1ull;
-      const double sep = cf_sep(xi, yi, ci, si, sp[0][j], sp[1][j], sp[2][j], sp[3][j], A.half_l, A.half_w);
+      const double sep = cf_sep(xi, yi, ci, si, sp[0][j], sp[1][j], sp[2][j], sp[3][j], A.V.half_l, A.V.half_w);
       if (sep < bs) { // rising (k, j): the first of equals stays
         bs = sep;
         bk = k;
         bj = j0 + j;
       }
-      if (fk < 0 && sep <= A.margin) {
+      if (fk < 0 && sep <= A.V.margin) {
         fk = k;
         fj = j0 + j;
       }

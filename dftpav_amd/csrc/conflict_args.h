@@ -1,6 +1,8 @@
 // conflict_args.h — what the host half of the conflict calls (dftpav_planner_check_conflicts, dftpav_planner_sample_poses) hands the
 // kernels of conflict.hip.
 #pragma once
+#include <cstddef>
+
 #include "../../include/dftpav_hip.h"
 #include "piece_eval.h"
 #include "plan_args.h"
@@ -31,14 +33,22 @@ struct ConflictRows {
   int *sep_sample, *sep_partner, *conflict_sample, *conflict_partner;
 };
 
+// The vehicle and the two distances of every pair kernel of the family (conflict.hip, cand_conflict.hip, joint_select.hip,
+// conflict_trigger.hip); the host forms them in one place (pair_consts, capi_conflicts.cpp)
+struct PairConsts {
+  double half_l, half_w; // 0.5 * veh_length, 0.5 * veh_width
+  double margin;
+  double reach2; // R * R of the broad phase, R = range + 2 * the footprint's circumradius
+};
+
 // conflict_pair_kernel: workgroup (I-tile, J-tile) writes the partial row jt * S_pad + i of every slot i of its I-tile
 struct ConflictPairArgs {
   ConflictPoses P; // read only
   ConflictRows part;
-  double half_l, half_w; // 0.5 * veh_length, 0.5 * veh_width
-  double margin;
-  double reach2; // R * R of the broad phase
+  PairConsts V;
 };
+static_assert(offsetof(ConflictPairArgs, V) == sizeof(ConflictPoses) + sizeof(ConflictRows) && sizeof(ConflictPairArgs) == offsetof(ConflictPairArgs, V) + 32,
+              "the four doubles lie where they lay");
 
 // conflict_reduce_kernel: slot i's partial rows merged into its output row
 struct ConflictReduceArgs {

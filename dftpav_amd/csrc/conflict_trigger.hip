@@ -75,15 +75,15 @@ __global__ void __launch_bounds__(256) trigger_pair_kernel(TriggerPairArgs A) {
     for (int j = 0; j < kConflictTile; j++) {
       const double dx = xi - sp[0][j], dy = yi - sp[1][j];
       const double d2 = dx * dx + dy * dy;
-      if (d2 <= A.reach2) cand |= 1ull << j;
+      if (d2 <= A.V.reach2) cand |= 1ull << j;
     }
     cand &= prec;            // only a pair that could make i yield reaches the narrow phase
     if (fk >= 0) cand = 0ull; // the lane has its minimum
     while (cand) {
       const int j = __ffsll((long long)cand) - 1;
       cand &= cand - 1ull;
-      const double sep = cf_sep(xi, yi, ci, si, sp[0][j], sp[1][j], sp[2][j], sp[3][j], A.half_l, A.half_w);
-      if (sep <= A.margin) { // rising (k, j): the first hit is the wave's minimum
+      const double sep = cf_sep(xi, yi, ci, si, sp[0][j], sp[1][j], sp[2][j], sp[3][j], A.V.half_l, A.V.half_w);
+      if (sep <= A.V.margin) { // rising (k, j): the first hit is the wave's minimum
         fk = k;
         fj = j0 + j;
         cand = 0ull;

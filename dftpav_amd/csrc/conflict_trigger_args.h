@@ -24,10 +24,10 @@ struct TriggerPairArgs {
   ConflictPoses P; // read only
   TriggerYield Y;
   TriggerRows part;
-  double half_l, half_w; // 0.5 * veh_length, 0.5 * veh_width
-  double margin;
-  double reach2; // R * R of the broad phase
+  PairConsts V;
 };
+static_assert(offsetof(TriggerPairArgs, V) == offsetof(TriggerPairArgs, part) + sizeof(TriggerRows) && sizeof(TriggerPairArgs) == offsetof(TriggerPairArgs, V) + 32,
+              "the four doubles lie where they lay");
 
 // trigger_reduce_kernel: slot i's partial rows merged into its output row; yield = can_yield(i) && sample >= 0
 struct TriggerReduceArgs {

@@ -40,10 +40,10 @@ struct JointPairArgs {
   JointPoses P; // read only
   unsigned long long *bits; // [C_pad][tiles]
   int C, R, tiles;
-  double half_l, half_w;
-  double margin;
-  double reach2;
+  PairConsts V;
 };
+static_assert(offsetof(JointPairArgs, V) == offsetof(JointPairArgs, tiles) + 8 && sizeof(JointPairArgs) == offsetof(JointPairArgs, V) + 32,
+              "the four doubles lie where they lay");
 
 // joint_greedy_kernel: one workgroup walks the queries in order
 struct JointGreedyArgs {
@@ -63,9 +63,9 @@ struct JointRowsArgs {
   const int *wcand;
   ConflictRows rows; // [C]; the partner index is the query index
   int C, Q, R;
-  double half_l, half_w;
-  double margin;
-  double reach2;
+  PairConsts V;
 };
+static_assert(offsetof(JointRowsArgs, V) == offsetof(JointRowsArgs, R) + 8 && sizeof(JointRowsArgs) == offsetof(JointRowsArgs, V) + 32,
+              "the four doubles lie where they lay");
 
 } // namespace dftpav

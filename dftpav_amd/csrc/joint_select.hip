@@ -114,12 +114,12 @@ __global__ void __launch_bounds__(256) joint_pair_kernel(JointPairArgs A) {
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     if (__ballot(sp[0][lane] == sp[0][lane]) != 0) { // a tile of NaN poses is not walked
-      unsigned long long cand = joint_broad(xi, yi, sp, A.reach2) & lower & ~word; // a bit that is set stays set
+      unsigned long long cand = joint_broad(xi, yi, sp, A.V.reach2) & lower & ~word; // a bit that is set stays set
       while (cand) {
         const int j = __ffsll((long long)cand) - 1;
         cand &= cand - 1ull;
-        const double sep = cf_sep(xi, yi, ci, si, sp[0][j], sp[1][j], sp[2][j], sp[3][j], A.half_l, A.half_w);
-        if (sep <= A.margin) word |= 1ull << j;
+        const double sep = cf_sep(xi, yi, ci, si, sp[0][j], sp[1][j], sp[2][j], sp[3][j], A.V.half_l, A.V.half_w);
+        if (sep <= A.V.margin) word |= 1ull << j;
       }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // the next sample's stores stay behind these reads
@@ -215,17 +215,17 @@ __global__ void __launch_bounds__(256) joint_rows_kernel(JointRowsArgs A) {
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       if (__ballot(sp[0][lane] == sp[0][lane]) != 0) { // 64 queries without a winner are not walked
-        unsigned long long cand = joint_broad(xi, yi, sp, A.reach2) & joint_below(q - q0); // the partners: q' < q
+        unsigned long long cand = joint_broad(xi, yi, sp, A.V.reach2) & joint_below(q - q0); // the partners: q' < q
         while (cand) {
           const int j = __ffsll((long long)cand) - 1;
           cand &= cand - 1ull;
-          const double sep = cf_sep(xi, yi, ci, si, sp[0][j], sp[1][j], sp[2][j], sp[3][j], A.half_l, A.half_w);
+          const double sep = cf_sep(xi, yi, ci, si, sp[0][j], sp[1][j], sp[2][j], sp[3][j], A.V.half_l, A.V.half_w);
           if (sep < bs) { // rising (k, q'): the first of equals stays
             bs = sep;
             bk = k;
             bj = q0 + j;
           }
-          if (fk < 0 && sep <= A.margin) {
+          if (fk < 0 && sep <= A.V.margin) {
             fk = k;
             fj = q0 + j;
           }

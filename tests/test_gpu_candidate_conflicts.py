@@ -525,6 +525,21 @@ def test_composition_with_the_limit_filter(hiplib, arena):
     pl.close()
 
 
+def test_a_larger_K_after_a_smaller_one(hiplib, arena):
+    """the filter set for K = 4, a call, then set for K = F_K: the poses are allocated again for the larger K, and the rows of the next
+    call are the oracle's at F_K, bit for bit"""
+    pl = hiplib.Planner(arena["h"], arena["Q"], lc.R)
+    _park(arena, pl, BLOCK_SLOT, BLOCKER)
+    ref = _chain_rows(_table(pl), M_1)
+    assert (ref["conflict_sample"] >= 4).any() and (ref["sep_sample"] >= 4).any()     # clocks that the first allocation has no poses for
+    pl.set_conflict_filter(M_1, F_RANGE, F_DT, 4)
+    pl.plan(arena["S"], arena["E"], pp=_pp(hiplib))
+    small = pl.last_conflicts(arena["Q"])
+    assert (small["sep_sample"] < 4).all() and (small["conflict_sample"] < 4).all()
+    _filter_case(hiplib, arena, pl, M_1, _wins(ref), ref)       # (sets F_K)
+    pl.close()
+
+
 def test_own_slots_through_the_tick(hiplib, oracle):
     """one adopted plan with an obstacle dropped on it replans in a tick with the filter on: its own old plan does not reject it; a
     vehicle parked on the start of its new path does, and it keeps its plan; plan_out is a separate call's with set_own_slots"""

@@ -473,3 +473,32 @@ def test_tick_with_the_trigger(hiplib, oracle, filtered):
     assert pl.info()["n_batches"] == nb
     pl.close()
     h.close()
+
+
+def test_a_larger_K_after_a_smaller_one(hiplib, oracle):
+    """the trigger set for K = 4, a tick, then set for K = 40: the allocation is made again for the larger K, the rows of the last tick
+    went with the old one, and the next tick's rows are the read-out's (and the oracle's) on the table that tick finds"""
+    sc = _tick_scene(oracle.minco_generate)
+    pp = _pp(hiplib)
+    t_now, t0 = sc["t_now"], sc["t_now"] + sc["budget"]
+    h = hiplib.Handle()
+    h.set_grid_map(sc["grid"], sc["resolution"], sc["origin"])
+    pl = hiplib.Planner(h, N_TICK, R)
+    _install(pl, sc, pp.max_seg, pp.max_pieces)
+    rows = []
+    for K in (4, 40):
+        pl.set_conflict_trigger(**dict(TRIGGER, K=K))
+        if rows:
+            with pytest.raises(hiplib.DftpavError) as e:
+                pl.last_trigger()                               # until the next tick
+            assert e.value.code == hiplib.E_INVALID
+        clocks = (t_now, t0, TRIGGER["dt"], K, TRIGGER["margin"], TRIGGER["range"])
+        want = pl.check_yield(*clocks)                          # the read-out writes nothing: the table is the one the tick finds
+        _same(want, _oracle(*_table(pl), *clocks))
+        pl.tick(t_now, sc["budget"], pp=pp)
+        rows.append(pl.last_trigger())
+        _same(rows[-1], want)
+    assert _empty(rows[0])                                      # nothing within four clocks; the rows of K = 40 lie beyond them
+    assert rows[1]["yield"].any() and (rows[1]["yield_sample"][rows[1]["yield"] != 0] >= 4).all()
+    pl.close()
+    h.close()

@@ -241,6 +241,21 @@ def test_a_margin_between_two_separations(hiplib, side):
     pl.close()
 
 
+def test_a_larger_K_after_a_smaller_one(hiplib, side):
+    """joint selection on, the filter set for K = 4, a call, then set for K = F_K: the filter's and the joint stage's poses are
+    allocated again for the larger K, and winners, blocked and rows of the next call equal the oracle at F_K"""
+    ref, _, _ = _side_ref(side, S_MARGIN)
+    assert ref["conflict_sample"].max() >= 4                    # the one conflict lies at a clock the first allocation has no poses for
+    pl = hiplib.Planner(side["h"], side["Q"], jc.PLAN_R)
+    pl.set_conflict_filter(S_MARGIN, S_RANGE, F_DT, 4)
+    pl.set_joint_selection(True)
+    _same_outputs(pl.plan(side["S"], side["E"], pp=_pp(hiplib)), side["plain"])       # (within four clocks nobody is blocked)
+    assert not pl.last_joint(side["Q"])["blocked"].any()
+    pl.set_conflict_filter(S_MARGIN, S_RANGE, F_DT, F_K)
+    _side_check(hiplib, side, pl, ref)
+    pl.close()
+
+
 def test_composition_with_the_limit_filter(hiplib, side):
     """A restart the limit filter rejects cannot win and cannot block.  A forward speed limit of 5.0 m/s rejects query 0's cheapest
     restart (and two more); query 0 takes the one that is left, and query 1 is blocked by THAT restart's poses: its winner differs
